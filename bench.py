@@ -20,6 +20,16 @@ on rank 0.  For N>1 it is launched under torch.distributed.run, one rank per GPU
 * cells        : per-cell EM (BASELINE configs[4]): a slice of cells x 50 k reads, batched on the device,
               cells/sec end to end from host buffers.  N>1: cells dealt to the ranks, no collective.
 
+A plain run does what the headline figure needs and nothing more: it generates and uploads the store, settles
+the device, runs W warm-up and K timed iterations and prints the line (N>1: the exchange of the count vector is
+chosen first).  ``--full`` adds everything else below -- roofline pass timings and side stores, EM to
+convergence, bootstraps, cells, the configs[1] and shard legs, the CPU baselines, the live HBM traffic, the
+shard compute time of a rank -- in the order they always ran; the other keys of the line are null without it.
+``--dump-outputs DIR`` writes, after the timed iterations, what the timed EM loop hands its caller: the counts
+of an oem_em_run of K iterations with no early exit on the same resident store (DIR/counts.npy, float64) and
+its run info (DIR/run_info.npy: niter, n_passes, converged, rel_diff).  The store is a pure function of the
+workload, so two builds given the same arguments can be compared output for output.
+
 ``--force-dist`` runs the whole N>1 code path (process group, native RCCL communicator, attach,
 barrier / all-reduce timing, replica-parallel bootstraps, dealt cells) with a world of ONE rank, so
 that the path an 8-GPU node takes is exercised on a 1-GPU box.
@@ -49,6 +59,12 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "tiny"])
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure (roofline, side stores, EM to "
+                         "convergence, bootstraps, cells, side legs, CPU baselines, live traffic); the options below "
+                         "that select or skip those parts act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the counts and run info of the timed EM loop as DIR/*.npy")
     ap.add_argument("--bootstraps", type=int, default=100,
                     help="bootstrap replicates to time per GPU (0 = skip; default 100 = BASELINE configs[2])")
     ap.add_argument("--no-batch-bootstrap", action="store_true", help="one replicate per pass instead of the batched chains")
@@ -380,9 +396,10 @@ def main():
         # What this rank's shard costs by itself: the E/M pass of the un-attached shard store (tile kernel + fold; the
         # sweep over the count vector is part of the exchange kernels in a sharded run), HIP-event-timed -- beside the
         # exchange's own time and the sharded iteration below, so that a scaling curve says which of the two did not
-        # scale (config.exchange).
-        store.time_m_step(20)
-        shard_compute_us = store.time_m_step(100) * 1e3
+        # scale (config.exchange).  --full only.
+        if args.full:
+            store.time_m_step(20)
+            shard_compute_us = store.time_m_step(100) * 1e3
         # RCCL plus the one-shot peer-to-peer exchange for the 1.6 MB count vector (oem_p2p.hip); world 1 under
         # --force-dist: a real one-rank RCCL communicator and a one-rank exchange buffer
         comm = odist.create_comm(rank, world, local_rank, backend="p2p" if args.same_device else "both",
@@ -392,16 +409,17 @@ def main():
         exchange = pick_exchange(store, comm, dist, torch, have_rccl=not args.same_device, cpu_group=args.same_device)
         # the three numbers of one rank's iteration side by side, per candidate: the shard's compute alone, the
         # exchange alone (back-to-back all-reduces of the count vector), the sharded iteration as timed
-        sc = torch.tensor([shard_compute_us], dtype=torch.float64, device="cpu" if args.same_device else "cuda")
-        per_rank = [torch.zeros_like(sc) for _ in range(world)]
-        dist.all_gather(per_rank, sc)
-        exchange["shard_compute_us"] = max(float(t.item()) for t in per_rank)
-        exchange["shard_compute_us_per_rank"] = [round(float(t.item()), 2) for t in per_rank]
-        for rec in exchange["candidates"].values():
-            if rec.get("ok"):
-                rec["exchange_us"] = rec["allreduce_us"]
-                rec["shard_compute_us"] = exchange["shard_compute_us"]
-                rec["iteration_minus_compute_us"] = rec["iteration_us"] - exchange["shard_compute_us"]
+        if args.full:
+            sc = torch.tensor([shard_compute_us], dtype=torch.float64, device="cpu" if args.same_device else "cuda")
+            per_rank = [torch.zeros_like(sc) for _ in range(world)]
+            dist.all_gather(per_rank, sc)
+            exchange["shard_compute_us"] = max(float(t.item()) for t in per_rank)
+            exchange["shard_compute_us_per_rank"] = [round(float(t.item()), 2) for t in per_rank]
+            for rec in exchange["candidates"].values():
+                if rec.get("ok"):
+                    rec["exchange_us"] = rec["allreduce_us"]
+                    rec["shard_compute_us"] = exchange["shard_compute_us"]
+                    rec["iteration_minus_compute_us"] = rec["iteration_us"] - exchange["shard_compute_us"]
         exchange["ranks"] = comm.info(_lib.OEM_COMM_INFO_RANKS)
         exchange["rccl_ranks_seen"] = comm.info(_lib.OEM_COMM_INFO_RCCL_RANKS)   # ncclCommCount; 0: no RCCL in this run
         exchange["p2p_connected_this_rank"] = bool(comm.info(_lib.OEM_COMM_INFO_P2P_CONNECTED))
@@ -427,10 +445,10 @@ def main():
     # pass timing in front, the loop and `kernel_avg_ms` are measured in the same, settled state; a second pass timing
     # behind the loop is on the line as `kernel_avg_ms_after_loop`.  The slow patch sits 3-10 ms after the wake-up
     # (whatever runs then: with the pass timing first it read 0.152 ms, the one behind the loop 0.142), so 200 untimed
-    # passes (29 ms) go first: `config.settle_passes`.
+    # passes (29 ms) go first: `config.settle_passes`.  A plain run settles the same way; the pass timings are --full.
     hbm_bytes, alg_bytes = store.bytes()
     store.time_m_step(SETTLE_PASSES)
-    k_ms = store.time_m_step(50)
+    k_ms = store.time_m_step(50) if args.full else None
     # warmup, then exactly K timed iterations
     if args.warmup > 0:
         store.time_em_iters(args.warmup)
@@ -440,111 +458,115 @@ def main():
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     it_per_s = args.steps / elapsed
-    k_ms_after = store.time_m_step(50)
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-    traffic, traffic_src, traffic_stale = hbm_traffic(args.workload) if world == 1 else (None, None, None)
-    roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=achieved / HBM_PEAK_GBS, traffic=traffic,
-                    kernel="k_em_tile + k_remote_fold (one E/M pass)", kernel_avg_ms=k_ms,
-                    algorithmic_bytes_per_launch=alg_bytes, traffic_source=traffic_src, traffic_stale=traffic_stale,
-                    frac_of_achievable=achieved / HBM_ACHIEVABLE_GBS, achievable_peak=HBM_ACHIEVABLE_GBS,
-                    kernel_avg_ms_after_loop=k_ms_after)
-    if traffic:
-        # the bytes the kernels actually moved (PMC passes of the same command) over the same duration: the rate of
-        # the memory system, next to the rate of the algorithmic bytes that `frac` is
-        roofline["traffic_gbs"] = traffic / (k_ms * 1e-3) / 1e9
-        roofline["frac_traffic"] = roofline["traffic_gbs"] / HBM_PEAK_GBS
-    # The store's local weights are dictionary-coded when it has at most 256 distinct ones (as_prob is exp of an
-    # integer score gap over a constant; the C3 store has 98): say so, and time the same pass on the plain f32
-    # stream beside it (oem_store_opts.weight_coding = 1) so that both figures are on the line.
-    def coding_of(n):
-        return ("f32" if not n else "fused7" if n <= 128 else "bytes8" if n <= 256 else "words16")
+    roofline = None
+    if args.full:
+        k_ms_after = store.time_m_step(50)
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+        traffic, traffic_src, traffic_stale = hbm_traffic(args.workload) if world == 1 else (None, None, None)
+        roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=achieved / HBM_PEAK_GBS, traffic=traffic,
+                        kernel="k_em_tile + k_remote_fold (one E/M pass)", kernel_avg_ms=k_ms,
+                        algorithmic_bytes_per_launch=alg_bytes, traffic_source=traffic_src, traffic_stale=traffic_stale,
+                        frac_of_achievable=achieved / HBM_ACHIEVABLE_GBS, achievable_peak=HBM_ACHIEVABLE_GBS,
+                        kernel_avg_ms_after_loop=k_ms_after)
+        if traffic:
+            # the bytes the kernels actually moved (PMC passes of the same command) over the same duration: the rate of
+            # the memory system, next to the rate of the algorithmic bytes that `frac` is
+            roofline["traffic_gbs"] = traffic / (k_ms * 1e-3) / 1e9
+            roofline["frac_traffic"] = roofline["traffic_gbs"] / HBM_PEAK_GBS
+        # The store's local weights are dictionary-coded when it has at most 256 distinct ones (as_prob is exp of an
+        # integer score gap over a constant; the C3 store has 98): say so, and time the same pass on the plain f32
+        # stream beside it (oem_store_opts.weight_coding = 1) so that both figures are on the line.
+        def coding_of(n):
+            return ("f32" if not n else "fused7" if n <= 128 else "bytes8" if n <= 256 else "words16")
 
-    n_dict = store.info(_lib.OEM_INFO_WEIGHT_DICT_ENTRIES)
-    roofline["weight_coding"] = coding_of(n_dict)   # oem_layout_dict.hip: lossless table of the store's distinct f32 weights
-    roofline["weight_dict_entries"] = n_dict
-    # The same pass on three more stores of the same shape, as numeric keys (the coded figure depends on the store having
-    # few distinct weights): the plain f32 stream (weight_coding = 1), the coverage column (f64 weights, 12 B / alignment,
-    # the authors' recommended --model-coverage) and long-read score gaps (uniform on [0, 0.05 best], best up to 20 000:
-    # ~520 distinct weights -> 16-bit indices).  `frac` of each against its own algorithmic bytes.
-    if rank == 0 and world == 1 and not args.no_f32_compare:
-        def timed(label, rp, ti, pp, cov, batched=False, **kw):
-            try:
-                bp = None
-                with DeviceStore(rp, ti, pp, cov, cfg["n_txps"], device=local_rank, **kw) as o:
-                    o.time_em_iters(5)
-                    pk = min(o.time_m_step(50) for _ in range(3))   # (three runs of 50 launches: the side stores are timed once, cold)
-                    pit = o.time_em_iters(args.steps) / args.steps
-                    _h, ab = o.bytes()
-                    nd = o.info(_lib.OEM_INFO_WEIGHT_DICT_ENTRIES)
-                    nrem = o.info(_lib.OEM_INFO_REMOTE_ALIGNMENTS)
-                    if batched:   # one batched bootstrap pass (4 replicates) over the same store
-                        o.time_bootstrap_passes(5)
-                        bp = o.time_bootstrap_passes(20)
-                roofline["frac_" + label] = ab / (pk * 1e-3) / 1e9 / HBM_PEAK_GBS
-                roofline[label] = dict(kernel_avg_ms=pk, device_ms_per_step=pit, algorithmic_bytes_per_launch=ab,
-                                       weight_coding=coding_of(nd), weight_dict_entries=nd, remote_alignments=nrem)
-                if bp:
-                    roofline[label].update(batched_pass_ms=bp[0], replicates_per_batched_pass=bp[1],
-                                           us_per_replicate_pass=bp[0] / bp[1] * 1e3)
-            except Exception as e:  # pragma: no cover
-                roofline[label] = dict(error=repr(e))
-        if n_dict:
-            timed("f32_stream", row_ptr, tid, p, None, weight_coding=1)
-        else:
-            roofline["frac_f32_stream"] = roofline["frac"]
-        if args.workload != "tiny":
-            threads = max(2, min(32, os.cpu_count() or 8))
-            cv = synth.make_store(cfg["n_reads"], cfg["n_txps"], cfg["kbar"], coverage=True, threads=threads)
-            timed("coverage", cv.row_ptr, cv.tid, cv.as_prob, cv.cov_prob)
-            # the same store with the opt-in oem_store_opts.weight_coding = 2: the static weight p * cov rounded once to
-            # f32 (<= 6e-8 relative per weight; SURVEY 8a note 2), 8 B per alignment through the f32 kernels
-            timed("coverage_f32w", cv.row_ptr, cv.tid, cv.as_prob, cv.cov_prob, weight_coding=2)
-            del cv
-            ug = synth.make_store(cfg["n_reads"], cfg["n_txps"], cfg["kbar"], threads=threads, gaps="uniform")
-            timed("uniform_gaps", ug.row_ptr, ug.tid, ug.as_prob, None)
-            del ug
-            # What the engine does when a read's far alignments RECUR (multi-mapping reads hit paralogs, not random
-            # transcripts): the BASELINE generator's 20 % uniformly random far hits are the worst case of the remote
-            # path (a quarter of the pass).  `paralog`: far hits inside families of three genes scattered over the
-            # annotation; `paralog_adjacent`: the same families numbered next to each other -- the annotation a
-            # co-mapping renumbering at store creation would produce (not built: this prices it).
-            for far in ("paralog", "paralog_adjacent"):
-                pf = synth.make_store(cfg["n_reads"], cfg["n_txps"], cfg["kbar"], threads=threads, far=far)
-                timed(far, pf.row_ptr, pf.tid, pf.as_prob, None, batched=True)
-                del pf
+        n_dict = store.info(_lib.OEM_INFO_WEIGHT_DICT_ENTRIES)
+        roofline["weight_coding"] = coding_of(n_dict)   # oem_layout_dict.hip: lossless table of the store's distinct f32 weights
+        roofline["weight_dict_entries"] = n_dict
+        # The same pass on three more stores of the same shape, as numeric keys (the coded figure depends on the store having
+        # few distinct weights): the plain f32 stream (weight_coding = 1), the coverage column (f64 weights, 12 B / alignment,
+        # the authors' recommended --model-coverage) and long-read score gaps (uniform on [0, 0.05 best], best up to 20 000:
+        # ~520 distinct weights -> 16-bit indices).  `frac` of each against its own algorithmic bytes.
+        if rank == 0 and world == 1 and not args.no_f32_compare:
+            def timed(label, rp, ti, pp, cov, batched=False, **kw):
+                try:
+                    bp = None
+                    with DeviceStore(rp, ti, pp, cov, cfg["n_txps"], device=local_rank, **kw) as o:
+                        o.time_em_iters(5)
+                        pk = min(o.time_m_step(50) for _ in range(3))   # (three runs of 50 launches: the side stores are timed once, cold)
+                        pit = o.time_em_iters(args.steps) / args.steps
+                        _h, ab = o.bytes()
+                        nd = o.info(_lib.OEM_INFO_WEIGHT_DICT_ENTRIES)
+                        nrem = o.info(_lib.OEM_INFO_REMOTE_ALIGNMENTS)
+                        if batched:   # one batched bootstrap pass (4 replicates) over the same store
+                            o.time_bootstrap_passes(5)
+                            bp = o.time_bootstrap_passes(20)
+                    roofline["frac_" + label] = ab / (pk * 1e-3) / 1e9 / HBM_PEAK_GBS
+                    roofline[label] = dict(kernel_avg_ms=pk, device_ms_per_step=pit, algorithmic_bytes_per_launch=ab,
+                                           weight_coding=coding_of(nd), weight_dict_entries=nd, remote_alignments=nrem)
+                    if bp:
+                        roofline[label].update(batched_pass_ms=bp[0], replicates_per_batched_pass=bp[1],
+                                               us_per_replicate_pass=bp[0] / bp[1] * 1e3)
+                except Exception as e:  # pragma: no cover
+                    roofline[label] = dict(error=repr(e))
+            if n_dict:
+                timed("f32_stream", row_ptr, tid, p, None, weight_coding=1)
+            else:
+                roofline["frac_f32_stream"] = roofline["frac"]
+            if args.workload != "tiny":
+                threads = max(2, min(32, os.cpu_count() or 8))
+                cv = synth.make_store(cfg["n_reads"], cfg["n_txps"], cfg["kbar"], coverage=True, threads=threads)
+                timed("coverage", cv.row_ptr, cv.tid, cv.as_prob, cv.cov_prob)
+                # the same store with the opt-in oem_store_opts.weight_coding = 2: the static weight p * cov rounded once to
+                # f32 (<= 6e-8 relative per weight; SURVEY 8a note 2), 8 B per alignment through the f32 kernels
+                timed("coverage_f32w", cv.row_ptr, cv.tid, cv.as_prob, cv.cov_prob, weight_coding=2)
+                del cv
+                ug = synth.make_store(cfg["n_reads"], cfg["n_txps"], cfg["kbar"], threads=threads, gaps="uniform")
+                timed("uniform_gaps", ug.row_ptr, ug.tid, ug.as_prob, None)
+                del ug
+                # What the engine does when a read's far alignments RECUR (multi-mapping reads hit paralogs, not random
+                # transcripts): the BASELINE generator's 20 % uniformly random far hits are the worst case of the remote
+                # path (a quarter of the pass).  `paralog`: far hits inside families of three genes scattered over the
+                # annotation; `paralog_adjacent`: the same families numbered next to each other -- the annotation a
+                # co-mapping renumbering at store creation would produce (not built: this prices it).
+                for far in ("paralog", "paralog_adjacent"):
+                    pf = synth.make_store(cfg["n_reads"], cfg["n_txps"], cfg["kbar"], threads=threads, far=far)
+                    timed(far, pf.row_ptr, pf.tid, pf.as_prob, None, batched=True)
+                    del pf
 
     # EM to convergence with the reference's defaults (max_iter 1000, thresh 1e-3), both gates
     sync()
-    conv = {}
-    for gate, name in ((1, "em_par"), (50, "em")):
-        tc = time.perf_counter()
-        _cnt, info = store.em_run(None, 1000, 1e-3, gate)
-        sync()
-        conv[name] = dict(niter=info.niter, n_passes=info.n_passes, converged=info.converged,
-                          seconds=time.perf_counter() - tc)
+    conv = None
+    if args.full:
+        conv = {}
+        for gate, name in ((1, "em_par"), (50, "em")):
+            tc = time.perf_counter()
+            _cnt, info = store.em_run(None, 1000, 1e-3, gate)
+            sync()
+            conv[name] = dict(niter=info.niter, n_passes=info.n_passes, converged=info.converged,
+                              seconds=time.perf_counter() - tc)
 
     # bootstraps/sec (each = one resampled EM to convergence, em.rs:273-290)
     boots = None
-    if args.bootstraps > 0:
+    if args.full and args.bootstraps > 0:
         boots = bootstrap_leg(args, cfg, full, store, dist_mode, rank, world, local_rank, sync, max_over_ranks)
 
     # per-cell EM (single_cell.rs:139-160), batched on the device
     cells = None
     n_cells = args.cells if args.cells is not None else (625 if args.workload == "c3" else 16)
-    if n_cells > 0:
+    if args.full and n_cells > 0:
         cells = cells_leg(args, n_cells, rank, world, local_rank, sync, max_over_ranks)
 
     # BASELINE configs[1] (1 M reads x 60 k transcripts, 1000 EM iterations) and the shard one of eight ranks would own
     # (configs[3]): both are ONE wave of workgroups deep -- the regime where a tile's chain, not the memory system, sets
     # the pass -- and were builder-only figures until round 6
     c2 = shard_n8 = None
-    if rank == 0 and world == 1 and args.workload == "c3" and not args.no_side_legs:
+    if args.full and rank == 0 and world == 1 and args.workload == "c3" and not args.no_side_legs:
         c2 = c2_leg(local_rank, sync)
         shard_n8 = shard_leg(full, cfg, 8, local_rank)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the CPU legs run on every CPU the cgroup grants, not on the GPU's NUMA node alone (the binding above would
         # hand the reference's side fewer cores on a multi-socket box and flatter the ratio)
         if AFFINITY_AT_START:
@@ -557,7 +579,7 @@ def main():
             boots["cpu_baseline"] = cpu_boot_baseline(row_ptr, tid, p, cfg["n_txps"], args.cpu_seconds,
                                                       boots.get("mean_passes"))
 
-    if rank == 0 and world == 1 and not args.no_live_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_live_traffic:
         # the pass's HBM traffic measured on THIS box in THIS run (the tracked JSON pairs the builder's box with this
         # box's time); last, so that the child processes run beside nothing that is timed
         lt, lsrc = live_hbm_traffic(args.workload, full, cfg)
@@ -569,6 +591,9 @@ def main():
             roofline["frac_traffic"] = roofline["traffic_gbs"] / HBM_PEAK_GBS
         else:
             roofline["traffic_live_error"] = lsrc
+
+    if args.dump_outputs:   # every rank: the sharded loop's run is collective
+        dump_outputs(args.dump_outputs, store, args.steps, rank == 0)
     if rank == 0:
         out = {
             "metric": "EM iterations/sec",
@@ -590,7 +615,9 @@ def main():
                        "gen_s": round(t_gen, 2), "upload_s": round(t_up, 3), "runtime_init_s": round(t_first, 3),
                        "host_binding": host_binding,
                        "device_ms_per_step": dev_ms / args.steps, "settle_passes": SETTLE_PASSES,
-                       "order": "settle passes, pass timing (1 + 50 launches), W warm-up iterations, K timed iterations, pass timing again",
+                       "order": ("settle passes, pass timing (1 + 50 launches), W warm-up iterations, K timed iterations, pass timing again"
+                                 if args.full else "settle passes, W warm-up iterations, K timed iterations"),
+                       "full": args.full,
                        "exchange": exchange},
             "roofline": roofline,
             "cpu_baseline": cpu,
@@ -606,6 +633,19 @@ def main():
         comm.close()
     if dist_mode:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, store, steps, write):
+    """What the timed loop hands its caller: oem_em_run over the same resident store with the timed loop's parameters
+    (`steps` iterations from the uniform init, no early exit: threshold -1 and a gate of u32::MAX, as oem_time_em_iters
+    runs them) -- the counts and the run info, as float64 .npy files (1.6 MB at C3)."""
+    counts, info = store.em_run(None, steps, -1.0, 0xFFFFFFFF)
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), np.asarray(counts, dtype=np.float64))
+    np.save(os.path.join(out_dir, "run_info.npy"),
+            np.asarray([info.niter, info.n_passes, float(info.converged), info.rel_diff], dtype=np.float64))
 
 
 def c2_leg(local_rank, sync):

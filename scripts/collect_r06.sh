@@ -45,7 +45,7 @@ cp $out/paralog/kernel_stats.csv $out/r06_c3_paralog_kernel_stats.csv
 KT_TOP=4 bash scripts/kt.sh $out/c2 python scripts/pass_time.py c2 > $out/c2.log 2>&1
 cp $out/c2/kernel_stats.csv $out/r06_c2_kernel_stats.csv
 bash scripts/loop_trace.sh $out/lt_c2 c2 200 20 > $out/r06_c2_loop_trace.txt 2>&1
-python bench.py --workload c2 --steps 1000 --warmup 50 --bootstraps 0 --cells 0 --no-live-traffic --no-cpu-baseline 2> /dev/null | tail -1 > $out/r06_bench_c2.json
+python bench.py --full --workload c2 --steps 1000 --warmup 50 --bootstraps 0 --cells 0 --no-live-traffic --no-cpu-baseline 2> /dev/null | tail -1 > $out/r06_bench_c2.json
 # in-kernel phase stamps (test-only library): where a tile's life goes, per phase (the stall-site account: no ATT decoder
 # and no PC sampling on this image)
 python scripts/tile_probe.py c3 2>/dev/null | grep -v amdgpu > $out/r06_tile_probe.txt

@@ -14,10 +14,10 @@ same=""; [ "${SAME_DEVICE:-0}" = "1" ] && same="--same-device"
 for n in 1 2 4 8; do
   if [ -z "$same" ] && [ "$n" -gt "$ngpu" ]; then break; fi
   if [ "$n" = 1 ]; then
-    python bench.py --gpus 1 --steps 200 --warmup 20 "$@" > "$out/scale_$n.json" 2> "$out/scale_$n.err"
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full "$@" > "$out/scale_$n.json" 2> "$out/scale_$n.err"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus $n --steps 200 --warmup 20 $same "$@" > "$out/scale_$n.json" 2> "$out/scale_$n.err"
+      bench.py --gpus $n --steps 200 --warmup 20 --full $same "$@" > "$out/scale_$n.json" 2> "$out/scale_$n.err"
   fi
   echo "N=$n rc=$?"
 done

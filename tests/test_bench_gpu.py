@@ -6,7 +6,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from oracle import c_oracle
+from tests.common import assert_counts_close
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,6 +21,14 @@ def _free_port():
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         return so.getsockname()[1]
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
 
 
 def _last_json(text):
@@ -42,7 +54,7 @@ def _check_contract(d, steps, warmup):
 
 @pytest.mark.timeout(900)
 def test_bench_contract_line_single_process():
-    cmd = [sys.executable, "bench.py", "--workload", "tiny", "--steps", "6", "--warmup", "2", "--bootstraps", "3",
+    cmd = [sys.executable, "bench.py", "--full", "--workload", "tiny", "--steps", "6", "--warmup", "2", "--bootstraps", "3",
            "--cells", "4", "--cpu-seconds", "1"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -52,10 +64,38 @@ def test_bench_contract_line_single_process():
     assert "forced" not in d["config"]["parallelism"]
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_the_steps_and_dumps_what_the_loop_computed(tmp_path):
+    """A plain run (no --full) prints the headline line and nothing else measured; --dump-outputs writes the counts
+    of the timed loop's K iterations, which the oracle's do_em of K iterations with no early exit reproduces."""
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--workload", "tiny", "--steps", "6", "--warmup", "2",
+           "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=500)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _last_json(p.stdout)
+    assert d["metric"] == "EM iterations/sec" and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 6 and d["warmup"] == 2 and d["value"] > 0
+    assert abs(d["ms_per_step"] - 1e3 / d["value"]) < 1e-9 * d["ms_per_step"] + 1e-12
+    assert d["config"]["full"] is False
+    for key in ("roofline", "cpu_baseline", "bootstraps", "cells", "em_to_convergence", "c2", "shard_n8"):
+        assert d[key] is None, key
+    counts = np.load(out / "counts.npy")
+    info = np.load(out / "run_info.npy")
+    assert counts.dtype == np.float64 and counts.shape == (d["config"]["n_txps"],)
+    assert sorted(os.listdir(out)) == ["counts.npy", "run_info.npy"]
+    bench = _bench_module()
+    st = bench.make_full(bench.WORKLOADS["tiny"])
+    want, wi = c_oracle.do_em(c_oracle.Store(st.row_ptr, st.tid, st.as_prob, None, st.n_txps), max_iter=6,
+                              conv_thresh=-1.0, min_iter_gate=0xFFFFFFFF)
+    assert int(info[0]) == wi.niter == 6 and info[2] == 0.0
+    assert_counts_close(counts, want, st.n_reads, st.n_txps, what="bench --dump-outputs counts")
+
+
 @pytest.mark.timeout(900)
 def test_bench_forced_dist_path_under_torchrun():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--workload", "tiny",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--full", "--workload", "tiny",
            "--steps", "6", "--warmup", "2", "--bootstraps", "3", "--cells", "4", "--no-cpu-baseline", "--force-dist"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=800, env=env)
@@ -73,7 +113,7 @@ def test_bench_two_ranks_on_one_device_over_p2p():
     hipIpc-mapped buffers inside the rel-diff kernel, replica-parallel bootstraps, dealt cells, max-over-ranks
     timing) -- every collective step of what an 8-GPU node executes, short of RCCL and xGMI."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--workload", "tiny",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--full", "--workload", "tiny",
            "--steps", "6", "--warmup", "2", "--bootstraps", "3", "--cells", "4", "--no-cpu-baseline", "--same-device"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=800, env=env)

@@ -51,5 +51,8 @@ def test_command_line_contract():
     bench = _bench()
     a = bench.parse([])
     assert a.gpus == 1 and a.steps > 0 and a.warmup >= 0 and a.bootstraps >= 16 and not a.force_dist
+    assert not a.full and a.dump_outputs is None
     a = bench.parse(["--gpus", "8", "--steps", "20", "--warmup", "3", "--force-dist"])
     assert (a.gpus, a.steps, a.warmup, a.force_dist) == (8, 20, 3, True)
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "1", "--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
