@@ -36,7 +36,8 @@ extern "C" {
 
 /* 2: oem_time_bootstrap_passes, oem_store_opts.layout_build and .weight_coding (were reserved words: zero = the
  *    default, as before), the peer-to-peer communicator entry points (oem_comm_p2p_*), oem_store_info; version 1
- *    callers keep working (additions only). */
+ *    callers keep working (additions only).  Later additions under the same number: the sparse per-cell results
+ *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -56,6 +57,7 @@ typedef enum {
 /* Opaque handles. */
 typedef struct oem_store oem_store; /* InMemoryAlignmentStore resident on one GPU (one row shard) */
 typedef struct oem_comm oem_comm;   /* RCCL communicator over the row shards of one node */
+typedef struct oem_cells_result oem_cells_result; /* sparse per-cell results, host-resident, immutable once returned */
 
 /* What do_em / em_par leave behind besides the counts. */
 typedef struct {
@@ -308,6 +310,25 @@ int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, const uint6
                      const uint32_t *tid, const float *as_prob, const double *cov_prob,
                      uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
                      uint32_t max_iter, double conv_thresh, double *out, oem_run_info *infos);
+
+/* Same inputs, validation and per-cell contract as oem_em_run_cells; the
+ * result is the cells x transcripts matrix as CSR, in the exact form
+ * single_cell.rs:151-160 writes: for cell c, entries [cell_off[c],
+ * cell_off[c+1]) are the transcripts with count > 0.0 (f64 test), ascending
+ * id, value (float)count rounded to nearest even.  Cells keep their input
+ * order; a cell without reads has no entries.  The entries are picked out on
+ * the device: host memory and read-back are proportional to the non-zeros,
+ * not to n_cells x n_txps.  *out = NULL on any failure; release the result
+ * with oem_cells_result_destroy. */
+int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                            const uint32_t *tid, const float *as_prob, const double *cov_prob,
+                            uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
+                            uint32_t max_iter, double conv_thresh, oem_cells_result **out);
+int oem_cells_result_dims(const oem_cells_result *r, uint32_t *n_cells, uint64_t *n_entries);
+/* cell_off: n_cells + 1; col, val: n_entries; infos: n_cells.  Any output may be NULL. */
+int oem_cells_result_copy(const oem_cells_result *r, uint64_t *cell_off, uint32_t *col, float *val,
+                          oem_run_info *infos);
+void oem_cells_result_destroy(oem_cells_result *r); /* NULL: no-op */
 
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */

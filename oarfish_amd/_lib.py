@@ -44,7 +44,8 @@ ABI_SYMBOLS = [
     "oem_builder_store_create",
     "oem_m_step", "oem_em_run", "oem_aux_counts", "oem_assignment_probs",
     "oem_bootstrap_weights", "oem_bootstrap",
-    "oem_em_run_cells",
+    "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
+    "oem_cells_result_destroy",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
     "oem_comm_set_option", "oem_comm_info", "oem_store_attach_comm",
     "oem_time_m_step", "oem_time_em_iters", "oem_time_bootstrap_passes", "oem_time_allreduce",
@@ -142,6 +143,11 @@ def _load(path: str) -> C.CDLL:
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]
     L.oem_bootstrap.argtypes = [vp, u32, u64, vp, vp, u32, f64, vp, vp]
     L.oem_em_run_cells.argtypes = [vp, u32, vp, vp, vp, vp, u64, u64, u32, i32, u32, f64, vp, vp]
+    L.oem_em_run_cells_sparse.argtypes = [vp, u32, vp, vp, vp, vp, u64, u64, u32, i32, u32, f64, C.POINTER(vp)]
+    L.oem_cells_result_dims.argtypes = [vp, C.POINTER(u32), C.POINTER(u64)]
+    L.oem_cells_result_copy.argtypes = [vp, vp, vp, vp, vp]
+    L.oem_cells_result_destroy.argtypes = [vp]
+    L.oem_cells_result_destroy.restype = None
     L.oem_comm_unique_id.argtypes = [vp]
     L.oem_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.oem_comm_destroy.argtypes = [vp]

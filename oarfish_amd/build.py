@@ -28,7 +28,7 @@ LIB_PATH = os.path.join(HERE, "liboarfish_em.so")
 TESTING_LIB_PATH = os.path.join(HERE, "liboarfish_em_testing.so")
 
 # sources of the product library
-SOURCES = ["oem_api.hip", "oem_em_driver.hip", "oem_bootstrap.hip", "oem_cells.hip", "oem_timing.hip", "oem_kernels.hip", "oem_tile_kernels.hip", "oem_batch_kernels.hip",
+SOURCES = ["oem_api.hip", "oem_em_driver.hip", "oem_bootstrap.hip", "oem_cells.hip", "oem_cells_sparse.hip", "oem_timing.hip", "oem_kernels.hip", "oem_tile_kernels.hip", "oem_batch_kernels.hip",
            "oem_multi_kernels.hip", "oem_layout.cpp", "oem_layout_device.hip", "oem_layout_pack.hip", "oem_layout_dict.hip", "oem_coverage_device.hip",
            "oem_builder.cpp", "oem_comm.cpp", "oem_p2p.hip", "oem_knobs.cpp"]
 # the testing library swaps these for their -DOEM_TESTING build and adds the hooks

@@ -4,16 +4,44 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "oem_driver.h"
 
 namespace oem {
+
+// std::vector storage whose resize leaves new elements default-initialised: a block's entries are written by the
+// device read-back, there is no point in zeroing them first
+template <typename T>
+struct NoInitAlloc : std::allocator<T> {
+    template <typename U>
+    struct rebind {
+        using other = NoInitAlloc<U>;
+    };
+    NoInitAlloc() = default;
+    template <typename U>
+    NoInitAlloc(const NoInitAlloc<U> &) noexcept {}
+    template <typename U>
+    void construct(U *p) noexcept(std::is_nothrow_default_constructible<U>::value) { ::new ((void *)p) U; }
+    template <typename U, typename... A>
+    void construct(U *p, A &&...a) { ::new ((void *)p) U(std::forward<A>(a)...); }
+};
+
+// The sparse results of one group of cells (oem_em_run_cells_sparse): entries per cell, then every cell's columns and
+// values one after the other, in cell order.
+struct SparseBlock {
+    std::vector<uint32_t> counts;
+    std::vector<uint32_t, NoInitAlloc<uint32_t>> col;
+    std::vector<float, NoInitAlloc<float>> val;
+};
+
 namespace {
 
 #ifndef OEM_CELLS_HEAD_DIV
@@ -53,12 +81,96 @@ struct CellsTiming {
 };
 thread_local CellsTiming *t_timing = nullptr;
 
+// Where the groups of one call put their results: the caller's dense n_cells x n_txps matrix (oem_em_run_cells), or
+// one SparseBlock per group index (oem_em_run_cells_sparse: groups finish in any order).
+struct CellsSink {
+    double *dense = nullptr;
+    std::vector<SparseBlock> *blocks = nullptr;
+};
+
+// Device buffers of the count / scan / emit steps, kept across the cells of a cell-by-cell group.
+struct NzScratch {
+    uint32_t *counts = nullptr;
+    uint64_t *off = nullptr;
+    uint32_t *col = nullptr;
+    float *val = nullptr;
+    size_t cap_cells = 0, cap_entries = 0;
+    NzScratch() = default;
+    NzScratch(const NzScratch &) = delete;
+    NzScratch &operator=(const NzScratch &) = delete;
+    ~NzScratch()
+    {
+        hipFree(counts);
+        hipFree(off);
+        hipFree(col);
+        hipFree(val);
+    }
+};
+
+// single_cell.rs:151-160 on the device: the entries > 0.0 of cells [0, n_cells) of `src`, in ascending transcript id,
+// appended to `blk` (k_cells_nz_count, a host scan of the counts, k_cells_nz_emit, then only the entries cross PCIe).
+// cell_row_off / row_ptr: the cells' reads and alignments -- a cell cannot have more entries than alignments.
+int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, const uint64_t *cell_row_off,
+                 const uint64_t *row_ptr, NzScratch &sc, SparseBlock *blk)
+{
+    if (n_cells == 0) return OEM_OK;
+    if (n_cells > sc.cap_cells) {
+        hipFree(sc.counts);
+        hipFree(sc.off);
+        sc.counts = nullptr;
+        sc.off = nullptr;
+        sc.cap_cells = 0;
+        OEM_TRY(dev_alloc(&sc.counts, n_cells, nullptr));
+        OEM_TRY(dev_alloc(&sc.off, (size_t)n_cells + 1, nullptr));
+        sc.cap_cells = n_cells;
+    }
+    const size_t first = blk->counts.size();
+    blk->counts.resize(first + n_cells);
+    uint32_t *h_counts = blk->counts.data() + first;
+    OEM_TRY(launch_cells_nz_count(st, src, n_cells, sc.counts));
+    OEM_HIP(hipMemcpyAsync(h_counts, sc.counts, sizeof(uint32_t) * n_cells, hipMemcpyDeviceToHost, st));
+    OEM_HIP(hipStreamSynchronize(st));
+    std::vector<uint64_t> off((size_t)n_cells + 1);
+    off[0] = 0;
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        const uint64_t aligned = row_ptr[cell_row_off[c + 1]] - row_ptr[cell_row_off[c]];
+        if (h_counts[c] > src.T || h_counts[c] > aligned)
+            return fail(OEM_ERR_STATE, "oem_em_run_cells_sparse: cell %u has %u entries, more than its %llu alignments or %u transcripts",
+                        c, h_counts[c], (unsigned long long)aligned, src.T);
+        off[c + 1] = off[c] + h_counts[c];
+    }
+    const uint64_t total = off[n_cells];
+    const size_t e0 = blk->col.size();
+    blk->col.resize(e0 + total);
+    blk->val.resize(e0 + total);
+    if (total == 0) return OEM_OK;
+    if (total > sc.cap_entries) {
+        hipFree(sc.col);
+        hipFree(sc.val);
+        sc.col = nullptr;
+        sc.val = nullptr;
+        sc.cap_entries = 0;
+        OEM_TRY(dev_alloc(&sc.col, total, nullptr));
+        OEM_TRY(dev_alloc(&sc.val, total, nullptr));
+        sc.cap_entries = total;
+    }
+    OEM_HIP(hipMemcpyAsync(sc.off, off.data(), sizeof(uint64_t) * (n_cells + 1), hipMemcpyHostToDevice, st));
+    int rc = launch_cells_nz_emit(st, src, n_cells, sc.off, sc.col, sc.val);
+    if (rc == OEM_OK &&
+        (hipMemcpyAsync(blk->col.data() + e0, sc.col, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+         hipMemcpyAsync(blk->val.data() + e0, sc.val, sizeof(float) * total, hipMemcpyDeviceToHost, st) != hipSuccess))
+        rc = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: read-back of the entries failed");
+    // (also on failure: `off` must outlive the upload queued above)
+    if (hipStreamSynchronize(st) != hipSuccess && rc == OEM_OK) rc = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: emit failed");
+    return rc;
+}
+
 // All cells in one store over the concatenated transcript space; every pass serves every
 // unfinished cell.  Returns *used = false (nothing done) when the batch form does not apply.
 int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
                       const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads,
                       uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
-                      double *out, oem_run_info *infos, bool *used)
+                      double *out, SparseBlock *blk, oem_run_info *infos, bool *used)
 {
     *used = false;
     StageTimer tm;
@@ -89,6 +201,7 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
     // (oem_api.hip: k_cells_mark); the caller's n_txps where the batch was not compacted
     const uint64_t full_total = total_txps;
     const bool compacted = s->multi.rank != nullptr;
+    const uint32_t caller_txps = n_txps;
     if (compacted) n_txps = s->multi.txps_eff;
     const uint64_t store_total = (uint64_t)n_cells * n_txps;
     if (tm.on)
@@ -190,41 +303,55 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
             hipEventDestroy(ev1);
             if (rc2 != OEM_OK) break;
             tm.lap("cells: EM loop");
-            const double *d_res = mb.out;
-            double *d_full = nullptr;
-            bool expanded_on_host = false;
-            if (compacted && (knob("OEM_TEST_FAIL_FULL_ALLOC", 0) || hipMalloc((void **)&d_full, sizeof(double) * full_total) != hipSuccess)) {
-                // no device memory for the expanded results: the compact ones and the rank table go to the host,
-                // which expands them (a transcript that does not occur in a cell is 0)
-                (void)hipGetLastError();
-                d_full = nullptr;
-                const size_t n_eff = (size_t)mb.n_problems * mb.txps_eff;
-                std::vector<double> h_eff(n_eff);
-                std::vector<uint32_t> h_rank((size_t)full_total);
-                if (hipMemcpy(h_eff.data(), mb.out, sizeof(double) * n_eff, hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(h_rank.data(), mb.rank, sizeof(uint32_t) * full_total, hipMemcpyDeviceToHost) != hipSuccess ||
+            if (blk) { // the entries > 0 straight from the compact (or uncompacted) results: no expansion, no dense copy
+                CellsNzSource src;
+                src.v = mb.out;
+                src.rank = compacted ? mb.rank : nullptr;
+                src.T = caller_txps;
+                src.stride = n_txps;
+                NzScratch sc;
+                if ((rc2 = cells_to_csr(s->stream, src, n_cells, cell_row_off, row_ptr, sc, blk)) != OEM_OK) break;
+                if (hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
+                    rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: state read-back failed");
+                    break;
+                }
+            } else {
+                const double *d_res = mb.out;
+                double *d_full = nullptr;
+                bool expanded_on_host = false;
+                if (compacted && (knob("OEM_TEST_FAIL_FULL_ALLOC", 0) || hipMalloc((void **)&d_full, sizeof(double) * full_total) != hipSuccess)) {
+                    // no device memory for the expanded results: the compact ones and the rank table go to the host,
+                    // which expands them (a transcript that does not occur in a cell is 0)
+                    (void)hipGetLastError();
+                    d_full = nullptr;
+                    const size_t n_eff = (size_t)mb.n_problems * mb.txps_eff;
+                    std::vector<double> h_eff(n_eff);
+                    std::vector<uint32_t> h_rank((size_t)full_total);
+                    if (hipMemcpy(h_eff.data(), mb.out, sizeof(double) * n_eff, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(h_rank.data(), mb.rank, sizeof(uint32_t) * full_total, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
+                        rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: read-back failed");
+                        break;
+                    }
+                    for (size_t i = 0; i < (size_t)full_total; ++i)
+                        out[i] = h_rank[i] == kNoRank ? 0.0 : h_eff[(i / mb.txps_full) * mb.txps_eff + h_rank[i]];
+                    expanded_on_host = true;
+                }
+                if (compacted && !expanded_on_host) { // expand to the caller's [cell][transcript] (the queue is done with: its memory is free by now)
+                    if ((rc2 = launch_multi_expand(s, mb, d_full)) != OEM_OK || hipStreamSynchronize(s->stream) != hipSuccess) {
+                        hipFree(d_full);
+                        if (rc2 == OEM_OK) rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: expanding the results failed");
+                        break;
+                    }
+                    d_res = d_full;
+                }
+                const bool copied = expanded_on_host || hipMemcpy(out, d_res, sizeof(double) * full_total, hipMemcpyDeviceToHost) == hipSuccess;
+                hipFree(d_full);
+                if (!copied ||
                     hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
-                    rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: read-back failed");
+                    rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: result read-back failed");
                     break;
                 }
-                for (size_t i = 0; i < (size_t)full_total; ++i)
-                    out[i] = h_rank[i] == kNoRank ? 0.0 : h_eff[(i / mb.txps_full) * mb.txps_eff + h_rank[i]];
-                expanded_on_host = true;
-            }
-            if (compacted && !expanded_on_host) { // expand to the caller's [cell][transcript] (the queue is done with: its memory is free by now)
-                if ((rc2 = launch_multi_expand(s, mb, d_full)) != OEM_OK || hipStreamSynchronize(s->stream) != hipSuccess) {
-                    hipFree(d_full);
-                    if (rc2 == OEM_OK) rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: expanding the results failed");
-                    break;
-                }
-                d_res = d_full;
-            }
-            const bool copied = expanded_on_host || hipMemcpy(out, d_res, sizeof(double) * full_total, hipMemcpyDeviceToHost) == hipSuccess;
-            hipFree(d_full);
-            if (!copied ||
-                hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: result read-back failed");
-                break;
             }
             if (infos)
                 for (uint32_t c = 0; c < n_cells; ++c) {
@@ -249,7 +376,7 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
 // resident store serves all unfinished cells), otherwise cell after cell over the caller-order CSR.
 int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, const uint64_t *row_ptr,
                     const uint32_t *tid, const float *as_prob, const double *cov_prob, uint32_t n_txps, int device,
-                    uint32_t max_iter, double conv_thresh, double *out, oem_run_info *infos)
+                    uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g, oem_run_info *infos)
 {
     const uint32_t n_cells = c1 - c0;
     const uint64_t r0 = cell_row_off[c0], r1 = cell_row_off[c1];
@@ -284,13 +411,14 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
     const uint32_t *tid_g = tid ? tid + a0 : nullptr;
     const float *p_g = as_prob ? as_prob + a0 : nullptr;
     const double *cov_g = cov_prob ? cov_prob + a0 : nullptr;
-    double *out_g = out + (uint64_t)c0 * n_txps;
+    double *out_g = sink.dense ? sink.dense + (uint64_t)c0 * n_txps : nullptr;
+    SparseBlock *blk = sink.blocks ? &(*sink.blocks)[g] : nullptr;
     oem_run_info *infos_g = infos ? infos + c0 : nullptr;
 
     if (knob("OEM_SERIAL_CELLS", 0) == 0) { // testing build: force the cell-by-cell path
         bool used = false;
         int rcb = run_cells_batched(off_p, n_cells, rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device,
-                                    max_iter, conv_thresh, out_g, infos_g, &used);
+                                    max_iter, conv_thresh, out_g, blk, infos_g, &used);
         if (rcb != OEM_OK || used) return rcb;
     }
     // fallback (max_iter == 0, a single cell, or a group the tiler declines): cells one after another
@@ -300,6 +428,9 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
     opts.reorder_rows = 1; // cells are row ranges of the caller-order CSR
     OEM_TRY(oem_store_create(rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device, &opts, &s));
     int rc = OEM_OK;
+    NzScratch sc;
+    CellsNzSource src; // the cell's count vector (s->cnt after the run, as copy_counts_out reads it), caller's transcript order
+    src.T = src.stride = n_txps;
     for (uint32_t c = 0; c < n_cells && rc == OEM_OK; ++c) {
         RunArgs a;
         a.row_begin = off_p[c];
@@ -309,7 +440,9 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
         a.conv_thresh = conv_thresh;
         a.min_iter_gate = 50;                    // em::em (single_cell.rs:150)
         rc = run_em_device(s, a, infos_g ? &infos_g[c] : nullptr);
-        if (rc == OEM_OK) rc = copy_counts_out(s, out_g + (uint64_t)c * n_txps);
+        src.v = s->cnt;
+        if (rc == OEM_OK)
+            rc = blk ? cells_to_csr(s->stream, src, 1, off_p + c, rp_p, sc, blk) : copy_counts_out(s, out_g + (uint64_t)c * n_txps);
     }
     free_store(s);
     return rc;
@@ -326,26 +459,24 @@ void cells_last_timing(double *loop_ms, uint64_t *batched_passes)
 }
 } // namespace oem
 
-using namespace oem;
+namespace oem {
+namespace {
 
-// ---------------------------------------------------------------------------
-// single-cell batch
-// ---------------------------------------------------------------------------
-extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
-                                const uint32_t *tid, const float *as_prob, const double *cov_prob,
-                                uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
-                                uint32_t max_iter, double conv_thresh, double *out,
-                                oem_run_info *infos)
+// The body of both per-cell entry points (`who` names the caller in messages): argument checks, the NaN-coverage
+// fix-up, the cut into groups and the workers; every group hands its results to `sink`.
+int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+              const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads, uint64_t nnz,
+              uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink,
+              oem_run_info *infos)
 {
-    OEM_API_BEGIN
-    if (!cell_row_off || !row_ptr || (n_cells && !out)) return fail(OEM_ERR_ARG, "oem_em_run_cells: NULL argument");
-    if (n_txps == 0) return fail(OEM_ERR_ARG, "oem_em_run_cells: n_txps is 0");
+    if (!cell_row_off || !row_ptr || (n_cells && !sink.dense && !sink.blocks)) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
+    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
     if (cell_row_off[0] != 0 || cell_row_off[n_cells] != n_reads)
-        return fail(OEM_ERR_ARG, "oem_em_run_cells: cell_row_off must span [0, n_reads]");
+        return fail(OEM_ERR_ARG, "%s: cell_row_off must span [0, n_reads]", who);
     for (uint32_t c = 0; c < n_cells; ++c)
         if (cell_row_off[c + 1] < cell_row_off[c])
-            return fail(OEM_ERR_ARG, "oem_em_run_cells: cell_row_off not non-decreasing at cell %u", c);
-    if (nnz > 0 && (!tid || !as_prob)) return fail(OEM_ERR_ARG, "oem_em_run_cells: tid/as_prob is NULL");
+            return fail(OEM_ERR_ARG, "%s: cell_row_off not non-decreasing at cell %u", who, c);
+    if (nnz > 0 && (!tid || !as_prob)) return fail(OEM_ERR_ARG, "%s: tid/as_prob is NULL", who);
     t_cells_loop_ms = 0.0;
     t_cells_batched_passes = 0;
     StageTimer tm_all;
@@ -400,6 +531,7 @@ extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, 
     // of a loop -- the few cells that run into max_iter, a handful of live tiles per pass -- shares the device with
     // the other group's full passes instead of leaving it idle (single_cell.rs:96-150 runs its cells on N worker
     // threads for the same reason).
+    if (sink.blocks) sink.blocks->assign(groups.size(), SparseBlock());
     CellsTiming timing;
     std::atomic<size_t> next{0};
     constexpr int kMaxWorkers = 4;
@@ -423,7 +555,7 @@ extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, 
                 const size_t g = next.fetch_add(1);
                 if (g >= groups.size() || failed.load()) break;
                 rcs[wk] = run_cells_group(cell_row_off, groups[g].first, groups[g].second, row_ptr, tid, as_prob, cov_prob,
-                                          n_txps, device, max_iter, conv_thresh, out, infos);
+                                          n_txps, device, max_iter, conv_thresh, sink, g, infos);
                 if (rcs[wk] != OEM_OK) break;
             }
         } catch (const std::exception &e) {
@@ -452,5 +584,103 @@ extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, 
     for (int wk = 0; wk < kMaxWorkers; ++wk)
         if (rcs[wk] != OEM_OK) return fail(rcs[wk], "%s", errs[wk].c_str());
     return OEM_OK;
+}
+
+} // namespace
+} // namespace oem
+
+using namespace oem;
+
+// one call's sparse results (immutable once returned): the groups' blocks in group order -- which is cell order --
+// and the cells' offsets; oem_cells_result_copy concatenates the blocks straight into the caller's arrays
+struct oem_cells_result {
+    uint32_t n_cells = 0;
+    uint64_t n_entries = 0;
+    std::vector<uint64_t> cell_off; // n_cells + 1
+    std::vector<SparseBlock> blocks;
+    std::vector<oem_run_info> infos; // n_cells
+};
+
+// ---------------------------------------------------------------------------
+// single-cell batch
+// ---------------------------------------------------------------------------
+extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                const uint32_t *tid, const float *as_prob, const double *cov_prob,
+                                uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
+                                uint32_t max_iter, double conv_thresh, double *out,
+                                oem_run_info *infos)
+{
+    OEM_API_BEGIN
+    CellsSink sink;
+    sink.dense = out;
+    return run_cells("oem_em_run_cells", cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps,
+                     device, max_iter, conv_thresh, sink, infos);
     OEM_API_END("oem_em_run_cells")
+}
+
+extern "C" int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                       const uint32_t *tid, const float *as_prob, const double *cov_prob,
+                                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
+                                       uint32_t max_iter, double conv_thresh, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    if (!out) return fail(OEM_ERR_ARG, "oem_em_run_cells_sparse: out is NULL");
+    *out = nullptr;
+    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
+    r->n_cells = n_cells;
+    r->infos.resize(n_cells);
+    std::vector<SparseBlock> blocks;
+    CellsSink sink;
+    sink.blocks = &blocks;
+    OEM_TRY(run_cells("oem_em_run_cells_sparse", cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz,
+                      n_txps, device, max_iter, conv_thresh, sink, r->infos.data()));
+    // the cells' offsets from the groups' blocks, in group (= cell) order
+    r->cell_off.assign((size_t)n_cells + 1, 0);
+    uint32_t c = 0;
+    for (const SparseBlock &b : blocks) {
+        uint64_t n = 0;
+        for (uint32_t k : b.counts) {
+            if (c >= n_cells) break;
+            r->cell_off[c + 1] = r->cell_off[c] + k;
+            n += k;
+            ++c;
+        }
+        if (n != b.col.size() || n != b.val.size())
+            return fail(OEM_ERR_STATE, "oem_em_run_cells_sparse: a group's entries do not match its counts");
+    }
+    if (c != n_cells) return fail(OEM_ERR_STATE, "oem_em_run_cells_sparse: the groups' results cover %u of %u cells", c, n_cells);
+    r->n_entries = r->cell_off[n_cells];
+    r->blocks = std::move(blocks);
+    *out = r.release();
+    return OEM_OK;
+    OEM_API_END("oem_em_run_cells_sparse")
+}
+
+extern "C" int oem_cells_result_dims(const oem_cells_result *r, uint32_t *n_cells, uint64_t *n_entries)
+{
+    if (!r) return fail(OEM_ERR_ARG, "oem_cells_result_dims: NULL result");
+    if (n_cells) *n_cells = r->n_cells;
+    if (n_entries) *n_entries = r->n_entries;
+    return OEM_OK;
+}
+
+extern "C" int oem_cells_result_copy(const oem_cells_result *r, uint64_t *cell_off, uint32_t *col, float *val,
+                                     oem_run_info *infos)
+{
+    if (!r) return fail(OEM_ERR_ARG, "oem_cells_result_copy: NULL result");
+    if (cell_off) std::memcpy(cell_off, r->cell_off.data(), sizeof(uint64_t) * r->cell_off.size());
+    uint64_t at = 0;
+    for (const SparseBlock &b : r->blocks) {
+        if (b.col.empty()) continue;
+        if (col) std::memcpy(col + at, b.col.data(), sizeof(uint32_t) * b.col.size());
+        if (val) std::memcpy(val + at, b.val.data(), sizeof(float) * b.val.size());
+        at += b.col.size();
+    }
+    if (infos && !r->infos.empty()) std::memcpy(infos, r->infos.data(), sizeof(oem_run_info) * r->infos.size());
+    return OEM_OK;
+}
+
+extern "C" void oem_cells_result_destroy(oem_cells_result *r)
+{
+    delete r;
 }

@@ -297,6 +297,20 @@ int launch_multi_reldiff(oem_store *s, double *theta, double *cnt, const MultiBu
 int multi_compact_live(oem_store *s, MultiBuffers &mb); // rebuilds the live lists (synchronises the stream)
 int launch_permute_row_w(oem_store *s, const uint32_t *row_w, uint32_t *row_w_perm);
 
+// per-cell results as CSR (oem_cells_sparse.hip): value of transcript t of cell c = rank ? (rank[c * T + t] == kNoRank ? 0
+// : v[c * stride + rank[c * T + t]]) : v[c * stride + t]
+struct CellsNzSource {
+    const double *v = nullptr;
+    const uint32_t *rank = nullptr;
+    uint32_t T = 0;      // the caller's n_txps
+    uint32_t stride = 0; // values per cell in v (txps_eff of a compacted batch, else T)
+};
+// counts[c] = entries > 0.0 of cell c
+int launch_cells_nz_count(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, uint32_t *d_counts);
+// cell c's entries at [off[c], off[c + 1]) in ascending transcript id: col = t, val = (float)v
+int launch_cells_nz_emit(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, const uint64_t *d_off, uint32_t *d_col,
+                         float *d_val);
+
 // batched bootstrap (oem_batch_kernels.hip)
 int launch_batch_pass(oem_store *s, const BatchBuffers &bb);
 int launch_batch_reldiff(oem_store *s, const BatchBuffers &bb, EmParams p);

@@ -94,6 +94,47 @@ def em_cells(cell_row_off: Sequence[int], boundaries, ref_ids, as_probabilities,
                  for i in list(infos)[:n_cells]]
 
 
+def em_cells_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, as_probabilities,
+                    coverage_probabilities, n_txps: int, max_iter: int = 1000,
+                    convergence_thresh: float = 1e-3, device: int = 0):
+    """``em_cells`` with the result in the form single_cell.rs:151-160 keeps it: per cell the
+    transcripts with ``v > 0`` as (col u32, val f32), ascending column, picked out on the device.
+
+    Returns (indptr u64[n_cells + 1], cols u32, vals f32, [RunInfo]): cell c's entries are
+    ``cols[indptr[c]:indptr[c + 1]]`` (``writers.csr_triplets`` turns them into the triplets of
+    ``.count.mtx``).  Memory is proportional to the non-zeros, not to n_cells x n_txps.
+    """
+    cell_row_off = np.ascontiguousarray(cell_row_off, dtype=np.uint64)
+    boundaries = np.ascontiguousarray(boundaries, dtype=np.uint64)
+    ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+    as_probabilities = np.ascontiguousarray(as_probabilities, dtype=np.float32)
+    cov = None if coverage_probabilities is None else np.ascontiguousarray(
+        coverage_probabilities, dtype=np.float64)
+    n_cells = len(cell_row_off) - 1
+    n_reads = len(boundaries) - 1
+    nnz = len(ref_ids)
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_em_run_cells_sparse(
+        cell_row_off.ctypes.data, n_cells, boundaries.ctypes.data,
+        ref_ids.ctypes.data if nnz else None, as_probabilities.ctypes.data if nnz else None,
+        None if cov is None else cov.ctypes.data, n_reads, nnz, n_txps, device, max_iter,
+        convergence_thresh, C.byref(res)))
+    try:
+        nc, ne = C.c_uint32(0), C.c_uint64(0)
+        _lib.check(L.oem_cells_result_dims(res, C.byref(nc), C.byref(ne)))
+        indptr = np.zeros(int(nc.value) + 1, dtype=np.uint64)
+        cols = np.empty(int(ne.value), dtype=np.uint32)
+        vals = np.empty(int(ne.value), dtype=np.float32)
+        infos = (_lib.RunInfoC * max(n_cells, 1))()
+        _lib.check(L.oem_cells_result_copy(res, indptr.ctypes.data, cols.ctypes.data, vals.ctypes.data,
+                                           C.addressof(infos)))
+    finally:
+        L.oem_cells_result_destroy(res)
+    return indptr, cols, vals, [RunInfo(i.niter, i.n_passes, bool(i.converged), i.rel_diff)
+                                for i in list(infos)[:n_cells]]
+
+
 def cells_last_timing():
     """(device milliseconds of the batched EM loops, batched passes launched) of this thread's last
     ``em_cells`` call -- oem_cells_last_timing; bench.py's per-cell roofline."""

@@ -124,11 +124,21 @@ def cell_triplets(cell_counts) -> tuple:
     return rows.astype(np.uint32), cols.astype(np.uint32), cell_counts[rows, cols].astype(np.float32)
 
 
+def csr_triplets(indptr, cols, vals) -> tuple:
+    """The (row_ids, col_ids, vals) of `cell_triplets` from the CSR form of `em_cells_sparse` (per cell the
+    entries v > 0 in ascending column, values already f32): the same triplets in the same order."""
+    indptr = np.asarray(indptr, dtype=np.uint64)
+    counts = np.diff(indptr.astype(np.int64))
+    rows = np.repeat(np.arange(len(counts), dtype=np.uint32), counts)
+    return rows, np.asarray(cols, dtype=np.uint32), np.asarray(vals, dtype=np.float32)
+
+
 def write_single_cell_output(output: str, info: dict, feature_names: Sequence[str], barcodes: Optional[Sequence[str]],
                              n_cells: int, row_ids, col_ids, vals) -> None:
     """write_function.rs:25-69: `.meta_info.json`, `.count.mtx` (MatrixMarket coordinate real
     general, 1-based, f32 values in triplet order as sprs::io::write_matrix_market emits them) and
-    `.features.txt`; `.barcodes.txt` in row order (single_cell.rs:176-178)."""
+    `.features.txt`; `.barcodes.txt` in row order (single_cell.rs:176-178).  The triplets come from
+    `cell_triplets(dense)` or `csr_triplets(*em_cells_sparse(...)[:3])`."""
     _make_parent(output)
     with open(with_additional_extension(output, ".meta_info.json"), "w") as fh:
         json.dump(info, fh, indent=2)
