@@ -37,7 +37,8 @@ extern "C" {
 /* 2: oem_time_bootstrap_passes, oem_store_opts.layout_build and .weight_coding (were reserved words: zero = the
  *    default, as before), the peer-to-peer communicator entry points (oem_comm_p2p_*), oem_store_info; version 1
  *    callers keep working (additions only).  Later additions under the same number: the sparse per-cell results
- *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy). */
+ *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy), the per-cell coverage model
+ *    (oem_coverage_probs_cells_device). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -230,6 +231,19 @@ int oem_coverage_probs_device(const uint64_t *row_ptr, const uint32_t *tid, cons
                               double *out_cov_prob);
 int oem_builder_coverage_probs_device(const oem_builder *b, uint32_t bin_width, int model, double growth_rate,
                                       int device, double *out_cov_prob);
+/* The per-cell coverage model of a single-cell run (single_cell.rs:117-137: every cell bins only its own
+ * retained alignments and normalises its own reads), for all cells in one call.  Cells as in oem_em_run_cells:
+ * one concatenated CSR plus cell_row_off[n_cells+1]; aln_start / aln_end / out_cov_prob: nnz each, the caller's
+ * alignment order.  The result is, cell by cell, what oem_coverage_probs_device returns on that cell's slice (row_ptr
+ * rebased to 0), up to the order of the f64 atomic sums.  Bins are allocated only for the (cell, transcript) pairs
+ * that occur, in chunks of consecutive cells that fit in device memory.  Cells without reads are allowed; nnz must
+ * be below 2^32 and n_txps below 2^31 - 1.  OEM_ERR_STATE conditions are those of oem_coverage_probs_device; the
+ * message names the first offending cell. */
+int oem_coverage_probs_cells_device(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                    const uint32_t *tid, const uint32_t *aln_start, const uint32_t *aln_end,
+                                    const uint64_t *txp_len, uint64_t n_reads, uint64_t nnz, uint32_t n_txps,
+                                    uint32_t bin_width, int model, double growth_rate, int device,
+                                    double *out_cov_prob);
 /* Uploads the built store (oem_store_create on the builder's arrays). */
 int oem_builder_store_create(const oem_builder *b, const double *cov_prob, int device,
                              const oem_store_opts *opts, oem_store **out);

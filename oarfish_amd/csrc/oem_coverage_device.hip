@@ -11,8 +11,10 @@
 //                    bin probabilities (sequential over the transcript's bins, as on the host)
 //   k_cov_reads      one thread per read: per-alignment coverage probability, normalised per read
 //
+// The arithmetic itself lives in oem_coverage_common.h, shared with the per-cell kernels of oem_coverage_cells.hip.
 // The host version manages 8 M alignments/s on one core; this one is bound by the upload of the
 // alignment coordinates.
+#include "oem_coverage_common.h"
 #include "oem_internal.h"
 
 namespace oem {
@@ -20,14 +22,13 @@ namespace oem {
 namespace {
 
 constexpr int kCT = 256;
-enum : uint32_t { kErrInterval = 1, kErrOlfrac = 2, kErrNoBins = 4, kErrDegenerate = 8, kErrNonFinite = 16 };
 
 __global__ __launch_bounds__(kCT) void k_cov_bin_counts(const uint64_t *__restrict__ txp_len, uint32_t n_txps,
                                                         uint32_t bin_width, uint32_t *__restrict__ n_bins)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_txps) return;
-    n_bins[t] = (uint32_t)ceil((double)txp_len[t] / (double)bin_width); // with_len_and_bin_width (:460-468)
+    n_bins[t] = cov_n_bins(txp_len[t], bin_width); // with_len_and_bin_width (:460-468)
 }
 
 // exclusive prefix sum of n_bins (one workgroup; T <= 2^32 but this is O(T / 1024) per thread)
@@ -61,73 +62,8 @@ __global__ __launch_bounds__(kCT) void k_cov_bins(const uint32_t *__restrict__ t
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nnz) return;
     const uint32_t t = tid[j];
-    const uint32_t num_intervals = n_bins[t];
-    const double nf = (double)num_intervals, tlen_f = (double)txp_len[t];
-    const double bw = round(tlen_f / nf);                                          // :501
-    uint32_t start = aln_start[j], stop = aln_end[j];
-    start = min(start, stop);                                                      // :502
-    stop = max(start, stop);                                                       // :503
-    const uint64_t start_bin = (uint64_t)floor(((double)start / tlen_f) * nf);     // :504
-    const uint64_t end_bin = (uint64_t)floor(((double)stop / tlen_f) * nf);        // :505
-    if (start_bin > end_bin || end_bin > num_intervals) { atomicOr(err, kErrInterval); return; }
-    double *tb = bins + off[t];
-    for (uint64_t bi = start_bin; bi < end_bin; ++bi) {                            // :515-536
-        const double bidxf = (double)bi;
-        const uint32_t cbs = (uint32_t)(bidxf * bw);
-        const uint32_t cbe = (uint32_t)fmin((bidxf + 1.0) * bw, tlen_f);
-        const uint32_t olap = start <= cbe ? min(stop, cbe) - max(start, cbs) : 0u; // :507-513 (u32)
-        const double olfrac = (double)olap / (double)(uint32_t)(cbe - cbs);
-        if (olfrac > 1.0 + 2.220446049250313e-16) atomicOr(err, kErrOlfrac);       // :524-535: the reference panics
-        unsafeAtomicAdd(&tb[bi], olfrac);
-    }
+    if (!cov_add_interval(aln_start[j], aln_end[j], n_bins[t], (double)txp_len[t], bins + off[t], err)) return;
     atomicAdd(&total_weight[t], 1u);                                               // :537 (weight 1.0, :727)
-}
-
-__device__ double binomial_bins(const double *tb, uint32_t n, float bwf, float lenf32, double *prob, uint32_t *err)
-{
-    // binomial_continuous_prob + binomial_probability (binomial_probability.rs:7-224); tb already holds
-    // bins + min_cov.  Two sweeps over the bins recompute the f32 counts rather than store them.
-    const double kZero = 1e-20, kMaxScale = 709.0;
-    float count_sum = 0.0f, max_val = 0.0f;
-    double distinct_rate = 0.0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const float c = (float)tb[i];
-        const float len = fminf(((float)i + 1.0f) * bwf, lenf32) - (float)i * bwf;
-        count_sum += c;                                                            // :14
-        max_val = i == 0 ? c : fmaxf(max_val, c);                                  // :50
-        distinct_rate += (double)c / (double)len;                                  // :184-188
-    }
-    if (count_sum == 0.0f || distinct_rate == 0.0) {                               // :19-25
-        for (uint32_t i = 0; i < n; ++i) prob[i] = 0.0;
-        return 0.0;
-    }
-    float sum_vec = 0.0f;
-    for (uint32_t i = 0; i < n; ++i) {                                             // :61-72
-        const float c = (float)tb[i];
-        sum_vec += c == max_val ? (float)kMaxScale : (float)(((double)c * kMaxScale) / (double)max_val);
-    }
-    const double ln1 = lgamma((double)sum_vec + 1.0);                              // :75
-    double total = 0.0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const float c = (float)tb[i];
-        const float len = fminf(((float)i + 1.0f) * bwf, lenf32) - (float)i * bwf;
-        const float m = c == max_val ? (float)kMaxScale : (float)(((double)c * kMaxScale) / (double)max_val);
-        const double p = (c == 0.0f || len == 0.0f) ? 0.0 : (double)c / ((double)len * distinct_rate); // :27-43
-        const double denom = lgamma((double)m + 1.0) + lgamma((double)(sum_vec - m) + 1.0);              // :76-79
-        const double num2 = (p > kZero ? log(p) : log(kZero)) * (double)m;                               // :82
-        const double q = 1.0 - p;
-        const double num3 = (q > kZero ? log(q) : log(kZero)) * (double)(sum_vec - m);                   // :89
-        const double res = exp(ln1 - denom + num2 + num3);                                               // :101
-        if (isnan(num2) || isinf(num2) || isnan(num3) || isinf(num3) || isnan(res) || isinf(res))
-            atomicOr(err, kErrNonFinite);                                          // the reference panics (:83-112)
-        prob[i] = res;
-        total += res;                                                              // :120
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-        prob[i] /= total;                                                          // :124
-        if (isnan(prob[i])) atomicOr(err, kErrNonFinite);
-    }
-    return total;
 }
 
 __global__ __launch_bounds__(kCT) void k_cov_bin_probs(const uint64_t *__restrict__ txp_len, const uint32_t *__restrict__ n_bins,
@@ -138,35 +74,7 @@ __global__ __launch_bounds__(kCT) void k_cov_bin_probs(const uint64_t *__restric
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_txps) return;
-    const uint32_t n = n_bins[t];
-    if (n == 0) { atomicOr(err, kErrNoBins); return; }                             // assert (logistic_probability.rs:54)
-    double *tb = bins + off[t], *tp = prob + off[t];
-    const double lenf = (double)txp_len[t];
-    const double min_cov = (double)total_weight[t] / 100.;                         // :55 / binomial :180
-    for (uint32_t i = 0; i < n; ++i) tb[i] += min_cov;                             // :56
-    // get_normalized_counts_and_lengths (oarfish_types.rs:471-493): f32 counts and bin widths
-    const float bwf = (float)round(lenf / (double)n), lenf32 = (float)lenf;
-    for (uint32_t i = 0; i < n; ++i) {
-        const float bs = (float)i * bwf, be = fminf(((float)i + 1.0f) * bwf, lenf32);
-        if (!(be > bs)) { atomicOr(err, kErrDegenerate); return; }                 // assert (:490)
-    }
-    if (model == 1) {
-        binomial_bins(tb, n, bwf, lenf32, tp, err);
-        return;
-    }
-    double count_sum = 0.0;                                                        // logstic_function (:13-39)
-    for (uint32_t i = 0; i < n; ++i) count_sum += (double)(float)tb[i];
-    if (count_sum <= 1e-8) {                                                       // :21-23
-        for (uint32_t i = 0; i < n; ++i) tp[i] = 0.0;
-        return;
-    }
-    const double expected = count_sum / (double)n;                                 // :27
-    for (uint32_t i = 0; i < n; ++i) {
-        const double diff = (expected - (double)(float)tb[i]) / expected;          // :32
-        double r = 1.0 / (1.0 + exp(-growth_rate * diff));                         // logistic (:7-10)
-        r = r < 1e-8 ? 1e-8 : (r > 0.99999 ? 0.99999 : r);
-        tp[i] = r;
-    }
+    cov_bin_probs(bins + off[t], prob + off[t], n_bins[t], (double)txp_len[t], total_weight[t], model, growth_rate, err);
 }
 
 __global__ __launch_bounds__(kCT) void k_cov_reads(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ tid,
@@ -178,33 +86,12 @@ __global__ __launch_bounds__(kCT) void k_cov_reads(const uint32_t *__restrict__ 
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_reads) return;
-    double nprob_sum = 0.0;                                                        // normalize_probability.rs:5-74
-    for (uint32_t j = row_ptr[r]; j < row_ptr[r + 1]; ++j) {
-        const uint32_t t = tid[j];
-        const double *tp = prob + off[t];
-        const double start_aln = (double)aln_start[j], end_aln = (double)aln_end[j], tlen = (double)txp_len[t];
-        const uint64_t start_bin = (uint64_t)(start_aln / bin_length);             // :25
-        uint64_t end_bin = (uint64_t)(end_aln / bin_length);                       // :26-27
-        if (end_bin > (uint64_t)n_bins[t] - 1) end_bin = (uint64_t)n_bins[t] - 1;
-        double total_weight = 0.0, cov_prob = 0.0;
-        if (start_bin == end_bin) {                                                // :33-35
-            const double w = (end_aln - start_aln) / bin_length;
-            total_weight = w;
-            cov_prob = w * tp[start_bin];
-        } else {
-            for (uint64_t i = start_bin; i < end_bin; ++i) {                       // :37-46
-                const double w = i == start_bin ? (fmin(bin_length * (double)i + bin_length, tlen) - start_aln) / bin_length : 1.0;
-                total_weight += w;
-                cov_prob += w * tp[i];
-            }
-        }
-        const double expected = cov_prob / total_weight;                           // :58
-        if (isnan(cov_prob) || isinf(cov_prob)) atomicOr(err, kErrNonFinite); // :49-57 (a 0/0 expected value is not an error there)
-        out[j] = expected;
-        nprob_sum += expected;
-    }
-    const double denom = nprob_sum > 0.0 ? nprob_sum : 1.0;                        // :62
-    for (uint32_t j = row_ptr[r]; j < row_ptr[r + 1]; ++j) out[j] /= denom;        // :65-69
+    cov_normalize_read(row_ptr[r], row_ptr[r + 1], aln_start, aln_end, bin_length,
+                       [&](uint64_t j) {
+                           const uint32_t t = tid[j];
+                           return CovTxpBins{prob + off[t], n_bins[t], (double)txp_len[t]};
+                       },
+                       out, err);
 }
 
 struct Bufs {
@@ -290,11 +177,11 @@ extern "C" int oem_coverage_probs_device(const uint64_t *row_ptr, const uint32_t
     OEM_HIP(hipGetLastError());
     uint32_t h_err = 0;
     OEM_HIP(hipMemcpy(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost));
-    if (h_err & kErrInterval) return fail(OEM_ERR_STATE, "add_interval: an alignment lies outside its transcript");
-    if (h_err & kErrOlfrac) return fail(OEM_ERR_STATE, "coverage computation error: overlap fraction above 1");
-    if (h_err & kErrNoBins) return fail(OEM_ERR_STATE, "a transcript has no coverage bins");
-    if (h_err & kErrDegenerate) return fail(OEM_ERR_STATE, "degenerate coverage bin (assert, oarfish_types.rs:490)");
-    if (h_err & kErrNonFinite) return fail(OEM_ERR_STATE, "coverage model: non-finite probability");
+    if (h_err & kCovErrInterval) return fail(OEM_ERR_STATE, "add_interval: an alignment lies outside its transcript");
+    if (h_err & kCovErrOlfrac) return fail(OEM_ERR_STATE, "coverage computation error: overlap fraction above 1");
+    if (h_err & kCovErrNoBins) return fail(OEM_ERR_STATE, "a transcript has no coverage bins");
+    if (h_err & kCovErrDegenerate) return fail(OEM_ERR_STATE, "degenerate coverage bin (assert, oarfish_types.rs:490)");
+    if (h_err & kCovErrNonFinite) return fail(OEM_ERR_STATE, "coverage model: non-finite probability");
     OEM_HIP(hipMemcpy(out_cov_prob, d_out, sizeof(double) * nnz, hipMemcpyDeviceToHost));
     return OEM_OK;
     OEM_API_END("oem_coverage_probs_device")

@@ -135,6 +135,43 @@ def em_cells_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, as_probabi
                                 for i in list(infos)[:n_cells]]
 
 
+_COVERAGE_MODELS = {"logistic": 0, "binomial": 1}
+
+
+def cells_coverage_probs(cell_row_off: Sequence[int], boundaries, ref_ids, aln_start, aln_end, txp_len,
+                         bin_width: int = 100, model: str = "binomial", growth_rate: float = 2.0,
+                         device: int = 0) -> np.ndarray:
+    """The coverage column of a single-cell ``--model-coverage`` run, every cell in one call.
+
+    single_cell.rs:132-137 gives each cell its own coverage model: the cell's retained alignments are binned
+    on pristine ``TranscriptInfo``s, ``binomial_continuous_prob`` turns the bins into probabilities and
+    ``normalize_read_probs`` normalises the cell's reads.  Cells are given as in ``em_cells`` (one
+    concatenated CSR plus ``cell_row_off``), with each alignment's ``aln_start`` / ``aln_end`` and the
+    annotation's ``txp_len``.  ``model`` is ``"binomial"`` (the single-cell driver's) or ``"logistic"``
+    (``growth_rate`` used).  Returns the nnz f64 ``coverage_probabilities`` of ``em_cells`` /
+    ``em_cells_sparse``, in the caller's alignment order; a zero-span alignment gives NaN, as in the
+    reference, and the cells EM drops its read.
+    """
+    if model not in _COVERAGE_MODELS:
+        raise ValueError(f"model must be one of {sorted(_COVERAGE_MODELS)}, not {model!r}")
+    cell_row_off = np.ascontiguousarray(cell_row_off, dtype=np.uint64)
+    boundaries = np.ascontiguousarray(boundaries, dtype=np.uint64)
+    ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+    aln_start = np.ascontiguousarray(aln_start, dtype=np.uint32)
+    aln_end = np.ascontiguousarray(aln_end, dtype=np.uint32)
+    txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+    nnz = len(ref_ids)
+    if len(aln_start) != nnz or len(aln_end) != nnz:
+        raise ValueError("ref_ids, aln_start and aln_end must have one entry per alignment")
+    out = np.empty(nnz, dtype=np.float64)
+    _lib.check(_lib.lib().oem_coverage_probs_cells_device(
+        cell_row_off.ctypes.data, len(cell_row_off) - 1, boundaries.ctypes.data,
+        ref_ids.ctypes.data if nnz else None, aln_start.ctypes.data if nnz else None,
+        aln_end.ctypes.data if nnz else None, txp_len.ctypes.data, len(boundaries) - 1, nnz, len(txp_len),
+        bin_width, _COVERAGE_MODELS[model], growth_rate, device, out.ctypes.data if nnz else None))
+    return out
+
+
 def cells_last_timing():
     """(device milliseconds of the batched EM loops, batched passes launched) of this thread's last
     ``em_cells`` call -- oem_cells_last_timing; bench.py's per-cell roofline."""

@@ -247,6 +247,43 @@ def make_cells(n_cells: int, reads_per_cell: int, n_txps: int, kbar: float = 8.0
             np.concatenate(ps) if ps else np.zeros(0, np.float32))
 
 
+def make_coordinates(tid, n_txps: int, seed: int = BASE_SEED + 9, zero_span_frac: float = 0.0,
+                     min_len: int = 400, max_len: int = 6000, threads: int = 1):
+    """Alignment coordinates consistent with a store's transcript ids, so that a store (``make_store``,
+    ``make_cells``) can carry a coverage model: (txp_len u64[n_txps], aln_start u32[nnz], aln_end u32[nnz]).
+
+    Transcript lengths are uniform on [min_len, max_len); alignment j of transcript t spans 100 .. 3000 bases
+    (at most the transcript) at a uniform position inside it, so 0 <= start <= end <= txp_len[t].  A fraction
+    ``zero_span_frac`` of the alignments get end == start (the reference's coverage model gives them NaN).
+    Alignments are drawn in chunks of ``CHUNK``, chunk c from ``default_rng([seed, c])``: the result is a pure
+    function of (tid, n_txps, seed, zero_span_frac, min_len, max_len)."""
+    tid = np.asarray(tid, dtype=np.uint32)
+    txp_len = np.random.default_rng([seed, 0x7E4]).integers(min_len, max_len, size=n_txps).astype(np.uint64)
+    nnz = len(tid)
+    start = np.empty(nnz, dtype=np.uint32)
+    end = np.empty(nnz, dtype=np.uint32)
+
+    def one(c):
+        a, b = c * CHUNK, min(nnz, (c + 1) * CHUNK)
+        rng = np.random.default_rng([seed, c])
+        L = txp_len[tid[a:b]].astype(np.int64)
+        span = np.minimum(rng.integers(100, 3000, size=b - a), L)
+        s = (rng.random(b - a) * (L - span + 1)).astype(np.int64)
+        s = np.minimum(s, L - span)
+        span = np.where(rng.random(b - a) < zero_span_frac, 0, span)
+        start[a:b] = s
+        end[a:b] = s + span
+
+    n_chunks = -(-nnz // CHUNK)
+    if threads > 1 and n_chunks > 1:
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            list(ex.map(one, range(n_chunks)))
+    else:
+        for c in range(n_chunks):
+            one(c)
+    return txp_len, start, end
+
+
 def cell_shift(rep: int, n_txps: int) -> int:
     """Transcript-id rotation of replica ``rep`` of a cell in ``replicate_cells``."""
     return (rep * 7919) % n_txps
