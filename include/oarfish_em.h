@@ -38,7 +38,7 @@ extern "C" {
  *    default, as before), the peer-to-peer communicator entry points (oem_comm_p2p_*), oem_store_info; version 1
  *    callers keep working (additions only).  Later additions under the same number: the sparse per-cell results
  *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy), the per-cell coverage model
- *    (oem_coverage_probs_cells_device). */
+ *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -343,6 +343,19 @@ int oem_cells_result_dims(const oem_cells_result *r, uint32_t *n_cells, uint64_t
 int oem_cells_result_copy(const oem_cells_result *r, uint64_t *cell_off, uint32_t *col, float *val,
                           oem_run_info *infos);
 void oem_cells_result_destroy(oem_cells_result *r); /* NULL: no-op */
+/* single_cell.rs:117-160 from the built store on, in one call: the result equals oem_coverage_probs_cells_device on
+ * the same cells, coordinates, bin_width, model and growth_rate, followed by oem_em_run_cells_sparse on that column --
+ * but the column is computed, turned into the EM's weights and used on the device, one group of cells at a time.
+ * Errors are those of the two calls, checked before any device work; an alignment outside its transcript is
+ * OEM_ERR_STATE naming the first such cell.  out_cov_prob (nnz, optional): receives the column the EM used (NaN where
+ * a zero-span alignment gives it, before the EM drops the read).  *out = NULL on any failure. */
+int oem_em_run_cells_coverage_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                     const uint32_t *tid, const float *as_prob,
+                                     const uint32_t *aln_start, const uint32_t *aln_end, const uint64_t *txp_len,
+                                     uint64_t n_reads, uint64_t nnz, uint32_t n_txps,
+                                     uint32_t bin_width, int model, double growth_rate,
+                                     int device, uint32_t max_iter, double conv_thresh,
+                                     double *out_cov_prob, oem_cells_result **out);
 
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */

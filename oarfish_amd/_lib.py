@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "oem_m_step", "oem_em_run", "oem_aux_counts", "oem_assignment_probs",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
-    "oem_cells_result_destroy",
+    "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
     "oem_comm_set_option", "oem_comm_info", "oem_store_attach_comm",
     "oem_time_m_step", "oem_time_em_iters", "oem_time_bootstrap_passes", "oem_time_allreduce",
@@ -150,6 +150,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_result_copy.argtypes = [vp, vp, vp, vp, vp]
     L.oem_cells_result_destroy.argtypes = [vp]
     L.oem_cells_result_destroy.restype = None
+    L.oem_em_run_cells_coverage_sparse.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, f64, i32,
+                                                   u32, f64, vp, C.POINTER(vp)]
     L.oem_comm_unique_id.argtypes = [vp]
     L.oem_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.oem_comm_destroy.argtypes = [vp]

@@ -298,15 +298,35 @@ __global__ __launch_bounds__(256) void k_cells_relabel_ranked(const uint32_t *__
 
 } // namespace
 
+int upload_row_ptr_u32(hipStream_t st, const uint64_t *row_ptr, uint64_t n, uint32_t *d_out)
+{
+    unsigned long long *d64 = nullptr;
+    OEM_HIP(hipMalloc((void **)&d64, sizeof(uint64_t) * n));
+    hipError_t e = hipMemcpyAsync(d64, row_ptr, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        uint64_t g = (n + 255) / 256;
+        if (g > 4096) g = 4096;
+        hipLaunchKernelGGL(k_narrow_u64, dim3((uint32_t)g), dim3(256), 0, st, d64, d_out, n);
+        e = hipStreamSynchronize(st);
+    }
+    hipFree(d64);
+    if (e != hipSuccess) return fail(OEM_ERR_HIP, "row_ptr upload failed: %s", hipGetErrorString(e));
+    return OEM_OK;
+}
+
 static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
                         const double *cov_prob, uint64_t n_reads, uint64_t nnz, uint32_t n_txps,
-                        int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel);
+                        int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel,
+                        ResidentCsr *resident);
 
 // upload + layout (either builder) + the slim remote records every kernel reads (oem_layout_pack.hip)
 int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
                       const double *cov_prob, uint64_t n_reads, uint64_t nnz, uint32_t n_txps,
-                      int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel)
+                      int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel,
+                      ResidentCsr *resident)
 {
+    if (resident && opts && (opts->weight_coding != 0 || opts->layout_build == 1))
+        return fail(OEM_ERR_ARG, "a store from a resident CSR keeps f64 weights and the device layout builder");
     // weight_coding = 2 (opt-in): with the coverage model the iteration-invariant weight w = (p as f64) * cov
     // (em.rs:107-111) is rounded ONCE to f32 and the store is an f32 store -- 8 B per alignment instead of 12, the
     // kernels of the plain f32 stream instead of the f64 ones.  Every product and sum of the EM stays f64; only the
@@ -325,7 +345,7 @@ int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float 
             cov_prob = nullptr;
         }
     }
-    OEM_TRY(create_store_layout(row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps, device, opts, s, relabel));
+    OEM_TRY(create_store_layout(row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps, device, opts, s, relabel, resident));
     StageTimer tm;
     // (the test-only library keeps the builders' streams when asked to: the layout tests hash them)
     OEM_TRY(pack_remote_records(s, s->multi.txps_eff ? s->multi.txps_eff : (opts ? opts->problem_size : 0u), knob("OEM_KEEP_UNPACKED", 0) != 0));
@@ -339,7 +359,8 @@ int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float 
 
 static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
                                const double *cov_prob, uint64_t n_reads, uint64_t nnz, uint32_t n_txps,
-                               int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel)
+                               int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel,
+                               ResidentCsr *resident)
 {
     s->device = device;
     StageTimer tm;
@@ -349,11 +370,21 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
     m.nnz = nnz;
     m.n_txps = n_txps;
     m.wide_ptr = nnz >= (1ull << 32);
-    m.w_is_f64 = cov_prob != nullptr;
+    m.w_is_f64 = cov_prob != nullptr || resident != nullptr;
+    if (resident && m.wide_ptr) return fail(OEM_ERR_ARG, "a resident CSR needs fewer than 2^32 alignments");
 
     // The caller-order CSR (row ranges of per-cell runs, aux counts, assignment probabilities) goes up
     // from a helper thread while this one builds the tiled layout: both are host-bound.
     auto upload_csr = [&]() -> int {
+        if (resident) { // already on the device, in caller order: the store takes the buffers over
+            m.row_ptr = resident->row_ptr;
+            m.tid = resident->tid;
+            m.w64 = resident->w64;
+            resident->row_ptr = resident->tid = nullptr;
+            resident->w64 = nullptr;
+            s->hbm_bytes += sizeof(uint32_t) * (n_reads + 1) + (sizeof(uint32_t) + sizeof(double)) * nnz;
+            return OEM_OK;
+        }
         if (m.wide_ptr) {
             uint64_t *d = nullptr;
             OEM_TRY(dev_alloc(&d, n_reads + 1, &s->hbm_bytes));
@@ -519,9 +550,22 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
         OEM_TRY(alloc_vectors());
         if (relabel) tm.lap("cells: transcripts relabelled");
         bool built = false;
-        OEM_TRY(build_tiled_layout_device(s, problem_size, win_cap, tile_rows, &built));
+        if (knob("OEM_TEST_HOST_LAYOUT", 0) == 0) // testing build: the host builder takes the store
+            OEM_TRY(build_tiled_layout_device(s, problem_size, win_cap, tile_rows, &built));
         tm.lap("tiled layout build (device)");
         if (built) return OEM_OK;
+        // A resident CSR's weights exist on the device only: the host builder gets them back as the coverage
+        // column of unit probabilities ((double)1.0f * w == w).  Rare: the device builder declines only stores
+        // the host one mostly declines too (a read with too many alignments inside one window).
+        std::vector<float> ones;
+        std::vector<double> w_host;
+        if (resident) {
+            ones.assign(nnz, 1.0f);
+            w_host.resize(nnz);
+            if (nnz) OEM_HIP(hipMemcpy(w_host.data(), m.w64, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+            as_prob = ones.data();
+            cov_prob = w_host.data();
+        }
         TiledHost h;
         const char *err = nullptr;
         if (build_tiled_layout(row_ptr, host_tids(), as_prob, cov_prob, n_reads, nnz, m.n_txps, &h, &err,

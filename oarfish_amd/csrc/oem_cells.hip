@@ -3,6 +3,7 @@
 // declines run cell after cell over the caller-order CSR.
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -170,7 +171,7 @@ int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, con
 int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
                       const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads,
                       uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
-                      double *out, SparseBlock *blk, oem_run_info *infos, bool *used)
+                      double *out, SparseBlock *blk, oem_run_info *infos, bool *used, ResidentCsr *resident)
 {
     *used = false;
     StageTimer tm;
@@ -186,14 +187,25 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
     opts.problem_size = n_txps;
     // transcripts of cell p -> [p*T, (p+1)*T), relabelled on the device after the upload
     CellRelabel rl{cell_row_off, n_cells, n_txps};
-    int rc = create_store_impl(row_ptr, tid, as_prob, cov_prob, n_reads, nnz, (uint32_t)total_txps, device, &opts, s, &rl);
+    int rc = create_store_impl(row_ptr, tid, as_prob, cov_prob, n_reads, nnz, (uint32_t)total_txps, device, &opts, s, &rl,
+                               resident);
     if (rc != OEM_OK) {
         free_store(s);
         return rc;
     }
     if (!s->tiled.present) { // e.g. a read with > 255 alignments inside one window: the serial path takes the group
+        if (resident) {      // ... over the resident CSR, back from the store with the caller's ids (they were relabelled)
+            resident->row_ptr = (uint32_t *)s->csr.row_ptr;
+            resident->tid = s->csr.tid;
+            resident->w64 = s->csr.w64;
+            s->csr.row_ptr = nullptr;
+            s->csr.tid = nullptr;
+            s->csr.w64 = nullptr;
+            if (nnz && hipMemcpy(resident->tid, tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice) != hipSuccess)
+                rc = fail(OEM_ERR_HIP, "oem_em_run_cells: restoring the transcript ids failed");
+        }
         free_store(s);
-        return OEM_OK;
+        return rc;
     }
     *used = true;
     tm.lap("cells: store create");
@@ -375,8 +387,9 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
 // One group of consecutive cells [c0, c1): batched on the device when it can be (every pass over the
 // resident store serves all unfinished cells), otherwise cell after cell over the caller-order CSR.
 int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, const uint64_t *row_ptr,
-                    const uint32_t *tid, const float *as_prob, const double *cov_prob, uint32_t n_txps, int device,
-                    uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g, oem_run_info *infos)
+                    const uint32_t *tid, const float *as_prob, const double *cov_prob, const CellsCoverage *cov_src,
+                    uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g,
+                    oem_run_info *infos)
 {
     const uint32_t n_cells = c1 - c0;
     const uint64_t r0 = cell_row_off[c0], r1 = cell_row_off[c1];
@@ -414,11 +427,19 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
     double *out_g = sink.dense ? sink.dense + (uint64_t)c0 * n_txps : nullptr;
     SparseBlock *blk = sink.blocks ? &(*sink.blocks)[g] : nullptr;
     oem_run_info *infos_g = infos ? infos + c0 : nullptr;
+    // the coverage model of the group's cells, computed on the device: the weights stay there for the store
+    ResidentCsr res_csr;
+    ResidentCsr *resident = nullptr;
+    if (cov_src) {
+        OEM_TRY(ensure_device(device));
+        OEM_TRY(cells_coverage_group(*cov_src, off_p, n_cells, c0, rp_p, tid_g, p_g, a0, n_reads, nnz, &res_csr));
+        resident = &res_csr;
+    }
 
     if (knob("OEM_SERIAL_CELLS", 0) == 0) { // testing build: force the cell-by-cell path
         bool used = false;
         int rcb = run_cells_batched(off_p, n_cells, rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device,
-                                    max_iter, conv_thresh, out_g, blk, infos_g, &used);
+                                    max_iter, conv_thresh, out_g, blk, infos_g, &used, resident);
         if (rcb != OEM_OK || used) return rcb;
     }
     // fallback (max_iter == 0, a single cell, or a group the tiler declines): cells one after another
@@ -426,7 +447,18 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
     oem_store_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.reorder_rows = 1; // cells are row ranges of the caller-order CSR
-    OEM_TRY(oem_store_create(rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device, &opts, &s));
+    if (resident) { // (the arrays were checked by the entry point; the store takes the resident CSR over)
+        OEM_TRY(ensure_device(device));
+        s = new (std::nothrow) oem_store();
+        if (!s) return fail(OEM_ERR_OOM, "oem_em_run_cells: host allocation failed");
+        const int rcs = create_store_impl(rp_p, tid_g, p_g, nullptr, n_reads, nnz, n_txps, device, &opts, s, nullptr, resident);
+        if (rcs != OEM_OK) {
+            free_store(s);
+            return rcs;
+        }
+    } else {
+        OEM_TRY(oem_store_create(rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device, &opts, &s));
+    }
     int rc = OEM_OK;
     NzScratch sc;
     CellsNzSource src; // the cell's count vector (s->cnt after the run, as copy_counts_out reads it), caller's transcript order
@@ -467,7 +499,7 @@ namespace {
 int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
               const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads, uint64_t nnz,
               uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink,
-              oem_run_info *infos)
+              oem_run_info *infos, CellsCoverage *cov_src = nullptr)
 {
     if (!cell_row_off || !row_ptr || (n_cells && !sink.dense && !sink.blocks)) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
     if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
@@ -482,6 +514,11 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     StageTimer tm_all;
     OEM_TRY(validate_csr(row_ptr, tid, n_reads, nnz, n_txps)); // all cells at once, on several host threads
     tm_all.lap("cells: range checks");
+    if (cov_src) { // the per-call part of the coverage model (the annotation), shared by the groups
+        OEM_TRY(ensure_device(device));
+        if (nnz) OEM_TRY(cells_coverage_setup(cov_src));
+        tm_all.lap("cells: coverage set-up");
+    }
     // a read with a NaN coverage probability is dropped (em.rs:115), on every path below: the batched
     // groups create their stores directly, not through oem_store_create
     std::vector<double> cov_fixed;
@@ -555,7 +592,7 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
                 const size_t g = next.fetch_add(1);
                 if (g >= groups.size() || failed.load()) break;
                 rcs[wk] = run_cells_group(cell_row_off, groups[g].first, groups[g].second, row_ptr, tid, as_prob, cov_prob,
-                                          n_txps, device, max_iter, conv_thresh, sink, g, infos);
+                                          cov_src, n_txps, device, max_iter, conv_thresh, sink, g, infos);
                 if (rcs[wk] != OEM_OK) break;
             }
         } catch (const std::exception &e) {
@@ -618,22 +655,21 @@ extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, 
     OEM_API_END("oem_em_run_cells")
 }
 
-extern "C" int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
-                                       const uint32_t *tid, const float *as_prob, const double *cov_prob,
-                                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
-                                       uint32_t max_iter, double conv_thresh, oem_cells_result **out)
+namespace {
+// The body of both sparse entry points: the groups' blocks become one oem_cells_result.
+int run_cells_sparse(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                     const uint32_t *tid, const float *as_prob, const double *cov_prob, CellsCoverage *cov_src,
+                     uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
+                     oem_cells_result **out)
 {
-    OEM_API_BEGIN
-    if (!out) return fail(OEM_ERR_ARG, "oem_em_run_cells_sparse: out is NULL");
-    *out = nullptr;
     std::unique_ptr<oem_cells_result> r(new oem_cells_result());
     r->n_cells = n_cells;
     r->infos.resize(n_cells);
     std::vector<SparseBlock> blocks;
     CellsSink sink;
     sink.blocks = &blocks;
-    OEM_TRY(run_cells("oem_em_run_cells_sparse", cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz,
-                      n_txps, device, max_iter, conv_thresh, sink, r->infos.data()));
+    OEM_TRY(run_cells(who, cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps, device, max_iter,
+                      conv_thresh, sink, r->infos.data(), cov_src));
     // the cells' offsets from the groups' blocks, in group (= cell) order
     r->cell_off.assign((size_t)n_cells + 1, 0);
     uint32_t c = 0;
@@ -646,14 +682,65 @@ extern "C" int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_
             ++c;
         }
         if (n != b.col.size() || n != b.val.size())
-            return fail(OEM_ERR_STATE, "oem_em_run_cells_sparse: a group's entries do not match its counts");
+            return fail(OEM_ERR_STATE, "%s: a group's entries do not match its counts", who);
     }
-    if (c != n_cells) return fail(OEM_ERR_STATE, "oem_em_run_cells_sparse: the groups' results cover %u of %u cells", c, n_cells);
+    if (c != n_cells) return fail(OEM_ERR_STATE, "%s: the groups' results cover %u of %u cells", who, c, n_cells);
     r->n_entries = r->cell_off[n_cells];
     r->blocks = std::move(blocks);
     *out = r.release();
     return OEM_OK;
+}
+} // namespace
+
+extern "C" int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                       const uint32_t *tid, const float *as_prob, const double *cov_prob,
+                                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
+                                       uint32_t max_iter, double conv_thresh, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    if (!out) return fail(OEM_ERR_ARG, "oem_em_run_cells_sparse: out is NULL");
+    *out = nullptr;
+    return run_cells_sparse("oem_em_run_cells_sparse", cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, nullptr,
+                            n_reads, nnz, n_txps, device, max_iter, conv_thresh, out);
     OEM_API_END("oem_em_run_cells_sparse")
+}
+
+// single_cell.rs:117-160 from the built store on: every cell's coverage model and its EM in one call.  Per group of
+// cells the caller's arrays go up once; the coverage column is computed and turned into the f64 weights on the device
+// and the group's store takes the buffers over, so neither the column nor the weights cross PCIe.
+extern "C" int oem_em_run_cells_coverage_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                                const uint32_t *tid, const float *as_prob, const uint32_t *aln_start,
+                                                const uint32_t *aln_end, const uint64_t *txp_len, uint64_t n_reads,
+                                                uint64_t nnz, uint32_t n_txps, uint32_t bin_width, int model,
+                                                double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+                                                double *out_cov_prob, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_em_run_cells_coverage_sparse";
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (!cell_row_off || !row_ptr || !txp_len || (nnz && (!tid || !as_prob || !aln_start || !aln_end)))
+        return fail(OEM_ERR_ARG, "%s: NULL argument", who);
+    if (bin_width == 0)
+        return fail(OEM_ERR_ARG, "coverage model with 0 bin width is not implemented (logistic_probability.rs:59, binomial_probability.rs:192)");
+    if (model != 0 && model != 1) return fail(OEM_ERR_ARG, "%s: model must be 0 (logistic) or 1 (binomial)", who);
+    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
+    if (n_txps >= (uint32_t)INT_MAX) return fail(OEM_ERR_ARG, "%s: needs n_txps < 2^31 - 1", who);
+    if (nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs nnz < 2^32", who);
+    if (n_reads >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs n_reads < 2^32", who);
+    // (run_cells checks cell_row_off and the CSR before any device work)
+    CellsCoverage cc;
+    cc.aln_start = aln_start;
+    cc.aln_end = aln_end;
+    cc.txp_len = txp_len;
+    cc.n_txps = n_txps;
+    cc.bin_width = bin_width;
+    cc.model = model;
+    cc.growth_rate = growth_rate;
+    cc.out_cov_prob = out_cov_prob;
+    return run_cells_sparse(who, cell_row_off, n_cells, row_ptr, tid, as_prob, nullptr, &cc, n_reads, nnz, n_txps, device,
+                            max_iter, conv_thresh, out);
+    OEM_API_END("oem_em_run_cells_coverage_sparse")
 }
 
 extern "C" int oem_cells_result_dims(const oem_cells_result *r, uint32_t *n_cells, uint64_t *n_entries)

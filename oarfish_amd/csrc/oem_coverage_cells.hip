@@ -16,6 +16,10 @@
 //                    sums and the running max are sequential in the reference, so they stay sequential here)
 //   k_cc_reads       one lane per read: per-alignment coverage probability through the segment id, normalised
 //
+// The same chunk body (run_chunk) serves oem_em_run_cells_coverage_sparse (cells_coverage_group): there a group of
+// the cells EM uploads its arrays once, runs the chunks over them, and k_cc_weights turns the column into the
+// store's f64 weights on the device.
+//
 // The dense slot table is chosen over a radix sort of (cell, tid) keys: its size is cells x T words, which on a
 // typical chunk (hundreds of thousands of alignments per cell over tens of thousands of transcripts) is several
 // times smaller than the nnz 64-bit keys and values a sort would move, and it needs one scan, not eight digit passes.
@@ -100,12 +104,12 @@ __global__ __launch_bounds__(kCC) void k_cc_reads(const uint32_t *__restrict__ r
                                                   const uint32_t *__restrict__ aln_end, const uint64_t *__restrict__ txp_len,
                                                   const uint32_t *__restrict__ n_bins, const unsigned long long *__restrict__ seg_off,
                                                   const uint32_t *__restrict__ seg_cell, const double *__restrict__ prob,
-                                                  uint32_t n_reads, double bin_length, double *__restrict__ out,
-                                                  uint32_t *__restrict__ err)
+                                                  uint32_t n_reads, uint32_t aln_base, double bin_length,
+                                                  double *__restrict__ out, uint32_t *__restrict__ err)
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_reads) return;
-    const uint32_t b = row_ptr[r], e = row_ptr[r + 1];
+    const uint32_t b = row_ptr[r] - aln_base, e = row_ptr[r + 1] - aln_base; // (row_ptr: relative to the resident arrays)
     if (b == e) return;
     cov_normalize_read(b, e, aln_start, aln_end, bin_length,
                        [&](uint64_t j) {
@@ -113,6 +117,21 @@ __global__ __launch_bounds__(kCC) void k_cc_reads(const uint32_t *__restrict__ r
                            return CovTxpBins{prob + seg_off[seg[j]], n_bins[t], (double)txp_len[t]};
                        },
                        out, err + seg_cell[seg[b]]);
+}
+
+// em.rs:107-111's iteration-invariant factor w = (p as f64) * cov of every alignment, the expression of upload_csr, so
+// the stream is bit-identical to the one a host coverage column gives.  A read with a NaN coverage (the 0/0 of a
+// zero-span alignment) gets w = p * 0 on every alignment, as zero_nan_rows leaves it: the EM drops it (em.rs:115).
+__global__ __launch_bounds__(kCC) void k_cc_weights(const uint32_t *__restrict__ row_ptr, const float *__restrict__ p,
+                                                    const double *__restrict__ cov, uint32_t n_reads,
+                                                    double *__restrict__ w)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const uint32_t b = row_ptr[r], e = row_ptr[r + 1];
+    bool nan = false;
+    for (uint32_t j = b; j < e; ++j) nan |= cov[j] != cov[j];
+    for (uint32_t j = b; j < e; ++j) w[j] = (double)p[j] * (nan ? 0.0 : cov[j]);
 }
 
 // The checks oem_coverage_probs_device makes on every transcript of the annotation, touched or not: they fail any
@@ -177,7 +196,239 @@ struct Chunk {
     uint64_t a0, a1;     // alignments
 };
 
+// Cuts cells [0, n_cells) into chunks of consecutive cells that fit `budget_bytes` (and the testing build's bin
+// budget).  A cell's bins are bounded by every transcript's bins and by one new segment of the widest transcript per
+// alignment; its other buffers are known from its size (`per_aln`, `per_read`: the bytes a chunk holds for each of its
+// alignments and reads besides the slot table, segments and bins).
+std::vector<Chunk> plan_chunks(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr, uint32_t n_txps,
+                               uint64_t all_bins, uint64_t max_nb, uint64_t budget_bytes, uint64_t per_aln, uint64_t per_read)
+{
+    const uint64_t budget_bins = (uint64_t)knob("OEM_COV_CELLS_CHUNK_BINS", 0); // testing build: force small chunks
+    std::vector<Chunk> chunks;
+    Chunk ch{0, 0, cell_row_off[0], cell_row_off[0], row_ptr[cell_row_off[0]], row_ptr[cell_row_off[0]]};
+    uint64_t bins = 0, bytes = 0;
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        const uint64_t reads = cell_row_off[c + 1] - cell_row_off[c];
+        const uint64_t a = row_ptr[cell_row_off[c + 1]] - row_ptr[cell_row_off[c]];
+        const uint64_t ub = std::min(all_bins, a * max_nb);
+        const uint64_t by = 16 * ub + 8 * (uint64_t)n_txps + 28 * std::min<uint64_t>(a, n_txps) + per_aln * a + per_read * reads + 8;
+        const bool full = ch.c1 > ch.c0 &&
+                          (bytes + by > budget_bytes || (budget_bins && bins + ub > budget_bins) ||
+                           (uint64_t)(ch.c1 - ch.c0 + 1) * n_txps + 1 > (uint64_t)INT_MAX);
+        if (full) {
+            chunks.push_back(ch);
+            ch = Chunk{c, c, ch.r1, ch.r1, ch.a1, ch.a1};
+            bins = bytes = 0;
+        }
+        ch.c1 = c + 1;
+        ch.r1 += reads;
+        ch.a1 += a;
+        bins += ub;
+        bytes += by;
+    }
+    if (ch.c1 > ch.c0) chunks.push_back(ch);
+    return chunks;
+}
+
+// The device buffers of the per-chunk steps, sized for the largest chunk (bins and probabilities grow on demand).
+struct ChunkBufs {
+    uint32_t *key, *coff, *flag, *pos, *seg_tid, *seg_cell, *tw, *err;
+    unsigned long long *seg_nb, *seg_off;
+    double *bins = nullptr, *prob = nullptr;
+    size_t cap_bins = 0, cap_prob = 0;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+};
+
+int alloc_chunk_bufs(hipStream_t st, Arena &ar, const std::vector<Chunk> &chunks, uint32_t n_txps, ChunkBufs *b)
+{
+    uint64_t max_cells = 0, max_aln = 0;
+    for (const Chunk &ch : chunks) {
+        max_cells = std::max<uint64_t>(max_cells, ch.c1 - ch.c0);
+        max_aln = std::max(max_aln, ch.a1 - ch.a0);
+    }
+    const uint64_t max_slots = max_cells * n_txps + 1;
+    const uint64_t max_segs = std::min<uint64_t>(max_slots - 1, max_aln) + 1;
+    OEM_TRY(ar.get(&b->key, max_aln));
+    OEM_TRY(ar.get(&b->coff, max_cells + 1));
+    OEM_TRY(ar.get(&b->err, max_cells));
+    OEM_TRY(ar.get(&b->flag, max_slots));
+    OEM_TRY(ar.get(&b->pos, max_slots));
+    OEM_TRY(ar.get(&b->seg_tid, max_segs));
+    OEM_TRY(ar.get(&b->seg_cell, max_segs));
+    OEM_TRY(ar.get(&b->tw, max_segs));
+    OEM_TRY(ar.get(&b->seg_nb, max_segs));
+    OEM_TRY(ar.get(&b->seg_off, max_segs));
+    size_t t1 = 0, t2 = 0;
+    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, b->flag, b->pos, (int)max_slots, st));
+    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, b->seg_nb, b->seg_off, (int)max_segs, st));
+    b->tmp_bytes = std::max(t1, t2);
+    OEM_TRY(ar.get((char **)&b->tmp, b->tmp_bytes));
+    return OEM_OK;
+}
+
+// The coverage of one chunk of `ncc` cells whose alignments are [0, na) of tid / start / end / out and whose reads are
+// [0, nr) of row_ptr (values relative to `aln_base` before it); h_coff: the cells' alignment offsets relative to the
+// chunk.  On return h_err[0, ncc) holds every cell's error bits (the annotation-wide ones not included).
+int run_chunk(hipStream_t st, Arena &ar, ChunkBufs &b, const uint64_t *d_len, const uint32_t *d_nb, uint32_t n_txps,
+              uint32_t bin_width, int model, double growth_rate, uint32_t ncc, uint32_t nr, uint32_t na,
+              const uint32_t *h_coff, const uint32_t *d_rp, uint32_t aln_base, const uint32_t *d_tid,
+              const uint32_t *d_start, const uint32_t *d_end, double *d_out, uint32_t *h_err)
+{
+    const uint32_t n_slots = ncc * n_txps;
+    OEM_HIP(hipMemcpyAsync(b.coff, h_coff, sizeof(uint32_t) * (ncc + 1), hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemsetAsync(b.flag, 0, sizeof(uint32_t) * ((size_t)n_slots + 1), st));
+    OEM_HIP(hipMemsetAsync(b.err, 0, sizeof(uint32_t) * ncc, st));
+    const dim3 ag((uint32_t)(((uint64_t)na + kCC - 1) / kCC));
+    if (na) hipLaunchKernelGGL(k_cc_mark, ag, dim3(kCC), 0, st, d_tid, b.coff, ncc, n_txps, na, b.key, b.flag);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(b.tmp, b.tmp_bytes, b.flag, b.pos, (int)n_slots + 1, st));
+    uint32_t n_segs = 0;
+    OEM_HIP(hipMemcpyAsync(&n_segs, b.pos + n_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    OEM_HIP(hipStreamSynchronize(st));
+    if (n_segs == 0) { // the chunk's cells have no alignments
+        std::fill(h_err, h_err + ncc, 0u);
+        return OEM_OK;
+    }
+    hipLaunchKernelGGL(k_cc_segments, dim3((n_slots + kCC - 1) / kCC), dim3(kCC), 0, st, b.flag, b.pos, n_slots, n_txps,
+                       d_nb, b.seg_tid, b.seg_cell, b.seg_nb);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemsetAsync(b.seg_nb + n_segs, 0, sizeof(unsigned long long), st));
+    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(b.tmp, b.tmp_bytes, b.seg_nb, b.seg_off, (int)n_segs + 1, st));
+    unsigned long long n_bins = 0;
+    OEM_HIP(hipMemcpyAsync(&n_bins, b.seg_off + n_segs, sizeof(n_bins), hipMemcpyDeviceToHost, st));
+    OEM_HIP(hipStreamSynchronize(st));
+    OEM_TRY(ar.grow(&b.bins, &b.cap_bins, n_bins));
+    OEM_TRY(ar.grow(&b.prob, &b.cap_prob, n_bins));
+    OEM_HIP(hipMemsetAsync(b.bins, 0, sizeof(double) * (n_bins ? n_bins : 1), st));
+    OEM_HIP(hipMemsetAsync(b.tw, 0, sizeof(uint32_t) * n_segs, st));
+    hipLaunchKernelGGL(k_cc_bins, ag, dim3(kCC), 0, st, b.key, b.pos, d_tid, d_start, d_end, d_len, d_nb, b.seg_off,
+                       b.seg_cell, na, b.bins, b.tw, b.err);
+    hipLaunchKernelGGL(k_cc_bin_probs, dim3((n_segs + kCC - 1) / kCC), dim3(kCC), 0, st, d_len, b.seg_tid, b.seg_cell,
+                       b.seg_off, b.tw, n_segs, model, growth_rate, b.bins, b.prob, b.err);
+    if (nr)
+        hipLaunchKernelGGL(k_cc_reads, dim3((uint32_t)(((uint64_t)nr + kCC - 1) / kCC)), dim3(kCC), 0, st, d_rp, b.key, d_tid,
+                           d_start, d_end, d_len, d_nb, b.seg_off, b.seg_cell, b.prob, nr, aln_base, (double)bin_width,
+                           d_out, b.err);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpyAsync(h_err, b.err, sizeof(uint32_t) * ncc, hipMemcpyDeviceToHost, st));
+    OEM_HIP(hipStreamSynchronize(st));
+    return OEM_OK;
+}
+
+// txp_len and the per-transcript bin counts on the device, and the checks every transcript must pass
+int setup_txps(hipStream_t st, const uint64_t *txp_len, uint32_t n_txps, uint32_t bin_width, uint64_t *d_len,
+               uint32_t *d_nb, uint32_t *d_gerr, uint32_t *h_gerr)
+{
+    OEM_HIP(hipMemcpyAsync(d_len, txp_len, sizeof(uint64_t) * n_txps, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemsetAsync(d_gerr, 0, sizeof(uint32_t), st));
+    const uint32_t tg = (n_txps + kCC - 1) / kCC;
+    hipLaunchKernelGGL(k_cc_bin_counts, dim3(tg), dim3(kCC), 0, st, d_len, n_txps, bin_width, d_nb);
+    hipLaunchKernelGGL(k_cc_txp_check, dim3(tg), dim3(kCC), 0, st, d_len, d_nb, n_txps, d_gerr);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpyAsync(h_gerr, d_gerr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return OEM_OK;
+}
+
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard()
+    {
+        if (!s) return;
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+};
+
 } // namespace
+
+int cells_coverage_setup(CellsCoverage *cc)
+{
+    uint64_t all_bins = 0, max_nb = 0;
+    for (uint32_t t = 0; t < cc->n_txps; ++t) {
+        const uint64_t nb = cov_n_bins(cc->txp_len[t], cc->bin_width);
+        all_bins += nb;
+        max_nb = std::max(max_nb, nb);
+    }
+    cc->all_bins = all_bins;
+    cc->max_nb = max_nb;
+    StreamGuard sg;
+    OEM_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    Arena ar;
+    uint32_t *d_gerr;
+    OEM_TRY(ar.get(&d_gerr, 1));
+    OEM_TRY(dev_alloc(&cc->d_len, cc->n_txps, nullptr));
+    OEM_TRY(dev_alloc(&cc->d_nb, cc->n_txps, nullptr));
+    OEM_TRY(setup_txps(sg.s, cc->txp_len, cc->n_txps, cc->bin_width, cc->d_len, cc->d_nb, d_gerr, &cc->gerr));
+    OEM_HIP(hipStreamSynchronize(sg.s));
+    return OEM_OK;
+}
+
+int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, uint32_t n_cells, uint32_t first_cell,
+                         const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob, uint64_t aln_base,
+                         uint64_t n_reads, uint64_t nnz, ResidentCsr *out)
+{
+    StageTimer tm;
+    const char *who = "oem_em_run_cells_coverage_sparse";
+    StreamGuard sg;
+    OEM_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
+    // 1. what the store keeps (caller order: row pointers narrowed on the device, ids, the weights written below)
+    OEM_TRY(dev_alloc(&out->row_ptr, n_reads + 1, nullptr));
+    OEM_TRY(dev_alloc(&out->tid, nnz, nullptr));
+    OEM_TRY(dev_alloc(&out->w64, nnz, nullptr));
+    OEM_TRY(upload_row_ptr_u32(st, row_ptr, n_reads + 1, out->row_ptr));
+    if (nnz == 0) return OEM_OK;
+    OEM_HIP(hipMemcpyAsync(out->tid, tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    // the coverage scratch: released when this scope ends, before the store's layout is built
+    Arena ar;
+    uint32_t *d_start, *d_end;
+    float *d_p;
+    double *d_cov;
+    OEM_TRY(ar.get(&d_start, nnz));
+    OEM_TRY(ar.get(&d_end, nnz));
+    OEM_TRY(ar.get(&d_p, nnz));
+    OEM_TRY(ar.get(&d_cov, nnz));
+    OEM_HIP(hipMemcpyAsync(d_start, cc.aln_start + aln_base, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_end, cc.aln_end + aln_base, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_p, as_prob, sizeof(float) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipStreamSynchronize(st));
+    tm.lap("cov+em: group upload");
+
+    // 2. coverage, in sub-chunks of consecutive cells over the resident arrays when the slot tables and bins of all
+    // of them do not fit half the free memory
+    size_t free_b = 0, total_b = 0;
+    OEM_HIP(hipMemGetInfo(&free_b, &total_b));
+    const std::vector<Chunk> chunks = plan_chunks(cell_row_off, n_cells, row_ptr, cc.n_txps, cc.all_bins, cc.max_nb,
+                                                  free_b / 2, 4 /* segment ids */, 0);
+    ChunkBufs b;
+    OEM_TRY(alloc_chunk_bufs(st, ar, chunks, cc.n_txps, &b));
+    std::vector<uint32_t> h_coff, h_err;
+    for (const Chunk &ch : chunks) {
+        const uint32_t ncc = ch.c1 - ch.c0;
+        h_coff.resize((size_t)ncc + 1);
+        h_err.resize(ncc);
+        for (uint32_t c = 0; c <= ncc; ++c) h_coff[c] = (uint32_t)(row_ptr[cell_row_off[ch.c0 + c]] - ch.a0);
+        OEM_TRY(run_chunk(st, ar, b, cc.d_len, cc.d_nb, cc.n_txps, cc.bin_width, cc.model, cc.growth_rate, ncc,
+                          (uint32_t)(ch.r1 - ch.r0), (uint32_t)(ch.a1 - ch.a0), h_coff.data(), out->row_ptr + ch.r0,
+                          (uint32_t)ch.a0, out->tid + ch.a0, d_start + ch.a0, d_end + ch.a0, d_cov + ch.a0, h_err.data()));
+        for (uint32_t c = 0; c < ncc; ++c) {
+            const uint32_t f = h_err[c] | (h_coff[c + 1] > h_coff[c] ? cc.gerr : 0u);
+            if (f) return fail(OEM_ERR_STATE, "%s: cell %u: %s", who, first_cell + ch.c0 + c, cov_err_text(f));
+        }
+    }
+    tm.lap("cov+em: coverage");
+    // 3. the column the EM uses, for the caller who asked for it; the weights straight into the store's buffer
+    if (cc.out_cov_prob)
+        OEM_HIP(hipMemcpyAsync(cc.out_cov_prob + aln_base, d_cov, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_cc_weights, dim3((uint32_t)((n_reads + kCC - 1) / kCC)), dim3(kCC), 0, st, out->row_ptr, d_p, d_cov,
+                       (uint32_t)n_reads, out->w64);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(st));
+    tm.lap("cov+em: weights");
+    return OEM_OK;
+}
+
 } // namespace oem
 
 using namespace oem;
@@ -213,146 +464,61 @@ extern "C" int oem_coverage_probs_cells_device(const uint64_t *cell_row_off, uin
     OEM_HIP(hipSetDevice(device));
     if (nnz == 0) return OEM_OK;
 
-    // ---- chunks of consecutive cells.  A cell's bins are bounded by every transcript's bins and by one new
-    // segment of the widest transcript per alignment; its other buffers are known from its size.
-    std::vector<uint32_t> h_nb(n_txps);
+    // ---- chunks of consecutive cells that fit half the free HBM
     uint64_t all_bins = 0, max_nb = 0;
     for (uint32_t t = 0; t < n_txps; ++t) {
-        h_nb[t] = cov_n_bins(txp_len[t], bin_width);
-        all_bins += h_nb[t];
-        max_nb = std::max<uint64_t>(max_nb, h_nb[t]);
+        const uint64_t nb = cov_n_bins(txp_len[t], bin_width);
+        all_bins += nb;
+        max_nb = std::max(max_nb, nb);
     }
     size_t free_b = 0, total_b = 0;
     OEM_HIP(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t budget_bytes = free_b / 2;
-    const uint64_t budget_bins = (uint64_t)knob("OEM_COV_CELLS_CHUNK_BINS", 0); // testing build: force small chunks
-    std::vector<Chunk> chunks;
-    {
-        Chunk ch{0, 0, 0, 0, 0, 0};
-        uint64_t bins = 0, bytes = 0;
-        for (uint32_t c = 0; c < n_cells; ++c) {
-            const uint64_t reads = cell_row_off[c + 1] - cell_row_off[c];
-            const uint64_t a = row_ptr[cell_row_off[c + 1]] - row_ptr[cell_row_off[c]];
-            const uint64_t ub = std::min(all_bins, a * max_nb);
-            const uint64_t by = 16 * ub + 8 * (uint64_t)n_txps + 28 * std::min<uint64_t>(a, n_txps) + 24 * a + 4 * reads + 8;
-            const bool full = ch.c1 > ch.c0 &&
-                              (bytes + by > budget_bytes || (budget_bins && bins + ub > budget_bins) ||
-                               (uint64_t)(ch.c1 - ch.c0 + 1) * n_txps + 1 > (uint64_t)INT_MAX);
-            if (full) {
-                chunks.push_back(ch);
-                ch = Chunk{c, c, ch.r1, ch.r1, ch.a1, ch.a1};
-                bins = bytes = 0;
-            }
-            ch.c1 = c + 1;
-            ch.r1 += reads;
-            ch.a1 += a;
-            bins += ub;
-            bytes += by;
-        }
-        if (ch.c1 > ch.c0) chunks.push_back(ch);
-    }
+    // (per alignment: id, start, end, segment id, f64 result; per read: a u32 row pointer)
+    const std::vector<Chunk> chunks = plan_chunks(cell_row_off, n_cells, row_ptr, n_txps, all_bins, max_nb, free_b / 2, 24, 4);
     uint64_t max_cells = 0, max_reads = 0, max_aln = 0;
     for (const Chunk &ch : chunks) {
         max_cells = std::max<uint64_t>(max_cells, ch.c1 - ch.c0);
         max_reads = std::max(max_reads, ch.r1 - ch.r0);
         max_aln = std::max(max_aln, ch.a1 - ch.a0);
     }
-    const uint64_t max_slots = max_cells * n_txps + 1;
-    const uint64_t max_segs = std::min<uint64_t>(max_slots - 1, max_aln) + 1;
     tm.lap("cov cells: plan");
 
-    hipStream_t st = nullptr;
-    OEM_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    struct StreamGuard {
-        hipStream_t s;
-        ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    } sg{st};
+    StreamGuard sg;
+    OEM_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
     Arena ar;
-    uint32_t *d_nb, *d_tid, *d_start, *d_end, *d_key, *d_rp, *d_coff, *d_flag, *d_pos, *d_seg_tid, *d_seg_cell, *d_tw, *d_err,
-        *d_gerr;
+    uint32_t *d_nb, *d_tid, *d_start, *d_end, *d_rp, *d_gerr;
     uint64_t *d_len;
-    unsigned long long *d_seg_nb, *d_seg_off;
-    double *d_out, *d_bins = nullptr, *d_prob = nullptr;
-    size_t cap_bins = 0, cap_prob = 0;
+    double *d_out;
     OEM_TRY(ar.get(&d_len, n_txps));
     OEM_TRY(ar.get(&d_nb, n_txps));
     OEM_TRY(ar.get(&d_gerr, 1));
     OEM_TRY(ar.get(&d_tid, max_aln));
     OEM_TRY(ar.get(&d_start, max_aln));
     OEM_TRY(ar.get(&d_end, max_aln));
-    OEM_TRY(ar.get(&d_key, max_aln));
     OEM_TRY(ar.get(&d_out, max_aln));
     OEM_TRY(ar.get(&d_rp, max_reads + 1));
-    OEM_TRY(ar.get(&d_coff, max_cells + 1));
-    OEM_TRY(ar.get(&d_err, max_cells));
-    OEM_TRY(ar.get(&d_flag, max_slots));
-    OEM_TRY(ar.get(&d_pos, max_slots));
-    OEM_TRY(ar.get(&d_seg_tid, max_segs));
-    OEM_TRY(ar.get(&d_seg_cell, max_segs));
-    OEM_TRY(ar.get(&d_tw, max_segs));
-    OEM_TRY(ar.get(&d_seg_nb, max_segs));
-    OEM_TRY(ar.get(&d_seg_off, max_segs));
-    size_t tmp_bytes = 0, tmp2 = 0;
-    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_pos, (int)max_slots, st));
-    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, d_seg_nb, d_seg_off, (int)max_segs, st));
-    void *d_tmp;
-    OEM_TRY(ar.get((char **)&d_tmp, std::max(tmp_bytes, tmp2)));
-    tmp_bytes = std::max(tmp_bytes, tmp2);
-
-    OEM_HIP(hipMemcpyAsync(d_len, txp_len, sizeof(uint64_t) * n_txps, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemsetAsync(d_gerr, 0, sizeof(uint32_t), st));
-    const uint32_t tg = (n_txps + kCC - 1) / kCC;
-    hipLaunchKernelGGL(k_cc_bin_counts, dim3(tg), dim3(kCC), 0, st, d_len, n_txps, bin_width, d_nb);
-    hipLaunchKernelGGL(k_cc_txp_check, dim3(tg), dim3(kCC), 0, st, d_len, d_nb, n_txps, d_gerr);
-    OEM_HIP(hipGetLastError());
+    ChunkBufs b;
+    OEM_TRY(alloc_chunk_bufs(st, ar, chunks, n_txps, &b));
     uint32_t h_gerr = 0;
-    OEM_HIP(hipMemcpyAsync(&h_gerr, d_gerr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    OEM_TRY(setup_txps(st, txp_len, n_txps, bin_width, d_len, d_nb, d_gerr, &h_gerr));
 
     std::vector<uint32_t> h_rp(max_reads + 1), h_coff(max_cells + 1), h_err(max_cells);
     for (const Chunk &ch : chunks) {
         const uint32_t ncc = ch.c1 - ch.c0;
         const uint32_t nr = (uint32_t)(ch.r1 - ch.r0), na = (uint32_t)(ch.a1 - ch.a0);
-        const uint32_t n_slots = ncc * n_txps;
         for (uint32_t c = 0; c <= ncc; ++c) h_coff[c] = (uint32_t)(row_ptr[cell_row_off[ch.c0 + c]] - ch.a0);
         for (uint64_t r = 0; r <= nr; ++r) h_rp[r] = (uint32_t)(row_ptr[ch.r0 + r] - ch.a0);
-        OEM_HIP(hipMemcpyAsync(d_coff, h_coff.data(), sizeof(uint32_t) * (ncc + 1), hipMemcpyHostToDevice, st));
         OEM_HIP(hipMemcpyAsync(d_rp, h_rp.data(), sizeof(uint32_t) * ((size_t)nr + 1), hipMemcpyHostToDevice, st));
         OEM_HIP(hipMemcpyAsync(d_tid, tid + ch.a0, sizeof(uint32_t) * (size_t)na, hipMemcpyHostToDevice, st));
         OEM_HIP(hipMemcpyAsync(d_start, aln_start + ch.a0, sizeof(uint32_t) * (size_t)na, hipMemcpyHostToDevice, st));
         OEM_HIP(hipMemcpyAsync(d_end, aln_end + ch.a0, sizeof(uint32_t) * (size_t)na, hipMemcpyHostToDevice, st));
-        OEM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t) * ((size_t)n_slots + 1), st));
-        OEM_HIP(hipMemsetAsync(d_err, 0, sizeof(uint32_t) * ncc, st));
-        const dim3 ag((uint32_t)(((uint64_t)na + kCC - 1) / kCC));
-        if (na) hipLaunchKernelGGL(k_cc_mark, ag, dim3(kCC), 0, st, d_tid, d_coff, ncc, n_txps, na, d_key, d_flag);
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos, (int)n_slots + 1, st));
-        uint32_t n_segs = 0;
-        OEM_HIP(hipMemcpyAsync(&n_segs, d_pos + n_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        OEM_HIP(hipStreamSynchronize(st));
-        if (n_segs == 0) continue; // the chunk's cells have no alignments
-        hipLaunchKernelGGL(k_cc_segments, dim3((n_slots + kCC - 1) / kCC), dim3(kCC), 0, st, d_flag, d_pos, n_slots, n_txps,
-                           d_nb, d_seg_tid, d_seg_cell, d_seg_nb);
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemsetAsync(d_seg_nb + n_segs, 0, sizeof(unsigned long long), st));
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_seg_nb, d_seg_off, (int)n_segs + 1, st));
-        unsigned long long n_bins = 0;
-        OEM_HIP(hipMemcpyAsync(&n_bins, d_seg_off + n_segs, sizeof(n_bins), hipMemcpyDeviceToHost, st));
-        OEM_HIP(hipStreamSynchronize(st));
-        OEM_TRY(ar.grow(&d_bins, &cap_bins, n_bins));
-        OEM_TRY(ar.grow(&d_prob, &cap_prob, n_bins));
-        OEM_HIP(hipMemsetAsync(d_bins, 0, sizeof(double) * (n_bins ? n_bins : 1), st));
-        OEM_HIP(hipMemsetAsync(d_tw, 0, sizeof(uint32_t) * n_segs, st));
-        hipLaunchKernelGGL(k_cc_bins, ag, dim3(kCC), 0, st, d_key, d_pos, d_tid, d_start, d_end, d_len, d_nb, d_seg_off,
-                           d_seg_cell, na, d_bins, d_tw, d_err);
-        hipLaunchKernelGGL(k_cc_bin_probs, dim3((n_segs + kCC - 1) / kCC), dim3(kCC), 0, st, d_len, d_seg_tid, d_seg_cell,
-                           d_seg_off, d_tw, n_segs, model, growth_rate, d_bins, d_prob, d_err);
-        if (nr)
-            hipLaunchKernelGGL(k_cc_reads, dim3((uint32_t)(((uint64_t)nr + kCC - 1) / kCC)), dim3(kCC), 0, st, d_rp, d_key, d_tid, d_start, d_end,
-                               d_len, d_nb, d_seg_off, d_seg_cell, d_prob, nr, (double)bin_width, d_out, d_err);
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpyAsync(h_err.data(), d_err, sizeof(uint32_t) * ncc, hipMemcpyDeviceToHost, st));
-        OEM_HIP(hipMemcpyAsync(out_cov_prob + ch.a0, d_out, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, st));
-        OEM_HIP(hipStreamSynchronize(st));
+        OEM_TRY(run_chunk(st, ar, b, d_len, d_nb, n_txps, bin_width, model, growth_rate, ncc, nr, na, h_coff.data(), d_rp, 0,
+                          d_tid, d_start, d_end, d_out, h_err.data()));
+        if (na) {
+            OEM_HIP(hipMemcpyAsync(out_cov_prob + ch.a0, d_out, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, st));
+            OEM_HIP(hipStreamSynchronize(st));
+        }
         for (uint32_t c = 0; c < ncc; ++c) {
             const bool has_aln = h_coff[c + 1] > h_coff[c];
             const uint32_t f = h_err[c] | (has_aln ? h_gerr : 0u);

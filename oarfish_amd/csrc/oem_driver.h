@@ -53,10 +53,60 @@ struct CellRelabel {
     uint32_t n_cells;
     uint32_t cell_txps;
 };
+// A caller-order CSR already resident on the device (u32 row pointers, transcript ids, f64 weights w = p * cov): a
+// store created from it takes the buffers over (nulls them here) instead of uploading the caller's arrays.  Whatever
+// is still held here is freed with it.
+struct ResidentCsr {
+    uint32_t *row_ptr = nullptr;
+    uint32_t *tid = nullptr;
+    double *w64 = nullptr;
+    ResidentCsr() = default;
+    ResidentCsr(const ResidentCsr &) = delete;
+    ResidentCsr &operator=(const ResidentCsr &) = delete;
+    ~ResidentCsr()
+    {
+        (void)hipFree(row_ptr);
+        (void)hipFree(tid);
+        (void)hipFree(w64);
+    }
+};
 int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob, const double *cov_prob,
                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, const oem_store_opts *opts, oem_store *s,
-                      const CellRelabel *relabel = nullptr);
+                      const CellRelabel *relabel = nullptr, ResidentCsr *resident = nullptr);
 void free_store(oem_store *s);
+// u64 row pointers (host) -> u32 ones on the device, through a temporary u64 copy (no second host array)
+int upload_row_ptr_u32(hipStream_t st, const uint64_t *row_ptr, uint64_t n, uint32_t *d_out);
+
+// oem_coverage_cells.hip: the per-cell coverage model as the source of a cells EM's weights
+// (oem_em_run_cells_coverage_sparse).  What the groups share is set up once per call; each group then computes its
+// cells' coverage on the device from its own resident arrays and leaves the weights in a ResidentCsr.
+struct CellsCoverage {
+    const uint32_t *aln_start = nullptr, *aln_end = nullptr; // host, caller order
+    const uint64_t *txp_len = nullptr;                       // host, n_txps
+    uint32_t n_txps = 0, bin_width = 0;
+    int model = 1;
+    double growth_rate = 2.0;
+    double *out_cov_prob = nullptr; // host, nnz, or NULL
+    // set up by cells_coverage_setup
+    uint64_t *d_len = nullptr;
+    uint32_t *d_nb = nullptr;
+    uint32_t gerr = 0; // the annotation-wide checks: they fail every cell with alignments
+    uint64_t all_bins = 0, max_nb = 0;
+    CellsCoverage() = default;
+    CellsCoverage(const CellsCoverage &) = delete;
+    CellsCoverage &operator=(const CellsCoverage &) = delete;
+    ~CellsCoverage()
+    {
+        (void)hipFree(d_len);
+        (void)hipFree(d_nb);
+    }
+};
+int cells_coverage_setup(CellsCoverage *cc);
+// Cells [0, n_cells) of a group (first_cell: the first one's index in the call, for messages); row_ptr and
+// cell_row_off relative to the group, tid / as_prob / aln_base: the group's first alignment is aln_base of the call.
+int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, uint32_t n_cells, uint32_t first_cell,
+                         const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob, uint64_t aln_base,
+                         uint64_t n_reads, uint64_t nnz, ResidentCsr *out);
 
 // oem_em_driver.hip: one EM run with the loop state on the device
 struct RunArgs {

@@ -120,6 +120,12 @@ def em_cells_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, as_probabi
         ref_ids.ctypes.data if nnz else None, as_probabilities.ctypes.data if nnz else None,
         None if cov is None else cov.ctypes.data, n_reads, nnz, n_txps, device, max_iter,
         convergence_thresh, C.byref(res)))
+    return _take_cells_result(res, n_cells)
+
+
+def _take_cells_result(res, n_cells):
+    """(indptr, cols, vals, [RunInfo]) of an ``oem_cells_result`` handle, which is released."""
+    L = _lib.lib()
     try:
         nc, ne = C.c_uint32(0), C.c_uint64(0)
         _lib.check(L.oem_cells_result_dims(res, C.byref(nc), C.byref(ne)))
@@ -170,6 +176,43 @@ def cells_coverage_probs(cell_row_off: Sequence[int], boundaries, ref_ids, aln_s
         aln_end.ctypes.data if nnz else None, txp_len.ctypes.data, len(boundaries) - 1, nnz, len(txp_len),
         bin_width, _COVERAGE_MODELS[model], growth_rate, device, out.ctypes.data if nnz else None))
     return out
+
+
+def em_cells_coverage_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, as_probabilities, aln_start, aln_end,
+                             txp_len, bin_width: int = 100, model: str = "binomial", growth_rate: float = 2.0,
+                             max_iter: int = 1000, convergence_thresh: float = 1e-3, device: int = 0,
+                             return_coverage: bool = False):
+    """A single-cell ``--model-coverage`` run from the built store on, in one device call
+    (single_cell.rs:117-160): every cell's own coverage model, then its EM, the entries ``v > 0`` kept.
+
+    The result equals ``cells_coverage_probs`` on the same arguments followed by ``em_cells_sparse`` on that
+    column, ``n_txps = len(txp_len)``; the column and the EM's weights stay on the device.  Returns
+    ``(indptr, cols, vals, [RunInfo])`` as ``em_cells_sparse`` does, and with ``return_coverage`` also the
+    nnz f64 coverage column the EM used (NaN for a zero-span alignment, whose read the EM drops).
+    """
+    if model not in _COVERAGE_MODELS:
+        raise ValueError(f"model must be one of {sorted(_COVERAGE_MODELS)}, not {model!r}")
+    cell_row_off = np.ascontiguousarray(cell_row_off, dtype=np.uint64)
+    boundaries = np.ascontiguousarray(boundaries, dtype=np.uint64)
+    ref_ids = np.ascontiguousarray(ref_ids, dtype=np.uint32)
+    as_probabilities = np.ascontiguousarray(as_probabilities, dtype=np.float32)
+    aln_start = np.ascontiguousarray(aln_start, dtype=np.uint32)
+    aln_end = np.ascontiguousarray(aln_end, dtype=np.uint32)
+    txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+    nnz = len(ref_ids)
+    if len(aln_start) != nnz or len(aln_end) != nnz or len(as_probabilities) != nnz:
+        raise ValueError("ref_ids, as_probabilities, aln_start and aln_end must have one entry per alignment")
+    n_cells = len(cell_row_off) - 1
+    cov = np.empty(nnz, dtype=np.float64) if return_coverage else None
+    res = C.c_void_p()
+    _lib.check(_lib.lib().oem_em_run_cells_coverage_sparse(
+        cell_row_off.ctypes.data, n_cells, boundaries.ctypes.data,
+        ref_ids.ctypes.data if nnz else None, as_probabilities.ctypes.data if nnz else None,
+        aln_start.ctypes.data if nnz else None, aln_end.ctypes.data if nnz else None, txp_len.ctypes.data,
+        len(boundaries) - 1, nnz, len(txp_len), bin_width, _COVERAGE_MODELS[model], growth_rate, device, max_iter,
+        convergence_thresh, cov.ctypes.data if cov is not None and nnz else None, C.byref(res)))
+    out = _take_cells_result(res, n_cells)
+    return (*out, cov) if return_coverage else out
 
 
 def cells_last_timing():
