@@ -38,7 +38,8 @@ extern "C" {
  *    default, as before), the peer-to-peer communicator entry points (oem_comm_p2p_*), oem_store_info; version 1
  *    callers keep working (additions only).  Later additions under the same number: the sparse per-cell results
  *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy), the per-cell coverage model
- *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse). */
+ *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse), the bulk coverage model
+ *    and the store on its column in one call (oem_store_create_coverage, oem_builder_store_create_coverage). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -88,7 +89,11 @@ typedef struct {
                               with a coverage column: the static weight (p as f64) * cov (em.rs:107-111) is rounded
                               once to f32 (relative error <= 6e-8 per weight, against the 1e-4 the abundances are held
                               to) and the store streams 8 B per alignment through the f32 kernels instead of 12 through
-                              the f64 ones; all arithmetic of the EM stays f64.  Without cov_prob: the same as 0 */
+                              the f64 ones; all arithmetic of the EM stays f64.  Without cov_prob: the same as 0.
+                              Underflow: a product below 1.2e-38 (FLT_MIN) is stored as an f32 subnormal, with fewer
+                              significant bits; one below 1.4e-45 (FLT_TRUE_MIN, half of it rounding to nearest) becomes
+                              0, so a read whose products all do has denominator 0 and is dropped by the EM's
+                              `denom > 1e-30` test (em.rs:115) where the f64 store would keep it */
     uint32_t reserved[3];
 } oem_store_opts;
 
@@ -247,6 +252,24 @@ int oem_coverage_probs_cells_device(const uint64_t *cell_row_off, uint32_t n_cel
 /* Uploads the built store (oem_store_create on the builder's arrays). */
 int oem_builder_store_create(const oem_builder *b, const double *cov_prob, int device,
                              const oem_store_opts *opts, oem_store **out);
+/* The bulk coverage model (oem_coverage_probs_device) and oem_store_create on its column, in one call: the coordinates
+ * go up once, the column and the weights never leave the device.  The store is the one oem_coverage_probs_device
+ * followed by oem_store_create(row_ptr, tid, as_prob, that column, n_reads, nnz, n_txps, device, opts) gives, for
+ * every opts: its weights are bit-identical (w = (double)p * cov; a read with a NaN coverage gets p * 0 on every
+ * alignment; weight_coding 2 rounds each product once to f32, see oem_store_opts).  Errors are those of the two calls;
+ * argument errors (nnz must be below 2^32) are reported before any device use, an alignment outside its transcript is
+ * OEM_ERR_STATE.  out_cov_prob (nnz, optional): the column as oem_coverage_probs_device returns it, NaN included.
+ * *out = NULL on any failure. */
+int oem_store_create_coverage(const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
+                              const uint32_t *aln_start, const uint32_t *aln_end, const uint64_t *txp_len,
+                              uint64_t n_reads, uint64_t nnz, uint32_t n_txps,
+                              uint32_t bin_width, int model, double growth_rate,
+                              int device, const oem_store_opts *opts,
+                              double *out_cov_prob /* nnz, or NULL */, oem_store **out);
+/* The same on the builder's arrays (oem_builder_export's view; n_txps: the builder's transcripts). */
+int oem_builder_store_create_coverage(const oem_builder *b, uint32_t bin_width, int model, double growth_rate,
+                                      int device, const oem_store_opts *opts,
+                                      double *out_cov_prob /* nnz, or NULL */, oem_store **out);
 
 /* --------------------------------------------------------------------- */
 /* EM                                                                     */

@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "oem_builder_discard_table", "oem_builder_export", "oem_builder_coverage_probs",
     "oem_builder_coverage_probs_binomial", "oem_coverage_probs_device", "oem_builder_coverage_probs_device",
     "oem_coverage_probs_cells_device",
-    "oem_builder_store_create",
+    "oem_builder_store_create", "oem_store_create_coverage", "oem_builder_store_create_coverage",
     "oem_m_step", "oem_em_run", "oem_aux_counts", "oem_assignment_probs",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
@@ -138,6 +138,9 @@ def _load(path: str) -> C.CDLL:
     L.oem_builder_coverage_probs_device.argtypes = [vp, u32, i32, f64, i32, vp]
     L.oem_coverage_probs_cells_device.argtypes = [vp, u32, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, f64, i32, vp]
     L.oem_builder_store_create.argtypes = [vp, vp, i32, vp, C.POINTER(vp)]
+    L.oem_store_create_coverage.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, f64, i32, vp, vp,
+                                            C.POINTER(vp)]
+    L.oem_builder_store_create_coverage.argtypes = [vp, u32, i32, f64, i32, vp, vp, C.POINTER(vp)]
     L.oem_m_step.argtypes = [vp, vp, vp, vp]
     L.oem_em_run.argtypes = [vp, vp, u32, f64, u32, vp, C.POINTER(RunInfoC)]
     L.oem_aux_counts.argtypes = [vp, vp, vp]

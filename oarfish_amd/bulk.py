@@ -2,8 +2,10 @@
 `perform_inference_and_write_output` (src/bulk.rs:82-209) from the built store onwards --
 EMInfo assembly, `em` / `em_par` by thread count (:155-159), aux counts (:161), `.quant` /
 `.ambig_info.tsv` / `.meta_info.json` (:168-174), bootstraps -> `.infreps.pq` (:178-193),
-assignment probabilities -> `.prob` (:196-207).  Alignment parsing, filtering and the coverage
-model come before this (oem_builder_* / the caller); KDE is not supported.
+assignment probabilities -> `.prob` (:196-207).  With a `BulkCoverage`, the driver also runs the coverage
+model of :103-108 (`logistic_prob` + `normalize_read_probs` when `model_coverage` is set) first, on the device
+and in the same call that creates the resident store (`InMemoryAlignmentStore.model_coverage_on_device`).
+Alignment parsing and filtering come before this (oem_builder_* / the caller); KDE is not supported.
 """
 from __future__ import annotations
 
@@ -40,6 +42,16 @@ def read_short_quant_vec(short_read_path: str, txps_name: Sequence[str]) -> np.n
 
 
 @dataclass
+class BulkCoverage:
+    """`--model-coverage` (prog_opts.rs) for the bulk driver: the alignments' coordinates (AlnInfo start / end, one
+    entry per alignment of the store, in its order) and the model's `--bin-width` / `--growth-rate`."""
+    aln_start: np.ndarray
+    aln_end: np.ndarray
+    bin_width: int = 100                  # prog_opts.rs:555
+    growth_rate: float = 2.0              # prog_opts.rs:502
+
+
+@dataclass
 class BulkArgs:
     """The `Args` fields this stage reads (prog_opts.rs): defaults are the reference's."""
     output: str
@@ -57,7 +69,11 @@ class BulkArgs:
 def perform_inference_and_write_output(store: InMemoryAlignmentStore, txps_name: Sequence[str],
                                        txp_lens: Sequence[int], args: BulkArgs,
                                        init_abundances: Optional[np.ndarray] = None,
-                                       read_names: Optional[Sequence[str]] = None) -> np.ndarray:
+                                       read_names: Optional[Sequence[str]] = None,
+                                       coverage: Optional[BulkCoverage] = None) -> np.ndarray:
+    if coverage is not None:                                                             # bulk.rs:103-108
+        store.model_coverage_on_device(coverage.aln_start, coverage.aln_end, np.asarray(txp_lens, dtype=np.uint64),
+                                       coverage.bin_width, coverage.growth_rate, device=args.device)
     txps = [TranscriptInfo.with_len(int(l)) for l in txp_lens]
     emi = EMInfo(eq_map=store, txp_info=txps, max_iter=args.max_em_iter,
                  convergence_thresh=args.convergence_thresh, init_abundances=init_abundances,

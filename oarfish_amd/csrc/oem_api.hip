@@ -325,8 +325,9 @@ int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float 
                       int device, const oem_store_opts *opts, oem_store *s, const CellRelabel *relabel,
                       ResidentCsr *resident)
 {
-    if (resident && opts && (opts->weight_coding != 0 || opts->layout_build == 1))
-        return fail(OEM_ERR_ARG, "a store from a resident CSR keeps f64 weights and the device layout builder");
+    if (resident && opts && (opts->weight_coding == 2 || (relabel && (opts->weight_coding != 0 || opts->layout_build == 1))))
+        return fail(OEM_ERR_ARG, "a store from a resident CSR takes its weights as given (a per-cell batch: f64 weights "
+                                 "and the device layout builder)");
     // weight_coding = 2 (opt-in): with the coverage model the iteration-invariant weight w = (p as f64) * cov
     // (em.rs:107-111) is rounded ONCE to f32 and the store is an f32 store -- 8 B per alignment instead of 12, the
     // kernels of the plain f32 stream instead of the f64 ones.  Every product and sum of the EM stays f64; only the
@@ -370,7 +371,7 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
     m.nnz = nnz;
     m.n_txps = n_txps;
     m.wide_ptr = nnz >= (1ull << 32);
-    m.w_is_f64 = cov_prob != nullptr || resident != nullptr;
+    m.w_is_f64 = resident ? resident->w32 == nullptr : cov_prob != nullptr;
     if (resident && m.wide_ptr) return fail(OEM_ERR_ARG, "a resident CSR needs fewer than 2^32 alignments");
 
     // The caller-order CSR (row ranges of per-cell runs, aux counts, assignment probabilities) goes up
@@ -380,9 +381,11 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
             m.row_ptr = resident->row_ptr;
             m.tid = resident->tid;
             m.w64 = resident->w64;
+            m.w32 = resident->w32;
             resident->row_ptr = resident->tid = nullptr;
             resident->w64 = nullptr;
-            s->hbm_bytes += sizeof(uint32_t) * (n_reads + 1) + (sizeof(uint32_t) + sizeof(double)) * nnz;
+            resident->w32 = nullptr;
+            s->hbm_bytes += sizeof(uint32_t) * (n_reads + 1) + (sizeof(uint32_t) + (m.w_is_f64 ? sizeof(double) : sizeof(float))) * nnz;
             return OEM_OK;
         }
         if (m.wide_ptr) {
@@ -481,6 +484,26 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
         }
         return vt.data();
     };
+    // A resident CSR's weights exist on the device only: the host builder gets them back -- f64 ones as the coverage
+    // column of unit probabilities ((double)1.0f * w == w), f32 ones as the probabilities of a store without a column
+    // (what oem_store_create hands the builder for weight_coding 2).
+    std::vector<float> h_p;
+    std::vector<double> h_w;
+    auto weights_to_host = [&](const double *d64, const float *d32) -> int {
+        if (d32) {
+            h_p.resize(nnz);
+            if (nnz) OEM_HIP(hipMemcpy(h_p.data(), d32, sizeof(float) * nnz, hipMemcpyDeviceToHost));
+            as_prob = h_p.data();
+            cov_prob = nullptr;
+        } else {
+            h_p.assign(nnz, 1.0f);
+            h_w.resize(nnz);
+            if (nnz) OEM_HIP(hipMemcpy(h_w.data(), d64, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+            as_prob = h_p.data();
+            cov_prob = h_w.data();
+        }
+        return OEM_OK;
+    };
     uint32_t problem_size = opts ? opts->problem_size : 0u; // (a compacted per-cell batch: its own, below)
     auto relabel_on_device = [&](bool compact) -> int {
         if (!relabel || nnz == 0) return OEM_OK;
@@ -554,18 +577,9 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
             OEM_TRY(build_tiled_layout_device(s, problem_size, win_cap, tile_rows, &built));
         tm.lap("tiled layout build (device)");
         if (built) return OEM_OK;
-        // A resident CSR's weights exist on the device only: the host builder gets them back as the coverage
-        // column of unit probabilities ((double)1.0f * w == w).  Rare: the device builder declines only stores
-        // the host one mostly declines too (a read with too many alignments inside one window).
-        std::vector<float> ones;
-        std::vector<double> w_host;
-        if (resident) {
-            ones.assign(nnz, 1.0f);
-            w_host.resize(nnz);
-            if (nnz) OEM_HIP(hipMemcpy(w_host.data(), m.w64, sizeof(double) * nnz, hipMemcpyDeviceToHost));
-            as_prob = ones.data();
-            cov_prob = w_host.data();
-        }
+        // (rare: the device builder declines only stores the host one mostly declines too -- a read with too many
+        // alignments inside one window)
+        if (resident) OEM_TRY(weights_to_host(m.w64, m.w32));
         TiledHost h;
         const char *err = nullptr;
         if (build_tiled_layout(row_ptr, host_tids(), as_prob, cov_prob, n_reads, nnz, m.n_txps, &h, &err,
@@ -576,6 +590,7 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
         }
         return OEM_OK;
     }
+    if (resident) OEM_TRY(weights_to_host(resident->w64, resident->w32)); // (before the upload thread takes them over)
     int csr_rc = OEM_OK;
     char csr_err[sizeof(t_err)] = {0};
     std::thread up([&] {

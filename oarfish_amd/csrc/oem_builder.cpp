@@ -357,3 +357,16 @@ extern "C" int oem_builder_store_create(const oem_builder *b, const double *cov_
                             b->row_ptr.size() - 1, b->tid.size(), (uint32_t)b->txp_len.size(), device, opts, out);
     OEM_API_END("oem_builder_store_create")
 }
+
+extern "C" int oem_builder_store_create_coverage(const oem_builder *b, uint32_t bin_width, int model, double growth_rate,
+                                                 int device, const oem_store_opts *opts, double *out_cov_prob,
+                                                 oem_store **out)
+{
+    OEM_API_BEGIN
+    if (out) *out = nullptr;
+    if (!b) return fail(OEM_ERR_ARG, "oem_builder_store_create_coverage: builder is NULL");
+    return oem_store_create_coverage(b->row_ptr.data(), b->tid.data(), b->as_prob.data(), b->start.data(), b->end.data(),
+                                     b->txp_len.data(), b->row_ptr.size() - 1, b->tid.size(), (uint32_t)b->txp_len.size(),
+                                     bin_width, model, growth_rate, device, opts, out_cov_prob, out);
+    OEM_API_END("oem_builder_store_create_coverage")
+}

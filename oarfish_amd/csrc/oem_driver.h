@@ -53,13 +53,15 @@ struct CellRelabel {
     uint32_t n_cells;
     uint32_t cell_txps;
 };
-// A caller-order CSR already resident on the device (u32 row pointers, transcript ids, f64 weights w = p * cov): a
-// store created from it takes the buffers over (nulls them here) instead of uploading the caller's arrays.  Whatever
-// is still held here is freed with it.
+// A caller-order CSR already resident on the device (u32 row pointers, transcript ids, and either the f64 weights
+// w = p * cov or, for an f32 store, the weights already rounded once to f32 in w32): a store created from it takes the
+// buffers over (nulls them here) instead of uploading the caller's arrays.  Whatever is still held here is freed with
+// it.
 struct ResidentCsr {
     uint32_t *row_ptr = nullptr;
     uint32_t *tid = nullptr;
     double *w64 = nullptr;
+    float *w32 = nullptr; // (set: an f32 store; w64 stays null)
     ResidentCsr() = default;
     ResidentCsr(const ResidentCsr &) = delete;
     ResidentCsr &operator=(const ResidentCsr &) = delete;
@@ -68,8 +70,13 @@ struct ResidentCsr {
         (void)hipFree(row_ptr);
         (void)hipFree(tid);
         (void)hipFree(w64);
+        (void)hipFree(w32);
     }
 };
+// With `resident`, tid / row_ptr are still the caller's host arrays in the same order (the host layout builder reads
+// them) and as_prob / cov_prob are not read: the weights come from the resident buffers.  A store from a resident CSR
+// takes its weights as given (weight_coding 2 is refused: the caller rounds them into w32 and asks for coding 1); a
+// per-cell batch (relabel) from one keeps f64 weights and the device layout builder.
 int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob, const double *cov_prob,
                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, const oem_store_opts *opts, oem_store *s,
                       const CellRelabel *relabel = nullptr, ResidentCsr *resident = nullptr);

@@ -78,6 +78,49 @@ class DeviceStore:
             None if cov is None else cov.ctypes.data, self.n_reads, self.nnz, self.n_txps,
             self.device, C.addressof(opts), C.byref(self._h)))
 
+    @classmethod
+    def with_coverage(cls, row_ptr, tid, as_prob, aln_start, aln_end, txp_len, bin_width: int = 100,
+                      model: str = "logistic", growth_rate: float = 2.0, device: int = 0, reorder_rows: int = 0,
+                      window_cap: int = 0, layout_build: int = 0, weight_coding: int = 0,
+                      return_coverage: bool = False):
+        """The bulk coverage model and the store on its column in one device call (oem_store_create_coverage):
+        the store ``DeviceStore(row_ptr, tid, as_prob, cov, len(txp_len), ...)`` would be, where ``cov`` is the
+        column of ``oem_coverage_probs_device`` (logistic with ``growth_rate``, or binomial) on the alignments'
+        ``aln_start`` / ``aln_end``; the column and the weights never leave the device.  With ``return_coverage``
+        returns ``(store, cov)`` (nnz f64, NaN for a zero-span alignment, whose read the EM drops)."""
+        models = {"logistic": 0, "binomial": 1}
+        if model not in models:
+            raise ValueError(f"model must be one of {sorted(models)}, not {model!r}")
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+        tid = np.ascontiguousarray(tid, dtype=np.uint32)
+        as_prob = np.ascontiguousarray(as_prob, dtype=np.float32)
+        aln_start = np.ascontiguousarray(aln_start, dtype=np.uint32)
+        aln_end = np.ascontiguousarray(aln_end, dtype=np.uint32)
+        txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        self.n_reads = len(self.row_ptr) - 1
+        self.nnz = len(tid)
+        self.n_txps = len(txp_len)
+        self.device = int(device)
+        if len(as_prob) != self.nnz or len(aln_start) != self.nnz or len(aln_end) != self.nnz:
+            raise ValueError("tid, as_prob, aln_start and aln_end must have one entry per alignment")
+        opts = _lib.StoreOptsC()
+        opts.reorder_rows = reorder_rows
+        opts.window_cap = window_cap
+        opts.layout_build = layout_build
+        opts.weight_coding = weight_coding  # 2: the products rounded once to f32 (oem_store_opts)
+        cov = np.empty(self.nnz, dtype=np.float64) if return_coverage else None
+        nz = self.nnz > 0
+        L = _lib.lib()
+        self._lib = L
+        self._check(L.oem_store_create_coverage(
+            self.row_ptr.ctypes.data, tid.ctypes.data if nz else None, as_prob.ctypes.data if nz else None,
+            aln_start.ctypes.data if nz else None, aln_end.ctypes.data if nz else None, txp_len.ctypes.data,
+            self.n_reads, self.nnz, self.n_txps, bin_width, models[model], growth_rate, self.device,
+            C.addressof(opts), cov.ctypes.data if cov is not None and nz else None, C.byref(self._h)))
+        return (self, cov) if return_coverage else self
+
     def _check(self, rc: int) -> None:
         if rc != _lib.OEM_OK:
             msg = self._lib.oem_last_error()
@@ -318,6 +361,33 @@ class InMemoryAlignmentStore:
             d.close()
         self._dev = {}
 
+    def model_coverage_on_device(self, aln_start, aln_end, txp_len, bin_width: int = 100, growth_rate: float = 2.0,
+                                 device: int = 0, weight_coding: int = 0) -> np.ndarray:
+        """bulk.rs:103-108 on the device: ``filter_opts.model_coverage`` on, the logistic coverage model of the
+        alignments (``aln_start`` / ``aln_end`` per alignment, ``txp_len`` per transcript) normalised per read into
+        ``coverage_probabilities``, where the reference's store holds it after ``normalize_read_probs``.  The store is
+        created on the device in the same call (``DeviceStore.with_coverage``) and kept as this store's resident
+        copy for ``len(txp_len)`` transcripts: ``em``, ``em_par``, ``bootstrap``, ``aux_counts`` and
+        ``assignment_probs`` then run on it without a second upload.  ``weight_coding`` 2 keeps the weights as f32
+        (oem_store_opts).  Returns the column."""
+        self._flush()
+        n_txps = len(txp_len)
+        dev, cov = DeviceStore.with_coverage(self.boundaries, self.alignments, self.as_probabilities, aln_start,
+                                             aln_end, txp_len, bin_width=bin_width, model="logistic",
+                                             growth_rate=growth_rate, device=device, weight_coding=weight_coding,
+                                             return_coverage=True)
+        self.filter_opts.model_coverage = True
+        self.coverage_probabilities = cov
+        key = (int(device), int(n_txps))
+        old = self._dev.pop(key, None)
+        if old is not None:
+            old[1].close()
+        self._dev[key] = (self._stamp(cov), dev)
+        return cov
+
+    def _stamp(self, cov):
+        return (self.boundaries, self.alignments, self.as_probabilities, cov, bool(self.filter_opts.model_coverage))
+
     def device_store(self, n_txps: int, device: int = 0) -> DeviceStore:
         """Upload once, keep resident (the analogue of the store living in RAM across
         em / bootstrap calls, bulk.rs:131-194)."""
@@ -330,7 +400,7 @@ class InMemoryAlignmentStore:
         key = (int(device), int(n_txps))
         # the stamp holds the arrays themselves (compared with `is`): an id() alone can be reused by a
         # later array once the first one is freed, and a stale resident copy would then look current
-        stamp = (self.boundaries, self.alignments, self.as_probabilities, cov, bool(self.filter_opts.model_coverage))
+        stamp = self._stamp(cov)
         hit = self._dev.get(key)
         if hit is not None and not (len(hit[0]) == len(stamp) and
                                     all(a is b for a, b in zip(hit[0][:4], stamp[:4])) and hit[0][4] == stamp[4]):
