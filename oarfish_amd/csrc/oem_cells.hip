@@ -81,6 +81,8 @@ struct CellsTiming {
     }
 };
 thread_local CellsTiming *t_timing = nullptr;
+// The groups of the last per-cell call of this thread and the path each one took, for oem_debug_cells_last_paths.
+thread_local std::vector<CellsGroupPath> t_cells_paths;
 
 // Where the groups of one call put their results: the caller's dense n_cells x n_txps matrix (oem_em_run_cells), or
 // one SparseBlock per group index (oem_em_run_cells_sparse: groups finish in any order).
@@ -389,8 +391,9 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
 int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, const uint64_t *row_ptr,
                     const uint32_t *tid, const float *as_prob, const double *cov_prob, const CellsCoverage *cov_src,
                     uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g,
-                    oem_run_info *infos)
+                    oem_run_info *infos, bool *batched)
 {
+    *batched = false;
     const uint32_t n_cells = c1 - c0;
     const uint64_t r0 = cell_row_off[c0], r1 = cell_row_off[c1];
     const uint64_t a0 = row_ptr[r0], a1 = row_ptr[r1];
@@ -440,6 +443,7 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
         bool used = false;
         int rcb = run_cells_batched(off_p, n_cells, rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device,
                                     max_iter, conv_thresh, out_g, blk, infos_g, &used, resident);
+        *batched = used;
         if (rcb != OEM_OK || used) return rcb;
     }
     // fallback (max_iter == 0, a single cell, or a group the tiler declines): cells one after another
@@ -489,6 +493,8 @@ void cells_last_timing(double *loop_ms, uint64_t *batched_passes)
     if (loop_ms) *loop_ms = t_cells_loop_ms;
     if (batched_passes) *batched_passes = t_cells_batched_passes;
 }
+
+const std::vector<CellsGroupPath> &cells_last_paths() { return t_cells_paths; }
 } // namespace oem
 
 namespace oem {
@@ -511,6 +517,7 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     if (nnz > 0 && (!tid || !as_prob)) return fail(OEM_ERR_ARG, "%s: tid/as_prob is NULL", who);
     t_cells_loop_ms = 0.0;
     t_cells_batched_passes = 0;
+    t_cells_paths.clear();
     StageTimer tm_all;
     OEM_TRY(validate_csr(row_ptr, tid, n_reads, nnz, n_txps)); // all cells at once, on several host threads
     tm_all.lap("cells: range checks");
@@ -555,7 +562,8 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     // 0.67 s call).  Measured (scripts/cells_groups_exp.sh, three rounds): heads of 40 / 80 / 160 / 312 of 625 cells
     // +7 / -0.5 / -3.4 / -0.5 % against one group -- a small head's own loop runs its few tiles badly, two halves just
     // share the device.
-    if (groups.size() == 1 && n_cells >= 64 && nnz >= (64ull << 20)) {
+    if (groups.size() == 1 && n_cells >= (uint64_t)knob("OEM_CELLS_SPLIT_CELLS", 64) &&
+        nnz >= (uint64_t)knob("OEM_CELLS_SPLIT_NNZ", 64l << 20)) { // testing build: split small calls too
         const long head = knob("OEM_CELLS_HEAD", (long)(kCellsHeadDiv ? n_cells / kCellsHeadDiv : 0));
         if (head >= 2 && (uint32_t)head + 2 <= n_cells) {
             groups.clear();
@@ -569,6 +577,8 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     // the other group's full passes instead of leaving it idle (single_cell.rs:96-150 runs its cells on N worker
     // threads for the same reason).
     if (sink.blocks) sink.blocks->assign(groups.size(), SparseBlock());
+    std::vector<CellsGroupPath> paths(groups.size()); // (each group's slot is written by the worker that runs it)
+    for (size_t g = 0; g < groups.size(); ++g) paths[g] = CellsGroupPath{groups[g].first, groups[g].second, 0};
     CellsTiming timing;
     std::atomic<size_t> next{0};
     constexpr int kMaxWorkers = 4;
@@ -591,8 +601,10 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
             for (;;) {
                 const size_t g = next.fetch_add(1);
                 if (g >= groups.size() || failed.load()) break;
+                bool batched = false;
                 rcs[wk] = run_cells_group(cell_row_off, groups[g].first, groups[g].second, row_ptr, tid, as_prob, cov_prob,
-                                          cov_src, n_txps, device, max_iter, conv_thresh, sink, g, infos);
+                                          cov_src, n_txps, device, max_iter, conv_thresh, sink, g, infos, &batched);
+                paths[g].batched = batched ? 1u : 0u;
                 if (rcs[wk] != OEM_OK) break;
             }
         } catch (const std::exception &e) {
@@ -618,6 +630,7 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     tm_all.lap("cells: all groups");
     t_cells_loop_ms = timing.loop_ms();
     t_cells_batched_passes = timing.passes;
+    t_cells_paths = std::move(paths);
     for (int wk = 0; wk < kMaxWorkers; ++wk)
         if (rcs[wk] != OEM_OK) return fail(rcs[wk], "%s", errs[wk].c_str());
     return OEM_OK;

@@ -203,5 +203,10 @@ int agree_any(oem_store *s, bool *flag);
 
 // oem_cells.hip: timing of the last oem_em_run_cells call of this thread
 void cells_last_timing(double *loop_ms, uint64_t *batched_passes);
+// ... and its groups: [c0, c1) and 1 when the group ran batched, 0 when cell by cell (oem_debug_cells_last_paths)
+struct CellsGroupPath {
+    uint32_t c0, c1, batched;
+};
+const std::vector<CellsGroupPath> &cells_last_paths();
 
 } // namespace oem

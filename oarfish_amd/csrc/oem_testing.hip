@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "oem_internal.h"
+#include "oem_driver.h"
 
 using namespace oem;
 
@@ -68,6 +68,22 @@ extern "C" int oem_debug_layout_hash(oem_store *s, uint64_t *out, uint32_t n_out
 // Test hook: what oem::knob() returns in THIS library (the environment variable in the test-only build; the
 // product's knob() is compiled without getenv and returns its default, checked on the object file).
 extern "C" long oem_debug_knob(const char *name, long dflt) { return oem::knob(name, dflt); }
+
+// Test hook: the groups of this thread's last per-cell call (oem_em_run_cells, oem_em_run_cells_sparse,
+// oem_em_run_cells_coverage_sparse) and the path each one took.  *n_groups = the number of groups; out[3 g .. 3 g + 2]
+// = c0, c1, 1 when group g ran batched / 0 when cell by cell, for the first `cap` groups.
+extern "C" int oem_debug_cells_last_paths(uint32_t *n_groups, uint32_t *out, uint32_t cap)
+{
+    if (!n_groups || (cap && !out)) return fail(OEM_ERR_ARG, "oem_debug_cells_last_paths: bad argument");
+    const std::vector<CellsGroupPath> &p = cells_last_paths();
+    *n_groups = (uint32_t)p.size();
+    for (size_t g = 0; g < p.size() && g < cap; ++g) {
+        out[3 * g] = p[g].c0;
+        out[3 * g + 1] = p[g].c1;
+        out[3 * g + 2] = p[g].batched;
+    }
+    return OEM_OK;
+}
 
 // ---------------------------------------------------------------------------
 // Stress test of k_reldiff_swap_clear's last-block election (oem_kernels.hip): the stopping

@@ -76,3 +76,33 @@ def tile_test_store(kind, seed):
     else:
         raise ValueError(kind)
     return st.row_ptr, st.tid, st.as_prob, st.n_txps
+
+
+def f32_ulps(a, b):
+    """Distance in f32 units in the last place between two f32 arrays of one sign."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
+
+
+def assert_cell_matches_oracle(info, want_info, n_reads, n_txps, what, dense=None, cols=None, vals=None):
+    """One cell of a per-cell EM call against the oracle's em::em on the cell's own store.  The iteration counts are
+    at most one apart; `converged` and the number of passes agree when they are equal.  Dense row: within 1e-8 when
+    the counts agree, the 1e-4 north star otherwise.  Sparse row (cols, vals): the columns are exactly the oracle's
+    v > 0 and each value is within one f32 ulp of the oracle's when the counts agree, the north star otherwise."""
+    want, wi = want_info
+    assert abs(int(info.niter) - int(wi.niter)) <= 1, (what, info, wi)
+    same = info.niter == wi.niter
+    if same:
+        assert bool(info.converged) == bool(wi.converged) and info.n_passes == wi.n_passes, (what, info, wi)
+    if dense is not None:
+        assert_counts_close(dense, want, n_reads, n_txps, 1e-8 if same else 1e-4, what)
+        return
+    got = np.zeros(n_txps)
+    got[cols] = vals
+    if same:
+        np.testing.assert_array_equal(cols, np.nonzero(want > 0.0)[0], err_msg=what)
+        ulps = f32_ulps(vals, want[cols].astype(np.float32))
+        assert ulps.max(initial=0) <= 1, f"{what}: {int(ulps.max())} f32 ulps from the oracle"
+    else:
+        assert_counts_close(got, want, n_reads, n_txps, 1e-4, what)

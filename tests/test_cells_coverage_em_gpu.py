@@ -12,7 +12,8 @@ import oarfish_amd
 from oarfish_amd import _lib, synth
 from oracle import c_oracle
 from oracle import filter_py as fp
-from tests.common import assert_counts_close
+from tests.common import assert_cell_matches_oracle, assert_counts_close
+from tests.test_cells_coverage_gpu import _per_cell_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -213,7 +214,8 @@ def test_an_alignment_past_its_transcript_names_the_cell():
 @pytest.mark.timeout(900)
 def test_fused_c5_slice_of_one_gpu():
     """625 cells x 50 k reads over 60 k transcripts in one call (the 1 : 3 head split, two workers): per-cell mass,
-    and 16 sampled cells against the composition."""
+    16 sampled cells against the composition, and four cells of the tail group against the oracle's em::em on the
+    per-cell device coverage."""
     n_cells, per_cell, T = 625, 50_000, 60_000
     cell_off, row_ptr, tid, p = synth.make_cells(n_cells, per_cell, T, seed=37, threads=THREADS)
     tl, s, e = synth.make_coordinates(tid, T, seed=37, zero_span_frac=0.001, threads=THREADS)
@@ -229,3 +231,12 @@ def test_fused_c5_slice_of_one_gpu():
     nan_rows = np.unique(np.searchsorted(row_ptr.astype(np.int64), np.nonzero(np.isnan(cov))[0], side="right") - 1)
     dropped = np.bincount(np.searchsorted(cell_off.astype(np.int64), nan_rows, side="right") - 1, minlength=n_cells)
     np.testing.assert_allclose(sums, per_cell - dropped, rtol=1e-6)
+    # cells of the tail group (625 // 4 = 156 head cells) against the oracle's EM on the per-cell device coverage
+    tail = (156, 157, 400, 624)
+    col = _per_cell_loop(cell_off, row_ptr, tid, s, e, tl, 100, 1, 2.0, cells=tail)
+    for c in tail:
+        r0, r1, a0, a1 = _slices(cell_off, row_ptr, c)
+        o = c_oracle.Store(row_ptr[r0:r1 + 1] - row_ptr[r0], tid[a0:a1], p[a0:a1], col[a0:a1], T)
+        want = c_oracle.do_em(o, max_iter=1000, conv_thresh=1e-3, min_iter_gate=50)
+        sl = slice(int(indptr[c]), int(indptr[c + 1]))
+        assert_cell_matches_oracle(infos[c], want, r1 - r0, T, f"cell {c}", cols=cols[sl], vals=vals[sl])

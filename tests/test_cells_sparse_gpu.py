@@ -11,7 +11,7 @@ import oarfish_amd
 from oarfish_amd import _lib, synth
 from oarfish_amd import writers as W
 from oracle import c_oracle
-from tests.common import assert_counts_close
+from tests.common import assert_cell_matches_oracle, assert_counts_close
 
 pytestmark = pytest.mark.gpu
 
@@ -172,8 +172,8 @@ def test_sparse_equals_dense_on_every_path(path, monkeypatch):
 @pytest.mark.timeout(900)
 def test_sparse_c5_slice_of_one_gpu():
     """The 625 x 50 k-read slice of BASELINE configs[4] over 60 k transcripts (the 1 : 3 head split, compacted batched
-    groups on two workers): sparse = dense, per-cell mass, unique <= val <= total, and the result at most half the
-    bytes of the dense one."""
+    groups on two workers): sparse = dense, per-cell mass, unique <= val <= total, four cells of the tail group against
+    the oracle, and the result at most half the bytes of the dense one."""
     n_cells, per_cell, T = 625, 50_000, 60_000
     cell_off, row_ptr, tid, p = synth.make_cells(n_cells, per_cell, T, seed=37, threads=THREADS)
     sp = oarfish_amd.em_cells_sparse(cell_off, row_ptr, tid, p, None, T, max_iter=1000, convergence_thresh=1e-3)
@@ -192,6 +192,11 @@ def test_sparse_c5_slice_of_one_gpu():
         got = _row(indptr, cols, vals, c, T)
         eps = 2.0 ** -23
         assert np.all(got >= uniq * (1 - eps) - 1e-6) and np.all(got <= tot * (1 + eps) + 1e-6), c
+    for c in (156, 157, 400, 624):   # cells of the tail group (625 // 4 = 156 head cells) against the oracle
+        o, n = _cell_store(cell_off, row_ptr, tid, p, None, c, T)
+        want = c_oracle.do_em(o, max_iter=1000, conv_thresh=1e-3, min_iter_gate=50)
+        s = slice(int(indptr[c]), int(indptr[c + 1]))
+        assert_cell_matches_oracle(infos[c], want, n, T, f"cell {c}", cols=cols[s], vals=vals[s])
     dense_bytes = n_cells * T * 8
     frac = len(cols) * 8 / dense_bytes
     print(f"625-cell slice: {len(cols)} entries, {frac:.3f} of the dense result's bytes")

@@ -12,7 +12,7 @@ import oarfish_amd
 from oarfish_amd import _lib, synth
 from oarfish_amd.types import DeviceStore, InMemoryAlignmentStore
 from oracle import c_oracle
-from tests.common import assert_counts_close, golden_names, load_golden
+from tests.common import assert_cell_matches_oracle, assert_counts_close, golden_names, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -1012,9 +1012,10 @@ def test_full_size_c3_other_weight_codings_match_oracle(kind):
 @pytest.mark.timeout(900)
 def test_c5_slice_of_one_gpu_properties():
     """BASELINE configs[4] at the size ONE GPU sees when 5 k cells are dealt to 8: 625 cells x 50 k reads (31 M reads,
-    250 M alignments, one batched store: wide windows, fused fold, live-tile compaction).  No oracle at this size: per
-    cell mass conservation and unique <= count <= total (aux counts over the cell's own rows), cells stop at their own
-    iterations, and a slice of the batch equals the same cells run as a batch of their own."""
+    250 M alignments, one batched store: wide windows, fused fold, live-tile compaction).  Per cell mass conservation
+    and unique <= count <= total (aux counts over the cell's own rows), cells stop at their own iterations, four cells
+    of the tail group of the head split against the oracle, and a slice of the batch equals the same cells run as a
+    batch of their own."""
     n_cells, per_cell, T = 625, 50_000, 60_000
     cell_off, row_ptr, tid, p = synth.make_cells(n_cells, per_cell, T, seed=37, threads=min(32, os.cpu_count() or 4))
     out, infos = oarfish_amd.em_cells(cell_off, row_ptr, tid, p, None, T, max_iter=1000, convergence_thresh=1e-3)
@@ -1029,6 +1030,12 @@ def test_c5_slice_of_one_gpu_properties():
         tot = np.bincount(tid[a0:a1], minlength=T)
         uniq = np.bincount(tid[a0:a1][np.repeat(lens == 1, lens)], minlength=T)
         assert np.all(out[c] >= uniq - 1e-6) and np.all(out[c] <= tot + 1e-6), c
+    for c in (156, 157, 400, 624):   # cells of the tail group (625 // 4 = 156 head cells) against the oracle
+        r0, r1 = int(cell_off[c]), int(cell_off[c + 1])
+        a0, a1 = int(row_ptr[r0]), int(row_ptr[r1])
+        o = c_oracle.Store(row_ptr[r0:r1 + 1] - row_ptr[r0], tid[a0:a1], p[a0:a1], None, T)
+        want = c_oracle.do_em(o, max_iter=1000, conv_thresh=1e-3, min_iter_gate=50)
+        assert_cell_matches_oracle(infos[c], want, per_cell, T, f"cell {c}", dense=out[c])
     # the first 8 cells as a batch of their own: the same answers (a cell's run does not depend on its batch)
     r8 = int(cell_off[8]); a8 = int(row_ptr[r8])
     out8, infos8 = oarfish_amd.em_cells(cell_off[:9], row_ptr[:r8 + 1], tid[:a8], p[:a8], None, T, max_iter=1000,
