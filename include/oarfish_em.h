@@ -130,7 +130,9 @@ typedef enum {
     OEM_OPT_BOOTSTRAP_FIRST_REPLICA = 2 /* value b0 (default 0): replicate k of the next oem_bootstrap calls
                                     draws the device resample of global replica b0 + k.  Lets N processes
                                     that each hold the whole store split one set of replicates with no
-                                    collective (the reference's replicates are independent, em.rs:303-309). */
+                                    collective (the reference's replicates are independent, em.rs:303-309).
+                                    b0 <= 2^32 - 1, and an oem_bootstrap call that draws its resamples must keep
+                                    b0 + n_boot - 1 <= 2^32 - 1: it returns OEM_ERR_ARG instead of wrapping. */
 } oem_option;
 int oem_store_set_option(oem_store *store, uint32_t option, uint64_t value);
 
@@ -318,14 +320,21 @@ int oem_assignment_probs(oem_store *store, const double *counts, double display_
  * Multinomial(n_reads; 1/n_reads ...) count vector of bootstrap.rs:7-16
  * (n draws from Uniform[0,n) with replacement; sorting is immaterial once
  * expressed as counts).  Counter-based (Philox4x32-10) stream keyed by
- * (seed, replica).  out_row_w: n_reads u32 on the host. */
+ * (seed, replica), a pure function of them and of the global read count n:
+ *   counter block q < ceil(n/2) = (q & 0xffffffff, q >> 32, replica, 0x6f656d62),
+ *   key = (seed & 0xffffffff, seed >> 32); draw 2q = (out[0] << 32) | out[1],
+ *   draw 2q+1 = (out[2] << 32) | out[3] (draws with index >= n do not exist);
+ *   a draw r selects read (r * n) >> 64.  A row shard keeps the counts of its
+ *   own rows.  oracle/resample_np.py restates it; tests hold the kernel to it
+ *   bit for bit.  out_row_w: n_reads u32 on the host. */
 int oem_bootstrap_weights(oem_store *store, uint64_t seed, uint32_t replica, uint32_t *out_row_w);
 
 /* em::bootstrap (em.rs:292-314): n_boot resampled EMs, each do_bootstrap
  * (em.rs:273-290) = do_em over random_sampling_iter with gate niter>50.
  *   row_w_all : optional n_boot x n_reads u32 (row-major) to inject the
  *               resamples (parity tests); NULL => drawn on the device as
- *               oem_bootstrap_weights(seed, b).
+ *               oem_bootstrap_weights(seed, b0 + b), b0 = OEM_OPT_BOOTSTRAP_FIRST_REPLICA
+ *               (OEM_ERR_ARG if b0 + n_boot - 1 > 2^32 - 1).
  *   out       : n_boot x n_txps f64, row-major (replicate-major, as the
  *               Vec<Vec<f64>> of em.rs:292 / columns bootstrap.{i} of bulk.rs:181-193)
  *   infos     : optional, n_boot entries. */

@@ -273,6 +273,9 @@ extern "C" int oem_bootstrap(oem_store *s, uint32_t n_boot, uint64_t seed, const
     OEM_API_BEGIN
     if (!s || (n_boot && !out)) return fail(OEM_ERR_ARG, "oem_bootstrap: NULL argument");
     std::lock_guard<std::mutex> lk(s->mu);
+    // the replica word of the stream is 32 bits: b0 + k must not wrap onto the replicas another call draws
+    if (!row_w_all && n_boot && (uint64_t)s->bootstrap_first_replica + (n_boot - 1) > 0xffffffffull)
+        return fail(OEM_ERR_ARG, "oem_bootstrap: replicas %u + [0, %u) exceed 2^32 - 1", s->bootstrap_first_replica, n_boot);
     OEM_TRY(ensure_device(s->device));
     OEM_TRY(ensure_row_w(s));
     const uint32_t T = s->csr.n_txps;

@@ -78,6 +78,26 @@ def tile_test_store(kind, seed):
     return st.row_ptr, st.tid, st.as_prob, st.n_txps
 
 
+def byte_edge_weights(n_reads, seed):
+    """Injected resamples around the batched bootstrap's byte-coded multiplicities (a replicate with a multiplicity
+    >= 256 must be handed to the one-per-pass path; 255 must still be exact in a byte).  Returns (row_w_all u32[7, R],
+    names): ordinary resamples (the device stream's, drawn by the reference) sit between the edge replicates, so that
+    a replicate that falls back is handed over in the middle of a running chain.  The reads that carry 255 / 256 are
+    spread over the store so that they land in different tiles."""
+    from oracle import resample_np
+    W = np.stack([resample_np.bootstrap_weights(n_reads, seed, b) for b in range(7)])
+    at = lambda f: int(f * (n_reads - 1))   # noqa: E731
+    W[1, [at(0.1), at(0.5), at(0.9)]] = 255
+    W[3, at(0.3)] = 256
+    W[4, [at(0.2), at(0.7)]] = (255, 256)
+    k = max(n_reads // 200, 1)
+    W[5] = 0
+    W[5, :k] = 255
+    names = ["ordinary", "a few at 255", "ordinary", "one at 256", "255 and 256", "all 255 on the first reads",
+             "ordinary"]
+    return W.astype(np.uint32), names
+
+
 def f32_ulps(a, b):
     """Distance in f32 units in the last place between two f32 arrays of one sign."""
     a = np.ascontiguousarray(a, dtype=np.float32)

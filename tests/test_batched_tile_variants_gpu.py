@@ -6,7 +6,7 @@ import pytest
 
 from oarfish_amd import _lib
 from oarfish_amd.types import DeviceStore
-from oracle import c_oracle
+from oracle import c_oracle, resample_np
 from tests.common import assert_counts_close, tile_test_store as _store
 
 pytestmark = pytest.mark.gpu
@@ -46,3 +46,27 @@ def test_fused_and_streamed_weights_draw_and_estimate_the_same_replicates():
     for b in range(6):
         assert res[0][1][b].niter == res[1][1][b].niter
         assert_counts_close(res[0][0][b], res[1][0][b], n_reads, T, 1e-10, f"replicate {b}")
+
+
+@pytest.mark.parametrize("variant", ["fused", "f32"])
+def test_device_drawn_replicates_are_those_of_the_reference_stream(variant):
+    """Resamples drawn on the device, first_replica = 3: row b of either kernel variant is the oracle's EM over the
+    reference draw (oracle/resample_np.py) of replica 3 + b -- not over weights fetched back from the device.  The
+    oracle's own results of neighbouring replicas do not pass for each other, so a row holding another replica's
+    replicate fails."""
+    row_ptr, tid, p, T = _store("dense", seed=31)
+    n_reads = len(row_ptr) - 1
+    seed, b0, n_rep = 0x0bad_cafe_0000_0009, 3, 6
+    o = c_oracle.Store(row_ptr, tid, p, None, T)
+    with DeviceStore(row_ptr, tid, p, None, T, weight_coding=1 if variant == "f32" else 0) as d:
+        got, infos = d.bootstrap(n_rep, seed=seed, max_iter=80, conv_thresh=1e-3, first_replica=b0)
+    want = [c_oracle.do_em(o, max_iter=80, conv_thresh=1e-3, row_w=resample_np.bootstrap_weights(n_reads, seed, b0 + b))
+            for b in range(-1, n_rep + 1)]
+    for a, b in zip(want, want[1:]):
+        with pytest.raises(AssertionError):
+            assert_counts_close(a[0], b[0], n_reads, T, 1e-4)
+    for b in range(n_rep):
+        w, wi = want[b + 1]
+        assert abs(infos[b].niter - wi.niter) <= 1, (variant, b, infos[b], wi)
+        assert_counts_close(got[b], w, n_reads, T, 1e-8 if infos[b].niter == wi.niter else 1e-4,
+                            f"{variant} row {b} (replica {b0 + b})")

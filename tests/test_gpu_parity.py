@@ -11,7 +11,7 @@ import pytest
 import oarfish_amd
 from oarfish_amd import _lib, synth
 from oarfish_amd.types import DeviceStore, InMemoryAlignmentStore
-from oracle import c_oracle
+from oracle import c_oracle, resample_np
 from tests.common import assert_cell_matches_oracle, assert_counts_close, golden_names, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -186,6 +186,9 @@ def test_device_multinomial_weights():
         assert abs((w == 1).mean() - np.exp(-1)) < 0.01
         assert abs((w == 2).mean() - np.exp(-1) / 2) < 0.01
     assert abs(np.corrcoef(w0, w1)[0, 1]) < 0.02
+    # the stream itself: the reference's, bit for bit (tests/test_bootstrap_draw_gpu.py covers sizes, seeds, shards)
+    for w, (seed, replica) in ((w0, (11, 0)), (w1, (11, 1)), (w2, (12, 0))):
+        assert np.array_equal(w, resample_np.bootstrap_weights(n, seed, replica)), (seed, replica)
     # a device-drawn bootstrap equals the oracle run on the same drawn weights
     o = c_oracle.Store(st.row_ptr, st.tid, st.as_prob, None, st.n_txps)
     with DeviceStore(st.row_ptr, st.tid, st.as_prob, None, st.n_txps) as d:
@@ -559,6 +562,8 @@ def test_row_shard_semantics_single_rank():
                 d.attach_comm(comm.handle, st.n_reads, sh.row_begin)
                 w = d.bootstrap_weights(42, 1)
                 assert np.array_equal(w, w_full[sh.row_begin:sh.row_end])
+                assert np.array_equal(w, resample_np.bootstrap_weights(st.n_reads, 42, 1, sh.row_begin,
+                                                                       sh.row_end - sh.row_begin))
                 partial_sum += d.m_step(theta0)                  # rank-local partial counts
                 # one iteration from the uniform init = one pass from theta = R_global / T
                 one, info = d.em_run(None, 1, 0.0, 50)
@@ -635,7 +640,11 @@ def _sharded_loop_body(world):
     want, wi = c_oracle.do_em(o, max_iter=400, conv_thresh=1e-3)
     wpar, wpi = c_oracle.do_em(o, max_iter=400, conv_thresh=1e-3, min_iter_gate=1)
     with DeviceStore(st.row_ptr, st.tid, st.as_prob, None, st.n_txps) as full:
-        wb = [c_oracle.do_em(o, max_iter=200, conv_thresh=1e-3, row_w=full.bootstrap_weights(17, b)) for b in range(3)]
+        ws = [full.bootstrap_weights(17, b) for b in range(3)]
+    for b in range(3):   # the oracle runs on the reference's draw, which the un-sharded store's equals
+        assert np.array_equal(ws[b], resample_np.bootstrap_weights(st.n_reads, 17, b)), b
+    wb = [c_oracle.do_em(o, max_iter=200, conv_thresh=1e-3, row_w=resample_np.bootstrap_weights(st.n_reads, 17, b))
+          for b in range(3)]
     for r in range(world):
         cnt, info, par, pinfo, boots, binfo = res[r]
         assert info.niter == res[0][1].niter and pinfo.niter == res[0][3].niter          # same decision on every rank

@@ -49,6 +49,27 @@ def test_numpy_restatement_independent_agreement():
             np.testing.assert_allclose(a, b, rtol=1e-10, atol=1e-10)
 
 
+@pytest.mark.parametrize("coverage", [False, True])
+def test_c_and_numpy_restatements_agree_on_byte_edge_multiplicities(coverage):
+    """The injected resamples of tests/test_bootstrap_draw_gpu.py (multiplicities of 255 and 256, a replicate that is
+    255 on a few reads and 0 elsewhere): before the device is held to the oracle on them, the two restatements must
+    agree on them."""
+    from oarfish_amd import synth
+    from tests.common import byte_edge_weights
+    st = synth.make_store(6_000, 400, seed=81, coverage=coverage)
+    s = c_oracle.Store(st.row_ptr, st.tid, st.as_prob, st.cov_prob, st.n_txps)
+    W, names = byte_edge_weights(st.n_reads, seed=0x5eed_0000_0001)
+    assert sorted(set(W.max(axis=1).tolist()))[-2:] == [255, 256]
+    for b in range(len(W)):
+        for mi in (1, 200):
+            a, info = c_oracle.do_em(s, row_w=W[b], max_iter=mi, conv_thresh=1e-3)
+            c, niter, npass, conv, rel = oracle_np.do_em(st.row_ptr, st.tid, st.as_prob, st.cov_prob, st.n_txps,
+                                                         row_w=W[b], max_iter=mi, conv_thresh=1e-3)
+            assert (info.niter, info.n_passes, info.converged) == (niter, npass, conv), (names[b], mi)
+            np.testing.assert_allclose(a, c, rtol=1e-10, atol=1e-10, err_msg=names[b])
+            assert abs(a.sum() - W[b].sum()) < 1e-8 * W[b].sum()   # every read has mass: the weights' sum is kept
+
+
 def test_invariants():
     """SURVEY.md section 8c (2)."""
     rng = np.random.default_rng(5)
