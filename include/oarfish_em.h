@@ -39,7 +39,8 @@ extern "C" {
  *    callers keep working (additions only).  Later additions under the same number: the sparse per-cell results
  *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy), the per-cell coverage model
  *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse), the bulk coverage model
- *    and the store on its column in one call (oem_store_create_coverage, oem_builder_store_create_coverage). */
+ *    and the store on its column in one call (oem_store_create_coverage, oem_builder_store_create_coverage), the
+ *    per-cell session (oem_cells_stream_*). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -388,6 +389,67 @@ int oem_em_run_cells_coverage_sparse(const uint64_t *cell_row_off, uint32_t n_ce
                                      uint32_t bin_width, int model, double growth_rate,
                                      int device, uint32_t max_iter, double conv_thresh,
                                      double *out_cov_prob, oem_cells_result **out);
+
+/* A per-cell SESSION: the caller pushes cells one by one, from any number of threads, as they become available
+ * (single_cell.rs:96-193: N workers each pop one cell and build its private store).  The library stages the cells,
+ * cuts them into groups, runs every group through the batched per-cell driver while later cells still arrive, and
+ * hands back one sparse result at the end.  One device per session. */
+typedef struct oem_cells_stream oem_cells_stream;
+
+typedef struct {
+    uint32_t n_txps;
+    int32_t  device;
+    uint32_t max_iter;        /* as oem_em_run_cells */
+    double   conv_thresh;
+    uint32_t coverage;        /* 0: no coverage model (w = as_prob); 1: the per-cell coverage model from the pushed
+                                 coordinates, as oem_em_run_cells_coverage_sparse */
+    uint32_t bin_width;       /* coverage = 1 only, with model / growth_rate as in that call */
+    int32_t  model;
+    double   growth_rate;
+    uint64_t group_nnz;       /* 0 = default: a group is started once this many alignments are staged ... */
+    uint32_t group_cells;     /* 0 = default: ... or this many cells; the limits of oem_em_run_cells' own group rule
+                                 (transcript space < 2^32, 65 535 cells, tile x bucket table) always apply */
+    uint64_t max_staged_nnz;  /* 0 = default: push blocks while more than this is staged and not yet on the device */
+    uint32_t reserved[4];     /* 0 */
+} oem_cells_stream_opts;
+
+#define OEM_CELLS_STREAM_INFO_CELLS 1u                /* cells accepted */
+#define OEM_CELLS_STREAM_INFO_ALIGNMENTS 2u           /* alignments accepted */
+#define OEM_CELLS_STREAM_INFO_GROUPS 3u               /* groups a device worker has started */
+#define OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH 4u /* ... of these, before oem_cells_stream_finish was called:
+                                                         above 0, arrival and compute overlapped */
+#define OEM_CELLS_STREAM_INFO_BLOCKED_US 5u           /* microseconds pushes spent blocked on back-pressure, summed
+                                                         over the pushing threads */
+#define OEM_CELLS_STREAM_INFO_GROUPS_BATCHED 6u       /* groups that ran as one batched store (the others: cell by cell) */
+
+/* Argument errors (n_txps = 0, opts or out NULL, coverage = 1 without txp_len, with bin_width = 0 or with a model
+ * other than 0 / 1, a non-zero reserved word) are reported before any device is touched; without a device the call
+ * returns OEM_ERR_NO_DEVICE.  txp_len (n_txps entries) is copied; it is not read with coverage = 0.  *out = NULL on
+ * any failure. */
+int oem_cells_stream_create(const oem_cells_stream_opts *opts, const uint64_t *txp_len, oem_cells_stream **out);
+/* One cell: its own CSR (row_ptr: n_reads + 1 entries starting at 0; tid, as_prob: nnz) and, with coverage = 1, its
+ * alignments' coordinates (NULL otherwise).  Thread-safe.  The cell is checked on the calling thread (row_ptr[0] = 0,
+ * non-decreasing, row_ptr[n_reads] = nnz, every tid < n_txps, coordinates present under coverage = 1) and its arrays
+ * are copied: the caller may free them on return.  *out_ticket (optional) receives the cell's ticket: 0, 1, 2 ... in
+ * the order in which pushes were accepted; cell k of the result is the cell with ticket k.  A cell without reads is
+ * allowed.  An argument error (OEM_ERR_ARG) rejects that cell only: no ticket is used up and the session stays
+ * usable.  The call blocks while more than max_staged_nnz alignments are staged and not yet on the device, except that
+ * a cell larger than that budget is accepted when nothing else is staged.  A device or allocation failure in a group
+ * is sticky: every later push and finish returns that status and its message.  After finish: OEM_ERR_STATE. */
+int oem_cells_stream_push(oem_cells_stream *s, const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
+                          const uint32_t *aln_start, const uint32_t *aln_end, uint64_t n_reads, uint64_t nnz,
+                          uint64_t *out_ticket);
+/* Runs what is still staged, waits for every group and returns the cells in ticket order as an ordinary
+ * oem_cells_result (oem_cells_result_dims / _copy / _destroy; infos included).  Per cell the result is what
+ * oem_em_run_cells_sparse (coverage = 1: oem_em_run_cells_coverage_sparse) gives for that cell, up to floating-point
+ * summation order: which group a cell lands in may change the tile layout, never the problem.  A session without
+ * cells gives a result with 0 cells.  While a push is in flight, or a second time: OEM_ERR_STATE.  *out = NULL on any
+ * failure. */
+int oem_cells_stream_finish(oem_cells_stream *s, oem_cells_result **out);
+int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, uint64_t *value);
+/* NULL: no-op.  Before finish: cancels -- groups not yet started are dropped, a group on the device runs to its end,
+ * the workers are joined.  No push may be in flight. */
+void oem_cells_stream_destroy(oem_cells_stream *s);
 
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */

@@ -10,10 +10,10 @@ path fail, and without a HIP device every compute call raises ``OemError``.
 from ._lib import OemError, device_count  # noqa: F401
 from .types import (AlignmentFilters, DeviceStore, EMInfo, InMemoryAlignmentStore,  # noqa: F401
                     RunInfo, TranscriptInfo)
-from .em import (bootstrap, cells_coverage_probs, em, em_cells, em_cells_coverage_sparse, em_cells_sparse,  # noqa: F401
+from .em import (CellsStream, bootstrap, cells_coverage_probs, em, em_cells, em_cells_coverage_sparse, em_cells_sparse,  # noqa: F401
                  em_par)
 
 __all__ = [
-    "AlignmentFilters", "DeviceStore", "EMInfo", "InMemoryAlignmentStore", "RunInfo",
+    "CellsStream", "AlignmentFilters", "DeviceStore", "EMInfo", "InMemoryAlignmentStore", "RunInfo",
     "TranscriptInfo", "bootstrap", "cells_coverage_probs", "em", "em_cells", "em_cells_coverage_sparse", "em_cells_sparse", "em_par", "OemError", "device_count",
 ]

@@ -30,6 +30,12 @@ OEM_COMM_OPT_P2P_SELF_CHECK = 4
 OEM_COMM_INFO_RANKS = 1
 OEM_COMM_INFO_RCCL_RANKS = 2
 OEM_COMM_INFO_P2P_CONNECTED = 3
+OEM_CELLS_STREAM_INFO_CELLS = 1
+OEM_CELLS_STREAM_INFO_ALIGNMENTS = 2
+OEM_CELLS_STREAM_INFO_GROUPS = 3
+OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH = 4
+OEM_CELLS_STREAM_INFO_BLOCKED_US = 5
+OEM_CELLS_STREAM_INFO_GROUPS_BATCHED = 6
 OEM_INFO_WEIGHT_DICT_ENTRIES = 1
 OEM_INFO_TILES = 2
 OEM_INFO_REMOTE_ALIGNMENTS = 3
@@ -47,6 +53,8 @@ ABI_SYMBOLS = [
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
+    "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_finish", "oem_cells_stream_info",
+    "oem_cells_stream_destroy",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
     "oem_comm_set_option", "oem_comm_info", "oem_store_attach_comm",
     "oem_time_m_step", "oem_time_em_iters", "oem_time_bootstrap_passes", "oem_time_allreduce",
@@ -90,6 +98,13 @@ class DiscardTableC(C.Structure):
 
 
 REC_UNMAPPED, REC_REVERSE, REC_SUPPLEMENTARY, REC_HAS_SCORE = 1, 2, 4, 8
+
+
+class CellsStreamOptsC(C.Structure):
+    _fields_ = [("n_txps", C.c_uint32), ("device", C.c_int32), ("max_iter", C.c_uint32), ("conv_thresh", C.c_double),
+                ("coverage", C.c_uint32), ("bin_width", C.c_uint32), ("model", C.c_int32), ("growth_rate", C.c_double),
+                ("group_nnz", C.c_uint64), ("group_cells", C.c_uint32), ("max_staged_nnz", C.c_uint64),
+                ("reserved", C.c_uint32 * 4)]
 
 
 class StoreOptsC(C.Structure):
@@ -155,6 +170,12 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_result_destroy.restype = None
     L.oem_em_run_cells_coverage_sparse.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, f64, i32,
                                                    u32, f64, vp, C.POINTER(vp)]
+    L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
+    L.oem_cells_stream_push.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]
+    L.oem_cells_stream_finish.argtypes = [vp, C.POINTER(vp)]
+    L.oem_cells_stream_info.argtypes = [vp, u32, C.POINTER(u64)]
+    L.oem_cells_stream_destroy.argtypes = [vp]
+    L.oem_cells_stream_destroy.restype = None
     L.oem_comm_unique_id.argtypes = [vp]
     L.oem_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.oem_comm_destroy.argtypes = [vp]

@@ -508,11 +508,16 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
     auto relabel_on_device = [&](bool compact) -> int {
         if (!relabel || nnz == 0) return OEM_OK;
         if (m.wide_ptr) return fail(OEM_ERR_ARG, "per-cell batch needs fewer than 2^32 alignments");
-        unsigned long long *d_off = nullptr;
+        unsigned long long *d_off_own = nullptr; // (the caller's device copy of the offsets, when it has one)
+        const unsigned long long *d_off = relabel->d_cell_row_off;
         uint32_t *d_counts = nullptr;
-        OEM_HIP(hipMalloc((void **)&d_off, sizeof(unsigned long long) * ((size_t)relabel->n_cells + 1)));
-        hipError_t e = hipMemcpy(d_off, relabel->cell_row_off, sizeof(unsigned long long) * ((size_t)relabel->n_cells + 1),
-                                 hipMemcpyHostToDevice);
+        hipError_t e = hipSuccess;
+        if (!d_off) {
+            OEM_HIP(hipMalloc((void **)&d_off_own, sizeof(unsigned long long) * ((size_t)relabel->n_cells + 1)));
+            e = hipMemcpy(d_off_own, relabel->cell_row_off, sizeof(unsigned long long) * ((size_t)relabel->n_cells + 1),
+                          hipMemcpyHostToDevice);
+            d_off = d_off_own;
+        }
         const dim3 rgrid((uint32_t)((n_reads + 255) / 256));
         const size_t n_rank = (size_t)relabel->n_cells * relabel->cell_txps;
         if (e == hipSuccess && compact) {
@@ -558,7 +563,7 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
                                (const uint32_t *)m.row_ptr, m.tid, d_off, relabel->n_cells, relabel->cell_txps, n_reads);
             e = hipStreamSynchronize(s->stream);
         }
-        hipFree(d_off);
+        hipFree(d_off_own);
         hipFree(d_counts);
         if (e != hipSuccess) return fail(OEM_ERR_HIP, "relabelling the cells failed: %s", hipGetErrorString(e));
         return OEM_OK;
@@ -580,6 +585,10 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
         // (rare: the device builder declines only stores the host one mostly declines too -- a read with too many
         // alignments inside one window)
         if (resident) OEM_TRY(weights_to_host(m.w64, m.w32));
+        if (!row_ptr && resident && resident->host_row_ptr) { // (host_tids reads it too)
+            row_ptr = resident->host_row_ptr(resident->host_row_ptr_ctx);
+            if (!row_ptr) return fail(OEM_ERR_OOM, "host row pointers for the host layout builder: allocation failed");
+        }
         TiledHost h;
         const char *err = nullptr;
         if (build_tiled_layout(row_ptr, host_tids(), as_prob, cov_prob, n_reads, nnz, m.n_txps, &h, &err,

@@ -14,34 +14,9 @@
 #include <utility>
 #include <vector>
 
-#include "oem_driver.h"
+#include "oem_cells.h"
 
 namespace oem {
-
-// std::vector storage whose resize leaves new elements default-initialised: a block's entries are written by the
-// device read-back, there is no point in zeroing them first
-template <typename T>
-struct NoInitAlloc : std::allocator<T> {
-    template <typename U>
-    struct rebind {
-        using other = NoInitAlloc<U>;
-    };
-    NoInitAlloc() = default;
-    template <typename U>
-    NoInitAlloc(const NoInitAlloc<U> &) noexcept {}
-    template <typename U>
-    void construct(U *p) noexcept(std::is_nothrow_default_constructible<U>::value) { ::new ((void *)p) U; }
-    template <typename U, typename... A>
-    void construct(U *p, A &&...a) { ::new ((void *)p) U(std::forward<A>(a)...); }
-};
-
-// The sparse results of one group of cells (oem_em_run_cells_sparse): entries per cell, then every cell's columns and
-// values one after the other, in cell order.
-struct SparseBlock {
-    std::vector<uint32_t> counts;
-    std::vector<uint32_t, NoInitAlloc<uint32_t>> col;
-    std::vector<float, NoInitAlloc<float>> val;
-};
 
 namespace {
 
@@ -84,13 +59,6 @@ thread_local CellsTiming *t_timing = nullptr;
 // The groups of the last per-cell call of this thread and the path each one took, for oem_debug_cells_last_paths.
 thread_local std::vector<CellsGroupPath> t_cells_paths;
 
-// Where the groups of one call put their results: the caller's dense n_cells x n_txps matrix (oem_em_run_cells), or
-// one SparseBlock per group index (oem_em_run_cells_sparse: groups finish in any order).
-struct CellsSink {
-    double *dense = nullptr;
-    std::vector<SparseBlock> *blocks = nullptr;
-};
-
 // Device buffers of the count / scan / emit steps, kept across the cells of a cell-by-cell group.
 struct NzScratch {
     uint32_t *counts = nullptr;
@@ -112,9 +80,9 @@ struct NzScratch {
 
 // single_cell.rs:151-160 on the device: the entries > 0.0 of cells [0, n_cells) of `src`, in ascending transcript id,
 // appended to `blk` (k_cells_nz_count, a host scan of the counts, k_cells_nz_emit, then only the entries cross PCIe).
-// cell_row_off / row_ptr: the cells' reads and alignments -- a cell cannot have more entries than alignments.
-int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, const uint64_t *cell_row_off,
-                 const uint64_t *row_ptr, NzScratch &sc, SparseBlock *blk)
+// cell_aln_off: the cells' first alignments -- a cell cannot have more entries than alignments.
+int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, const uint64_t *cell_aln_off, NzScratch &sc,
+                 SparseBlock *blk)
 {
     if (n_cells == 0) return OEM_OK;
     if (n_cells > sc.cap_cells) {
@@ -136,7 +104,7 @@ int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, con
     std::vector<uint64_t> off((size_t)n_cells + 1);
     off[0] = 0;
     for (uint32_t c = 0; c < n_cells; ++c) {
-        const uint64_t aligned = row_ptr[cell_row_off[c + 1]] - row_ptr[cell_row_off[c]];
+        const uint64_t aligned = cell_aln_off[c + 1] - cell_aln_off[c];
         if (h_counts[c] > src.T || h_counts[c] > aligned)
             return fail(OEM_ERR_STATE, "oem_em_run_cells_sparse: cell %u has %u entries, more than its %llu alignments or %u transcripts",
                         c, h_counts[c], (unsigned long long)aligned, src.T);
@@ -170,7 +138,8 @@ int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, con
 
 // All cells in one store over the concatenated transcript space; every pass serves every
 // unfinished cell.  Returns *used = false (nothing done) when the batch form does not apply.
-int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+int run_cells_batched(const uint64_t *cell_row_off, const uint64_t *cell_aln_off, const unsigned long long *d_cell_row_off,
+                      uint32_t n_cells, const uint64_t *row_ptr,
                       const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads,
                       uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
                       double *out, SparseBlock *blk, oem_run_info *infos, bool *used, ResidentCsr *resident)
@@ -188,7 +157,7 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
     opts.reorder_rows = 0; // a batch that cannot be tiled falls through to the cell-by-cell path
     opts.problem_size = n_txps;
     // transcripts of cell p -> [p*T, (p+1)*T), relabelled on the device after the upload
-    CellRelabel rl{cell_row_off, n_cells, n_txps};
+    CellRelabel rl{cell_row_off, n_cells, n_txps, d_cell_row_off};
     int rc = create_store_impl(row_ptr, tid, as_prob, cov_prob, n_reads, nnz, (uint32_t)total_txps, device, &opts, s, &rl,
                                resident);
     if (rc != OEM_OK) {
@@ -200,9 +169,11 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
             resident->row_ptr = (uint32_t *)s->csr.row_ptr;
             resident->tid = s->csr.tid;
             resident->w64 = s->csr.w64;
+            resident->w32 = s->csr.w32;
             s->csr.row_ptr = nullptr;
             s->csr.tid = nullptr;
             s->csr.w64 = nullptr;
+            s->csr.w32 = nullptr;
             if (nnz && hipMemcpy(resident->tid, tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice) != hipSuccess)
                 rc = fail(OEM_ERR_HIP, "oem_em_run_cells: restoring the transcript ids failed");
         }
@@ -324,7 +295,7 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
                 src.T = caller_txps;
                 src.stride = n_txps;
                 NzScratch sc;
-                if ((rc2 = cells_to_csr(s->stream, src, n_cells, cell_row_off, row_ptr, sc, blk)) != OEM_OK) break;
+                if ((rc2 = cells_to_csr(s->stream, src, n_cells, cell_aln_off, sc, blk)) != OEM_OK) break;
                 if (hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
                     rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: state read-back failed");
                     break;
@@ -386,17 +357,19 @@ int run_cells_batched(const uint64_t *cell_row_off, uint32_t n_cells, const uint
     return rc;
 }
 
+} // namespace
+
 // One group of consecutive cells [c0, c1): batched on the device when it can be (every pass over the
 // resident store serves all unfinished cells), otherwise cell after cell over the caller-order CSR.
 int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, const uint64_t *row_ptr,
                     const uint32_t *tid, const float *as_prob, const double *cov_prob, const CellsCoverage *cov_src,
                     uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g,
-                    oem_run_info *infos, bool *batched)
+                    oem_run_info *infos, bool *batched, const CellsGroupDevice *dev)
 {
     *batched = false;
     const uint32_t n_cells = c1 - c0;
     const uint64_t r0 = cell_row_off[c0], r1 = cell_row_off[c1];
-    const uint64_t a0 = row_ptr[r0], a1 = row_ptr[r1];
+    const uint64_t a0 = dev ? 0 : row_ptr[r0], a1 = dev ? dev->nnz : row_ptr[r1];
     const uint64_t n_reads = r1 - r0, nnz = a1 - a0;
     // The group's own offsets.  A group that starts at read 0 (the whole experiment, when it fits one group)
     // takes the caller's arrays as they are: rebasing 31 M row offsets of a 625-cell batch into a fresh
@@ -424,6 +397,14 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
         off_p = off_v.data();
         rp_p = rp_v.data();
     }
+    // the cells' first alignments within the group
+    std::vector<uint64_t> aoff_v;
+    const uint64_t *aoff_p = dev ? dev->cell_aln_off : nullptr;
+    if (!dev) {
+        aoff_v.resize((size_t)n_cells + 1);
+        for (uint32_t c = 0; c <= n_cells; ++c) aoff_v[c] = rp_p[off_p[c]];
+        aoff_p = aoff_v.data();
+    }
     const uint32_t *tid_g = tid ? tid + a0 : nullptr;
     const float *p_g = as_prob ? as_prob + a0 : nullptr;
     const double *cov_g = cov_prob ? cov_prob + a0 : nullptr;
@@ -432,16 +413,18 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
     oem_run_info *infos_g = infos ? infos + c0 : nullptr;
     // the coverage model of the group's cells, computed on the device: the weights stay there for the store
     ResidentCsr res_csr;
-    ResidentCsr *resident = nullptr;
+    ResidentCsr *resident = dev ? dev->resident : nullptr;
     if (cov_src) {
         OEM_TRY(ensure_device(device));
-        OEM_TRY(cells_coverage_group(*cov_src, off_p, n_cells, c0, rp_p, tid_g, p_g, a0, n_reads, nnz, &res_csr));
-        resident = &res_csr;
+        if (!resident) resident = &res_csr;
+        OEM_TRY(cells_coverage_group(*cov_src, off_p, aoff_p, n_cells, dev ? dev->first_cell : c0, rp_p, tid_g, p_g,
+                                     dev ? dev->aln_start : cov_src->aln_start + a0, dev ? dev->aln_end : cov_src->aln_end + a0,
+                                     cov_src->out_cov_prob ? cov_src->out_cov_prob + a0 : nullptr, n_reads, nnz, resident));
     }
 
     if (knob("OEM_SERIAL_CELLS", 0) == 0) { // testing build: force the cell-by-cell path
         bool used = false;
-        int rcb = run_cells_batched(off_p, n_cells, rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device,
+        int rcb = run_cells_batched(off_p, aoff_p, dev ? dev->d_cell_row_off : nullptr, n_cells, rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device,
                                     max_iter, conv_thresh, out_g, blk, infos_g, &used, resident);
         *batched = used;
         if (rcb != OEM_OK || used) return rcb;
@@ -478,13 +461,12 @@ int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, cons
         rc = run_em_device(s, a, infos_g ? &infos_g[c] : nullptr);
         src.v = s->cnt;
         if (rc == OEM_OK)
-            rc = blk ? cells_to_csr(s->stream, src, 1, off_p + c, rp_p, sc, blk) : copy_counts_out(s, out_g + (uint64_t)c * n_txps);
+            rc = blk ? cells_to_csr(s->stream, src, 1, aoff_p + c, sc, blk) : copy_counts_out(s, out_g + (uint64_t)c * n_txps);
     }
     free_store(s);
     return rc;
 }
 
-} // namespace
 } // namespace oem
 
 namespace oem {
@@ -498,6 +480,20 @@ const std::vector<CellsGroupPath> &cells_last_paths() { return t_cells_paths; }
 } // namespace oem
 
 namespace oem {
+
+uint64_t cells_max_group_nnz() { return (uint64_t)knob("OEM_CELLS_GROUP_NNZ", 1l << 30); } // testing build: small groups
+
+bool cells_group_fits(uint64_t cells, uint64_t reads, uint64_t gnnz, uint32_t n_txps, uint64_t max_group_nnz)
+{
+    const uint64_t buckets = (cells * n_txps + kBucket - 1) / kBucket;
+    // tiles per group: ~300 reads per tile with the narrow window cap on sparse cells, ~700 with the
+    // wide one that create_store_impl picks below 4 reads per transcript
+    const bool wide = reads < 2 * cells * n_txps && reads >= 1000000; // as create_store_impl chooses
+    const uint64_t tiles_est = reads / (wide ? 600 : 256) + 2 * cells;
+    return !(cells * n_txps >= (1ull << 32) || reads >= (1ull << 32) || gnnz > max_group_nnz ||
+             tiles_est * buckets > (1ull << 29) || cells > 65535 /* gridDim.y of the per-cell kernels */);
+}
+
 namespace {
 
 // The body of both per-cell entry points (`who` names the caller in messages): argument checks, the NaN-coverage
@@ -534,7 +530,7 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     // Cells are independent problems, so a large experiment is cut into groups of consecutive cells
     // that bound the batched store (transcript space < 2^32, <= 2^30 alignments, and the layout
     // builder's tile x bucket table); each group is one batched run on the device.
-    const uint64_t max_group_nnz = (uint64_t)knob("OEM_CELLS_GROUP_NNZ", 1l << 30); // testing build: small groups
+    const uint64_t max_group_nnz = cells_max_group_nnz();
     std::vector<std::pair<uint32_t, uint32_t>> groups;
     uint32_t c0 = 0;
     while (c0 < n_cells) {
@@ -543,14 +539,7 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
             const uint64_t cells = (uint64_t)(c1 + 1 - c0);
             const uint64_t reads = cell_row_off[c1 + 1] - cell_row_off[c0];
             const uint64_t gnnz = row_ptr[cell_row_off[c1 + 1]] - row_ptr[cell_row_off[c0]];
-            const uint64_t buckets = (cells * n_txps + kBucket - 1) / kBucket;
-            // tiles per group: ~300 reads per tile with the narrow window cap on sparse cells, ~700 with the
-            // wide one that create_store_impl picks below 4 reads per transcript
-            const bool wide = reads < 2 * cells * n_txps && reads >= 1000000; // as create_store_impl chooses
-            const uint64_t tiles_est = reads / (wide ? 600 : 256) + 2 * cells;
-            if (cells * n_txps >= (1ull << 32) || reads >= (1ull << 32) || gnnz > max_group_nnz ||
-                tiles_est * buckets > (1ull << 29) || cells > 65535 /* gridDim.y of the per-cell kernels */)
-                break;
+            if (!cells_group_fits(cells, reads, gnnz, n_txps, max_group_nnz)) break;
             ++c1;
         }
         groups.emplace_back(c0, c1);
@@ -641,16 +630,6 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
 
 using namespace oem;
 
-// one call's sparse results (immutable once returned): the groups' blocks in group order -- which is cell order --
-// and the cells' offsets; oem_cells_result_copy concatenates the blocks straight into the caller's arrays
-struct oem_cells_result {
-    uint32_t n_cells = 0;
-    uint64_t n_entries = 0;
-    std::vector<uint64_t> cell_off; // n_cells + 1
-    std::vector<SparseBlock> blocks;
-    std::vector<oem_run_info> infos; // n_cells
-};
-
 // ---------------------------------------------------------------------------
 // single-cell batch
 // ---------------------------------------------------------------------------
@@ -668,22 +647,9 @@ extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, 
     OEM_API_END("oem_em_run_cells")
 }
 
-namespace {
-// The body of both sparse entry points: the groups' blocks become one oem_cells_result.
-int run_cells_sparse(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
-                     const uint32_t *tid, const float *as_prob, const double *cov_prob, CellsCoverage *cov_src,
-                     uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
-                     oem_cells_result **out)
+int oem::cells_result_from_blocks(const char *who, std::vector<SparseBlock> &blocks, oem_cells_result *r)
 {
-    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
-    r->n_cells = n_cells;
-    r->infos.resize(n_cells);
-    std::vector<SparseBlock> blocks;
-    CellsSink sink;
-    sink.blocks = &blocks;
-    OEM_TRY(run_cells(who, cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps, device, max_iter,
-                      conv_thresh, sink, r->infos.data(), cov_src));
-    // the cells' offsets from the groups' blocks, in group (= cell) order
+    const uint32_t n_cells = r->n_cells;
     r->cell_off.assign((size_t)n_cells + 1, 0);
     uint32_t c = 0;
     for (const SparseBlock &b : blocks) {
@@ -700,6 +666,25 @@ int run_cells_sparse(const char *who, const uint64_t *cell_row_off, uint32_t n_c
     if (c != n_cells) return fail(OEM_ERR_STATE, "%s: the groups' results cover %u of %u cells", who, c, n_cells);
     r->n_entries = r->cell_off[n_cells];
     r->blocks = std::move(blocks);
+    return OEM_OK;
+}
+
+namespace {
+// The body of both sparse entry points: the groups' blocks become one oem_cells_result.
+int run_cells_sparse(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                     const uint32_t *tid, const float *as_prob, const double *cov_prob, CellsCoverage *cov_src,
+                     uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
+                     oem_cells_result **out)
+{
+    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
+    r->n_cells = n_cells;
+    r->infos.resize(n_cells);
+    std::vector<SparseBlock> blocks;
+    CellsSink sink;
+    sink.blocks = &blocks;
+    OEM_TRY(run_cells(who, cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps, device, max_iter,
+                      conv_thresh, sink, r->infos.data(), cov_src));
+    OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
     *out = r.release();
     return OEM_OK;
 }

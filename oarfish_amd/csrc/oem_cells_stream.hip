@@ -1,0 +1,617 @@
+// oem_cells_stream.hip -- the per-cell session (oem_cells_stream_*): cells are pushed one by one, from any number of
+// threads (single_cell.rs:96-193: N workers each pop one cell and build its store), staged in host memory, cut into
+// groups and run through the per-cell driver's unit of work (run_cells_group, oem_cells.hip) by two device workers
+// while later cells still arrive.
+//
+//   push      checks the cell on the calling thread, reserves its place in the open group under the session lock
+//             (ticket, read and alignment offsets) and copies the arrays outside the lock.  The open group is closed --
+//             handed to the workers -- once it holds group_nnz alignments or group_cells cells, when the next cell would
+//             break the driver's group rule (cells_group_fits), or when a push has to wait for room.
+//   staging   one allocation per group: the cells' row pointers AS PUSHED (each cell's n + 1 entries, starting at 0),
+//             ids, probabilities and, for the coverage model, coordinates.  Pinned (page-locked) memory, so that the
+//             upload of one group is an asynchronous copy under the other worker's EM loop; pageable when the pinned
+//             allocation fails.  Arenas are reused from group to group.
+//   worker    uploads the row pointers with the per-cell read / alignment offset tables; k_stream_row_ptr builds the
+//             group's u32 row pointers and its cell_row_off on the device and range-checks them in the same pass (no
+//             host pass over the reads of the group).  The store adopts these buffers (ResidentCsr), and
+//             run_cells_group does the rest exactly as for a group of a one-call run, fallbacks included.
+//   finish    closes the last group, joins the workers and concatenates the groups' blocks in ticket order.
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <condition_variable>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "oem_cells.h"
+
+namespace oem {
+namespace {
+
+// Defaults of oem_cells_stream_opts.  group_nnz is the best point of the one sweep that exists (scripts/
+// cells_stream_bench.py, profiles/cells_stream_bench.json: 625 cells x 400 k alignments from 8 pushing threads, 8 / 16 /
+// 32 / 64 / 128 Mi alignments per group: 1.15 / 0.83 / 0.83 / 0.90 / 0.99 s) -- larger groups start the device late,
+// smaller ones run their few tiles badly, as the head-split experiment of run_cells had it.  group_cells and
+// max_staged_nnz (two groups' worth) have NOT been measured.
+constexpr uint64_t kDefaultGroupNnz = 32ull << 20;
+constexpr uint32_t kDefaultGroupCells = 65535; // (the driver's own bound: gridDim.y of the per-cell kernels)
+constexpr int kStreamWorkers = 2;              // as run_cells: one group's upload and layout under the other's loop
+constexpr int kPinnedArenas = 4;               // open + queued + one per worker; further arenas are pageable
+constexpr uint64_t kFirstArenaNnz = 1ull << 20; // an arena starts small and grows x4 up to the group's size
+
+// One lane per read of the group: its cell by binary search in the read-offset table, then the group-wide u32 row
+// pointer from the cell's own (0-based) one, range-checked on the way.  The first n_cells + 1 lanes also write the
+// group's cell_row_off.  rp_local holds every cell's n + 1 entries one after the other: cell c starts at
+// read_off[c] + c.
+__global__ __launch_bounds__(256) void k_stream_row_ptr(const unsigned long long *__restrict__ rp_local,
+                                                        const unsigned long long *__restrict__ read_off,
+                                                        const unsigned long long *__restrict__ aln_off, uint32_t n_cells,
+                                                        uint64_t n_reads, uint32_t *__restrict__ row_ptr,
+                                                        unsigned long long *__restrict__ cell_row_off, uint32_t *__restrict__ err)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r <= n_cells) cell_row_off[r] = read_off[r];
+    if (r == 0) row_ptr[n_reads] = (uint32_t)aln_off[n_cells];
+    if (r >= n_reads) return;
+    uint32_t a = 0, b = n_cells; // last cell whose first read is <= r (empty cells share offsets: never the last)
+    while (b - a > 1) {
+        const uint32_t m = (a + b) >> 1;
+        if (read_off[m] <= r) a = m;
+        else b = m;
+    }
+    const uint64_t first = read_off[a], i = r - first;
+    const uint64_t cell_reads = read_off[a + 1] - first, cell_nnz = aln_off[a + 1] - aln_off[a];
+    const unsigned long long *loc = rp_local + first + a;
+    const uint64_t v0 = loc[i], v1 = loc[i + 1];
+    const bool bad = v1 < v0 || v1 > cell_nnz || (i == 0 && v0 != 0) || (i + 1 == cell_reads && v1 != cell_nnz);
+    if (bad) atomicOr(err, 1u);
+    row_ptr[r] = (uint32_t)(aln_off[a] + (bad ? 0 : v0));
+}
+
+// The host staging of one group, one allocation.
+struct Staging {
+    void *base = nullptr;
+    bool pinned = false;
+    uint64_t cap_nnz = 0, cap_rp = 0;
+    uint64_t *rp = nullptr;
+    uint32_t *tid = nullptr, *start = nullptr, *end = nullptr;
+    float *p = nullptr;
+    Staging() = default;
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging()
+    {
+        if (pinned) (void)hipHostFree(base);
+        else free(base);
+    }
+    static std::unique_ptr<Staging> make(uint64_t cap_nnz, uint64_t cap_rp, bool coverage, bool try_pinned)
+    {
+        std::unique_ptr<Staging> s(new Staging());
+        const size_t bytes = sizeof(uint64_t) * cap_rp + (coverage ? 16 : 8) * cap_nnz + 64;
+        if (try_pinned && hipHostMalloc(&s->base, bytes, hipHostMallocPortable) == hipSuccess) {
+            s->pinned = true;
+        } else {
+            if (try_pinned) (void)hipGetLastError();
+            s->base = malloc(bytes);
+            if (!s->base) throw std::bad_alloc();
+        }
+        s->cap_nnz = cap_nnz;
+        s->cap_rp = cap_rp;
+        char *q = (char *)s->base;
+        s->rp = (uint64_t *)q;
+        q += sizeof(uint64_t) * cap_rp;
+        s->tid = (uint32_t *)q;
+        q += sizeof(uint32_t) * cap_nnz;
+        s->p = (float *)q;
+        q += sizeof(float) * cap_nnz;
+        if (coverage) {
+            s->start = (uint32_t *)q;
+            q += sizeof(uint32_t) * cap_nnz;
+            s->end = (uint32_t *)q;
+        }
+        return s;
+    }
+};
+
+struct Group {
+    std::unique_ptr<Staging> st;
+    size_t index = 0;          // the group's number: its place in the result
+    uint64_t first_ticket = 0;
+    uint32_t n_cells = 0;
+    uint64_t n_reads = 0, nnz = 0;
+    std::vector<uint64_t> read_off{0}, aln_off{0}; // n_cells + 1 each
+    int pending = 0;           // pushes still copying into the staging
+    std::vector<uint64_t> host_rp; // the concatenated row pointers, only when the host layout builder asks
+    uint64_t rp_used() const { return n_reads + n_cells; }
+
+    static const uint64_t *host_row_ptr(void *ctx)
+    {
+        Group *g = (Group *)ctx;
+        try {
+            if (g->host_rp.empty()) {
+                g->host_rp.resize(g->n_reads + 1);
+                for (uint32_t c = 0; c < g->n_cells; ++c) {
+                    const uint64_t r0 = g->read_off[c], n = g->read_off[c + 1] - r0;
+                    const uint64_t *loc = g->st->rp + r0 + c;
+                    for (uint64_t i = 0; i < n; ++i) g->host_rp[r0 + i] = g->aln_off[c] + loc[i];
+                }
+                g->host_rp[g->n_reads] = g->nnz;
+            }
+            return g->host_rp.data();
+        } catch (...) {
+            return nullptr;
+        }
+    }
+};
+
+struct GroupResult {
+    SparseBlock blk;
+    std::vector<oem_run_info> infos;
+};
+
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+};
+
+} // namespace
+} // namespace oem
+
+using namespace oem;
+
+struct oem_cells_stream {
+    oem_cells_stream_opts o;
+    uint64_t group_nnz = 0, max_staged = 0;
+    uint32_t group_cells = 0;
+    std::vector<uint64_t> txp_len;
+    CellsCoverage cov;
+
+    mutable std::mutex mu;
+    std::condition_variable cv_work, cv_space, cv_copy;
+    std::unique_ptr<Group> open;
+    std::deque<std::unique_ptr<Group>> queue;
+    std::vector<std::unique_ptr<Staging>> pool;
+    std::vector<GroupResult> results; // by group index
+    int arenas_pinned = 0;
+    uint64_t arena_nnz = 0, arena_rp = 0; // what a new group's arena starts with (the high-water mark so far)
+    uint64_t next_ticket = 0, total_nnz = 0, staged_nnz = 0;
+    uint64_t groups_started = 0, groups_before_finish = 0, groups_batched = 0, blocked_us = 0;
+    int pushes_in_flight = 0;
+    bool finish_called = false, stop = false, cancel = false;
+    int sticky_rc = OEM_OK;
+    std::string sticky_msg;
+    std::vector<std::thread> workers;
+
+    uint64_t full_arena_nnz() const { return group_nnz + group_nnz / 8 + 4096; }
+    uint64_t full_arena_rp() const { return full_arena_nnz() / 2 + 65536 + 8; }
+
+    // (mu held) an arena of at least this capacity: from the pool, or a new one
+    std::unique_ptr<Staging> take_arena(uint64_t need_nnz, uint64_t need_rp)
+    {
+        for (size_t k = 0; k < pool.size(); ++k)
+            if (pool[k]->cap_nnz >= need_nnz && pool[k]->cap_rp >= need_rp) {
+                std::unique_ptr<Staging> s = std::move(pool[k]);
+                pool.erase(pool.begin() + k);
+                return s;
+            }
+        if (!pool.empty()) { // too small for this group: not kept
+            if (pool.back()->pinned) --arenas_pinned;
+            pool.pop_back();
+        }
+        const bool try_pinned = arenas_pinned < kPinnedArenas && hipSetDevice(o.device) == hipSuccess;
+        StageTimer tm;
+        std::unique_ptr<Staging> s = Staging::make(need_nnz, need_rp, o.coverage != 0, try_pinned);
+        if (s->pinned) ++arenas_pinned;
+        if (tm.on)
+            fprintf(stderr, "[oem] stream: new %s arena for %llu alignments, %llu row pointers\n", s->pinned ? "pinned" : "pageable",
+                    (unsigned long long)need_nnz, (unsigned long long)need_rp);
+        tm.lap("stream: arena allocation");
+        return s;
+    }
+    void give_arena(std::unique_ptr<Staging> s)
+    {
+        if (!s) return;
+        if (pool.size() < (size_t)kPinnedArenas) {
+            pool.push_back(std::move(s));
+        } else if (s->pinned) {
+            --arenas_pinned;
+        }
+    }
+    // (mu held) the open group goes to the workers
+    void close_open()
+    {
+        if (!open) return;
+        if (open->n_cells == 0) {
+            give_arena(std::move(open->st));
+            open.reset();
+            return;
+        }
+        queue.push_back(std::move(open));
+        cv_work.notify_one();
+    }
+    void set_sticky(int rc, const char *msg)
+    {
+        if (sticky_rc != OEM_OK) return;
+        sticky_rc = rc;
+        sticky_msg = msg;
+    }
+
+    int run_group(Group &g, hipStream_t st, GroupResult *out, bool *batched, bool *uploaded);
+    void work(int wk);
+};
+
+// One closed group on a worker's stream: upload, row pointers on the device, then the driver's unit of work.
+int oem_cells_stream::run_group(Group &g, hipStream_t st, GroupResult *out, bool *batched, bool *uploaded)
+{
+    StageTimer tm;
+    const Staging &sg = *g.st;
+    const uint32_t nc = g.n_cells;
+    ResidentCsr res;
+    DevBuf<unsigned long long> d_rp, d_tab; // the cells' row pointers as pushed; read_off | aln_off | cell_row_off
+    DevBuf<uint32_t> d_err;
+    uint32_t h_err = 0;
+    OEM_TRY(dev_alloc(&res.row_ptr, g.n_reads + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_rp.p, g.rp_used(), nullptr));
+    OEM_TRY(dev_alloc(&d_tab.p, 3 * ((size_t)nc + 1), nullptr));
+    OEM_TRY(dev_alloc(&d_err.p, 1, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_rp.p, sg.rp, sizeof(uint64_t) * g.rp_used(), hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_tab.p, g.read_off.data(), sizeof(uint64_t) * (nc + 1), hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_tab.p + nc + 1, g.aln_off.data(), sizeof(uint64_t) * (nc + 1), hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemsetAsync(d_err.p, 0, sizeof(uint32_t), st));
+    const uint64_t lanes = std::max<uint64_t>(g.n_reads, (uint64_t)nc + 1);
+    hipLaunchKernelGGL(k_stream_row_ptr, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, st, d_rp.p, d_tab.p,
+                       d_tab.p + nc + 1, nc, g.n_reads, res.row_ptr, d_tab.p + 2 * ((size_t)nc + 1), d_err.p);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpyAsync(&h_err, d_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (!o.coverage) { // (with the coverage model the group's coverage step uploads ids and coordinates and writes w64)
+        OEM_TRY(dev_alloc(&res.tid, g.nnz, nullptr));
+        OEM_TRY(dev_alloc(&res.w32, g.nnz, nullptr));
+        if (g.nnz) {
+            OEM_HIP(hipMemcpyAsync(res.tid, sg.tid, sizeof(uint32_t) * g.nnz, hipMemcpyHostToDevice, st));
+            OEM_HIP(hipMemcpyAsync(res.w32, sg.p, sizeof(float) * g.nnz, hipMemcpyHostToDevice, st));
+        }
+    }
+    OEM_HIP(hipStreamSynchronize(st));
+    if (h_err)
+        return fail(OEM_ERR_STATE, "oem_cells_stream: the staged row pointers of the group of cell %llu fail the device's range check",
+                    (unsigned long long)g.first_ticket);
+    (void)hipFree(d_rp.p);
+    d_rp.p = nullptr;
+    tm.lap("stream: upload + row pointers");
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        staged_nnz -= g.nnz;
+        *uploaded = true;
+    }
+    cv_space.notify_all();
+
+    res.host_row_ptr = &Group::host_row_ptr;
+    res.host_row_ptr_ctx = &g;
+    CellsGroupDevice dev;
+    dev.resident = &res;
+    dev.d_cell_row_off = d_tab.p + 2 * ((size_t)nc + 1);
+    dev.cell_aln_off = g.aln_off.data();
+    dev.aln_start = sg.start;
+    dev.aln_end = sg.end;
+    dev.nnz = g.nnz;
+    dev.first_cell = g.first_ticket;
+    std::vector<SparseBlock> blocks(1);
+    CellsSink sink;
+    sink.blocks = &blocks;
+    out->infos.assign(nc, oem_run_info{});
+    OEM_TRY(run_cells_group(g.read_off.data(), 0, nc, nullptr, sg.tid, sg.p, nullptr, o.coverage ? &cov : nullptr, o.n_txps,
+                            o.device, o.max_iter, o.conv_thresh, sink, 0, out->infos.data(), batched, &dev));
+    out->blk = std::move(blocks[0]);
+    tm.lap("stream: group run");
+    return OEM_OK;
+}
+
+void oem_cells_stream::work(int wk)
+{
+    hipStream_t st = nullptr;
+    if (hipSetDevice(o.device) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+        std::lock_guard<std::mutex> lk(mu);
+        set_sticky(OEM_ERR_HIP, "oem_cells_stream: a device worker could not open its stream");
+        st = nullptr;
+    }
+    for (;;) {
+        std::unique_ptr<Group> g;
+        bool skip;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv_work.wait(lk, [&] { return !queue.empty() || stop; });
+            if (queue.empty()) break;
+            g = std::move(queue.front());
+            queue.pop_front();
+            skip = cancel || sticky_rc != OEM_OK || !st;
+            if (!skip) {
+                ++groups_started;
+                if (!finish_called) ++groups_before_finish;
+            }
+            cv_copy.wait(lk, [&] { return g->pending == 0; });
+        }
+        GroupResult res;
+        bool batched = false, uploaded = false;
+        int rc = OEM_OK;
+        std::string msg;
+        if (!skip) {
+            try {
+                rc = run_group(*g, st, &res, &batched, &uploaded);
+            } catch (const std::bad_alloc &) {
+                rc = fail(OEM_ERR_OOM, "oem_cells_stream: host allocation failed in a device worker");
+            } catch (const std::exception &e) {
+                rc = fail(OEM_ERR_STATE, "oem_cells_stream: %s", e.what());
+            }
+            if (rc != OEM_OK) msg = last_error_text(); // (the message is thread-local)
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!uploaded) staged_nnz -= g->nnz;
+            if (rc != OEM_OK) set_sticky(rc, msg.c_str());
+            else if (!skip) {
+                results[g->index] = std::move(res);
+                if (batched) ++groups_batched;
+            }
+            give_arena(std::move(g->st));
+        }
+        cv_space.notify_all();
+    }
+    if (st) {
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+    }
+    (void)wk;
+}
+
+extern "C" int oem_cells_stream_create(const oem_cells_stream_opts *opts, const uint64_t *txp_len, oem_cells_stream **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_create";
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (!opts) return fail(OEM_ERR_ARG, "%s: opts is NULL", who);
+    if (opts->n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
+    if (opts->coverage > 1) return fail(OEM_ERR_ARG, "%s: coverage must be 0 or 1", who);
+    for (uint32_t r : opts->reserved)
+        if (r) return fail(OEM_ERR_ARG, "%s: a reserved word is not 0", who);
+    if (opts->coverage) {
+        if (!txp_len) return fail(OEM_ERR_ARG, "%s: coverage = 1 needs txp_len", who);
+        if (opts->bin_width == 0)
+            return fail(OEM_ERR_ARG, "coverage model with 0 bin width is not implemented (logistic_probability.rs:59, binomial_probability.rs:192)");
+        if (opts->model != 0 && opts->model != 1) return fail(OEM_ERR_ARG, "%s: model must be 0 (logistic) or 1 (binomial)", who);
+        if (opts->n_txps >= (uint32_t)INT_MAX) return fail(OEM_ERR_ARG, "%s: needs n_txps < 2^31 - 1", who);
+    }
+    OEM_TRY(ensure_device(opts->device));
+    std::unique_ptr<oem_cells_stream> s(new oem_cells_stream());
+    s->o = *opts;
+    s->group_nnz = opts->group_nnz ? opts->group_nnz : kDefaultGroupNnz;
+    s->group_nnz = std::min(s->group_nnz, cells_max_group_nnz());
+    s->group_cells = opts->group_cells ? std::min(opts->group_cells, kDefaultGroupCells) : kDefaultGroupCells;
+    s->max_staged = opts->max_staged_nnz ? opts->max_staged_nnz : 2 * s->group_nnz; // not measured either
+    s->arena_nnz = std::min(kFirstArenaNnz, s->full_arena_nnz());
+    s->arena_rp = std::min(kFirstArenaNnz / 2 + 4096, s->full_arena_rp());
+    if (opts->coverage) { // the per-session part of the coverage model (the annotation), shared by the groups
+        s->txp_len.assign(txp_len, txp_len + opts->n_txps);
+        s->cov.txp_len = s->txp_len.data();
+        s->cov.n_txps = opts->n_txps;
+        s->cov.bin_width = opts->bin_width;
+        s->cov.model = opts->model;
+        s->cov.growth_rate = opts->growth_rate;
+        OEM_TRY(cells_coverage_setup(&s->cov));
+    }
+    oem_cells_stream *raw = s.get();
+    try {
+        for (int wk = 0; wk < kStreamWorkers; ++wk) raw->workers.emplace_back([raw, wk] { raw->work(wk); });
+    } catch (...) {
+        if (raw->workers.empty()) {
+            return fail(OEM_ERR_STATE, "%s: no device worker could be started", who);
+        } // (fewer threads: the ones that started take all the groups)
+    }
+    *out = s.release();
+    return OEM_OK;
+    OEM_API_END("oem_cells_stream_create")
+}
+
+extern "C" int oem_cells_stream_push(oem_cells_stream *s, const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
+                                     const uint32_t *aln_start, const uint32_t *aln_end, uint64_t n_reads, uint64_t nnz,
+                                     uint64_t *out_ticket)
+{
+    const char *who = "oem_cells_stream_push";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    // the cell's own checks, on the calling thread, before the session is touched
+    if (!row_ptr) return fail(OEM_ERR_ARG, "%s: row_ptr is NULL", who);
+    if (nnz > 0 && (!tid || !as_prob)) return fail(OEM_ERR_ARG, "%s: tid/as_prob is NULL", who);
+    if (s->o.coverage && nnz > 0 && (!aln_start || !aln_end))
+        return fail(OEM_ERR_ARG, "%s: coverage = 1 needs aln_start and aln_end", who);
+    if (n_reads >= (1ull << 32) || nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a cell needs fewer than 2^32 reads and alignments", who);
+    try {
+        OEM_TRY(validate_csr(row_ptr, tid, n_reads, nnz, s->o.n_txps));
+    } catch (const std::exception &) {
+        return fail(OEM_ERR_OOM, "%s: host allocation failed", who);
+    }
+
+    std::unique_lock<std::mutex> lk(s->mu);
+    ++s->pushes_in_flight;
+    struct InFlight { // (mu is held whenever this scope is left)
+        oem_cells_stream *s;
+        ~InFlight() { --s->pushes_in_flight; }
+    } in_flight{s};
+    const uint64_t hard_nnz = cells_max_group_nnz();
+    Group *g = nullptr;
+    try {
+        for (;;) {
+            if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+            if (s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str());
+            if (s->next_ticket >= 0xffffffffull) return fail(OEM_ERR_STATE, "%s: a session holds fewer than 2^32 cells", who);
+            g = s->open.get();
+            // the driver's own group rule: the cell starts a new group when it would break the open one's
+            if (g && g->n_cells > 0 && !cells_group_fits((uint64_t)g->n_cells + 1, g->n_reads + n_reads, g->nnz + nnz, s->o.n_txps, hard_nnz)) {
+                s->close_open();
+                continue;
+            }
+            // back-pressure; what waits in the open group goes to the workers first, or nothing would ever drain
+            if (s->staged_nnz > 0 && s->staged_nnz + nnz > s->max_staged) {
+                s->close_open();
+                const auto t0 = std::chrono::steady_clock::now();
+                s->cv_space.wait(lk);
+                s->blocked_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+                continue;
+            }
+            if (!g) {
+                std::unique_ptr<Group> ng(new Group());
+                ng->st = s->take_arena(std::max(s->arena_nnz, nnz), std::max(s->arena_rp, n_reads + 1));
+                ng->index = s->results.size();
+                ng->first_ticket = s->next_ticket;
+                s->results.emplace_back();
+                s->open = std::move(ng);
+                g = s->open.get();
+            }
+            if (g->nnz + nnz > g->st->cap_nnz || g->rp_used() + n_reads + 1 > g->st->cap_rp) {
+                const bool full_size = g->st->cap_nnz >= s->full_arena_nnz() && g->st->cap_rp >= s->full_arena_rp();
+                if (full_size && g->n_cells > 0) { // a full-sized arena is full: the group is large enough
+                    s->close_open();
+                    continue;
+                }
+                if (g->pending) { // pushes still copy into the arena: it cannot move yet
+                    s->cv_copy.wait(lk);
+                    continue;
+                }
+                // grow x4 towards the full size (or to what a single large cell needs); the staged part moves over
+                uint64_t cn = g->st->cap_nnz, cr = g->st->cap_rp;
+                while (cn < g->nnz + nnz) cn = std::max(cn * 4, g->nnz + nnz);
+                while (cr < g->rp_used() + n_reads + 1) cr = std::max(cr * 4, g->rp_used() + n_reads + 1);
+                if (g->nnz + nnz <= s->full_arena_nnz()) cn = std::min(cn, s->full_arena_nnz());
+                if (g->rp_used() + n_reads + 1 <= s->full_arena_rp()) cr = std::min(cr, s->full_arena_rp());
+                std::unique_ptr<Staging> old = std::move(g->st);
+                g->st = s->take_arena(cn, cr);
+                std::memcpy(g->st->rp, old->rp, sizeof(uint64_t) * g->rp_used());
+                std::memcpy(g->st->tid, old->tid, sizeof(uint32_t) * g->nnz);
+                std::memcpy(g->st->p, old->p, sizeof(float) * g->nnz);
+                if (s->o.coverage) {
+                    std::memcpy(g->st->start, old->start, sizeof(uint32_t) * g->nnz);
+                    std::memcpy(g->st->end, old->end, sizeof(uint32_t) * g->nnz);
+                }
+                if (old->pinned) --s->arenas_pinned; // (released here: smaller than what groups need by now)
+                old.reset();
+                s->arena_nnz = std::min(std::max(s->arena_nnz, cn), s->full_arena_nnz());
+                s->arena_rp = std::min(std::max(s->arena_rp, cr), s->full_arena_rp());
+                continue;
+            }
+            g->read_off.reserve(g->read_off.size() + 1); // (so that taking the cell's place below cannot throw)
+            g->aln_off.reserve(g->aln_off.size() + 1);
+            break;
+        }
+    } catch (const std::bad_alloc &) { // staging could not be allocated: the session cannot keep its promise
+        s->set_sticky(OEM_ERR_OOM, "oem_cells_stream_push: host allocation of the staging memory failed");
+        s->cv_space.notify_all();
+        return fail(OEM_ERR_OOM, "%s", s->sticky_msg.c_str());
+    }
+    // the cell's place: ticket, offsets; the arrays are copied outside the lock
+    const uint64_t ticket = s->next_ticket++;
+    const uint64_t rp_at = g->rp_used(), a_at = g->nnz;
+    Staging *st = g->st.get();
+    g->n_cells += 1;
+    g->n_reads += n_reads;
+    g->nnz += nnz;
+    g->read_off.push_back(g->n_reads);
+    g->aln_off.push_back(g->nnz);
+    g->pending += 1;
+    s->total_nnz += nnz;
+    s->staged_nnz += nnz;
+    if (g->nnz >= s->group_nnz || g->n_cells >= s->group_cells) s->close_open(); // (the worker waits for the copy below)
+    lk.unlock();
+    std::memcpy(st->rp + rp_at, row_ptr, sizeof(uint64_t) * (n_reads + 1));
+    if (nnz) {
+        std::memcpy(st->tid + a_at, tid, sizeof(uint32_t) * nnz);
+        std::memcpy(st->p + a_at, as_prob, sizeof(float) * nnz);
+        if (s->o.coverage) {
+            std::memcpy(st->start + a_at, aln_start, sizeof(uint32_t) * nnz);
+            std::memcpy(st->end + a_at, aln_end, sizeof(uint32_t) * nnz);
+        }
+    }
+    lk.lock();
+    g->pending -= 1;
+    s->cv_copy.notify_all();
+    if (out_ticket) *out_ticket = ticket;
+    return OEM_OK;
+}
+
+extern "C" int oem_cells_stream_finish(oem_cells_stream *s, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_finish";
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished already", who);
+        if (s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a push is in flight", who);
+        s->finish_called = true;
+        s->close_open();
+        s->stop = true;
+    }
+    s->cv_work.notify_all();
+    for (auto &t : s->workers)
+        if (t.joinable()) t.join();
+    if (s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str());
+    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
+    r->n_cells = (uint32_t)s->next_ticket;
+    r->infos.reserve(r->n_cells);
+    std::vector<SparseBlock> blocks;
+    blocks.reserve(s->results.size());
+    for (GroupResult &gr : s->results) { // group order is ticket order
+        r->infos.insert(r->infos.end(), gr.infos.begin(), gr.infos.end());
+        blocks.push_back(std::move(gr.blk));
+    }
+    s->results.clear();
+    if (r->infos.size() != r->n_cells) return fail(OEM_ERR_STATE, "%s: the groups' results cover %zu of %u cells", who, r->infos.size(), r->n_cells);
+    OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
+    *out = r.release();
+    return OEM_OK;
+    OEM_API_END("oem_cells_stream_finish")
+}
+
+extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, uint64_t *value)
+{
+    if (!s || !value) return fail(OEM_ERR_ARG, "oem_cells_stream_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    switch (key) {
+    case OEM_CELLS_STREAM_INFO_CELLS: *value = s->next_ticket; break;
+    case OEM_CELLS_STREAM_INFO_ALIGNMENTS: *value = s->total_nnz; break;
+    case OEM_CELLS_STREAM_INFO_GROUPS: *value = s->groups_started; break;
+    case OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH: *value = s->groups_before_finish; break;
+    case OEM_CELLS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us; break;
+    case OEM_CELLS_STREAM_INFO_GROUPS_BATCHED: *value = s->groups_batched; break;
+    default: return fail(OEM_ERR_ARG, "oem_cells_stream_info: unknown key %u", key);
+    }
+    return OEM_OK;
+}
+
+extern "C" void oem_cells_stream_destroy(oem_cells_stream *s)
+{
+    if (!s) return;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (!s->finish_called) s->cancel = true; // queued groups are dropped; a group on the device runs to its end
+        s->finish_called = true;
+        if (s->open) s->queue.push_back(std::move(s->open)); // (skipped by the worker that takes it)
+        s->stop = true;
+    }
+    s->cv_work.notify_all();
+    s->cv_space.notify_all();
+    for (auto &t : s->workers)
+        if (t.joinable()) t.join();
+    (void)hipSetDevice(s->o.device); // the coverage tables and the pinned arenas are released on their device
+    delete s;
+}

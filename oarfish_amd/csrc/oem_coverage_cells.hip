@@ -201,15 +201,17 @@ struct Chunk {
 // alignment; its other buffers are known from its size (`per_aln`, `per_read`: the bytes a chunk holds for each of its
 // alignments and reads besides the slot table, segments and bins).
 std::vector<Chunk> plan_chunks(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr, uint32_t n_txps,
-                               uint64_t all_bins, uint64_t max_nb, uint64_t budget_bytes, uint64_t per_aln, uint64_t per_read)
+                               uint64_t all_bins, uint64_t max_nb, uint64_t budget_bytes, uint64_t per_aln, uint64_t per_read,
+                               const uint64_t *cell_aln_off = nullptr /* given: row_ptr[cell_row_off[c]], row_ptr not read */)
 {
+    auto aln_at = [&](uint32_t c) { return cell_aln_off ? cell_aln_off[c] : row_ptr[cell_row_off[c]]; };
     const uint64_t budget_bins = (uint64_t)knob("OEM_COV_CELLS_CHUNK_BINS", 0); // testing build: force small chunks
     std::vector<Chunk> chunks;
-    Chunk ch{0, 0, cell_row_off[0], cell_row_off[0], row_ptr[cell_row_off[0]], row_ptr[cell_row_off[0]]};
+    Chunk ch{0, 0, cell_row_off[0], cell_row_off[0], aln_at(0), aln_at(0)};
     uint64_t bins = 0, bytes = 0;
     for (uint32_t c = 0; c < n_cells; ++c) {
         const uint64_t reads = cell_row_off[c + 1] - cell_row_off[c];
-        const uint64_t a = row_ptr[cell_row_off[c + 1]] - row_ptr[cell_row_off[c]];
+        const uint64_t a = aln_at(c + 1) - aln_at(c);
         const uint64_t ub = std::min(all_bins, a * max_nb);
         const uint64_t by = 16 * ub + 8 * (uint64_t)n_txps + 28 * std::min<uint64_t>(a, n_txps) + per_aln * a + per_read * reads + 8;
         const bool full = ch.c1 > ch.c0 &&
@@ -364,8 +366,9 @@ int cells_coverage_setup(CellsCoverage *cc)
     return OEM_OK;
 }
 
-int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, uint32_t n_cells, uint32_t first_cell,
-                         const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob, uint64_t aln_base,
+int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, const uint64_t *cell_aln_off,
+                         uint32_t n_cells, uint64_t first_cell, const uint64_t *row_ptr, const uint32_t *tid,
+                         const float *as_prob, const uint32_t *aln_start, const uint32_t *aln_end, double *out_cov_prob,
                          uint64_t n_reads, uint64_t nnz, ResidentCsr *out)
 {
     StageTimer tm;
@@ -374,10 +377,12 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
     OEM_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     hipStream_t st = sg.s;
     // 1. what the store keeps (caller order: row pointers narrowed on the device, ids, the weights written below)
-    OEM_TRY(dev_alloc(&out->row_ptr, n_reads + 1, nullptr));
+    if (!out->row_ptr) {
+        OEM_TRY(dev_alloc(&out->row_ptr, n_reads + 1, nullptr));
+        OEM_TRY(upload_row_ptr_u32(st, row_ptr, n_reads + 1, out->row_ptr));
+    }
     OEM_TRY(dev_alloc(&out->tid, nnz, nullptr));
     OEM_TRY(dev_alloc(&out->w64, nnz, nullptr));
-    OEM_TRY(upload_row_ptr_u32(st, row_ptr, n_reads + 1, out->row_ptr));
     if (nnz == 0) return OEM_OK;
     OEM_HIP(hipMemcpyAsync(out->tid, tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
     // the coverage scratch: released when this scope ends, before the store's layout is built
@@ -389,8 +394,8 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
     OEM_TRY(ar.get(&d_end, nnz));
     OEM_TRY(ar.get(&d_p, nnz));
     OEM_TRY(ar.get(&d_cov, nnz));
-    OEM_HIP(hipMemcpyAsync(d_start, cc.aln_start + aln_base, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemcpyAsync(d_end, cc.aln_end + aln_base, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_start, aln_start, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_end, aln_end, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
     OEM_HIP(hipMemcpyAsync(d_p, as_prob, sizeof(float) * nnz, hipMemcpyHostToDevice, st));
     OEM_HIP(hipStreamSynchronize(st));
     tm.lap("cov+em: group upload");
@@ -400,7 +405,7 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
     size_t free_b = 0, total_b = 0;
     OEM_HIP(hipMemGetInfo(&free_b, &total_b));
     const std::vector<Chunk> chunks = plan_chunks(cell_row_off, n_cells, row_ptr, cc.n_txps, cc.all_bins, cc.max_nb,
-                                                  free_b / 2, 4 /* segment ids */, 0);
+                                                  free_b / 2, 4 /* segment ids */, 0, cell_aln_off);
     ChunkBufs b;
     OEM_TRY(alloc_chunk_bufs(st, ar, chunks, cc.n_txps, &b));
     std::vector<uint32_t> h_coff, h_err;
@@ -408,19 +413,19 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
         const uint32_t ncc = ch.c1 - ch.c0;
         h_coff.resize((size_t)ncc + 1);
         h_err.resize(ncc);
-        for (uint32_t c = 0; c <= ncc; ++c) h_coff[c] = (uint32_t)(row_ptr[cell_row_off[ch.c0 + c]] - ch.a0);
+        for (uint32_t c = 0; c <= ncc; ++c) h_coff[c] = (uint32_t)(cell_aln_off[ch.c0 + c] - ch.a0);
         OEM_TRY(run_chunk(st, ar, b, cc.d_len, cc.d_nb, cc.n_txps, cc.bin_width, cc.model, cc.growth_rate, ncc,
                           (uint32_t)(ch.r1 - ch.r0), (uint32_t)(ch.a1 - ch.a0), h_coff.data(), out->row_ptr + ch.r0,
                           (uint32_t)ch.a0, out->tid + ch.a0, d_start + ch.a0, d_end + ch.a0, d_cov + ch.a0, h_err.data()));
         for (uint32_t c = 0; c < ncc; ++c) {
             const uint32_t f = h_err[c] | (h_coff[c + 1] > h_coff[c] ? cc.gerr : 0u);
-            if (f) return fail(OEM_ERR_STATE, "%s: cell %u: %s", who, first_cell + ch.c0 + c, cov_err_text(f));
+            if (f) return fail(OEM_ERR_STATE, "%s: cell %llu: %s", who, (unsigned long long)(first_cell + ch.c0 + c), cov_err_text(f));
         }
     }
     tm.lap("cov+em: coverage");
     // 3. the column the EM uses, for the caller who asked for it; the weights straight into the store's buffer
-    if (cc.out_cov_prob)
-        OEM_HIP(hipMemcpyAsync(cc.out_cov_prob + aln_base, d_cov, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
+    if (out_cov_prob)
+        OEM_HIP(hipMemcpyAsync(out_cov_prob, d_cov, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_cc_weights, dim3((uint32_t)((n_reads + kCC - 1) / kCC)), dim3(kCC), 0, st, out->row_ptr, d_p, d_cov,
                        (uint32_t)n_reads, out->w64);
     OEM_HIP(hipGetLastError());

@@ -52,6 +52,7 @@ struct CellRelabel {
     const uint64_t *cell_row_off;
     uint32_t n_cells;
     uint32_t cell_txps;
+    const unsigned long long *d_cell_row_off = nullptr; // the same offsets on the device already, or NULL
 };
 // A caller-order CSR already resident on the device (u32 row pointers, transcript ids, and either the f64 weights
 // w = p * cov or, for an f32 store, the weights already rounded once to f32 in w32): a store created from it takes the
@@ -62,6 +63,10 @@ struct ResidentCsr {
     uint32_t *tid = nullptr;
     double *w64 = nullptr;
     float *w32 = nullptr; // (set: an f32 store; w64 stays null)
+    // A resident CSR without a host row_ptr (create_store_impl is given NULL): the host layout builder, which takes
+    // the stores the device builder declines, asks for one here (NULL: allocation failed)
+    const uint64_t *(*host_row_ptr)(void *) = nullptr;
+    void *host_row_ptr_ctx = nullptr;
     ResidentCsr() = default;
     ResidentCsr(const ResidentCsr &) = delete;
     ResidentCsr &operator=(const ResidentCsr &) = delete;
@@ -109,10 +114,13 @@ struct CellsCoverage {
     }
 };
 int cells_coverage_setup(CellsCoverage *cc);
-// Cells [0, n_cells) of a group (first_cell: the first one's index in the call, for messages); row_ptr and
-// cell_row_off relative to the group, tid / as_prob / aln_base: the group's first alignment is aln_base of the call.
-int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, uint32_t n_cells, uint32_t first_cell,
-                         const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob, uint64_t aln_base,
+// Cells [0, n_cells) of a group (first_cell: the first one's index in the call, for messages); row_ptr, cell_row_off
+// and cell_aln_off (the cells' first alignments) relative to the group, tid / as_prob / aln_start / aln_end the
+// group's own; out_cov_prob: the group's part of the caller's column, or NULL.  A group whose u32 row pointers are on
+// the device already has them in out->row_ptr, and row_ptr is not read.
+int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, const uint64_t *cell_aln_off,
+                         uint32_t n_cells, uint64_t first_cell, const uint64_t *row_ptr, const uint32_t *tid,
+                         const float *as_prob, const uint32_t *aln_start, const uint32_t *aln_end, double *out_cov_prob,
                          uint64_t n_reads, uint64_t nnz, ResidentCsr *out);
 
 // oem_em_driver.hip: one EM run with the loop state on the device

@@ -123,9 +123,9 @@ def em_cells_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, as_probabi
     return _take_cells_result(res, n_cells)
 
 
-def _take_cells_result(res, n_cells):
+def _take_cells_result(res, n_cells, L=None):
     """(indptr, cols, vals, [RunInfo]) of an ``oem_cells_result`` handle, which is released."""
-    L = _lib.lib()
+    L = L or _lib.lib()
     try:
         nc, ne = C.c_uint32(0), C.c_uint64(0)
         _lib.check(L.oem_cells_result_dims(res, C.byref(nc), C.byref(ne)))
@@ -213,6 +213,109 @@ def em_cells_coverage_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, a
         convergence_thresh, cov.ctypes.data if cov is not None and nnz else None, C.byref(res)))
     out = _take_cells_result(res, n_cells)
     return (*out, cov) if return_coverage else out
+
+
+class CellsStream:
+    """A per-cell session (``oem_cells_stream_*``): cells are pushed one by one, from any number of threads, as
+    they become available -- the way single_cell.rs:96-193 produces them -- and the library runs them in batched
+    groups on the device while later cells still arrive.
+
+    ``coverage``: None, or ``dict(bin_width=..., model="binomial" | "logistic", growth_rate=..., txp_len=...)`` for
+    the per-cell coverage model of ``em_cells_coverage_sparse`` (cells are then pushed with their coordinates).
+    ``group_nnz`` / ``group_cells`` / ``max_staged_nnz``: 0 = the library's defaults.  Use as a context manager;
+    leaving the block before ``finish()`` cancels the session.
+
+    ``push`` returns the cell's ticket: cell ``k`` of the result is the cell with ticket ``k``.  ``finish()`` returns
+    what ``em_cells_sparse`` returns.  ``push`` is thread-safe and releases the GIL while the library works.
+    """
+
+    def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
+                 group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0):
+        o = _lib.CellsStreamOptsC()
+        o.n_txps, o.device, o.max_iter, o.conv_thresh = n_txps, device, max_iter, conv_thresh
+        o.group_nnz, o.group_cells, o.max_staged_nnz = group_nnz, group_cells, max_staged_nnz
+        txp_len = None
+        if coverage is not None:
+            model = coverage.get("model", "binomial")
+            if model not in _COVERAGE_MODELS:
+                raise ValueError(f"model must be one of {sorted(_COVERAGE_MODELS)}, not {model!r}")
+            txp_len = np.ascontiguousarray(coverage["txp_len"], dtype=np.uint64)
+            if len(txp_len) != n_txps:
+                raise ValueError("coverage['txp_len'] must have n_txps entries")
+            o.coverage, o.bin_width, o.model = 1, coverage.get("bin_width", 100), _COVERAGE_MODELS[model]
+            o.growth_rate = coverage.get("growth_rate", 2.0)
+        self._coverage = coverage is not None
+        self._L = _lib.lib()   # (a handle belongs to the library that made it)
+        self._h = C.c_void_p()
+        _lib.check(self._L.oem_cells_stream_create(C.byref(o), None if txp_len is None else txp_len.ctypes.data,
+                                                   C.byref(self._h)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            self._L.oem_cells_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # pragma: no cover - interpreter shutdown
+            pass
+
+    def _check(self, rc: int) -> None:
+        if rc != _lib.OEM_OK:
+            msg = self._L.oem_last_error()
+            raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
+
+    def push(self, row_ptr, tid, as_prob, start=None, end=None) -> int:
+        if not self._h:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+        tid = np.ascontiguousarray(tid, dtype=np.uint32)
+        as_prob = np.ascontiguousarray(as_prob, dtype=np.float32)
+        nnz = len(tid)
+        if len(as_prob) != nnz:
+            raise ValueError("tid and as_prob must have one entry per alignment")
+        if len(row_ptr) < 1:
+            raise ValueError("row_ptr needs n_reads + 1 entries")
+        if start is not None:
+            start = np.ascontiguousarray(start, dtype=np.uint32)
+            end = np.ascontiguousarray(end, dtype=np.uint32)
+            if len(start) != nnz or len(end) != nnz:
+                raise ValueError("start and end must have one entry per alignment")
+        ticket = C.c_uint64(0)
+        self._check(self._L.oem_cells_stream_push(
+            self._h, row_ptr.ctypes.data, tid.ctypes.data if nnz else None, as_prob.ctypes.data if nnz else None,
+            None if start is None or not nnz else start.ctypes.data, None if start is None or not nnz else end.ctypes.data,
+            len(row_ptr) - 1, nnz, C.byref(ticket)))
+        return int(ticket.value)
+
+    def finish(self):
+        """(indptr, cols, vals, [RunInfo]) of every pushed cell, in ticket order."""
+        if not self._h:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
+        res = C.c_void_p()
+        self._check(self._L.oem_cells_stream_finish(self._h, C.byref(res)))
+        nc = C.c_uint32(0)
+        self._check(self._L.oem_cells_result_dims(res, C.byref(nc), None))
+        return _take_cells_result(res, int(nc.value), self._L)
+
+    def info(self) -> dict:
+        keys = dict(cells=_lib.OEM_CELLS_STREAM_INFO_CELLS, alignments=_lib.OEM_CELLS_STREAM_INFO_ALIGNMENTS,
+                    groups=_lib.OEM_CELLS_STREAM_INFO_GROUPS,
+                    groups_before_finish=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH,
+                    blocked_s=_lib.OEM_CELLS_STREAM_INFO_BLOCKED_US, groups_batched=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BATCHED)
+        out = {}
+        for name, key in keys.items():
+            v = C.c_uint64(0)
+            self._check(self._L.oem_cells_stream_info(self._h, key, C.byref(v)))
+            out[name] = v.value * 1e-6 if name == "blocked_s" else int(v.value)
+        return out
 
 
 def cells_last_timing():
