@@ -165,6 +165,22 @@ void free_store(oem_store *s)
     delete s;
 }
 
+// (the adopt: create_store_layout's upload_csr)
+int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *tid)
+{
+    resident->row_ptr = (uint32_t *)s->csr.row_ptr;
+    resident->tid = s->csr.tid;
+    resident->w64 = s->csr.w64;
+    resident->w32 = s->csr.w32;
+    s->csr.row_ptr = nullptr;
+    s->csr.tid = nullptr;
+    s->csr.w64 = nullptr;
+    s->csr.w32 = nullptr;
+    if (s->csr.nnz && hipMemcpy(resident->tid, tid, sizeof(uint32_t) * s->csr.nnz, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(OEM_ERR_HIP, "oem_em_run_cells: restoring the transcript ids failed");
+    return OEM_OK;
+}
+
 template <typename T, typename A>
 int upload_vec(T **dst, const std::vector<T, A> &v, uint64_t *acct)
 {

@@ -1,5 +1,5 @@
 // oem_cells.h -- what the one-call per-cell entry points (oem_cells.hip) and the per-cell session
-// (oem_cells_stream.hip) share: the sparse blocks of a group, the group rule, the unit of work and the result handle.
+// (oem_cells_stream.hip) share: the sparse blocks of a group, the group itself, the group rule and the result handle.
 #pragma once
 
 #include <memory>
@@ -36,22 +36,35 @@ struct SparseBlock {
     std::vector<float, NoInitAlloc<float>> val;
 };
 
-// Where the groups of one call put their results: the caller's dense n_cells x n_txps matrix (oem_em_run_cells), or
-// one SparseBlock per group index (oem_em_run_cells_sparse: groups finish in any order).
-struct CellsSink {
-    double *dense = nullptr;
-    std::vector<SparseBlock> *blocks = nullptr;
+struct CellsTiming; // oem_cells.hip: where the groups' EM loops are recorded (oem_cells_last_timing)
+// What all groups of a call or a session run with.
+struct CellsRun {
+    uint32_t n_txps = 0;
+    int device = 0;
+    uint32_t max_iter = 0;
+    double conv_thresh = 0.0;
+    CellsCoverage *cov = nullptr;  // the per-cell coverage model as the source of the weights, or NULL
+    CellsTiming *timing = nullptr; // or NULL: the loops are not recorded
 };
 
-// A group whose row pointers are on the device already (the session builds them there from the pushed cells): the
-// group has no concatenated host row_ptr unless a fallback asks for one.
-struct CellsGroupDevice {
-    ResidentCsr *resident = nullptr;           // row_ptr set; without the coverage model also tid and w32
-    const unsigned long long *d_cell_row_off = nullptr; // device, n_cells + 1
-    const uint64_t *cell_aln_off = nullptr;    // host, n_cells + 1: the cells' first alignments
-    const uint32_t *aln_start = nullptr, *aln_end = nullptr; // host, the group's own (coverage model)
-    uint64_t nnz = 0;
-    uint64_t first_cell = 0;                   // the first cell's number, for messages
+// A group of consecutive cells, the unit of work of the per-cell driver.  Two producers: the one-call form slices it
+// out of the caller's arrays (oem_cells.hip: slice_cells), the session fills it from its staging (oem_cells_stream.hip:
+// run_group).  Offsets are relative to the group, arrays and results start at its first cell; what is not there is NULL.
+struct CellsGroup {
+    uint32_t n_cells = 0;
+    uint64_t n_reads = 0, nnz = 0, first_cell = 0; // (first_cell: its number in the call or session, for messages)
+    const uint64_t *cell_row_off = nullptr, *cell_aln_off = nullptr; // host, n_cells + 1: the cells' first reads / alignments
+    const uint64_t *row_ptr = nullptr;      // host, n_reads + 1, or NULL: the u32 row pointers are in `resident` already
+    const uint32_t *tid = nullptr;          // host, nnz
+    const float *as_prob = nullptr;
+    const double *cov_prob = nullptr;       // a host coverage column, or NULL
+    const uint32_t *aln_start = nullptr, *aln_end = nullptr; // host (coverage model)
+    double *out_cov_prob = nullptr;         // host: the group's part of the caller's coverage column, or NULL
+    ResidentCsr *resident = nullptr;        // set: the store adopts it instead of uploading (coverage model, session)
+    const unsigned long long *d_cell_row_off = nullptr; // cell_row_off on the device already, or NULL
+    double *out_dense = nullptr;            // the results: the group's rows of the caller's n_cells x n_txps matrix,
+    SparseBlock *blk = nullptr;             // ... or its sparse block
+    oem_run_info *infos = nullptr;          // n_cells, or NULL
 };
 
 // The group rule of the per-cell driver: may `cells` consecutive cells with `reads` reads and `gnnz` alignments be
@@ -59,12 +72,11 @@ struct CellsGroupDevice {
 bool cells_group_fits(uint64_t cells, uint64_t reads, uint64_t gnnz, uint32_t n_txps, uint64_t max_group_nnz);
 uint64_t cells_max_group_nnz(); // the alignment bound of a group (testing build: OEM_CELLS_GROUP_NNZ)
 
-// One group of consecutive cells [c0, c1): batched on the device when it can be, otherwise cell after cell.  With
-// `dev` (c0 = 0, row_ptr NULL) the group's CSR is resident already.
-int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, const uint64_t *row_ptr,
-                    const uint32_t *tid, const float *as_prob, const double *cov_prob, const CellsCoverage *cov_src,
-                    uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g,
-                    oem_run_info *infos, bool *batched, const CellsGroupDevice *dev = nullptr);
+// One group: batched on the device when it can be, otherwise cell after cell (*batched says which).
+int run_cells_group(const CellsRun &run, const CellsGroup &g, bool *batched);
+// oem_coverage_cells.hip: the group's coverage on the device from its own arrays; the row pointers (uploaded here
+// unless out->row_ptr holds them), the ids and the f64 weights are left in `out`.
+int cells_coverage_group(const CellsCoverage &cc, const CellsGroup &g, ResidentCsr *out);
 
 } // namespace oem
 

@@ -3,14 +3,12 @@
 // declines run cell after cell over the caller-order CSR.
 #include <algorithm>
 #include <atomic>
-#include <climits>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -18,20 +16,13 @@
 
 namespace oem {
 
-namespace {
-
 #ifndef OEM_CELLS_HEAD_DIV
 #define OEM_CELLS_HEAD_DIV 4 // a large single group is split head : rest = 1 : (div - 1); 0 = not split
 #endif
-constexpr uint32_t kCellsHeadDiv = OEM_CELLS_HEAD_DIV;
 
-
-// What the last oem_em_run_cells call of this thread spent in its batched EM loops (HIP events on the
-// group's stream around the loop), for oem_cells_last_timing.
-thread_local double t_cells_loop_ms = 0.0;
-thread_local uint64_t t_cells_batched_passes = 0;
-// (the groups of one call may run on two host threads: they add into the call's accumulators under this lock,
-// and the calling thread copies them into its thread-local pair at the end)
+// ---- helpers
+// The EM loops of the groups of one call (they may run on two host threads and add themselves under the lock); the
+// calling thread copies the result into its thread-local pair at the end, for oem_cells_last_timing.
 struct CellsTiming {
     std::mutex mu;
     std::vector<std::pair<double, double>> loops; // [begin, end) of every group's EM loop, ms on the host's steady clock
@@ -55,29 +46,44 @@ struct CellsTiming {
         return total;
     }
 };
-thread_local CellsTiming *t_timing = nullptr;
+
+namespace {
+
+constexpr uint32_t kCellsHeadDiv = OEM_CELLS_HEAD_DIV;
+
+// What the last oem_em_run_cells call of this thread spent in its batched EM loops (HIP events on the
+// group's stream around the loop), for oem_cells_last_timing.
+thread_local double t_cells_loop_ms = 0.0;
+thread_local uint64_t t_cells_batched_passes = 0;
 // The groups of the last per-cell call of this thread and the path each one took, for oem_debug_cells_last_paths.
 thread_local std::vector<CellsGroupPath> t_cells_paths;
 
 // Device buffers of the count / scan / emit steps, kept across the cells of a cell-by-cell group.
 struct NzScratch {
-    uint32_t *counts = nullptr;
-    uint64_t *off = nullptr;
-    uint32_t *col = nullptr;
-    float *val = nullptr;
+    DevBuf<uint32_t> counts, col;
+    DevBuf<uint64_t> off;
+    DevBuf<float> val;
     size_t cap_cells = 0, cap_entries = 0;
-    NzScratch() = default;
-    NzScratch(const NzScratch &) = delete;
-    NzScratch &operator=(const NzScratch &) = delete;
-    ~NzScratch()
+};
+
+struct EventPair { // the HIP events around a group's EM loop
+    hipEvent_t begin = nullptr, end = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    ~EventPair()
     {
-        hipFree(counts);
-        hipFree(off);
-        hipFree(col);
-        hipFree(val);
+        if (begin) hipEventDestroy(begin);
+        if (end) hipEventDestroy(end);
     }
 };
 
+struct StoreFree {
+    void operator()(oem_store *s) const { free_store(s); }
+};
+using StorePtr = std::unique_ptr<oem_store, StoreFree>;
+
+// ---- sinks
 // single_cell.rs:151-160 on the device: the entries > 0.0 of cells [0, n_cells) of `src`, in ascending transcript id,
 // appended to `blk` (k_cells_nz_count, a host scan of the counts, k_cells_nz_emit, then only the entries cross PCIe).
 // cell_aln_off: the cells' first alignments -- a cell cannot have more entries than alignments.
@@ -86,20 +92,18 @@ int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, con
 {
     if (n_cells == 0) return OEM_OK;
     if (n_cells > sc.cap_cells) {
-        hipFree(sc.counts);
-        hipFree(sc.off);
-        sc.counts = nullptr;
-        sc.off = nullptr;
+        sc.counts.reset();
+        sc.off.reset();
         sc.cap_cells = 0;
-        OEM_TRY(dev_alloc(&sc.counts, n_cells, nullptr));
-        OEM_TRY(dev_alloc(&sc.off, (size_t)n_cells + 1, nullptr));
+        OEM_TRY(dev_alloc(&sc.counts.p, n_cells, nullptr));
+        OEM_TRY(dev_alloc(&sc.off.p, (size_t)n_cells + 1, nullptr));
         sc.cap_cells = n_cells;
     }
     const size_t first = blk->counts.size();
     blk->counts.resize(first + n_cells);
     uint32_t *h_counts = blk->counts.data() + first;
-    OEM_TRY(launch_cells_nz_count(st, src, n_cells, sc.counts));
-    OEM_HIP(hipMemcpyAsync(h_counts, sc.counts, sizeof(uint32_t) * n_cells, hipMemcpyDeviceToHost, st));
+    OEM_TRY(launch_cells_nz_count(st, src, n_cells, sc.counts.p));
+    OEM_HIP(hipMemcpyAsync(h_counts, sc.counts.p, sizeof(uint32_t) * n_cells, hipMemcpyDeviceToHost, st));
     OEM_HIP(hipStreamSynchronize(st));
     std::vector<uint64_t> off((size_t)n_cells + 1);
     off[0] = 0;
@@ -116,371 +120,276 @@ int cells_to_csr(hipStream_t st, const CellsNzSource &src, uint32_t n_cells, con
     blk->val.resize(e0 + total);
     if (total == 0) return OEM_OK;
     if (total > sc.cap_entries) {
-        hipFree(sc.col);
-        hipFree(sc.val);
-        sc.col = nullptr;
-        sc.val = nullptr;
+        sc.col.reset();
+        sc.val.reset();
         sc.cap_entries = 0;
-        OEM_TRY(dev_alloc(&sc.col, total, nullptr));
-        OEM_TRY(dev_alloc(&sc.val, total, nullptr));
+        OEM_TRY(dev_alloc(&sc.col.p, total, nullptr));
+        OEM_TRY(dev_alloc(&sc.val.p, total, nullptr));
         sc.cap_entries = total;
     }
-    OEM_HIP(hipMemcpyAsync(sc.off, off.data(), sizeof(uint64_t) * (n_cells + 1), hipMemcpyHostToDevice, st));
-    int rc = launch_cells_nz_emit(st, src, n_cells, sc.off, sc.col, sc.val);
+    OEM_HIP(hipMemcpyAsync(sc.off.p, off.data(), sizeof(uint64_t) * (n_cells + 1), hipMemcpyHostToDevice, st));
+    int rc = launch_cells_nz_emit(st, src, n_cells, sc.off.p, sc.col.p, sc.val.p);
     if (rc == OEM_OK &&
-        (hipMemcpyAsync(blk->col.data() + e0, sc.col, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-         hipMemcpyAsync(blk->val.data() + e0, sc.val, sizeof(float) * total, hipMemcpyDeviceToHost, st) != hipSuccess))
+        (hipMemcpyAsync(blk->col.data() + e0, sc.col.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+         hipMemcpyAsync(blk->val.data() + e0, sc.val.p, sizeof(float) * total, hipMemcpyDeviceToHost, st) != hipSuccess))
         rc = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: read-back of the entries failed");
     // (also on failure: `off` must outlive the upload queued above)
     if (hipStreamSynchronize(st) != hipSuccess && rc == OEM_OK) rc = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: emit failed");
     return rc;
 }
 
-// All cells in one store over the concatenated transcript space; every pass serves every
-// unfinished cell.  Returns *used = false (nothing done) when the batch form does not apply.
-int run_cells_batched(const uint64_t *cell_row_off, const uint64_t *cell_aln_off, const unsigned long long *d_cell_row_off,
-                      uint32_t n_cells, const uint64_t *row_ptr,
-                      const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads,
-                      uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
-                      double *out, SparseBlock *blk, oem_run_info *infos, bool *used, ResidentCsr *resident)
+// The dense sink of a batched group: its results in the caller's [cell][transcript] rows.  A compacted batch is
+// expanded on the device, or on the host when there is no device memory for the expanded results.
+int cells_to_dense(oem_store *s, uint32_t n_cells, uint32_t n_txps, double *out)
 {
-    *used = false;
-    StageTimer tm;
-    const uint64_t total_txps = (uint64_t)n_cells * n_txps;
-    if (max_iter < 1 || n_cells < 2 || total_txps >= (1ull << 32) || n_reads >= (1ull << 32)) return OEM_OK;
-    tm.lap("cells: group set-up");   // (the arrays were range-checked once by oem_em_run_cells)
-    OEM_TRY(ensure_device(device));
-    oem_store *s = new (std::nothrow) oem_store();
+    MultiBuffers &mb = s->multi;
+    const uint64_t full_total = (uint64_t)n_cells * n_txps;
+    const double *d_res = mb.out;
+    DevBuf<double> d_full;
+    if (mb.rank) { // compacted
+        if (knob("OEM_TEST_FAIL_FULL_ALLOC", 0) || hipMalloc((void **)&d_full.p, sizeof(double) * full_total) != hipSuccess) {
+            // the compact results and the rank table go to the host, which expands them (a transcript that does not
+            // occur in a cell is 0)
+            (void)hipGetLastError();
+            d_full.p = nullptr;
+            const size_t n_eff = (size_t)mb.n_problems * mb.txps_eff;
+            std::vector<double> h_eff(n_eff);
+            std::vector<uint32_t> h_rank((size_t)full_total);
+            if (hipMemcpy(h_eff.data(), mb.out, sizeof(double) * n_eff, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(h_rank.data(), mb.rank, sizeof(uint32_t) * full_total, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(OEM_ERR_HIP, "oem_em_run_cells: read-back failed");
+            for (size_t i = 0; i < (size_t)full_total; ++i)
+                out[i] = h_rank[i] == kNoRank ? 0.0 : h_eff[(i / mb.txps_full) * mb.txps_eff + h_rank[i]];
+            return OEM_OK;
+        }
+        // expand to the caller's [cell][transcript] (the queue is done with: its memory is free by now)
+        OEM_TRY(launch_multi_expand(s, mb, d_full.p));
+        if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(OEM_ERR_HIP, "oem_em_run_cells: expanding the results failed");
+        d_res = d_full.p;
+    }
+    if (hipMemcpy(out, d_res, sizeof(double) * full_total, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(OEM_ERR_HIP, "oem_em_run_cells: result read-back failed");
+    return OEM_OK;
+}
+
+// ---- the batched run: all cells of a group in one store over the concatenated transcript space; every pass serves
+// every unfinished cell.  Three steps: the store, the loop, the read-back.
+
+// Step 1.  *out stays empty when the tiler declines the batch (e.g. a read with > 255 alignments inside one window):
+// the cell-by-cell path takes the group, over the resident CSR if there is one.
+int create_batched_store(const CellsRun &run, const CellsGroup &g, StorePtr *out)
+{
+    StorePtr s(new (std::nothrow) oem_store());
     if (!s) return fail(OEM_ERR_OOM, "oem_em_run_cells: host allocation failed");
     oem_store_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.reorder_rows = 0; // a batch that cannot be tiled falls through to the cell-by-cell path
-    opts.problem_size = n_txps;
+    opts.problem_size = run.n_txps;
     // transcripts of cell p -> [p*T, (p+1)*T), relabelled on the device after the upload
-    CellRelabel rl{cell_row_off, n_cells, n_txps, d_cell_row_off};
-    int rc = create_store_impl(row_ptr, tid, as_prob, cov_prob, n_reads, nnz, (uint32_t)total_txps, device, &opts, s, &rl,
-                               resident);
-    if (rc != OEM_OK) {
-        free_store(s);
-        return rc;
-    }
-    if (!s->tiled.present) { // e.g. a read with > 255 alignments inside one window: the serial path takes the group
-        if (resident) {      // ... over the resident CSR, back from the store with the caller's ids (they were relabelled)
-            resident->row_ptr = (uint32_t *)s->csr.row_ptr;
-            resident->tid = s->csr.tid;
-            resident->w64 = s->csr.w64;
-            resident->w32 = s->csr.w32;
-            s->csr.row_ptr = nullptr;
-            s->csr.tid = nullptr;
-            s->csr.w64 = nullptr;
-            s->csr.w32 = nullptr;
-            if (nnz && hipMemcpy(resident->tid, tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice) != hipSuccess)
-                rc = fail(OEM_ERR_HIP, "oem_em_run_cells: restoring the transcript ids failed");
-        }
-        free_store(s);
-        return rc;
-    }
-    *used = true;
-    tm.lap("cells: store create");
+    CellRelabel rl{g.cell_row_off, g.n_cells, run.n_txps, g.d_cell_row_off};
+    OEM_TRY(create_store_impl(g.row_ptr, g.tid, g.as_prob, g.cov_prob, g.n_reads, g.nnz, g.n_cells * run.n_txps, run.device, &opts,
+                              s.get(), &rl, g.resident));
+    if (!s->tiled.present) // the CSR goes back with the caller's ids (they were relabelled)
+        return g.resident ? release_resident_csr(s.get(), g.resident, g.tid) : OEM_OK;
+    *out = std::move(s);
+    return OEM_OK;
+}
+
+// Step 2: the per-cell state, then passes in chunks until every cell has finished.  d_reads (the cells' read counts)
+// stays with the caller until the results are back.
+int run_batched_loop(const CellsRun &run, const CellsGroup &g, oem_store *s, DevBuf<uint64_t> &d_reads)
+{
+    const uint32_t n_cells = g.n_cells;
+    MultiBuffers &mb = s->multi;
     // transcripts per cell IN THE STORE: the ones that occur in the cell, padded to the fullest cell's count
     // (oem_api.hip: k_cells_mark); the caller's n_txps where the batch was not compacted
-    const uint64_t full_total = total_txps;
-    const bool compacted = s->multi.rank != nullptr;
-    const uint32_t caller_txps = n_txps;
-    if (compacted) n_txps = s->multi.txps_eff;
+    const uint32_t n_txps = mb.rank ? mb.txps_eff : run.n_txps;
     const uint64_t store_total = (uint64_t)n_cells * n_txps;
+    mb.n_problems = n_cells;
+    mb.problem_size = n_txps;
+    OEM_TRY(dev_alloc(&mb.state, n_cells, &s->hbm_bytes));
+    OEM_TRY(dev_alloc(&mb.out, (size_t)store_total, &s->hbm_bytes));
+    OEM_TRY(dev_alloc(&mb.n_unfinished, 1, &s->hbm_bytes));
+    std::vector<BatchState> hs(n_cells);
+    std::vector<uint64_t> reads(n_cells);
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        std::memset(&hs[c], 0, sizeof(BatchState));
+        hs[c].phase = kPhaseRunning;
+        reads[c] = g.cell_row_off[c + 1] - g.cell_row_off[c]; // the cell's own store.len() (single_cell.rs:122-130)
+    }
+    OEM_TRY(dev_alloc(&d_reads.p, n_cells, nullptr));
+    if (hipMemcpyAsync(d_reads.p, reads.data(), sizeof(uint64_t) * n_cells, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemcpyAsync(mb.state, hs.data(), sizeof(BatchState) * n_cells, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemcpyAsync(mb.n_unfinished, &n_cells, sizeof(uint32_t), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipMemsetAsync(s->cnt, 0, sizeof(double) * store_total, s->stream) != hipSuccess)
+        return fail(OEM_ERR_HIP, "oem_em_run_cells: upload of the per-cell state failed");
+    OEM_TRY(launch_multi_init(s, s->theta, d_reads.p, mb));
+    EmParams p{n_txps, run.max_iter, 50u /* em::em, single_cell.rs:150 */, run.conv_thresh};
+    if (hipMemsetAsync(mb.out, 0, sizeof(double) * store_total, s->stream) != hipSuccess)
+        return fail(OEM_ERR_HIP, "oem_em_run_cells: clearing the result buffer failed");
+    const uint64_t total = (uint64_t)run.max_iter + 1; // loop passes + the final one (em.rs:245-252)
+    // one workgroup per bucket folds the queue AND finishes the pass (k_multi_fold_reldiff); a
+    // store without remote alignments has no buckets to own and takes the separate kernels
+    const bool fused_fold = s->tiled.n_remote > 0 && s->tiled.n_buckets > 0 && knob("OEM_CELLS_FUSED_FOLD", 1) != 0;
+    uint64_t launched = 0;
+    uint32_t unfinished = n_cells, compacted_at = n_cells;
+    EventPair ev;
+    if (hipEventCreate(&ev.begin) != hipSuccess || hipEventCreate(&ev.end) != hipSuccess ||
+        hipEventRecord(ev.begin, s->stream) != hipSuccess)
+        return fail(OEM_ERR_HIP, "oem_em_run_cells: event set-up failed");
+    auto one_pass = [&]() -> int {
+        if (fused_fold) {
+            OEM_TRY(launch_em_pass_tiled(s, s->theta, s->cnt, nullptr, nullptr, mb.state, n_txps, true));
+            return launch_multi_fold_reldiff(s, s->theta, s->cnt, mb, p);
+        }
+        OEM_TRY(launch_em_pass_tiled(s, s->theta, s->cnt, nullptr, nullptr, mb.state, n_txps));
+        return launch_multi_reldiff(s, s->theta, s->cnt, mb, p);
+    };
+    ChunkGraph cg; // kGraphIters batched passes (five to six kernels each), replayed
+    if (graph_ok(s) && total >= 4 * kGraphIters) OEM_TRY(capture_chunk(s->stream, kGraphIters, one_pass, &cg));
+    while (launched < total && unfinished) {
+        uint64_t chunk = launched == 0 ? 53 : 16;
+        if (chunk > total - launched) chunk = total - launched;
+        if (cg.ready()) { // (passes beyond `total` find every cell FINISHED: no-ops)
+            chunk = (chunk + kGraphIters - 1) / kGraphIters * kGraphIters;
+            for (uint64_t k = 0; k < chunk; k += kGraphIters)
+                if (hipGraphLaunch(cg.ge, s->stream) != hipSuccess) return fail(OEM_ERR_HIP, "oem_em_run_cells: graph launch failed");
+        } else {
+            for (uint64_t k = 0; k < chunk; ++k) OEM_TRY(one_pass());
+        }
+        launched += chunk;
+        if (hipMemcpyAsync(&unfinished, mb.n_unfinished, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+            hipStreamSynchronize(s->stream) != hipSuccess)
+            return fail(OEM_ERR_HIP, "oem_em_run_cells: state read-back failed");
+        // cells have finished since the live lists were built: the next passes launch the live tiles and
+        // buckets only (the lists stay supersets of the live work until the next look)
+        if (unfinished && unfinished < compacted_at && !cg.ready() && knob("OEM_CELLS_COMPACT", 1) != 0) {
+            OEM_TRY(multi_compact_live(s, mb));
+            compacted_at = unfinished;
+        }
+    }
+    float ms = 0.f;
+    if (hipEventRecord(ev.end, s->stream) == hipSuccess && hipEventSynchronize(ev.end) == hipSuccess &&
+        hipEventElapsedTime(&ms, ev.begin, ev.end) == hipSuccess && run.timing) {
+        // the loop ended just now and lasted `ms` on the device
+        const double end = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        std::lock_guard<std::mutex> lk(run.timing->mu);
+        run.timing->loops.emplace_back(end - (double)ms, end);
+        run.timing->passes += launched;
+    }
+    return OEM_OK;
+}
+
+// Step 3: the results through the group's sink, then every cell's final state into `infos`.
+int read_back_batched(const CellsRun &run, const CellsGroup &g, oem_store *s)
+{
+    MultiBuffers &mb = s->multi;
+    NzScratch sc;
+    if (g.blk) // the entries > 0 straight from the compact (or uncompacted) results: no expansion, no dense copy
+        OEM_TRY(cells_to_csr(s->stream, CellsNzSource{mb.out, mb.rank, run.n_txps, mb.problem_size}, g.n_cells, g.cell_aln_off, sc, g.blk));
+    else
+        OEM_TRY(cells_to_dense(s, g.n_cells, run.n_txps, g.out_dense));
+    std::vector<BatchState> hs(g.n_cells);
+    if (hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * g.n_cells, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(OEM_ERR_HIP, g.blk ? "oem_em_run_cells_sparse: state read-back failed" : "oem_em_run_cells: result read-back failed");
+    if (g.infos)
+        for (uint32_t c = 0; c < g.n_cells; ++c) {
+            g.infos[c].niter = hs[c].niter;
+            g.infos[c].n_passes = hs[c].n_passes;
+            g.infos[c].converged = hs[c].converged;
+            g.infos[c].reserved = 0;
+            g.infos[c].rel_diff = hs[c].last_rel;
+        }
+    return OEM_OK;
+}
+
+// Returns *used = false (nothing done) when the batch form does not apply.
+int run_cells_batched(const CellsRun &run, const CellsGroup &g, bool *used)
+{
+    *used = false;
+    StageTimer tm;
+    const uint64_t total_txps = (uint64_t)g.n_cells * run.n_txps;
+    if (run.max_iter < 1 || g.n_cells < 2 || total_txps >= (1ull << 32) || g.n_reads >= (1ull << 32)) return OEM_OK;
+    tm.lap("cells: group set-up");   // (the arrays were range-checked once by oem_em_run_cells)
+    OEM_TRY(ensure_device(run.device));
+    StorePtr s;
+    OEM_TRY(create_batched_store(run, g, &s));
+    if (!s) return OEM_OK;
+    *used = true;
+    tm.lap("cells: store create");
     if (tm.on)
         fprintf(stderr, "[oem] cells: %u transcripts per cell in the store (of %u), %u tiles, %llu local + %llu remote alignments\n",
-                n_txps, (unsigned)(full_total / n_cells), s->tiled.n_tiles, (unsigned long long)s->tiled.n_local,
+                s->multi.rank ? s->multi.txps_eff : run.n_txps, run.n_txps, s->tiled.n_tiles, (unsigned long long)s->tiled.n_local,
                 (unsigned long long)s->tiled.n_remote);
-
-    auto body = [&]() -> int {
-        MultiBuffers &mb = s->multi;
-        mb.n_problems = n_cells;
-        mb.problem_size = n_txps;
-        OEM_TRY(dev_alloc(&mb.state, n_cells, &s->hbm_bytes));
-        OEM_TRY(dev_alloc(&mb.out, (size_t)store_total, &s->hbm_bytes));
-        OEM_TRY(dev_alloc(&mb.n_unfinished, 1, &s->hbm_bytes));
-        std::vector<BatchState> hs(n_cells);
-        std::vector<uint64_t> reads(n_cells);
-        for (uint32_t c = 0; c < n_cells; ++c) {
-            std::memset(&hs[c], 0, sizeof(BatchState));
-            hs[c].phase = kPhaseRunning;
-            reads[c] = cell_row_off[c + 1] - cell_row_off[c]; // the cell's own store.len() (single_cell.rs:122-130)
-        }
-        uint64_t *d_reads = nullptr;
-        OEM_TRY(dev_alloc(&d_reads, n_cells, nullptr));
-        int rc2 = OEM_OK;
-        do {
-            if (hipMemcpyAsync(d_reads, reads.data(), sizeof(uint64_t) * n_cells, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemcpyAsync(mb.state, hs.data(), sizeof(BatchState) * n_cells, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemcpyAsync(mb.n_unfinished, &n_cells, sizeof(uint32_t), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-                hipMemsetAsync(s->cnt, 0, sizeof(double) * store_total, s->stream) != hipSuccess) {
-                rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: upload of the per-cell state failed");
-                break;
-            }
-            if ((rc2 = launch_multi_init(s, s->theta, d_reads, mb)) != OEM_OK) break;
-            EmParams p{n_txps, max_iter, 50u /* em::em, single_cell.rs:150 */, conv_thresh};
-            if (hipMemsetAsync(mb.out, 0, sizeof(double) * store_total, s->stream) != hipSuccess) {
-                rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: clearing the result buffer failed");
-                break;
-            }
-            const uint64_t total = (uint64_t)max_iter + 1; // loop passes + the final one (em.rs:245-252)
-            // one workgroup per bucket folds the queue AND finishes the pass (k_multi_fold_reldiff); a
-            // store without remote alignments has no buckets to own and takes the separate kernels
-            const bool fused_fold = s->tiled.n_remote > 0 && s->tiled.n_buckets > 0 && knob("OEM_CELLS_FUSED_FOLD", 1) != 0;
-            uint64_t launched = 0;
-            uint32_t unfinished = n_cells, compacted_at = n_cells;
-            hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess ||
-                hipEventRecord(ev0, s->stream) != hipSuccess) {
-                if (ev0) hipEventDestroy(ev0);
-                if (ev1) hipEventDestroy(ev1);
-                rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: event set-up failed");
-                break;
-            }
-            auto one_pass = [&]() -> int {
-                if (fused_fold) {
-                    OEM_TRY(launch_em_pass_tiled(s, s->theta, s->cnt, nullptr, nullptr, mb.state, n_txps, true));
-                    return launch_multi_fold_reldiff(s, s->theta, s->cnt, mb, p);
-                }
-                OEM_TRY(launch_em_pass_tiled(s, s->theta, s->cnt, nullptr, nullptr, mb.state, n_txps));
-                return launch_multi_reldiff(s, s->theta, s->cnt, mb, p);
-            };
-            ChunkGraph cg; // kGraphIters batched passes (five to six kernels each), replayed
-            if (graph_ok(s) && total >= 4 * kGraphIters) rc2 = capture_chunk(s->stream, kGraphIters, one_pass, &cg);
-            while (rc2 == OEM_OK && launched < total && unfinished) {
-                uint64_t chunk = launched == 0 ? 53 : 16;
-                if (chunk > total - launched) chunk = total - launched;
-                if (cg.ready()) { // (passes beyond `total` find every cell FINISHED: no-ops)
-                    chunk = (chunk + kGraphIters - 1) / kGraphIters * kGraphIters;
-                    for (uint64_t k = 0; k < chunk && rc2 == OEM_OK; k += kGraphIters)
-                        if (hipGraphLaunch(cg.ge, s->stream) != hipSuccess) rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: graph launch failed");
-                } else {
-                    for (uint64_t k = 0; k < chunk && rc2 == OEM_OK; ++k) rc2 = one_pass();
-                }
-                if (rc2 != OEM_OK) break;
-                launched += chunk;
-                if (hipMemcpyAsync(&unfinished, mb.n_unfinished, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                    hipStreamSynchronize(s->stream) != hipSuccess) {
-                    rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: state read-back failed");
-                    break;
-                }
-                // cells have finished since the live lists were built: the next passes launch the live tiles and
-                // buckets only (the lists stay supersets of the live work until the next look)
-                if (unfinished && unfinished < compacted_at && !cg.ready() && knob("OEM_CELLS_COMPACT", 1) != 0) {
-                    rc2 = multi_compact_live(s, mb);
-                    compacted_at = unfinished;
-                }
-            }
-            if (rc2 == OEM_OK && hipEventRecord(ev1, s->stream) == hipSuccess && hipEventSynchronize(ev1) == hipSuccess) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
-                    if (t_timing) { // the loop ended just now and lasted `ms` on the device
-                        const double end = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-                        std::lock_guard<std::mutex> lk(t_timing->mu);
-                        t_timing->loops.emplace_back(end - (double)ms, end);
-                        t_timing->passes += launched;
-                    }
-                }
-            }
-            hipEventDestroy(ev0);
-            hipEventDestroy(ev1);
-            if (rc2 != OEM_OK) break;
-            tm.lap("cells: EM loop");
-            if (blk) { // the entries > 0 straight from the compact (or uncompacted) results: no expansion, no dense copy
-                CellsNzSource src;
-                src.v = mb.out;
-                src.rank = compacted ? mb.rank : nullptr;
-                src.T = caller_txps;
-                src.stride = n_txps;
-                NzScratch sc;
-                if ((rc2 = cells_to_csr(s->stream, src, n_cells, cell_aln_off, sc, blk)) != OEM_OK) break;
-                if (hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
-                    rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells_sparse: state read-back failed");
-                    break;
-                }
-            } else {
-                const double *d_res = mb.out;
-                double *d_full = nullptr;
-                bool expanded_on_host = false;
-                if (compacted && (knob("OEM_TEST_FAIL_FULL_ALLOC", 0) || hipMalloc((void **)&d_full, sizeof(double) * full_total) != hipSuccess)) {
-                    // no device memory for the expanded results: the compact ones and the rank table go to the host,
-                    // which expands them (a transcript that does not occur in a cell is 0)
-                    (void)hipGetLastError();
-                    d_full = nullptr;
-                    const size_t n_eff = (size_t)mb.n_problems * mb.txps_eff;
-                    std::vector<double> h_eff(n_eff);
-                    std::vector<uint32_t> h_rank((size_t)full_total);
-                    if (hipMemcpy(h_eff.data(), mb.out, sizeof(double) * n_eff, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(h_rank.data(), mb.rank, sizeof(uint32_t) * full_total, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
-                        rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: read-back failed");
-                        break;
-                    }
-                    for (size_t i = 0; i < (size_t)full_total; ++i)
-                        out[i] = h_rank[i] == kNoRank ? 0.0 : h_eff[(i / mb.txps_full) * mb.txps_eff + h_rank[i]];
-                    expanded_on_host = true;
-                }
-                if (compacted && !expanded_on_host) { // expand to the caller's [cell][transcript] (the queue is done with: its memory is free by now)
-                    if ((rc2 = launch_multi_expand(s, mb, d_full)) != OEM_OK || hipStreamSynchronize(s->stream) != hipSuccess) {
-                        hipFree(d_full);
-                        if (rc2 == OEM_OK) rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: expanding the results failed");
-                        break;
-                    }
-                    d_res = d_full;
-                }
-                const bool copied = expanded_on_host || hipMemcpy(out, d_res, sizeof(double) * full_total, hipMemcpyDeviceToHost) == hipSuccess;
-                hipFree(d_full);
-                if (!copied ||
-                    hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost) != hipSuccess) {
-                    rc2 = fail(OEM_ERR_HIP, "oem_em_run_cells: result read-back failed");
-                    break;
-                }
-            }
-            if (infos)
-                for (uint32_t c = 0; c < n_cells; ++c) {
-                    infos[c].niter = hs[c].niter;
-                    infos[c].n_passes = hs[c].n_passes;
-                    infos[c].converged = hs[c].converged;
-                    infos[c].reserved = 0;
-                    infos[c].rel_diff = hs[c].last_rel;
-                }
-        } while (false);
-        hipFree(d_reads);
-        return rc2;
-    };
-    rc = body();
+    DevBuf<uint64_t> d_reads;
+    int rc = run_batched_loop(run, g, s.get(), d_reads);
+    if (rc == OEM_OK) {
+        tm.lap("cells: EM loop");
+        rc = read_back_batched(run, g, s.get());
+    }
+    d_reads.reset();
     tm.lap("cells: read-back");
-    free_store(s);
+    s.reset();
     tm.lap("cells: free");
     return rc;
 }
 
-} // namespace
-
-// One group of consecutive cells [c0, c1): batched on the device when it can be (every pass over the
-// resident store serves all unfinished cells), otherwise cell after cell over the caller-order CSR.
-int run_cells_group(const uint64_t *cell_row_off, uint32_t c0, uint32_t c1, const uint64_t *row_ptr,
-                    const uint32_t *tid, const float *as_prob, const double *cov_prob, const CellsCoverage *cov_src,
-                    uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink, size_t g,
-                    oem_run_info *infos, bool *batched, const CellsGroupDevice *dev)
+// The fallback (max_iter == 0, a single cell, or a group the tiler declines): cells one after another, as row ranges
+// of one store over the caller-order CSR.
+int run_cells_serial(const CellsRun &run, const CellsGroup &g)
 {
-    *batched = false;
-    const uint32_t n_cells = c1 - c0;
-    const uint64_t r0 = cell_row_off[c0], r1 = cell_row_off[c1];
-    const uint64_t a0 = dev ? 0 : row_ptr[r0], a1 = dev ? dev->nnz : row_ptr[r1];
-    const uint64_t n_reads = r1 - r0, nnz = a1 - a0;
-    // The group's own offsets.  A group that starts at read 0 (the whole experiment, when it fits one group)
-    // takes the caller's arrays as they are: rebasing 31 M row offsets of a 625-cell batch into a fresh
-    // 250 MB vector cost ~60 ms of page faults, 7 % of the call.  Later groups rebase on a few threads.
-    std::vector<uint64_t> off_v, rp_v;
-    const uint64_t *off_p = cell_row_off + c0, *rp_p = row_ptr;
-    if (r0 != 0 || a0 != 0) {
-        off_v.resize((size_t)n_cells + 1);
-        rp_v.resize(n_reads + 1);
-        for (uint32_t c = 0; c <= n_cells; ++c) off_v[c] = cell_row_off[c0 + c] - r0;
-        unsigned nt = std::thread::hardware_concurrency();
-        if (nt > 16) nt = 16;
-        if (nt < 1 || n_reads < (1u << 20)) nt = 1;
-        auto rebase = [&](unsigned k) {
-            const uint64_t b = (n_reads + 1) * k / nt, e = (n_reads + 1) * (k + 1) / nt;
-            for (uint64_t r = b; r < e; ++r) rp_v[r] = row_ptr[r0 + r] - a0;
-        };
-        if (nt == 1) {
-            rebase(0);
-        } else {
-            std::vector<std::thread> th;
-            for (unsigned k = 0; k < nt; ++k) th.emplace_back(rebase, k);
-            for (auto &t : th) t.join();
-        }
-        off_p = off_v.data();
-        rp_p = rp_v.data();
-    }
-    // the cells' first alignments within the group
-    std::vector<uint64_t> aoff_v;
-    const uint64_t *aoff_p = dev ? dev->cell_aln_off : nullptr;
-    if (!dev) {
-        aoff_v.resize((size_t)n_cells + 1);
-        for (uint32_t c = 0; c <= n_cells; ++c) aoff_v[c] = rp_p[off_p[c]];
-        aoff_p = aoff_v.data();
-    }
-    const uint32_t *tid_g = tid ? tid + a0 : nullptr;
-    const float *p_g = as_prob ? as_prob + a0 : nullptr;
-    const double *cov_g = cov_prob ? cov_prob + a0 : nullptr;
-    double *out_g = sink.dense ? sink.dense + (uint64_t)c0 * n_txps : nullptr;
-    SparseBlock *blk = sink.blocks ? &(*sink.blocks)[g] : nullptr;
-    oem_run_info *infos_g = infos ? infos + c0 : nullptr;
-    // the coverage model of the group's cells, computed on the device: the weights stay there for the store
-    ResidentCsr res_csr;
-    ResidentCsr *resident = dev ? dev->resident : nullptr;
-    if (cov_src) {
-        OEM_TRY(ensure_device(device));
-        if (!resident) resident = &res_csr;
-        OEM_TRY(cells_coverage_group(*cov_src, off_p, aoff_p, n_cells, dev ? dev->first_cell : c0, rp_p, tid_g, p_g,
-                                     dev ? dev->aln_start : cov_src->aln_start + a0, dev ? dev->aln_end : cov_src->aln_end + a0,
-                                     cov_src->out_cov_prob ? cov_src->out_cov_prob + a0 : nullptr, n_reads, nnz, resident));
-    }
-
-    if (knob("OEM_SERIAL_CELLS", 0) == 0) { // testing build: force the cell-by-cell path
-        bool used = false;
-        int rcb = run_cells_batched(off_p, aoff_p, dev ? dev->d_cell_row_off : nullptr, n_cells, rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device,
-                                    max_iter, conv_thresh, out_g, blk, infos_g, &used, resident);
-        *batched = used;
-        if (rcb != OEM_OK || used) return rcb;
-    }
-    // fallback (max_iter == 0, a single cell, or a group the tiler declines): cells one after another
-    oem_store *s = nullptr;
+    oem_store *raw = nullptr;
     oem_store_opts opts;
     std::memset(&opts, 0, sizeof(opts));
     opts.reorder_rows = 1; // cells are row ranges of the caller-order CSR
-    if (resident) { // (the arrays were checked by the entry point; the store takes the resident CSR over)
-        OEM_TRY(ensure_device(device));
-        s = new (std::nothrow) oem_store();
-        if (!s) return fail(OEM_ERR_OOM, "oem_em_run_cells: host allocation failed");
-        const int rcs = create_store_impl(rp_p, tid_g, p_g, nullptr, n_reads, nnz, n_txps, device, &opts, s, nullptr, resident);
-        if (rcs != OEM_OK) {
-            free_store(s);
-            return rcs;
-        }
-    } else {
-        OEM_TRY(oem_store_create(rp_p, tid_g, p_g, cov_g, n_reads, nnz, n_txps, device, &opts, &s));
-    }
-    int rc = OEM_OK;
     NzScratch sc;
-    CellsNzSource src; // the cell's count vector (s->cnt after the run, as copy_counts_out reads it), caller's transcript order
-    src.T = src.stride = n_txps;
-    for (uint32_t c = 0; c < n_cells && rc == OEM_OK; ++c) {
-        RunArgs a;
-        a.row_begin = off_p[c];
-        a.row_end = off_p[c + 1];
-        a.total_reads = a.row_end - a.row_begin; // the cell's own store.len() (single_cell.rs:122-130)
-        a.max_iter = max_iter;
-        a.conv_thresh = conv_thresh;
-        a.min_iter_gate = 50;                    // em::em (single_cell.rs:150)
-        rc = run_em_device(s, a, infos_g ? &infos_g[c] : nullptr);
-        src.v = s->cnt;
-        if (rc == OEM_OK)
-            rc = blk ? cells_to_csr(s->stream, src, 1, aoff_p + c, sc, blk) : copy_counts_out(s, out_g + (uint64_t)c * n_txps);
+    StorePtr s;
+    if (g.resident) { // (the arrays were checked by the entry point; the store takes the resident CSR over)
+        OEM_TRY(ensure_device(run.device));
+        s.reset(new (std::nothrow) oem_store());
+        if (!s) return fail(OEM_ERR_OOM, "oem_em_run_cells: host allocation failed");
+        OEM_TRY(create_store_impl(g.row_ptr, g.tid, g.as_prob, nullptr, g.n_reads, g.nnz, run.n_txps, run.device, &opts, s.get(),
+                                  nullptr, g.resident));
+    } else {
+        OEM_TRY(oem_store_create(g.row_ptr, g.tid, g.as_prob, g.cov_prob, g.n_reads, g.nnz, run.n_txps, run.device, &opts, &raw));
+        s.reset(raw);
     }
-    free_store(s);
-    return rc;
+    CellsNzSource src; // the cell's count vector (s->cnt after the run, as copy_counts_out reads it), caller's transcript order
+    src.T = src.stride = run.n_txps;
+    for (uint32_t c = 0; c < g.n_cells; ++c) {
+        RunArgs a;
+        a.row_begin = g.cell_row_off[c];
+        a.row_end = g.cell_row_off[c + 1];
+        a.total_reads = a.row_end - a.row_begin; // the cell's own store.len() (single_cell.rs:122-130)
+        a.max_iter = run.max_iter;
+        a.conv_thresh = run.conv_thresh;
+        a.min_iter_gate = 50;                    // em::em (single_cell.rs:150)
+        OEM_TRY(run_em_device(s.get(), a, g.infos ? &g.infos[c] : nullptr));
+        src.v = s->cnt;
+        if (g.blk) OEM_TRY(cells_to_csr(s->stream, src, 1, g.cell_aln_off + c, sc, g.blk));
+        else OEM_TRY(copy_counts_out(s.get(), g.out_dense + (uint64_t)c * run.n_txps));
+    }
+    return OEM_OK;
 }
 
-} // namespace oem
+} // namespace
 
-namespace oem {
-void cells_last_timing(double *loop_ms, uint64_t *batched_passes)
+// ---- one group
+int run_cells_group(const CellsRun &run, const CellsGroup &g, bool *batched)
 {
-    if (loop_ms) *loop_ms = t_cells_loop_ms;
-    if (batched_passes) *batched_passes = t_cells_batched_passes;
+    *batched = false;
+    if (run.cov) { // the coverage model of the group's cells, computed on the device: the weights stay there for the store
+        OEM_TRY(ensure_device(run.device));
+        OEM_TRY(cells_coverage_group(*run.cov, g, g.resident));
+    }
+    if (knob("OEM_SERIAL_CELLS", 0) == 0) { // testing build: force the cell-by-cell path
+        const int rc = run_cells_batched(run, g, batched);
+        if (rc != OEM_OK || *batched) return rc;
+    }
+    return run_cells_serial(run, g);
 }
 
-const std::vector<CellsGroupPath> &cells_last_paths() { return t_cells_paths; }
-} // namespace oem
-
-namespace oem {
-
+// ---- the grouping rule
 uint64_t cells_max_group_nnz() { return (uint64_t)knob("OEM_CELLS_GROUP_NNZ", 1l << 30); } // testing build: small groups
 
 bool cells_group_fits(uint64_t cells, uint64_t reads, uint64_t gnnz, uint32_t n_txps, uint64_t max_group_nnz)
@@ -494,38 +403,127 @@ bool cells_group_fits(uint64_t cells, uint64_t reads, uint64_t gnnz, uint32_t n_
              tiles_est * buckets > (1ull << 29) || cells > 65535 /* gridDim.y of the per-cell kernels */);
 }
 
-namespace {
-
-// The body of both per-cell entry points (`who` names the caller in messages): argument checks, the NaN-coverage
-// fix-up, the cut into groups and the workers; every group hands its results to `sink`.
-int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
-              const uint32_t *tid, const float *as_prob, const double *cov_prob, uint64_t n_reads, uint64_t nnz,
-              uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh, const CellsSink &sink,
-              oem_run_info *infos, CellsCoverage *cov_src = nullptr)
+// ---- the record of the last call of this thread, and the argument check shared with the coverage entry point
+void cells_last_timing(double *loop_ms, uint64_t *batched_passes)
 {
-    if (!cell_row_off || !row_ptr || (n_cells && !sink.dense && !sink.blocks)) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
-    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
+    if (loop_ms) *loop_ms = t_cells_loop_ms;
+    if (batched_passes) *batched_passes = t_cells_batched_passes;
+}
+
+const std::vector<CellsGroupPath> &cells_last_paths() { return t_cells_paths; }
+
+int check_cell_row_off(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, uint64_t n_reads)
+{
     if (cell_row_off[0] != 0 || cell_row_off[n_cells] != n_reads)
         return fail(OEM_ERR_ARG, "%s: cell_row_off must span [0, n_reads]", who);
     for (uint32_t c = 0; c < n_cells; ++c)
         if (cell_row_off[c + 1] < cell_row_off[c])
             return fail(OEM_ERR_ARG, "%s: cell_row_off not non-decreasing at cell %u", who, c);
-    if (nnz > 0 && (!tid || !as_prob)) return fail(OEM_ERR_ARG, "%s: tid/as_prob is NULL", who);
+    return OEM_OK;
+}
+
+namespace {
+
+// ---- the one-call form
+// The caller's arrays of one call.
+struct CellsInput {
+    const uint64_t *cell_row_off;
+    uint32_t n_cells;
+    const uint64_t *row_ptr;
+    const uint32_t *tid;
+    const float *as_prob;
+    const double *cov_prob;
+    uint64_t n_reads, nnz;
+};
+
+// A group of a one-call run with what it owns: the rebased offsets and, with the coverage model, the CSR that stays on
+// the device for the store.
+struct CellsSlice {
+    CellsGroup g;
+    std::vector<uint64_t> off_v, rp_v, aoff_v;
+    ResidentCsr res;
+};
+
+// Cells [c0, c1) of the call as a group (the sink is the caller's to fill in).
+void slice_cells(const CellsInput &in, const CellsRun &run, uint32_t c0, uint32_t c1, CellsSlice *sl)
+{
+    CellsGroup &g = sl->g;
+    const uint32_t n_cells = c1 - c0;
+    const uint64_t r0 = in.cell_row_off[c0], r1 = in.cell_row_off[c1];
+    const uint64_t a0 = in.row_ptr[r0], a1 = in.row_ptr[r1];
+    const uint64_t n_reads = r1 - r0;
+    // The group's own offsets.  A group that starts at read 0 (the whole experiment, when it fits one group)
+    // takes the caller's arrays as they are: rebasing 31 M row offsets of a 625-cell batch into a fresh
+    // 250 MB vector cost ~60 ms of page faults, 7 % of the call.  Later groups rebase on a few threads.
+    g.cell_row_off = in.cell_row_off + c0;
+    g.row_ptr = in.row_ptr;
+    if (r0 != 0 || a0 != 0) {
+        sl->off_v.resize((size_t)n_cells + 1);
+        sl->rp_v.resize(n_reads + 1);
+        for (uint32_t c = 0; c <= n_cells; ++c) sl->off_v[c] = in.cell_row_off[c0 + c] - r0;
+        unsigned nt = std::thread::hardware_concurrency();
+        if (nt > 16) nt = 16;
+        if (nt < 1 || n_reads < (1u << 20)) nt = 1;
+        auto rebase = [&](unsigned k) {
+            const uint64_t b = (n_reads + 1) * k / nt, e = (n_reads + 1) * (k + 1) / nt;
+            for (uint64_t r = b; r < e; ++r) sl->rp_v[r] = in.row_ptr[r0 + r] - a0;
+        };
+        if (nt == 1) {
+            rebase(0);
+        } else {
+            std::vector<std::thread> th;
+            for (unsigned k = 0; k < nt; ++k) th.emplace_back(rebase, k);
+            for (auto &t : th) t.join();
+        }
+        g.cell_row_off = sl->off_v.data();
+        g.row_ptr = sl->rp_v.data();
+    }
+    // the cells' first alignments within the group
+    sl->aoff_v.resize((size_t)n_cells + 1);
+    for (uint32_t c = 0; c <= n_cells; ++c) sl->aoff_v[c] = g.row_ptr[g.cell_row_off[c]];
+    g.cell_aln_off = sl->aoff_v.data();
+    g.n_cells = n_cells;
+    g.n_reads = n_reads;
+    g.nnz = a1 - a0;
+    g.first_cell = c0;
+    g.tid = in.tid ? in.tid + a0 : nullptr;
+    g.as_prob = in.as_prob ? in.as_prob + a0 : nullptr;
+    g.cov_prob = in.cov_prob ? in.cov_prob + a0 : nullptr;
+    if (run.cov) {
+        g.aln_start = run.cov->aln_start + a0;
+        g.aln_end = run.cov->aln_end + a0;
+        g.out_cov_prob = run.cov->out_cov_prob ? run.cov->out_cov_prob + a0 : nullptr;
+        g.resident = &sl->res;
+    }
+}
+
+// The body of both per-cell entry points (`who` names the caller in messages): argument checks, the NaN-coverage
+// fix-up, the cut into groups and the workers; every group hands its results to `sink`.
+// (`dense`: the caller's n_cells x n_txps matrix, or `blocks`: one SparseBlock per group, in group = cell order).
+int run_cells(const char *who, CellsInput in, CellsRun run, double *dense, std::vector<SparseBlock> *blocks, oem_run_info *infos)
+{
+    const uint64_t *cell_row_off = in.cell_row_off, *row_ptr = in.row_ptr;
+    const uint32_t n_cells = in.n_cells, n_txps = run.n_txps;
+    const uint64_t n_reads = in.n_reads, nnz = in.nnz;
+    if (!cell_row_off || !row_ptr || (n_cells && !dense && !blocks)) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
+    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
+    OEM_TRY(check_cell_row_off(who, cell_row_off, n_cells, n_reads));
+    if (nnz > 0 && (!in.tid || !in.as_prob)) return fail(OEM_ERR_ARG, "%s: tid/as_prob is NULL", who);
     t_cells_loop_ms = 0.0;
     t_cells_batched_passes = 0;
     t_cells_paths.clear();
     StageTimer tm_all;
-    OEM_TRY(validate_csr(row_ptr, tid, n_reads, nnz, n_txps)); // all cells at once, on several host threads
+    OEM_TRY(validate_csr(row_ptr, in.tid, n_reads, nnz, n_txps)); // all cells at once, on several host threads
     tm_all.lap("cells: range checks");
-    if (cov_src) { // the per-call part of the coverage model (the annotation), shared by the groups
-        OEM_TRY(ensure_device(device));
-        if (nnz) OEM_TRY(cells_coverage_setup(cov_src));
+    if (run.cov) { // the per-call part of the coverage model (the annotation), shared by the groups
+        OEM_TRY(ensure_device(run.device));
+        if (nnz) OEM_TRY(cells_coverage_setup(run.cov));
         tm_all.lap("cells: coverage set-up");
     }
     // a read with a NaN coverage probability is dropped (em.rs:115), on every path below: the batched
     // groups create their stores directly, not through oem_store_create
     std::vector<double> cov_fixed;
-    if (cov_prob && zero_nan_rows(row_ptr, cov_prob, n_reads, nnz, &cov_fixed)) cov_prob = cov_fixed.data();
+    if (in.cov_prob && zero_nan_rows(row_ptr, in.cov_prob, n_reads, nnz, &cov_fixed)) in.cov_prob = cov_fixed.data();
 
     // Cells are independent problems, so a large experiment is cut into groups of consecutive cells
     // that bound the batched store (transcript space < 2^32, <= 2^30 alignments, and the layout
@@ -565,10 +563,11 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     // of a loop -- the few cells that run into max_iter, a handful of live tiles per pass -- shares the device with
     // the other group's full passes instead of leaving it idle (single_cell.rs:96-150 runs its cells on N worker
     // threads for the same reason).
-    if (sink.blocks) sink.blocks->assign(groups.size(), SparseBlock());
+    if (blocks) blocks->assign(groups.size(), SparseBlock());
     std::vector<CellsGroupPath> paths(groups.size()); // (each group's slot is written by the worker that runs it)
     for (size_t g = 0; g < groups.size(); ++g) paths[g] = CellsGroupPath{groups[g].first, groups[g].second, 0};
     CellsTiming timing;
+    run.timing = &timing;
     std::atomic<size_t> next{0};
     constexpr int kMaxWorkers = 4;
     int n_workers = (int)knob("OEM_CELLS_WORKERS", 2);
@@ -579,8 +578,7 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     std::atomic<bool> failed{false};                         // ... and this is what they stop on
     std::string errs[kMaxWorkers];
     auto work = [&](int wk) {
-        t_timing = &timing;
-        if (wk != 0 && hipSetDevice(device) != hipSuccess) {
+        if (wk != 0 && hipSetDevice(run.device) != hipSuccess) {
             rcs[wk] = OEM_ERR_HIP;
             errs[wk] = "hipSetDevice failed in a per-cell worker";
             failed.store(true);
@@ -591,8 +589,12 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
                 const size_t g = next.fetch_add(1);
                 if (g >= groups.size() || failed.load()) break;
                 bool batched = false;
-                rcs[wk] = run_cells_group(cell_row_off, groups[g].first, groups[g].second, row_ptr, tid, as_prob, cov_prob,
-                                          cov_src, n_txps, device, max_iter, conv_thresh, sink, g, infos, &batched);
+                CellsSlice sl;
+                slice_cells(in, run, groups[g].first, groups[g].second, &sl);
+                sl.g.out_dense = dense ? dense + (uint64_t)groups[g].first * n_txps : nullptr;
+                sl.g.blk = blocks ? &(*blocks)[g] : nullptr;
+                sl.g.infos = infos ? infos + groups[g].first : nullptr;
+                rcs[wk] = run_cells_group(run, sl.g, &batched);
                 paths[g].batched = batched ? 1u : 0u;
                 if (rcs[wk] != OEM_OK) break;
             }
@@ -603,7 +605,6 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
         }
         if (rcs[wk] != OEM_OK) failed.store(true);
         if (rcs[wk] != OEM_OK && errs[wk].empty()) errs[wk] = last_error_text(); // (the message is thread-local)
-        t_timing = nullptr;
     };
     {
         struct Joiner { // (a std::thread constructor that throws must not leave joinable threads behind)
@@ -625,29 +626,22 @@ int run_cells(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, c
     return OEM_OK;
 }
 
-} // namespace
-} // namespace oem
-
-using namespace oem;
-
-// ---------------------------------------------------------------------------
-// single-cell batch
-// ---------------------------------------------------------------------------
-extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
-                                const uint32_t *tid, const float *as_prob, const double *cov_prob,
-                                uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
-                                uint32_t max_iter, double conv_thresh, double *out,
-                                oem_run_info *infos)
+// The body of both sparse entry points: the groups' blocks become one oem_cells_result.
+int run_cells_sparse(const char *who, const CellsInput &in, const CellsRun &run, oem_cells_result **out)
 {
-    OEM_API_BEGIN
-    CellsSink sink;
-    sink.dense = out;
-    return run_cells("oem_em_run_cells", cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps,
-                     device, max_iter, conv_thresh, sink, infos);
-    OEM_API_END("oem_em_run_cells")
+    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
+    r->n_cells = in.n_cells;
+    r->infos.resize(in.n_cells);
+    std::vector<SparseBlock> blocks;
+    OEM_TRY(run_cells(who, in, run, nullptr, &blocks, r->infos.data()));
+    OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
+    *out = r.release();
+    return OEM_OK;
 }
 
-int oem::cells_result_from_blocks(const char *who, std::vector<SparseBlock> &blocks, oem_cells_result *r)
+} // namespace
+
+int cells_result_from_blocks(const char *who, std::vector<SparseBlock> &blocks, oem_cells_result *r)
 {
     const uint32_t n_cells = r->n_cells;
     r->cell_off.assign((size_t)n_cells + 1, 0);
@@ -669,26 +663,22 @@ int oem::cells_result_from_blocks(const char *who, std::vector<SparseBlock> &blo
     return OEM_OK;
 }
 
-namespace {
-// The body of both sparse entry points: the groups' blocks become one oem_cells_result.
-int run_cells_sparse(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
-                     const uint32_t *tid, const float *as_prob, const double *cov_prob, CellsCoverage *cov_src,
-                     uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, uint32_t max_iter, double conv_thresh,
-                     oem_cells_result **out)
+} // namespace oem
+
+using namespace oem;
+
+// ---- entry points
+extern "C" int oem_em_run_cells(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
+                                const uint32_t *tid, const float *as_prob, const double *cov_prob,
+                                uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device,
+                                uint32_t max_iter, double conv_thresh, double *out,
+                                oem_run_info *infos)
 {
-    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
-    r->n_cells = n_cells;
-    r->infos.resize(n_cells);
-    std::vector<SparseBlock> blocks;
-    CellsSink sink;
-    sink.blocks = &blocks;
-    OEM_TRY(run_cells(who, cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz, n_txps, device, max_iter,
-                      conv_thresh, sink, r->infos.data(), cov_src));
-    OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
-    *out = r.release();
-    return OEM_OK;
+    OEM_API_BEGIN
+    return run_cells("oem_em_run_cells", CellsInput{cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz},
+                     CellsRun{n_txps, device, max_iter, conv_thresh}, out, nullptr, infos);
+    OEM_API_END("oem_em_run_cells")
 }
-} // namespace
 
 extern "C" int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_cells, const uint64_t *row_ptr,
                                        const uint32_t *tid, const float *as_prob, const double *cov_prob,
@@ -698,8 +688,8 @@ extern "C" int oem_em_run_cells_sparse(const uint64_t *cell_row_off, uint32_t n_
     OEM_API_BEGIN
     if (!out) return fail(OEM_ERR_ARG, "oem_em_run_cells_sparse: out is NULL");
     *out = nullptr;
-    return run_cells_sparse("oem_em_run_cells_sparse", cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, nullptr,
-                            n_reads, nnz, n_txps, device, max_iter, conv_thresh, out);
+    return run_cells_sparse("oem_em_run_cells_sparse", CellsInput{cell_row_off, n_cells, row_ptr, tid, as_prob, cov_prob, n_reads, nnz},
+                            CellsRun{n_txps, device, max_iter, conv_thresh}, out);
     OEM_API_END("oem_em_run_cells_sparse")
 }
 
@@ -719,13 +709,7 @@ extern "C" int oem_em_run_cells_coverage_sparse(const uint64_t *cell_row_off, ui
     *out = nullptr;
     if (!cell_row_off || !row_ptr || !txp_len || (nnz && (!tid || !as_prob || !aln_start || !aln_end)))
         return fail(OEM_ERR_ARG, "%s: NULL argument", who);
-    if (bin_width == 0)
-        return fail(OEM_ERR_ARG, "coverage model with 0 bin width is not implemented (logistic_probability.rs:59, binomial_probability.rs:192)");
-    if (model != 0 && model != 1) return fail(OEM_ERR_ARG, "%s: model must be 0 (logistic) or 1 (binomial)", who);
-    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
-    if (n_txps >= (uint32_t)INT_MAX) return fail(OEM_ERR_ARG, "%s: needs n_txps < 2^31 - 1", who);
-    if (nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs nnz < 2^32", who);
-    if (n_reads >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs n_reads < 2^32", who);
+    OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, nnz, n_reads));
     // (run_cells checks cell_row_off and the CSR before any device work)
     CellsCoverage cc;
     cc.aln_start = aln_start;
@@ -736,8 +720,8 @@ extern "C" int oem_em_run_cells_coverage_sparse(const uint64_t *cell_row_off, ui
     cc.model = model;
     cc.growth_rate = growth_rate;
     cc.out_cov_prob = out_cov_prob;
-    return run_cells_sparse(who, cell_row_off, n_cells, row_ptr, tid, as_prob, nullptr, &cc, n_reads, nnz, n_txps, device,
-                            max_iter, conv_thresh, out);
+    return run_cells_sparse(who, CellsInput{cell_row_off, n_cells, row_ptr, tid, as_prob, nullptr, n_reads, nnz},
+                            CellsRun{n_txps, device, max_iter, conv_thresh, &cc}, out);
     OEM_API_END("oem_em_run_cells_coverage_sparse")
 }
 

@@ -1,7 +1,7 @@
 // oem_cells_stream.hip -- the per-cell session (oem_cells_stream_*): cells are pushed one by one, from any number of
 // threads (single_cell.rs:96-193: N workers each pop one cell and build its store), staged in host memory, cut into
-// groups and run through the per-cell driver's unit of work (run_cells_group, oem_cells.hip) by two device workers
-// while later cells still arrive.
+// groups and run through the per-cell driver's unit of work (a CellsGroup, run_cells_group, oem_cells.hip) by two
+// device workers while later cells still arrive.
 //
 //   push      checks the cell on the calling thread, reserves its place in the open group under the session lock
 //             (ticket, read and alignment offsets) and copies the arrays outside the lock.  The open group is closed --
@@ -18,7 +18,6 @@
 //   finish    closes the last group, joins the workers and concatenates the groups' blocks in ticket order.
 #include <algorithm>
 #include <chrono>
-#include <climits>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -155,15 +154,6 @@ struct GroupResult {
     std::vector<oem_run_info> infos;
 };
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { (void)hipFree(p); }
-};
-
 } // namespace
 } // namespace oem
 
@@ -285,8 +275,7 @@ int oem_cells_stream::run_group(Group &g, hipStream_t st, GroupResult *out, bool
     if (h_err)
         return fail(OEM_ERR_STATE, "oem_cells_stream: the staged row pointers of the group of cell %llu fail the device's range check",
                     (unsigned long long)g.first_ticket);
-    (void)hipFree(d_rp.p);
-    d_rp.p = nullptr;
+    d_rp.reset();
     tm.lap("stream: upload + row pointers");
     {
         std::lock_guard<std::mutex> lk(mu);
@@ -297,21 +286,24 @@ int oem_cells_stream::run_group(Group &g, hipStream_t st, GroupResult *out, bool
 
     res.host_row_ptr = &Group::host_row_ptr;
     res.host_row_ptr_ctx = &g;
-    CellsGroupDevice dev;
-    dev.resident = &res;
-    dev.d_cell_row_off = d_tab.p + 2 * ((size_t)nc + 1);
-    dev.cell_aln_off = g.aln_off.data();
-    dev.aln_start = sg.start;
-    dev.aln_end = sg.end;
-    dev.nnz = g.nnz;
-    dev.first_cell = g.first_ticket;
-    std::vector<SparseBlock> blocks(1);
-    CellsSink sink;
-    sink.blocks = &blocks;
     out->infos.assign(nc, oem_run_info{});
-    OEM_TRY(run_cells_group(g.read_off.data(), 0, nc, nullptr, sg.tid, sg.p, nullptr, o.coverage ? &cov : nullptr, o.n_txps,
-                            o.device, o.max_iter, o.conv_thresh, sink, 0, out->infos.data(), batched, &dev));
-    out->blk = std::move(blocks[0]);
+    CellsGroup cg; // no host row_ptr (the host layout builder asks `res` for one), cell_row_off on the device too
+    cg.n_cells = nc;
+    cg.n_reads = g.n_reads;
+    cg.nnz = g.nnz;
+    cg.first_cell = g.first_ticket;
+    cg.cell_row_off = g.read_off.data();
+    cg.cell_aln_off = g.aln_off.data();
+    cg.tid = sg.tid;
+    cg.as_prob = sg.p;
+    cg.aln_start = sg.start;
+    cg.aln_end = sg.end;
+    cg.resident = &res;
+    cg.d_cell_row_off = d_tab.p + 2 * ((size_t)nc + 1);
+    cg.blk = &out->blk;
+    cg.infos = out->infos.data();
+    CellsRun run{o.n_txps, o.device, o.max_iter, o.conv_thresh, o.coverage ? &cov : nullptr};
+    OEM_TRY(run_cells_group(run, cg, batched));
     tm.lap("stream: group run");
     return OEM_OK;
 }
@@ -386,10 +378,7 @@ extern "C" int oem_cells_stream_create(const oem_cells_stream_opts *opts, const 
         if (r) return fail(OEM_ERR_ARG, "%s: a reserved word is not 0", who);
     if (opts->coverage) {
         if (!txp_len) return fail(OEM_ERR_ARG, "%s: coverage = 1 needs txp_len", who);
-        if (opts->bin_width == 0)
-            return fail(OEM_ERR_ARG, "coverage model with 0 bin width is not implemented (logistic_probability.rs:59, binomial_probability.rs:192)");
-        if (opts->model != 0 && opts->model != 1) return fail(OEM_ERR_ARG, "%s: model must be 0 (logistic) or 1 (binomial)", who);
-        if (opts->n_txps >= (uint32_t)INT_MAX) return fail(OEM_ERR_ARG, "%s: needs n_txps < 2^31 - 1", who);
+        OEM_TRY(check_cells_coverage_args(who, opts->bin_width, opts->model, opts->n_txps, 0, 0));
     }
     OEM_TRY(ensure_device(opts->device));
     std::unique_ptr<oem_cells_stream> s(new oem_cells_stream());

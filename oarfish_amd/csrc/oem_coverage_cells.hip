@@ -29,8 +29,8 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "oem_cells.h"
 #include "oem_coverage_common.h"
-#include "oem_driver.h"
 
 namespace oem {
 namespace {
@@ -356,22 +356,31 @@ int cells_coverage_setup(CellsCoverage *cc)
     cc->max_nb = max_nb;
     StreamGuard sg;
     OEM_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    Arena ar;
-    uint32_t *d_gerr;
-    OEM_TRY(ar.get(&d_gerr, 1));
+    DevBuf<uint32_t> d_gerr;
+    OEM_TRY(dev_alloc(&d_gerr.p, 1, nullptr));
     OEM_TRY(dev_alloc(&cc->d_len, cc->n_txps, nullptr));
     OEM_TRY(dev_alloc(&cc->d_nb, cc->n_txps, nullptr));
-    OEM_TRY(setup_txps(sg.s, cc->txp_len, cc->n_txps, cc->bin_width, cc->d_len, cc->d_nb, d_gerr, &cc->gerr));
+    OEM_TRY(setup_txps(sg.s, cc->txp_len, cc->n_txps, cc->bin_width, cc->d_len, cc->d_nb, d_gerr.p, &cc->gerr));
     OEM_HIP(hipStreamSynchronize(sg.s));
     return OEM_OK;
 }
 
-int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, const uint64_t *cell_aln_off,
-                         uint32_t n_cells, uint64_t first_cell, const uint64_t *row_ptr, const uint32_t *tid,
-                         const float *as_prob, const uint32_t *aln_start, const uint32_t *aln_end, double *out_cov_prob,
-                         uint64_t n_reads, uint64_t nnz, ResidentCsr *out)
+int check_cells_coverage_args(const char *who, uint32_t bin_width, int model, uint32_t n_txps, uint64_t nnz, uint64_t n_reads)
+{
+    if (bin_width == 0)
+        return fail(OEM_ERR_ARG, "coverage model with 0 bin width is not implemented (logistic_probability.rs:59, binomial_probability.rs:192)");
+    if (model != 0 && model != 1) return fail(OEM_ERR_ARG, "%s: model must be 0 (logistic) or 1 (binomial)", who);
+    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
+    if (n_txps >= (uint32_t)INT_MAX) return fail(OEM_ERR_ARG, "%s: needs n_txps < 2^31 - 1", who);
+    if (nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs nnz < 2^32", who);
+    if (n_reads >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs n_reads < 2^32", who);
+    return OEM_OK;
+}
+
+int cells_coverage_group(const CellsCoverage &cc, const CellsGroup &g, ResidentCsr *out)
 {
     StageTimer tm;
+    const uint64_t n_reads = g.n_reads, nnz = g.nnz;
     const char *who = "oem_em_run_cells_coverage_sparse";
     StreamGuard sg;
     OEM_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
@@ -379,12 +388,12 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
     // 1. what the store keeps (caller order: row pointers narrowed on the device, ids, the weights written below)
     if (!out->row_ptr) {
         OEM_TRY(dev_alloc(&out->row_ptr, n_reads + 1, nullptr));
-        OEM_TRY(upload_row_ptr_u32(st, row_ptr, n_reads + 1, out->row_ptr));
+        OEM_TRY(upload_row_ptr_u32(st, g.row_ptr, n_reads + 1, out->row_ptr));
     }
     OEM_TRY(dev_alloc(&out->tid, nnz, nullptr));
     OEM_TRY(dev_alloc(&out->w64, nnz, nullptr));
     if (nnz == 0) return OEM_OK;
-    OEM_HIP(hipMemcpyAsync(out->tid, tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(out->tid, g.tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
     // the coverage scratch: released when this scope ends, before the store's layout is built
     Arena ar;
     uint32_t *d_start, *d_end;
@@ -394,9 +403,9 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
     OEM_TRY(ar.get(&d_end, nnz));
     OEM_TRY(ar.get(&d_p, nnz));
     OEM_TRY(ar.get(&d_cov, nnz));
-    OEM_HIP(hipMemcpyAsync(d_start, aln_start, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemcpyAsync(d_end, aln_end, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemcpyAsync(d_p, as_prob, sizeof(float) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_start, g.aln_start, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_end, g.aln_end, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+    OEM_HIP(hipMemcpyAsync(d_p, g.as_prob, sizeof(float) * nnz, hipMemcpyHostToDevice, st));
     OEM_HIP(hipStreamSynchronize(st));
     tm.lap("cov+em: group upload");
 
@@ -404,8 +413,8 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
     // of them do not fit half the free memory
     size_t free_b = 0, total_b = 0;
     OEM_HIP(hipMemGetInfo(&free_b, &total_b));
-    const std::vector<Chunk> chunks = plan_chunks(cell_row_off, n_cells, row_ptr, cc.n_txps, cc.all_bins, cc.max_nb,
-                                                  free_b / 2, 4 /* segment ids */, 0, cell_aln_off);
+    const std::vector<Chunk> chunks = plan_chunks(g.cell_row_off, g.n_cells, g.row_ptr, cc.n_txps, cc.all_bins, cc.max_nb,
+                                                  free_b / 2, 4 /* segment ids */, 0, g.cell_aln_off);
     ChunkBufs b;
     OEM_TRY(alloc_chunk_bufs(st, ar, chunks, cc.n_txps, &b));
     std::vector<uint32_t> h_coff, h_err;
@@ -413,19 +422,19 @@ int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, 
         const uint32_t ncc = ch.c1 - ch.c0;
         h_coff.resize((size_t)ncc + 1);
         h_err.resize(ncc);
-        for (uint32_t c = 0; c <= ncc; ++c) h_coff[c] = (uint32_t)(cell_aln_off[ch.c0 + c] - ch.a0);
+        for (uint32_t c = 0; c <= ncc; ++c) h_coff[c] = (uint32_t)(g.cell_aln_off[ch.c0 + c] - ch.a0);
         OEM_TRY(run_chunk(st, ar, b, cc.d_len, cc.d_nb, cc.n_txps, cc.bin_width, cc.model, cc.growth_rate, ncc,
                           (uint32_t)(ch.r1 - ch.r0), (uint32_t)(ch.a1 - ch.a0), h_coff.data(), out->row_ptr + ch.r0,
                           (uint32_t)ch.a0, out->tid + ch.a0, d_start + ch.a0, d_end + ch.a0, d_cov + ch.a0, h_err.data()));
         for (uint32_t c = 0; c < ncc; ++c) {
             const uint32_t f = h_err[c] | (h_coff[c + 1] > h_coff[c] ? cc.gerr : 0u);
-            if (f) return fail(OEM_ERR_STATE, "%s: cell %llu: %s", who, (unsigned long long)(first_cell + ch.c0 + c), cov_err_text(f));
+            if (f) return fail(OEM_ERR_STATE, "%s: cell %llu: %s", who, (unsigned long long)(g.first_cell + ch.c0 + c), cov_err_text(f));
         }
     }
     tm.lap("cov+em: coverage");
     // 3. the column the EM uses, for the caller who asked for it; the weights straight into the store's buffer
-    if (out_cov_prob)
-        OEM_HIP(hipMemcpyAsync(out_cov_prob, d_cov, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
+    if (g.out_cov_prob)
+        OEM_HIP(hipMemcpyAsync(g.out_cov_prob, d_cov, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
     hipLaunchKernelGGL(k_cc_weights, dim3((uint32_t)((n_reads + kCC - 1) / kCC)), dim3(kCC), 0, st, out->row_ptr, d_p, d_cov,
                        (uint32_t)n_reads, out->w64);
     OEM_HIP(hipGetLastError());
@@ -448,18 +457,8 @@ extern "C" int oem_coverage_probs_cells_device(const uint64_t *cell_row_off, uin
     const char *who = "oem_coverage_probs_cells_device";
     if (!cell_row_off || !row_ptr || !txp_len || (nnz && (!tid || !aln_start || !aln_end || !out_cov_prob)))
         return fail(OEM_ERR_ARG, "%s: NULL argument", who);
-    if (bin_width == 0)
-        return fail(OEM_ERR_ARG, "coverage model with 0 bin width is not implemented (logistic_probability.rs:59, binomial_probability.rs:192)");
-    if (model != 0 && model != 1) return fail(OEM_ERR_ARG, "%s: model must be 0 (logistic) or 1 (binomial)", who);
-    if (n_txps == 0) return fail(OEM_ERR_ARG, "%s: n_txps is 0", who);
-    if (n_txps >= (uint32_t)INT_MAX) return fail(OEM_ERR_ARG, "%s: needs n_txps < 2^31 - 1", who);
-    if (nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs nnz < 2^32", who);
-    if (n_reads >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: needs n_reads < 2^32", who);
-    if (cell_row_off[0] != 0 || cell_row_off[n_cells] != n_reads)
-        return fail(OEM_ERR_ARG, "%s: cell_row_off must span [0, n_reads]", who);
-    for (uint32_t c = 0; c < n_cells; ++c)
-        if (cell_row_off[c + 1] < cell_row_off[c])
-            return fail(OEM_ERR_ARG, "%s: cell_row_off not non-decreasing at cell %u", who, c);
+    OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, nnz, n_reads));
+    OEM_TRY(check_cell_row_off(who, cell_row_off, n_cells, n_reads));
     StageTimer tm;
     OEM_TRY(validate_csr(row_ptr, tid, n_reads, nnz, n_txps));
     tm.lap("cov cells: range checks");

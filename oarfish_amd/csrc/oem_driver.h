@@ -42,6 +42,21 @@ int dev_alloc(T **p, size_t n, uint64_t *acct)
     return OEM_OK;
 }
 
+// A device buffer that is freed with its scope (filled through dev_alloc(&b.p, ...) or hipMalloc).
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    void reset()
+    {
+        (void)hipFree(p);
+        p = nullptr;
+    }
+};
+
 // oem_api.hip: checks of the caller's arrays, store creation and destruction
 int validate_csr(const uint64_t *row_ptr, const uint32_t *tid, uint64_t n_reads, uint64_t nnz, uint32_t n_txps);
 uint64_t zero_nan_rows(const uint64_t *row_ptr, const double *cov, uint64_t n_reads, uint64_t nnz, std::vector<double> *fixed);
@@ -86,12 +101,15 @@ int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float 
                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, const oem_store_opts *opts, oem_store *s,
                       const CellRelabel *relabel = nullptr, ResidentCsr *resident = nullptr);
 void free_store(oem_store *s);
+// The inverse: a per-cell batch the tiler declined hands the CSR back, with the caller's ids `tid` (host) again.
+int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *tid);
 // u64 row pointers (host) -> u32 ones on the device, through a temporary u64 copy (no second host array)
 int upload_row_ptr_u32(hipStream_t st, const uint64_t *row_ptr, uint64_t n, uint32_t *d_out);
 
 // oem_coverage_cells.hip: the per-cell coverage model as the source of a cells EM's weights
 // (oem_em_run_cells_coverage_sparse).  What the groups share is set up once per call; each group then computes its
-// cells' coverage on the device from its own resident arrays and leaves the weights in a ResidentCsr.
+// cells' coverage on the device from its own resident arrays and leaves the weights in a ResidentCsr
+// (cells_coverage_group, oem_cells.h).
 struct CellsCoverage {
     const uint32_t *aln_start = nullptr, *aln_end = nullptr; // host, caller order
     const uint64_t *txp_len = nullptr;                       // host, n_txps
@@ -114,14 +132,10 @@ struct CellsCoverage {
     }
 };
 int cells_coverage_setup(CellsCoverage *cc);
-// Cells [0, n_cells) of a group (first_cell: the first one's index in the call, for messages); row_ptr, cell_row_off
-// and cell_aln_off (the cells' first alignments) relative to the group, tid / as_prob / aln_start / aln_end the
-// group's own; out_cov_prob: the group's part of the caller's column, or NULL.  A group whose u32 row pointers are on
-// the device already has them in out->row_ptr, and row_ptr is not read.
-int cells_coverage_group(const CellsCoverage &cc, const uint64_t *cell_row_off, const uint64_t *cell_aln_off,
-                         uint32_t n_cells, uint64_t first_cell, const uint64_t *row_ptr, const uint32_t *tid,
-                         const float *as_prob, const uint32_t *aln_start, const uint32_t *aln_end, double *out_cov_prob,
-                         uint64_t n_reads, uint64_t nnz, ResidentCsr *out);
+// ... and the checks its entry points share, in this order: bin width, model, n_txps, nnz, n_reads
+int check_cells_coverage_args(const char *who, uint32_t bin_width, int model, uint32_t n_txps, uint64_t nnz, uint64_t n_reads);
+// oem_cells.hip: cell_row_off spans [0, n_reads] and does not decrease
+int check_cell_row_off(const char *who, const uint64_t *cell_row_off, uint32_t n_cells, uint64_t n_reads);
 
 // oem_em_driver.hip: one EM run with the loop state on the device
 struct RunArgs {

@@ -23,7 +23,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import _ab  # noqa: E402,F401  (OEM_AB_DIR: A/B against a snapshot build)
 import oarfish_amd  # noqa: E402
 from oarfish_amd import _lib, synth  # noqa: E402
 from oarfish_amd.em import _take_cells_result  # noqa: E402
