@@ -40,7 +40,7 @@ extern "C" {
  *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy), the per-cell coverage model
  *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse), the bulk coverage model
  *    and the store on its column in one call (oem_store_create_coverage, oem_builder_store_create_coverage), the
- *    per-cell session (oem_cells_stream_*). */
+ *    per-cell session (oem_cells_stream_*), the per-iteration rel_diff record (OEM_OPT_RUN_HISTORY, oem_run_history). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -128,12 +128,18 @@ typedef enum {
     OEM_OPT_BATCH_BOOTSTRAP = 1, /* value 1 (default): oem_bootstrap runs its replicates in batches that share
                                     each pass over the matrix (4 per pass, two such chains side by side on their
                                     own streams) when it can (narrow window cap, multiplicities < 256); 0: one per pass */
-    OEM_OPT_BOOTSTRAP_FIRST_REPLICA = 2 /* value b0 (default 0): replicate k of the next oem_bootstrap calls
+    OEM_OPT_BOOTSTRAP_FIRST_REPLICA = 2, /* value b0 (default 0): replicate k of the next oem_bootstrap calls
                                     draws the device resample of global replica b0 + k.  Lets N processes
                                     that each hold the whole store split one set of replicates with no
                                     collective (the reference's replicates are independent, em.rs:303-309).
                                     b0 <= 2^32 - 1, and an oem_bootstrap call that draws its resamples must keep
                                     b0 + n_boot - 1 <= 2^32 - 1: it returns OEM_ERR_ARG instead of wrapping. */
+    OEM_OPT_RUN_HISTORY = 3 /* value K (default 0 = off): every oem_em_run and oem_bootstrap on the store records the
+                                    rel_diff of each loop pass (em.rs:194-201, the value logged at :219-233 / :405-419),
+                                    the first min(K, max_iter) passes of each run; later passes are counted, not
+                                    stored.  Read with oem_run_history.  The lane that takes the stopping decision
+                                    writes the 8 bytes; K <= 2^32 - 1, and the record takes min(K, max_iter) doubles on
+                                    the device and per replicate on the host.  The per-cell calls do not record. */
 } oem_option;
 int oem_store_set_option(oem_store *store, uint32_t option, uint64_t value);
 
@@ -147,8 +153,11 @@ int oem_store_bytes(const oem_store *store, uint64_t *hbm_bytes, uint64_t *algor
 
 /* Facts about the resident layout.  OEM_INFO_WEIGHT_DICT_ENTRIES: entries of the weight table when the local
  * weights are dictionary-coded (oem_store_opts.weight_coding), 0 when the store streams f32 / f64 weights;
- * OEM_INFO_TILES, OEM_INFO_REMOTE_ALIGNMENTS: tiles of the layout and alignments outside their tile's window. */
-typedef enum { OEM_INFO_WEIGHT_DICT_ENTRIES = 1, OEM_INFO_TILES = 2, OEM_INFO_REMOTE_ALIGNMENTS = 3 } oem_store_info_key;
+ * OEM_INFO_TILES, OEM_INFO_REMOTE_ALIGNMENTS: tiles of the layout and alignments outside their tile's window;
+ * OEM_INFO_RUN_HISTORY_STORED: entries per run the last oem_em_run / oem_bootstrap could store under OEM_OPT_RUN_HISTORY,
+ * min(K, max_iter) of that call (a run holds the smaller of this and its length); 0 when it recorded nothing. */
+typedef enum { OEM_INFO_WEIGHT_DICT_ENTRIES = 1, OEM_INFO_TILES = 2, OEM_INFO_REMOTE_ALIGNMENTS = 3,
+               OEM_INFO_RUN_HISTORY_STORED = 4 } oem_store_info_key;
 int oem_store_info(const oem_store *store, uint32_t key, uint64_t *value);
 
 /* --------------------------------------------------------------------- */
@@ -297,6 +306,18 @@ int oem_m_step(oem_store *store, const double *theta, const uint32_t *row_w, dou
 int oem_em_run(oem_store *store, const double *init_abundances, uint32_t max_iter,
                double conv_thresh, uint32_t min_iter_gate, double *out_counts,
                oem_run_info *info);
+
+/* The rel_diff trajectory of a run recorded under OEM_OPT_RUN_HISTORY: h[k] is the rel_diff of loop pass k
+ * (em.rs:194-201, before :234 resets it), k = `niter` as the stopping rule sees it (before em.rs:218, and on the
+ * `break` branch), so the reference's line `iteration N; rel diff R` (em.rs:219-233 / :405-419) is h[N-1].  A run has
+ * n = info.niter + info.converged = info.n_passes - 1 entries and h[n-1] is info.rel_diff, bit for bit.
+ *   run      : 0 after oem_em_run; the replicate index b (row b of `out` / `infos`) after oem_bootstrap
+ *   out      : receives min(capacity, recorded) entries; NULL with capacity 0 queries the length alone
+ *   out_len  : optional; the run's n, which may exceed what was recorded (oem_store_info: OEM_INFO_RUN_HISTORY_STORED)
+ * OEM_ERR_STATE when the last oem_em_run / oem_bootstrap on the store recorded nothing (the option was off, or there has
+ * been no run yet); OEM_ERR_ARG for a run out of range.  The record of a call is valid until the next oem_em_run,
+ * oem_bootstrap or change of the option on that store. */
+int oem_run_history(const oem_store *store, uint32_t run, double *out, uint32_t capacity, uint32_t *out_len);
 
 /* --------------------------------------------------------------------- */
 /* the steps right after the EM, on the same resident store                */

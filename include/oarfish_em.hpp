@@ -130,6 +130,28 @@ struct EMInfo { // oarfish_types.rs:408-428
     int device = 0;
 };
 
+// OEM_OPT_RUN_HISTORY: the store records the rel_diff of each loop pass of its next em / em_par / bootstrap calls, the
+// first min(capacity, max_iter) passes of each run; 0 switches it off (the default).
+inline void set_run_history(oem_store *store, uint32_t capacity)
+{
+    check(oem_store_set_option(store, OEM_OPT_RUN_HISTORY, capacity), "oem_store_set_option");
+}
+
+// The recorded rel_diff of run `run` of the last call on the store (0 after em / em_par, the replicate after
+// bootstrap): entry N - 1 is the R of the reference's log line `iteration N; rel diff R` (em.rs:219-233, :405-419).
+// *run_len (optional) receives the run's loop passes, which may exceed the entries stored.
+inline std::vector<double> run_history(const oem_store *store, uint32_t run = 0, uint32_t *run_len = nullptr)
+{
+    uint32_t n = 0;
+    uint64_t stored = 0;
+    check(oem_run_history(store, run, nullptr, 0, &n), "oem_run_history");
+    check(oem_store_info(store, OEM_INFO_RUN_HISTORY_STORED, &stored), "oem_store_info");
+    std::vector<double> h(n < stored ? n : (size_t)stored);
+    check(oem_run_history(store, run, h.data(), (uint32_t)h.size(), nullptr), "oem_run_history");
+    if (run_len) *run_len = n;
+    return h;
+}
+
 namespace em {
 
 namespace detail {

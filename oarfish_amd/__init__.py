@@ -11,9 +11,9 @@ from ._lib import OemError, device_count  # noqa: F401
 from .types import (AlignmentFilters, DeviceStore, EMInfo, InMemoryAlignmentStore,  # noqa: F401
                     RunInfo, TranscriptInfo)
 from .em import (CellsStream, bootstrap, cells_coverage_probs, em, em_cells, em_cells_coverage_sparse, em_cells_sparse,  # noqa: F401
-                 em_par)
+                 em_par, history_log_records)
 
 __all__ = [
     "CellsStream", "AlignmentFilters", "DeviceStore", "EMInfo", "InMemoryAlignmentStore", "RunInfo",
-    "TranscriptInfo", "bootstrap", "cells_coverage_probs", "em", "em_cells", "em_cells_coverage_sparse", "em_cells_sparse", "em_par", "OemError", "device_count",
+    "TranscriptInfo", "bootstrap", "cells_coverage_probs", "em", "em_cells", "em_cells_coverage_sparse", "em_cells_sparse", "em_par", "history_log_records", "OemError", "device_count",
 ]

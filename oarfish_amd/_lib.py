@@ -23,6 +23,7 @@ OEM_UNIQUE_ID_BYTES = 128
 OEM_P2P_HANDLE_BYTES = 128
 OEM_OPT_BATCH_BOOTSTRAP = 1
 OEM_OPT_BOOTSTRAP_FIRST_REPLICA = 2
+OEM_OPT_RUN_HISTORY = 3
 OEM_COMM_OPT_P2P_MAX_BYTES = 1
 OEM_COMM_OPT_P2P_SHAPE = 2
 OEM_COMM_OPT_P2P_TIMEOUT_MS = 3
@@ -39,6 +40,7 @@ OEM_CELLS_STREAM_INFO_GROUPS_BATCHED = 6
 OEM_INFO_WEIGHT_DICT_ENTRIES = 1
 OEM_INFO_TILES = 2
 OEM_INFO_REMOTE_ALIGNMENTS = 3
+OEM_INFO_RUN_HISTORY_STORED = 4
 
 # every symbol include/oarfish_em.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -49,7 +51,7 @@ ABI_SYMBOLS = [
     "oem_builder_coverage_probs_binomial", "oem_coverage_probs_device", "oem_builder_coverage_probs_device",
     "oem_coverage_probs_cells_device",
     "oem_builder_store_create", "oem_store_create_coverage", "oem_builder_store_create_coverage",
-    "oem_m_step", "oem_em_run", "oem_aux_counts", "oem_assignment_probs",
+    "oem_m_step", "oem_em_run", "oem_run_history", "oem_aux_counts", "oem_assignment_probs",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
@@ -158,6 +160,7 @@ def _load(path: str) -> C.CDLL:
     L.oem_builder_store_create_coverage.argtypes = [vp, u32, i32, f64, i32, vp, vp, C.POINTER(vp)]
     L.oem_m_step.argtypes = [vp, vp, vp, vp]
     L.oem_em_run.argtypes = [vp, vp, u32, f64, u32, vp, C.POINTER(RunInfoC)]
+    L.oem_run_history.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
     L.oem_aux_counts.argtypes = [vp, vp, vp]
     L.oem_assignment_probs.argtypes = [vp, vp, f64, vp]
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]

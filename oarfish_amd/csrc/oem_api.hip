@@ -146,7 +146,7 @@ void free_store(oem_store *s)
         if (c > 0 && b.stream) { hipStreamSynchronize(b.stream); hipStreamDestroy(b.stream); }
         hipFree(b.d_row_w);
         hipFree(b.theta); hipFree(b.cnt); hipFree(b.out); hipFree(b.queue); hipFree(b.state); hipFree(b.rel_slots);
-        hipFree(b.row_w); hipFree(b.overflow);
+        hipFree(b.row_w); hipFree(b.overflow); hipFree(b.d_history);
         if (b.h_state) hipHostFree(b.h_state);
         if (b.h_out) hipHostFree(b.h_out);
     }
@@ -159,6 +159,7 @@ void free_store(oem_store *s)
     hipFree(s->rel_slots);
     hipFree(s->d_state);
     hipFree(s->d_row_w);
+    hipFree(s->d_history);
     if (s->h_state) hipHostFree(s->h_state);
     if (s->h_pinned) hipHostFree(s->h_pinned);
     if (s->stream) hipStreamDestroy(s->stream);
@@ -728,9 +729,31 @@ extern "C" int oem_store_set_option(oem_store *store, uint32_t option, uint64_t 
         if (value > 0xffffffffull) return fail(OEM_ERR_ARG, "oem_store_set_option: replica index out of range");
         store->bootstrap_first_replica = (uint32_t)value;
         return OEM_OK;
+    case OEM_OPT_RUN_HISTORY:
+        if (value > 0xffffffffull) return fail(OEM_ERR_ARG, "oem_store_set_option: history capacity out of range");
+        store->history_opt = (uint32_t)value;
+        store->history = oem::RunHistory(); // a change of the option ends the previous call's record
+        return OEM_OK;
     default: return fail(OEM_ERR_ARG, "oem_store_set_option: unknown option %u", option);
     }
     OEM_API_END("oem_store_set_option")
+}
+
+extern "C" int oem_run_history(const oem_store *store, uint32_t run, double *out, uint32_t capacity, uint32_t *out_len)
+{
+    OEM_API_BEGIN
+    if (!store) return fail(OEM_ERR_ARG, "oem_run_history: store is NULL");
+    if (!out && capacity) return fail(OEM_ERR_ARG, "oem_run_history: out is NULL with a capacity of %u", capacity);
+    std::lock_guard<std::mutex> lk(const_cast<oem_store *>(store)->mu);
+    const oem::RunHistory &h = store->history;
+    if (!h.valid) return fail(OEM_ERR_STATE, "oem_run_history: the last call on this store recorded nothing (OEM_OPT_RUN_HISTORY)");
+    if (run >= h.n.size()) return fail(OEM_ERR_ARG, "oem_run_history: run %u of %zu", run, h.n.size());
+    uint32_t n_rec = h.n[run] < h.stride ? h.n[run] : h.stride;
+    if (n_rec > capacity) n_rec = capacity;
+    if (n_rec) std::memcpy(out, h.h.data() + (size_t)run * h.stride, sizeof(double) * n_rec);
+    if (out_len) *out_len = h.n[run];
+    return OEM_OK;
+    OEM_API_END("oem_run_history")
 }
 
 extern "C" int oem_store_info(const oem_store *store, uint32_t key, uint64_t *value)
@@ -741,6 +764,11 @@ extern "C" int oem_store_info(const oem_store *store, uint32_t key, uint64_t *va
     case OEM_INFO_WEIGHT_DICT_ENTRIES: *value = store->tiled.present ? store->tiled.dict_n : 0u; return OEM_OK;
     case OEM_INFO_TILES: *value = store->tiled.present ? store->tiled.n_tiles : 0u; return OEM_OK;
     case OEM_INFO_REMOTE_ALIGNMENTS: *value = store->tiled.present ? store->tiled.n_remote : 0u; return OEM_OK;
+    case OEM_INFO_RUN_HISTORY_STORED: {
+        std::lock_guard<std::mutex> lk(const_cast<oem_store *>(store)->mu);
+        *value = store->history.valid ? store->history.stride : 0u;
+        return OEM_OK;
+    }
     default: return fail(OEM_ERR_ARG, "oem_store_info: unknown key %u", key);
     }
     OEM_API_END("oem_store_info")

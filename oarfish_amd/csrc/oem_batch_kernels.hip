@@ -890,6 +890,7 @@ __global__ __launch_bounds__(kRelB) void k_reldiff_b(double *__restrict__ theta,
             st[b].last_rel = rel_diff;
             st[b].n_passes += 1;
             uint32_t niter = st[b].niter;
+            if (st[b].history && niter < p.hist_cap) st[b].history[niter] = rel_diff; // OEM_OPT_RUN_HISTORY
             if (rel_diff < p.conv_thresh && niter > p.min_iter_gate) { // em.rs:212
                 st[b].converged = 1;
                 st[b].phase = kPhaseFinal;

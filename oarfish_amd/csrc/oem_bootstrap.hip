@@ -94,6 +94,7 @@ int run_bootstrap_chain(oem_store *s, int chain, BootJob *job)
     const uint64_t R = s->csr.n_reads;
     const double avg = (double)s->global_n_reads / (double)T; // em.rs:154: the store's read count also for a replicate
     EmParams p{T, job->max_iter, 50u /* do_bootstrap -> do_em, em.rs:289,:212 */, job->conv_thresh};
+    p.hist_cap = history_cap(s, job->max_iter); // (OEM_OPT_RUN_HISTORY: bb.d_history holds kBatch records of this length)
     const bool sharded = comm_exchanges(s->comm);
     int slot_rep[kBatch];
     OEM_HIP(hipMemsetAsync(bb.cnt, 0, sizeof(double) * T * kBatch, st));
@@ -131,6 +132,7 @@ int run_bootstrap_chain(oem_store *s, int chain, BootJob *job)
             OEM_TRY(launch_batch_reset_slot(s, bb, job->d_init, avg, (uint32_t)k));
             std::memset(&bb.h_state[k], 0, sizeof(BatchState));
             bb.h_state[k].phase = kPhaseRunning;
+            bb.h_state[k].history = p.hist_cap ? bb.d_history + (size_t)k * p.hist_cap : nullptr;
             OEM_HIP(hipMemcpyAsync(&bb.state[k], &bb.h_state[k], sizeof(BatchState), hipMemcpyHostToDevice, st));
             slot_rep[k] = (int)rep;
             return OEM_OK;
@@ -168,6 +170,14 @@ int run_bootstrap_chain(oem_store *s, int chain, BootJob *job)
             const uint32_t rep = (uint32_t)slot_rep[k];
             OEM_HIP(hipMemcpyAsync(bb.h_out + (size_t)k * T, bb.out + (size_t)k * T, sizeof(double) * T,
                                    hipMemcpyDeviceToHost, st));
+            if (s->history_opt) { // the slot's record goes to its replicate's row before the slot is handed the next one
+                RunHistory &h = s->history;
+                const uint32_t n = bb.h_state[k].niter + bb.h_state[k].converged;
+                h.n[rep] = n;
+                if (n && p.hist_cap)
+                    OEM_HIP(hipMemcpyAsync(h.h.data() + (size_t)rep * h.stride, bb.d_history + (size_t)k * p.hist_cap,
+                                           sizeof(double) * (n < p.hist_cap ? n : p.hist_cap), hipMemcpyDeviceToHost, st));
+            }
             OEM_HIP(hipStreamSynchronize(st));
             if (sharded) OEM_TRY(comm_check(s->comm, st));
             std::memcpy(job->out + (size_t)rep * T, bb.h_out + (size_t)k * T, sizeof(double) * T);
@@ -200,6 +210,9 @@ int run_bootstrap_rolling(oem_store *s, uint32_t n_boot, uint64_t seed, const ui
     n_chains = (int)knob("OEM_BOOT_CHAINS", n_chains) < n_chains ? (int)knob("OEM_BOOT_CHAINS", n_chains) : n_chains;
     if (n_chains < 1) n_chains = 1;
     for (int c = 0; c < n_chains; ++c) OEM_TRY(ensure_batch(s, c));
+    if (const uint32_t cap = history_cap(s, max_iter)) // (here, not in the chains: they run side by side)
+        for (int c = 0; c < n_chains; ++c)
+            OEM_TRY(ensure_history_buf(s, &s->batch[c].d_history, &s->batch[c].d_history_cap, (size_t)cap * kBatch));
     if (init) {
         OEM_HIP(hipMemcpyAsync(s->theta, init, sizeof(double) * T, hipMemcpyHostToDevice, s->stream));
         job.d_init = s->theta;
@@ -278,6 +291,7 @@ extern "C" int oem_bootstrap(oem_store *s, uint32_t n_boot, uint64_t seed, const
         return fail(OEM_ERR_ARG, "oem_bootstrap: replicas %u + [0, %u) exceed 2^32 - 1", s->bootstrap_first_replica, n_boot);
     OEM_TRY(ensure_device(s->device));
     OEM_TRY(ensure_row_w(s));
+    OEM_TRY(history_begin(s, n_boot, max_iter));
     const uint32_t T = s->csr.n_txps;
     const uint64_t R = s->csr.n_reads;
     // the replicates that run one per pass: all of them, or those the rolling batch hands back
@@ -307,9 +321,11 @@ extern "C" int oem_bootstrap(oem_store *s, uint32_t n_boot, uint64_t seed, const
         a.max_iter = max_iter;
         a.conv_thresh = conv_thresh;
         a.min_iter_gate = 50;              // do_bootstrap -> do_em (em.rs:289, :212)
+        a.history_run = s->history_opt ? (int64_t)b : -1;
         OEM_TRY(run_em_device(s, a, infos ? &infos[b] : nullptr));
         OEM_TRY(copy_counts_out(s, out + (uint64_t)b * T));
     }
+    history_end(s);
     return OEM_OK;
     OEM_API_END("oem_bootstrap")
 }

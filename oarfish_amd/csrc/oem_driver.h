@@ -146,7 +146,17 @@ struct RunArgs {
     uint32_t max_iter = 1000;
     double conv_thresh = 1e-3;
     uint32_t min_iter_gate = 50;
+    int64_t history_run = -1; // row of the store's RunHistory this run records into (history_begin); -1: no record
 };
+// OEM_OPT_RUN_HISTORY (oem_em_driver.hip).  history_begin opens the record of an oem_em_run / oem_bootstrap call
+// (n_runs rows of min(K, max_iter) entries; with the option off it only drops the previous call's), history_end marks it
+// readable.  ensure_history_buf (re)allocates a device record of n doubles; history_cap is this call's row length.
+uint32_t history_cap(const oem_store *s, uint32_t max_iter);
+int history_begin(oem_store *s, uint32_t n_runs, uint32_t max_iter);
+void history_end(oem_store *s);
+int ensure_history_buf(oem_store *s, double **buf, uint32_t *have, size_t n);
+// the run on s->d_state: its record's address into the (freshly cleared) state words; cap = 0: nothing to do
+int history_arm(oem_store *s, uint32_t cap);
 bool use_tiled(const oem_store *s, const RunArgs &a);
 int enqueue_pass(oem_store *s, const RunArgs &a, const EmState *state);
 int prepare_row_w(oem_store *s, const RunArgs &a);

@@ -41,6 +41,64 @@ int enqueue_iteration(oem_store *s, const RunArgs &a, const EmParams &p)
     return OEM_OK;
 }
 
+// ---- OEM_OPT_RUN_HISTORY: the rel_diff of every loop pass, written by the lane that takes the stopping decision ----
+uint32_t history_cap(const oem_store *s, uint32_t max_iter) { return s->history_opt < max_iter ? s->history_opt : max_iter; }
+
+int history_begin(oem_store *s, uint32_t n_runs, uint32_t max_iter)
+{
+    RunHistory &h = s->history;
+    h.valid = false;
+    h.h.clear();
+    h.n.clear();
+    h.stride = 0;
+    if (!s->history_opt) return OEM_OK;
+    h.stride = history_cap(s, max_iter);
+    h.h.assign((size_t)n_runs * h.stride, 0.0);
+    h.n.assign(n_runs, 0u);
+    return OEM_OK;
+}
+
+void history_end(oem_store *s) { s->history.valid = s->history_opt != 0; }
+
+int ensure_history_buf(oem_store *s, double **buf, uint32_t *have, size_t n)
+{
+    if (*buf && *have >= n) return OEM_OK;
+    if (*buf) {
+        OEM_HIP(hipStreamSynchronize(s->stream));
+        (void)hipFree(*buf);
+        s->hbm_bytes -= sizeof(double) * (size_t)*have;
+        *buf = nullptr;
+        *have = 0;
+    }
+    OEM_TRY(dev_alloc(buf, n, &s->hbm_bytes));
+    *have = (uint32_t)n;
+    return OEM_OK;
+}
+
+int history_arm(oem_store *s, uint32_t cap)
+{
+    if (!cap) return OEM_OK;
+    OEM_TRY(ensure_history_buf(s, &s->d_history, &s->d_history_cap, cap));
+    OEM_HIP(hipMemcpyAsync(&s->d_state->history, &s->d_history, sizeof(double *), hipMemcpyHostToDevice, s->stream));
+    return OEM_OK;
+}
+
+// after the loop: h_state is the final state of the run
+static int history_collect(oem_store *s, const RunArgs &a, uint32_t cap)
+{
+    if (a.history_run < 0 || !s->history_opt) return OEM_OK;
+    RunHistory &h = s->history;
+    const uint32_t n = s->h_state->niter + s->h_state->converged;
+    h.n[(size_t)a.history_run] = n;
+    const uint32_t n_rec = n < cap ? n : cap;
+    if (n_rec) {
+        OEM_HIP(hipMemcpyAsync(h.h.data() + (size_t)a.history_run * h.stride, s->d_history, sizeof(double) * n_rec,
+                               hipMemcpyDeviceToHost, s->stream));
+        OEM_HIP(hipStreamSynchronize(s->stream));
+    }
+    return OEM_OK;
+}
+
 // ---- the stopping rule one pass behind ------------------------------------------------------------------------
 // An iteration of do_em is a pass and then a sweep over the two count vectors (rel-diff, swap, clear: em.rs:194-207)
 // whose only product is one number and a decision.  On the device that sweep is a 6 us kernel between 0.15 ms passes
@@ -92,10 +150,12 @@ static int run_em_deferred(oem_store *s, const RunArgs &a, oem_run_info *info)
 {
     const uint32_t T = s->csr.n_txps;
     EmParams p{T, a.max_iter, a.min_iter_gate, a.conv_thresh};
+    p.hist_cap = a.history_run >= 0 ? history_cap(s, a.max_iter) : 0u;
     OEM_TRY(ensure_deferred(s));
     double *const bufs[3] = {s->theta, s->cnt, s->third};
     if (a.init) OEM_HIP(hipMemcpyAsync(bufs[0], a.init, sizeof(double) * T, hipMemcpyHostToDevice, s->stream));
     OEM_TRY(launch_deferred_init(s, bufs, (double)a.total_reads / (double)T, a.init == nullptr)); // em.rs:160-166
+    OEM_TRY(history_arm(s, p.hist_cap));
     std::memset(s->h_state, 0, sizeof(EmState));
     OEM_TRY(prepare_row_w(s, a));
     // iteration j is decided by launch j + 1: max_iter iterations take max_iter passes + the sweep that decides the last
@@ -155,7 +215,7 @@ static int run_em_deferred(oem_store *s, const RunArgs &a, oem_run_info *info)
         info->reserved = 0;
         info->rel_diff = s->h_state->last_rel;
     }
-    return OEM_OK;
+    return history_collect(s, a, p.hist_cap);
 }
 
 // em.rs:144-255 / :320-447 with the loop state on the device.  On return the
@@ -165,6 +225,7 @@ int run_em_device(oem_store *s, const RunArgs &a, oem_run_info *info)
     if (deferred_reldiff_ok(s, a)) return run_em_deferred(s, a, info);
     const uint32_t T = s->csr.n_txps;
     EmParams p{T, a.max_iter, a.min_iter_gate, a.conv_thresh};
+    p.hist_cap = a.history_run >= 0 ? history_cap(s, a.max_iter) : 0u;
 
     if (a.init) {
         OEM_HIP(hipMemcpyAsync(s->theta, a.init, sizeof(double) * T, hipMemcpyHostToDevice, s->stream));
@@ -174,6 +235,7 @@ int run_em_device(oem_store *s, const RunArgs &a, oem_run_info *info)
     }
     OEM_HIP(hipMemsetAsync(s->cnt, 0, sizeof(double) * T, s->stream));
     OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
+    OEM_TRY(history_arm(s, p.hist_cap));
     std::memset(s->h_state, 0, sizeof(EmState));
     OEM_TRY(prepare_row_w(s, a));
 
@@ -216,7 +278,7 @@ int run_em_device(oem_store *s, const RunArgs &a, oem_run_info *info)
         info->reserved = 0;
         info->rel_diff = s->h_state->last_rel;
     }
-    return OEM_OK;
+    return history_collect(s, a, p.hist_cap);
 }
 
 int copy_counts_out(oem_store *s, double *out)
@@ -284,8 +346,12 @@ extern "C" int oem_em_run(oem_store *s, const double *init_abundances, uint32_t 
     a.max_iter = max_iter;
     a.conv_thresh = conv_thresh;
     a.min_iter_gate = min_iter_gate;
+    OEM_TRY(history_begin(s, 1, max_iter));
+    a.history_run = s->history_opt ? 0 : -1;
     OEM_TRY(run_em_device(s, a, info));
-    return copy_counts_out(s, out_counts);
+    OEM_TRY(copy_counts_out(s, out_counts));
+    history_end(s);
+    return OEM_OK;
     OEM_API_END("oem_em_run")
 }
 

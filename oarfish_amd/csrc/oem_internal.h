@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <exception>
@@ -61,17 +62,24 @@ struct EmState {
     uint32_t done;               // loop has exited (break or niter == max_iter)
     uint32_t converged;          // exit was through `break`
     uint32_t blocks_arrived;     // last-block election counter of the rel-diff kernel
-    uint32_t pad[3];
+    uint32_t pad[1];             // [0]: the deferred rule's final buffer (deferred_decide)
+    double *history;             // OEM_OPT_RUN_HISTORY: history[k] = rel_diff of loop pass k; NULL = recording off.  In the
+                                 // state words, not a kernel argument: a replayed graph and launches enqueued far ahead
+                                 // read it where they read `niter`
 };
-static_assert(sizeof(EmState) == 48, "EmState layout");
+static_assert(sizeof(EmState) == 48 && offsetof(EmState, history) == 40, "EmState layout");
 
 // Parameters that do not change during a run.
 struct EmParams {
     uint32_t n_txps;
     uint32_t max_iter;
     uint32_t min_iter_gate;
+    uint32_t hist_cap; // entries of EmState / BatchState::history: min(OEM_OPT_RUN_HISTORY, max_iter); later passes are not
+                       // stored.  (In the word that was padding: the kernels' argument blocks keep their layout.)
     double conv_thresh;
+    EmParams(uint32_t t, uint32_t m, uint32_t g, double c) : n_txps(t), max_iter(m), min_iter_gate(g), hist_cap(0), conv_thresh(c) {}
 };
+static_assert(sizeof(EmParams) == 24, "EmParams layout");
 
 // ---------------------------------------------------------------------------
 // The alignment store as laid out in HBM.
@@ -162,9 +170,9 @@ struct BatchState {
     uint32_t blocks_arrived; // only [0] is used
     uint32_t phase;
     uint32_t reserved0;
-    uint32_t pad[2];
+    double *history; // as EmState::history, one record per slot (the per-cell batch leaves it NULL)
 };
-static_assert(sizeof(BatchState) == 48, "BatchState layout");
+static_assert(sizeof(BatchState) == 48 && offsetof(BatchState, history) == 40, "BatchState layout");
 
 // k_reldiff_b keeps its workgroups' maxima in kBatchRelSlots x kBatch words, not in the slots' four state words: ~200
 // workgroups x 4 atomics on ONE line ran at the rate of one hot address (0.08 G/s: 12 of the kernel's 16 us).
@@ -182,6 +190,17 @@ struct BatchBuffers {
     uint32_t *overflow = nullptr;
     BatchState *h_state = nullptr; // pinned
     double *h_out = nullptr;       // pinned [kBatch][T]
+    double *d_history = nullptr;   // [kBatch][d_history_cap]: the slots' rel_diff records (OEM_OPT_RUN_HISTORY), lazily
+    uint32_t d_history_cap = 0;
+};
+
+// What the last oem_em_run / oem_bootstrap on a store recorded (OEM_OPT_RUN_HISTORY): run r's first
+// min(n[r], stride) entries at h[r * stride].
+struct RunHistory {
+    bool valid = false;      // the last call recorded (oem_run_history: OEM_ERR_STATE otherwise)
+    uint32_t stride = 0;     // min(K, max_iter) of that call
+    std::vector<double> h;   // n_runs x stride
+    std::vector<uint32_t> n; // per run: niter + converged, which may exceed stride
 };
 
 // Per-cell batch: the cells are laid out as one store over a concatenated transcript
@@ -232,6 +251,10 @@ struct oem_store {
     oem::MultiBuffers multi;             // per-cell batches
     uint32_t bootstrap_first_replica = 0; // OEM_OPT_BOOTSTRAP_FIRST_REPLICA
     bool batch_bootstrap = true;         // OEM_OPT_BATCH_BOOTSTRAP (kChains chains of kBatch replicates per pass when applicable)
+    uint32_t history_opt = 0;            // OEM_OPT_RUN_HISTORY: K, the capacity in iterations; 0 = off
+    double *d_history = nullptr;         // d_history_cap f64: the record of the run on d_state, lazily
+    uint32_t d_history_cap = 0;
+    oem::RunHistory history;
     // multi-GPU
     oem::Comm *comm = nullptr;
     uint64_t global_n_reads = 0;

@@ -359,6 +359,7 @@ __global__ __launch_bounds__(kRB) void k_p2p_reldiff(double *__restrict__ prev, 
         state->last_rel = rel_diff;
         state->n_passes += 1;
         uint32_t niter = state->niter;
+        if (state->history && niter < p.hist_cap) state->history[niter] = rel_diff; // OEM_OPT_RUN_HISTORY (every rank: same value)
         if (rel_diff < p.conv_thresh && niter > p.min_iter_gate) { // em.rs:212 / :399
             state->done = 1;
             state->converged = 1;

@@ -401,6 +401,7 @@ __device__ __forceinline__ void deferred_decide(unsigned long long *slots, EmSta
     state->last_rel = rel;
     state->n_passes += 1;
     uint32_t niter = state->niter;
+    if (state->history && niter < p.hist_cap) state->history[niter] = rel; // OEM_OPT_RUN_HISTORY
     bool stop = false;
     if (rel < p.conv_thresh && niter > p.min_iter_gate) {          // em.rs:212 / :399
         state->converged = 1;

@@ -87,12 +87,14 @@ extern "C" int oem_time_em_iters(oem_store *s, uint32_t n_iters, float *out_ms)
     a.max_iter = n_iters;
     a.conv_thresh = -1.0; // rel_diff >= 0 is never < -1: no early exit (SURVEY.md 8a note 3)
     EmParams p{T, a.max_iter, 0xffffffffu, a.conv_thresh};
+    p.hist_cap = history_cap(s, n_iters); // OEM_OPT_RUN_HISTORY on: the timed iterations record as oem_em_run's do (nothing is kept)
     EventPair ev;
     OEM_TRY(ev.create());
     if (deferred_reldiff_ok(s, a)) { // as oem_em_run runs them: n_iters passes, the rule one pass behind, the last iteration decided by the sweep
         OEM_TRY(ensure_deferred(s));
         double *const bufs[3] = {s->theta, s->cnt, s->third};
         OEM_TRY(launch_deferred_init(s, bufs, (double)a.total_reads / (double)T, true));
+        OEM_TRY(history_arm(s, p.hist_cap));
         OEM_HIP(hipEventRecord(ev.e0, s->stream));
         for (uint64_t k = 0; k <= n_iters; ++k) OEM_TRY(enqueue_deferred_pass(s, a, p, bufs, k));
         OEM_HIP(hipEventRecord(ev.e1, s->stream));
@@ -101,6 +103,7 @@ extern "C" int oem_time_em_iters(oem_store *s, uint32_t n_iters, float *out_ms)
     OEM_TRY(launch_fill(s, s->theta, (double)a.total_reads / (double)T, T));
     OEM_HIP(hipMemsetAsync(s->cnt, 0, sizeof(double) * T, s->stream));
     OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
+    OEM_TRY(history_arm(s, p.hist_cap));
     OEM_HIP(hipEventRecord(ev.e0, s->stream));
     ChunkGraph cg; // launched the way oem_em_run launches: chunks of kGraphIters iterations from a graph
     if (graph_ok(s) && n_iters >= kGraphIters && n_iters % kGraphIters == 0)
@@ -108,6 +111,7 @@ extern "C" int oem_time_em_iters(oem_store *s, uint32_t n_iters, float *out_ms)
     if (cg.ready()) {
         OEM_HIP(hipGraphLaunch(cg.ge, s->stream)); // untimed: the first launch of an executable graph uploads it
         OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
+        OEM_TRY(history_arm(s, p.hist_cap));
         OEM_HIP(hipEventRecord(ev.e0, s->stream));
         for (uint32_t k = 0; k < n_iters; k += kGraphIters) OEM_HIP(hipGraphLaunch(cg.ge, s->stream));
     } else {

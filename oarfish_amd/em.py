@@ -14,7 +14,8 @@ bulk.rs:155-159 (``threads > 4``): it only changes the stopping gate.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+import logging
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -33,22 +34,61 @@ def _dev(em_info: EMInfo):
     return em_info.eq_map.device_store(len(em_info.txp_info), em_info.device)
 
 
-def em(em_info: EMInfo, _nthreads: int = 1) -> np.ndarray:
-    """em.rs:262-271: serial-path semantics (stop when rel_diff < thresh and niter > 50)."""
-    _require_no_kde(em_info)
-    counts, info = _dev(em_info).em_run(em_info.init_abundances, em_info.max_iter,
-                                        em_info.convergence_thresh, 50)
+logger = logging.getLogger("oarfish_amd.em")
+TRACE = 5  # the level that stands for the reference's `trace!` (below logging.DEBUG = 10)
+logging.addLevelName(TRACE, "TRACE")
+_LOGGED_ITERS = 1 << 20  # em / em_par record at most this many iterations (8 MB), whatever max_iter is
+
+
+def history_log_records(history) -> List[Tuple[int, str]]:
+    """The reference's convergence log of one run, from its rel_diff history (``DeviceStore.run_history``).
+
+    do_em and em_par log ``iteration N; rel diff R`` after the increment of ``niter`` (em.rs:218) whenever
+    ``N % 10 == 0``: ``info!`` when ``N % 100 == 0``, ``trace!`` otherwise (em.rs:219-233, :405-419).  ``N`` is
+    formatted with ``Locale::en`` (``1,000``) and ``R`` is the rel_diff of the pass that ended with ``niter == N``,
+    ``history[N - 1]``.  Returns ``[(level, message)]`` with ``logging.INFO`` or ``TRACE``, one per ``N % 10 == 0``
+    up to ``len(history)``, in iteration order.  The pass through which a converged run leaves (``break``,
+    em.rs:212-214) comes before the log line and is never logged: a caller passes ``history[:niter]``.
+
+    The float's text is Python's ``repr`` (shortest round-trip, exponent notation for small values); Rust's ``{}``
+    prints the same digits without an exponent (``0.00001`` for ``1e-05``).  That difference is left as it is.
+    """
+    out = []
+    for n in range(10, len(history) + 1, 10):
+        level = logging.INFO if n % 100 == 0 else TRACE
+        out.append((level, f"iteration {n:,}; rel diff {float(history[n - 1])!r}"))
+    return out
+
+
+def _em_logged(em_info: EMInfo, gate: int) -> np.ndarray:
+    """One EM run with the per-iteration record on (em.rs:270 / :326: ``do_log = true``), its lines handed to
+    ``logging`` at the reference's cadence; the store's option is put back to off afterwards."""
+    dev = _dev(em_info)
+    dev.set_option(_lib.OEM_OPT_RUN_HISTORY, max(1, min(int(em_info.max_iter), _LOGGED_ITERS)))
+    try:
+        counts, info = dev.em_run(em_info.init_abundances, em_info.max_iter, em_info.convergence_thresh, gate)
+        hist = dev.run_history(0)
+    finally:
+        dev.set_option(_lib.OEM_OPT_RUN_HISTORY, 0)
     em_info.last_run_info = info
+    em_info.last_run_history = hist
+    for level, msg in history_log_records(hist[:info.niter]):
+        logger.log(level, msg)
     return counts
+
+
+def em(em_info: EMInfo, _nthreads: int = 1) -> np.ndarray:
+    """em.rs:262-271: serial-path semantics (stop when rel_diff < thresh and niter > 50).  Logs the reference's
+    ``iteration N; rel diff R`` lines (``history_log_records``) to the logger ``oarfish_amd.em``; the run's whole
+    rel_diff history is left in ``em_info.last_run_history``."""
+    _require_no_kde(em_info)
+    return _em_logged(em_info, 50)
 
 
 def em_par(em_info: EMInfo, nthreads: int = 8) -> np.ndarray:
-    """em.rs:320-447: parallel-path semantics (stop when rel_diff < thresh and niter > 1)."""
+    """em.rs:320-447: parallel-path semantics (stop when rel_diff < thresh and niter > 1).  Logs as ``em`` does."""
     _require_no_kde(em_info)
-    counts, info = _dev(em_info).em_run(em_info.init_abundances, em_info.max_iter,
-                                        em_info.convergence_thresh, 1)
-    em_info.last_run_info = info
-    return counts
+    return _em_logged(em_info, 1)
 
 
 def bootstrap(em_info: EMInfo, num_boot: int, nthreads: int = 1, seed: int = 0,
@@ -58,6 +98,10 @@ def bootstrap(em_info: EMInfo, num_boot: int, nthreads: int = 1, seed: int = 0,
     The reference seeds each replicate from the OS (em.rs:274), so its stream
     is not reproducible; here ``seed`` keys a counter-based device RNG, and
     ``row_weights`` (num_boot x n_reads multiplicities) injects the resamples.
+
+    Silent, as the reference's replicates are (em.rs:289, ``do_log = false``); a caller who wants the
+    replicates' rel_diff histories sets ``OEM_OPT_RUN_HISTORY`` on ``eq_map.device_store(...)`` and reads
+    ``run_history(b)`` after the call.
     """
     _require_no_kde(em_info)
     out, _infos = _dev(em_info).bootstrap(num_boot, seed, row_weights, em_info.init_abundances,

@@ -187,6 +187,24 @@ class DeviceStore:
                                          out.ctypes.data, C.byref(ri)))
         return out, RunInfo(ri.niter, ri.n_passes, bool(ri.converged), ri.rel_diff)
 
+    def run_history(self, run: int = 0) -> np.ndarray:
+        """The rel_diff of every loop pass of run ``run`` of the last ``em_run`` (run 0) or ``bootstrap``
+        (replicate ``run``) on this store, recorded on the device under
+        ``set_option(_lib.OEM_OPT_RUN_HISTORY, K)`` (oem_run_history): entry ``k`` is the value the stopping rule
+        saw at ``niter == k``, so the reference's line ``iteration N; rel diff R`` is entry ``N - 1``, and the last
+        entry is ``RunInfo.rel_diff``.  At most ``min(K, max_iter)`` entries are stored; ``run_history_len`` gives
+        the run's full count.  Raises ``OemError`` (OEM_ERR_STATE) when the last call recorded nothing."""
+        n = min(self.run_history_len(run), self.info(_lib.OEM_INFO_RUN_HISTORY_STORED))  # what was stored
+        out = np.zeros(n, dtype=np.float64)
+        self._check(self._lib.oem_run_history(self.handle, run, out.ctypes.data if n else None, n, None))
+        return out
+
+    def run_history_len(self, run: int = 0) -> int:
+        """``niter + converged`` of that run: its loop passes, recorded or not."""
+        n = C.c_uint32(0)
+        self._check(self._lib.oem_run_history(self.handle, run, None, 0, C.byref(n)))
+        return int(n.value)
+
     def aux_counts(self):
         """aux_counts.rs:23-50 -> (unique_count u32[T], total_count u32[T])."""
         u = np.zeros(self.n_txps, dtype=np.uint32)
@@ -240,7 +258,7 @@ class DeviceStore:
         return float(ms.value)
 
     def info(self, key: int) -> int:
-        """oem_store_info: _lib.OEM_INFO_WEIGHT_DICT_ENTRIES / _TILES / _REMOTE_ALIGNMENTS."""
+        """oem_store_info: _lib.OEM_INFO_WEIGHT_DICT_ENTRIES / _TILES / _REMOTE_ALIGNMENTS / _RUN_HISTORY_STORED."""
         v = C.c_uint64(0)
         self._check(self._lib.oem_store_info(self.handle, key, C.byref(v)))
         return int(v.value)
@@ -423,3 +441,4 @@ class EMInfo:
     kde_model: Optional[object] = None   # hidden --use-kde: not supported (SURVEY.md 8a note 4)
     device: int = 0
     last_run_info: Optional[RunInfo] = field(default=None, compare=False)
+    last_run_history: Optional[np.ndarray] = field(default=None, compare=False)  # em / em_par: rel_diff per loop pass
