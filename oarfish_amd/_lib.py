@@ -220,6 +220,7 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_local_comm_create.argtypes = [i32, i32, vp]
         L.oem_test_reldiff_stress.argtypes = [u32, u32, u32, i32, vp]
         L.oem_debug_cells_last_paths.argtypes = [vp, vp, u32]
+        L.oem_debug_last_launch.argtypes = [vp, vp, u32]
         _testing = L
     return _testing
 

@@ -955,14 +955,17 @@ int launch_batch_pass(oem_store *s, const BatchBuffers &bb)
     }
 #endif
     const bool f64w = s->csr.w_is_f64;
-    const uint64_t wsz = f64w ? 8 : 4;
-    const uint64_t stream_bytes = (t.n_local + t.n_local / 8) * (wsz + 2) + t.n_remote * (wsz + (t.packed ? 4 : 6));
-    const bool nt = stream_bytes > (192ull << 20); // beyond the Infinity Cache: stream non-temporally
+    const bool nt = tile_streams_nt(t, f64w); // beyond the Infinity Cache: stream non-temporally (testing build: OEM_TILE_NT)
     const bool fused = !f64w && t.dict_fused && t.dict && t.r_wi && t.dict_n <= kDictE; // (no weight stream: see kFused)
+// (the record of the launch -- LaunchRecord -- is made of the template arguments, not of what chose them)
 #define OEM_LAUNCH_TILE_E4(NT, WT, W, RW, PK, ROWS, FUSED)                                                            \
-    hipLaunchKernelGGL((k_em_tile_e<NT, WT, PK, ROWS, FUSED>), dim3(t.n_tiles), dim3(kTileThreadsE), 0, bb.stream,      \
-                       t.tiles, t.codes, (const WT *)W, PK ? t.r_pk : t.r_tid, (const WT *)RW, t.r_row, t.sd,            \
-                       t.problem_size, bb.queue, bb.theta, bb.cnt, bb.state, bb.row_w, t.dict, t.r_wi)
+    do {                                                                                                              \
+        record_launch(&s->last_launch.batch, 1u | (uint32_t)(sizeof(WT) == 8) << 1 | (uint32_t)(FUSED) << 2 |         \
+                                                 (uint32_t)(PK) << 3 | (uint32_t)(NT) << 4);                          \
+        hipLaunchKernelGGL((k_em_tile_e<NT, WT, PK, ROWS, FUSED>), dim3(t.n_tiles), dim3(kTileThreadsE), 0, bb.stream,  \
+                           t.tiles, t.codes, (const WT *)W, PK ? t.r_pk : t.r_tid, (const WT *)RW, t.r_row, t.sd,        \
+                           t.problem_size, bb.queue, bb.theta, bb.cnt, bb.state, bb.row_w, t.dict, t.r_wi);              \
+    } while (0)
 #define OEM_LAUNCH_TILE_E3(NT, WT, W, RW, PK, ROWS)                                                                   \
     do {                                                                                                              \
         if (sizeof(WT) == 4 && fused) OEM_LAUNCH_TILE_E4(NT, WT, W, RW, PK, ROWS, (sizeof(WT) == 4));                  \

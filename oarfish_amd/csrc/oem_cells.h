@@ -65,6 +65,7 @@ struct CellsGroup {
     double *out_dense = nullptr;            // the results: the group's rows of the caller's n_cells x n_txps matrix,
     SparseBlock *blk = nullptr;             // ... or its sparse block
     oem_run_info *infos = nullptr;          // n_cells, or NULL
+    LaunchRecord *launch = nullptr;         // or NULL; a batched group leaves its store's record of the last launches here
 };
 
 // The group rule of the per-cell driver: may `cells` consecutive cells with `reads` reads and `gnnz` alignments be

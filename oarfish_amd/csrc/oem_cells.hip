@@ -323,6 +323,7 @@ int run_cells_batched(const CellsRun &run, const CellsGroup &g, bool *used)
                 (unsigned long long)s->tiled.n_remote);
     DevBuf<uint64_t> d_reads;
     int rc = run_batched_loop(run, g, s.get(), d_reads);
+    if (g.launch) *g.launch = s->last_launch;
     if (rc == OEM_OK) {
         tm.lap("cells: EM loop");
         rc = read_back_batched(run, g, s.get());
@@ -565,7 +566,7 @@ int run_cells(const char *who, CellsInput in, CellsRun run, double *dense, std::
     // threads for the same reason).
     if (blocks) blocks->assign(groups.size(), SparseBlock());
     std::vector<CellsGroupPath> paths(groups.size()); // (each group's slot is written by the worker that runs it)
-    for (size_t g = 0; g < groups.size(); ++g) paths[g] = CellsGroupPath{groups[g].first, groups[g].second, 0};
+    for (size_t g = 0; g < groups.size(); ++g) paths[g] = CellsGroupPath{groups[g].first, groups[g].second, 0, LaunchRecord()};
     CellsTiming timing;
     run.timing = &timing;
     std::atomic<size_t> next{0};
@@ -594,6 +595,7 @@ int run_cells(const char *who, CellsInput in, CellsRun run, double *dense, std::
                 sl.g.out_dense = dense ? dense + (uint64_t)groups[g].first * n_txps : nullptr;
                 sl.g.blk = blocks ? &(*blocks)[g] : nullptr;
                 sl.g.infos = infos ? infos + groups[g].first : nullptr;
+                sl.g.launch = &paths[g].launch;
                 rcs[wk] = run_cells_group(run, sl.g, &batched);
                 paths[g].batched = batched ? 1u : 0u;
                 if (rcs[wk] != OEM_OK) break;

@@ -238,6 +238,7 @@ void cells_last_timing(double *loop_ms, uint64_t *batched_passes);
 // ... and its groups: [c0, c1) and 1 when the group ran batched, 0 when cell by cell (oem_debug_cells_last_paths)
 struct CellsGroupPath {
     uint32_t c0, c1, batched;
+    LaunchRecord launch; // a batched group: its store's record when the loop had ended (oem_debug_last_launch)
 };
 const std::vector<CellsGroupPath> &cells_last_paths();
 

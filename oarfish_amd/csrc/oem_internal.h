@@ -229,6 +229,39 @@ struct MultiBuffers {
 };
 constexpr uint32_t kNoRank = 0xffffffffu;
 
+// Matrix bytes one pass over a tiled store streams (the slices with their codes, the remote records): what the
+// launchers hold against the cache sizes to choose how the streams are loaded.  One definition for the tile
+// kernel, its fold and the batched tile kernel, so that their thresholds are thresholds on the same number.
+inline uint64_t stream_bytes(const DeviceTiled &t, bool w_is_f64)
+{
+    const uint64_t wsz = w_is_f64 ? 8 : 4;
+    return (t.n_local + t.n_local / 8) * (wsz + 2) + t.n_remote * (wsz + (t.packed ? 4 : 6));
+}
+constexpr uint64_t kTileNtBytes = 192ull << 20;    // beyond the Infinity Cache: k_em_tile / k_em_tile_e stream non-temporally
+constexpr uint64_t kFoldCachedBytes = 96ull << 20; // beyond this k_remote_fold reads its queue through the caches (see kNTQ)
+// -1 = by the store's size (all the product does: knob() returns the default there), 0 / 1 = the test-only library's
+// OEM_TILE_NT / OEM_FOLD_NT
+inline bool tile_streams_nt(const DeviceTiled &t, bool w_is_f64)
+{
+    const long k = knob("OEM_TILE_NT", -1);
+    return k < 0 ? stream_bytes(t, w_is_f64) > kTileNtBytes : k != 0;
+}
+inline bool fold_reads_nt(const DeviceTiled &t, bool w_is_f64)
+{
+    const long k = knob("OEM_FOLD_NT", -1);
+    return k < 0 ? !(stream_bytes(t, w_is_f64) > kFoldCachedBytes) : k != 0;
+}
+
+// Which instantiation the launchers last launched on a store, written on the host at launch time (a word per kernel
+// family; relaxed atomic stores: the chains of a batched bootstrap launch from two threads).  0 = none since the record
+// was cleared.  Read by the test-only library's oem_debug_last_launch; the product never looks at it.
+struct LaunchRecord {
+    uint32_t tile = 0;  // k_em_tile: 1 | wide << 1 | f64 << 2 | coding << 3 (kWPlain ..) | packed << 5 | nt << 6 | per-cell batch << 7
+    uint32_t batch = 0; // k_em_tile_e: 1 | f64 << 1 | fused << 2 | packed << 3 | nt << 4
+    uint32_t fold = 0;  // k_remote_fold: 1 | ntq << 1 | n_groups << 8
+};
+inline void record_launch(uint32_t *word, uint32_t v) { __atomic_store_n(word, v, __ATOMIC_RELAXED); }
+
 struct Comm; // oem_comm.cpp
 
 } // namespace oem
@@ -255,6 +288,7 @@ struct oem_store {
     double *d_history = nullptr;         // d_history_cap f64: the record of the run on d_state, lazily
     uint32_t d_history_cap = 0;
     oem::RunHistory history;
+    oem::LaunchRecord last_launch;
     // multi-GPU
     oem::Comm *comm = nullptr;
     uint64_t global_n_reads = 0;

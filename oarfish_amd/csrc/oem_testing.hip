@@ -85,6 +85,33 @@ extern "C" int oem_debug_cells_last_paths(uint32_t *n_groups, uint32_t *out, uin
     return OEM_OK;
 }
 
+// Test hook: which instantiations the launchers last launched (LaunchRecord, oem_internal.h) -- on store `s` since the
+// previous call of this hook on it (the record is cleared: a step that launches nothing of a family reads as none), or,
+// with s == NULL, in the last batched group of this thread's last per-cell call, whose stores the caller never sees.
+// out[0..6]   k_em_tile:     launched, wide window, f64 weights, coding (0 plain, 1 bytes, 2 fused, 3 words), packed
+//                            records, non-temporal streams, per-cell batch
+// out[7..11]  k_em_tile_e:   launched, f64 weights, fused, packed records, non-temporal streams
+// out[12..14] k_remote_fold: launched, non-temporal queue (kNTQ), workgroups per bucket
+extern "C" int oem_debug_last_launch(oem_store *s, uint32_t *out, uint32_t n_out)
+{
+    if (!out || n_out < 15) return fail(OEM_ERR_ARG, "oem_debug_last_launch: bad argument");
+    LaunchRecord r;
+    if (s) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        r = s->last_launch;
+        s->last_launch = LaunchRecord();
+    } else {
+        for (const CellsGroupPath &p : cells_last_paths())
+            if (p.batched) r = p.launch;
+    }
+    const uint32_t v[15] = {r.tile & 1u, (r.tile >> 1) & 1u, (r.tile >> 2) & 1u, (r.tile >> 3) & 3u, (r.tile >> 5) & 1u,
+                            (r.tile >> 6) & 1u, (r.tile >> 7) & 1u,
+                            r.batch & 1u, (r.batch >> 1) & 1u, (r.batch >> 2) & 1u, (r.batch >> 3) & 1u, (r.batch >> 4) & 1u,
+                            r.fold & 1u, (r.fold >> 1) & 1u, r.fold >> 8};
+    std::memcpy(out, v, sizeof(v));
+    return OEM_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Stress test of k_reldiff_swap_clear's last-block election (oem_kernels.hip): the stopping
 // decision of every EM run (em.rs:194-218) is taken by the workgroup that draws the last ticket,

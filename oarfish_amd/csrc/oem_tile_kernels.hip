@@ -571,6 +571,9 @@ static void launch_tile(oem_store *s, const WT *w, const WT *r_w, const double *
     // (the deferred rel-diff: kRdBlocks more workgroups behind the tiles', a share of the transcripts each)
     const uint32_t n_rd = rd_prev ? kRdBlocks : 0u;
     const uint32_t n_txps = s->csr.n_txps, rd_chunk = n_rd ? (n_txps + n_rd - 1) / n_rd : 0u;
+    // (from the template arguments, not from what chose them: the record is of the instantiation)
+    record_launch(&s->last_launch.tile, 1u | (uint32_t)(t.win_cap > kWin) << 1 | (uint32_t)(sizeof(WT) == 8) << 2 | (uint32_t)kDict << 3 |
+                                            (uint32_t)kPacked << 5 | (uint32_t)kNT << 6 | (uint32_t)(problems != nullptr) << 7);
     if (t.win_cap > kWin)
         hipLaunchKernelGGL((k_em_tile<WT, 8, 6, 256, (sizeof(WT) == 4 ? OEM_WAVES_WIDE : 2), 1, kNT, kWinWideLds, kPacked, kDict, (sizeof(WT) == 4 ? OEM_SETS_WIDE : 2)>), dim3(grid + n_rd), dim3(256), 0, s->stream,
                            t.tiles, t.codes, w, r_a, r_w, t.r_row, t.sd, t.queue, theta, cnt, state,
@@ -604,10 +607,9 @@ static int launch_remote_fold(oem_store *s, hipStream_t stream, double *cnt, con
                               uint32_t rd_decide)
 {
     const DeviceTiled &t = s->tiled;
-    const uint64_t wsz = s->csr.w_is_f64 ? 8 : 4;
-    const uint64_t stream_bytes = (t.n_local + t.n_local / 8) * (wsz + 2) + t.n_remote * (wsz + (t.packed ? 4 : 6));
     const uint32_t n_groups = fold_groups(t);
-    if (stream_bytes > (96ull << 20)) // (2.5 M reads, 170 MB of streams: already better cached -- see kNTQ)
+    const bool ntq = fold_reads_nt(t, s->csr.w_is_f64); // (2.5 M reads, 170 MB of streams: already better cached -- see kNTQ)
+    if (!ntq)
         hipLaunchKernelGGL(k_remote_fold<false>, dim3(t.n_buckets * n_groups), dim3(kFoldThreads), 0,
                            stream, t.bucket_base, t.queue, t.q_dst, cnt, state, n_groups,
                            s->csr.n_txps, problems, problem_size, rd_slots, rd_state, rd_p, rd_decide);
@@ -615,6 +617,7 @@ static int launch_remote_fold(oem_store *s, hipStream_t stream, double *cnt, con
         hipLaunchKernelGGL(k_remote_fold<true>, dim3(t.n_buckets * n_groups), dim3(kFoldThreads), 0,
                            stream, t.bucket_base, t.queue, t.q_dst, cnt, state, n_groups,
                            s->csr.n_txps, problems, problem_size, rd_slots, rd_state, rd_p, rd_decide);
+    record_launch(&s->last_launch.fold, 1u | (uint32_t)ntq << 1 | n_groups << 8);
     OEM_HIP(hipGetLastError());
     return OEM_OK;
 }
@@ -639,11 +642,8 @@ int launch_em_pass_tiled(oem_store *s, const double *theta, double *cnt, const E
     }
 #endif
     const bool f64w = s->csr.w_is_f64;
-    // matrix bytes one pass streams; beyond the Infinity Cache they are loaded non-temporally
-    const uint64_t wsz = f64w ? 8 : 4;
-    const uint64_t stream_bytes = (t.n_local + t.n_local / 8) * (wsz + 2) + t.n_remote * (wsz + (t.packed ? 4 : 6));
-    const long nt_knob = knob("OEM_TILE_NT", -1); // testing build: 0 never, 1 always
-    const bool nt = nt_knob < 0 ? stream_bytes > (192ull << 20) : nt_knob != 0;
+    // matrix bytes one pass streams: beyond the Infinity Cache they are loaded non-temporally (testing build: OEM_TILE_NT)
+    const bool nt = tile_streams_nt(t, f64w);
 #define OEM_TILE(WT, NT, W, RW, DICT)                                                                       \
     do {                                                                                                   \
         if (t.packed) launch_tile<WT, NT, true, DICT>(s, W, RW, theta, cnt, state, row_w_perm, problems, rd);      \
