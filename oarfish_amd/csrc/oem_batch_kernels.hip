@@ -35,7 +35,7 @@
 // do in k_em_tile, with no extra LDS.
 //
 // Every slot keeps its own loop state on the device and walks the reference's state machine
-// by itself: RUNNING -(stopping rule em.rs:212 / max_iter em.rs:181)-> FINAL (theta < 1e-5
+// by itself: RUNNING -(the stopping rule, oem_stopping_rule.h: em.rs:212 / max_iter em.rs:181)-> FINAL (theta < 1e-5
 // read as 0, em.rs:238-242; one more pass, em.rs:245-252) -> FINISHED (counts parked in
 // `out`, slot ignored from then on, handed the next replicate by the host).
 #include <atomic>
@@ -836,7 +836,7 @@ __global__ __launch_bounds__(kRelB) void k_reldiff_b(double *__restrict__ theta,
                 if (is_final) {
                     out[(size_t)b * p.n_txps + j / kB] = cc[k];                           // em.rs:254
                 } else {
-                    if (pc[k] > OEM_MIN_READ_THRESH) rel = fmax(rel, (cc[k] - pc[k]) / pc[k]); // em.rs:195-199
+                    rel = rel_diff_term(rel, pc[k], cc[k]);
                     theta[j] = cc[k];                           // em.rs:204 (zeroing of small values: k_em_tile_e reads them as 0)
                 }
             }
@@ -858,10 +858,7 @@ __global__ __launch_bounds__(kRelB) void k_reldiff_b(double *__restrict__ theta,
             for (int i = 1; i < kRelB / 64; ++i) m = fmax(m, smax[i][b]);
             if (m > 0.0) atomicMax(&row[b], (unsigned long long)__double_as_longlong(m));
         }
-        // (ordering of the maxima against the ticket: see k_reldiff_swap_clear, oem_kernels.hip)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t ticket = atomicAdd(&st[0].blocks_arrived, 1u);
-        is_last = (ticket == gridDim.x - 1);
+        is_last = elect_last(&st[0].blocks_arrived);
     }
     __syncthreads();
     __shared__ unsigned long long slot_max[kB];
@@ -886,19 +883,7 @@ __global__ __launch_bounds__(kRelB) void k_reldiff_b(double *__restrict__ theta,
                 continue;
             }
             if (!((running >> b) & 1u)) continue;
-            const double rel_diff = __longlong_as_double((long long)slot_max[b]);
-            st[b].last_rel = rel_diff;
-            st[b].n_passes += 1;
-            uint32_t niter = st[b].niter;
-            if (st[b].history && niter < p.hist_cap) st[b].history[niter] = rel_diff; // OEM_OPT_RUN_HISTORY
-            if (rel_diff < p.conv_thresh && niter > p.min_iter_gate) { // em.rs:212
-                st[b].converged = 1;
-                st[b].phase = kPhaseFinal;
-            } else {
-                niter += 1;                                            // em.rs:218
-                st[b].niter = niter;
-                if (niter >= p.max_iter) st[b].phase = kPhaseFinal;    // em.rs:181
-            }
+            if (decide(&st[b], __longlong_as_double((long long)slot_max[b]), p)) st[b].phase = kPhaseFinal;
         }
         st[0].blocks_arrived = 0u;
     }

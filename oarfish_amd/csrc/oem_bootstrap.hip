@@ -181,13 +181,7 @@ int run_bootstrap_chain(oem_store *s, int chain, BootJob *job)
             OEM_HIP(hipStreamSynchronize(st));
             if (sharded) OEM_TRY(comm_check(s->comm, st));
             std::memcpy(job->out + (size_t)rep * T, bb.h_out + (size_t)k * T, sizeof(double) * T);
-            if (job->infos) {
-                job->infos[rep].niter = bb.h_state[k].niter;
-                job->infos[rep].n_passes = bb.h_state[k].n_passes;
-                job->infos[rep].converged = bb.h_state[k].converged;
-                job->infos[rep].reserved = 0;
-                job->infos[rep].rel_diff = bb.h_state[k].last_rel;
-            }
+            if (job->infos) job->infos[rep] = run_info_from(bb.h_state[k], 0); // (the slot has counted its final pass)
             slot_rep[k] = -1;
             OEM_TRY(load(k));
         }

@@ -293,13 +293,7 @@ int read_back_batched(const CellsRun &run, const CellsGroup &g, oem_store *s)
     if (hipMemcpy(hs.data(), mb.state, sizeof(BatchState) * g.n_cells, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(OEM_ERR_HIP, g.blk ? "oem_em_run_cells_sparse: state read-back failed" : "oem_em_run_cells: result read-back failed");
     if (g.infos)
-        for (uint32_t c = 0; c < g.n_cells; ++c) {
-            g.infos[c].niter = hs[c].niter;
-            g.infos[c].n_passes = hs[c].n_passes;
-            g.infos[c].converged = hs[c].converged;
-            g.infos[c].reserved = 0;
-            g.infos[c].rel_diff = hs[c].last_rel;
-        }
+        for (uint32_t c = 0; c < g.n_cells; ++c) g.infos[c] = run_info_from(hs[c], 0); // (a cell counts its own final pass)
     return OEM_OK;
 }
 

@@ -157,6 +157,23 @@ void history_end(oem_store *s);
 int ensure_history_buf(oem_store *s, double **buf, uint32_t *have, size_t n);
 // the run on s->d_state: its record's address into the (freshly cleared) state words; cap = 0: nothing to do
 int history_arm(oem_store *s, uint32_t cap);
+// What a finished loop state (EmState, BatchState) tells the caller; extra_passes: the final pass of em.rs:245-252 where
+// the state has not counted it.
+template <typename State>
+oem_run_info run_info_from(const State &h, uint32_t extra_passes)
+{
+    oem_run_info info;
+    info.niter = h.niter;
+    info.n_passes = h.n_passes + extra_passes;
+    info.converged = h.converged;
+    info.reserved = 0;
+    info.rel_diff = h.last_rel;
+    return info;
+}
+// The loop state of a run on s->d_state cleared (device and host copy) and its record armed; and the start of a classic
+// loop around it: theta filled with `avg` (em.rs:165) or left as uploaded (init_abundances), the counts cleared.
+int reset_loop_state(oem_store *s, uint32_t hist_cap);
+int begin_classic_loop(oem_store *s, const EmParams &p, double avg, bool fill);
 bool use_tiled(const oem_store *s, const RunArgs &a);
 int enqueue_pass(oem_store *s, const RunArgs &a, const EmState *state);
 int prepare_row_w(oem_store *s, const RunArgs &a);

@@ -208,14 +208,25 @@ static int run_em_deferred(oem_store *s, const RunArgs &a, oem_run_info *info)
     s->cnt = cnt;
     s->third = rest;
     OEM_TRY(enqueue_pass(s, a, nullptr));
-    if (info) {
-        info->niter = s->h_state->niter;
-        info->n_passes = s->h_state->n_passes + 1;
-        info->converged = s->h_state->converged;
-        info->reserved = 0;
-        info->rel_diff = s->h_state->last_rel;
-    }
+    if (info) *info = run_info_from(*s->h_state, 1);
     return history_collect(s, a, p.hist_cap);
+}
+
+int reset_loop_state(oem_store *s, uint32_t hist_cap)
+{
+    OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
+    OEM_TRY(history_arm(s, hist_cap));
+    std::memset(s->h_state, 0, sizeof(EmState));
+    return OEM_OK;
+}
+
+// What a classic loop starts from -- oem_em_run's and the one oem_time_em_iters times (the deferred loop's start
+// is one launch: launch_deferred_init)
+int begin_classic_loop(oem_store *s, const EmParams &p, double avg, bool fill)
+{
+    if (fill) OEM_TRY(launch_fill(s, s->theta, avg, p.n_txps));
+    OEM_HIP(hipMemsetAsync(s->cnt, 0, sizeof(double) * p.n_txps, s->stream));
+    return reset_loop_state(s, p.hist_cap);
 }
 
 // em.rs:144-255 / :320-447 with the loop state on the device.  On return the
@@ -227,16 +238,8 @@ int run_em_device(oem_store *s, const RunArgs &a, oem_run_info *info)
     EmParams p{T, a.max_iter, a.min_iter_gate, a.conv_thresh};
     p.hist_cap = a.history_run >= 0 ? history_cap(s, a.max_iter) : 0u;
 
-    if (a.init) {
-        OEM_HIP(hipMemcpyAsync(s->theta, a.init, sizeof(double) * T, hipMemcpyHostToDevice, s->stream));
-    } else {
-        const double avg = (double)a.total_reads / (double)T; // em.rs:165
-        OEM_TRY(launch_fill(s, s->theta, avg, T));
-    }
-    OEM_HIP(hipMemsetAsync(s->cnt, 0, sizeof(double) * T, s->stream));
-    OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
-    OEM_TRY(history_arm(s, p.hist_cap));
-    std::memset(s->h_state, 0, sizeof(EmState));
+    if (a.init) OEM_HIP(hipMemcpyAsync(s->theta, a.init, sizeof(double) * T, hipMemcpyHostToDevice, s->stream));
+    OEM_TRY(begin_classic_loop(s, p, (double)a.total_reads / (double)T, a.init == nullptr)); // em.rs:160-166
     OEM_TRY(prepare_row_w(s, a));
 
     // The stopping rule cannot fire before niter > gate, so the first look at
@@ -271,13 +274,7 @@ int run_em_device(oem_store *s, const RunArgs &a, oem_run_info *info)
     OEM_TRY(enqueue_pass(s, a, nullptr));                                                 // em.rs:245-252
     if (comm_exchanges(s->comm))
         OEM_TRY(comm_allreduce_sum_f64(s->comm, s->cnt, s->cnt, T, s->stream));
-    if (info) {
-        info->niter = s->h_state->niter;
-        info->n_passes = s->h_state->n_passes + 1;
-        info->converged = s->h_state->converged;
-        info->reserved = 0;
-        info->rel_diff = s->h_state->last_rel;
-    }
+    if (info) *info = run_info_from(*s->h_state, 1);
     return history_collect(s, a, p.hist_cap);
 }
 

@@ -13,6 +13,7 @@
 
 #include "../../include/oarfish_em.h"
 #include "oem_layout.h"
+#include "oem_stopping_rule.h"
 
 namespace oem {
 
@@ -69,17 +70,7 @@ struct EmState {
 };
 static_assert(sizeof(EmState) == 48 && offsetof(EmState, history) == 40, "EmState layout");
 
-// Parameters that do not change during a run.
-struct EmParams {
-    uint32_t n_txps;
-    uint32_t max_iter;
-    uint32_t min_iter_gate;
-    uint32_t hist_cap; // entries of EmState / BatchState::history: min(OEM_OPT_RUN_HISTORY, max_iter); later passes are not
-                       // stored.  (In the word that was padding: the kernels' argument blocks keep their layout.)
-    double conv_thresh;
-    EmParams(uint32_t t, uint32_t m, uint32_t g, double c) : n_txps(t), max_iter(m), min_iter_gate(g), hist_cap(0), conv_thresh(c) {}
-};
-static_assert(sizeof(EmParams) == 24, "EmParams layout");
+// (EmParams, the parameters that do not change during a run: oem_stopping_rule.h)
 
 // ---------------------------------------------------------------------------
 // The alignment store as laid out in HBM.

@@ -2,7 +2,8 @@
 //
 // Reference semantics (COMBINE-lab/oarfish v0.10.3):
 //   E/M pass                 src/em.rs:87-133 (m_step), :22-79 (m_step_par)
-//   rel-diff / swap / clear  src/em.rs:194-218 (do_em), :379-405 (em_par)
+//   rel-diff / swap / clear  src/em.rs:194-207 (do_em), :379-394 (em_par); the term, the last-workgroup election
+//                            and the stopping rule itself: oem_stopping_rule.h
 //   zero small + final pass  src/em.rs:238-252
 //   bootstrap resample       src/bootstrap.rs:7-16
 // Nothing here is a translation of that code: the reference walks an AoS store
@@ -60,7 +61,8 @@ __global__ __launch_bounds__(kBlock) void k_em_pass_csr(
 }
 
 // ---------------------------------------------------------------------------
-// rel-diff + swap + clear + stopping rule, fused (em.rs:194-218 / :379-405).
+// rel-diff + swap + clear + stopping rule, fused (em.rs:194-218 / :379-405): the sweep is this kernel's, the
+// workgroup maximum, the election of the last workgroup and the rule it applies are oem_stopping_rule.h's.
 // ---------------------------------------------------------------------------
 template <int kRB>
 __global__ __launch_bounds__(kRB) void k_reldiff_swap_clear(double *__restrict__ prev,
@@ -86,54 +88,17 @@ __global__ __launch_bounds__(kRB) void k_reldiff_swap_clear(double *__restrict__
         for (int k = 0; k < 4; ++k) {
             const uint32_t i = i0 + k * stride;
             if (i < p.n_txps) {
-                if (pc[k] > OEM_MIN_READ_THRESH) rel = fmax(rel, (cc[k] - pc[k]) / pc[k]); // em.rs:195-199 (signed)
+                rel = rel_diff_term(rel, pc[k], cc[k]);
                 prev[i] = cc[k];              // em.rs:204 swap: prev_counts <- this pass's counts
                 curr[i] = 0.0;                // em.rs:207 clear
             }
         }
     }
-    // wave64 max, then one atomic per wave
-    for (int off = 32; off > 0; off >>= 1) rel = fmax(rel, __shfl_xor(rel, off, 64));
-    __shared__ double smax[kRB / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) smax[wv] = rel;
-    __syncthreads();
-    __shared__ bool is_last;
-    if (threadIdx.x == 0) {
-        double m = smax[0];
-        for (int i = 1; i < kRB / 64; ++i) m = fmax(m, smax[i]);
-        // non-negative doubles order like their bit patterns.  Both this and the ticket below are
-        // device-scope read-modify-write atomics, performed at the one point of coherence of their
-        // line (memory side), and on gfx9 a no-return atomic is counted by vmcnt until it has been
-        // performed there: draining vmcnt before taking the ticket means the maximum is in place
-        // before the ticket can be observed, so the workgroup that draws the last ticket reads (with
-        // an agent-scope atomic load) a maximum that contains every workgroup's.  A release fence
-        // here would add an L2 write-back (buffer_wbl2) that publishes nothing this decision needs
-        // (~3.5 us per workgroup tail, measured in round 1).  The election is hammered in isolation
-        // by oem_test_reldiff_stress (test-only library): > 10^5 launches over 1..64 workgroups,
-        // planted maxima, the decision workgroup's view compared bit for bit.
-        if (m > 0.0) atomicMax(&state->rel_bits, (unsigned long long)__double_as_longlong(m));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t ticket = atomicAdd(&state->blocks_arrived, 1u);
-        is_last = (ticket == gridDim.x - 1);
-    }
-    __syncthreads();
+    const bool is_last = workgroup_max_and_elect<kRB>(rel, &state->rel_bits, &state->blocks_arrived);
     if (is_last && threadIdx.x == 0) {
         const unsigned long long bits =
             __hip_atomic_load(&state->rel_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double rel_diff = __longlong_as_double((long long)bits);
-        state->last_rel = rel_diff;
-        state->n_passes += 1;
-        uint32_t niter = state->niter;
-        if (state->history && niter < p.hist_cap) state->history[niter] = rel_diff; // OEM_OPT_RUN_HISTORY
-        if (rel_diff < p.conv_thresh && niter > p.min_iter_gate) { // em.rs:212 / :399
-            state->done = 1;
-            state->converged = 1;
-        } else {
-            niter += 1;                                            // em.rs:218
-            state->niter = niter;
-            if (niter >= p.max_iter) state->done = 1;              // em.rs:181 loop condition
-        }
+        if (decide(state, __longlong_as_double((long long)bits), p)) state->done = 1;
         state->rel_bits = 0ull;                                    // em.rs:234
         state->blocks_arrived = 0u;
     }

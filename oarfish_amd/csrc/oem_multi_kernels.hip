@@ -5,7 +5,7 @@
 // resident store whose transcript space is the concatenation of the cells' (cell p owns
 // transcripts [p*T, (p+1)*T)); the tile / fold kernels are the ordinary ones, and each
 // cell walks the reference's loop on the device with its own state:
-//   RUNNING -(em.rs:212 stopping rule / em.rs:181 max_iter)-> FINAL (em.rs:238-242 zero
+//   RUNNING -(em.rs:212 stopping rule / em.rs:181 max_iter: oem_stopping_rule.h)-> FINAL (em.rs:238-242 zero
 //   small, em.rs:245-252 one more pass) -> FINISHED (counts parked in `out`).
 #include "oem_internal.h"
 #include "oem_lane_runs.h"
@@ -53,12 +53,12 @@ __global__ __launch_bounds__(kMT) void k_multi_reldiff(double *__restrict__ thet
             out[k] = cc;                                      // em.rs:254
         } else {
             const double pc = theta[k];
-            if (pc > OEM_MIN_READ_THRESH) rel = fmax(rel, (cc - pc) / pc); // em.rs:195-199
+            rel = rel_diff_term(rel, pc, cc);
             theta[k] = cc;                                    // em.rs:204
         }
     }
     if (phase == kPhaseFinal) return;
-    for (int off = 32; off > 0; off >>= 1) rel = fmax(rel, __shfl_xor(rel, off, 64));
+    rel = wave_max(rel);
     if ((threadIdx.x & 63) == 0 && rel > 0.0)
         atomicMax(&st[p].rel_bits, (unsigned long long)__double_as_longlong(rel));
 }
@@ -142,13 +142,11 @@ __global__ __launch_bounds__(kFT) void k_multi_fold_reldiff(const uint32_t *__re
         } else {
             const double pc = pv[k];
             theta[t] = cc;                                        // em.rs:204
-            if (pc > OEM_MIN_READ_THRESH) {                       // em.rs:195-199 (signed, floored at 0 by the max)
-                const double rel = (cc - pc) / pc;
-                if (rel > 0.0) {
-                    const unsigned long long bits = (unsigned long long)__double_as_longlong(rel);
-                    if (small) atomicMax(&cmax[p - p0], bits);
-                    else atomicMax(&st[p].rel_bits, bits);
-                }
+            const double rel = rel_diff_term(0.0, pc, cc);        // (floored at 0 as the loop's maximum is)
+            if (rel > 0.0) {
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(rel);
+                if (small) atomicMax(&cmax[p - p0], bits);
+                else atomicMax(&st[p].rel_bits, bits);
             }
         }
     }
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(kFT) void k_multi_fold_reldiff(const uint32_t *__re
     if (threadIdx.x < n_cells && cmax[threadIdx.x] != 0ull) atomicMax(&st[p0 + threadIdx.x].rel_bits, cmax[threadIdx.x]);
 }
 
-// one thread per cell: the stopping rule (em.rs:212-218, :181)
+// one thread per cell: the stopping rule (oem_stopping_rule.h) on a register copy of the cell's state
 __global__ __launch_bounds__(kMT) void k_multi_decide(BatchState *st, uint32_t n_problems, EmParams p,
                                                       uint32_t *n_unfinished)
 {
@@ -170,16 +168,8 @@ __global__ __launch_bounds__(kMT) void k_multi_decide(BatchState *st, uint32_t n
         s.phase = kPhaseFinished;
         atomicSub(n_unfinished, 1u);
     } else {
-        const double rel_diff = __longlong_as_double((long long)s.rel_bits);
-        s.last_rel = rel_diff;
-        s.n_passes += 1;
-        if (rel_diff < p.conv_thresh && s.niter > p.min_iter_gate) {
-            s.converged = 1;
-            s.phase = kPhaseFinal;
-        } else {
-            s.niter += 1;
-            if (s.niter >= p.max_iter) s.phase = kPhaseFinal;
-        }
+        // (the per-cell batch records no history: `history` is NULL here)
+        if (decide(&s, __longlong_as_double((long long)s.rel_bits), p)) s.phase = kPhaseFinal;
         s.rel_bits = 0ull;
     }
     st[i] = s;

@@ -13,7 +13,8 @@
 //                     peer's flag block (a peer spins on its OWN memory)
 //     k_p2p_reduce    waits for the flags, recv[i] = sum over ranks r = 0..N-1 of slot_r[parity][i]
 //     k_p2p_reldiff   the same wait and sum fused into rel-diff / swap / clear / stopping rule
-//                     (em.rs:194-218): the reduced vector is never written and read back
+//                     (em.rs:194-218): the reduced vector is never written and read back; the term, the
+//                     election and the rule are the ones every loop shares (oem_stopping_rule.h)
 //   two-phase (N >= 3 and vectors of half a megabyte or more): one-shot pulls (N - 1) whole vectors through every rank's links -- 11 MB per rank and
 //     pass at N = 8 -- where a reduce-scatter + all-gather pulls 2 (N - 1) / N of ONE vector (2.8 MB), spread
 //     over the same N - 1 links: rank r sums slice r of all partials in rank order into its `red` buffer
@@ -333,41 +334,16 @@ __global__ __launch_bounds__(kRB) void k_p2p_reldiff(double *__restrict__ prev, 
 #pragma unroll
         for (int k = 0; k < kP2PBatch; ++k)
             if (i0 + k * stride < n) {
-                if (pc[k] > OEM_MIN_READ_THRESH) rel = fmax(rel, (cc[k] - pc[k]) / pc[k]); // em.rs:195-199
+                rel = rel_diff_term(rel, pc[k], cc[k]);
                 prev[idx[k]] = cc[k];                                                    // em.rs:204
                 curr[idx[k]] = 0.0;                                                      // em.rs:207
             }
     }
-    for (int off = 32; off > 0; off >>= 1) rel = fmax(rel, __shfl_xor(rel, off, 64));
-    __shared__ double smax[kRB / 64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) smax[wv] = rel;
-    __syncthreads();
-    __shared__ bool is_last;
-    if (threadIdx.x == 0) {
-        double m = smax[0];
-        for (int i = 1; i < kRB / 64; ++i) m = fmax(m, smax[i]);
-        if (m > 0.0) atomicMax(&state->rel_bits, (unsigned long long)__double_as_longlong(m));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (ordering argument: k_reldiff_swap_clear)
-        const uint32_t ticket = atomicAdd(&state->blocks_arrived, 1u);
-        is_last = (ticket == gridDim.x - 1);
-    }
-    __syncthreads();
+    const bool is_last = workgroup_max_and_elect<kRB>(rel, &state->rel_bits, &state->blocks_arrived);
     if (is_last && threadIdx.x == 0) {
         const unsigned long long bits = __hip_atomic_load(&state->rel_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double rel_diff = __longlong_as_double((long long)bits);
-        state->last_rel = rel_diff;
-        state->n_passes += 1;
-        uint32_t niter = state->niter;
-        if (state->history && niter < p.hist_cap) state->history[niter] = rel_diff; // OEM_OPT_RUN_HISTORY (every rank: same value)
-        if (rel_diff < p.conv_thresh && niter > p.min_iter_gate) { // em.rs:212 / :399
-            state->done = 1;
-            state->converged = 1;
-        } else {
-            niter += 1;                                            // em.rs:218
-            state->niter = niter;
-            if (niter >= p.max_iter) state->done = 1;              // em.rs:181
-        }
+        // (every rank decides on the same value, and records it: OEM_OPT_RUN_HISTORY)
+        if (decide(state, __longlong_as_double((long long)bits), p)) state->done = 1;
         // a wait that gave up: the sums of this run are lost -- end it here instead of iterating on stale slots
         if (__hip_atomic_load(&ctl->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) state->done = 1;
         state->rel_bits = 0ull;

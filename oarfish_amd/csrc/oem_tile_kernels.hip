@@ -9,6 +9,8 @@
 //                written to the bucket-major queue, window flushed with
 //                cache-line-coalesced global atomics.
 // k_remote_fold  streams each bucket's queue range into an LDS window, flushes.
+// The rel-diff that rides on a pass (k_em_tile's last workgroups, deferred_decide, k_deferred_sweep) takes its term,
+// its reduction and the stopping rule from oem_stopping_rule.h.
 //
 // HBM-bound by design (no MFMA: this is sparse gather/scatter).  Algorithmic
 // bytes per pass are SURVEY.md section 8d's nnz*(4+4) + (R+1)*4 + 2*T*8.
@@ -124,12 +126,12 @@ __global__ __launch_bounds__(kTileThreads, kMinWaves) void k_em_tile(
             for (int k = 0; k < 4; ++k) {
                 const uint32_t i = ib + k * kTileThreads;
                 if (i < i1) {
-                    if (pv[k] > OEM_MIN_READ_THRESH) rel = fmax(rel, (cv[k] - pv[k]) / pv[k]);
+                    rel = rel_diff_term(rel, pv[k], cv[k]);
                     rd_prev[i] = 0.0;
                 }
             }
         }
-        for (int off = 32; off > 0; off >>= 1) rel = fmax(rel, __shfl_xor(rel, off, 64));
+        rel = wave_max(rel);
         if ((threadIdx.x & 63u) == 0 && rel > 0.0) // (non-negative doubles order like their bit patterns; no return value: nothing waits)
             atomicMax(&rd_slots[(rb * (kTileThreads / 64) + (threadIdx.x >> 6)) & (kRelSlots - 1u)], (unsigned long long)__double_as_longlong(rel));
         return;
@@ -387,7 +389,7 @@ __global__ __launch_bounds__(kTileThreads, kMinWaves) void k_em_tile(
     OEM_PROBE(11); // queue stores and window flush issued
 }
 
-// The stopping rule of the deferred rel-diff (em.rs:212-218, :181), by one wavefront: the maximum over the slots the
+// The stopping rule (oem_stopping_rule.h) on the deferred rel-diff, by one wavefront: the maximum over the slots the
 // tile workgroups of this pass filled, the slots reset for the next pass.
 __device__ __forceinline__ void deferred_decide(unsigned long long *slots, EmState *state, EmParams p, uint32_t decide)
 {
@@ -395,23 +397,9 @@ __device__ __forceinline__ void deferred_decide(unsigned long long *slots, EmSta
     static_assert(kRelSlots == 64, "one slot per lane");
     unsigned long long bits = __hip_atomic_load(&slots[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     slots[lane] = 0ull;                                            // em.rs:234
-    double rel = __longlong_as_double((long long)bits);
-    for (int off = 32; off > 0; off >>= 1) rel = fmax(rel, __shfl_xor(rel, off, 64));
+    const double rel = wave_max(__longlong_as_double((long long)bits));
     if (lane != 0) return;
-    state->last_rel = rel;
-    state->n_passes += 1;
-    uint32_t niter = state->niter;
-    if (state->history && niter < p.hist_cap) state->history[niter] = rel; // OEM_OPT_RUN_HISTORY
-    bool stop = false;
-    if (rel < p.conv_thresh && niter > p.min_iter_gate) {          // em.rs:212 / :399
-        state->converged = 1;
-        stop = true;
-    } else {
-        niter += 1;                                                // em.rs:218
-        state->niter = niter;
-        stop = niter >= p.max_iter;                                // em.rs:181 loop condition
-    }
-    if (stop) {
+    if (oem::decide(state, rel, p)) { // (qualified: the argument `decide` names the final buffer)
         state->pad[0] = decide; // 1 + the buffer that holds the final abundances (theta of the pass that decides)
         state->done = 1;
     }
@@ -428,8 +416,8 @@ __global__ __launch_bounds__(64) void k_deferred_decide(unsigned long long *slot
 // before the break of :212); only `converged`, `niter` and `rel_diff` of oem_run_info hang on that last comparison.
 // So instead of a speculative pass whose counts are dropped (0.146 ms at C3, 27 us at C2) this sweep takes the rel-diff
 // of theta_{N-1} (`prev`) against theta_N (`cur`) -- the tile workgroups' share of the work in k_em_tile -- zeroes
-// `prev` (the accumulator of the final pass, em.rs:245) and its last workgroup applies the rule.  Election as in
-// k_reldiff_swap_clear (oem_kernels.hip): the maxima are device-scope atomics drained before the ticket is taken.
+// `prev` (the accumulator of the final pass, em.rs:245) and its last workgroup applies the rule (elected as every
+// sweep's is: oem_stopping_rule.h).
 constexpr int kSweepThreads = 256;
 __global__ __launch_bounds__(kSweepThreads) void k_deferred_sweep(double *__restrict__ prev, const double *__restrict__ cur,
                                                                   unsigned long long *slots, EmState *state, EmParams p,
@@ -450,24 +438,12 @@ __global__ __launch_bounds__(kSweepThreads) void k_deferred_sweep(double *__rest
         for (int k = 0; k < 4; ++k) {
             const uint32_t i = i0 + k * stride;
             if (i < p.n_txps) {
-                if (pc[k] > OEM_MIN_READ_THRESH) rel = fmax(rel, (cc[k] - pc[k]) / pc[k]); // em.rs:195-199 (signed)
+                rel = rel_diff_term(rel, pc[k], cc[k]);
                 prev[i] = 0.0;                                                             // em.rs:207
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) rel = fmax(rel, __shfl_xor(rel, off, 64));
-    __shared__ double smax[kSweepThreads / 64];
-    __shared__ bool is_last;
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = rel;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = smax[0];
-        for (int i = 1; i < kSweepThreads / 64; ++i) m = fmax(m, smax[i]);
-        if (m > 0.0) atomicMax(&slots[blockIdx.x & (kRelSlots - 1u)], (unsigned long long)__double_as_longlong(m));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        is_last = atomicAdd(&state->blocks_arrived, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
+    const bool is_last = workgroup_max_and_elect<kSweepThreads>(rel, &slots[blockIdx.x & (kRelSlots - 1u)], &state->blocks_arrived);
     if (is_last && threadIdx.x < 64) {
         if (threadIdx.x == 0) state->blocks_arrived = 0u;
         deferred_decide(slots, state, p, decide);

@@ -100,18 +100,14 @@ extern "C" int oem_time_em_iters(oem_store *s, uint32_t n_iters, float *out_ms)
         OEM_HIP(hipEventRecord(ev.e1, s->stream));
         return ev.elapsed(out_ms);
     }
-    OEM_TRY(launch_fill(s, s->theta, (double)a.total_reads / (double)T, T));
-    OEM_HIP(hipMemsetAsync(s->cnt, 0, sizeof(double) * T, s->stream));
-    OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
-    OEM_TRY(history_arm(s, p.hist_cap));
+    OEM_TRY(begin_classic_loop(s, p, (double)a.total_reads / (double)T, true)); // what oem_em_run's loop starts from
     OEM_HIP(hipEventRecord(ev.e0, s->stream));
     ChunkGraph cg; // launched the way oem_em_run launches: chunks of kGraphIters iterations from a graph
     if (graph_ok(s) && n_iters >= kGraphIters && n_iters % kGraphIters == 0)
         OEM_TRY(capture_chunk(s->stream, kGraphIters, [&]() { return enqueue_iteration(s, a, p); }, &cg));
     if (cg.ready()) {
         OEM_HIP(hipGraphLaunch(cg.ge, s->stream)); // untimed: the first launch of an executable graph uploads it
-        OEM_HIP(hipMemsetAsync(s->d_state, 0, sizeof(EmState), s->stream));
-        OEM_TRY(history_arm(s, p.hist_cap));
+        OEM_TRY(reset_loop_state(s, p.hist_cap));
         OEM_HIP(hipEventRecord(ev.e0, s->stream));
         for (uint32_t k = 0; k < n_iters; k += kGraphIters) OEM_HIP(hipGraphLaunch(cg.ge, s->stream));
     } else {
