@@ -40,7 +40,8 @@ extern "C" {
  *    (oem_em_run_cells_sparse, oem_cells_result_dims / _copy / _destroy), the per-cell coverage model
  *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse), the bulk coverage model
  *    and the store on its column in one call (oem_store_create_coverage, oem_builder_store_create_coverage), the
- *    per-cell session (oem_cells_stream_*), the per-iteration rel_diff record (OEM_OPT_RUN_HISTORY, oem_run_history). */
+ *    per-cell session (oem_cells_stream_*), the per-iteration rel_diff record (OEM_OPT_RUN_HISTORY, oem_run_history),
+ *    the `.prob` body as text formatted on the device (oem_assignment_text, oem_text_result_dims / _copy / _destroy). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -61,6 +62,7 @@ typedef enum {
 typedef struct oem_store oem_store; /* InMemoryAlignmentStore resident on one GPU (one row shard) */
 typedef struct oem_comm oem_comm;   /* RCCL communicator over the row shards of one node */
 typedef struct oem_cells_result oem_cells_result; /* sparse per-cell results, host-resident, immutable once returned */
+typedef struct oem_text_result oem_text_result;   /* host-resident, immutable once returned */
 
 /* What do_em / em_par leave behind besides the counts. */
 typedef struct {
@@ -333,6 +335,31 @@ int oem_aux_counts(oem_store *store, uint32_t *out_unique, uint32_t *out_total);
  * alignment order: the probability the reference prints, or -1 for an alignment it omits. */
 int oem_assignment_probs(oem_store *store, const double *counts, double display_thresh,
                          double *out_prob);
+
+/* The body of the `.prob` file (write_function.rs:283-332) for every read of the store, in the caller's read and
+ * alignment order, as the bytes the reference writes: the E-step above, then per read the line
+ *     name '\t' k '\t' id_1 '\t' .. id_k '\t' p_1 '\t' .. p_k '\n'       (a read that keeps nothing: name "\t0\t\t\n")
+ * formatted on the device.  k and the ids are plain decimal; each p is Rust's `{:.d}` with d =
+ * prob_display_decimals(display_thresh) (:218-224: ceil(-log10(thresh)) in 3 .. 9; 9 for a threshold that is not
+ * positive and finite): the exact binary value correctly rounded, ties to even, as glibc's "%.*f" prints it; 0/0
+ * (display_thresh <= 0 and every kept nprob zero) prints as `NaN`.  The file's header lines (the counts and the
+ * transcript names) are the caller's.
+ * names / name_off: the read names as one byte blob and n_reads + 1 offsets (name r = bytes
+ * [name_off[r], name_off[r+1])); trailing NUL bytes of a name are dropped (trim_end_matches('\0'), :294).
+ * names == NULL (then name_off == NULL too): every name is empty (the line starts with the tab).  counts: n_txps f64.
+ * Argument errors (a NULL store / counts / out, names without name_off or the reverse, name_off[0] != 0, name_off
+ * decreasing) are reported before any device use; *out is NULL after any failure.  Like oem_assignment_probs the call
+ * overwrites the store's theta scratch (no other state), works on every kind of store (f32 / f64 weights, any
+ * weight_coding, wide row pointers, oem_store_create_coverage), and a row shard produces the lines of its own reads.
+ * The text leaves the device in chunks of consecutive reads (256 MiB of text each, double-buffered), so the device
+ * never holds the whole file.  The result is independent of the store; free it with oem_text_result_destroy. */
+int oem_assignment_text(oem_store *store, const double *counts, double display_thresh,
+                        const uint8_t *names, const uint64_t *name_off, oem_text_result **out);
+/* n_bytes of text, n_lines (= the store's reads), n_kept (= the sum of the lines' k); each may be NULL */
+int oem_text_result_dims(const oem_text_result *r, uint64_t *n_bytes, uint64_t *n_lines, uint64_t *n_kept);
+/* text: n_bytes; line_off (optional): n_lines + 1 byte offsets; kept (optional): n_lines u32, the k of each line */
+int oem_text_result_copy(const oem_text_result *r, uint8_t *text, uint64_t *line_off, uint32_t *kept);
+void oem_text_result_destroy(oem_text_result *r); /* NULL: no-op */
 
 /* --------------------------------------------------------------------- */
 /* bootstrap                                                              */

@@ -152,6 +152,40 @@ inline std::vector<double> run_history(const oem_store *store, uint32_t run = 0,
     return h;
 }
 
+// write_function.rs:283-332: the body lines of the `.prob` file for every read of the store, formatted on the device
+// (oem_assignment_text).  `names` holds one name per read (empty: every name is empty); *line_off / *kept (optional)
+// receive the n_reads + 1 byte offsets of the lines and each line's k.
+inline std::string assignment_text(oem_store *store, const std::vector<double> &counts, double display_thresh,
+                                   const std::vector<std::string> &names = {}, std::vector<uint64_t> *line_off = nullptr,
+                                   std::vector<uint32_t> *kept = nullptr)
+{
+    std::string blob;
+    std::vector<uint64_t> off;
+    if (!names.empty()) {
+        off.reserve(names.size() + 1);
+        off.push_back(0);
+        for (const std::string &n : names) {
+            blob += n;
+            off.push_back(blob.size());
+        }
+    }
+    oem_text_result *r = nullptr;
+    check(oem_assignment_text(store, counts.data(), display_thresh,
+                              names.empty() ? nullptr : reinterpret_cast<const uint8_t *>(blob.data()),
+                              names.empty() ? nullptr : off.data(), &r),
+          "oem_assignment_text");
+    std::unique_ptr<oem_text_result, void (*)(oem_text_result *)> guard(r, oem_text_result_destroy);
+    uint64_t n_bytes = 0, n_lines = 0;
+    check(oem_text_result_dims(r, &n_bytes, &n_lines, nullptr), "oem_text_result_dims");
+    std::string text(n_bytes, '\0');
+    if (line_off) line_off->resize(n_lines + 1);
+    if (kept) kept->resize(n_lines);
+    check(oem_text_result_copy(r, reinterpret_cast<uint8_t *>(&text[0]), line_off ? line_off->data() : nullptr,
+                               kept ? kept->data() : nullptr),
+          "oem_text_result_copy");
+    return text;
+}
+
 namespace em {
 
 namespace detail {

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "oem_coverage_probs_cells_device",
     "oem_builder_store_create", "oem_store_create_coverage", "oem_builder_store_create_coverage",
     "oem_m_step", "oem_em_run", "oem_run_history", "oem_aux_counts", "oem_assignment_probs",
+    "oem_assignment_text", "oem_text_result_dims", "oem_text_result_copy", "oem_text_result_destroy",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
@@ -163,6 +164,11 @@ def _load(path: str) -> C.CDLL:
     L.oem_run_history.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
     L.oem_aux_counts.argtypes = [vp, vp, vp]
     L.oem_assignment_probs.argtypes = [vp, vp, f64, vp]
+    L.oem_assignment_text.argtypes = [vp, vp, f64, vp, vp, C.POINTER(vp)]
+    L.oem_text_result_dims.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.oem_text_result_copy.argtypes = [vp, vp, vp, vp]
+    L.oem_text_result_destroy.argtypes = [vp]
+    L.oem_text_result_destroy.restype = None
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]
     L.oem_bootstrap.argtypes = [vp, u32, u64, vp, vp, u32, f64, vp, vp]
     L.oem_em_run_cells.argtypes = [vp, u32, vp, vp, vp, vp, u64, u64, u32, i32, u32, f64, vp, vp]
@@ -221,6 +227,7 @@ def testing_lib() -> C.CDLL:
         L.oem_test_reldiff_stress.argtypes = [u32, u32, u32, i32, vp]
         L.oem_debug_cells_last_paths.argtypes = [vp, vp, u32]
         L.oem_debug_last_launch.argtypes = [vp, vp, u32]
+        L.oem_debug_text_last_timing.argtypes = [vp]
         _testing = L
     return _testing
 

@@ -61,6 +61,7 @@ class BulkArgs:
     num_bootstraps: int = 0
     write_assignment_probs: bool = False
     display_thresh: float = 1e-6
+    prob_on_device: bool = False          # `.prob` body formatted on the device (writers.write_out_prob_device)
     seed: int = 0                         # the reference seeds from the OS (em.rs:274)
     device: int = 0
     extra_info: dict = field(default_factory=dict)
@@ -94,6 +95,9 @@ def perform_inference_and_write_output(store: InMemoryAlignmentStore, txps_name:
     if args.write_assignment_probs:                                                      # bulk.rs:196-207
         if read_names is None:
             raise ValueError("cannot write assignment probabilities without valid vector of read names")
+        if args.prob_on_device:
+            writers.write_out_prob_device(args.output, dev, counts, read_names, txps_name, args.display_thresh)
+            return counts
         probs = dev.assignment_probs(counts, args.display_thresh)
         writers.write_out_prob(args.output, store.boundaries, store.alignments, probs, read_names, txps_name,
                                args.display_thresh)

@@ -259,4 +259,8 @@ struct CellsGroupPath {
 };
 const std::vector<CellsGroupPath> &cells_last_paths();
 
+// oem_assignment_text.hip: kernel time of this thread's last oem_assignment_text under OEM_TEXT_TIMING=1 (test-only
+// library), from HIP events: ms of the measure kernel, the scan and the emit kernels (all chunks)
+void text_last_timing(float *ms3);
+
 } // namespace oem

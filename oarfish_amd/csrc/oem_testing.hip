@@ -112,6 +112,14 @@ extern "C" int oem_debug_last_launch(oem_store *s, uint32_t *out, uint32_t n_out
     return OEM_OK;
 }
 
+// out[0..2] = kernel ms of this thread's last oem_assignment_text under OEM_TEXT_TIMING=1: measure, scan, emit (all chunks)
+extern "C" int oem_debug_text_last_timing(float *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_text_last_timing: NULL argument");
+    text_last_timing(out);
+    return OEM_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Stress test of k_reldiff_swap_clear's last-block election (oem_kernels.hip): the stopping
 // decision of every EM run (em.rs:194-218) is taken by the workgroup that draws the last ticket,

@@ -49,6 +49,41 @@ class RunInfo:
     rel_diff: float
 
 
+class AssignmentText:
+    """What ``DeviceStore.assignment_text`` returns: ``text``, the body lines of the `.prob` file as one contiguous
+    ``uint8`` array (a bytes-like buffer: ``fh.write(r.text)``, ``bytes(r.text)``); ``line_off``, the ``n_reads + 1``
+    byte offsets of the lines; ``kept``, the ``k`` of each line."""
+
+    def __init__(self, text: np.ndarray, line_off: np.ndarray, kept: np.ndarray):
+        self.text = text
+        self.line_off = line_off
+        self.kept = kept
+
+    def __len__(self) -> int:
+        return len(self.kept)
+
+    def line(self, r: int) -> bytes:
+        return self.text[int(self.line_off[r]):int(self.line_off[r + 1])].tobytes()
+
+
+def pack_read_names(read_names, n_reads: int):
+    """Read names as the C ABI takes them: (blob uint8, offsets uint64[n_reads + 1]).  ``read_names`` is a sequence of
+    ``str`` / ``bytes`` or already such a pair."""
+    if isinstance(read_names, tuple) and len(read_names) == 2 and not isinstance(read_names[1], (str, bytes)):
+        blob = np.ascontiguousarray(np.frombuffer(read_names[0], dtype=np.uint8) if isinstance(read_names[0], (bytes, bytearray, memoryview))
+                                    else read_names[0], dtype=np.uint8)
+        off = np.ascontiguousarray(read_names[1], dtype=np.uint64)
+        if len(off) != n_reads + 1 or int(off[-1]) > len(blob):
+            raise ValueError("read_names offsets must have n_reads + 1 entries that end inside the blob")
+        return blob, off
+    enc = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in read_names]
+    if len(enc) != n_reads:
+        raise ValueError("read_names length != n_reads")
+    off = np.zeros(n_reads + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter(map(len, enc), dtype=np.uint64, count=n_reads), out=off[1:])
+    return np.frombuffer(b"".join(enc), dtype=np.uint8), off
+
+
 class DeviceStore:
     """RAII wrapper of an ``oem_store*`` (the matrix resident in HBM on one GPU)."""
 
@@ -221,6 +256,36 @@ class DeviceStore:
         self._check(self._lib.oem_assignment_probs(self.handle, counts.ctypes.data, display_thresh,
                                                    out.ctypes.data))
         return out
+
+    def assignment_text(self, counts, display_thresh: float, read_names=None) -> AssignmentText:
+        """write_function.rs:283-332: the body lines of the `.prob` file, formatted on the device
+        (oem_assignment_text) -- byte for byte what ``writers.write_out_prob`` writes after its header lines from
+        ``assignment_probs``, except that a read whose kept probabilities are all 0/0 prints them as Rust's ``NaN``.  ``read_names``: a sequence of ``str`` /
+        ``bytes``, a pair ``(blob, offsets)``, or None (every name empty)."""
+        counts = np.ascontiguousarray(counts, dtype=np.float64)
+        if len(counts) != self.n_txps:
+            raise ValueError("counts length != n_txps")
+        blob = off = None
+        if read_names is not None:
+            blob, off = pack_read_names(read_names, self.n_reads)
+            if len(blob) == 0:
+                blob = np.zeros(1, dtype=np.uint8)     # a non-NULL pointer: the names exist, they are all empty
+        L = self._lib
+        h = C.c_void_p()
+        self._check(L.oem_assignment_text(self.handle, counts.ctypes.data, display_thresh,
+                                          None if blob is None else blob.ctypes.data,
+                                          None if off is None else off.ctypes.data, C.byref(h)))
+        try:
+            nb, nl, nk = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+            self._check(L.oem_text_result_dims(h, C.byref(nb), C.byref(nl), C.byref(nk)))
+            text = np.empty(nb.value, dtype=np.uint8)
+            line_off = np.empty(nl.value + 1, dtype=np.uint64)
+            kept = np.empty(nl.value, dtype=np.uint32)
+            self._check(L.oem_text_result_copy(h, text.ctypes.data if nb.value else None, line_off.ctypes.data,
+                                               kept.ctypes.data if nl.value else None))
+        finally:
+            L.oem_text_result_destroy(h)
+        return AssignmentText(text, line_off, kept)
 
     def bootstrap_weights(self, seed: int, replica: int) -> np.ndarray:
         w = np.zeros(self.n_reads, dtype=np.uint32)

@@ -6,6 +6,7 @@ Host-side formatting only; every number written here comes out of the device eng
   write_output               write_function.rs:72-148   <out>.meta_info.json, .quant, .ambig_info.tsv
   write_infrep_file          write_function.rs:199-209, parquet_utils.rs:15-44, bulk.rs:181-193
   write_out_prob             write_function.rs:226-340  <out>.prob
+  write_out_prob_device      the same file, its body formatted on the device (DeviceStore.assignment_text)
   write_single_cell_output   write_function.rs:25-69    <out>.count.mtx, .features.txt (+ .barcodes.txt,
                              single_cell.rs:176-178)
 
@@ -113,6 +114,23 @@ def write_out_prob(output: str, row_ptr, tid, probs, read_names: Iterable[str], 
             pv = probs[b:e][keep]
             fh.write(f"{name.rstrip(chr(0))}\t{len(ids)}\t" + "\t".join(str(int(x)) for x in ids) + "\t"
                      + "\t".join(f"{x:.{d}f}" for x in pv) + "\n")
+    return path
+
+
+def write_out_prob_device(output: str, dev, counts, read_names, txp_names: Sequence[str], display_thresh: float) -> str:
+    """write_function.rs:226-340 with the body lines formatted on the device: the header (`T\tR`, the transcript
+    names) is written here, then the bytes of ``dev.assignment_text(counts, display_thresh, read_names)`` in one
+    write.  The file equals ``write_out_prob``'s byte for byte, with one exception: where every kept alignment of a
+    read has probability zero (``display_thresh <= 0`` only), the renormalised values are 0/0; the reference keeps
+    those alignments and prints each as `NaN`, and so does the device, while ``write_out_prob`` -- whose ``probs >= 0``
+    mask a NaN fails -- prints the read with ``k = 0``."""
+    body = dev.assignment_text(counts, display_thresh, read_names)
+    path = with_additional_extension(output, ".prob")
+    _make_parent(output)
+    with open(path, "wb") as fh:
+        fh.write(f"{len(txp_names)}\t{len(body)}\n".encode())
+        fh.write("".join(f"{t}\n" for t in txp_names).encode())
+        fh.write(body.text)
     return path
 
 
