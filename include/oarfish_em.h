@@ -41,7 +41,9 @@ extern "C" {
  *    (oem_coverage_probs_cells_device), both in one call (oem_em_run_cells_coverage_sparse), the bulk coverage model
  *    and the store on its column in one call (oem_store_create_coverage, oem_builder_store_create_coverage), the
  *    per-cell session (oem_cells_stream_*), the per-iteration rel_diff record (OEM_OPT_RUN_HISTORY, oem_run_history),
- *    the `.prob` body as text formatted on the device (oem_assignment_text, oem_text_result_dims / _copy / _destroy). */
+ *    the `.prob` body as text formatted on the device (oem_assignment_text, oem_text_result_dims / _copy / _destroy),
+ *    the whole `.prob.lz4` file as one LZ4 frame compressed on the device (oem_assignment_text_lz4,
+ *    oem_text_result_info). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -360,6 +362,32 @@ int oem_text_result_dims(const oem_text_result *r, uint64_t *n_bytes, uint64_t *
 /* text: n_bytes; line_off (optional): n_lines + 1 byte offsets; kept (optional): n_lines u32, the k of each line */
 int oem_text_result_copy(const oem_text_result *r, uint8_t *text, uint64_t *line_off, uint32_t *kept);
 void oem_text_result_destroy(oem_text_result *r); /* NULL: no-op */
+
+/* The `.prob.lz4` file (write_function.rs:243-263, 334-337): `prefix` followed by exactly the bytes oem_assignment_text
+ * returns for the same arguments, as ONE complete LZ4 frame compressed on the device -- the text never leaves the
+ * device uncompressed, and the caller links no LZ4 encoder.  prefix carries the file's header lines ("T\tR\n" and the
+ * transcript names), so the result's text / n_bytes (oem_text_result_dims, _copy) are written to disk as they are;
+ * prefix == NULL requires prefix_len == 0.  line_off and kept are what oem_assignment_text returns: offsets into the
+ * body, after the prefix.
+ * The frame: descriptor (FLG 0x78: version 01, independent blocks, block checksums, content size, no content
+ * checksum; BD 0x40: blocks of at most 64 KiB), the blocks, the zero EndMark.  Any LZ4 frame decoder reads it.  It
+ * departs from the file the reference's encoder writes (HC level 4, linked blocks, content checksum) in three ways:
+ * blocks are independent (they compress in parallel), integrity is carried by per-block XXH32 checksums instead of a
+ * content checksum (one serial chain over the whole content), and the parse is a fast greedy one, so the frame is
+ * valid but larger than the reference's.  A block that does not shrink is stored raw; a chunk's last block may be
+ * shorter than 64 KiB (legal anywhere in a frame).  The frame is a function of the content alone.
+ * A store without reads gives a frame of the prefix alone; with an empty prefix as well that is the 15-byte
+ * descriptor and the EndMark, which decodes to nothing.  Argument errors are those of oem_assignment_text plus the
+ * NULL prefix with a length; all are reported before any device use, and *out is NULL after any failure. */
+int oem_assignment_text_lz4(oem_store *store, const double *counts, double display_thresh,
+                            const uint8_t *names, const uint64_t *name_off,
+                            const uint8_t *prefix, uint64_t prefix_len, oem_text_result **out);
+/* What a text result holds beyond its dims.  A result of oem_assignment_text answers CONTENT_BYTES with its n_bytes
+ * and the other two with 0. */
+#define OEM_TEXT_INFO_CONTENT_BYTES 1u /* the frame's content: prefix + body */
+#define OEM_TEXT_INFO_BLOCKS 2u        /* blocks of the frame */
+#define OEM_TEXT_INFO_RAW_BLOCKS 3u    /* ... of which stored uncompressed */
+int oem_text_result_info(const oem_text_result *r, uint32_t key, uint64_t *value);
 
 /* --------------------------------------------------------------------- */
 /* bootstrap                                                              */

@@ -41,6 +41,9 @@ OEM_INFO_WEIGHT_DICT_ENTRIES = 1
 OEM_INFO_TILES = 2
 OEM_INFO_REMOTE_ALIGNMENTS = 3
 OEM_INFO_RUN_HISTORY_STORED = 4
+OEM_TEXT_INFO_CONTENT_BYTES = 1
+OEM_TEXT_INFO_BLOCKS = 2
+OEM_TEXT_INFO_RAW_BLOCKS = 3
 
 # every symbol include/oarfish_em.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -53,6 +56,7 @@ ABI_SYMBOLS = [
     "oem_builder_store_create", "oem_store_create_coverage", "oem_builder_store_create_coverage",
     "oem_m_step", "oem_em_run", "oem_run_history", "oem_aux_counts", "oem_assignment_probs",
     "oem_assignment_text", "oem_text_result_dims", "oem_text_result_copy", "oem_text_result_destroy",
+    "oem_assignment_text_lz4", "oem_text_result_info",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
@@ -169,6 +173,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_text_result_copy.argtypes = [vp, vp, vp, vp]
     L.oem_text_result_destroy.argtypes = [vp]
     L.oem_text_result_destroy.restype = None
+    L.oem_assignment_text_lz4.argtypes = [vp, vp, f64, vp, vp, vp, u64, C.POINTER(vp)]
+    L.oem_text_result_info.argtypes = [vp, u32, C.POINTER(u64)]
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]
     L.oem_bootstrap.argtypes = [vp, u32, u64, vp, vp, u32, f64, vp, vp]
     L.oem_em_run_cells.argtypes = [vp, u32, vp, vp, vp, vp, u64, u64, u32, i32, u32, f64, vp, vp]
@@ -228,6 +234,8 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_cells_last_paths.argtypes = [vp, vp, u32]
         L.oem_debug_last_launch.argtypes = [vp, vp, u32]
         L.oem_debug_text_last_timing.argtypes = [vp]
+        L.oem_debug_text_lz4_last_timing.argtypes = [vp]
+        L.oem_test_lz4_frame.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
         _testing = L
     return _testing
 

@@ -62,6 +62,7 @@ class BulkArgs:
     write_assignment_probs: bool = False
     display_thresh: float = 1e-6
     prob_on_device: bool = False          # `.prob` body formatted on the device (writers.write_out_prob_device)
+    prob_compressed: bool = False         # `--write-assignment-probs=compressed` (prog_opts.rs:506-513): `.prob.lz4`; on the device with prob_on_device
     seed: int = 0                         # the reference seeds from the OS (em.rs:274)
     device: int = 0
     extra_info: dict = field(default_factory=dict)
@@ -96,9 +97,10 @@ def perform_inference_and_write_output(store: InMemoryAlignmentStore, txps_name:
         if read_names is None:
             raise ValueError("cannot write assignment probabilities without valid vector of read names")
         if args.prob_on_device:
-            writers.write_out_prob_device(args.output, dev, counts, read_names, txps_name, args.display_thresh)
+            writers.write_out_prob_device(args.output, dev, counts, read_names, txps_name, args.display_thresh,
+                                          compressed=args.prob_compressed)
             return counts
         probs = dev.assignment_probs(counts, args.display_thresh)
         writers.write_out_prob(args.output, store.boundaries, store.alignments, probs, read_names, txps_name,
-                               args.display_thresh)
+                               args.display_thresh, compressed=args.prob_compressed)
     return counts

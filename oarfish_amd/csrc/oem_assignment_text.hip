@@ -9,6 +9,11 @@
 //                    function the measure kernel ran (line_nprob), so the two agree bit for bit
 // The text leaves the device in chunks of consecutive reads that fit a device text buffer; two buffers on two streams,
 // so that the read-back of chunk c runs while chunk c + 1 is being written.
+//
+// oem_assignment_text_lz4 is the same call with one more step per chunk: the chunk's text (after the caller's prefix, in
+// the first chunk) is compressed where it lies (oem_lz4.hip: blocks, scan, gather), and only the chunk's part of the
+// LZ4 frame is read back.  The host learns that part's length from the device; it waits for it when the next chunk's
+// kernels are already enqueued on the other stream.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -17,12 +22,15 @@
 #include <memory>
 
 #include "oem_driver.h"
+#include "oem_lz4.h"
 #include "oem_text_format.h"
 
 struct oem_text_result {
     uint64_t n_bytes = 0;
     uint64_t n_lines = 0;
     uint64_t n_kept = 0;
+    // oem_assignment_text_lz4: text is one LZ4 frame of content_bytes (prefix + body) in n_blocks blocks
+    uint64_t content_bytes = 0, n_blocks = 0, raw_blocks = 0;
     std::unique_ptr<uint8_t[]> text;  // n_bytes
     std::vector<uint64_t> line_off;   // n_lines + 1
     std::vector<uint32_t> kept;       // n_lines
@@ -35,6 +43,7 @@ constexpr int kTextBlock = 256;
 constexpr uint64_t kTextBufBytes = 256ull << 20; // a device text buffer (the test-only library: OEM_TEXT_BUF_BYTES)
 
 thread_local float g_text_ms[3] = {0.f, 0.f, 0.f}; // measure, scan, emit of this thread's last call (OEM_TEXT_TIMING)
+thread_local float g_text_lz4_ms[2] = {0.f, 0.f};  // k_lz4_blocks, scan + k_lz4_gather of its last compressed call
 
 // write_function.rs:307 as k_assignment_probs computes it: clamp keeps NaN, and NaN is never kept (:309)
 template <typename WT>
@@ -166,6 +175,10 @@ struct TextLane {
     uint8_t *host_dst = nullptr;
     uint64_t bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the compressed call: the chunk's blocks, and whether their read-back is still to be enqueued
+    Lz4Chunk lz;
+    bool lz_pending = false;
+    hipEvent_t ev2 = nullptr, ev3 = nullptr; // after k_lz4_blocks, after k_lz4_gather
     TextLane() = default;
     TextLane(const TextLane &) = delete;
     TextLane &operator=(const TextLane &) = delete;
@@ -177,6 +190,8 @@ struct TextLane {
         (void)hipFree(name_off);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
+        if (ev2) (void)hipEventDestroy(ev2);
+        if (ev3) (void)hipEventDestroy(ev3);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -202,15 +217,49 @@ int lane_read_back(TextLane &ln)
     return OEM_OK;
 }
 
+// The compressed call's part of the frame that a lane's chunk made: waits for the chunk (the other lane's kernels are
+// enqueued by now), then enqueues the read-back of exactly its bytes behind the frame so far.
+int lane_read_back_lz4(TextLane &ln, oem_text_result *res, uint64_t *frame_at)
+{
+    if (!ln.lz_pending) return OEM_OK;
+    ln.lz_pending = false;
+    OEM_HIP(hipStreamSynchronize(ln.stream));
+    const uint64_t bytes = ln.lz.h_info[0];
+    if (bytes) OEM_HIP(hipMemcpyAsync(res->text.get() + *frame_at, ln.lz.frame, bytes, hipMemcpyDeviceToHost, ln.stream));
+    *frame_at += bytes;
+    res->n_blocks += ln.lz.n_blocks;
+    res->raw_blocks += ln.lz.h_info[1];
+    return OEM_OK;
+}
+
+// oem_assignment_text_lz4: the bytes ahead of the body
+struct Lz4Prefix {
+    const uint8_t *bytes = nullptr;
+    uint64_t len = 0;
+};
+
+// the reads [r0, r1) of the chunk that starts at r0: those whose lines fit `budget` bytes, one read at the least
+uint64_t chunk_end(const std::vector<uint64_t> &off, uint64_t r0, uint64_t budget)
+{
+    const uint64_t r1 = (uint64_t)(std::upper_bound(off.begin() + r0, off.end(), off[r0] + budget) - off.begin()) - 1;
+    return r1 <= r0 ? r0 + 1 : r1;
+}
+
 int assignment_text(oem_store *s, const double *counts, double display_thresh, const uint8_t *names, const uint64_t *name_off,
-                    const std::vector<uint32_t> &name_len, oem_text_result *res)
+                    const std::vector<uint32_t> &name_len, oem_text_result *res, const Lz4Prefix *lz = nullptr)
 {
     const DeviceCsr &m = s->csr;
     const uint64_t R = m.n_reads;
     res->n_lines = R;
     res->line_off.assign(R + 1, 0);
     res->kept.assign(R, 0);
-    if (R == 0) return OEM_OK;
+    if (R == 0) {
+        if (lz) { // a frame of the prefix alone
+            res->content_bytes = lz->len;
+            OEM_TRY(lz4_frame_from_host(lz->bytes, lz->len, s->stream, &res->text, &res->n_bytes, &res->n_blocks, &res->raw_blocks));
+        }
+        return OEM_OK;
+    }
     if (R > 0x7ffffffeull) return fail(OEM_ERR_STATE, "oem_assignment_text: %llu reads in one store (the scan takes 2^31 - 2)", (unsigned long long)R);
     const uint32_t decimals = prob_display_decimals(display_thresh);
     const bool timing = knob("OEM_TEXT_TIMING", 0) != 0;
@@ -250,6 +299,10 @@ int assignment_text(oem_store *s, const double *counts, double display_thresh, c
         for (auto &ln : lanes) {
             OEM_HIP(hipEventCreate(&ln.ev0));
             OEM_HIP(hipEventCreate(&ln.ev1));
+            if (lz) {
+                OEM_HIP(hipEventCreate(&ln.ev2));
+                OEM_HIP(hipEventCreate(&ln.ev3));
+            }
         }
         OEM_HIP(hipEventRecord(ev[0], st));
     }
@@ -286,29 +339,57 @@ int assignment_text(oem_store *s, const double *counts, double display_thresh, c
     OEM_HIP(hipMemcpyAsync(res->kept.data(), d_kept.p, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, st));
     OEM_HIP(hipStreamSynchronize(st));
     const std::vector<uint64_t> &off = res->line_off;
-    res->n_bytes = off[R];
     for (uint32_t k : res->kept) res->n_kept += k;
-    res->text.reset(new uint8_t[res->n_bytes ? res->n_bytes : 1]);
-
-    // -- emit, chunk by chunk -------------------------------------------------------------------------------------------
     const long cap_knob = knob("OEM_TEXT_BUF_BYTES", (long)kTextBufBytes);
     const uint64_t cap = cap_knob > 0 ? (uint64_t)cap_knob : kTextBufBytes;
-    float emit_ms = 0.f;
+    // the compressed call: the prefix lies in the first chunk's buffer ahead of the body, and takes its room there (a
+    // prefix longer than the buffer grows it for that chunk, as a single long line does)
+    const uint64_t prefix_len = lz ? lz->len : 0;
+    const uint64_t first_budget = cap > prefix_len ? cap - prefix_len : 0;
+    const uint32_t lz_block = lz ? lz4_block_bytes() : 0;
+    const uint64_t text_bytes = prefix_len + off[R];
+    uint64_t frame_at = lz4::kFrameHeaderBytes; // (the compressed call) the frame so far
+    if (lz) {
+        // the content size is known here, before any text exists; so is every chunk, and with them the frame's bound
+        uint64_t n_blocks = 0;
+        for (uint64_t a = 0, c = 0; a < R; ++c) {
+            const uint64_t b = chunk_end(off, a, c ? cap : first_budget);
+            n_blocks += lz4_blocks_of((c ? 0 : prefix_len) + off[b] - off[a], lz_block);
+            a = b;
+        }
+        res->content_bytes = text_bytes;
+        res->text.reset(new uint8_t[lz4::kFrameHeaderBytes + text_bytes + lz4::kBlockOverheadBytes * n_blocks + lz4::kEndMarkBytes]);
+        lz4::frame_header(res->text.get(), text_bytes);
+    } else {
+        res->n_bytes = off[R];
+        res->text.reset(new uint8_t[res->n_bytes ? res->n_bytes : 1]);
+    }
+
+    // -- emit, chunk by chunk -------------------------------------------------------------------------------------------
+    float emit_ms = 0.f, lz_ms[2] = {0.f, 0.f};
+    // a lane's last chunk, once its events are complete
+    auto lane_times = [&](TextLane &ln) { // (a lane that never ran a chunk has no times: not an error)
+        float ms[3] = {0.f, 0.f, 0.f};
+        if (hipEventElapsedTime(&ms[0], ln.ev0, ln.ev1) != hipSuccess) return;
+        if (lz && (hipEventElapsedTime(&ms[1], ln.ev1, ln.ev2) != hipSuccess || hipEventElapsedTime(&ms[2], ln.ev2, ln.ev3) != hipSuccess)) return;
+        emit_ms += ms[0];
+        lz_ms[0] += ms[1];
+        lz_ms[1] += ms[2];
+    };
     uint64_t r0 = 0;
     for (uint32_t c = 0; r0 < R; ++c) {
         // the reads whose lines fit the buffer; a single line longer than it grows the buffer for this chunk
-        uint64_t r1 = (uint64_t)(std::upper_bound(off.begin() + r0, off.end(), off[r0] + cap) - off.begin()) - 1;
-        if (r1 <= r0) r1 = r0 + 1;
+        const uint64_t r1 = chunk_end(off, r0, c ? cap : first_budget);
         const uint64_t bytes = off[r1] - off[r0];
+        const uint64_t pre = c ? 0 : prefix_len;
         TextLane &ln = lanes[c & 1];
         TextLane &prev = lanes[(c & 1) ^ 1];
         if (timing && c >= 2) { // the lane's previous chunk, before its events are recorded again
-            float ms = 0.f;
-            OEM_HIP(hipEventSynchronize(ln.ev1));
-            OEM_HIP(hipEventElapsedTime(&ms, ln.ev0, ln.ev1));
-            emit_ms += ms;
+            OEM_HIP(hipEventSynchronize(lz ? ln.ev3 : ln.ev1));
+            lane_times(ln);
         }
-        OEM_TRY(lane_reserve(ln, &ln.text, &ln.text_cap, std::max(bytes, std::min(cap, res->n_bytes))));
+        OEM_TRY(lane_reserve(ln, &ln.text, &ln.text_cap, std::max(pre + bytes, std::min(cap, text_bytes))));
+        if (pre) OEM_HIP(hipMemcpyAsync(ln.text, lz->bytes, pre, hipMemcpyHostToDevice, ln.stream));
         if (names) {
             const uint64_t nb = name_off[r1] - name_off[r0];
             OEM_TRY(lane_reserve(ln, &ln.names, &ln.names_cap, nb));
@@ -320,31 +401,45 @@ int assignment_text(oem_store *s, const double *counts, double display_thresh, c
 #define OEM_LAUNCH_EMIT(PT, WT, wptr)                                                                                    \
     hipLaunchKernelGGL((k_text_emit<PT, WT>), dim3(text_grid(r1 - r0)), dim3(kTextBlock), 0, ln.stream,                  \
                        (const PT *)m.row_ptr, m.tid, wptr, s->theta, r0, r1, display_thresh, decimals, ln.names, ln.name_off, \
-                       d_name_len.p, d_denom.p, d_denom2.p, d_kept.p, d_off.p, ln.text)
+                       d_name_len.p, d_denom.p, d_denom2.p, d_kept.p, d_off.p, ln.text + pre)
         OEM_TEXT_DISPATCH(OEM_LAUNCH_EMIT);
 #undef OEM_LAUNCH_EMIT
         OEM_HIP(hipGetLastError());
         if (timing) OEM_HIP(hipEventRecord(ln.ev1, ln.stream));
-        ln.host_dst = res->text.get() + off[r0];
-        ln.bytes = bytes;
-        // the previous chunk's text comes back while this chunk's kernel runs
-        OEM_TRY(lane_read_back(prev));
+        if (lz) {
+            OEM_TRY(lz4_chunk_enqueue(ln.lz, ln.text, pre + bytes, lz_block, ln.stream, ln.ev2, ln.ev3));
+            ln.lz_pending = true;
+            // the previous chunk's blocks come back while this chunk's kernels run
+            OEM_TRY(lane_read_back_lz4(prev, res, &frame_at));
+        } else {
+            ln.host_dst = res->text.get() + off[r0];
+            ln.bytes = bytes;
+            // the previous chunk's text comes back while this chunk's kernel runs
+            OEM_TRY(lane_read_back(prev));
+        }
         r0 = r1;
     }
 #undef OEM_TEXT_DISPATCH
-    OEM_TRY(lane_read_back(lanes[0]));
-    OEM_TRY(lane_read_back(lanes[1]));
+    if (lz) { // (one of the two is pending: the last chunk's)
+        OEM_TRY(lane_read_back_lz4(lanes[0], res, &frame_at));
+        OEM_TRY(lane_read_back_lz4(lanes[1], res, &frame_at));
+        std::memset(res->text.get() + frame_at, 0, lz4::kEndMarkBytes);
+        res->n_bytes = frame_at + lz4::kEndMarkBytes;
+    } else {
+        OEM_TRY(lane_read_back(lanes[0]));
+        OEM_TRY(lane_read_back(lanes[1]));
+    }
     OEM_HIP(hipStreamSynchronize(lanes[0].stream));
     OEM_HIP(hipStreamSynchronize(lanes[1].stream));
     if (timing) {
         for (auto &ln : lanes) {
-            float ms = 0.f;
-            if (hipEventQuery(ln.ev1) == hipSuccess && hipEventElapsedTime(&ms, ln.ev0, ln.ev1) == hipSuccess) emit_ms += ms;
+            if (hipEventQuery(lz ? ln.ev3 : ln.ev1) == hipSuccess) lane_times(ln);
             (void)hipGetLastError();
         }
         OEM_HIP(hipEventElapsedTime(&g_text_ms[0], ev[0], ev[1]));
         OEM_HIP(hipEventElapsedTime(&g_text_ms[1], ev[1], ev[2]));
         g_text_ms[2] = emit_ms;
+        if (lz) std::memcpy(g_text_lz4_ms, lz_ms, sizeof lz_ms);
     }
     return OEM_OK;
 }
@@ -352,28 +447,32 @@ int assignment_text(oem_store *s, const double *counts, double display_thresh, c
 } // namespace
 
 void text_last_timing(float *ms3) { std::memcpy(ms3, g_text_ms, sizeof g_text_ms); }
+void text_lz4_last_timing(float *ms2) { std::memcpy(ms2, g_text_lz4_ms, sizeof g_text_lz4_ms); }
 
 } // namespace oem
 
 using namespace oem;
 
-extern "C" int oem_assignment_text(oem_store *s, const double *counts, double display_thresh, const uint8_t *names,
-                                   const uint64_t *name_off, oem_text_result **out)
+namespace {
+
+// what the two entry points share: the argument checks (before any device use), the lock, the result
+int assignment_text_call(const char *who, oem_store *s, const double *counts, double display_thresh, const uint8_t *names,
+                         const uint64_t *name_off, const Lz4Prefix *lz, oem_text_result **out)
 {
-    OEM_API_BEGIN
     if (out) *out = nullptr;
-    if (!s || !counts || !out) return fail(OEM_ERR_ARG, "oem_assignment_text: NULL argument");
+    if (!s || !counts || !out) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
     if ((names == nullptr) != (name_off == nullptr))
-        return fail(OEM_ERR_ARG, "oem_assignment_text: names and name_off come together (both NULL: empty names)");
+        return fail(OEM_ERR_ARG, "%s: names and name_off come together (both NULL: empty names)", who);
+    if (lz && !lz->bytes && lz->len) return fail(OEM_ERR_ARG, "%s: prefix is NULL and prefix_len is not 0", who);
     const uint64_t R = s->csr.n_reads;
     std::vector<uint32_t> name_len;
     if (names) {
-        if (name_off[0] != 0) return fail(OEM_ERR_ARG, "oem_assignment_text: name_off[0] must be 0");
+        if (name_off[0] != 0) return fail(OEM_ERR_ARG, "%s: name_off[0] must be 0", who);
         name_len.resize(R);
         for (uint64_t r = 0; r < R; ++r) {
-            if (name_off[r + 1] < name_off[r]) return fail(OEM_ERR_ARG, "oem_assignment_text: name_off must be non-decreasing (read %llu)", (unsigned long long)r);
+            if (name_off[r + 1] < name_off[r]) return fail(OEM_ERR_ARG, "%s: name_off must be non-decreasing (read %llu)", who, (unsigned long long)r);
             uint64_t n = name_off[r + 1] - name_off[r];
-            if (n > 0xffffffffull) return fail(OEM_ERR_ARG, "oem_assignment_text: name of read %llu is longer than 2^32 - 1 bytes", (unsigned long long)r);
+            if (n > 0xffffffffull) return fail(OEM_ERR_ARG, "%s: name of read %llu is longer than 2^32 - 1 bytes", who, (unsigned long long)r);
             const uint8_t *p = names + name_off[r];
             while (n && p[n - 1] == 0) --n; // trim_end_matches('\0'), write_function.rs:294
             name_len[r] = (uint32_t)n;
@@ -382,10 +481,42 @@ extern "C" int oem_assignment_text(oem_store *s, const double *counts, double di
     std::lock_guard<std::mutex> lk(s->mu);
     OEM_TRY(ensure_device(s->device));
     std::unique_ptr<oem_text_result> res(new oem_text_result);
-    OEM_TRY(assignment_text(s, counts, display_thresh, names, name_off, name_len, res.get()));
+    OEM_TRY(assignment_text(s, counts, display_thresh, names, name_off, name_len, res.get(), lz));
+    if (!lz) res->content_bytes = res->n_bytes;
     *out = res.release();
     return OEM_OK;
+}
+
+} // namespace
+
+extern "C" int oem_assignment_text(oem_store *s, const double *counts, double display_thresh, const uint8_t *names,
+                                   const uint64_t *name_off, oem_text_result **out)
+{
+    OEM_API_BEGIN
+    return assignment_text_call("oem_assignment_text", s, counts, display_thresh, names, name_off, nullptr, out);
     OEM_API_END("oem_assignment_text")
+}
+
+extern "C" int oem_assignment_text_lz4(oem_store *s, const double *counts, double display_thresh, const uint8_t *names,
+                                       const uint64_t *name_off, const uint8_t *prefix, uint64_t prefix_len, oem_text_result **out)
+{
+    OEM_API_BEGIN
+    Lz4Prefix lz;
+    lz.bytes = prefix;
+    lz.len = prefix_len;
+    return assignment_text_call("oem_assignment_text_lz4", s, counts, display_thresh, names, name_off, &lz, out);
+    OEM_API_END("oem_assignment_text_lz4")
+}
+
+extern "C" int oem_text_result_info(const oem_text_result *r, uint32_t key, uint64_t *value)
+{
+    if (!r || !value) return fail(OEM_ERR_ARG, "oem_text_result_info: NULL argument");
+    switch (key) {
+    case OEM_TEXT_INFO_CONTENT_BYTES: *value = r->content_bytes; return OEM_OK;
+    case OEM_TEXT_INFO_BLOCKS: *value = r->n_blocks; return OEM_OK;
+    case OEM_TEXT_INFO_RAW_BLOCKS: *value = r->raw_blocks; return OEM_OK;
+    }
+    return fail(OEM_ERR_ARG, "oem_text_result_info: unknown key %u", key);
 }
 
 extern "C" int oem_text_result_dims(const oem_text_result *r, uint64_t *n_bytes, uint64_t *n_lines, uint64_t *n_kept)

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 
 #include "oem_internal.h"
 
@@ -262,5 +263,38 @@ const std::vector<CellsGroupPath> &cells_last_paths();
 // oem_assignment_text.hip: kernel time of this thread's last oem_assignment_text under OEM_TEXT_TIMING=1 (test-only
 // library), from HIP events: ms of the measure kernel, the scan and the emit kernels (all chunks)
 void text_last_timing(float *ms3);
+// ... and of this thread's last oem_assignment_text_lz4: ms of k_lz4_blocks and of scan + k_lz4_gather (all chunks)
+void text_lz4_last_timing(float *ms2);
+
+// oem_lz4.hip: the device buffers the compression of one chunk owns; reused by the chunks that follow it on its stream
+struct Lz4Chunk {
+    uint8_t *slots = nullptr; // one bound-strided slot per block: its compressed payload
+    uint64_t slots_cap = 0;
+    uint32_t *sizes = nullptr, *sums = nullptr; // per block: bytes of the payload as stored, XXH32 of it
+    uint64_t *offs = nullptr;                   // per block: its offset in `frame`; offs[n_blocks] = the frame's bytes
+    uint64_t blocks_cap = 0;
+    uint8_t *tmp = nullptr; // the scan's
+    uint64_t tmp_cap = 0;
+    uint8_t *frame = nullptr; // the chunk's blocks as the frame holds them: size word, payload, checksum each
+    uint64_t frame_cap = 0;
+    unsigned long long *d_raw = nullptr;
+    uint64_t *h_info = nullptr; // pinned: [0] bytes of `frame`, [1] raw blocks, once the stream has passed the enqueue
+    uint64_t n_blocks = 0;
+    Lz4Chunk() = default;
+    Lz4Chunk(const Lz4Chunk &) = delete;
+    Lz4Chunk &operator=(const Lz4Chunk &) = delete;
+    ~Lz4Chunk(); // the stream is idle
+};
+// the block length: 64 KiB (the test-only library: OEM_LZ4_BLOCK_BYTES, at most that)
+uint32_t lz4_block_bytes();
+uint64_t lz4_blocks_of(uint64_t n, uint32_t block_bytes);
+// Enqueues blocks / scan / gather of the n device bytes at d_in on `st`, and the copy of the result's length to
+// c.h_info.  d_in stays untouched until the stream has passed (raw blocks are gathered from it).  The events, where
+// given, are recorded after k_lz4_blocks and after k_lz4_gather.
+int lz4_chunk_enqueue(Lz4Chunk &c, const uint8_t *d_in, uint64_t n, uint32_t block_bytes, hipStream_t st,
+                      hipEvent_t ev_blocks = nullptr, hipEvent_t ev_gather = nullptr);
+// One complete frame (descriptor, blocks, EndMark) of n host bytes, through the same three steps; synchronises `st`.
+int lz4_frame_from_host(const uint8_t *data, uint64_t n, hipStream_t st, std::unique_ptr<uint8_t[]> *out, uint64_t *out_len,
+                        uint64_t *n_blocks, uint64_t *raw_blocks);
 
 } // namespace oem

@@ -120,6 +120,39 @@ extern "C" int oem_debug_text_last_timing(float *out)
     return OEM_OK;
 }
 
+// out[0..1] = kernel ms of this thread's last oem_assignment_text_lz4 under OEM_TEXT_TIMING=1: k_lz4_blocks, scan +
+// k_lz4_gather (all chunks); its measure / scan / emit are in oem_debug_text_last_timing
+extern "C" int oem_debug_text_lz4_last_timing(float *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_text_lz4_last_timing: NULL argument");
+    text_lz4_last_timing(out);
+    return OEM_OK;
+}
+
+// Test hook: the n caller bytes at `data` as one LZ4 frame, by the path oem_assignment_text_lz4 compresses a chunk with
+// (upload, k_lz4_blocks, scan, k_lz4_gather; blocks of OEM_LZ4_BLOCK_BYTES), so that tests can feed crafted inputs.
+// *out_len = the frame's length, always; the frame is copied to out when it fits cap (else OEM_ERR_ARG).
+extern "C" int oem_test_lz4_frame(const uint8_t *data, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len)
+{
+    OEM_API_BEGIN
+    if ((!data && n) || (!out && cap) || !out_len) return fail(OEM_ERR_ARG, "oem_test_lz4_frame: bad argument");
+    *out_len = 0;
+    OEM_TRY(ensure_device(0));
+    hipStream_t st = nullptr;
+    OEM_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    std::unique_ptr<uint8_t[]> frame;
+    uint64_t len = 0, n_blocks = 0, raw_blocks = 0;
+    const int rc = lz4_frame_from_host(data, n, st, &frame, &len, &n_blocks, &raw_blocks);
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    OEM_TRY(rc);
+    *out_len = len;
+    if (len > cap) return fail(OEM_ERR_ARG, "oem_test_lz4_frame: the frame has %llu bytes, out holds %llu", (unsigned long long)len, (unsigned long long)cap);
+    std::memcpy(out, frame.get(), len);
+    return OEM_OK;
+    OEM_API_END("oem_test_lz4_frame")
+}
+
 // ---------------------------------------------------------------------------
 // Stress test of k_reldiff_swap_clear's last-block election (oem_kernels.hip): the stopping
 // decision of every EM run (em.rs:194-218) is taken by the workgroup that draws the last ticket,

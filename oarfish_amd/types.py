@@ -52,7 +52,9 @@ class RunInfo:
 class AssignmentText:
     """What ``DeviceStore.assignment_text`` returns: ``text``, the body lines of the `.prob` file as one contiguous
     ``uint8`` array (a bytes-like buffer: ``fh.write(r.text)``, ``bytes(r.text)``); ``line_off``, the ``n_reads + 1``
-    byte offsets of the lines; ``kept``, the ``k`` of each line."""
+    byte offsets of the lines; ``kept``, the ``k`` of each line.  From ``DeviceStore.assignment_text_lz4`` ``text`` is
+    the LZ4 frame of the whole file instead (``line_off`` still describes the uncompressed body), and the result also
+    carries ``content_bytes``, ``n_blocks`` and ``raw_blocks``."""
 
     def __init__(self, text: np.ndarray, line_off: np.ndarray, kept: np.ndarray):
         self.text = text
@@ -286,6 +288,45 @@ class DeviceStore:
         finally:
             L.oem_text_result_destroy(h)
         return AssignmentText(text, line_off, kept)
+
+    def assignment_text_lz4(self, counts, display_thresh: float, read_names=None, prefix: bytes = b"") -> AssignmentText:
+        """The `.prob.lz4` file (write_function.rs:243-263, 334-337) compressed on the device
+        (oem_assignment_text_lz4): ``text`` is one complete LZ4 frame whose content is ``prefix`` -- the file's header
+        lines -- followed by exactly the bytes ``assignment_text`` returns for the same arguments; ``line_off`` and
+        ``kept`` are that call's (offsets into the body, after the prefix).  The result also has ``content_bytes``
+        (prefix + body), ``n_blocks`` and ``raw_blocks`` (blocks stored uncompressed)."""
+        counts = np.ascontiguousarray(counts, dtype=np.float64)
+        if len(counts) != self.n_txps:
+            raise ValueError("counts length != n_txps")
+        blob = off = None
+        if read_names is not None:
+            blob, off = pack_read_names(read_names, self.n_reads)
+            if len(blob) == 0:
+                blob = np.zeros(1, dtype=np.uint8)     # a non-NULL pointer: the names exist, they are all empty
+        pre = np.frombuffer(bytes(prefix), dtype=np.uint8)
+        L = self._lib
+        h = C.c_void_p()
+        self._check(L.oem_assignment_text_lz4(self.handle, counts.ctypes.data, display_thresh,
+                                              None if blob is None else blob.ctypes.data,
+                                              None if off is None else off.ctypes.data,
+                                              pre.ctypes.data if len(pre) else None, len(pre), C.byref(h)))
+        try:
+            nb, nl, nk = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+            self._check(L.oem_text_result_dims(h, C.byref(nb), C.byref(nl), C.byref(nk)))
+            text = np.empty(nb.value, dtype=np.uint8)
+            line_off = np.empty(nl.value + 1, dtype=np.uint64)
+            kept = np.empty(nl.value, dtype=np.uint32)
+            self._check(L.oem_text_result_copy(h, text.ctypes.data, line_off.ctypes.data,
+                                               kept.ctypes.data if nl.value else None))
+            res = AssignmentText(text, line_off, kept)
+            v = C.c_uint64(0)
+            for name, key in (("content_bytes", _lib.OEM_TEXT_INFO_CONTENT_BYTES), ("n_blocks", _lib.OEM_TEXT_INFO_BLOCKS),
+                              ("raw_blocks", _lib.OEM_TEXT_INFO_RAW_BLOCKS)):
+                self._check(L.oem_text_result_info(h, key, C.byref(v)))
+                setattr(res, name, int(v.value))
+        finally:
+            L.oem_text_result_destroy(h)
+        return res
 
     def bootstrap_weights(self, seed: int, replica: int) -> np.ndarray:
         w = np.zeros(self.n_reads, dtype=np.uint32)

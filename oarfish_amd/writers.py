@@ -6,7 +6,12 @@ Host-side formatting only; every number written here comes out of the device eng
   write_output               write_function.rs:72-148   <out>.meta_info.json, .quant, .ambig_info.tsv
   write_infrep_file          write_function.rs:199-209, parquet_utils.rs:15-44, bulk.rs:181-193
   write_out_prob             write_function.rs:226-340  <out>.prob
-  write_out_prob_device      the same file, its body formatted on the device (DeviceStore.assignment_text)
+  write_out_prob_device      the same file, its body formatted on the device (DeviceStore.assignment_text); with
+                             compressed=True <out>.prob.lz4 (:243-263, 334-337), formatted AND compressed on the
+                             device (DeviceStore.assignment_text_lz4): one valid LZ4 frame of the same bytes, which
+                             departs from the reference's file in its encoding only -- independent 64 KiB blocks,
+                             per-block checksums instead of a content checksum, a fast greedy parse instead of HC
+                             level 4 -- so it is larger than the reference's and every LZ4 frame decoder reads it
   write_single_cell_output   write_function.rs:25-69    <out>.count.mtx, .features.txt (+ .barcodes.txt,
                              single_cell.rs:176-178)
 
@@ -117,19 +122,29 @@ def write_out_prob(output: str, row_ptr, tid, probs, read_names: Iterable[str], 
     return path
 
 
-def write_out_prob_device(output: str, dev, counts, read_names, txp_names: Sequence[str], display_thresh: float) -> str:
+def write_out_prob_device(output: str, dev, counts, read_names, txp_names: Sequence[str], display_thresh: float,
+                          compressed: bool = False) -> str:
     """write_function.rs:226-340 with the body lines formatted on the device: the header (`T\tR`, the transcript
     names) is written here, then the bytes of ``dev.assignment_text(counts, display_thresh, read_names)`` in one
     write.  The file equals ``write_out_prob``'s byte for byte, with one exception: where every kept alignment of a
     read has probability zero (``display_thresh <= 0`` only), the renormalised values are 0/0; the reference keeps
     those alignments and prints each as `NaN`, and so does the device, while ``write_out_prob`` -- whose ``probs >= 0``
-    mask a NaN fails -- prints the read with ``k = 0``."""
+    mask a NaN fails -- prints the read with ``k = 0``.
+
+    ``compressed``: `<out>.prob.lz4` instead, in one write: the LZ4 frame ``dev.assignment_text_lz4`` makes on the
+    device of the header lines (its prefix) and the same body; it decodes to the bytes of the uncompressed file."""
+    header = f"{len(txp_names)}\t{dev.n_reads}\n".encode() + "".join(f"{t}\n" for t in txp_names).encode()
+    _make_parent(output)
+    if compressed:
+        frame = dev.assignment_text_lz4(counts, display_thresh, read_names, prefix=header)
+        path = with_additional_extension(output, ".prob.lz4")
+        with open(path, "wb") as fh:
+            fh.write(frame.text)
+        return path
     body = dev.assignment_text(counts, display_thresh, read_names)
     path = with_additional_extension(output, ".prob")
-    _make_parent(output)
     with open(path, "wb") as fh:
-        fh.write(f"{len(txp_names)}\t{len(body)}\n".encode())
-        fh.write("".join(f"{t}\n" for t in txp_names).encode())
+        fh.write(header)
         fh.write(body.text)
     return path
 
