@@ -43,7 +43,8 @@ extern "C" {
  *    per-cell session (oem_cells_stream_*), the per-iteration rel_diff record (OEM_OPT_RUN_HISTORY, oem_run_history),
  *    the `.prob` body as text formatted on the device (oem_assignment_text, oem_text_result_dims / _copy / _destroy),
  *    the whole `.prob.lz4` file as one LZ4 frame compressed on the device (oem_assignment_text_lz4,
- *    oem_text_result_info). */
+ *    oem_text_result_info), the batched filter on the host and on the device and the store straight from the records
+ *    (oem_builder_add_groups, oem_builder_add_groups_device, oem_store_create_records). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -216,6 +217,29 @@ void oem_builder_destroy(oem_builder *b);
  * alignments by the coverage entry points below. */
 int oem_builder_add_group(oem_builder *b, const oem_aln_record *records, uint32_t n_records,
                           uint32_t *out_kept);
+/* n_groups add_group calls in one: group g = records[group_off[g] .. group_off[g+1]) (group_off: n_groups + 1 entries).
+ * The builder's state afterwards -- everything oem_builder_export, _dims and _discard_table show -- is byte for byte the
+ * state after the loop of oem_builder_add_group over the same groups in order; appending to a non-empty builder works.
+ * out_kept[g] (n_groups entries, or NULL) is what add_group would have returned for group g; row r of what the call
+ * appends is the r-th group with out_kept > 0, which is how a caller lines read names up for oem_assignment_text.
+ * The call is atomic: on any error the builder is unchanged.  Argument errors are those of add_group plus those of
+ * group_off (NULL, group_off[0] != 0, decreasing, a group of more than 2^32 - 1 records); a ref_id that is not below
+ * n_txps is reported with the index of the first such record. */
+int oem_builder_add_groups(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off,
+                           uint64_t n_groups, uint32_t *out_kept /* n_groups, or NULL */);
+/* The same builder state afterwards, byte for byte, computed on the device (oem_filter_device.hip): the records go up
+ * in chunks, one lane filters each read, the retained alignments are compacted on the device and copied back.  The f32
+ * as_prob is bit-identical to the host's because the device never computes exp: the host fills a table
+ * tab[g] = expf((float)(-g) / D) over the integer score gap g = best - score, up to the first entry that is +0.0f, and
+ * the device looks as_prob up by g (exact for |score| <= 2^24).  The batch goes through the host loop of
+ * oem_builder_add_groups instead -- same result -- when score_prob_denom is not finite and positive, when the table
+ * would need more than 2^22 entries, or when a mapped record with OEM_REC_HAS_SCORE has |(int32_t)score| > 2^24 (found
+ * by the device pass, which the host then repeats).  The result does not depend on how the call cuts its input into
+ * chunks.  At most 2^31 - 2 groups per call (OEM_ERR_ARG).  Without a device: OEM_ERR_NO_DEVICE -- also for a batch
+ * the host loop will take (the device is asked for before the fallback is chosen, so the call never succeeds on a box
+ * where its device form could not run). */
+int oem_builder_add_groups_device(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off,
+                                  uint64_t n_groups, int device, uint32_t *out_kept);
 int oem_builder_dims(const oem_builder *b, uint64_t *n_reads, uint64_t *nnz);
 int oem_builder_discard_table(const oem_builder *b, oem_discard_table *out);
 /* Copies the store out: row_ptr[n_reads+1], and per alignment tid / as_prob / start / end / strand
@@ -286,6 +310,20 @@ int oem_store_create_coverage(const uint64_t *row_ptr, const uint32_t *tid, cons
 int oem_builder_store_create_coverage(const oem_builder *b, uint32_t bin_width, int model, double growth_rate,
                                       int device, const oem_store_opts *opts,
                                       double *out_cov_prob /* nnz, or NULL */, oem_store **out);
+/* records -> resident store in one call; the CSR never exists on the host.  The store is the one the long way round
+ * gives: oem_builder_create(filters, txp_len, n_txps), oem_builder_add_groups, then oem_builder_store_create (model -1:
+ * no coverage column) or oem_builder_store_create_coverage (model 0 / 1 with bin_width and growth_rate as there), with
+ * the same opts, for every weight_coding and both layout_build values (host arrays come back from the device only for
+ * the host layout builder).  out_kept (n_groups, or NULL) and out_discard (or NULL) are add_groups' out_kept and the
+ * builder's discard table.  Requires fewer than 2^32 kept alignments (OEM_ERR_ARG otherwise); the other argument errors
+ * are those of oem_builder_add_groups_device and oem_store_create_coverage, an alignment outside its transcript under a
+ * coverage model is OEM_ERR_STATE.  *out = NULL on any failure. */
+int oem_store_create_records(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                             const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
+                             uint32_t bin_width, int model, double growth_rate,
+                             int device, const oem_store_opts *opts,
+                             uint32_t *out_kept /* n_groups, or NULL */, oem_discard_table *out_discard /* or NULL */,
+                             oem_store **out);
 
 /* --------------------------------------------------------------------- */
 /* EM                                                                     */

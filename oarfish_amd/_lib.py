@@ -49,7 +49,8 @@ OEM_TEXT_INFO_RAW_BLOCKS = 3
 ABI_SYMBOLS = [
     "oem_abi_version", "oem_last_error", "oem_device_count",
     "oem_store_create", "oem_store_destroy", "oem_store_dims", "oem_store_bytes", "oem_store_info", "oem_store_set_option",
-    "oem_builder_create", "oem_builder_destroy", "oem_builder_add_group", "oem_builder_dims",
+    "oem_builder_create", "oem_builder_destroy", "oem_builder_add_group", "oem_builder_add_groups",
+    "oem_builder_add_groups_device", "oem_store_create_records", "oem_builder_dims",
     "oem_builder_discard_table", "oem_builder_export", "oem_builder_coverage_probs",
     "oem_builder_coverage_probs_binomial", "oem_coverage_probs_device", "oem_builder_coverage_probs_device",
     "oem_coverage_probs_cells_device",
@@ -151,6 +152,9 @@ def _load(path: str) -> C.CDLL:
     L.oem_builder_destroy.argtypes = [vp]
     L.oem_builder_destroy.restype = None
     L.oem_builder_add_group.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.oem_builder_add_groups.argtypes = [vp, vp, vp, u64, vp]
+    L.oem_builder_add_groups_device.argtypes = [vp, vp, vp, u64, i32, vp]
+    L.oem_store_create_records.argtypes = [vp, vp, u32, vp, vp, u64, u32, i32, f64, i32, vp, vp, vp, C.POINTER(vp)]
     L.oem_builder_dims.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.oem_builder_discard_table.argtypes = [vp, vp]
     L.oem_builder_export.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -236,6 +240,7 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_text_last_timing.argtypes = [vp]
         L.oem_debug_text_lz4_last_timing.argtypes = [vp]
         L.oem_test_lz4_frame.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
+        L.oem_debug_filter_last_timing.argtypes = [vp]
         _testing = L
     return _testing
 

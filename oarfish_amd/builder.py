@@ -1,0 +1,190 @@
+"""The store builder: alignment records -> the CSR the EM consumes.
+
+``StoreBuilder`` wraps ``oem_builder_*``: AlignmentFilters::filter + add_filtered_group
+(src/util/oarfish_types.rs:955-1130, :718-738) per read, one read per call (``add_group``) or a batch of reads per call
+(``add_groups``), on the host or -- ``device=`` -- on the GPU (oem_filter_device.hip), with the same builder state
+afterwards byte for byte.  ``DeviceStore.from_records`` (types.py) goes from the records to a resident store in one
+call, without the CSR ever existing on the host.
+
+Records are a numpy structured array of dtype ``ALN_RECORD`` (the 40 bytes of ``oem_aln_record``); group g of a batch
+is ``records[group_off[g]:group_off[g + 1]]``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+from ._lib import REC_HAS_SCORE, REC_REVERSE, REC_SUPPLEMENTARY, REC_UNMAPPED  # noqa: F401  (re-exported)
+
+ALN_RECORD = np.dtype([("ref_id", "<u4"), ("aln_start", "<u4"), ("aln_end", "<u4"), ("aln_span", "<u4"),
+                       ("score", "<i8"), ("seq_len", "<i8"), ("flags", "<u4"), ("reserved", "<u4")])
+assert ALN_RECORD.itemsize == C.sizeof(_lib.AlnRecordC) == 40
+
+DISCARD_FIELDS = tuple(n for n, _ in _lib.DiscardTableC._fields_)
+
+
+def filters_c(filters) -> _lib.FiltersC:
+    """An ``oem_filters`` from a ``FiltersC``, a mapping or any object with the fields of AlignmentFilters
+    (five_prime_clip, three_prime_clip, score_threshold, min_aligned_fraction, min_aligned_len, which_strand,
+    score_prob_denom)."""
+    if isinstance(filters, _lib.FiltersC):
+        return filters
+    get = (lambda k: filters[k]) if isinstance(filters, dict) else (lambda k: getattr(filters, k))
+    return _lib.FiltersC(int(get("five_prime_clip")), int(get("three_prime_clip")), float(get("score_threshold")),
+                         float(get("min_aligned_fraction")), int(get("min_aligned_len")), int(get("which_strand")),
+                         float(get("score_prob_denom")), 0)
+
+
+def check_batch(records, group_off):
+    """(records, group_off) as the contiguous arrays the C calls read."""
+    records = np.ascontiguousarray(records, dtype=ALN_RECORD)
+    group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+    if group_off.ndim != 1 or len(group_off) < 1:
+        raise ValueError("group_off needs n_groups + 1 entries")
+    if int(group_off[-1]) > len(records):
+        raise ValueError("group_off runs past the end of records")
+    return records, group_off
+
+
+def discard_dict(dt: _lib.DiscardTableC) -> dict:
+    return {n: int(getattr(dt, n)) for n in DISCARD_FIELDS}
+
+
+class StoreBuilder:
+    """RAII wrapper of an ``oem_builder*``."""
+
+    def __init__(self, filters, txp_len):
+        self._lib = _lib.lib()
+        self.filters = filters_c(filters)
+        self.txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        self._h = C.c_void_p()
+        self._check(self._lib.oem_builder_create(C.addressof(self.filters), self.txp_len.ctypes.data, len(self.txp_len),
+                                                 C.byref(self._h)))
+
+    def _check(self, rc: int) -> None:
+        if rc != _lib.OEM_OK:
+            msg = self._lib.oem_last_error()
+            raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.oem_builder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        if not self._h.value:
+            raise RuntimeError("StoreBuilder is closed")
+        return self._h
+
+    # -- filling -----------------------------------------------------------------------------------------------------
+    def add_group(self, records) -> int:
+        """One read's records; returns the number of alignments kept (0: the read was dropped)."""
+        records = np.ascontiguousarray(records, dtype=ALN_RECORD)
+        kept = C.c_uint32(0)
+        self._check(self._lib.oem_builder_add_group(self.handle, records.ctypes.data if len(records) else None,
+                                                    len(records), C.byref(kept)))
+        return int(kept.value)
+
+    def add_groups(self, records, group_off, device: Optional[int] = None) -> np.ndarray:
+        """A batch of reads in one call, on the host (``device=None``) or on GPU ``device``.  Returns ``kept`` (u32 per
+        group: what ``add_group`` would have returned); row r of what the call appends is the r-th group with
+        ``kept > 0``.  The call is atomic: on an error the builder is unchanged."""
+        records, group_off = check_batch(records, group_off)
+        n_groups = len(group_off) - 1
+        kept = np.zeros(n_groups, dtype=np.uint32)
+        rec = records.ctypes.data if len(records) else None
+        if device is None:
+            rc = self._lib.oem_builder_add_groups(self.handle, rec, group_off.ctypes.data, n_groups, kept.ctypes.data)
+        else:
+            rc = self._lib.oem_builder_add_groups_device(self.handle, rec, group_off.ctypes.data, n_groups, int(device),
+                                                         kept.ctypes.data)
+        self._check(rc)
+        return kept
+
+    # -- reading -----------------------------------------------------------------------------------------------------
+    def dims(self):
+        """(n_reads, nnz)"""
+        R, nnz = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.oem_builder_dims(self.handle, C.byref(R), C.byref(nnz)))
+        return int(R.value), int(nnz.value)
+
+    def export(self):
+        """(row_ptr u64, tid u32, as_prob f32, start u32, end u32, strand u8)"""
+        R, nnz = self.dims()
+        rp = np.zeros(R + 1, dtype=np.uint64)
+        tid, p = np.zeros(nnz, dtype=np.uint32), np.zeros(nnz, dtype=np.float32)
+        s, e, sd = np.zeros(nnz, dtype=np.uint32), np.zeros(nnz, dtype=np.uint32), np.zeros(nnz, dtype=np.uint8)
+        self._check(self._lib.oem_builder_export(self.handle, rp.ctypes.data, tid.ctypes.data, p.ctypes.data,
+                                                 s.ctypes.data, e.ctypes.data, sd.ctypes.data))
+        return rp, tid, p, s, e, sd
+
+    def discard_table(self) -> dict:
+        dt = _lib.DiscardTableC()
+        self._check(self._lib.oem_builder_discard_table(self.handle, C.addressof(dt)))
+        return discard_dict(dt)
+
+    # -- coverage model ------------------------------------------------------------------------------------------------
+    def coverage_probs(self, bin_width: int = 100, growth_rate: float = 2.0) -> np.ndarray:
+        out = np.zeros(self.dims()[1], dtype=np.float64)
+        self._check(self._lib.oem_builder_coverage_probs(self.handle, bin_width, growth_rate, out.ctypes.data))
+        return out
+
+    def coverage_probs_binomial(self, bin_width: int = 100) -> np.ndarray:
+        out = np.zeros(self.dims()[1], dtype=np.float64)
+        self._check(self._lib.oem_builder_coverage_probs_binomial(self.handle, bin_width, out.ctypes.data))
+        return out
+
+    def coverage_probs_device(self, bin_width: int = 100, model: str = "logistic", growth_rate: float = 2.0,
+                              device: int = 0) -> np.ndarray:
+        out = np.zeros(self.dims()[1], dtype=np.float64)
+        self._check(self._lib.oem_builder_coverage_probs_device(self.handle, bin_width, _model_code(model), growth_rate,
+                                                                int(device), out.ctypes.data))
+        return out
+
+    # -- upload --------------------------------------------------------------------------------------------------------
+    def device_store(self, coverage: Optional[str] = None, bin_width: int = 100, growth_rate: float = 2.0,
+                     device: int = 0, cov_prob=None, **opts):
+        """The built store on GPU ``device``: ``coverage=None`` -- oem_builder_store_create (with ``cov_prob``, a
+        column computed elsewhere); "logistic" / "binomial" -- oem_builder_store_create_coverage.  ``opts``:
+        reorder_rows, window_cap, layout_build, weight_coding (oem_store_opts)."""
+        from .types import DeviceStore
+        o = store_opts(**opts)
+        h = C.c_void_p()
+        if coverage is None:
+            cov = None if cov_prob is None else np.ascontiguousarray(cov_prob, dtype=np.float64)
+            self._check(self._lib.oem_builder_store_create(self.handle, None if cov is None else cov.ctypes.data,
+                                                           int(device), C.addressof(o), C.byref(h)))
+        else:
+            self._check(self._lib.oem_builder_store_create_coverage(self.handle, bin_width, _model_code(coverage),
+                                                                    growth_rate, int(device), C.addressof(o), None,
+                                                                    C.byref(h)))
+        return DeviceStore._adopt(self._lib, h, len(self.txp_len), int(device))
+
+
+def _model_code(model) -> int:
+    codes = {None: -1, "logistic": 0, "binomial": 1}
+    if model not in codes:
+        raise ValueError(f"coverage model must be None, 'logistic' or 'binomial', not {model!r}")
+    return codes[model]
+
+
+def store_opts(reorder_rows: int = 0, window_cap: int = 0, layout_build: int = 0, weight_coding: int = 0) -> _lib.StoreOptsC:
+    o = _lib.StoreOptsC()
+    o.reorder_rows, o.window_cap, o.layout_build, o.weight_coding = reorder_rows, window_cap, layout_build, weight_coding
+    return o

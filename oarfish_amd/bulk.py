@@ -5,7 +5,9 @@ EMInfo assembly, `em` / `em_par` by thread count (:155-159), aux counts (:161), 
 assignment probabilities -> `.prob` (:196-207).  With a `BulkCoverage`, the driver also runs the coverage
 model of :103-108 (`logistic_prob` + `normalize_read_probs` when `model_coverage` is set) first, on the device
 and in the same call that creates the resident store (`InMemoryAlignmentStore.model_coverage_on_device`).
-Alignment parsing and filtering come before this (oem_builder_* / the caller); KDE is not supported.
+Alignment parsing comes before this (the caller); the filtering is `builder.StoreBuilder` (one read or a batch of
+reads per call, on the host or on the device) or, from the parsed records straight to the resident store in one device
+call, `DeviceStore.from_records` (oem_store_create_records).  KDE is not supported.
 """
 from __future__ import annotations
 

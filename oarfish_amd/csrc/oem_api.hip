@@ -608,6 +608,10 @@ static int create_store_layout(const uint64_t *row_ptr, const uint32_t *tid, con
             row_ptr = resident->host_row_ptr(resident->host_row_ptr_ctx);
             if (!row_ptr) return fail(OEM_ERR_OOM, "host row pointers for the host layout builder: allocation failed");
         }
+        if (!tid && nnz && resident && resident->host_tid) {
+            tid = resident->host_tid(resident->host_row_ptr_ctx);
+            if (!tid) return fail(OEM_ERR_OOM, "host transcript ids for the host layout builder: allocation failed");
+        }
         TiledHost h;
         const char *err = nullptr;
         if (build_tiled_layout(row_ptr, host_tids(), as_prob, cov_prob, n_reads, nnz, m.n_txps, &h, &err,

@@ -4,26 +4,19 @@
 // Reference: AlignmentFilters::filter (src/util/oarfish_types.rs:955-1130) produces, per read, the
 // retained alignments and their conditional probabilities as_prob = expf((score - best) / D) in
 // f32 (:1107-1113); InMemoryAlignmentStore::add_group / add_filtered_group (:672-685, :718-738)
-// append them to the CSR the EM consumes.  This runs once per store on the host; nothing here
-// touches the GPU.  BAM parsing stays out of scope: the caller supplies the record fields the
-// AlnRecordLike trait exposes (:180-202).
+// append them to the CSR the EM consumes.  The per-read rule itself lives in oem_filter.h (shared with
+// the kernels of oem_filter_device.hip, which run it on the device for a batch of reads); this file is
+// its host caller, one read (oem_builder_add_group) or a batch (oem_builder_add_groups) per call.  BAM
+// parsing stays out of scope: the caller supplies the record fields the AlnRecordLike trait exposes
+// (:180-202).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
 
-#include "oem_internal.h"
-
-struct oem_builder {
-    oem_filters f;
-    std::vector<uint64_t> txp_len;
-    std::vector<uint64_t> row_ptr{0};           // boundaries, starts [0] (oarfish_types.rs:645)
-    std::vector<uint32_t> tid, start, end;
-    std::vector<uint8_t> strand;
-    std::vector<float> as_prob;
-    oem_discard_table dt{};
-};
+#include "oem_driver.h"
+#include "oem_filter.h"
 
 using namespace oem;
 
@@ -43,82 +36,116 @@ extern "C" int oem_builder_create(const oem_filters *filters, const uint64_t *tx
 
 extern "C" void oem_builder_destroy(oem_builder *b) { delete b; }
 
+namespace oem {
+
+void add_counts(oem_discard_table &dt, const FilterCounts &c)
+{
+    dt.discard_5p += c.discard_5p;
+    dt.discard_3p += c.discard_3p;
+    dt.discard_score += c.discard_score;
+    dt.discard_aln_frac += c.discard_aln_frac;
+    dt.discard_aln_len += c.discard_aln_len;
+    dt.discard_ori += c.discard_ori;
+    dt.discard_supp += c.discard_supp;
+    dt.valid_best_aln += c.valid_best_aln;
+    dt.no_mapping += c.no_mapping;
+    dt.no_valid_aln += c.no_valid_aln;
+}
+
+// One read through oem_filter.h: the discard table is touched only once no argument error is left (`who` names the
+// entry point, `first` the index of the group's first record in the caller's array).
+static int add_one_group(oem_builder *b, const oem_aln_record *ag, uint32_t n, uint32_t *out_kept, const char *who,
+                         uint64_t first)
+{
+    if (out_kept) *out_kept = 0;
+    const uint32_t T = (uint32_t)b->txp_len.size();
+    FilterCounts c;
+    const FilterGroup g = filter_group_measure(b->f, ag, n, b->txp_len.data(), T, c);
+    if (g.flags & kFilterFlagBadRef) {
+        if (first == ~0ull) return fail(OEM_ERR_ARG, "%s: ref_id %u is not below n_txps", who, ag[g.bad_record].ref_id);
+        return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who,
+                    (unsigned long long)(first + g.bad_record), ag[g.bad_record].ref_id);
+    }
+    add_counts(b->dt, c);
+    if (g.verdict != kGroupValid || g.n_kept == 0) return OEM_OK;
+    const float mscore = (float)g.best;                                                    // :1095
+    const float D = b->f.score_prob_denom;
+    filter_group_emit(b->f, ag, n, b->txp_len.data(), T, g.best, [&](uint32_t, uint32_t, const oem_aln_record &x, uint64_t) {
+        const float fexp = ((float)filter_score_i32(x, 0) - mscore) / D;
+        b->as_prob.push_back(expf(fexp));                                                  // f32 exp (:1113)
+        b->tid.push_back(x.ref_id);                                                        // AlnInfo::from_aln_rec_like (:346-360)
+        b->start.push_back(x.aln_start);
+        b->end.push_back(x.aln_end);
+        b->strand.push_back((x.flags & OEM_REC_REVERSE) ? 1 : 0);
+    });
+    b->row_ptr.push_back(b->tid.size());                                                   // add_filtered_group (:724-735)
+    if (out_kept) *out_kept = g.n_kept;
+    return OEM_OK;
+}
+
+int check_group_off(const char *who, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups)
+{
+    if (!group_off) return fail(OEM_ERR_ARG, "%s: group_off is NULL", who);
+    if (group_off[0] != 0) return fail(OEM_ERR_ARG, "%s: group_off[0] must be 0", who);
+    for (uint64_t g = 0; g < n_groups; ++g) {
+        if (group_off[g + 1] < group_off[g]) return fail(OEM_ERR_ARG, "%s: group_off decreases at group %llu", who, (unsigned long long)g);
+        if (group_off[g + 1] - group_off[g] > 0xffffffffull)
+            return fail(OEM_ERR_ARG, "%s: group %llu has more than 2^32 - 1 records", who, (unsigned long long)g);
+    }
+    if (group_off[n_groups] && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+    return OEM_OK;
+}
+
+BuilderMark builder_mark(const oem_builder *b) { return BuilderMark{b->row_ptr.size(), b->tid.size(), b->dt}; }
+
+void builder_rollback(oem_builder *b, const BuilderMark &m)
+{
+    b->row_ptr.resize(m.n_row_ptr);
+    b->tid.resize(m.nnz);
+    b->as_prob.resize(m.nnz);
+    b->start.resize(m.nnz);
+    b->end.resize(m.nnz);
+    b->strand.resize(m.nnz);
+    b->dt = m.dt;
+}
+
+// The host loop of a batch: atomic (the builder is rolled back on any error, allocation failures included).
+int add_groups_host(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
+                    uint32_t *out_kept, const char *who)
+{
+    const BuilderMark mark = builder_mark(b);
+    int rc = OEM_OK;
+    try {
+        for (uint64_t g = 0; g < n_groups && rc == OEM_OK; ++g)
+            rc = add_one_group(b, records + group_off[g], (uint32_t)(group_off[g + 1] - group_off[g]),
+                               out_kept ? out_kept + g : nullptr, who, group_off[g]);
+    } catch (...) {
+        builder_rollback(b, mark);
+        throw;
+    }
+    if (rc != OEM_OK) builder_rollback(b, mark);
+    return rc;
+}
+
+} // namespace oem
+
 extern "C" int oem_builder_add_group(oem_builder *b, const oem_aln_record *ag, uint32_t n, uint32_t *out_kept)
 {
     OEM_API_BEGIN
     if (!b || (n && !ag)) return fail(OEM_ERR_ARG, "oem_builder_add_group: NULL argument");
-    if (out_kept) *out_kept = 0;
-    if (n == 0) return OEM_OK;                                    // add_group: `if !ag.is_empty()` (:677)
-    for (uint32_t i = 0; i < n; ++i)   // every argument error is reported before the discard table is touched
-        if (!(ag[i].flags & OEM_REC_UNMAPPED) && ag[i].ref_id >= b->txp_len.size())
-            return fail(OEM_ERR_ARG, "oem_builder_add_group: ref_id %u is not below n_txps", ag[i].ref_id);
-    const oem_filters &F = b->f;
-    oem_discard_table &dt = b->dt;
-
-    int32_t best_retained_score = INT32_MIN;                      // :963
-    float aln_frac_at_best_retained = 0.f;                        // :966
-    uint32_t aln_len_at_best_retained = 0;                        // :969
-    uint64_t n_mapped_in = 0;                                     // :974
-    for (uint32_t i = 0; i < n; ++i) n_mapped_in += !(ag[i].flags & OEM_REC_UNMAPPED);
-    uint32_t seq_len = 0;                                         // :979-982: first record that has a length
-    for (uint32_t i = 0; i < n; ++i)
-        if (ag[i].seq_len >= 0) { seq_len = (uint32_t)ag[i].seq_len; break; }
-
-    std::vector<uint32_t> kept;                                   // ag.retain (:985-1069)
-    kept.reserve(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const oem_aln_record &x = ag[i];
-        if (x.flags & OEM_REC_UNMAPPED) continue;                 // :987
-        const uint32_t aln_span = x.aln_span;                     // :991
-        const int32_t score = (x.flags & OEM_REC_HAS_SCORE) ? (int32_t)x.score : INT32_MIN; // :994
-        const bool is_rc = x.flags & OEM_REC_REVERSE;             // :997
-        if (F.which_strand == 2 && !is_rc) { dt.discard_ori += 1; continue; }              // :1008-1011
-        if (F.which_strand == 1 && is_rc) { dt.discard_ori += 1; continue; }               // :1013-1016
-        if (x.flags & OEM_REC_SUPPLEMENTARY) { dt.discard_supp += 1; continue; }           // :1022-1026
-        if (aln_span < F.min_aligned_len) { dt.discard_aln_len += 1; continue; }           // :1029-1033
-        if ((int64_t)x.aln_end <= (int64_t)b->txp_len[x.ref_id] - F.three_prime_clip) {    // :1036-1041
-            dt.discard_3p += 1;
-            continue;
-        }
-        if (x.aln_start >= F.five_prime_clip) { dt.discard_5p += 1; continue; }            // :1044-1048
-        if (score > best_retained_score) {                        // :1053-1063
-            best_retained_score = score;
-            aln_len_at_best_retained = aln_span;
-            aln_frac_at_best_retained = seq_len > 0 ? (float)aln_span / (float)seq_len : 0.f;
-        }
-        kept.push_back(i);
-    }
-    if (kept.empty() || aln_len_at_best_retained == 0 || best_retained_score <= 0) {       // :1071-1083
-        if (n_mapped_in == 0) dt.no_mapping += 1;
-        else dt.no_valid_aln += 1;
-        return OEM_OK;
-    }
-    if (aln_frac_at_best_retained < F.min_aligned_fraction) {     // :1084-1089
-        dt.discard_aln_frac += 1;
-        return OEM_OK;
-    }
-    dt.valid_best_aln += 1;                                       // :1092
-    const float mscore = (float)best_retained_score;              // :1095
-    const float inv_max_score = 1.0f / mscore;                    // :1096
-    uint32_t n_kept = 0;
-    for (uint32_t i : kept) {                                     // :1107-1118
-        const oem_aln_record &x = ag[i];
-        const int32_t sc = (x.flags & OEM_REC_HAS_SCORE) ? (int32_t)x.score : 0; // unwrap_or(0) (:1102)
-        const float fscore = (float)sc;
-        const bool score_ok = (fscore * inv_max_score) >= F.score_threshold;
-        if (!score_ok) { dt.discard_score += 1; continue; }
-        const float fexp = (fscore - mscore) / F.score_prob_denom;
-        b->as_prob.push_back(expf(fexp));                         // f32 exp (:1113)
-        b->tid.push_back(x.ref_id);                               // AlnInfo::from_aln_rec_like (:346-360)
-        b->start.push_back(x.aln_start);
-        b->end.push_back(x.aln_end);
-        b->strand.push_back((x.flags & OEM_REC_REVERSE) ? 1 : 0);
-        ++n_kept;
-    }
-    if (n_kept) b->row_ptr.push_back(b->tid.size());              // add_filtered_group (:724-735)
-    if (out_kept) *out_kept = n_kept;
-    return OEM_OK;
+    return add_one_group(b, ag, n, out_kept, "oem_builder_add_group", ~0ull);
     OEM_API_END("oem_builder_add_group")
+}
+
+extern "C" int oem_builder_add_groups(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off,
+                                      uint64_t n_groups, uint32_t *out_kept)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_builder_add_groups";
+    if (!b) return fail(OEM_ERR_ARG, "%s: builder is NULL", who);
+    OEM_TRY(check_group_off(who, records, group_off, n_groups));
+    return add_groups_host(b, records, group_off, n_groups, out_kept, who);
+    OEM_API_END("oem_builder_add_groups")
 }
 
 extern "C" int oem_builder_dims(const oem_builder *b, uint64_t *n_reads, uint64_t *nnz)

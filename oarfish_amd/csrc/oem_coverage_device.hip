@@ -227,6 +227,16 @@ int check_coverage_store_args(const char *who, const uint64_t *row_ptr, const ui
 }
 
 } // namespace
+
+int coverage_resident(const uint32_t *d_row_ptr, const uint32_t *d_tid, const uint32_t *d_start, const uint32_t *d_end,
+                      const uint64_t *d_txp_len, uint64_t n_reads, uint64_t nnz, uint32_t n_txps, uint32_t bin_width,
+                      int model, double growth_rate, double *d_out, const float *d_p, double *d_w64, float *d_w32)
+{
+    StageTimer tm;
+    return coverage_body(d_row_ptr, d_tid, d_start, d_end, d_txp_len, n_reads, nnz, n_txps, bin_width, model, growth_rate,
+                         d_out, CovWeights{d_p, d_w64, d_w32}, &tm);
+}
+
 } // namespace oem
 
 using namespace oem;

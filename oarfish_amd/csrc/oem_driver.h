@@ -10,6 +10,17 @@
 
 #include "oem_internal.h"
 
+// The host-side store builder (oem_builder.cpp); the batch entry points of oem_filter_device.hip append to it.
+struct oem_builder {
+    oem_filters f;
+    std::vector<uint64_t> txp_len;
+    std::vector<uint64_t> row_ptr{0};           // boundaries, starts [0] (oarfish_types.rs:645)
+    std::vector<uint32_t> tid, start, end;
+    std::vector<uint8_t> strand;
+    std::vector<float> as_prob;
+    oem_discard_table dt{};
+};
+
 namespace oem {
 
 const char *last_error_text(); // this thread's message (oem_last_error)
@@ -83,6 +94,8 @@ struct ResidentCsr {
     // the stores the device builder declines, asks for one here (NULL: allocation failed)
     const uint64_t *(*host_row_ptr)(void *) = nullptr;
     void *host_row_ptr_ctx = nullptr;
+    // ... and, where the transcript ids have no host copy either (create_store_impl is given a NULL tid), for those
+    const uint32_t *(*host_tid)(void *) = nullptr;
     ResidentCsr() = default;
     ResidentCsr(const ResidentCsr &) = delete;
     ResidentCsr &operator=(const ResidentCsr &) = delete;
@@ -296,5 +309,31 @@ int lz4_chunk_enqueue(Lz4Chunk &c, const uint8_t *d_in, uint64_t n, uint32_t blo
 // One complete frame (descriptor, blocks, EndMark) of n host bytes, through the same three steps; synchronises `st`.
 int lz4_frame_from_host(const uint8_t *data, uint64_t n, hipStream_t st, std::unique_ptr<uint8_t[]> *out, uint64_t *out_len,
                         uint64_t *n_blocks, uint64_t *raw_blocks);
+
+// oem_coverage_device.hip: the bulk coverage model on arrays already on the device (u32 row pointers, ids, coordinates,
+// transcript lengths): the column into d_out and, with d_p, the store's weights w = (double)p * cov into d_w64 or,
+// rounded once to f32, into d_w32 (exactly one of the two is set).
+int coverage_resident(const uint32_t *d_row_ptr, const uint32_t *d_tid, const uint32_t *d_start, const uint32_t *d_end,
+                      const uint64_t *d_txp_len, uint64_t n_reads, uint64_t nnz, uint32_t n_txps, uint32_t bin_width,
+                      int model, double growth_rate, double *d_out, const float *d_p, double *d_w64, float *d_w32);
+
+// oem_builder.cpp: what a batch call needs of the builder.  A mark taken before a batch restores the builder when the
+// batch fails (builder_rollback), which is what makes the batch calls atomic.
+struct BuilderMark {
+    size_t n_row_ptr, nnz;
+    oem_discard_table dt;
+};
+BuilderMark builder_mark(const oem_builder *b);
+void builder_rollback(oem_builder *b, const BuilderMark &m);
+int check_group_off(const char *who, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups);
+int add_groups_host(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
+                    uint32_t *out_kept, const char *who);
+
+// oem_filter_device.hip: times of this thread's last device batch call under OEM_FILTER_TIMING=1 (test-only library; all
+// zero when the call never reached the device pass): from HIP events, ms of the record uploads (sum over the chunks), of
+// k_filter_measure (sum), of the two scans, of k_filter_emit, and the fraction of the measure kernels' time during which
+// a record copy was in flight; from the host clock, ms the calling thread spent copying the records into pinned staging
+void filter_last_timing(float *ms6);
+void filter_timing_reset();
 
 } // namespace oem

@@ -129,6 +129,17 @@ extern "C" int oem_debug_text_lz4_last_timing(float *out)
     return OEM_OK;
 }
 
+// out[0..5] = this thread's last device batch call (oem_builder_add_groups_device, oem_store_create_records) under
+// OEM_FILTER_TIMING=1: from HIP events, ms of the record uploads, k_filter_measure (both summed over the chunks), the two
+// scans, k_filter_emit, and the fraction of the measure kernels' time during which a record copy was in flight; from the
+// host clock, ms of the copies into pinned staging.  All zero when the host loop took the batch without a device pass.
+extern "C" int oem_debug_filter_last_timing(float *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_filter_last_timing: NULL argument");
+    filter_last_timing(out);
+    return OEM_OK;
+}
+
 // Test hook: the n caller bytes at `data` as one LZ4 frame, by the path oem_assignment_text_lz4 compresses a chunk with
 // (upload, k_lz4_blocks, scan, k_lz4_gather; blocks of OEM_LZ4_BLOCK_BYTES), so that tests can feed crafted inputs.
 // *out_len = the frame's length, always; the frame is copied to out when it fits cap (else OEM_ERR_ARG).

@@ -284,6 +284,138 @@ def make_coordinates(tid, n_txps: int, seed: int = BASE_SEED + 9, zero_span_frac
     return txp_len, start, end
 
 
+@dataclass
+class SyntheticRecords:
+    filters: dict                # the fields of oem_filters the records were made for
+    txp_len: np.ndarray          # u64 [T]
+    records: np.ndarray          # builder.ALN_RECORD [n_records]
+    group_off: np.ndarray        # u64 [n_groups + 1]
+    kept: np.ndarray             # u32 [n_groups]: what the filter keeps of each group
+    discard: dict                # the discard table the filter ends with
+
+
+def make_records(store: SyntheticStore, seed: int = BASE_SEED + 21, decoy_rate: float = 0.3, drop_frac: float = 0.05,
+                 score_prob_denom: float = 5.0) -> SyntheticRecords:
+    """A synthetic store turned back into the alignment records it could have come from, so that
+    AlignmentFilters::filter (oarfish_types.rs:955-1130) over the records gives the store again: the same reads in the
+    same order, the same transcripts and the same score gaps (``as_prob`` is then libm's expf of the gap, which can
+    differ in the last bit from the numpy exp the synthetic store was made with).
+
+    Each kept alignment gets the integer score ``best - g`` that reproduces its ``as_prob = expf(-g / D)`` (g =
+    round(-D ln p): the store's probabilities are exp of an integer gap over D, and every read has a g = 0 alignment),
+    with the read's best score high enough that ``score / best >= 0.95`` holds with room to spare.  Coordinates are drawn
+    inside the transcripts (lengths uniform on [400, 6000)) so that the 5' clip (2000) and the 3' clip (3000) keep them,
+    and are usable for the coverage model.  On top of that the generator adds, per read, Poisson(``decoy_rate``) DECOY
+    records, each rejected by exactly one filter (orientation, supplementary, aligned length, 3' clip, 5' clip in the
+    first walk -- these carry a score above the read's best, which they must not become -- or the score threshold in the
+    second), before or after the read's real records; and whole reads that are dropped (``drop_frac`` of the groups:
+    unmapped records only, a non-positive best score, or a best alignment that covers too little of the read).
+    ``kept`` and ``discard`` are what the filter must report.  A pure function of (store, seed, rates, D)."""
+    from .builder import ALN_RECORD, REC_HAS_SCORE, REC_REVERSE, REC_SUPPLEMENTARY, REC_UNMAPPED
+    F5, F3 = 2000, 3000
+    filters = dict(five_prime_clip=F5, three_prime_clip=F3, score_threshold=0.95, min_aligned_fraction=0.5,
+                   min_aligned_len=50, which_strand=1, score_prob_denom=float(score_prob_denom))
+    rng = np.random.default_rng([seed, 0xF117E4])
+    R, T, nnz = store.n_reads, store.n_txps, store.nnz
+    rp = store.row_ptr.astype(np.int64)
+    lens = np.diff(rp)
+    if R and lens.min() < 1:
+        raise ValueError("make_records needs a store without empty reads")
+    txp_len = rng.integers(400, 6000, size=T).astype(np.uint64)
+    gap = np.rint(-float(score_prob_denom) * np.log(store.as_prob.astype(np.float64))).astype(np.int64)
+    first = rp[:-1]
+    if R:
+        if np.minimum.reduceat(gap, first).max() != 0:
+            raise ValueError("make_records needs a read's best alignment to have as_prob 1")
+        gmax = np.maximum.reduceat(gap, first)
+    else:
+        gmax = np.zeros(0, dtype=np.int64)
+    best = 20 * gmax + rng.integers(1000, 3000, size=R)
+    read_of = np.repeat(np.arange(R, dtype=np.int64), lens)
+    # coordinates of the real alignments: start < min(L - 100, F5), end in (max(start + 100, L - F3), L]
+    L = txp_len[store.tid].astype(np.int64)
+    start = (rng.random(nnz) * np.minimum(L - 100, F5)).astype(np.int64)
+    lo = np.maximum(start + 100, L - F3 + 1)
+    end = np.minimum(lo + (rng.random(nnz) * (L - lo + 1)).astype(np.int64), L)
+    span = end - start
+    # the read's length: the first best alignment covers more than half of it
+    is_best = np.flatnonzero(gap == 0)
+    _, where = np.unique(read_of[is_best], return_index=True)
+    span_best = span[is_best[where]] if R else np.zeros(0, dtype=np.int64)
+    seq_len = span_best + (rng.random(R) * span_best).astype(np.int64)
+    seq_len = np.minimum(seq_len, 2 * span_best - 1)
+
+    # groups: the R reads in order, with dropped reads scattered between them
+    n_drop = int(round(R * drop_frac / max(1e-9, 1.0 - drop_frac))) if R else 0
+    G = R + n_drop
+    is_real = np.ones(G, dtype=bool)
+    if n_drop:
+        is_real[rng.choice(G, size=n_drop, replace=False)] = False
+    drop_kind = rng.integers(0, 3, size=n_drop)
+    nd = rng.poisson(decoy_rate, size=R).astype(np.int64)
+    nf = rng.binomial(nd, 0.5).astype(np.int64)                        # decoys in front of the real records
+    n_rec = np.zeros(G, dtype=np.int64)
+    n_rec[is_real] = lens + nd
+    n_rec[~is_real] = np.where(drop_kind == 0, 2, 1)
+    group_off = np.zeros(G + 1, dtype=np.uint64)
+    np.cumsum(n_rec, out=group_off[1:])
+    base_real = group_off[:-1][is_real].astype(np.int64)
+    base_drop = group_off[:-1][~is_real].astype(np.int64)
+    rec = np.zeros(int(group_off[-1]), dtype=ALN_RECORD)
+    rec["seq_len"] = -1
+
+    # the real records
+    pos = np.repeat(base_real + nf, lens) + (np.arange(nnz, dtype=np.int64) - np.repeat(first, lens))
+    rec["ref_id"][pos] = store.tid
+    rec["aln_start"][pos] = start
+    rec["aln_end"][pos] = end
+    rec["aln_span"][pos] = span
+    rec["score"][pos] = best[read_of] - gap
+    rec["seq_len"][pos] = seq_len[read_of]
+    rec["flags"][pos] = REC_HAS_SCORE
+
+    # the decoys: kind 0 orientation, 1 supplementary, 2 aligned length, 3 3' clip, 4 5' clip, 5 score threshold
+    n_dec = int(nd.sum())
+    d_read = np.repeat(np.arange(R, dtype=np.int64), nd)
+    q = np.arange(n_dec, dtype=np.int64) - np.repeat(np.cumsum(nd) - nd, nd)
+    d_pos = base_real[d_read] + np.where(q < nf[d_read], q, lens[d_read] + q)
+    d_tid = rng.integers(0, T, size=n_dec)
+    d_L = txp_len[d_tid].astype(np.int64)
+    kind = rng.integers(0, 6, size=n_dec)
+    kind = np.where((kind == 3) & (d_L < F3), 1, kind)                 # (no 3' decoy on a transcript shorter than the clip)
+    rec["ref_id"][d_pos] = d_tid
+    rec["aln_start"][d_pos] = np.where(kind == 4, F5, 0)
+    rec["aln_end"][d_pos] = np.where(kind == 3, d_L - F3, d_L)
+    rec["aln_span"][d_pos] = np.where(kind == 2, 10, 100)
+    rec["score"][d_pos] = np.where(kind == 5, best[d_read] * 9 // 10, best[d_read] + 50)
+    rec["seq_len"][d_pos] = seq_len[d_read]
+    rec["flags"][d_pos] = REC_HAS_SCORE | np.where(kind == 0, REC_REVERSE, 0) | np.where(kind == 1, REC_SUPPLEMENTARY, 0)
+
+    # the dropped reads: 0 = two unmapped records (their ref_id is never looked at), 1 = best score 0, 2 = the best
+    # alignment covers a tenth of the read
+    for k in range(3):
+        b = base_drop[drop_kind == k]
+        if k == 0:
+            for j in (0, 1):
+                rec["ref_id"][b + j] = 0xFFFFFFFF
+                rec["flags"][b + j] = REC_UNMAPPED
+        else:
+            t = rng.integers(0, T, size=len(b))
+            rec["ref_id"][b] = t
+            rec["aln_end"][b] = txp_len[t]
+            rec["aln_span"][b] = 100
+            rec["score"][b] = 0 if k == 1 else 1000
+            rec["seq_len"][b] = 100 if k == 1 else 1000
+            rec["flags"][b] = REC_HAS_SCORE
+    kept = np.zeros(G, dtype=np.uint32)
+    kept[is_real] = lens
+    discard = dict(discard_5p=int((kind == 4).sum()), discard_3p=int((kind == 3).sum()), discard_score=int((kind == 5).sum()),
+                   discard_aln_frac=int((drop_kind == 2).sum()), discard_aln_len=int((kind == 2).sum()),
+                   discard_ori=int((kind == 0).sum()), discard_supp=int((kind == 1).sum()), valid_best_aln=R,
+                   no_mapping=int((drop_kind == 0).sum()), no_valid_aln=int((drop_kind == 1).sum()))
+    return SyntheticRecords(filters, txp_len, rec, group_off, kept, discard)
+
+
 def cell_shift(rep: int, n_txps: int) -> int:
     """Transcript-id rotation of replica ``rep`` of a cell in ``replicate_cells``."""
     return (rep * 7919) % n_txps

@@ -158,6 +158,50 @@ class DeviceStore:
             C.addressof(opts), cov.ctypes.data if cov is not None and nz else None, C.byref(self._h)))
         return (self, cov) if return_coverage else self
 
+    @classmethod
+    def _adopt(cls, L, handle, n_txps: int, device: int) -> "DeviceStore":
+        """A DeviceStore around a handle the library has just returned (the CSR has no host copy: ``row_ptr`` is None)."""
+        self = cls.__new__(cls)
+        self._h = handle
+        self._lib = L
+        self.row_ptr = None
+        self.n_txps = int(n_txps)
+        self.device = int(device)
+        R, nnz, T = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self._check(L.oem_store_dims(handle, C.byref(R), C.byref(nnz), C.byref(T)))
+        self.n_reads, self.nnz = int(R.value), int(nnz.value)
+        return self
+
+    @classmethod
+    def from_records(cls, filters, txp_len, records, group_off, coverage: Optional[str] = None, bin_width: int = 100,
+                     growth_rate: float = 2.0, device: int = 0, reorder_rows: int = 0, window_cap: int = 0,
+                     layout_build: int = 0, weight_coding: int = 0):
+        """Alignment records -> resident store in one device call (oem_store_create_records): the filter cascade of
+        AlignmentFilters::filter runs on the GPU and the CSR never exists on the host.  ``records`` / ``group_off`` as in
+        ``builder.StoreBuilder.add_groups``; ``coverage``: None, "logistic" or "binomial".  Returns
+        ``(store, kept, discard_table)``: ``kept[g]`` alignments of group g were kept, read r of the store is the r-th
+        group with ``kept > 0`` (pick the read names for ``assignment_text`` with it), and the discard table is a dict
+        with DiscardTable's counters.  The store is the one ``StoreBuilder(...).add_groups(...)`` followed by
+        ``device_store(coverage, ...)`` gives."""
+        from . import builder as _b
+        fc = _b.filters_c(filters)
+        txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        records, group_off = _b.check_batch(records, group_off)
+        n_groups = len(group_off) - 1
+        kept = np.zeros(n_groups, dtype=np.uint32)
+        dt = _lib.DiscardTableC()
+        o = _b.store_opts(reorder_rows, window_cap, layout_build, weight_coding)
+        L = _lib.lib()
+        h = C.c_void_p()
+        rc = L.oem_store_create_records(C.addressof(fc), txp_len.ctypes.data, len(txp_len),
+                                        records.ctypes.data if len(records) else None, group_off.ctypes.data, n_groups,
+                                        bin_width, _b._model_code(coverage), growth_rate, int(device), C.addressof(o),
+                                        kept.ctypes.data, C.addressof(dt), C.byref(h))
+        if rc != _lib.OEM_OK:
+            msg = L.oem_last_error()
+            raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
+        return cls._adopt(L, h, len(txp_len), device), kept, _b.discard_dict(dt)
+
     def _check(self, rc: int) -> None:
         if rc != _lib.OEM_OK:
             msg = self._lib.oem_last_error()
