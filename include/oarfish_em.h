@@ -44,7 +44,8 @@ extern "C" {
  *    the `.prob` body as text formatted on the device (oem_assignment_text, oem_text_result_dims / _copy / _destroy),
  *    the whole `.prob.lz4` file as one LZ4 frame compressed on the device (oem_assignment_text_lz4,
  *    oem_text_result_info), the batched filter on the host and on the device and the store straight from the records
- *    (oem_builder_add_groups, oem_builder_add_groups_device, oem_store_create_records). */
+ *    (oem_builder_add_groups, oem_builder_add_groups_device, oem_store_create_records), the `.count.mtx` file of the
+ *    single-cell path as text formatted on the device (oem_count_matrix_text). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -426,6 +427,28 @@ int oem_assignment_text_lz4(oem_store *store, const double *counts, double displ
 #define OEM_TEXT_INFO_BLOCKS 2u        /* blocks of the frame */
 #define OEM_TEXT_INFO_RAW_BLOCKS 3u    /* ... of which stored uncompressed */
 int oem_text_result_info(const oem_text_result *r, uint32_t key, uint64_t *value);
+
+/* The `.count.mtx` file of the single-cell path (write_function.rs:53-54, through sprs::io::write_matrix_market):
+ * `prefix` followed by one line per entry of the cells x transcripts matrix, in CSR order,
+ *     "{row_base + cell + 1} {col + 1} {val}\n"
+ * rows and columns 1-based, the f32 value as Rust's `{}` prints it: the shortest digits that read back as the same
+ * f32, positional notation, no trailing ".0" (`1`, `0.1`, `16777216`, 1e30 as `1` and thirty zeros).  The matrix is the
+ * CSR that oem_em_run_cells_sparse and the session return: cell_off has n_cells + 1 offsets (cell_off[0] = 0, never
+ * decreasing; empty cells are fine), col / val have cell_off[n_cells] entries, every col is below n_txps.  prefix
+ * carries the Matrix Market banner and the dimension line, so the result's text / n_bytes (oem_text_result_dims,
+ * _copy) are the finished file; prefix == NULL requires prefix_len == 0.  row_base lets a rank that owns the cells
+ * [row_base, row_base + n_cells) of a larger matrix produce its share of the body; row_base + n_cells may not exceed
+ * 2^32 - 1.
+ * The result: n_lines = n_kept = the number of entries, line_off the n_lines + 1 byte offsets of the lines into the body
+ * (after the prefix), kept one per line; oem_text_result_info answers as for oem_assignment_text (CONTENT_BYTES =
+ * n_bytes, 0 blocks).  No store is involved: the entries go up in chunks (8 B each), the text comes back; `device`
+ * is the ordinal to run on.  All argument errors are reported before any device use, and *out is NULL after any
+ * failure; without a device the call returns OEM_ERR_NO_DEVICE (there is no host fallback). */
+int oem_count_matrix_text(const uint64_t *cell_off, uint32_t n_cells,
+                          const uint32_t *col, const float *val,
+                          uint32_t n_txps, uint32_t row_base,
+                          const uint8_t *prefix, uint64_t prefix_len,
+                          int device, oem_text_result **out);
 
 /* --------------------------------------------------------------------- */
 /* bootstrap                                                              */

@@ -57,7 +57,7 @@ ABI_SYMBOLS = [
     "oem_builder_store_create", "oem_store_create_coverage", "oem_builder_store_create_coverage",
     "oem_m_step", "oem_em_run", "oem_run_history", "oem_aux_counts", "oem_assignment_probs",
     "oem_assignment_text", "oem_text_result_dims", "oem_text_result_copy", "oem_text_result_destroy",
-    "oem_assignment_text_lz4", "oem_text_result_info",
+    "oem_assignment_text_lz4", "oem_text_result_info", "oem_count_matrix_text",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
@@ -179,6 +179,7 @@ def _load(path: str) -> C.CDLL:
     L.oem_text_result_destroy.restype = None
     L.oem_assignment_text_lz4.argtypes = [vp, vp, f64, vp, vp, vp, u64, C.POINTER(vp)]
     L.oem_text_result_info.argtypes = [vp, u32, C.POINTER(u64)]
+    L.oem_count_matrix_text.argtypes = [vp, u32, vp, vp, u32, u32, vp, u64, i32, C.POINTER(vp)]
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]
     L.oem_bootstrap.argtypes = [vp, u32, u64, vp, vp, u32, f64, vp, vp]
     L.oem_em_run_cells.argtypes = [vp, u32, vp, vp, vp, vp, u64, u64, u32, i32, u32, f64, vp, vp]
@@ -241,6 +242,7 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_text_lz4_last_timing.argtypes = [vp]
         L.oem_test_lz4_frame.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
         L.oem_debug_filter_last_timing.argtypes = [vp]
+        L.oem_debug_mtx_last_timing.argtypes = [vp]
         _testing = L
     return _testing
 

@@ -25,17 +25,6 @@
 #include "oem_lz4.h"
 #include "oem_text_format.h"
 
-struct oem_text_result {
-    uint64_t n_bytes = 0;
-    uint64_t n_lines = 0;
-    uint64_t n_kept = 0;
-    // oem_assignment_text_lz4: text is one LZ4 frame of content_bytes (prefix + body) in n_blocks blocks
-    uint64_t content_bytes = 0, n_blocks = 0, raw_blocks = 0;
-    std::unique_ptr<uint8_t[]> text;  // n_bytes
-    std::vector<uint64_t> line_off;   // n_lines + 1
-    std::vector<uint32_t> kept;       // n_lines
-};
-
 namespace oem {
 namespace {
 

@@ -21,6 +21,19 @@ struct oem_builder {
     oem_discard_table dt{};
 };
 
+// What oem_assignment_text, oem_assignment_text_lz4 (oem_assignment_text.hip) and oem_count_matrix_text
+// (oem_count_matrix_text.hip) return; read through oem_text_result_dims / _copy / _info.
+struct oem_text_result {
+    uint64_t n_bytes = 0;
+    uint64_t n_lines = 0;
+    uint64_t n_kept = 0;
+    // oem_assignment_text_lz4: text is one LZ4 frame of content_bytes (prefix + body) in n_blocks blocks
+    uint64_t content_bytes = 0, n_blocks = 0, raw_blocks = 0;
+    std::unique_ptr<uint8_t[]> text;  // n_bytes
+    std::vector<uint64_t> line_off;   // n_lines + 1
+    std::vector<uint32_t> kept;       // n_lines
+};
+
 namespace oem {
 
 const char *last_error_text(); // this thread's message (oem_last_error)
@@ -278,6 +291,8 @@ const std::vector<CellsGroupPath> &cells_last_paths();
 void text_last_timing(float *ms3);
 // ... and of this thread's last oem_assignment_text_lz4: ms of k_lz4_blocks and of scan + k_lz4_gather (all chunks)
 void text_lz4_last_timing(float *ms2);
+// oem_count_matrix_text.hip: the same three of this thread's last oem_count_matrix_text under OEM_MTX_TIMING=1
+void mtx_last_timing(float *ms3);
 
 // oem_lz4.hip: the device buffers the compression of one chunk owns; reused by the chunks that follow it on its stream
 struct Lz4Chunk {

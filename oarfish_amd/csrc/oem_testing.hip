@@ -120,6 +120,14 @@ extern "C" int oem_debug_text_last_timing(float *out)
     return OEM_OK;
 }
 
+// out[0..2] = kernel ms of this thread's last oem_count_matrix_text under OEM_MTX_TIMING=1: measure, scan, emit (all chunks)
+extern "C" int oem_debug_mtx_last_timing(float *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_mtx_last_timing: NULL argument");
+    mtx_last_timing(out);
+    return OEM_OK;
+}
+
 // out[0..1] = kernel ms of this thread's last oem_assignment_text_lz4 under OEM_TEXT_TIMING=1: k_lz4_blocks, scan +
 // k_lz4_gather (all chunks); its measure / scan / emit are in oem_debug_text_last_timing
 extern "C" int oem_debug_text_lz4_last_timing(float *out)

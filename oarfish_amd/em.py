@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .types import EMInfo, RunInfo
+from .types import AssignmentText, EMInfo, RunInfo
 
 
 def _require_no_kde(em_info: EMInfo):
@@ -183,6 +183,45 @@ def _take_cells_result(res, n_cells, L=None):
         L.oem_cells_result_destroy(res)
     return indptr, cols, vals, [RunInfo(i.niter, i.n_passes, bool(i.converged), i.rel_diff)
                                 for i in list(infos)[:n_cells]]
+
+
+def count_matrix_text(indptr, cols, vals, n_txps: int, row_base: int = 0, prefix: bytes = b"", device: int = 0,
+                      offsets: bool = True) -> AssignmentText:
+    """write_function.rs:53-54: the `.count.mtx` text of the cells x transcripts matrix, formatted on the device
+    (oem_count_matrix_text).  ``indptr, cols, vals`` is the CSR that ``em_cells_sparse``, ``em_cells_coverage_sparse``
+    and ``CellsStream.finish`` return.  ``text`` is ``prefix`` (the banner and the dimension line) followed by one line
+    ``"{row_base + cell + 1} {col + 1} {val}\n"`` per entry, the value as Rust's ``{}`` prints an f32 -- byte for byte
+    what ``writers.write_single_cell_output`` writes for ``writers.csr_triplets(indptr, cols, vals)``.  ``line_off``:
+    the byte offsets of the lines into the body (after the prefix); ``kept``: one per line.  ``offsets=False`` leaves
+    those two ``None`` (a writer needs the text alone)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    vals = np.ascontiguousarray(vals, dtype=np.float32)
+    if len(indptr) < 1:
+        raise ValueError("indptr needs n_cells + 1 offsets")
+    n_cells = len(indptr) - 1
+    if len(cols) != len(vals) or int(indptr[-1]) != len(cols):
+        raise ValueError("cols and vals must hold indptr[-1] entries each")
+    prefix = bytes(prefix)
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.oem_count_matrix_text(indptr.ctypes.data, n_cells, cols.ctypes.data if len(cols) else None,
+                                       vals.ctypes.data if len(vals) else None, n_txps, row_base,
+                                       prefix if prefix else None, len(prefix), device, C.byref(h)))
+    try:
+        nb, nl = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(L.oem_text_result_dims(h, C.byref(nb), C.byref(nl), None))
+        text = np.empty(nb.value, dtype=np.uint8)
+        line_off = np.empty(nl.value + 1, dtype=np.uint64) if offsets else None
+        kept = np.empty(nl.value, dtype=np.uint32) if offsets else None
+        _lib.check(L.oem_text_result_copy(h, text.ctypes.data if nb.value else None,
+                                          line_off.ctypes.data if offsets else None,
+                                          kept.ctypes.data if offsets and nl.value else None))
+        res = AssignmentText(text, line_off, kept)
+        res.content_bytes = int(nb.value)
+    finally:
+        L.oem_text_result_destroy(h)
+    return res
 
 
 _COVERAGE_MODELS = {"logistic": 0, "binomial": 1}

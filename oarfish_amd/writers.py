@@ -14,6 +14,7 @@ Host-side formatting only; every number written here comes out of the device eng
                              level 4 -- so it is larger than the reference's and every LZ4 frame decoder reads it
   write_single_cell_output   write_function.rs:25-69    <out>.count.mtx, .features.txt (+ .barcodes.txt,
                              single_cell.rs:176-178)
+  write_single_cell_output_device  the same files, the matrix lines formatted on the device (em.count_matrix_text)
 
 Numbers are printed the way Rust's `{}` prints them (shortest digits that round-trip, never an
 exponent, no trailing ".0" -- `rust_display`), so a `.quant` written here is byte-identical to the
@@ -166,20 +167,16 @@ def csr_triplets(indptr, cols, vals) -> tuple:
     return rows, np.asarray(cols, dtype=np.uint32), np.asarray(vals, dtype=np.float32)
 
 
-def write_single_cell_output(output: str, info: dict, feature_names: Sequence[str], barcodes: Optional[Sequence[str]],
-                             n_cells: int, row_ids, col_ids, vals) -> None:
-    """write_function.rs:25-69: `.meta_info.json`, `.count.mtx` (MatrixMarket coordinate real
-    general, 1-based, f32 values in triplet order as sprs::io::write_matrix_market emits them) and
-    `.features.txt`; `.barcodes.txt` in row order (single_cell.rs:176-178).  The triplets come from
-    `cell_triplets(dense)` or `csr_triplets(*em_cells_sparse(...)[:3])`."""
+_MTX_BANNER = "%%MatrixMarket matrix coordinate real general\n% written by sprs\n"
+
+
+def _write_single_cell_side_files(output: str, info: dict, feature_names: Sequence[str],
+                                  barcodes: Optional[Sequence[str]]) -> None:
+    """What a single-cell run writes besides the matrix: `.meta_info.json`, `.features.txt` and, in row order,
+    `.barcodes.txt` (write_function.rs:25-69, single_cell.rs:176-178)."""
     _make_parent(output)
     with open(with_additional_extension(output, ".meta_info.json"), "w") as fh:
         json.dump(info, fh, indent=2)
-    with open(with_additional_extension(output, ".count.mtx"), "w") as fh:
-        fh.write("%%MatrixMarket matrix coordinate real general\n% written by sprs\n")
-        fh.write(f"{int(n_cells)} {len(feature_names)} {len(vals)}\n")
-        for r, c, v in zip(row_ids, col_ids, vals):
-            fh.write(f"{int(r) + 1} {int(c) + 1} {rust_display(v, f32=True)}\n")
     with open(with_additional_extension(output, ".features.txt"), "w") as fh:
         for n in feature_names:
             fh.write(f"{n}\n")
@@ -187,3 +184,34 @@ def write_single_cell_output(output: str, info: dict, feature_names: Sequence[st
         with open(with_additional_extension(output, ".barcodes.txt"), "w") as fh:
             for b in barcodes:
                 fh.write(f"{b}\n")
+
+
+def write_single_cell_output(output: str, info: dict, feature_names: Sequence[str], barcodes: Optional[Sequence[str]],
+                             n_cells: int, row_ids, col_ids, vals) -> None:
+    """write_function.rs:25-69: `.meta_info.json`, `.count.mtx` (MatrixMarket coordinate real
+    general, 1-based, f32 values in triplet order as sprs::io::write_matrix_market emits them) and
+    `.features.txt`; `.barcodes.txt` in row order (single_cell.rs:176-178).  The triplets come from
+    `cell_triplets(dense)` or `csr_triplets(*em_cells_sparse(...)[:3])`."""
+    _write_single_cell_side_files(output, info, feature_names, barcodes)
+    with open(with_additional_extension(output, ".count.mtx"), "w") as fh:
+        fh.write(_MTX_BANNER)
+        fh.write(f"{int(n_cells)} {len(feature_names)} {len(vals)}\n")
+        for r, c, v in zip(row_ids, col_ids, vals):
+            fh.write(f"{int(r) + 1} {int(c) + 1} {rust_display(v, f32=True)}\n")
+
+
+def write_single_cell_output_device(output: str, info: dict, feature_names: Sequence[str],
+                                    barcodes: Optional[Sequence[str]], n_cells: int, indptr, cols, vals,
+                                    device: int = 0) -> None:
+    """``write_single_cell_output`` with the matrix lines formatted on the device: the same four files, byte for
+    byte, from the CSR ``em_cells_sparse`` returns (no triplets are built).  `.count.mtx` is the text of
+    ``em.count_matrix_text`` -- the banner and the dimension line go in as its prefix -- written in one write."""
+    from .em import count_matrix_text
+
+    if len(indptr) != int(n_cells) + 1:
+        raise ValueError("indptr must hold n_cells + 1 offsets")
+    _write_single_cell_side_files(output, info, feature_names, barcodes)
+    prefix = (_MTX_BANNER + f"{int(n_cells)} {len(feature_names)} {len(vals)}\n").encode()
+    body = count_matrix_text(indptr, cols, vals, len(feature_names), prefix=prefix, device=device, offsets=False)
+    with open(with_additional_extension(output, ".count.mtx"), "wb") as fh:
+        fh.write(body.text)
