@@ -45,7 +45,9 @@ extern "C" {
  *    the whole `.prob.lz4` file as one LZ4 frame compressed on the device (oem_assignment_text_lz4,
  *    oem_text_result_info), the batched filter on the host and on the device and the store straight from the records
  *    (oem_builder_add_groups, oem_builder_add_groups_device, oem_store_create_records), the `.count.mtx` file of the
- *    single-cell path as text formatted on the device (oem_count_matrix_text). */
+ *    single-cell path as text formatted on the device (oem_count_matrix_text), the projected filter of genome mode
+ *    (oem_proj_record, oem_proj_opts, oem_builder_add_projected_group / _groups / _groups_device,
+ *    oem_store_create_projected_records). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -325,6 +327,74 @@ int oem_store_create_records(const oem_filters *filters, const uint64_t *txp_len
                              int device, const oem_store_opts *opts,
                              uint32_t *out_kept /* n_groups, or NULL */, oem_discard_table *out_discard /* or NULL */,
                              oem_store **out);
+
+/* One projected (transcriptome-space) alignment of a genome-mode read: ProjectedAlnRecord
+ * (src/util/oarfish_types.rs:1142-1164).  40 bytes. */
+typedef struct {
+    double similarity;          /* :1158  higher is better; the best of a read anchors the probability */
+    uint32_t ref_id;            /* :1145 */
+    uint32_t start;             /* :1147  1-based */
+    uint32_t end;               /* :1149  1-based, inclusive */
+    uint32_t aligned_len;       /* :1151  transcript bases spanned */
+    uint32_t query_aligned_len; /* :1153  read bases aligned, for the aligned fraction */
+    int32_t aln_score;          /* :1163  score of the genomic alignment this was projected from */
+    uint32_t flags;             /* OEM_REC_REVERSE (is_reverse, :1155); other bits are ignored */
+    uint32_t reserved;
+} oem_proj_record;
+
+/* What filter_projected takes besides the filters: --projected-prob-beta and ProjProbSource (src/prog_opts.rs:48-57). */
+typedef struct {
+    float beta;          /* default 10.0 */
+    int32_t prob_source; /* OEM_PROJ_SIMILARITY, _SCORE or _COMBINED */
+} oem_proj_opts;
+#define OEM_PROJ_SIMILARITY 0 /* exp((float)(sim - best_sim) * beta) */
+#define OEM_PROJ_SCORE 1      /* exp((float)(score - best_score) / D) */
+#define OEM_PROJ_COMBINED 2   /* exp((float)(score - best_score) / D + beta * (float)(sim - best_sim)) */
+
+/* InMemoryAlignmentStore::add_projected_group (src/util/oarfish_types.rs:695-715): AlignmentFilters::filter_projected
+ * (:1179-1297) followed by add_filtered_group, for one genome-mode read.  Of oem_filters it reads which_strand,
+ * min_aligned_len, three_prime_clip, five_prime_clip, min_aligned_fraction, score_threshold and score_prob_denom.  The
+ * first walk discards by orientation, aligned length, 3' and 5' distance, in that order, and tracks the best similarity
+ * (the first maximum; it fixes the aligned fraction query_aligned_len / read_len, 0 for read_len 0) and, independently,
+ * the best score.  Nothing retained or a best similarity <= 0 (a NaN never becomes the best): no counter moves, no row.
+ * An aligned fraction below min_aligned_fraction: discard_aln_frac.  Otherwise valid_best_aln, and a retained record
+ * is kept iff (float)(similarity * (1.0 / best)) >= score_threshold (discard_score otherwise), with its interval clamped
+ * into [1, txp_len] and as_prob = expf(f), f as under OEM_PROJ_* in f32 (the score difference wraps as i32), expf the
+ * host libm's.  no_mapping, no_valid_aln and discard_supp are never counted here.  A row is appended iff an alignment
+ * is kept; *out_kept = alignments appended.  A ref_id that is not below n_txps or a transcript of length 0, on any
+ * record of the group, is OEM_ERR_ARG (the reference would panic) and leaves the builder unchanged.  Projected and plain
+ * groups may be added to one builder in turn. */
+int oem_builder_add_projected_group(oem_builder *b, const oem_proj_record *records, uint32_t n_records,
+                                    uint64_t read_len, const oem_proj_opts *popts, uint32_t *out_kept);
+/* n_groups add_projected_group calls in one, as oem_builder_add_groups is to oem_builder_add_group: the same builder
+ * state afterwards byte for byte, the same out_kept, atomic, the same group_off errors; read_len has n_groups entries.
+ * An argument error of a record is reported with the index of the first such record. */
+int oem_builder_add_projected_groups(oem_builder *b, const oem_proj_record *records, const uint64_t *group_off,
+                                     const uint64_t *read_len, uint64_t n_groups, const oem_proj_opts *popts,
+                                     uint32_t *out_kept /* n_groups, or NULL */);
+/* The same builder state afterwards, byte for byte, computed on the device (oem_filter_projected_device.hip), as
+ * oem_builder_add_groups_device is to oem_builder_add_groups.  OEM_PROJ_SCORE looks as_prob up in the host's table over
+ * the integer score gap, with that call's fallbacks to the host loop (score_prob_denom, |aln_score| > 2^24).  For
+ * OEM_PROJ_SIMILARITY and _COMBINED the argument f is continuous: the device computes (float)exp((double)f) and keeps it
+ * only where that is provably what a libm expf returns -- f finite and <= 0, the result not subnormal, the f64 value
+ * at least 1/256 of an f32 ulp away from a rounding tie.  The other alignments (about 0.4 %) come down as (index, f),
+ * the host applies its expf and the values go back up before anything reads the weights.  A beta that is not finite
+ * sends these two sources through the host loop, as does |aln_score| > 2^24 for every source.  The result does not
+ * depend on the chunking; at most 2^31 - 2 groups per call; without a device OEM_ERR_NO_DEVICE, as there. */
+int oem_builder_add_projected_groups_device(oem_builder *b, const oem_proj_record *records, const uint64_t *group_off,
+                                            const uint64_t *read_len, uint64_t n_groups, const oem_proj_opts *popts,
+                                            int device, uint32_t *out_kept);
+/* Projected records -> resident store in one call, as oem_store_create_records: the store is the one
+ * oem_builder_create, oem_builder_add_projected_groups and oem_builder_store_create (model -1) or
+ * oem_builder_store_create_coverage (model 0 / 1) give with the same opts; out_kept, out_discard, the limits and the
+ * errors are those of that call and of oem_builder_add_projected_groups_device.  *out = NULL on any failure. */
+int oem_store_create_projected_records(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                       const oem_proj_record *records, const uint64_t *group_off,
+                                       const uint64_t *read_len, uint64_t n_groups, const oem_proj_opts *popts,
+                                       uint32_t bin_width, int model, double growth_rate,
+                                       int device, const oem_store_opts *opts,
+                                       uint32_t *out_kept /* n_groups, or NULL */,
+                                       oem_discard_table *out_discard /* or NULL */, oem_store **out);
 
 /* --------------------------------------------------------------------- */
 /* EM                                                                     */

@@ -50,7 +50,9 @@ ABI_SYMBOLS = [
     "oem_abi_version", "oem_last_error", "oem_device_count",
     "oem_store_create", "oem_store_destroy", "oem_store_dims", "oem_store_bytes", "oem_store_info", "oem_store_set_option",
     "oem_builder_create", "oem_builder_destroy", "oem_builder_add_group", "oem_builder_add_groups",
-    "oem_builder_add_groups_device", "oem_store_create_records", "oem_builder_dims",
+    "oem_builder_add_groups_device", "oem_store_create_records", "oem_builder_add_projected_group",
+    "oem_builder_add_projected_groups", "oem_builder_add_projected_groups_device", "oem_store_create_projected_records",
+    "oem_builder_dims",
     "oem_builder_discard_table", "oem_builder_export", "oem_builder_coverage_probs",
     "oem_builder_coverage_probs_binomial", "oem_coverage_probs_device", "oem_builder_coverage_probs_device",
     "oem_coverage_probs_cells_device",
@@ -108,6 +110,19 @@ class DiscardTableC(C.Structure):
 REC_UNMAPPED, REC_REVERSE, REC_SUPPLEMENTARY, REC_HAS_SCORE = 1, 2, 4, 8
 
 
+class ProjRecordC(C.Structure):
+    _fields_ = [("similarity", C.c_double), ("ref_id", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32),
+                ("aligned_len", C.c_uint32), ("query_aligned_len", C.c_uint32), ("aln_score", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ProjOptsC(C.Structure):
+    _fields_ = [("beta", C.c_float), ("prob_source", C.c_int32)]
+
+
+PROJ_SIMILARITY, PROJ_SCORE, PROJ_COMBINED = 0, 1, 2
+
+
 class CellsStreamOptsC(C.Structure):
     _fields_ = [("n_txps", C.c_uint32), ("device", C.c_int32), ("max_iter", C.c_uint32), ("conv_thresh", C.c_double),
                 ("coverage", C.c_uint32), ("bin_width", C.c_uint32), ("model", C.c_int32), ("growth_rate", C.c_double),
@@ -155,6 +170,11 @@ def _load(path: str) -> C.CDLL:
     L.oem_builder_add_groups.argtypes = [vp, vp, vp, u64, vp]
     L.oem_builder_add_groups_device.argtypes = [vp, vp, vp, u64, i32, vp]
     L.oem_store_create_records.argtypes = [vp, vp, u32, vp, vp, u64, u32, i32, f64, i32, vp, vp, vp, C.POINTER(vp)]
+    L.oem_builder_add_projected_group.argtypes = [vp, vp, u32, u64, vp, C.POINTER(u32)]
+    L.oem_builder_add_projected_groups.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.oem_builder_add_projected_groups_device.argtypes = [vp, vp, vp, vp, u64, vp, i32, vp]
+    L.oem_store_create_projected_records.argtypes = [vp, vp, u32, vp, vp, vp, u64, vp, u32, i32, f64, i32, vp, vp, vp,
+                                                     C.POINTER(vp)]
     L.oem_builder_dims.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.oem_builder_discard_table.argtypes = [vp, vp]
     L.oem_builder_export.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -243,6 +263,7 @@ def testing_lib() -> C.CDLL:
         L.oem_test_lz4_frame.argtypes = [vp, u64, vp, u64, C.POINTER(u64)]
         L.oem_debug_filter_last_timing.argtypes = [vp]
         L.oem_debug_mtx_last_timing.argtypes = [vp]
+        L.oem_debug_proj_last_pass.argtypes = [vp]
         _testing = L
     return _testing
 

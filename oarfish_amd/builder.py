@@ -8,6 +8,10 @@ call, without the CSR ever existing on the host.
 
 Records are a numpy structured array of dtype ``ALN_RECORD`` (the 40 bytes of ``oem_aln_record``); group g of a batch
 is ``records[group_off[g]:group_off[g + 1]]``.
+
+Genome mode has its own pair: ``add_projected_group`` / ``add_projected_groups`` run AlignmentFilters::filter_projected
+(:1179-1297) over records of dtype ``PROJ_RECORD`` (``oem_proj_record``) with one read length per group, into the same
+builder; ``DeviceStore.from_projected_records`` is the one-call form.
 """
 from __future__ import annotations
 
@@ -22,6 +26,11 @@ from ._lib import REC_HAS_SCORE, REC_REVERSE, REC_SUPPLEMENTARY, REC_UNMAPPED  #
 ALN_RECORD = np.dtype([("ref_id", "<u4"), ("aln_start", "<u4"), ("aln_end", "<u4"), ("aln_span", "<u4"),
                        ("score", "<i8"), ("seq_len", "<i8"), ("flags", "<u4"), ("reserved", "<u4")])
 assert ALN_RECORD.itemsize == C.sizeof(_lib.AlnRecordC) == 40
+
+PROJ_RECORD = np.dtype([("similarity", "<f8"), ("ref_id", "<u4"), ("start", "<u4"), ("end", "<u4"), ("aligned_len", "<u4"),
+                        ("query_aligned_len", "<u4"), ("aln_score", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert PROJ_RECORD.itemsize == C.sizeof(_lib.ProjRecordC) == 40
+PROB_SOURCES = {"similarity": _lib.PROJ_SIMILARITY, "score": _lib.PROJ_SCORE, "combined": _lib.PROJ_COMBINED}
 
 DISCARD_FIELDS = tuple(n for n, _ in _lib.DiscardTableC._fields_)
 
@@ -47,6 +56,29 @@ def check_batch(records, group_off):
     if int(group_off[-1]) > len(records):
         raise ValueError("group_off runs past the end of records")
     return records, group_off
+
+
+def proj_opts_c(beta: float = 10.0, prob_source="similarity") -> _lib.ProjOptsC:
+    """An ``oem_proj_opts``: ``prob_source`` by name ("similarity", "score", "combined") or by its code."""
+    if isinstance(prob_source, str):
+        if prob_source not in PROB_SOURCES:
+            raise ValueError(f"prob_source must be one of {sorted(PROB_SOURCES)}, not {prob_source!r}")
+        prob_source = PROB_SOURCES[prob_source]
+    return _lib.ProjOptsC(float(beta), int(prob_source))
+
+
+def check_projected_batch(records, group_off, read_len):
+    """(records, group_off, read_len) as the contiguous arrays the projected batch calls read."""
+    records = np.ascontiguousarray(records, dtype=PROJ_RECORD)
+    group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+    read_len = np.ascontiguousarray(read_len, dtype=np.uint64)
+    if group_off.ndim != 1 or len(group_off) < 1:
+        raise ValueError("group_off needs n_groups + 1 entries")
+    if int(group_off[-1]) > len(records):
+        raise ValueError("group_off runs past the end of records")
+    if read_len.shape != (len(group_off) - 1,):
+        raise ValueError("read_len needs n_groups entries")
+    return records, group_off, read_len
 
 
 def discard_dict(dt: _lib.DiscardTableC) -> dict:
@@ -114,6 +146,36 @@ class StoreBuilder:
         else:
             rc = self._lib.oem_builder_add_groups_device(self.handle, rec, group_off.ctypes.data, n_groups, int(device),
                                                          kept.ctypes.data)
+        self._check(rc)
+        return kept
+
+    def add_projected_group(self, records, read_len: int, beta: float = 10.0, prob_source="similarity") -> int:
+        """One genome-mode read's projected records (dtype ``PROJ_RECORD``) through filter_projected
+        (oarfish_types.rs:1179-1297); returns the number of alignments kept (0: the read was dropped)."""
+        records = np.ascontiguousarray(records, dtype=PROJ_RECORD)
+        po = proj_opts_c(beta, prob_source)
+        kept = C.c_uint32(0)
+        self._check(self._lib.oem_builder_add_projected_group(self.handle, records.ctypes.data if len(records) else None,
+                                                              len(records), int(read_len), C.addressof(po), C.byref(kept)))
+        return int(kept.value)
+
+    def add_projected_groups(self, records, group_off, read_len, beta: float = 10.0, prob_source="similarity",
+                             device: Optional[int] = None) -> np.ndarray:
+        """A batch of genome-mode reads in one call, as ``add_groups``: ``read_len[g]`` is read g's length,
+        ``prob_source`` "similarity", "score" or "combined" (ProjProbSource), ``beta`` --projected-prob-beta.  On the
+        host (``device=None``) or on GPU ``device``, with the same builder state afterwards byte for byte.  Atomic."""
+        records, group_off, read_len = check_projected_batch(records, group_off, read_len)
+        po = proj_opts_c(beta, prob_source)
+        n_groups = len(group_off) - 1
+        kept = np.zeros(n_groups, dtype=np.uint32)
+        rec = records.ctypes.data if len(records) else None
+        rl = read_len.ctypes.data if n_groups else None
+        if device is None:
+            rc = self._lib.oem_builder_add_projected_groups(self.handle, rec, group_off.ctypes.data, rl, n_groups,
+                                                            C.addressof(po), kept.ctypes.data)
+        else:
+            rc = self._lib.oem_builder_add_projected_groups_device(self.handle, rec, group_off.ctypes.data, rl, n_groups,
+                                                                   C.addressof(po), int(device), kept.ctypes.data)
         self._check(rc)
         return kept
 

@@ -83,7 +83,7 @@ static int add_one_group(oem_builder *b, const oem_aln_record *ag, uint32_t n, u
     return OEM_OK;
 }
 
-int check_group_off(const char *who, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups)
+int check_group_off(const char *who, const void *records, const uint64_t *group_off, uint64_t n_groups)
 {
     if (!group_off) return fail(OEM_ERR_ARG, "%s: group_off is NULL", who);
     if (group_off[0] != 0) return fail(OEM_ERR_ARG, "%s: group_off[0] must be 0", who);

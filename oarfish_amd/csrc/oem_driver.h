@@ -340,9 +340,16 @@ struct BuilderMark {
 };
 BuilderMark builder_mark(const oem_builder *b);
 void builder_rollback(oem_builder *b, const BuilderMark &m);
-int check_group_off(const char *who, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups);
+int check_group_off(const char *who, const void *records, const uint64_t *group_off, uint64_t n_groups);
 int add_groups_host(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
                     uint32_t *out_kept, const char *who);
+// oem_builder_projected.cpp: the host loop of a projected batch (atomic, as add_groups_host) and the checks every
+// projected batch call makes first
+int add_projected_groups_host(oem_builder *b, const oem_proj_record *records, const uint64_t *group_off,
+                              const uint64_t *read_len, uint64_t n_groups, const oem_proj_opts &popts, uint32_t *out_kept,
+                              const char *who);
+int check_projected_batch(const char *who, const oem_proj_record *records, const uint64_t *group_off,
+                          const uint64_t *read_len, uint64_t n_groups, const oem_proj_opts *popts);
 
 // oem_filter_device.hip: times of this thread's last device batch call under OEM_FILTER_TIMING=1 (test-only library; all
 // zero when the call never reached the device pass): from HIP events, ms of the record uploads (sum over the chunks), of
@@ -350,5 +357,11 @@ int add_groups_host(oem_builder *b, const oem_aln_record *records, const uint64_
 // a record copy was in flight; from the host clock, ms the calling thread spent copying the records into pinned staging
 void filter_last_timing(float *ms6);
 void filter_timing_reset();
+// oem_filter_projected_device.hip: this thread's last projected device batch call (test-only library): ms of
+// k_proj_measure (summed over the chunks), of k_proj_emit, and of finishing the unsure alignments on the host (select,
+// copy down, libm expf, copy up, scatter) -- the first two from HIP events under OEM_FILTER_TIMING=1, the third from the
+// host clock -- then the number of alignments the host finished and the number emitted.  All zero when the call never
+// reached the device pass; out[1] is zero when the host loop took the batch after the measure pass.
+void proj_last_pass(double *out5);
 
 } // namespace oem

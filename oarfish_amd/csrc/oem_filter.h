@@ -185,7 +185,10 @@ OEM_HD inline void filter_group_emit(const oem_filters &F, const oem_aln_record 
     }
 }
 
-// -- host only: the table ------------------------------------------------------------------------------------------------
+// -- host only: the discard table, the gap table ---------------------------------------------------------------------------
+void add_counts(oem_discard_table &dt, const FilterCounts &c); // oem_builder.cpp: a group's contributions into the table
+
+
 // D admits the gap table at all (finite and positive)
 inline bool filter_denom_ok(float D) { return D > 0.0f && D <= 3.4028234663852886e38f; }
 

@@ -18,6 +18,9 @@
 //   k_filter_emit     one lane per kept group: row_ptr, tid, as_prob (looked up in the host's expf table by the integer
 //                     score gap: the device never computes exp), start, end, strand at the group's offsets
 //
+// The upload lanes, the scans and what is made of a pass's result (filter_result_to_builder, filter_result_to_store) are
+// shared with the projected filter of oem_filter_projected_device.hip through oem_filter_device.h.
+//
 // oem_builder_add_groups_device copies the arrays back and appends them to the builder; oem_store_create_records frees
 // the records and hands the arrays on as a ResidentCsr (model -1) or runs the coverage model on them first (0 / 1), as
 // oem_store_create_coverage does after its upload.  Host arrays are brought back only for the host layout builder.
@@ -27,26 +30,13 @@
 #include <new>
 #include <vector>
 
-#include "oem_driver.h"
-#include "oem_filter.h"
+#include "oem_filter_device.h"
 
 namespace oem {
 
 namespace {
 
-constexpr int kFT = 256;
-constexpr uint64_t kFilterChunkGroups = 1ull << 18; // groups per upload chunk (the test-only library: OEM_FILTER_CHUNK_GROUPS)
-constexpr unsigned long long kNoRecord = ~0ull;
-
 thread_local float g_filter_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-// what the measure pass leaves besides n_kept / best
-struct FilterTotals {
-    unsigned long long counts[kFilterCounters]; // oem_discard_table's order
-    unsigned long long bad_record;              // the first record with ref_id >= n_txps (kNoRecord: none)
-    uint32_t flags;
-    uint32_t pad;
-};
 
 __global__ __launch_bounds__(kFT) void k_filter_measure(oem_filters F, const oem_aln_record *__restrict__ recs,
                                                         const unsigned long long *__restrict__ group_off, uint64_t g0,
@@ -115,32 +105,6 @@ struct NonZeroToU64 {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v ? 1 : 0; }
 };
 
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-};
-struct Pinned {
-    void *p = nullptr;
-    ~Pinned() { if (p) (void)hipHostFree(p); }
-};
-
-// What a device filter pass returns: the new reads' CSR on the device.  row_ptr has n_rows + 1 entries, the first one
-// `base`; exactly one of row_ptr64 / row_ptr32 is filled.
-struct FilterResult {
-    uint64_t n_rows = 0, nnz = 0;
-    DevBuf<uint64_t> row_ptr64;
-    DevBuf<uint32_t> row_ptr32, tid, start, end, n_kept;
-    DevBuf<float> as_prob;
-    DevBuf<uint8_t> strand;
-    DevBuf<uint64_t> txp_len; // the transcript lengths, kept for the coverage model
-    oem_discard_table dt{};
-    bool host_rerun = false;  // a score beyond +-2^24: nothing above is filled, the host loop takes the batch
-};
-
 // Measure, scans and emit of one batch on the current device.  want_coords: start / end / strand too.  narrow: u32 row
 // pointers (the total is checked against 2^32 first).  An argument error found on the device (ref_id) is reported here.
 int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
@@ -149,8 +113,7 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
 {
     const bool timing = knob("OEM_FILTER_TIMING", 0) != 0;
     const uint64_t n_records = group_off[n_groups];
-    long ck = knob("OEM_FILTER_CHUNK_GROUPS", (long)kFilterChunkGroups);
-    const uint64_t chunk = ck > 0 ? (uint64_t)ck : kFilterChunkGroups;
+    const uint64_t chunk = (uint64_t)filter_chunk_groups();
 
     DevBuf<oem_aln_record> d_recs;
     DevBuf<unsigned long long> d_goff;
@@ -173,74 +136,14 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
     OEM_HIP(hipMemset(out->n_kept.p + n_groups, 0, sizeof(uint32_t))); // (the scans read n_groups + 1 entries)
     OEM_HIP(hipStreamSynchronize(nullptr)); // (the lanes below do not wait for the null stream)
 
-    // -- upload + measure: two lanes, each a stream with its pinned staging buffer ------------------------------------
-    uint64_t max_chunk_records = 0;
-    for (uint64_t g0 = 0; g0 < n_groups; g0 += chunk) {
-        const uint64_t g1 = g0 + chunk < n_groups ? g0 + chunk : n_groups;
-        if (group_off[g1] - group_off[g0] > max_chunk_records) max_chunk_records = group_off[g1] - group_off[g0];
-    }
-    Stream lane[2];
-    Pinned stage[2];
-    Event copied[2]; // the lane's last copy has left its staging buffer
-    const uint64_t n_chunks = (n_groups + chunk - 1) / chunk;
-    for (int l = 0; l < 2 && (uint64_t)l < n_chunks; ++l) {
-        OEM_HIP(hipStreamCreateWithFlags(&lane[l].s, hipStreamNonBlocking));
-        OEM_HIP(hipHostMalloc(&stage[l].p, (max_chunk_records ? max_chunk_records : 1) * sizeof(oem_aln_record), hipHostMallocDefault));
-        OEM_HIP(hipEventCreateWithFlags(&copied[l].e, hipEventDisableTiming));
-    }
-    struct ChunkEvents { hipEvent_t c0 = nullptr, c1 = nullptr, m1 = nullptr; };
-    std::vector<ChunkEvents> cev(timing ? n_chunks : 0);
-    struct EvGuard {
-        std::vector<ChunkEvents> &v;
-        ~EvGuard() { for (auto &c : v) { if (c.c0) (void)hipEventDestroy(c.c0); if (c.c1) (void)hipEventDestroy(c.c1); if (c.m1) (void)hipEventDestroy(c.m1); } }
-    } ev_guard{cev};
-    for (auto &c : cev) {
-        OEM_HIP(hipEventCreate(&c.c0));
-        OEM_HIP(hipEventCreate(&c.c1));
-        OEM_HIP(hipEventCreate(&c.m1));
-    }
-    uint64_t ci = 0;
-    for (uint64_t g0 = 0; g0 < n_groups; g0 += chunk, ++ci) {
-        const int l = (int)(ci & 1);
-        const uint64_t g1 = g0 + chunk < n_groups ? g0 + chunk : n_groups;
-        const uint64_t r0 = group_off[g0], nr = group_off[g1] - r0;
-        if (ci >= 2) OEM_HIP(hipEventSynchronize(copied[l].e));
-        const auto t_stage = std::chrono::steady_clock::now();
-        if (nr) std::memcpy(stage[l].p, records + r0, nr * sizeof(oem_aln_record));
-        if (timing) g_filter_ms[5] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_stage).count();
-        if (timing) OEM_HIP(hipEventRecord(cev[ci].c0, lane[l].s));
-        if (nr) OEM_HIP(hipMemcpyAsync(d_recs.p + r0, stage[l].p, nr * sizeof(oem_aln_record), hipMemcpyHostToDevice, lane[l].s));
-        OEM_HIP(hipEventRecord(copied[l].e, lane[l].s));
-        if (timing) OEM_HIP(hipEventRecord(cev[ci].c1, lane[l].s));
-        hipLaunchKernelGGL(k_filter_measure, dim3((uint32_t)((g1 - g0 + kFT - 1) / kFT)), dim3(kFT), 0, lane[l].s, F, d_recs.p,
-                           d_goff.p, g0, g1, out->txp_len.p, n_txps, out->n_kept.p, d_best.p, d_tot.p);
-        OEM_HIP(hipGetLastError());
-        if (timing) OEM_HIP(hipEventRecord(cev[ci].m1, lane[l].s));
-    }
-    for (int l = 0; l < 2; ++l)
-        if (lane[l].s) OEM_HIP(hipStreamSynchronize(lane[l].s));
+    // -- upload + measure ----------------------------------------------------------------------------------------------
+    OEM_TRY(filter_upload_measure(records, d_recs.p, group_off, n_groups, chunk, timing ? g_filter_ms : nullptr,
+                                  [&](hipStream_t st, uint64_t g0, uint64_t g1) {
+                                      hipLaunchKernelGGL(k_filter_measure, dim3((uint32_t)((g1 - g0 + kFT - 1) / kFT)), dim3(kFT), 0,
+                                                         st, F, d_recs.p, d_goff.p, g0, g1, out->txp_len.p, n_txps, out->n_kept.p,
+                                                         d_best.p, d_tot.p);
+                                  }));
     OEM_HIP(hipMemcpy(&h_tot, d_tot.p, sizeof(h_tot), hipMemcpyDeviceToHost));
-    if (timing && n_chunks) { // intervals relative to the first chunk's copy start; overlap of each measure with the copies
-        std::vector<float> c0(n_chunks), c1(n_chunks), m1(n_chunks);
-        for (uint64_t i = 0; i < n_chunks; ++i) {
-            OEM_HIP(hipEventElapsedTime(&c0[i], cev[0].c0, cev[i].c0));
-            OEM_HIP(hipEventElapsedTime(&c1[i], cev[0].c0, cev[i].c1));
-            OEM_HIP(hipEventElapsedTime(&m1[i], cev[0].c0, cev[i].m1));
-        }
-        float up = 0.f, ms = 0.f, ov = 0.f;
-        for (uint64_t i = 0; i < n_chunks; ++i) {
-            up += c1[i] - c0[i];
-            ms += m1[i] - c1[i];
-            for (uint64_t j = 0; j < n_chunks; ++j) { // (copies of the other lane only: a lane's own work is serial)
-                if (((i ^ j) & 1) == 0) continue;
-                const float a = c1[i] > c0[j] ? c1[i] : c0[j], b = m1[i] < c1[j] ? m1[i] : c1[j];
-                if (b > a) ov += b - a;
-            }
-        }
-        g_filter_ms[0] = up;
-        g_filter_ms[1] = ms;
-        g_filter_ms[4] = ms > 0.f ? ov / ms : 0.f;
-    }
     if (h_tot.flags & kFilterFlagBadRef)
         return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, h_tot.bad_record,
                     records[h_tot.bad_record].ref_id);
@@ -251,51 +154,13 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
     const uint64_t *cnt = (const uint64_t *)h_tot.counts;
     out->dt = oem_discard_table{cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]};
 
-    // -- scans ---------------------------------------------------------------------------------------------------------
+    // -- scans, emit ---------------------------------------------------------------------------------------------------
     hipStream_t st = nullptr; // the emit follows the scans on the null stream (the lanes are idle)
     Event ev[3];
     if (timing)
         for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
-    OEM_TRY(dev_alloc(&d_aln_off.p, n_groups + 1, nullptr));
-    OEM_TRY(dev_alloc(&d_row_idx.p, n_groups + 1, nullptr));
-    if (timing) OEM_HIP(hipEventRecord(ev[0].e, st));
-    {
-        hipcub::TransformInputIterator<uint64_t, U32ToU64, const uint32_t *> in_a(out->n_kept.p, U32ToU64());
-        hipcub::TransformInputIterator<uint64_t, NonZeroToU64, const uint32_t *> in_r(out->n_kept.p, NonZeroToU64());
-        size_t tmp_a = 0, tmp_r = 0;
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_a, in_a, d_aln_off.p, (int)(n_groups + 1), st));
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_r, in_r, d_row_idx.p, (int)(n_groups + 1), st));
-        DevBuf<uint8_t> d_tmp;
-        OEM_TRY(dev_alloc(&d_tmp.p, tmp_a > tmp_r ? tmp_a : tmp_r, nullptr));
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_a, in_a, d_aln_off.p, (int)(n_groups + 1), st));
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_r, in_r, d_row_idx.p, (int)(n_groups + 1), st));
-        OEM_HIP(hipStreamSynchronize(st));
-    }
-    if (timing) OEM_HIP(hipEventRecord(ev[1].e, st));
-    uint64_t nnz = 0, n_rows = 0;
-    OEM_HIP(hipMemcpy(&nnz, d_aln_off.p + n_groups, sizeof(nnz), hipMemcpyDeviceToHost));
-    OEM_HIP(hipMemcpy(&n_rows, d_row_idx.p + n_groups, sizeof(n_rows), hipMemcpyDeviceToHost));
-    if (narrow && base + nnz >= (1ull << 32))
-        return fail(OEM_ERR_ARG, "%s: %llu alignments are kept; a resident store needs fewer than 2^32", who, (unsigned long long)nnz);
-    out->nnz = nnz;
-    out->n_rows = n_rows;
-
-    // -- emit ----------------------------------------------------------------------------------------------------------
-    if (narrow) {
-        OEM_TRY(dev_alloc(&out->row_ptr32.p, n_rows + 1, nullptr));
-        const uint32_t b32 = (uint32_t)base;
-        OEM_HIP(hipMemcpy(out->row_ptr32.p, &b32, sizeof(b32), hipMemcpyHostToDevice));
-    } else {
-        OEM_TRY(dev_alloc(&out->row_ptr64.p, n_rows + 1, nullptr));
-        OEM_HIP(hipMemcpy(out->row_ptr64.p, &base, sizeof(base), hipMemcpyHostToDevice));
-    }
-    OEM_TRY(dev_alloc(&out->tid.p, nnz, nullptr));
-    OEM_TRY(dev_alloc(&out->as_prob.p, nnz, nullptr));
-    if (want_coords) {
-        OEM_TRY(dev_alloc(&out->start.p, nnz, nullptr));
-        OEM_TRY(dev_alloc(&out->end.p, nnz, nullptr));
-        OEM_TRY(dev_alloc(&out->strand.p, nnz, nullptr));
-    }
+    OEM_TRY(filter_scan_alloc(who, n_groups, base, want_coords, narrow, out, &d_aln_off, &d_row_idx, ev[0].e, ev[1].e));
+    const uint64_t nnz = out->nnz;
     OEM_TRY(dev_alloc(&d_tab.p, tab.size(), nullptr));
     if (!tab.empty()) OEM_HIP(hipMemcpy(d_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
     if (n_groups && nnz) {
@@ -359,27 +224,53 @@ struct HostCsr {
 void filter_last_timing(float *ms6) { std::memcpy(ms6, g_filter_ms, sizeof g_filter_ms); }
 void filter_timing_reset() { for (float &m : g_filter_ms) m = 0.f; }
 
-} // namespace oem
-
-using namespace oem;
-
-extern "C" int oem_builder_add_groups_device(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off,
-                                             uint64_t n_groups, int device, uint32_t *out_kept)
+int filter_scan_alloc(const char *who, uint64_t n_groups, uint64_t base, bool want_coords, bool narrow, FilterResult *out,
+                      DevBuf<uint64_t> *aln_off, DevBuf<uint64_t> *row_idx, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
-    OEM_API_BEGIN
-    const char *who = "oem_builder_add_groups_device";
-    filter_timing_reset();
-    if (!b) return fail(OEM_ERR_ARG, "%s: builder is NULL", who);
-    std::vector<float> tab;
-    bool host_only = false;
-    OEM_TRY(prepare_batch(who, b->f, records, group_off, n_groups, &tab, &host_only));
-    OEM_TRY(ensure_device(device));
-    if (host_only) return add_groups_host(b, records, group_off, n_groups, out_kept, who);
-    FilterResult r;
-    const uint64_t base = b->tid.size();
-    OEM_TRY(filter_device(who, b->f, b->txp_len.data(), (uint32_t)b->txp_len.size(), tab, records, group_off, n_groups, base,
-                          true, false, &r));
-    if (r.host_rerun) return add_groups_host(b, records, group_off, n_groups, out_kept, who);
+    hipStream_t st = nullptr;
+    OEM_TRY(dev_alloc(&aln_off->p, n_groups + 1, nullptr));
+    OEM_TRY(dev_alloc(&row_idx->p, n_groups + 1, nullptr));
+    if (ev_begin) OEM_HIP(hipEventRecord(ev_begin, st));
+    {
+        hipcub::TransformInputIterator<uint64_t, U32ToU64, const uint32_t *> in_a(out->n_kept.p, U32ToU64());
+        hipcub::TransformInputIterator<uint64_t, NonZeroToU64, const uint32_t *> in_r(out->n_kept.p, NonZeroToU64());
+        size_t tmp_a = 0, tmp_r = 0;
+        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_a, in_a, aln_off->p, (int)(n_groups + 1), st));
+        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_r, in_r, row_idx->p, (int)(n_groups + 1), st));
+        DevBuf<uint8_t> d_tmp;
+        OEM_TRY(dev_alloc(&d_tmp.p, tmp_a > tmp_r ? tmp_a : tmp_r, nullptr));
+        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_a, in_a, aln_off->p, (int)(n_groups + 1), st));
+        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_r, in_r, row_idx->p, (int)(n_groups + 1), st));
+        OEM_HIP(hipStreamSynchronize(st));
+    }
+    if (ev_end) OEM_HIP(hipEventRecord(ev_end, st));
+    uint64_t nnz = 0, n_rows = 0;
+    OEM_HIP(hipMemcpy(&nnz, aln_off->p + n_groups, sizeof(nnz), hipMemcpyDeviceToHost));
+    OEM_HIP(hipMemcpy(&n_rows, row_idx->p + n_groups, sizeof(n_rows), hipMemcpyDeviceToHost));
+    if (narrow && base + nnz >= (1ull << 32))
+        return fail(OEM_ERR_ARG, "%s: %llu alignments are kept; a resident store needs fewer than 2^32", who, (unsigned long long)nnz);
+    out->nnz = nnz;
+    out->n_rows = n_rows;
+    if (narrow) {
+        OEM_TRY(dev_alloc(&out->row_ptr32.p, n_rows + 1, nullptr));
+        const uint32_t b32 = (uint32_t)base;
+        OEM_HIP(hipMemcpy(out->row_ptr32.p, &b32, sizeof(b32), hipMemcpyHostToDevice));
+    } else {
+        OEM_TRY(dev_alloc(&out->row_ptr64.p, n_rows + 1, nullptr));
+        OEM_HIP(hipMemcpy(out->row_ptr64.p, &base, sizeof(base), hipMemcpyHostToDevice));
+    }
+    OEM_TRY(dev_alloc(&out->tid.p, nnz, nullptr));
+    OEM_TRY(dev_alloc(&out->as_prob.p, nnz, nullptr));
+    if (want_coords) {
+        OEM_TRY(dev_alloc(&out->start.p, nnz, nullptr));
+        OEM_TRY(dev_alloc(&out->end.p, nnz, nullptr));
+        OEM_TRY(dev_alloc(&out->strand.p, nnz, nullptr));
+    }
+    return OEM_OK;
+}
+
+int filter_result_to_builder(oem_builder *b, FilterResult &r, uint64_t n_groups, uint32_t *out_kept)
+{
     const BuilderMark mark = builder_mark(b);
     int rc = OEM_OK;
     try {
@@ -412,20 +303,11 @@ extern "C" int oem_builder_add_groups_device(oem_builder *b, const oem_aln_recor
     uint64_t *dt = &b->dt.discard_5p;
     for (int k = 0; k < kFilterCounters; ++k) dt[k] += add[k];
     return OEM_OK;
-    OEM_API_END("oem_builder_add_groups_device")
 }
 
-extern "C" int oem_store_create_records(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
-                                        const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
-                                        uint32_t bin_width, int model, double growth_rate, int device,
-                                        const oem_store_opts *opts, uint32_t *out_kept, oem_discard_table *out_discard,
-                                        oem_store **out)
+int check_store_from_records(const char *who, const void *filters, const uint64_t *txp_len, uint32_t n_txps, uint32_t bin_width,
+                             int model, const oem_store_opts *opts)
 {
-    OEM_API_BEGIN
-    const char *who = "oem_store_create_records";
-    filter_timing_reset();
-    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
-    *out = nullptr;
     if (!filters || !txp_len || n_txps == 0) return fail(OEM_ERR_ARG, "%s: bad argument", who);
     if (model < -1 || model > 1) return fail(OEM_ERR_ARG, "%s: model must be -1 (none), 0 (logistic) or 1 (binomial)", who);
     if (model >= 0 && bin_width == 0)
@@ -433,24 +315,13 @@ extern "C" int oem_store_create_records(const oem_filters *filters, const uint64
     if (opts && opts->weight_coding > 2) return fail(OEM_ERR_ARG, "%s: weight_coding %u (0, 1 or 2)", who, opts->weight_coding);
     if (opts && opts->layout_build > 1) return fail(OEM_ERR_ARG, "%s: layout_build %u (0 or 1)", who, opts->layout_build);
     if (opts && opts->reorder_rows > 2) return fail(OEM_ERR_ARG, "%s: reorder_rows %u (0, 1 or 2)", who, opts->reorder_rows);
-    std::vector<float> tab;
-    bool host_only = false;
-    OEM_TRY(prepare_batch(who, *filters, records, group_off, n_groups, &tab, &host_only));
-    OEM_TRY(ensure_device(device));
+    return OEM_OK;
+}
 
-    FilterResult r;
-    if (!host_only)
-        OEM_TRY(filter_device(who, *filters, txp_len, n_txps, tab, records, group_off, n_groups, 0, model >= 0, true, &r));
-    if (host_only || r.host_rerun) { // the host loop takes the batch: the long way round, same store
-        oem_builder hb;
-        hb.f = *filters;
-        hb.txp_len.assign(txp_len, txp_len + n_txps);
-        OEM_TRY(add_groups_host(&hb, records, group_off, n_groups, out_kept, who));
-        if (hb.tid.size() >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a resident store needs fewer than 2^32 alignments", who);
-        if (out_discard) *out_discard = hb.dt;
-        if (model < 0) return oem_builder_store_create(&hb, nullptr, device, opts, out);
-        return oem_builder_store_create_coverage(&hb, bin_width, model, growth_rate, device, opts, nullptr, out);
-    }
+int filter_result_to_store(const char *who, FilterResult &r, uint32_t n_txps, uint64_t n_groups, uint32_t bin_width, int model,
+                           double growth_rate, int device, const oem_store_opts *opts, uint32_t *out_kept,
+                           oem_discard_table *out_discard, oem_store **out)
+{
     if (out_kept && n_groups) OEM_HIP(hipMemcpy(out_kept, r.n_kept.p, sizeof(uint32_t) * n_groups, hipMemcpyDeviceToHost));
     if (out_discard) *out_discard = r.dt;
     r.n_kept.reset();
@@ -518,5 +389,63 @@ extern "C" int oem_store_create_records(const oem_filters *filters, const uint64
     }
     *out = s;
     return OEM_OK;
+}
+
+} // namespace oem
+
+using namespace oem;
+
+extern "C" int oem_builder_add_groups_device(oem_builder *b, const oem_aln_record *records, const uint64_t *group_off,
+                                             uint64_t n_groups, int device, uint32_t *out_kept)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_builder_add_groups_device";
+    filter_timing_reset();
+    if (!b) return fail(OEM_ERR_ARG, "%s: builder is NULL", who);
+    std::vector<float> tab;
+    bool host_only = false;
+    OEM_TRY(prepare_batch(who, b->f, records, group_off, n_groups, &tab, &host_only));
+    OEM_TRY(ensure_device(device));
+    if (host_only) return add_groups_host(b, records, group_off, n_groups, out_kept, who);
+    FilterResult r;
+    const uint64_t base = b->tid.size();
+    OEM_TRY(filter_device(who, b->f, b->txp_len.data(), (uint32_t)b->txp_len.size(), tab, records, group_off, n_groups, base,
+                          true, false, &r));
+    if (r.host_rerun) return add_groups_host(b, records, group_off, n_groups, out_kept, who);
+    return filter_result_to_builder(b, r, n_groups, out_kept);
+    OEM_API_END("oem_builder_add_groups_device")
+}
+
+extern "C" int oem_store_create_records(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                        const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
+                                        uint32_t bin_width, int model, double growth_rate, int device,
+                                        const oem_store_opts *opts, uint32_t *out_kept, oem_discard_table *out_discard,
+                                        oem_store **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_store_create_records";
+    filter_timing_reset();
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    OEM_TRY(check_store_from_records(who, filters, txp_len, n_txps, bin_width, model, opts));
+    std::vector<float> tab;
+    bool host_only = false;
+    OEM_TRY(prepare_batch(who, *filters, records, group_off, n_groups, &tab, &host_only));
+    OEM_TRY(ensure_device(device));
+
+    FilterResult r;
+    if (!host_only)
+        OEM_TRY(filter_device(who, *filters, txp_len, n_txps, tab, records, group_off, n_groups, 0, model >= 0, true, &r));
+    if (host_only || r.host_rerun) { // the host loop takes the batch: the long way round, same store
+        oem_builder hb;
+        hb.f = *filters;
+        hb.txp_len.assign(txp_len, txp_len + n_txps);
+        OEM_TRY(add_groups_host(&hb, records, group_off, n_groups, out_kept, who));
+        if (hb.tid.size() >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a resident store needs fewer than 2^32 alignments", who);
+        if (out_discard) *out_discard = hb.dt;
+        if (model < 0) return oem_builder_store_create(&hb, nullptr, device, opts, out);
+        return oem_builder_store_create_coverage(&hb, bin_width, model, growth_rate, device, opts, nullptr, out);
+    }
+    return filter_result_to_store(who, r, n_txps, n_groups, bin_width, model, growth_rate, device, opts, out_kept, out_discard, out);
     OEM_API_END("oem_store_create_records")
 }

@@ -148,6 +148,17 @@ extern "C" int oem_debug_filter_last_timing(float *out)
     return OEM_OK;
 }
 
+// out[0..4] = this thread's last projected device batch call (oem_builder_add_projected_groups_device,
+// oem_store_create_projected_records): ms of k_proj_measure (summed over the chunks) and of k_proj_emit from HIP events
+// under OEM_FILTER_TIMING=1, ms of finishing the unsure alignments on the host (host clock), the number of alignments the
+// host finished with libm's expf and the number emitted.  All zero when the host loop took the batch without a device pass.
+extern "C" int oem_debug_proj_last_pass(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_proj_last_pass: NULL argument");
+    proj_last_pass(out);
+    return OEM_OK;
+}
+
 // Test hook: the n caller bytes at `data` as one LZ4 frame, by the path oem_assignment_text_lz4 compresses a chunk with
 // (upload, k_lz4_blocks, scan, k_lz4_gather; blocks of OEM_LZ4_BLOCK_BYTES), so that tests can feed crafted inputs.
 // *out_len = the frame's length, always; the frame is copied to out when it fits cap (else OEM_ERR_ARG).

@@ -416,6 +416,142 @@ def make_records(store: SyntheticStore, seed: int = BASE_SEED + 21, decoy_rate: 
     return SyntheticRecords(filters, txp_len, rec, group_off, kept, discard)
 
 
+@dataclass
+class SyntheticProjectedRecords:
+    filters: dict                # the fields of oem_filters the records were made for
+    txp_len: np.ndarray          # u64 [T]
+    records: np.ndarray          # builder.PROJ_RECORD [n_records]
+    group_off: np.ndarray        # u64 [n_groups + 1]
+    read_len: np.ndarray         # u64 [n_groups]
+    beta: float                  # --projected-prob-beta the similarities were made for
+    kept: np.ndarray             # u32 [n_groups]: what the filter keeps of each group
+    discard: dict                # the discard table the filter ends with
+
+
+def make_projected_records(store: SyntheticStore, seed: int = BASE_SEED + 22, decoy_rate: float = 0.3, drop_frac: float = 0.05,
+                           score_prob_denom: float = 5.0) -> SyntheticProjectedRecords:
+    """A synthetic store turned back into the projected (genome-mode) records it could have come from, so that
+    AlignmentFilters::filter_projected (oarfish_types.rs:1179-1297) over them gives the store again: the same reads in
+    the same order, the same transcripts, and -- under the default probability source, similarity -- the same
+    ``as_prob``, in the spirit of ``make_records``.
+
+    Each read gets a best similarity in [0.9, 1) and each kept alignment ``similarity = best + ln(p) / beta``, so that
+    ``expf((float)(similarity - best) * beta)`` is its ``as_prob`` p again up to the f32 rounding of the argument
+    (relative error about 1.2e-7 * (1 + |ln p|)).  ``beta`` is chosen from the store, at least 10, so that no kept
+    similarity falls below 0.55 of its read's best; the score threshold is 0.5.  ``aln_score`` is ``best - g`` with g the
+    integer gap of ``make_records``, so the score source reproduces ``expf(-g / D)`` as well.  Coordinates are 1-based
+    and inside the transcripts (the clamp leaves them alone).  Per read, Poisson(``decoy_rate``) DECOY records are each
+    rejected by exactly one test (orientation, aligned length, 3' clip, 5' clip in the first walk -- these carry a
+    similarity above the read's best, which they must not become -- or the similarity threshold in the second); whole
+    reads are dropped (``drop_frac`` of the groups) by a best similarity of 0, by a best alignment that covers a tenth
+    of the read, or because the orientation test leaves nothing.  ``kept`` and ``discard`` are what the filter must
+    report; discard_supp, no_mapping and no_valid_aln stay 0, filter_projected never counts them.  A pure function of
+    (store, seed, rates, D)."""
+    from .builder import PROJ_RECORD, REC_REVERSE
+    F5, F3 = 2000, 3000
+    filters = dict(five_prime_clip=F5, three_prime_clip=F3, score_threshold=0.5, min_aligned_fraction=0.5,
+                   min_aligned_len=50, which_strand=1, score_prob_denom=float(score_prob_denom))
+    rng = np.random.default_rng([seed, 0x9207EC])
+    R, T, nnz = store.n_reads, store.n_txps, store.nnz
+    rp = store.row_ptr.astype(np.int64)
+    lens = np.diff(rp)
+    if R and lens.min() < 1:
+        raise ValueError("make_projected_records needs a store without empty reads")
+    txp_len = rng.integers(400, 6000, size=T).astype(np.uint64)
+    logp = np.log(store.as_prob.astype(np.float64))
+    gap = np.rint(-float(score_prob_denom) * logp).astype(np.int64)
+    first = rp[:-1]
+    if R and np.maximum.reduceat(logp, first).min() != 0.0:
+        raise ValueError("make_projected_records needs a read's best alignment to have as_prob 1")
+    beta = float(max(10.0, np.ceil(2.5 * float(-logp.min())))) if nnz else 10.0
+    best_sim = 0.9 + 0.1 * rng.random(R)
+    best_score = rng.integers(1000, 3000, size=R)
+    read_of = np.repeat(np.arange(R, dtype=np.int64), lens)
+    # coordinates of the real alignments: 1 <= start < min(L - 100, F5), end in (max(start + 100, L - F3), L]
+    L = txp_len[store.tid].astype(np.int64)
+    start = 1 + (rng.random(nnz) * (np.minimum(L - 100, F5) - 1)).astype(np.int64)
+    lo = np.maximum(start + 100, L - F3 + 1)
+    end = np.minimum(lo + (rng.random(nnz) * (L - lo + 1)).astype(np.int64), L)
+    span = end - start + 1
+    # the read's length: the first best alignment covers more than half of it
+    is_best = np.flatnonzero(logp == 0.0)
+    _, where = np.unique(read_of[is_best], return_index=True)
+    span_best = span[is_best[where]] if R else np.zeros(0, dtype=np.int64)
+    rlen = span_best + (rng.random(R) * span_best).astype(np.int64)
+    rlen = np.minimum(rlen, 2 * span_best - 1)
+
+    # groups: the R reads in order, with dropped reads scattered between them
+    n_drop = int(round(R * drop_frac / max(1e-9, 1.0 - drop_frac))) if R else 0
+    G = R + n_drop
+    is_real = np.ones(G, dtype=bool)
+    if n_drop:
+        is_real[rng.choice(G, size=n_drop, replace=False)] = False
+    drop_kind = rng.integers(0, 3, size=n_drop)
+    nd = rng.poisson(decoy_rate, size=R).astype(np.int64)
+    nf = rng.binomial(nd, 0.5).astype(np.int64)                        # decoys in front of the real records
+    n_rec = np.zeros(G, dtype=np.int64)
+    n_rec[is_real] = lens + nd
+    n_rec[~is_real] = np.where(drop_kind == 2, 2, 1)
+    group_off = np.zeros(G + 1, dtype=np.uint64)
+    np.cumsum(n_rec, out=group_off[1:])
+    base_real = group_off[:-1][is_real].astype(np.int64)
+    base_drop = group_off[:-1][~is_real].astype(np.int64)
+    rec = np.zeros(int(group_off[-1]), dtype=PROJ_RECORD)
+    read_len = np.zeros(G, dtype=np.uint64)
+    read_len[is_real] = rlen
+    read_len[~is_real] = 1000
+
+    # the real records
+    pos = np.repeat(base_real + nf, lens) + (np.arange(nnz, dtype=np.int64) - np.repeat(first, lens))
+    rec["ref_id"][pos] = store.tid
+    rec["start"][pos] = start
+    rec["end"][pos] = end
+    rec["aligned_len"][pos] = span
+    rec["query_aligned_len"][pos] = span
+    rec["similarity"][pos] = np.where(logp == 0.0, best_sim[read_of], best_sim[read_of] + logp / beta)
+    rec["aln_score"][pos] = best_score[read_of] - gap
+
+    # the decoys: kind 0 orientation, 1 aligned length, 2 3' clip, 3 5' clip, 4 similarity threshold
+    n_dec = int(nd.sum())
+    d_read = np.repeat(np.arange(R, dtype=np.int64), nd)
+    q = np.arange(n_dec, dtype=np.int64) - np.repeat(np.cumsum(nd) - nd, nd)
+    d_pos = base_real[d_read] + np.where(q < nf[d_read], q, lens[d_read] + q)
+    d_tid = rng.integers(0, T, size=n_dec)
+    d_L = txp_len[d_tid].astype(np.int64)
+    kind = rng.integers(0, 5, size=n_dec)
+    kind = np.where((kind == 2) & (d_L < F3), 0, kind)                 # (no 3' decoy on a transcript shorter than the clip)
+    rec["ref_id"][d_pos] = d_tid
+    rec["start"][d_pos] = np.where(kind == 3, F5, 1)
+    rec["end"][d_pos] = np.where(kind == 2, d_L - F3, d_L)
+    rec["aligned_len"][d_pos] = np.where(kind == 1, 10, 100)
+    rec["query_aligned_len"][d_pos] = rlen[d_read]
+    rec["similarity"][d_pos] = np.where(kind == 4, 0.3 * best_sim[d_read], best_sim[d_read] + 0.5)
+    rec["aln_score"][d_pos] = np.where(kind == 4, best_score[d_read] - 1000, best_score[d_read] + 50)
+    rec["flags"][d_pos] = np.where(kind == 0, REC_REVERSE, 0)
+
+    # the dropped reads: 0 = best similarity 0 (no counter moves), 1 = the best alignment covers a tenth of the read,
+    # 2 = two reverse-strand records, so that nothing is retained
+    for k in range(3):
+        b = base_drop[drop_kind == k]
+        for j in range(2 if k == 2 else 1):
+            t = rng.integers(0, T, size=len(b))
+            rec["ref_id"][b + j] = t
+            rec["start"][b + j] = 1
+            rec["end"][b + j] = txp_len[t]
+            rec["aligned_len"][b + j] = 100
+            rec["query_aligned_len"][b + j] = 100
+            rec["similarity"][b + j] = 0.0 if k == 0 else 0.95
+            rec["aln_score"][b + j] = 500
+            rec["flags"][b + j] = REC_REVERSE if k == 2 else 0
+    kept = np.zeros(G, dtype=np.uint32)
+    kept[is_real] = lens
+    discard = dict(discard_5p=int((kind == 3).sum()), discard_3p=int((kind == 2).sum()), discard_score=int((kind == 4).sum()),
+                   discard_aln_frac=int((drop_kind == 1).sum()), discard_aln_len=int((kind == 1).sum()),
+                   discard_ori=int((kind == 0).sum()) + 2 * int((drop_kind == 2).sum()), discard_supp=0, valid_best_aln=R,
+                   no_mapping=0, no_valid_aln=0)
+    return SyntheticProjectedRecords(filters, txp_len, rec, group_off, read_len, beta, kept, discard)
+
+
 def cell_shift(rep: int, n_txps: int) -> int:
     """Transcript-id rotation of replica ``rep`` of a cell in ``replicate_cells``."""
     return (rep * 7919) % n_txps

@@ -202,6 +202,37 @@ class DeviceStore:
             raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
         return cls._adopt(L, h, len(txp_len), device), kept, _b.discard_dict(dt)
 
+    @classmethod
+    def from_projected_records(cls, filters, txp_len, records, group_off, read_len, beta: float = 10.0,
+                               prob_source="similarity", coverage: Optional[str] = None, bin_width: int = 100,
+                               growth_rate: float = 2.0, device: int = 0, reorder_rows: int = 0, window_cap: int = 0,
+                               layout_build: int = 0, weight_coding: int = 0):
+        """Projected (genome-mode) records -> resident store in one device call (oem_store_create_projected_records):
+        AlignmentFilters::filter_projected runs on the GPU.  ``records`` / ``group_off`` / ``read_len`` / ``beta`` /
+        ``prob_source`` as in ``builder.StoreBuilder.add_projected_groups``, the rest and the returned
+        ``(store, kept, discard_table)`` as in ``from_records``.  The store is the one
+        ``StoreBuilder(...).add_projected_groups(...)`` followed by ``device_store(coverage, ...)`` gives."""
+        from . import builder as _b
+        fc = _b.filters_c(filters)
+        txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        records, group_off, read_len = _b.check_projected_batch(records, group_off, read_len)
+        po = _b.proj_opts_c(beta, prob_source)
+        n_groups = len(group_off) - 1
+        kept = np.zeros(n_groups, dtype=np.uint32)
+        dt = _lib.DiscardTableC()
+        o = _b.store_opts(reorder_rows, window_cap, layout_build, weight_coding)
+        L = _lib.lib()
+        h = C.c_void_p()
+        rc = L.oem_store_create_projected_records(C.addressof(fc), txp_len.ctypes.data, len(txp_len),
+                                                  records.ctypes.data if len(records) else None, group_off.ctypes.data,
+                                                  read_len.ctypes.data if n_groups else None, n_groups, C.addressof(po),
+                                                  bin_width, _b._model_code(coverage), growth_rate, int(device),
+                                                  C.addressof(o), kept.ctypes.data, C.addressof(dt), C.byref(h))
+        if rc != _lib.OEM_OK:
+            msg = L.oem_last_error()
+            raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
+        return cls._adopt(L, h, len(txp_len), device), kept, _b.discard_dict(dt)
+
     def _check(self, rc: int) -> None:
         if rc != _lib.OEM_OK:
             msg = self._lib.oem_last_error()
