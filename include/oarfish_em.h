@@ -597,6 +597,39 @@ int oem_em_run_cells_coverage_sparse(const uint64_t *cell_row_off, uint32_t n_ce
                                      int device, uint32_t max_iter, double conv_thresh,
                                      double *out_cov_prob, oem_cells_result **out);
 
+/* single_cell.rs:104-188 for all cells in one call: AlignmentFilters::filter over every cell's records into the cell's
+ * own store, the per-cell coverage model if asked, em::em, the entries > 0.  records / group_off / n_groups are a
+ * batch as oem_builder_add_groups takes it (group g = one read = records[group_off[g] .. group_off[g + 1])); cell c
+ * owns the groups [cell_group_off[c], cell_group_off[c + 1]); cells without groups are allowed.  model: -1 no
+ * coverage model, 0 logistic, 1 binomial (bin_width, growth_rate as in oem_em_run_cells_coverage_sparse).
+ *
+ * Per cell the result equals the long way round -- oem_builder_create(filters, txp_len, n_txps), oem_builder_add_groups
+ * over that cell's groups only, oem_builder_export, then oem_em_run_cells_sparse (model -1) or
+ * oem_em_run_cells_coverage_sparse (model 0 / 1) on the concatenation of the exports -- up to floating-point summation
+ * order (which group of cells a cell lands in may change the tile layout, never the problem).  Exactly equal are:
+ * out_kept (n_groups, optional), what add_groups returns for each group; table c of oem_cells_result_discard_tables,
+ * that cell's builder's discard table.  A cell whose reads are all dropped has no entries and the oem_run_info of a
+ * cell without reads.  The records are filtered on the device one group of cells at a time and the filtered CSR never
+ * exists on the host; a group whose filter has to take the host loop (score_prob_denom not finite and positive, a gap
+ * table above 2^22 entries, a mapped score beyond +-2^24: see oem_builder_add_groups_device) takes it, with the same
+ * result.
+ *
+ * Argument errors are reported before any device use: those of oem_store_create_records (filters / txp_len NULL,
+ * n_txps = 0, model, bin_width = 0 with a model, group_off NULL / not from 0 / decreasing, records NULL), those of the
+ * cells calls, and cell_group_off NULL, not from 0, decreasing or not ending at n_groups.  A mapped record whose ref_id
+ * is not below n_txps is OEM_ERR_ARG naming the cell and the first such record of the first such group of cells; an
+ * alignment outside its transcript under a coverage model is OEM_ERR_STATE naming the cell.  Without a device:
+ * OEM_ERR_NO_DEVICE.  *out = NULL on any failure. */
+int oem_em_run_cells_records_sparse(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                    const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups,
+                                    const uint64_t *cell_group_off, uint32_t n_cells,
+                                    uint32_t bin_width, int model, double growth_rate,
+                                    int device, uint32_t max_iter, double conv_thresh,
+                                    uint32_t *out_kept /* n_groups, or NULL */, oem_cells_result **out);
+/* The per-cell DiscardTable of a result that came from records (oem_em_run_cells_records_sparse, a records session):
+ * n_cells entries, in result order.  OEM_ERR_STATE for a result that did not; NULL arguments are OEM_ERR_ARG. */
+int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out);
+
 /* A per-cell SESSION: the caller pushes cells one by one, from any number of threads, as they become available
  * (single_cell.rs:96-193: N workers each pop one cell and build its private store).  The library stages the cells,
  * cuts them into groups, runs every group through the batched per-cell driver while later cells still arrive, and
@@ -646,6 +679,21 @@ int oem_cells_stream_create(const oem_cells_stream_opts *opts, const uint64_t *t
 int oem_cells_stream_push(oem_cells_stream *s, const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
                           const uint32_t *aln_start, const uint32_t *aln_end, uint64_t n_reads, uint64_t nnz,
                           uint64_t *out_ticket);
+/* Turns a fresh session (no cell pushed yet) into a RECORDS session: cells are then pushed as their alignment records
+ * (oem_cells_stream_push_records) and filtered on the device, as oem_em_run_cells_records_sparse does; with
+ * coverage = 1 the coverage model runs on the filter's coordinates.  filters and txp_len (n_txps entries) are copied.
+ * NULL arguments: OEM_ERR_ARG.  Once a cell has been pushed, or after finish: OEM_ERR_STATE.  On a records session
+ * oem_cells_stream_push returns OEM_ERR_STATE; on a plain one oem_cells_stream_push_records does. */
+int oem_cells_stream_set_filters(oem_cells_stream *s, const oem_filters *filters, const uint64_t *txp_len);
+/* One cell of a records session: its reads' records as a batch (group_off: n_groups + 1 entries from 0).  In every
+ * other respect as oem_cells_stream_push: thread-safe; checked on the calling thread (group_off from 0 and not
+ * decreasing, records present; an argument error rejects that cell only and uses no ticket); the arrays are copied,
+ * into page-locked staging, 40 B per record; tickets are issued the same way; the same back-pressure, its budget
+ * (max_staged_nnz, group_nnz) counted in records; the same sticky device errors.  A ref_id that is not below n_txps is
+ * found on the device: it fails the group, is sticky and names the cell's ticket ("cell <ticket>") and the record's
+ * index within its group of cells.  After finish, oem_cells_result_discard_tables gives the cells' tables. */
+int oem_cells_stream_push_records(oem_cells_stream *s, const oem_aln_record *records, const uint64_t *group_off,
+                                  uint64_t n_groups, uint64_t *out_ticket);
 /* Runs what is still staged, waits for every group and returns the cells in ticket order as an ordinary
  * oem_cells_result (oem_cells_result_dims / _copy / _destroy; infos included).  Per cell the result is what
  * oem_em_run_cells_sparse (coverage = 1: oem_em_run_cells_coverage_sparse) gives for that cell, up to floating-point

@@ -63,8 +63,9 @@ ABI_SYMBOLS = [
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
-    "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_finish", "oem_cells_stream_info",
-    "oem_cells_stream_destroy",
+    "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables",
+    "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
+    "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
     "oem_comm_set_option", "oem_comm_info", "oem_store_attach_comm",
     "oem_time_m_step", "oem_time_em_iters", "oem_time_bootstrap_passes", "oem_time_allreduce",
@@ -210,6 +211,11 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_result_destroy.restype = None
     L.oem_em_run_cells_coverage_sparse.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u64, u64, u32, u32, i32, f64, i32,
                                                    u32, f64, vp, C.POINTER(vp)]
+    L.oem_em_run_cells_records_sparse.argtypes = [vp, vp, u32, vp, vp, u64, vp, u32, u32, i32, f64, i32, u32, f64, vp,
+                                                  C.POINTER(vp)]
+    L.oem_cells_result_discard_tables.argtypes = [vp, vp]
+    L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
+    L.oem_cells_stream_push_records.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
     L.oem_cells_stream_push.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]
     L.oem_cells_stream_finish.argtypes = [vp, C.POINTER(vp)]
@@ -264,6 +270,7 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_filter_last_timing.argtypes = [vp]
         L.oem_debug_mtx_last_timing.argtypes = [vp]
         L.oem_debug_proj_last_pass.argtypes = [vp]
+        L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         _testing = L
     return _testing
 

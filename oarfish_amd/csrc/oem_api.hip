@@ -167,7 +167,7 @@ void free_store(oem_store *s)
 }
 
 // (the adopt: create_store_layout's upload_csr)
-int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *tid)
+int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *tid, const uint32_t *d_tid)
 {
     resident->row_ptr = (uint32_t *)s->csr.row_ptr;
     resident->tid = s->csr.tid;
@@ -177,7 +177,8 @@ int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *ti
     s->csr.tid = nullptr;
     s->csr.w64 = nullptr;
     s->csr.w32 = nullptr;
-    if (s->csr.nnz && hipMemcpy(resident->tid, tid, sizeof(uint32_t) * s->csr.nnz, hipMemcpyHostToDevice) != hipSuccess)
+    if (s->csr.nnz && hipMemcpy(resident->tid, tid ? tid : d_tid, sizeof(uint32_t) * s->csr.nnz,
+                                tid ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) != hipSuccess)
         return fail(OEM_ERR_HIP, "oem_em_run_cells: restoring the transcript ids failed");
     return OEM_OK;
 }

@@ -3,6 +3,7 @@
 // declines run cell after cell over the caller-order CSR.
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -190,7 +191,7 @@ int create_batched_store(const CellsRun &run, const CellsGroup &g, StorePtr *out
     OEM_TRY(create_store_impl(g.row_ptr, g.tid, g.as_prob, g.cov_prob, g.n_reads, g.nnz, g.n_cells * run.n_txps, run.device, &opts,
                               s.get(), &rl, g.resident));
     if (!s->tiled.present) // the CSR goes back with the caller's ids (they were relabelled)
-        return g.resident ? release_resident_csr(s.get(), g.resident, g.tid) : OEM_OK;
+        return g.resident ? release_resident_csr(s.get(), g.resident, g.tid, g.d_tid_orig) : OEM_OK;
     *out = std::move(s);
     return OEM_OK;
 }
@@ -417,6 +418,114 @@ int check_cell_row_off(const char *who, const uint64_t *cell_row_off, uint32_t n
     return OEM_OK;
 }
 
+// ---- the cut and the workers
+std::vector<std::pair<uint32_t, uint32_t>> cut_cells_groups(const uint64_t *cell_off, uint32_t n_cells, const uint64_t *ptr,
+                                                            uint32_t n_txps)
+{
+    const uint64_t nnz = n_cells ? ptr[cell_off[n_cells]] - ptr[cell_off[0]] : 0;
+    // Cells are independent problems, so a large experiment is cut into groups of consecutive cells
+    // that bound the batched store (transcript space < 2^32, <= 2^30 alignments, and the layout
+    // builder's tile x bucket table); each group is one batched run on the device.
+    const uint64_t max_group_nnz = cells_max_group_nnz();
+    std::vector<std::pair<uint32_t, uint32_t>> groups;
+    uint32_t c0 = 0;
+    while (c0 < n_cells) {
+        uint32_t c1 = c0 + 1;
+        while (c1 < n_cells) {
+            const uint64_t cells = (uint64_t)(c1 + 1 - c0);
+            const uint64_t reads = cell_off[c1 + 1] - cell_off[c0];
+            const uint64_t gnnz = ptr[cell_off[c1 + 1]] - ptr[cell_off[c0]];
+            if (!cells_group_fits(cells, reads, gnnz, n_txps, max_group_nnz)) break;
+            ++c1;
+        }
+        groups.emplace_back(c0, c1);
+        c0 = c1;
+    }
+    // One large group only (BASELINE configs[4]'s slice of one GPU: 625 cells, 250 M alignments, 2 GB of caller arrays):
+    // a quarter of the cells is cut off as a group of its own, so that the second worker uploads and lays out the rest
+    // under the head's EM loop instead of the device idling through the whole upload and layout build (~70 ms of a
+    // 0.67 s call).  Measured (scripts/cells_groups_exp.sh, three rounds): heads of 40 / 80 / 160 / 312 of 625 cells
+    // +7 / -0.5 / -3.4 / -0.5 % against one group -- a small head's own loop runs its few tiles badly, two halves just
+    // share the device.
+    if (groups.size() == 1 && n_cells >= (uint64_t)knob("OEM_CELLS_SPLIT_CELLS", 64) &&
+        nnz >= (uint64_t)knob("OEM_CELLS_SPLIT_NNZ", 64l << 20)) { // testing build: split small calls too
+        const long head = knob("OEM_CELLS_HEAD", (long)(kCellsHeadDiv ? n_cells / kCellsHeadDiv : 0));
+        if (head >= 2 && (uint32_t)head + 2 <= n_cells) {
+            groups.clear();
+            groups.emplace_back(0u, (uint32_t)head);
+            groups.emplace_back((uint32_t)head, n_cells);
+        }
+    }
+    return groups;
+}
+
+int run_cells_workers(const char *who, CellsRun run, const std::vector<std::pair<uint32_t, uint32_t>> &groups,
+                      const std::function<int(size_t, const CellsRun &, CellsGroupPath *)> &one)
+{
+    // Groups are independent runs.  With several of them two host threads draw groups from one counter, each group
+    // on its own stream: one group's upload, layout build and read-back run under the other's EM loop, and the tail
+    // of a loop -- the few cells that run into max_iter, a handful of live tiles per pass -- shares the device with
+    // the other group's full passes instead of leaving it idle (single_cell.rs:96-150 runs its cells on N worker
+    // threads for the same reason).
+    std::vector<CellsGroupPath> paths(groups.size()); // (each group's slot is written by the worker that runs it)
+    for (size_t g = 0; g < groups.size(); ++g) paths[g] = CellsGroupPath{groups[g].first, groups[g].second, 0, LaunchRecord()};
+    CellsTiming timing;
+    run.timing = &timing;
+    std::atomic<size_t> next{0};
+    constexpr int kMaxWorkers = 4;
+    int n_workers = (int)knob("OEM_CELLS_WORKERS", 2);
+    if (n_workers > kMaxWorkers) n_workers = kMaxWorkers;
+    if ((size_t)n_workers > groups.size()) n_workers = (int)groups.size();
+    if (n_workers < 1) n_workers = 1;
+    int rcs[kMaxWorkers] = {OEM_OK, OEM_OK, OEM_OK, OEM_OK}; // each worker's own; read by the others only after the join
+    std::atomic<bool> failed{false};                         // ... and this is what they stop on
+    std::string errs[kMaxWorkers];
+    size_t fail_group[kMaxWorkers] = {~(size_t)0, ~(size_t)0, ~(size_t)0, ~(size_t)0}; // (groups are drawn in order: the lowest
+                                                                                      // failed group is the same every time)
+    auto work = [&](int wk) {
+        if (wk != 0 && hipSetDevice(run.device) != hipSuccess) {
+            rcs[wk] = OEM_ERR_HIP;
+            errs[wk] = "hipSetDevice failed in a per-cell worker";
+            failed.store(true);
+            return;
+        }
+        try {
+            for (;;) {
+                const size_t g = next.fetch_add(1);
+                if (g >= groups.size() || failed.load()) break;
+                rcs[wk] = one(g, run, &paths[g]);
+                if (rcs[wk] != OEM_OK) fail_group[wk] = g;
+                if (rcs[wk] != OEM_OK) break;
+            }
+        } catch (const std::exception &e) {
+            rcs[wk] = fail(OEM_ERR_OOM, "per-cell worker: %s", e.what());
+        } catch (...) {
+            rcs[wk] = fail(OEM_ERR_STATE, "per-cell worker: unknown C++ exception");
+        }
+        if (rcs[wk] != OEM_OK) failed.store(true);
+        if (rcs[wk] != OEM_OK && errs[wk].empty()) errs[wk] = last_error_text(); // (the message is thread-local)
+    };
+    {
+        struct Joiner { // (a std::thread constructor that throws must not leave joinable threads behind)
+            std::vector<std::thread> th;
+            ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
+        } pool;
+        try {
+            for (int wk = 1; wk < n_workers; ++wk) pool.th.emplace_back(work, wk);
+        } catch (...) { // fewer threads: the ones that started take all the groups
+        }
+        work(0);
+    }
+    t_cells_loop_ms = timing.loop_ms();
+    t_cells_batched_passes = timing.passes;
+    t_cells_paths = std::move(paths);
+    int first = -1;
+    for (int wk = 0; wk < kMaxWorkers; ++wk)
+        if (rcs[wk] != OEM_OK && (first < 0 || fail_group[wk] < fail_group[first])) first = wk;
+    if (first >= 0) return fail(rcs[first], "%s", errs[first].c_str());
+    return OEM_OK;
+}
+
 namespace {
 
 // ---- the one-call form
@@ -520,105 +629,21 @@ int run_cells(const char *who, CellsInput in, CellsRun run, double *dense, std::
     std::vector<double> cov_fixed;
     if (in.cov_prob && zero_nan_rows(row_ptr, in.cov_prob, n_reads, nnz, &cov_fixed)) in.cov_prob = cov_fixed.data();
 
-    // Cells are independent problems, so a large experiment is cut into groups of consecutive cells
-    // that bound the batched store (transcript space < 2^32, <= 2^30 alignments, and the layout
-    // builder's tile x bucket table); each group is one batched run on the device.
-    const uint64_t max_group_nnz = cells_max_group_nnz();
-    std::vector<std::pair<uint32_t, uint32_t>> groups;
-    uint32_t c0 = 0;
-    while (c0 < n_cells) {
-        uint32_t c1 = c0 + 1;
-        while (c1 < n_cells) {
-            const uint64_t cells = (uint64_t)(c1 + 1 - c0);
-            const uint64_t reads = cell_row_off[c1 + 1] - cell_row_off[c0];
-            const uint64_t gnnz = row_ptr[cell_row_off[c1 + 1]] - row_ptr[cell_row_off[c0]];
-            if (!cells_group_fits(cells, reads, gnnz, n_txps, max_group_nnz)) break;
-            ++c1;
-        }
-        groups.emplace_back(c0, c1);
-        c0 = c1;
-    }
-    // One large group only (BASELINE configs[4]'s slice of one GPU: 625 cells, 250 M alignments, 2 GB of caller arrays):
-    // a quarter of the cells is cut off as a group of its own, so that the second worker uploads and lays out the rest
-    // under the head's EM loop instead of the device idling through the whole upload and layout build (~70 ms of a
-    // 0.67 s call).  Measured (scripts/cells_groups_exp.sh, three rounds): heads of 40 / 80 / 160 / 312 of 625 cells
-    // +7 / -0.5 / -3.4 / -0.5 % against one group -- a small head's own loop runs its few tiles badly, two halves just
-    // share the device.
-    if (groups.size() == 1 && n_cells >= (uint64_t)knob("OEM_CELLS_SPLIT_CELLS", 64) &&
-        nnz >= (uint64_t)knob("OEM_CELLS_SPLIT_NNZ", 64l << 20)) { // testing build: split small calls too
-        const long head = knob("OEM_CELLS_HEAD", (long)(kCellsHeadDiv ? n_cells / kCellsHeadDiv : 0));
-        if (head >= 2 && (uint32_t)head + 2 <= n_cells) {
-            groups.clear();
-            groups.emplace_back(0u, (uint32_t)head);
-            groups.emplace_back((uint32_t)head, n_cells);
-        }
-    }
-    // Groups are independent runs.  With several of them two host threads draw groups from one counter, each group
-    // on its own stream: one group's upload, layout build and read-back run under the other's EM loop, and the tail
-    // of a loop -- the few cells that run into max_iter, a handful of live tiles per pass -- shares the device with
-    // the other group's full passes instead of leaving it idle (single_cell.rs:96-150 runs its cells on N worker
-    // threads for the same reason).
+    const std::vector<std::pair<uint32_t, uint32_t>> groups = cut_cells_groups(cell_row_off, n_cells, row_ptr, n_txps);
     if (blocks) blocks->assign(groups.size(), SparseBlock());
-    std::vector<CellsGroupPath> paths(groups.size()); // (each group's slot is written by the worker that runs it)
-    for (size_t g = 0; g < groups.size(); ++g) paths[g] = CellsGroupPath{groups[g].first, groups[g].second, 0, LaunchRecord()};
-    CellsTiming timing;
-    run.timing = &timing;
-    std::atomic<size_t> next{0};
-    constexpr int kMaxWorkers = 4;
-    int n_workers = (int)knob("OEM_CELLS_WORKERS", 2);
-    if (n_workers > kMaxWorkers) n_workers = kMaxWorkers;
-    if ((size_t)n_workers > groups.size()) n_workers = (int)groups.size();
-    if (n_workers < 1) n_workers = 1;
-    int rcs[kMaxWorkers] = {OEM_OK, OEM_OK, OEM_OK, OEM_OK}; // each worker's own; read by the others only after the join
-    std::atomic<bool> failed{false};                         // ... and this is what they stop on
-    std::string errs[kMaxWorkers];
-    auto work = [&](int wk) {
-        if (wk != 0 && hipSetDevice(run.device) != hipSuccess) {
-            rcs[wk] = OEM_ERR_HIP;
-            errs[wk] = "hipSetDevice failed in a per-cell worker";
-            failed.store(true);
-            return;
-        }
-        try {
-            for (;;) {
-                const size_t g = next.fetch_add(1);
-                if (g >= groups.size() || failed.load()) break;
-                bool batched = false;
-                CellsSlice sl;
-                slice_cells(in, run, groups[g].first, groups[g].second, &sl);
-                sl.g.out_dense = dense ? dense + (uint64_t)groups[g].first * n_txps : nullptr;
-                sl.g.blk = blocks ? &(*blocks)[g] : nullptr;
-                sl.g.infos = infos ? infos + groups[g].first : nullptr;
-                sl.g.launch = &paths[g].launch;
-                rcs[wk] = run_cells_group(run, sl.g, &batched);
-                paths[g].batched = batched ? 1u : 0u;
-                if (rcs[wk] != OEM_OK) break;
-            }
-        } catch (const std::exception &e) {
-            rcs[wk] = fail(OEM_ERR_OOM, "per-cell worker: %s", e.what());
-        } catch (...) {
-            rcs[wk] = fail(OEM_ERR_STATE, "per-cell worker: unknown C++ exception");
-        }
-        if (rcs[wk] != OEM_OK) failed.store(true);
-        if (rcs[wk] != OEM_OK && errs[wk].empty()) errs[wk] = last_error_text(); // (the message is thread-local)
-    };
-    {
-        struct Joiner { // (a std::thread constructor that throws must not leave joinable threads behind)
-            std::vector<std::thread> th;
-            ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
-        } pool;
-        try {
-            for (int wk = 1; wk < n_workers; ++wk) pool.th.emplace_back(work, wk);
-        } catch (...) { // fewer threads: the ones that started take all the groups
-        }
-        work(0);
-    }
+    OEM_TRY(run_cells_workers(who, run, groups, [&](size_t g, const CellsRun &grun, CellsGroupPath *path) -> int {
+        bool batched = false;
+        CellsSlice sl;
+        slice_cells(in, grun, groups[g].first, groups[g].second, &sl);
+        sl.g.out_dense = dense ? dense + (uint64_t)groups[g].first * n_txps : nullptr;
+        sl.g.blk = blocks ? &(*blocks)[g] : nullptr;
+        sl.g.infos = infos ? infos + groups[g].first : nullptr;
+        sl.g.launch = &path->launch;
+        const int rc = run_cells_group(grun, sl.g, &batched);
+        path->batched = batched ? 1u : 0u;
+        return rc;
+    }));
     tm_all.lap("cells: all groups");
-    t_cells_loop_ms = timing.loop_ms();
-    t_cells_batched_passes = timing.passes;
-    t_cells_paths = std::move(paths);
-    for (int wk = 0; wk < kMaxWorkers; ++wk)
-        if (rcs[wk] != OEM_OK) return fail(rcs[wk], "%s", errs[wk].c_str());
     return OEM_OK;
 }
 

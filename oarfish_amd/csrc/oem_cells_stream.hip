@@ -16,6 +16,12 @@
 //             host pass over the reads of the group).  The store adopts these buffers (ResidentCsr), and
 //             run_cells_group does the rest exactly as for a group of a one-call run, fallbacks included.
 //   finish    closes the last group, joins the workers and concatenates the groups' blocks in ticket order.
+//
+// A RECORDS session (oem_cells_stream_set_filters, oem_cells_stream_push_records) stages the cells' alignment records
+// instead, 40 B each, with each cell's group offsets where the row pointers would be; the budgets count records.  Its
+// worker concatenates the group offsets on the host (8 B per read) and runs the records-to-group step of
+// oem_em_run_cells_records_sparse (run_records_group, oem_cells_records.hip) straight from the page-locked staging:
+// filter, per-cell offsets and discard tables on the device, then run_cells_group.  k_stream_row_ptr is not needed there.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -81,6 +87,7 @@ struct Staging {
     uint64_t *rp = nullptr;
     uint32_t *tid = nullptr, *start = nullptr, *end = nullptr;
     float *p = nullptr;
+    oem_aln_record *rec = nullptr; // a records session: the records (cap_nnz of them); rp holds the group offsets
     Staging() = default;
     Staging(const Staging &) = delete;
     Staging &operator=(const Staging &) = delete;
@@ -89,10 +96,10 @@ struct Staging {
         if (pinned) (void)hipHostFree(base);
         else free(base);
     }
-    static std::unique_ptr<Staging> make(uint64_t cap_nnz, uint64_t cap_rp, bool coverage, bool try_pinned)
+    static std::unique_ptr<Staging> make(uint64_t cap_nnz, uint64_t cap_rp, bool coverage, bool try_pinned, bool records)
     {
         std::unique_ptr<Staging> s(new Staging());
-        const size_t bytes = sizeof(uint64_t) * cap_rp + (coverage ? 16 : 8) * cap_nnz + 64;
+        const size_t bytes = sizeof(uint64_t) * cap_rp + (records ? sizeof(oem_aln_record) : coverage ? 16 : 8) * cap_nnz + 64;
         if (try_pinned && hipHostMalloc(&s->base, bytes, hipHostMallocPortable) == hipSuccess) {
             s->pinned = true;
         } else {
@@ -105,6 +112,10 @@ struct Staging {
         char *q = (char *)s->base;
         s->rp = (uint64_t *)q;
         q += sizeof(uint64_t) * cap_rp;
+        if (records) {
+            s->rec = (oem_aln_record *)q;
+            return s;
+        }
         s->tid = (uint32_t *)q;
         q += sizeof(uint32_t) * cap_nnz;
         s->p = (float *)q;
@@ -152,6 +163,16 @@ struct Group {
 struct GroupResult {
     SparseBlock blk;
     std::vector<oem_run_info> infos;
+    std::vector<oem_discard_table> tables; // a records session: the cells' discard tables
+};
+
+// what a push stages: a cell's CSR, or its records
+struct CellArrays {
+    const uint64_t *rp = nullptr; // row pointers, or the group offsets of the records
+    const uint32_t *tid = nullptr;
+    const float *p = nullptr;
+    const uint32_t *start = nullptr, *end = nullptr;
+    const oem_aln_record *rec = nullptr;
 };
 
 } // namespace
@@ -165,6 +186,8 @@ struct oem_cells_stream {
     uint32_t group_cells = 0;
     std::vector<uint64_t> txp_len;
     CellsCoverage cov;
+    bool records_mode = false; // set by oem_cells_stream_set_filters before the first push
+    RecordsFilter rf;
 
     mutable std::mutex mu;
     std::condition_variable cv_work, cv_space, cv_copy;
@@ -200,7 +223,7 @@ struct oem_cells_stream {
         }
         const bool try_pinned = arenas_pinned < kPinnedArenas && hipSetDevice(o.device) == hipSuccess;
         StageTimer tm;
-        std::unique_ptr<Staging> s = Staging::make(need_nnz, need_rp, o.coverage != 0, try_pinned);
+        std::unique_ptr<Staging> s = Staging::make(need_nnz, need_rp, o.coverage != 0, try_pinned, records_mode);
         if (s->pinned) ++arenas_pinned;
         if (tm.on)
             fprintf(stderr, "[oem] stream: new %s arena for %llu alignments, %llu row pointers\n", s->pinned ? "pinned" : "pageable",
@@ -237,6 +260,8 @@ struct oem_cells_stream {
     }
 
     int run_group(Group &g, hipStream_t st, GroupResult *out, bool *batched, bool *uploaded);
+    int run_records(Group &g, GroupResult *out, bool *batched);
+    int push_cell(const char *who, bool records, const CellArrays &a, uint64_t n_reads, uint64_t nnz, uint64_t *out_ticket);
     void work(int wk);
 };
 
@@ -308,6 +333,34 @@ int oem_cells_stream::run_group(Group &g, hipStream_t st, GroupResult *out, bool
     return OEM_OK;
 }
 
+// One closed group of a records session: the group-wide offsets, then the records-to-group step of the one-call form.
+int oem_cells_stream::run_records(Group &g, GroupResult *out, bool *batched)
+{
+    const uint32_t nc = g.n_cells;
+    std::vector<uint64_t> goff(g.n_reads + 1); // (reads = record groups, alignments = records)
+    for (uint32_t c = 0; c < nc; ++c) {
+        const uint64_t r0 = g.read_off[c], n = g.read_off[c + 1] - r0;
+        const uint64_t *loc = g.st->rp + r0 + c;
+        for (uint64_t i = 0; i < n; ++i) goff[r0 + i] = g.aln_off[c] + loc[i];
+    }
+    goff[g.n_reads] = g.nnz;
+    out->infos.assign(nc, oem_run_info{});
+    out->tables.assign(nc, oem_discard_table{});
+    RecordsGroup rg;
+    rg.records = g.st->rec;
+    rg.pinned = g.st->pinned;
+    rg.group_off = goff.data();
+    rg.n_groups = g.n_reads;
+    rg.cell_group_off = g.read_off.data();
+    rg.n_cells = nc;
+    rg.first_cell = g.first_ticket;
+    rg.out_tables = out->tables.data();
+    rg.blk = &out->blk;
+    rg.infos = out->infos.data();
+    CellsRun run{o.n_txps, o.device, o.max_iter, o.conv_thresh, o.coverage ? &cov : nullptr};
+    return run_records_group("oem_cells_stream", run, rf, rg, batched);
+}
+
 void oem_cells_stream::work(int wk)
 {
     hipStream_t st = nullptr;
@@ -338,7 +391,7 @@ void oem_cells_stream::work(int wk)
         std::string msg;
         if (!skip) {
             try {
-                rc = run_group(*g, st, &res, &batched, &uploaded);
+                rc = records_mode ? run_records(*g, &res, &batched) : run_group(*g, st, &res, &batched, &uploaded);
             } catch (const std::bad_alloc &) {
                 rc = fail(OEM_ERR_OOM, "oem_cells_stream: host allocation failed in a device worker");
             } catch (const std::exception &e) {
@@ -411,6 +464,127 @@ extern "C" int oem_cells_stream_create(const oem_cells_stream_opts *opts, const 
     OEM_API_END("oem_cells_stream_create")
 }
 
+// The session's half of a push (the cell has been checked by its entry point): the cell's place in the open group
+// under the lock -- group rule, back-pressure, arena growth -- and the copy of its arrays outside it.  n_reads / nnz:
+// reads and alignments, or record groups and records.
+int oem_cells_stream::push_cell(const char *who, bool records, const CellArrays &a, uint64_t n_reads, uint64_t nnz,
+                                uint64_t *out_ticket)
+{
+    std::unique_lock<std::mutex> lk(mu);
+    ++pushes_in_flight;
+    struct InFlight { // (mu is held whenever this scope is left)
+        oem_cells_stream *s;
+        ~InFlight() { --s->pushes_in_flight; }
+    } in_flight{this};
+    const uint64_t hard_nnz = cells_max_group_nnz();
+    Group *g = nullptr;
+    try {
+        for (;;) {
+            if (finish_called || cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+            if (records != records_mode)
+                return fail(OEM_ERR_STATE, records ? "%s: not a records session (oem_cells_stream_set_filters)"
+                                                   : "%s: a records session takes cells through oem_cells_stream_push_records", who);
+            if (sticky_rc != OEM_OK) return fail(sticky_rc, "%s", sticky_msg.c_str());
+            if (next_ticket >= 0xffffffffull) return fail(OEM_ERR_STATE, "%s: a session holds fewer than 2^32 cells", who);
+            g = open.get();
+            // the driver's own group rule: the cell starts a new group when it would break the open one's
+            if (g && g->n_cells > 0 && !cells_group_fits((uint64_t)g->n_cells + 1, g->n_reads + n_reads, g->nnz + nnz, o.n_txps, hard_nnz)) {
+                close_open();
+                continue;
+            }
+            // back-pressure; what waits in the open group goes to the workers first, or nothing would ever drain
+            if (staged_nnz > 0 && staged_nnz + nnz > max_staged) {
+                close_open();
+                const auto t0 = std::chrono::steady_clock::now();
+                cv_space.wait(lk);
+                blocked_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+                continue;
+            }
+            if (!g) {
+                std::unique_ptr<Group> ng(new Group());
+                ng->st = take_arena(std::max(arena_nnz, nnz), std::max(arena_rp, n_reads + 1));
+                ng->index = results.size();
+                ng->first_ticket = next_ticket;
+                results.emplace_back();
+                open = std::move(ng);
+                g = open.get();
+            }
+            if (g->nnz + nnz > g->st->cap_nnz || g->rp_used() + n_reads + 1 > g->st->cap_rp) {
+                const bool full_size = g->st->cap_nnz >= full_arena_nnz() && g->st->cap_rp >= full_arena_rp();
+                if (full_size && g->n_cells > 0) { // a full-sized arena is full: the group is large enough
+                    close_open();
+                    continue;
+                }
+                if (g->pending) { // pushes still copy into the arena: it cannot move yet
+                    cv_copy.wait(lk);
+                    continue;
+                }
+                // grow x4 towards the full size (or to what a single large cell needs); the staged part moves over
+                uint64_t cn = g->st->cap_nnz, cr = g->st->cap_rp;
+                while (cn < g->nnz + nnz) cn = std::max(cn * 4, g->nnz + nnz);
+                while (cr < g->rp_used() + n_reads + 1) cr = std::max(cr * 4, g->rp_used() + n_reads + 1);
+                if (g->nnz + nnz <= full_arena_nnz()) cn = std::min(cn, full_arena_nnz());
+                if (g->rp_used() + n_reads + 1 <= full_arena_rp()) cr = std::min(cr, full_arena_rp());
+                std::unique_ptr<Staging> old = std::move(g->st);
+                g->st = take_arena(cn, cr);
+                std::memcpy(g->st->rp, old->rp, sizeof(uint64_t) * g->rp_used());
+                if (records) {
+                    std::memcpy(g->st->rec, old->rec, sizeof(oem_aln_record) * g->nnz);
+                } else {
+                    std::memcpy(g->st->tid, old->tid, sizeof(uint32_t) * g->nnz);
+                    std::memcpy(g->st->p, old->p, sizeof(float) * g->nnz);
+                }
+                if (!records && o.coverage) {
+                    std::memcpy(g->st->start, old->start, sizeof(uint32_t) * g->nnz);
+                    std::memcpy(g->st->end, old->end, sizeof(uint32_t) * g->nnz);
+                }
+                if (old->pinned) --arenas_pinned; // (released here: smaller than what groups need by now)
+                old.reset();
+                arena_nnz = std::min(std::max(arena_nnz, cn), full_arena_nnz());
+                arena_rp = std::min(std::max(arena_rp, cr), full_arena_rp());
+                continue;
+            }
+            g->read_off.reserve(g->read_off.size() + 1); // (so that taking the cell's place below cannot throw)
+            g->aln_off.reserve(g->aln_off.size() + 1);
+            break;
+        }
+    } catch (const std::bad_alloc &) { // staging could not be allocated: the session cannot keep its promise
+        set_sticky(OEM_ERR_OOM, "oem_cells_stream_push: host allocation of the staging memory failed");
+        cv_space.notify_all();
+        return fail(OEM_ERR_OOM, "%s", sticky_msg.c_str());
+    }
+    // the cell's place: ticket, offsets; the arrays are copied outside the lock
+    const uint64_t ticket = next_ticket++;
+    const uint64_t rp_at = g->rp_used(), a_at = g->nnz;
+    Staging *st = g->st.get();
+    g->n_cells += 1;
+    g->n_reads += n_reads;
+    g->nnz += nnz;
+    g->read_off.push_back(g->n_reads);
+    g->aln_off.push_back(g->nnz);
+    g->pending += 1;
+    total_nnz += nnz;
+    staged_nnz += nnz;
+    if (g->nnz >= group_nnz || g->n_cells >= group_cells) close_open(); // (the worker waits for the copy below)
+    lk.unlock();
+    std::memcpy(st->rp + rp_at, a.rp, sizeof(uint64_t) * (n_reads + 1));
+    if (nnz && records) {
+        std::memcpy(st->rec + a_at, a.rec, sizeof(oem_aln_record) * nnz);
+    } else if (nnz) {
+        std::memcpy(st->tid + a_at, a.tid, sizeof(uint32_t) * nnz);
+        std::memcpy(st->p + a_at, a.p, sizeof(float) * nnz);
+        if (o.coverage) {
+            std::memcpy(st->start + a_at, a.start, sizeof(uint32_t) * nnz);
+            std::memcpy(st->end + a_at, a.end, sizeof(uint32_t) * nnz);
+        }
+    }
+    lk.lock();
+    g->pending -= 1;
+    cv_copy.notify_all();
+    if (out_ticket) *out_ticket = ticket;
+    return OEM_OK;
+}
+
 extern "C" int oem_cells_stream_push(oem_cells_stream *s, const uint64_t *row_ptr, const uint32_t *tid, const float *as_prob,
                                      const uint32_t *aln_start, const uint32_t *aln_end, uint64_t n_reads, uint64_t nnz,
                                      uint64_t *out_ticket)
@@ -429,110 +603,43 @@ extern "C" int oem_cells_stream_push(oem_cells_stream *s, const uint64_t *row_pt
         return fail(OEM_ERR_OOM, "%s: host allocation failed", who);
     }
 
-    std::unique_lock<std::mutex> lk(s->mu);
-    ++s->pushes_in_flight;
-    struct InFlight { // (mu is held whenever this scope is left)
-        oem_cells_stream *s;
-        ~InFlight() { --s->pushes_in_flight; }
-    } in_flight{s};
-    const uint64_t hard_nnz = cells_max_group_nnz();
-    Group *g = nullptr;
-    try {
-        for (;;) {
-            if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
-            if (s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str());
-            if (s->next_ticket >= 0xffffffffull) return fail(OEM_ERR_STATE, "%s: a session holds fewer than 2^32 cells", who);
-            g = s->open.get();
-            // the driver's own group rule: the cell starts a new group when it would break the open one's
-            if (g && g->n_cells > 0 && !cells_group_fits((uint64_t)g->n_cells + 1, g->n_reads + n_reads, g->nnz + nnz, s->o.n_txps, hard_nnz)) {
-                s->close_open();
-                continue;
-            }
-            // back-pressure; what waits in the open group goes to the workers first, or nothing would ever drain
-            if (s->staged_nnz > 0 && s->staged_nnz + nnz > s->max_staged) {
-                s->close_open();
-                const auto t0 = std::chrono::steady_clock::now();
-                s->cv_space.wait(lk);
-                s->blocked_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-                continue;
-            }
-            if (!g) {
-                std::unique_ptr<Group> ng(new Group());
-                ng->st = s->take_arena(std::max(s->arena_nnz, nnz), std::max(s->arena_rp, n_reads + 1));
-                ng->index = s->results.size();
-                ng->first_ticket = s->next_ticket;
-                s->results.emplace_back();
-                s->open = std::move(ng);
-                g = s->open.get();
-            }
-            if (g->nnz + nnz > g->st->cap_nnz || g->rp_used() + n_reads + 1 > g->st->cap_rp) {
-                const bool full_size = g->st->cap_nnz >= s->full_arena_nnz() && g->st->cap_rp >= s->full_arena_rp();
-                if (full_size && g->n_cells > 0) { // a full-sized arena is full: the group is large enough
-                    s->close_open();
-                    continue;
-                }
-                if (g->pending) { // pushes still copy into the arena: it cannot move yet
-                    s->cv_copy.wait(lk);
-                    continue;
-                }
-                // grow x4 towards the full size (or to what a single large cell needs); the staged part moves over
-                uint64_t cn = g->st->cap_nnz, cr = g->st->cap_rp;
-                while (cn < g->nnz + nnz) cn = std::max(cn * 4, g->nnz + nnz);
-                while (cr < g->rp_used() + n_reads + 1) cr = std::max(cr * 4, g->rp_used() + n_reads + 1);
-                if (g->nnz + nnz <= s->full_arena_nnz()) cn = std::min(cn, s->full_arena_nnz());
-                if (g->rp_used() + n_reads + 1 <= s->full_arena_rp()) cr = std::min(cr, s->full_arena_rp());
-                std::unique_ptr<Staging> old = std::move(g->st);
-                g->st = s->take_arena(cn, cr);
-                std::memcpy(g->st->rp, old->rp, sizeof(uint64_t) * g->rp_used());
-                std::memcpy(g->st->tid, old->tid, sizeof(uint32_t) * g->nnz);
-                std::memcpy(g->st->p, old->p, sizeof(float) * g->nnz);
-                if (s->o.coverage) {
-                    std::memcpy(g->st->start, old->start, sizeof(uint32_t) * g->nnz);
-                    std::memcpy(g->st->end, old->end, sizeof(uint32_t) * g->nnz);
-                }
-                if (old->pinned) --s->arenas_pinned; // (released here: smaller than what groups need by now)
-                old.reset();
-                s->arena_nnz = std::min(std::max(s->arena_nnz, cn), s->full_arena_nnz());
-                s->arena_rp = std::min(std::max(s->arena_rp, cr), s->full_arena_rp());
-                continue;
-            }
-            g->read_off.reserve(g->read_off.size() + 1); // (so that taking the cell's place below cannot throw)
-            g->aln_off.reserve(g->aln_off.size() + 1);
-            break;
-        }
-    } catch (const std::bad_alloc &) { // staging could not be allocated: the session cannot keep its promise
-        s->set_sticky(OEM_ERR_OOM, "oem_cells_stream_push: host allocation of the staging memory failed");
-        s->cv_space.notify_all();
-        return fail(OEM_ERR_OOM, "%s", s->sticky_msg.c_str());
-    }
-    // the cell's place: ticket, offsets; the arrays are copied outside the lock
-    const uint64_t ticket = s->next_ticket++;
-    const uint64_t rp_at = g->rp_used(), a_at = g->nnz;
-    Staging *st = g->st.get();
-    g->n_cells += 1;
-    g->n_reads += n_reads;
-    g->nnz += nnz;
-    g->read_off.push_back(g->n_reads);
-    g->aln_off.push_back(g->nnz);
-    g->pending += 1;
-    s->total_nnz += nnz;
-    s->staged_nnz += nnz;
-    if (g->nnz >= s->group_nnz || g->n_cells >= s->group_cells) s->close_open(); // (the worker waits for the copy below)
-    lk.unlock();
-    std::memcpy(st->rp + rp_at, row_ptr, sizeof(uint64_t) * (n_reads + 1));
-    if (nnz) {
-        std::memcpy(st->tid + a_at, tid, sizeof(uint32_t) * nnz);
-        std::memcpy(st->p + a_at, as_prob, sizeof(float) * nnz);
-        if (s->o.coverage) {
-            std::memcpy(st->start + a_at, aln_start, sizeof(uint32_t) * nnz);
-            std::memcpy(st->end + a_at, aln_end, sizeof(uint32_t) * nnz);
-        }
-    }
-    lk.lock();
-    g->pending -= 1;
-    s->cv_copy.notify_all();
-    if (out_ticket) *out_ticket = ticket;
+    CellArrays a;
+    a.rp = row_ptr;
+    a.tid = tid;
+    a.p = as_prob;
+    a.start = aln_start;
+    a.end = aln_end;
+    return s->push_cell(who, false, a, n_reads, nnz, out_ticket);
+}
+
+extern "C" int oem_cells_stream_set_filters(oem_cells_stream *s, const oem_filters *filters, const uint64_t *txp_len)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_set_filters";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!filters || !txp_len) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->next_ticket || s->pushes_in_flight || s->open) return fail(OEM_ERR_STATE, "%s: a cell has been pushed already", who);
+    OEM_TRY(records_filter_setup(who, filters, txp_len, s->o.n_txps, &s->rf));
+    s->records_mode = true; // (no arena exists yet: the first push makes the first one, in the records layout)
     return OEM_OK;
+    OEM_API_END("oem_cells_stream_set_filters")
+}
+
+extern "C" int oem_cells_stream_push_records(oem_cells_stream *s, const oem_aln_record *records, const uint64_t *group_off,
+                                             uint64_t n_groups, uint64_t *out_ticket)
+{
+    const char *who = "oem_cells_stream_push_records";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    // the cell's own checks, on the calling thread, before the session is touched
+    OEM_TRY(check_group_off(who, records, group_off, n_groups));
+    if (n_groups >= 0x7fffffffull || group_off[n_groups] >= (1ull << 32))
+        return fail(OEM_ERR_ARG, "%s: a cell needs fewer than 2^31 - 1 reads and 2^32 records", who);
+    CellArrays a;
+    a.rp = group_off;
+    a.rec = records;
+    return s->push_cell(who, true, a, n_groups, group_off[n_groups], out_ticket);
 }
 
 extern "C" int oem_cells_stream_finish(oem_cells_stream *s, oem_cells_result **out)
@@ -559,8 +666,10 @@ extern "C" int oem_cells_stream_finish(oem_cells_stream *s, oem_cells_result **o
     r->infos.reserve(r->n_cells);
     std::vector<SparseBlock> blocks;
     blocks.reserve(s->results.size());
+    r->from_records = s->records_mode;
     for (GroupResult &gr : s->results) { // group order is ticket order
         r->infos.insert(r->infos.end(), gr.infos.begin(), gr.infos.end());
+        r->discard.insert(r->discard.end(), gr.tables.begin(), gr.tables.end());
         blocks.push_back(std::move(gr.blk));
     }
     s->results.clear();

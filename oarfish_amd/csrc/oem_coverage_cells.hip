@@ -390,24 +390,32 @@ int cells_coverage_group(const CellsCoverage &cc, const CellsGroup &g, ResidentC
         OEM_TRY(dev_alloc(&out->row_ptr, n_reads + 1, nullptr));
         OEM_TRY(upload_row_ptr_u32(st, g.row_ptr, n_reads + 1, out->row_ptr));
     }
-    OEM_TRY(dev_alloc(&out->tid, nnz, nullptr));
+    const bool on_device = g.d_aln_start != nullptr; // (a group filtered from records: nothing to upload)
+    if (!on_device) OEM_TRY(dev_alloc(&out->tid, nnz, nullptr));
     OEM_TRY(dev_alloc(&out->w64, nnz, nullptr));
     if (nnz == 0) return OEM_OK;
-    OEM_HIP(hipMemcpyAsync(out->tid, g.tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
     // the coverage scratch: released when this scope ends, before the store's layout is built
     Arena ar;
-    uint32_t *d_start, *d_end;
-    float *d_p;
+    const uint32_t *d_start = g.d_aln_start, *d_end = g.d_aln_end;
+    const float *d_p = g.d_as_prob;
     double *d_cov;
-    OEM_TRY(ar.get(&d_start, nnz));
-    OEM_TRY(ar.get(&d_end, nnz));
-    OEM_TRY(ar.get(&d_p, nnz));
     OEM_TRY(ar.get(&d_cov, nnz));
-    OEM_HIP(hipMemcpyAsync(d_start, g.aln_start, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemcpyAsync(d_end, g.aln_end, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemcpyAsync(d_p, g.as_prob, sizeof(float) * nnz, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipStreamSynchronize(st));
-    tm.lap("cov+em: group upload");
+    if (!on_device) {
+        uint32_t *u_start, *u_end;
+        float *u_p;
+        OEM_HIP(hipMemcpyAsync(out->tid, g.tid, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+        OEM_TRY(ar.get(&u_start, nnz));
+        OEM_TRY(ar.get(&u_end, nnz));
+        OEM_TRY(ar.get(&u_p, nnz));
+        OEM_HIP(hipMemcpyAsync(u_start, g.aln_start, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+        OEM_HIP(hipMemcpyAsync(u_end, g.aln_end, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, st));
+        OEM_HIP(hipMemcpyAsync(u_p, g.as_prob, sizeof(float) * nnz, hipMemcpyHostToDevice, st));
+        OEM_HIP(hipStreamSynchronize(st));
+        d_start = u_start;
+        d_end = u_end;
+        d_p = u_p;
+        tm.lap("cov+em: group upload");
+    }
 
     // 2. coverage, in sub-chunks of consecutive cells over the resident arrays when the slot tables and bins of all
     // of them do not fit half the free memory

@@ -128,8 +128,9 @@ int create_store_impl(const uint64_t *row_ptr, const uint32_t *tid, const float 
                       uint64_t n_reads, uint64_t nnz, uint32_t n_txps, int device, const oem_store_opts *opts, oem_store *s,
                       const CellRelabel *relabel = nullptr, ResidentCsr *resident = nullptr);
 void free_store(oem_store *s);
-// The inverse: a per-cell batch the tiler declined hands the CSR back, with the caller's ids `tid` (host) again.
-int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *tid);
+// The inverse: a per-cell batch the tiler declined hands the CSR back, with the caller's ids `tid` (host) again -- or,
+// where they have no host copy (tid NULL), from their device copy d_tid.
+int release_resident_csr(oem_store *s, ResidentCsr *resident, const uint32_t *tid, const uint32_t *d_tid = nullptr);
 // u64 row pointers (host) -> u32 ones on the device, through a temporary u64 copy (no second host array)
 int upload_row_ptr_u32(hipStream_t st, const uint64_t *row_ptr, uint64_t n, uint32_t *d_out);
 

@@ -50,6 +50,19 @@ struct FilterResult {
     bool host_rerun = false;  // a score beyond +-2^24: nothing above is filled, the host loop takes the batch
 };
 
+// The per-cell form of a pass (oem_cells_records.hip): the batch's groups belong to n_cells consecutive cells, cell c
+// owning groups [cell_group_off[c], cell_group_off[c + 1]) of the batch.  The pass then counts the discards per cell
+// (k_filter_measure's per-cell form) and samples the two scans at the cells' first groups (k_filter_cell_offsets), so
+// that the result is a group of the per-cell driver: d_cell_row_off is the device cell_row_off a CellsGroup takes.
+struct FilterCells {
+    const uint64_t *cell_group_off = nullptr; // host, n_cells + 1, from 0 to the batch's n_groups
+    uint32_t n_cells = 0;
+    uint64_t first_cell = 0, first_record = 0; // the batch's place in the call or session, for messages
+    DevBuf<unsigned long long> d_cell_row_off, d_cell_aln_off;        // n_cells + 1 each
+    std::vector<uint64_t> cell_row_off, cell_aln_off;                 // ... and on the host
+    std::vector<oem_discard_table> tables;                            // n_cells
+};
+
 inline long filter_chunk_groups()
 {
     const long ck = knob("OEM_FILTER_CHUNK_GROUPS", (long)kFilterChunkGroups);
@@ -62,9 +75,11 @@ inline long filter_chunk_groups()
 // idle.  ms (6 floats, or NULL for no timing): [0] the uploads and [1] the measure kernels from HIP events, summed over
 // the chunks, [4] the fraction of the measure kernels' time during which a record copy was in flight, [5] += the staging
 // copies by the host clock.
+// pinned_src: the caller's array is page-locked already (the records session's staging): the chunks are copied from it
+// directly, there are no staging buffers and no staging copies.
 template <typename Rec, typename Launch>
 int filter_upload_measure(const Rec *records, Rec *d_recs, const uint64_t *group_off, uint64_t n_groups, uint64_t chunk,
-                          float *ms, Launch &&launch)
+                          float *ms, Launch &&launch, bool pinned_src = false)
 {
     const bool timing = ms != nullptr;
     uint64_t max_chunk_records = 0;
@@ -78,7 +93,8 @@ int filter_upload_measure(const Rec *records, Rec *d_recs, const uint64_t *group
     const uint64_t n_chunks = (n_groups + chunk - 1) / chunk;
     for (int l = 0; l < 2 && (uint64_t)l < n_chunks; ++l) {
         OEM_HIP(hipStreamCreateWithFlags(&lane[l].s, hipStreamNonBlocking));
-        OEM_HIP(hipHostMalloc(&stage[l].p, (max_chunk_records ? max_chunk_records : 1) * sizeof(Rec), hipHostMallocDefault));
+        if (!pinned_src)
+            OEM_HIP(hipHostMalloc(&stage[l].p, (max_chunk_records ? max_chunk_records : 1) * sizeof(Rec), hipHostMallocDefault));
         OEM_HIP(hipEventCreateWithFlags(&copied[l].e, hipEventDisableTiming));
     }
     struct ChunkEvents { hipEvent_t c0 = nullptr, c1 = nullptr, m1 = nullptr; };
@@ -97,12 +113,16 @@ int filter_upload_measure(const Rec *records, Rec *d_recs, const uint64_t *group
         const int l = (int)(ci & 1);
         const uint64_t g1 = g0 + chunk < n_groups ? g0 + chunk : n_groups;
         const uint64_t r0 = group_off[g0], nr = group_off[g1] - r0;
-        if (ci >= 2) OEM_HIP(hipEventSynchronize(copied[l].e));
-        const auto t_stage = std::chrono::steady_clock::now();
-        if (nr) std::memcpy(stage[l].p, records + r0, nr * sizeof(Rec));
-        if (timing) ms[5] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_stage).count();
+        const Rec *src = records + r0;
+        if (!pinned_src) {
+            if (ci >= 2) OEM_HIP(hipEventSynchronize(copied[l].e));
+            const auto t_stage = std::chrono::steady_clock::now();
+            if (nr) std::memcpy(stage[l].p, records + r0, nr * sizeof(Rec));
+            if (timing) ms[5] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_stage).count();
+            src = (const Rec *)stage[l].p;
+        }
         if (timing) OEM_HIP(hipEventRecord(cev[ci].c0, lane[l].s));
-        if (nr) OEM_HIP(hipMemcpyAsync(d_recs + r0, stage[l].p, nr * sizeof(Rec), hipMemcpyHostToDevice, lane[l].s));
+        if (nr) OEM_HIP(hipMemcpyAsync(d_recs + r0, src, nr * sizeof(Rec), hipMemcpyHostToDevice, lane[l].s));
         OEM_HIP(hipEventRecord(copied[l].e, lane[l].s));
         if (timing) OEM_HIP(hipEventRecord(cev[ci].c1, lane[l].s));
         launch(lane[l].s, g0, g1);
@@ -136,6 +156,18 @@ int filter_upload_measure(const Rec *records, Rec *d_recs, const uint64_t *group
 }
 
 // oem_filter_device.hip --------------------------------------------------------------------------------------------------
+// Measure, scans and emit of one batch on the current device: the body of oem_builder_add_groups_device and
+// oem_store_create_records.  tab: filter_prob_table of F.score_prob_denom.  want_coords: start / end / strand too.
+// narrow: u32 row pointers (the total is checked against 2^32 first).  An argument error found on the device (ref_id) is
+// reported here.  cells (or NULL): the per-cell form -- its device and host offsets and its tables are filled, out->dt
+// is their sum, and a ref_id error names the cell too.  pinned_src: as filter_upload_measure.
+int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
+                  const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, uint64_t base, bool want_coords,
+                  bool narrow, FilterResult *out, FilterCells *cells = nullptr, bool pinned_src = false);
+// The checks a device batch makes before any device use, and whether the host loop has to take it from the start
+// (*host_only: no gap table for this score_prob_denom).
+int filter_prepare_batch(const char *who, const oem_filters &F, const oem_aln_record *records, const uint64_t *group_off,
+                         uint64_t n_groups, std::vector<float> *tab, bool *host_only);
 // After a measure pass: the scans n_kept -> alignment offsets (aln_off) and n_kept > 0 -> row indices (row_idx), both of
 // n_groups + 1 entries (out->n_kept has that many, the last one 0), out->nnz and out->n_rows from their ends, and the
 // result's arrays allocated: row pointers (u32 when narrow, after checking base + nnz against 2^32; entry 0 = base), tid,

@@ -26,6 +26,7 @@
 // oem_store_create_coverage does after its upload.  Host arrays are brought back only for the host layout builder.
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -38,11 +39,18 @@ namespace {
 
 thread_local float g_filter_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
+// kPerCell (oem_cells_records.hip): the counters go to the lane's cell, cell_counts[cell * kFilterCounters + k], instead
+// of tot->counts.  cell_group_off (n_cells + 1) holds the cells' first groups; the lane finds its cell by binary search.
+// Groups are in cell order, so the lanes of a wavefront that share a cell are neighbours: a segmented sum over the
+// wavefront leaves every cell's total in the first of its lanes, which issues the one u64 atomic per counter.
+template <bool kPerCell>
 __global__ __launch_bounds__(kFT) void k_filter_measure(oem_filters F, const oem_aln_record *__restrict__ recs,
                                                         const unsigned long long *__restrict__ group_off, uint64_t g0,
                                                         uint64_t g1, const uint64_t *__restrict__ txp_len, uint32_t n_txps,
                                                         uint32_t *__restrict__ n_kept, int32_t *__restrict__ best,
-                                                        FilterTotals *__restrict__ tot)
+                                                        FilterTotals *__restrict__ tot,
+                                                        const unsigned long long *__restrict__ cell_group_off, uint32_t n_cells,
+                                                        unsigned long long *__restrict__ cell_counts)
 {
     const uint64_t g = g0 + (uint64_t)blockIdx.x * kFT + threadIdx.x;
     FilterCounts c;
@@ -57,12 +65,52 @@ __global__ __launch_bounds__(kFT) void k_filter_measure(oem_filters F, const oem
     // every lane of the wavefront takes part (lanes past g1 add zeros)
     const uint32_t v[kFilterCounters] = {c.discard_5p, c.discard_3p, c.discard_score, c.discard_aln_frac, c.discard_aln_len,
                                          c.discard_ori, c.discard_supp, c.valid_best_aln, c.no_mapping, c.no_valid_aln};
+    if constexpr (kPerCell) {
+        const int lane = threadIdx.x & 63;
+        uint32_t cell = 0xffffffffu; // (lanes past g1: a cell of their own, never written)
+        if (g < g1) {
+            uint32_t a = 0, b = n_cells; // the last cell whose first group is <= g (cells without groups share offsets)
+            while (b - a > 1) {
+                const uint32_t m = (a + b) >> 1;
+                if (cell_group_off[m] <= g) a = m;
+                else b = m;
+            }
+            cell = a;
+        }
+        const uint32_t before = __shfl_up(cell, 1);
+        const bool head = lane == 0 || before != cell;
 #pragma unroll
-    for (int k = 0; k < kFilterCounters; ++k) {
-        unsigned long long s = v[k];
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tot->counts[k], s);
+        for (int k = 0; k < kFilterCounters; ++k) {
+            unsigned long long s = v[k];
+            for (int off = 1; off < 64; off <<= 1) { // s = the sum over [lane, min(lane + 2 off, end of the cell's lanes))
+                const unsigned long long t = __shfl_down(s, off);
+                const uint32_t other = __shfl_down(cell, off);
+                if (lane + off < 64 && other == cell) s += t;
+            }
+            if (head && s && cell != 0xffffffffu) atomicAdd(&cell_counts[(uint64_t)cell * kFilterCounters + k], s);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kFilterCounters; ++k) {
+            unsigned long long s = v[k];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tot->counts[k], s);
+        }
     }
+}
+
+// One lane per cell boundary: the two scans sampled at the cells' first groups are the cells' first reads and first
+// alignments in the filtered CSR.
+__global__ __launch_bounds__(kFT) void k_filter_cell_offsets(const unsigned long long *__restrict__ cell_group_off, uint32_t n_cells,
+                                                             const uint64_t *__restrict__ row_idx, const uint64_t *__restrict__ aln_off,
+                                                             unsigned long long *__restrict__ cell_row_off,
+                                                             unsigned long long *__restrict__ cell_aln_off)
+{
+    const uint32_t c = blockIdx.x * kFT + threadIdx.x;
+    if (c > n_cells) return;
+    const unsigned long long g = cell_group_off[c];
+    cell_row_off[c] = row_idx[g];
+    cell_aln_off[c] = aln_off[g];
 }
 
 // row_ptr64 or row_ptr32 (one of the two); start / end / strand may be NULL together (a store without a coverage model)
@@ -105,11 +153,11 @@ struct NonZeroToU64 {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v ? 1 : 0; }
 };
 
-// Measure, scans and emit of one batch on the current device.  want_coords: start / end / strand too.  narrow: u32 row
-// pointers (the total is checked against 2^32 first).  An argument error found on the device (ref_id) is reported here.
+} // namespace
+
 int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
                   const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, uint64_t base, bool want_coords,
-                  bool narrow, FilterResult *out)
+                  bool narrow, FilterResult *out, FilterCells *cells, bool pinned_src)
 {
     const bool timing = knob("OEM_FILTER_TIMING", 0) != 0;
     const uint64_t n_records = group_off[n_groups];
@@ -121,6 +169,14 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
     DevBuf<FilterTotals> d_tot;
     DevBuf<uint64_t> d_aln_off, d_row_idx;
     DevBuf<float> d_tab;
+    DevBuf<unsigned long long> d_cgo, d_ccnt; // the per-cell form: the cells' first groups, their counters
+    const uint32_t n_cells = cells ? cells->n_cells : 0;
+    if (cells) {
+        OEM_TRY(dev_alloc(&d_cgo.p, (size_t)n_cells + 1, nullptr));
+        OEM_TRY(dev_alloc(&d_ccnt.p, (size_t)n_cells * kFilterCounters, nullptr));
+        OEM_HIP(hipMemcpy(d_cgo.p, cells->cell_group_off, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyHostToDevice));
+        OEM_HIP(hipMemset(d_ccnt.p, 0, sizeof(uint64_t) * (n_cells ? (size_t)n_cells * kFilterCounters : 1)));
+    }
     OEM_TRY(dev_alloc(&d_recs.p, n_records, nullptr));
     OEM_TRY(dev_alloc(&d_goff.p, n_groups + 1, nullptr));
     OEM_TRY(dev_alloc(&out->n_kept.p, n_groups + 1, nullptr));
@@ -139,20 +195,43 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
     // -- upload + measure ----------------------------------------------------------------------------------------------
     OEM_TRY(filter_upload_measure(records, d_recs.p, group_off, n_groups, chunk, timing ? g_filter_ms : nullptr,
                                   [&](hipStream_t st, uint64_t g0, uint64_t g1) {
-                                      hipLaunchKernelGGL(k_filter_measure, dim3((uint32_t)((g1 - g0 + kFT - 1) / kFT)), dim3(kFT), 0,
-                                                         st, F, d_recs.p, d_goff.p, g0, g1, out->txp_len.p, n_txps, out->n_kept.p,
-                                                         d_best.p, d_tot.p);
-                                  }));
+                                      const dim3 grid((uint32_t)((g1 - g0 + kFT - 1) / kFT));
+                                      if (cells)
+                                          hipLaunchKernelGGL(k_filter_measure<true>, grid, dim3(kFT), 0, st, F, d_recs.p, d_goff.p, g0,
+                                                             g1, out->txp_len.p, n_txps, out->n_kept.p, d_best.p, d_tot.p, d_cgo.p,
+                                                             n_cells, d_ccnt.p);
+                                      else
+                                          hipLaunchKernelGGL(k_filter_measure<false>, grid, dim3(kFT), 0, st, F, d_recs.p, d_goff.p, g0,
+                                                             g1, out->txp_len.p, n_txps, out->n_kept.p, d_best.p, d_tot.p, nullptr, 0u,
+                                                             nullptr);
+                                  },
+                                  pinned_src));
     OEM_HIP(hipMemcpy(&h_tot, d_tot.p, sizeof(h_tot), hipMemcpyDeviceToHost));
-    if (h_tot.flags & kFilterFlagBadRef)
-        return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, h_tot.bad_record,
+    if (h_tot.flags & kFilterFlagBadRef) {
+        if (!cells)
+            return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, h_tot.bad_record,
+                        records[h_tot.bad_record].ref_id);
+        // the record's group, then the group's cell (the last one that starts at or before it)
+        const uint64_t g = (uint64_t)(std::upper_bound(group_off, group_off + n_groups + 1, (uint64_t)h_tot.bad_record) - group_off) - 1;
+        const uint64_t c = (uint64_t)(std::upper_bound(cells->cell_group_off, cells->cell_group_off + n_cells + 1, g) - cells->cell_group_off) - 1;
+        return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who,
+                    (unsigned long long)(cells->first_cell + c), (unsigned long long)(cells->first_record + h_tot.bad_record),
                     records[h_tot.bad_record].ref_id);
+    }
     if (h_tot.flags & kFilterFlagBigScore) {
         out->host_rerun = true;
         return OEM_OK;
     }
     const uint64_t *cnt = (const uint64_t *)h_tot.counts;
     out->dt = oem_discard_table{cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]};
+    if (cells) { // the cells' tables; the batch's is their sum
+        cells->tables.assign(n_cells, oem_discard_table{});
+        if (n_cells)
+            OEM_HIP(hipMemcpy(cells->tables.data(), d_ccnt.p, sizeof(oem_discard_table) * n_cells, hipMemcpyDeviceToHost));
+        uint64_t *sum = &out->dt.discard_5p;
+        for (const oem_discard_table &t : cells->tables)
+            for (int k = 0; k < kFilterCounters; ++k) sum[k] += (&t.discard_5p)[k];
+    }
 
     // -- scans, emit ---------------------------------------------------------------------------------------------------
     hipStream_t st = nullptr; // the emit follows the scans on the null stream (the lanes are idle)
@@ -161,6 +240,17 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
         for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
     OEM_TRY(filter_scan_alloc(who, n_groups, base, want_coords, narrow, out, &d_aln_off, &d_row_idx, ev[0].e, ev[1].e));
     const uint64_t nnz = out->nnz;
+    if (cells) {
+        OEM_TRY(dev_alloc(&cells->d_cell_row_off.p, (size_t)n_cells + 1, nullptr));
+        OEM_TRY(dev_alloc(&cells->d_cell_aln_off.p, (size_t)n_cells + 1, nullptr));
+        hipLaunchKernelGGL(k_filter_cell_offsets, dim3((n_cells + 1 + kFT - 1) / kFT), dim3(kFT), 0, st, d_cgo.p, n_cells,
+                           d_row_idx.p, d_aln_off.p, cells->d_cell_row_off.p, cells->d_cell_aln_off.p);
+        OEM_HIP(hipGetLastError());
+        cells->cell_row_off.resize((size_t)n_cells + 1);
+        cells->cell_aln_off.resize((size_t)n_cells + 1);
+        OEM_HIP(hipMemcpyAsync(cells->cell_row_off.data(), cells->d_cell_row_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost, st));
+        OEM_HIP(hipMemcpyAsync(cells->cell_aln_off.data(), cells->d_cell_aln_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost, st));
+    }
     OEM_TRY(dev_alloc(&d_tab.p, tab.size(), nullptr));
     if (!tab.empty()) OEM_HIP(hipMemcpy(d_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
     if (n_groups && nnz) {
@@ -179,8 +269,7 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
     return OEM_OK; // (the records, offsets and scan results are released here)
 }
 
-// The checks a device batch makes before any device use, and whether the host loop has to take it from the start.
-int prepare_batch(const char *who, const oem_filters &F, const oem_aln_record *records, const uint64_t *group_off,
+int filter_prepare_batch(const char *who, const oem_filters &F, const oem_aln_record *records, const uint64_t *group_off,
                   uint64_t n_groups, std::vector<float> *tab, bool *host_only)
 {
     OEM_TRY(check_group_off(who, records, group_off, n_groups));
@@ -188,6 +277,8 @@ int prepare_batch(const char *who, const oem_filters &F, const oem_aln_record *r
     *host_only = !filter_prob_table(F.score_prob_denom, *tab);
     return OEM_OK;
 }
+
+namespace {
 
 // host arrays for the host layout builder, fetched from the store that adopted the resident CSR
 struct HostCsr {
@@ -404,7 +495,7 @@ extern "C" int oem_builder_add_groups_device(oem_builder *b, const oem_aln_recor
     if (!b) return fail(OEM_ERR_ARG, "%s: builder is NULL", who);
     std::vector<float> tab;
     bool host_only = false;
-    OEM_TRY(prepare_batch(who, b->f, records, group_off, n_groups, &tab, &host_only));
+    OEM_TRY(filter_prepare_batch(who, b->f, records, group_off, n_groups, &tab, &host_only));
     OEM_TRY(ensure_device(device));
     if (host_only) return add_groups_host(b, records, group_off, n_groups, out_kept, who);
     FilterResult r;
@@ -430,7 +521,7 @@ extern "C" int oem_store_create_records(const oem_filters *filters, const uint64
     OEM_TRY(check_store_from_records(who, filters, txp_len, n_txps, bin_width, model, opts));
     std::vector<float> tab;
     bool host_only = false;
-    OEM_TRY(prepare_batch(who, *filters, records, group_off, n_groups, &tab, &host_only));
+    OEM_TRY(filter_prepare_batch(who, *filters, records, group_off, n_groups, &tab, &host_only));
     OEM_TRY(ensure_device(device));
 
     FilterResult r;

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "oem_driver.h"
+#include "oem_cells.h"
 
 using namespace oem;
 
@@ -157,6 +157,16 @@ extern "C" int oem_debug_proj_last_pass(double *out)
     if (!out) return fail(OEM_ERR_ARG, "oem_debug_proj_last_pass: NULL argument");
     proj_last_pass(out);
     return OEM_OK;
+}
+
+// Test hook: the filtered CSR of the last group of cells that went through the device pass of the records path
+// (oem_em_run_cells_records_sparse, a records session) while OEM_TEST_KEEP_RECORDS_CSR=1 was set: dims3 = reads,
+// alignments, cells; row_ptr (reads + 1, u32), tid / as_prob as bits / start / end (alignments each), cell_row_off
+// (cells + 1).  Any output may be NULL: call once for the sizes, once for the arrays.
+extern "C" int oem_debug_cells_records_last_csr(uint64_t *dims3, uint32_t *row_ptr, uint32_t *tid, uint32_t *as_prob_bits,
+                                                uint32_t *start, uint32_t *end, uint64_t *cell_row_off)
+{
+    return cells_records_last_csr(dims3, row_ptr, tid, as_prob_bits, start, end, cell_row_off);
 }
 
 // Test hook: the n caller bytes at `data` as one LZ4 frame, by the path oem_assignment_text_lz4 compresses a chunk with

@@ -227,6 +227,11 @@ def count_matrix_text(indptr, cols, vals, n_txps: int, row_base: int = 0, prefix
 _COVERAGE_MODELS = {"logistic": 0, "binomial": 1}
 
 
+def _aln_record_dtype():
+    from .builder import ALN_RECORD
+    return ALN_RECORD
+
+
 def cells_coverage_probs(cell_row_off: Sequence[int], boundaries, ref_ids, aln_start, aln_end, txp_len,
                          bin_width: int = 100, model: str = "binomial", growth_rate: float = 2.0,
                          device: int = 0) -> np.ndarray:
@@ -298,6 +303,58 @@ def em_cells_coverage_sparse(cell_row_off: Sequence[int], boundaries, ref_ids, a
     return (*out, cov) if return_coverage else out
 
 
+def _discard_tables(L, res, n_cells):
+    """The per-cell discard tables of a result that came from records, as a list of dicts."""
+    from .builder import discard_dict
+    dts = (_lib.DiscardTableC * max(n_cells, 1))()
+    rc = L.oem_cells_result_discard_tables(res, C.addressof(dts))
+    if rc != _lib.OEM_OK:
+        msg = L.oem_last_error()
+        raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
+    return [discard_dict(dts[c]) for c in range(n_cells)]
+
+
+def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
+                            conv_thresh: float = 1e-3, device: int = 0):
+    """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
+    oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
+    model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
+
+    ``records`` / ``group_off`` are a batch as ``StoreBuilder.add_groups`` takes it (one group per read); cell ``c``
+    owns the groups ``cell_group_off[c] : cell_group_off[c + 1]``.  ``coverage``: None, or
+    ``dict(bin_width=..., model="binomial" | "logistic", growth_rate=...)``.  Returns ``(indptr, cols, vals,
+    [RunInfo], kept, discard_tables)``: the first four as ``em_cells_sparse`` returns them, ``kept`` what
+    ``add_groups`` returns per group, ``discard_tables`` one dict per cell -- that cell's builder's discard table.
+    """
+    from .builder import check_batch, filters_c
+    F = filters_c(filters)
+    txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+    records, group_off = check_batch(records, group_off)
+    cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
+    if cell_group_off.ndim != 1 or len(cell_group_off) < 1:
+        raise ValueError("cell_group_off needs n_cells + 1 entries")
+    n_groups, n_cells = len(group_off) - 1, len(cell_group_off) - 1
+    model, bin_width, growth_rate = -1, 0, 0.0
+    if coverage is not None:
+        name = coverage.get("model", "binomial")
+        if name not in _COVERAGE_MODELS:
+            raise ValueError(f"model must be one of {sorted(_COVERAGE_MODELS)}, not {name!r}")
+        model, bin_width, growth_rate = _COVERAGE_MODELS[name], coverage.get("bin_width", 100), coverage.get("growth_rate", 2.0)
+    kept = np.zeros(n_groups, dtype=np.uint32)
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_em_run_cells_records_sparse(
+        C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if len(records) else None,
+        group_off.ctypes.data, n_groups, cell_group_off.ctypes.data, n_cells, bin_width, model, growth_rate, device,
+        max_iter, conv_thresh, kept.ctypes.data, C.byref(res)))
+    try:
+        tables = _discard_tables(L, res, n_cells)
+    except BaseException:
+        L.oem_cells_result_destroy(res)
+        raise
+    return (*_take_cells_result(res, n_cells, L), kept, tables)
+
+
 class CellsStream:
     """A per-cell session (``oem_cells_stream_*``): cells are pushed one by one, from any number of threads, as
     they become available -- the way single_cell.rs:96-193 produces them -- and the library runs them in batched
@@ -310,10 +367,22 @@ class CellsStream:
 
     ``push`` returns the cell's ticket: cell ``k`` of the result is the cell with ticket ``k``.  ``finish()`` returns
     what ``em_cells_sparse`` returns.  ``push`` is thread-safe and releases the GIL while the library works.
+
+    ``filters`` with ``txp_len`` makes it a RECORDS session (``oem_cells_stream_set_filters``): cells are pushed as
+    their alignment records with ``push_records`` and filtered on the device, as ``em_cells_records_sparse`` does; the
+    budgets then count records, and ``discard_tables()`` gives every cell's discard table after ``finish()``.
     """
 
     def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
-                 group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0):
+                 group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None):
+        if filters is not None and txp_len is None and coverage is not None:
+            txp_len = coverage.get("txp_len")
+        if filters is not None and txp_len is None:
+            raise ValueError("a records session needs txp_len with its filters")
+        if filters is not None and coverage is not None and "txp_len" not in coverage:
+            coverage = dict(coverage, txp_len=txp_len)
+        self._tables = None
+        records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
         o.n_txps, o.device, o.max_iter, o.conv_thresh = n_txps, device, max_iter, conv_thresh
         o.group_nnz, o.group_cells, o.max_staged_nnz = group_nnz, group_cells, max_staged_nnz
@@ -332,6 +401,27 @@ class CellsStream:
         self._h = C.c_void_p()
         _lib.check(self._L.oem_cells_stream_create(C.byref(o), None if txp_len is None else txp_len.ctypes.data,
                                                    C.byref(self._h)))
+        if filters is not None:
+            from .builder import filters_c
+            F = filters_c(filters)
+            tl = np.ascontiguousarray(records_txp_len, dtype=np.uint64)
+            if len(tl) != n_txps:
+                self.close()
+                raise ValueError("txp_len must have n_txps entries")
+            try:
+                self.set_filters(F, tl)
+            except BaseException:
+                self.close()
+                raise
+
+    def set_filters(self, filters, txp_len) -> None:
+        """Turns a fresh session into a records session (``oem_cells_stream_set_filters``)."""
+        from .builder import filters_c
+        if not self._h:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
+        F = filters_c(filters)
+        tl = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        self._check(self._L.oem_cells_stream_set_filters(self._h, C.addressof(F), tl.ctypes.data))
 
     def __enter__(self):
         return self
@@ -378,6 +468,22 @@ class CellsStream:
             len(row_ptr) - 1, nnz, C.byref(ticket)))
         return int(ticket.value)
 
+    def push_records(self, records, group_off) -> int:
+        """One cell of a records session: its reads' records as a batch (``StoreBuilder.add_groups``' arguments).
+        Returns the cell's ticket."""
+        if not self._h:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
+        records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
+        group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+        if group_off.ndim != 1 or len(group_off) < 1:
+            raise ValueError("group_off needs n_groups + 1 entries")
+        if int(group_off.max()) > len(records):
+            raise ValueError("group_off runs past the end of records")
+        ticket = C.c_uint64(0)
+        self._check(self._L.oem_cells_stream_push_records(self._h, records.ctypes.data if len(records) else None,
+                                                          group_off.ctypes.data, len(group_off) - 1, C.byref(ticket)))
+        return int(ticket.value)
+
     def finish(self):
         """(indptr, cols, vals, [RunInfo]) of every pushed cell, in ticket order."""
         if not self._h:
@@ -386,7 +492,18 @@ class CellsStream:
         self._check(self._L.oem_cells_stream_finish(self._h, C.byref(res)))
         nc = C.c_uint32(0)
         self._check(self._L.oem_cells_result_dims(res, C.byref(nc), None))
+        dts = (_lib.DiscardTableC * max(int(nc.value), 1))()
+        if self._L.oem_cells_result_discard_tables(res, C.addressof(dts)) == _lib.OEM_OK:   # (a records session)
+            from .builder import discard_dict
+            self._tables = [discard_dict(dts[c]) for c in range(int(nc.value))]
         return _take_cells_result(res, int(nc.value), self._L)
+
+    def discard_tables(self):
+        """After ``finish()`` of a records session: one dict per cell, in ticket order -- the discard table of that
+        cell's own builder."""
+        if self._tables is None:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "discard_tables(): a finished records session has them")
+        return self._tables
 
     def info(self) -> dict:
         keys = dict(cells=_lib.OEM_CELLS_STREAM_INFO_CELLS, alignments=_lib.OEM_CELLS_STREAM_INFO_ALIGNMENTS,

@@ -295,7 +295,7 @@ class SyntheticRecords:
 
 
 def make_records(store: SyntheticStore, seed: int = BASE_SEED + 21, decoy_rate: float = 0.3, drop_frac: float = 0.05,
-                 score_prob_denom: float = 5.0) -> SyntheticRecords:
+                 score_prob_denom: float = 5.0, txp_len=None) -> SyntheticRecords:
     """A synthetic store turned back into the alignment records it could have come from, so that
     AlignmentFilters::filter (oarfish_types.rs:955-1130) over the records gives the store again: the same reads in the
     same order, the same transcripts and the same score gaps (``as_prob`` is then libm's expf of the gap, which can
@@ -310,7 +310,9 @@ def make_records(store: SyntheticStore, seed: int = BASE_SEED + 21, decoy_rate: 
     first walk -- these carry a score above the read's best, which they must not become -- or the score threshold in the
     second), before or after the read's real records; and whole reads that are dropped (``drop_frac`` of the groups:
     unmapped records only, a non-positive best score, or a best alignment that covers too little of the read).
-    ``kept`` and ``discard`` are what the filter must report.  A pure function of (store, seed, rates, D)."""
+    ``kept`` and ``discard`` are what the filter must report.  A pure function of (store, seed, rates, D).
+    ``txp_len`` (lengths of at least 400): the annotation to draw the coordinates in, instead of one drawn here
+    (``make_cell_records``: every cell of an experiment has the same)."""
     from .builder import ALN_RECORD, REC_HAS_SCORE, REC_REVERSE, REC_SUPPLEMENTARY, REC_UNMAPPED
     F5, F3 = 2000, 3000
     filters = dict(five_prime_clip=F5, three_prime_clip=F3, score_threshold=0.95, min_aligned_fraction=0.5,
@@ -321,7 +323,10 @@ def make_records(store: SyntheticStore, seed: int = BASE_SEED + 21, decoy_rate: 
     lens = np.diff(rp)
     if R and lens.min() < 1:
         raise ValueError("make_records needs a store without empty reads")
-    txp_len = rng.integers(400, 6000, size=T).astype(np.uint64)
+    drawn = rng.integers(400, 6000, size=T).astype(np.uint64)
+    txp_len = drawn if txp_len is None else np.ascontiguousarray(txp_len, dtype=np.uint64)
+    if len(txp_len) != T or (T and txp_len.min() < 400):
+        raise ValueError("make_records needs n_txps transcript lengths of at least 400")
     gap = np.rint(-float(score_prob_denom) * np.log(store.as_prob.astype(np.float64))).astype(np.int64)
     first = rp[:-1]
     if R:
@@ -414,6 +419,56 @@ def make_records(store: SyntheticStore, seed: int = BASE_SEED + 21, decoy_rate: 
                    discard_ori=int((kind == 0).sum()), discard_supp=int((kind == 1).sum()), valid_best_aln=R,
                    no_mapping=int((drop_kind == 0).sum()), no_valid_aln=int((drop_kind == 1).sum()))
     return SyntheticRecords(filters, txp_len, rec, group_off, kept, discard)
+
+
+@dataclass
+class SyntheticCellRecords:
+    filters: dict                # the fields of oem_filters the records were made for
+    txp_len: np.ndarray          # u64 [T]: one annotation for all cells
+    records: np.ndarray          # builder.ALN_RECORD [n_records]: the cells' records one after the other
+    group_off: np.ndarray        # u64 [n_groups + 1]
+    cell_group_off: np.ndarray   # u64 [n_cells + 1]: cell c owns the groups cell_group_off[c] : cell_group_off[c + 1]
+    kept: np.ndarray             # u32 [n_groups]
+    discard: list                # one discard table (dict) per cell
+
+
+def make_cell_records(cells, n_txps: int, seed: int = BASE_SEED + 23, threads: int = 1, **kw) -> SyntheticCellRecords:
+    """``make_records`` per cell of ``cells = make_cells(...)`` (``(cell_row_off, row_ptr, tid, as_prob)``), concatenated:
+    the input of ``em_cells_records_sparse``.  Cell c's records are a pure function of (the cell's store, seed, c, the
+    keyword arguments of ``make_records``); all cells share one annotation, drawn from ``seed``.  A cell without reads
+    has no groups."""
+    from .builder import ALN_RECORD
+    cell_off, row_ptr, tid, p = cells
+    n_cells = len(cell_off) - 1
+    txp_len = np.random.default_rng([seed, 0x7E4]).integers(400, 6000, size=n_txps).astype(np.uint64)
+    recs, goffs, kepts, tables = [], [np.zeros(1, dtype=np.uint64)], [], []
+    cgo = np.zeros(n_cells + 1, dtype=np.uint64)
+    filters, base = None, 0
+
+    def one(c):
+        r0, r1 = int(cell_off[c]), int(cell_off[c + 1])
+        a0, a1 = int(row_ptr[r0]), int(row_ptr[r1])
+        st = SyntheticStore(row_ptr[r0:r1 + 1] - row_ptr[r0], tid[a0:a1], p[a0:a1], None, n_txps, None, None)
+        return make_records(st, seed=seed * 1000 + c, txp_len=txp_len, **kw)
+
+    if threads > 1 and n_cells > 1:
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            per_cell = list(ex.map(one, range(n_cells)))
+    else:
+        per_cell = (one(c) for c in range(n_cells))
+    for c, sr in enumerate(per_cell):
+        filters = sr.filters
+        recs.append(sr.records)
+        goffs.append(sr.group_off[1:] + np.uint64(base))
+        kepts.append(sr.kept)
+        tables.append(sr.discard)
+        base += len(sr.records)
+        cgo[c + 1] = cgo[c] + np.uint64(len(sr.group_off) - 1)
+    if filters is None:
+        filters = make_records(SyntheticStore(np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.float32), None,
+                                              n_txps, None, None), seed=seed, txp_len=txp_len, **kw).filters
+    return SyntheticCellRecords(filters, txp_len, np.concatenate(recs) if recs else np.zeros(0, dtype=ALN_RECORD),
+                                np.concatenate(goffs), cgo, np.concatenate(kepts) if kepts else np.zeros(0, np.uint32), tables)
 
 
 @dataclass

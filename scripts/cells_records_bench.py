@@ -1,0 +1,176 @@
+#!/usr/bin/env python
+"""Cells from their alignment records in one device call (oem_em_run_cells_records_sparse) against the long way round
+on the entry points that existed before it, on the slice behind bench.py's cells.cells_per_s (625 cells x 50 k reads
+over 60 k transcripts, synth.make_cells), records from synth.make_cell_records.  Per model (-1: none, 1: binomial):
+
+  (a) the one call, from the records to the entries;
+  (b) the long way round, in the same process: a host builder per cell (add_groups over the cell's groups, export,
+      discard table), the exports concatenated, then em_cells_sparse / em_cells_coverage_sparse;
+  (c) em_cells_sparse (em_cells_coverage_sparse) alone on the exported CSR: what (a) adds in front of the EM is (a) - (c);
+  (d) the floor of that excess: the records' bytes at the pinned host-to-device rate measured here.
+
+A warm-up on the first cells, then three repeats of everything, best taken.  One more one-call run goes through the
+test-only library under OEM_FILTER_TIMING=1 with one worker: HIP-event times of the filter stages of its last group.
+The result goes to --out as JSON (rewritten after every measurement).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import oarfish_amd  # noqa: E402
+from oarfish_amd import _lib, synth  # noqa: E402
+from oarfish_amd.builder import StoreBuilder  # noqa: E402
+
+COV = dict(bin_width=100, model="binomial", growth_rate=2.0)
+
+
+def pinned_rate_gbs(n_bytes=1 << 30, repeats=3):
+    """Pinned host-to-device copy rate, GB/s, best of `repeats` (HIP events through torch)."""
+    import torch
+    h = torch.empty(n_bytes, dtype=torch.uint8, pin_memory=True)
+    d = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+    d.copy_(h, non_blocking=True)
+    torch.cuda.synchronize()
+    best = 0.0
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        d.copy_(h, non_blocking=True)
+        e1.record()
+        torch.cuda.synchronize()
+        best = max(best, n_bytes / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", type=int, default=625)
+    ap.add_argument("--cell-reads", type=int, default=50_000)
+    ap.add_argument("--txps", type=int, default=60_000)
+    ap.add_argument("--warm-cells", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--models", type=int, nargs="*", default=[-1, 1])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cells_records_bench.json"))
+    args = ap.parse_args()
+    T, n = args.txps, args.cells
+    t0 = time.perf_counter()
+    cells = synth.make_cells(n, args.cell_reads, T, threads=16)
+    cr = synth.make_cell_records(cells, T, threads=16)
+    del cells
+    rec, goff, cgo = cr.records, cr.group_off, cr.cell_group_off
+    print(f"[bench] {n} cells, {len(goff) - 1} reads, {len(rec)} records generated in {time.perf_counter() - t0:.1f} s", flush=True)
+    res = dict(cells=n, cell_reads=args.cell_reads, n_txps=T, groups=int(len(goff) - 1), records=int(len(rec)),
+               record_bytes=int(rec.nbytes), runs_per_point=args.runs, warm_up_cells=min(args.warm_cells, n), max_iter=1000,
+               conv_thresh=1e-3)
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+    def one_call(model, nc=n):
+        g1 = int(cgo[nc])
+        t0 = time.perf_counter()
+        got = oarfish_amd.em_cells_records_sparse(cr.filters, cr.txp_len, rec[:int(goff[g1])], goff[:g1 + 1], cgo[:nc + 1],
+                                                  coverage=None if model < 0 else COV)
+        return time.perf_counter() - t0, got
+
+    def long_way(model, nc=n):
+        """-> (seconds, seconds of the host builders + export + concatenation, result, the exported CSR)"""
+        t0 = time.perf_counter()
+        co, rps, tids, ps, ss, es, base = np.zeros(nc + 1, dtype=np.uint64), [np.zeros(1, dtype=np.uint64)], [], [], [], [], 0
+        tables = []
+        for c in range(nc):
+            g0, g1 = int(cgo[c]), int(cgo[c + 1])
+            r0, r1 = int(goff[g0]), int(goff[g1])
+            with StoreBuilder(cr.filters, cr.txp_len) as b:
+                b.add_groups(rec[r0:r1], goff[g0:g1 + 1] - goff[g0])
+                rp, tid, p, s, e, _ = b.export()
+                tables.append(b.discard_table())
+            rps.append(rp[1:] + np.uint64(base))
+            tids.append(tid)
+            ps.append(p)
+            ss.append(s)
+            es.append(e)
+            base += len(tid)
+            co[c + 1] = co[c] + np.uint64(len(rp) - 1)
+        csr = (co, np.concatenate(rps), np.concatenate(tids), np.concatenate(ps), np.concatenate(ss), np.concatenate(es))
+        t_build = time.perf_counter() - t0
+        got = em_alone(model, csr)[1]
+        return time.perf_counter() - t0, t_build, got, csr
+
+    def em_alone(model, csr):
+        co, rp, tid, p, s, e = csr
+        t0 = time.perf_counter()
+        if model < 0:
+            got = oarfish_amd.em_cells_sparse(co, rp, tid, p, None, T)
+        else:
+            got = oarfish_amd.em_cells_coverage_sparse(co, rp, tid, p, s, e, cr.txp_len, **COV)
+        return time.perf_counter() - t0, got
+
+    def differs(got, want):
+        """Largest relative difference of a value between two results (same columns asserted)."""
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
+        return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
+
+    rate = pinned_rate_gbs()
+    res["pinned_h2d_gbs"] = rate
+    res["records_pcie_floor_s"] = rec.nbytes / (rate * 1e9)
+    save()
+    for model in args.models:
+        key = "no_coverage" if model < 0 else "binomial_coverage"
+        nw = min(args.warm_cells, n)
+        one_call(model, nw)
+        long_way(model, nw)
+        r = res[key] = {}
+        runs_a, keep_a = [], None
+        for _ in range(args.runs):
+            dt, got = one_call(model)
+            runs_a.append(dt)
+            keep_a = got
+        r["one_call_s_runs"], r["one_call_s"] = runs_a, min(runs_a)
+        print(f"[bench] {key}: (a) one call {[round(x, 3) for x in runs_a]} s", flush=True)
+        save()
+        runs_b, builds, csr, keep_b = [], [], None, None
+        for _ in range(args.runs):
+            dt, tb, got, csr = long_way(model)
+            runs_b.append(dt)
+            builds.append(tb)
+            keep_b = got
+        r["long_way_s_runs"], r["long_way_s"] = runs_b, min(runs_b)
+        r["long_way_host_builders_s"] = min(builds)
+        print(f"[bench] {key}: (b) long way {[round(x, 3) for x in runs_b]} s (builders + export {min(builds):.3f} s)", flush=True)
+        r["max_rel_diff_one_call_to_long_way"] = differs(keep_a, keep_b)
+        r["alignments_kept"] = int(len(csr[2]))
+        save()
+        runs_c = [em_alone(model, csr)[0] for _ in range(args.runs)]
+        r["em_alone_s_runs"], r["em_alone_s"] = runs_c, min(runs_c)
+        print(f"[bench] {key}: (c) EM alone {[round(x, 3) for x in runs_c]} s", flush=True)
+        r["speedup_over_long_way"] = r["long_way_s"] / r["one_call_s"]
+        r["excess_over_em_alone_s"] = r["one_call_s"] - r["em_alone_s"]
+        r["excess_over_pcie_floor"] = r["excess_over_em_alone_s"] / res["records_pcie_floor_s"]
+        save()
+        del csr, keep_a, keep_b
+    # the filter stages of the last group, from HIP events (test-only library, one worker)
+    os.environ["OEM_FILTER_TIMING"] = "1"
+    os.environ["OEM_CELLS_WORKERS"] = "1"
+    with _lib.testing() as L:
+        dt, _ = one_call(args.models[0])
+        ms = (C.c_float * 6)()
+        _lib.check(L.oem_debug_filter_last_timing(ms))
+    res["filter_stages_last_group"] = dict(call_s_one_worker=dt, upload_ms=ms[0], k_filter_measure_ms=ms[1], scans_ms=ms[2],
+                                           k_filter_emit_ms=ms[3], measure_under_copy_fraction=ms[4], staging_copy_host_ms_all_groups=ms[5])
+    save()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
