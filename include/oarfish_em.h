@@ -47,7 +47,8 @@ extern "C" {
  *    (oem_builder_add_groups, oem_builder_add_groups_device, oem_store_create_records), the `.count.mtx` file of the
  *    single-cell path as text formatted on the device (oem_count_matrix_text), the projected filter of genome mode
  *    (oem_proj_record, oem_proj_opts, oem_builder_add_projected_group / _groups / _groups_device,
- *    oem_store_create_projected_records). */
+ *    oem_store_create_projected_records), the `.quant` and `.ambig_info.tsv` files of the bulk path as text formatted on
+ *    the device (oem_quant_text, oem_ambig_text). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -519,6 +520,35 @@ int oem_count_matrix_text(const uint64_t *cell_off, uint32_t n_cells,
                           uint32_t n_txps, uint32_t row_base,
                           const uint8_t *prefix, uint64_t prefix_len,
                           int device, oem_text_result **out);
+
+/* The `.quant` file of the bulk path (write_function.rs:104-120): `prefix` followed by one line per transcript,
+ *     name '\t' len '\t' count '\n'
+ * len in plain decimal, the f64 count as Rust's `{}` prints it: the shortest digits that read back as the same f64,
+ * positional notation, never an exponent, no trailing ".0" (`1`, `0.1`, 1e23 as `1` and twenty-three zeros, 5e-324 as
+ * `0.`, 323 zeros and `5`, -0.0 as `-0`; at most 327 bytes).  names / name_off: the transcript names as one byte blob
+ * and n_txps + 1 offsets (name t = bytes [name_off[t], name_off[t+1])), as oem_assignment_text takes the read names;
+ * lens and counts have n_txps entries.  prefix carries the header line "tname\tlen\tnum_reads\n", so the result's text /
+ * n_bytes (oem_text_result_dims, _copy) are the finished file; prefix == NULL requires prefix_len == 0.
+ * The result: n_lines = n_kept = n_txps, line_off the n_lines + 1 byte offsets of the lines into the body (after the
+ * prefix), kept one per line; oem_text_result_info answers as for oem_assignment_text (CONTENT_BYTES = n_bytes, 0
+ * blocks).  No store is involved: the columns go up in chunks, the text comes back; `device` is the ordinal to run on.
+ * Argument errors -- a count that is not finite, name_off decreasing, a name that contains a tab or a newline, a NULL
+ * array with n_txps > 0, a NULL out -- are reported before any device use, and *out is NULL after any failure.
+ * n_txps == 0 is valid (the text is the prefix).  Without a device the call returns OEM_ERR_NO_DEVICE (there is no host
+ * fallback). */
+int oem_quant_text(const uint8_t *names, const uint64_t *name_off,
+                   const uint64_t *lens, const double *counts, uint32_t n_txps,
+                   const uint8_t *prefix, uint64_t prefix_len,
+                   int device, oem_text_result **out);
+
+/* The `.ambig_info.tsv` file (write_function.rs:122-145): `prefix` followed by one line per transcript,
+ *     unique '\t' ambig '\t' total '\n',    ambig = total - unique, 0 where unique > total (saturating_sub)
+ * from the two arrays oem_aux_counts returns (n_txps u32 each).  prefix carries the header line
+ * "unique_reads\tambig_reads\ttotal_reads\n".  The result, the errors (a NULL array with n_txps > 0, a NULL prefix with a
+ * length, a NULL out) and the behaviour without a device are those of oem_quant_text. */
+int oem_ambig_text(const uint32_t *unique, const uint32_t *total, uint32_t n_txps,
+                   const uint8_t *prefix, uint64_t prefix_len,
+                   int device, oem_text_result **out);
 
 /* --------------------------------------------------------------------- */
 /* bootstrap                                                              */

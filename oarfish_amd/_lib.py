@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "oem_m_step", "oem_em_run", "oem_run_history", "oem_aux_counts", "oem_assignment_probs",
     "oem_assignment_text", "oem_text_result_dims", "oem_text_result_copy", "oem_text_result_destroy",
     "oem_assignment_text_lz4", "oem_text_result_info", "oem_count_matrix_text",
+    "oem_quant_text", "oem_ambig_text",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
@@ -201,6 +202,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_assignment_text_lz4.argtypes = [vp, vp, f64, vp, vp, vp, u64, C.POINTER(vp)]
     L.oem_text_result_info.argtypes = [vp, u32, C.POINTER(u64)]
     L.oem_count_matrix_text.argtypes = [vp, u32, vp, vp, u32, u32, vp, u64, i32, C.POINTER(vp)]
+    L.oem_quant_text.argtypes = [vp, vp, vp, vp, u32, vp, u64, i32, C.POINTER(vp)]
+    L.oem_ambig_text.argtypes = [vp, vp, u32, vp, u64, i32, C.POINTER(vp)]
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]
     L.oem_bootstrap.argtypes = [vp, u32, u64, vp, vp, u32, f64, vp, vp]
     L.oem_em_run_cells.argtypes = [vp, u32, vp, vp, vp, vp, u64, u64, u32, i32, u32, f64, vp, vp]
@@ -270,6 +273,8 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_filter_last_timing.argtypes = [vp]
         L.oem_debug_mtx_last_timing.argtypes = [vp]
         L.oem_debug_proj_last_pass.argtypes = [vp]
+        L.oem_debug_quant_last_call.argtypes = [vp]
+        L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         _testing = L
     return _testing

@@ -65,6 +65,7 @@ class BulkArgs:
     display_thresh: float = 1e-6
     prob_on_device: bool = False          # `.prob` body formatted on the device (writers.write_out_prob_device)
     prob_compressed: bool = False         # `--write-assignment-probs=compressed` (prog_opts.rs:506-513): `.prob.lz4`; on the device with prob_on_device
+    quant_on_device: bool = False         # `.quant` and `.ambig_info.tsv` lines formatted on the device (writers.write_output_device)
     seed: int = 0                         # the reference seeds from the OS (em.rs:274)
     device: int = 0
     extra_info: dict = field(default_factory=dict)
@@ -91,7 +92,10 @@ def perform_inference_and_write_output(store: InMemoryAlignmentStore, txps_name:
             "filter_options": {"model_coverage": store.filter_opts.model_coverage},
             "em_iterations": emi.last_run_info.niter if emi.last_run_info else None}
     info.update(args.extra_info)
-    writers.write_output(args.output, info, txps_name, txp_lens, counts, unique, total)  # bulk.rs:168-174
+    if args.quant_on_device:                                                             # bulk.rs:168-174
+        writers.write_output_device(args.output, info, txps_name, txp_lens, counts, (unique, total), device=args.device)
+    else:
+        writers.write_output(args.output, info, txps_name, txp_lens, counts, unique, total)
     if args.num_bootstraps > 0:                                                          # bulk.rs:178-193
         breps = bootstrap(emi, args.num_bootstraps, args.threads, seed=args.seed)
         writers.write_infrep_file(args.output, breps)

@@ -21,8 +21,8 @@ struct oem_builder {
     oem_discard_table dt{};
 };
 
-// What oem_assignment_text, oem_assignment_text_lz4 (oem_assignment_text.hip) and oem_count_matrix_text
-// (oem_count_matrix_text.hip) return; read through oem_text_result_dims / _copy / _info.
+// What oem_assignment_text, oem_assignment_text_lz4 (oem_assignment_text.hip), oem_count_matrix_text
+// (oem_count_matrix_text.hip), oem_quant_text and oem_ambig_text (oem_quant_text.hip) return; read through oem_text_result_dims / _copy / _info.
 struct oem_text_result {
     uint64_t n_bytes = 0;
     uint64_t n_lines = 0;
@@ -294,6 +294,9 @@ void text_last_timing(float *ms3);
 void text_lz4_last_timing(float *ms2);
 // oem_count_matrix_text.hip: the same three of this thread's last oem_count_matrix_text under OEM_MTX_TIMING=1
 void mtx_last_timing(float *ms3);
+// oem_quant_text.hip: this thread's last oem_quant_text / oem_ambig_text: its chunks, the workgroup tiles that went
+// through the LDS stage and those written directly, then ms of measure, scan and emit under OEM_QUANT_TIMING=1
+void quant_last_call(double *out6);
 
 // oem_lz4.hip: the device buffers the compression of one chunk owns; reused by the chunks that follow it on its stream
 struct Lz4Chunk {

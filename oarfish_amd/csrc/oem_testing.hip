@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "oem_cells.h"
+#include "oem_shortest_f64.h"
 
 using namespace oem;
 
@@ -125,6 +126,32 @@ extern "C" int oem_debug_mtx_last_timing(float *out)
 {
     if (!out) return fail(OEM_ERR_ARG, "oem_debug_mtx_last_timing: NULL argument");
     mtx_last_timing(out);
+    return OEM_OK;
+}
+
+// out[0..5] = this thread's last oem_quant_text / oem_ambig_text: chunks, workgroup tiles that went through the LDS stage,
+// tiles written directly, then kernel ms under OEM_QUANT_TIMING=1: measure, scan, emit (all chunks)
+extern "C" int oem_debug_quant_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_quant_last_call: NULL argument");
+    quant_last_call(out);
+    return OEM_OK;
+}
+
+// Test hook: the host build of oem_shortest_f64.h.  The texts of the n finite f64 with these bits, one after the other
+// in `text`; off[i] .. off[i + 1] are the bytes of value i (off has n + 1 entries, from the length function; the
+// emitter must end where it says).  OEM_ERR_ARG for a value that is not finite or a text that would pass `cap`.
+extern "C" int oem_test_shortest_f64(const uint64_t *bits, uint64_t n, uint8_t *text, uint64_t cap, uint64_t *off)
+{
+    if ((n && !bits) || !off || (cap && !text)) return fail(OEM_ERR_ARG, "oem_test_shortest_f64: NULL argument");
+    off[0] = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!f64_is_finite(bits[i])) return fail(OEM_ERR_ARG, "oem_test_shortest_f64: value %llu is not finite", (unsigned long long)i);
+        off[i + 1] = off[i] + shortest_f64_len(bits[i]);
+        if (off[i + 1] > cap) return fail(OEM_ERR_ARG, "oem_test_shortest_f64: text holds %llu bytes", (unsigned long long)cap);
+        if (emit_shortest_f64(text + off[i], bits[i]) != text + off[i + 1])
+            return fail(OEM_ERR_STATE, "oem_test_shortest_f64: value %llu: the emitter and the length function differ", (unsigned long long)i);
+    }
     return OEM_OK;
 }
 

@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .types import AssignmentText, EMInfo, RunInfo
+from .types import AssignmentText, EMInfo, RunInfo, take_text_result
 
 
 def _require_no_kde(em_info: EMInfo):
@@ -208,20 +208,7 @@ def count_matrix_text(indptr, cols, vals, n_txps: int, row_base: int = 0, prefix
     _lib.check(L.oem_count_matrix_text(indptr.ctypes.data, n_cells, cols.ctypes.data if len(cols) else None,
                                        vals.ctypes.data if len(vals) else None, n_txps, row_base,
                                        prefix if prefix else None, len(prefix), device, C.byref(h)))
-    try:
-        nb, nl = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(L.oem_text_result_dims(h, C.byref(nb), C.byref(nl), None))
-        text = np.empty(nb.value, dtype=np.uint8)
-        line_off = np.empty(nl.value + 1, dtype=np.uint64) if offsets else None
-        kept = np.empty(nl.value, dtype=np.uint32) if offsets else None
-        _lib.check(L.oem_text_result_copy(h, text.ctypes.data if nb.value else None,
-                                          line_off.ctypes.data if offsets else None,
-                                          kept.ctypes.data if offsets and nl.value else None))
-        res = AssignmentText(text, line_off, kept)
-        res.content_bytes = int(nb.value)
-    finally:
-        L.oem_text_result_destroy(h)
-    return res
+    return take_text_result(L, h, offsets)
 
 
 _COVERAGE_MODELS = {"logistic": 0, "binomial": 1}

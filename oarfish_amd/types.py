@@ -68,6 +68,26 @@ class AssignmentText:
         return self.text[int(self.line_off[r]):int(self.line_off[r + 1])].tobytes()
 
 
+def take_text_result(L, h, offsets: bool = True) -> AssignmentText:
+    """The ``AssignmentText`` of an ``oem_text_result`` handle of a call that needs no store (oem_count_matrix_text,
+    oem_quant_text, oem_ambig_text), which is released.  ``offsets=False`` leaves ``line_off`` and ``kept`` ``None``
+    (a writer needs the text alone)."""
+    try:
+        nb, nl = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(L.oem_text_result_dims(h, C.byref(nb), C.byref(nl), None))
+        text = np.empty(nb.value, dtype=np.uint8)
+        line_off = np.empty(nl.value + 1, dtype=np.uint64) if offsets else None
+        kept = np.empty(nl.value, dtype=np.uint32) if offsets else None
+        _lib.check(L.oem_text_result_copy(h, text.ctypes.data if nb.value else None,
+                                          line_off.ctypes.data if offsets else None,
+                                          kept.ctypes.data if offsets and nl.value else None))
+        res = AssignmentText(text, line_off, kept)
+        res.content_bytes = int(nb.value)
+    finally:
+        L.oem_text_result_destroy(h)
+    return res
+
+
 def pack_read_names(read_names, n_reads: int):
     """Read names as the C ABI takes them: (blob uint8, offsets uint64[n_reads + 1]).  ``read_names`` is a sequence of
     ``str`` / ``bytes`` or already such a pair."""

@@ -4,6 +4,8 @@ Host-side formatting only; every number written here comes out of the device eng
 (`em` / `em_par` / `bootstrap` / `DeviceStore.aux_counts` / `DeviceStore.assignment_probs`).
 
   write_output               write_function.rs:72-148   <out>.meta_info.json, .quant, .ambig_info.tsv
+  write_output_device        the same three files, the lines of `.quant` and `.ambig_info.tsv` formatted on the device
+                             (quant_text, ambig_text)
   write_infrep_file          write_function.rs:199-209, parquet_utils.rs:15-44, bulk.rs:181-193
   write_out_prob             write_function.rs:226-340  <out>.prob
   write_out_prob_device      the same file, its body formatted on the device (DeviceStore.assignment_text); with
@@ -51,24 +53,136 @@ def _make_parent(output: str) -> None:  # write_function.rs:32-40
         os.makedirs(parent, exist_ok=True)
 
 
+_QUANT_HEADER = "tname\tlen\tnum_reads\n"
+_AMBIG_HEADER = "unique_reads\tambig_reads\ttotal_reads\n"
+
+
+def _write_meta_info(output: str, info: dict) -> None:
+    """The parent directory and `.meta_info.json` (write_function.rs:78-102), what every form of `write_output` starts
+    with."""
+    _make_parent(output)
+    with open(with_additional_extension(output, ".meta_info.json"), "w") as fh:
+        json.dump(info, fh, indent=2)                       # serde_json to_writer_pretty
+
+
 def write_output(output: str, info: dict, names: Sequence[str], lens: Sequence[int], counts,
                  unique_counts, total_counts) -> None:
     """write_function.rs:72-148: `.meta_info.json`, `.quant` (tname, len, num_reads) and
     `.ambig_info.tsv` (unique, ambig = total - unique saturating, total)."""
     if not (len(names) == len(lens) == len(counts) == len(unique_counts) == len(total_counts)):
         raise ValueError("write_output: per-transcript columns differ in length")
-    _make_parent(output)
-    with open(with_additional_extension(output, ".meta_info.json"), "w") as fh:
-        json.dump(info, fh, indent=2)                       # serde_json to_writer_pretty
+    _write_meta_info(output, info)
     with open(with_additional_extension(output, ".quant"), "w") as fh:
-        fh.write("tname\tlen\tnum_reads\n")
+        fh.write(_QUANT_HEADER)
         for n, l, c in zip(names, lens, counts):
             fh.write(f"{n}\t{int(l)}\t{rust_display(c)}\n")
     with open(with_additional_extension(output, ".ambig_info.tsv"), "w") as fh:
-        fh.write("unique_reads\tambig_reads\ttotal_reads\n")
+        fh.write(_AMBIG_HEADER)
         for u, t in zip(unique_counts, total_counts):
             u, t = int(u), int(t)
             fh.write(f"{u}\t{max(t - u, 0)}\t{t}\n")
+
+
+def pack_names(names):
+    """Transcript names as the C ABI takes them: (blob uint8, offsets uint64[n + 1]).  ``names`` is a sequence of
+    ``str`` / ``bytes`` or already such a pair.  A list of ``str`` is joined and encoded in one go (no work per name in
+    the interpreter); anything else goes through ``types.pack_read_names``."""
+    from .types import pack_read_names
+
+    if not (isinstance(names, tuple) and len(names) == 2 and not isinstance(names[1], (str, bytes))):
+        names = list(names)
+        n = len(names)
+        try:
+            joined = np.frombuffer("\n".join(names).encode("utf-8"), dtype=np.uint8)
+        except TypeError:                                   # bytes among them
+            joined = None
+        if joined is not None and n:
+            is_nl = joined == 10
+            ends = np.flatnonzero(is_nl)
+            if len(ends) == n - 1:                          # (a name with a newline in it: the slow way, and the library refuses it)
+                off = np.zeros(n + 1, dtype=np.uint64)
+                off[1:n] = ends - np.arange(n - 1)
+                off[n] = len(joined) - (n - 1)
+                return np.ascontiguousarray(joined[~is_nl]), off
+        return pack_read_names(names, n)
+    return pack_read_names(names, len(names[1]) - 1)
+
+
+def quant_text_lines(names, lens, counts, prefix: bytes = b"", device: int = 0, offsets: bool = True):
+    """write_function.rs:104-120 on the device (oem_quant_text): ``text`` is ``prefix`` followed by one line
+    ``name\tlen\tcount\n`` per transcript, the count as Rust's ``{}`` prints an f64 -- byte for byte what
+    ``write_output`` writes into `.quant` after its header line.  ``names``: a sequence of ``str`` / ``bytes`` or a pair
+    ``(blob, offsets)``.  ``line_off``: the byte offsets of the lines into the body (after the prefix); ``kept``: one
+    per line; ``offsets=False`` leaves those two ``None``.  A count that is not finite, or a name with a tab or a
+    newline in it, is an ``OemError`` (OEM_ERR_ARG)."""
+    import ctypes as C
+
+    from . import _lib
+    from .types import take_text_result
+
+    blob, off = pack_names(names)
+    n = len(off) - 1
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.float64)
+    if len(lens) != n or len(counts) != n:
+        raise ValueError("quant_text: names, lens and counts differ in length")
+    if len(blob) == 0:
+        blob = np.zeros(1, dtype=np.uint8)                  # a non-NULL pointer: the names exist, they are all empty
+    prefix = bytes(prefix)
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.oem_quant_text(blob.ctypes.data, off.ctypes.data, lens.ctypes.data if n else None,
+                                counts.ctypes.data if n else None, n, prefix if prefix else None, len(prefix), device,
+                                C.byref(h)))
+    return take_text_result(L, h, offsets)
+
+
+def ambig_text_lines(unique, total, prefix: bytes = b"", device: int = 0, offsets: bool = True):
+    """write_function.rs:122-145 on the device (oem_ambig_text): ``prefix`` and one line
+    ``unique\tambig\ttotal\n`` per transcript, ``ambig = total - unique`` saturating, from the two u32 arrays
+    ``DeviceStore.aux_counts`` returns.  The result is ``quant_text_lines``'s."""
+    import ctypes as C
+
+    from . import _lib
+    from .types import take_text_result
+
+    unique = np.ascontiguousarray(unique, dtype=np.uint32)
+    total = np.ascontiguousarray(total, dtype=np.uint32)
+    if len(unique) != len(total):
+        raise ValueError("ambig_text: unique and total differ in length")
+    n = len(unique)
+    prefix = bytes(prefix)
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.oem_ambig_text(unique.ctypes.data if n else None, total.ctypes.data if n else None, n,
+                                prefix if prefix else None, len(prefix), device, C.byref(h)))
+    return take_text_result(L, h, offsets)
+
+
+def quant_text(names, lens, counts, device: int = 0) -> bytes:
+    """The finished `.quant` file (header line and all), its lines formatted on the device."""
+    return quant_text_lines(names, lens, counts, _QUANT_HEADER.encode(), device, offsets=False).text.tobytes()
+
+
+def ambig_text(unique, total, device: int = 0) -> bytes:
+    """The finished `.ambig_info.tsv` file (header line and all), its lines formatted on the device."""
+    return ambig_text_lines(unique, total, _AMBIG_HEADER.encode(), device, offsets=False).text.tobytes()
+
+
+def write_output_device(output: str, info: dict, names, lens, counts, aux_counts, device: int = 0) -> None:
+    """``write_output`` with the lines of `.quant` and `.ambig_info.tsv` formatted on the device: the same three
+    files, byte for byte.  ``aux_counts`` is the pair ``(unique, total)`` that ``DeviceStore.aux_counts`` returns.
+    Each text file is one device call and one write."""
+    unique, total = aux_counts
+    if not (len(lens) == len(counts) == len(unique) == len(total)):
+        raise ValueError("write_output_device: per-transcript columns differ in length")
+    quant = quant_text_lines(names, lens, counts, _QUANT_HEADER.encode(), device, offsets=False)
+    ambig = ambig_text_lines(unique, total, _AMBIG_HEADER.encode(), device, offsets=False)
+    _write_meta_info(output, info)
+    with open(with_additional_extension(output, ".quant"), "wb") as fh:
+        fh.write(quant.text)
+    with open(with_additional_extension(output, ".ambig_info.tsv"), "wb") as fh:
+        fh.write(ambig.text)
 
 
 def write_infrep_file(output: str, breps) -> str:
