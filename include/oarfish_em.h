@@ -48,7 +48,8 @@ extern "C" {
  *    single-cell path as text formatted on the device (oem_count_matrix_text), the projected filter of genome mode
  *    (oem_proj_record, oem_proj_opts, oem_builder_add_projected_group / _groups / _groups_device,
  *    oem_store_create_projected_records), the `.quant` and `.ambig_info.tsv` files of the bulk path as text formatted on
- *    the device (oem_quant_text, oem_ambig_text). */
+ *    the device (oem_quant_text, oem_ambig_text), a cell's records collated by read name on the device
+ *    (oem_collate_names). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -659,6 +660,41 @@ int oem_em_run_cells_records_sparse(const oem_filters *filters, const uint64_t *
 /* The per-cell DiscardTable of a result that came from records (oem_em_run_cells_records_sparse, a records session):
  * n_cells entries, in result order.  OEM_ERR_STATE for a result that did not; NULL arguments are OEM_ERR_ARG. */
 int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out);
+
+/* Collates the alignment records of cells by READ NAME, on the device: the first step of the reference's single-cell
+ * worker (alignment_parser.rs:170-241, sort_and_parse_barcode_records), whose input is collated by barcode only.  What
+ * it returns is the `group_off` / `cell_group_off` the records calls above take, once the caller has put its records
+ * into `out_order` order.
+ *
+ * names / name_off: the n_records read names as one blob, record i's bytes at [name_off[i], name_off[i + 1]); name_off
+ * starts at 0.  secondary: one byte per record, non-zero = the SAM secondary flag; NULL = no record has it.
+ * cell_rec_off (n_cells + 1, from 0 to n_records, non-decreasing): cell c owns the records
+ * [cell_rec_off[c], cell_rec_off[c + 1]); a cell may be empty.
+ *
+ * OEM_COLLATE_SORT.  For every cell, out_order[cell_rec_off[c] .. cell_rec_off[c + 1]) holds that cell's record indices
+ * sorted by (1) the name as bytes, unsigned and lexicographic, a proper prefix first -- <[u8]>::cmp, what the
+ * reference's x.name().cmp(&y.name()) does; (2) secondary != 0, so the primary comes first (:182-188); (3) the record
+ * index.  The reference's sort is unstable and leaves the order among a read's secondaries open; (3) is the stable
+ * choice, one of the orders its comparator allows.  out_group_off (capacity n_records + 1) receives the positions in
+ * out_order where a new read starts -- a read is a maximal run of identical names inside one cell, so the same name in
+ * two cells gives two groups (:201-239) -- and then n_records; *out_n_groups their number; out_cell_group_off
+ * (n_cells + 1) the first group of every cell.
+ * OEM_COLLATE_ADJACENT.  Nothing is sorted and out_order is the identity: a group ends where the name differs from the
+ * previous record's or where a cell ends, the grouping of the bulk parser for name-collated input (:301-437).
+ *
+ * OEM_ERR_ARG before any device use: name_off, cell_rec_off or an output NULL, names NULL with n_records > 0, offsets
+ * not from 0 or decreasing, cell_rec_off not ending at n_records, n_records > 2^32 - 1, a cell of more than 2^31 - 2
+ * records, a mode that is none.  OEM_ERR_ARG found on the device, naming the first such record: an empty name (the
+ * reference skips such records at :202; drop them before the call) and a name that contains a 0 byte (a BAM name
+ * cannot; it is what lets the device compare zero-padded 8-byte keys).  The outputs are then unspecified.  Without a
+ * device: OEM_ERR_NO_DEVICE.  The rule is oarfish_amd/csrc/oem_collate.h. */
+#define OEM_COLLATE_SORT 0u
+#define OEM_COLLATE_ADJACENT 1u
+int oem_collate_names(const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+                      uint64_t n_records, const uint64_t *cell_rec_off, uint32_t n_cells,
+                      uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */, int device,
+                      uint32_t *out_order, uint64_t *out_group_off, uint64_t *out_n_groups,
+                      uint64_t *out_cell_group_off);
 
 /* A per-cell SESSION: the caller pushes cells one by one, from any number of threads, as they become available
  * (single_cell.rs:96-193: N workers each pop one cell and build its private store).  The library stages the cells,

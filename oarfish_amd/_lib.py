@@ -44,6 +44,8 @@ OEM_INFO_RUN_HISTORY_STORED = 4
 OEM_TEXT_INFO_CONTENT_BYTES = 1
 OEM_TEXT_INFO_BLOCKS = 2
 OEM_TEXT_INFO_RAW_BLOCKS = 3
+OEM_COLLATE_SORT = 0
+OEM_COLLATE_ADJACENT = 1
 
 # every symbol include/oarfish_em.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -64,7 +66,7 @@ ABI_SYMBOLS = [
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
-    "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables",
+    "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables", "oem_collate_names",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
@@ -217,6 +219,7 @@ def _load(path: str) -> C.CDLL:
     L.oem_em_run_cells_records_sparse.argtypes = [vp, vp, u32, vp, vp, u64, vp, u32, u32, i32, f64, i32, u32, f64, vp,
                                                   C.POINTER(vp)]
     L.oem_cells_result_discard_tables.argtypes = [vp, vp]
+    L.oem_collate_names.argtypes = [vp, vp, vp, u64, vp, u32, u32, i32, vp, vp, C.POINTER(u64), vp]
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
     L.oem_cells_stream_push_records.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
@@ -274,6 +277,8 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_mtx_last_timing.argtypes = [vp]
         L.oem_debug_proj_last_pass.argtypes = [vp]
         L.oem_debug_quant_last_call.argtypes = [vp]
+        L.oem_debug_collate_last_call.argtypes = [vp]
+        L.oem_test_collate_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, C.POINTER(u64), vp]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         _testing = L

@@ -1,0 +1,139 @@
+// oem_collate.h -- collating a cell's alignment records by read name, as pure host / device functions.
+//
+// Reference (COMBINE-lab/oarfish v0.10.3, src/alignment_parser.rs): in single-cell mode the input is collated by barcode
+// only, so sort_and_parse_barcode_records (:170-241) first sorts the cell's records by read name with a read's primary
+// record before its secondaries (:180-191) and then cuts a group wherever the name changes (:201-239).  The bulk parser
+// (:301-437) takes name-collated input and only cuts.  Both are stated here once; the kernels of oem_collate_device.hip,
+// the host walk below (the testing library's oem_test_collate_host, the stand-alone program of tests/test_collate.py)
+// and the documentation of oem_collate_names all refer to this file.
+//
+// The order inside a cell, for records i and j:
+//   1. the names as bytes, unsigned and lexicographic, a proper prefix first (<[u8]>::cmp, what x.name().cmp(&y.name())
+//      does);
+//   2. secondary != 0 after secondary == 0 (the primary first);
+//   3. the record index.
+// The reference's sort is unstable and its comparator calls two secondaries of one read (and two primaries, "this one
+// shouldn't happen") equal, so it leaves their order open.  Rule 3 is the stable choice: one of the orders the
+// reference's comparator allows, and the one every implementation here gives.
+//
+// A group is a maximal run of identical names inside one cell: the same name in two cells gives two groups.  In
+// kCollateAdjacent mode nothing is sorted; a group ends where the name differs from the previous record's or where a
+// cell ends.
+//
+// Names are never empty (the reference skips such records at :202, the hook drops them before calling) and hold no 0
+// byte (a BAM read name cannot).  The second condition lets a name be compared through zero-padded keys: key r of a name
+// is its bytes [8r, 8r + 8) as one big-endian u64, zero past the end.  Comparing names equals comparing their key
+// sequences; two names whose keys agree up to and including a key whose last byte is 0 are the same name.
+#pragma once
+
+#include <stdint.h>
+#include <string.h>
+
+#ifndef OEM_HD
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#define OEM_HD __host__ __device__
+#else
+#define OEM_HD
+#endif
+#endif
+
+#include <algorithm>
+#include <vector>
+
+namespace oem {
+
+enum : uint32_t { kCollateSort = 0, kCollateAdjacent = 1 };
+constexpr uint64_t kCollateNoRecord = ~0ull;
+
+// key `round` of the name at p[0 .. len)
+OEM_HD inline uint64_t collate_key(const uint8_t *p, uint64_t len, uint64_t round)
+{
+    uint64_t k = 0;
+    for (uint64_t b = 0; b < 8; ++b) {
+        const uint64_t at = 8 * round + b;
+        k = (k << 8) | (at < len ? (uint64_t)p[at] : 0ull);
+    }
+    return k;
+}
+
+// a name's keys are over once one of them ends in a 0 byte
+OEM_HD inline bool collate_key_is_last(uint64_t key) { return (key & 0xffull) == 0; }
+
+// <[u8]>::cmp
+OEM_HD inline int collate_name_cmp(const uint8_t *a, uint64_t la, const uint8_t *b, uint64_t lb)
+{
+    const uint64_t n = la < lb ? la : lb;
+    for (uint64_t i = 0; i < n; ++i)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+// the whole key of the order: is record i before record j?
+inline bool collate_before(const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary, uint32_t i, uint32_t j)
+{
+    const int c = collate_name_cmp(names + name_off[i], name_off[i + 1] - name_off[i], names + name_off[j], name_off[j + 1] - name_off[j]);
+    if (c) return c < 0;
+    const bool si = secondary && secondary[i], sj = secondary && secondary[j];
+    if (si != sj) return sj;
+    return i < j;
+}
+
+// The first record (kCollateNoRecord: none) with an empty name, or with a 0 byte in its name; *zero_byte tells which.
+inline uint64_t collate_first_bad_name(const uint8_t *names, const uint64_t *name_off, uint64_t n_records, bool *zero_byte)
+{
+    for (uint64_t i = 0; i < n_records; ++i) {
+        const uint64_t len = name_off[i + 1] - name_off[i];
+        const bool z = len && memchr(names + name_off[i], 0, len);
+        if (!len || z) {
+            *zero_byte = z;
+            return i;
+        }
+    }
+    return kCollateNoRecord;
+}
+
+// One cell of the host walk: order[r0 .. r1) sorted (or the identity), the group starts appended to group_off.
+inline void collate_host_cell(const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary, uint64_t r0, uint64_t r1,
+                              uint32_t mode, uint32_t *order)
+{
+    for (uint64_t i = r0; i < r1; ++i) order[i] = (uint32_t)i;
+    if (mode == kCollateSort)
+        std::sort(order + r0, order + r1, [&](uint32_t i, uint32_t j) { return collate_before(names, name_off, secondary, i, j); });
+}
+
+// The cut: the positions of `order` where a read starts, cell by cell, then n_records; cell_group_off from them.
+inline void collate_host_cut(const uint8_t *names, const uint64_t *name_off, uint64_t n_records, const uint64_t *cell_rec_off,
+                             uint32_t n_cells, const uint32_t *order, uint64_t *group_off, uint64_t *n_groups, uint64_t *cell_group_off)
+{
+    uint64_t g = 0;
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        cell_group_off[c] = g;
+        for (uint64_t p = cell_rec_off[c]; p < cell_rec_off[c + 1]; ++p) {
+            bool head = p == cell_rec_off[c];
+            if (!head) {
+                const uint32_t i = order[p], j = order[p - 1];
+                head = collate_name_cmp(names + name_off[i], name_off[i + 1] - name_off[i], names + name_off[j], name_off[j + 1] - name_off[j]) != 0;
+            }
+            if (head) group_off[g++] = p;
+        }
+    }
+    cell_group_off[n_cells] = g;
+    group_off[g] = n_records;
+    *n_groups = g;
+}
+
+// The host walk of the whole rule (arguments as oem_collate_names, already checked).  Returns the first bad record as
+// collate_first_bad_name does, and then leaves the outputs alone.
+inline uint64_t collate_host(const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary, uint64_t n_records,
+                             const uint64_t *cell_rec_off, uint32_t n_cells, uint32_t mode, uint32_t *order, uint64_t *group_off,
+                             uint64_t *n_groups, uint64_t *cell_group_off, bool *zero_byte)
+{
+    const uint64_t bad = collate_first_bad_name(names, name_off, n_records, zero_byte);
+    if (bad != kCollateNoRecord) return bad;
+    for (uint32_t c = 0; c < n_cells; ++c) collate_host_cell(names, name_off, secondary, cell_rec_off[c], cell_rec_off[c + 1], mode, order);
+    collate_host_cut(names, name_off, n_records, cell_rec_off, n_cells, order, group_off, n_groups, cell_group_off);
+    return kCollateNoRecord;
+}
+
+} // namespace oem

@@ -297,6 +297,11 @@ void mtx_last_timing(float *ms3);
 // oem_quant_text.hip: this thread's last oem_quant_text / oem_ambig_text: its chunks, the workgroup tiles that went
 // through the LDS stage and those written directly, then ms of measure, scan and emit under OEM_QUANT_TIMING=1
 void quant_last_call(double *out6);
+// oem_collate_device.hip: this thread's last oem_collate_names: the key rounds it ran (the most of any batch), its upload
+// chunks, its batches; under OEM_COLLATE_TIMING=1 ms of the name uploads and of the kernels behind each chunk (HIP events,
+// summed over the chunks), of the rounds and the cut after the upload (HIP events), of the copies into pinned staging
+// (host clock); the rounds that had to sort
+void collate_last_call(double *out8);
 
 // oem_lz4.hip: the device buffers the compression of one chunk owns; reused by the chunks that follow it on its stream
 struct Lz4Chunk {

@@ -4,10 +4,13 @@
 // public header.  tests/ and scripts/ use it to look inside a resident store (layout hashes), to
 // hammer the stopping-rule kernel in isolation, and -- together with the OEM_TESTING build of
 // oem_comm.cpp -- to run the row-sharded loop with several shards on one GPU.
+#include <atomic>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "oem_cells.h"
+#include "oem_collate.h"
 #include "oem_shortest_f64.h"
 
 using namespace oem;
@@ -136,6 +139,45 @@ extern "C" int oem_debug_quant_last_call(double *out)
     if (!out) return fail(OEM_ERR_ARG, "oem_debug_quant_last_call: NULL argument");
     quant_last_call(out);
     return OEM_OK;
+}
+
+// out[0..7] = this thread's last oem_collate_names: key rounds (the most of any batch), upload chunks, batches; under
+// OEM_COLLATE_TIMING=1 ms of the name uploads, of the kernels behind each chunk, of the rounds and the cut after the upload
+// (HIP events) and of the copies into pinned staging (host clock); the rounds that had to sort
+extern "C" int oem_debug_collate_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_collate_last_call: NULL argument");
+    collate_last_call(out);
+    return OEM_OK;
+}
+
+// Test hook: the host walk of oem_collate.h -- std::sort of each cell's record indices with the rule's comparator, then
+// the cut -- with oem_collate_names' arguments (checked by the caller) and outputs; n_threads workers take the cells one
+// by one, the way the reference's workers do.  An empty name or a 0 byte is OEM_ERR_ARG naming the record.
+extern "C" int oem_test_collate_host(const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary, uint64_t n_records,
+                                     const uint64_t *cell_rec_off, uint32_t n_cells, uint32_t mode, uint32_t n_threads,
+                                     uint32_t *out_order, uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off)
+{
+    OEM_API_BEGIN
+    if (!name_off || !cell_rec_off || !out_order || !out_group_off || !out_n_groups || !out_cell_group_off || (n_records && !names))
+        return fail(OEM_ERR_ARG, "oem_test_collate_host: NULL argument");
+    bool zero_byte = false;
+    const uint64_t bad = collate_first_bad_name(names, name_off, n_records, &zero_byte);
+    if (bad != kCollateNoRecord)
+        return fail(OEM_ERR_ARG, zero_byte ? "oem_test_collate_host: the name of record %llu contains a 0 byte"
+                                           : "oem_test_collate_host: record %llu has an empty name", (unsigned long long)bad);
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (uint32_t c = next.fetch_add(1); c < n_cells; c = next.fetch_add(1))
+            collate_host_cell(names, name_off, secondary, cell_rec_off[c], cell_rec_off[c + 1], mode, out_order);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < n_threads && t < n_cells; ++t) pool.emplace_back(work);
+    work();
+    for (auto &t : pool) t.join();
+    collate_host_cut(names, name_off, n_records, cell_rec_off, n_cells, out_order, out_group_off, out_n_groups, out_cell_group_off);
+    return OEM_OK;
+    OEM_API_END("oem_test_collate_host")
 }
 
 // Test hook: the host build of oem_shortest_f64.h.  The texts of the n finite f64 with these bits, one after the other

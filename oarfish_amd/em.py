@@ -301,8 +301,49 @@ def _discard_tables(L, res, n_cells):
     return [discard_dict(dts[c]) for c in range(n_cells)]
 
 
+_COLLATE_MODES = {"sort": _lib.OEM_COLLATE_SORT, "adjacent": _lib.OEM_COLLATE_ADJACENT}
+
+
+def collate_names(names, cell_rec_off, secondary=None, mode: str = "sort", device: int = 0):
+    """The records of cells collated by read name on the device (``oem_collate_names``; alignment_parser.rs:170-241,
+    and :301-437 with ``mode="adjacent"``).
+
+    ``names``: the records' read names, whatever ``types.pack_read_names`` accepts (a sequence of ``str`` / ``bytes`` or
+    a ``(blob, offsets)`` pair); none is empty or holds a 0 byte.  ``cell_rec_off``: cell ``c`` owns the records
+    ``cell_rec_off[c] : cell_rec_off[c + 1]``.  ``secondary``: one flag per record (the SAM secondary flag), or None.
+
+    Returns ``(order, group_off, cell_group_off)``: per cell, ``order`` holds the cell's record indices sorted by
+    (name bytes, secondary, index) -- the identity under ``"adjacent"`` --; ``records[order]`` with ``group_off`` and
+    ``cell_group_off`` is what ``em_cells_records_sparse`` and ``CellsStream.push_records`` take.
+    """
+    from .types import pack_read_names
+    if mode not in _COLLATE_MODES:
+        raise ValueError(f"mode must be one of {sorted(_COLLATE_MODES)}, not {mode!r}")
+    cell_rec_off = np.ascontiguousarray(cell_rec_off, dtype=np.uint64)
+    if cell_rec_off.ndim != 1 or len(cell_rec_off) < 1:
+        raise ValueError("cell_rec_off needs n_cells + 1 entries")
+    n = len(names[1]) - 1 if isinstance(names, tuple) and len(names) == 2 and not isinstance(names[1], (str, bytes)) else len(names)
+    blob, off = pack_read_names(names, n)
+    sec = None
+    if secondary is not None:
+        sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
+        if len(sec) != n:
+            raise ValueError("secondary must have one entry per record")
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    group_off = np.empty(n + 1, dtype=np.uint64)
+    cell_group_off = np.empty(len(cell_rec_off), dtype=np.uint64)
+    n_groups = C.c_uint64(0)
+    if n and not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)   # (every name is empty: the call says so)
+    _lib.check(_lib.lib().oem_collate_names(
+        blob.ctypes.data if n else None, off.ctypes.data,
+        None if sec is None or not n else sec.ctypes.data, n, cell_rec_off.ctypes.data, len(cell_rec_off) - 1,
+        _COLLATE_MODES[mode], device, order.ctypes.data, group_off.ctypes.data, C.byref(n_groups), cell_group_off.ctypes.data))
+    return order[:n], group_off[:int(n_groups.value) + 1].copy(), cell_group_off
+
+
 def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
-                            conv_thresh: float = 1e-3, device: int = 0):
+                            conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None):
     """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
     oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
     model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
@@ -312,10 +353,24 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     ``dict(bin_width=..., model="binomial" | "logistic", growth_rate=...)``.  Returns ``(indptr, cols, vals,
     [RunInfo], kept, discard_tables)``: the first four as ``em_cells_sparse`` returns them, ``kept`` what
     ``add_groups`` returns per group, ``discard_tables`` one dict per cell -- that cell's builder's discard table.
+
+    ``names`` (with ``secondary``, as ``collate_names`` takes them): the records are collated by barcode only.
+    ``group_off`` is then ignored and ``cell_group_off`` is read as ``cell_rec_off``; the call collates the records on
+    the device, runs on ``records[order]`` and appends ``order`` to what it returns (``kept`` counts the groups of the
+    collated order).
     """
     from .builder import check_batch, filters_c
     F = filters_c(filters)
     txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+    order = None
+    if names is not None:
+        order, group_off, cell_group_off = collate_names(names, cell_group_off, secondary, device=device)
+        records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
+        if len(records) != len(order):
+            raise ValueError("names must have one entry per record")
+        records = records[order]
+    elif secondary is not None:
+        raise ValueError("secondary goes with names")
     records, group_off = check_batch(records, group_off)
     cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
     if cell_group_off.ndim != 1 or len(cell_group_off) < 1:
@@ -339,7 +394,8 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     except BaseException:
         L.oem_cells_result_destroy(res)
         raise
-    return (*_take_cells_result(res, n_cells, L), kept, tables)
+    out = (*_take_cells_result(res, n_cells, L), kept, tables)
+    return out if order is None else (*out, order)
 
 
 class CellsStream:
@@ -369,6 +425,7 @@ class CellsStream:
         if filters is not None and coverage is not None and "txp_len" not in coverage:
             coverage = dict(coverage, txp_len=txp_len)
         self._tables = None
+        self._device = device
         records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
         o.n_txps, o.device, o.max_iter, o.conv_thresh = n_txps, device, max_iter, conv_thresh
@@ -455,12 +512,23 @@ class CellsStream:
             len(row_ptr) - 1, nnz, C.byref(ticket)))
         return int(ticket.value)
 
-    def push_records(self, records, group_off) -> int:
+    def push_records(self, records, group_off=None, names=None, secondary=None):
         """One cell of a records session: its reads' records as a batch (``StoreBuilder.add_groups``' arguments).
-        Returns the cell's ticket."""
+        Returns the cell's ticket.
+
+        With ``names`` (and ``secondary``, as ``collate_names`` takes them) the cell's records are in any order and
+        ``group_off`` is not given: the cell is collated on the device first, ``records[order]`` is pushed, and the call
+        returns ``(ticket, order)``."""
         if not self._h:
             raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
         records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
+        if names is not None:
+            order, group_off, _ = collate_names(names, [0, len(records)], secondary, device=self._device)
+            return self.push_records(records[order], group_off), order
+        if secondary is not None:
+            raise ValueError("secondary goes with names")
+        if group_off is None:
+            raise ValueError("push_records needs group_off, or the records' names")
         group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
         if group_off.ndim != 1 or len(group_off) < 1:
             raise ValueError("group_off needs n_groups + 1 entries")

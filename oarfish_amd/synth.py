@@ -471,6 +471,131 @@ def make_cell_records(cells, n_txps: int, seed: int = BASE_SEED + 23, threads: i
                                 np.concatenate(goffs), cgo, np.concatenate(kepts) if kepts else np.zeros(0, np.uint32), tables)
 
 
+_HEX = np.frombuffer(b"0123456789abcdef", dtype=np.uint8)
+_ILLUMINA_PREFIX = b"A00741:132:HJ3KVDSX2:"
+_ILLUMINA_XY = 31000   # x and y run over [1000, 32000): four or five digits
+
+
+def _coprime_multiplier(rng: np.random.Generator, m: int) -> int:
+    import math
+    while True:
+        a = int(rng.integers(1 << 16, 1 << 20)) | 1
+        if math.gcd(a, m) == 1:
+            return a
+
+
+def make_record_names(group_off, style: str = "uuid", seed: int = BASE_SEED + 24):
+    """Read names for grouped records: one name per group, distinct between groups, repeated for every record of the
+    group.  Returns ``(blob uint8, offsets uint64[n_records + 1])``, what ``types.pack_read_names`` passes through.
+
+    ``style="uuid"``: 36 bytes, lower-case hex with dashes, as ONT reads carry them -- random from the first byte on.
+    ``style="illumina"``: ``instrument:run:flowcell:lane:tile:x:y`` with one instrument, run and flowcell, so that all
+    names share their first 21 bytes and differ in length (37 to 39 bytes)."""
+    group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+    per_group = _group_names(len(group_off) - 1, style, seed)
+    return _flatten_names(np.repeat(per_group, np.diff(group_off).astype(np.int64), axis=0))
+
+
+def _flatten_names(per_record):
+    """Rows of name bytes, 0 where a name has no byte -> (blob, offsets)."""
+    present = per_record != 0
+    off = np.zeros(len(per_record) + 1, dtype=np.uint64)
+    np.cumsum(present.sum(axis=1, dtype=np.uint64), out=off[1:])
+    return per_record[present], off
+
+
+def _group_names(n_groups: int, style: str, seed: int):
+    """One row of name bytes per group (0: no byte there)."""
+    rng = np.random.default_rng([seed, 0xC011])
+    if style == "uuid":
+        raw = rng.integers(0, 256, size=(n_groups, 16), dtype=np.uint8)
+        with np.errstate(over="ignore"):   # times an odd number modulo 2^64: a bijection, so the names are distinct
+            head = (np.arange(n_groups, dtype=np.uint64) * np.uint64(int(rng.integers(1 << 62, 1 << 63)) | 1)
+                    + np.uint64(rng.integers(0, 1 << 63)))
+        raw[:, :8] = head.view(np.uint8).reshape(n_groups, 8)
+        hx = np.empty((n_groups, 32), dtype=np.uint8)
+        hx[:, 0::2] = _HEX[raw >> 4]
+        hx[:, 1::2] = _HEX[raw & 15]
+        per_group = np.full((n_groups, 36), ord("-"), dtype=np.uint8)
+        for dst, src, w in ((0, 0, 8), (9, 8, 4), (14, 12, 4), (19, 16, 4), (24, 20, 12)):
+            per_group[:, dst:dst + w] = hx[:, src:src + w]
+    elif style == "illumina":
+        modulus = 4 * 64 * _ILLUMINA_XY * _ILLUMINA_XY
+        if n_groups > modulus:
+            raise ValueError("too many groups for distinct illumina-style names")
+        u = (np.arange(n_groups, dtype=np.uint64) * np.uint64(_coprime_multiplier(rng, modulus))
+             + np.uint64(rng.integers(0, modulus))) % np.uint64(modulus)   # a bijection of [0, modulus): names stay distinct
+        x = u % np.uint64(_ILLUMINA_XY) + np.uint64(1000)
+        u //= np.uint64(_ILLUMINA_XY)
+        y = u % np.uint64(_ILLUMINA_XY) + np.uint64(1000)
+        u //= np.uint64(_ILLUMINA_XY)
+        tile = u % np.uint64(64) + np.uint64(1101)
+        lane = u // np.uint64(64) + np.uint64(1)
+        pre = np.frombuffer(_ILLUMINA_PREFIX, dtype=np.uint8)
+        per_group = np.zeros((n_groups, len(pre) + 1 + 1 + 4 + 1 + 5 + 1 + 5), dtype=np.uint8)   # 0: no byte here
+        per_group[:, :len(pre)] = pre
+        col = len(pre)
+
+        def digits(v, width, at):
+            for k in range(width):
+                d = (v // np.uint64(10 ** (width - 1 - k))) % np.uint64(10)
+                lead = v < np.uint64(10 ** (width - 1 - k))
+                per_group[:, at + k] = np.where(lead & (k < width - 1), 0, d.astype(np.uint8) + ord("0"))
+            return at + width
+
+        col = digits(lane, 1, col)
+        per_group[:, col] = ord(":")
+        col = digits(tile, 4, col + 1)
+        per_group[:, col] = ord(":")
+        col = digits(x, 5, col + 1)
+        per_group[:, col] = ord(":")
+        digits(y, 5, col + 1)
+    else:
+        raise ValueError(f"style must be 'uuid' or 'illumina', not {style!r}")
+    return per_group
+
+
+def shuffle_cell_records(cell_records: SyntheticCellRecords, seed: int = BASE_SEED + 25, style: str = "uuid", threads: int = 1,
+                         with_records: bool = True):
+    """``make_cell_records``' cells as a barcode-collated input holds them: every cell's records permuted, each with its
+    read's name (``make_record_names``; distinct between the reads of a cell).  The first record of a group is the
+    read's primary alignment, the others carry the secondary flag.  Returns ``(records, names, secondary,
+    cell_rec_off)`` -- ``names`` a ``(blob, offsets)`` pair --, the input of ``em.collate_names`` and of
+    ``em_cells_records_sparse(..., names=, secondary=)``.  Cell c's share is a pure function of (its groups, seed, c,
+    style).  ``with_records=False`` leaves the records alone and returns None in their place."""
+    cr = cell_records
+    group_off = np.ascontiguousarray(cr.group_off, dtype=np.uint64)
+    cgo = np.ascontiguousarray(cr.cell_group_off, dtype=np.int64)
+    n_cells = len(cgo) - 1
+    cell_rec_off = group_off[cgo]
+
+    def one(c):
+        goff = group_off[cgo[c]:cgo[c + 1] + 1] - group_off[cgo[c]]
+        n = int(goff[-1])
+        group_of = np.repeat(np.arange(len(goff) - 1), np.diff(goff).astype(np.int64))
+        secondary = np.ones(n, dtype=np.uint8)
+        secondary[goff[:-1][np.diff(goff) > 0].astype(np.int64)] = 0
+        perm = np.random.default_rng([seed, 0x5AFF, c]).permutation(n)
+        blob, off = _flatten_names(_group_names(len(goff) - 1, style, seed * 1000 + c)[group_of[perm]])
+        return perm + int(cell_rec_off[c]), blob, np.diff(off), secondary[perm]
+
+    if threads > 1 and n_cells > 1:
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            per_cell = list(ex.map(one, range(n_cells)))
+    else:
+        per_cell = [one(c) for c in range(n_cells)]
+    n = int(cell_rec_off[-1])
+    off = np.zeros(n + 1, dtype=np.uint64)
+    if per_cell:
+        np.cumsum(np.concatenate([x[2] for x in per_cell]), out=off[1:])
+    blob = np.concatenate([x[1] for x in per_cell]) if per_cell else np.zeros(0, dtype=np.uint8)
+    secondary = np.concatenate([x[3] for x in per_cell]) if per_cell else np.zeros(0, dtype=np.uint8)
+    records = None
+    if with_records:
+        records = cr.records[np.concatenate([x[0] for x in per_cell])] if per_cell else cr.records[:0]
+    return records, (blob, off), secondary, cell_rec_off
+
+
 @dataclass
 class SyntheticProjectedRecords:
     filters: dict                # the fields of oem_filters the records were made for
