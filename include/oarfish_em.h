@@ -49,7 +49,7 @@ extern "C" {
  *    (oem_proj_record, oem_proj_opts, oem_builder_add_projected_group / _groups / _groups_device,
  *    oem_store_create_projected_records), the `.quant` and `.ambig_info.tsv` files of the bulk path as text formatted on
  *    the device (oem_quant_text, oem_ambig_text), a cell's records collated by read name on the device
- *    (oem_collate_names). */
+ *    (oem_collate_names), the bulk records session (oem_records_stream_*). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -771,6 +771,66 @@ int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, uint64_t *val
 /* NULL: no-op.  Before finish: cancels -- groups not yet started are dropped, a group on the device runs to its end,
  * the workers are joined.  No push may be in flight. */
 void oem_cells_stream_destroy(oem_cells_stream *s);
+
+/* A bulk RECORDS SESSION: oem_store_create_records for a caller that never holds all records at once (the reference's
+ * parse_alignments, alignment_parser.rs:301-437, adds group by group; its raw-read drivers, bulk.rs:364-682, hand
+ * chunks from mapper threads to a consumer).  Batches of whole groups are pushed from any number of threads as they are
+ * parsed; each pushing thread copies its batch into page-locked staging, one device worker filters the batches in ticket
+ * order while later ones arrive, a batch's records leave the device once its alignments are emitted, and finish joins
+ * the batches' CSR pieces on the device into the store.  One device per session. */
+typedef struct oem_records_stream oem_records_stream;
+
+typedef struct {
+    uint32_t n_txps;
+    int32_t  device;
+    uint32_t bin_width;          /* as oem_store_create_records */
+    int32_t  model;              /* -1 no coverage column, 0 logistic, 1 binomial */
+    double   growth_rate;
+    uint64_t max_staged_records; /* 0 = default; push blocks while more than this is staged and not yet on the device */
+    uint32_t reserved[4];        /* 0 */
+} oem_records_stream_opts;
+
+#define OEM_RECORDS_STREAM_INFO_BATCHES 1u               /* batches accepted */
+#define OEM_RECORDS_STREAM_INFO_GROUPS 2u                /* groups accepted */
+#define OEM_RECORDS_STREAM_INFO_RECORDS 3u               /* records accepted */
+#define OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH 4u /* batches whose device pass had started before
+                                                            oem_records_stream_finish was called */
+#define OEM_RECORDS_STREAM_INFO_BLOCKED_US 5u            /* microseconds pushes spent blocked on back-pressure, summed
+                                                            over the pushing threads */
+#define OEM_RECORDS_STREAM_INFO_HOST_BATCHES 6u          /* batches the host loop took (a score beyond +-2^24, or a
+                                                            score_prob_denom without a table) */
+
+/* Argument errors (opts, filters, txp_len or out NULL, n_txps = 0, a model outside -1 .. 1, bin_width = 0 under a
+ * model, a non-zero reserved word) are reported before any device is touched; without a device the call returns
+ * OEM_ERR_NO_DEVICE.  filters and txp_len (n_txps entries) are copied.  *out = NULL on any failure. */
+int oem_records_stream_create(const oem_records_stream_opts *opts, const oem_filters *filters, const uint64_t *txp_len,
+                              oem_records_stream **out);
+/* One batch of whole groups, as oem_store_create_records takes all of them (group_off: n_groups + 1 entries from 0).
+ * Thread-safe.  Checked on the calling thread: group_off starts at 0 and does not decrease, no group has more than
+ * 2^32 - 1 records, at most 2^31 - 2 groups; an argument error (OEM_ERR_ARG) rejects that batch only, uses no ticket and
+ * leaves the session usable.  The arrays are copied into page-locked staging by the calling thread: the caller may free
+ * them on return.  *out_ticket (optional) receives the batch's ticket: 0, 1, 2 ... in the order in which pushes were
+ * accepted; the session's input is the batches in ticket order.  A batch without groups is accepted and takes a ticket.
+ * The call blocks while more than max_staged_records records are staged and not yet on the device, except that a batch
+ * larger than that budget is accepted when nothing else is staged.  A ref_id that is not below n_txps is found on the
+ * device: it is sticky and its message names the batch ("ticket <ticket>") and the record's index within the batch.
+ * Device and allocation failures are sticky too: every later push and finish returns that status and its message.
+ * 2^32 or more kept alignments in all: OEM_ERR_ARG, sticky.  After finish: OEM_ERR_STATE. */
+int oem_records_stream_push(oem_records_stream *s, const oem_aln_record *records, const uint64_t *group_off,
+                            uint64_t n_groups, uint64_t *out_ticket);
+/* Waits for the batches still staged, joins the pieces and returns what oem_store_create_records returns for the
+ * concatenation of the accepted batches in ticket order, with the session's filters, txp_len, bin_width, model and
+ * growth_rate and these opts: the same store (row r is the r-th group, in ticket order, with out_kept > 0), out_kept
+ * (one entry per accepted group) and out_discard, however the input was cut into batches and whichever thread pushed
+ * what.  A session without batches gives a store of 0 reads.  opts are checked first (OEM_ERR_ARG leaves the session as
+ * it was).  While a push is in flight, or a second time: OEM_ERR_STATE.  *out = NULL on any failure. */
+int oem_records_stream_finish(oem_records_stream *s, const oem_store_opts *opts,
+                              uint32_t *out_kept /* all groups, ticket order; or NULL */,
+                              oem_discard_table *out_discard /* or NULL */, oem_store **out);
+int oem_records_stream_info(const oem_records_stream *s, uint32_t key, uint64_t *value);
+/* NULL: no-op.  Before finish: cancels -- batches not yet started are dropped, the batch on the device runs to its end,
+ * the worker is joined.  No push may be in flight. */
+void oem_records_stream_destroy(oem_records_stream *s);
 
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */

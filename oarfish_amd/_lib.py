@@ -37,6 +37,12 @@ OEM_CELLS_STREAM_INFO_GROUPS = 3
 OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH = 4
 OEM_CELLS_STREAM_INFO_BLOCKED_US = 5
 OEM_CELLS_STREAM_INFO_GROUPS_BATCHED = 6
+OEM_RECORDS_STREAM_INFO_BATCHES = 1
+OEM_RECORDS_STREAM_INFO_GROUPS = 2
+OEM_RECORDS_STREAM_INFO_RECORDS = 3
+OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH = 4
+OEM_RECORDS_STREAM_INFO_BLOCKED_US = 5
+OEM_RECORDS_STREAM_INFO_HOST_BATCHES = 6
 OEM_INFO_WEIGHT_DICT_ENTRIES = 1
 OEM_INFO_TILES = 2
 OEM_INFO_REMOTE_ALIGNMENTS = 3
@@ -69,6 +75,8 @@ ABI_SYMBOLS = [
     "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables", "oem_collate_names",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
+    "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
+    "oem_records_stream_destroy",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
     "oem_comm_set_option", "oem_comm_info", "oem_store_attach_comm",
     "oem_time_m_step", "oem_time_em_iters", "oem_time_bootstrap_passes", "oem_time_allreduce",
@@ -132,6 +140,11 @@ class CellsStreamOptsC(C.Structure):
                 ("coverage", C.c_uint32), ("bin_width", C.c_uint32), ("model", C.c_int32), ("growth_rate", C.c_double),
                 ("group_nnz", C.c_uint64), ("group_cells", C.c_uint32), ("max_staged_nnz", C.c_uint64),
                 ("reserved", C.c_uint32 * 4)]
+
+
+class RecordsStreamOptsC(C.Structure):
+    _fields_ = [("n_txps", C.c_uint32), ("device", C.c_int32), ("bin_width", C.c_uint32), ("model", C.c_int32),
+                ("growth_rate", C.c_double), ("max_staged_records", C.c_uint64), ("reserved", C.c_uint32 * 4)]
 
 
 class StoreOptsC(C.Structure):
@@ -228,6 +241,12 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_stream_info.argtypes = [vp, u32, C.POINTER(u64)]
     L.oem_cells_stream_destroy.argtypes = [vp]
     L.oem_cells_stream_destroy.restype = None
+    L.oem_records_stream_create.argtypes = [C.POINTER(RecordsStreamOptsC), vp, vp, C.POINTER(vp)]
+    L.oem_records_stream_push.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    L.oem_records_stream_finish.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
+    L.oem_records_stream_info.argtypes = [vp, u32, C.POINTER(u64)]
+    L.oem_records_stream_destroy.argtypes = [vp]
+    L.oem_records_stream_destroy.restype = None
     L.oem_comm_unique_id.argtypes = [vp]
     L.oem_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.oem_comm_destroy.argtypes = [vp]
@@ -281,6 +300,8 @@ def testing_lib() -> C.CDLL:
         L.oem_test_collate_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, C.POINTER(u64), vp]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.oem_debug_records_stream_finish_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.oem_debug_records_stream_last_join.argtypes = [vp]
         _testing = L
     return _testing
 

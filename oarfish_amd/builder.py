@@ -239,6 +239,88 @@ class StoreBuilder:
         return DeviceStore._adopt(self._lib, h, len(self.txp_len), int(device))
 
 
+RECORDS_STREAM_INFO = {"batches": _lib.OEM_RECORDS_STREAM_INFO_BATCHES, "groups": _lib.OEM_RECORDS_STREAM_INFO_GROUPS,
+                       "records": _lib.OEM_RECORDS_STREAM_INFO_RECORDS,
+                       "batches_before_finish": _lib.OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH,
+                       "blocked_us": _lib.OEM_RECORDS_STREAM_INFO_BLOCKED_US,
+                       "host_batches": _lib.OEM_RECORDS_STREAM_INFO_HOST_BATCHES}
+
+
+class RecordsStream:
+    """The bulk records session (``oem_records_stream_*``): ``DeviceStore.from_records`` for a pipeline that never holds
+    all records at once.  ``push`` batches of whole groups from any number of threads as they are parsed (each call
+    copies its batch into page-locked staging and returns its ticket; the device filters batch k while batch k + 1 is
+    staged); ``finish`` returns what ``from_records`` returns for the batches concatenated in ticket order.  A context
+    manager: leaving the block destroys the session (an unfinished one is cancelled)."""
+
+    def __init__(self, filters, txp_len, coverage: Optional[str] = None, bin_width: int = 100, growth_rate: float = 2.0,
+                 device: int = 0, max_staged_records: int = 0):
+        self._lib = _lib.lib()
+        self.filters = filters_c(filters)
+        self.txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        self.device = int(device)
+        o = _lib.RecordsStreamOptsC()
+        o.n_txps, o.device, o.bin_width, o.model = len(self.txp_len), self.device, bin_width, _model_code(coverage)
+        o.growth_rate, o.max_staged_records = growth_rate, int(max_staged_records)
+        self._h = C.c_void_p()
+        self._check(self._lib.oem_records_stream_create(C.byref(o), C.addressof(self.filters), self.txp_len.ctypes.data,
+                                                        C.byref(self._h)))
+
+    _check = StoreBuilder._check
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.oem_records_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        if not self._h.value:
+            raise RuntimeError("RecordsStream is closed")
+        return self._h
+
+    def push(self, records, group_off) -> int:
+        """One batch (``records`` / ``group_off`` as in ``StoreBuilder.add_groups``); returns its ticket.  Thread-safe;
+        blocks while the staging budget is full."""
+        records, group_off = check_batch(records, group_off)
+        ticket = C.c_uint64(0)
+        self._check(self._lib.oem_records_stream_push(self.handle, records.ctypes.data if len(records) else None,
+                                                      group_off.ctypes.data, len(group_off) - 1, C.byref(ticket)))
+        return int(ticket.value)
+
+    def info(self) -> dict:
+        out = {}
+        for name, key in RECORDS_STREAM_INFO.items():
+            v = C.c_uint64(0)
+            self._check(self._lib.oem_records_stream_info(self.handle, key, C.byref(v)))
+            out[name] = int(v.value)
+        return out
+
+    def finish(self, reorder_rows: int = 0, window_cap: int = 0, layout_build: int = 0, weight_coding: int = 0):
+        """``(DeviceStore, kept, discard_table)`` as ``DeviceStore.from_records`` returns them for the accepted batches
+        concatenated in ticket order."""
+        from .types import DeviceStore
+        o = store_opts(reorder_rows, window_cap, layout_build, weight_coding)
+        kept = np.zeros(self.info()["groups"], dtype=np.uint32)
+        dt = _lib.DiscardTableC()
+        h = C.c_void_p()
+        self._check(self._lib.oem_records_stream_finish(self.handle, C.addressof(o), kept.ctypes.data, C.addressof(dt),
+                                                        C.byref(h)))
+        return DeviceStore._adopt(self._lib, h, len(self.txp_len), self.device), kept, discard_dict(dt)
+
+
 def _model_code(model) -> int:
     codes = {None: -1, "logistic": 0, "binomial": 1}
     if model not in codes:

@@ -238,6 +238,34 @@ extern "C" int oem_debug_cells_records_last_csr(uint64_t *dims3, uint32_t *row_p
     return cells_records_last_csr(dims3, row_ptr, tid, as_prob_bits, start, end, cell_row_off);
 }
 
+// Test hook: ends a records session (oem_records_stream_*) as oem_records_stream_finish does, but copies the joined CSR
+// to the host instead of making a store of it, so that the join can be compared bit for bit.  dims3 = rows, alignments,
+// groups, always; row_ptr (rows + 1, u32), tid / as_prob as bits / start / end / strand (alignments each; the last three
+// are left alone by a session without a model) and kept (groups) are copied when they fit caps3 (OEM_ERR_ARG otherwise);
+// any of them may be NULL.  *join_ms (or NULL): k_stream_concat by HIP events.
+namespace oem {
+int records_stream_finish_csr(oem_records_stream *s, uint64_t *dims3, const uint64_t *caps3, uint32_t *row_ptr, uint32_t *tid,
+                              uint32_t *as_prob_bits, uint32_t *start, uint32_t *end, uint8_t *strand, uint32_t *kept,
+                              oem_discard_table *dt, float *join_ms);
+float records_stream_last_join_ms();
+}
+extern "C" int oem_debug_records_stream_finish_csr(oem_records_stream *s, uint64_t *dims3, const uint64_t *caps3, uint32_t *row_ptr,
+                                                   uint32_t *tid, uint32_t *as_prob_bits, uint32_t *start, uint32_t *end,
+                                                   uint8_t *strand, uint32_t *kept, oem_discard_table *dt, float *join_ms)
+{
+    OEM_API_BEGIN
+    return records_stream_finish_csr(s, dims3, caps3, row_ptr, tid, as_prob_bits, start, end, strand, kept, dt, join_ms);
+    OEM_API_END("oem_debug_records_stream_finish_csr")
+}
+
+// ms of k_stream_concat (HIP events) in this thread's last oem_records_stream_finish; 0 when there was nothing to join
+extern "C" int oem_debug_records_stream_last_join(float *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_records_stream_last_join: NULL argument");
+    *out = records_stream_last_join_ms();
+    return OEM_OK;
+}
+
 // Test hook: the n caller bytes at `data` as one LZ4 frame, by the path oem_assignment_text_lz4 compresses a chunk with
 // (upload, k_lz4_blocks, scan, k_lz4_gather; blocks of OEM_LZ4_BLOCK_BYTES), so that tests can feed crafted inputs.
 // *out_len = the frame's length, always; the frame is copied to out when it fits cap (else OEM_ERR_ARG).
