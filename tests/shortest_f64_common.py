@@ -1,5 +1,5 @@
 """Value sets shared by tests/test_shortest_f64.py (the host build of oem_shortest_f64.h) and
-tests/test_quant_text_gpu.py (its device build)."""
+tests/test_quant_text_gpu.py (its device build): both builds see literally the same arrays."""
 import numpy as np
 
 LONGEST = 0x8000000000000001          # -5e-324: `-0.`, 323 zeros, `5` -- the 327 bytes of kShortestF64MaxLen
@@ -32,3 +32,14 @@ def edge_bits() -> np.ndarray:
     bits += [b | (1 << 63) for b in bits[::10]]
     bits += [0, 1 << 63, LONGEST]
     return np.array(bits, dtype=np.uint64)
+
+
+def seeded_bits() -> np.ndarray:
+    """10^5 finite bit patterns: 50 000 random ones, then counts as an EM leaves them -- 40 000 log-uniform in
+    (1e-12, 5e6), the integers 1 .. 5000 and the eighths 1/8 .. 625."""
+    rng = np.random.default_rng(20250119)
+    raw = rng.integers(0, 1 << 64, 60_000, dtype=np.uint64)
+    raw = raw[(raw & np.uint64(0x7FF0000000000000)) != np.uint64(0x7FF0000000000000)][:50_000]
+    em = np.concatenate([np.exp(rng.uniform(np.log(1e-12), np.log(5e6), 40_000)), np.arange(1, 5001, dtype=np.float64),
+                         np.arange(1, 5001) / 8.0])
+    return np.concatenate([raw, bits_of(em)])

@@ -3,7 +3,12 @@
 The reference for the body is existing code: `writers.write_out_prob` on `DeviceStore.assignment_probs` (held to the
 oracle by tests/test_gpu_parity.py::test_aux_counts_and_assignment_probs); the device text must equal the file it
 writes, after its T + 1 header lines, byte for byte.  The one place the two differ by design -- 0/0, which the
-reference prints as `NaN` -- has its expected bytes written out by hand (test_nan_literal)."""
+reference prints as `NaN` -- has its expected bytes written out by hand (test_nan_literal).
+
+That reference shares the device's own probabilities with the text, so a wrong kept set would cancel.  The edge cases
+(tests/prob_edges_common.py: rounding ties at every decimal count, probabilities equal to the threshold, a kept -0.0,
+the carry into the integer digit) take nothing from the device: their expected bytes are the oracle's probabilities
+printed by Python (tests/test_prob_edges.py checks that side on the CPU)."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +16,10 @@ import pytest
 
 from oarfish_amd import _lib, synth, writers
 from oarfish_amd.types import DeviceStore, InMemoryAlignmentStore, pack_read_names
+from oracle import c_oracle
+
+from . import lz4_common
+from . import prob_edges_common as pe
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +157,86 @@ def test_hand_built_store(tmp_path):
         assert bare.text.tobytes().split(b"\n")[:-1] == [l[l.index(b"\t"):] for l in lines[:-1]]
         pair = d.assignment_text(counts, 1e-6, pack_read_names(names, n))
         assert pair.text.tobytes() == res.text.tobytes()
+
+
+@pytest.mark.parametrize("thresh,decimals", [(1e-4, 4), (1e-5, 5), (1e-7, 7), (1e-8, 8)])
+def test_hand_built_store_at_the_other_decimal_counts(thresh, decimals, tmp_path):
+    """test_hand_built_store prints with 6, 3 and 3 decimals; these are the counts in between."""
+    row_ptr, tid, as_prob, counts, names = hand_built()
+    str_names = [b.decode("latin-1") for b in names]
+    assert writers.prob_display_decimals(thresh) == decimals
+    with DeviceStore(row_ptr, tid, as_prob, None, WIDE_T) as d:
+        probs = d.assignment_probs(counts, thresh)
+        res = d.assignment_text(counts, thresh, names)
+    assert res.text.tobytes() == python_body(tmp_path, row_ptr, tid, probs, str_names, WIDE_T, thresh)
+    check_offsets(res, len(names))
+    assert res.line(11) == b"half-mass\t1\t42\t1." + b"0" * decimals + b"\n"
+
+
+_edges = {}
+
+
+def edge_case():
+    """The edge store and, once for the module, the oracle's probabilities and the expected text at every threshold."""
+    if not _edges:
+        st = pe.EdgeStore()
+        pe.assert_exact(st)
+        o = c_oracle.Store(st.row_ptr, st.tid, st.as_prob, None, st.n_txps)
+        want = {}
+        for thresh in pe.THRESHOLDS:
+            probs = c_oracle.assignment_probs(o, st.counts, thresh)
+            want[thresh] = (probs,) + pe.expected_text(st, probs, thresh, st.names)
+        _edges.update(st=st, want=want)
+    return _edges["st"], _edges["want"]
+
+
+def assert_same_text(res, body, line_off, kept, what):
+    got = res.text.tobytes()
+    if got != body:
+        gl, wl = got.split(b"\n"), body.split(b"\n")
+        bad = next((i for i, (a, b) in enumerate(zip(gl, wl)) if a != b), min(len(gl), len(wl)))
+        pytest.fail(f"{what}: line {bad}: device {gl[bad:bad + 1]!r}, expected {wl[bad:bad + 1]!r}")
+    assert np.array_equal(res.line_off, line_off) and np.array_equal(res.kept, kept), what
+
+
+@pytest.mark.parametrize("thresh", pe.THRESHOLDS, ids=repr)
+def test_edge_store_equals_the_oracle_printed_by_python(thresh):
+    """Ties (d = 3 .. 9), threshold equality and its two neighbours (0.2, 0.25, 0.5), -0.0 and the carry (0): the
+    device's probabilities are the oracle's bit for bit, -1 markers included, and text, line_off and kept are what
+    Python's formatting makes of the oracle's probabilities."""
+    st, want = edge_case()
+    probs, body, line_off, kept = want[thresh]
+    with DeviceStore(st.row_ptr, st.tid, st.as_prob, None, st.n_txps) as d:
+        got_probs = d.assignment_probs(st.counts, thresh)
+        res = d.assignment_text(st.counts, thresh, st.names)
+    assert np.array_equal(got_probs, probs) and np.array_equal(np.signbit(got_probs), np.signbit(probs))
+    assert_same_text(res, body, line_off, kept, thresh)
+    pe.check_edge_lines(st, thresh, res.text.tobytes(), res.line_off, res.kept)
+    check_offsets(res, st.n_reads)
+
+
+@pytest.mark.parametrize("thresh", [0.0, 1e-3, pe.around(0.2)[2]], ids=repr)
+def test_edge_store_in_chunks_and_compressed(thresh, monkeypatch):
+    """The same expected bytes from the chunked call (four or more chunks, two workgroups striding over each) and,
+    decoded, from the compressed call; 0 has the signs and the carry, 1e-3 the d = 3 ties, the neighbour above 0.2
+    the lines that keep nothing."""
+    st, want = edge_case()
+    _, body, line_off, kept = want[thresh]
+    buf = len(body) // 4 - 50
+    assert len(body) > 4 * buf and buf > 200
+    prefix = b"%d\t%d\n" % (st.n_txps, st.n_reads)
+    with DeviceStore(st.row_ptr, st.tid, st.as_prob, None, st.n_txps) as d:
+        frame = d.assignment_text_lz4(st.counts, thresh, st.names, prefix=prefix)
+    assert lz4_common.decode_everywhere(frame.text.tobytes()).content == prefix + body
+    assert np.array_equal(frame.line_off, line_off) and np.array_equal(frame.kept, kept)
+    monkeypatch.setenv("OEM_TEXT_BUF_BYTES", str(buf))
+    monkeypatch.setenv("OEM_TEXT_GRID_BLOCKS", "2")
+    with _lib.testing():
+        with DeviceStore(st.row_ptr, st.tid, st.as_prob, None, st.n_txps) as d:
+            parts = d.assignment_text(st.counts, thresh, st.names)
+            bare = d.assignment_text(st.counts, thresh)
+    assert_same_text(parts, body, line_off, kept, "chunks")
+    assert bare.text.tobytes().split(b"\n") == [l[l.index(b"\t"):] if l else l for l in body.split(b"\n")]
 
 
 def test_nan_literal():

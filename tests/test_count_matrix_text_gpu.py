@@ -3,7 +3,11 @@
 The reference is existing code: every case compares the device bytes with the `.count.mtx` that
 `writers.write_single_cell_output` writes for the same triplets (`writers.csr_triplets` of the CSR).  The cases with
 knobs run in the test-only library, where OEM_MTX_BUF_BYTES cuts the entries into chunks and OEM_MTX_GRID_BLOCKS makes
-a workgroup walk several tiles."""
+a workgroup walk several tiles.
+
+The value sets tests/test_shortest_f32.py holds the host build of oem_shortest_f32.h to (tests/shortest_f32_common.py)
+run through the device build as well (test_host_value_sets_on_the_device): there each line's value field is also
+compared with `writers.rust_display` computed in the test."""
 import os
 
 import numpy as np
@@ -13,6 +17,7 @@ import oarfish_amd
 from oarfish_amd import _lib, synth, writers
 from oarfish_amd.em import count_matrix_text
 
+from . import shortest_f32_common as sets
 from .shortest_f32_common import as_f32, exponent_grid
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +157,51 @@ def test_every_exponent_on_the_device(tmp_path):
     vals = as_f32(np.concatenate([bits, bits[::7] | np.uint32(0x80000000)]))
     cols = (np.arange(len(vals)) % 1000).astype(np.uint32)
     check_against_writer(tmp_path, [0, len(vals)], cols, vals, 1000)
+
+
+# name -> (the set as tests/test_shortest_f32.py draws it, values there are rounded to f32; how many there must be)
+HOST_SETS = {
+    "random_bit_patterns": (sets.random_bit_patterns, 100_000),
+    "em_counts": (lambda: sets.bits_of_f32(sets.em_counts()), 100_000),
+    "integers": (lambda: sets.bits_of_f32(sets.integers()), 70_000),
+    "eighths": (lambda: sets.bits_of_f32(sets.eighths()), 4096),
+    "subnormal_ladder": (sets.subnormal_ladder, 1023),
+    "powers_of_ten_neighbours": (sets.powers_of_ten_neighbours, 418),
+    "specials_and_negatives": (sets.specials_and_negatives, 14),
+}
+
+
+@pytest.mark.parametrize("name", list(HOST_SETS))
+def test_host_value_sets_on_the_device(name, tmp_path, monkeypatch):
+    """A value set of the host build as a matrix of four cells (the second empty, the cuts off the workgroup tiles):
+    the text is the writer's, and the value field of every line is `rust_display(x, f32=True)`, NaNs and infinities
+    included as drawn.  The random patterns once more in the test-only library, in six or more chunks with two
+    workgroups walking the tiles: the same bytes and line_off."""
+    make, count = HOST_SETS[name]
+    vals = as_f32(make())
+    n = len(vals)
+    assert n == count
+    if name == "random_bit_patterns":
+        assert np.isnan(vals).sum() > 100                     # (the infinities are in specials_and_negatives)
+    n_txps = 60_000
+    cols = (np.arange(n) * 7 % n_txps).astype(np.uint32)
+    indptr = [0, n // 3 + 1, n // 3 + 1, n - n // 5, n]
+    whole, body = check_against_writer(tmp_path, indptr, cols, vals, n_txps)
+    fields = [l.split(b" ")[2] for l in body.split(b"\n")[:-1]]
+    got = whole.text.tobytes().split(b"\n")[3:-1]
+    assert len(got) == len(fields) == n
+    for i, (x, line, f) in enumerate(zip(vals, got, fields)):
+        want = writers.rust_display(x, f32=True).encode()
+        assert line.split(b" ")[2] == want == f, (i, hex(int(vals.view(np.uint32)[i])), line)
+    if name == "random_bit_patterns":
+        buf = MAX_LINE * (n // 6)
+        assert -(-n // (buf // MAX_LINE)) >= 6
+        monkeypatch.setenv("OEM_MTX_BUF_BYTES", str(buf))
+        monkeypatch.setenv("OEM_MTX_GRID_BLOCKS", "2")
+        with _lib.testing():
+            parts = count_matrix_text(indptr, cols, vals, n_txps, prefix=b"")
+        assert parts.text.tobytes() == body
+        assert np.array_equal(parts.line_off, whole.line_off) and np.array_equal(parts.kept, whole.kept)
 
 
 def test_end_to_end_files(tmp_path):

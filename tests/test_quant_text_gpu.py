@@ -9,7 +9,11 @@ through the LDS stage or were written directly.
 
 The columns (see `columns`): lines 0 .. 255, the first workgroup at the defaults, have short names and short counts
 around the longest text an f64 has (327 bytes, next to a `0`), and fit the stage; lines 256 .. 511 have 300-byte names
-and overflow it; the rest draw their counts from the edge list of tests/test_shortest_f64.py."""
+and overflow it; the rest draw their counts from the edge list of tests/test_shortest_f64.py.
+
+The 10^5 seeded values tests/test_shortest_f64.py holds the host build of oem_shortest_f64.h to
+(shortest_f64_common.seeded_bits) run through the device build too, next to 10^5 seeded (unique, total) pairs for
+`.ambig_info.tsv` (the `seeded` fixture: one call of the host writer makes both references)."""
 import ctypes as C
 import os
 
@@ -18,7 +22,7 @@ import pytest
 
 from oarfish_amd import _lib, synth, writers
 
-from .shortest_f64_common import LONGEST, as_f64, edge_bits
+from .shortest_f64_common import LONGEST, as_f64, edge_bits, seeded_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -249,3 +253,85 @@ def test_end_to_end_files(tmp_path):
     for ext in (".quant", ".ambig_info.tsv"):
         assert open(out + ext, "rb").read() == open(want + ext, "rb").read(), ext
     assert os.path.exists(out + ".meta_info.json")
+
+
+# -- the host build's 10^5 seeded values, and 10^5 seeded pairs ---------------------------------------------------------
+def ambig_pairs(n=100_000):
+    """(unique, total): the first half uniform over all u32; the second half drawn from the values within 2 of a
+    power of ten, 10^0 .. 10^9 (every digit-count edge of all three columns; unique > total saturates to 0)."""
+    rng = np.random.default_rng(20250121)
+    near = np.array(sorted({10 ** k + o for k in range(10) for o in range(-2, 3)} - {-1}), dtype=np.uint32)
+    assert len(near) == 49 and near[0] == 0 and near[-1] == 1_000_000_002
+    half = n // 2
+    unique = np.concatenate([rng.integers(0, 1 << 32, half, dtype=np.uint64), near[rng.integers(0, len(near), n - half)]])
+    total = np.concatenate([rng.integers(0, 1 << 32, half, dtype=np.uint64), near[rng.integers(0, len(near), n - half)]])
+    unique[half:half + len(near)] = near                          # every one of them at least once in each column,
+    total[half:half + len(near)] = near[::-1]
+    unique[half + len(near):half + 2 * len(near)] = near[::-1]    # and as the difference's neighbour on either side
+    total[half + len(near):half + 2 * len(near)] = near
+    return unique.astype(np.uint32), total.astype(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def seeded(tmp_path_factory):
+    counts = as_f64(seeded_bits())
+    n = len(counts)
+    assert n == 100_000
+    names = [f"t{i % 10}" if i % 3 else "" for i in range(n)]
+    lens = list(range(n))
+    unique, total = ambig_pairs(n)
+    out = str(tmp_path_factory.mktemp("seeded") / "ref")
+    writers.write_output(out, {}, names, lens, counts, unique, total)
+    q = open(out + ".quant", "rb").read()[len(QUANT_HEADER):].split(b"\n")
+    a = open(out + ".ambig_info.tsv", "rb").read()[len(AMBIG_HEADER):].split(b"\n")
+    assert len(q) == n + 1 and len(a) == n + 1
+    return dict(names=names, lens=lens, counts=counts, unique=unique, total=total, quant=q[:-1], ambig=a[:-1])
+
+
+def test_seeded_values_on_the_device(seeded):
+    """50 000 random finite patterns, 40 000 log-uniform, 5 000 integers, 5 000 eighths: every count field is
+    `rust_display(x)`, the text and line_off are the host writer's.  The random patterns average well over 128 bytes
+    a line (a tile of 256 overflows the 32 KiB stage), the EM-shaped counts under 20, so the call takes both the
+    LDS-staged path and the direct one."""
+    s = seeded
+    res = quant(s, len(s["counts"]))
+    check(res, b"", s["quant"])
+    got = res.text.tobytes().split(b"\n")[:-1]
+    for i, (x, line) in enumerate(zip(s["counts"], got)):
+        assert line.rsplit(b"\t", 1)[1] == writers.rust_display(x).encode(), (i, hex(int(s["counts"].view(np.uint64)[i])), line)
+    with _lib.testing():
+        again = quant(s, len(s["counts"]))
+        path = last_call()
+    assert again.text.tobytes() == res.text.tobytes() and np.array_equal(again.line_off, res.line_off)
+    assert path["chunks"] == 1 and path["staged"] >= 1 and path["direct"] >= 1
+    assert path["staged"] + path["direct"] == -(-len(got) // 256)
+
+
+def test_seeded_values_in_chunks(seeded, monkeypatch):
+    """The same 10^5 lines cut into four or more chunks, 64 workgroups walking each chunk's tiles."""
+    s = seeded
+    bounds = [len(x) + MAX_TAIL for x in s["names"]]
+    buf = sum(bounds) // 4 + 7
+    want_chunks, _ = planned_chunks(bounds, buf)
+    assert want_chunks >= 4
+    monkeypatch.setenv("OEM_QUANT_BUF_BYTES", str(buf))
+    monkeypatch.setenv("OEM_QUANT_GRID_BLOCKS", "64")
+    with _lib.testing():
+        check(quant(s, len(bounds), QUANT_HEADER), QUANT_HEADER, s["quant"])
+        path = last_call()
+    assert path["chunks"] == want_chunks and path["staged"] >= 1 and path["direct"] >= 1
+
+
+def test_seeded_pairs_on_the_device(seeded, monkeypatch):
+    """10^5 (unique, total) pairs against the host writer's lines: whole, and in three or more chunks."""
+    s = seeded
+    n = len(s["unique"])
+    u, t = s["unique"].astype(np.int64), s["total"].astype(np.int64)
+    assert (u[: n // 2] > 10 ** 9).sum() > 1000 and (u > t).sum() > 1000 and (u == t).sum() > 100
+    assert s["ambig"][n // 2] == b"0\t1000000002\t1000000002" and s["ambig"][n // 2 + 48] == b"1000000002\t0\t0"
+    check(ambig(s, n), b"", s["ambig"])
+    buf = AMBIG_MAX_LINE * (n // 3) + 5
+    monkeypatch.setenv("OEM_QUANT_BUF_BYTES", str(buf))
+    with _lib.testing():
+        check(ambig(s, n, AMBIG_HEADER), AMBIG_HEADER, s["ambig"])
+        assert last_call()["chunks"] == -(-n // (buf // AMBIG_MAX_LINE)) >= 3

@@ -13,7 +13,8 @@ import pytest
 
 from oarfish_amd.writers import rust_display
 
-from .shortest_f32_common import as_f32, exponent_grid
+from .shortest_f32_common import (as_f32, em_counts, eighths, exponent_grid, integers, powers_of_ten_neighbours,
+                                   random_bit_patterns, specials_and_negatives, subnormal_ladder)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "shortest_f32_main.cpp")
@@ -55,38 +56,38 @@ def test_every_exponent(exe):
 
 
 def test_subnormals(exe):
-    check_bits(exe, [1 << k for k in range(23)] + list(range(1, 1001)))
+    bits = subnormal_ladder()
+    assert len(bits) == 23 + 1000
+    check_bits(exe, bits)
 
 
 def test_around_the_powers_of_ten(exe):
-    bits = []
-    for k in range(-45, 39):
-        b = int(np.array([float(f"1e{k}")], dtype=np.float64).astype(np.float32).view(np.uint32)[0])
-        bits += [v for v in range(b - 2, b + 3) if 0 < v < 0x7F800000]
+    bits = powers_of_ten_neighbours()
     assert len(bits) > 5 * 80
     check_bits(exe, bits)
 
 
 def test_integers_and_eighths(exe):
-    check_values(exe, np.arange(1, 70_001))
-    check_values(exe, np.arange(1, 4097) / 8.0)
+    assert len(integers()) == 70_000 and len(eighths()) == 4096
+    check_values(exe, integers())
+    check_values(exe, eighths())
 
 
 def test_counts_of_the_em(exe):
-    rng = np.random.default_rng(20250117)
-    x = np.exp(rng.uniform(np.log(1e-6), np.log(5e4), 100_000))
-    assert x.min() > 1e-6 and x.max() < 5e4
+    x = em_counts()
+    assert len(x) == 100_000 and x.min() > 1e-6 and x.max() < 5e4
     check_values(exe, x)
 
 
 def test_random_bit_patterns(exe):
-    rng = np.random.default_rng(20250118)
-    check_bits(exe, rng.integers(0, 1 << 32, 100_000, dtype=np.uint64).astype(np.uint32))
+    bits = random_bit_patterns()
+    assert len(bits) == 100_000
+    check_bits(exe, bits)
 
 
 def test_specials_and_negatives(exe):
-    bits = [0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F800001]
-    bits += [0x80000000 | int(b) for b in (0x3F800000, 0x3DCCCCCD, 0x00000001, 0x7F7FFFFF, 0x4B800000, 0x00800000, 0x501502F9)]
+    bits = specials_and_negatives()
+    assert len(bits) == 14
     check_bits(exe, bits)
     r = subprocess.run([exe], input="".join(f"{b:x}\n" for b in bits[:7]), capture_output=True, text=True)
     assert r.stdout.split("\n")[:7] == ["0 1", "-0 2", "inf 3", "-inf 4", "NaN 3", "NaN 3", "NaN 3"]

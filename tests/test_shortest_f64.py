@@ -19,7 +19,7 @@ import pytest
 from oarfish_amd import _lib, build
 from oarfish_amd.writers import rust_display
 
-from .shortest_f64_common import LONGEST, as_f64, bits_of, edge_bits
+from .shortest_f64_common import LONGEST, as_f64, bits_of, edge_bits, seeded_bits
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "shortest_f64_main.cpp")
@@ -92,12 +92,7 @@ def test_edge_list_equals_rust_display():
 
 def test_seeded_values_equal_rust_display():
     """10^5 values: random finite bit patterns, and counts as an EM leaves them (log-uniform, integers, eighths)."""
-    rng = np.random.default_rng(20250119)
-    raw = rng.integers(0, 1 << 64, 60_000, dtype=np.uint64)
-    raw = raw[(raw & np.uint64(0x7FF0000000000000)) != np.uint64(0x7FF0000000000000)][:50_000]
-    em = np.concatenate([np.exp(rng.uniform(np.log(1e-12), np.log(5e6), 40_000)), np.arange(1, 5001, dtype=np.float64),
-                         np.arange(1, 5001) / 8.0])
-    bits = np.concatenate([raw, bits_of(em)])
+    bits = seeded_bits()
     assert len(bits) == 100_000
     check_against_rust_display(bits)
 
