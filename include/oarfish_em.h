@@ -49,7 +49,8 @@ extern "C" {
  *    (oem_proj_record, oem_proj_opts, oem_builder_add_projected_group / _groups / _groups_device,
  *    oem_store_create_projected_records), the `.quant` and `.ambig_info.tsv` files of the bulk path as text formatted on
  *    the device (oem_quant_text, oem_ambig_text), a cell's records collated by read name on the device
- *    (oem_collate_names), the bulk records session (oem_records_stream_*). */
+ *    (oem_collate_names), the bulk records session (oem_records_stream_*), the collation and the records call in one
+ *    (oem_em_run_cells_records_names_sparse). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -695,6 +696,38 @@ int oem_collate_names(const uint8_t *names, const uint64_t *name_off, const uint
                       uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */, int device,
                       uint32_t *out_order, uint64_t *out_group_off, uint64_t *out_n_groups,
                       uint64_t *out_cell_group_off);
+
+/* single_cell.rs:104-188 from its first step on, in one call: oem_collate_names and oem_em_run_cells_records_sparse
+ * joined on the device.  records (n_records) and names / name_off / secondary are in the caller's INPUT order, collated
+ * by barcode only; cell c owns the records [cell_rec_off[c], cell_rec_off[c + 1]).  mode, names, name_off, secondary and
+ * cell_rec_off are oem_collate_names' arguments, the rest oem_em_run_cells_records_sparse's.
+ *
+ * The result is what the two calls give when the caller joins them -- oem_collate_names, the records put into
+ * out_order order, oem_em_run_cells_records_sparse with the collation's group_off and cell_group_off -- but the order
+ * is applied on the device, one group of cells at a time, and the caller neither waits for it nor gathers.  Exactly
+ * equal to that join: out_order (n_records), out_group_off (capacity n_records + 1), *out_n_groups, out_cell_group_off
+ * (n_cells + 1), out_kept (capacity n_records; *out_n_groups entries are written, one per group of the collated order)
+ * and every table of oem_cells_result_discard_tables.  Each of the five outputs may be NULL.  The entries and infos are
+ * equal as oem_em_run_cells_records_sparse states it: up to floating-point summation order.  Under
+ * OEM_COLLATE_ADJACENT the order is the identity and nothing is moved.
+ *
+ * Argument errors are those of the two calls (oem_collate_names' on names, name_off, cell_rec_off, n_records, a cell's
+ * size and mode; oem_em_run_cells_records_sparse's on filters, txp_len, n_txps, model and bin_width; records NULL with
+ * n_records > 0), reported before any device use.  Found on the device: an empty name or a name with a 0 byte
+ * (OEM_ERR_ARG naming the first such record of the first such group of cells); a mapped record whose ref_id is not
+ * below n_txps (OEM_ERR_ARG naming the cell and the record's index in the caller's input order); an alignment outside
+ * its transcript under a coverage model (OEM_ERR_STATE naming the cell).  Limits: n_records <= 2^32 - 1, a cell at most
+ * 2^31 - 2 records.  Without a device: OEM_ERR_NO_DEVICE.  *out = NULL on any failure. */
+int oem_em_run_cells_records_names_sparse(
+    const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+    const oem_aln_record *records, uint64_t n_records,
+    const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+    const uint64_t *cell_rec_off, uint32_t n_cells, uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */,
+    uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+    uint32_t *out_order /* n_records, or NULL */, uint64_t *out_group_off /* n_records + 1, or NULL */,
+    uint64_t *out_n_groups /* or NULL */, uint64_t *out_cell_group_off /* n_cells + 1, or NULL */,
+    uint32_t *out_kept /* capacity n_records, *out_n_groups entries written; or NULL */,
+    oem_cells_result **out);
 
 /* A per-cell SESSION: the caller pushes cells one by one, from any number of threads, as they become available
  * (single_cell.rs:96-193: N workers each pop one cell and build its private store).  The library stages the cells,

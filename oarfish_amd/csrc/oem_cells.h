@@ -122,7 +122,8 @@ int cells_records_last_csr(uint64_t *dims3, uint32_t *row_ptr, uint32_t *tid, ui
 // oem_cells.hip: the two halves of a per-cell call that its forms share.
 // The cut: cells [0, n_cells) into groups of consecutive cells under the group rule, cell c owning entries
 // [cell_off[c], cell_off[c + 1]) of `ptr` (reads of a CSR's row pointers, or record groups of their offsets: then the
-// bound counts records, which bound the alignments kept); one large group is split head : rest.
+// bound counts records, which bound the alignments kept); one large group is split head : rest.  ptr = NULL: cell_off
+// are record offsets themselves (records that are not cut into reads yet: they bound the reads and the alignments).
 std::vector<std::pair<uint32_t, uint32_t>> cut_cells_groups(const uint64_t *cell_off, uint32_t n_cells, const uint64_t *ptr,
                                                             uint32_t n_txps);
 // The workers: two host threads (testing build: OEM_CELLS_WORKERS) draw groups from one counter and call

@@ -422,7 +422,8 @@ int check_cell_row_off(const char *who, const uint64_t *cell_row_off, uint32_t n
 std::vector<std::pair<uint32_t, uint32_t>> cut_cells_groups(const uint64_t *cell_off, uint32_t n_cells, const uint64_t *ptr,
                                                             uint32_t n_txps)
 {
-    const uint64_t nnz = n_cells ? ptr[cell_off[n_cells]] - ptr[cell_off[0]] : 0;
+    const auto at = [ptr](uint64_t i) { return ptr ? ptr[i] : i; }; // (no ptr: the entries are counted themselves)
+    const uint64_t nnz = n_cells ? at(cell_off[n_cells]) - at(cell_off[0]) : 0;
     // Cells are independent problems, so a large experiment is cut into groups of consecutive cells
     // that bound the batched store (transcript space < 2^32, <= 2^30 alignments, and the layout
     // builder's tile x bucket table); each group is one batched run on the device.
@@ -434,7 +435,7 @@ std::vector<std::pair<uint32_t, uint32_t>> cut_cells_groups(const uint64_t *cell
         while (c1 < n_cells) {
             const uint64_t cells = (uint64_t)(c1 + 1 - c0);
             const uint64_t reads = cell_off[c1 + 1] - cell_off[c0];
-            const uint64_t gnnz = ptr[cell_off[c1 + 1]] - ptr[cell_off[c0]];
+            const uint64_t gnnz = at(cell_off[c1 + 1]) - at(cell_off[c0]);
             if (!cells_group_fits(cells, reads, gnnz, n_txps, max_group_nnz)) break;
             ++c1;
         }

@@ -18,6 +18,18 @@
 //
 // A group takes the host loop instead (one host builder, cell after cell; the same result) when the filter does: no gap
 // table for score_prob_denom, or a mapped score beyond +-2^24 found by the measure pass.
+//
+// oem_em_run_cells_records_names_sparse takes the worker from its first step, sort_and_parse_barcode_records
+// (alignment_parser.rs:170-241): names and records in input order in.  Per group of cells, on the group's worker:
+//   collate     collate_resident (oem_collate_device.hip): the group's names go up through the upload lanes, the rounds
+//               run, and `order`, the group's group_off and cell_group_off stay on the device; the sort's buffers and the
+//               names are released before the records arrive
+//   upload      the group's records, in input order, through the same lanes (no kernel behind the chunks)
+//   gather      k_records_gather: dst[k] = src[order[k]] over 40-byte records, then the buffer in input order is freed
+//   filter      filter_device_resident: one k_filter_measure launch, the scans, k_filter_emit, k_filter_cell_offsets;
+//               one scalar (n_groups) and the n_cells + 1 cell offsets are what the host sees
+// and the group goes on as above.  The host loop, when the group takes it, gets order and group_off down and gathers
+// the group's records on the host.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -26,6 +38,7 @@
 #include <vector>
 
 #include "oem_cells.h"
+#include "oem_collate_device.h"
 #include "oem_filter_device.h"
 
 namespace oem {
@@ -136,38 +149,11 @@ int run_records_group_host(const char *who, const CellsRun &run, const RecordsFi
     return run_cells_group(run, cg, batched);
 }
 
-} // namespace
-
-int records_filter_setup(const char *who, const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps, RecordsFilter *rf)
+// The group behind its device filter pass (r, fc): kept and the tables go to the caller, the filtered CSR becomes the
+// group's resident one, and the group runs.  Consumes r.
+int run_filtered_group(const CellsRun &run, const RecordsGroup &rg, FilterResult &r, FilterCells &fc, bool keep, bool *batched)
 {
-    if (!filters || !txp_len || n_txps == 0) return fail(OEM_ERR_ARG, "%s: bad argument", who);
-    rf->f = *filters;
-    rf->txp_len.assign(txp_len, txp_len + n_txps);
-    rf->host_only = !filter_prob_table(filters->score_prob_denom, rf->tab);
-    return OEM_OK;
-}
-
-int run_records_group(const char *who, const CellsRun &run, const RecordsFilter &rf, const RecordsGroup &rg, bool *batched)
-{
-    *batched = false;
-    StageTimer tm;
     const uint32_t nc = rg.n_cells;
-    const bool keep = knob("OEM_TEST_KEEP_RECORDS_CSR", 0) != 0; // testing build: the hook reads the coordinates too
-    OEM_TRY(ensure_device(run.device));
-    FilterResult r;
-    FilterCells fc;
-    bool host = rf.host_only;
-    if (!host) {
-        fc.cell_group_off = rg.cell_group_off;
-        fc.n_cells = nc;
-        fc.first_cell = rg.first_cell;
-        fc.first_record = rg.first_record;
-        OEM_TRY(filter_device(who, rf.f, rf.txp_len.data(), run.n_txps, rf.tab, rg.records, rg.group_off, rg.n_groups, 0,
-                              run.cov != nullptr || keep, true, &r, &fc, rg.pinned));
-        host = r.host_rerun;
-    }
-    if (host) return run_records_group_host(who, run, rf, rg, batched);
-    tm.lap("records: upload + filter");
     if (rg.out_kept && rg.n_groups)
         OEM_HIP(hipMemcpy(rg.out_kept, r.n_kept.p, sizeof(uint32_t) * rg.n_groups, hipMemcpyDeviceToHost));
     std::copy(fc.tables.begin(), fc.tables.end(), rg.out_tables);
@@ -218,7 +204,189 @@ int run_records_group(const char *who, const CellsRun &run, const RecordsFilter 
     cg.blk = rg.blk;
     cg.infos = rg.infos;
     cg.launch = rg.launch;
-    const int rc = run_cells_group(run, cg, batched);
+    return run_cells_group(run, cg, batched);
+}
+
+
+// ---- names and records in input order (oem_em_run_cells_records_names_sparse)
+constexpr int kGT = 256;                           // k_records_gather's workgroup
+constexpr uint64_t kRecordWords = 5;               // a record as aligned 8-byte words
+constexpr uint64_t kUploadChunkRecords = 1ull << 20; // records per upload chunk of the lanes (40 MiB)
+constexpr uint64_t kGroupNameBytes = 16ull << 30;  // name bytes a group of cells may hold (testing build: OEM_CELLS_GROUP_NAME_BYTES)
+static_assert(sizeof(oem_aln_record) == 8 * kRecordWords && alignof(oem_aln_record) == 8, "a record is five aligned words");
+
+// dst[k] = src[order[k] - order_base] over the m records of a group, one lane per 8-byte word: word j of the
+// destination is word j % 5 of record j / 5.  The stores are lane i at base + 8 i, fully coalesced; the loads are runs of
+// five lanes on 40 contiguous bytes, scattered at that granularity, which is all the source allows.  (One lane per
+// record would make both sides 8 bytes at a stride of 40.)
+__global__ __launch_bounds__(kGT) void k_records_gather(uint64_t n_words, const uint32_t *__restrict__ order, uint32_t order_base,
+                                                         const uint64_t *__restrict__ src, uint64_t *__restrict__ dst)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kGT + threadIdx.x;
+    if (j >= n_words) return;
+    const uint64_t k = j / kRecordWords, w = j - k * kRecordWords;
+    dst[j] = src[(uint64_t)(order[k] - order_base) * kRecordWords + w];
+}
+
+// What a call of the names form shares between its groups, and where a group leaves what the caller asked for: the
+// groups' numbers in the call are known only when every group before has been collated, so kept and group_off wait in
+// the group's slot until the workers have joined.
+struct NamesCall {
+    CollateInput in;
+    const oem_aln_record *records = nullptr;
+    uint32_t *out_order = nullptr;
+    bool want_group_off = false, want_kept = false;
+};
+struct NamesSlot {
+    uint64_t n_groups = 0;
+    std::vector<uint64_t> group_off, cell_group_off; // from 0: n_groups + 1 (if asked for), n_cells + 1
+    std::vector<uint32_t> kept;                      // n_groups (if asked for)
+};
+
+// The records [r0, r0 + m) of the caller into d (input order) through the upload lanes.
+int upload_records(const oem_aln_record *records, uint64_t m, oem_aln_record *d)
+{
+    std::vector<uint64_t> cut;
+    for (uint64_t r = 0; r < m; r += kUploadChunkRecords) cut.push_back(r);
+    cut.push_back(m);
+    return filter_upload_measure<oem_aln_record>(records, d, cut.data(), cut.size() - 1, 1, nullptr, [](hipStream_t, uint64_t, uint64_t) {});
+}
+
+// The cells [c0, c1) of the call: collate, gather, filter and run.  rg: the group's place and outputs (records,
+// offsets and out_kept are filled in here).
+int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &rf, const NamesCall &nc, uint32_t c0, uint32_t c1,
+                    RecordsGroup rg, NamesSlot *slot, bool *batched)
+{
+    *batched = false;
+    StageTimer tm;
+    const uint32_t n_cells = c1 - c0;
+    const uint64_t r0 = nc.in.cell_rec_off[c0], m = nc.in.cell_rec_off[c1] - r0;
+    const bool keep = knob("OEM_TEST_KEEP_RECORDS_CSR", 0) != 0;
+    OEM_TRY(ensure_device(run.device));
+    slot->cell_group_off.assign((size_t)n_cells + 1, 0);
+    if (nc.want_group_off) slot->group_off.assign(1, 0);
+    rg.first_cell = c0;
+    rg.first_record = r0;
+    rg.n_cells = n_cells;
+    rg.cell_group_off = slot->cell_group_off.data();
+    if (m == 0) { // cells without records: no groups, and the run of cells without reads
+        const uint64_t zero = 0;
+        rg.group_off = &zero;
+        rg.n_groups = 0;
+        return run_records_group(who, run, rf, rg, batched);
+    }
+
+    CollateResident cr;
+    double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    OEM_TRY(collate_resident(nc.in, c0, c1, r0, 0, 0, info, &cr));
+    tm.lap("names: collate");
+    const uint64_t ng = cr.n_groups;
+    slot->n_groups = ng;
+    OEM_HIP(hipMemcpy(slot->cell_group_off.data(), cr.cell_group_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost));
+    if (nc.out_order) OEM_HIP(hipMemcpy(nc.out_order + r0, cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    if (nc.want_group_off) {
+        slot->group_off.resize(ng + 1);
+        OEM_HIP(hipMemcpy(slot->group_off.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
+    }
+    if (nc.want_kept) slot->kept.assign(ng, 0);
+    rg.n_groups = ng;
+    rg.out_kept = nc.want_kept ? slot->kept.data() : nullptr;
+    const bool sorting = nc.in.mode == kCollateSort;
+
+    FilterResult r;
+    FilterCells fc;
+    bool host = rf.host_only;
+    if (!host) {
+        DevBuf<oem_aln_record> d_in, d_sorted;
+        OEM_TRY(dev_alloc(&d_in.p, m, nullptr));
+        OEM_TRY(upload_records(nc.records + r0, m, d_in.p));
+        const oem_aln_record *d_recs = d_in.p;
+        if (sorting) { // (the adjacent cut's order is the identity)
+            OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
+            const uint64_t n_words = m * kRecordWords;
+            hipLaunchKernelGGL(k_records_gather, dim3((uint32_t)((n_words + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, n_words,
+                               (const uint32_t *)cr.order.p, (uint32_t)r0, (const uint64_t *)d_in.p, (uint64_t *)d_sorted.p);
+            OEM_HIP(hipGetLastError());
+            OEM_HIP(hipStreamSynchronize(nullptr));
+            d_in.reset(); // the group holds its records twice only for the length of the gather
+            d_recs = d_sorted.p;
+        }
+        fc.n_cells = n_cells;
+        fc.first_cell = c0;
+        fc.first_record = r0;
+        OEM_TRY(filter_device_resident(who, rf.f, rf.txp_len.data(), run.n_txps, rf.tab, d_recs, (const unsigned long long *)cr.group_off.p,
+                                       ng, (const unsigned long long *)cr.cell_group_off.p, run.cov != nullptr || keep, &r, &fc));
+        if (r.bad_ref_record != kNoRecord) { // a collated index: the caller knows its records by their input index
+            uint32_t at = 0;
+            OEM_HIP(hipMemcpy(&at, cr.order.p + r.bad_ref_record, sizeof at, hipMemcpyDeviceToHost));
+            const uint64_t *cro = nc.in.cell_rec_off;
+            const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, (uint64_t)at) - cro) - 1;
+            return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)c,
+                        (unsigned long long)at, nc.records[at].ref_id);
+        }
+        host = r.host_rerun;
+    }
+    if (host) { // the host loop: order and group_off come down, the host gathers the group's records
+        std::vector<uint32_t> order(m);
+        std::vector<uint64_t> goff(ng + 1);
+        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(goff.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
+        std::vector<oem_aln_record> sorted(m);
+        const uint64_t *cro = nc.in.cell_rec_off;
+        for (uint64_t k = 0; k < m; ++k) {
+            sorted[k] = nc.records[order[k]];
+            if (!(sorted[k].flags & OEM_REC_UNMAPPED) && sorted[k].ref_id >= run.n_txps) {
+                const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, (uint64_t)order[k]) - cro) - 1;
+                return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)c,
+                            (unsigned long long)order[k], sorted[k].ref_id);
+            }
+        }
+        rg.records = sorted.data();
+        rg.group_off = goff.data();
+        return run_records_group_host(who, run, rf, rg, batched);
+    }
+    tm.lap("names: upload + gather + filter");
+    cr.order.reset();
+    cr.group_off.reset();
+    cr.cell_group_off.reset();
+    const int rc = run_filtered_group(run, rg, r, fc, keep, batched);
+    tm.lap("names: group run");
+    return rc;
+}
+
+} // namespace
+
+int records_filter_setup(const char *who, const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps, RecordsFilter *rf)
+{
+    if (!filters || !txp_len || n_txps == 0) return fail(OEM_ERR_ARG, "%s: bad argument", who);
+    rf->f = *filters;
+    rf->txp_len.assign(txp_len, txp_len + n_txps);
+    rf->host_only = !filter_prob_table(filters->score_prob_denom, rf->tab);
+    return OEM_OK;
+}
+
+int run_records_group(const char *who, const CellsRun &run, const RecordsFilter &rf, const RecordsGroup &rg, bool *batched)
+{
+    *batched = false;
+    StageTimer tm;
+    const uint32_t nc = rg.n_cells;
+    const bool keep = knob("OEM_TEST_KEEP_RECORDS_CSR", 0) != 0; // testing build: the hook reads the coordinates too
+    OEM_TRY(ensure_device(run.device));
+    FilterResult r;
+    FilterCells fc;
+    bool host = rf.host_only;
+    if (!host) {
+        fc.cell_group_off = rg.cell_group_off;
+        fc.n_cells = nc;
+        fc.first_cell = rg.first_cell;
+        fc.first_record = rg.first_record;
+        OEM_TRY(filter_device(who, rf.f, rf.txp_len.data(), run.n_txps, rf.tab, rg.records, rg.group_off, rg.n_groups, 0,
+                              run.cov != nullptr || keep, true, &r, &fc, rg.pinned));
+        host = r.host_rerun;
+    }
+    if (host) return run_records_group_host(who, run, rf, rg, batched);
+    tm.lap("records: upload + filter");
+    const int rc = run_filtered_group(run, rg, r, fc, keep, batched);
     tm.lap("records: group run");
     return rc;
 }
@@ -328,6 +496,110 @@ extern "C" int oem_em_run_cells_records_sparse(const oem_filters *filters, const
     *out = r.release();
     return OEM_OK;
     OEM_API_END("oem_em_run_cells_records_sparse")
+}
+
+extern "C" int oem_em_run_cells_records_names_sparse(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                                     const oem_aln_record *records, uint64_t n_records, const uint8_t *names,
+                                                     const uint64_t *name_off, const uint8_t *secondary, const uint64_t *cell_rec_off,
+                                                     uint32_t n_cells, uint32_t mode, uint32_t bin_width, int model, double growth_rate,
+                                                     int device, uint32_t max_iter, double conv_thresh, uint32_t *out_order,
+                                                     uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off,
+                                                     uint32_t *out_kept, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_em_run_cells_records_names_sparse";
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (out_n_groups) *out_n_groups = 0;
+    // the checks of oem_store_create_records, of oem_collate_names and of the cells calls, before any device use
+    OEM_TRY(check_store_from_records(who, filters, txp_len, n_txps, bin_width, model, nullptr));
+    if (!name_off || !cell_rec_off) return fail(OEM_ERR_ARG, "%s: name_off or cell_rec_off is NULL", who);
+    OEM_TRY(check_collate_input(who, names, name_off, n_records, cell_rec_off, n_cells, mode));
+    if (n_records && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+    if (model >= 0) OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, 0, 0));
+    OEM_TRY(ensure_device(device));
+    RecordsFilter rf;
+    OEM_TRY(records_filter_setup(who, filters, txp_len, n_txps, &rf));
+
+    CellsCoverage cc;
+    CellsRun run{n_txps, device, max_iter, conv_thresh};
+    if (model >= 0) {
+        cc.txp_len = rf.txp_len.data();
+        cc.n_txps = n_txps;
+        cc.bin_width = bin_width;
+        cc.model = model;
+        cc.growth_rate = growth_rate;
+        OEM_TRY(cells_coverage_setup(&cc));
+        run.cov = &cc;
+    }
+    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
+    r->n_cells = n_cells;
+    r->infos.resize(n_cells);
+    r->from_records = true;
+    r->discard.assign(n_cells, oem_discard_table{});
+
+    // The cut of the records call (a group's records bound its reads and alignments), and then what the collation adds:
+    // a group is one collation batch, so it also stays within a batch's records and within the name bytes of a group.
+    std::vector<std::pair<uint32_t, uint32_t>> groups;
+    {
+        const uint64_t max_records = collate_batch_records(), max_bytes = (uint64_t)knob("OEM_CELLS_GROUP_NAME_BYTES", (long)kGroupNameBytes);
+        for (const auto &g : cut_cells_groups(cell_rec_off, n_cells, nullptr, n_txps)) {
+            uint32_t c0 = g.first;
+            while (c0 < g.second) {
+                uint32_t c1 = c0 + 1;
+                while (c1 < g.second && cell_rec_off[c1 + 1] - cell_rec_off[c0] <= max_records &&
+                       name_off[cell_rec_off[c1 + 1]] - name_off[cell_rec_off[c0]] <= max_bytes)
+                    ++c1;
+                groups.emplace_back(c0, c1);
+                c0 = c1;
+            }
+        }
+    }
+    NamesCall nc;
+    nc.in.who = who;
+    nc.in.names = names;
+    nc.in.name_off = name_off;
+    nc.in.secondary = secondary;
+    nc.in.cell_rec_off = cell_rec_off;
+    nc.in.mode = mode;
+    nc.in.chunk_bytes = collate_chunk_bytes();
+    nc.records = records;
+    nc.out_order = out_order;
+    nc.want_group_off = out_group_off != nullptr;
+    nc.want_kept = out_kept != nullptr;
+    std::vector<SparseBlock> blocks(groups.size());
+    std::vector<NamesSlot> slots(groups.size());
+    OEM_TRY(run_cells_workers(who, run, groups, [&](size_t g, const CellsRun &grun, CellsGroupPath *path) -> int {
+        const uint32_t c0 = groups[g].first, c1 = groups[g].second;
+        RecordsGroup rg;
+        rg.out_tables = r->discard.data() + c0;
+        rg.blk = &blocks[g];
+        rg.infos = r->infos.data() + c0;
+        rg.launch = &path->launch;
+        bool batched = false;
+        const int rc = run_names_group(who, grun, rf, nc, c0, c1, rg, &slots[g], &batched);
+        path->batched = batched ? 1u : 0u;
+        return rc;
+    }));
+    // the groups' numbers in the call, now that every group's count is known
+    uint64_t group_base = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const uint32_t c0 = groups[g].first, c1 = groups[g].second;
+        const NamesSlot &sl = slots[g];
+        if (out_cell_group_off)
+            for (uint32_t c = c0; c <= c1; ++c) out_cell_group_off[c] = group_base + sl.cell_group_off[c - c0];
+        if (out_group_off)
+            for (uint64_t k = 0; k < sl.n_groups; ++k) out_group_off[group_base + k] = cell_rec_off[c0] + sl.group_off[k];
+        if (out_kept && sl.n_groups) std::memcpy(out_kept + group_base, sl.kept.data(), sizeof(uint32_t) * sl.n_groups);
+        group_base += sl.n_groups;
+    }
+    if (out_cell_group_off && groups.empty()) out_cell_group_off[0] = 0;
+    if (out_group_off) out_group_off[group_base] = n_records;
+    if (out_n_groups) *out_n_groups = group_base;
+    OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
+    *out = r.release();
+    return OEM_OK;
+    OEM_API_END("oem_em_run_cells_records_names_sparse")
 }
 
 extern "C" int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out)

@@ -6,6 +6,10 @@
 // behind each chunk, on its lane, run k_collate_validate (an empty name, a 0 byte) and the first key kernel, so both
 // overlap the next chunk's copy.  Nothing after the upload knows of the chunks.
 //
+// A batch is collate_resident (oem_collate_device.h): it leaves order, the batch's group_off and cell_group_off on the
+// device.  oem_collate_names copies them to the caller's arrays; oem_em_run_cells_records_names_sparse
+// (oem_cells_records.hip) gathers and filters the batch's records behind them and copies only what its caller asked for.
+//
 // kCollateSort is a most-significant-key-first radix sort over 8-byte keys (collate_key), on the records that are still
 // undecided:
 //   - the start is, per cell, the primaries in index order and then the secondaries in index order (k_collate_start,
@@ -31,7 +35,7 @@
 // where the input is collated already.
 #include <hipcub/hipcub.hpp>
 
-#include "oem_collate.h"
+#include "oem_collate_device.h"
 #include "oem_filter_device.h"
 
 namespace oem {
@@ -41,7 +45,6 @@ namespace {
 constexpr int kCT = 256;
 constexpr uint64_t kCollateChunkBytes = 64ull << 20;    // name bytes per upload chunk (the test-only library: OEM_COLLATE_CHUNK_BYTES)
 constexpr uint64_t kCollateBatchRecords = 1ull << 27;   // records per batch (the test-only library: OEM_COLLATE_BATCH_RECORDS)
-constexpr uint64_t kCollateMaxBatch = (1ull << 31) - 2; // a single cell beyond this is refused (the scans take m + 1 items as an int)
 
 thread_local double g_collate_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -264,18 +267,20 @@ __global__ __launch_bounds__(kCT) void k_collate_adjacent(uint64_t r0, uint64_t 
     head[i] = h ? 1u : 0u;
 }
 
-// gidx: the exclusive scan of head (m + 1 entries).  The marks become group_off (positions of the call), the order's
-// entries record indices of the call, and the cells' first groups are sampled.
+// gidx: the exclusive scan of head (m + 1 entries).  The marks become group_off (positions from pos_base, closed by
+// pos_base + m), the order's entries record indices from order_base, and the cells' first groups are sampled.
 __global__ __launch_bounds__(kCT) void k_collate_finish(uint64_t m, uint32_t n_cells, const uint32_t *__restrict__ head,
                                                          const uint64_t *__restrict__ gidx, const unsigned long long *__restrict__ cell_off,
-                                                         uint64_t rec_base, uint64_t group_base, uint32_t *__restrict__ order,
-                                                         uint64_t *__restrict__ group_off, uint64_t *__restrict__ cell_group_off)
+                                                         uint64_t order_base, uint64_t pos_base, uint64_t group_base,
+                                                         uint32_t *__restrict__ order, uint64_t *__restrict__ group_off,
+                                                         uint64_t *__restrict__ cell_group_off)
 {
     const uint64_t i = tid64();
     if (i <= n_cells) cell_group_off[i] = group_base + gidx[cell_off[i]];
+    if (i == 0) group_off[gidx[m]] = pos_base + m; // (gidx[m] = the batch's groups, at most m: the buffer has m + 1 entries)
     if (i >= m) return;
-    order[i] += (uint32_t)rec_base;
-    if (head[i]) group_off[gidx[i]] = rec_base + i;
+    order[i] += (uint32_t)order_base;
+    if (head[i]) group_off[gidx[i]] = pos_base + i;
 }
 
 inline dim3 grid_for(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kCT - 1) / kCT, 1)); }
@@ -326,22 +331,10 @@ int scan_u64(Scratch &sc, bool inclusive, In in, uint64_t *out, uint64_t n, hipS
 
 inline int bits_of(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 
-struct CollateCall {
-    const uint8_t *names;
-    const uint64_t *name_off;
-    const uint8_t *secondary;
-    const uint64_t *cell_rec_off;
-    uint32_t mode;
-    uint64_t chunk_bytes;
-    bool timing;
-    uint32_t *out_order;
-    uint64_t *out_group_off, *out_cell_group_off;
-    double info[8];
-};
+} // namespace
 
-// The cells [c0, c1) of the call, which hold its records [rec_base, rec_base + m), m > 0; *group_base counts the groups
-// before them and is advanced.
-int collate_batch(CollateCall &cc, uint32_t c0, uint32_t c1, uint64_t *group_base)
+int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t order_base, uint64_t pos_base, uint64_t group_base,
+                     double *info, CollateResident *out)
 {
     const uint32_t nc = c1 - c0;
     const uint64_t rec_base = cc.cell_rec_off[c0], m = cc.cell_rec_off[c1] - rec_base;
@@ -376,7 +369,7 @@ int collate_batch(CollateCall &cc, uint32_t c0, uint32_t c1, uint64_t *group_bas
     Scratch sc;
     sc.st = st;
     DevBuf<uint8_t> d_names, d_sec;
-    DevBuf<uint64_t> d_off, d_key, d_key_s, d_flags, d_scan, d_cgo;
+    DevBuf<uint64_t> d_off, d_key, d_key_s, d_flags, d_scan, d_cgo; // (d_key_s and d_cgo are handed to `out` in the end)
     DevBuf<unsigned long long> d_cell_off, d_words; // d_words: [0] zero byte, [1] empty name, [2] or, [3] and
     DevBuf<uint32_t> d_order, d_head, d_iota, d_perm1, d_perm2, d_run1, d_run1_s, d_pos[2], d_ord[2], d_run[2];
     OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16, nullptr));
@@ -446,16 +439,16 @@ int collate_batch(CollateCall &cc, uint32_t c0, uint32_t c1, uint64_t *group_bas
                 hipLaunchKernelGGL(k_collate_adjacent, grid_for(r1 - r0), dim3(kCT), 0, lane, r0, r1, (const uint8_t *)d_names.p,
                                    (const uint64_t *)d_off.p, off_base, (const unsigned long long *)d_cell_off.p, nc, d_order.p, d_head.p);
         }));
-    cc.info[1] += (double)n_chunks;
-    cc.info[3] += ms[0];
-    cc.info[4] += ms[1];
-    cc.info[6] += ms[5];
+    info[1] += (double)n_chunks;
+    info[3] += ms[0];
+    info[4] += ms[1];
+    info[6] += ms[5];
 
     unsigned long long words[4];
     OEM_HIP(hipMemcpy(words, d_words.p, sizeof words, hipMemcpyDeviceToHost));
     if (words[0] != kNoRecord || words[1] != kNoRecord) {
-        if (words[1] < words[0]) return fail(OEM_ERR_ARG, "oem_collate_names: record %llu has an empty name", words[1]);
-        return fail(OEM_ERR_ARG, "oem_collate_names: the name of record %llu contains a 0 byte", words[0]);
+        if (words[1] < words[0]) return fail(OEM_ERR_ARG, "%s: record %llu has an empty name", cc.who, words[1]);
+        return fail(OEM_ERR_ARG, "%s: the name of record %llu contains a 0 byte", cc.who, words[0]);
     }
 
     if (cc.timing) OEM_HIP(hipEventRecord(ev[0].e, st));
@@ -511,8 +504,8 @@ int collate_batch(CollateCall &cc, uint32_t c0, uint32_t c1, uint64_t *group_bas
             if (!n) break;
             run_max = (total >> 32) - 1;
         }
-        cc.info[0] = std::max(cc.info[0], (double)(round + 1));
-        cc.info[7] = std::max(cc.info[7], (double)sorted_rounds);
+        info[0] = std::max(info[0], (double)(round + 1));
+        info[7] = std::max(info[7], (double)sorted_rounds);
     }
     if (cc.timing) OEM_HIP(hipEventRecord(ev[1].e, st));
 
@@ -522,28 +515,75 @@ int collate_batch(CollateCall &cc, uint32_t c0, uint32_t c1, uint64_t *group_bas
         OEM_TRY(scan_u64(sc, false, in, d_scan.p, m + 1, st));
     }
     hipLaunchKernelGGL(k_collate_finish, grid_for(std::max<uint64_t>(m, nc + 1)), dim3(kCT), 0, st, m, nc, (const uint32_t *)d_head.p,
-                       (const uint64_t *)d_scan.p, (const unsigned long long *)d_cell_off.p, rec_base, *group_base, d_order.p, d_key_s.p,
-                       d_cgo.p);
+                       (const uint64_t *)d_scan.p, (const unsigned long long *)d_cell_off.p, order_base, pos_base, group_base, d_order.p,
+                       d_key_s.p, d_cgo.p);
     OEM_HIP(hipGetLastError());
     if (cc.timing) OEM_HIP(hipEventRecord(ev[2].e, st));
-    uint64_t n_groups = 0;
-    OEM_HIP(hipMemcpyAsync(&n_groups, d_scan.p + m, sizeof n_groups, hipMemcpyDeviceToHost, st));
-    OEM_HIP(hipMemcpyAsync(cc.out_order + rec_base, d_order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, st));
-    OEM_HIP(hipMemcpyAsync(cc.out_cell_group_off + c0, d_cgo.p, sizeof(uint64_t) * (nc + 1), hipMemcpyDeviceToHost, st));
+    OEM_HIP(hipMemcpyAsync(&out->n_groups, d_scan.p + m, sizeof out->n_groups, hipMemcpyDeviceToHost, st));
     OEM_HIP(hipStreamSynchronize(st));
-    if (n_groups) OEM_HIP(hipMemcpy(cc.out_group_off + *group_base, d_key_s.p, sizeof(uint64_t) * n_groups, hipMemcpyDeviceToHost));
-    *group_base += n_groups;
     if (cc.timing) {
         float t = 0.f;
         OEM_HIP(hipEventElapsedTime(&t, ev[0].e, ev[1].e));
-        cc.info[5] += t;
+        info[5] += t;
         OEM_HIP(hipEventElapsedTime(&t, ev[1].e, ev[2].e));
-        cc.info[5] += t;
+        info[5] += t;
     }
+    std::swap(out->order.p, d_order.p);
+    std::swap(out->group_off.p, d_key_s.p);
+    std::swap(out->cell_group_off.p, d_cgo.p);
+    return OEM_OK;
+}
+
+namespace {
+
+// One batch of oem_collate_names: the resident form, then its arrays to the caller's; *group_base counts the groups before
+// the batch and is advanced.
+int collate_batch(const CollateInput &cc, uint32_t c0, uint32_t c1, double *info, uint32_t *out_order, uint64_t *out_group_off,
+                  uint64_t *out_cell_group_off, uint64_t *group_base)
+{
+    const uint64_t rec_base = cc.cell_rec_off[c0], m = cc.cell_rec_off[c1] - rec_base;
+    CollateResident r;
+    OEM_TRY(collate_resident(cc, c0, c1, rec_base, rec_base, *group_base, info, &r));
+    OEM_HIP(hipMemcpy(out_order + rec_base, r.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    OEM_HIP(hipMemcpy(out_cell_group_off + c0, r.cell_group_off.p, sizeof(uint64_t) * ((size_t)(c1 - c0) + 1), hipMemcpyDeviceToHost));
+    if (r.n_groups) OEM_HIP(hipMemcpy(out_group_off + *group_base, r.group_off.p, sizeof(uint64_t) * r.n_groups, hipMemcpyDeviceToHost));
+    *group_base += r.n_groups;
     return OEM_OK;
 }
 
 } // namespace
+
+uint64_t collate_chunk_bytes()
+{
+    const long ck = knob("OEM_COLLATE_CHUNK_BYTES", (long)kCollateChunkBytes);
+    return ck > 0 ? (uint64_t)ck : kCollateChunkBytes;
+}
+
+uint64_t collate_batch_records()
+{
+    const long bk = knob("OEM_COLLATE_BATCH_RECORDS", (long)kCollateBatchRecords);
+    return bk > 0 ? std::min<uint64_t>((uint64_t)bk, kCollateMaxBatch) : kCollateBatchRecords;
+}
+
+int check_collate_input(const char *who, const uint8_t *names, const uint64_t *name_off, uint64_t n_records, const uint64_t *cell_rec_off,
+                        uint32_t n_cells, uint32_t mode)
+{
+    if (mode != OEM_COLLATE_SORT && mode != OEM_COLLATE_ADJACENT) return fail(OEM_ERR_ARG, "%s: mode %u is not a mode", who, mode);
+    if (n_records > 0xffffffffull) return fail(OEM_ERR_ARG, "%s: %llu records: more than 2^32 - 1", who, (unsigned long long)n_records);
+    if (n_records && !names) return fail(OEM_ERR_ARG, "%s: names is NULL and n_records is not 0", who);
+    if (name_off[0] != 0) return fail(OEM_ERR_ARG, "%s: name_off must start at 0", who);
+    for (uint64_t i = 0; i < n_records; ++i)
+        if (name_off[i + 1] < name_off[i]) return fail(OEM_ERR_ARG, "%s: name_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+    if (cell_rec_off[0] != 0) return fail(OEM_ERR_ARG, "%s: cell_rec_off must start at 0", who);
+    for (uint32_t c = 0; c < n_cells; ++c)
+        if (cell_rec_off[c + 1] < cell_rec_off[c]) return fail(OEM_ERR_ARG, "%s: cell_rec_off must be non-decreasing (cell %u)", who, c);
+    if (cell_rec_off[n_cells] != n_records)
+        return fail(OEM_ERR_ARG, "%s: cell_rec_off ends at %llu, not at n_records = %llu", who, (unsigned long long)cell_rec_off[n_cells],
+                    (unsigned long long)n_records);
+    for (uint32_t c = 0; c < n_cells; ++c)
+        if (cell_rec_off[c + 1] - cell_rec_off[c] > kCollateMaxBatch) return fail(OEM_ERR_ARG, "%s: cell %u has more than 2^31 - 2 records", who, c);
+    return OEM_OK;
+}
 
 void collate_last_call(double *out8) { std::memcpy(out8, g_collate_last, sizeof g_collate_last); }
 
@@ -558,30 +598,21 @@ extern "C" int oem_collate_names(const uint8_t *names, const uint64_t *name_off,
     OEM_API_BEGIN
     if (!name_off || !cell_rec_off || !out_order || !out_group_off || !out_n_groups || !out_cell_group_off)
         return fail(OEM_ERR_ARG, "oem_collate_names: name_off, cell_rec_off or an output is NULL");
-    if (mode != OEM_COLLATE_SORT && mode != OEM_COLLATE_ADJACENT) return fail(OEM_ERR_ARG, "oem_collate_names: mode %u is not a mode", mode);
-    if (n_records > 0xffffffffull) return fail(OEM_ERR_ARG, "oem_collate_names: %llu records: more than 2^32 - 1", (unsigned long long)n_records);
-    if (n_records && !names) return fail(OEM_ERR_ARG, "oem_collate_names: names is NULL and n_records is not 0");
-    if (name_off[0] != 0) return fail(OEM_ERR_ARG, "oem_collate_names: name_off must start at 0");
-    for (uint64_t i = 0; i < n_records; ++i)
-        if (name_off[i + 1] < name_off[i]) return fail(OEM_ERR_ARG, "oem_collate_names: name_off must be non-decreasing (record %llu)", (unsigned long long)i);
-    if (cell_rec_off[0] != 0) return fail(OEM_ERR_ARG, "oem_collate_names: cell_rec_off must start at 0");
-    for (uint32_t c = 0; c < n_cells; ++c)
-        if (cell_rec_off[c + 1] < cell_rec_off[c]) return fail(OEM_ERR_ARG, "oem_collate_names: cell_rec_off must be non-decreasing (cell %u)", c);
-    if (cell_rec_off[n_cells] != n_records)
-        return fail(OEM_ERR_ARG, "oem_collate_names: cell_rec_off ends at %llu, not at n_records = %llu", (unsigned long long)cell_rec_off[n_cells],
-                    (unsigned long long)n_records);
-    for (uint32_t c = 0; c < n_cells; ++c)
-        if (cell_rec_off[c + 1] - cell_rec_off[c] > kCollateMaxBatch)
-            return fail(OEM_ERR_ARG, "oem_collate_names: cell %u has more than 2^31 - 2 records", c);
+    OEM_TRY(check_collate_input("oem_collate_names", names, name_off, n_records, cell_rec_off, n_cells, mode));
     *out_n_groups = 0;
     OEM_TRY(ensure_device(device));
 
-    CollateCall cc{names, name_off, secondary, cell_rec_off, mode, 0, knob("OEM_COLLATE_TIMING", 0) != 0, out_order, out_group_off,
-                   out_cell_group_off, {0, 0, 0, 0, 0, 0, 0, 0}};
-    const long ck = knob("OEM_COLLATE_CHUNK_BYTES", (long)kCollateChunkBytes);
-    cc.chunk_bytes = ck > 0 ? (uint64_t)ck : kCollateChunkBytes;
-    const long bk = knob("OEM_COLLATE_BATCH_RECORDS", (long)kCollateBatchRecords);
-    const uint64_t batch_records = bk > 0 ? std::min<uint64_t>((uint64_t)bk, kCollateMaxBatch) : kCollateBatchRecords;
+    CollateInput cc;
+    cc.who = "oem_collate_names";
+    cc.names = names;
+    cc.name_off = name_off;
+    cc.secondary = secondary;
+    cc.cell_rec_off = cell_rec_off;
+    cc.mode = mode;
+    cc.chunk_bytes = collate_chunk_bytes();
+    cc.timing = knob("OEM_COLLATE_TIMING", 0) != 0;
+    double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint64_t batch_records = collate_batch_records();
     std::memset(g_collate_last, 0, sizeof g_collate_last);
 
     uint64_t group_base = 0;
@@ -590,8 +621,8 @@ extern "C" int oem_collate_names(const uint8_t *names, const uint64_t *name_off,
         uint32_t c1 = c0 + 1;
         while (c1 < n_cells && cell_rec_off[c1 + 1] - cell_rec_off[c0] <= batch_records) ++c1;
         if (cell_rec_off[c1] > cell_rec_off[c0]) {
-            OEM_TRY(collate_batch(cc, c0, c1, &group_base));
-            cc.info[2] += 1;
+            OEM_TRY(collate_batch(cc, c0, c1, info, out_order, out_group_off, out_cell_group_off, &group_base));
+            info[2] += 1;
         } else {
             for (uint32_t c = c0; c <= c1; ++c) out_cell_group_off[c] = group_base;
         }
@@ -599,7 +630,7 @@ extern "C" int oem_collate_names(const uint8_t *names, const uint64_t *name_off,
     }
     out_group_off[group_base] = n_records;
     *out_n_groups = group_base;
-    std::memcpy(g_collate_last, cc.info, sizeof cc.info);
+    std::memcpy(g_collate_last, info, sizeof info);
     return OEM_OK;
     OEM_API_END("oem_collate_names")
 }

@@ -48,6 +48,7 @@ struct FilterResult {
     DevBuf<uint64_t> txp_len; // the transcript lengths, kept for the coverage model
     oem_discard_table dt{};
     bool host_rerun = false;  // a score beyond +-2^24: nothing above is filled, the host loop takes the batch
+    unsigned long long bad_ref_record = kNoRecord; // the resident form only: the first record whose ref_id is not below n_txps
 };
 
 // The per-cell form of a pass (oem_cells_records.hip): the batch's groups belong to n_cells consecutive cells, cell c
@@ -164,6 +165,15 @@ int filter_upload_measure(const Rec *records, Rec *d_recs, const uint64_t *group
 int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
                   const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, uint64_t base, bool want_coords,
                   bool narrow, FilterResult *out, FilterCells *cells = nullptr, bool pinned_src = false);
+// The resident form of the per-cell pass (oem_em_run_cells_records_names_sparse): the batch's records, its group_off
+// (n_groups + 1, from 0) and its cells' cell_group_off (cells->n_cells + 1) are on the device already, so there are no
+// upload lanes: one k_filter_measure launch over [0, n_groups), then what filter_device does after its measure passes --
+// u32 row pointers, the cells' offsets and tables in `cells` (whose host cell_group_off is not read).  A ref_id that is
+// not below n_txps is no error here: out->bad_ref_record names the record (its index in d_records) and nothing else is
+// filled; the caller knows the record's origin and writes the message.  Runs on the null stream and leaves it idle.
+int filter_device_resident(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
+                           const oem_aln_record *d_records, const unsigned long long *d_group_off, uint64_t n_groups,
+                           const unsigned long long *d_cell_group_off, bool want_coords, FilterResult *out, FilterCells *cells);
 // The checks a device batch makes before any device use, and whether the host loop has to take it from the start
 // (*host_only: no gap table for this score_prob_denom).
 int filter_prepare_batch(const char *who, const oem_filters &F, const oem_aln_record *records, const uint64_t *group_off,

@@ -153,6 +153,63 @@ struct NonZeroToU64 {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v ? 1 : 0; }
 };
 
+// What follows a measure pass that found nothing to report: the tables, the two scans, the cells' offsets and the emit.
+// d_cgo / d_ccnt: the per-cell form's device arrays (with `cells`).
+int filter_scans_emit(const char *who, const oem_filters &F, uint32_t n_txps, const std::vector<float> &tab,
+                      const oem_aln_record *d_recs, const unsigned long long *d_goff, uint64_t n_groups, uint64_t base,
+                      bool want_coords, bool narrow, FilterResult *out, FilterCells *cells, const unsigned long long *d_cgo,
+                      const unsigned long long *d_ccnt, const int32_t *d_best, const FilterTotals &h_tot, bool timing)
+{
+    const uint32_t n_cells = cells ? cells->n_cells : 0;
+    DevBuf<uint64_t> d_aln_off, d_row_idx;
+    DevBuf<float> d_tab;
+    const uint64_t *cnt = (const uint64_t *)h_tot.counts;
+    out->dt = oem_discard_table{cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]};
+    if (cells) { // the cells' tables; the batch's is their sum
+        cells->tables.assign(n_cells, oem_discard_table{});
+        if (n_cells)
+            OEM_HIP(hipMemcpy(cells->tables.data(), d_ccnt, sizeof(oem_discard_table) * n_cells, hipMemcpyDeviceToHost));
+        uint64_t *sum = &out->dt.discard_5p;
+        for (const oem_discard_table &t : cells->tables)
+            for (int k = 0; k < kFilterCounters; ++k) sum[k] += (&t.discard_5p)[k];
+    }
+
+    // -- scans, emit ---------------------------------------------------------------------------------------------------
+    hipStream_t st = nullptr; // the emit follows the scans on the null stream (the lanes are idle)
+    Event ev[3];
+    if (timing)
+        for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
+    OEM_TRY(filter_scan_alloc(who, n_groups, base, want_coords, narrow, out, &d_aln_off, &d_row_idx, ev[0].e, ev[1].e));
+    const uint64_t nnz = out->nnz;
+    if (cells) {
+        OEM_TRY(dev_alloc(&cells->d_cell_row_off.p, (size_t)n_cells + 1, nullptr));
+        OEM_TRY(dev_alloc(&cells->d_cell_aln_off.p, (size_t)n_cells + 1, nullptr));
+        hipLaunchKernelGGL(k_filter_cell_offsets, dim3((n_cells + 1 + kFT - 1) / kFT), dim3(kFT), 0, st, d_cgo, n_cells,
+                           d_row_idx.p, d_aln_off.p, cells->d_cell_row_off.p, cells->d_cell_aln_off.p);
+        OEM_HIP(hipGetLastError());
+        cells->cell_row_off.resize((size_t)n_cells + 1);
+        cells->cell_aln_off.resize((size_t)n_cells + 1);
+        OEM_HIP(hipMemcpyAsync(cells->cell_row_off.data(), cells->d_cell_row_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost, st));
+        OEM_HIP(hipMemcpyAsync(cells->cell_aln_off.data(), cells->d_cell_aln_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost, st));
+    }
+    OEM_TRY(dev_alloc(&d_tab.p, tab.size(), nullptr));
+    if (!tab.empty()) OEM_HIP(hipMemcpy(d_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    if (n_groups && nnz) {
+        hipLaunchKernelGGL(k_filter_emit, dim3((uint32_t)((n_groups + kFT - 1) / kFT)), dim3(kFT), 0, st, F, d_recs, d_goff,
+                           n_groups, out->txp_len.p, n_txps, out->n_kept.p, d_best, d_aln_off.p, d_row_idx.p, d_tab.p,
+                           (uint64_t)tab.size(), base, out->row_ptr64.p, out->row_ptr32.p, out->tid.p, out->as_prob.p,
+                           out->start.p, out->end.p, out->strand.p);
+        OEM_HIP(hipGetLastError());
+    }
+    if (timing) OEM_HIP(hipEventRecord(ev[2].e, st));
+    OEM_HIP(hipStreamSynchronize(st));
+    if (timing) {
+        OEM_HIP(hipEventElapsedTime(&g_filter_ms[2], ev[0].e, ev[1].e));
+        OEM_HIP(hipEventElapsedTime(&g_filter_ms[3], ev[1].e, ev[2].e));
+    }
+    return OEM_OK; // (the scan results are released here, the records and offsets with the caller's scope)
+}
+
 } // namespace
 
 int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
@@ -167,8 +224,6 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
     DevBuf<unsigned long long> d_goff;
     DevBuf<int32_t> d_best;
     DevBuf<FilterTotals> d_tot;
-    DevBuf<uint64_t> d_aln_off, d_row_idx;
-    DevBuf<float> d_tab;
     DevBuf<unsigned long long> d_cgo, d_ccnt; // the per-cell form: the cells' first groups, their counters
     const uint32_t n_cells = cells ? cells->n_cells : 0;
     if (cells) {
@@ -222,51 +277,50 @@ int filter_device(const char *who, const oem_filters &F, const uint64_t *txp_len
         out->host_rerun = true;
         return OEM_OK;
     }
-    const uint64_t *cnt = (const uint64_t *)h_tot.counts;
-    out->dt = oem_discard_table{cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5], cnt[6], cnt[7], cnt[8], cnt[9]};
-    if (cells) { // the cells' tables; the batch's is their sum
-        cells->tables.assign(n_cells, oem_discard_table{});
-        if (n_cells)
-            OEM_HIP(hipMemcpy(cells->tables.data(), d_ccnt.p, sizeof(oem_discard_table) * n_cells, hipMemcpyDeviceToHost));
-        uint64_t *sum = &out->dt.discard_5p;
-        for (const oem_discard_table &t : cells->tables)
-            for (int k = 0; k < kFilterCounters; ++k) sum[k] += (&t.discard_5p)[k];
-    }
+    return filter_scans_emit(who, F, n_txps, tab, d_recs.p, d_goff.p, n_groups, base, want_coords, narrow, out, cells, d_cgo.p, d_ccnt.p,
+                             d_best.p, h_tot, timing);
+}
 
-    // -- scans, emit ---------------------------------------------------------------------------------------------------
-    hipStream_t st = nullptr; // the emit follows the scans on the null stream (the lanes are idle)
-    Event ev[3];
-    if (timing)
-        for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
-    OEM_TRY(filter_scan_alloc(who, n_groups, base, want_coords, narrow, out, &d_aln_off, &d_row_idx, ev[0].e, ev[1].e));
-    const uint64_t nnz = out->nnz;
-    if (cells) {
-        OEM_TRY(dev_alloc(&cells->d_cell_row_off.p, (size_t)n_cells + 1, nullptr));
-        OEM_TRY(dev_alloc(&cells->d_cell_aln_off.p, (size_t)n_cells + 1, nullptr));
-        hipLaunchKernelGGL(k_filter_cell_offsets, dim3((n_cells + 1 + kFT - 1) / kFT), dim3(kFT), 0, st, d_cgo.p, n_cells,
-                           d_row_idx.p, d_aln_off.p, cells->d_cell_row_off.p, cells->d_cell_aln_off.p);
+// The resident form (oem_filter_device.h): no upload lanes, one measure launch over all groups.
+int filter_device_resident(const char *who, const oem_filters &F, const uint64_t *txp_len, uint32_t n_txps, const std::vector<float> &tab,
+                           const oem_aln_record *d_records, const unsigned long long *d_group_off, uint64_t n_groups,
+                           const unsigned long long *d_cell_group_off, bool want_coords, FilterResult *out, FilterCells *cells)
+{
+    const bool timing = knob("OEM_FILTER_TIMING", 0) != 0;
+    const uint32_t n_cells = cells->n_cells;
+    hipStream_t st = nullptr;
+    DevBuf<int32_t> d_best;
+    DevBuf<FilterTotals> d_tot;
+    DevBuf<unsigned long long> d_ccnt;
+    OEM_TRY(dev_alloc(&d_ccnt.p, (size_t)n_cells * kFilterCounters, nullptr));
+    OEM_TRY(dev_alloc(&out->n_kept.p, n_groups + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_best.p, n_groups + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_tot.p, 1, nullptr));
+    OEM_TRY(dev_alloc(&out->txp_len.p, n_txps, nullptr));
+    FilterTotals h_tot;
+    std::memset(&h_tot, 0, sizeof(h_tot));
+    h_tot.bad_record = kNoRecord;
+    OEM_HIP(hipMemset(d_ccnt.p, 0, sizeof(uint64_t) * (n_cells ? (size_t)n_cells * kFilterCounters : 1)));
+    OEM_HIP(hipMemcpy(d_tot.p, &h_tot, sizeof(h_tot), hipMemcpyHostToDevice));
+    OEM_HIP(hipMemcpy(out->txp_len.p, txp_len, sizeof(uint64_t) * n_txps, hipMemcpyHostToDevice));
+    OEM_HIP(hipMemset(out->n_kept.p + n_groups, 0, sizeof(uint32_t))); // (the scans read n_groups + 1 entries)
+    if (n_groups) {
+        hipLaunchKernelGGL(k_filter_measure<true>, dim3((uint32_t)((n_groups + kFT - 1) / kFT)), dim3(kFT), 0, st, F, d_records,
+                           d_group_off, (uint64_t)0, n_groups, out->txp_len.p, n_txps, out->n_kept.p, d_best.p, d_tot.p,
+                           d_cell_group_off, n_cells, d_ccnt.p);
         OEM_HIP(hipGetLastError());
-        cells->cell_row_off.resize((size_t)n_cells + 1);
-        cells->cell_aln_off.resize((size_t)n_cells + 1);
-        OEM_HIP(hipMemcpyAsync(cells->cell_row_off.data(), cells->d_cell_row_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost, st));
-        OEM_HIP(hipMemcpyAsync(cells->cell_aln_off.data(), cells->d_cell_aln_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost, st));
     }
-    OEM_TRY(dev_alloc(&d_tab.p, tab.size(), nullptr));
-    if (!tab.empty()) OEM_HIP(hipMemcpy(d_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    if (n_groups && nnz) {
-        hipLaunchKernelGGL(k_filter_emit, dim3((uint32_t)((n_groups + kFT - 1) / kFT)), dim3(kFT), 0, st, F, d_recs.p, d_goff.p,
-                           n_groups, out->txp_len.p, n_txps, out->n_kept.p, d_best.p, d_aln_off.p, d_row_idx.p, d_tab.p,
-                           (uint64_t)tab.size(), base, out->row_ptr64.p, out->row_ptr32.p, out->tid.p, out->as_prob.p,
-                           out->start.p, out->end.p, out->strand.p);
-        OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpy(&h_tot, d_tot.p, sizeof(h_tot), hipMemcpyDeviceToHost));
+    if (h_tot.flags & kFilterFlagBadRef) { // the caller knows where the record came from: it writes the message
+        out->bad_ref_record = h_tot.bad_record;
+        return OEM_OK;
     }
-    if (timing) OEM_HIP(hipEventRecord(ev[2].e, st));
-    OEM_HIP(hipStreamSynchronize(st));
-    if (timing) {
-        OEM_HIP(hipEventElapsedTime(&g_filter_ms[2], ev[0].e, ev[1].e));
-        OEM_HIP(hipEventElapsedTime(&g_filter_ms[3], ev[1].e, ev[2].e));
+    if (h_tot.flags & kFilterFlagBigScore) {
+        out->host_rerun = true;
+        return OEM_OK;
     }
-    return OEM_OK; // (the records, offsets and scan results are released here)
+    return filter_scans_emit(who, F, n_txps, tab, d_records, d_group_off, n_groups, 0, want_coords, true, out, cells, d_cell_group_off,
+                             d_ccnt.p, d_best.p, h_tot, timing);
 }
 
 int filter_prepare_batch(const char *who, const oem_filters &F, const oem_aln_record *records, const uint64_t *group_off,

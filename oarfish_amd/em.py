@@ -342,8 +342,58 @@ def collate_names(names, cell_rec_off, secondary=None, mode: str = "sort", devic
     return order[:n], group_off[:int(n_groups.value) + 1].copy(), cell_group_off
 
 
+def _coverage_args(coverage):
+    """(model, bin_width, growth_rate) of a ``coverage`` dict as the records calls take it; None = no model."""
+    if coverage is None:
+        return -1, 0, 0.0
+    name = coverage.get("model", "binomial")
+    if name not in _COVERAGE_MODELS:
+        raise ValueError(f"model must be one of {sorted(_COVERAGE_MODELS)}, not {name!r}")
+    return _COVERAGE_MODELS[name], coverage.get("bin_width", 100), coverage.get("growth_rate", 2.0)
+
+
+def _em_cells_records_names(F, txp_len, records, cell_rec_off, coverage, max_iter, conv_thresh, device, names, secondary, mode):
+    """``em_cells_records_sparse(..., names=, collate="device")``: the one call."""
+    from .types import pack_read_names
+    records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
+    n = len(records)
+    cell_rec_off = np.ascontiguousarray(cell_rec_off, dtype=np.uint64)
+    if cell_rec_off.ndim != 1 or len(cell_rec_off) < 1:
+        raise ValueError("cell_rec_off needs n_cells + 1 entries")
+    n_names = len(names[1]) - 1 if isinstance(names, tuple) and len(names) == 2 and not isinstance(names[1], (str, bytes)) else len(names)
+    if n_names != n:
+        raise ValueError("names must have one entry per record")
+    blob, off = pack_read_names(names, n)
+    sec = None
+    if secondary is not None:
+        sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
+        if len(sec) != n:
+            raise ValueError("secondary must have one entry per record")
+    if n and not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)   # (every name is empty: the call says so)
+    n_cells = len(cell_rec_off) - 1
+    model, bin_width, growth_rate = _coverage_args(coverage)
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    kept = np.zeros(max(n, 1), dtype=np.uint32)
+    n_groups = C.c_uint64(0)
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_em_run_cells_records_names_sparse(
+        C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
+        blob.ctypes.data if n else None, off.ctypes.data, None if sec is None or not n else sec.ctypes.data,
+        cell_rec_off.ctypes.data, n_cells, _COLLATE_MODES[mode], bin_width, model, growth_rate, device, max_iter, conv_thresh,
+        order.ctypes.data, None, C.byref(n_groups), None, kept.ctypes.data, C.byref(res)))
+    try:
+        tables = _discard_tables(L, res, n_cells)
+    except BaseException:
+        L.oem_cells_result_destroy(res)
+        raise
+    return (*_take_cells_result(res, n_cells, L), kept[:int(n_groups.value)].copy(), tables, order[:n])
+
+
 def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
-                            conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None):
+                            conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None, collate: str = "host",
+                            mode: str = "sort"):
     """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
     oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
     model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
@@ -357,31 +407,36 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     ``names`` (with ``secondary``, as ``collate_names`` takes them): the records are collated by barcode only.
     ``group_off`` is then ignored and ``cell_group_off`` is read as ``cell_rec_off``; the call collates the records on
     the device, runs on ``records[order]`` and appends ``order`` to what it returns (``kept`` counts the groups of the
-    collated order).
+    collated order).  ``collate="host"`` joins the two device calls here: ``collate_names``, ``records[order]`` with
+    NumPy, then the records call.  ``collate="device"`` is one call (oem_em_run_cells_records_names_sparse): names and
+    records go up in input order and the order is applied on the device; same seven values.  ``mode`` is
+    ``collate_names``': ``"adjacent"`` for input that is name-collated already.
     """
     from .builder import check_batch, filters_c
+    if collate not in ("host", "device"):
+        raise ValueError(f"collate must be 'host' or 'device', not {collate!r}")
+    if mode not in _COLLATE_MODES:
+        raise ValueError(f"mode must be one of {sorted(_COLLATE_MODES)}, not {mode!r}")
+    if names is None and secondary is not None:
+        raise ValueError("secondary goes with names")
     F = filters_c(filters)
     txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+    if names is not None and collate == "device":
+        return _em_cells_records_names(F, txp_len, records, cell_group_off, coverage, max_iter, conv_thresh, device, names,
+                                       secondary, mode)
     order = None
     if names is not None:
-        order, group_off, cell_group_off = collate_names(names, cell_group_off, secondary, device=device)
+        order, group_off, cell_group_off = collate_names(names, cell_group_off, secondary, mode=mode, device=device)
         records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
         if len(records) != len(order):
             raise ValueError("names must have one entry per record")
         records = records[order]
-    elif secondary is not None:
-        raise ValueError("secondary goes with names")
     records, group_off = check_batch(records, group_off)
     cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
     if cell_group_off.ndim != 1 or len(cell_group_off) < 1:
         raise ValueError("cell_group_off needs n_cells + 1 entries")
     n_groups, n_cells = len(group_off) - 1, len(cell_group_off) - 1
-    model, bin_width, growth_rate = -1, 0, 0.0
-    if coverage is not None:
-        name = coverage.get("model", "binomial")
-        if name not in _COVERAGE_MODELS:
-            raise ValueError(f"model must be one of {sorted(_COVERAGE_MODELS)}, not {name!r}")
-        model, bin_width, growth_rate = _COVERAGE_MODELS[name], coverage.get("bin_width", 100), coverage.get("growth_rate", 2.0)
+    model, bin_width, growth_rate = _coverage_args(coverage)
     kept = np.zeros(n_groups, dtype=np.uint32)
     L = _lib.lib()
     res = C.c_void_p()

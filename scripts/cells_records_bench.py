@@ -12,6 +12,17 @@ over 60 k transcripts, synth.make_cells), records from synth.make_cell_records. 
 A warm-up on the first cells, then three repeats of everything, best taken.  One more one-call run goes through the
 test-only library under OEM_FILTER_TIMING=1 with one worker: HIP-event times of the filter stages of its last group.
 The result goes to --out as JSON (rewritten after every measurement).
+
+--names is a leg of its own (profiles/cells_records_names_bench.json): the same slice as a barcode-collated input holds
+it (synth.shuffle_cell_records: every cell's records permuted, each with its read's name), per name style:
+
+  (a) the one call from names and records in input order (oem_em_run_cells_records_names_sparse,
+      em_cells_records_sparse(..., names=, collate="device"));
+  (b) the path it replaces, by stage: collate_names, the NumPy gather records[order], em_cells_records_sparse;
+  (c) em_cells_records_sparse on records that are sorted already: the floor of the filter and EM part.
+
+A warm-up on the first cells, then --runs repeats (default five for this leg) of (a), (b), (c) in turn; best and
+spread, (a)/(b), (a) - (c), and the peak of the device memory in use during (a), sampled from another thread.
 """
 import argparse
 import ctypes as C
@@ -50,16 +61,121 @@ def pinned_rate_gbs(n_bytes=1 << 30, repeats=3):
     return best
 
 
+class PeakDeviceMemory:
+    """Samples the device memory in use (hipMemGetInfo through torch) from another thread: the peak above the level at
+    entry, in bytes.  The sampling period bounds what it can miss."""
+
+    def __init__(self, period_s=0.002):
+        import threading
+        import torch
+        self._torch, self._period, self._stop = torch, period_s, threading.Event()
+        self._thread = threading.Thread(target=self._run, daemon=True)
+        self.peak = 0
+
+    def _used(self):
+        free, total = self._torch.cuda.mem_get_info()
+        return total - free
+
+    def _run(self):
+        while not self._stop.is_set():
+            self.peak = max(self.peak, self._used() - self._base)
+            time.sleep(self._period)
+
+    def __enter__(self):
+        self._base = self._used()
+        self._thread.start()
+        return self
+
+    def __exit__(self, *exc):
+        self._stop.set()
+        self._thread.join()
+
+
+def spread(ts):
+    return dict(runs_s=[round(t, 4) for t in ts], best_s=round(min(ts), 4), worst_s=round(max(ts), 4))
+
+
+def names_leg(args, cr, res, save):
+    """The --names leg (see the module docstring); fills res[style] for every name style."""
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    for style in args.styles:
+        t0 = time.perf_counter()
+        rec, (blob, off), sec, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        print(f"[bench] {style}: shuffled and named in {time.perf_counter() - t0:.1f} s ({blob.nbytes / 1e9:.2f} GB of names)", flush=True)
+        r = res[style] = dict(name_bytes=int(blob.nbytes), record_bytes=int(rec.nbytes))
+
+        def one_call(nc=n):
+            m = int(cro[nc])
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:m], None, cro[:nc + 1], names=(blob[:int(off[m])], off[:m + 1]),
+                                                       secondary=sec[:m], collate="device")
+
+        def two_step(nc=n):
+            m = int(cro[nc])
+            t_c, (order, goff, cgo) = clock(lambda: oarfish_amd.collate_names((blob[:int(off[m])], off[:m + 1]), cro[:nc + 1], sec[:m]))
+            t_g, sorted_rec = clock(lambda: rec[:m][order])
+            t_e, got = clock(lambda: oarfish_amd.em_cells_records_sparse(f, tl, sorted_rec, goff, cgo))
+            return (t_c, t_g, t_e), got, (sorted_rec, goff, cgo, order)
+
+        nw = min(args.warm_cells, n)
+        one_call(nw)
+        two_step(nw)
+        runs_a, runs_b, runs_c, stages = [], [], [], []
+        keep = None
+        for k in range(args.runs):
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_a = clock(one_call)
+                r["peak_device_bytes_during_the_call"] = int(pk.peak)
+            else:
+                dt, got_a = clock(one_call)
+            runs_a.append(dt)
+            st, got_b, keep = two_step()
+            runs_b.append(sum(st))
+            stages.append(st)
+            runs_c.append(clock(lambda: oarfish_amd.em_cells_records_sparse(f, tl, keep[0], keep[1], keep[2]))[0])
+            if k == 0:   # the two paths agree: the exact outputs exactly, the values within an f32 ulp
+                assert np.array_equal(got_a[6], keep[3]) and np.array_equal(got_a[4], got_b[4]) and got_a[5] == got_b[5]
+                assert np.array_equal(got_a[0], got_b[0]) and np.array_equal(got_a[1], got_b[1])
+                ulps = np.abs(got_a[2].view(np.int32).astype(np.int64) - got_b[2].view(np.int32).astype(np.int64))
+                r["max_f32_ulps_one_call_to_two_step"] = int(ulps.max(initial=0))
+                r["n_groups"] = int(len(keep[1]) - 1)
+            del got_a, got_b
+            print(f"[bench] {style} run {k}: (a) {runs_a[-1]:.3f} s, (b) {runs_b[-1]:.3f} s = collate {st[0]:.3f} + gather {st[1]:.3f} "
+                  f"+ records call {st[2]:.3f}, (c) {runs_c[-1]:.3f} s", flush=True)
+            r["one_call"], r["two_step"], r["sorted_records_call"] = spread(runs_a), spread(runs_b), spread(runs_c)
+            best = min(range(len(runs_b)), key=lambda i: runs_b[i])
+            r["two_step_stages_of_best_run_s"] = dict(collate_names=round(stages[best][0], 4), numpy_gather=round(stages[best][1], 4),
+                                                      em_cells_records_sparse=round(stages[best][2], 4))
+            r["numpy_gather"] = spread([s[1] for s in stages])
+            r["one_call_over_two_step"] = round(min(runs_a) / min(runs_b), 3)
+            r["one_call_minus_sorted_records_call_s"] = round(min(runs_a) - min(runs_c), 4)
+            save()
+        del rec, blob, off, sec, keep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=625)
     ap.add_argument("--cell-reads", type=int, default=50_000)
     ap.add_argument("--txps", type=int, default=60_000)
     ap.add_argument("--warm-cells", type=int, default=20)
-    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=None, help="repeats per point (3; 5 with --names)")
     ap.add_argument("--models", type=int, nargs="*", default=[-1, 1])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cells_records_bench.json"))
+    ap.add_argument("--names", action="store_true", help="the leg from names and records in input order")
+    ap.add_argument("--styles", nargs="*", default=["uuid", "illumina"])
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.runs is None:
+        args.runs = 5 if args.names else 3
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
     T, n = args.txps, args.cells
     t0 = time.perf_counter()
     cells = synth.make_cells(n, args.cell_reads, T, threads=16)
@@ -121,6 +237,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.names:
+        names_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     rate = pinned_rate_gbs()
     res["pinned_h2d_gbs"] = rate
     res["records_pcie_floor_s"] = rec.nbytes / (rate * 1e9)
