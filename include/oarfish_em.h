@@ -50,7 +50,8 @@ extern "C" {
  *    oem_store_create_projected_records), the `.quant` and `.ambig_info.tsv` files of the bulk path as text formatted on
  *    the device (oem_quant_text, oem_ambig_text), a cell's records collated by read name on the device
  *    (oem_collate_names), the bulk records session (oem_records_stream_*), the collation and the records call in one
- *    (oem_em_run_cells_records_names_sparse). */
+ *    (oem_em_run_cells_records_names_sparse), cells found from barcodes in any record order (oem_collate_barcodes,
+ *    oem_em_run_cells_records_barcodes_sparse). */
 #define OEM_ABI_VERSION 2
 
 typedef enum {
@@ -727,6 +728,71 @@ int oem_em_run_cells_records_names_sparse(
     uint32_t *out_order /* n_records, or NULL */, uint64_t *out_group_off /* n_records + 1, or NULL */,
     uint64_t *out_n_groups /* or NULL */, uint64_t *out_cell_group_off /* n_cells + 1, or NULL */,
     uint32_t *out_kept /* capacity n_records, *out_n_groups entries written; or NULL */,
+    oem_cells_result **out);
+
+/* Finds the CELLS of alignment records that are in any order, on the device.  The reference takes input in which all
+ * records of a barcode are adjacent (single_cell.rs:196-213, alignment_parser.rs:244-299; docs/index.md: "all records of
+ * a barcode must be adjacent"), which means a sort of the whole file by the CB tag before it starts.  This call lifts
+ * that: it returns the permutation that collates the records by barcode and the cells' offsets in it, the
+ * `cell_rec_off` oem_collate_names and oem_em_run_cells_records_names_sparse take.
+ *
+ * barcodes / barcode_off: the n_records barcodes as one blob, record i's bytes at [barcode_off[i], barcode_off[i + 1]);
+ * barcode_off starts at 0.  Barcodes may differ in length.
+ *
+ * A cell is the set of records with one barcode, compared as bytes.  Cells are numbered in the order of their first
+ * record in the input, so input that is barcode-collated already gives its cells in its own order.  Inside a cell the
+ * records keep their input order.  out_order (n_records) is that cell-major permutation: out_order[k] is the input
+ * index of the record at position k.  out_cell_rec_off (capacity n_records + 1; *out_n_cells + 1 entries are written)
+ * holds every cell's first position and then n_records; *out_n_cells is the number of distinct barcodes.
+ *
+ * OEM_ERR_ARG before any device use: barcode_off or an output NULL, barcodes NULL with n_records > 0, offsets not from 0
+ * or decreasing, n_records > 2^32 - 1 (and, in this version, n_records > 2^31 - 2: the barcodes are sorted as one batch
+ * of oem_collate_names' sort).  OEM_ERR_ARG found on the device, naming the first such record: an empty barcode (the
+ * reference bails when CB is missing, single_cell.rs:203, alignment_parser.rs:150) and a barcode that contains a 0
+ * byte.  The outputs are then unspecified.  Without a device: OEM_ERR_NO_DEVICE.  The rule is
+ * oarfish_amd/csrc/oem_collate.h. */
+int oem_collate_barcodes(const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, int device,
+                         uint32_t *out_order            /* n_records */,
+                         uint64_t *out_cell_rec_off     /* capacity n_records + 1; *out_n_cells + 1 written */,
+                         uint64_t *out_n_cells);
+
+/* single_cell.rs:104-188 from records in ANY order, in one call: oem_collate_barcodes and
+ * oem_em_run_cells_records_names_sparse joined on the device.  records (n_records), barcodes / barcode_off, names /
+ * name_off and secondary are in the caller's input order, one entry per record; nothing needs to be collated.  mode is
+ * applied inside each cell, after the barcode collation.
+ *
+ * The result is what the caller gets by joining four steps: oem_collate_barcodes (order_bc, cell_rec_off); records,
+ * names and secondary put into order_bc order on the host; oem_em_run_cells_records_names_sparse with that cell_rec_off
+ * (order_names, ...); the two orders composed.  out_order[k] = order_bc[order_names[k]] is the caller's input index of
+ * the record at position k of the final collated order.  Exactly equal to that join: out_order (n_records),
+ * out_cell_rec_off (capacity n_records + 1) and *out_n_cells, out_group_off (capacity n_records + 1) and *out_n_groups,
+ * out_cell_group_off (capacity n_records + 1; *out_n_cells + 1 written), out_kept (capacity n_records; *out_n_groups
+ * written), every table of oem_cells_result_discard_tables and the entries' columns.  Each of the seven outputs may be
+ * NULL.  The entries' values and the infos are equal as oem_em_run_cells_records_sparse states it: up to
+ * floating-point summation order.
+ *
+ * The whole input is resident on the device during the call: 40 bytes a record, the names and their offsets, the
+ * barcode order and one more offset a record; the barcode sort's buffers are released before the records go up, a
+ * group's while it is collated.  Running out of device memory is OEM_ERR_OOM with everything released.
+ *
+ * Errors are those of the three calls.  Before any device use: theirs on filters, txp_len, n_txps, model, bin_width,
+ * barcodes, barcode_off, names, name_off, n_records, mode; records NULL with n_records > 0.  Found on the device, all
+ * OEM_ERR_ARG: an empty barcode or one with a 0 byte, naming the first such record; an empty name or one with a 0 byte,
+ * naming the first such record of the input; a mapped record whose ref_id is not below n_txps, naming the cell and the
+ * record's index in the caller's input order.  Limits: those of oem_collate_barcodes; a cell at most 2^31 - 2 records.
+ * Without a device: OEM_ERR_NO_DEVICE.  *out = NULL on any failure. */
+int oem_em_run_cells_records_barcodes_sparse(
+    const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+    const oem_aln_record *records, uint64_t n_records,
+    const uint8_t *barcodes, const uint64_t *barcode_off,
+    const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+    uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT: applied inside each cell, after the barcode collation */,
+    uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+    uint32_t *out_order /* n_records, or NULL */,
+    uint64_t *out_cell_rec_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_cells /* or NULL */,
+    uint64_t *out_group_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_groups /* or NULL */,
+    uint64_t *out_cell_group_off /* capacity n_records + 1, or NULL */,
+    uint32_t *out_kept /* capacity n_records, or NULL */,
     oem_cells_result **out);
 
 /* A per-cell SESSION: the caller pushes cells one by one, from any number of threads, as they become available

@@ -73,7 +73,7 @@ ABI_SYMBOLS = [
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
     "oem_cells_result_destroy", "oem_em_run_cells_coverage_sparse",
     "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables", "oem_collate_names",
-    "oem_em_run_cells_records_names_sparse",
+    "oem_em_run_cells_records_names_sparse", "oem_collate_barcodes", "oem_em_run_cells_records_barcodes_sparse",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
@@ -236,6 +236,10 @@ def _load(path: str) -> C.CDLL:
     L.oem_collate_names.argtypes = [vp, vp, vp, u64, vp, u32, u32, i32, vp, vp, C.POINTER(u64), vp]
     L.oem_em_run_cells_records_names_sparse.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, u32, u32, u32, i32, f64, i32,
                                                         u32, f64, vp, vp, C.POINTER(u64), vp, vp, C.POINTER(vp)]
+    L.oem_collate_barcodes.argtypes = [vp, vp, u64, i32, vp, vp, C.POINTER(u64)]
+    L.oem_em_run_cells_records_barcodes_sparse.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, u32, u32, i32, f64, i32,
+                                                           u32, f64, vp, vp, C.POINTER(u64), vp, C.POINTER(u64), vp, vp,
+                                                           C.POINTER(vp)]
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
     L.oem_cells_stream_push_records.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
@@ -301,6 +305,9 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_quant_last_call.argtypes = [vp]
         L.oem_debug_collate_last_call.argtypes = [vp]
         L.oem_test_collate_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, C.POINTER(u64), vp]
+        L.oem_debug_collate_barcodes_last_call.argtypes = [vp]
+        L.oem_debug_cells_barcodes_last_call.argtypes = [vp]
+        L.oem_test_collate_barcodes_host.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.oem_debug_records_stream_finish_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -109,6 +109,7 @@ TESTING_HOOKS = ["oem_debug_layout_hash", "oem_debug_local_comm_create", "oem_te
                  "oem_debug_text_lz4_last_timing", "oem_test_lz4_frame", "oem_debug_filter_last_timing", "oem_debug_mtx_last_timing",
                  "oem_debug_proj_last_pass", "oem_debug_cells_records_last_csr", "oem_debug_quant_last_call",
                  "oem_test_shortest_f64", "oem_debug_collate_last_call", "oem_test_collate_host",
+                 "oem_debug_collate_barcodes_last_call", "oem_debug_cells_barcodes_last_call", "oem_test_collate_barcodes_host",
                  "oem_debug_records_stream_finish_csr", "oem_debug_records_stream_last_join"]
 
 

@@ -30,7 +30,18 @@
 //               one scalar (n_groups) and the n_cells + 1 cell offsets are what the host sees
 // and the group goes on as above.  The host loop, when the group takes it, gets order and group_off down and gathers
 // the group's records on the host.
+//
+// oem_em_run_cells_records_barcodes_sparse takes records that are not collated at all (oem_collate.h's barcode rule; the
+// reference requires a barcode's records to be adjacent, single_cell.rs:196-213).  Once per call: collate_barcodes_resident
+// leaves order_bc and cell_rec_off on the device; names (validated behind their upload chunks, so a bad name is named
+// by its input index), flags and records go up once, in input order, and stay; one scan of the name lengths in order_bc
+// order gives every record's place in its group's gathered blob.  Then the groups of cells, as above, except that
+//   collate     k_names_gather / k_flags_gather put the group's names and flags into a dense blob in order_bc order, and
+//               collate_resident runs in its device form (no lanes, no validate pass) with positions for record indices
+//   compose     k_order_compose: order[k] = order_bc[r0 + order[k]], the record's index in the caller's input
+//   gather      k_records_gather straight from the whole-input buffer, under either mode (order_bc is no identity)
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -219,6 +230,21 @@ static_assert(sizeof(oem_aln_record) == 8 * kRecordWords && alignof(oem_aln_reco
 // destination is word j % 5 of record j / 5.  The stores are lane i at base + 8 i, fully coalesced; the loads are runs of
 // five lanes on 40 contiguous bytes, scattered at that granularity, which is all the source allows.  (One lane per
 // record would make both sides 8 bytes at a stride of 40.)
+// order[k] = order_bc[order[k]]: a group's collated positions become the records' indices in the caller's input
+__global__ __launch_bounds__(kGT) void k_order_compose(uint64_t m, const uint32_t *__restrict__ order_bc, uint32_t *__restrict__ order)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kGT + threadIdx.x;
+    if (k < m) order[k] = order_bc[order[k]];
+}
+
+// dst[c] = src[at[c]]: the gathered name offsets at the cells' first records
+__global__ __launch_bounds__(kGT) void k_sample_offsets(uint64_t n, const uint64_t *__restrict__ at, const uint64_t *__restrict__ src,
+                                                         uint64_t *__restrict__ dst)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * kGT + threadIdx.x;
+    if (c < n) dst[c] = src[at[c]];
+}
+
 __global__ __launch_bounds__(kGT) void k_records_gather(uint64_t n_words, const uint32_t *__restrict__ order, uint32_t order_base,
                                                          const uint64_t *__restrict__ src, uint64_t *__restrict__ dst)
 {
@@ -231,8 +257,18 @@ __global__ __launch_bounds__(kGT) void k_records_gather(uint64_t n_words, const 
 // What a call of the names form shares between its groups, and where a group leaves what the caller asked for: the
 // groups' numbers in the call are known only when every group before has been collated, so kept and group_off wait in
 // the group's slot until the workers have joined.
+// The whole input of the barcodes form on the device, in the caller's order, and the barcode collation's result.
+struct ResidentInput {
+    const oem_aln_record *records = nullptr;
+    const uint8_t *names = nullptr, *sec = nullptr; // sec: NULL without flags
+    const uint64_t *name_off = nullptr;             // n_records + 1
+    const uint32_t *order_bc = nullptr;             // n_records
+    const uint64_t *gathered_off = nullptr;         // n_records + 1: the names' offsets in order_bc order
+    const uint64_t *cell_name_off = nullptr;        // HOST, n_cells + 1: gathered_off at the cells' first records
+};
 struct NamesCall {
     CollateInput in;
+    const ResidentInput *dev = nullptr;             // the barcodes form; in.cell_rec_off is then the barcode collation's
     const oem_aln_record *records = nullptr;
     uint32_t *out_order = nullptr;
     bool want_group_off = false, want_kept = false;
@@ -278,7 +314,27 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
 
     CollateResident cr;
     double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    OEM_TRY(collate_resident(nc.in, c0, c1, r0, 0, 0, info, &cr));
+    if (nc.dev) { // the group's names and flags out of the resident input, in order_bc order; positions, then input indices
+        const ResidentInput &dv = *nc.dev;
+        const uint64_t b0 = dv.cell_name_off[c0], nb = dv.cell_name_off[c1] - b0;
+        DevBuf<uint8_t> d_gnames, d_gsec;
+        OEM_TRY(dev_alloc(&d_gnames.p, nb + 16, nullptr));
+        if (dv.sec) OEM_TRY(dev_alloc(&d_gsec.p, ((m + 8) / 8) * 8, nullptr));
+        OEM_TRY(gather_names(dv.order_bc + r0, m, dv.names, dv.name_off, dv.gathered_off + r0, b0, nb, d_gnames.p, dv.sec, d_gsec.p));
+        tm.lap("barcodes: names gather");
+        CollateInput in = nc.in;
+        in.d_names = d_gnames.p;
+        in.d_name_off = dv.gathered_off + r0;
+        in.d_off_base = b0;
+        in.d_n_bytes = nb;
+        in.d_secondary = d_gsec.p;
+        OEM_TRY(collate_resident(in, c0, c1, 0, 0, 0, info, &cr));
+        hipLaunchKernelGGL(k_order_compose, dim3((uint32_t)((m + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, m, dv.order_bc + r0, cr.order.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipStreamSynchronize(nullptr));
+    } else {
+        OEM_TRY(collate_resident(nc.in, c0, c1, r0, 0, 0, info, &cr));
+    }
     tm.lap("names: collate");
     const uint64_t ng = cr.n_groups;
     slot->n_groups = ng;
@@ -298,14 +354,17 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
     bool host = rf.host_only;
     if (!host) {
         DevBuf<oem_aln_record> d_in, d_sorted;
-        OEM_TRY(dev_alloc(&d_in.p, m, nullptr));
-        OEM_TRY(upload_records(nc.records + r0, m, d_in.p));
+        if (!nc.dev) {
+            OEM_TRY(dev_alloc(&d_in.p, m, nullptr));
+            OEM_TRY(upload_records(nc.records + r0, m, d_in.p));
+        }
         const oem_aln_record *d_recs = d_in.p;
-        if (sorting) { // (the adjacent cut's order is the identity)
+        if (sorting || nc.dev) { // (the adjacent cut's order is the identity; with barcodes it is order_bc's slice)
             OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
             const uint64_t n_words = m * kRecordWords;
             hipLaunchKernelGGL(k_records_gather, dim3((uint32_t)((n_words + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, n_words,
-                               (const uint32_t *)cr.order.p, (uint32_t)r0, (const uint64_t *)d_in.p, (uint64_t *)d_sorted.p);
+                               (const uint32_t *)cr.order.p, (uint32_t)(nc.dev ? 0 : r0),
+                               (const uint64_t *)(nc.dev ? nc.dev->records : d_in.p), (uint64_t *)d_sorted.p);
             OEM_HIP(hipGetLastError());
             OEM_HIP(hipStreamSynchronize(nullptr));
             d_in.reset(); // the group holds its records twice only for the length of the gather
@@ -319,8 +378,8 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
         if (r.bad_ref_record != kNoRecord) { // a collated index: the caller knows its records by their input index
             uint32_t at = 0;
             OEM_HIP(hipMemcpy(&at, cr.order.p + r.bad_ref_record, sizeof at, hipMemcpyDeviceToHost));
-            const uint64_t *cro = nc.in.cell_rec_off;
-            const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, (uint64_t)at) - cro) - 1;
+            const uint64_t *cro = nc.in.cell_rec_off; // (a record's cell from its collated position: the sort stays inside cells)
+            const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, r0 + (uint64_t)r.bad_ref_record) - cro) - 1;
             return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)c,
                         (unsigned long long)at, nc.records[at].ref_id);
         }
@@ -336,7 +395,7 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
         for (uint64_t k = 0; k < m; ++k) {
             sorted[k] = nc.records[order[k]];
             if (!(sorted[k].flags & OEM_REC_UNMAPPED) && sorted[k].ref_id >= run.n_txps) {
-                const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, (uint64_t)order[k]) - cro) - 1;
+                const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, r0 + k) - cro) - 1;
                 return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)c,
                             (unsigned long long)order[k], sorted[k].ref_id);
             }
@@ -354,7 +413,53 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
     return rc;
 }
 
+// The groups' numbers in the call, once every group's count is known: the slots into the caller's arrays (each or NULL).
+void names_call_outputs(const std::vector<std::pair<uint32_t, uint32_t>> &groups, const std::vector<NamesSlot> &slots,
+                        const uint64_t *cell_rec_off, uint64_t n_records, uint64_t *out_group_off, uint64_t *out_n_groups,
+                        uint64_t *out_cell_group_off, uint32_t *out_kept)
+{
+    uint64_t group_base = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const uint32_t c0 = groups[g].first, c1 = groups[g].second;
+        const NamesSlot &sl = slots[g];
+        if (out_cell_group_off)
+            for (uint32_t c = c0; c <= c1; ++c) out_cell_group_off[c] = group_base + sl.cell_group_off[c - c0];
+        if (out_group_off)
+            for (uint64_t k = 0; k < sl.n_groups; ++k) out_group_off[group_base + k] = cell_rec_off[c0] + sl.group_off[k];
+        if (out_kept && sl.n_groups) std::memcpy(out_kept + group_base, sl.kept.data(), sizeof(uint32_t) * sl.n_groups);
+        group_base += sl.n_groups;
+    }
+    if (out_cell_group_off && groups.empty()) out_cell_group_off[0] = 0;
+    if (out_group_off) out_group_off[group_base] = n_records;
+    if (out_n_groups) *out_n_groups = group_base;
+}
+
+// The cut of the records call (a group's records bound its reads and alignments), and then what the collation adds: a
+// group is one collation batch, so it also stays within a batch's records and within the name bytes of a group.
+// name_byte_off (n_cells + 1): the cells' first name bytes.
+template <typename NameBytes>
+std::vector<std::pair<uint32_t, uint32_t>> cut_names_groups(const uint64_t *cell_rec_off, uint32_t n_cells, uint32_t n_txps, NameBytes &&cell_bytes)
+{
+    std::vector<std::pair<uint32_t, uint32_t>> groups;
+    const uint64_t max_records = collate_batch_records(), max_bytes = (uint64_t)knob("OEM_CELLS_GROUP_NAME_BYTES", (long)kGroupNameBytes);
+    for (const auto &g : cut_cells_groups(cell_rec_off, n_cells, nullptr, n_txps)) {
+        uint32_t c0 = g.first;
+        while (c0 < g.second) {
+            uint32_t c1 = c0 + 1;
+            while (c1 < g.second && cell_rec_off[c1 + 1] - cell_rec_off[c0] <= max_records && cell_bytes(c1 + 1) - cell_bytes(c0) <= max_bytes)
+                ++c1;
+            groups.emplace_back(c0, c1);
+            c0 = c1;
+        }
+    }
+    return groups;
+}
+
+thread_local double g_cells_barcodes_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
 } // namespace
+
+void cells_barcodes_last_call(double *out8) { std::memcpy(out8, g_cells_barcodes_last, sizeof g_cells_barcodes_last); }
 
 int records_filter_setup(const char *who, const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps, RecordsFilter *rf)
 {
@@ -538,23 +643,8 @@ extern "C" int oem_em_run_cells_records_names_sparse(const oem_filters *filters,
     r->from_records = true;
     r->discard.assign(n_cells, oem_discard_table{});
 
-    // The cut of the records call (a group's records bound its reads and alignments), and then what the collation adds:
-    // a group is one collation batch, so it also stays within a batch's records and within the name bytes of a group.
-    std::vector<std::pair<uint32_t, uint32_t>> groups;
-    {
-        const uint64_t max_records = collate_batch_records(), max_bytes = (uint64_t)knob("OEM_CELLS_GROUP_NAME_BYTES", (long)kGroupNameBytes);
-        for (const auto &g : cut_cells_groups(cell_rec_off, n_cells, nullptr, n_txps)) {
-            uint32_t c0 = g.first;
-            while (c0 < g.second) {
-                uint32_t c1 = c0 + 1;
-                while (c1 < g.second && cell_rec_off[c1 + 1] - cell_rec_off[c0] <= max_records &&
-                       name_off[cell_rec_off[c1 + 1]] - name_off[cell_rec_off[c0]] <= max_bytes)
-                    ++c1;
-                groups.emplace_back(c0, c1);
-                c0 = c1;
-            }
-        }
-    }
+    const std::vector<std::pair<uint32_t, uint32_t>> groups =
+        cut_names_groups(cell_rec_off, n_cells, n_txps, [&](uint32_t c) { return name_off[cell_rec_off[c]]; });
     NamesCall nc;
     nc.in.who = who;
     nc.in.names = names;
@@ -581,25 +671,181 @@ extern "C" int oem_em_run_cells_records_names_sparse(const oem_filters *filters,
         path->batched = batched ? 1u : 0u;
         return rc;
     }));
-    // the groups' numbers in the call, now that every group's count is known
-    uint64_t group_base = 0;
-    for (size_t g = 0; g < groups.size(); ++g) {
-        const uint32_t c0 = groups[g].first, c1 = groups[g].second;
-        const NamesSlot &sl = slots[g];
-        if (out_cell_group_off)
-            for (uint32_t c = c0; c <= c1; ++c) out_cell_group_off[c] = group_base + sl.cell_group_off[c - c0];
-        if (out_group_off)
-            for (uint64_t k = 0; k < sl.n_groups; ++k) out_group_off[group_base + k] = cell_rec_off[c0] + sl.group_off[k];
-        if (out_kept && sl.n_groups) std::memcpy(out_kept + group_base, sl.kept.data(), sizeof(uint32_t) * sl.n_groups);
-        group_base += sl.n_groups;
-    }
-    if (out_cell_group_off && groups.empty()) out_cell_group_off[0] = 0;
-    if (out_group_off) out_group_off[group_base] = n_records;
-    if (out_n_groups) *out_n_groups = group_base;
+    names_call_outputs(groups, slots, cell_rec_off, n_records, out_group_off, out_n_groups, out_cell_group_off, out_kept);
     OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
     *out = r.release();
     return OEM_OK;
     OEM_API_END("oem_em_run_cells_records_names_sparse")
+}
+
+extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                                        const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
+                                                        const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off,
+                                                        const uint8_t *secondary, uint32_t mode, uint32_t bin_width, int model,
+                                                        double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+                                                        uint32_t *out_order, uint64_t *out_cell_rec_off, uint64_t *out_n_cells,
+                                                        uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off,
+                                                        uint32_t *out_kept, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_em_run_cells_records_barcodes_sparse";
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (out_n_groups) *out_n_groups = 0;
+    if (out_n_cells) *out_n_cells = 0;
+    // the checks of oem_store_create_records, of oem_collate_barcodes, of oem_collate_names and of the cells calls, before
+    // any device use
+    OEM_TRY(check_store_from_records(who, filters, txp_len, n_txps, bin_width, model, nullptr));
+    if (!barcode_off || !name_off) return fail(OEM_ERR_ARG, "%s: barcode_off or name_off is NULL", who);
+    OEM_TRY(check_barcode_input(who, barcodes, barcode_off, n_records));
+    const uint64_t n = n_records, one_cell[2] = {0, n};
+    OEM_TRY(check_collate_input(who, names, name_off, n, one_cell, 1, mode));
+    if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+    if (model >= 0) OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, 0, 0));
+    OEM_TRY(ensure_device(device));
+    RecordsFilter rf;
+    OEM_TRY(records_filter_setup(who, filters, txp_len, n_txps, &rf));
+
+    CellsCoverage cc;
+    CellsRun run{n_txps, device, max_iter, conv_thresh};
+    if (model >= 0) {
+        cc.txp_len = rf.txp_len.data();
+        cc.n_txps = n_txps;
+        cc.bin_width = bin_width;
+        cc.model = model;
+        cc.growth_rate = growth_rate;
+        OEM_TRY(cells_coverage_setup(&cc));
+        run.cov = &cc;
+    }
+    const bool timing = knob("OEM_COLLATE_TIMING", 0) != 0;
+    double last[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bc_info[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bc_cells_ms = 0;
+    std::memset(g_cells_barcodes_last, 0, sizeof g_cells_barcodes_last);
+
+    // the cells: order_bc and cell_rec_off stay on the device, the offsets come down for the cut
+    BarcodeCells bc;
+    std::vector<uint64_t> cro(1, 0), cell_name_off(1, 0);
+    auto t0 = clk::now();
+    if (n) {
+        OEM_TRY(collate_barcodes_resident(who, barcodes, barcode_off, n, timing, bc_info, &bc_cells_ms, &bc));
+        cro.resize(bc.n_cells + 1);
+        OEM_HIP(hipMemcpy(cro.data(), bc.cell_rec_off.p, sizeof(uint64_t) * (bc.n_cells + 1), hipMemcpyDeviceToHost));
+    }
+    bc_info[2] = bc_cells_ms;
+    collate_barcodes_set_last(bc_info);
+    const uint32_t n_cells = (uint32_t)bc.n_cells;
+    last[0] = (double)n_cells;
+    last[2] = ms_since(t0);
+
+    // the whole input, once and in input order; the names are checked behind their chunks
+    DevBuf<oem_aln_record> d_records;
+    DevBuf<uint8_t> d_names, d_sec;
+    DevBuf<uint64_t> d_name_off, d_gathered_off, d_cell_name_off;
+    t0 = clk::now();
+    if (n) {
+        const uint64_t n_bytes = name_off[n], chunk_bytes = collate_chunk_bytes();
+        DevBuf<unsigned long long> d_bad;
+        OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16, nullptr));
+        OEM_TRY(dev_alloc(&d_name_off.p, n + 1, nullptr));
+        OEM_TRY(dev_alloc(&d_bad.p, 2, nullptr));
+        OEM_TRY(dev_alloc(&d_records.p, n, nullptr));
+        const unsigned long long bad0[2] = {kNoRecord, kNoRecord};
+        OEM_HIP(hipMemcpy(d_bad.p, bad0, sizeof bad0, hipMemcpyHostToDevice));
+        OEM_HIP(hipMemcpy(d_name_off.p, name_off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice));
+        OEM_HIP(hipMemset(d_names.p + n_bytes, 0, 16));
+        std::vector<uint64_t> byte_cut{0}, rec_cut{0};
+        for (uint64_t r = 0; r < n;) {
+            uint64_t r1 = (uint64_t)(std::upper_bound(name_off + r + 1, name_off + n + 1, name_off[r] + chunk_bytes) - name_off) - 1;
+            r1 = std::max(r1, r + 1);
+            byte_cut.push_back(name_off[r1]);
+            rec_cut.push_back(r1);
+            r = r1;
+        }
+        float ms[6] = {0, 0, 0, 0, 0, 0};
+        OEM_TRY(filter_upload_measure<uint8_t>(names, d_names.p, byte_cut.data(), byte_cut.size() - 1, 1, timing ? ms : nullptr,
+                                               [&](hipStream_t lane, uint64_t g0, uint64_t) {
+                                                   launch_collate_validate(lane, d_names.p, byte_cut[g0], byte_cut[g0 + 1], d_name_off.p,
+                                                                           rec_cut[g0], rec_cut[g0 + 1], d_bad.p);
+                                               }));
+        last[6] = ms[0];
+        last[7] = ms[1];
+        unsigned long long bad[2];
+        OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad[0] != kNoRecord || bad[1] != kNoRecord) {
+            if (bad[1] < bad[0]) return fail(OEM_ERR_ARG, "%s: record %llu has an empty name", who, bad[1]);
+            return fail(OEM_ERR_ARG, "%s: the name of record %llu contains a 0 byte", who, bad[0]);
+        }
+        if (secondary && mode == kCollateSort) { // (read through aligned 4-byte words: padded)
+            OEM_TRY(dev_alloc(&d_sec.p, n + 8, nullptr));
+            OEM_HIP(hipMemset(d_sec.p + n, 0, 8));
+            OEM_HIP(hipMemcpy(d_sec.p, secondary, n, hipMemcpyHostToDevice));
+        }
+        OEM_TRY(upload_records(records, n, d_records.p));
+        last[3] = ms_since(t0);
+        t0 = clk::now();
+        OEM_TRY(dev_alloc(&d_gathered_off.p, n + 1, nullptr));
+        OEM_TRY(gather_name_offsets(bc.order.p, n, d_name_off.p, d_gathered_off.p));
+        OEM_TRY(dev_alloc(&d_cell_name_off.p, (size_t)n_cells + 1, nullptr));
+        hipLaunchKernelGGL(k_sample_offsets, dim3((n_cells + 1 + kGT - 1) / kGT), dim3(kGT), 0, nullptr, (uint64_t)n_cells + 1,
+                           (const uint64_t *)bc.cell_rec_off.p, (const uint64_t *)d_gathered_off.p, d_cell_name_off.p);
+        OEM_HIP(hipGetLastError());
+        cell_name_off.resize((size_t)n_cells + 1);
+        OEM_HIP(hipMemcpy(cell_name_off.data(), d_cell_name_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost));
+        d_cell_name_off.reset();
+        last[4] = ms_since(t0);
+    }
+
+    std::unique_ptr<oem_cells_result> r(new oem_cells_result());
+    r->n_cells = n_cells;
+    r->infos.resize(n_cells);
+    r->from_records = true;
+    r->discard.assign(n_cells, oem_discard_table{});
+    const std::vector<std::pair<uint32_t, uint32_t>> groups =
+        cut_names_groups(cro.data(), n_cells, n_txps, [&](uint32_t c) { return cell_name_off[c]; });
+    ResidentInput dv;
+    dv.records = d_records.p;
+    dv.names = d_names.p;
+    dv.sec = d_sec.p;
+    dv.name_off = d_name_off.p;
+    dv.order_bc = bc.order.p;
+    dv.gathered_off = d_gathered_off.p;
+    dv.cell_name_off = cell_name_off.data();
+    NamesCall nc;
+    nc.in.who = who;
+    nc.in.cell_rec_off = cro.data();
+    nc.in.mode = mode;
+    nc.in.chunk_bytes = collate_chunk_bytes();
+    nc.dev = &dv;
+    nc.records = records;
+    nc.out_order = out_order;
+    nc.want_group_off = out_group_off != nullptr;
+    nc.want_kept = out_kept != nullptr;
+    std::vector<SparseBlock> blocks(groups.size());
+    std::vector<NamesSlot> slots(groups.size());
+    t0 = clk::now();
+    OEM_TRY(run_cells_workers(who, run, groups, [&](size_t g, const CellsRun &grun, CellsGroupPath *path) -> int {
+        const uint32_t c0 = groups[g].first, c1 = groups[g].second;
+        RecordsGroup rg;
+        rg.out_tables = r->discard.data() + c0;
+        rg.blk = &blocks[g];
+        rg.infos = r->infos.data() + c0;
+        rg.launch = &path->launch;
+        bool batched = false;
+        const int rc = run_names_group(who, grun, rf, nc, c0, c1, rg, &slots[g], &batched);
+        path->batched = batched ? 1u : 0u;
+        return rc;
+    }));
+    last[1] = (double)groups.size();
+    last[5] = ms_since(t0);
+    names_call_outputs(groups, slots, cro.data(), n, out_group_off, out_n_groups, out_cell_group_off, out_kept);
+    OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
+    if (out_cell_rec_off) std::memcpy(out_cell_rec_off, cro.data(), sizeof(uint64_t) * ((size_t)n_cells + 1));
+    if (out_n_cells) *out_n_cells = n_cells;
+    std::memcpy(g_cells_barcodes_last, last, sizeof last);
+    *out = r.release();
+    return OEM_OK;
+    OEM_API_END("oem_em_run_cells_records_barcodes_sparse")
 }
 
 extern "C" int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out)

@@ -24,6 +24,19 @@
 // byte (a BAM read name cannot).  The second condition lets a name be compared through zero-padded keys: key r of a name
 // is its bytes [8r, 8r + 8) as one big-endian u64, zero past the end.  Comparing names equals comparing their key
 // sequences; two names whose keys agree up to and including a key whose last byte is 0 are the same name.
+//
+// Cells from barcodes (collate_barcodes_host below, oem_collate_barcodes): the reference takes input whose records are
+// adjacent per barcode (single_cell.rs:196-213 reads the CB tag of a run's first record, alignment_parser.rs:244-299
+// cuts where it changes; docs/index.md "all records of a barcode must be adjacent").  Here the records may come in any
+// order:
+//   - a cell is the set of records with one barcode, the barcodes compared as bytes;
+//   - cells are numbered in the order of their first record in the input (first seen), so input that is collated by
+//     barcode already gives the cells it gives today, in the same order;
+//   - inside a cell the records keep their input order (the name rule above is applied afterwards, inside each cell);
+//   - order_bc is the cell-major permutation of the records, cell_rec_off[c] cell c's first position in it, n_cells the
+//     number of distinct barcodes.
+// A barcode is never empty (the reference bails when CB is missing: single_cell.rs:203, alignment_parser.rs:150) and
+// holds no 0 byte: the conditions names carry, and what lets the same zero-padded keys sort them.
 #pragma once
 
 #include <stdint.h>
@@ -133,6 +146,40 @@ inline uint64_t collate_host(const uint8_t *names, const uint64_t *name_off, con
     if (bad != kCollateNoRecord) return bad;
     for (uint32_t c = 0; c < n_cells; ++c) collate_host_cell(names, name_off, secondary, cell_rec_off[c], cell_rec_off[c + 1], mode, order);
     collate_host_cut(names, name_off, n_records, cell_rec_off, n_cells, order, group_off, n_groups, cell_group_off);
+    return kCollateNoRecord;
+}
+
+// The host walk of the barcode rule: a stable sort of the records by barcode bytes, the runs of one barcode ranked by
+// their first (= smallest, the sort being stable) record, and the runs laid out in that rank.  order (n_records),
+// cell_rec_off (capacity n_records + 1; *n_cells + 1 written).  Returns the first bad barcode as collate_first_bad_name
+// does, and then leaves the outputs alone.
+inline uint64_t collate_barcodes_host(const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, uint32_t *order,
+                                      uint64_t *cell_rec_off, uint64_t *n_cells, bool *zero_byte)
+{
+    const uint64_t bad = collate_first_bad_name(barcodes, barcode_off, n_records, zero_byte);
+    if (bad != kCollateNoRecord) return bad;
+    auto cmp = [&](uint32_t i, uint32_t j) {
+        return collate_name_cmp(barcodes + barcode_off[i], barcode_off[i + 1] - barcode_off[i], barcodes + barcode_off[j],
+                                barcode_off[j + 1] - barcode_off[j]);
+    };
+    std::vector<uint32_t> sorted(n_records);
+    for (uint64_t i = 0; i < n_records; ++i) sorted[i] = (uint32_t)i;
+    std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t i, uint32_t j) { return cmp(i, j) < 0; });
+    std::vector<uint64_t> run_off; // the positions of `sorted` where a barcode starts, then n_records
+    for (uint64_t p = 0; p < n_records; ++p)
+        if (p == 0 || cmp(sorted[p - 1], sorted[p]) != 0) run_off.push_back(p);
+    const uint64_t n_runs = run_off.size();
+    run_off.push_back(n_records);
+    std::vector<uint64_t> by_head(n_runs);
+    for (uint64_t r = 0; r < n_runs; ++r) by_head[r] = r;
+    std::sort(by_head.begin(), by_head.end(), [&](uint64_t a, uint64_t b) { return sorted[run_off[a]] < sorted[run_off[b]]; });
+    uint64_t at = 0;
+    for (uint64_t c = 0; c < n_runs; ++c) {
+        cell_rec_off[c] = at;
+        for (uint64_t p = run_off[by_head[c]]; p < run_off[by_head[c] + 1]; ++p) order[at++] = sorted[p];
+    }
+    cell_rec_off[n_runs] = n_records;
+    *n_cells = n_runs;
     return kCollateNoRecord;
 }
 

@@ -18,6 +18,16 @@ struct CollateInput {
     uint32_t mode = kCollateSort;
     uint64_t chunk_bytes = 0;    // name bytes per upload chunk
     bool timing = false;
+    bool cut_records = false;    // the upload chunks may end inside a cell (sorting without secondary only: one cell of everything)
+    const char *what = "name";   // what the bytes are called in the device-found errors ("barcode": oem_collate_barcodes)
+    // The device form (the groups of oem_em_run_cells_records_barcodes_sparse): the batch's names are on the device
+    // already, checked when they went up.  d_names: the batch's blob, 8-byte aligned and padded by 16; d_name_off: the
+    // batch's m + 1 offsets into it, d_off_base to be subtracted; d_secondary (or NULL): m flags and a 0 behind them.
+    // names / name_off / secondary above are then not read, and there are no upload lanes and no validate pass.
+    const uint8_t *d_names = nullptr;
+    const uint64_t *d_name_off = nullptr;
+    uint64_t d_off_base = 0, d_n_bytes = 0;
+    const uint8_t *d_secondary = nullptr;
 };
 
 // What a batch leaves on the device.  The batch holds the cells [c0, c1) and their m records.
@@ -34,6 +44,46 @@ struct CollateResident {
 // layout) is accumulated.  Returns with the device idle and the scratch of the sort released.
 int collate_resident(const CollateInput &in, uint32_t c0, uint32_t c1, uint64_t order_base, uint64_t pos_base, uint64_t group_base,
                      double *info, CollateResident *out);
+
+// The cells of uncollated records, left on the device (collate_barcodes_resident): order_bc and cell_rec_off of
+// oem_collate.h's barcode rule.
+struct BarcodeCells {
+    DevBuf<uint32_t> order;        // n_records: order_bc
+    DevBuf<uint64_t> cell_rec_off; // n_cells + 1
+    uint64_t n_cells = 0;
+};
+
+// The barcodes of n_records > 0 records (checked by check_barcode_input) sorted as one cell by the key rounds of
+// collate_resident, then the runs ranked by their first record and laid out in that rank.  An empty barcode or a 0 byte
+// is OEM_ERR_ARG naming the first such record.  info: collate_last_call's layout, accumulated; info8 (8 doubles): [0]
+// the cells' kernels in ms under `timing`.  Returns with the device idle.
+int collate_barcodes_resident(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, bool timing,
+                              double *info, double *cells_ms, BarcodeCells *out);
+// The argument checks of oem_collate_barcodes on the input side, before any device use.
+int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records);
+
+// The names of the records order[0 .. m) (indices into the whole input's d_name_off, n + 1 offsets into d_names, which
+// is 8-byte aligned and padded) gathered into one dense blob: d_out_off (m + 1, from 0: the scan of the lengths, filled
+// by gather_name_offsets) and d_out (8-byte aligned, out_bytes + 16 allocated) by gather_names, which takes any window
+// [k0, k1) of the records whose offsets are d_out_off[k0 .. k1] - off_base.  d_sec / d_out_sec: the flags likewise
+// (d_out_sec: m + 1 rounded up to 8, zero behind the m flags), or NULL.  On the null stream, which is left idle.
+int gather_name_offsets(const uint32_t *d_order, uint64_t m, const uint64_t *d_name_off, uint64_t *d_out_off);
+int gather_names(const uint32_t *d_order, uint64_t m, const uint8_t *d_names, const uint64_t *d_name_off, const uint64_t *d_out_off,
+                 uint64_t off_base, uint64_t out_bytes, uint8_t *d_out, const uint8_t *d_sec, uint8_t *d_out_sec);
+// Validates names that are resident (the blob 16-byte padded): the first record with a 0 byte -> d_bad[0], with an empty
+// name -> d_bad[1] (both start as kNoRecord), over the records [r0, r1) and their bytes [b0, b1), on `st`.
+void launch_collate_validate(hipStream_t st, const uint8_t *d_names, uint64_t b0, uint64_t b1, const uint64_t *d_off, uint64_t r0,
+                             uint64_t r1, unsigned long long *d_bad);
+
+// The last oem_collate_barcodes / oem_em_run_cells_records_barcodes_sparse of this thread (8 doubles): [0] key rounds,
+// [1] upload chunks of the barcodes, [2] the cells' kernels (ms), [3] the barcode uploads, [4] their chunk kernels, [5]
+// the rounds, [6] staging (ms, under OEM_COLLATE_TIMING), [7] the rounds that sorted.
+void collate_barcodes_last_call(double *out8);
+void collate_barcodes_set_last(const double *in8);
+// The last oem_em_run_cells_records_barcodes_sparse of this thread (8 doubles): [0] cells, [1] groups of cells, and by
+// the host clock in ms [2] the barcode collation, [3] names, flags and records going up, [4] the gathered name offsets,
+// [5] the groups on their workers; under OEM_COLLATE_TIMING from HIP events [6] the name uploads, [7] the validate kernels.
+void cells_barcodes_last_call(double *out8);
 
 uint64_t collate_chunk_bytes();   // the upload chunk (testing build: OEM_COLLATE_CHUNK_BYTES)
 uint64_t collate_batch_records(); // records per batch of oem_collate_names (testing build: OEM_COLLATE_BATCH_RECORDS)

@@ -47,6 +47,7 @@ constexpr uint64_t kCollateChunkBytes = 64ull << 20;    // name bytes per upload
 constexpr uint64_t kCollateBatchRecords = 1ull << 27;   // records per batch (the test-only library: OEM_COLLATE_BATCH_RECORDS)
 
 thread_local double g_collate_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+thread_local double g_barcodes_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 struct U32ToU64 {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
@@ -283,6 +284,138 @@ __global__ __launch_bounds__(kCT) void k_collate_finish(uint64_t m, uint32_t n_c
     if (head[i]) group_off[gidx[i]] = pos_base + i;
 }
 
+// ---- cells from barcodes (oem_collate.h's barcode rule), behind the sort of all records as one cell: `sorted` is the
+// stable order by barcode bytes, run_off (n_runs + 1, closed by n) the positions where a barcode starts.
+
+// the run of position p: the last r with run_off[r] <= p
+__device__ __forceinline__ uint64_t run_of(const uint64_t *__restrict__ run_off, uint64_t n_runs, uint64_t p)
+{
+    uint64_t lo = 0, hi = n_runs - 1;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (run_off[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// a run's head is its first record: its smallest, the sort being stable
+__global__ __launch_bounds__(kCT) void k_barcode_heads(uint64_t n_runs, const uint32_t *__restrict__ sorted, const uint64_t *__restrict__ run_off,
+                                                        uint32_t *__restrict__ head, uint32_t *__restrict__ idx)
+{
+    const uint64_t r = tid64();
+    if (r >= n_runs) return;
+    head[r] = sorted[run_off[r]];
+    idx[r] = (uint32_t)r;
+}
+
+// run_of_rank: the runs sorted by head.  len[k] = the length of the run of rank k (len[n_runs] = 0, for the scan).
+__global__ __launch_bounds__(kCT) void k_barcode_lengths(uint64_t n_runs, const uint32_t *__restrict__ run_of_rank,
+                                                          const uint64_t *__restrict__ run_off, uint64_t *__restrict__ len,
+                                                          uint32_t *__restrict__ rank_of_run)
+{
+    const uint64_t k = tid64();
+    if (k > n_runs) return;
+    if (k == n_runs) {
+        len[k] = 0;
+        return;
+    }
+    const uint32_t r = run_of_rank[k];
+    len[k] = run_off[r + 1] - run_off[r];
+    rank_of_run[r] = (uint32_t)k;
+}
+
+// every run to the place of its rank: cell_rec_off is the exclusive scan of len
+__global__ __launch_bounds__(kCT) void k_barcode_scatter(uint64_t n, uint64_t n_runs, const uint32_t *__restrict__ sorted,
+                                                          const uint64_t *__restrict__ run_off, const uint32_t *__restrict__ rank_of_run,
+                                                          const uint64_t *__restrict__ cell_rec_off, uint32_t *__restrict__ order_bc)
+{
+    const uint64_t p = tid64();
+    if (p >= n) return;
+    const uint64_t r = run_of(run_off, n_runs, p);
+    order_bc[cell_rec_off[rank_of_run[r]] + (p - run_off[r])] = sorted[p];
+}
+
+// ---- the gather of names that are resident
+
+// len[k] = the length of the name of record order[k]; len[m] = 0
+__global__ __launch_bounds__(kCT) void k_names_lengths(uint64_t m, const uint32_t *__restrict__ order, const uint64_t *__restrict__ off,
+                                                        uint64_t *__restrict__ len)
+{
+    const uint64_t k = tid64();
+    if (k > m) return;
+    len[k] = k < m ? off[(uint64_t)order[k] + 1] - off[order[k]] : 0ull;
+}
+
+// up to 8 bytes from byte `at` of the blob through its aligned words, byte 0 in the low bits (the blob is 8-byte aligned
+// and padded: the second word is read only when the bytes reach into it)
+__device__ __forceinline__ uint64_t load_bytes(const uint8_t *__restrict__ blob, uint64_t at, uint32_t n)
+{
+    const uint64_t *w = (const uint64_t *)(blob + (at & ~7ull));
+    const uint32_t sh = (uint32_t)(at & 7u) * 8u;
+    uint64_t v = w[0] >> sh;
+    if (sh && (at & 7u) + n > 8u) v |= w[1] << (64u - sh);
+    if (n < 8) v &= (1ull << (8 * n)) - 1;
+    return v;
+}
+
+// One lane per 8-byte word of the gathered blob, so the stores are coalesced and no access is byte-wide: word j holds
+// the bytes [8 j, 8 j + 8) of the concatenation of the names of order[0 .. m), name k at out_off[k] - off_base.  A word
+// may take its bytes from several names (a name can be one byte long); the lane walks them.  The record of the
+// workgroup's first byte is searched once among all m, each lane's own among the few that a workgroup's 2 KiB can hold.
+// Bytes past out_bytes are written as 0.
+__global__ __launch_bounds__(kCT) void k_names_gather(uint64_t n_words, uint64_t out_bytes, uint64_t m, const uint32_t *__restrict__ order,
+                                                       const uint8_t *__restrict__ names, const uint64_t *__restrict__ off,
+                                                       const uint64_t *__restrict__ out_off, uint64_t off_base, uint64_t *__restrict__ out)
+{
+    const uint64_t j = tid64();
+    if (j >= n_words) return;
+    uint64_t lo = 0, hi = m - 1; // the record that holds byte p: the last k with out_off[k] - off_base <= p
+    {
+        const uint64_t p0 = (uint64_t)blockIdx.x * kCT * 8;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (out_off[mid] - off_base <= p0) lo = mid;
+            else hi = mid - 1;
+        }
+        hi = lo + (uint64_t)kCT * 8 < m - 1 ? lo + (uint64_t)kCT * 8 : m - 1; // (names are never empty: a byte each at least)
+    }
+    uint64_t p = 8 * j;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (out_off[mid] - off_base <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    uint64_t k = lo, v = 0;
+    const uint64_t end = 8 * j + 8 < out_bytes ? 8 * j + 8 : out_bytes;
+    while (p < end) {
+        const uint64_t k0 = out_off[k] - off_base, k1 = out_off[k + 1] - off_base;
+        const uint32_t n = (uint32_t)((k1 < end ? k1 : end) - p);
+        v |= load_bytes(names, off[order[k]] + (p - k0), n) << (8 * (p - 8 * j));
+        p += n;
+        ++k;
+    }
+    out[j] = v;
+}
+
+// The flags likewise, eight records per lane: out word j = the flags of order[8 j .. 8 j + 8), 0 past m.  The source is
+// read through its aligned 4-byte words.
+__global__ __launch_bounds__(kCT) void k_flags_gather(uint64_t n_words, uint64_t m, const uint32_t *__restrict__ order,
+                                                       const uint8_t *__restrict__ sec, uint64_t *__restrict__ out)
+{
+    const uint64_t j = tid64();
+    if (j >= n_words) return;
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < 8; ++b) {
+        const uint64_t k = 8 * j + b;
+        if (k >= m) break;
+        const uint32_t r = order[k];
+        const uint32_t w = ((const uint32_t *)sec)[r >> 2];
+        v |= (uint64_t)(((w >> (8 * (r & 3u))) & 0xffu) != 0) << (8 * b);
+    }
+    out[j] = v;
+}
+
 inline dim3 grid_for(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kCT - 1) / kCT, 1)); }
 
 // a device buffer that only grows (the scans' and sorts' temporary storage)
@@ -338,18 +471,37 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
 {
     const uint32_t nc = c1 - c0;
     const uint64_t rec_base = cc.cell_rec_off[c0], m = cc.cell_rec_off[c1] - rec_base;
-    const uint64_t off_base = cc.name_off[rec_base], n_bytes = cc.name_off[rec_base + m] - off_base;
+    const bool resident = cc.d_names != nullptr; // the device form: the names are here and checked already
+    const uint64_t off_base = resident ? cc.d_off_base : cc.name_off[rec_base];
+    const uint64_t n_bytes = resident ? cc.d_n_bytes : cc.name_off[rec_base + m] - off_base;
+    const bool has_sec = resident ? cc.d_secondary != nullptr : cc.secondary != nullptr;
     const bool sorting = cc.mode == kCollateSort;
 
     // the upload chunks: whole cells, at most chunk_bytes of names unless one cell has more
     std::vector<uint64_t> byte_cut{0}, rec_cut{0};
     std::vector<unsigned long long> cell_off(nc + 1);
-    {
+    if (cc.cut_records && !resident) { // one cell of everything: cut wherever a record ends
+        const uint64_t *off = cc.name_off + rec_base;
+        cell_off[0] = 0;
+        for (uint64_t r = 0; r < m;) {
+            uint64_t r1 = (uint64_t)(std::upper_bound(off + r + 1, off + m + 1, off[r] + cc.chunk_bytes) - off) - 1;
+            r1 = std::max(r1, r + 1);
+            if (r1 < m) {
+                byte_cut.push_back(off[r1] - off_base);
+                rec_cut.push_back(r1);
+            }
+            r = r1;
+        }
+        cell_off[nc] = m;
+        byte_cut.push_back(n_bytes);
+        rec_cut.push_back(m);
+    } else {
         uint64_t start_b = 0, start_r = 0;
         for (uint32_t c = c0; c < c1; ++c) {
             const uint64_t r0 = cc.cell_rec_off[c] - rec_base, r1 = cc.cell_rec_off[c + 1] - rec_base;
-            const uint64_t b0 = cc.name_off[rec_base + r0] - off_base, b1 = cc.name_off[rec_base + r1] - off_base;
             cell_off[c - c0] = r0;
+            if (resident) continue;
+            const uint64_t b0 = cc.name_off[rec_base + r0] - off_base, b1 = cc.name_off[rec_base + r1] - off_base;
             if (r0 > start_r && b1 - start_b > cc.chunk_bytes) {
                 byte_cut.push_back(b0);
                 rec_cut.push_back(r0);
@@ -368,12 +520,14 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
     hipStream_t st = main.s;
     Scratch sc;
     sc.st = st;
-    DevBuf<uint8_t> d_names, d_sec;
-    DevBuf<uint64_t> d_off, d_key, d_key_s, d_flags, d_scan, d_cgo; // (d_key_s and d_cgo are handed to `out` in the end)
+    DevBuf<uint8_t> d_names_own, d_sec_own;
+    DevBuf<uint64_t> d_off_own, d_key, d_key_s, d_flags, d_scan, d_cgo; // (d_key_s and d_cgo are handed to `out` in the end)
     DevBuf<unsigned long long> d_cell_off, d_words; // d_words: [0] zero byte, [1] empty name, [2] or, [3] and
     DevBuf<uint32_t> d_order, d_head, d_iota, d_perm1, d_perm2, d_run1, d_run1_s, d_pos[2], d_ord[2], d_run[2];
-    OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16, nullptr));
-    OEM_TRY(dev_alloc(&d_off.p, m + 1, nullptr));
+    if (!resident) {
+        OEM_TRY(dev_alloc(&d_names_own.p, n_bytes + 16, nullptr));
+        OEM_TRY(dev_alloc(&d_off_own.p, m + 1, nullptr));
+    }
     OEM_TRY(dev_alloc(&d_cell_off.p, nc + 1, nullptr));
     OEM_TRY(dev_alloc(&d_words.p, 4, nullptr));
     OEM_TRY(dev_alloc(&d_order.p, m, nullptr));
@@ -394,8 +548,10 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
             OEM_TRY(dev_alloc(&d_ord[k].p, m, nullptr));
             OEM_TRY(dev_alloc(&d_run[k].p, m, nullptr));
         }
-        if (cc.secondary) OEM_TRY(dev_alloc(&d_sec.p, m + 1, nullptr));
+        if (has_sec && !resident) OEM_TRY(dev_alloc(&d_sec_own.p, m + 1, nullptr));
     }
+    struct { const uint8_t *p; } d_names{resident ? cc.d_names : d_names_own.p}, d_sec{resident ? cc.d_secondary : d_sec_own.p};
+    struct { const uint64_t *p; } d_off{resident ? cc.d_name_off : d_off_own.p};
     Event ev[3];
     if (cc.timing)
         for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
@@ -403,19 +559,21 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
     // what the chunks' kernels need before the first name arrives
     const unsigned long long words0[4] = {kNoRecord, kNoRecord, 0ull, ~0ull};
     OEM_HIP(hipMemcpyAsync(d_words.p, words0, sizeof words0, hipMemcpyHostToDevice, st));
-    OEM_HIP(hipMemcpyAsync(d_off.p, cc.name_off + rec_base, sizeof(uint64_t) * (m + 1), hipMemcpyHostToDevice, st));
+    if (!resident) OEM_HIP(hipMemcpyAsync(d_off_own.p, cc.name_off + rec_base, sizeof(uint64_t) * (m + 1), hipMemcpyHostToDevice, st));
     OEM_HIP(hipMemcpyAsync(d_cell_off.p, cell_off.data(), sizeof(unsigned long long) * (nc + 1), hipMemcpyHostToDevice, st));
     OEM_HIP(hipMemsetAsync(d_head.p, 0, sizeof(uint32_t) * (m + 1), st));
-    OEM_HIP(hipMemsetAsync(d_names.p + n_bytes, 0, 16, st));
+    if (!resident) OEM_HIP(hipMemsetAsync(d_names_own.p + n_bytes, 0, 16, st));
     if (sorting) {
-        if (cc.secondary) {
-            OEM_HIP(hipMemcpyAsync(d_sec.p, cc.secondary + rec_base, m, hipMemcpyHostToDevice, st));
-            OEM_HIP(hipMemsetAsync(d_sec.p + m, 0, 1, st));
+        if (has_sec) {
+            if (!resident) {
+                OEM_HIP(hipMemcpyAsync(d_sec_own.p, cc.secondary + rec_base, m, hipMemcpyHostToDevice, st));
+                OEM_HIP(hipMemsetAsync(d_sec_own.p + m, 0, 1, st));
+            }
             hipcub::TransformInputIterator<uint64_t, U8ToU64, const uint8_t *> in(d_sec.p, U8ToU64());
             OEM_TRY(scan_u64(sc, false, in, d_scan.p, m + 1, st));
         }
         hipLaunchKernelGGL(k_collate_start, grid_for(m), dim3(kCT), 0, st, m, (const unsigned long long *)d_cell_off.p, nc,
-                           (const uint8_t *)d_sec.p, (const uint64_t *)(cc.secondary ? d_scan.p : nullptr), d_ord[0].p, d_pos[0].p,
+                           (const uint8_t *)d_sec.p, (const uint64_t *)(has_sec ? d_scan.p : nullptr), d_ord[0].p, d_pos[0].p,
                            d_run[0].p);
         OEM_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_collate_iota, grid_for(m), dim3(kCT), 0, st, m, d_iota.p);
@@ -425,8 +583,18 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
 
     // the names, chunk by chunk; behind each chunk its checks and its share of round 0 (or of the adjacent cut)
     float ms[6] = {0, 0, 0, 0, 0, 0};
+    if (resident) { // no lanes: round 0's keys (or the adjacent cut) over the whole batch
+        if (sorting)
+            hipLaunchKernelGGL(k_collate_keys, grid_for(m), dim3(kCT), 0, st, (uint64_t)0, m, (const uint32_t *)d_ord[0].p,
+                               (const uint8_t *)d_names.p, (const uint64_t *)d_off.p, off_base, (uint64_t)0, d_key.p, d_words.p + 2);
+        else
+            hipLaunchKernelGGL(k_collate_adjacent, grid_for(m), dim3(kCT), 0, st, (uint64_t)0, m, (const uint8_t *)d_names.p,
+                               (const uint64_t *)d_off.p, off_base, (const unsigned long long *)d_cell_off.p, nc, d_order.p, d_head.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipStreamSynchronize(st));
+    } else
     OEM_TRY(filter_upload_measure<uint8_t>(
-        cc.names + off_base, d_names.p, byte_cut.data(), n_chunks, 1, cc.timing ? ms : nullptr,
+        cc.names + off_base, d_names_own.p, byte_cut.data(), n_chunks, 1, cc.timing ? ms : nullptr,
         [&](hipStream_t lane, uint64_t g0, uint64_t) {
             const uint64_t b0 = byte_cut[g0], b1 = byte_cut[g0 + 1], r0 = rec_cut[g0], r1 = rec_cut[g0 + 1];
             const uint64_t words = b1 > b0 ? ((b1 + 15) >> 4) - (b0 >> 4) : 0;
@@ -439,7 +607,7 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
                 hipLaunchKernelGGL(k_collate_adjacent, grid_for(r1 - r0), dim3(kCT), 0, lane, r0, r1, (const uint8_t *)d_names.p,
                                    (const uint64_t *)d_off.p, off_base, (const unsigned long long *)d_cell_off.p, nc, d_order.p, d_head.p);
         }));
-    info[1] += (double)n_chunks;
+    info[1] += resident ? 0.0 : (double)n_chunks;
     info[3] += ms[0];
     info[4] += ms[1];
     info[6] += ms[5];
@@ -447,8 +615,8 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
     unsigned long long words[4];
     OEM_HIP(hipMemcpy(words, d_words.p, sizeof words, hipMemcpyDeviceToHost));
     if (words[0] != kNoRecord || words[1] != kNoRecord) {
-        if (words[1] < words[0]) return fail(OEM_ERR_ARG, "%s: record %llu has an empty name", cc.who, words[1]);
-        return fail(OEM_ERR_ARG, "%s: the name of record %llu contains a 0 byte", cc.who, words[0]);
+        if (words[1] < words[0]) return fail(OEM_ERR_ARG, "%s: record %llu has an empty %s", cc.who, words[1], cc.what);
+        return fail(OEM_ERR_ARG, "%s: the %s of record %llu contains a 0 byte", cc.who, cc.what, words[0]);
     }
 
     if (cc.timing) OEM_HIP(hipEventRecord(ev[0].e, st));
@@ -534,6 +702,112 @@ int collate_resident(const CollateInput &cc, uint32_t c0, uint32_t c1, uint64_t 
     return OEM_OK;
 }
 
+void launch_collate_validate(hipStream_t st, const uint8_t *d_names, uint64_t b0, uint64_t b1, const uint64_t *d_off, uint64_t r0,
+                             uint64_t r1, unsigned long long *d_bad)
+{
+    const uint64_t words = b1 > b0 ? ((b1 + 15) >> 4) - (b0 >> 4) : 0;
+    hipLaunchKernelGGL(k_collate_validate, grid_for(std::max(words, r1 - r0)), dim3(kCT), 0, st, d_names, b0, b1, d_off, (uint64_t)0, r0, r1,
+                       (uint64_t)0, d_bad);
+}
+
+int gather_name_offsets(const uint32_t *d_order, uint64_t m, const uint64_t *d_name_off, uint64_t *d_out_off)
+{
+    Scratch sc;
+    DevBuf<uint64_t> d_len;
+    OEM_TRY(dev_alloc(&d_len.p, m + 1, nullptr));
+    hipLaunchKernelGGL(k_names_lengths, grid_for(m + 1), dim3(kCT), 0, nullptr, m, d_order, d_name_off, d_len.p);
+    OEM_HIP(hipGetLastError());
+    OEM_TRY(scan_u64(sc, false, (const uint64_t *)d_len.p, d_out_off, m + 1, nullptr));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
+
+int gather_names(const uint32_t *d_order, uint64_t m, const uint8_t *d_names, const uint64_t *d_name_off, const uint64_t *d_out_off,
+                 uint64_t off_base, uint64_t out_bytes, uint8_t *d_out, const uint8_t *d_sec, uint8_t *d_out_sec)
+{
+    const uint64_t n_words = (out_bytes + 16) / 8; // the blob and its padding
+    hipLaunchKernelGGL(k_names_gather, grid_for(n_words), dim3(kCT), 0, nullptr, n_words, out_bytes, m, d_order, d_names, d_name_off,
+                       d_out_off, off_base, (uint64_t *)d_out);
+    OEM_HIP(hipGetLastError());
+    if (d_sec) {
+        const uint64_t sec_words = (m + 1 + 7) / 8;
+        hipLaunchKernelGGL(k_flags_gather, grid_for(sec_words), dim3(kCT), 0, nullptr, sec_words, m, d_order, d_sec, (uint64_t *)d_out_sec);
+        OEM_HIP(hipGetLastError());
+    }
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
+
+int collate_barcodes_resident(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, bool timing,
+                              double *info, double *cells_ms, BarcodeCells *out)
+{
+    const uint64_t n = n_records, one_cell[2] = {0, n};
+    CollateInput cc;
+    cc.who = who;
+    cc.what = "barcode";
+    cc.names = barcodes;
+    cc.name_off = barcode_off;
+    cc.cell_rec_off = one_cell;
+    cc.mode = kCollateSort;
+    cc.chunk_bytes = collate_chunk_bytes();
+    cc.timing = timing;
+    cc.cut_records = true;
+    CollateResident cr; // order: the stable sort by barcode; group_off: where a barcode starts, closed by n
+    OEM_TRY(collate_resident(cc, 0, 1, 0, 0, 0, info, &cr));
+    const uint64_t n_runs = cr.n_groups;
+
+    Scratch sc;
+    Event ev[2];
+    if (timing)
+        for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
+    DevBuf<uint32_t> d_head, d_head_s, d_idx, d_run_of_rank, d_rank_of_run, d_order_bc;
+    DevBuf<uint64_t> d_len, d_cro;
+    OEM_TRY(dev_alloc(&d_head.p, n_runs, nullptr));
+    OEM_TRY(dev_alloc(&d_head_s.p, n_runs, nullptr));
+    OEM_TRY(dev_alloc(&d_idx.p, n_runs, nullptr));
+    OEM_TRY(dev_alloc(&d_run_of_rank.p, n_runs, nullptr));
+    OEM_TRY(dev_alloc(&d_rank_of_run.p, n_runs, nullptr));
+    OEM_TRY(dev_alloc(&d_order_bc.p, n, nullptr));
+    OEM_TRY(dev_alloc(&d_len.p, n_runs + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_cro.p, n_runs + 1, nullptr));
+    if (timing) OEM_HIP(hipEventRecord(ev[0].e, nullptr));
+    hipLaunchKernelGGL(k_barcode_heads, grid_for(n_runs), dim3(kCT), 0, nullptr, n_runs, (const uint32_t *)cr.order.p,
+                       (const uint64_t *)cr.group_off.p, d_head.p, d_idx.p);
+    OEM_HIP(hipGetLastError());
+    OEM_TRY(sort_pairs<uint32_t>(sc, d_head.p, d_head_s.p, d_idx.p, d_run_of_rank.p, n_runs, 0, std::max(bits_of(n - 1), 1), nullptr));
+    hipLaunchKernelGGL(k_barcode_lengths, grid_for(n_runs + 1), dim3(kCT), 0, nullptr, n_runs, (const uint32_t *)d_run_of_rank.p,
+                       (const uint64_t *)cr.group_off.p, d_len.p, d_rank_of_run.p);
+    OEM_HIP(hipGetLastError());
+    OEM_TRY(scan_u64(sc, false, (const uint64_t *)d_len.p, d_cro.p, n_runs + 1, nullptr));
+    hipLaunchKernelGGL(k_barcode_scatter, grid_for(n), dim3(kCT), 0, nullptr, n, n_runs, (const uint32_t *)cr.order.p,
+                       (const uint64_t *)cr.group_off.p, (const uint32_t *)d_rank_of_run.p, (const uint64_t *)d_cro.p, d_order_bc.p);
+    OEM_HIP(hipGetLastError());
+    if (timing) OEM_HIP(hipEventRecord(ev[1].e, nullptr));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    if (timing) {
+        float t = 0.f;
+        OEM_HIP(hipEventElapsedTime(&t, ev[0].e, ev[1].e));
+        *cells_ms += t;
+    }
+    std::swap(out->order.p, d_order_bc.p);
+    std::swap(out->cell_rec_off.p, d_cro.p);
+    out->n_cells = n_runs;
+    return OEM_OK;
+}
+
+int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records)
+{
+    if (n_records > 0xffffffffull) return fail(OEM_ERR_ARG, "%s: %llu records: more than 2^32 - 1", who, (unsigned long long)n_records);
+    if (n_records > kCollateMaxBatch)
+        return fail(OEM_ERR_ARG, "%s: %llu records: the barcodes are sorted as one batch of at most 2^31 - 2", who, (unsigned long long)n_records);
+    if (n_records && !barcodes) return fail(OEM_ERR_ARG, "%s: barcodes is NULL and n_records is not 0", who);
+    if (barcode_off[0] != 0) return fail(OEM_ERR_ARG, "%s: barcode_off must start at 0", who);
+    for (uint64_t i = 0; i < n_records; ++i)
+        if (barcode_off[i + 1] < barcode_off[i])
+            return fail(OEM_ERR_ARG, "%s: barcode_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+    return OEM_OK;
+}
+
 namespace {
 
 // One batch of oem_collate_names: the resident form, then its arrays to the caller's; *group_base counts the groups before
@@ -586,6 +860,8 @@ int check_collate_input(const char *who, const uint8_t *names, const uint64_t *n
 }
 
 void collate_last_call(double *out8) { std::memcpy(out8, g_collate_last, sizeof g_collate_last); }
+void collate_barcodes_last_call(double *out8) { std::memcpy(out8, g_barcodes_last, sizeof g_barcodes_last); }
+void collate_barcodes_set_last(const double *in8) { std::memcpy(g_barcodes_last, in8, sizeof g_barcodes_last); }
 
 } // namespace oem
 
@@ -633,4 +909,29 @@ extern "C" int oem_collate_names(const uint8_t *names, const uint64_t *name_off,
     std::memcpy(g_collate_last, info, sizeof info);
     return OEM_OK;
     OEM_API_END("oem_collate_names")
+}
+
+extern "C" int oem_collate_barcodes(const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, int device, uint32_t *out_order,
+                                    uint64_t *out_cell_rec_off, uint64_t *out_n_cells)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_collate_barcodes";
+    if (!barcode_off || !out_order || !out_cell_rec_off || !out_n_cells)
+        return fail(OEM_ERR_ARG, "%s: barcode_off or an output is NULL", who);
+    OEM_TRY(check_barcode_input(who, barcodes, barcode_off, n_records));
+    *out_n_cells = 0;
+    OEM_TRY(ensure_device(device));
+    double info[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cells_ms = 0;
+    std::memset(g_barcodes_last, 0, sizeof g_barcodes_last);
+    out_cell_rec_off[0] = 0;
+    if (n_records == 0) return OEM_OK;
+    BarcodeCells bc;
+    OEM_TRY(collate_barcodes_resident(who, barcodes, barcode_off, n_records, knob("OEM_COLLATE_TIMING", 0) != 0, info, &cells_ms, &bc));
+    OEM_HIP(hipMemcpy(out_order, bc.order.p, sizeof(uint32_t) * n_records, hipMemcpyDeviceToHost));
+    OEM_HIP(hipMemcpy(out_cell_rec_off, bc.cell_rec_off.p, sizeof(uint64_t) * (bc.n_cells + 1), hipMemcpyDeviceToHost));
+    *out_n_cells = bc.n_cells;
+    info[2] = cells_ms; // (no batches here: the slot holds the cells' kernels)
+    std::memcpy(g_barcodes_last, info, sizeof info);
+    return OEM_OK;
+    OEM_API_END("oem_collate_barcodes")
 }

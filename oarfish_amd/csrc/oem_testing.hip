@@ -11,6 +11,7 @@
 
 #include "oem_cells.h"
 #include "oem_collate.h"
+#include "oem_collate_device.h"
 #include "oem_shortest_f64.h"
 
 using namespace oem;
@@ -178,6 +179,38 @@ extern "C" int oem_test_collate_host(const uint8_t *names, const uint64_t *name_
     collate_host_cut(names, name_off, n_records, cell_rec_off, n_cells, out_order, out_group_off, out_n_groups, out_cell_group_off);
     return OEM_OK;
     OEM_API_END("oem_test_collate_host")
+}
+
+// out[0..7] = this thread's last oem_collate_barcodes (or the barcode stage of the one call), and the stages of its last
+// oem_em_run_cells_records_barcodes_sparse: the layouts of oem_collate_device.h
+extern "C" int oem_debug_collate_barcodes_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_collate_barcodes_last_call: NULL argument");
+    collate_barcodes_last_call(out);
+    return OEM_OK;
+}
+extern "C" int oem_debug_cells_barcodes_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_cells_barcodes_last_call: NULL argument");
+    cells_barcodes_last_call(out);
+    return OEM_OK;
+}
+
+// Test hook: the host walk of oem_collate.h's barcode rule (collate_barcodes_host) with oem_collate_barcodes' arguments
+// (checked by the caller) and outputs.  An empty barcode or a 0 byte is OEM_ERR_ARG naming the first such record.
+extern "C" int oem_test_collate_barcodes_host(const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, uint32_t *out_order,
+                                              uint64_t *out_cell_rec_off, uint64_t *out_n_cells)
+{
+    OEM_API_BEGIN
+    if (!barcode_off || !out_order || !out_cell_rec_off || !out_n_cells || (n_records && !barcodes))
+        return fail(OEM_ERR_ARG, "oem_test_collate_barcodes_host: NULL argument");
+    bool zero_byte = false;
+    const uint64_t bad = collate_barcodes_host(barcodes, barcode_off, n_records, out_order, out_cell_rec_off, out_n_cells, &zero_byte);
+    if (bad != kCollateNoRecord)
+        return fail(OEM_ERR_ARG, zero_byte ? "oem_test_collate_barcodes_host: the barcode of record %llu contains a 0 byte"
+                                           : "oem_test_collate_barcodes_host: record %llu has an empty barcode", (unsigned long long)bad);
+    return OEM_OK;
+    OEM_API_END("oem_test_collate_barcodes_host")
 }
 
 // Test hook: the host build of oem_shortest_f64.h.  The texts of the n finite f64 with these bits, one after the other

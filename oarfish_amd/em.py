@@ -342,6 +342,92 @@ def collate_names(names, cell_rec_off, secondary=None, mode: str = "sort", devic
     return order[:n], group_off[:int(n_groups.value) + 1].copy(), cell_group_off
 
 
+def _n_packed(names) -> int:
+    """How many names ``pack_read_names`` will find in ``names``."""
+    return len(names[1]) - 1 if isinstance(names, tuple) and len(names) == 2 and not isinstance(names[1], (str, bytes)) else len(names)
+
+
+def collate_barcodes(barcodes, device: int = 0):
+    """The cells of records that are in any order (``oem_collate_barcodes``; the reference wants a barcode's records
+    adjacent: single_cell.rs:196-213, alignment_parser.rs:244-299).
+
+    ``barcodes``: one barcode per record, whatever ``types.pack_read_names`` accepts; none is empty or holds a 0 byte.
+    Returns ``(order, cell_rec_off)``: ``order`` puts the records cell by cell -- cells in the order of their first
+    record, records in input order inside a cell --, cell ``c`` owns ``order[cell_rec_off[c] : cell_rec_off[c + 1]]``.
+    ``records[order]`` and ``names`` in that order, with ``cell_rec_off``, are what ``collate_names`` and
+    ``em_cells_records_sparse(..., names=)`` take.
+    """
+    from .types import pack_read_names
+    n = _n_packed(barcodes)
+    blob, off = pack_read_names(barcodes, n)
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    cell_rec_off = np.empty(n + 1, dtype=np.uint64)
+    n_cells = C.c_uint64(0)
+    if n and not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)   # (every barcode is empty: the call says so)
+    _lib.check(_lib.lib().oem_collate_barcodes(blob.ctypes.data if n else None, off.ctypes.data, n, device, order.ctypes.data,
+                                               cell_rec_off.ctypes.data, C.byref(n_cells)))
+    return order[:n], cell_rec_off[:int(n_cells.value) + 1].copy()
+
+
+def gather_names(names, idx):
+    """``names`` (a ``(blob, offsets)`` pair) in the order ``idx``: the NumPy gather of a variable-length blob."""
+    blob, off = np.asarray(names[0]), np.ascontiguousarray(names[1], dtype=np.int64)
+    idx = np.asarray(idx, dtype=np.int64)
+    lens = (off[1:] - off[:-1])[idx]
+    new_off = np.zeros(len(idx) + 1, dtype=np.uint64)
+    np.cumsum(lens, out=new_off[1:])
+    src = np.repeat(off[:-1][idx] - new_off[:-1].astype(np.int64), lens) + np.arange(int(new_off[-1]), dtype=np.int64)
+    return np.ascontiguousarray(blob[src]), new_off
+
+
+def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes, collate, mode):
+    """``em_cells_records_sparse(..., names=, barcodes=)``: the one call (``collate="device"``), or the join it replaces."""
+    from .types import pack_read_names
+    records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
+    n = len(records)
+    if _n_packed(names) != n:
+        raise ValueError("names must have one entry per record")
+    if _n_packed(barcodes) != n:
+        raise ValueError("barcodes must have one entry per record")
+    blob, off = pack_read_names(names, n)
+    bc_blob, bc_off = pack_read_names(barcodes, n)
+    sec = None
+    if secondary is not None:
+        sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
+        if len(sec) != n:
+            raise ValueError("secondary must have one entry per record")
+    if collate == "host":   # the four steps the one call replaces
+        order_bc, cell_rec_off = collate_barcodes((bc_blob, bc_off), device=device)
+        out = _em_cells_records_names(F, txp_len, records[order_bc], cell_rec_off, coverage, max_iter, conv_thresh, device,
+                                      gather_names((blob, off), order_bc), None if sec is None else sec[order_bc], mode)
+        return (*out[:6], order_bc[out[6]], cell_rec_off)
+    if n and not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)
+    if n and not len(bc_blob):
+        bc_blob = np.zeros(1, dtype=np.uint8)
+    model, bin_width, growth_rate = _coverage_args(coverage)
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    kept = np.zeros(max(n, 1), dtype=np.uint32)
+    cell_rec_off = np.empty(n + 1, dtype=np.uint64)
+    n_groups, n_cells = C.c_uint64(0), C.c_uint64(0)
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_em_run_cells_records_barcodes_sparse(
+        C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
+        bc_blob.ctypes.data if n else None, bc_off.ctypes.data, blob.ctypes.data if n else None, off.ctypes.data,
+        None if sec is None or not n else sec.ctypes.data, _COLLATE_MODES[mode], bin_width, model, growth_rate, device, max_iter,
+        conv_thresh, order.ctypes.data, cell_rec_off.ctypes.data, C.byref(n_cells), None, C.byref(n_groups), None,
+        kept.ctypes.data, C.byref(res)))
+    nc = int(n_cells.value)
+    try:
+        tables = _discard_tables(L, res, nc)
+    except BaseException:
+        L.oem_cells_result_destroy(res)
+        raise
+    return (*_take_cells_result(res, nc, L), kept[:int(n_groups.value)].copy(), tables, order[:n], cell_rec_off[:nc + 1].copy())
+
+
 def _coverage_args(coverage):
     """(model, bin_width, growth_rate) of a ``coverage`` dict as the records calls take it; None = no model."""
     if coverage is None:
@@ -393,7 +479,7 @@ def _em_cells_records_names(F, txp_len, records, cell_rec_off, coverage, max_ite
 
 def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
                             conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None, collate: str = "host",
-                            mode: str = "sort"):
+                            mode: str = "sort", barcodes=None):
     """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
     oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
     model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
@@ -411,6 +497,14 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     NumPy, then the records call.  ``collate="device"`` is one call (oem_em_run_cells_records_names_sparse): names and
     records go up in input order and the order is applied on the device; same seven values.  ``mode`` is
     ``collate_names``': ``"adjacent"`` for input that is name-collated already.
+
+    ``barcodes`` (one per record, as ``collate_barcodes`` takes them; ``names`` is then required and ``group_off`` /
+    ``cell_group_off`` must be None): the records are in any order at all and the cells are found from the barcodes.
+    ``collate="device"`` is one call (oem_em_run_cells_records_barcodes_sparse): barcodes, names and records go up in
+    input order, nothing is gathered on the host.  ``collate="host"`` joins ``collate_barcodes``, the NumPy gathers of
+    records, names and ``secondary``, and the names call: the path the one call replaces.  Both return the seven
+    values of the names form -- ``order`` is the composed one, the input index of every collated position -- and
+    ``cell_rec_off`` as an eighth.
     """
     from .builder import check_batch, filters_c
     if collate not in ("host", "device"):
@@ -419,8 +513,16 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
         raise ValueError(f"mode must be one of {sorted(_COLLATE_MODES)}, not {mode!r}")
     if names is None and secondary is not None:
         raise ValueError("secondary goes with names")
+    if barcodes is not None:
+        if cell_group_off is not None or group_off is not None:
+            raise ValueError("with barcodes the cells are found by the call: group_off and cell_group_off must be None")
+        if names is None:
+            raise ValueError("barcodes needs names")
     F = filters_c(filters)
     txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+    if barcodes is not None:
+        return _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes,
+                                          collate, mode)
     if names is not None and collate == "device":
         return _em_cells_records_names(F, txp_len, records, cell_group_off, coverage, max_iter, conv_thresh, device, names,
                                        secondary, mode)

@@ -596,6 +596,75 @@ def shuffle_cell_records(cell_records: SyntheticCellRecords, seed: int = BASE_SE
     return records, (blob, off), secondary, cell_rec_off
 
 
+_NUC = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def make_barcodes(n_cells: int, style: str = "10x", seed: int = BASE_SEED + 26) -> list:
+    """``n_cells`` distinct cell barcodes, as ``bytes``.
+
+    ``style="10x"``: 16 nucleotides and ``-1``, 18 bytes: three 8-byte key rounds of the device sort.
+    ``style="var"``: lengths 1 to 20 over ``ACGT``; every third barcode is a proper prefix of its predecessor where
+    that still gives a new one, so prefixes of other barcodes occur."""
+    rng = np.random.default_rng([seed, 0xBA2C])
+    out, seen = [], set()
+    if style == "10x":
+        while len(out) < n_cells:
+            b = _NUC[rng.integers(0, 4, size=16)].tobytes() + b"-1"
+            if b not in seen:
+                seen.add(b)
+                out.append(b)
+    elif style == "var":
+        while len(out) < n_cells:
+            b = _NUC[rng.integers(0, 4, size=int(rng.integers(1, 21)))].tobytes()
+            if len(out) % 3 == 2 and len(out[-1]) > 1:
+                pre = out[-1][:int(rng.integers(1, len(out[-1])))]
+                b = pre if pre not in seen else b
+            if b not in seen:
+                seen.add(b)
+                out.append(b)
+    else:
+        raise ValueError(f"style must be '10x' or 'var', not {style!r}")
+    return out
+
+
+def interleave_cells(records, names, secondary, cell_rec_off, barcodes, seed: int = BASE_SEED + 27, how: str = "uniform"):
+    """``shuffle_cell_records``' barcode-collated input as an UNCOLLATED input: the records of all cells interleaved,
+    each with its cell's barcode.  ``barcodes``: one per cell (``make_barcodes``).  ``how="uniform"``: a uniform
+    permutation of all records.  ``how="blocks"``: every cell's records are cut into runs of 1 to 8 and the runs of all
+    cells shuffled: a few records of a cell side by side, as a coordinate-sorted file interleaves cells.  Returns ``(records, names,
+    secondary, record_barcodes, perm)``: ``names`` and ``record_barcodes`` are ``(blob, offsets)`` pairs and ``perm[k]``
+    is the collated index of the record at input position k.  ``records`` / ``secondary`` may be None."""
+    from .em import gather_names
+    cell_rec_off = np.ascontiguousarray(cell_rec_off, dtype=np.int64)
+    n, n_cells = int(cell_rec_off[-1]), len(cell_rec_off) - 1
+    if len(barcodes) != n_cells:
+        raise ValueError("one barcode per cell")
+    rng = np.random.default_rng([seed, 0x1EAF])
+    if how == "uniform":
+        perm = rng.permutation(n)
+    elif how == "blocks":
+        starts = []
+        for c in range(n_cells):
+            at, end = int(cell_rec_off[c]), int(cell_rec_off[c + 1])
+            while at < end:
+                w = min(int(rng.integers(1, 9)), end - at)
+                starts.append((at, w))
+                at += w
+        pick = rng.permutation(len(starts))
+        perm = (np.concatenate([np.arange(starts[i][0], starts[i][0] + starts[i][1]) for i in pick]) if starts
+                else np.zeros(0, dtype=np.int64))
+    else:
+        raise ValueError(f"how must be 'uniform' or 'blocks', not {how!r}")
+    perm = perm.astype(np.int64)
+    cell_of = np.repeat(np.arange(n_cells), np.diff(cell_rec_off))[perm]
+    enc = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+    bc_off = np.zeros(n_cells + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in enc], out=bc_off[1:])
+    bc_blob = np.frombuffer(b"".join(enc), dtype=np.uint8)
+    return (None if records is None else records[perm], gather_names(names, perm),
+            None if secondary is None else np.asarray(secondary)[perm], gather_names((bc_blob, bc_off), cell_of), perm)
+
+
 @dataclass
 class SyntheticProjectedRecords:
     filters: dict                # the fields of oem_filters the records were made for

@@ -284,6 +284,25 @@ def csr_triplets(indptr, cols, vals) -> tuple:
 _MTX_BANNER = "%%MatrixMarket matrix coordinate real general\n% written by sprs\n"
 
 
+def cell_barcodes(barcodes, order, cell_rec_off) -> list:
+    """The cells' barcodes in result order, for `.barcodes.txt`: cell c's is the barcode of record
+    ``order[cell_rec_off[c]]``.  ``barcodes``: one per record in input order, whatever ``types.pack_read_names`` accepts;
+    ``order`` / ``cell_rec_off``: what ``em.collate_barcodes`` or ``em_cells_records_sparse(..., barcodes=)`` returned.
+    Returns a list of ``str`` (bytes above 0x7f as latin-1), what ``write_single_cell_output*`` take."""
+    import numpy as np
+    from .types import pack_read_names
+    n = len(barcodes[1]) - 1 if isinstance(barcodes, tuple) and len(barcodes) == 2 and not isinstance(barcodes[1], (str, bytes)) else len(barcodes)
+    blob, off = pack_read_names(barcodes, n)
+    order = np.asarray(order)
+    cell_rec_off = np.asarray(cell_rec_off, dtype=np.int64)
+    raw = blob.tobytes()
+    out = []
+    for c in range(len(cell_rec_off) - 1):
+        i = int(order[cell_rec_off[c]])
+        out.append(raw[int(off[i]):int(off[i + 1])].decode("latin-1"))
+    return out
+
+
 def _write_single_cell_side_files(output: str, info: dict, feature_names: Sequence[str],
                                   barcodes: Optional[Sequence[str]]) -> None:
     """What a single-cell run writes besides the matrix: `.meta_info.json`, `.features.txt` and, in row order,

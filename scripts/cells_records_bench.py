@@ -160,6 +160,72 @@ def names_leg(args, cr, res, save):
         del rec, blob, off, sec, keep
 
 
+def barcodes_leg(args, cr, res, save):
+    """The --barcodes leg: the slice with names, interleaved uniformly, with 10x barcodes.  (a) the one call
+    (oem_em_run_cells_records_barcodes_sparse); (b) the collate="host" join by stage -- collate_barcodes, the NumPy gathers
+    of records and of names, the names call; (c) oem_em_run_cells_records_names_sparse on the same data already
+    barcode-collated.  Also the PCIe floor of barcodes + names + records, the peak device memory and the stage times."""
+    import ctypes as C
+    from oarfish_amd import _lib
+    from oarfish_amd.em import gather_names
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+    rate = 57.3   # GB/s pinned, profiles/filter_device_bench.json
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    def run(rec, names, sec, bc=None, cro=None, collate="device"):
+        if bc is None:
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec, None, cro, names=names, secondary=sec, collate="device")
+        return oarfish_amd.em_cells_records_sparse(f, tl, rec, None, None, names=names, secondary=sec, barcodes=bc, collate=collate)
+
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        cell_bc = synth.make_barcodes(n, "10x")
+        rec, names, sec, bc, _ = synth.interleave_cells(rec0, names0, sec0, cro, cell_bc, how="uniform")
+        r = res[style] = dict(name_bytes=int(names[0].nbytes), record_bytes=int(rec.nbytes), barcode_bytes=int(bc[0].nbytes))
+        r["pcie_floor_s_at_57.3_gbs"] = round((names[0].nbytes + rec.nbytes + bc[0].nbytes) / (rate * 1e9), 4)
+        m = int(cro[min(args.warm_cells, n)])   # warm-up on the first records of the input
+        run(rec[:m], (names[0][:int(names[1][m])], names[1][:m + 1]), sec[:m], (bc[0][:int(bc[1][m])], bc[1][:m + 1]))
+        runs_a, runs_b, runs_c, stages = [], [], [], []
+        for k in range(args.runs):
+            os.environ["OEM_COLLATE_TIMING"] = "1" if k == 0 else "0"
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_a = clock(lambda: run(rec, names, sec, bc))
+                r["peak_device_bytes_during_the_call"] = int(pk.peak)
+            else:
+                dt, got_a = clock(lambda: run(rec, names, sec, bc))
+            runs_a.append(dt)
+            t_bc, (order_bc, cro_b) = clock(lambda: oarfish_amd.collate_barcodes(bc))
+            t_gr, rec_b = clock(lambda: rec[order_bc])
+            t_gn, names_b = clock(lambda: gather_names(names, order_bc))
+            sec_b = sec[order_bc]
+            t_nc, got_b = clock(lambda: run(rec_b, names_b, sec_b, cro=cro_b))
+            stages.append((t_bc, t_gr, t_gn, t_nc))
+            runs_b.append(sum(stages[-1]))
+            runs_c.append(clock(lambda: run(rec_b, names_b, sec_b, cro=cro_b))[0])
+            if k == 0:
+                assert np.array_equal(got_a[6], order_bc[got_b[6]]) and np.array_equal(got_a[7], cro_b)
+                assert np.array_equal(got_a[4], got_b[4]) and got_a[5] == got_b[5]
+                assert np.array_equal(got_a[0], got_b[0]) and np.array_equal(got_a[1], got_b[1])
+                r["n_cells"] = int(len(cro_b) - 1)
+            del got_a, got_b, rec_b, names_b
+            print(f"[bench] {style} run {k}: (a) {runs_a[-1]:.3f} s, (b) {runs_b[-1]:.3f} s = barcodes {t_bc:.3f} + records gather {t_gr:.3f} "
+                  f"+ names gather {t_gn:.3f} + names call {t_nc:.3f}, (c) {runs_c[-1]:.3f} s", flush=True)
+            r["one_call"], r["host_join"], r["names_call_on_collated_input"] = spread(runs_a), spread(runs_b), spread(runs_c)
+            best = min(range(len(runs_b)), key=lambda i: runs_b[i])
+            r["host_join_stages_of_best_run_s"] = dict(zip(("collate_barcodes", "numpy_gather_records", "numpy_gather_names", "names_call"),
+                                                           (round(x, 4) for x in stages[best])))
+            r["one_call_over_host_join"] = round(min(runs_a) / min(runs_b), 3)
+            r["one_call_minus_names_call_s"] = round(min(runs_a) - min(runs_c), 4)
+            save()
+        del rec, names, sec, bc, rec0, names0, sec0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=625)
@@ -169,13 +235,15 @@ def main():
     ap.add_argument("--runs", type=int, default=None, help="repeats per point (3; 5 with --names)")
     ap.add_argument("--models", type=int, nargs="*", default=[-1, 1])
     ap.add_argument("--names", action="store_true", help="the leg from names and records in input order")
+    ap.add_argument("--barcodes", action="store_true", help="the leg from records in any order: cells from barcodes")
     ap.add_argument("--styles", nargs="*", default=["uuid", "illumina"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names else 3
+        args.runs = 5 if args.names or args.barcodes else 3
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "cells_records_barcodes_bench.json" if args.barcodes else
+                                "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
     T, n = args.txps, args.cells
     t0 = time.perf_counter()
     cells = synth.make_cells(n, args.cell_reads, T, threads=16)
@@ -237,6 +305,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.barcodes:
+        barcodes_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     if args.names:
         names_leg(args, cr, res, save)
         print(json.dumps(res))
