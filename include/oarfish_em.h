@@ -795,6 +795,69 @@ int oem_em_run_cells_records_barcodes_sparse(
     uint32_t *out_kept /* capacity n_records, or NULL */,
     oem_cells_result **out);
 
+/* The bulk parser and oem_store_create_records in one call: parse_alignments (alignment_parser.rs:301-437) from the
+ * records and read names as a BAM reader produces them, in input order, to the resident store.  records (n_records),
+ * names / name_off and secondary are oem_collate_names' per-record arrays; the rule is oarfish_amd/csrc/oem_collate.h
+ * (the bulk parser):
+ *   - a record with OEM_REC_UNMAPPED takes no part (:367-370): it cuts no read, its name is never looked at (it may be
+ *     empty or hold a 0 byte), and a read made only of such records is no group, so no `no_mapping` entry either.
+ *     (oem_aln_record has no "mapped, but without a reference id" state, :377 and :410: nothing corresponds to it.)
+ *   - OEM_COLLATE_ADJACENT is the reference's parser: the surviving records in input order, a read a maximal run of
+ *     identical names among them (`A, unmapped, A` is one read of two).  OEM_COLLATE_SORT lifts the requirement that the
+ *     input be name-collated: the surviving records are sorted by oem_collate_names' rule as one cell, then cut.
+ *   - under OEM_COLLATE_ADJACENT with sort_check_num = N > 0 (--sort-check-num, prog_opts.rs:558-561, 100 000 there) the
+ *     first min(N, n_groups) groups are checked as at :396-408: if a checked group has the name of an earlier group the
+ *     call fails with OEM_ERR_STATE, naming the smallest such group, the input index of its first record, that of the
+ *     earlier group's first record, and that OEM_COLLATE_SORT accepts such input.  A repeat at a group index >= N is
+ *     accepted, as by the reference; N = 0 is no check; under OEM_COLLATE_SORT there is nothing to check.
+ *   - the filter is oem_store_create_records', over the groups in order; row r of the store is the r-th group with
+ *     out_kept > 0 and its name the name of the first record of that group (name_vec, :341-351).
+ *
+ * The call gives what the caller gets by joining these steps by hand: drop the unmapped records, their names and flags
+ * on the host; oem_collate_names on what is left as ONE cell (cell_rec_off = {0, n_parsed}); the records put into that
+ * order; oem_store_create_records with the collation's group_off and the same opts, model, bin_width and growth_rate.
+ * Exactly equal to that join, for every weight_coding and both layout_build values: out_order mapped back to input
+ * indices (n_parsed entries: out_order[k] is the caller's index of the record at position k), out_group_off
+ * (n_groups + 1 entries), out_kept (n_groups), the discard table, every field of out_info and the row names
+ * (out_row_name_off: n_reads + 1 offsets from 0 into out_row_names).  The store is that store: its weights are
+ * bit-identical, EM results agree as oem_store_create_records states for its own long way round.  Every output but `out`
+ * may be NULL, out_row_names and out_row_name_off only together.
+ *
+ * oem_parse_info: n_unmapped records skipped, n_parsed = n_records - n_unmapped, n_groups reads among them, n_reads
+ * rows of the store, unique_alignments = groups with out_kept == 1 (:386-388), n_checked groups the collation check
+ * looked at.
+ *
+ * The whole input is resident on the device until the filter has run: 40 bytes a record, the names and 8 bytes of
+ * offsets a record (the records twice for the length of their gather), 4 more bytes a record when there are unmapped
+ * records; the collation holds about 150 bytes a surviving record while it runs and releases them before the records
+ * are gathered.  Running out of device memory is OEM_ERR_OOM with everything released.
+ *
+ * Errors.  Before any device use, OEM_ERR_ARG: those of oem_store_create_records on filters, txp_len, n_txps, model,
+ * bin_width and opts; those of oem_collate_names on names, name_off and mode; records NULL with n_records > 0; one of
+ * out_row_names / out_row_name_off without the other; n_records > 2^31 - 2 (one collation batch).  Found on the device:
+ * a surviving record with an empty name or a 0 byte in its name (OEM_ERR_ARG naming the first such record by its input
+ * index); the collation check (OEM_ERR_STATE, above); a mapped record whose ref_id is not below n_txps (OEM_ERR_ARG
+ * naming the input index); an alignment outside its transcript under a coverage model (OEM_ERR_STATE); 2^32 or more
+ * kept alignments (OEM_ERR_ARG).  The host loop takes the groups, with the same result, when
+ * oem_builder_add_groups_device's would.  Without a device: OEM_ERR_NO_DEVICE.  *out = NULL on any failure; the other
+ * outputs are then unspecified. */
+typedef struct {
+    uint64_t n_unmapped, n_parsed, n_groups, n_reads, unique_alignments, n_checked, reserved[2];
+} oem_parse_info;
+int oem_store_create_records_names(
+    const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+    const oem_aln_record *records, uint64_t n_records,
+    const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+    uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */, uint64_t sort_check_num,
+    uint32_t bin_width, int model, double growth_rate, int device, const oem_store_opts *opts,
+    uint32_t *out_order          /* capacity n_records; n_parsed written; or NULL */,
+    uint64_t *out_group_off      /* capacity n_records + 1; n_groups + 1 written; or NULL */,
+    uint32_t *out_kept           /* capacity n_records; n_groups written; or NULL */,
+    uint8_t *out_row_names       /* capacity name_off[n_records]; or NULL */,
+    uint64_t *out_row_name_off   /* capacity n_records + 1; n_reads + 1 written; or NULL (together with out_row_names) */,
+    oem_discard_table *out_discard /* or NULL */, oem_parse_info *out_info /* or NULL */,
+    oem_store **out);
+
 /* A per-cell SESSION: the caller pushes cells one by one, from any number of threads, as they become available
  * (single_cell.rs:96-193: N workers each pop one cell and build its private store).  The library stages the cells,
  * cuts them into groups, runs every group through the batched per-cell driver while later cells still arrive, and

@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "oem_abi_version", "oem_last_error", "oem_device_count",
     "oem_store_create", "oem_store_destroy", "oem_store_dims", "oem_store_bytes", "oem_store_info", "oem_store_set_option",
     "oem_builder_create", "oem_builder_destroy", "oem_builder_add_group", "oem_builder_add_groups",
-    "oem_builder_add_groups_device", "oem_store_create_records", "oem_builder_add_projected_group",
+    "oem_builder_add_groups_device", "oem_store_create_records", "oem_store_create_records_names", "oem_builder_add_projected_group",
     "oem_builder_add_projected_groups", "oem_builder_add_projected_groups_device", "oem_store_create_projected_records",
     "oem_builder_dims",
     "oem_builder_discard_table", "oem_builder_export", "oem_builder_coverage_probs",
@@ -146,6 +146,11 @@ class CellsStreamOptsC(C.Structure):
 class RecordsStreamOptsC(C.Structure):
     _fields_ = [("n_txps", C.c_uint32), ("device", C.c_int32), ("bin_width", C.c_uint32), ("model", C.c_int32),
                 ("growth_rate", C.c_double), ("max_staged_records", C.c_uint64), ("reserved", C.c_uint32 * 4)]
+
+
+class ParseInfoC(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_unmapped", "n_parsed", "n_groups", "n_reads", "unique_alignments", "n_checked")] \
+        + [("reserved", C.c_uint64 * 2)]
 
 
 class StoreOptsC(C.Structure):
@@ -240,6 +245,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_em_run_cells_records_barcodes_sparse.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, u32, u32, i32, f64, i32,
                                                            u32, f64, vp, vp, C.POINTER(u64), vp, C.POINTER(u64), vp, vp,
                                                            C.POINTER(vp)]
+    L.oem_store_create_records_names.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, u32, u64, u32, i32, f64, i32, vp, vp, vp, vp, vp,
+                                                 vp, vp, vp, C.POINTER(vp)]
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
     L.oem_cells_stream_push_records.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
@@ -312,6 +319,8 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.oem_debug_records_stream_finish_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.oem_debug_records_stream_last_join.argtypes = [vp]
+        L.oem_debug_records_names_last_call.argtypes = [vp]
+        L.oem_test_parse_bulk_host.argtypes = [vp, u64, vp, vp, vp, u32, u64, vp, vp, vp]
         _testing = L
     return _testing
 

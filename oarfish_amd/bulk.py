@@ -7,7 +7,9 @@ model of :103-108 (`logistic_prob` + `normalize_read_probs` when `model_coverage
 and in the same call that creates the resident store (`InMemoryAlignmentStore.model_coverage_on_device`).
 Alignment parsing comes before this (the caller); the filtering is `builder.StoreBuilder` (one read or a batch of
 reads per call, on the host or on the device) or, from the parsed records straight to the resident store in one device
-call, `DeviceStore.from_records` (oem_store_create_records).  KDE is not supported.
+call, `DeviceStore.from_records` (oem_store_create_records).  `quantify_bulk_alignments_from_records` is the whole of
+`quantify_bulk_alignments_from_bam` (bulk.rs:212-259) from the parsed records on: the parser itself
+(alignment_parser.rs:301-437) runs on the device too (`DeviceStore.from_named_records`).  KDE is not supported.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import numpy as np
 
 from . import writers
 from .em import bootstrap, em, em_par
-from .types import EMInfo, InMemoryAlignmentStore, TranscriptInfo
+from .types import DeviceStore, EMInfo, InMemoryAlignmentStore, TranscriptInfo
 
 
 def read_short_quant_vec(short_read_path: str, txps_name: Sequence[str]) -> np.ndarray:
@@ -109,4 +111,54 @@ def perform_inference_and_write_output(store: InMemoryAlignmentStore, txps_name:
         probs = dev.assignment_probs(counts, args.display_thresh)
         writers.write_out_prob(args.output, store.boundaries, store.alignments, probs, read_names, txps_name,
                                args.display_thresh, compressed=args.prob_compressed)
+    return counts
+
+
+def quantify_bulk_alignments_from_records(filters, txps_name: Sequence[str], txp_lens: Sequence[int], records, names,
+                                          args: BulkArgs, secondary=None, mode: str = "adjacent",
+                                          sort_check_num: int = 100_000, coverage: Optional[str] = None,
+                                          bin_width: int = 100, growth_rate: float = 2.0) -> np.ndarray:
+    """`quantify_bulk_alignments_from_bam` (bulk.rs:212-259) from the parsed records on: ``records``, their read
+    ``names`` and ``secondary`` flags in input order go through ``DeviceStore.from_named_records`` (the parser of
+    alignment_parser.rs:301-437, the filter and, with ``coverage`` "logistic" / "binomial", the coverage model of
+    bulk.rs:103-108, in one device call), then the tail of ``perform_inference_and_write_output``: the EM by thread count
+    (:155-159), aux counts, `.quant` / `.ambig_info.tsv` / `.meta_info.json`, bootstraps, and `.prob` with the read names
+    the parser collected.  The files are those of ``perform_inference_and_write_output`` on the store the host builder
+    makes of the same groups.  The resident store has no host CSR, so the host `.prob` writer (``prob_on_device``
+    False) first runs the host filter once more over the collated records for the rows' transcript ids;
+    ``prob_on_device`` formats the body from the resident store and needs none of that."""
+    from .builder import StoreBuilder
+    txp_len = np.asarray(txp_lens, dtype=np.uint64)
+    dev, _kept, _discard, parse = DeviceStore.from_named_records(
+        filters, txp_len, records, names, secondary=secondary, mode=mode, sort_check_num=sort_check_num, coverage=coverage,
+        bin_width=bin_width, growth_rate=growth_rate, device=args.device)
+    with dev:
+        counts, run = dev.em_run(None, args.max_em_iter, args.convergence_thresh, 50 if args.threads <= 4 else 1)  # bulk.rs:155-159
+        unique, total = dev.aux_counts()                                                     # bulk.rs:161
+        info = {"num_aligned_reads": dev.n_reads, "total_alignments": dev.nnz,
+                "em_max_iter": args.max_em_iter, "em_convergence_thresh": args.convergence_thresh,
+                "threads": args.threads, "num_bootstraps": args.num_bootstraps, "output": args.output,
+                "filter_options": {"model_coverage": coverage is not None},
+                "em_iterations": run.niter}
+        info.update(args.extra_info)
+        if args.quant_on_device:                                                             # bulk.rs:168-174
+            writers.write_output_device(args.output, info, txps_name, txp_lens, counts, (unique, total), device=args.device)
+        else:
+            writers.write_output(args.output, info, txps_name, txp_lens, counts, unique, total)
+        if args.num_bootstraps > 0:                                                          # bulk.rs:178-193
+            breps, _ = dev.bootstrap(args.num_bootstraps, args.seed, None, None, args.max_em_iter, args.convergence_thresh)
+            writers.write_infrep_file(args.output, [breps[b] for b in range(args.num_bootstraps)])
+        if args.write_assignment_probs:                                                      # bulk.rs:196-207
+            if args.prob_on_device:
+                writers.write_out_prob_device(args.output, dev, counts, parse.read_names, txps_name, args.display_thresh,
+                                              compressed=args.prob_compressed)
+                return counts
+            with StoreBuilder(filters, txp_len) as hb:   # the rows' transcript ids: the host filter over the same groups
+                hb.add_groups(np.asarray(records)[parse.order], parse.group_off)
+                row_ptr, tid = hb.export()[:2]
+            blob, off = parse.read_names
+            read_names = [bytes(blob[int(off[r]):int(off[r + 1])]).decode("utf-8", "replace") for r in range(dev.n_reads)]
+            probs = dev.assignment_probs(counts, args.display_thresh)
+            writers.write_out_prob(args.output, row_ptr, tid, probs, read_names, txps_name, args.display_thresh,
+                                   compressed=args.prob_compressed)
     return counts

@@ -279,15 +279,6 @@ struct NamesSlot {
     std::vector<uint32_t> kept;                      // n_groups (if asked for)
 };
 
-// The records [r0, r0 + m) of the caller into d (input order) through the upload lanes.
-int upload_records(const oem_aln_record *records, uint64_t m, oem_aln_record *d)
-{
-    std::vector<uint64_t> cut;
-    for (uint64_t r = 0; r < m; r += kUploadChunkRecords) cut.push_back(r);
-    cut.push_back(m);
-    return filter_upload_measure<oem_aln_record>(records, d, cut.data(), cut.size() - 1, 1, nullptr, [](hipStream_t, uint64_t, uint64_t) {});
-}
-
 // The cells [c0, c1) of the call: collate, gather, filter and run.  rg: the group's place and outputs (records,
 // offsets and out_kept are filled in here).
 int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &rf, const NamesCall &nc, uint32_t c0, uint32_t c1,
@@ -460,6 +451,36 @@ thread_local double g_cells_barcodes_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 } // namespace
 
 void cells_barcodes_last_call(double *out8) { std::memcpy(out8, g_cells_barcodes_last, sizeof g_cells_barcodes_last); }
+
+// The records [r0, r0 + m) of the caller into d (input order) through the upload lanes.
+int upload_records(const oem_aln_record *records, uint64_t m, oem_aln_record *d)
+{
+    std::vector<uint64_t> cut;
+    for (uint64_t r = 0; r < m; r += kUploadChunkRecords) cut.push_back(r);
+    cut.push_back(m);
+    return filter_upload_measure<oem_aln_record>(records, d, cut.data(), cut.size() - 1, 1, nullptr, [](hipStream_t, uint64_t, uint64_t) {});
+}
+
+// k_order_compose and k_records_gather for oem_records_names.hip, on the null stream, which is left idle
+int order_compose(uint64_t m, const uint32_t *d_outer, uint32_t *d_order)
+{
+    if (!m) return OEM_OK;
+    hipLaunchKernelGGL(k_order_compose, dim3((uint32_t)((m + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, m, d_outer, d_order);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
+
+int records_gather(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_src, oem_aln_record *d_dst)
+{
+    if (!m) return OEM_OK;
+    const uint64_t n_words = m * kRecordWords;
+    hipLaunchKernelGGL(k_records_gather, dim3((uint32_t)((n_words + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, n_words, d_order, 0u,
+                       (const uint64_t *)d_src, (uint64_t *)d_dst);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
 
 int records_filter_setup(const char *who, const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps, RecordsFilter *rf)
 {

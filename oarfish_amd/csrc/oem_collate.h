@@ -37,6 +37,31 @@
 //     number of distinct barcodes.
 // A barcode is never empty (the reference bails when CB is missing: single_cell.rs:203, alignment_parser.rs:150) and
 // holds no 0 byte: the conditions names carry, and what lets the same zero-padded keys sort them.
+//
+// The bulk parser (parse_bulk_host below, oem_store_create_records_names): alignment_parser.rs:301-437, parse_alignments,
+// from records and read names in input order to the groups AlignmentFilters::filter takes.
+//   skip     a record with OEM_REC_UNMAPPED takes no part in anything below (:367-370): it cuts no read, its name is
+//            never looked at (it may be empty or hold a 0 byte), and a read made only of such records is no group at
+//            all, so it is no `no_mapping` entry of the discard table either.  n_unmapped counts these records,
+//            n_parsed = n_records - n_unmapped.  (The reference also drops a mapped record that has no reference id,
+//            :377 and :410; oem_aln_record has no such state -- every record that is not unmapped carries a ref_id --
+//            so there is nothing to build for it.)
+//   names    the names of the surviving records are not empty and hold no 0 byte; the first violation, by the record's
+//            index in the caller's input, is an error.
+//   order    kCollateAdjacent is the reference's parser: `order` is the surviving input indices, ascending, and a group
+//            is a maximal run of identical names in it -- `A, unmapped, A` is one group of two whatever the unmapped
+//            record is called.  kCollateSort lifts the requirement that the input be name-collated: `order` is the
+//            surviving indices sorted by the name rule above (name bytes, primary before secondary, index), all of
+//            them as one cell, and the groups are cut the same way.
+//   check    under kCollateAdjacent with sort_check_num = N > 0 the first min(N, n_groups) groups are checked (:396-408,
+//            prog_opts.rs:558-561, N = 100 000 there): if the name of a checked group g equals the name of an earlier
+//            group the input is not name-collated and the call fails, naming the smallest such g, the input index of
+//            its first record and that of the earlier group's first record.  A repeat at a group index >= N is not an
+//            error (the reference's behaviour), N = 0 is no check, and under kCollateSort there is nothing to check.
+//   filter   oem_filter.h unchanged over the groups in order; row r of the store is the r-th group with kept > 0, its
+//            name the name of the first record of its group (the name_vec of :341-351), and unique_alignments is the
+//            number of groups with kept == 1 (:386-388: after add_group returned true records_for_read holds what
+//            filter retained, oarfish_types.rs:987, :1121).
 #pragma once
 
 #include <stdint.h>
@@ -181,6 +206,73 @@ inline uint64_t collate_barcodes_host(const uint8_t *barcodes, const uint64_t *b
     cell_rec_off[n_runs] = n_records;
     *n_cells = n_runs;
     return kCollateNoRecord;
+}
+
+constexpr uint32_t kRecUnmapped = 1u; // OEM_REC_UNMAPPED
+
+// What the host walk of the bulk parser finds besides order and group_off.
+struct ParseBulk {
+    uint64_t n_unmapped = 0, n_parsed = 0, n_groups = 0, n_checked = 0;
+    uint64_t bad_record = kCollateNoRecord;   // the first surviving record with a bad name (input index); zero_byte tells which
+    bool zero_byte = false;
+    uint64_t repeat_group = kCollateNoRecord; // the collation check: the smallest checked group whose name an earlier group has,
+    uint64_t repeat_record = 0, earlier_record = 0; // the input indices of its first record and of the earlier group's
+};
+
+// The host walk of the bulk rule.  Rec: any record with a `flags` word (oem_aln_record).  order (capacity n_records;
+// n_parsed written), group_off (capacity n_records + 1; n_groups + 1 written).  With a bad name nothing but the counts
+// and bad_record is filled; with a repeat everything is.
+template <typename Rec>
+inline ParseBulk parse_bulk_host(const Rec *records, uint64_t n_records, const uint8_t *names, const uint64_t *name_off,
+                                 const uint8_t *secondary, uint32_t mode, uint64_t sort_check_num, uint32_t *order, uint64_t *group_off)
+{
+    ParseBulk pb;
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n_records; ++i) {
+        if (records[i].flags & kRecUnmapped) continue;
+        const uint64_t len = name_off[i + 1] - name_off[i];
+        const bool z = len && memchr(names + name_off[i], 0, len);
+        if ((!len || z) && pb.bad_record == kCollateNoRecord) {
+            pb.bad_record = i;
+            pb.zero_byte = z;
+        }
+        order[m++] = (uint32_t)i;
+    }
+    pb.n_parsed = m;
+    pb.n_unmapped = n_records - m;
+    if (pb.bad_record != kCollateNoRecord) return pb;
+    if (mode == kCollateSort)
+        std::sort(order, order + m, [&](uint32_t i, uint32_t j) { return collate_before(names, name_off, secondary, i, j); });
+    auto same = [&](uint32_t i, uint32_t j) {
+        return collate_name_cmp(names + name_off[i], name_off[i + 1] - name_off[i], names + name_off[j], name_off[j + 1] - name_off[j]) == 0;
+    };
+    uint64_t g = 0;
+    for (uint64_t p = 0; p < m; ++p)
+        if (p == 0 || !same(order[p], order[p - 1])) group_off[g++] = p;
+    group_off[g] = m;
+    pb.n_groups = g;
+    if (mode == kCollateAdjacent && sort_check_num) {
+        const uint64_t nc = sort_check_num < g ? sort_check_num : g;
+        pb.n_checked = nc;
+        std::vector<uint64_t> by_name(nc); // the checked groups sorted by the name of their head, then by group index
+        for (uint64_t k = 0; k < nc; ++k) by_name[k] = k;
+        auto head = [&](uint64_t k) { return order[group_off[k]]; };
+        std::sort(by_name.begin(), by_name.end(), [&](uint64_t a, uint64_t b) {
+            const uint32_t i = head(a), j = head(b);
+            const int c = collate_name_cmp(names + name_off[i], name_off[i + 1] - name_off[i], names + name_off[j], name_off[j + 1] - name_off[j]);
+            return c ? c < 0 : a < b;
+        });
+        for (uint64_t k = 1; k < nc; ++k) { // a run's second member is the first group to repeat the run's name
+            if (!same(head(by_name[k]), head(by_name[k - 1]))) continue;
+            if (k >= 2 && same(head(by_name[k - 1]), head(by_name[k - 2]))) continue;
+            if (by_name[k] < pb.repeat_group) {
+                pb.repeat_group = by_name[k];
+                pb.repeat_record = head(by_name[k]);
+                pb.earlier_record = head(by_name[k - 1]);
+            }
+        }
+    }
+    return pb;
 }
 
 } // namespace oem

@@ -85,6 +85,13 @@ void collate_barcodes_set_last(const double *in8);
 // [5] the groups on their workers; under OEM_COLLATE_TIMING from HIP events [6] the name uploads, [7] the validate kernels.
 void cells_barcodes_last_call(double *out8);
 
+// oem_cells_records.hip: the caller's records [0, m) into d through the upload lanes; order[k] = outer[order[k]]
+// (k_order_compose); dst[k] = src[order[k]] over 40-byte records (k_records_gather).  The last two run on the null
+// stream and leave it idle.
+int upload_records(const oem_aln_record *records, uint64_t m, oem_aln_record *d);
+int order_compose(uint64_t m, const uint32_t *d_outer, uint32_t *d_order);
+int records_gather(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_src, oem_aln_record *d_dst);
+
 uint64_t collate_chunk_bytes();   // the upload chunk (testing build: OEM_COLLATE_CHUNK_BYTES)
 uint64_t collate_batch_records(); // records per batch of oem_collate_names (testing build: OEM_COLLATE_BATCH_RECORDS)
 constexpr uint64_t kCollateMaxBatch = (1ull << 31) - 2; // a single cell beyond this is refused (the scans take m + 1 items as an int)

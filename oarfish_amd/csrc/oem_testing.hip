@@ -213,6 +213,40 @@ extern "C" int oem_test_collate_barcodes_host(const uint8_t *barcodes, const uin
     OEM_API_END("oem_test_collate_barcodes_host")
 }
 
+// out[0..7] = this thread's last oem_store_create_records_names: [0] 1 if k_records_gather ran, [1] 1 if the survivors'
+// names were gathered, [2] the groups the collation check looked at, [3] 1 if the host loop took the groups
+namespace oem { void records_names_last_call(double *out8); }
+extern "C" int oem_debug_records_names_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_records_names_last_call: NULL argument");
+    records_names_last_call(out);
+    return OEM_OK;
+}
+
+// Test hook: the host walk of oem_collate.h's bulk rule (parse_bulk_host) with oem_store_create_records_names' input
+// arguments (checked by the caller).  out_order (capacity n_records), out_group_off (capacity n_records + 1), out_info:
+// n_unmapped, n_parsed, n_groups, n_checked, then the repeat's group, record and earlier record when the collation
+// check fails (OEM_ERR_STATE).  A bad name is OEM_ERR_ARG naming the record.
+extern "C" int oem_test_parse_bulk_host(const oem_aln_record *records, uint64_t n_records, const uint8_t *names, const uint64_t *name_off,
+                                        const uint8_t *secondary, uint32_t mode, uint64_t sort_check_num, uint32_t *out_order,
+                                        uint64_t *out_group_off, uint64_t *out_info)
+{
+    OEM_API_BEGIN
+    if (!name_off || !out_order || !out_group_off || !out_info || (n_records && (!names || !records)))
+        return fail(OEM_ERR_ARG, "oem_test_parse_bulk_host: NULL argument");
+    const ParseBulk pb = parse_bulk_host(records, n_records, names, name_off, secondary, mode, sort_check_num, out_order, out_group_off);
+    const uint64_t info[7] = {pb.n_unmapped, pb.n_parsed, pb.n_groups, pb.n_checked, pb.repeat_group, pb.repeat_record, pb.earlier_record};
+    std::memcpy(out_info, info, sizeof info);
+    if (pb.bad_record != kCollateNoRecord)
+        return fail(OEM_ERR_ARG, pb.zero_byte ? "oem_test_parse_bulk_host: the name of record %llu contains a 0 byte"
+                                              : "oem_test_parse_bulk_host: record %llu has an empty name", (unsigned long long)pb.bad_record);
+    if (pb.repeat_group != kCollateNoRecord)
+        return fail(OEM_ERR_STATE, "oem_test_parse_bulk_host: group %llu (first record %llu) has the name of an earlier group (first record %llu)",
+                    (unsigned long long)pb.repeat_group, (unsigned long long)pb.repeat_record, (unsigned long long)pb.earlier_record);
+    return OEM_OK;
+    OEM_API_END("oem_test_parse_bulk_host")
+}
+
 // Test hook: the host build of oem_shortest_f64.h.  The texts of the n finite f64 with these bits, one after the other
 // in `text`; off[i] .. off[i + 1] are the bytes of value i (off has n + 1 entries, from the length function; the
 // emitter must end where it says).  OEM_ERR_ARG for a value that is not finite or a text that would pass `cap`.

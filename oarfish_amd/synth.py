@@ -555,6 +555,42 @@ def _group_names(n_groups: int, style: str, seed: int):
     return per_group
 
 
+def make_named_records(synthetic_records: SyntheticRecords, style: str = "uuid", seed: int = BASE_SEED + 28,
+                       unmapped_rate: float = 0.0, shuffle: bool = False):
+    """``make_records``' groups as a BAM reader hands them to the bulk parser (alignment_parser.rs:301-437): every record
+    with its read's name (``make_record_names``), the first record of a group the read's primary alignment and the
+    others carrying the secondary flag.  ``unmapped_rate``: that many extra UNMAPPED records per record, sprinkled inside
+    and between the reads, half of them with a name of their own and half with an empty name -- the parser skips them
+    before it groups, so they cut no read.  ``shuffle``: the whole input permuted (what ``mode="sort"`` is for).
+    Returns ``(records, names, secondary)`` in input order, ``names`` a ``(blob, offsets)`` pair: the input of
+    ``DeviceStore.from_named_records``.  A pure function of its arguments."""
+    from .builder import REC_UNMAPPED
+    sr = synthetic_records
+    group_off = np.ascontiguousarray(sr.group_off, dtype=np.uint64)
+    sizes = np.diff(group_off).astype(np.int64)
+    n = int(group_off[-1])
+    rows = np.repeat(_group_names(len(sizes), style, seed), sizes, axis=0)
+    records = sr.records[:n]
+    secondary = np.ones(n, dtype=np.uint8)
+    secondary[group_off[:-1][sizes > 0].astype(np.int64)] = 0
+    rng = np.random.default_rng([seed, 0x0A3ED])
+    k = int(round(float(unmapped_rate) * n))
+    if k:
+        at = np.sort(rng.integers(0, n + 1, size=k))          # an extra record goes in front of record at[j]
+        extra = np.zeros(k, dtype=records.dtype)
+        extra["ref_id"] = 0xFFFFFFFF
+        extra["flags"] = REC_UNMAPPED
+        extra_rows = _group_names(k, style, seed + 1)
+        extra_rows[rng.random(k) < 0.5] = 0                     # half of them have no name at all
+        records = np.insert(records, at, extra)
+        rows = np.insert(rows, at, extra_rows, axis=0)
+        secondary = np.insert(secondary, at, np.zeros(k, dtype=np.uint8))
+    if shuffle:
+        perm = rng.permutation(len(records))
+        records, rows, secondary = records[perm], rows[perm], secondary[perm]
+    return np.ascontiguousarray(records), _flatten_names(rows), np.ascontiguousarray(secondary)
+
+
 def shuffle_cell_records(cell_records: SyntheticCellRecords, seed: int = BASE_SEED + 25, style: str = "uuid", threads: int = 1,
                          with_records: bool = True):
     """``make_cell_records``' cells as a barcode-collated input holds them: every cell's records permuted, each with its

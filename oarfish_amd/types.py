@@ -223,6 +223,69 @@ class DeviceStore:
         return cls._adopt(L, h, len(txp_len), device), kept, _b.discard_dict(dt)
 
     @classmethod
+    def from_named_records(cls, filters, txp_len, records, names, secondary=None, mode: str = "adjacent",
+                           sort_check_num: int = 100_000, coverage: Optional[str] = None, bin_width: int = 100,
+                           growth_rate: float = 2.0, device: int = 0, reorder_rows: int = 0, window_cap: int = 0,
+                           layout_build: int = 0, weight_coding: int = 0):
+        """Records and read names in input order -> resident store in one device call (oem_store_create_records_names):
+        the reference's bulk parser (alignment_parser.rs:301-437) and ``from_records`` joined on the GPU.  Unmapped
+        records are skipped before the reads are cut; ``mode="adjacent"`` is the reference's parser (name-collated input,
+        refused with OEM_ERR_STATE when one of the first ``sort_check_num`` reads repeats an earlier name; 0 = no check),
+        ``mode="sort"`` collates input in any order by read name on the device.  ``names``: one per record, a sequence of
+        ``str`` / ``bytes`` or a ``(blob, offsets)`` pair; ``secondary``: one flag per record, or None.
+
+        Returns ``(store, kept, discard_table, parse)``: the first three as ``from_records`` returns them for the groups
+        of the parsed input; ``parse`` has ``order`` (input indices of the surviving records, collated), ``group_off``
+        (positions of ``order`` where a read starts, then ``n_parsed``), ``read_names`` (the names of the store's rows as
+        a ``(blob, offsets)`` pair, what ``assignment_text`` and ``writers.write_out_prob_device`` take as is),
+        ``n_unmapped``, ``n_parsed``, ``n_groups``, ``n_reads``, ``unique_alignments`` and ``n_checked``."""
+        from types import SimpleNamespace
+
+        from . import builder as _b
+        modes = {"sort": _lib.OEM_COLLATE_SORT, "adjacent": _lib.OEM_COLLATE_ADJACENT}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}, not {mode!r}")
+        fc = _b.filters_c(filters)
+        txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
+        records = np.ascontiguousarray(records, dtype=_b.ALN_RECORD)
+        n = len(records)
+        packed = isinstance(names, tuple) and len(names) == 2 and not isinstance(names[1], (str, bytes))
+        if (len(names[1]) - 1 if packed else len(names)) != n:
+            raise ValueError("names must have one entry per record")
+        blob, off = pack_read_names(names, n)
+        sec = None
+        if secondary is not None:
+            sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
+            if len(sec) != n:
+                raise ValueError("secondary must have one entry per record")
+        if n and not len(blob):
+            blob = np.zeros(1, dtype=np.uint8)   # (every name is empty: the call says so)
+        order = np.empty(max(n, 1), dtype=np.uint32)
+        group_off = np.empty(n + 1, dtype=np.uint64)
+        kept = np.empty(max(n, 1), dtype=np.uint32)
+        row_blob = np.empty(max(int(off[n]), 1), dtype=np.uint8)
+        row_off = np.empty(n + 1, dtype=np.uint64)
+        dt, pi = _lib.DiscardTableC(), _lib.ParseInfoC()
+        o = _b.store_opts(reorder_rows, window_cap, layout_build, weight_coding)
+        L = _lib.lib()
+        h = C.c_void_p()
+        rc = L.oem_store_create_records_names(C.addressof(fc), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
+                                              blob.ctypes.data if n else None, off.ctypes.data,
+                                              None if sec is None or not n else sec.ctypes.data, modes[mode], int(sort_check_num),
+                                              bin_width, _b._model_code(coverage), growth_rate, int(device), C.addressof(o),
+                                              order.ctypes.data, group_off.ctypes.data, kept.ctypes.data, row_blob.ctypes.data,
+                                              row_off.ctypes.data, C.addressof(dt), C.addressof(pi), C.byref(h))
+        if rc != _lib.OEM_OK:
+            msg = L.oem_last_error()
+            raise _lib.OemError(rc, msg.decode("utf-8", "replace") if msg else "")
+        row_off = row_off[:pi.n_reads + 1].copy()
+        parse = SimpleNamespace(order=order[:pi.n_parsed].copy(), group_off=group_off[:pi.n_groups + 1].copy(),
+                                read_names=(row_blob[:int(row_off[-1])].copy(), row_off), n_unmapped=int(pi.n_unmapped),
+                                n_parsed=int(pi.n_parsed), n_groups=int(pi.n_groups), n_reads=int(pi.n_reads),
+                                unique_alignments=int(pi.unique_alignments), n_checked=int(pi.n_checked))
+        return cls._adopt(L, h, len(txp_len), device), kept[:pi.n_groups].copy(), _b.discard_dict(dt), parse
+
+    @classmethod
     def from_projected_records(cls, filters, txp_len, records, group_off, read_len, beta: float = 10.0,
                                prob_source="similarity", coverage: Optional[str] = None, bin_width: int = 100,
                                growth_rate: float = 2.0, device: int = 0, reorder_rows: int = 0, window_cap: int = 0,
