@@ -961,6 +961,7 @@ typedef struct {
                                                             over the pushing threads */
 #define OEM_RECORDS_STREAM_INFO_HOST_BATCHES 6u          /* batches the host loop took (a score beyond +-2^24, or a
                                                             score_prob_denom without a table) */
+#define OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES 7u        /* a names session, after finish: bytes of the rows' names */
 
 /* Argument errors (opts, filters, txp_len or out NULL, n_txps = 0, a model outside -1 .. 1, bin_width = 0 under a
  * model, a non-zero reserved word) are reported before any device is touched; without a device the call returns
@@ -993,6 +994,64 @@ int oem_records_stream_info(const oem_records_stream *s, uint32_t key, uint64_t 
 /* NULL: no-op.  Before finish: cancels -- batches not yet started are dropped, the batch on the device runs to its end,
  * the worker is joined.  No push may be in flight. */
 void oem_records_stream_destroy(oem_records_stream *s);
+
+/* The NAMES form of the session: oem_store_create_records_names for a caller that never holds all records or names at
+ * once (parse_alignments walks a BAM reader record by record).  Batches are records and their read names in input
+ * order, cut at ANY record positions -- a read may straddle two batches, or any number of them.
+ *
+ * The contract.  Let R, names, name_off be the accepted batches concatenated in ticket order.  finish_names gives
+ * exactly what oem_store_create_records_names(filters, txp_len, n_txps, R, names, name_off, secondary = NULL,
+ * OEM_COLLATE_ADJACENT, sort_check_num, ...) gives with the session's filters, txp_len, bin_width, model and
+ * growth_rate and finish's opts, however the input was cut into batches, cuts inside a read included: the store (CSR
+ * and weights bit for bit), out_group_off, out_kept, the discard table, every field of oem_parse_info, the row names and
+ * their offsets.  out_order has no session form: under OEM_COLLATE_ADJACENT it is the ascending input indices of the
+ * records without OEM_REC_UNMAPPED, which the caller already has.  How a batch's surviving records attach to the open
+ * read is stated once, in oarfish_amd/csrc/oem_collate.h (ParseBulkStream): the open read -- the trailing run of one
+ * name among the survivors so far -- is carried on the device from batch to batch; a batch's first run joins it when
+ * the names are equal byte for byte; a batch closes every run but its last; a batch without a survivor changes nothing;
+ * finish closes the open read.  A record's index in messages is session-global: it counts all records of all accepted
+ * batches in ticket order, unmapped ones included, in 64 bits.
+ *
+ * oem_records_stream_set_names turns a fresh session into a names session (oem_records_stream_opts has no room for the
+ * parameter: its reserved words stay 0).  After a push, after finish, or a second time: OEM_ERR_STATE.  On a names
+ * session oem_records_stream_push and oem_records_stream_finish return OEM_ERR_STATE; on a plain one
+ * oem_records_stream_push_names and oem_records_stream_finish_names do. */
+int oem_records_stream_set_names(oem_records_stream *s, uint64_t sort_check_num);
+/* One batch: records (n_records) with names / name_off as oem_store_create_records_names takes them for the whole
+ * input.  There is no `secondary` argument: only OEM_COLLATE_SORT reads it, and a session cannot sort what it has not
+ * seen.  Thread-safe; tickets, back-pressure (max_staged_records, counted in records) and the reuse of staging memory
+ * are oem_records_stream_push's.  Checked on the calling thread before the session is touched: name_off present,
+ * starting at 0 and not decreasing; names present when name_off[n_records] > 0; records present when n_records > 0;
+ * n_records <= 2^31 - 2.  An argument error (OEM_ERR_ARG) rejects that batch only and uses no ticket.  Records, offsets
+ * and name bytes are copied into page-locked staging by the calling thread: the caller may free its arrays on return.
+ * An empty batch, and a batch of unmapped records only, is accepted, takes a ticket and changes nothing else.
+ *
+ * Found on the device, sticky (every later push and finish returns the status and message), the first batch in ticket
+ * order that has a fault reporting it: a surviving record with an empty name or a 0 byte in its name (OEM_ERR_ARG,
+ * naming the record by its session-global index); a ref_id that is not below n_txps (OEM_ERR_ARG, naming "ticket
+ * <ticket>" and the session-global index); 2^32 or more kept alignments (OEM_ERR_ARG); a read of more than 2^32 - 1
+ * records (OEM_ERR_ARG).  The collation check covers the first min(sort_check_num, n_groups) groups of the SESSION: the
+ * head names of the closed groups are held on the device until sort_check_num of them are there, or until finish; the
+ * one call's check runs once then.  A repeat is OEM_ERR_STATE with the one call's message on the concatenation (the
+ * same group, first-record index and earlier index); being sticky it may surface at the push after the one that closed
+ * group sort_check_num - 1, or at finish.  A repeat at a group index >= sort_check_num is accepted.  The host loop takes
+ * a batch's closed groups where oem_records_stream_push's would (OEM_RECORDS_STREAM_INFO_HOST_BATCHES counts them). */
+int oem_records_stream_push_names(oem_records_stream *s, const oem_aln_record *records, uint64_t n_records,
+                                  const uint8_t *names, const uint64_t *name_off, uint64_t *out_ticket);
+/* Waits for the staged batches, closes the open read, runs the collation check if it is still pending, joins the pieces
+ * on the device and returns the store of the contract above, with the discard table and the parse info.  An alignment
+ * outside its transcript under a coverage model: OEM_ERR_STATE.  The variable-length outputs stay with the session
+ * (oem_records_stream_names_copy).  A session without a surviving record gives the store of no groups.  opts are
+ * checked first (OEM_ERR_ARG leaves the session as it was).  While a push is in flight, or a second time:
+ * OEM_ERR_STATE.  *out = NULL on any failure. */
+int oem_records_stream_finish_names(oem_records_stream *s, const oem_store_opts *opts,
+                                    oem_discard_table *out_discard /* or NULL */, oem_parse_info *out_info /* or NULL */,
+                                    oem_store **out);
+/* After a successful oem_records_stream_finish_names (before: OEM_ERR_STATE): out_group_off (n_groups + 1 positions
+ * among the surviving records), out_kept (n_groups), out_row_names (OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES bytes) and
+ * out_row_name_off (n_reads + 1 offsets from 0).  Each may be NULL, the two row-name outputs only together. */
+int oem_records_stream_names_copy(const oem_records_stream *s, uint64_t *out_group_off, uint32_t *out_kept,
+                                  uint8_t *out_row_names, uint64_t *out_row_name_off);
 
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */

@@ -243,7 +243,8 @@ RECORDS_STREAM_INFO = {"batches": _lib.OEM_RECORDS_STREAM_INFO_BATCHES, "groups"
                        "records": _lib.OEM_RECORDS_STREAM_INFO_RECORDS,
                        "batches_before_finish": _lib.OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH,
                        "blocked_us": _lib.OEM_RECORDS_STREAM_INFO_BLOCKED_US,
-                       "host_batches": _lib.OEM_RECORDS_STREAM_INFO_HOST_BATCHES}
+                       "host_batches": _lib.OEM_RECORDS_STREAM_INFO_HOST_BATCHES,
+                       "row_name_bytes": _lib.OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES}
 
 
 class RecordsStream:
@@ -251,10 +252,14 @@ class RecordsStream:
     all records at once.  ``push`` batches of whole groups from any number of threads as they are parsed (each call
     copies its batch into page-locked staging and returns its ticket; the device filters batch k while batch k + 1 is
     staged); ``finish`` returns what ``from_records`` returns for the batches concatenated in ticket order.  A context
-    manager: leaving the block destroys the session (an unfinished one is cancelled)."""
+    manager: leaving the block destroys the session (an unfinished one is cancelled).
+
+    ``names=True`` makes it a names session (``oem_records_stream_set_names``): ``push(records, names=...)`` takes
+    records and their read names in input order, cut at any record positions (a read may straddle pushes), and ``finish``
+    returns what ``DeviceStore.from_named_records(mode="adjacent", sort_check_num=...)`` returns for the concatenation."""
 
     def __init__(self, filters, txp_len, coverage: Optional[str] = None, bin_width: int = 100, growth_rate: float = 2.0,
-                 device: int = 0, max_staged_records: int = 0):
+                 device: int = 0, max_staged_records: int = 0, names: bool = False, sort_check_num: int = 100_000):
         self._lib = _lib.lib()
         self.filters = filters_c(filters)
         self.txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
@@ -265,6 +270,9 @@ class RecordsStream:
         self._h = C.c_void_p()
         self._check(self._lib.oem_records_stream_create(C.byref(o), C.addressof(self.filters), self.txp_len.ctypes.data,
                                                         C.byref(self._h)))
+        self.names = bool(names)
+        if self.names:
+            self._check(self._lib.oem_records_stream_set_names(self._h, int(sort_check_num)))
 
     _check = StoreBuilder._check
 
@@ -291,9 +299,30 @@ class RecordsStream:
             raise RuntimeError("RecordsStream is closed")
         return self._h
 
-    def push(self, records, group_off) -> int:
+    def push(self, records, group_off=None, names=None) -> int:
         """One batch (``records`` / ``group_off`` as in ``StoreBuilder.add_groups``); returns its ticket.  Thread-safe;
-        blocks while the staging budget is full."""
+        blocks while the staging budget is full.  A names session takes ``names=`` instead of ``group_off``: one name
+        per record, a sequence of ``str`` / ``bytes`` or a ``(blob, offsets)`` pair, packed as ``from_named_records``
+        packs it."""
+        if names is not None:
+            from .types import pack_read_names
+            if group_off is not None:
+                raise ValueError("push takes group_off or names, not both")
+            records = np.ascontiguousarray(records, dtype=ALN_RECORD)
+            n = len(records)
+            packed = isinstance(names, tuple) and len(names) == 2 and not isinstance(names[1], (str, bytes))
+            if (len(names[1]) - 1 if packed else len(names)) != n:
+                raise ValueError("names must have one entry per record")
+            blob, off = pack_read_names(names, n)
+            if n and not len(blob):
+                blob = np.zeros(1, dtype=np.uint8)   # (every name is empty: the session says so)
+            ticket = C.c_uint64(0)
+            self._check(self._lib.oem_records_stream_push_names(self.handle, records.ctypes.data if n else None, n,
+                                                                blob.ctypes.data if n else None, off.ctypes.data,
+                                                                C.byref(ticket)))
+            return int(ticket.value)
+        if group_off is None:
+            raise ValueError("push needs group_off (or names= on a names session)")
         records, group_off = check_batch(records, group_off)
         ticket = C.c_uint64(0)
         self._check(self._lib.oem_records_stream_push(self.handle, records.ctypes.data if len(records) else None,
@@ -303,6 +332,8 @@ class RecordsStream:
     def info(self) -> dict:
         out = {}
         for name, key in RECORDS_STREAM_INFO.items():
+            if name == "row_name_bytes" and not self.names:   # (a names session's key)
+                continue
             v = C.c_uint64(0)
             self._check(self._lib.oem_records_stream_info(self.handle, key, C.byref(v)))
             out[name] = int(v.value)
@@ -310,9 +341,28 @@ class RecordsStream:
 
     def finish(self, reorder_rows: int = 0, window_cap: int = 0, layout_build: int = 0, weight_coding: int = 0):
         """``(DeviceStore, kept, discard_table)`` as ``DeviceStore.from_records`` returns them for the accepted batches
-        concatenated in ticket order."""
+        concatenated in ticket order.  A names session returns ``(DeviceStore, kept, discard_table, parse)`` as
+        ``DeviceStore.from_named_records`` does, ``parse.order`` being None."""
         from .types import DeviceStore
         o = store_opts(reorder_rows, window_cap, layout_build, weight_coding)
+        if self.names:
+            from types import SimpleNamespace
+            dt, pi = _lib.DiscardTableC(), _lib.ParseInfoC()
+            h = C.c_void_p()
+            self._check(self._lib.oem_records_stream_finish_names(self.handle, C.addressof(o), C.addressof(dt), C.addressof(pi),
+                                                                  C.byref(h)))
+            store = DeviceStore._adopt(self._lib, h, len(self.txp_len), self.device)
+            group_off = np.zeros(pi.n_groups + 1, dtype=np.uint64)
+            kept = np.zeros(max(pi.n_groups, 1), dtype=np.uint32)
+            row_blob = np.zeros(max(self.info()["row_name_bytes"], 1), dtype=np.uint8)
+            row_off = np.zeros(pi.n_reads + 1, dtype=np.uint64)
+            self._check(self._lib.oem_records_stream_names_copy(self.handle, group_off.ctypes.data, kept.ctypes.data,
+                                                                row_blob.ctypes.data, row_off.ctypes.data))
+            parse = SimpleNamespace(order=None, group_off=group_off, read_names=(row_blob[:int(row_off[-1])].copy(), row_off),
+                                    n_unmapped=int(pi.n_unmapped), n_parsed=int(pi.n_parsed), n_groups=int(pi.n_groups),
+                                    n_reads=int(pi.n_reads), unique_alignments=int(pi.unique_alignments),
+                                    n_checked=int(pi.n_checked))
+            return store, kept[:pi.n_groups].copy(), discard_dict(dt), parse
         kept = np.zeros(self.info()["groups"], dtype=np.uint32)
         dt = _lib.DiscardTableC()
         h = C.c_void_p()

@@ -9,7 +9,9 @@ Alignment parsing comes before this (the caller); the filtering is `builder.Stor
 reads per call, on the host or on the device) or, from the parsed records straight to the resident store in one device
 call, `DeviceStore.from_records` (oem_store_create_records).  `quantify_bulk_alignments_from_records` is the whole of
 `quantify_bulk_alignments_from_bam` (bulk.rs:212-259) from the parsed records on: the parser itself
-(alignment_parser.rs:301-437) runs on the device too (`DeviceStore.from_named_records`).  KDE is not supported.
+(alignment_parser.rs:301-437) runs on the device too (`DeviceStore.from_named_records`);
+`quantify_bulk_alignments_from_record_batches` is the same for a reader that hands the records and names over in chunks
+(`builder.RecordsStream(names=True)`).  KDE is not supported.
 """
 from __future__ import annotations
 
@@ -127,11 +129,47 @@ def quantify_bulk_alignments_from_records(filters, txps_name: Sequence[str], txp
     makes of the same groups.  The resident store has no host CSR, so the host `.prob` writer (``prob_on_device``
     False) first runs the host filter once more over the collated records for the rows' transcript ids;
     ``prob_on_device`` formats the body from the resident store and needs none of that."""
-    from .builder import StoreBuilder
     txp_len = np.asarray(txp_lens, dtype=np.uint64)
     dev, _kept, _discard, parse = DeviceStore.from_named_records(
         filters, txp_len, records, names, secondary=secondary, mode=mode, sort_check_num=sort_check_num, coverage=coverage,
         bin_width=bin_width, growth_rate=growth_rate, device=args.device)
+    return _write_from_resident(dev, parse, lambda: (np.asarray(records)[parse.order], parse.group_off), filters, txp_len,
+                                txps_name, txp_lens, args, coverage)
+
+
+def quantify_bulk_alignments_from_record_batches(filters, txps_name: Sequence[str], txp_lens: Sequence[int], batches,
+                                                 args: BulkArgs, sort_check_num: int = 100_000,
+                                                 coverage: Optional[str] = None, bin_width: int = 100,
+                                                 growth_rate: float = 2.0, max_staged_records: int = 0) -> np.ndarray:
+    """``quantify_bulk_alignments_from_records`` for a reader that hands over chunks: ``batches`` is an iterable of
+    ``(records, names)`` in input order, cut at any record positions (a read may straddle batches).  They go through a
+    names session (``RecordsStream(names=True)``: the reference's parser, ``mode="adjacent"``); the files are those of
+    ``quantify_bulk_alignments_from_records`` on the concatenation.  The host `.prob` writer (``prob_on_device`` False)
+    keeps the mapped records it has seen for the rows' transcript ids; ``prob_on_device`` needs none of that."""
+    from .builder import REC_UNMAPPED, RecordsStream
+    txp_len = np.asarray(txp_lens, dtype=np.uint64)
+    keep_rows = args.write_assignment_probs and not args.prob_on_device
+    mapped = []
+    with RecordsStream(filters, txp_len, coverage=coverage, bin_width=bin_width, growth_rate=growth_rate, device=args.device,
+                       max_staged_records=max_staged_records, names=True, sort_check_num=sort_check_num) as rs:
+        for records, names in batches:
+            records = np.asarray(records)
+            rs.push(records, names=names)
+            if keep_rows:
+                mapped.append(records[(records["flags"] & REC_UNMAPPED) == 0])
+        dev, _kept, _discard, parse = rs.finish()
+
+    def host_rows():
+        from .builder import ALN_RECORD
+        return (np.concatenate(mapped) if mapped else np.zeros(0, dtype=ALN_RECORD)), parse.group_off
+
+    return _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args, coverage)
+
+
+def _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args: BulkArgs, coverage) -> np.ndarray:
+    """The tail both records drivers share, from the resident store on.  ``host_rows()``: the collated records and their
+    group_off for the host `.prob` writer, which needs the rows' transcript ids."""
+    from .builder import StoreBuilder
     with dev:
         counts, run = dev.em_run(None, args.max_em_iter, args.convergence_thresh, 50 if args.threads <= 4 else 1)  # bulk.rs:155-159
         unique, total = dev.aux_counts()                                                     # bulk.rs:161
@@ -154,7 +192,7 @@ def quantify_bulk_alignments_from_records(filters, txps_name: Sequence[str], txp
                                               compressed=args.prob_compressed)
                 return counts
             with StoreBuilder(filters, txp_len) as hb:   # the rows' transcript ids: the host filter over the same groups
-                hb.add_groups(np.asarray(records)[parse.order], parse.group_off)
+                hb.add_groups(*host_rows())
                 row_ptr, tid = hb.export()[:2]
             blob, off = parse.read_names
             read_names = [bytes(blob[int(off[r]):int(off[r + 1])]).decode("utf-8", "replace") for r in range(dev.n_reads)]

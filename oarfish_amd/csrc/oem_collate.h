@@ -275,4 +275,55 @@ inline ParseBulk parse_bulk_host(const Rec *records, uint64_t n_records, const u
     return pb;
 }
 
+// The streamed form of parse_bulk_host, for kCollateAdjacent only: the same input cut into batches at ANY record
+// positions (oem_records_stream_push_names), a cut inside a read included.  This is the one statement of how a batch's
+// surviving records attach to the open read:
+//   - a batch's survivors are its records without OEM_REC_UNMAPPED, in input order;
+//   - the open read (the carry) is the trailing run of one name among all survivors pushed so far;
+//   - a batch's first run joins the carry when its name is the carry's name, byte for byte; otherwise the carry is
+//     closed before the batch's first run;
+//   - every run of the batch but the last is closed by the batch itself, the last run becomes the new carry;
+//   - a batch without a survivor (an empty batch, a batch of unmapped records only) changes nothing but the counts;
+//   - finish closes the carry.
+// Groups are numbered in closing order.  A group's head is its first record's session-global input index: 64-bit, it
+// counts all records of all pushed batches in push order, unmapped ones included.  The names of surviving records are
+// the caller's to check (collate_first_bad_name's conditions); unmapped records' names are never read.
+struct ParseBulkStream {
+    uint64_t n_records = 0, n_unmapped = 0;       // of all batches pushed
+    std::vector<uint64_t> group_size, group_head; // the closed groups
+    bool open = false;                            // the carry: its name, its size so far and its head
+    std::vector<uint8_t> open_name;
+    uint64_t open_size = 0, open_head = 0;
+
+    void close()
+    {
+        if (!open) return;
+        group_size.push_back(open_size);
+        group_head.push_back(open_head);
+        open = false;
+        open_size = 0;
+    }
+    template <typename Rec>
+    void push(const Rec *records, uint64_t n, const uint8_t *names, const uint64_t *name_off)
+    {
+        for (uint64_t i = 0; i < n; ++i) {
+            if (records[i].flags & kRecUnmapped) {
+                ++n_unmapped;
+                continue;
+            }
+            const uint8_t *nm = names + name_off[i];
+            const uint64_t len = name_off[i + 1] - name_off[i];
+            if (!open || collate_name_cmp(nm, len, open_name.data(), open_name.size()) != 0) {
+                close();
+                open = true;
+                open_name.assign(nm, nm + len);
+                open_head = n_records + i;
+            }
+            ++open_size;
+        }
+        n_records += n;
+    }
+    void finish() { close(); }
+};
+
 } // namespace oem

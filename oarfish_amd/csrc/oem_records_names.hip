@@ -37,8 +37,7 @@
 #include <cstring>
 #include <vector>
 
-#include "oem_collate_device.h"
-#include "oem_filter_device.h"
+#include "oem_parse_device.h"
 
 namespace oem {
 namespace {
@@ -126,13 +125,15 @@ int exclusive_scan(In in, uint64_t *out, uint64_t n)
     return OEM_OK;
 }
 
-int bad_name(const char *who, bool zero_byte, uint64_t record)
+} // namespace
+
+int parse_bad_name(const char *who, bool zero_byte, uint64_t record)
 {
     if (zero_byte) return fail(OEM_ERR_ARG, "%s: the name of record %llu contains a 0 byte", who, (unsigned long long)record);
     return fail(OEM_ERR_ARG, "%s: record %llu has an empty name", who, (unsigned long long)record);
 }
 
-int not_collated(const char *who, uint64_t group, uint64_t record, uint64_t earlier)
+int parse_not_collated(const char *who, uint64_t group, uint64_t record, uint64_t earlier)
 {
     return fail(OEM_ERR_STATE,
                 "%s: the input is not name-collated: group %llu (first record %llu) has the name of an earlier group (first record %llu); "
@@ -152,7 +153,123 @@ int gather_input_names(const uint32_t *d_idx, uint64_t k, const uint8_t *d_names
     return gather_names(d_idx, k, d_names, d_name_off, d_off_out->p, 0, *n_bytes, d_blob_out->p, nullptr, nullptr);
 }
 
-} // namespace
+
+int parse_survivors(const oem_aln_record *d_in, uint64_t n, bool always, DevBuf<uint32_t> *d_order_parse, uint64_t *m)
+{
+    DevBuf<uint32_t> d_keep;
+    DevBuf<uint64_t> d_at;
+    OEM_TRY(dev_alloc(&d_keep.p, n + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_at.p, n + 1, nullptr));
+    hipLaunchKernelGGL(k_parse_keep, grid_for(n + 1), dim3(kPT), 0, nullptr, n, (const uint64_t *)d_in, d_keep.p);
+    OEM_HIP(hipGetLastError());
+    hipcub::TransformInputIterator<uint64_t, U32ToU64, const uint32_t *> in(d_keep.p, U32ToU64());
+    OEM_TRY(exclusive_scan(in, d_at.p, n + 1));
+    OEM_HIP(hipMemcpy(m, d_at.p + n, sizeof *m, hipMemcpyDeviceToHost));
+    if (*m && (*m < n || always)) {
+        OEM_TRY(dev_alloc(&d_order_parse->p, *m, nullptr));
+        hipLaunchKernelGGL(k_parse_compact, grid_for(n), dim3(kPT), 0, nullptr, n, (const uint32_t *)d_keep.p, (const uint64_t *)d_at.p,
+                           d_order_parse->p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipStreamSynchronize(nullptr));
+    }
+    return OEM_OK;
+}
+
+int parse_survivor_names(const uint8_t *d_names, uint64_t n_bytes, const uint64_t *d_name_off, uint64_t n, const uint32_t *d_order_parse,
+                         uint64_t m, const uint8_t *d_sec, DevBuf<uint8_t> *d_dense, DevBuf<uint64_t> *d_dense_off,
+                         DevBuf<uint8_t> *d_dense_sec, uint64_t *dense_bytes, uint64_t *bad_record, bool *zero_byte)
+{
+    DevBuf<unsigned long long> d_bad;
+    OEM_TRY(dev_alloc(&d_bad.p, 2, nullptr));
+    const unsigned long long bad0[2] = {kNoRecord, kNoRecord};
+    unsigned long long bad[2];
+    OEM_HIP(hipMemcpy(d_bad.p, bad0, sizeof bad0, hipMemcpyHostToDevice));
+    *bad_record = kNoRecord;
+    *zero_byte = false;
+    *dense_bytes = n_bytes;
+    if (!d_order_parse) {
+        launch_collate_validate(nullptr, d_names, 0, n_bytes, d_name_off, 0, n, d_bad.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad[0] != kNoRecord || bad[1] != kNoRecord) {
+            *zero_byte = !(bad[1] < bad[0]);
+            *bad_record = bad[1] < bad[0] ? bad[1] : bad[0];
+        }
+        return OEM_OK;
+    }
+    OEM_TRY(dev_alloc(&d_dense_off->p, m + 1, nullptr));
+    OEM_TRY(gather_name_offsets(d_order_parse, m, d_name_off, d_dense_off->p));
+    launch_collate_validate(nullptr, d_names, 0, 0, d_dense_off->p, 0, m, d_bad.p); // the empty names, from the offsets alone
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+    const uint64_t m_ok = bad[1] != kNoRecord ? bad[1] : m; // the survivors before the first empty name
+    OEM_HIP(hipMemcpy(dense_bytes, d_dense_off->p + m_ok, sizeof *dense_bytes, hipMemcpyDeviceToHost));
+    OEM_TRY(dev_alloc(&d_dense->p, *dense_bytes + 16, nullptr));
+    if (m_ok) {
+        const bool flags = d_sec && m_ok == m;
+        if (flags) OEM_TRY(dev_alloc(&d_dense_sec->p, ((m + 8) / 8) * 8, nullptr));
+        OEM_TRY(gather_names(d_order_parse, m_ok, d_names, d_name_off, d_dense_off->p, 0, *dense_bytes, d_dense->p, flags ? d_sec : nullptr,
+                             flags ? d_dense_sec->p : nullptr));
+        launch_collate_validate(nullptr, d_dense->p, 0, *dense_bytes, d_dense_off->p, 0, m_ok, d_bad.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+    }
+    if (bad[0] != kNoRecord || bad[1] != kNoRecord) { // (a 0 byte can only have been found before the first empty name)
+        const uint64_t at = bad[0] != kNoRecord ? bad[0] : bad[1];
+        uint32_t record = 0;
+        OEM_HIP(hipMemcpy(&record, d_order_parse + at, sizeof record, hipMemcpyDeviceToHost));
+        *zero_byte = bad[0] != kNoRecord;
+        *bad_record = record;
+    }
+    return OEM_OK;
+}
+
+int parse_check_repeat(const char *who, const uint8_t *d_chk, const uint64_t *d_chk_off, uint64_t chk_bytes, uint64_t nchk, uint64_t *found)
+{
+    *found = ~0ull;
+    const uint64_t chk_cell[2] = {0, nchk};
+    CollateInput in;
+    in.who = who;
+    in.cell_rec_off = chk_cell;
+    in.mode = kCollateSort;
+    in.chunk_bytes = collate_chunk_bytes();
+    in.d_names = d_chk;
+    in.d_name_off = d_chk_off;
+    in.d_n_bytes = chk_bytes;
+    CollateResident runs; // order: the checked groups sorted by name, stably; group_off: where a name starts
+    double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    OEM_TRY(collate_resident(in, 0, 1, 0, 0, 0, info, &runs));
+    if (runs.n_groups == nchk) return OEM_OK;
+    DevBuf<unsigned long long> d_found;
+    unsigned long long f = ~0ull;
+    OEM_TRY(dev_alloc(&d_found.p, 1, nullptr));
+    OEM_HIP(hipMemcpy(d_found.p, &f, sizeof f, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_parse_check, grid_for(runs.n_groups), dim3(kPT), 0, nullptr, runs.n_groups, (const uint64_t *)runs.group_off.p,
+                       (const uint32_t *)runs.order.p, d_found.p);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpy(&f, d_found.p, sizeof f, hipMemcpyDeviceToHost));
+    *found = f;
+    return OEM_OK;
+}
+
+int parse_count_unique(uint64_t n_groups, const uint32_t *d_n_kept, uint64_t *unique)
+{
+    DevBuf<unsigned long long> d_u;
+    unsigned long long u = 0;
+    OEM_TRY(dev_alloc(&d_u.p, 1, nullptr));
+    OEM_HIP(hipMemcpy(d_u.p, &u, sizeof u, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_parse_unique, grid_for(n_groups), dim3(kPT), 0, nullptr, n_groups, d_n_kept, d_u.p);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpy(&u, d_u.p, sizeof u, hipMemcpyDeviceToHost));
+    *unique = u;
+    return OEM_OK;
+}
+
+int parse_row_index(const uint32_t *d_n_kept, uint64_t n, uint64_t *d_row_idx)
+{
+    hipcub::TransformInputIterator<uint64_t, NonZeroToU64, const uint32_t *> in(d_n_kept, NonZeroToU64());
+    return exclusive_scan(in, d_row_idx, n);
+}
 
 void records_names_last_call(double *out8) { std::memcpy(out8, g_records_names_last, sizeof g_records_names_last); }
 
@@ -220,22 +337,7 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
                                                [](hipStream_t, uint64_t, uint64_t) {}));
 
         // -- the survivors ---------------------------------------------------------------------------------------------
-        DevBuf<uint32_t> d_keep;
-        DevBuf<uint64_t> d_at;
-        OEM_TRY(dev_alloc(&d_keep.p, n + 1, nullptr));
-        OEM_TRY(dev_alloc(&d_at.p, n + 1, nullptr));
-        hipLaunchKernelGGL(k_parse_keep, grid_for(n + 1), dim3(kPT), 0, nullptr, n, (const uint64_t *)d_in.p, d_keep.p);
-        OEM_HIP(hipGetLastError());
-        hipcub::TransformInputIterator<uint64_t, U32ToU64, const uint32_t *> in(d_keep.p, U32ToU64());
-        OEM_TRY(exclusive_scan(in, d_at.p, n + 1));
-        OEM_HIP(hipMemcpy(&m, d_at.p + n, sizeof m, hipMemcpyDeviceToHost));
-        if (m && m < n) {
-            OEM_TRY(dev_alloc(&d_order_parse.p, m, nullptr));
-            hipLaunchKernelGGL(k_parse_compact, grid_for(n), dim3(kPT), 0, nullptr, n, (const uint32_t *)d_keep.p, (const uint64_t *)d_at.p,
-                               d_order_parse.p);
-            OEM_HIP(hipGetLastError());
-            OEM_HIP(hipStreamSynchronize(nullptr));
-        }
+        OEM_TRY(parse_survivors(d_in.p, n, false, &d_order_parse, &m));
     }
     pi.n_parsed = m;
     pi.n_unmapped = n - m;
@@ -257,42 +359,14 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
     // -- the names of the survivors, checked ----------------------------------------------------------------------------
     DevBuf<uint8_t> d_dense, d_dense_sec;
     DevBuf<uint64_t> d_dense_off;
-    DevBuf<unsigned long long> d_bad;
     uint64_t dense_bytes = n_bytes;
-    OEM_TRY(dev_alloc(&d_bad.p, 2, nullptr));
-    const unsigned long long bad0[2] = {kNoRecord, kNoRecord};
-    unsigned long long bad[2];
-    OEM_HIP(hipMemcpy(d_bad.p, bad0, sizeof bad0, hipMemcpyHostToDevice));
-    if (!dense) {
-        launch_collate_validate(nullptr, d_names.p, 0, n_bytes, d_name_off.p, 0, n, d_bad.p);
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad[0] != kNoRecord || bad[1] != kNoRecord) return bad_name(who, !(bad[1] < bad[0]), bad[1] < bad[0] ? bad[1] : bad[0]);
-    } else {
-        OEM_TRY(dev_alloc(&d_dense_off.p, m + 1, nullptr));
-        OEM_TRY(gather_name_offsets(d_order_parse.p, m, d_name_off.p, d_dense_off.p));
-        launch_collate_validate(nullptr, d_names.p, 0, 0, d_dense_off.p, 0, m, d_bad.p); // the empty names, from the offsets alone
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-        const uint64_t m_ok = bad[1] != kNoRecord ? bad[1] : m; // the survivors before the first empty name
-        OEM_HIP(hipMemcpy(&dense_bytes, d_dense_off.p + m_ok, sizeof dense_bytes, hipMemcpyDeviceToHost));
-        OEM_TRY(dev_alloc(&d_dense.p, dense_bytes + 16, nullptr));
-        if (m_ok) {
-            const bool flags = d_sec.p && m_ok == m;
-            if (flags) OEM_TRY(dev_alloc(&d_dense_sec.p, ((m + 8) / 8) * 8, nullptr));
-            OEM_TRY(gather_names(d_order_parse.p, m_ok, d_names.p, d_name_off.p, d_dense_off.p, 0, dense_bytes, d_dense.p,
-                                 flags ? d_sec.p : nullptr, d_dense_sec.p));
-            launch_collate_validate(nullptr, d_dense.p, 0, dense_bytes, d_dense_off.p, 0, m_ok, d_bad.p);
-            OEM_HIP(hipGetLastError());
-            OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-        }
-        if (bad[0] != kNoRecord || bad[1] != kNoRecord) { // (a 0 byte can only have been found before the first empty name)
-            const uint64_t at = bad[0] != kNoRecord ? bad[0] : bad[1];
-            uint32_t record = 0;
-            OEM_HIP(hipMemcpy(&record, d_order_parse.p + at, sizeof record, hipMemcpyDeviceToHost));
-            return bad_name(who, bad[0] != kNoRecord, record);
-        }
-        last[1] = 1;
+    {
+        uint64_t bad_record = kNoRecord;
+        bool zero_byte = false;
+        OEM_TRY(parse_survivor_names(d_names.p, n_bytes, d_name_off.p, n, dense ? d_order_parse.p : nullptr, m, d_sec.p, &d_dense, &d_dense_off,
+                                     &d_dense_sec, &dense_bytes, &bad_record, &zero_byte));
+        if (bad_record != kNoRecord) return parse_bad_name(who, zero_byte, bad_record);
+        if (dense) last[1] = 1;
     }
 
     // -- collate: the survivors as one cell -----------------------------------------------------------------------------
@@ -335,30 +409,14 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
                                (const uint32_t *)cr.order.p, d_heads.p);
             OEM_HIP(hipGetLastError());
             OEM_TRY(gather_input_names(d_heads.p, nchk, d_names.p, d_name_off.p, &d_chk_off, &d_chk, &chk_bytes));
-            const uint64_t chk_cell[2] = {0, nchk};
-            CollateInput in;
-            in.who = who;
-            in.cell_rec_off = chk_cell;
-            in.mode = kCollateSort;
-            in.chunk_bytes = collate_chunk_bytes();
-            in.d_names = d_chk.p;
-            in.d_name_off = d_chk_off.p;
-            in.d_n_bytes = chk_bytes;
-            CollateResident runs; // order: the checked groups sorted by name, stably; group_off: where a name starts
-            double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            OEM_TRY(collate_resident(in, 0, 1, 0, 0, 0, info, &runs));
-            if (runs.n_groups < nchk) {
-                unsigned long long found = ~0ull;
-                OEM_HIP(hipMemcpy(d_bad.p, &found, sizeof found, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(k_parse_check, grid_for(runs.n_groups), dim3(kPT), 0, nullptr, runs.n_groups,
-                                   (const uint64_t *)runs.group_off.p, (const uint32_t *)runs.order.p, d_bad.p);
-                OEM_HIP(hipGetLastError());
-                OEM_HIP(hipMemcpy(&found, d_bad.p, sizeof found, hipMemcpyDeviceToHost));
+            uint64_t found = ~0ull;
+            OEM_TRY(parse_check_repeat(who, d_chk.p, d_chk_off.p, chk_bytes, nchk, &found));
+            if (found != ~0ull) {
                 const uint64_t g = found >> 32, earlier = found & 0xffffffffull;
                 uint32_t rec_g = 0, rec_e = 0;
                 OEM_HIP(hipMemcpy(&rec_g, d_heads.p + g, sizeof rec_g, hipMemcpyDeviceToHost));
                 OEM_HIP(hipMemcpy(&rec_e, d_heads.p + earlier, sizeof rec_e, hipMemcpyDeviceToHost));
-                return not_collated(who, g, rec_g, rec_e);
+                return parse_not_collated(who, g, rec_g, rec_e);
             }
         }
     }
@@ -436,14 +494,7 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
 
     // -- unique_alignments and the row names, before the store takes the arrays -----------------------------------------
     pi.n_reads = r.n_rows;
-    {
-        unsigned long long unique = 0;
-        OEM_HIP(hipMemcpy(d_bad.p, &unique, sizeof unique, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_parse_unique, grid_for(ng), dim3(kPT), 0, nullptr, ng, (const uint32_t *)r.n_kept.p, d_bad.p);
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpy(&unique, d_bad.p, sizeof unique, hipMemcpyDeviceToHost));
-        pi.unique_alignments = unique;
-    }
+    OEM_TRY(parse_count_unique(ng, r.n_kept.p, &pi.unique_alignments));
     if (want_rows) {
         out_row_name_off[0] = 0;
         if (r.n_rows) {
@@ -453,8 +504,7 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
             uint64_t row_bytes = 0;
             OEM_TRY(dev_alloc(&d_row_idx.p, ng + 1, nullptr));
             OEM_TRY(dev_alloc(&d_heads.p, r.n_rows, nullptr));
-            hipcub::TransformInputIterator<uint64_t, NonZeroToU64, const uint32_t *> in(r.n_kept.p, NonZeroToU64());
-            OEM_TRY(exclusive_scan(in, d_row_idx.p, ng + 1)); // (n_kept has n_groups + 1 entries, the last one 0)
+            OEM_TRY(parse_row_index(r.n_kept.p, ng + 1, d_row_idx.p)); // (n_kept has n_groups + 1 entries, the last one 0)
             hipLaunchKernelGGL(k_parse_row_heads, grid_for(ng), dim3(kPT), 0, nullptr, ng, (const uint32_t *)r.n_kept.p,
                                (const uint64_t *)d_row_idx.p, (const uint64_t *)cr.group_off.p, (const uint32_t *)cr.order.p, d_heads.p);
             OEM_HIP(hipGetLastError());
@@ -469,7 +519,6 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
     cr.cell_group_off.reset();
     d_names.reset();
     d_name_off.reset();
-    d_bad.reset();
 
     OEM_TRY(filter_result_to_store(who, r, n_txps, ng, bin_width, model, growth_rate, device, opts, out_kept, out_discard, out));
     if (out_info) *out_info = pi;

@@ -17,6 +17,11 @@
 //             k_stream_concat once over all arrays of all pieces: the result is the FilterResult the one call's pass
 //             would have left, and filter_result_to_store makes the store of it.  The pieces are freed after the join.
 //
+// The NAMES form (oem_records_stream_set_names; "the names session" below and in DESIGN.md section 5d) takes records and
+// read names cut at any record positions: its worker parses each batch as oem_store_create_records_names does
+// (oem_parse_device.h), carries the open read on the device from batch to batch, and its pieces hold the groups a batch
+// CLOSED, with their group offsets and row names; finish joins those too.
+//
 // The batch type is oem_aln_record throughout; a session over projected records would template Batch and run_batch on
 // the record type, as filter_upload_measure is.
 #include <algorithm>
@@ -32,6 +37,7 @@
 #include <vector>
 
 #include "oem_filter_device.h"
+#include "oem_parse_device.h"
 
 namespace oem {
 namespace {
@@ -49,15 +55,17 @@ constexpr int kCT = 256;
 thread_local float g_join_ms = 0.f;
 
 // One array of one piece on its way into the joined result: n_bytes from src to dst, as u32 elements with `add` added
-// to each (elem 4: row pointers get the piece's alignment base, the other arrays 0) or as bytes (elem 1: strand).
-// The job's workgroups are first_block .. of the one launch.
+// to each modulo 2^32 (elem 4: row pointers get the piece's alignment base, the other arrays 0), as u64 elements with
+// the 64-bit `add` (elem 8: the names session's group offsets and row-name offsets get the piece's record and byte
+// base) or as bytes (elem 1: strand, row names).  The job's workgroups are first_block .. of the one launch.
 struct ConcatJob {
     const uint8_t *src;
     uint8_t *dst;
     uint64_t n_bytes;
     uint64_t first_block;
-    uint32_t add;
+    uint64_t add;
     uint32_t elem;
+    uint32_t pad;
 };
 
 // The split of a job into a head (up to the destination's first 16-byte boundary), 16-byte body units and a tail.  A
@@ -111,16 +119,26 @@ __global__ __launch_bounds__(kCT) void k_stream_concat(const ConcatJob *__restri
             const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
             v = make_uint4((w0 >> lo) | (w1 << hi), (w1 >> lo) | (w2 << hi), (w2 >> lo) | (w3 << hi), (w3 >> lo) | (w4 << hi));
         }
-        v.x += j.add; // (0 for everything but row pointers)
-        v.y += j.add;
-        v.z += j.add;
-        v.w += j.add;
+        if (j.elem == 8) { // (uniform per workgroup) two u64 elements: source and destination are 8-byte aligned, rel is 0 or 8
+            const uint64_t e0 = (((uint64_t)v.y << 32) | v.x) + j.add, e1 = (((uint64_t)v.w << 32) | v.z) + j.add;
+            v = make_uint4((uint32_t)e0, (uint32_t)(e0 >> 32), (uint32_t)e1, (uint32_t)(e1 >> 32));
+        } else {
+            const uint32_t add = (uint32_t)j.add; // (0 for everything but row pointers)
+            v.x += add;
+            v.y += add;
+            v.z += add;
+            v.w += add;
+        }
         *(uint4 *)(j.dst + sp.head + 16 * u) = v;
     } else if (u == sp.n_body) {
         const uint64_t t0 = sp.head + 16 * sp.n_body;
         if (j.elem == 4) {
-            for (uint64_t i = 0; i < sp.head; i += 4) *(uint32_t *)(j.dst + i) = *(const uint32_t *)(j.src + i) + j.add;
-            for (uint64_t i = t0; i < j.n_bytes; i += 4) *(uint32_t *)(j.dst + i) = *(const uint32_t *)(j.src + i) + j.add;
+            const uint32_t add = (uint32_t)j.add;
+            for (uint64_t i = 0; i < sp.head; i += 4) *(uint32_t *)(j.dst + i) = *(const uint32_t *)(j.src + i) + add;
+            for (uint64_t i = t0; i < j.n_bytes; i += 4) *(uint32_t *)(j.dst + i) = *(const uint32_t *)(j.src + i) + add;
+        } else if (j.elem == 8) {
+            for (uint64_t i = 0; i < sp.head; i += 8) *(uint64_t *)(j.dst + i) = *(const uint64_t *)(j.src + i) + j.add;
+            for (uint64_t i = t0; i < j.n_bytes; i += 8) *(uint64_t *)(j.dst + i) = *(const uint64_t *)(j.src + i) + j.add;
         } else {
             for (uint64_t i = 0; i < sp.head; ++i) j.dst[i] = j.src[i];
             for (uint64_t i = t0; i < j.n_bytes; ++i) j.dst[i] = j.src[i];
@@ -143,7 +161,10 @@ void arena_free(Arena &a)
 
 struct Batch {
     uint64_t ticket = 0, n_groups = 0, n_records = 0;
-    Arena mem;          // (none for a batch without groups)
+    // a names session's batch: no groups yet; the arena holds name_off (n_records + 1), the records and the name bytes
+    bool named = false;
+    uint64_t rec_base = 0, name_bytes = 0; // the session-global input index of its first record; name_off[n_records]
+    Arena mem;          // (none for a batch without groups, or without records in a names session)
     bool ready = false; // the pushing thread has finished its copy
     Batch() = default;
     Batch(const Batch &) = delete;
@@ -152,14 +173,100 @@ struct Batch {
     const uint64_t *group_off() const { return (const uint64_t *)mem.p; }
     static size_t records_at(uint64_t n_groups) { return (sizeof(uint64_t) * (n_groups + 1) + 63) & ~(size_t)63; }
     const oem_aln_record *records() const { return (const oem_aln_record *)((const char *)mem.p + records_at(n_groups)); }
+    // the names form: offsets first (as group_off is), records at records_at(n_records), the bytes behind them
+    const uint64_t *name_off() const { return (const uint64_t *)mem.p; }
+    const oem_aln_record *named_records() const { return (const oem_aln_record *)((const char *)mem.p + records_at(n_records)); }
+    static size_t names_at(uint64_t n_records) { return records_at(n_records) + ((sizeof(oem_aln_record) * n_records + 63) & ~(size_t)63); }
+    const uint8_t *names() const { return (const uint8_t *)mem.p + names_at(n_records); }
 };
 
 // What a batch leaves on the device: r.row_ptr32 (n_rows + 1, from 0), r.tid, r.as_prob, with a model r.start / r.end /
 // r.strand, r.n_kept (n_groups + 1) and r.dt.  A batch without groups leaves no arrays.
+// A names session's piece holds the groups its batch CLOSED (oem_collate.h, the streamed rule), and besides the above:
+// group_off (n_groups + 1 positions from 0 among the closed groups' records, n_records of them), the names of its rows
+// as a dense blob (row_bytes) with row_off (n_rows + 1 offsets from 0), and the number of groups with n_kept == 1.
 struct Piece {
     FilterResult r;
     uint64_t n_groups = 0;
+    DevBuf<uint64_t> group_off, row_off;
+    DevBuf<uint8_t> rows;
+    uint64_t n_records = 0, row_bytes = 0, unique = 0;
 };
+
+// The head names of one batch's first closed groups, kept for the session's collation check: k names as a dense blob
+// with k + 1 offsets from 0, and the heads' session-global input indices.
+struct CheckChunk {
+    DevBuf<uint8_t> blob;
+    DevBuf<uint64_t> off, heads;
+    uint64_t k = 0, bytes = 0;
+};
+
+// ---- the names session's kernels: one lane per word, nothing staged ------------------------------------------------------
+
+// *equal = the name of record order[0] is the name of record `other`, byte for byte (one workgroup; names are short)
+__global__ __launch_bounds__(kCT) void k_names_equal(const uint8_t *__restrict__ names, const uint64_t *__restrict__ name_off,
+                                                     const uint32_t *__restrict__ order, uint64_t other, uint32_t *__restrict__ equal)
+{
+    const uint64_t i = order[0], a0 = name_off[i], la = name_off[i + 1] - a0, b0 = name_off[other], lb = name_off[other + 1] - b0;
+    int diff = la != lb;
+    if (!diff)
+        for (uint64_t k = threadIdx.x; k < la; k += kCT) diff |= names[a0 + k] != names[b0 + k];
+    diff = __syncthreads_or(diff);
+    if (threadIdx.x == 0) *equal = diff ? 0u : 1u;
+}
+
+// The closed groups of a batch, the carry spliced in: group j's first position among the closed records (goff, nc + 1
+// entries from 0) and the record that carries its name (head: an input index of the batch, or carry_rec for the group
+// the carry opens).  c carry records come first; gb: the batch's own cut (positions among its survivors), order: the
+// survivors' input indices.  first_is_carry: c > 0; shift 1: the carry closes as a group of its own, the batch's run b
+// is group b + 1; shift 0: the batch's first run joins the carry (or there is no carry), run b is group b.
+__global__ __launch_bounds__(kCT) void k_names_splice(uint64_t nc, uint64_t c, uint32_t shift, uint32_t first_is_carry,
+                                                      const uint64_t *__restrict__ gb, const uint32_t *__restrict__ order, uint32_t carry_rec,
+                                                      uint64_t *__restrict__ goff, uint32_t *__restrict__ head)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kCT + threadIdx.x;
+    if (j > nc) return;
+    if (j == nc) {
+        goff[nc] = c + gb[nc - shift];
+    } else if (first_is_carry && j == 0) {
+        goff[0] = 0;
+        head[0] = carry_rec;
+    } else {
+        const uint64_t p = gb[j - shift];
+        goff[j] = c + p;
+        head[j] = order[p];
+    }
+}
+
+// out[j] = the session-global input index of head[j]
+__global__ __launch_bounds__(kCT) void k_names_heads64(uint64_t k, const uint32_t *__restrict__ head, uint32_t carry_rec, uint64_t carry_head,
+                                                       uint64_t rec_base, uint64_t *__restrict__ out)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kCT + threadIdx.x;
+    if (j < k) out[j] = head[j] == carry_rec ? carry_head : rec_base + head[j];
+}
+
+// out[row_idx[g]] = head[g] for the groups with n_kept > 0
+__global__ __launch_bounds__(kCT) void k_names_row_heads(uint64_t nc, const uint32_t *__restrict__ n_kept, const uint64_t *__restrict__ row_idx,
+                                                         const uint32_t *__restrict__ head, uint32_t *__restrict__ out)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * kCT + threadIdx.x;
+    if (g < nc && n_kept[g]) out[row_idx[g]] = head[g];
+}
+
+// *bad = min(*bad, i) over the records i = order[0 .. cnt) whose ref_id (the low half of a record's first word) is not
+// below n_txps: the run that goes into the carry is checked where its batch still knows its indices
+__global__ __launch_bounds__(kCT) void k_names_ref_check(uint64_t cnt, const uint32_t *__restrict__ order, const uint64_t *__restrict__ rec_words,
+                                                         uint32_t n_txps, unsigned long long *__restrict__ bad)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kCT + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t i = order[k];
+    if ((uint32_t)rec_words[(uint64_t)i * 5] >= n_txps) atomicMin(bad, (unsigned long long)i);
+}
+
+inline dim3 names_grid(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kCT - 1) / kCT, 1)); }
+static_assert(offsetof(oem_aln_record, ref_id) == 0, "k_names_ref_check reads ref_id from a record's first word");
 
 } // namespace
 } // namespace oem
@@ -180,7 +287,7 @@ struct oem_records_stream {
     std::vector<Arena> pool;
     std::vector<std::unique_ptr<Piece>> pieces; // by ticket
     uint64_t next_ticket = 0, total_groups = 0, total_records = 0, staged_records = 0, total_kept = 0;
-    uint64_t before_finish = 0, blocked_us = 0, host_batches = 0;
+    uint64_t before_finish = 0, blocked_us = 0, host_batches = 0, names_unique = 0;
     int pushes_in_flight = 0;
     bool finish_called = false, stop = false, cancel = false;
     int sticky_rc = OEM_OK;
@@ -223,15 +330,41 @@ struct oem_records_stream {
         a = Arena();
     }
 
+    // -- the names session (oem_records_stream_set_names) --------------------------------------------------------------
+    bool named = false;
+    uint64_t sort_check_num = 0;
+    // the carry: the open read's surviving records and its one name, on the device; its head and sizes on the host
+    DevBuf<oem_aln_record> carry;
+    DevBuf<uint8_t> carry_name;
+    uint64_t carry_cap = 0, carry_n = 0, carry_head = 0, carry_len = 0;
+    uint64_t n_unmapped = 0, n_parsed = 0;
+    // the collation check: the head names of the first closed groups until sort_check_num are held or finish comes
+    std::vector<std::unique_ptr<CheckChunk>> chk;
+    uint64_t chk_held = 0;
+    bool chk_done = false;
+    // what finish leaves for oem_records_stream_names_copy
+    bool names_ready = false;
+    std::vector<uint64_t> out_group_off, out_row_off;
+    std::vector<uint32_t> out_kept;
+    std::vector<uint8_t> out_rows;
+
     int run_batch(const Batch &b, Piece *out, bool *host);
-    int host_piece(const Batch &b, const char *who, Piece *out);
+    int run_batch_names(const Batch &b, Piece *out, bool *host);
+    int close_groups(const char *who, uint64_t rec_base, uint64_t n, const oem_aln_record *h_records,
+                     const oem_aln_record *d_in, const uint32_t *d_order, uint64_t p_last, const uint64_t *d_gb, uint64_t ngb, bool joins,
+                     const uint8_t *d_names, const uint64_t *d_name_off, Piece *out, bool *host);
+    int carry_append(const char *who, uint64_t rec_base, const oem_aln_record *h_records, const oem_aln_record *d_in, const uint32_t *d_order,
+                     uint64_t cnt);
+    int run_check(const char *who);
+    int names_close(const char *who);
+    int host_piece(const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, const char *who, Piece *out);
     void work();
     int join(const char *who, FilterResult *out, uint64_t *n_groups);
-    int finish_begin(const char *who);
+    int finish_begin(const char *who, bool names_form);
 };
 
 // The host loop on one batch (a fresh builder: bases 0), and its arrays uploaded as the piece.
-int oem_records_stream::host_piece(const Batch &b, const char *who, Piece *out)
+int oem_records_stream::host_piece(const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, const char *who, Piece *out)
 {
     FilterResult &r = out->r;
     r.row_ptr32.reset(); // (a device pass that met a big score has left n_kept behind)
@@ -239,8 +372,8 @@ int oem_records_stream::host_piece(const Batch &b, const char *who, Piece *out)
     oem_builder hb;
     hb.f = f;
     hb.txp_len = txp_len;
-    std::vector<uint32_t> kept(b.n_groups + 1, 0);
-    OEM_TRY(add_groups_host(&hb, b.records(), b.group_off(), b.n_groups, kept.data(), who));
+    std::vector<uint32_t> kept(n_groups + 1, 0);
+    OEM_TRY(add_groups_host(&hb, records, group_off, n_groups, kept.data(), who));
     const uint64_t nnz = hb.tid.size(), n_rows = hb.row_ptr.size() - 1;
     if (nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a resident store needs fewer than 2^32 alignments", who);
     std::vector<uint32_t> rp32(hb.row_ptr.begin(), hb.row_ptr.end());
@@ -250,7 +383,7 @@ int oem_records_stream::host_piece(const Batch &b, const char *who, Piece *out)
         return OEM_OK;
     };
     OEM_TRY(up(&r.row_ptr32, rp32.data(), n_rows + 1));
-    OEM_TRY(up(&r.n_kept, kept.data(), b.n_groups + 1));
+    OEM_TRY(up(&r.n_kept, kept.data(), n_groups + 1));
     OEM_TRY(up(&r.tid, hb.tid.data(), nnz));
     OEM_TRY(up(&r.as_prob, hb.as_prob.data(), nnz));
     if (o.model >= 0) {
@@ -278,7 +411,335 @@ int oem_records_stream::run_batch(const Batch &b, Piece *out, bool *host)
         if (!out->r.host_rerun) return OEM_OK;
     }
     *host = true;
-    return host_piece(b, who, out);
+    return host_piece(b.records(), b.group_off(), b.n_groups, who, out);
+}
+
+// ---- the names session's worker ("The names session") ---------------------------------------------
+
+namespace oem {
+namespace {
+
+// Copy jobs for one k_stream_concat launch.
+struct ConcatPlan {
+    std::vector<ConcatJob> jobs;
+    uint64_t n_blocks = 0;
+    void add(const void *src, void *dst, uint64_t n, uint32_t elem, uint64_t add_)
+    {
+        if (n == 0) return;
+        ConcatJob j{(const uint8_t *)src, (uint8_t *)dst, n * elem, n_blocks, add_, elem, 0};
+        n_blocks += concat_blocks(j);
+        jobs.push_back(j);
+    }
+    int run(const char *who, float *ms)
+    {
+        if (n_blocks > 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: the join needs %llu workgroups", who, (unsigned long long)n_blocks);
+        if (jobs.empty()) return OEM_OK;
+        DevBuf<ConcatJob> d_jobs;
+        Event ev[2];
+        OEM_TRY(dev_alloc(&d_jobs.p, jobs.size(), nullptr));
+        OEM_HIP(hipMemcpy(d_jobs.p, jobs.data(), sizeof(ConcatJob) * jobs.size(), hipMemcpyHostToDevice));
+        for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
+        OEM_HIP(hipEventRecord(ev[0].e, nullptr));
+        hipLaunchKernelGGL(k_stream_concat, dim3((uint32_t)n_blocks), dim3(kCT), 0, nullptr, d_jobs.p, (uint32_t)jobs.size());
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipEventRecord(ev[1].e, nullptr));
+        OEM_HIP(hipStreamSynchronize(nullptr));
+        if (ms) OEM_HIP(hipEventElapsedTime(ms, ev[0].e, ev[1].e));
+        return OEM_OK;
+    }
+};
+
+int bad_ref(const char *who, uint64_t record, uint32_t ref_id)
+{
+    return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)record, ref_id);
+}
+
+} // namespace
+} // namespace oem
+
+// The survivors order[0 .. cnt) of the batch behind the carry's records, their ref_ids checked first: the carry holds
+// only records the filter can take, so a ref_id error always names a record of the batch that is being worked on.
+// The buffer doubles: a read that spans many batches is copied a constant number of times per record.
+int oem_records_stream::carry_append(const char *who, uint64_t rec_base, const oem_aln_record *h_records, const oem_aln_record *d_in,
+                                     const uint32_t *d_order, uint64_t cnt)
+{
+    if (!cnt) return OEM_OK;
+    if (carry_n + cnt > 0xffffffffull)
+        return fail(OEM_ERR_ARG, "%s: the read that starts at record %llu has more than 2^32 - 1 records", who, (unsigned long long)carry_head);
+    DevBuf<unsigned long long> d_bad;
+    unsigned long long bad = kNoRecord;
+    OEM_TRY(dev_alloc(&d_bad.p, 1, nullptr));
+    OEM_HIP(hipMemcpy(d_bad.p, &bad, sizeof bad, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_names_ref_check, names_grid(cnt), dim3(kCT), 0, nullptr, cnt, d_order, (const uint64_t *)d_in, o.n_txps, d_bad.p);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad != kNoRecord) return bad_ref(who, rec_base + bad, h_records[bad].ref_id);
+    if (carry_n + cnt > carry_cap) {
+        const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * carry_cap, carry_n + cnt), 64);
+        DevBuf<oem_aln_record> grown;
+        OEM_TRY(dev_alloc(&grown.p, cap, nullptr));
+        if (carry_n) OEM_HIP(hipMemcpy(grown.p, carry.p, sizeof(oem_aln_record) * carry_n, hipMemcpyDeviceToDevice));
+        std::swap(grown.p, carry.p);
+        carry_cap = cap;
+    }
+    OEM_TRY(records_gather(cnt, d_order, d_in, carry.p + carry_n));
+    carry_n += cnt;
+    return OEM_OK;
+}
+
+// The session's collation check, once: the held head names joined into one blob (k_stream_concat) and the one call's
+// check run over them.  The checked groups are the session's first ones, so the check's indices are group numbers.
+int oem_records_stream::run_check(const char *who)
+{
+    chk_done = true;
+    const uint64_t nchk = chk_held;
+    uint64_t n_bytes = 0;
+    for (const auto &c : chk) n_bytes += c->bytes;
+    if (nchk > 1) {
+        DevBuf<uint8_t> blob;
+        DevBuf<uint64_t> off, heads;
+        OEM_TRY(dev_alloc(&blob.p, n_bytes + 16, nullptr));
+        OEM_TRY(dev_alloc(&off.p, nchk + 1, nullptr));
+        OEM_TRY(dev_alloc(&heads.p, nchk, nullptr));
+        OEM_HIP(hipMemset(blob.p + n_bytes, 0, 16));
+        OEM_HIP(hipMemset(off.p, 0, sizeof(uint64_t)));
+        ConcatPlan plan;
+        uint64_t k0 = 0, b0 = 0;
+        for (const auto &c : chk) {
+            plan.add(c->blob.p, blob.p + b0, c->bytes, 1, 0);
+            plan.add(c->off.p + 1, off.p + k0 + 1, c->k, 8, b0);
+            plan.add(c->heads.p, heads.p + k0, c->k, 8, 0);
+            k0 += c->k;
+            b0 += c->bytes;
+        }
+        OEM_TRY(plan.run(who, nullptr));
+        uint64_t found = ~0ull;
+        OEM_TRY(parse_check_repeat(who, blob.p, off.p, n_bytes, nchk, &found));
+        if (found != ~0ull) {
+            const uint64_t g = found >> 32, earlier = found & 0xffffffffull;
+            uint64_t rec_g = 0, rec_e = 0;
+            OEM_HIP(hipMemcpy(&rec_g, heads.p + g, sizeof rec_g, hipMemcpyDeviceToHost));
+            OEM_HIP(hipMemcpy(&rec_e, heads.p + earlier, sizeof rec_e, hipMemcpyDeviceToHost));
+            chk.clear();
+            return parse_not_collated(who, g, rec_g, rec_e);
+        }
+    }
+    chk.clear();
+    return OEM_OK;
+}
+
+// The groups a batch closes, filtered into its piece.  The batch: n records on the device (d_in) and in its arena
+// (h_records), its survivors' input indices d_order, its own cut d_gb (ngb runs, the last one starting at survivor
+// p_last), its names with the carry's name as record n + 1 (d_names / d_name_off).  Closed are the carry (with the
+// batch's first run when `joins`) and every run but the last; finish closes the carry alone (n = 0, one empty run).
+int oem_records_stream::close_groups(const char *who, uint64_t rec_base, uint64_t n, const oem_aln_record *h_records,
+                                     const oem_aln_record *d_in, const uint32_t *d_order, uint64_t p_last, const uint64_t *d_gb, uint64_t ngb,
+                                     bool joins, const uint8_t *d_names, const uint64_t *d_name_off, Piece *out, bool *host)
+{
+    const uint64_t c = carry_n;
+    const uint32_t carry_rec = (uint32_t)(n + 1), shift = c > 0 && !joins ? 1u : 0u;
+    const uint64_t nc = ngb - 1 + shift, tot = c + p_last;
+    if (nc == 0) return OEM_OK;
+    if (nc >= 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: at most 2^31 - 2 reads per batch", who);
+    DevBuf<oem_aln_record> d_comb; // the closed groups' records: the carry's, then the batch's survivors before its last run
+    DevBuf<uint32_t> d_head;
+    OEM_TRY(dev_alloc(&d_comb.p, tot, nullptr));
+    OEM_TRY(dev_alloc(&d_head.p, nc, nullptr));
+    OEM_TRY(dev_alloc(&out->group_off.p, nc + 1, nullptr));
+    if (c) OEM_HIP(hipMemcpy(d_comb.p, carry.p, sizeof(oem_aln_record) * c, hipMemcpyDeviceToDevice));
+    if (p_last) OEM_TRY(records_gather(p_last, d_order, d_in, d_comb.p + c));
+    hipLaunchKernelGGL(k_names_splice, names_grid(nc + 1), dim3(kCT), 0, nullptr, nc, c, shift, c > 0 ? 1u : 0u, d_gb, d_order, carry_rec,
+                       out->group_off.p, d_head.p);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    out->n_groups = nc;
+    out->n_records = tot;
+
+    // the collation check's share: the head names of the session's first sort_check_num groups
+    if (sort_check_num && !chk_done && chk_held < sort_check_num) {
+        std::unique_ptr<CheckChunk> ch(new CheckChunk());
+        ch->k = std::min<uint64_t>(sort_check_num - chk_held, nc);
+        OEM_TRY(gather_input_names(d_head.p, ch->k, d_names, d_name_off, &ch->off, &ch->blob, &ch->bytes));
+        OEM_TRY(dev_alloc(&ch->heads.p, ch->k, nullptr));
+        hipLaunchKernelGGL(k_names_heads64, names_grid(ch->k), dim3(kCT), 0, nullptr, ch->k, (const uint32_t *)d_head.p, carry_rec, carry_head,
+                           rec_base, ch->heads.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipStreamSynchronize(nullptr));
+        chk_held += ch->k;
+        chk.push_back(std::move(ch));
+        if (chk_held == sort_check_num) OEM_TRY(run_check(who));
+    }
+
+    // the filter over the closed groups as one cell; the host loop where the records session's would take the batch
+    FilterResult &r = out->r;
+    bool on_host = host_only;
+    if (!on_host) {
+        FilterCells fc;
+        fc.n_cells = 1;
+        DevBuf<unsigned long long> d_cell;
+        const unsigned long long cell[2] = {0, nc};
+        OEM_TRY(dev_alloc(&d_cell.p, 2, nullptr));
+        OEM_HIP(hipMemcpy(d_cell.p, cell, sizeof cell, hipMemcpyHostToDevice));
+        OEM_TRY(filter_device_resident(who, f, txp_len.data(), o.n_txps, tab, d_comb.p, (const unsigned long long *)out->group_off.p, nc,
+                                       d_cell.p, o.model >= 0, &r, &fc));
+        if (r.bad_ref_record != kNoRecord) { // (never one of the carry's: carry_append has checked those)
+            if (r.bad_ref_record < c || !d_order) return fail(OEM_ERR_ARG, "%s: a carried record's ref_id is not below n_txps", who);
+            uint32_t at = 0;
+            OEM_HIP(hipMemcpy(&at, d_order + (r.bad_ref_record - c), sizeof at, hipMemcpyDeviceToHost));
+            return bad_ref(who, rec_base + at, h_records[at].ref_id);
+        }
+        on_host = r.host_rerun;
+    }
+    if (on_host) { // the closed groups' records and offsets come down; the piece is uploaded
+        *host = true;
+        std::vector<oem_aln_record> recs(tot);
+        std::vector<uint64_t> goff(nc + 1);
+        if (tot) OEM_HIP(hipMemcpy(recs.data(), d_comb.p, sizeof(oem_aln_record) * tot, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(goff.data(), out->group_off.p, sizeof(uint64_t) * (nc + 1), hipMemcpyDeviceToHost));
+        for (uint64_t k = c; k < tot; ++k) {
+            if (recs[k].ref_id < o.n_txps) continue;
+            uint32_t at = 0;
+            OEM_HIP(hipMemcpy(&at, d_order + (k - c), sizeof at, hipMemcpyDeviceToHost));
+            return bad_ref(who, rec_base + at, recs[k].ref_id);
+        }
+        OEM_TRY(host_piece(recs.data(), goff.data(), nc, who, out));
+    }
+    d_comb.reset();
+    r.txp_len.reset(); // (the join uploads the lengths once)
+
+    // unique_alignments' share and the rows' names
+    OEM_TRY(parse_count_unique(nc, r.n_kept.p, &out->unique));
+    if (r.n_rows) {
+        DevBuf<uint64_t> d_row_idx;
+        DevBuf<uint32_t> d_row_head;
+        OEM_TRY(dev_alloc(&d_row_idx.p, nc + 1, nullptr));
+        OEM_TRY(dev_alloc(&d_row_head.p, r.n_rows, nullptr));
+        OEM_TRY(parse_row_index(r.n_kept.p, nc + 1, d_row_idx.p)); // (n_kept has nc + 1 entries, the last one 0)
+        hipLaunchKernelGGL(k_names_row_heads, names_grid(nc), dim3(kCT), 0, nullptr, nc, (const uint32_t *)r.n_kept.p,
+                           (const uint64_t *)d_row_idx.p, (const uint32_t *)d_head.p, d_row_head.p);
+        OEM_HIP(hipGetLastError());
+        OEM_TRY(gather_input_names(d_row_head.p, r.n_rows, d_names, d_name_off, &out->row_off, &out->rows, &out->row_bytes));
+    }
+    return OEM_OK;
+}
+
+// One batch of a names session: upload from the arena, the survivors, their names checked, the adjacent cut, the carry
+// spliced in, the closed groups filtered into the piece, the last run carried on.
+int oem_records_stream::run_batch_names(const Batch &b, Piece *out, bool *host)
+{
+    const uint64_t n = b.n_records;
+    if (n == 0) return OEM_OK;
+    char who[64];
+    snprintf(who, sizeof who, "oem_records_stream: ticket %llu", (unsigned long long)b.ticket);
+    const uint64_t n_bytes = b.name_bytes, L = carry_n ? carry_len : 0;
+    // the batch's names, 16 zero bytes (record n: never read), the carry's name as record n + 1, 16 zero bytes
+    DevBuf<oem_aln_record> d_in;
+    DevBuf<uint8_t> d_names;
+    DevBuf<uint64_t> d_name_off;
+    OEM_TRY(dev_alloc(&d_in.p, n, nullptr));
+    OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16 + L + 16, nullptr));
+    OEM_TRY(dev_alloc(&d_name_off.p, n + 3, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_in.p, b.named_records(), sizeof(oem_aln_record) * n, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_name_off.p, b.name_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
+    if (n_bytes) OEM_HIP(hipMemcpyAsync(d_names.p, b.names(), n_bytes, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemsetAsync(d_names.p + n_bytes, 0, 16, nullptr));
+    OEM_HIP(hipMemsetAsync(d_names.p + n_bytes + 16 + L, 0, 16, nullptr));
+    if (L) OEM_HIP(hipMemcpyAsync(d_names.p + n_bytes + 16, carry_name.p, L, hipMemcpyDeviceToDevice, nullptr));
+    const uint64_t tail[2] = {n_bytes + 16, n_bytes + 16 + L};
+    OEM_HIP(hipMemcpy(d_name_off.p + n + 1, tail, sizeof tail, hipMemcpyHostToDevice));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+
+    DevBuf<uint32_t> d_order;
+    uint64_t m = 0;
+    OEM_TRY(parse_survivors(d_in.p, n, true, &d_order, &m));
+    n_unmapped += n - m;
+    n_parsed += m;
+    if (m == 0) return OEM_OK;
+    const bool dense = m < n;
+    CollateResident cr;
+    {
+        DevBuf<uint8_t> d_dense, d_dense_sec;
+        DevBuf<uint64_t> d_dense_off;
+        uint64_t dense_bytes = n_bytes, bad_record = kNoRecord;
+        bool zero_byte = false;
+        OEM_TRY(parse_survivor_names(d_names.p, n_bytes, d_name_off.p, n, dense ? d_order.p : nullptr, m, nullptr, &d_dense, &d_dense_off,
+                                     &d_dense_sec, &dense_bytes, &bad_record, &zero_byte));
+        if (bad_record != kNoRecord) return parse_bad_name(who, zero_byte, b.rec_base + bad_record);
+        const uint64_t one_cell[2] = {0, m};
+        CollateInput in;
+        in.who = who;
+        in.cell_rec_off = one_cell;
+        in.mode = kCollateAdjacent;
+        in.chunk_bytes = collate_chunk_bytes();
+        in.d_names = dense ? d_dense.p : d_names.p;
+        in.d_name_off = dense ? d_dense_off.p : d_name_off.p;
+        in.d_n_bytes = dense_bytes;
+        double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        OEM_TRY(collate_resident(in, 0, 1, 0, 0, 0, info, &cr));
+    }
+    cr.order.reset(); // (positions among the survivors: under ADJACENT the identity)
+    const uint64_t ngb = cr.n_groups;
+    uint64_t p_last = 0;
+    OEM_HIP(hipMemcpy(&p_last, cr.group_off.p + (ngb - 1), sizeof p_last, hipMemcpyDeviceToHost));
+    bool joins = false;
+    if (carry_n) {
+        DevBuf<uint32_t> d_eq;
+        uint32_t eq = 0;
+        OEM_TRY(dev_alloc(&d_eq.p, 1, nullptr));
+        hipLaunchKernelGGL(k_names_equal, dim3(1), dim3(kCT), 0, nullptr, (const uint8_t *)d_names.p, (const uint64_t *)d_name_off.p,
+                           (const uint32_t *)d_order.p, n + 1, d_eq.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(&eq, d_eq.p, sizeof eq, hipMemcpyDeviceToHost));
+        joins = eq != 0;
+    }
+    if (ngb == 1 && joins) // the whole batch is more of the open read
+        return carry_append(who, b.rec_base, b.named_records(), d_in.p, d_order.p, m);
+    OEM_TRY(close_groups(who, b.rec_base, n, b.named_records(), d_in.p, d_order.p, p_last, cr.group_off.p, ngb, joins, d_names.p,
+                         d_name_off.p, out, host));
+    // the batch's last run is the new carry: its head's index comes down, its name stays on the device
+    uint32_t last_head = 0;
+    OEM_HIP(hipMemcpy(&last_head, d_order.p + p_last, sizeof last_head, hipMemcpyDeviceToHost));
+    const uint64_t off0 = b.name_off()[last_head], len = b.name_off()[last_head + 1] - off0;
+    carry_n = 0;
+    carry_head = b.rec_base + last_head;
+    carry_name.reset();
+    OEM_TRY(dev_alloc(&carry_name.p, len, nullptr));
+    OEM_HIP(hipMemcpy(carry_name.p, d_names.p + off0, len, hipMemcpyDeviceToDevice));
+    carry_len = len;
+    return carry_append(who, b.rec_base, b.named_records(), d_in.p, d_order.p + p_last, m - p_last);
+}
+
+// What a names session's finish does between the worker's end and the join: the carry closes as a last piece, and the
+// collation check runs if fewer than sort_check_num groups were ever held.
+int oem_records_stream::names_close(const char *who)
+{
+    if (!named) return OEM_OK;
+    if (carry_n) {
+        const uint64_t L = carry_len, off[3] = {0, 16, 16 + L}, gb[1] = {0};
+        DevBuf<uint8_t> d_names;
+        DevBuf<uint64_t> d_name_off, d_gb;
+        OEM_TRY(dev_alloc(&d_names.p, 16 + L + 16, nullptr));
+        OEM_TRY(dev_alloc(&d_name_off.p, 3, nullptr));
+        OEM_TRY(dev_alloc(&d_gb.p, 1, nullptr));
+        OEM_HIP(hipMemset(d_names.p, 0, 16 + L + 16));
+        OEM_HIP(hipMemcpy(d_names.p + 16, carry_name.p, L, hipMemcpyDeviceToDevice));
+        OEM_HIP(hipMemcpy(d_name_off.p, off, sizeof off, hipMemcpyHostToDevice));
+        OEM_HIP(hipMemcpy(d_gb.p, gb, sizeof gb, hipMemcpyHostToDevice));
+        std::unique_ptr<Piece> piece(new Piece());
+        bool host = false;
+        OEM_TRY(close_groups(who, total_records, 0, nullptr, nullptr, nullptr, 0, d_gb.p, 1, false, d_names.p, d_name_off.p,
+                             piece.get(), &host));
+        total_kept += piece->r.nnz;
+        total_groups += piece->n_groups;
+        if (host) ++host_batches;
+        pieces.push_back(std::move(piece));
+        carry_n = 0;
+        carry.reset();
+        carry_name.reset();
+        carry_cap = 0;
+    }
+    if (sort_check_num && !chk_done) OEM_TRY(run_check(who));
+    return OEM_OK;
 }
 
 void oem_records_stream::work()
@@ -304,7 +765,7 @@ void oem_records_stream::work()
         if (!skip) {
             try {
                 piece.reset(new Piece());
-                rc = run_batch(*b, piece.get(), &host);
+                rc = b->named ? run_batch_names(*b, piece.get(), &host) : run_batch(*b, piece.get(), &host);
             } catch (const std::bad_alloc &) {
                 rc = fail(OEM_ERR_OOM, "oem_records_stream: host allocation failed in the device worker");
             } catch (const std::exception &e) {
@@ -323,6 +784,7 @@ void oem_records_stream::work()
                 set_sticky(rc, msg.c_str());
             } else if (!skip) {
                 total_kept += piece->r.nnz;
+                if (b->named) total_groups += piece->n_groups;
                 if (host) ++host_batches;
                 if (total_kept >= (1ull << 32))
                     set_sticky(OEM_ERR_ARG, "oem_records_stream: 2^32 or more alignments are kept; a resident store needs fewer");
@@ -362,45 +824,54 @@ int oem_records_stream::join(const char *who, FilterResult *out, uint64_t *n_gro
     OEM_HIP(hipMemcpy(out->txp_len.p, txp_len.data(), sizeof(uint64_t) * o.n_txps, hipMemcpyHostToDevice));
     OEM_HIP(hipMemset(out->row_ptr32.p, 0, sizeof(uint32_t)));
 
-    std::vector<ConcatJob> jobs;
-    uint64_t n_blocks = 0;
-    auto add_job = [&](const void *src, void *dst, uint64_t n, uint32_t elem, uint32_t add) {
-        if (n == 0) return;
-        ConcatJob j{(const uint8_t *)src, (uint8_t *)dst, n * elem, n_blocks, add, elem};
-        n_blocks += concat_blocks(j);
-        jobs.push_back(j);
-    };
+    // a names session: group_off, the row names and their offsets are joined in the same launch
+    DevBuf<uint64_t> d_goff, d_row_off;
+    DevBuf<uint8_t> d_rows;
+    uint64_t B = 0;
+    if (named) {
+        for (const auto &p : pieces) B += p->row_bytes;
+        OEM_TRY(dev_alloc(&d_goff.p, G + 1, nullptr));
+        OEM_TRY(dev_alloc(&d_row_off.p, R + 1, nullptr));
+        OEM_TRY(dev_alloc(&d_rows.p, B, nullptr));
+        OEM_HIP(hipMemset(d_goff.p, 0, sizeof(uint64_t)));
+        OEM_HIP(hipMemset(d_row_off.p, 0, sizeof(uint64_t)));
+    }
+
+    ConcatPlan plan;
     uint64_t *sum = &out->dt.discard_5p;
-    uint64_t r0 = 0, a0 = 0, g0 = 0; // the piece's row, alignment and group base
+    uint64_t r0 = 0, a0 = 0, g0 = 0, p0 = 0, b0 = 0; // the piece's row, alignment, group, record and row-name byte base
     for (const auto &p : pieces) {
         const FilterResult &r = p->r;
-        add_job(r.n_kept.p, out->n_kept.p + g0, p->n_groups, 4, 0);
-        add_job(r.row_ptr32.p + 1, out->row_ptr32.p + r0 + 1, r.n_rows, 4, (uint32_t)a0);
-        add_job(r.tid.p, out->tid.p + a0, r.nnz, 4, 0);
-        add_job(r.as_prob.p, out->as_prob.p + a0, r.nnz, 4, 0);
+        plan.add(r.n_kept.p, out->n_kept.p + g0, p->n_groups, 4, 0);
+        plan.add(r.row_ptr32.p + 1, out->row_ptr32.p + r0 + 1, r.n_rows, 4, (uint32_t)a0);
+        plan.add(r.tid.p, out->tid.p + a0, r.nnz, 4, 0);
+        plan.add(r.as_prob.p, out->as_prob.p + a0, r.nnz, 4, 0);
         if (coords) {
-            add_job(r.start.p, out->start.p + a0, r.nnz, 4, 0);
-            add_job(r.end.p, out->end.p + a0, r.nnz, 4, 0);
-            add_job(r.strand.p, out->strand.p + a0, r.nnz, 1, 0);
+            plan.add(r.start.p, out->start.p + a0, r.nnz, 4, 0);
+            plan.add(r.end.p, out->end.p + a0, r.nnz, 4, 0);
+            plan.add(r.strand.p, out->strand.p + a0, r.nnz, 1, 0);
+        }
+        if (named && p->n_groups) {
+            plan.add(p->group_off.p + 1, d_goff.p + g0 + 1, p->n_groups, 8, p0);
+            plan.add(p->row_off.p + 1, d_row_off.p + r0 + 1, r.n_rows, 8, b0);
+            plan.add(p->rows.p, d_rows.p + b0, p->row_bytes, 1, 0);
         }
         for (int k = 0; k < kFilterCounters; ++k) sum[k] += (&r.dt.discard_5p)[k];
+        names_unique += p->unique;
         r0 += r.n_rows;
         a0 += r.nnz;
         g0 += p->n_groups;
+        p0 += p->n_records;
+        b0 += p->row_bytes;
     }
-    if (n_blocks > 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: the join needs %llu workgroups", who, (unsigned long long)n_blocks);
-    if (!jobs.empty()) {
-        DevBuf<ConcatJob> d_jobs;
-        Event ev[2];
-        OEM_TRY(dev_alloc(&d_jobs.p, jobs.size(), nullptr));
-        OEM_HIP(hipMemcpy(d_jobs.p, jobs.data(), sizeof(ConcatJob) * jobs.size(), hipMemcpyHostToDevice));
-        for (auto &e : ev) OEM_HIP(hipEventCreate(&e.e));
-        OEM_HIP(hipEventRecord(ev[0].e, nullptr));
-        hipLaunchKernelGGL(k_stream_concat, dim3((uint32_t)n_blocks), dim3(kCT), 0, nullptr, d_jobs.p, (uint32_t)jobs.size());
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipEventRecord(ev[1].e, nullptr));
-        OEM_HIP(hipStreamSynchronize(nullptr));
-        OEM_HIP(hipEventElapsedTime(&g_join_ms, ev[0].e, ev[1].e));
+    OEM_TRY(plan.run(who, &g_join_ms));
+    if (named) { // the variable-length outputs stay with the session (oem_records_stream_names_copy)
+        out_group_off.resize(G + 1);
+        out_row_off.resize(R + 1);
+        out_rows.resize(B);
+        OEM_HIP(hipMemcpy(out_group_off.data(), d_goff.p, sizeof(uint64_t) * (G + 1), hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(out_row_off.data(), d_row_off.p, sizeof(uint64_t) * (R + 1), hipMemcpyDeviceToHost));
+        if (B) OEM_HIP(hipMemcpy(out_rows.data(), d_rows.p, B, hipMemcpyDeviceToHost));
     }
     pieces.clear();
     *n_groups = G;
@@ -408,10 +879,14 @@ int oem_records_stream::join(const char *who, FilterResult *out, uint64_t *n_gro
 }
 
 // What finish does before the join: the state checks, then the worker drains the queue and is joined.
-int oem_records_stream::finish_begin(const char *who)
+int oem_records_stream::finish_begin(const char *who, bool names_form)
 {
     {
         std::lock_guard<std::mutex> lk(mu);
+        if (named && names_form && sticky_rc != OEM_OK) return fail(sticky_rc, "%s", sticky_msg.c_str()); // (sticky: every later call)
+        if (named != names_form)
+            return fail(OEM_ERR_STATE, names_form ? "%s: not a names session (oem_records_stream_set_names)"
+                                                  : "%s: a names session is finished by oem_records_stream_finish_names", who);
         if (finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished already", who);
         if (pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a push is in flight", who);
         finish_called = true;
@@ -449,27 +924,29 @@ extern "C" int oem_records_stream_create(const oem_records_stream_opts *opts, co
     OEM_API_END("oem_records_stream_create")
 }
 
-extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_record *records, const uint64_t *group_off,
-                                       uint64_t n_groups, uint64_t *out_ticket)
-{
-    OEM_API_BEGIN
-    const char *who = "oem_records_stream_push";
-    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
-    // the batch's own checks, on the calling thread, before the session is touched
-    OEM_TRY(check_group_off(who, records, group_off, n_groups));
-    if (n_groups >= 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: at most 2^31 - 2 groups per batch", who);
-    const uint64_t n_records = group_off[n_groups];
-    const size_t rec_at = Batch::records_at(n_groups), bytes = rec_at + sizeof(oem_aln_record) * n_records;
+namespace oem {
+namespace {
 
+// What both pushes do once the batch's own checks have passed: wait for room in the staging budget, take the ticket
+// under the session lock, then -- outside it -- find an arena of `bytes` and let fill(arena) copy the caller's arrays.
+// named: the batch of a names session (n_groups 0, name_bytes = name_off[n_records]); a batch has a payload when
+// `bytes` > 0.
+template <typename Fill>
+int stage_batch(oem_records_stream *s, const char *who, bool named, uint64_t n_groups, uint64_t n_records, uint64_t name_bytes, size_t bytes,
+                Fill &&fill, uint64_t *out_ticket)
+{
     Batch *b = nullptr;
     {
         std::unique_lock<std::mutex> lk(s->mu);
+        if (s->named != named)
+            return fail(OEM_ERR_STATE, named ? "%s: not a names session (oem_records_stream_set_names)" : "%s: a names session takes oem_records_stream_push_names", who);
         ++s->pushes_in_flight;
         struct InFlight { // (mu is held whenever this scope is left)
             oem_records_stream *s;
             ~InFlight() { --s->pushes_in_flight; }
         } in_flight{s};
         for (;;) {
+            if (named && s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str()); // (a names session: before all else)
             if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
             if (s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str());
             if (s->staged_records == 0 || s->staged_records + n_records <= s->max_staged) break;
@@ -478,11 +955,14 @@ extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_reco
             s->blocked_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
         }
         std::unique_ptr<Batch> nb(new Batch());
-        s->pieces.reserve(s->pieces.size() + 1); // (so that taking the ticket below cannot throw half-way)
+        s->pieces.reserve(s->pieces.size() + 2); // (so that taking the ticket below cannot throw half-way; + the carry's piece)
         nb->ticket = s->next_ticket;
         nb->n_groups = n_groups;
         nb->n_records = n_records;
-        if (n_groups) nb->mem = s->take_arena(bytes);
+        nb->named = named;
+        nb->rec_base = s->total_records;
+        nb->name_bytes = name_bytes;
+        if (bytes) nb->mem = s->take_arena(bytes);
         b = nb.get();
         s->queue.push_back(std::move(nb));
         s->pieces.emplace_back();
@@ -495,7 +975,7 @@ extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_reco
     // outside the lock: the arena, where the pool had none, and the copies.  The batch stays in the queue until it is
     // ready (the worker waits for that), so `b` is valid.
     bool oom = false;
-    if (!b->mem.p && n_groups) {
+    if (!b->mem.p && bytes) {
         const size_t cap = bytes + bytes / 8 + 4096; // (batches of a run are of one size, more or less)
         if (hipSetDevice(s->o.device) == hipSuccess && hipHostMalloc(&b->mem.p, cap, hipHostMallocPortable) == hipSuccess) {
             b->mem.pinned = true;
@@ -506,10 +986,7 @@ extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_reco
         }
         b->mem.bytes = cap;
     }
-    if (b->mem.p) {
-        std::memcpy(b->mem.p, group_off, sizeof(uint64_t) * (n_groups + 1));
-        if (n_records) std::memcpy((char *)b->mem.p + rec_at, records, sizeof(oem_aln_record) * n_records);
-    }
+    if (b->mem.p) fill((char *)b->mem.p);
     const uint64_t ticket = b->ticket;
     {
         std::lock_guard<std::mutex> lk(s->mu);
@@ -521,7 +998,64 @@ extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_reco
     if (oom) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who);
     if (out_ticket) *out_ticket = ticket;
     return OEM_OK;
+}
+
+} // namespace
+} // namespace oem
+
+extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_record *records, const uint64_t *group_off,
+                                       uint64_t n_groups, uint64_t *out_ticket)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_push";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    // the batch's own checks, on the calling thread, before the session is touched
+    OEM_TRY(check_group_off(who, records, group_off, n_groups));
+    if (n_groups >= 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: at most 2^31 - 2 groups per batch", who);
+    const uint64_t n_records = group_off[n_groups];
+    const size_t rec_at = Batch::records_at(n_groups), bytes = rec_at + sizeof(oem_aln_record) * n_records;
+    return stage_batch(s, who, false, n_groups, n_records, 0, n_groups ? bytes : 0, [&](char *mem) {
+        std::memcpy(mem, group_off, sizeof(uint64_t) * (n_groups + 1));
+        if (n_records) std::memcpy(mem + rec_at, records, sizeof(oem_aln_record) * n_records);
+    }, out_ticket);
     OEM_API_END("oem_records_stream_push")
+}
+
+extern "C" int oem_records_stream_set_names(oem_records_stream *s, uint64_t sort_check_num)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_set_names";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session already", who);
+    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    s->named = true;
+    s->sort_check_num = sort_check_num;
+    return OEM_OK;
+    OEM_API_END("oem_records_stream_set_names")
+}
+
+extern "C" int oem_records_stream_push_names(oem_records_stream *s, const oem_aln_record *records, uint64_t n_records, const uint8_t *names,
+                                             const uint64_t *name_off, uint64_t *out_ticket)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_push_names";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    // the batch's own checks, on the calling thread, before the session is touched
+    if (!name_off) return fail(OEM_ERR_ARG, "%s: name_off is NULL", who);
+    const uint64_t n = n_records, whole[2] = {0, n};
+    if (n > kCollateMaxBatch) return fail(OEM_ERR_ARG, "%s: %llu records: at most 2^31 - 2 per batch", who, (unsigned long long)n);
+    OEM_TRY(check_collate_input(who, names, name_off, n, whole, 1, kCollateAdjacent));
+    if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+    const uint64_t n_bytes = name_off[n];
+    const size_t rec_at = Batch::records_at(n), names_at = Batch::names_at(n), bytes = names_at + n_bytes;
+    return stage_batch(s, who, true, 0, n, n_bytes, n ? bytes : 0, [&](char *mem) {
+        std::memcpy(mem, name_off, sizeof(uint64_t) * (n + 1));
+        std::memcpy(mem + rec_at, records, sizeof(oem_aln_record) * n);
+        if (n_bytes) std::memcpy(mem + names_at, names, n_bytes);
+    }, out_ticket);
+    OEM_API_END("oem_records_stream_push_names")
 }
 
 extern "C" int oem_records_stream_finish(oem_records_stream *s, const oem_store_opts *opts, uint32_t *out_kept,
@@ -533,13 +1067,66 @@ extern "C" int oem_records_stream_finish(oem_records_stream *s, const oem_store_
     *out = nullptr;
     if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
     OEM_TRY(check_store_from_records(who, &s->f, s->txp_len.data(), s->o.n_txps, s->o.bin_width, s->o.model, opts));
-    OEM_TRY(s->finish_begin(who));
+    OEM_TRY(s->finish_begin(who, false));
     FilterResult r;
     uint64_t n_groups = 0;
     OEM_TRY(s->join(who, &r, &n_groups));
     return filter_result_to_store(who, r, s->o.n_txps, n_groups, s->o.bin_width, s->o.model, s->o.growth_rate, s->o.device, opts,
                                   out_kept, out_discard, out);
     OEM_API_END("oem_records_stream_finish")
+}
+
+extern "C" int oem_records_stream_finish_names(oem_records_stream *s, const oem_store_opts *opts, oem_discard_table *out_discard,
+                                               oem_parse_info *out_info, oem_store **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_finish_names";
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    OEM_TRY(check_store_from_records(who, &s->f, s->txp_len.data(), s->o.n_txps, s->o.bin_width, s->o.model, opts));
+    OEM_TRY(s->finish_begin(who, true));
+    OEM_TRY(s->names_close(who));
+    FilterResult r;
+    uint64_t n_groups = 0;
+    OEM_TRY(s->join(who, &r, &n_groups));
+    oem_parse_info pi;
+    std::memset(&pi, 0, sizeof pi);
+    pi.n_unmapped = s->n_unmapped;
+    pi.n_parsed = s->n_parsed;
+    pi.n_groups = n_groups;
+    pi.n_reads = r.n_rows;
+    pi.unique_alignments = s->names_unique;
+    pi.n_checked = s->sort_check_num ? std::min<uint64_t>(s->sort_check_num, n_groups) : 0;
+    s->out_kept.assign(n_groups + 1, 0);
+    OEM_TRY(filter_result_to_store(who, r, s->o.n_txps, n_groups, s->o.bin_width, s->o.model, s->o.growth_rate, s->o.device, opts,
+                                   s->out_kept.data(), out_discard, out));
+    s->out_kept.resize(n_groups);
+    if (out_info) *out_info = pi;
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->names_ready = true;
+    return OEM_OK;
+    OEM_API_END("oem_records_stream_finish_names")
+}
+
+extern "C" int oem_records_stream_names_copy(const oem_records_stream *s, uint64_t *out_group_off, uint32_t *out_kept, uint8_t *out_row_names,
+                                             uint64_t *out_row_name_off)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_names_copy";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if ((out_row_names == nullptr) != (out_row_name_off == nullptr))
+        return fail(OEM_ERR_ARG, "%s: out_row_names and out_row_name_off must both be NULL or both be given", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->names_ready) return fail(OEM_ERR_STATE, "%s: no names session has been finished", who);
+    if (out_group_off) std::memcpy(out_group_off, s->out_group_off.data(), sizeof(uint64_t) * s->out_group_off.size());
+    if (out_kept && !s->out_kept.empty()) std::memcpy(out_kept, s->out_kept.data(), sizeof(uint32_t) * s->out_kept.size());
+    if (out_row_names) {
+        if (!s->out_rows.empty()) std::memcpy(out_row_names, s->out_rows.data(), s->out_rows.size());
+        std::memcpy(out_row_name_off, s->out_row_off.data(), sizeof(uint64_t) * s->out_row_off.size());
+    }
+    return OEM_OK;
+    OEM_API_END("oem_records_stream_names_copy")
 }
 
 namespace oem {
@@ -554,7 +1141,8 @@ int records_stream_finish_csr(oem_records_stream *s, uint64_t *dims3, const uint
 {
     const char *who = "oem_debug_records_stream_finish_csr";
     if (!s || !dims3 || !caps3) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
-    OEM_TRY(s->finish_begin(who));
+    OEM_TRY(s->finish_begin(who, s->named));
+    OEM_TRY(s->names_close(who)); // (a names session: the carry's piece and the check; the joined CSR is the same kind)
     FilterResult r;
     uint64_t n_groups = 0;
     OEM_TRY(s->join(who, &r, &n_groups));
@@ -595,6 +1183,7 @@ extern "C" int oem_records_stream_info(const oem_records_stream *s, uint32_t key
     case OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH: *value = s->before_finish; break;
     case OEM_RECORDS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us; break;
     case OEM_RECORDS_STREAM_INFO_HOST_BATCHES: *value = s->host_batches; break;
+    case OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES: *value = s->out_rows.size(); break;
     default: return fail(OEM_ERR_ARG, "oem_records_stream_info: unknown key %u", key);
     }
     return OEM_OK;

@@ -11,7 +11,13 @@ synth.make_named_records, 83.7 M records, per name style (UUID, Illumina-style):
 
 A warm-up on a slice, then --runs repeats (default five) of (a), (b), (c) in alternation; best and worst of each,
 (a) - (c) -- what the names cost on the device -- and (a) / (b).  The result goes to --out as JSON, rewritten after every
-measurement.  --reads / --txps shrink the shape for a trial run."""
+measurement.  --reads / --txps shrink the shape for a trial run.
+
+--stream is the names session's leg instead (RecordsStream(names=True), oem_records_stream_push_names): the same input
+cut at record positions into batches of 2^18 and of 2^20 groups' worth of records (--batch-groups), pushed from one
+thread; seconds from the first push to the end of finish, beside the one call (ADJACENT) timed in the same run, --runs
+repeats in alternation, and for both the peak of the device memory above the level at entry.  The result goes to
+profiles/records_names_stream_bench.json."""
 import argparse
 import json
 import os
@@ -26,6 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import oarfish_amd  # noqa: E402
 from oarfish_amd import synth  # noqa: E402
+from oarfish_amd.builder import RecordsStream  # noqa: E402
 from oarfish_amd.types import DeviceStore  # noqa: E402
 from cells_records_bench import PeakDeviceMemory, pinned_rate_gbs, spread  # noqa: E402
 
@@ -52,9 +59,64 @@ def close(result):
     return result[1:]
 
 
+def stream_leg(args, sr, res, save):
+    """The --stream leg (see the module docstring); fills res[style]["batch_groups_<g>"]."""
+    F, tl = sr.filters, sr.txp_len
+    n_groups = len(sr.group_off) - 1
+    for style in args.styles:
+        rec, (blob, off), _ = synth.make_named_records(sr, style=style, unmapped_rate=args.unmapped_rate)
+        n = len(rec)
+        r = res[style] = dict(record_bytes=int(rec.nbytes), name_bytes=int(blob.nbytes))
+
+        def one_call(m=n):
+            return close(DeviceStore.from_named_records(F, tl, rec[:m], (blob[:int(off[m])], off[:m + 1]),
+                                                        sort_check_num=0 if m < n else 100_000))
+
+        one_call(min(args.warm_records, n))                      # warm-up on a slice
+        for g in args.batch_groups:
+            per = max(1, int(round(g * n / max(n_groups, 1))))   # records per batch: g groups' worth, cut at record positions
+            edges = list(range(0, n, per)) + [n]
+            batches = [(rec[a:b], (blob[int(off[a]):int(off[b])], off[a:b + 1] - off[a])) for a, b in zip(edges[:-1], edges[1:])]
+            q = r[f"batch_groups_{g}"] = dict(records_per_batch=per, batches=len(batches))
+
+            def session():
+                with RecordsStream(F, tl, names=True) as s:
+                    t0 = time.perf_counter()
+                    for b_rec, b_names in batches:
+                        s.push(b_rec, names=b_names)
+                    store, kept, dt, parse = s.finish()
+                    t = time.perf_counter() - t0
+                    info = s.info()
+                store.close()
+                return t, kept, dt, info
+
+            a_runs, s_runs = [], []
+            for k in range(args.runs):
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        t_a, got = clock(one_call)
+                    q["peak_device_bytes_one_call"] = int(pk.peak)
+                    with PeakDeviceMemory() as pk:
+                        t_s, kept, dt, info = session()
+                    q["peak_device_bytes_session"] = int(pk.peak)
+                else:
+                    t_a, got = clock(one_call)
+                    t_s, kept, dt, info = session()
+                assert np.array_equal(kept, got[0]) and dt == got[1]              # kept and the discard table agree
+                a_runs.append(t_a)
+                s_runs.append(t_s)
+                q.update(one_call=spread(a_runs), session=spread(s_runs), session_over_one_call=round(min(s_runs) / min(a_runs), 4),
+                         batches_before_finish=info["batches_before_finish"], blocked_us=info["blocked_us"], host_batches=info["host_batches"])
+                q["peak_session_over_one_call"] = round(q["peak_device_bytes_session"] / max(q["peak_device_bytes_one_call"], 1), 4)
+                save()
+                print(f"[bench] {style} {g} groups a batch, run {k}: one call {t_a:.3f} s, session {t_s:.3f} s", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "records_names_bench.json"))
+    ap.add_argument("--stream", action="store_true", help="the names session against the one call (see the module docstring)")
+    ap.add_argument("--batch-groups", type=int, nargs="+", default=[1 << 18, 1 << 20])
+    ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--styles", nargs="+", default=["uuid", "illumina"])
     ap.add_argument("--reads", type=int, default=0, help="0: the bench shape (c3)")
@@ -62,6 +124,8 @@ def main():
     ap.add_argument("--unmapped-rate", type=float, default=0.0)
     ap.add_argument("--warm-records", type=int, default=2_000_000)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "records_names_stream_bench.json" if args.stream else "records_names_bench.json")
 
     st = synth.make_store(args.reads, args.txps, threads=16) if args.reads else synth.make_config("c3")
     sr = synth.make_records(st)
@@ -79,6 +143,10 @@ def main():
         with open(args.out, "w") as fh:
             json.dump(res, fh, indent=1)
 
+    if args.stream:
+        stream_leg(args, sr, res, save)
+        print(json.dumps({k: v for k, v in res.items() if not isinstance(v, dict)}))
+        return
     for style in args.styles:
         rec, (blob, off), sec = synth.make_named_records(sr, style=style, unmapped_rate=args.unmapped_rate)
         rec_p, (blob_p, off_p), sec_p = synth.make_named_records(sr, style=style, unmapped_rate=args.unmapped_rate, shuffle=True)
