@@ -1053,6 +1053,45 @@ int oem_records_stream_finish_names(oem_records_stream *s, const oem_store_opts 
 int oem_records_stream_names_copy(const oem_records_stream *s, uint64_t *out_group_off, uint32_t *out_kept,
                                   uint8_t *out_row_names, uint64_t *out_row_name_off);
 
+/* The PROJECTED form of the session: oem_store_create_projected_records for a genome-mode caller that projects and
+ * filters reads as they come (parse_genome_alignments, alignment_parser.rs:580-700, adds read by read; the mapper threads
+ * of quantify_genome_raw_reads, bulk.rs:337-682, hand chunks to a consumer) and never holds a run-sized oem_proj_record
+ * array.  Batches are whole groups, as oem_records_stream_push takes them, with one read length per group.
+ *
+ * oem_records_stream_set_projected turns a fresh session into a projected session, as oem_records_stream_set_names
+ * turns one into a names session (oem_records_stream_opts has no room for the parameter).  popts is copied.  NULL
+ * session, NULL popts or a prob_source outside 0 .. 2: OEM_ERR_ARG.  After a push, after finish, a second time or on a
+ * names session: OEM_ERR_STATE; oem_records_stream_set_names on a projected session is OEM_ERR_STATE too.  On a
+ * projected session oem_records_stream_push, _push_names, _finish_names and _names_copy return OEM_ERR_STATE; on a plain
+ * or names session oem_records_stream_push_projected does. */
+int oem_records_stream_set_projected(oem_records_stream *s, const oem_proj_opts *popts);
+/* One batch of whole groups: records / group_off (n_groups + 1 entries from 0) / read_len (n_groups entries) as
+ * oem_store_create_projected_records takes them for the whole input.  Thread-safe; tickets, back-pressure and the reuse
+ * of staging memory are oem_records_stream_push's.  Checked on the calling thread before the session is looked at:
+ * group_off present, starting at 0 and not decreasing, no group of more than 2^32 - 1 records, records present when
+ * there are any, read_len present when there are groups, at most 2^31 - 2 groups.  An argument error (OEM_ERR_ARG)
+ * rejects that batch only, uses no ticket and leaves *out_ticket untouched.  The three arrays are copied into page-locked
+ * staging by the calling thread.
+ *
+ * The device worker runs the pass of oem_builder_add_projected_groups_device on each batch.  Under OEM_PROJ_SIMILARITY
+ * and _COMBINED the alignments whose device exponential is not provably libm's are not finished batch by batch: each
+ * batch keeps their (index, f) pairs on the device, finish joins the lists and the host applies expf once
+ * (OEM_RECORDS_STREAM_INFO_HOST_FINISHED).  The host loop takes a batch with |aln_score| > 2^24, and every batch when
+ * score_prob_denom has no table under OEM_PROJ_SCORE or beta is not finite under the other two sources
+ * (OEM_RECORDS_STREAM_INFO_HOST_BATCHES).  A ref_id that is not below n_txps, or that names a transcript of length 0, is
+ * found on the device: OEM_ERR_ARG, sticky, its message naming "ticket <ticket>", the record's index within the batch
+ * and the ref_id.
+ *
+ * oem_records_stream_finish on a projected session returns what oem_store_create_projected_records returns for the
+ * accepted batches concatenated in ticket order, with the session's filters, txp_len, popts, bin_width, model and
+ * growth_rate and finish's opts: the same store (row pointers, ids and as_prob bit for bit, the same coverage column),
+ * out_kept and out_discard, however the input was cut into batches. */
+int oem_records_stream_push_projected(oem_records_stream *s, const oem_proj_record *records,
+                                      const uint64_t *group_off, const uint64_t *read_len,
+                                      uint64_t n_groups, uint64_t *out_ticket);
+#define OEM_RECORDS_STREAM_INFO_HOST_FINISHED 8u /* a projected session, after finish: alignments whose expf the host
+                                                    supplied; 0 on a plain or names session */
+
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */
 /* --------------------------------------------------------------------- */

@@ -244,7 +244,8 @@ RECORDS_STREAM_INFO = {"batches": _lib.OEM_RECORDS_STREAM_INFO_BATCHES, "groups"
                        "batches_before_finish": _lib.OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH,
                        "blocked_us": _lib.OEM_RECORDS_STREAM_INFO_BLOCKED_US,
                        "host_batches": _lib.OEM_RECORDS_STREAM_INFO_HOST_BATCHES,
-                       "row_name_bytes": _lib.OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES}
+                       "row_name_bytes": _lib.OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES,
+                       "host_finished": _lib.OEM_RECORDS_STREAM_INFO_HOST_FINISHED}
 
 
 class RecordsStream:
@@ -256,10 +257,20 @@ class RecordsStream:
 
     ``names=True`` makes it a names session (``oem_records_stream_set_names``): ``push(records, names=...)`` takes
     records and their read names in input order, cut at any record positions (a read may straddle pushes), and ``finish``
-    returns what ``DeviceStore.from_named_records(mode="adjacent", sort_check_num=...)`` returns for the concatenation."""
+    returns what ``DeviceStore.from_named_records(mode="adjacent", sort_check_num=...)`` returns for the concatenation.
+
+    ``projected=True`` makes it a projected session (``oem_records_stream_set_projected``) for genome mode:
+    ``push(records, group_off, read_len=...)`` takes batches of whole groups of ``PROJ_RECORD`` with one read length per
+    group, and ``finish`` returns what ``DeviceStore.from_projected_records(beta=..., prob_source=...)`` returns for the
+    concatenation.  ``info()["host_finished"]`` is, after ``finish``, the number of alignments whose ``expf`` the host
+    supplied."""
 
     def __init__(self, filters, txp_len, coverage: Optional[str] = None, bin_width: int = 100, growth_rate: float = 2.0,
-                 device: int = 0, max_staged_records: int = 0, names: bool = False, sort_check_num: int = 100_000):
+                 device: int = 0, max_staged_records: int = 0, names: bool = False, sort_check_num: int = 100_000,
+                 projected: bool = False, beta: float = 10.0, prob_source="similarity"):
+        if names and projected:
+            raise ValueError("a session takes names=True or projected=True, not both")
+        po = proj_opts_c(beta, prob_source) if projected else None
         self._lib = _lib.lib()
         self.filters = filters_c(filters)
         self.txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
@@ -273,6 +284,9 @@ class RecordsStream:
         self.names = bool(names)
         if self.names:
             self._check(self._lib.oem_records_stream_set_names(self._h, int(sort_check_num)))
+        self.projected = bool(projected)
+        if self.projected:
+            self._check(self._lib.oem_records_stream_set_projected(self._h, C.addressof(po)))
 
     _check = StoreBuilder._check
 
@@ -299,11 +313,26 @@ class RecordsStream:
             raise RuntimeError("RecordsStream is closed")
         return self._h
 
-    def push(self, records, group_off=None, names=None) -> int:
+    def push(self, records, group_off=None, names=None, read_len=None) -> int:
         """One batch (``records`` / ``group_off`` as in ``StoreBuilder.add_groups``); returns its ticket.  Thread-safe;
         blocks while the staging budget is full.  A names session takes ``names=`` instead of ``group_off``: one name
         per record, a sequence of ``str`` / ``bytes`` or a ``(blob, offsets)`` pair, packed as ``from_named_records``
-        packs it."""
+        packs it.  A projected session takes ``read_len=`` besides ``group_off``, as
+        ``StoreBuilder.add_projected_groups`` does."""
+        if read_len is not None and not self.projected:
+            raise ValueError("read_len= belongs to a projected session (projected=True)")
+        if self.projected:
+            if names is not None:
+                raise ValueError("a projected session takes group_off and read_len=, not names=")
+            if group_off is None or read_len is None:
+                raise ValueError("a projected session's push needs group_off and read_len=")
+            records, group_off, read_len = check_projected_batch(records, group_off, read_len)
+            n_groups = len(group_off) - 1
+            ticket = C.c_uint64(0)
+            self._check(self._lib.oem_records_stream_push_projected(self.handle, records.ctypes.data if len(records) else None,
+                                                                    group_off.ctypes.data, read_len.ctypes.data if n_groups else None,
+                                                                    n_groups, C.byref(ticket)))
+            return int(ticket.value)
         if names is not None:
             from .types import pack_read_names
             if group_off is not None:
@@ -333,6 +362,8 @@ class RecordsStream:
         out = {}
         for name, key in RECORDS_STREAM_INFO.items():
             if name == "row_name_bytes" and not self.names:   # (a names session's key)
+                continue
+            if name == "host_finished" and not self.projected:   # (a projected session's key)
                 continue
             v = C.c_uint64(0)
             self._check(self._lib.oem_records_stream_info(self.handle, key, C.byref(v)))

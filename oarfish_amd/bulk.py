@@ -11,7 +11,10 @@ call, `DeviceStore.from_records` (oem_store_create_records).  `quantify_bulk_ali
 `quantify_bulk_alignments_from_bam` (bulk.rs:212-259) from the parsed records on: the parser itself
 (alignment_parser.rs:301-437) runs on the device too (`DeviceStore.from_named_records`);
 `quantify_bulk_alignments_from_record_batches` is the same for a reader that hands the records and names over in chunks
-(`builder.RecordsStream(names=True)`).  KDE is not supported.
+(`builder.RecordsStream(names=True)`).  Genome mode has the same pair from the projected groups on
+(`quantify_genome_alignments_from_bam`, bulk.rs:268-335): `quantify_genome_alignments_from_projected_records`
+(`DeviceStore.from_projected_records`) and `quantify_genome_alignments_from_projected_batches`
+(`builder.RecordsStream(projected=True)`).  KDE is not supported.
 """
 from __future__ import annotations
 
@@ -166,9 +169,113 @@ def quantify_bulk_alignments_from_record_batches(filters, txps_name: Sequence[st
     return _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args, coverage)
 
 
-def _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args: BulkArgs, coverage) -> np.ndarray:
-    """The tail both records drivers share, from the resident store on.  ``host_rows()``: the collated records and their
-    group_off for the host `.prob` writer, which needs the rows' transcript ids."""
+def _projected_batch(batch):
+    """One ``(records, group_off, read_len[, read_names[, genomic_counts]])`` of the genome-mode drivers, checked: the
+    arrays, the groups' names as a list (or None) and the genomic record counts (or None)."""
+    from .builder import check_projected_batch
+    if not 3 <= len(batch) <= 5:
+        raise ValueError("a projected batch is (records, group_off, read_len[, read_names[, genomic_counts]])")
+    records, group_off, read_len = check_projected_batch(*batch[:3])
+    n_groups = len(group_off) - 1
+    names = None if len(batch) < 4 or batch[3] is None else list(batch[3])
+    if names is not None and len(names) != n_groups:
+        raise ValueError("read_names must have one entry per group")
+    counts = None if len(batch) < 5 or batch[4] is None else np.asarray(batch[4], dtype=np.int64)
+    if counts is not None and counts.shape != (n_groups,):
+        raise ValueError("genomic_counts must have one entry per group")
+    return records, group_off, read_len, names, counts
+
+
+def _projected_tail(dev, kept, pieces, filters, txp_len, txps_name, txp_lens, args: BulkArgs, beta, prob_source, coverage):
+    """What both genome-mode drivers do once the store stands: ``unique_alignments`` (alignment_parser.rs:654-657: a kept
+    group that was projected from one genomic record), the kept groups' names (:620-630) and the shared tail."""
+    from types import SimpleNamespace
+    from .builder import PROJ_RECORD
+    from .types import pack_read_names
+    names, counts = [], []
+    for _, _, _, nm, cnt in pieces:
+        names.append(nm)
+        counts.append(cnt)
+    unique = None
+    if all(c is not None for c in counts):
+        genomic = np.concatenate(counts) if counts else np.zeros(0, dtype=np.int64)
+        unique = int(np.count_nonzero((kept > 0) & (genomic == 1)))
+    read_names = None
+    if args.write_assignment_probs:
+        if any(n is None for n in names):
+            raise ValueError("cannot write assignment probabilities without valid vector of read names")
+        flat = [n for nm in names for n in nm]
+        rows = [flat[g] for g in np.flatnonzero(kept)]
+        read_names = pack_read_names(rows, len(rows))
+
+    def host_rows():   # (the host `.prob` writer alone: the groups once more, concatenated)
+        off, base = [np.zeros(1, dtype=np.uint64)], 0
+        for _, group_off, _, _, _ in pieces:
+            off.append(group_off[1:] + np.uint64(base))
+            base += int(group_off[-1])
+        recs = [p[0] for p in pieces]
+        return (np.concatenate(recs) if recs else np.zeros(0, dtype=PROJ_RECORD), np.concatenate(off),
+                np.concatenate([p[2] for p in pieces]) if pieces else np.zeros(0, dtype=np.uint64))
+
+    parse = SimpleNamespace(read_names=read_names)
+    counts_out = _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args, coverage,
+                                      projected=(beta, prob_source))
+    return counts_out, unique
+
+
+def quantify_genome_alignments_from_projected_records(filters, txps_name: Sequence[str], txp_lens: Sequence[int], records,
+                                                      group_off, read_len, args: BulkArgs, read_names=None,
+                                                      genomic_counts=None, beta: float = 10.0, prob_source="similarity",
+                                                      coverage: Optional[str] = None, bin_width: int = 100,
+                                                      growth_rate: float = 2.0):
+    """`quantify_genome_alignments_from_bam` (bulk.rs:268-335) from the projected groups on: the reads' projected
+    ``records`` (``builder.PROJ_RECORD``) with ``group_off`` and ``read_len`` go through
+    ``DeviceStore.from_projected_records`` (filter_projected and, with ``coverage``, the model of bulk.rs:103-108, in one
+    device call), then the tail of ``perform_inference_and_write_output``.  ``read_names``: one name per group, needed
+    for `.prob`, whose rows are the kept groups' names (alignment_parser.rs:620-630).  ``genomic_counts``: the number of
+    genomic records each group was projected from.  Returns ``(counts, unique_alignments)``: the groups with
+    ``kept > 0`` and ``genomic_counts == 1`` (:654-657), None without ``genomic_counts``.  The files are those of
+    ``perform_inference_and_write_output`` on the store the host builder makes of the same groups
+    (``StoreBuilder.add_projected_groups``)."""
+    txp_len = np.asarray(txp_lens, dtype=np.uint64)
+    piece = _projected_batch((records, group_off, read_len, read_names, genomic_counts))
+    dev, kept, _discard = DeviceStore.from_projected_records(filters, txp_len, piece[0], piece[1], piece[2], beta=beta,
+                                                             prob_source=prob_source, coverage=coverage, bin_width=bin_width,
+                                                             growth_rate=growth_rate, device=args.device)
+    return _projected_tail(dev, kept, [piece], filters, txp_len, txps_name, txp_lens, args, beta, prob_source, coverage)
+
+
+def quantify_genome_alignments_from_projected_batches(filters, txps_name: Sequence[str], txp_lens: Sequence[int], batches,
+                                                      args: BulkArgs, beta: float = 10.0, prob_source="similarity",
+                                                      coverage: Optional[str] = None, bin_width: int = 100,
+                                                      growth_rate: float = 2.0, max_staged_records: int = 0):
+    """``quantify_genome_alignments_from_projected_records`` for a driver that projects reads as they come
+    (parse_genome_alignments, alignment_parser.rs:580-700; the mapper threads of quantify_genome_raw_reads,
+    bulk.rs:337-682): ``batches`` is an iterable of ``(records, group_off, read_len[, read_names[, genomic_counts]])``,
+    whole groups each, ``group_off`` from 0.  They go through a projected session
+    (``RecordsStream(projected=True)``); the files and the returned ``(counts, unique_alignments)`` are those of the
+    one-call form on the concatenation.  Only the host `.prob` writer (``prob_on_device`` False) keeps the records it has
+    seen; names and genomic counts are kept per group."""
+    from .builder import RecordsStream
+    txp_len = np.asarray(txp_lens, dtype=np.uint64)
+    keep_rows = args.write_assignment_probs and not args.prob_on_device
+    pieces = []
+    with RecordsStream(filters, txp_len, coverage=coverage, bin_width=bin_width, growth_rate=growth_rate, device=args.device,
+                       max_staged_records=max_staged_records, projected=True, beta=beta, prob_source=prob_source) as rs:
+        for batch in batches:
+            records, group_off, read_len, names, counts = _projected_batch(batch)
+            rs.push(records, group_off, read_len=read_len)
+            pieces.append((records, group_off, read_len, names, counts) if keep_rows else (None, None, None, names, counts))
+        dev, kept, _discard = rs.finish()
+    return _projected_tail(dev, kept, pieces, filters, txp_len, txps_name, txp_lens, args, beta, prob_source, coverage)
+
+
+def _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args: BulkArgs, coverage,
+                         projected=None) -> np.ndarray:
+    """The tail the records drivers share, from the resident store on.  ``host_rows()``: the collated records and their
+    group_off for the host `.prob` writer, which needs the rows' transcript ids; with ``projected`` = (beta,
+    prob_source) they are projected records, ``host_rows()`` gives their read lengths too and the host filter is
+    ``add_projected_groups``."""
     from .builder import StoreBuilder
     with dev:
         counts, run = dev.em_run(None, args.max_em_iter, args.convergence_thresh, 50 if args.threads <= 4 else 1)  # bulk.rs:155-159
@@ -192,7 +299,10 @@ def _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp
                                               compressed=args.prob_compressed)
                 return counts
             with StoreBuilder(filters, txp_len) as hb:   # the rows' transcript ids: the host filter over the same groups
-                hb.add_groups(*host_rows())
+                if projected is None:
+                    hb.add_groups(*host_rows())
+                else:
+                    hb.add_projected_groups(*host_rows(), beta=projected[0], prob_source=projected[1])
                 row_ptr, tid = hb.export()[:2]
             blob, off = parse.read_names
             read_names = [bytes(blob[int(off[r]):int(off[r + 1])]).decode("utf-8", "replace") for r in range(dev.n_reads)]

@@ -192,6 +192,32 @@ int filter_result_to_builder(oem_builder *b, FilterResult &r, uint64_t n_groups,
 int filter_result_to_store(const char *who, FilterResult &r, uint32_t n_txps, uint64_t n_groups, uint32_t bin_width, int model,
                            double growth_rate, int device, const oem_store_opts *opts, uint32_t *out_kept,
                            oem_discard_table *out_discard, oem_store **out);
+// oem_filter_projected_device.hip -----------------------------------------------------------------------------------------
+// What a projected batch of the records session keeps of the alignments k_proj_emit left unsure, instead of finishing
+// them on the host batch by batch: n pairs (idx[i], f[i]) on the device, idx the alignment's index within the batch, in
+// no particular order (k_proj_collect).  Their as_prob slots hold f until the session's finish has scattered expf(f).
+struct ProjDeferred {
+    DevBuf<uint64_t> idx;
+    DevBuf<float> f;
+    uint64_t n = 0;
+};
+// Measure, scans and emit of one projected batch on the current device: the body of
+// oem_builder_add_projected_groups_device and oem_store_create_projected_records; the arguments are filter_device's plus
+// the reads' lengths and the options (tab is read for OEM_PROJ_SCORE only).  An argument error found on the device
+// (ref_id) is reported here.  deferred == NULL: the unsure alignments are finished on the host before the call returns.
+// deferred != NULL (the session): they are collected into *deferred and left for proj_finish_deferred; under
+// OEM_PROJ_SCORE the list is empty.  pinned_src: as filter_upload_measure.
+int proj_device(const char *who, const oem_filters &F, const oem_proj_opts &P, const uint64_t *txp_len, uint32_t n_txps,
+                const std::vector<float> &tab, const oem_proj_record *records, const uint64_t *group_off, const uint64_t *read_len,
+                uint64_t n_groups, uint64_t base, bool want_coords, bool narrow, FilterResult *out, ProjDeferred *deferred = nullptr,
+                bool pinned_src = false);
+// Whether the host loop has to take every projected batch: no table for OEM_PROJ_SCORE (score_prob_denom; *tab is
+// filled otherwise), a beta that is not finite for the two sources that use it.
+bool proj_host_only(const oem_filters &F, const oem_proj_opts &P, std::vector<float> *tab);
+// The deferred finish: n values f on the device come down, libm's expf goes back up and as_prob[idx[i]] = expf(f[i]).
+// d_f is overwritten.  Leaves the null stream idle.
+int proj_finish_deferred(const uint64_t *d_idx, float *d_f, uint64_t n, float *d_as_prob);
+
 // The argument checks oem_store_create_records makes before any device use (shared by its projected counterpart).
 int check_store_from_records(const char *who, const void *filters, const uint64_t *txp_len, uint32_t n_txps, uint32_t bin_width,
                              int model, const oem_store_opts *opts);

@@ -20,7 +20,9 @@
 // of a rounding tie: about 0.4 % of the alignments) it writes f itself into the as_prob slot and sets the alignment's
 // flag.  The flagged (index, f) pairs are compacted with hipcub::DeviceSelect::Flagged and copied down, the host applies
 // expf, the values go back up and k_proj_scatter stores them -- before the arrays are handed to the builder, the coverage
-// model or the layout build.
+// model or the layout build.  The records session (oem_records_stream.hip) does not finish batch by batch: its batches
+// keep their (index, f) pairs on the device (k_proj_collect, a wavefront ballot instead of the select passes) and its
+// finish runs the host's expf once over all of them (proj_finish_deferred).
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
@@ -118,6 +120,57 @@ __global__ __launch_bounds__(kFT) void k_proj_scatter(const uint64_t *__restrict
     if (i < n) as_prob[idx[i]] = val[i];
 }
 
+// The session's form of the compaction ("The projected session"): one lane per alignment of a
+// batch's piece.  A wavefront takes the ballot of its lanes' flags, its first lane reserves that many entries of the
+// piece's list with one atomicAdd, and the flagged lanes store (piece-local index, f) behind one another.  The list's
+// order is whatever order the wavefronts arrive in: indices are distinct and the later scatter is by index.  No lane
+// leaves before the ballot, so lane 0 always holds the reservation.
+__global__ __launch_bounds__(kFT) void k_proj_collect(const uint8_t *__restrict__ unsure, const float *__restrict__ as_prob, uint64_t nnz,
+                                                      unsigned long long *__restrict__ count, uint64_t *__restrict__ idx,
+                                                      float *__restrict__ f)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kFT + threadIdx.x;
+    const bool flagged = j < nnz && unsure[j] != 0;
+    const unsigned long long votes = __ballot(flagged);
+    if (votes == 0) return; // (uniform over the wavefront)
+    const uint32_t lane = threadIdx.x & 63;
+    unsigned long long first = 0;
+    if (lane == 0) first = atomicAdd(count, (unsigned long long)__popcll(votes));
+    first = __shfl(first, 0);
+    if (flagged) {
+        const uint64_t at = first + (uint64_t)__popcll(votes & ((1ull << lane) - 1));
+        idx[at] = j;
+        f[at] = as_prob[j];
+    }
+}
+
+// The batch's unsure alignments into *d: k_proj_collect into lists of nnz entries, the count down, the lists cut to size.
+int collect_deferred(const float *d_as_prob, const uint8_t *d_unsure, uint64_t nnz, ProjDeferred *d)
+{
+    d->n = 0;
+    if (nnz == 0) return OEM_OK;
+    DevBuf<uint64_t> d_idx;
+    DevBuf<float> d_f;
+    DevBuf<unsigned long long> d_count;
+    OEM_TRY(dev_alloc(&d_idx.p, nnz, nullptr));
+    OEM_TRY(dev_alloc(&d_f.p, nnz, nullptr));
+    OEM_TRY(dev_alloc(&d_count.p, 1, nullptr));
+    OEM_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), nullptr));
+    hipLaunchKernelGGL(k_proj_collect, dim3((uint32_t)((nnz + kFT - 1) / kFT)), dim3(kFT), 0, nullptr, d_unsure, d_as_prob, nnz, d_count.p,
+                       d_idx.p, d_f.p);
+    OEM_HIP(hipGetLastError());
+    unsigned long long m = 0;
+    OEM_HIP(hipMemcpy(&m, d_count.p, sizeof m, hipMemcpyDeviceToHost)); // (the pass's one wait after emit)
+    if (m > nnz) return fail(OEM_ERR_STATE, "k_proj_collect: %llu entries for %llu alignments", m, (unsigned long long)nnz);
+    if (m == 0) return OEM_OK;
+    OEM_TRY(dev_alloc(&d->idx.p, m, nullptr));
+    OEM_TRY(dev_alloc(&d->f.p, m, nullptr));
+    OEM_HIP(hipMemcpy(d->idx.p, d_idx.p, sizeof(uint64_t) * m, hipMemcpyDeviceToDevice));
+    OEM_HIP(hipMemcpy(d->f.p, d_f.p, sizeof(float) * m, hipMemcpyDeviceToDevice));
+    d->n = m;
+    return OEM_OK;
+}
+
 // The alignments k_proj_emit left unsure: their f comes down, libm's expf goes back up.  Segments keep hipcub's int counts.
 int finish_on_host(float *d_as_prob, const uint8_t *d_unsure, uint64_t nnz, uint64_t *n_finished)
 {
@@ -161,11 +214,13 @@ int finish_on_host(float *d_as_prob, const uint8_t *d_unsure, uint64_t nnz, uint
     return OEM_OK;
 }
 
-// Measure, scans, emit and finish of one batch on the current device; the arguments are filter_device's
-// (oem_filter_device.hip) plus the reads' lengths and the options.  tab is read for OEM_PROJ_SCORE only.
+} // namespace
+
+// Measure, scans, emit and finish of one batch on the current device (oem_filter_device.h).
 int proj_device(const char *who, const oem_filters &F, const oem_proj_opts &P, const uint64_t *txp_len, uint32_t n_txps,
                 const std::vector<float> &tab, const oem_proj_record *records, const uint64_t *group_off, const uint64_t *read_len,
-                uint64_t n_groups, uint64_t base, bool want_coords, bool narrow, FilterResult *out)
+                uint64_t n_groups, uint64_t base, bool want_coords, bool narrow, FilterResult *out, ProjDeferred *deferred,
+                bool pinned_src)
 {
     const bool timing = knob("OEM_FILTER_TIMING", 0) != 0;
     const bool by_table = P.prob_source == OEM_PROJ_SCORE;
@@ -204,7 +259,8 @@ int proj_device(const char *who, const oem_filters &F, const oem_proj_opts &P, c
                                       hipLaunchKernelGGL(k_proj_measure, dim3((uint32_t)((g1 - g0 + kFT - 1) / kFT)), dim3(kFT), 0, st,
                                                          F, d_recs.p, d_goff.p, d_read_len.p, g0, g1, out->txp_len.p, n_txps,
                                                          out->n_kept.p, d_best_sim.p, d_best_score.p, d_tot.p);
-                                  }));
+                                  },
+                                  pinned_src));
     g_proj_pass[0] = ms[1];
     OEM_HIP(hipMemcpy(&h_tot, d_tot.p, sizeof(h_tot), hipMemcpyDeviceToHost));
     if (h_tot.flags & kFilterFlagBadRef) {
@@ -240,6 +296,7 @@ int proj_device(const char *who, const oem_filters &F, const oem_proj_opts &P, c
         OEM_HIP(hipGetLastError());
     }
     if (timing) OEM_HIP(hipEventRecord(ev[1].e, st));
+    if (deferred && !by_table) OEM_TRY(collect_deferred(out->as_prob.p, d_unsure.p, nnz, deferred)); // (behind emit on the null stream)
     OEM_HIP(hipStreamSynchronize(st));
     if (timing) {
         float emit_ms = 0.f;
@@ -248,7 +305,7 @@ int proj_device(const char *who, const oem_filters &F, const oem_proj_opts &P, c
     }
     d_recs.reset();
     uint64_t n_finished = 0;
-    if (!by_table) {
+    if (!by_table && !deferred) {
         const auto t0 = std::chrono::steady_clock::now();
         OEM_TRY(finish_on_host(out->as_prob.p, d_unsure.p, nnz, &n_finished));
         g_proj_pass[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -266,7 +323,19 @@ bool proj_host_only(const oem_filters &F, const oem_proj_opts &P, std::vector<fl
     return !std::isfinite(P.beta);
 }
 
-} // namespace
+int proj_finish_deferred(const uint64_t *d_idx, float *d_f, uint64_t n, float *d_as_prob)
+{
+    if (n == 0) return OEM_OK;
+    if (n > 0x7fffffffull * kFT) return fail(OEM_ERR_ARG, "proj_finish_deferred: %llu alignments", (unsigned long long)n);
+    std::vector<float> h_f(n);
+    OEM_HIP(hipMemcpy(h_f.data(), d_f, sizeof(float) * n, hipMemcpyDeviceToHost));
+    for (float &f : h_f) f = expf(f);                                                      // f.exp() (:1282), libm's
+    OEM_HIP(hipMemcpy(d_f, h_f.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_proj_scatter, dim3((uint32_t)((n + kFT - 1) / kFT)), dim3(kFT), 0, nullptr, d_idx, (const float *)d_f, n, d_as_prob);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
 
 void proj_last_pass(double *out5) { std::memcpy(out5, g_proj_pass, sizeof g_proj_pass); }
 

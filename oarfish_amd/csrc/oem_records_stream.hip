@@ -22,8 +22,13 @@
 // (oem_parse_device.h), carries the open read on the device from batch to batch, and its pieces hold the groups a batch
 // CLOSED, with their group offsets and row names; finish joins those too.
 //
-// The batch type is oem_aln_record throughout; a session over projected records would template Batch and run_batch on
-// the record type, as filter_upload_measure is.
+// The PROJECTED form (oem_records_stream_set_projected; "the projected session" in DESIGN.md section 5d) takes batches
+// of whole genome-mode groups with one read length per group.  Batch's accessors and run_batch are templates on the
+// record type (oem_aln_record / oem_proj_record, 40 bytes both), as filter_upload_measure is: the projected batch's arena
+// holds its read lengths behind its group offsets, its pass is proj_device with pinned_src, and its piece keeps, besides
+// the CSR, the (index, f) list of the alignments whose expf the host has to supply (k_proj_collect).  finish joins the
+// lists in the one k_stream_concat launch, the indices with the piece's alignment base added, and runs the host's expf
+// and the scatter once, before filter_result_to_store.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -34,6 +39,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "oem_filter_device.h"
@@ -163,6 +169,7 @@ struct Batch {
     uint64_t ticket = 0, n_groups = 0, n_records = 0;
     // a names session's batch: no groups yet; the arena holds name_off (n_records + 1), the records and the name bytes
     bool named = false;
+    bool projected = false; // a projected session's batch: whole groups of oem_proj_record with their read lengths
     uint64_t rec_base = 0, name_bytes = 0; // the session-global input index of its first record; name_off[n_records]
     Arena mem;          // (none for a batch without groups, or without records in a names session)
     bool ready = false; // the pushing thread has finished its copy
@@ -172,7 +179,16 @@ struct Batch {
     ~Batch() { if (mem.p) arena_free(mem); }
     const uint64_t *group_off() const { return (const uint64_t *)mem.p; }
     static size_t records_at(uint64_t n_groups) { return (sizeof(uint64_t) * (n_groups + 1) + 63) & ~(size_t)63; }
-    const oem_aln_record *records() const { return (const oem_aln_record *)((const char *)mem.p + records_at(n_groups)); }
+    // Where a batch of whole groups keeps its records, by record type: a projected batch has its n_groups read lengths
+    // between the group offsets and the records.
+    template <typename Rec>
+    static size_t groups_records_at(uint64_t n_groups)
+    {
+        return std::is_same<Rec, oem_proj_record>::value ? records_at(2 * n_groups) : records_at(n_groups);
+    }
+    template <typename Rec>
+    const Rec *records() const { return (const Rec *)((const char *)mem.p + groups_records_at<Rec>(n_groups)); }
+    const uint64_t *read_len() const { return group_off() + n_groups + 1; } // (a projected batch)
     // the names form: offsets first (as group_off is), records at records_at(n_records), the bytes behind them
     const uint64_t *name_off() const { return (const uint64_t *)mem.p; }
     const oem_aln_record *named_records() const { return (const oem_aln_record *)((const char *)mem.p + records_at(n_records)); }
@@ -185,8 +201,10 @@ struct Batch {
 // A names session's piece holds the groups its batch CLOSED (oem_collate.h, the streamed rule), and besides the above:
 // group_off (n_groups + 1 positions from 0 among the closed groups' records, n_records of them), the names of its rows
 // as a dense blob (row_bytes) with row_off (n_rows + 1 offsets from 0), and the number of groups with n_kept == 1.
+// A projected session's piece has `unsure`: the alignments whose as_prob slot still holds f (oem_filter_device.h).
 struct Piece {
     FilterResult r;
+    ProjDeferred unsure;
     uint64_t n_groups = 0;
     DevBuf<uint64_t> group_off, row_off;
     DevBuf<uint8_t> rows;
@@ -348,8 +366,18 @@ struct oem_records_stream {
     std::vector<uint32_t> out_kept;
     std::vector<uint8_t> out_rows;
 
+    // -- the projected session (oem_records_stream_set_projected) --------------------------------------------------------
+    bool projected = false;
+    oem_proj_opts popts{10.f, OEM_PROJ_SIMILARITY};
+    uint64_t host_finished = 0; // after finish: alignments whose expf the host supplied
+
+    // the session's kind as the calls name it: 0 plain, 1 names, 2 projected (mu held)
+    int kind() const { return named ? 1 : projected ? 2 : 0; }
+
+    template <typename Rec>
     int run_batch(const Batch &b, Piece *out, bool *host);
     int run_batch_names(const Batch &b, Piece *out, bool *host);
+    int upload_piece(oem_builder &hb, const std::vector<uint32_t> &kept, uint64_t n_groups, const char *who, Piece *out);
     int close_groups(const char *who, uint64_t rec_base, uint64_t n, const oem_aln_record *h_records,
                      const oem_aln_record *d_in, const uint32_t *d_order, uint64_t p_last, const uint64_t *d_gb, uint64_t ngb, bool joins,
                      const uint8_t *d_names, const uint64_t *d_name_off, Piece *out, bool *host);
@@ -366,14 +394,20 @@ struct oem_records_stream {
 // The host loop on one batch (a fresh builder: bases 0), and its arrays uploaded as the piece.
 int oem_records_stream::host_piece(const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, const char *who, Piece *out)
 {
-    FilterResult &r = out->r;
-    r.row_ptr32.reset(); // (a device pass that met a big score has left n_kept behind)
-    r.n_kept.reset();
     oem_builder hb;
     hb.f = f;
     hb.txp_len = txp_len;
     std::vector<uint32_t> kept(n_groups + 1, 0);
     OEM_TRY(add_groups_host(&hb, records, group_off, n_groups, kept.data(), who));
+    return upload_piece(hb, kept, n_groups, who, out);
+}
+
+// The arrays of a scratch builder that has taken one batch (kept: n_groups + 1 entries, the last one 0) as the piece.
+int oem_records_stream::upload_piece(oem_builder &hb, const std::vector<uint32_t> &kept, uint64_t n_groups, const char *who, Piece *out)
+{
+    FilterResult &r = out->r;
+    r.row_ptr32.reset(); // (a device pass that met a big score has left n_kept behind)
+    r.n_kept.reset();
     const uint64_t nnz = hb.tid.size(), n_rows = hb.row_ptr.size() - 1;
     if (nnz >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a resident store needs fewer than 2^32 alignments", who);
     std::vector<uint32_t> rp32(hb.row_ptr.begin(), hb.row_ptr.end());
@@ -398,20 +432,40 @@ int oem_records_stream::host_piece(const oem_aln_record *records, const uint64_t
     return OEM_OK;
 }
 
+// One batch of whole groups, for either record type: the one call's pass with base 0 straight from the arena, or --
+// the one call's fallbacks -- the host loop into a scratch builder.  A projected batch leaves its unsure alignments in
+// the piece's list (proj_device with `deferred`); the host loop's as_prob is final and its list is empty.
+template <typename Rec>
 int oem_records_stream::run_batch(const Batch &b, Piece *out, bool *host)
 {
+    constexpr bool kProj = std::is_same<Rec, oem_proj_record>::value;
     out->n_groups = b.n_groups;
     if (b.n_groups == 0) return OEM_OK;
     char who[64];
     snprintf(who, sizeof who, "oem_records_stream: ticket %llu", (unsigned long long)b.ticket);
+    const Rec *records = b.records<Rec>();
     if (!host_only) {
-        OEM_TRY(filter_device(who, f, txp_len.data(), o.n_txps, tab, b.records(), b.group_off(), b.n_groups, 0, o.model >= 0, true,
-                              &out->r, nullptr, b.mem.pinned));
+        if constexpr (kProj) {
+            OEM_TRY(proj_device(who, f, popts, txp_len.data(), o.n_txps, tab, records, b.group_off(), b.read_len(), b.n_groups, 0,
+                                o.model >= 0, true, &out->r, &out->unsure, b.mem.pinned));
+        } else {
+            OEM_TRY(filter_device(who, f, txp_len.data(), o.n_txps, tab, records, b.group_off(), b.n_groups, 0, o.model >= 0, true,
+                                  &out->r, nullptr, b.mem.pinned));
+        }
         out->r.txp_len.reset(); // (the join uploads the lengths once)
         if (!out->r.host_rerun) return OEM_OK;
     }
     *host = true;
-    return host_piece(b.records(), b.group_off(), b.n_groups, who, out);
+    if constexpr (kProj) {
+        oem_builder hb;
+        hb.f = f;
+        hb.txp_len = txp_len;
+        std::vector<uint32_t> kept(b.n_groups + 1, 0);
+        OEM_TRY(add_projected_groups_host(&hb, records, b.group_off(), b.read_len(), b.n_groups, popts, kept.data(), who));
+        return upload_piece(hb, kept, b.n_groups, who, out);
+    } else {
+        return host_piece(records, b.group_off(), b.n_groups, who, out);
+    }
 }
 
 // ---- the names session's worker ("The names session") ---------------------------------------------
@@ -765,7 +819,9 @@ void oem_records_stream::work()
         if (!skip) {
             try {
                 piece.reset(new Piece());
-                rc = b->named ? run_batch_names(*b, piece.get(), &host) : run_batch(*b, piece.get(), &host);
+                rc = b->named       ? run_batch_names(*b, piece.get(), &host)
+                     : b->projected ? run_batch<oem_proj_record>(*b, piece.get(), &host)
+                                    : run_batch<oem_aln_record>(*b, piece.get(), &host);
             } catch (const std::bad_alloc &) {
                 rc = fail(OEM_ERR_OOM, "oem_records_stream: host allocation failed in the device worker");
             } catch (const std::exception &e) {
@@ -837,10 +893,25 @@ int oem_records_stream::join(const char *who, FilterResult *out, uint64_t *n_gro
         OEM_HIP(hipMemset(d_row_off.p, 0, sizeof(uint64_t)));
     }
 
+    // a projected session: the pieces' lists of unsure alignments are joined in the same launch, the indices made global
+    DevBuf<uint64_t> d_uidx;
+    DevBuf<float> d_uf;
+    uint64_t U = 0, u0 = 0;
+    for (const auto &p : pieces) U += p->unsure.n;
+    if (U) {
+        OEM_TRY(dev_alloc(&d_uidx.p, U, nullptr));
+        OEM_TRY(dev_alloc(&d_uf.p, U, nullptr));
+    }
+
     ConcatPlan plan;
     uint64_t *sum = &out->dt.discard_5p;
     uint64_t r0 = 0, a0 = 0, g0 = 0, p0 = 0, b0 = 0; // the piece's row, alignment, group, record and row-name byte base
     for (const auto &p : pieces) {
+        if (p->unsure.n) {
+            plan.add(p->unsure.idx.p, d_uidx.p + u0, p->unsure.n, 8, a0);
+            plan.add(p->unsure.f.p, d_uf.p + u0, p->unsure.n, 4, 0);
+            u0 += p->unsure.n;
+        }
         const FilterResult &r = p->r;
         plan.add(r.n_kept.p, out->n_kept.p + g0, p->n_groups, 4, 0);
         plan.add(r.row_ptr32.p + 1, out->row_ptr32.p + r0 + 1, r.n_rows, 4, (uint32_t)a0);
@@ -865,6 +936,12 @@ int oem_records_stream::join(const char *who, FilterResult *out, uint64_t *n_gro
         b0 += p->row_bytes;
     }
     OEM_TRY(plan.run(who, &g_join_ms));
+    // the deferred expf, once for the session: whatever reads the joined weights next sees them finished
+    OEM_TRY(proj_finish_deferred(d_uidx.p, d_uf.p, U, out->as_prob.p));
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        host_finished = U;
+    }
     if (named) { // the variable-length outputs stay with the session (oem_records_stream_names_copy)
         out_group_off.resize(G + 1);
         out_row_off.resize(R + 1);
@@ -927,19 +1004,25 @@ extern "C" int oem_records_stream_create(const oem_records_stream_opts *opts, co
 namespace oem {
 namespace {
 
-// What both pushes do once the batch's own checks have passed: wait for room in the staging budget, take the ticket
+// What the three pushes do once the batch's own checks have passed: wait for room in the staging budget, take the ticket
 // under the session lock, then -- outside it -- find an arena of `bytes` and let fill(arena) copy the caller's arrays.
-// named: the batch of a names session (n_groups 0, name_bytes = name_off[n_records]); a batch has a payload when
-// `bytes` > 0.
+// kind: the session the push belongs to (oem_records_stream::kind()).  1: the batch of a names session (n_groups 0,
+// name_bytes = name_off[n_records]); 2: of a projected session; a batch has a payload when `bytes` > 0.
 template <typename Fill>
-int stage_batch(oem_records_stream *s, const char *who, bool named, uint64_t n_groups, uint64_t n_records, uint64_t name_bytes, size_t bytes,
+int stage_batch(oem_records_stream *s, const char *who, int kind, uint64_t n_groups, uint64_t n_records, uint64_t name_bytes, size_t bytes,
                 Fill &&fill, uint64_t *out_ticket)
 {
+    const bool named = kind == 1;
     Batch *b = nullptr;
     {
         std::unique_lock<std::mutex> lk(s->mu);
-        if (s->named != named)
-            return fail(OEM_ERR_STATE, named ? "%s: not a names session (oem_records_stream_set_names)" : "%s: a names session takes oem_records_stream_push_names", who);
+        if (s->kind() != kind)
+            return fail(OEM_ERR_STATE,
+                        kind == 1   ? "%s: not a names session (oem_records_stream_set_names)"
+                        : kind == 2 ? "%s: not a projected session (oem_records_stream_set_projected)"
+                        : s->named  ? "%s: a names session takes oem_records_stream_push_names"
+                                    : "%s: a projected session takes oem_records_stream_push_projected",
+                        who);
         ++s->pushes_in_flight;
         struct InFlight { // (mu is held whenever this scope is left)
             oem_records_stream *s;
@@ -960,6 +1043,7 @@ int stage_batch(oem_records_stream *s, const char *who, bool named, uint64_t n_g
         nb->n_groups = n_groups;
         nb->n_records = n_records;
         nb->named = named;
+        nb->projected = kind == 2;
         nb->rec_base = s->total_records;
         nb->name_bytes = name_bytes;
         if (bytes) nb->mem = s->take_arena(bytes);
@@ -1014,11 +1098,53 @@ extern "C" int oem_records_stream_push(oem_records_stream *s, const oem_aln_reco
     if (n_groups >= 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: at most 2^31 - 2 groups per batch", who);
     const uint64_t n_records = group_off[n_groups];
     const size_t rec_at = Batch::records_at(n_groups), bytes = rec_at + sizeof(oem_aln_record) * n_records;
-    return stage_batch(s, who, false, n_groups, n_records, 0, n_groups ? bytes : 0, [&](char *mem) {
+    return stage_batch(s, who, 0, n_groups, n_records, 0, n_groups ? bytes : 0, [&](char *mem) {
         std::memcpy(mem, group_off, sizeof(uint64_t) * (n_groups + 1));
         if (n_records) std::memcpy(mem + rec_at, records, sizeof(oem_aln_record) * n_records);
     }, out_ticket);
     OEM_API_END("oem_records_stream_push")
+}
+
+extern "C" int oem_records_stream_set_projected(oem_records_stream *s, const oem_proj_opts *popts)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_set_projected";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    const uint64_t no_groups[1] = {0};
+    OEM_TRY(check_projected_batch(who, nullptr, no_groups, nullptr, 0, popts)); // (popts and its prob_source: the one call's check)
+    std::vector<float> tab;
+    const bool host_only = proj_host_only(s->f, *popts, &tab);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->projected) return fail(OEM_ERR_STATE, "%s: the session is a projected session already", who);
+    if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session", who);
+    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    s->projected = true;
+    s->popts = *popts;
+    s->host_only = host_only; // (the worker reads these two with its first batch, which no thread has pushed yet)
+    s->tab.swap(tab);
+    return OEM_OK;
+    OEM_API_END("oem_records_stream_set_projected")
+}
+
+extern "C" int oem_records_stream_push_projected(oem_records_stream *s, const oem_proj_record *records, const uint64_t *group_off,
+                                                 const uint64_t *read_len, uint64_t n_groups, uint64_t *out_ticket)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_push_projected";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    // the batch's own checks, on the calling thread, before the session is touched (the options are the session's)
+    if (n_groups >= 0x7fffffffull) return fail(OEM_ERR_ARG, "%s: at most 2^31 - 2 groups per batch", who);
+    const oem_proj_opts any{10.f, OEM_PROJ_SIMILARITY};
+    OEM_TRY(check_projected_batch(who, records, group_off, read_len, n_groups, &any));
+    const uint64_t n_records = group_off[n_groups];
+    const size_t rec_at = Batch::groups_records_at<oem_proj_record>(n_groups), bytes = rec_at + sizeof(oem_proj_record) * n_records;
+    return stage_batch(s, who, 2, n_groups, n_records, 0, n_groups ? bytes : 0, [&](char *mem) {
+        std::memcpy(mem, group_off, sizeof(uint64_t) * (n_groups + 1));
+        std::memcpy(mem + sizeof(uint64_t) * (n_groups + 1), read_len, sizeof(uint64_t) * n_groups);
+        if (n_records) std::memcpy(mem + rec_at, records, sizeof(oem_proj_record) * n_records);
+    }, out_ticket);
+    OEM_API_END("oem_records_stream_push_projected")
 }
 
 extern "C" int oem_records_stream_set_names(oem_records_stream *s, uint64_t sort_check_num)
@@ -1028,6 +1154,7 @@ extern "C" int oem_records_stream_set_names(oem_records_stream *s, uint64_t sort
     if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
     std::lock_guard<std::mutex> lk(s->mu);
     if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session already", who);
+    if (s->projected) return fail(OEM_ERR_STATE, "%s: the session is a projected session", who);
     if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
     if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
     s->named = true;
@@ -1050,7 +1177,7 @@ extern "C" int oem_records_stream_push_names(oem_records_stream *s, const oem_al
     if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
     const uint64_t n_bytes = name_off[n];
     const size_t rec_at = Batch::records_at(n), names_at = Batch::names_at(n), bytes = names_at + n_bytes;
-    return stage_batch(s, who, true, 0, n, n_bytes, n ? bytes : 0, [&](char *mem) {
+    return stage_batch(s, who, 1, 0, n, n_bytes, n ? bytes : 0, [&](char *mem) {
         std::memcpy(mem, name_off, sizeof(uint64_t) * (n + 1));
         std::memcpy(mem + rec_at, records, sizeof(oem_aln_record) * n);
         if (n_bytes) std::memcpy(mem + names_at, names, n_bytes);
@@ -1184,6 +1311,7 @@ extern "C" int oem_records_stream_info(const oem_records_stream *s, uint32_t key
     case OEM_RECORDS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us; break;
     case OEM_RECORDS_STREAM_INFO_HOST_BATCHES: *value = s->host_batches; break;
     case OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES: *value = s->out_rows.size(); break;
+    case OEM_RECORDS_STREAM_INFO_HOST_FINISHED: *value = s->host_finished; break;
     default: return fail(OEM_ERR_ARG, "oem_records_stream_info: unknown key %u", key);
     }
     return OEM_OK;

@@ -858,6 +858,30 @@ def make_projected_records(store: SyntheticStore, seed: int = BASE_SEED + 22, de
     return SyntheticProjectedRecords(filters, txp_len, rec, group_off, read_len, beta, kept, discard)
 
 
+def cut_projected_records(spr, sizes):
+    """``make_projected_records``' output cut at group boundaries into batches for a projected session
+    (``RecordsStream(projected=True)``): ``sizes`` are numbers of groups, in input order; a size 0 gives an empty batch,
+    and the groups the sizes leave over form a last batch (also when none are left and ``sizes`` is empty).  ``spr`` is
+    a ``SyntheticProjectedRecords`` or a ``(records, group_off, read_len)`` triple.  Returns a list of ``(records,
+    group_off, read_len)``, each batch's ``group_off`` from 0.  A pure function of its arguments."""
+    records, group_off, read_len = (spr.records, spr.group_off, spr.read_len) if hasattr(spr, "group_off") else spr
+    records = np.asarray(records)
+    group_off, read_len = np.asarray(group_off, dtype=np.uint64), np.asarray(read_len, dtype=np.uint64)
+    n_groups = len(group_off) - 1
+    sizes = [int(s) for s in sizes]
+    if any(s < 0 for s in sizes) or sum(sizes) > n_groups:
+        raise ValueError("the sizes must be non-negative and sum to at most the number of groups")
+    if sum(sizes) < n_groups or not sizes:
+        sizes = sizes + [n_groups - sum(sizes)]
+    out, g0 = [], 0
+    for s in sizes:
+        o = group_off[g0:g0 + s + 1]
+        out.append((np.ascontiguousarray(records[int(o[0]):int(o[-1])]), np.ascontiguousarray(o - o[0]),
+                    np.ascontiguousarray(read_len[g0:g0 + s])))
+        g0 += s
+    return out
+
+
 def cell_shift(rep: int, n_txps: int) -> int:
     """Transcript-id rotation of replica ``rep`` of a cell in ``replicate_cells``."""
     return (rep * 7919) % n_txps
