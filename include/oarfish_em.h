@@ -922,6 +922,81 @@ int oem_cells_stream_set_filters(oem_cells_stream *s, const oem_filters *filters
  * index within its group of cells.  After finish, oem_cells_result_discard_tables gives the cells' tables. */
 int oem_cells_stream_push_records(oem_cells_stream *s, const oem_aln_record *records, const uint64_t *group_off,
                                   uint64_t n_groups, uint64_t *out_ticket);
+/* A BARCODED session: oem_em_run_cells_records_names_sparse for a caller that never holds the whole input and has not
+ * cut it into cells (the reference's single-cell reader, single_cell.rs:196-227 with alignment_parser.rs:244-299,
+ * walks a barcode-collated BAM record by record and cuts a cell where the CB tag changes, while workers sort and run
+ * the cells behind it).  oem_cells_stream_set_barcodes turns a fresh RECORDS session (after
+ * oem_cells_stream_set_filters, before any push) into one; `mode` is the name rule applied inside every cell
+ * (oem_collate_names).  A mode that is neither: OEM_ERR_ARG.  On a plain session, after a push, after finish, or a
+ * second time: OEM_ERR_STATE.
+ *
+ * The rule (oarfish_amd/csrc/oem_collate.h, "Cells from a barcode-collated stream").  The session's input is its
+ * accepted batches concatenated in ticket order; a record's session-global index counts all records of that input,
+ * 64 bits, unmapped ones included.
+ *   - A record with OEM_REC_UNMAPPED takes no part: it cuts no cell and no read, and its barcode and name are never
+ *     looked at (they may be empty or hold a 0 byte).  The other records are the survivors.
+ *   - The survivors' barcodes and names are not empty and hold no 0 byte.
+ *   - A cell is a maximal run of byte-equal barcodes among the survivors; a barcode that comes back later is a NEW cell
+ *     with the same label (the reference has no memory of earlier barcodes either); cells are numbered in closing
+ *     order, which is input order; there is no case folding.  Unlike the reference, an unmapped record that leads a
+ *     run under a foreign barcode gives no empty cell (single_cell.rs:200-213 reads CB before it skips).
+ *   - Inside a cell the name rule as it stands: OEM_COLLATE_SORT orders by name bytes, primary first, index;
+ *     OEM_COLLATE_ADJACENT only cuts.  The same name in two cells is two reads.
+ *   - The open cell -- the trailing run of one barcode so far -- is carried on the device from batch to batch; a batch's
+ *     first run joins it when the barcodes are equal byte for byte; a batch closes every run but its last; a batch
+ *     without a survivor changes nothing; finish closes the open cell.
+ * With S the survivors' indices, ascending, oem_cells_stream_finish gives what oem_em_run_cells_records_names_sparse
+ * gives on records[S], names[S], secondary[S] and the cell_rec_off of the rule, with the session's filters, model and
+ * mode -- however the input was cut and whichever thread pushed what: cell_rec_off, order (S[order of the one call]),
+ * group_off, cell_group_off, kept, the discard tables, the entries' offsets and columns and the cells' labels exactly,
+ * values and infos as a session is held to its one call (which group a cell lands in may change the tile layout,
+ * never the problem).  Cell k of the result is the k-th cell closed; tickets number batches, not cells.
+ *
+ * oem_cells_stream_push_barcodes, one batch: n_records records with one barcode and one name each (a blob and
+ * n_records + 1 offsets from 0, as oem_collate_barcodes and oem_collate_names take them) and their secondary flags
+ * (NULL: none is set).  Thread-safe.  Checked on the calling thread before the session is touched: both offset tables
+ * present, starting at 0 and not decreasing; a blob present when its last offset is above 0; records present when
+ * n_records > 0; n_records <= 2^31 - 2.  An argument error (OEM_ERR_ARG) rejects that batch only and uses no ticket.
+ * Everything is copied into page-locked staging by the caller's thread: the arrays may be freed on return.  The call
+ * blocks while more than max_staged_nnz RECORDS are staged and not yet on the device (a batch larger than that is
+ * accepted when nothing else is staged).  An empty batch, and a batch of unmapped records only, takes a ticket and
+ * changes nothing.  A parse worker takes the batches in ticket order: survivors, checks, the barcode cut, and the
+ * survivors' records, names, flags and indices appended to a device arena of cells not yet run.  Once the arena's
+ * closed cells reach group_nnz records or group_cells cells (the limits of oem_em_run_cells' own group rule always
+ * apply) they run on the session's group workers -- collation, gather, filter, coverage model, EM -- while later
+ * batches arrive; OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH counts such groups, OEM_CELLS_STREAM_INFO_CELLS the
+ * batches and OEM_CELLS_STREAM_INFO_ALIGNMENTS the records accepted.  Nothing run-sized exists on the host before
+ * finish, and no cell is collated or gathered there; a group whose filter must take the host loop (no gap table for
+ * score_prob_denom, a score beyond +-2^24) takes it, with the same result.
+ *
+ * Found on the device and sticky (every later push and finish returns the status and the message of the first):
+ *   - an empty barcode or name, or one with a 0 byte, of a survivor: OEM_ERR_ARG, "record <i> has an empty barcode" /
+ *     "the name of record <i> contains a 0 byte" as the one calls say it, with the batch's "ticket <t>" and the
+ *     session-global index i;
+ *   - a ref_id that is not below n_txps: OEM_ERR_ARG, naming "ticket <t>" and the session-global index;
+ *   - a cell of more than 2^31 - 2 records: OEM_ERR_ARG;
+ *   - an alignment outside its transcript under a coverage model: OEM_ERR_STATE, naming the cell;
+ *   - running out of memory: OEM_ERR_OOM, with everything released.
+ * On a barcoded session oem_cells_stream_push and oem_cells_stream_push_records return OEM_ERR_STATE; on the other
+ * sessions the four calls below do. */
+int oem_cells_stream_set_barcodes(oem_cells_stream *s, uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */);
+int oem_cells_stream_push_barcodes(oem_cells_stream *s, const oem_aln_record *records, uint64_t n_records,
+                                   const uint8_t *barcodes, const uint64_t *barcode_off,
+                                   const uint8_t *names, const uint64_t *name_off,
+                                   const uint8_t *secondary /* or NULL */, uint64_t *out_ticket);
+/* After a successful oem_cells_stream_finish of a barcoded session (otherwise OEM_ERR_STATE): the sizes of what
+ * oem_cells_stream_barcodes_copy gives (each may be NULL) -- the cells, the survivors, the reads (record groups) of all
+ * cells, the bytes of all labels, and the unmapped records that were skipped. */
+int oem_cells_stream_barcodes_dims(const oem_cells_stream *s, uint64_t *n_cells, uint64_t *n_survivors,
+                                   uint64_t *n_groups, uint64_t *barcode_bytes, uint64_t *n_unmapped);
+/* out_barcodes (barcode_bytes) with out_barcode_off (n_cells + 1): the cells' labels in cell order;
+ * out_cell_rec_off (n_cells + 1): the cells' first positions among the survivors; out_order (n_survivors): the
+ * session-global index of the record at every collated position; out_group_off (n_groups + 1): the positions where a
+ * read starts, then n_survivors; out_cell_group_off (n_cells + 1); out_kept (n_groups): the alignments the filter kept
+ * per read.  Each may be NULL; the two barcode outputs only together (OEM_ERR_ARG). */
+int oem_cells_stream_barcodes_copy(const oem_cells_stream *s, uint8_t *out_barcodes, uint64_t *out_barcode_off,
+                                   uint64_t *out_cell_rec_off, uint64_t *out_order, uint64_t *out_group_off,
+                                   uint64_t *out_cell_group_off, uint32_t *out_kept);
 /* Runs what is still staged, waits for every group and returns the cells in ticket order as an ordinary
  * oem_cells_result (oem_cells_result_dims / _copy / _destroy; infos included).  Per cell the result is what
  * oem_em_run_cells_sparse (coverage = 1: oem_em_run_cells_coverage_sparse) gives for that cell, up to floating-point

@@ -77,6 +77,8 @@ ABI_SYMBOLS = [
     "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables", "oem_collate_names",
     "oem_em_run_cells_records_names_sparse", "oem_collate_barcodes", "oem_em_run_cells_records_barcodes_sparse",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
+    "oem_cells_stream_set_barcodes", "oem_cells_stream_push_barcodes", "oem_cells_stream_barcodes_dims",
+    "oem_cells_stream_barcodes_copy",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
     "oem_records_stream_destroy", "oem_records_stream_set_names", "oem_records_stream_push_names",
@@ -253,6 +255,10 @@ def _load(path: str) -> C.CDLL:
                                                  vp, vp, vp, C.POINTER(vp)]
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
     L.oem_cells_stream_push_records.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    L.oem_cells_stream_set_barcodes.argtypes = [vp, u32]
+    L.oem_cells_stream_push_barcodes.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.oem_cells_stream_barcodes_dims.argtypes = [vp] + [C.POINTER(u64)] * 5
+    L.oem_cells_stream_barcodes_copy.argtypes = [vp] * 8
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
     L.oem_cells_stream_push.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]
     L.oem_cells_stream_finish.argtypes = [vp, C.POINTER(vp)]

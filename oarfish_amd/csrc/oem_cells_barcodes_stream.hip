@@ -1,0 +1,923 @@
+// oem_cells_barcodes_stream.hip -- the barcoded form of the per-cell session (oem_cells_stream_set_barcodes,
+// oem_cells_stream_push_barcodes): single_cell.rs:196-227 with alignment_parser.rs:244-299 from the parsed records on.
+// Batches of records go up as a reader produces them, with their barcodes, read names and secondary flags, cut at ANY
+// record position; the device skips the unmapped records, cuts the cells where the barcode changes, carries the open
+// cell from batch to batch, and the session's group workers collate, gather, filter and run the closed cells in groups
+// while later batches arrive.  The rule is stated once, in oem_collate.h ("Cells from a barcode-collated stream").
+//
+//   push      checks the batch on the calling thread, waits for room in the staging budget (max_staged_nnz, counted in
+//             records), takes the ticket and copies everything into page-locked staging outside the lock
+//   parse     one worker, batches in ticket order, on the null stream:
+//               upload; parse_survivors drops the unmapped records; parse_survivor_names gathers the survivors' names
+//               (with their flags) and barcodes into dense blobs and validates them, so that a skipped record's bytes
+//               are never examined;
+//               k_barcode_heads: one survivor per lane, a head when its barcode differs from the previous survivor's --
+//               lengths first, then 8 bytes at a time over the padded blob; survivor 0 compares against the carried
+//               open cell's barcode, which stays on the device;
+//               a scan of the heads gives the batch's cell starts (k_barcode_starts); the labels of the cells it opens
+//               are gathered (gather_names), one barcode per cell, and come down;
+//               the survivors' records (k_records_gather), names, flags and session-global indices are appended to the
+//               CELL ARENA, the device buffer of the cells that are not yet run; the batch's own buffers are released
+//   the cut   once the arena's closed cells reach group_nnz records or group_cells cells (and always within the
+//             driver's own group rule and a collation batch) they go to the session's group workers as groups that
+//             share the arena; what is left -- closed cells short of a group and the open cell -- moves to the head of a
+//             fresh arena with device-to-device copies, so that parsing goes on under the groups' EM.  An arena grows
+//             when a cell outgrows it.
+//   a group   run_names_group's sequence on arena memory instead of caller memory: collate_resident in its device form
+//             over the arena's names and flags, k_order_compose64 (the group's order as session-global indices, kept for
+//             oem_cells_stream_barcodes_copy), records_gather, filter_device_resident, the coverage model if asked,
+//             run_cells_group.  A group whose filter must take the host loop takes it (records_group_host).
+//   finish    the staged batches are parsed, the open cell closes, the rest of the arena is run; the groups' pieces --
+//             order, group_off, cell_group_off, kept -- and the labels are joined on the host.
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <cstdio>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include <hipcub/hipcub.hpp>
+
+#include "oem_cells_barcodes_stream.h"
+#include "oem_collate_device.h"
+#include "oem_parse_device.h"
+
+namespace oem {
+namespace {
+
+constexpr int kBT = 256;
+constexpr int kMaxGroupsInFlight = 3;        // groups handed to the two workers and not yet done: the parser waits beyond
+constexpr uint64_t kFirstArenaRecords = 1ull << 12; // an arena starts small and doubles up to what its cells need
+constexpr uint64_t kFirstArenaBytes = 64ull << 10;
+constexpr int kPoolBatches = 8;              // idle staging allocations kept for reuse
+
+inline dim3 grid_of(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kBT - 1) / kBT, 1)); }
+
+struct U32AsU64 {
+    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
+};
+
+// len bytes at a and at b, 8 at a time; both blobs are readable 15 bytes past their last name
+__device__ __forceinline__ bool bytes_equal(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint64_t len)
+{
+    for (uint64_t at = 0; at < len; at += 8) {
+        uint64_t x, y;
+        __builtin_memcpy(&x, a + at, 8);
+        __builtin_memcpy(&y, b + at, 8);
+        uint64_t d = x ^ y;
+        const uint64_t left = len - at;
+        if (left < 8) d &= (1ull << (8 * left)) - 1;
+        if (d) return false;
+    }
+    return true;
+}
+
+// head[k] = survivor k starts a cell: its barcode differs from survivor k - 1's, survivor 0's from the carry's (no
+// carry: a head).  off: m + 1 offsets from 0 into the dense blob bc.  head[m] = 0, for the scan over m + 1 entries.
+__global__ __launch_bounds__(kBT) void k_barcode_heads(uint64_t m, const uint8_t *__restrict__ bc, const uint64_t *__restrict__ off,
+                                                        const uint8_t *__restrict__ carry, uint64_t carry_len, uint32_t has_carry,
+                                                        uint32_t *__restrict__ head)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
+    if (k > m) return;
+    if (k == m) {
+        head[m] = 0u;
+        return;
+    }
+    const uint64_t b0 = off[k], len = off[k + 1] - b0;
+    bool h;
+    if (k == 0) {
+        h = !has_carry || len != carry_len || !bytes_equal(bc + b0, carry, len);
+    } else {
+        const uint64_t p0 = off[k - 1];
+        h = b0 - p0 != len || !bytes_equal(bc + b0, bc + p0, len);
+    }
+    head[k] = h ? 1u : 0u;
+}
+
+// at: the exclusive scan of head.  The j-th head's survivor and its first name byte in the dense names.
+__global__ __launch_bounds__(kBT) void k_barcode_starts(uint64_t m, const uint32_t *__restrict__ head, const uint64_t *__restrict__ at,
+                                                         const uint64_t *__restrict__ name_off, uint32_t *__restrict__ start,
+                                                         uint64_t *__restrict__ start_byte)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
+    if (k >= m || !head[k]) return;
+    start[at[k]] = (uint32_t)k;
+    start_byte[at[k]] = name_off[k];
+}
+
+// dst[k] = src[k] + add over n entries (add wraps: the tail of an arena moves down by its first byte)
+__global__ __launch_bounds__(kBT) void k_offsets_shift(uint64_t n, const uint64_t *__restrict__ src, uint64_t add, uint64_t *__restrict__ dst)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
+    if (k < n) dst[k] = src[k] + add;
+}
+
+// dst[k] = rec_base + order[k]: the survivors' session-global indices
+__global__ __launch_bounds__(kBT) void k_global_index(uint64_t m, const uint32_t *__restrict__ order, uint64_t rec_base,
+                                                       uint64_t *__restrict__ dst)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
+    if (k < m) dst[k] = rec_base + order[k];
+}
+
+// out[k] = gidx[order[k]]: a group's collated positions as session-global indices (k_order_compose over 64 bits)
+__global__ __launch_bounds__(kBT) void k_order_compose64(uint64_t m, const uint32_t *__restrict__ order, const uint64_t *__restrict__ gidx,
+                                                          uint64_t *__restrict__ out)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
+    if (k < m) out[k] = gidx[order[k]];
+}
+
+// The cells that are not yet run, on the device, in survivor order.  names is 8-byte aligned (an allocation's start) and
+// allocated 16 bytes past cap_bytes; name_off holds n + 1 offsets from 0; sec one byte past cap.
+struct Arena {
+    DevBuf<oem_aln_record> rec;
+    DevBuf<uint8_t> names, sec;
+    DevBuf<uint64_t> name_off, gidx;
+    uint64_t cap = 0, cap_bytes = 0;
+};
+
+int arena_make(uint64_t cap, uint64_t cap_bytes, std::shared_ptr<Arena> *out)
+{
+    std::shared_ptr<Arena> a(new Arena());
+    OEM_TRY(dev_alloc(&a->rec.p, cap, nullptr));
+    OEM_TRY(dev_alloc(&a->names.p, cap_bytes + 16, nullptr));
+    OEM_TRY(dev_alloc(&a->sec.p, cap + 8, nullptr));
+    OEM_TRY(dev_alloc(&a->name_off.p, cap + 1, nullptr));
+    OEM_TRY(dev_alloc(&a->gidx.p, cap, nullptr));
+    OEM_HIP(hipMemset(a->name_off.p, 0, sizeof(uint64_t)));
+    a->cap = cap;
+    a->cap_bytes = cap_bytes;
+    *out = std::move(a);
+    return OEM_OK;
+}
+
+// page-locked (or, when that allocation fails, pageable) host memory of one staged batch
+struct HostMem {
+    void *p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+};
+void host_free(HostMem &h)
+{
+    if (h.pinned) (void)hipHostFree(h.p);
+    else free(h.p);
+    h = HostMem();
+}
+
+inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
+
+// A staged batch: the records, the two offset tables, the flags, the two blobs.
+struct Batch {
+    uint64_t ticket = 0, n = 0, rec_base = 0, bc_bytes = 0, name_bytes = 0;
+    bool has_sec = false, ready = false;
+    HostMem mem;
+    size_t at_bc_off() const { return up64(sizeof(oem_aln_record) * n); }
+    size_t at_name_off() const { return at_bc_off() + up64(sizeof(uint64_t) * (n + 1)); }
+    size_t at_sec() const { return at_name_off() + up64(sizeof(uint64_t) * (n + 1)); }
+    size_t at_bc() const { return at_sec() + up64(n); }
+    size_t at_names() const { return at_bc() + up64(bc_bytes); }
+    size_t bytes() const { return at_names() + up64(name_bytes); }
+    const char *base() const { return (const char *)mem.p; }
+};
+
+// What a group leaves for oem_cells_stream_barcodes_copy, from 0.
+struct Slot {
+    uint32_t n_cells = 0;
+    uint64_t n_records = 0, n_groups = 0;
+    std::vector<uint64_t> order, group_off, cell_group_off; // n_records; n_groups + 1; n_cells + 1
+    std::vector<uint32_t> kept;                             // n_groups
+    bool done = false;
+};
+
+int exclusive_scan_u32(const uint32_t *d_in, uint64_t *d_out, uint64_t n)
+{
+    hipcub::TransformInputIterator<uint64_t, U32AsU64, const uint32_t *> in(d_in, U32AsU64());
+    size_t tb = 0;
+    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, d_out, (int)n, nullptr));
+    DevBuf<uint8_t> tmp;
+    OEM_TRY(dev_alloc(&tmp.p, tb, nullptr));
+    OEM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, d_out, (int)n, nullptr));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
+
+} // namespace
+
+struct BarcodesStream {
+    BarcodesEnv env;
+
+    std::mutex mu;
+    std::condition_variable cv_work, cv_space, cv_groups;
+    std::deque<std::unique_ptr<Batch>> queue; // ticket order
+    std::vector<HostMem> pool;
+    std::vector<uint64_t> ticket_base;        // by ticket: the session-global index of the batch's first record
+    uint64_t next_ticket = 0, total_records = 0, staged_records = 0;
+    int pushes_in_flight = 0, groups_in_flight = 0;
+    bool closed = false, stop = false, cancel = false;
+    int stuck_rc = OEM_OK; // the parse worker's own error (the session's sticky status holds it too)
+    std::string stuck_msg;
+    std::thread worker;
+
+    // -- the parse worker's state (no lock: one thread; finish reads it after the join) ---------------------------------
+    std::shared_ptr<Arena> arena;
+    uint64_t arena_n = 0, arena_bytes = 0;     // survivors and name bytes in the arena
+    std::vector<uint64_t> cstart, cbyte;       // the arena's cells: first survivor and first name byte; the last one is open
+    uint64_t first_cell = 0;                   // the session's number of the arena's first cell
+    DevBuf<uint8_t> carry;                     // the open cell's barcode, padded by 16
+    uint64_t carry_len = 0;
+    uint64_t n_unmapped = 0, n_survivors = 0, run_records = 0; // run_records: survivors handed to the workers
+    std::vector<uint8_t> labels;               // every opened cell's barcode, in cell order
+    std::vector<uint64_t> label_off{0};
+    std::deque<std::unique_ptr<Slot>> slots;   // by group (mu: the deque itself; a slot is its group's alone)
+
+    // -- what finish leaves ------------------------------------------------------------------------------------------------
+    bool assembled = false;
+    std::vector<uint64_t> out_cell_rec_off, out_order, out_group_off, out_cell_group_off;
+    std::vector<uint32_t> out_kept;
+
+    ~BarcodesStream()
+    {
+        for (HostMem &h : pool) host_free(h);
+        for (auto &b : queue)
+            if (b->mem.p) host_free(b->mem);
+    }
+    uint64_t n_cells_opened() const { return label_off.size() - 1; }
+    void set_stuck(int rc, const char *msg)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (stuck_rc == OEM_OK) {
+                stuck_rc = rc;
+                stuck_msg = msg;
+            }
+        }
+        env.set_sticky(rc, msg);
+        cv_space.notify_all();
+    }
+    uint64_t ticket_of(uint64_t record)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        return (uint64_t)(std::upper_bound(ticket_base.begin(), ticket_base.end(), record) - ticket_base.begin()) - 1;
+    }
+
+    int arena_reserve(uint64_t need, uint64_t need_bytes);
+    int run_batch(const Batch &b);
+    int cut_groups(bool final);
+    int run_group(const std::shared_ptr<Arena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot, StreamGroupResult *out,
+                  bool *batched);
+    void work();
+};
+
+// Room for `need` survivors and `need_bytes` name bytes: the arena as it is, or a larger one with the contents moved over.
+int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes)
+{
+    if (arena && need <= arena->cap && need_bytes <= arena->cap_bytes) return OEM_OK;
+    uint64_t cap = arena ? arena->cap : kFirstArenaRecords, cap_bytes = arena ? arena->cap_bytes : kFirstArenaBytes;
+    while (cap < need) cap = std::max(cap * 2, need);
+    while (cap_bytes < need_bytes) cap_bytes = std::max(cap_bytes * 2, need_bytes);
+    std::shared_ptr<Arena> na;
+    OEM_TRY(arena_make(cap, cap_bytes, &na));
+    if (arena && arena_n) {
+        OEM_HIP(hipMemcpy(na->rec.p, arena->rec.p, sizeof(oem_aln_record) * arena_n, hipMemcpyDeviceToDevice));
+        OEM_HIP(hipMemcpy(na->names.p, arena->names.p, arena_bytes, hipMemcpyDeviceToDevice));
+        OEM_HIP(hipMemcpy(na->sec.p, arena->sec.p, arena_n, hipMemcpyDeviceToDevice));
+        OEM_HIP(hipMemcpy(na->name_off.p, arena->name_off.p, sizeof(uint64_t) * (arena_n + 1), hipMemcpyDeviceToDevice));
+        OEM_HIP(hipMemcpy(na->gidx.p, arena->gidx.p, sizeof(uint64_t) * arena_n, hipMemcpyDeviceToDevice));
+    }
+    arena = std::move(na);
+    return OEM_OK;
+}
+
+// One batch on the parse worker: see the head of the file.
+int BarcodesStream::run_batch(const Batch &b)
+{
+    const uint64_t n = b.n;
+    if (n == 0) return OEM_OK;
+    char who[64];
+    snprintf(who, sizeof who, "oem_cells_stream: ticket %llu", (unsigned long long)b.ticket);
+    DevBuf<oem_aln_record> d_in;
+    DevBuf<uint8_t> d_bc, d_names, d_sec;
+    DevBuf<uint64_t> d_bc_off, d_name_off;
+    OEM_TRY(dev_alloc(&d_in.p, n, nullptr));
+    OEM_TRY(dev_alloc(&d_bc.p, b.bc_bytes + 16, nullptr));
+    OEM_TRY(dev_alloc(&d_names.p, b.name_bytes + 16, nullptr));
+    OEM_TRY(dev_alloc(&d_bc_off.p, n + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_name_off.p, n + 1, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_in.p, b.base(), sizeof(oem_aln_record) * n, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_bc_off.p, b.base() + b.at_bc_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_name_off.p, b.base() + b.at_name_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
+    if (b.bc_bytes) OEM_HIP(hipMemcpyAsync(d_bc.p, b.base() + b.at_bc(), b.bc_bytes, hipMemcpyHostToDevice, nullptr));
+    if (b.name_bytes) OEM_HIP(hipMemcpyAsync(d_names.p, b.base() + b.at_names(), b.name_bytes, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemsetAsync(d_bc.p + b.bc_bytes, 0, 16, nullptr));
+    OEM_HIP(hipMemsetAsync(d_names.p + b.name_bytes, 0, 16, nullptr));
+    if (b.has_sec) {
+        OEM_TRY(dev_alloc(&d_sec.p, n + 8, nullptr));
+        OEM_HIP(hipMemcpyAsync(d_sec.p, b.base() + b.at_sec(), n, hipMemcpyHostToDevice, nullptr));
+        OEM_HIP(hipMemsetAsync(d_sec.p + n, 0, 8, nullptr));
+    }
+    OEM_HIP(hipStreamSynchronize(nullptr));
+
+    // the survivors; their barcodes and names as dense blobs, checked
+    DevBuf<uint32_t> d_order;
+    uint64_t m = 0;
+    OEM_TRY(parse_survivors(d_in.p, n, true, &d_order, &m));
+    n_unmapped += n - m;
+    if (m == 0) return OEM_OK;
+    DevBuf<uint8_t> d_dbc, d_dnames, d_dsec, d_none;
+    DevBuf<uint64_t> d_dbc_off, d_dname_off;
+    uint64_t dbc_bytes = 0, dname_bytes = 0, bad_bc = kNoRecord, bad_name = kNoRecord;
+    bool zero_bc = false, zero_name = false;
+    OEM_TRY(parse_survivor_names(d_bc.p, b.bc_bytes, d_bc_off.p, n, d_order.p, m, nullptr, &d_dbc, &d_dbc_off, &d_none, &dbc_bytes, &bad_bc,
+                                 &zero_bc));
+    OEM_TRY(parse_survivor_names(d_names.p, b.name_bytes, d_name_off.p, n, d_order.p, m, d_sec.p, &d_dnames, &d_dname_off, &d_dsec,
+                                 &dname_bytes, &bad_name, &zero_name));
+    if (bad_bc != kNoRecord && bad_bc <= bad_name) {
+        if (zero_bc)
+            return fail(OEM_ERR_ARG, "%s: the barcode of record %llu contains a 0 byte", who, (unsigned long long)(b.rec_base + bad_bc));
+        return fail(OEM_ERR_ARG, "%s: record %llu has an empty barcode", who, (unsigned long long)(b.rec_base + bad_bc));
+    }
+    if (bad_name != kNoRecord) return parse_bad_name(who, zero_name, b.rec_base + bad_name);
+    d_bc.reset();
+    d_bc_off.reset();
+    d_names.reset();
+    d_name_off.reset();
+
+    // the heads and the batch's cell starts
+    DevBuf<uint32_t> d_head, d_start;
+    DevBuf<uint64_t> d_at, d_start_byte;
+    OEM_TRY(dev_alloc(&d_head.p, m + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_at.p, m + 1, nullptr));
+    const bool has_carry = !cstart.empty();
+    hipLaunchKernelGGL(k_barcode_heads, grid_of(m + 1), dim3(kBT), 0, nullptr, m, (const uint8_t *)d_dbc.p, (const uint64_t *)d_dbc_off.p,
+                       (const uint8_t *)carry.p, carry_len, has_carry ? 1u : 0u, d_head.p);
+    OEM_HIP(hipGetLastError());
+    OEM_TRY(exclusive_scan_u32(d_head.p, d_at.p, m + 1));
+    uint64_t nh = 0;
+    OEM_HIP(hipMemcpy(&nh, d_at.p + m, sizeof nh, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> start(nh);
+    std::vector<uint64_t> start_byte(nh);
+    if (nh) {
+        OEM_TRY(dev_alloc(&d_start.p, nh, nullptr));
+        OEM_TRY(dev_alloc(&d_start_byte.p, nh, nullptr));
+        hipLaunchKernelGGL(k_barcode_starts, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_head.p, (const uint64_t *)d_at.p,
+                           (const uint64_t *)d_dname_off.p, d_start.p, d_start_byte.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(start.data(), d_start.p, sizeof(uint32_t) * nh, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(start_byte.data(), d_start_byte.p, sizeof(uint64_t) * nh, hipMemcpyDeviceToHost));
+        // the labels of the cells the batch opens: one barcode per cell; the last one is the new carry
+        DevBuf<uint64_t> d_lab_off;
+        DevBuf<uint8_t> d_lab;
+        uint64_t lab_bytes = 0;
+        OEM_TRY(gather_input_names(d_start.p, nh, d_dbc.p, d_dbc_off.p, &d_lab_off, &d_lab, &lab_bytes));
+        std::vector<uint64_t> lab_off(nh + 1);
+        OEM_HIP(hipMemcpy(lab_off.data(), d_lab_off.p, sizeof(uint64_t) * (nh + 1), hipMemcpyDeviceToHost));
+        const size_t l0 = labels.size();
+        labels.resize(l0 + lab_bytes);
+        if (lab_bytes) OEM_HIP(hipMemcpy(labels.data() + l0, d_lab.p, lab_bytes, hipMemcpyDeviceToHost));
+        label_off.reserve(label_off.size() + nh);
+        for (uint64_t j = 0; j < nh; ++j) label_off.push_back(l0 + lab_off[j + 1]);
+        carry_len = lab_off[nh] - lab_off[nh - 1];
+        carry.reset();
+        OEM_TRY(dev_alloc(&carry.p, carry_len + 16, nullptr));
+        OEM_HIP(hipMemset(carry.p, 0, carry_len + 16));
+        OEM_HIP(hipMemcpy(carry.p, d_lab.p + lab_off[nh - 1], carry_len, hipMemcpyDeviceToDevice));
+    }
+    d_head.reset();
+    d_at.reset();
+    d_dbc.reset();
+    d_dbc_off.reset();
+
+    // the survivors into the arena: records, names, flags, session-global indices
+    OEM_TRY(arena_reserve(arena_n + m, arena_bytes + dname_bytes));
+    Arena &a = *arena;
+    OEM_TRY(records_gather(m, d_order.p, d_in.p, a.rec.p + arena_n));
+    if (dname_bytes) OEM_HIP(hipMemcpyAsync(a.names.p + arena_bytes, d_dnames.p, dname_bytes, hipMemcpyDeviceToDevice, nullptr));
+    hipLaunchKernelGGL(k_offsets_shift, grid_of(m + 1), dim3(kBT), 0, nullptr, m + 1, (const uint64_t *)d_dname_off.p, arena_bytes,
+                       a.name_off.p + arena_n);
+    OEM_HIP(hipGetLastError());
+    if (d_dsec.p) OEM_HIP(hipMemcpyAsync(a.sec.p + arena_n, d_dsec.p, m, hipMemcpyDeviceToDevice, nullptr));
+    else OEM_HIP(hipMemsetAsync(a.sec.p + arena_n, 0, m, nullptr));
+    hipLaunchKernelGGL(k_global_index, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_order.p, b.rec_base, a.gidx.p + arena_n);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    for (uint64_t j = 0; j < nh; ++j) {
+        cstart.push_back(arena_n + start[j]);
+        cbyte.push_back(arena_bytes + start_byte[j]);
+    }
+    arena_n += m;
+    arena_bytes += dname_bytes;
+    n_survivors += m;
+    return cut_groups(false);
+}
+
+// The arena's closed cells (final: all of its cells) in groups to the workers, as far as they fill groups; the rest moves
+// to the head of a fresh arena.
+int BarcodesStream::cut_groups(bool final)
+{
+    const size_t n_all = cstart.size(), n_closed = final ? n_all : (n_all ? n_all - 1 : 0);
+    auto cell_end = [&](size_t i) { return i + 1 < n_all ? cstart[i + 1] : arena_n; };
+    const uint64_t hard = cells_max_group_nnz(), max_batch = std::min<uint64_t>(collate_batch_records(), kCollateMaxBatch);
+    size_t i = 0;
+    while (i < n_closed) {
+        size_t j = i;
+        uint64_t recs = 0;
+        bool full = false;
+        while (j < n_closed) {
+            const uint64_t sz = cell_end(j) - cstart[j];
+            if (sz > kCollateMaxBatch)
+                return fail(OEM_ERR_ARG, "oem_cells_stream: cell %llu has %llu records: at most 2^31 - 2 per cell",
+                            (unsigned long long)(first_cell + j), (unsigned long long)sz);
+            if (j > i && (!cells_group_fits((uint64_t)(j - i) + 1, recs + sz, recs + sz, env.n_txps, hard) || recs + sz > max_batch)) {
+                full = true;
+                break;
+            }
+            recs += sz;
+            ++j;
+            if (recs >= env.group_nnz || j - i >= env.group_cells) {
+                full = true;
+                break;
+            }
+        }
+        if (!full && !final) break;
+        { // the workers take a few groups at a time: every group holds its arena
+            std::unique_lock<std::mutex> lk(mu);
+            cv_groups.wait(lk, [&] { return groups_in_flight < kMaxGroupsInFlight || cancel; });
+            if (cancel) return OEM_OK;
+            ++groups_in_flight;
+        }
+        std::vector<uint64_t> cro(j - i + 1);
+        for (size_t c = i; c < j; ++c) cro[c - i] = cstart[c];
+        cro[j - i] = cell_end(j - 1);
+        Slot *slot;
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            slots.emplace_back(new Slot());
+            slot = slots.back().get();
+        }
+        slot->n_cells = (uint32_t)(j - i);
+        slot->n_records = recs;
+        struct InFlight { // released when the group has run, or with the group when it never does
+            BarcodesStream *b;
+            ~InFlight()
+            {
+                {
+                    std::lock_guard<std::mutex> lk(b->mu);
+                    --b->groups_in_flight;
+                }
+                b->cv_groups.notify_all();
+            }
+        };
+        std::shared_ptr<InFlight> guard(new InFlight{this});
+        std::shared_ptr<Arena> a = arena;
+        const uint64_t cell0 = first_cell + i;
+        run_records += recs;
+        env.submit([this, a, cro, cell0, slot, guard](StreamGroupResult *out, bool *batched) {
+            (void)guard;
+            return run_group(a, cro, cell0, slot, out, batched);
+        });
+        i = j;
+    }
+    if (i == 0) return OEM_OK;
+    // what is left moves to the head of a fresh arena; the groups keep the old one
+    const uint64_t t = i < n_all ? cstart[i] : arena_n, tb = i < n_all ? cbyte[i] : arena_bytes;
+    const uint64_t tail_n = arena_n - t, tail_bytes = arena_bytes - tb;
+    std::shared_ptr<Arena> old = std::move(arena);
+    arena.reset();
+    if (!final) {
+        const uint64_t cap = std::max(tail_n, std::min(old->cap, 2 * env.group_nnz)) + 4096;
+        OEM_TRY(arena_make(cap, std::max(tail_bytes, std::min<uint64_t>(old->cap_bytes, 64 * cap)) + 4096, &arena));
+        if (tail_n) {
+            OEM_HIP(hipMemcpyAsync(arena->rec.p, old->rec.p + t, sizeof(oem_aln_record) * tail_n, hipMemcpyDeviceToDevice, nullptr));
+            if (tail_bytes) OEM_HIP(hipMemcpyAsync(arena->names.p, old->names.p + tb, tail_bytes, hipMemcpyDeviceToDevice, nullptr));
+            OEM_HIP(hipMemcpyAsync(arena->sec.p, old->sec.p + t, tail_n, hipMemcpyDeviceToDevice, nullptr));
+            OEM_HIP(hipMemcpyAsync(arena->gidx.p, old->gidx.p + t, sizeof(uint64_t) * tail_n, hipMemcpyDeviceToDevice, nullptr));
+            hipLaunchKernelGGL(k_offsets_shift, grid_of(tail_n + 1), dim3(kBT), 0, nullptr, tail_n + 1, (const uint64_t *)(old->name_off.p + t),
+                               (uint64_t)0 - tb, arena->name_off.p);
+            OEM_HIP(hipGetLastError());
+            OEM_HIP(hipStreamSynchronize(nullptr));
+        }
+    }
+    first_cell += i;
+    cstart.erase(cstart.begin(), cstart.begin() + i);
+    cbyte.erase(cbyte.begin(), cbyte.begin() + i);
+    for (uint64_t &v : cstart) v -= t;
+    for (uint64_t &v : cbyte) v -= tb;
+    arena_n = tail_n;
+    arena_bytes = tail_bytes;
+    return OEM_OK;
+}
+
+// One group on a group worker: the cells at cro[0 .. n_cells] of the arena `a`, the session's cells cell0 ...
+int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot,
+                              StreamGroupResult *out, bool *batched)
+{
+    *batched = false;
+    const char *who = "oem_cells_stream";
+    StageTimer tm;
+    const uint32_t n_cells = (uint32_t)(cro.size() - 1);
+    const uint64_t r0 = cro[0], m = cro[n_cells] - r0; // (m > 0: a cell holds a survivor)
+    const RecordsFilter &rf = *env.rf;
+    const bool keep = knob("OEM_TEST_KEEP_RECORDS_CSR", 0) != 0;
+    CellsRun run{env.n_txps, env.device, env.max_iter, env.conv_thresh, env.cov};
+    OEM_TRY(ensure_device(env.device));
+    out->infos.assign(n_cells, oem_run_info{});
+    out->tables.assign(n_cells, oem_discard_table{});
+
+    CollateInput in;
+    in.who = who;
+    in.cell_rec_off = cro.data();
+    in.mode = env.mode;
+    in.chunk_bytes = collate_chunk_bytes();
+    in.d_names = a->names.p;
+    in.d_name_off = a->name_off.p + r0;
+    in.d_secondary = a->sec.p + r0;
+    CollateResident cr;
+    double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    OEM_TRY(collate_resident(in, 0, n_cells, 0, 0, 0, info, &cr));
+    tm.lap("barcodes: collate");
+    const uint64_t ng = cr.n_groups;
+    slot->n_groups = ng;
+    slot->cell_group_off.assign((size_t)n_cells + 1, 0);
+    slot->group_off.assign(ng + 1, 0);
+    slot->kept.assign(ng, 0);
+    slot->order.assign(m, 0);
+    OEM_HIP(hipMemcpy(slot->cell_group_off.data(), cr.cell_group_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost));
+    OEM_HIP(hipMemcpy(slot->group_off.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
+    {
+        DevBuf<uint64_t> d_order64;
+        OEM_TRY(dev_alloc(&d_order64.p, m, nullptr));
+        hipLaunchKernelGGL(k_order_compose64, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)cr.order.p,
+                           (const uint64_t *)(a->gidx.p + r0), d_order64.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(slot->order.data(), d_order64.p, sizeof(uint64_t) * m, hipMemcpyDeviceToHost));
+    }
+    RecordsGroup rg;
+    rg.n_groups = ng;
+    rg.cell_group_off = slot->cell_group_off.data();
+    rg.n_cells = n_cells;
+    rg.first_cell = cell0;
+    rg.out_kept = slot->kept.data();
+    rg.out_tables = out->tables.data();
+    rg.blk = &out->blk;
+    rg.infos = out->infos.data();
+    auto bad_ref = [&](uint64_t record, uint32_t ref_id) {
+        return fail(OEM_ERR_ARG, "%s: ticket %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)ticket_of(record),
+                    (unsigned long long)record, ref_id);
+    };
+
+    FilterResult r;
+    FilterCells fc;
+    bool host = rf.host_only;
+    if (!host) {
+        DevBuf<oem_aln_record> d_sorted;
+        const oem_aln_record *d_recs = a->rec.p + r0;
+        if (env.mode == kCollateSort) { // (the adjacent cut's order is the identity)
+            OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
+            OEM_TRY(records_gather(m, cr.order.p, a->rec.p + r0, d_sorted.p));
+            d_recs = d_sorted.p;
+        }
+        fc.n_cells = n_cells;
+        fc.first_cell = cell0;
+        OEM_TRY(filter_device_resident(who, rf.f, rf.txp_len.data(), env.n_txps, rf.tab, d_recs, (const unsigned long long *)cr.group_off.p, ng,
+                                       (const unsigned long long *)cr.cell_group_off.p, run.cov != nullptr || keep, &r, &fc));
+        if (r.bad_ref_record != kNoRecord) { // a collated position of the group: the caller knows its records by their session index
+            oem_aln_record rec;
+            OEM_HIP(hipMemcpy(&rec, d_recs + r.bad_ref_record, sizeof rec, hipMemcpyDeviceToHost));
+            return bad_ref(slot->order[r.bad_ref_record], rec.ref_id);
+        }
+        host = r.host_rerun;
+    }
+    if (host) { // the host loop: the group's records come down and are gathered here
+        std::vector<uint32_t> order(m);
+        std::vector<oem_aln_record> recs(m), sorted(m);
+        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(recs.data(), a->rec.p + r0, sizeof(oem_aln_record) * m, hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < m; ++k) {
+            sorted[k] = recs[order[k]];
+            if (sorted[k].ref_id >= env.n_txps) return bad_ref(slot->order[k], sorted[k].ref_id);
+        }
+        recs = std::vector<oem_aln_record>();
+        rg.records = sorted.data();
+        rg.group_off = slot->group_off.data();
+        OEM_TRY(records_group_host(who, run, rf, rg, batched));
+        slot->done = true;
+        return OEM_OK;
+    }
+    tm.lap("barcodes: gather + filter");
+    cr.order.reset();
+    cr.group_off.reset();
+    cr.cell_group_off.reset();
+    OEM_TRY(records_group_filtered(run, rg, r, fc, batched));
+    tm.lap("barcodes: group run");
+    slot->done = true;
+    return OEM_OK;
+}
+
+void BarcodesStream::work()
+{
+    const bool dev_ok = hipSetDevice(env.device) == hipSuccess;
+    if (!dev_ok) set_stuck(OEM_ERR_HIP, "oem_cells_stream: the parse worker could not select its device");
+    for (;;) {
+        std::unique_ptr<Batch> b;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv_work.wait(lk, [&] { return (!queue.empty() && queue.front()->ready) || (stop && queue.empty()); });
+            if (queue.empty()) break;
+            b = std::move(queue.front());
+            queue.pop_front();
+        }
+        std::string msg;
+        const bool skip = cancel || env.sticky(&msg) != OEM_OK;
+        int rc = OEM_OK;
+        if (!skip) {
+            try {
+                rc = run_batch(*b);
+            } catch (const std::bad_alloc &) {
+                rc = fail(OEM_ERR_OOM, "oem_cells_stream: host allocation failed in the parse worker");
+            } catch (const std::exception &e) {
+                rc = fail(OEM_ERR_STATE, "oem_cells_stream: %s", e.what());
+            }
+            if (rc != OEM_OK) { // sticky, with everything released
+                msg = last_error_text();
+                arena.reset();
+                carry.reset();
+                set_stuck(rc, msg.c_str());
+            }
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            staged_records -= b->n;
+            if (b->mem.p) {
+                if (pool.size() < (size_t)kPoolBatches) pool.push_back(b->mem);
+                else host_free(b->mem);
+                b->mem = HostMem();
+            }
+        }
+        cv_space.notify_all();
+    }
+}
+
+int barcodes_stream_create(const BarcodesEnv &env, BarcodesStream **out)
+{
+    std::unique_ptr<BarcodesStream> b(new BarcodesStream());
+    b->env = env;
+    BarcodesStream *raw = b.get();
+    b->worker = std::thread([raw] { raw->work(); });
+    *out = b.release();
+    return OEM_OK;
+}
+
+int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
+                         const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary,
+                         uint64_t *out_ticket)
+{
+    // the batch's own checks, on the calling thread, before the session is touched
+    const uint64_t n = n_records;
+    if (!barcode_off || !name_off) return fail(OEM_ERR_ARG, "%s: barcode_off or name_off is NULL", who);
+    if (n > kCollateMaxBatch) return fail(OEM_ERR_ARG, "%s: %llu records: at most 2^31 - 2 per batch", who, (unsigned long long)n);
+    for (const auto &t : {std::make_pair("barcode", barcode_off), std::make_pair("name", name_off)}) {
+        if (t.second[0] != 0) return fail(OEM_ERR_ARG, "%s: %s_off must start at 0", who, t.first);
+        for (uint64_t i = 0; i < n; ++i)
+            if (t.second[i + 1] < t.second[i])
+                return fail(OEM_ERR_ARG, "%s: %s_off must be non-decreasing (record %llu)", who, t.first, (unsigned long long)i);
+    }
+    // (a batch of unmapped records only may come without bytes: a blob is needed where its offsets say it has some)
+    if (barcode_off[n] && !barcodes) return fail(OEM_ERR_ARG, "%s: barcodes is NULL and barcode_off[n_records] is not 0", who);
+    if (name_off[n] && !names) return fail(OEM_ERR_ARG, "%s: names is NULL and name_off[n_records] is not 0", who);
+    if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+
+    Batch *b = nullptr;
+    {
+        std::unique_lock<std::mutex> lk(s->mu);
+        ++s->pushes_in_flight;
+        struct InFlight { // (mu is held whenever this scope is left)
+            BarcodesStream *s;
+            ~InFlight() { --s->pushes_in_flight; }
+        } in_flight{s};
+        for (;;) {
+            if (s->stuck_rc != OEM_OK) return fail(s->stuck_rc, "%s", s->stuck_msg.c_str()); // (the first error: before all else)
+            std::string msg;
+            lk.unlock();
+            const int rc = s->env.sticky(&msg); // (a group's error: the session holds it)
+            lk.lock();
+            if (rc != OEM_OK) return fail(rc, "%s", msg.c_str());
+            if (s->closed || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+            if (s->staged_records == 0 || s->staged_records + n <= s->env.max_staged) break;
+            const auto t0 = std::chrono::steady_clock::now();
+            s->cv_space.wait(lk);
+            const uint64_t us = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+            lk.unlock();
+            s->env.add_blocked_us(us);
+            lk.lock();
+        }
+        std::unique_ptr<Batch> nb(new Batch());
+        s->ticket_base.reserve(s->ticket_base.size() + 1);
+        nb->ticket = s->next_ticket;
+        nb->n = n;
+        nb->rec_base = s->total_records;
+        nb->bc_bytes = barcode_off[n];
+        nb->name_bytes = name_off[n];
+        nb->has_sec = secondary != nullptr && n > 0;
+        if (n) { // the smallest idle allocation that holds the batch
+            const size_t need = nb->bytes();
+            size_t best = s->pool.size();
+            for (size_t k = 0; k < s->pool.size(); ++k)
+                if (s->pool[k].bytes >= need && (best == s->pool.size() || s->pool[k].bytes < s->pool[best].bytes)) best = k;
+            if (best != s->pool.size()) {
+                nb->mem = s->pool[best];
+                s->pool.erase(s->pool.begin() + best);
+            }
+        }
+        b = nb.get();
+        s->queue.push_back(std::move(nb));
+        s->ticket_base.push_back(s->total_records);
+        ++s->next_ticket;
+        s->total_records += n;
+        s->staged_records += n;
+        ++s->pushes_in_flight; // (the copy below: until the batch is ready)
+    }
+    // outside the lock: the allocation, where the pool had none, and the copies.  The batch stays in the queue until it
+    // is ready (the worker waits for that), so `b` is valid.
+    bool oom = false;
+    if (n && !b->mem.p) {
+        const size_t need = b->bytes(), cap = need + need / 8 + 4096;
+        if (hipSetDevice(s->env.device) == hipSuccess && hipHostMalloc(&b->mem.p, cap, hipHostMallocPortable) == hipSuccess) {
+            b->mem.pinned = true;
+        } else {
+            (void)hipGetLastError();
+            b->mem.p = malloc(cap);
+            oom = !b->mem.p;
+        }
+        b->mem.bytes = cap;
+    }
+    if (n && b->mem.p) {
+        char *mem = (char *)b->mem.p;
+        std::memcpy(mem, records, sizeof(oem_aln_record) * n);
+        std::memcpy(mem + b->at_bc_off(), barcode_off, sizeof(uint64_t) * (n + 1));
+        std::memcpy(mem + b->at_name_off(), name_off, sizeof(uint64_t) * (n + 1));
+        if (b->has_sec) std::memcpy(mem + b->at_sec(), secondary, n);
+        if (b->bc_bytes) std::memcpy(mem + b->at_bc(), barcodes, b->bc_bytes);
+        if (b->name_bytes) std::memcpy(mem + b->at_names(), names, b->name_bytes);
+    }
+    const uint64_t ticket = b->ticket;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (oom) {
+            b->n = 0; // (nothing was staged: the worker passes it by)
+            s->staged_records -= n;
+        }
+        b->ready = true;
+        --s->pushes_in_flight;
+    }
+    if (oom) s->set_stuck(OEM_ERR_OOM, "oem_cells_stream_push_barcodes: host allocation of the staging memory failed");
+    s->cv_work.notify_all();
+    if (oom) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who);
+    if (out_ticket) *out_ticket = ticket;
+    return OEM_OK;
+}
+
+bool barcodes_stream_push_in_flight(BarcodesStream *b)
+{
+    std::lock_guard<std::mutex> lk(b->mu);
+    return b->pushes_in_flight != 0;
+}
+
+int barcodes_stream_close(BarcodesStream *b, const char *who)
+{
+    {
+        std::lock_guard<std::mutex> lk(b->mu);
+        b->closed = true;
+        b->stop = true;
+    }
+    b->cv_work.notify_all();
+    b->cv_space.notify_all();
+    if (b->worker.joinable()) b->worker.join();
+    std::string msg;
+    const int rc = b->env.sticky(&msg);
+    if (rc != OEM_OK) return fail(rc, "%s", msg.c_str());
+    int rc2 = OEM_OK;
+    try {
+        OEM_HIP(hipSetDevice(b->env.device));
+        rc2 = b->cut_groups(true); // the open cell closes with the session
+    } catch (const std::bad_alloc &) {
+        rc2 = fail(OEM_ERR_OOM, "%s: host allocation failed", who);
+    }
+    b->arena.reset(); // (the groups hold it)
+    b->carry.reset();
+    if (rc2 != OEM_OK) {
+        const std::string m2 = last_error_text();
+        b->set_stuck(rc2, m2.c_str());
+        return fail(rc2, "%s", m2.c_str());
+    }
+    return OEM_OK;
+}
+
+int barcodes_stream_assemble(BarcodesStream *b, const char *who)
+{
+    const uint64_t nc = b->n_cells_opened();
+    uint64_t n_groups = 0, n_rec = 0, cells = 0;
+    for (const auto &sl : b->slots) {
+        if (!sl->done) return fail(OEM_ERR_STATE, "%s: a group of cells did not run", who);
+        n_groups += sl->n_groups;
+        n_rec += sl->n_records;
+        cells += sl->n_cells;
+    }
+    if (cells != nc || n_rec != b->n_survivors)
+        return fail(OEM_ERR_STATE, "%s: the groups cover %llu of %llu cells", who, (unsigned long long)cells, (unsigned long long)nc);
+    b->out_cell_rec_off.assign(1, 0);
+    b->out_cell_rec_off.reserve(nc + 1);
+    b->out_cell_group_off.assign(1, 0);
+    b->out_cell_group_off.reserve(nc + 1);
+    b->out_group_off.reserve(n_groups + 1);
+    b->out_order.reserve(n_rec);
+    b->out_kept.reserve(n_groups);
+    uint64_t rec_base = 0, group_base = 0;
+    for (auto &sl : b->slots) {
+        // a cell's records from its groups: the cells' first groups, sampled in the group's own group_off
+        for (uint32_t c = 1; c <= sl->n_cells; ++c) {
+            b->out_cell_rec_off.push_back(rec_base + sl->group_off[sl->cell_group_off[c]]);
+            b->out_cell_group_off.push_back(group_base + sl->cell_group_off[c]);
+        }
+        for (uint64_t g = 0; g < sl->n_groups; ++g) b->out_group_off.push_back(rec_base + sl->group_off[g]);
+        b->out_order.insert(b->out_order.end(), sl->order.begin(), sl->order.end());
+        b->out_kept.insert(b->out_kept.end(), sl->kept.begin(), sl->kept.end());
+        rec_base += sl->n_records;
+        group_base += sl->n_groups;
+        sl.reset();
+    }
+    b->out_group_off.push_back(rec_base);
+    b->slots.clear();
+    b->assembled = true;
+    return OEM_OK;
+}
+
+void barcodes_stream_counts(BarcodesStream *b, uint64_t *n_batches, uint64_t *n_records)
+{
+    std::lock_guard<std::mutex> lk(b->mu);
+    *n_batches = b->next_ticket;
+    *n_records = b->total_records;
+}
+
+int barcodes_stream_dims(const BarcodesStream *b, const char *who, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
+                         uint64_t *barcode_bytes, uint64_t *n_unmapped)
+{
+    if (!b->assembled) return fail(OEM_ERR_STATE, "%s: after a successful oem_cells_stream_finish", who);
+    if (n_cells) *n_cells = b->n_cells_opened();
+    if (n_survivors) *n_survivors = b->n_survivors;
+    if (n_groups) *n_groups = b->out_kept.size();
+    if (barcode_bytes) *barcode_bytes = b->labels.size();
+    if (n_unmapped) *n_unmapped = b->n_unmapped;
+    return OEM_OK;
+}
+
+int barcodes_stream_copy(const BarcodesStream *b, const char *who, uint8_t *out_barcodes, uint64_t *out_barcode_off,
+                         uint64_t *out_cell_rec_off, uint64_t *out_order, uint64_t *out_group_off, uint64_t *out_cell_group_off,
+                         uint32_t *out_kept)
+{
+    if (!b->assembled) return fail(OEM_ERR_STATE, "%s: after a successful oem_cells_stream_finish", who);
+    if ((out_barcodes == nullptr) != (out_barcode_off == nullptr))
+        return fail(OEM_ERR_ARG, "%s: out_barcodes and out_barcode_off go together", who);
+    auto put = [](auto *dst, const auto &v) {
+        if (dst && !v.empty()) std::memcpy(dst, v.data(), sizeof(v[0]) * v.size());
+    };
+    put(out_barcodes, b->labels);
+    put(out_barcode_off, b->label_off);
+    put(out_cell_rec_off, b->out_cell_rec_off);
+    put(out_order, b->out_order);
+    put(out_group_off, b->out_group_off);
+    put(out_cell_group_off, b->out_cell_group_off);
+    put(out_kept, b->out_kept);
+    return OEM_OK;
+}
+
+void barcodes_stream_cancel(BarcodesStream *b)
+{
+    {
+        std::lock_guard<std::mutex> lk(b->mu);
+        b->cancel = true;
+        b->closed = true;
+        b->stop = true;
+    }
+    b->cv_work.notify_all();
+    b->cv_space.notify_all();
+    b->cv_groups.notify_all();
+    if (b->worker.joinable()) b->worker.join();
+}
+
+void barcodes_stream_destroy(BarcodesStream *b)
+{
+    if (!b) return;
+    barcodes_stream_cancel(b);
+    (void)hipSetDevice(b->env.device);
+    delete b;
+}
+
+} // namespace oem

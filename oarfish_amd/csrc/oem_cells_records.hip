@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "oem_cells.h"
+#include "oem_cells_barcodes_stream.h"
 #include "oem_collate_device.h"
 #include "oem_filter_device.h"
 
@@ -451,6 +452,17 @@ thread_local double g_cells_barcodes_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 } // namespace
 
 void cells_barcodes_last_call(double *out8) { std::memcpy(out8, g_cells_barcodes_last, sizeof g_cells_barcodes_last); }
+
+// the two ends of run_names_group for the barcoded session (oem_cells_barcodes_stream.hip), whose groups are cut from
+// its device arena
+int records_group_filtered(const CellsRun &run, const RecordsGroup &rg, FilterResult &r, FilterCells &fc, bool *batched)
+{
+    return run_filtered_group(run, rg, r, fc, knob("OEM_TEST_KEEP_RECORDS_CSR", 0) != 0, batched);
+}
+int records_group_host(const char *who, const CellsRun &run, const RecordsFilter &rf, const RecordsGroup &rg, bool *batched)
+{
+    return run_records_group_host(who, run, rf, rg, batched);
+}
 
 // The records [r0, r0 + m) of the caller into d (input order) through the upload lanes.
 int upload_records(const oem_aln_record *records, uint64_t m, oem_aln_record *d)

@@ -22,6 +22,10 @@
 // worker concatenates the group offsets on the host (8 B per read) and runs the records-to-group step of
 // oem_em_run_cells_records_sparse (run_records_group, oem_cells_records.hip) straight from the page-locked staging:
 // filter, per-cell offsets and discard tables on the device, then run_cells_group.  k_stream_row_ptr is not needed there.
+//
+// A BARCODED session (oem_cells_stream_set_barcodes, oem_cells_stream_push_barcodes) takes batches of records cut at any
+// position and finds the cells itself (oem_cells_barcodes_stream.hip).  Nothing of it is staged here: its groups come
+// from its device arena as closures (Group::dev_run) that the same two workers run, in the same result slots.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -35,6 +39,7 @@
 #include <vector>
 
 #include "oem_cells.h"
+#include "oem_cells_barcodes_stream.h"
 
 namespace oem {
 namespace {
@@ -138,6 +143,7 @@ struct Group {
     std::vector<uint64_t> read_off{0}, aln_off{0}; // n_cells + 1 each
     int pending = 0;           // pushes still copying into the staging
     std::vector<uint64_t> host_rp; // the concatenated row pointers, only when the host layout builder asks
+    StreamGroupRun dev_run;        // a barcoded session's group: nothing is staged, it runs from the session's device arena
     uint64_t rp_used() const { return n_reads + n_cells; }
 
     static const uint64_t *host_row_ptr(void *ctx)
@@ -160,11 +166,7 @@ struct Group {
     }
 };
 
-struct GroupResult {
-    SparseBlock blk;
-    std::vector<oem_run_info> infos;
-    std::vector<oem_discard_table> tables; // a records session: the cells' discard tables
-};
+using GroupResult = StreamGroupResult; // (tables: a records session's discard tables)
 
 // what a push stages: a cell's CSR, or its records
 struct CellArrays {
@@ -188,6 +190,7 @@ struct oem_cells_stream {
     CellsCoverage cov;
     bool records_mode = false; // set by oem_cells_stream_set_filters before the first push
     RecordsFilter rf;
+    BarcodesStream *bc = nullptr; // set by oem_cells_stream_set_barcodes: the barcoded form of a records session
 
     mutable std::mutex mu;
     std::condition_variable cv_work, cv_space, cv_copy;
@@ -391,7 +394,9 @@ void oem_cells_stream::work(int wk)
         std::string msg;
         if (!skip) {
             try {
-                rc = records_mode ? run_records(*g, &res, &batched) : run_group(*g, st, &res, &batched, &uploaded);
+                rc = g->dev_run      ? g->dev_run(&res, &batched)
+                     : records_mode ? run_records(*g, &res, &batched)
+                                    : run_group(*g, st, &res, &batched, &uploaded);
             } catch (const std::bad_alloc &) {
                 rc = fail(OEM_ERR_OOM, "oem_cells_stream: host allocation failed in a device worker");
             } catch (const std::exception &e) {
@@ -481,6 +486,7 @@ int oem_cells_stream::push_cell(const char *who, bool records, const CellArrays 
     try {
         for (;;) {
             if (finish_called || cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+            if (bc) return fail(OEM_ERR_STATE, "%s: a barcoded session takes batches through oem_cells_stream_push_barcodes", who);
             if (records != records_mode)
                 return fail(OEM_ERR_STATE, records ? "%s: not a records session (oem_cells_stream_set_filters)"
                                                    : "%s: a records session takes cells through oem_cells_stream_push_records", who);
@@ -642,6 +648,87 @@ extern "C" int oem_cells_stream_push_records(oem_cells_stream *s, const oem_aln_
     return s->push_cell(who, true, a, n_groups, group_off[n_groups], out_ticket);
 }
 
+extern "C" int oem_cells_stream_set_barcodes(oem_cells_stream *s, uint32_t mode)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_set_barcodes";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (mode != kCollateSort && mode != kCollateAdjacent)
+        return fail(OEM_ERR_ARG, "%s: mode must be OEM_COLLATE_SORT or OEM_COLLATE_ADJACENT", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->bc) return fail(OEM_ERR_STATE, "%s: the session is a barcoded session already", who);
+    if (!s->records_mode) return fail(OEM_ERR_STATE, "%s: not a records session (oem_cells_stream_set_filters)", who);
+    if (s->next_ticket || s->pushes_in_flight || s->open) return fail(OEM_ERR_STATE, "%s: a cell has been pushed already", who);
+    BarcodesEnv env;
+    env.n_txps = s->o.n_txps;
+    env.device = s->o.device;
+    env.max_iter = s->o.max_iter;
+    env.conv_thresh = s->o.conv_thresh;
+    env.cov = s->o.coverage ? &s->cov : nullptr;
+    env.rf = &s->rf;
+    env.group_nnz = s->group_nnz;
+    env.group_cells = s->group_cells;
+    env.max_staged = s->max_staged;
+    env.mode = mode;
+    env.submit = [s](StreamGroupRun run) { // the group's place in the result is its place in this order
+        std::unique_ptr<Group> g(new Group());
+        g->dev_run = std::move(run);
+        std::lock_guard<std::mutex> lk2(s->mu);
+        g->index = s->results.size();
+        s->results.emplace_back();
+        s->queue.push_back(std::move(g));
+        s->cv_work.notify_one();
+    };
+    env.set_sticky = [s](int rc, const char *msg) {
+        std::lock_guard<std::mutex> lk2(s->mu);
+        s->set_sticky(rc, msg);
+    };
+    env.sticky = [s](std::string *msg) {
+        std::lock_guard<std::mutex> lk2(s->mu);
+        if (s->sticky_rc != OEM_OK) *msg = s->sticky_msg;
+        return s->sticky_rc;
+    };
+    env.add_blocked_us = [s](uint64_t us) {
+        std::lock_guard<std::mutex> lk2(s->mu);
+        s->blocked_us += us;
+    };
+    return barcodes_stream_create(env, &s->bc);
+    OEM_API_END("oem_cells_stream_set_barcodes")
+}
+
+extern "C" int oem_cells_stream_push_barcodes(oem_cells_stream *s, const oem_aln_record *records, uint64_t n_records,
+                                              const uint8_t *barcodes, const uint64_t *barcode_off, const uint8_t *names,
+                                              const uint64_t *name_off, const uint8_t *secondary, uint64_t *out_ticket)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_push_barcodes";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a barcoded session (oem_cells_stream_set_barcodes)", who);
+    return barcodes_stream_push(s->bc, who, records, n_records, barcodes, barcode_off, names, name_off, secondary, out_ticket);
+    OEM_API_END("oem_cells_stream_push_barcodes")
+}
+
+extern "C" int oem_cells_stream_barcodes_dims(const oem_cells_stream *s, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
+                                              uint64_t *barcode_bytes, uint64_t *n_unmapped)
+{
+    const char *who = "oem_cells_stream_barcodes_dims";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a barcoded session (oem_cells_stream_set_barcodes)", who);
+    return barcodes_stream_dims(s->bc, who, n_cells, n_survivors, n_groups, barcode_bytes, n_unmapped);
+}
+
+extern "C" int oem_cells_stream_barcodes_copy(const oem_cells_stream *s, uint8_t *out_barcodes, uint64_t *out_barcode_off,
+                                              uint64_t *out_cell_rec_off, uint64_t *out_order, uint64_t *out_group_off,
+                                              uint64_t *out_cell_group_off, uint32_t *out_kept)
+{
+    const char *who = "oem_cells_stream_barcodes_copy";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a barcoded session (oem_cells_stream_set_barcodes)", who);
+    return barcodes_stream_copy(s->bc, who, out_barcodes, out_barcode_off, out_cell_rec_off, out_order, out_group_off,
+                                out_cell_group_off, out_kept);
+}
+
 extern "C" int oem_cells_stream_finish(oem_cells_stream *s, oem_cells_result **out)
 {
     OEM_API_BEGIN
@@ -652,17 +739,31 @@ extern "C" int oem_cells_stream_finish(oem_cells_stream *s, oem_cells_result **o
     {
         std::lock_guard<std::mutex> lk(s->mu);
         if (s->finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished already", who);
-        if (s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a push is in flight", who);
+        if (s->pushes_in_flight || (s->bc && barcodes_stream_push_in_flight(s->bc))) return fail(OEM_ERR_STATE, "%s: a push is in flight", who);
         s->finish_called = true;
         s->close_open();
+        if (!s->bc) s->stop = true;
+    }
+    int bc_rc = OEM_OK;
+    std::string bc_msg;
+    if (s->bc) { // the staged batches are parsed, the open cell closes, the last groups go to the workers
+        bc_rc = barcodes_stream_close(s->bc, who);
+        if (bc_rc != OEM_OK) bc_msg = last_error_text();
+        std::lock_guard<std::mutex> lk(s->mu);
         s->stop = true;
     }
     s->cv_work.notify_all();
     for (auto &t : s->workers)
         if (t.joinable()) t.join();
     if (s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str());
+    if (bc_rc != OEM_OK) return fail(bc_rc, "%s", bc_msg.c_str());
+    uint64_t n_cells = s->next_ticket;
+    if (s->bc) {
+        OEM_TRY(barcodes_stream_assemble(s->bc, who));
+        OEM_TRY(barcodes_stream_dims(s->bc, who, &n_cells, nullptr, nullptr, nullptr, nullptr));
+    }
     std::unique_ptr<oem_cells_result> r(new oem_cells_result());
-    r->n_cells = (uint32_t)s->next_ticket;
+    r->n_cells = (uint32_t)n_cells;
     r->infos.reserve(r->n_cells);
     std::vector<SparseBlock> blocks;
     blocks.reserve(s->results.size());
@@ -684,9 +785,11 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
 {
     if (!s || !value) return fail(OEM_ERR_ARG, "oem_cells_stream_info: NULL argument");
     std::lock_guard<std::mutex> lk(s->mu);
+    uint64_t bc_batches = 0, bc_records = 0;
+    if (s->bc) barcodes_stream_counts(s->bc, &bc_batches, &bc_records);
     switch (key) {
-    case OEM_CELLS_STREAM_INFO_CELLS: *value = s->next_ticket; break;
-    case OEM_CELLS_STREAM_INFO_ALIGNMENTS: *value = s->total_nnz; break;
+    case OEM_CELLS_STREAM_INFO_CELLS: *value = s->bc ? bc_batches : s->next_ticket; break; // (a barcoded session: batches)
+    case OEM_CELLS_STREAM_INFO_ALIGNMENTS: *value = s->bc ? bc_records : s->total_nnz; break;
     case OEM_CELLS_STREAM_INFO_GROUPS: *value = s->groups_started; break;
     case OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH: *value = s->groups_before_finish; break;
     case OEM_CELLS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us; break;
@@ -699,6 +802,7 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
 extern "C" void oem_cells_stream_destroy(oem_cells_stream *s)
 {
     if (!s) return;
+    if (s->bc) barcodes_stream_cancel(s->bc); // (nothing more is parsed or handed to the workers)
     {
         std::lock_guard<std::mutex> lk(s->mu);
         if (!s->finish_called) s->cancel = true; // queued groups are dropped; a group on the device runs to its end
@@ -711,5 +815,6 @@ extern "C" void oem_cells_stream_destroy(oem_cells_stream *s)
     for (auto &t : s->workers)
         if (t.joinable()) t.join();
     (void)hipSetDevice(s->o.device); // the coverage tables and the pinned arenas are released on their device
+    barcodes_stream_destroy(s->bc);
     delete s;
 }

@@ -326,4 +326,71 @@ struct ParseBulkStream {
     void finish() { close(); }
 };
 
+// Cells from a barcode-collated stream (ParseCellsStream below, oem_cells_stream_push_barcodes): single_cell.rs:196-227
+// with alignment_parser.rs:244-299 -- the reference's single-cell driver walks a barcode-collated BAM record by record,
+// cuts a cell where the CB tag changes and hands the cell to a worker that sorts it by read name.  The session's input
+// is its accepted batches concatenated in ticket order; a record's session-global index (64 bits) counts all records
+// of all batches in that order, unmapped ones included.
+//   skip     a record with OEM_REC_UNMAPPED takes no part in anything below (alignment_parser.rs:265-288): it cuts no
+//            cell and no read, its barcode and its name are never looked at (they may be empty or hold a 0 byte), and
+//            n_unmapped counts these records.  The survivors are the other records, in input order.
+//   bytes    the survivors' barcodes and names are not empty and hold no 0 byte; the first violation, by the record's
+//            session-global index, is an error.
+//   cells    a cell is a maximal run of byte-equal barcodes among the survivors.  A barcode that comes back later is a
+//            NEW cell with the same label: the reference has no memory of earlier barcodes either.  Cells are numbered
+//            in closing order, which is input order.  There is no case folding: the reference uppercases the label
+//            (single_cell.rs:206) but compares raw bytes (alignment_parser.rs:153), so lower-case input never
+//            terminates there and there is nothing to mirror.
+//   NOT reproduced: the reference reads the CB of the peeked record BEFORE it skips unmapped records
+//            (single_cell.rs:200-213), so an unmapped record that leads a run under a foreign barcode gives an empty
+//            cell there.  Here it gives nothing.
+//   inside a cell   the name rule at the top of this file, as it stands: kCollateSort orders by name bytes, primary
+//            first, index; kCollateAdjacent only cuts.  The same name in two cells is two groups.
+//   stream   the open cell (the carry) is the trailing run of one barcode among all survivors pushed so far;
+//            a batch's first run joins it when the barcodes are equal byte for byte, otherwise the carry is closed
+//            before the batch's first run; a batch closes every run but its last, which becomes the new carry; a batch
+//            without a survivor (an empty batch, a batch of unmapped records only) changes nothing but the counts;
+//            finish closes the carry.
+// With S the survivors' session-global indices, ascending, the session gives what the one call over the cells
+// (oem_em_run_cells_records_names_sparse) gives on R[S], names[S], secondary[S] with the walk's cell_rec_off.
+struct ParseCellsStream {
+    uint64_t n_records = 0, n_unmapped = 0;        // of all batches pushed
+    std::vector<uint64_t> survivors;               // S
+    std::vector<uint64_t> cell_rec_off{0};         // positions in S: the closed cells' first survivors, then their end
+    std::vector<std::vector<uint8_t>> cell_barcode; // the closed cells' labels
+    bool open = false;                             // the carry: its barcode and its size so far
+    std::vector<uint8_t> open_barcode;
+    uint64_t open_size = 0;
+
+    void close()
+    {
+        if (!open) return;
+        cell_rec_off.push_back(cell_rec_off.back() + open_size);
+        cell_barcode.push_back(open_barcode);
+        open = false;
+        open_size = 0;
+    }
+    template <typename Rec>
+    void push(const Rec *records, uint64_t n, const uint8_t *barcodes, const uint64_t *barcode_off)
+    {
+        for (uint64_t i = 0; i < n; ++i) {
+            if (records[i].flags & kRecUnmapped) {
+                ++n_unmapped;
+                continue;
+            }
+            const uint8_t *bc = barcodes + barcode_off[i];
+            const uint64_t len = barcode_off[i + 1] - barcode_off[i];
+            if (!open || collate_name_cmp(bc, len, open_barcode.data(), open_barcode.size()) != 0) {
+                close();
+                open = true;
+                open_barcode.assign(bc, bc + len);
+            }
+            ++open_size;
+            survivors.push_back(n_records + i);
+        }
+        n_records += n;
+    }
+    void finish() { close(); }
+};
+
 } // namespace oem

@@ -571,10 +571,22 @@ class CellsStream:
     ``filters`` with ``txp_len`` makes it a RECORDS session (``oem_cells_stream_set_filters``): cells are pushed as
     their alignment records with ``push_records`` and filtered on the device, as ``em_cells_records_sparse`` does; the
     budgets then count records, and ``discard_tables()`` gives every cell's discard table after ``finish()``.
+
+    ``barcodes=True`` (with ``filters``) makes it a BARCODED session (``oem_cells_stream_set_barcodes``): the input is a
+    barcode-collated stream of records, pushed with ``push_batch`` in batches cut at any record position.  The device
+    skips the unmapped records, cuts a cell where the barcode changes, carries the open cell from batch to batch and
+    runs the closed cells in groups while later batches arrive.  ``mode`` is ``collate_names``' (applied inside every
+    cell).  ``finish()`` returns the usual four values -- what ``em_cells_records_sparse(names=, collate="device")`` gives
+    for the surviving records with the cells the barcodes cut -- and ``cells()`` what the session found.
     """
 
     def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
-                 group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None):
+                 group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None,
+                 barcodes: bool = False, mode: str = "sort"):
+        if barcodes and filters is None:
+            raise ValueError("a barcoded session is a records session: it needs filters and txp_len")
+        if mode not in _COLLATE_MODES:
+            raise ValueError(f"mode must be one of {sorted(_COLLATE_MODES)}, not {mode!r}")
         if filters is not None and txp_len is None and coverage is not None:
             txp_len = coverage.get("txp_len")
         if filters is not None and txp_len is None:
@@ -582,6 +594,8 @@ class CellsStream:
         if filters is not None and coverage is not None and "txp_len" not in coverage:
             coverage = dict(coverage, txp_len=txp_len)
         self._tables = None
+        self._cells = None
+        self._barcoded = bool(barcodes)
         self._device = device
         records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
@@ -611,6 +625,8 @@ class CellsStream:
                 raise ValueError("txp_len must have n_txps entries")
             try:
                 self.set_filters(F, tl)
+                if barcodes:
+                    self._check(self._L.oem_cells_stream_set_barcodes(self._h, _COLLATE_MODES[mode]))
             except BaseException:
                 self.close()
                 raise
@@ -696,12 +712,73 @@ class CellsStream:
                                                           group_off.ctypes.data, len(group_off) - 1, C.byref(ticket)))
         return int(ticket.value)
 
+    def push_batch(self, records, barcodes, names, secondary=None) -> int:
+        """One batch of a barcoded session: ``records`` with one barcode and one read name each -- ``(blob, offsets)``
+        pairs or sequences of ``bytes``, as ``collate_barcodes`` and ``collate_names`` take them -- and their
+        ``secondary`` flags.  The batch may start and end anywhere: inside a cell, inside a read.  Returns the batch's
+        ticket; the session's input is its batches in ticket order.  Thread-safe; releases the GIL."""
+        from .types import pack_read_names
+        if not self._h:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
+        records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
+        n = len(records)
+        if _n_packed(barcodes) != n:
+            raise ValueError("barcodes must have one entry per record")
+        if _n_packed(names) != n:
+            raise ValueError("names must have one entry per record")
+        bc_blob, bc_off = pack_read_names(barcodes, n)
+        blob, off = pack_read_names(names, n)
+        sec = None
+        if secondary is not None:
+            sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
+            if len(sec) != n:
+                raise ValueError("secondary must have one entry per record")
+        ticket = C.c_uint64(0)
+        self._check(self._L.oem_cells_stream_push_barcodes(
+            self._h, records.ctypes.data if n else None, n, bc_blob.ctypes.data if len(bc_blob) else None, bc_off.ctypes.data,
+            blob.ctypes.data if len(blob) else None, off.ctypes.data, None if sec is None or not n else sec.ctypes.data,
+            C.byref(ticket)))
+        return int(ticket.value)
+
+    def cells(self) -> dict:
+        """After ``finish()`` of a barcoded session: ``barcodes`` (the cells' labels, a list of ``bytes``, in cell order),
+        ``cell_rec_off`` (positions among the surviving records), ``order`` (uint64: the index in the pushed stream of the
+        record at every collated position), ``group_off``, ``cell_group_off``, ``kept`` and ``n_unmapped``."""
+        if self._cells is None:
+            raise _lib.OemError(_lib.OEM_ERR_STATE, "cells(): a finished barcoded session has them")
+        return self._cells
+
+    def _take_cells(self) -> dict:
+        d = [C.c_uint64(0) for _ in range(5)]
+        self._check(self._L.oem_cells_stream_barcodes_dims(self._h, *[C.byref(x) for x in d]))
+        nc, m, ng, nb, n_unmapped = (int(x.value) for x in d)
+        blob = np.zeros(max(nb, 1), dtype=np.uint8)
+        bc_off = np.zeros(nc + 1, dtype=np.uint64)
+        cell_rec_off = np.zeros(nc + 1, dtype=np.uint64)
+        order = np.zeros(max(m, 1), dtype=np.uint64)
+        group_off = np.zeros(ng + 1, dtype=np.uint64)
+        cell_group_off = np.zeros(nc + 1, dtype=np.uint64)
+        kept = np.zeros(max(ng, 1), dtype=np.uint32)
+        self._check(self._L.oem_cells_stream_barcodes_copy(
+            self._h, blob.ctypes.data, bc_off.ctypes.data, cell_rec_off.ctypes.data, order.ctypes.data, group_off.ctypes.data,
+            cell_group_off.ctypes.data, kept.ctypes.data))
+        raw = blob.tobytes()
+        return dict(barcodes=[raw[int(bc_off[c]):int(bc_off[c + 1])] for c in range(nc)], cell_rec_off=cell_rec_off,
+                    order=order[:m], group_off=group_off, cell_group_off=cell_group_off, kept=kept[:ng], n_unmapped=n_unmapped)
+
     def finish(self):
-        """(indptr, cols, vals, [RunInfo]) of every pushed cell, in ticket order."""
+        """(indptr, cols, vals, [RunInfo]) of every pushed cell, in ticket order (a barcoded session: of every cell it
+        found, in input order)."""
         if not self._h:
             raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
         res = C.c_void_p()
         self._check(self._L.oem_cells_stream_finish(self._h, C.byref(res)))
+        if self._barcoded:
+            try:
+                self._cells = self._take_cells()
+            except BaseException:
+                self._L.oem_cells_result_destroy(res)
+                raise
         nc = C.c_uint32(0)
         self._check(self._L.oem_cells_result_dims(res, C.byref(nc), None))
         dts = (_lib.DiscardTableC * max(int(nc.value), 1))()

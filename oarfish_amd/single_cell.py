@@ -1,0 +1,64 @@
+"""The single-cell driver (src/single_cell.rs:54-290 of COMBINE-lab/oarfish) from the parsed records on.
+
+The reference walks a barcode-collated BAM record by record, cuts a cell where the ``CB`` tag changes
+(single_cell.rs:196-227, alignment_parser.rs:244-299), hands every cell to a worker -- sort by read name, filter,
+coverage model, EM, the entries above 0 (:104-188) -- and writes the matrix with its side files (:259).  Here the
+reader's batches go into a barcoded session (``CellsStream(barcodes=True)``): the cut, the collation, the filter and the
+EM run on the device while the reader goes on, and nothing run-sized is held on the host.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import writers
+from .em import CellsStream
+
+
+@dataclass
+class SingleCellArgs:
+    """The `Args` fields this stage reads (prog_opts.rs): defaults are the reference's."""
+    output: str
+    threads: int = 3
+    max_em_iter: int = 1000
+    convergence_thresh: float = 1e-3
+    model_coverage: Optional[str] = None   # None, "binomial" or "logistic"
+    bin_width: int = 100
+    growth_rate: float = 2.0
+    mode: str = "sort"                     # the reference sorts every cell by read name; "adjacent": name-collated cells
+    device: int = 0
+    group_nnz: int = 0                     # the session's budgets, 0 = the library's defaults
+    group_cells: int = 0
+    max_staged_records: int = 0
+    extra_info: dict = field(default_factory=dict)
+
+
+def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], txp_lens: Sequence[int], batches,
+                                             args: SingleCellArgs):
+    """``get_single_cell_abundances`` for a reader that hands over chunks: ``batches`` is an iterable of ``(records,
+    barcodes, names, secondary)`` in input order (``synth.cut_cell_records``' tuples), barcode-collated and cut at any
+    record positions.  Writes `.count.mtx`, `.features.txt`, `.barcodes.txt` (the session's labels, in cell order) and
+    `.meta_info.json` with ``writers.write_single_cell_output_device`` and returns ``(indptr, cols, vals, infos,
+    cells)``: the session's result and its ``cells()``."""
+    txp_len = np.asarray(txp_lens, dtype=np.uint64)
+    coverage = None
+    if args.model_coverage is not None:
+        coverage = dict(model=args.model_coverage, bin_width=args.bin_width, growth_rate=args.growth_rate, txp_len=txp_len)
+    with CellsStream(len(txp_len), max_iter=args.max_em_iter, conv_thresh=args.convergence_thresh, coverage=coverage,
+                     device=args.device, group_nnz=args.group_nnz, group_cells=args.group_cells,
+                     max_staged_nnz=args.max_staged_records, filters=filters, txp_len=txp_len, barcodes=True,
+                     mode=args.mode) as cs:
+        for records, barcodes, names, secondary in batches:
+            cs.push_batch(records, barcodes, names, secondary)
+        indptr, cols, vals, infos = cs.finish()
+        cells = cs.cells()
+    info = {"output": args.output, "single_cell": True, "em_max_iter": args.max_em_iter,
+            "em_convergence_thresh": args.convergence_thresh, "threads": args.threads,
+            "filter_options": {"model_coverage": args.model_coverage is not None}}
+    info.update(args.extra_info)
+    labels = [b.decode("latin-1") for b in cells["barcodes"]]
+    writers.write_single_cell_output_device(args.output, info, txps_name, labels, len(labels), indptr, cols, vals,
+                                            device=args.device)
+    return indptr, cols, vals, infos, cells

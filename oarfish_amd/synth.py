@@ -722,6 +722,59 @@ def interleave_cells(records, names, secondary, cell_rec_off, barcodes, seed: in
             None if secondary is None else np.asarray(secondary)[perm], gather_names((bc_blob, bc_off), cell_of), perm)
 
 
+def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, unmapped_every: int = 0):
+    """``shuffle_cell_records``' barcode-collated input cut into batches for a barcoded session
+    (``CellsStream(barcodes=True)``), every record with its cell's barcode.  ``barcodes``: one per cell
+    (``make_barcodes``; a label may recur).  ``unmapped_every=k > 0`` first sprinkles in extra unmapped records, one
+    in front of the records 0, k, 2k, ... of the input, each with an empty name and an empty barcode.  ``cuts`` are record
+    positions of the stream that results (the sprinkled records counted), in any order and with repeats (a repeat gives
+    an empty batch); 0 and the stream's length are implied.  A cut may fall inside a cell and inside a read.  Returns a
+    list of ``(records, barcodes, names, secondary)``, ``barcodes`` and ``names`` as ``(blob, offsets)`` pairs with the
+    offsets of each batch from 0.  A pure function of its arguments."""
+    from .builder import REC_UNMAPPED
+    from .em import gather_names
+    records = np.asarray(records)
+    blob, off = np.asarray(names[0], dtype=np.uint8), np.asarray(names[1], dtype=np.int64)
+    cell_rec_off = np.asarray(cell_rec_off, dtype=np.int64)
+    n, n_cells = len(records), len(cell_rec_off) - 1
+    if len(off) != n + 1 or int(cell_rec_off[-1]) != n or len(barcodes) != n_cells:
+        raise ValueError("names need one entry per record, cell_rec_off must end at len(records), barcodes need one per cell")
+    secondary = np.zeros(n, dtype=np.uint8) if secondary is None else np.asarray(secondary, dtype=np.uint8)
+    if len(secondary) != n:
+        raise ValueError("secondary must have one entry per record")
+    enc = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+    cell_off = np.zeros(n_cells + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in enc], out=cell_off[1:])
+    cell_of = np.repeat(np.arange(n_cells), np.diff(cell_rec_off))
+    bc_blob, bc_off = gather_names((np.frombuffer(b"".join(enc), dtype=np.uint8), cell_off), cell_of)
+    bc_off = np.asarray(bc_off, dtype=np.int64)
+    if unmapped_every > 0 and n:   # record i of the input goes to position i + i // k + 1
+        pos = np.arange(n) + np.arange(n) // unmapped_every + 1
+        total = int(pos[-1]) + 1
+        stream = np.zeros(total, dtype=records.dtype)
+        stream["flags"] = REC_UNMAPPED
+        stream[pos] = records
+        sec = np.zeros(total, dtype=np.uint8)
+        sec[pos] = secondary
+        name_len, bc_len = np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.int64)
+        name_len[pos], bc_len[pos] = np.diff(off), np.diff(bc_off)
+        off, bc_off = np.zeros(total + 1, dtype=np.int64), np.zeros(total + 1, dtype=np.int64)
+        np.cumsum(name_len, out=off[1:])
+        np.cumsum(bc_len, out=bc_off[1:])
+        records, secondary, n = stream, sec, total
+    edges = [0] + sorted(int(c) for c in cuts) + [n]
+    if edges[1] < 0 or edges[-2] > n:
+        raise ValueError("a cut lies outside the records")
+    out = []
+    for a, b in zip(edges[:-1], edges[1:]):
+        o, bo = off[a:b + 1], bc_off[a:b + 1]
+        out.append((np.ascontiguousarray(records[a:b]),
+                    (np.ascontiguousarray(bc_blob[int(bo[0]):int(bo[-1])]), np.ascontiguousarray(bo - bo[0], dtype=np.uint64)),
+                    (np.ascontiguousarray(blob[int(o[0]):int(o[-1])]), np.ascontiguousarray(o - o[0], dtype=np.uint64)),
+                    np.ascontiguousarray(secondary[a:b])))
+    return out
+
+
 @dataclass
 class SyntheticProjectedRecords:
     filters: dict                # the fields of oem_filters the records were made for

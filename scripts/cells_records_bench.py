@@ -23,6 +23,16 @@ it (synth.shuffle_cell_records: every cell's records permuted, each with its rea
 
 A warm-up on the first cells, then --runs repeats (default five for this leg) of (a), (b), (c) in turn; best and
 spread, (a)/(b), (a) - (c), and the peak of the device memory in use during (a), sampled from another thread.
+
+--barcodes-stream is the leg of the barcoded session (profiles/cells_barcodes_stream_bench.json): the same shuffled, named
+slice with a 10x barcode per record, alternated in one process, --runs repeats (five), best to worst:
+
+  (a) the session (CellsStream(barcodes=True), oem_cells_stream_push_barcodes) from one pushing thread, at two batch
+      sizes (--batch-records), from the first push to the end of finish;
+  (b) the one call on the concatenation (em_cells_records_sparse(..., names=, collate="device"));
+  (c) today's session path: CellsStream.push_records(records, names=) per cell -- collate_names, the NumPy gather, the push.
+
+With the peak device memory of (a) and (b) and the session's groups_before_finish.
 """
 import argparse
 import ctypes as C
@@ -226,6 +236,87 @@ def barcodes_leg(args, cr, res, save):
         del rec, names, sec, bc, rec0, names0, sec0
 
 
+def barcodes_stream_leg(args, cr, res, save):
+    """The --barcodes-stream leg (see the module docstring); fills res[style] for every name style."""
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    for style in args.styles:
+        rec, (blob, off), sec, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        m = len(rec)
+        cell_bc = np.frombuffer(b"".join(synth.make_barcodes(n, "10x")), dtype=np.uint8).reshape(n, 18)
+        bc_blob = np.repeat(cell_bc, np.diff(cro.astype(np.int64)), axis=0).reshape(-1)   # 18 bytes per record
+        r = res[style] = dict(name_bytes=int(blob.nbytes), record_bytes=int(rec.nbytes), barcode_bytes=int(bc_blob.nbytes))
+
+        def session(batch, upto=m):
+            info = {}
+
+            def go():
+                with oarfish_amd.CellsStream(len(tl), filters=f, txp_len=tl, barcodes=True) as cs:
+                    for a in range(0, upto, batch):
+                        b = min(a + batch, upto)
+                        cs.push_batch(rec[a:b], (bc_blob[18 * a:18 * b], np.arange(b - a + 1, dtype=np.uint64) * 18),
+                                      (blob[int(off[a]):int(off[b])], off[a:b + 1] - off[a]), sec[a:b])
+                    out = cs.finish()
+                    info.update(cs.info(), n_cells=len(cs.cells()["barcodes"]))
+                return out
+            dt, out = clock(go)
+            return dt, out, info
+
+        def one_call(nc=n):
+            k = int(cro[nc])
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:k], None, cro[:nc + 1], names=(blob[:int(off[k])], off[:k + 1]),
+                                                       secondary=sec[:k], collate="device")
+
+        def per_cell(nc=n):
+            with oarfish_amd.CellsStream(len(tl), filters=f, txp_len=tl) as cs:
+                for c in range(nc):
+                    a, b = int(cro[c]), int(cro[c + 1])
+                    cs.push_records(rec[a:b], names=(blob[int(off[a]):int(off[b])], off[a:b + 1] - off[a]), secondary=sec[a:b])
+                return cs.finish()
+
+        nw = min(args.warm_cells, n)
+        session(args.batch_records[0], int(cro[nw]))
+        one_call(nw)
+        per_cell(nw)
+        runs_a, runs_b, runs_c = {b: [] for b in args.batch_records}, [], []
+        for k in range(args.runs):
+            for batch in args.batch_records:
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        dt, got_a, info = session(batch)
+                    r[f"session_{batch}_peak_device_bytes"] = int(pk.peak)
+                    r[f"session_{batch}_info"] = info
+                else:
+                    dt, got_a, info = session(batch)
+                runs_a[batch].append(dt)
+                r[f"session_{batch}_records_per_batch"] = spread(runs_a[batch])
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_b = clock(one_call)
+                r["one_call_peak_device_bytes"] = int(pk.peak)
+                assert info["n_cells"] == n and np.array_equal(got_a[0], got_b[0]) and np.array_equal(got_a[1], got_b[1])
+                ulps = np.abs(got_a[2].view(np.int32).astype(np.int64) - got_b[2].view(np.int32).astype(np.int64))
+                r["max_f32_ulps_session_to_one_call"] = int(ulps.max(initial=0))
+            else:
+                dt, got_b = clock(one_call)
+            runs_b.append(dt)
+            del got_a, got_b
+            runs_c.append(clock(per_cell)[0])
+            r["one_call"], r["push_records_names_per_cell"] = spread(runs_b), spread(runs_c)
+            for batch in args.batch_records:
+                r[f"session_{batch}_over_one_call"] = round(min(runs_a[batch]) / min(runs_b), 3)
+            print(f"[bench] {style} run {k}: (a) " + ", ".join(f"{runs_a[b][-1]:.3f} s at {b}" for b in args.batch_records)
+                  + f", (b) {runs_b[-1]:.3f} s, (c) {runs_c[-1]:.3f} s", flush=True)
+            save()
+        del rec, blob, off, sec, bc_blob
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=625)
@@ -236,13 +327,16 @@ def main():
     ap.add_argument("--models", type=int, nargs="*", default=[-1, 1])
     ap.add_argument("--names", action="store_true", help="the leg from names and records in input order")
     ap.add_argument("--barcodes", action="store_true", help="the leg from records in any order: cells from barcodes")
+    ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
+    ap.add_argument("--batch-records", type=int, nargs="*", default=[1 << 21, 1 << 23], help="--barcodes-stream: records per pushed batch")
     ap.add_argument("--styles", nargs="*", default=["uuid", "illumina"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes else 3
+        args.runs = 5 if args.names or args.barcodes or args.barcodes_stream else 3
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "cells_records_barcodes_bench.json" if args.barcodes else
+        args.out = os.path.join(ROOT, "profiles", "cells_barcodes_stream_bench.json" if args.barcodes_stream else
+                                "cells_records_barcodes_bench.json" if args.barcodes else
                                 "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
     T, n = args.txps, args.cells
     t0 = time.perf_counter()
@@ -305,6 +399,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.barcodes_stream:
+        barcodes_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     if args.barcodes:
         barcodes_leg(args, cr, res, save)
         print(json.dumps(res))
