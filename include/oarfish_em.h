@@ -1094,7 +1094,8 @@ void oem_records_stream_destroy(oem_records_stream *s);
 int oem_records_stream_set_names(oem_records_stream *s, uint64_t sort_check_num);
 /* One batch: records (n_records) with names / name_off as oem_store_create_records_names takes them for the whole
  * input.  There is no `secondary` argument: only OEM_COLLATE_SORT reads it, and a session cannot sort what it has not
- * seen.  Thread-safe; tickets, back-pressure (max_staged_records, counted in records) and the reuse of staging memory
+ * seen (the sorting names form, oem_records_stream_set_sort below, holds the survivors until finish for that).
+ * Thread-safe; tickets, back-pressure (max_staged_records, counted in records) and the reuse of staging memory
  * are oem_records_stream_push's.  Checked on the calling thread before the session is touched: name_off present,
  * starting at 0 and not decreasing; names present when name_off[n_records] > 0; records present when n_records > 0;
  * n_records <= 2^31 - 2.  An argument error (OEM_ERR_ARG) rejects that batch only and uses no ticket.  Records, offsets
@@ -1166,6 +1167,54 @@ int oem_records_stream_push_projected(oem_records_stream *s, const oem_proj_reco
                                       uint64_t n_groups, uint64_t *out_ticket);
 #define OEM_RECORDS_STREAM_INFO_HOST_FINISHED 8u /* a projected session, after finish: alignments whose expf the host
                                                     supplied; 0 on a plain or names session */
+
+/* The SORTING NAMES form of the session: oem_store_create_records_names under OEM_COLLATE_SORT for a caller that never
+ * holds all records or names at once -- a coordinate-sorted or unsorted BAM read batch by batch.  Batches are records,
+ * their read names and (optionally) their secondary flags, in any order and cut at any record positions: the records
+ * of one read may lie in any number of batches, a secondary before its primary.
+ *
+ * The contract.  Let R, names, name_off, secondary be the accepted batches concatenated in ticket order (a batch
+ * pushed without flags counting as flags of 0).  finish_names gives exactly what oem_store_create_records_names(...,
+ * R, names, name_off, secondary, OEM_COLLATE_SORT, sort_check_num = 0, ...) gives for them with the session's filters,
+ * txp_len, bin_width, model and growth_rate and finish's opts, wherever the batches were cut: the store (CSR and
+ * weights bit for bit, for every weight_coding and layout_build), out_group_off, out_kept, the discard table, the row
+ * names and their offsets, every field of oem_parse_info (n_checked = 0), and out_order -- as 64-bit session-global
+ * input indices (oem_records_stream_order_copy), which count all records of all accepted batches in ticket order,
+ * unmapped ones included.  The rule is stated once, in oarfish_amd/csrc/oem_collate.h (ParseBulkSortStream).
+ *
+ * A session cannot sort what it has not seen: nothing is cut or filtered before finish.  The device worker uploads
+ * each batch, drops its unmapped records, checks and densifies the survivors' names and appends the survivors -- 40
+ * bytes of record, the name, one flag byte, 8 bytes of offset and 8 of index each -- to an arena that stays on the
+ * device and grows by doubling (OEM_RECORDS_STREAM_INFO_ARENA_BYTES); finish collates the arena as one batch and goes
+ * on as the one call does.  Device memory is therefore the one call's, not less: what the session saves is the
+ * run-sized host arrays.
+ *
+ * oem_records_stream_set_sort turns a fresh session into a sorting names session.  After a push, after another
+ * oem_records_stream_set_*, after finish, or a second time: OEM_ERR_STATE.  On a sorting names session
+ * oem_records_stream_push, _push_names, _push_projected and _finish return OEM_ERR_STATE; on any other session
+ * oem_records_stream_push_sort and oem_records_stream_order_copy do.  oem_records_stream_finish_names and
+ * oem_records_stream_names_copy serve it as they serve a names session. */
+int oem_records_stream_set_sort(oem_records_stream *s);
+/* One batch: as oem_records_stream_push_names, with `secondary` (n_records flags, or NULL for none) besides.  The
+ * argument checks, made on the calling thread before the session is touched, and staging, tickets and back-pressure
+ * are oem_records_stream_push_names'; a rejected batch uses no ticket.
+ *
+ * Found on the device, sticky as in a names session, the first batch in ticket order that has a fault reporting it: a
+ * surviving record with an empty name or a 0 byte in its name (OEM_ERR_ARG, naming the record's session-global index);
+ * a surviving record's ref_id that is not below n_txps (OEM_ERR_ARG, naming "ticket <ticket>" and the session-global
+ * index); more than 2^31 - 2 surviving records in the session (OEM_ERR_ARG at the batch that crosses: the collation is
+ * one batch); out of device memory (OEM_ERR_OOM).  After a sticky error the arena is released.  Where the host loop
+ * takes the groups (a score beyond +-2^24, or a score_prob_denom without a table) the survivors come down from the
+ * arena once, at finish, and OEM_RECORDS_STREAM_INFO_HOST_BATCHES is 1. */
+int oem_records_stream_push_sort(oem_records_stream *s, const oem_aln_record *records, uint64_t n_records,
+                                 const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+                                 uint64_t *out_ticket);
+/* After a successful oem_records_stream_finish_names on a sorting names session (before, or on another session:
+ * OEM_ERR_STATE): out_order, n_parsed session-global input indices -- the surviving records collated by the name rule,
+ * what oem_store_create_records_names writes to its out_order in 32 bits. */
+int oem_records_stream_order_copy(const oem_records_stream *s, uint64_t *out_order);
+#define OEM_RECORDS_STREAM_INFO_ARENA_BYTES 9u /* a sorting names session: the most device bytes its arena has held
+                                                  (a growing array counted twice while it is copied); 0 otherwise */
 
 /* --------------------------------------------------------------------- */
 /* multi-GPU (row shards + one RCCL all-reduce of the count vector / pass) */

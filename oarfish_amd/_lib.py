@@ -45,6 +45,7 @@ OEM_RECORDS_STREAM_INFO_BLOCKED_US = 5
 OEM_RECORDS_STREAM_INFO_HOST_BATCHES = 6
 OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES = 7
 OEM_RECORDS_STREAM_INFO_HOST_FINISHED = 8
+OEM_RECORDS_STREAM_INFO_ARENA_BYTES = 9
 OEM_INFO_WEIGHT_DICT_ENTRIES = 1
 OEM_INFO_TILES = 2
 OEM_INFO_REMOTE_ALIGNMENTS = 3
@@ -83,7 +84,8 @@ ABI_SYMBOLS = [
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
     "oem_records_stream_destroy", "oem_records_stream_set_names", "oem_records_stream_push_names",
     "oem_records_stream_finish_names", "oem_records_stream_names_copy", "oem_records_stream_set_projected",
-    "oem_records_stream_push_projected",
+    "oem_records_stream_push_projected", "oem_records_stream_set_sort", "oem_records_stream_push_sort",
+    "oem_records_stream_order_copy",
     "oem_comm_unique_id", "oem_comm_create", "oem_comm_destroy", "oem_comm_p2p_export", "oem_comm_p2p_connect",
     "oem_comm_set_option", "oem_comm_info", "oem_store_attach_comm",
     "oem_time_m_step", "oem_time_em_iters", "oem_time_bootstrap_passes", "oem_time_allreduce",
@@ -277,6 +279,9 @@ def _load(path: str) -> C.CDLL:
     L.oem_records_stream_names_copy.argtypes = [vp, vp, vp, vp, vp]
     L.oem_records_stream_set_projected.argtypes = [vp, vp]
     L.oem_records_stream_push_projected.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.oem_records_stream_set_sort.argtypes = [vp]
+    L.oem_records_stream_push_sort.argtypes = [vp, vp, u64, vp, vp, vp, C.POINTER(u64)]
+    L.oem_records_stream_order_copy.argtypes = [vp, vp]
     L.oem_comm_unique_id.argtypes = [vp]
     L.oem_comm_create.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
     L.oem_comm_destroy.argtypes = [vp]

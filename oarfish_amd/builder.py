@@ -245,7 +245,8 @@ RECORDS_STREAM_INFO = {"batches": _lib.OEM_RECORDS_STREAM_INFO_BATCHES, "groups"
                        "blocked_us": _lib.OEM_RECORDS_STREAM_INFO_BLOCKED_US,
                        "host_batches": _lib.OEM_RECORDS_STREAM_INFO_HOST_BATCHES,
                        "row_name_bytes": _lib.OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES,
-                       "host_finished": _lib.OEM_RECORDS_STREAM_INFO_HOST_FINISHED}
+                       "host_finished": _lib.OEM_RECORDS_STREAM_INFO_HOST_FINISHED,
+                       "arena_bytes": _lib.OEM_RECORDS_STREAM_INFO_ARENA_BYTES}
 
 
 class RecordsStream:
@@ -259,6 +260,12 @@ class RecordsStream:
     records and their read names in input order, cut at any record positions (a read may straddle pushes), and ``finish``
     returns what ``DeviceStore.from_named_records(mode="adjacent", sort_check_num=...)`` returns for the concatenation.
 
+    ``names=True, mode="sort"`` makes it a sorting names session (``oem_records_stream_set_sort``) for input in ANY
+    order, a coordinate-sorted BAM for one: ``push(records, names=..., secondary=...)``, and ``finish`` returns what
+    ``DeviceStore.from_named_records(secondary=..., mode="sort")`` returns for the concatenation, ``parse.order`` as
+    ``int64`` session-global input indices.  The survivors stay on the device until ``finish``
+    (``info()["arena_bytes"]``: the most the arena held): the session saves the run-sized host arrays, not device memory.
+
     ``projected=True`` makes it a projected session (``oem_records_stream_set_projected``) for genome mode:
     ``push(records, group_off, read_len=...)`` takes batches of whole groups of ``PROJ_RECORD`` with one read length per
     group, and ``finish`` returns what ``DeviceStore.from_projected_records(beta=..., prob_source=...)`` returns for the
@@ -267,9 +274,13 @@ class RecordsStream:
 
     def __init__(self, filters, txp_len, coverage: Optional[str] = None, bin_width: int = 100, growth_rate: float = 2.0,
                  device: int = 0, max_staged_records: int = 0, names: bool = False, sort_check_num: int = 100_000,
-                 projected: bool = False, beta: float = 10.0, prob_source="similarity"):
+                 projected: bool = False, beta: float = 10.0, prob_source="similarity", mode: str = "adjacent"):
         if names and projected:
             raise ValueError("a session takes names=True or projected=True, not both")
+        if mode not in ("adjacent", "sort"):
+            raise ValueError(f"mode must be 'adjacent' or 'sort', not {mode!r}")
+        if mode == "sort" and not names:
+            raise ValueError('mode="sort" belongs to a names session (names=True)')
         po = proj_opts_c(beta, prob_source) if projected else None
         self._lib = _lib.lib()
         self.filters = filters_c(filters)
@@ -282,7 +293,10 @@ class RecordsStream:
         self._check(self._lib.oem_records_stream_create(C.byref(o), C.addressof(self.filters), self.txp_len.ctypes.data,
                                                         C.byref(self._h)))
         self.names = bool(names)
-        if self.names:
+        self.sorting = mode == "sort"
+        if self.sorting:
+            self._check(self._lib.oem_records_stream_set_sort(self._h))
+        elif self.names:
             self._check(self._lib.oem_records_stream_set_names(self._h, int(sort_check_num)))
         self.projected = bool(projected)
         if self.projected:
@@ -313,12 +327,15 @@ class RecordsStream:
             raise RuntimeError("RecordsStream is closed")
         return self._h
 
-    def push(self, records, group_off=None, names=None, read_len=None) -> int:
+    def push(self, records, group_off=None, names=None, read_len=None, secondary=None) -> int:
         """One batch (``records`` / ``group_off`` as in ``StoreBuilder.add_groups``); returns its ticket.  Thread-safe;
         blocks while the staging budget is full.  A names session takes ``names=`` instead of ``group_off``: one name
         per record, a sequence of ``str`` / ``bytes`` or a ``(blob, offsets)`` pair, packed as ``from_named_records``
         packs it.  A projected session takes ``read_len=`` besides ``group_off``, as
-        ``StoreBuilder.add_projected_groups`` does."""
+        ``StoreBuilder.add_projected_groups`` does.  A sorting names session takes ``secondary=`` besides ``names=``:
+        one flag per record, or None for a batch without secondary alignments."""
+        if secondary is not None and not self.sorting:
+            raise ValueError('secondary= belongs to a sorting names session (names=True, mode="sort")')
         if read_len is not None and not self.projected:
             raise ValueError("read_len= belongs to a projected session (projected=True)")
         if self.projected:
@@ -346,6 +363,17 @@ class RecordsStream:
             if n and not len(blob):
                 blob = np.zeros(1, dtype=np.uint8)   # (every name is empty: the session says so)
             ticket = C.c_uint64(0)
+            if self.sorting:
+                sec = None
+                if secondary is not None:
+                    sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
+                    if len(sec) != n:
+                        raise ValueError("secondary must have one entry per record")
+                self._check(self._lib.oem_records_stream_push_sort(self.handle, records.ctypes.data if n else None, n,
+                                                                   blob.ctypes.data if n else None, off.ctypes.data,
+                                                                   None if sec is None or not n else sec.ctypes.data,
+                                                                   C.byref(ticket)))
+                return int(ticket.value)
             self._check(self._lib.oem_records_stream_push_names(self.handle, records.ctypes.data if n else None, n,
                                                                 blob.ctypes.data if n else None, off.ctypes.data,
                                                                 C.byref(ticket)))
@@ -365,6 +393,8 @@ class RecordsStream:
                 continue
             if name == "host_finished" and not self.projected:   # (a projected session's key)
                 continue
+            if name == "arena_bytes" and not self.sorting:   # (a sorting names session's key)
+                continue
             v = C.c_uint64(0)
             self._check(self._lib.oem_records_stream_info(self.handle, key, C.byref(v)))
             out[name] = int(v.value)
@@ -373,7 +403,8 @@ class RecordsStream:
     def finish(self, reorder_rows: int = 0, window_cap: int = 0, layout_build: int = 0, weight_coding: int = 0):
         """``(DeviceStore, kept, discard_table)`` as ``DeviceStore.from_records`` returns them for the accepted batches
         concatenated in ticket order.  A names session returns ``(DeviceStore, kept, discard_table, parse)`` as
-        ``DeviceStore.from_named_records`` does, ``parse.order`` being None."""
+        ``DeviceStore.from_named_records`` does, ``parse.order`` being None -- or, in a sorting names session, the
+        collated survivors' session-global input indices as ``int64``."""
         from .types import DeviceStore
         o = store_opts(reorder_rows, window_cap, layout_build, weight_coding)
         if self.names:
@@ -389,7 +420,11 @@ class RecordsStream:
             row_off = np.zeros(pi.n_reads + 1, dtype=np.uint64)
             self._check(self._lib.oem_records_stream_names_copy(self.handle, group_off.ctypes.data, kept.ctypes.data,
                                                                 row_blob.ctypes.data, row_off.ctypes.data))
-            parse = SimpleNamespace(order=None, group_off=group_off, read_names=(row_blob[:int(row_off[-1])].copy(), row_off),
+            order = None
+            if self.sorting:
+                order = np.zeros(pi.n_parsed, dtype=np.int64)
+                self._check(self._lib.oem_records_stream_order_copy(self.handle, order.ctypes.data if pi.n_parsed else None))
+            parse = SimpleNamespace(order=order, group_off=group_off, read_names=(row_blob[:int(row_off[-1])].copy(), row_off),
                                     n_unmapped=int(pi.n_unmapped), n_parsed=int(pi.n_parsed), n_groups=int(pi.n_groups),
                                     n_reads=int(pi.n_reads), unique_alignments=int(pi.unique_alignments),
                                     n_checked=int(pi.n_checked))

@@ -143,28 +143,42 @@ def quantify_bulk_alignments_from_records(filters, txps_name: Sequence[str], txp
 def quantify_bulk_alignments_from_record_batches(filters, txps_name: Sequence[str], txp_lens: Sequence[int], batches,
                                                  args: BulkArgs, sort_check_num: int = 100_000,
                                                  coverage: Optional[str] = None, bin_width: int = 100,
-                                                 growth_rate: float = 2.0, max_staged_records: int = 0) -> np.ndarray:
+                                                 growth_rate: float = 2.0, max_staged_records: int = 0,
+                                                 mode: str = "adjacent") -> np.ndarray:
     """``quantify_bulk_alignments_from_records`` for a reader that hands over chunks: ``batches`` is an iterable of
     ``(records, names)`` in input order, cut at any record positions (a read may straddle batches).  They go through a
     names session (``RecordsStream(names=True)``: the reference's parser, ``mode="adjacent"``); the files are those of
     ``quantify_bulk_alignments_from_records`` on the concatenation.  The host `.prob` writer (``prob_on_device`` False)
-    keeps the mapped records it has seen for the rows' transcript ids; ``prob_on_device`` needs none of that."""
-    from .builder import REC_UNMAPPED, RecordsStream
+    keeps the mapped records it has seen for the rows' transcript ids; ``prob_on_device`` needs none of that.
+
+    ``mode="sort"`` takes ``(records, names[, secondary])`` batches in ANY order -- a coordinate-sorted or unsorted
+    input -- through a sorting names session (``RecordsStream(names=True, mode="sort")``); the files are those of
+    ``quantify_bulk_alignments_from_records(mode="sort")`` on the concatenation.  ``sort_check_num`` is not read then.
+    The host `.prob` writer keeps every record it has seen, ``parse.order`` indexing all of them."""
+    from .builder import ALN_RECORD, REC_UNMAPPED, RecordsStream
+    if mode not in ("adjacent", "sort"):
+        raise ValueError(f"mode must be 'adjacent' or 'sort', not {mode!r}")
+    sorting = mode == "sort"
     txp_len = np.asarray(txp_lens, dtype=np.uint64)
     keep_rows = args.write_assignment_probs and not args.prob_on_device
     mapped = []
     with RecordsStream(filters, txp_len, coverage=coverage, bin_width=bin_width, growth_rate=growth_rate, device=args.device,
-                       max_staged_records=max_staged_records, names=True, sort_check_num=sort_check_num) as rs:
-        for records, names in batches:
-            records = np.asarray(records)
-            rs.push(records, names=names)
+                       max_staged_records=max_staged_records, names=True, sort_check_num=sort_check_num, mode=mode) as rs:
+        for batch in batches:
+            if len(batch) != 2 and not (sorting and len(batch) == 3):
+                raise ValueError("a batch is (records, names)" + (" or (records, names, secondary)" if sorting else ""))
+            records = np.asarray(batch[0])
+            if sorting:
+                rs.push(records, names=batch[1], secondary=batch[2] if len(batch) == 3 else None)
+            else:
+                rs.push(records, names=batch[1])
             if keep_rows:
-                mapped.append(records[(records["flags"] & REC_UNMAPPED) == 0])
+                mapped.append(records if sorting else records[(records["flags"] & REC_UNMAPPED) == 0])
         dev, _kept, _discard, parse = rs.finish()
 
     def host_rows():
-        from .builder import ALN_RECORD
-        return (np.concatenate(mapped) if mapped else np.zeros(0, dtype=ALN_RECORD)), parse.group_off
+        seen = np.concatenate(mapped) if mapped else np.zeros(0, dtype=ALN_RECORD)
+        return (seen[parse.order] if sorting else seen), parse.group_off
 
     return _write_from_resident(dev, parse, host_rows, filters, txp_len, txps_name, txp_lens, args, coverage)
 

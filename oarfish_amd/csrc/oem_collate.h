@@ -326,6 +326,70 @@ struct ParseBulkStream {
     void finish() { close(); }
 };
 
+// The streamed form of parse_bulk_host for kCollateSort (oem_records_stream_push_sort): the same input cut into batches
+// at ANY record positions, in any order of the records.  A session cannot sort what it has not seen, so the rule only
+// accumulates until finish:
+//   - a batch's survivors are its records without OEM_REC_UNMAPPED, in input order; their names (dense, the offsets
+//     rebased), their secondary flags (0 for a batch pushed without flags) and their session-global input indices
+//     (64-bit: all records of all pushed batches in push order, unmapped ones included) are appended to what is held;
+//   - the first surviving record with a bad name (collate_first_bad_name's conditions) is recorded by its
+//     session-global index; unmapped records' names are never read;
+//   - finish applies parse_bulk_host's sort rule to the held survivors as one cell -- name bytes, primary before
+//     secondary, index; a survivor's index among the survivors is ascending in its global index, so rule 3 orders by
+//     either -- and cuts the groups where the name changes.  order holds session-global indices.
+// The result does not depend on where the batches were cut.
+struct ParseBulkSortStream {
+    uint64_t n_records = 0, n_unmapped = 0; // of all batches pushed
+    std::vector<uint8_t> names;             // the survivors', dense
+    std::vector<uint64_t> name_off{0}, global;
+    std::vector<uint8_t> secondary;
+    uint64_t bad_record = kCollateNoRecord; // session-global; zero_byte tells which
+    bool zero_byte = false;
+    std::vector<uint64_t> order, group_off; // after finish: n_parsed global indices, n_groups + 1 positions
+
+    template <typename Rec>
+    void push(const Rec *records, uint64_t n, const uint8_t *nm, const uint64_t *nm_off, const uint8_t *sec)
+    {
+        for (uint64_t i = 0; i < n; ++i) {
+            if (records[i].flags & kRecUnmapped) {
+                ++n_unmapped;
+                continue;
+            }
+            const uint64_t len = nm_off[i + 1] - nm_off[i];
+            const bool z = len && memchr(nm + nm_off[i], 0, len);
+            if ((!len || z) && bad_record == kCollateNoRecord) {
+                bad_record = n_records + i;
+                zero_byte = z;
+            }
+            if (len) names.insert(names.end(), nm + nm_off[i], nm + nm_off[i] + len);
+            name_off.push_back(names.size());
+            secondary.push_back(sec && sec[i] ? 1 : 0);
+            global.push_back(n_records + i);
+        }
+        n_records += n;
+    }
+    uint64_t n_parsed() const { return global.size(); }
+    void finish()
+    {
+        const uint64_t m = global.size();
+        order.clear();
+        group_off.assign(1, 0);
+        if (bad_record != kCollateNoRecord || m == 0) return;
+        std::vector<uint32_t> pos(m);
+        for (uint64_t k = 0; k < m; ++k) pos[k] = (uint32_t)k;
+        std::sort(pos.begin(), pos.end(), [&](uint32_t i, uint32_t j) { return collate_before(names.data(), name_off.data(), secondary.data(), i, j); });
+        group_off.clear();
+        for (uint64_t p = 0; p < m; ++p) {
+            const uint32_t i = pos[p], j = p ? pos[p - 1] : 0;
+            if (p == 0 || collate_name_cmp(names.data() + name_off[i], name_off[i + 1] - name_off[i], names.data() + name_off[j],
+                                           name_off[j + 1] - name_off[j]) != 0)
+                group_off.push_back(p);
+            order.push_back(global[i]);
+        }
+        group_off.push_back(m);
+    }
+};
+
 // Cells from a barcode-collated stream (ParseCellsStream below, oem_cells_stream_push_barcodes): single_cell.rs:196-227
 // with alignment_parser.rs:244-299 -- the reference's single-cell driver walks a barcode-collated BAM record by record,
 // cuts a cell where the CB tag changes and hands the cell to a worker that sorts it by read name.  The session's input

@@ -25,6 +25,9 @@
 //              gather writes the rows' names
 //   store      filter_result_to_store, with the coverage model first when there is one
 //
+// Everything from `collate` on is parse_tail (oem_parse_device.h): the sorting names session's finish
+// (oem_records_stream.hip) runs it on its arena of survivors, as this call runs it on its uploaded input.
+//
 // The host loop takes the groups when the filter would (no gap table for score_prob_denom, a score beyond +-2^24): order
 // and group_off come down, the records are gathered on the host and go through add_groups_host; the result is the same.
 //
@@ -271,6 +274,237 @@ int parse_row_index(const uint32_t *d_n_kept, uint64_t n, uint64_t *d_row_idx)
     return exclusive_scan(in, d_row_idx, n);
 }
 
+namespace {
+
+// out[k] = global[order[k]]: the collated order as 64-bit session-global input indices.  order holds resident indices
+// below n; an index that is not (there is none) reads nothing and writes kNoRecord.
+__global__ __launch_bounds__(kPT) void k_order_global(uint64_t m, uint64_t n, const uint32_t *__restrict__ order,
+                                                       const uint64_t *__restrict__ global, uint64_t *__restrict__ out)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kPT + threadIdx.x;
+    if (k >= m) return;
+    const uint32_t i = order[k];
+    out[k] = i < n ? global[i] : kNoRecord;
+}
+
+int tail_bad_ref(const ParseTail &t, uint64_t resident, uint32_t ref_id)
+{
+    uint64_t at = resident;
+    if (t.d_global) OEM_HIP(hipMemcpy(&at, t.d_global + resident, sizeof at, hipMemcpyDeviceToHost));
+    return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", t.who, (unsigned long long)at, ref_id);
+}
+
+} // namespace
+
+int parse_tail(ParseTail &t)
+{
+    const char *who = t.who;
+    const uint64_t m = t.m;
+    const bool sorting = t.mode == kCollateSort, dense = t.dense;
+    const uint32_t n_txps = t.n_txps;
+    const int model = t.model;
+    oem_parse_info &pi = *t.pi;
+    double none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double *last = t.last ? t.last : none;
+    DevBuf<oem_aln_record> d_sorted;
+
+    // -- collate: the survivors as one cell -----------------------------------------------------------------------------
+    const uint64_t one_cell[2] = {0, m};
+    CollateResident cr;
+    {
+        CollateInput in;
+        in.who = who;
+        in.cell_rec_off = one_cell;
+        in.mode = t.mode;
+        in.chunk_bytes = collate_chunk_bytes();
+        in.d_names = dense ? t.d_dense.p : t.d_names.p;
+        in.d_name_off = dense ? t.d_dense_off.p : t.d_name_off.p;
+        in.d_n_bytes = t.dense_bytes;
+        in.d_secondary = dense ? t.d_dense_sec.p : t.d_sec.p;
+        double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        OEM_TRY(collate_resident(in, 0, 1, 0, 0, 0, info, &cr));
+    }
+    t.d_dense.reset();
+    t.d_dense_sec.reset();
+    t.d_dense_off.reset();
+    t.d_sec.reset();
+    if (dense) OEM_TRY(order_compose(m, t.d_order_parse.p, cr.order.p));
+    t.d_order_parse.reset();
+    const uint64_t ng = cr.n_groups;
+    pi.n_groups = ng;
+
+    // -- the collation check --------------------------------------------------------------------------------------------
+    if (!sorting && t.sort_check_num) {
+        const uint64_t nchk = std::min<uint64_t>(t.sort_check_num, ng);
+        pi.n_checked = nchk;
+        last[2] = (double)nchk;
+        if (nchk > 1) {
+            DevBuf<uint32_t> d_heads;
+            DevBuf<uint64_t> d_chk_off;
+            DevBuf<uint8_t> d_chk;
+            uint64_t chk_bytes = 0;
+            OEM_TRY(dev_alloc(&d_heads.p, nchk, nullptr));
+            hipLaunchKernelGGL(k_parse_heads, grid_for(nchk), dim3(kPT), 0, nullptr, nchk, (const uint64_t *)cr.group_off.p,
+                               (const uint32_t *)cr.order.p, d_heads.p);
+            OEM_HIP(hipGetLastError());
+            OEM_TRY(gather_input_names(d_heads.p, nchk, t.d_names.p, t.d_name_off.p, &d_chk_off, &d_chk, &chk_bytes));
+            uint64_t found = ~0ull;
+            OEM_TRY(parse_check_repeat(who, d_chk.p, d_chk_off.p, chk_bytes, nchk, &found));
+            if (found != ~0ull) {
+                const uint64_t g = found >> 32, earlier = found & 0xffffffffull;
+                uint32_t rec_g = 0, rec_e = 0;
+                OEM_HIP(hipMemcpy(&rec_g, d_heads.p + g, sizeof rec_g, hipMemcpyDeviceToHost));
+                OEM_HIP(hipMemcpy(&rec_e, d_heads.p + earlier, sizeof rec_e, hipMemcpyDeviceToHost));
+                return parse_not_collated(who, g, rec_g, rec_e);
+            }
+        }
+    }
+
+    if (t.on_groups) t.on_groups(ng);
+    if (t.out_order) OEM_HIP(hipMemcpy(t.out_order, cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    if (t.out_order64 && t.d_global) {
+        DevBuf<uint64_t> d_order64;
+        OEM_TRY(dev_alloc(&d_order64.p, m, nullptr));
+        hipLaunchKernelGGL(k_order_global, grid_for(m), dim3(kPT), 0, nullptr, m, m, (const uint32_t *)cr.order.p, t.d_global, d_order64.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(t.out_order64, d_order64.p, sizeof(uint64_t) * m, hipMemcpyDeviceToHost));
+    }
+    if (t.out_group_off) OEM_HIP(hipMemcpy(t.out_group_off, cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
+
+    // -- gather and filter ----------------------------------------------------------------------------------------------
+    FilterResult r;
+    FilterCells fc;
+    bool host = t.host_only;
+    if (!host) {
+        const oem_aln_record *d_recs = t.d_in.p;
+        if (sorting || dense) {
+            OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
+            OEM_TRY(records_gather(m, cr.order.p, t.d_in.p, d_sorted.p));
+            t.d_in.reset(); // the records are held twice only for the length of the gather
+            d_recs = d_sorted.p;
+            last[0] = 1;
+        }
+        fc.n_cells = 1;
+        OEM_TRY(filter_device_resident(who, *t.filters, t.txp_len, n_txps, *t.tab, d_recs, (const unsigned long long *)cr.group_off.p, ng,
+                                       (const unsigned long long *)cr.cell_group_off.p, model >= 0, &r, &fc));
+        if (r.bad_ref_record != kNoRecord) { // a collated position: the caller knows its records by their input index
+            uint32_t at = 0;
+            OEM_HIP(hipMemcpy(&at, cr.order.p + r.bad_ref_record, sizeof at, hipMemcpyDeviceToHost));
+            oem_aln_record rec;
+            if (t.h_records) rec = t.h_records[at];
+            else OEM_HIP(hipMemcpy(&rec, d_recs + r.bad_ref_record, sizeof rec, hipMemcpyDeviceToHost));
+            return tail_bad_ref(t, at, rec.ref_id);
+        }
+        host = r.host_rerun;
+    }
+
+    if (host) { // the host loop: order and group_off come down, the host gathers the records
+        last[3] = 1;
+        std::vector<uint32_t> order(m), kept(ng);
+        std::vector<uint64_t> goff(ng + 1);
+        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(goff.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
+        std::vector<oem_aln_record> sorted(m);
+        if (t.h_records) {
+            for (uint64_t k = 0; k < m; ++k) sorted[k] = t.h_records[order[k]];
+        } else { // no host copy of the input: the survivors come down once, collated on the device
+            if (!d_sorted.p) {
+                OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
+                OEM_TRY(records_gather(m, cr.order.p, t.d_in.p, d_sorted.p));
+            }
+            OEM_HIP(hipMemcpy(sorted.data(), d_sorted.p, sizeof(oem_aln_record) * m, hipMemcpyDeviceToHost));
+        }
+        t.d_in.reset();
+        d_sorted.reset();
+        cr.order.reset();
+        cr.group_off.reset();
+        cr.cell_group_off.reset();
+        if (t.h_names) {
+            t.d_names.reset();
+            t.d_name_off.reset();
+        }
+        for (uint64_t k = 0; k < m; ++k)
+            if (sorted[k].ref_id >= n_txps) return tail_bad_ref(t, order[k], sorted[k].ref_id);
+        oem_builder hb;
+        hb.f = *t.filters;
+        hb.txp_len.assign(t.txp_len, t.txp_len + n_txps);
+        OEM_TRY(add_groups_host(&hb, sorted.data(), goff.data(), ng, kept.data(), who));
+        if (hb.tid.size() >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a resident store needs fewer than 2^32 alignments", who);
+        pi.n_reads = hb.row_ptr.size() - 1;
+        for (uint64_t g = 0; g < ng; ++g)
+            if (kept[g] == 1) ++pi.unique_alignments;
+        if (t.want_rows && t.h_names) {
+            uint64_t row_bytes = 0, row = 0;
+            t.out_row_name_off[0] = 0;
+            for (uint64_t g = 0; g < ng; ++g) {
+                if (!kept[g]) continue;
+                const uint32_t i = order[goff[g]];
+                std::memcpy(t.out_row_names + row_bytes, t.h_names + t.h_name_off[i], t.h_name_off[i + 1] - t.h_name_off[i]);
+                row_bytes += t.h_name_off[i + 1] - t.h_name_off[i];
+                t.out_row_name_off[++row] = row_bytes;
+            }
+        } else if (t.want_rows) { // the rows' heads go up, the resident names are gathered as the device path gathers them
+            std::vector<uint32_t> heads;
+            for (uint64_t g = 0; g < ng; ++g)
+                if (kept[g]) heads.push_back(order[goff[g]]);
+            const uint64_t n_rows = heads.size();
+            DevBuf<uint32_t> d_heads;
+            DevBuf<uint64_t> d_row_off;
+            DevBuf<uint8_t> d_rows;
+            uint64_t row_bytes = 0;
+            if (n_rows) {
+                OEM_TRY(dev_alloc(&d_heads.p, n_rows, nullptr));
+                OEM_HIP(hipMemcpy(d_heads.p, heads.data(), sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice));
+                OEM_TRY(gather_input_names(d_heads.p, n_rows, t.d_names.p, t.d_name_off.p, &d_row_off, &d_rows, &row_bytes));
+            }
+            if (t.on_rows) t.on_rows(n_rows, row_bytes);
+            t.out_row_name_off[0] = 0;
+            if (n_rows) OEM_HIP(hipMemcpy(t.out_row_name_off, d_row_off.p, sizeof(uint64_t) * (n_rows + 1), hipMemcpyDeviceToHost));
+            if (row_bytes) OEM_HIP(hipMemcpy(t.out_row_names, d_rows.p, row_bytes, hipMemcpyDeviceToHost));
+        }
+        t.d_names.reset();
+        t.d_name_off.reset();
+        if (t.out_kept) std::memcpy(t.out_kept, kept.data(), sizeof(uint32_t) * ng);
+        if (t.out_discard) *t.out_discard = hb.dt;
+        if (model < 0) OEM_TRY(oem_builder_store_create(&hb, nullptr, t.device, t.opts, t.out));
+        else OEM_TRY(oem_builder_store_create_coverage(&hb, t.bin_width, model, t.growth_rate, t.device, t.opts, nullptr, t.out));
+        return OEM_OK;
+    }
+    t.d_in.reset();
+    d_sorted.reset();
+
+    // -- unique_alignments and the row names, before the store takes the arrays -----------------------------------------
+    pi.n_reads = r.n_rows;
+    OEM_TRY(parse_count_unique(ng, r.n_kept.p, &pi.unique_alignments));
+    if (t.want_rows) {
+        DevBuf<uint64_t> d_row_idx, d_row_off;
+        DevBuf<uint32_t> d_heads;
+        DevBuf<uint8_t> d_rows;
+        uint64_t row_bytes = 0;
+        if (r.n_rows) {
+            OEM_TRY(dev_alloc(&d_row_idx.p, ng + 1, nullptr));
+            OEM_TRY(dev_alloc(&d_heads.p, r.n_rows, nullptr));
+            OEM_TRY(parse_row_index(r.n_kept.p, ng + 1, d_row_idx.p)); // (n_kept has n_groups + 1 entries, the last one 0)
+            hipLaunchKernelGGL(k_parse_row_heads, grid_for(ng), dim3(kPT), 0, nullptr, ng, (const uint32_t *)r.n_kept.p,
+                               (const uint64_t *)d_row_idx.p, (const uint64_t *)cr.group_off.p, (const uint32_t *)cr.order.p, d_heads.p);
+            OEM_HIP(hipGetLastError());
+            d_row_idx.reset();
+            OEM_TRY(gather_input_names(d_heads.p, r.n_rows, t.d_names.p, t.d_name_off.p, &d_row_off, &d_rows, &row_bytes));
+        }
+        if (t.on_rows) t.on_rows(r.n_rows, row_bytes);
+        t.out_row_name_off[0] = 0;
+        if (r.n_rows) OEM_HIP(hipMemcpy(t.out_row_name_off, d_row_off.p, sizeof(uint64_t) * (r.n_rows + 1), hipMemcpyDeviceToHost));
+        if (row_bytes) OEM_HIP(hipMemcpy(t.out_row_names, d_rows.p, row_bytes, hipMemcpyDeviceToHost));
+    }
+    cr.order.reset();
+    cr.group_off.reset();
+    cr.cell_group_off.reset();
+    t.d_names.reset();
+    t.d_name_off.reset();
+
+    return filter_result_to_store(who, r, n_txps, ng, t.bin_width, model, t.growth_rate, t.device, t.opts, t.out_kept, t.out_discard, t.out);
+}
+
 void records_names_last_call(double *out8) { std::memcpy(out8, g_records_names_last, sizeof g_records_names_last); }
 
 } // namespace oem
@@ -311,7 +545,7 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
 
     // -- upload -------------------------------------------------------------------------------------------------------
     const uint64_t n_bytes = name_off[n];
-    DevBuf<oem_aln_record> d_in, d_sorted;
+    DevBuf<oem_aln_record> d_in;
     DevBuf<uint8_t> d_names, d_sec;
     DevBuf<uint64_t> d_name_off;
     DevBuf<uint32_t> d_order_parse;
@@ -369,158 +603,46 @@ extern "C" int oem_store_create_records_names(const oem_filters *filters, const 
         if (dense) last[1] = 1;
     }
 
-    // -- collate: the survivors as one cell -----------------------------------------------------------------------------
-    const uint64_t one_cell[2] = {0, m};
-    CollateResident cr;
-    {
-        CollateInput in;
-        in.who = who;
-        in.cell_rec_off = one_cell;
-        in.mode = mode;
-        in.chunk_bytes = collate_chunk_bytes();
-        in.d_names = dense ? d_dense.p : d_names.p;
-        in.d_name_off = dense ? d_dense_off.p : d_name_off.p;
-        in.d_n_bytes = dense_bytes;
-        in.d_secondary = dense ? d_dense_sec.p : d_sec.p;
-        double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        OEM_TRY(collate_resident(in, 0, 1, 0, 0, 0, info, &cr));
-    }
-    d_dense.reset();
-    d_dense_sec.reset();
-    d_dense_off.reset();
-    d_sec.reset();
-    if (dense) OEM_TRY(order_compose(m, d_order_parse.p, cr.order.p));
-    d_order_parse.reset();
-    const uint64_t ng = cr.n_groups;
-    pi.n_groups = ng;
-
-    // -- the collation check --------------------------------------------------------------------------------------------
-    if (!sorting && sort_check_num) {
-        const uint64_t nchk = std::min<uint64_t>(sort_check_num, ng);
-        pi.n_checked = nchk;
-        last[2] = (double)nchk;
-        if (nchk > 1) {
-            DevBuf<uint32_t> d_heads;
-            DevBuf<uint64_t> d_chk_off;
-            DevBuf<uint8_t> d_chk;
-            uint64_t chk_bytes = 0;
-            OEM_TRY(dev_alloc(&d_heads.p, nchk, nullptr));
-            hipLaunchKernelGGL(k_parse_heads, grid_for(nchk), dim3(kPT), 0, nullptr, nchk, (const uint64_t *)cr.group_off.p,
-                               (const uint32_t *)cr.order.p, d_heads.p);
-            OEM_HIP(hipGetLastError());
-            OEM_TRY(gather_input_names(d_heads.p, nchk, d_names.p, d_name_off.p, &d_chk_off, &d_chk, &chk_bytes));
-            uint64_t found = ~0ull;
-            OEM_TRY(parse_check_repeat(who, d_chk.p, d_chk_off.p, chk_bytes, nchk, &found));
-            if (found != ~0ull) {
-                const uint64_t g = found >> 32, earlier = found & 0xffffffffull;
-                uint32_t rec_g = 0, rec_e = 0;
-                OEM_HIP(hipMemcpy(&rec_g, d_heads.p + g, sizeof rec_g, hipMemcpyDeviceToHost));
-                OEM_HIP(hipMemcpy(&rec_e, d_heads.p + earlier, sizeof rec_e, hipMemcpyDeviceToHost));
-                return parse_not_collated(who, g, rec_g, rec_e);
-            }
-        }
-    }
-
-    if (out_order) OEM_HIP(hipMemcpy(out_order, cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-    if (out_group_off) OEM_HIP(hipMemcpy(out_group_off, cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
-
-    // -- gather and filter ----------------------------------------------------------------------------------------------
-    FilterResult r;
-    FilterCells fc;
-    bool host = host_only;
-    if (!host) {
-        const oem_aln_record *d_recs = d_in.p;
-        if (sorting || dense) {
-            OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
-            OEM_TRY(records_gather(m, cr.order.p, d_in.p, d_sorted.p));
-            d_in.reset(); // the records are held twice only for the length of the gather
-            d_recs = d_sorted.p;
-            last[0] = 1;
-        }
-        fc.n_cells = 1;
-        OEM_TRY(filter_device_resident(who, *filters, txp_len, n_txps, tab, d_recs, (const unsigned long long *)cr.group_off.p, ng,
-                                       (const unsigned long long *)cr.cell_group_off.p, model >= 0, &r, &fc));
-        if (r.bad_ref_record != kNoRecord) { // a collated position: the caller knows its records by their input index
-            uint32_t at = 0;
-            OEM_HIP(hipMemcpy(&at, cr.order.p + r.bad_ref_record, sizeof at, hipMemcpyDeviceToHost));
-            return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)at, records[at].ref_id);
-        }
-        host = r.host_rerun;
-    }
-    d_in.reset();
-    d_sorted.reset();
-
-    if (host) { // the host loop: order and group_off come down, the host gathers the records
-        last[3] = 1;
-        std::vector<uint32_t> order(m), kept(ng);
-        std::vector<uint64_t> goff(ng + 1);
-        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-        OEM_HIP(hipMemcpy(goff.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
-        cr.order.reset();
-        cr.group_off.reset();
-        cr.cell_group_off.reset();
-        d_names.reset();
-        d_name_off.reset();
-        std::vector<oem_aln_record> sorted(m);
-        for (uint64_t k = 0; k < m; ++k) {
-            sorted[k] = records[order[k]];
-            if (sorted[k].ref_id >= n_txps)
-                return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)order[k], sorted[k].ref_id);
-        }
-        oem_builder hb;
-        hb.f = *filters;
-        hb.txp_len.assign(txp_len, txp_len + n_txps);
-        OEM_TRY(add_groups_host(&hb, sorted.data(), goff.data(), ng, kept.data(), who));
-        if (hb.tid.size() >= (1ull << 32)) return fail(OEM_ERR_ARG, "%s: a resident store needs fewer than 2^32 alignments", who);
-        pi.n_reads = hb.row_ptr.size() - 1;
-        uint64_t row_bytes = 0, row = 0;
-        if (want_rows) out_row_name_off[0] = 0;
-        for (uint64_t g = 0; g < ng; ++g) {
-            if (kept[g] == 1) ++pi.unique_alignments;
-            if (!kept[g] || !want_rows) continue;
-            const uint32_t i = order[goff[g]];
-            std::memcpy(out_row_names + row_bytes, names + name_off[i], name_off[i + 1] - name_off[i]);
-            row_bytes += name_off[i + 1] - name_off[i];
-            out_row_name_off[++row] = row_bytes;
-        }
-        if (out_kept) std::memcpy(out_kept, kept.data(), sizeof(uint32_t) * ng);
-        if (out_discard) *out_discard = hb.dt;
-        if (model < 0) OEM_TRY(oem_builder_store_create(&hb, nullptr, device, opts, out));
-        else OEM_TRY(oem_builder_store_create_coverage(&hb, bin_width, model, growth_rate, device, opts, nullptr, out));
-        if (out_info) *out_info = pi;
-        std::memcpy(g_records_names_last, last, sizeof last);
-        return OEM_OK;
-    }
-
-    // -- unique_alignments and the row names, before the store takes the arrays -----------------------------------------
-    pi.n_reads = r.n_rows;
-    OEM_TRY(parse_count_unique(ng, r.n_kept.p, &pi.unique_alignments));
-    if (want_rows) {
-        out_row_name_off[0] = 0;
-        if (r.n_rows) {
-            DevBuf<uint64_t> d_row_idx, d_row_off;
-            DevBuf<uint32_t> d_heads;
-            DevBuf<uint8_t> d_rows;
-            uint64_t row_bytes = 0;
-            OEM_TRY(dev_alloc(&d_row_idx.p, ng + 1, nullptr));
-            OEM_TRY(dev_alloc(&d_heads.p, r.n_rows, nullptr));
-            OEM_TRY(parse_row_index(r.n_kept.p, ng + 1, d_row_idx.p)); // (n_kept has n_groups + 1 entries, the last one 0)
-            hipLaunchKernelGGL(k_parse_row_heads, grid_for(ng), dim3(kPT), 0, nullptr, ng, (const uint32_t *)r.n_kept.p,
-                               (const uint64_t *)d_row_idx.p, (const uint64_t *)cr.group_off.p, (const uint32_t *)cr.order.p, d_heads.p);
-            OEM_HIP(hipGetLastError());
-            d_row_idx.reset();
-            OEM_TRY(gather_input_names(d_heads.p, r.n_rows, d_names.p, d_name_off.p, &d_row_off, &d_rows, &row_bytes));
-            OEM_HIP(hipMemcpy(out_row_name_off, d_row_off.p, sizeof(uint64_t) * (r.n_rows + 1), hipMemcpyDeviceToHost));
-            if (row_bytes) OEM_HIP(hipMemcpy(out_row_names, d_rows.p, row_bytes, hipMemcpyDeviceToHost));
-        }
-    }
-    cr.order.reset();
-    cr.group_off.reset();
-    cr.cell_group_off.reset();
-    d_names.reset();
-    d_name_off.reset();
-
-    OEM_TRY(filter_result_to_store(who, r, n_txps, ng, bin_width, model, growth_rate, device, opts, out_kept, out_discard, out));
+    // -- the tail: collate, check, gather, filter, store, row names (parse_tail) ------------------------------------------
+    ParseTail t;
+    t.who = who;
+    t.filters = filters;
+    t.txp_len = txp_len;
+    t.n_txps = n_txps;
+    t.tab = &tab;
+    t.host_only = host_only;
+    t.mode = mode;
+    t.sort_check_num = sort_check_num;
+    t.bin_width = bin_width;
+    t.model = model;
+    t.growth_rate = growth_rate;
+    t.device = device;
+    t.opts = opts;
+    t.m = m;
+    t.dense = dense;
+    t.dense_bytes = dense_bytes;
+    std::swap(t.d_in.p, d_in.p);
+    std::swap(t.d_names.p, d_names.p);
+    std::swap(t.d_sec.p, d_sec.p);
+    std::swap(t.d_name_off.p, d_name_off.p);
+    std::swap(t.d_order_parse.p, d_order_parse.p);
+    std::swap(t.d_dense.p, d_dense.p);
+    std::swap(t.d_dense_sec.p, d_dense_sec.p);
+    std::swap(t.d_dense_off.p, d_dense_off.p);
+    t.h_records = records;
+    t.h_names = names;
+    t.h_name_off = name_off;
+    t.out_order = out_order;
+    t.out_group_off = out_group_off;
+    t.out_kept = out_kept;
+    t.out_row_names = out_row_names;
+    t.out_row_name_off = out_row_name_off;
+    t.want_rows = want_rows;
+    t.out_discard = out_discard;
+    t.pi = &pi;
+    t.last = last;
+    t.out = out;
+    OEM_TRY(parse_tail(t));
     if (out_info) *out_info = pi;
     std::memcpy(g_records_names_last, last, sizeof last);
     return OEM_OK;

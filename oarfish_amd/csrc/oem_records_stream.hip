@@ -29,6 +29,12 @@
 // the CSR, the (index, f) list of the alignments whose expf the host has to supply (k_proj_collect).  finish joins the
 // lists in the one k_stream_concat launch, the indices with the piece's alignment base added, and runs the host's expf
 // and the scatter once, before filter_result_to_store.
+//
+// The SORTING NAMES form (oem_records_stream_set_sort; "the sorting names session" in DESIGN.md section 5d) takes records,
+// read names and secondary flags in ANY order.  Nothing can be cut or filtered before the last record is in, so its
+// worker only parses: each batch's survivors -- their records, their dense names with offsets rebased, their flags and
+// their 64-bit session-global indices (k_arena_append) -- are appended to an arena that stays on the device and grows
+// geometrically; finish runs the one call's tail (parse_tail, oem_parse_device.h) on the arena as on an uploaded input.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -170,6 +176,7 @@ struct Batch {
     // a names session's batch: no groups yet; the arena holds name_off (n_records + 1), the records and the name bytes
     bool named = false;
     bool projected = false; // a projected session's batch: whole groups of oem_proj_record with their read lengths
+    bool sorting = false, has_sec = false; // a sorting names session's batch (named too); its n_records flags behind the names
     uint64_t rec_base = 0, name_bytes = 0; // the session-global input index of its first record; name_off[n_records]
     Arena mem;          // (none for a batch without groups, or without records in a names session)
     bool ready = false; // the pushing thread has finished its copy
@@ -194,6 +201,8 @@ struct Batch {
     const oem_aln_record *named_records() const { return (const oem_aln_record *)((const char *)mem.p + records_at(n_records)); }
     static size_t names_at(uint64_t n_records) { return records_at(n_records) + ((sizeof(oem_aln_record) * n_records + 63) & ~(size_t)63); }
     const uint8_t *names() const { return (const uint8_t *)mem.p + names_at(n_records); }
+    static size_t sec_at(uint64_t n_records, uint64_t name_bytes) { return names_at(n_records) + ((name_bytes + 63) & ~(size_t)63); }
+    const uint8_t *secondary() const { return (const uint8_t *)mem.p + sec_at(n_records, name_bytes); }
 };
 
 // What a batch leaves on the device: r.row_ptr32 (n_rows + 1, from 0), r.tid, r.as_prob, with a model r.start / r.end /
@@ -283,6 +292,90 @@ __global__ __launch_bounds__(kCT) void k_names_ref_check(uint64_t cnt, const uin
     if ((uint32_t)rec_words[(uint64_t)i * 5] >= n_txps) atomicMin(bad, (unsigned long long)i);
 }
 
+// ---- the sorting names session: the survivors' arena ----------------------------------------------------------------------
+
+// What a sorting names session keeps on the device until finish: the n survivors of all batches so far in ticket order.
+// recs / idx / sec / off have room for cap survivors (sec 8 bytes and off one entry more), names for byte_cap bytes
+// and 16 more.  off[0] = 0.  rec_held / name_held / peak: the device bytes of the arrays, now and at most (a growing
+// array is held twice while it is copied).
+struct SortArena {
+    DevBuf<oem_aln_record> recs;
+    DevBuf<uint64_t> idx, off;
+    DevBuf<uint8_t> sec, names;
+    uint64_t n = 0, cap = 0, bytes = 0, byte_cap = 0, rec_held = 0, name_held = 0, peak = 0;
+    bool any_sec = false;
+    static uint64_t per_record() { return sizeof(oem_aln_record) + 2 * sizeof(uint64_t) + 1; }
+    void release()
+    {
+        recs.reset();
+        idx.reset();
+        off.reset();
+        sec.reset();
+        names.reset();
+        n = cap = bytes = byte_cap = rec_held = name_held = 0;
+    }
+    // room for n_need survivors and bytes_need name bytes: geometric reallocation, the used part copied on the device
+    int reserve(uint64_t n_need, uint64_t bytes_need)
+    {
+        if (n_need > cap) {
+            const uint64_t nc = std::max<uint64_t>(std::max<uint64_t>(2 * cap, n_need), 1024);
+            const uint64_t grown = nc * per_record() + 16;
+            peak = std::max(peak, rec_held + name_held + grown);
+            DevBuf<oem_aln_record> r2;
+            DevBuf<uint64_t> i2, o2;
+            DevBuf<uint8_t> s2;
+            OEM_TRY(dev_alloc(&r2.p, nc, nullptr));
+            OEM_TRY(dev_alloc(&i2.p, nc, nullptr));
+            OEM_TRY(dev_alloc(&o2.p, nc + 1, nullptr));
+            OEM_TRY(dev_alloc(&s2.p, nc + 8, nullptr));
+            if (n) {
+                OEM_HIP(hipMemcpy(r2.p, recs.p, sizeof(oem_aln_record) * n, hipMemcpyDeviceToDevice));
+                OEM_HIP(hipMemcpy(i2.p, idx.p, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice));
+                OEM_HIP(hipMemcpy(o2.p, off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToDevice));
+                OEM_HIP(hipMemcpy(s2.p, sec.p, n, hipMemcpyDeviceToDevice));
+            } else {
+                OEM_HIP(hipMemset(o2.p, 0, sizeof(uint64_t)));
+            }
+            std::swap(recs.p, r2.p);
+            std::swap(idx.p, i2.p);
+            std::swap(off.p, o2.p);
+            std::swap(sec.p, s2.p);
+            rec_held = grown;
+            cap = nc;
+        }
+        if (bytes_need > byte_cap || !names.p) {
+            const uint64_t bc = std::max<uint64_t>(std::max<uint64_t>(2 * byte_cap, bytes_need), 4096);
+            peak = std::max(peak, rec_held + name_held + bc + 16);
+            DevBuf<uint8_t> n2;
+            OEM_TRY(dev_alloc(&n2.p, bc + 16, nullptr));
+            if (bytes) OEM_HIP(hipMemcpy(n2.p, names.p, bytes, hipMemcpyDeviceToDevice));
+            std::swap(names.p, n2.p);
+            name_held = bc + 16;
+            byte_cap = bc;
+        }
+        return OEM_OK;
+    }
+};
+
+// The per-survivor part of an arena append, one lane per survivor k < m of the batch, which becomes arena record
+// base + k (below cap: checked by the caller, and here):
+//   idx[base + k]     = rec_base + order[k], its session-global input index, 64 bits (order[k] < n_in, the batch's size)
+//   off[base + k + 1] = byte_base + src_off[k + 1]: the batch's dense offsets (from 0) rebased to the arena's blob
+//   sec[base + k]     = src_sec[k] != 0, or 0 for a batch without flags
+// The 40-byte records go through records_gather, the name bytes through k_stream_concat's 16-byte units.
+__global__ __launch_bounds__(kCT) void k_arena_append(uint64_t m, uint64_t n_in, uint64_t base, uint64_t cap, uint64_t rec_base, uint64_t byte_base,
+                                                      const uint32_t *__restrict__ order, const uint64_t *__restrict__ src_off,
+                                                      const uint8_t *__restrict__ src_sec, uint64_t *__restrict__ idx, uint64_t *__restrict__ off,
+                                                      uint8_t *__restrict__ sec)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kCT + threadIdx.x;
+    if (k >= m || base + k >= cap) return;
+    const uint32_t i = order[k];
+    idx[base + k] = i < n_in ? rec_base + i : kNoRecord;
+    off[base + k + 1] = byte_base + src_off[k + 1];
+    sec[base + k] = src_sec ? (uint8_t)(src_sec[k] != 0) : (uint8_t)0;
+}
+
 inline dim3 names_grid(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kCT - 1) / kCT, 1)); }
 static_assert(offsetof(oem_aln_record, ref_id) == 0, "k_names_ref_check reads ref_id from a record's first word");
 
@@ -366,17 +459,25 @@ struct oem_records_stream {
     std::vector<uint32_t> out_kept;
     std::vector<uint8_t> out_rows;
 
+    // -- the sorting names session (oem_records_stream_set_sort): `named` too ------------------------------------------------
+    bool sorting = false;
+    SortArena arena;
+    uint64_t arena_peak = 0;         // (mu held) arena.peak as of the last batch
+    std::vector<uint64_t> out_order; // what finish leaves for oem_records_stream_order_copy
+
     // -- the projected session (oem_records_stream_set_projected) --------------------------------------------------------
     bool projected = false;
     oem_proj_opts popts{10.f, OEM_PROJ_SIMILARITY};
     uint64_t host_finished = 0; // after finish: alignments whose expf the host supplied
 
-    // the session's kind as the calls name it: 0 plain, 1 names, 2 projected (mu held)
-    int kind() const { return named ? 1 : projected ? 2 : 0; }
+    // the session's kind as the calls name it: 0 plain, 1 names, 2 projected, 3 sorting names (mu held)
+    int kind() const { return sorting ? 3 : named ? 1 : projected ? 2 : 0; }
 
     template <typename Rec>
     int run_batch(const Batch &b, Piece *out, bool *host);
     int run_batch_names(const Batch &b, Piece *out, bool *host);
+    int run_batch_sort(const Batch &b);
+    int finish_sort(const char *who, const oem_store_opts *opts, oem_discard_table *out_discard, oem_parse_info *pi, oem_store **out);
     int upload_piece(oem_builder &hb, const std::vector<uint32_t> &kept, uint64_t n_groups, const char *who, Piece *out);
     int close_groups(const char *who, uint64_t rec_base, uint64_t n, const oem_aln_record *h_records,
                      const oem_aln_record *d_in, const uint32_t *d_order, uint64_t p_last, const uint64_t *d_gb, uint64_t ngb, bool joins,
@@ -796,6 +897,147 @@ int oem_records_stream::names_close(const char *who)
     return OEM_OK;
 }
 
+// ---- the sorting names session's worker and finish ("The sorting names session") -------------------
+
+// One batch of a sorting names session: upload from the staging arena, the survivors, their names checked and made
+// dense, their ref_ids checked, and all of it appended to the device arena.  Nothing is cut or filtered here.
+int oem_records_stream::run_batch_sort(const Batch &b)
+{
+    const uint64_t n = b.n_records;
+    if (n == 0) return OEM_OK;
+    char who[64];
+    snprintf(who, sizeof who, "oem_records_stream: ticket %llu", (unsigned long long)b.ticket);
+    const uint64_t n_bytes = b.name_bytes;
+    DevBuf<oem_aln_record> d_in;
+    DevBuf<uint8_t> d_names, d_sec;
+    DevBuf<uint64_t> d_name_off;
+    OEM_TRY(dev_alloc(&d_in.p, n, nullptr));
+    OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16, nullptr));
+    OEM_TRY(dev_alloc(&d_name_off.p, n + 1, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_in.p, b.named_records(), sizeof(oem_aln_record) * n, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_name_off.p, b.name_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
+    if (n_bytes) OEM_HIP(hipMemcpyAsync(d_names.p, b.names(), n_bytes, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemsetAsync(d_names.p + n_bytes, 0, 16, nullptr));
+    if (b.has_sec) { // (read through aligned 4-byte words: padded)
+        OEM_TRY(dev_alloc(&d_sec.p, n + 8, nullptr));
+        OEM_HIP(hipMemcpyAsync(d_sec.p, b.secondary(), n, hipMemcpyHostToDevice, nullptr));
+        OEM_HIP(hipMemsetAsync(d_sec.p + n, 0, 8, nullptr));
+    }
+    OEM_HIP(hipStreamSynchronize(nullptr));
+
+    DevBuf<uint32_t> d_order;
+    uint64_t m = 0;
+    OEM_TRY(parse_survivors(d_in.p, n, true, &d_order, &m));
+    n_unmapped += n - m;
+    if (m == 0) return OEM_OK;
+    if (arena.n + m > kCollateMaxBatch)
+        return fail(OEM_ERR_ARG, "%s: more than 2^31 - 2 surviving records in the session: the names are collated as one batch", who);
+    const bool dense = m < n;
+    DevBuf<uint8_t> d_dense, d_dense_sec;
+    DevBuf<uint64_t> d_dense_off;
+    uint64_t dense_bytes = n_bytes, bad_record = kNoRecord;
+    bool zero_byte = false;
+    OEM_TRY(parse_survivor_names(d_names.p, n_bytes, d_name_off.p, n, dense ? d_order.p : nullptr, m, d_sec.p, &d_dense, &d_dense_off,
+                                 &d_dense_sec, &dense_bytes, &bad_record, &zero_byte));
+    if (bad_record != kNoRecord) return parse_bad_name(who, zero_byte, b.rec_base + bad_record);
+    {
+        DevBuf<unsigned long long> d_bad;
+        unsigned long long bad = kNoRecord;
+        OEM_TRY(dev_alloc(&d_bad.p, 1, nullptr));
+        OEM_HIP(hipMemcpy(d_bad.p, &bad, sizeof bad, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_names_ref_check, names_grid(m), dim3(kCT), 0, nullptr, m, (const uint32_t *)d_order.p, (const uint64_t *)d_in.p,
+                           o.n_txps, d_bad.p);
+        OEM_HIP(hipGetLastError());
+        OEM_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad != kNoRecord) return bad_ref(who, b.rec_base + bad, b.named_records()[bad].ref_id);
+    }
+
+    // the append: records, per-survivor words, name bytes
+    OEM_TRY(arena.reserve(arena.n + m, arena.bytes + dense_bytes));
+    OEM_TRY(records_gather(m, d_order.p, d_in.p, arena.recs.p + arena.n));
+    const uint8_t *src_sec = !b.has_sec ? nullptr : dense ? d_dense_sec.p : d_sec.p;
+    hipLaunchKernelGGL(k_arena_append, names_grid(m), dim3(kCT), 0, nullptr, m, n, arena.n, arena.cap, b.rec_base, arena.bytes,
+                       (const uint32_t *)d_order.p, (const uint64_t *)(dense ? d_dense_off.p : d_name_off.p), src_sec, arena.idx.p, arena.off.p,
+                       arena.sec.p);
+    OEM_HIP(hipGetLastError());
+    ConcatPlan plan;
+    plan.add(dense ? d_dense.p : d_names.p, arena.names.p + arena.bytes, dense_bytes, 1, 0);
+    OEM_TRY(plan.run(who, nullptr));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    arena.n += m;
+    arena.bytes += dense_bytes;
+    arena.any_sec |= b.has_sec;
+    n_parsed += m;
+    return OEM_OK;
+}
+
+// A sorting names session's finish, after the worker's end: the one call's tail on the arena.
+int oem_records_stream::finish_sort(const char *who, const oem_store_opts *opts, oem_discard_table *out_discard, oem_parse_info *pi,
+                                    oem_store **out)
+{
+    pi->n_unmapped = n_unmapped;
+    pi->n_parsed = n_parsed;
+    pieces.clear();
+    const uint64_t m = arena.n;
+    if (m == 0) { // nothing survives: the store of no groups, as the one call makes it
+        const uint64_t no_groups[1] = {0};
+        arena.release();
+        out_group_off.assign(1, 0);
+        out_row_off.assign(1, 0);
+        return oem_store_create_records(&f, txp_len.data(), o.n_txps, nullptr, no_groups, 0, o.bin_width, o.model, o.growth_rate, o.device,
+                                        opts, nullptr, out_discard, out);
+    }
+    OEM_HIP(hipMemset(arena.names.p + arena.bytes, 0, 16));
+    OEM_HIP(hipMemset(arena.sec.p + m, 0, 8));
+    double last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    ParseTail t;
+    t.who = who;
+    t.filters = &f;
+    t.txp_len = txp_len.data();
+    t.n_txps = o.n_txps;
+    t.tab = &tab;
+    t.host_only = host_only;
+    t.mode = kCollateSort;
+    t.bin_width = o.bin_width;
+    t.model = o.model;
+    t.growth_rate = o.growth_rate;
+    t.device = o.device;
+    t.opts = opts;
+    t.m = m;
+    t.dense_bytes = arena.bytes;
+    std::swap(t.d_in.p, arena.recs.p);
+    std::swap(t.d_names.p, arena.names.p);
+    std::swap(t.d_name_off.p, arena.off.p);
+    if (arena.any_sec) std::swap(t.d_sec.p, arena.sec.p);
+    t.d_global = arena.idx.p; // (stays the arena's until the tail is over)
+    t.want_rows = true;
+    t.on_groups = [&](uint64_t ng) {
+        out_order.resize(m);
+        out_group_off.resize(ng + 1);
+        out_kept.resize(ng);
+        t.out_order64 = out_order.data();
+        t.out_group_off = out_group_off.data();
+        t.out_kept = out_kept.data();
+    };
+    t.on_rows = [&](uint64_t n_rows, uint64_t row_bytes) {
+        out_row_off.resize(n_rows + 1);
+        out_rows.resize(row_bytes);
+        t.out_row_name_off = out_row_off.data();
+        t.out_row_names = out_rows.data();
+    };
+    t.out_discard = out_discard;
+    t.pi = pi;
+    t.last = last;
+    t.out = out;
+    const int rc = parse_tail(t);
+    arena.release();
+    if (rc != OEM_OK) return rc;
+    std::lock_guard<std::mutex> lk(mu);
+    total_groups = pi->n_groups;
+    if (last[3] != 0) ++host_batches;
+    return OEM_OK;
+}
+
 void oem_records_stream::work()
 {
     const bool dev_ok = hipSetDevice(o.device) == hipSuccess;
@@ -819,7 +1061,8 @@ void oem_records_stream::work()
         if (!skip) {
             try {
                 piece.reset(new Piece());
-                rc = b->named       ? run_batch_names(*b, piece.get(), &host)
+                rc = b->sorting     ? run_batch_sort(*b)
+                     : b->named     ? run_batch_names(*b, piece.get(), &host)
                      : b->projected ? run_batch<oem_proj_record>(*b, piece.get(), &host)
                                     : run_batch<oem_aln_record>(*b, piece.get(), &host);
             } catch (const std::bad_alloc &) {
@@ -830,12 +1073,14 @@ void oem_records_stream::work()
             if (rc != OEM_OK) {
                 msg = last_error_text(); // (the message is thread-local)
                 piece.reset();
+                arena.release(); // (a sorting names session is stuck from here on: everything it held goes)
             }
         }
         {
             std::lock_guard<std::mutex> lk(mu);
             staged_records -= b->n_records;
             give_arena(b->mem);
+            arena_peak = arena.peak;
             if (rc != OEM_OK) {
                 set_sticky(rc, msg.c_str());
             } else if (!skip) {
@@ -1007,18 +1252,21 @@ namespace {
 // What the three pushes do once the batch's own checks have passed: wait for room in the staging budget, take the ticket
 // under the session lock, then -- outside it -- find an arena of `bytes` and let fill(arena) copy the caller's arrays.
 // kind: the session the push belongs to (oem_records_stream::kind()).  1: the batch of a names session (n_groups 0,
-// name_bytes = name_off[n_records]); 2: of a projected session; a batch has a payload when `bytes` > 0.
+// name_bytes = name_off[n_records]); 2: of a projected session; 3: of a sorting names session (as 1, has_sec: with
+// flags); a batch has a payload when `bytes` > 0.
 template <typename Fill>
 int stage_batch(oem_records_stream *s, const char *who, int kind, uint64_t n_groups, uint64_t n_records, uint64_t name_bytes, size_t bytes,
-                Fill &&fill, uint64_t *out_ticket)
+                Fill &&fill, uint64_t *out_ticket, bool has_sec = false)
 {
-    const bool named = kind == 1;
+    const bool named = kind == 1 || kind == 3;
     Batch *b = nullptr;
     {
         std::unique_lock<std::mutex> lk(s->mu);
         if (s->kind() != kind)
             return fail(OEM_ERR_STATE,
-                        kind == 1   ? "%s: not a names session (oem_records_stream_set_names)"
+                        s->sorting  ? "%s: a sorting names session takes oem_records_stream_push_sort"
+                        : kind == 3 ? "%s: not a sorting names session (oem_records_stream_set_sort)"
+                        : kind == 1 ? "%s: not a names session (oem_records_stream_set_names)"
                         : kind == 2 ? "%s: not a projected session (oem_records_stream_set_projected)"
                         : s->named  ? "%s: a names session takes oem_records_stream_push_names"
                                     : "%s: a projected session takes oem_records_stream_push_projected",
@@ -1044,6 +1292,8 @@ int stage_batch(oem_records_stream *s, const char *who, int kind, uint64_t n_gro
         nb->n_records = n_records;
         nb->named = named;
         nb->projected = kind == 2;
+        nb->sorting = kind == 3;
+        nb->has_sec = has_sec;
         nb->rec_base = s->total_records;
         nb->name_bytes = name_bytes;
         if (bytes) nb->mem = s->take_arena(bytes);
@@ -1185,6 +1435,48 @@ extern "C" int oem_records_stream_push_names(oem_records_stream *s, const oem_al
     OEM_API_END("oem_records_stream_push_names")
 }
 
+extern "C" int oem_records_stream_set_sort(oem_records_stream *s)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_set_sort";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->sorting) return fail(OEM_ERR_STATE, "%s: the session is a sorting names session already", who);
+    if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session", who);
+    if (s->projected) return fail(OEM_ERR_STATE, "%s: the session is a projected session", who);
+    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    s->named = true; // (finish_names, names_copy and the sticky rules are the names session's)
+    s->sorting = true;
+    s->sort_check_num = 0;
+    return OEM_OK;
+    OEM_API_END("oem_records_stream_set_sort")
+}
+
+extern "C" int oem_records_stream_push_sort(oem_records_stream *s, const oem_aln_record *records, uint64_t n_records, const uint8_t *names,
+                                            const uint64_t *name_off, const uint8_t *secondary, uint64_t *out_ticket)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_push_sort";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    // the batch's own checks (oem_records_stream_push_names'), on the calling thread, before the session is touched
+    if (!name_off) return fail(OEM_ERR_ARG, "%s: name_off is NULL", who);
+    const uint64_t n = n_records, whole[2] = {0, n};
+    if (n > kCollateMaxBatch) return fail(OEM_ERR_ARG, "%s: %llu records: at most 2^31 - 2 per batch", who, (unsigned long long)n);
+    OEM_TRY(check_collate_input(who, names, name_off, n, whole, 1, kCollateSort));
+    if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+    const uint64_t n_bytes = name_off[n];
+    const size_t rec_at = Batch::records_at(n), names_at = Batch::names_at(n), sec_at = Batch::sec_at(n, n_bytes);
+    const size_t bytes = secondary ? sec_at + n : names_at + n_bytes;
+    return stage_batch(s, who, 3, 0, n, n_bytes, n ? bytes : 0, [&](char *mem) {
+        std::memcpy(mem, name_off, sizeof(uint64_t) * (n + 1));
+        std::memcpy(mem + rec_at, records, sizeof(oem_aln_record) * n);
+        if (n_bytes) std::memcpy(mem + names_at, names, n_bytes);
+        if (secondary) std::memcpy(mem + sec_at, secondary, n);
+    }, out_ticket, secondary != nullptr && n > 0);
+    OEM_API_END("oem_records_stream_push_sort")
+}
+
 extern "C" int oem_records_stream_finish(oem_records_stream *s, const oem_store_opts *opts, uint32_t *out_kept,
                                          oem_discard_table *out_discard, oem_store **out)
 {
@@ -1213,12 +1505,19 @@ extern "C" int oem_records_stream_finish_names(oem_records_stream *s, const oem_
     if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
     OEM_TRY(check_store_from_records(who, &s->f, s->txp_len.data(), s->o.n_txps, s->o.bin_width, s->o.model, opts));
     OEM_TRY(s->finish_begin(who, true));
+    oem_parse_info pi;
+    std::memset(&pi, 0, sizeof pi);
+    if (s->sorting) { // the one call's tail on the arena; the variable-length outputs stay with the session as below
+        OEM_TRY(s->finish_sort(who, opts, out_discard, &pi, out));
+        if (out_info) *out_info = pi;
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->names_ready = true;
+        return OEM_OK;
+    }
     OEM_TRY(s->names_close(who));
     FilterResult r;
     uint64_t n_groups = 0;
     OEM_TRY(s->join(who, &r, &n_groups));
-    oem_parse_info pi;
-    std::memset(&pi, 0, sizeof pi);
     pi.n_unmapped = s->n_unmapped;
     pi.n_parsed = s->n_parsed;
     pi.n_groups = n_groups;
@@ -1256,6 +1555,20 @@ extern "C" int oem_records_stream_names_copy(const oem_records_stream *s, uint64
     OEM_API_END("oem_records_stream_names_copy")
 }
 
+extern "C" int oem_records_stream_order_copy(const oem_records_stream *s, uint64_t *out_order)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_records_stream_order_copy";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->sorting) return fail(OEM_ERR_STATE, "%s: not a sorting names session (oem_records_stream_set_sort)", who);
+    if (!s->names_ready) return fail(OEM_ERR_STATE, "%s: the session has not been finished", who);
+    if (!out_order && !s->out_order.empty()) return fail(OEM_ERR_ARG, "%s: out_order is NULL", who);
+    if (!s->out_order.empty()) std::memcpy(out_order, s->out_order.data(), sizeof(uint64_t) * s->out_order.size());
+    return OEM_OK;
+    OEM_API_END("oem_records_stream_order_copy")
+}
+
 namespace oem {
 
 // The test-only library's oem_debug_records_stream_finish_csr: ends the session as finish does, but copies the joined
@@ -1268,6 +1581,7 @@ int records_stream_finish_csr(oem_records_stream *s, uint64_t *dims3, const uint
 {
     const char *who = "oem_debug_records_stream_finish_csr";
     if (!s || !dims3 || !caps3) return fail(OEM_ERR_ARG, "%s: NULL argument", who);
+    if (s->sorting) return fail(OEM_ERR_STATE, "%s: a sorting names session has no joined CSR", who);
     OEM_TRY(s->finish_begin(who, s->named));
     OEM_TRY(s->names_close(who)); // (a names session: the carry's piece and the check; the joined CSR is the same kind)
     FilterResult r;
@@ -1312,6 +1626,7 @@ extern "C" int oem_records_stream_info(const oem_records_stream *s, uint32_t key
     case OEM_RECORDS_STREAM_INFO_HOST_BATCHES: *value = s->host_batches; break;
     case OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES: *value = s->out_rows.size(); break;
     case OEM_RECORDS_STREAM_INFO_HOST_FINISHED: *value = s->host_finished; break;
+    case OEM_RECORDS_STREAM_INFO_ARENA_BYTES: *value = s->arena_peak; break;
     default: return fail(OEM_ERR_ARG, "oem_records_stream_info: unknown key %u", key);
     }
     return OEM_OK;

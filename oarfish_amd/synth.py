@@ -591,11 +591,12 @@ def make_named_records(synthetic_records: SyntheticRecords, style: str = "uuid",
     return np.ascontiguousarray(records), _flatten_names(rows), np.ascontiguousarray(secondary)
 
 
-def cut_named_records(records, names, cuts):
+def cut_named_records(records, names, cuts, secondary=None):
     """``make_named_records``' input cut into batches for a names session (``RecordsStream(names=True)``): ``cuts`` are
     record positions, in any order and with repeats (a repeat gives an empty batch); 0 and ``len(records)`` are implied.
-    A cut may fall inside a read.  Returns a list of ``(records, (blob, offsets))``, the offsets of each batch from 0.
-    A pure function of its arguments."""
+    A cut may fall inside a read.  Returns a list of ``(records, (blob, offsets))``, the offsets of each batch from 0;
+    with ``secondary`` (one flag per record, for a sorting names session) a list of ``(records, (blob, offsets),
+    secondary)``.  A pure function of its arguments."""
     records = np.asarray(records)
     blob, off = np.asarray(names[0], dtype=np.uint8), np.asarray(names[1], dtype=np.uint64)
     n = len(records)
@@ -604,11 +605,16 @@ def cut_named_records(records, names, cuts):
     edges = [0] + sorted(int(c) for c in cuts) + [n]
     if edges[1] < 0 or edges[-2] > n:
         raise ValueError("a cut lies outside the records")
+    if secondary is not None:
+        secondary = np.asarray(secondary)
+        if len(secondary) != n:
+            raise ValueError("secondary must have one entry per record")
     out = []
     for a, b in zip(edges[:-1], edges[1:]):
         o = off[a:b + 1]
-        out.append((np.ascontiguousarray(records[a:b]),
-                    (np.ascontiguousarray(blob[int(o[0]):int(o[-1])]), np.ascontiguousarray(o - o[0]))))
+        batch = (np.ascontiguousarray(records[a:b]),
+                 (np.ascontiguousarray(blob[int(o[0]):int(o[-1])]), np.ascontiguousarray(o - o[0])))
+        out.append(batch if secondary is None else batch + (np.ascontiguousarray(secondary[a:b]),))
     return out
 
 

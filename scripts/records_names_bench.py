@@ -17,7 +17,12 @@ measurement.  --reads / --txps shrink the shape for a trial run.
 cut at record positions into batches of 2^18 and of 2^20 groups' worth of records (--batch-groups), pushed from one
 thread; seconds from the first push to the end of finish, beside the one call (ADJACENT) timed in the same run, --runs
 repeats in alternation, and for both the peak of the device memory above the level at entry.  The result goes to
-profiles/records_names_stream_bench.json."""
+profiles/records_names_stream_bench.json.
+
+--stream --sort is the sorting names session's leg (RecordsStream(names=True, mode="sort"),
+oem_records_stream_push_sort): the same input PERMUTED, with its secondary flags, in the same batches, beside the one
+call with mode="sort" on the permuted input; order, kept and the discard table are compared in every run, and the
+arena's peak (info()["arena_bytes"]) is recorded.  The result goes to profiles/records_names_sort_stream_bench.json."""
 import argparse
 import json
 import os
@@ -64,11 +69,14 @@ def stream_leg(args, sr, res, save):
     F, tl = sr.filters, sr.txp_len
     n_groups = len(sr.group_off) - 1
     for style in args.styles:
-        rec, (blob, off), _ = synth.make_named_records(sr, style=style, unmapped_rate=args.unmapped_rate)
+        rec, (blob, off), sec = synth.make_named_records(sr, style=style, unmapped_rate=args.unmapped_rate, shuffle=args.sort)
         n = len(rec)
         r = res[style] = dict(record_bytes=int(rec.nbytes), name_bytes=int(blob.nbytes))
 
         def one_call(m=n):
+            if args.sort:   # (the parse comes back too: its order is compared with the session's)
+                out = DeviceStore.from_named_records(F, tl, rec[:m], (blob[:int(off[m])], off[:m + 1]), secondary=sec[:m], mode="sort")
+                return close(out[:3]) + (out[3].order,)
             return close(DeviceStore.from_named_records(F, tl, rec[:m], (blob[:int(off[m])], off[:m + 1]),
                                                         sort_check_num=0 if m < n else 100_000))
 
@@ -76,18 +84,21 @@ def stream_leg(args, sr, res, save):
         for g in args.batch_groups:
             per = max(1, int(round(g * n / max(n_groups, 1))))   # records per batch: g groups' worth, cut at record positions
             edges = list(range(0, n, per)) + [n]
-            batches = [(rec[a:b], (blob[int(off[a]):int(off[b])], off[a:b + 1] - off[a])) for a, b in zip(edges[:-1], edges[1:])]
+            batches = [(rec[a:b], (blob[int(off[a]):int(off[b])], off[a:b + 1] - off[a]), sec[a:b] if args.sort else None)
+                       for a, b in zip(edges[:-1], edges[1:])]
             q = r[f"batch_groups_{g}"] = dict(records_per_batch=per, batches=len(batches))
 
             def session():
-                with RecordsStream(F, tl, names=True) as s:
+                with RecordsStream(F, tl, names=True, mode="sort" if args.sort else "adjacent") as s:
                     t0 = time.perf_counter()
-                    for b_rec, b_names in batches:
-                        s.push(b_rec, names=b_names)
+                    for b_rec, b_names, b_sec in batches:
+                        s.push(b_rec, names=b_names, secondary=b_sec)
                     store, kept, dt, parse = s.finish()
                     t = time.perf_counter() - t0
                     info = s.info()
                 store.close()
+                if args.sort:
+                    info["order"] = parse.order
                 return t, kept, dt, info
 
             a_runs, s_runs = [], []
@@ -103,6 +114,9 @@ def stream_leg(args, sr, res, save):
                     t_a, got = clock(one_call)
                     t_s, kept, dt, info = session()
                 assert np.array_equal(kept, got[0]) and dt == got[1]              # kept and the discard table agree
+                if args.sort:                                                     # ... and so does the collated order
+                    assert np.array_equal(info.pop("order"), got[2].astype(np.int64))
+                    q["arena_bytes"] = info["arena_bytes"]
                 a_runs.append(t_a)
                 s_runs.append(t_s)
                 q.update(one_call=spread(a_runs), session=spread(s_runs), session_over_one_call=round(min(s_runs) / min(a_runs), 4),
@@ -115,6 +129,7 @@ def stream_leg(args, sr, res, save):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stream", action="store_true", help="the names session against the one call (see the module docstring)")
+    ap.add_argument("--sort", action="store_true", help="with --stream: the sorting names session on permuted input against the one call's mode=\"sort\"")
     ap.add_argument("--batch-groups", type=int, nargs="+", default=[1 << 18, 1 << 20])
     ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=5)
@@ -124,8 +139,11 @@ def main():
     ap.add_argument("--unmapped-rate", type=float, default=0.0)
     ap.add_argument("--warm-records", type=int, default=2_000_000)
     args = ap.parse_args()
+    if args.sort and not args.stream:
+        ap.error("--sort belongs to --stream")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "records_names_stream_bench.json" if args.stream else "records_names_bench.json")
+        name = "records_names_sort_stream_bench.json" if args.sort else "records_names_stream_bench.json" if args.stream else "records_names_bench.json"
+        args.out = os.path.join(ROOT, "profiles", name)
 
     st = synth.make_store(args.reads, args.txps, threads=16) if args.reads else synth.make_config("c3")
     sr = synth.make_records(st)
