@@ -889,6 +889,12 @@ typedef struct {
 #define OEM_CELLS_STREAM_INFO_BLOCKED_US 5u           /* microseconds pushes spent blocked on back-pressure, summed
                                                          over the pushing threads */
 #define OEM_CELLS_STREAM_INFO_GROUPS_BATCHED 6u       /* groups that ran as one batched store (the others: cell by cell) */
+/* an any-order barcoded session (oem_cells_stream_set_barcodes_any_order); 0 on every other session */
+#define OEM_CELLS_STREAM_INFO_ARENA_BYTES 7u          /* the most device memory the arena of survivors held, in bytes (a
+                                                         growing array is counted twice while it is copied, and so is
+                                                         the arena while finish lays it out by cell) */
+#define OEM_CELLS_STREAM_INFO_BARCODE_MISSES 8u       /* survivors that missed the first lookup of their batch */
+#define OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS 9u  /* the barcode table's capacity (after finish: the final one) */
 
 /* Argument errors (n_txps = 0, opts or out NULL, coverage = 1 without txp_len, with bin_width = 0 or with a model
  * other than 0 / 1, a non-zero reserved word) are reported before any device is touched; without a device the call
@@ -984,6 +990,33 @@ int oem_cells_stream_push_barcodes(oem_cells_stream *s, const oem_aln_record *re
                                    const uint8_t *barcodes, const uint64_t *barcode_off,
                                    const uint8_t *names, const uint64_t *name_off,
                                    const uint8_t *secondary /* or NULL */, uint64_t *out_ticket);
+/* The ANY-ORDER form of the barcoded session: oem_em_run_cells_records_barcodes_sparse for a caller that never holds
+ * the whole input -- a coordinate-sorted single-cell BAM read buffer by buffer, which the collated session above cannot
+ * take.  Same preconditions and errors as oem_cells_stream_set_barcodes (a fresh records session only; a mode that is
+ * neither value: OEM_ERR_ARG; on a plain session, after a push, after finish, or after either set_barcodes call:
+ * OEM_ERR_STATE -- and oem_cells_stream_set_barcodes on such a session returns OEM_ERR_STATE too).  Batches arrive
+ * through oem_cells_stream_push_barcodes, results leave through oem_cells_stream_finish, _barcodes_dims and
+ * _barcodes_copy, all unchanged.
+ *
+ * The rule (oarfish_amd/csrc/oem_collate.h, "Cells from a stream in any order"): unmapped records take no part and
+ * their bytes are never examined; a survivor's barcode and name are not empty and hold no 0 byte; a cell is the set of
+ * survivors with one barcode, compared as bytes; cells are numbered by their first survivor, and a barcode that comes
+ * back is the SAME cell; inside a cell the survivors keep session order and the name rule (mode) is then applied.
+ * With S the survivors' indices, ascending, finish gives exactly what oem_em_run_cells_records_barcodes_sparse gives on
+ * records[S], barcodes[S], names[S], secondary[S], however the input was cut and whichever thread pushed what:
+ * cell_rec_off, group_off, cell_group_off, kept, the discard tables, the entries' offsets and columns, the labels in
+ * cell order, and order as S[order of the one call]; values and infos as a session is held to its one call.
+ *
+ * Per batch the survivors' barcodes are interned on the device against a hash table of the labels seen so far, and
+ * the arena keeps a 4-byte cell id per survivor instead of its barcode.  NOTHING RUNS BEFORE finish, because any
+ * barcode may return: finish finds the cells with one stable integer sort of the cell ids, lays the arena out by cell
+ * and runs the cells in groups as the collated session does (OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH stays 0).
+ * The arena therefore holds every survivor until finish: its records, names, flags, 64-bit indices and cell ids
+ * (OEM_CELLS_STREAM_INFO_ARENA_BYTES).  Device-found errors are sticky, worded as the collated session's with "ticket
+ * <t>" and the session-global index: a bad barcode or name; a ref_id not below n_txps, checked per batch; more than
+ * 2^31 - 2 survivors in the session, refused at the batch that crosses (OEM_ERR_ARG); OEM_ERR_OOM with everything
+ * released. */
+int oem_cells_stream_set_barcodes_any_order(oem_cells_stream *s, uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */);
 /* After a successful oem_cells_stream_finish of a barcoded session (otherwise OEM_ERR_STATE): the sizes of what
  * oem_cells_stream_barcodes_copy gives (each may be NULL) -- the cells, the survivors, the reads (record groups) of all
  * cells, the bytes of all labels, and the unmapped records that were skipped. */

@@ -37,6 +37,9 @@ OEM_CELLS_STREAM_INFO_GROUPS = 3
 OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH = 4
 OEM_CELLS_STREAM_INFO_BLOCKED_US = 5
 OEM_CELLS_STREAM_INFO_GROUPS_BATCHED = 6
+OEM_CELLS_STREAM_INFO_ARENA_BYTES = 7
+OEM_CELLS_STREAM_INFO_BARCODE_MISSES = 8
+OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS = 9
 OEM_RECORDS_STREAM_INFO_BATCHES = 1
 OEM_RECORDS_STREAM_INFO_GROUPS = 2
 OEM_RECORDS_STREAM_INFO_RECORDS = 3
@@ -79,7 +82,7 @@ ABI_SYMBOLS = [
     "oem_em_run_cells_records_names_sparse", "oem_collate_barcodes", "oem_em_run_cells_records_barcodes_sparse",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_set_barcodes", "oem_cells_stream_push_barcodes", "oem_cells_stream_barcodes_dims",
-    "oem_cells_stream_barcodes_copy",
+    "oem_cells_stream_barcodes_copy", "oem_cells_stream_set_barcodes_any_order",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
     "oem_records_stream_destroy", "oem_records_stream_set_names", "oem_records_stream_push_names",
@@ -258,6 +261,7 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
     L.oem_cells_stream_push_records.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.oem_cells_stream_set_barcodes.argtypes = [vp, u32]
+    L.oem_cells_stream_set_barcodes_any_order.argtypes = [vp, u32]
     L.oem_cells_stream_push_barcodes.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.oem_cells_stream_barcodes_dims.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.oem_cells_stream_barcodes_copy.argtypes = [vp] * 8
@@ -335,6 +339,7 @@ def testing_lib() -> C.CDLL:
         L.oem_test_collate_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, vp, C.POINTER(u64), vp]
         L.oem_debug_collate_barcodes_last_call.argtypes = [vp]
         L.oem_debug_cells_barcodes_last_call.argtypes = [vp]
+        L.oem_debug_barcode_table_last.argtypes = [vp]
         L.oem_test_collate_barcodes_host.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]

@@ -1,7 +1,7 @@
 // oem_cells_barcodes_stream.h -- what the per-cell session (oem_cells_stream.hip) and its barcoded form
 // (oem_cells_barcodes_stream.hip) share: what a group leaves for the session's result, what the barcoded part asks of
 // the session it belongs to, and the calls between the two.  The rule is oem_collate.h's "Cells from a barcode-collated
-// stream".
+// stream" or, for the any-order form (oem_cells_barcodes_sort_stream.hip), "Cells from a stream in any order".
 #pragma once
 
 #include <functional>
@@ -10,6 +10,7 @@
 
 #include "oem_cells.h"
 #include "oem_collate.h"
+#include "oem_collate_device.h"
 #include "oem_filter_device.h"
 
 namespace oem {
@@ -42,8 +43,44 @@ struct BarcodesEnv {
     std::function<void(uint64_t)> add_blocked_us;
 };
 
+// The any-order session's table of the labels seen so far, on the device (oem_cells_barcodes_sort_stream.hip,
+// oem_barcode_table.h): its slots, the label blob in id order (zero-padded by 16) with its offsets, and what it counts.
+// Everything runs on the null stream and leaves it idle.
+struct BarcodeIntern {
+    DevBuf<uint32_t> slot;
+    DevBuf<uint8_t> labels;
+    DevBuf<uint64_t> label_off;
+    DevBuf<unsigned long long> stats; // the kernels' words: the longest probe, a probe wrapped, an error
+    uint64_t capacity = 0, n_labels = 0, label_bytes = 0, label_cap = 0, byte_cap = 0;
+    uint32_t hash_bits = 64;
+    uint64_t misses = 0, rebuilds = 0, max_doublings = 0, longest_probe = 0;
+    bool wrapped = false;
+
+    int init(); // the first capacity (the testing library: OEM_BARCODE_TABLE_SLOTS0, OEM_BARCODE_HASH_BITS)
+    void release();
+    // One batch: its m survivors' barcodes as a dense checked blob (8-byte aligned, padded by 16) with m + 1 offsets
+    // from 0 -> d_cell_id[0 .. m), the cells' numbers.  New labels are numbered by their first survivor.
+    int batch(const char *who, const uint8_t *d_bc, const uint64_t *d_bc_off, uint64_t m, uint32_t *d_cell_id);
+    // finish: order_bc and cell_rec_off of n > 0 survivors from their cell ids, by one stable radix sort
+    int cells(const uint32_t *d_cell_id, uint64_t n, BarcodeCells *out);
+    int labels_down(std::vector<uint8_t> *out_labels, std::vector<uint64_t> *out_label_off);
+    uint64_t device_bytes() const { return capacity * sizeof(uint32_t) + (label_cap + 1) * sizeof(uint64_t) + byte_cap + 16; }
+    void publish_last() const; // what oem_debug_barcode_table_last reports
+    int reserve_labels(uint64_t n_need, uint64_t bytes_need);
+    int check_stats(const char *who);
+};
+// the last finished any-order session's table (8 words): [0] rebuilds, [1] the longest probe, [2] a probe wrapped past the
+// table's end, [3] the most doublings one rebuild covered, [4] the final capacity, [5] labels, [6] misses
+void barcode_table_last(uint64_t *out8);
+// *bad = the smallest i = d_order[k], k < m, whose record's ref_id is not below n_txps, or kNoRecord
+int cells_ref_check(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, uint32_t n_txps, uint64_t *bad);
+
 struct BarcodesStream;
-int barcodes_stream_create(const BarcodesEnv &env, BarcodesStream **out);
+// any_order: oem_collate.h's "Cells from a stream in any order" instead of "Cells from a barcode-collated stream"
+int barcodes_stream_create(const BarcodesEnv &env, bool any_order, BarcodesStream **out);
+// what oem_cells_stream_info reports of an any-order session (0 for a collated one): the arena's peak in bytes, the
+// survivors that missed the first lookup of their batch, the table's capacity
+void barcodes_stream_table_info(BarcodesStream *b, uint64_t *arena_peak, uint64_t *misses, uint64_t *slots);
 // oem_cells_stream_push_barcodes behind its NULL-session check
 int barcodes_stream_push(BarcodesStream *b, const char *who, const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
                          const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary,

@@ -29,6 +29,12 @@
 //             run_cells_group.  A group whose filter must take the host loop takes it (records_group_host).
 //   finish    the staged batches are parsed, the open cell closes, the rest of the arena is run; the groups' pieces --
 //             order, group_off, cell_group_off, kept -- and the labels are joined on the host.
+//
+// The ANY-ORDER form (oem_cells_stream_set_barcodes_any_order; oem_collate.h, "Cells from a stream in any order") shares
+// push, staging, parse worker, arena and groups.  Its batches are not cut: their survivors' barcodes are interned
+// (BarcodeIntern, oem_cells_barcodes_sort_stream.hip) and the arena keeps a cell id per survivor; nothing is handed to the
+// workers before finish, which sorts the survivors by cell id, lays the arena out in that order (finish_any_order) and
+// then makes the last cut of a collated arena whose cells are all closed.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -141,12 +147,26 @@ struct Arena {
     DevBuf<oem_aln_record> rec;
     DevBuf<uint8_t> names, sec;
     DevBuf<uint64_t> name_off, gidx;
+    DevBuf<uint32_t> cell_id; // an any-order session: the survivors' cells
     uint64_t cap = 0, cap_bytes = 0;
+    uint64_t device_bytes(bool with_ids) const
+    {
+        return cap * (sizeof(oem_aln_record) + 2 * sizeof(uint64_t) + 1 + (with_ids ? sizeof(uint32_t) : 0)) + cap_bytes + 32;
+    }
 };
 
-int arena_make(uint64_t cap, uint64_t cap_bytes, std::shared_ptr<Arena> *out)
+// dst[k] = src[at[k]] over n entries
+__global__ __launch_bounds__(kBT) void k_sample64(uint64_t n, const uint64_t *__restrict__ at, const uint64_t *__restrict__ src,
+                                                   uint64_t *__restrict__ dst)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
+    if (k < n) dst[k] = src[at[k]];
+}
+
+int arena_make(uint64_t cap, uint64_t cap_bytes, bool with_ids, std::shared_ptr<Arena> *out)
 {
     std::shared_ptr<Arena> a(new Arena());
+    if (with_ids) OEM_TRY(dev_alloc(&a->cell_id.p, cap, nullptr));
     OEM_TRY(dev_alloc(&a->rec.p, cap, nullptr));
     OEM_TRY(dev_alloc(&a->names.p, cap_bytes + 16, nullptr));
     OEM_TRY(dev_alloc(&a->sec.p, cap + 8, nullptr));
@@ -237,6 +257,11 @@ struct BarcodesStream {
     std::vector<uint8_t> labels;               // every opened cell's barcode, in cell order
     std::vector<uint64_t> label_off{0};
     std::deque<std::unique_ptr<Slot>> slots;   // by group (mu: the deque itself; a slot is its group's alone)
+    // an any-order session (oem_cells_barcodes_sort_stream.hip): the table of the labels seen so far; the arena keeps a
+    // cell id per survivor and nothing is cut before finish
+    bool any_order = false;
+    BarcodeIntern intern;
+    uint64_t arena_peak = 0, info_misses = 0, info_slots = 0; // (mu) as of the last batch, for oem_cells_stream_info
 
     // -- what finish leaves ------------------------------------------------------------------------------------------------
     bool assembled = false;
@@ -268,7 +293,17 @@ struct BarcodesStream {
         return (uint64_t)(std::upper_bound(ticket_base.begin(), ticket_base.end(), record) - ticket_base.begin()) - 1;
     }
 
+    void note_arena_bytes(uint64_t held)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        arena_peak = std::max(arena_peak, held);
+    }
     int arena_reserve(uint64_t need, uint64_t need_bytes);
+    int arena_append(const Batch &b, uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, const uint8_t *d_dnames,
+                     const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id);
+    int intern_batch(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_order, uint64_t m, const uint8_t *d_dbc,
+                     const uint64_t *d_dbc_off, DevBuf<uint32_t> *d_cell_id);
+    int finish_any_order(const char *who);
     int run_batch(const Batch &b);
     int cut_groups(bool final);
     int run_group(const std::shared_ptr<Arena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot, StreamGroupResult *out,
@@ -284,7 +319,10 @@ int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes)
     while (cap < need) cap = std::max(cap * 2, need);
     while (cap_bytes < need_bytes) cap_bytes = std::max(cap_bytes * 2, need_bytes);
     std::shared_ptr<Arena> na;
-    OEM_TRY(arena_make(cap, cap_bytes, &na));
+    OEM_TRY(arena_make(cap, cap_bytes, any_order, &na));
+    note_arena_bytes((arena ? arena->device_bytes(any_order) : 0) + na->device_bytes(any_order)); // (a growing array is held twice)
+    if (arena && arena_n && any_order)
+        OEM_HIP(hipMemcpy(na->cell_id.p, arena->cell_id.p, sizeof(uint32_t) * arena_n, hipMemcpyDeviceToDevice));
     if (arena && arena_n) {
         OEM_HIP(hipMemcpy(na->rec.p, arena->rec.p, sizeof(oem_aln_record) * arena_n, hipMemcpyDeviceToDevice));
         OEM_HIP(hipMemcpy(na->names.p, arena->names.p, arena_bytes, hipMemcpyDeviceToDevice));
@@ -293,6 +331,91 @@ int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes)
         OEM_HIP(hipMemcpy(na->gidx.p, arena->gidx.p, sizeof(uint64_t) * arena_n, hipMemcpyDeviceToDevice));
     }
     arena = std::move(na);
+    return OEM_OK;
+}
+
+// The batch's m survivors into the arena: records, names, flags, session-global indices and (an any-order session)
+// cell ids.  arena_n and arena_bytes are the caller's to advance.
+int BarcodesStream::arena_append(const Batch &b, uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, const uint8_t *d_dnames,
+                                 const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id)
+{
+    OEM_TRY(arena_reserve(arena_n + m, arena_bytes + dname_bytes));
+    Arena &a = *arena;
+    OEM_TRY(records_gather(m, d_order, d_in, a.rec.p + arena_n));
+    if (dname_bytes) OEM_HIP(hipMemcpyAsync(a.names.p + arena_bytes, d_dnames, dname_bytes, hipMemcpyDeviceToDevice, nullptr));
+    hipLaunchKernelGGL(k_offsets_shift, grid_of(m + 1), dim3(kBT), 0, nullptr, m + 1, d_dname_off, arena_bytes, a.name_off.p + arena_n);
+    OEM_HIP(hipGetLastError());
+    if (d_dsec) OEM_HIP(hipMemcpyAsync(a.sec.p + arena_n, d_dsec, m, hipMemcpyDeviceToDevice, nullptr));
+    else OEM_HIP(hipMemsetAsync(a.sec.p + arena_n, 0, m, nullptr));
+    hipLaunchKernelGGL(k_global_index, grid_of(m), dim3(kBT), 0, nullptr, m, d_order, b.rec_base, a.gidx.p + arena_n);
+    OEM_HIP(hipGetLastError());
+    if (d_cell_id) OEM_HIP(hipMemcpyAsync(a.cell_id.p + arena_n, d_cell_id, sizeof(uint32_t) * m, hipMemcpyDeviceToDevice, nullptr));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
+
+// An any-order session's batch behind its name checks: the ref_ids while the batch still knows its ticket, the bound on
+// the survivors (finish collates them as one batch), then the cells of the m survivors from the table.
+int BarcodesStream::intern_batch(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_order, uint64_t m,
+                                 const uint8_t *d_dbc, const uint64_t *d_dbc_off, DevBuf<uint32_t> *d_cell_id)
+{
+    uint64_t bad = kNoRecord;
+    OEM_TRY(cells_ref_check(m, d_order, d_in, env.n_txps, &bad));
+    if (bad != kNoRecord) {
+        const oem_aln_record *h = (const oem_aln_record *)b.base();
+        return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)(b.rec_base + bad), h[bad].ref_id);
+    }
+    if (arena_n + m > kCollateMaxBatch)
+        return fail(OEM_ERR_ARG, "%s: more than 2^31 - 2 surviving records in the session: its cells are found by one sort at finish", who);
+    OEM_TRY(dev_alloc(&d_cell_id->p, m, nullptr));
+    OEM_TRY(intern.batch(who, d_dbc, d_dbc_off, m, d_cell_id->p));
+    std::lock_guard<std::mutex> lk(mu);
+    info_misses = intern.misses;
+    info_slots = intern.capacity;
+    return OEM_OK;
+}
+
+// An any-order session's finish, after the parse worker's end and before the last cut: the survivors sorted by cell id,
+// the arena laid out in that order -- from here on it is a collated session's arena whose cells are all closed -- and
+// the labels down.
+int BarcodesStream::finish_any_order(const char *who)
+{
+    intern.publish_last();
+    const uint64_t m = arena_n;
+    if (m == 0) {
+        intern.release();
+        return OEM_OK;
+    }
+    BarcodeCells bc;
+    OEM_TRY(intern.cells(arena->cell_id.p, m, &bc));
+    OEM_TRY(intern.labels_down(&labels, &label_off));
+    intern.release();
+    const uint64_t nc = bc.n_cells;
+    std::shared_ptr<Arena> na;
+    OEM_TRY(arena_make(m, arena_bytes, false, &na));
+    note_arena_bytes(arena->device_bytes(true) + na->device_bytes(false));
+    Arena &a = *arena;
+    OEM_HIP(hipMemset(a.names.p + arena_bytes, 0, 16));
+    OEM_HIP(hipMemset(a.sec.p + m, 0, 8));
+    OEM_TRY(records_gather(m, bc.order.p, a.rec.p, na->rec.p));
+    OEM_TRY(gather_name_offsets(bc.order.p, m, a.name_off.p, na->name_off.p));
+    OEM_TRY(gather_names(bc.order.p, m, a.names.p, a.name_off.p, na->name_off.p, 0, arena_bytes, na->names.p, a.sec.p, na->sec.p));
+    hipLaunchKernelGGL(k_order_compose64, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)bc.order.p, (const uint64_t *)a.gidx.p,
+                       na->gidx.p);
+    OEM_HIP(hipGetLastError());
+    // the cells: their first survivors and first name bytes
+    DevBuf<uint64_t> d_cbyte;
+    OEM_TRY(dev_alloc(&d_cbyte.p, nc, nullptr));
+    hipLaunchKernelGGL(k_sample64, grid_of(nc), dim3(kBT), 0, nullptr, nc, (const uint64_t *)bc.cell_rec_off.p, (const uint64_t *)na->name_off.p,
+                       d_cbyte.p);
+    OEM_HIP(hipGetLastError());
+    cstart.assign(nc, 0);
+    cbyte.assign(nc, 0);
+    OEM_HIP(hipMemcpy(cstart.data(), bc.cell_rec_off.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
+    OEM_HIP(hipMemcpy(cbyte.data(), d_cbyte.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
+    first_cell = 0;
+    arena = std::move(na);
+    (void)who;
     return OEM_OK;
 }
 
@@ -350,6 +473,18 @@ int BarcodesStream::run_batch(const Batch &b)
     d_names.reset();
     d_name_off.reset();
 
+    if (any_order) { // the survivors' cells from the table; the arena takes them with their cell ids, and nothing is cut
+        DevBuf<uint32_t> d_cell_id;
+        OEM_TRY(intern_batch(b, who, d_in.p, d_order.p, m, d_dbc.p, d_dbc_off.p, &d_cell_id));
+        d_dbc.reset();
+        d_dbc_off.reset();
+        OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, d_cell_id.p));
+        arena_n += m;
+        arena_bytes += dname_bytes;
+        n_survivors += m;
+        return OEM_OK;
+    }
+
     // the heads and the batch's cell starts
     DevBuf<uint32_t> d_head, d_start;
     DevBuf<uint64_t> d_at, d_start_byte;
@@ -395,19 +530,7 @@ int BarcodesStream::run_batch(const Batch &b)
     d_dbc.reset();
     d_dbc_off.reset();
 
-    // the survivors into the arena: records, names, flags, session-global indices
-    OEM_TRY(arena_reserve(arena_n + m, arena_bytes + dname_bytes));
-    Arena &a = *arena;
-    OEM_TRY(records_gather(m, d_order.p, d_in.p, a.rec.p + arena_n));
-    if (dname_bytes) OEM_HIP(hipMemcpyAsync(a.names.p + arena_bytes, d_dnames.p, dname_bytes, hipMemcpyDeviceToDevice, nullptr));
-    hipLaunchKernelGGL(k_offsets_shift, grid_of(m + 1), dim3(kBT), 0, nullptr, m + 1, (const uint64_t *)d_dname_off.p, arena_bytes,
-                       a.name_off.p + arena_n);
-    OEM_HIP(hipGetLastError());
-    if (d_dsec.p) OEM_HIP(hipMemcpyAsync(a.sec.p + arena_n, d_dsec.p, m, hipMemcpyDeviceToDevice, nullptr));
-    else OEM_HIP(hipMemsetAsync(a.sec.p + arena_n, 0, m, nullptr));
-    hipLaunchKernelGGL(k_global_index, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_order.p, b.rec_base, a.gidx.p + arena_n);
-    OEM_HIP(hipGetLastError());
-    OEM_HIP(hipStreamSynchronize(nullptr));
+    OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, nullptr));
     for (uint64_t j = 0; j < nh; ++j) {
         cstart.push_back(arena_n + start[j]);
         cbyte.push_back(arena_bytes + start_byte[j]);
@@ -493,7 +616,7 @@ int BarcodesStream::cut_groups(bool final)
     arena.reset();
     if (!final) {
         const uint64_t cap = std::max(tail_n, std::min(old->cap, 2 * env.group_nnz)) + 4096;
-        OEM_TRY(arena_make(cap, std::max(tail_bytes, std::min<uint64_t>(old->cap_bytes, 64 * cap)) + 4096, &arena));
+        OEM_TRY(arena_make(cap, std::max(tail_bytes, std::min<uint64_t>(old->cap_bytes, 64 * cap)) + 4096, false, &arena));
         if (tail_n) {
             OEM_HIP(hipMemcpyAsync(arena->rec.p, old->rec.p + t, sizeof(oem_aln_record) * tail_n, hipMemcpyDeviceToDevice, nullptr));
             if (tail_bytes) OEM_HIP(hipMemcpyAsync(arena->names.p, old->names.p + tb, tail_bytes, hipMemcpyDeviceToDevice, nullptr));
@@ -649,6 +772,7 @@ void BarcodesStream::work()
                 msg = last_error_text();
                 arena.reset();
                 carry.reset();
+                intern.release();
                 set_stuck(rc, msg.c_str());
             }
         }
@@ -665,10 +789,24 @@ void BarcodesStream::work()
     }
 }
 
-int barcodes_stream_create(const BarcodesEnv &env, BarcodesStream **out)
+void barcodes_stream_table_info(BarcodesStream *b, uint64_t *arena_peak, uint64_t *misses, uint64_t *slots)
+{
+    std::lock_guard<std::mutex> lk(b->mu);
+    *arena_peak = b->any_order ? b->arena_peak : 0;
+    *misses = b->any_order ? b->info_misses : 0;
+    *slots = b->any_order ? b->info_slots : 0;
+}
+
+int barcodes_stream_create(const BarcodesEnv &env, bool any_order, BarcodesStream **out)
 {
     std::unique_ptr<BarcodesStream> b(new BarcodesStream());
     b->env = env;
+    b->any_order = any_order;
+    if (any_order) {
+        OEM_HIP(hipSetDevice(env.device));
+        OEM_TRY(b->intern.init());
+        b->info_slots = b->intern.capacity;
+    }
     BarcodesStream *raw = b.get();
     b->worker = std::thread([raw] { raw->work(); });
     *out = b.release();
@@ -806,12 +944,14 @@ int barcodes_stream_close(BarcodesStream *b, const char *who)
     int rc2 = OEM_OK;
     try {
         OEM_HIP(hipSetDevice(b->env.device));
-        rc2 = b->cut_groups(true); // the open cell closes with the session
+        if (b->any_order) rc2 = b->finish_any_order(who); // the cells, at last: the arena becomes a collated one
+        if (rc2 == OEM_OK) rc2 = b->cut_groups(true);     // the open cell closes with the session
     } catch (const std::bad_alloc &) {
         rc2 = fail(OEM_ERR_OOM, "%s: host allocation failed", who);
     }
     b->arena.reset(); // (the groups hold it)
     b->carry.reset();
+    b->intern.release();
     if (rc2 != OEM_OK) {
         const std::string m2 = last_error_text();
         b->set_stuck(rc2, m2.c_str());

@@ -25,7 +25,9 @@
 //
 // A BARCODED session (oem_cells_stream_set_barcodes, oem_cells_stream_push_barcodes) takes batches of records cut at any
 // position and finds the cells itself (oem_cells_barcodes_stream.hip).  Nothing of it is staged here: its groups come
-// from its device arena as closures (Group::dev_run) that the same two workers run, in the same result slots.
+// from its device arena as closures (Group::dev_run) that the same two workers run, in the same result slots.  Its
+// ANY-ORDER form (oem_cells_stream_set_barcodes_any_order, oem_cells_barcodes_sort_stream.hip) is the same session under
+// another rule: a barcode that comes back is the same cell, so its groups come only at finish.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -648,10 +650,10 @@ extern "C" int oem_cells_stream_push_records(oem_cells_stream *s, const oem_aln_
     return s->push_cell(who, true, a, n_groups, group_off[n_groups], out_ticket);
 }
 
-extern "C" int oem_cells_stream_set_barcodes(oem_cells_stream *s, uint32_t mode)
+// oem_cells_stream_set_barcodes and oem_cells_stream_set_barcodes_any_order: the same preconditions, the same session
+// behind them; any_order chooses the rule the batches' cells are found by.
+static int set_barcodes(oem_cells_stream *s, const char *who, uint32_t mode, bool any_order)
 {
-    OEM_API_BEGIN
-    const char *who = "oem_cells_stream_set_barcodes";
     if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
     if (mode != kCollateSort && mode != kCollateAdjacent)
         return fail(OEM_ERR_ARG, "%s: mode must be OEM_COLLATE_SORT or OEM_COLLATE_ADJACENT", who);
@@ -693,8 +695,21 @@ extern "C" int oem_cells_stream_set_barcodes(oem_cells_stream *s, uint32_t mode)
         std::lock_guard<std::mutex> lk2(s->mu);
         s->blocked_us += us;
     };
-    return barcodes_stream_create(env, &s->bc);
+    return barcodes_stream_create(env, any_order, &s->bc);
+}
+
+extern "C" int oem_cells_stream_set_barcodes(oem_cells_stream *s, uint32_t mode)
+{
+    OEM_API_BEGIN
+    return set_barcodes(s, "oem_cells_stream_set_barcodes", mode, false);
     OEM_API_END("oem_cells_stream_set_barcodes")
+}
+
+extern "C" int oem_cells_stream_set_barcodes_any_order(oem_cells_stream *s, uint32_t mode)
+{
+    OEM_API_BEGIN
+    return set_barcodes(s, "oem_cells_stream_set_barcodes_any_order", mode, true);
+    OEM_API_END("oem_cells_stream_set_barcodes_any_order")
 }
 
 extern "C" int oem_cells_stream_push_barcodes(oem_cells_stream *s, const oem_aln_record *records, uint64_t n_records,
@@ -785,9 +800,13 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
 {
     if (!s || !value) return fail(OEM_ERR_ARG, "oem_cells_stream_info: NULL argument");
     std::lock_guard<std::mutex> lk(s->mu);
-    uint64_t bc_batches = 0, bc_records = 0;
+    uint64_t bc_batches = 0, bc_records = 0, bc_arena = 0, bc_misses = 0, bc_slots = 0;
     if (s->bc) barcodes_stream_counts(s->bc, &bc_batches, &bc_records);
+    if (s->bc) barcodes_stream_table_info(s->bc, &bc_arena, &bc_misses, &bc_slots);
     switch (key) {
+    case OEM_CELLS_STREAM_INFO_ARENA_BYTES: *value = bc_arena; break; // (an any-order barcoded session; 0 otherwise)
+    case OEM_CELLS_STREAM_INFO_BARCODE_MISSES: *value = bc_misses; break;
+    case OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS: *value = bc_slots; break;
     case OEM_CELLS_STREAM_INFO_CELLS: *value = s->bc ? bc_batches : s->next_ticket; break; // (a barcoded session: batches)
     case OEM_CELLS_STREAM_INFO_ALIGNMENTS: *value = s->bc ? bc_records : s->total_nnz; break;
     case OEM_CELLS_STREAM_INFO_GROUPS: *value = s->groups_started; break;

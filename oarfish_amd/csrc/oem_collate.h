@@ -79,6 +79,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "oem_barcode_table.h"
+
 namespace oem {
 
 enum : uint32_t { kCollateSort = 0, kCollateAdjacent = 1 };
@@ -455,6 +457,94 @@ struct ParseCellsStream {
         n_records += n;
     }
     void finish() { close(); }
+};
+
+// Cells from a stream in any order (ParseCellsAnyOrderStream below, oem_cells_stream_set_barcodes_any_order): the barcode
+// rule at the top of this file ("Cells from barcodes") applied to a session's input, which is its accepted batches
+// concatenated in ticket order; a record's session-global index (64 bits) counts every record of every batch in that
+// order, unmapped ones included.
+//   skip     a record with OEM_REC_UNMAPPED takes no part: its barcode and name bytes are never examined, so they may be
+//            empty or hold a 0 byte.  The other records are the survivors S, ascending.
+//   bytes    a survivor's barcode and name are not empty and hold no 0 byte.
+//   cells    a cell is the set of survivors with one barcode, compared as bytes.  Cells are numbered by their first
+//            survivor in S.  A barcode that comes back is the SAME cell, unlike the collated session above.
+//   inside a cell   the survivors keep session order; the name rule (mode) is then applied as it stands.
+//   result   finish gives exactly what oem_em_run_cells_records_barcodes_sparse gives on records[S], barcodes[S],
+//            names[S], secondary[S], however the input was cut and whichever thread pushed what; `order` is S[order of the
+//            one call], 64 bits wide.
+//   stream   nothing can run before finish, because any barcode may return.  Per batch the barcodes are INTERNED against
+//            the table of the labels seen so far (oem_barcode_table.h): every survivor is looked up; the survivors that
+//            miss are sorted by barcode, the runs' heads ranked by survivor index, and the new labels get the ids
+//            n_labels + rank -- so ids are first-survivor numbers whatever the cut; the table grows to keep its load at
+//            or below 1/2 and takes the new labels; the misses are looked up again.  A survivor keeps its 4-byte cell
+//            id; finish sorts the survivors by id, stably.
+// The walk below does per batch on the host what the device does per batch.
+struct ParseCellsAnyOrderStream {
+    uint64_t n_records = 0, n_unmapped = 0, misses = 0; // misses: survivors that missed the first lookup of their batch
+    std::vector<uint64_t> survivors;                    // S
+    std::vector<uint32_t> cell_id;                      // by survivor
+    BarcodeTableHost table;
+    uint64_t max_batch_rebuilds = 0;
+    // after finish: the survivors' positions in S, cell-major, and the cells' first positions in that order
+    std::vector<uint64_t> order, cell_rec_off;
+
+    explicit ParseCellsAnyOrderStream(uint64_t slots0 = kBarcodeTableSlots0, uint32_t hash_bits = 64) : table(slots0, hash_bits) {}
+
+    template <typename Rec>
+    void push(const Rec *records, uint64_t n, const uint8_t *barcodes, const uint64_t *barcode_off)
+    {
+        std::vector<uint64_t> at; // the batch's survivors, as batch indices
+        for (uint64_t i = 0; i < n; ++i) {
+            if (records[i].flags & kRecUnmapped) ++n_unmapped;
+            else at.push_back(i);
+        }
+        auto bc = [&](uint64_t i) { return barcodes + barcode_off[i]; };
+        auto len = [&](uint64_t i) { return barcode_off[i + 1] - barcode_off[i]; };
+        // 1. the lookup, against the table as the batch finds it
+        const size_t base = cell_id.size();
+        std::vector<uint64_t> miss; // positions in `at`
+        for (size_t k = 0; k < at.size(); ++k) {
+            cell_id.push_back(table.find(bc(at[k]), len(at[k])));
+            survivors.push_back(n_records + at[k]);
+            if (cell_id.back() == kBarcodeEmpty) miss.push_back(k);
+        }
+        misses += miss.size();
+        if (!miss.empty()) {
+            // 2. the distinct barcodes among the misses, numbered by their first survivor
+            std::vector<uint64_t> sorted = miss;
+            std::stable_sort(sorted.begin(), sorted.end(), [&](uint64_t a, uint64_t b) {
+                return collate_name_cmp(bc(at[a]), len(at[a]), bc(at[b]), len(at[b])) < 0;
+            });
+            std::vector<uint64_t> heads; // a run's head is its first member: its smallest, the sort being stable
+            for (size_t p = 0; p < sorted.size(); ++p)
+                if (p == 0 || collate_name_cmp(bc(at[sorted[p - 1]]), len(at[sorted[p - 1]]), bc(at[sorted[p]]), len(at[sorted[p]])) != 0)
+                    heads.push_back(sorted[p]);
+            std::sort(heads.begin(), heads.end());
+            const uint64_t first_new = table.n_labels();
+            for (uint64_t h : heads) {
+                table.labels.insert(table.labels.end(), bc(at[h]), bc(at[h]) + len(at[h]));
+                table.label_off.push_back(table.labels.size());
+            }
+            // 3. / 4. the table grows if it must and takes the new labels
+            const uint64_t before = table.rebuilds;
+            table.add_from(first_new);
+            max_batch_rebuilds = std::max(max_batch_rebuilds, table.rebuilds - before);
+            // 5. the misses again
+            for (uint64_t k : miss) cell_id[base + k] = table.find(bc(at[k]), len(at[k]));
+        }
+        n_records += n;
+    }
+    uint64_t n_cells() const { return table.n_labels(); }
+    void finish()
+    {
+        const uint64_t m = cell_id.size(), nc = n_cells();
+        cell_rec_off.assign(nc + 1, 0);
+        for (uint64_t k = 0; k < m; ++k) ++cell_rec_off[cell_id[k] + 1];
+        for (uint64_t c = 0; c < nc; ++c) cell_rec_off[c + 1] += cell_rec_off[c];
+        std::vector<uint64_t> next(cell_rec_off.begin(), cell_rec_off.end() - 1);
+        order.assign(m, 0);
+        for (uint64_t k = 0; k < m; ++k) order[next[cell_id[k]]++] = k; // stable: session order inside a cell
+    }
 };
 
 } // namespace oem

@@ -59,6 +59,11 @@ struct BarcodeCells {
 // the cells' kernels in ms under `timing`.  Returns with the device idle.
 int collate_barcodes_resident(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, bool timing,
                               double *info, double *cells_ms, BarcodeCells *out);
+// The same on barcodes that are on the device already and checked (the misses of a batch of the any-order barcoded
+// session, oem_cells_barcodes_sort_stream.hip): a dense blob, 8-byte aligned and padded by 16, with its n_records + 1
+// offsets from 0.  out_heads (or NULL): the cells' first records, ascending -- cell c's label is that record's barcode.
+int collate_barcodes_device(const char *who, const uint8_t *d_barcodes, const uint64_t *d_barcode_off, uint64_t n_bytes, uint64_t n_records,
+                            BarcodeCells *out, DevBuf<uint32_t> *out_heads);
 // The argument checks of oem_collate_barcodes on the input side, before any device use.
 int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records);
 

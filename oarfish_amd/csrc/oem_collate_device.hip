@@ -738,15 +738,15 @@ int gather_names(const uint32_t *d_order, uint64_t m, const uint8_t *d_names, co
     return OEM_OK;
 }
 
-int collate_barcodes_resident(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, bool timing,
-                              double *info, double *cells_ms, BarcodeCells *out)
+namespace {
+
+// The barcodes as one cell through the key rounds (cc: the host or the device form of the input), then the runs ranked by
+// their first record and laid out in that rank.  out_heads (or NULL): the cells' first records, ascending.
+int barcode_cells_of(CollateInput &cc, uint64_t n, bool timing, double *info, double *cells_ms, BarcodeCells *out,
+                     DevBuf<uint32_t> *out_heads)
 {
-    const uint64_t n = n_records, one_cell[2] = {0, n};
-    CollateInput cc;
-    cc.who = who;
+    const uint64_t one_cell[2] = {0, n};
     cc.what = "barcode";
-    cc.names = barcodes;
-    cc.name_off = barcode_off;
     cc.cell_rec_off = one_cell;
     cc.mode = kCollateSort;
     cc.chunk_bytes = collate_chunk_bytes();
@@ -792,7 +792,32 @@ int collate_barcodes_resident(const char *who, const uint8_t *barcodes, const ui
     std::swap(out->order.p, d_order_bc.p);
     std::swap(out->cell_rec_off.p, d_cro.p);
     out->n_cells = n_runs;
+    if (out_heads) std::swap(out_heads->p, d_head_s.p);
     return OEM_OK;
+}
+
+} // namespace
+
+int collate_barcodes_resident(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, bool timing,
+                              double *info, double *cells_ms, BarcodeCells *out)
+{
+    CollateInput cc;
+    cc.who = who;
+    cc.names = barcodes;
+    cc.name_off = barcode_off;
+    return barcode_cells_of(cc, n_records, timing, info, cells_ms, out, nullptr);
+}
+
+int collate_barcodes_device(const char *who, const uint8_t *d_barcodes, const uint64_t *d_barcode_off, uint64_t n_bytes, uint64_t n_records,
+                            BarcodeCells *out, DevBuf<uint32_t> *out_heads)
+{
+    CollateInput cc;
+    cc.who = who;
+    cc.d_names = d_barcodes;
+    cc.d_name_off = d_barcode_off;
+    cc.d_n_bytes = n_bytes;
+    double info[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ms = 0;
+    return barcode_cells_of(cc, n_records, false, info, &ms, out, out_heads);
 }
 
 int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records)

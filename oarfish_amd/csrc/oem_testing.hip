@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "oem_cells.h"
+#include "oem_cells_barcodes_stream.h"
 #include "oem_collate.h"
 #include "oem_collate_device.h"
 #include "oem_shortest_f64.h"
@@ -193,6 +194,15 @@ extern "C" int oem_debug_cells_barcodes_last_call(double *out)
 {
     if (!out) return fail(OEM_ERR_ARG, "oem_debug_cells_barcodes_last_call: NULL argument");
     cells_barcodes_last_call(out);
+    return OEM_OK;
+}
+// Test hook: the barcode table of the last any-order barcoded session that reached finish in this library (8 words):
+// [0] rebuilds, [1] the longest probe in slots, [2] 1 when a probe went past the table's end, [3] the most doublings one
+// rebuild covered (above 1: several inside one batch), [4] the final capacity, [5] labels, [6] misses.
+extern "C" int oem_debug_barcode_table_last(uint64_t *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_barcode_table_last: NULL argument");
+    barcode_table_last(out);
     return OEM_OK;
 }
 

@@ -578,11 +578,20 @@ class CellsStream:
     runs the closed cells in groups while later batches arrive.  ``mode`` is ``collate_names``' (applied inside every
     cell).  ``finish()`` returns the usual four values -- what ``em_cells_records_sparse(names=, collate="device")`` gives
     for the surviving records with the cells the barcodes cut -- and ``cells()`` what the session found.
+
+    ``collated=False`` (with ``barcodes=True``) is the ANY-ORDER barcoded session
+    (``oem_cells_stream_set_barcodes_any_order``): the batches' records come in any order, a barcode that comes back is
+    the same cell, and cells are numbered by their first surviving record.  Every batch's barcodes are interned on the
+    device against a table of the labels seen so far; nothing runs before ``finish()``, which gives exactly what
+    ``em_cells_records_sparse(..., barcodes=, collate="device")`` gives on the surviving records.  ``info()`` then has
+    ``arena_bytes``, ``barcode_misses`` and ``barcode_table_slots`` (0 on every other session).
     """
 
     def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
                  group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None,
-                 barcodes: bool = False, mode: str = "sort"):
+                 barcodes: bool = False, mode: str = "sort", collated: bool = True):
+        if not collated and not barcodes:
+            raise ValueError("collated=False goes with barcodes=True: only a barcoded session finds its cells itself")
         if barcodes and filters is None:
             raise ValueError("a barcoded session is a records session: it needs filters and txp_len")
         if mode not in _COLLATE_MODES:
@@ -596,6 +605,7 @@ class CellsStream:
         self._tables = None
         self._cells = None
         self._barcoded = bool(barcodes)
+        self._any_order = bool(barcodes) and not collated
         self._device = device
         records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
@@ -626,7 +636,8 @@ class CellsStream:
             try:
                 self.set_filters(F, tl)
                 if barcodes:
-                    self._check(self._L.oem_cells_stream_set_barcodes(self._h, _COLLATE_MODES[mode]))
+                    set_barcodes = self._L.oem_cells_stream_set_barcodes if collated else self._L.oem_cells_stream_set_barcodes_any_order
+                    self._check(set_barcodes(self._h, _COLLATE_MODES[mode]))
             except BaseException:
                 self.close()
                 raise
@@ -798,7 +809,9 @@ class CellsStream:
         keys = dict(cells=_lib.OEM_CELLS_STREAM_INFO_CELLS, alignments=_lib.OEM_CELLS_STREAM_INFO_ALIGNMENTS,
                     groups=_lib.OEM_CELLS_STREAM_INFO_GROUPS,
                     groups_before_finish=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH,
-                    blocked_s=_lib.OEM_CELLS_STREAM_INFO_BLOCKED_US, groups_batched=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BATCHED)
+                    blocked_s=_lib.OEM_CELLS_STREAM_INFO_BLOCKED_US, groups_batched=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BATCHED,
+                    arena_bytes=_lib.OEM_CELLS_STREAM_INFO_ARENA_BYTES, barcode_misses=_lib.OEM_CELLS_STREAM_INFO_BARCODE_MISSES,
+                    barcode_table_slots=_lib.OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS)
         out = {}
         for name, key in keys.items():
             v = C.c_uint64(0)

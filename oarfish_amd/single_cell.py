@@ -32,6 +32,7 @@ class SingleCellArgs:
     group_nnz: int = 0                     # the session's budgets, 0 = the library's defaults
     group_cells: int = 0
     max_staged_records: int = 0
+    collated: bool = True                  # False: the batches' records come in any order (the any-order barcoded session)
     extra_info: dict = field(default_factory=dict)
 
 
@@ -39,7 +40,8 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
                                              args: SingleCellArgs):
     """``get_single_cell_abundances`` for a reader that hands over chunks: ``batches`` is an iterable of ``(records,
     barcodes, names, secondary)`` in input order (``synth.cut_cell_records``' tuples), barcode-collated and cut at any
-    record positions.  Writes `.count.mtx`, `.features.txt`, `.barcodes.txt` (the session's labels, in cell order) and
+    record positions -- or, with ``args.collated=False``, in any order at all (``synth.cut_interleaved_records``' tuples:
+    the any-order barcoded session, whose cells are those of the one barcodes call).  Writes `.count.mtx`, `.features.txt`, `.barcodes.txt` (the session's labels, in cell order) and
     `.meta_info.json` with ``writers.write_single_cell_output_device`` and returns ``(indptr, cols, vals, infos,
     cells)``: the session's result and its ``cells()``."""
     txp_len = np.asarray(txp_lens, dtype=np.uint64)
@@ -49,7 +51,7 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
     with CellsStream(len(txp_len), max_iter=args.max_em_iter, conv_thresh=args.convergence_thresh, coverage=coverage,
                      device=args.device, group_nnz=args.group_nnz, group_cells=args.group_cells,
                      max_staged_nnz=args.max_staged_records, filters=filters, txp_len=txp_len, barcodes=True,
-                     mode=args.mode) as cs:
+                     mode=args.mode, collated=args.collated) as cs:
         for records, barcodes, names, secondary in batches:
             cs.push_batch(records, barcodes, names, secondary)
         indptr, cols, vals, infos = cs.finish()

@@ -737,7 +737,6 @@ def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, un
     an empty batch); 0 and the stream's length are implied.  A cut may fall inside a cell and inside a read.  Returns a
     list of ``(records, barcodes, names, secondary)``, ``barcodes`` and ``names`` as ``(blob, offsets)`` pairs with the
     offsets of each batch from 0.  A pure function of its arguments."""
-    from .builder import REC_UNMAPPED
     from .em import gather_names
     records = np.asarray(records)
     blob, off = np.asarray(names[0], dtype=np.uint8), np.asarray(names[1], dtype=np.int64)
@@ -753,7 +752,31 @@ def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, un
     np.cumsum([len(b) for b in enc], out=cell_off[1:])
     cell_of = np.repeat(np.arange(n_cells), np.diff(cell_rec_off))
     bc_blob, bc_off = gather_names((np.frombuffer(b"".join(enc), dtype=np.uint8), cell_off), cell_of)
-    bc_off = np.asarray(bc_off, dtype=np.int64)
+    return _sprinkle_and_cut(records, blob, off, bc_blob, np.asarray(bc_off, dtype=np.int64), secondary, cuts, unmapped_every)
+
+
+def cut_interleaved_records(records, names, secondary, record_barcodes, cuts, unmapped_every: int = 0):
+    """``interleave_cells``' uncollated input cut into batches for an any-order barcoded session
+    (``CellsStream(barcodes=True, collated=False)``), as ``cut_cell_records`` cuts collated input: ``record_barcodes`` is
+    the ``(blob, offsets)`` pair with one barcode per record that ``interleave_cells`` returns; ``unmapped_every`` and
+    ``cuts`` mean what they mean there.  Returns a list of ``(records, barcodes, names, secondary)``.  A pure function of
+    its arguments."""
+    records = np.asarray(records)
+    blob, off = np.asarray(names[0], dtype=np.uint8), np.asarray(names[1], dtype=np.int64)
+    bc_blob, bc_off = np.asarray(record_barcodes[0], dtype=np.uint8), np.asarray(record_barcodes[1], dtype=np.int64)
+    n = len(records)
+    if len(off) != n + 1 or len(bc_off) != n + 1:
+        raise ValueError("names and record_barcodes need one entry per record")
+    secondary = np.zeros(n, dtype=np.uint8) if secondary is None else np.asarray(secondary, dtype=np.uint8)
+    if len(secondary) != n:
+        raise ValueError("secondary must have one entry per record")
+    return _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unmapped_every)
+
+
+def _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unmapped_every):
+    """the stream of ``cut_cell_records`` / ``cut_interleaved_records`` from one name and one barcode per record"""
+    from .builder import REC_UNMAPPED
+    n = len(records)
     if unmapped_every > 0 and n:   # record i of the input goes to position i + i // k + 1
         pos = np.arange(n) + np.arange(n) // unmapped_every + 1
         total = int(pos[-1]) + 1

@@ -33,6 +33,17 @@ slice with a 10x barcode per record, alternated in one process, --runs repeats (
   (c) today's session path: CellsStream.push_records(records, names=) per cell -- collate_names, the NumPy gather, the push.
 
 With the peak device memory of (a) and (b) and the session's groups_before_finish.
+
+--barcodes-any-order-stream is the leg of the any-order barcoded session
+(profiles/cells_barcodes_any_order_stream_bench.json): the slice with UUID names and a 10x barcode per record, interleaved
+by synth.interleave_cells in both its forms (uniform, blocks), alternated in one process, --runs repeats (five), best to
+worst:
+
+  (a) the session (CellsStream(barcodes=True, collated=False)) from one pushing thread at the two --batch-records sizes;
+  (b) the one barcodes call on the concatenation (em_cells_records_sparse(..., names=, barcodes=, collate="device")).
+
+With the peak device memory of both, the arena's peak and its bytes per survivor, finish's share of the session's time and
+the lookups that missed.  No ratio is promised: the baseline is (b) in the same run.
 """
 import argparse
 import ctypes as C
@@ -317,6 +328,91 @@ def barcodes_stream_leg(args, cr, res, save):
         del rec, blob, off, sec, bc_blob
 
 
+def barcodes_any_order_stream_leg(args, cr, res, save):
+    """The --barcodes-any-order-stream leg (see the module docstring); fills res[how] for both interleave_cells forms."""
+    from oarfish_amd.em import gather_names
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style="uuid", threads=16)
+    cell_bc = synth.make_barcodes(n, "10x")
+    for how in ("uniform", "blocks"):
+        rec, (blob, off), sec, (bc_blob, bc_off), _ = synth.interleave_cells(rec0, names0, sec0, cro, cell_bc, how=how)
+        off, bc_off = np.asarray(off, dtype=np.uint64), np.asarray(bc_off, dtype=np.uint64)
+        m = len(rec)
+        r = res[how] = dict(name_bytes=int(blob.nbytes), record_bytes=int(rec.nbytes), barcode_bytes=int(bc_blob.nbytes))
+        # the one call's input: the survivors (the session skips the unmapped records and numbers a cell by its first
+        # survivor; the one call has no such rule, so it gets what the session keeps)
+        S = np.flatnonzero((rec["flags"] & _lib.REC_UNMAPPED) == 0)
+        r["records"], r["survivors"] = int(m), int(len(S))
+        rec_s, sec_s = rec[S], sec[S]
+        names_s, bc_s = gather_names((blob, off), S), gather_names((bc_blob, bc_off), S)
+
+        def session(batch, upto=m):
+            info = {}
+
+            def go():
+                with oarfish_amd.CellsStream(len(tl), filters=f, txp_len=tl, barcodes=True, collated=False) as cs:
+                    for a in range(0, upto, batch):
+                        b = min(a + batch, upto)
+                        cs.push_batch(rec[a:b], (bc_blob[int(bc_off[a]):int(bc_off[b])], bc_off[a:b + 1] - bc_off[a]),
+                                      (blob[int(off[a]):int(off[b])], off[a:b + 1] - off[a]), sec[a:b])
+                    t0 = time.perf_counter()
+                    out = cs.finish()
+                    info.update(cs.info(), finish_s=time.perf_counter() - t0, n_cells=len(cs.cells()["barcodes"]))
+                return out
+            dt, out = clock(go)
+            return dt, out, info
+
+        def one_call(upto=len(S)):
+            (nb, no), (bb, bo) = names_s, bc_s
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec_s[:upto], None, None, names=(nb[:int(no[upto])], no[:upto + 1]),
+                                                       secondary=sec_s[:upto], barcodes=(bb[:int(bo[upto])], bo[:upto + 1]),
+                                                       collate="device")
+
+        warm = min(len(S), int(cro[min(args.warm_cells, n)]))
+        session(args.batch_records[0], warm)
+        one_call(warm)
+        runs_a, runs_b, shares = {b: [] for b in args.batch_records}, [], {b: [] for b in args.batch_records}
+        for k in range(args.runs):
+            for batch in args.batch_records:
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        dt, got_a, info = session(batch)
+                    r[f"session_{batch}_peak_device_bytes"] = int(pk.peak)
+                    r[f"session_{batch}_info"] = info
+                    r[f"session_{batch}_arena_bytes_per_survivor"] = round(info["arena_bytes"] / max(len(S), 1), 2)
+                else:
+                    dt, got_a, info = session(batch)
+                runs_a[batch].append(dt)
+                shares[batch].append(info["finish_s"] / dt)
+                r[f"session_{batch}_records_per_batch"] = spread(runs_a[batch])
+                r[f"session_{batch}_finish_share"] = [round(min(shares[batch]), 3), round(max(shares[batch]), 3)]
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_b = clock(one_call)
+                r["one_call_peak_device_bytes"] = int(pk.peak)
+                assert info["n_cells"] == n and np.array_equal(got_a[0], got_b[0]) and np.array_equal(got_a[1], got_b[1])
+                ulps = np.abs(got_a[2].view(np.int32).astype(np.int64) - got_b[2].view(np.int32).astype(np.int64))
+                r["max_f32_ulps_session_to_one_call"] = int(ulps.max(initial=0))
+            else:
+                dt, got_b = clock(one_call)
+            runs_b.append(dt)
+            del got_a, got_b
+            r["one_call"] = spread(runs_b)
+            for batch in args.batch_records:
+                r[f"session_{batch}_over_one_call"] = round(min(runs_a[batch]) / min(runs_b), 3)
+            print(f"[bench] {how} run {k}: session " + ", ".join(f"{runs_a[b][-1]:.3f} s at {b}" for b in args.batch_records)
+                  + f", one call {runs_b[-1]:.3f} s", flush=True)
+            save()
+        del rec, blob, off, sec, bc_blob, bc_off, rec_s, sec_s, names_s, bc_s
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=625)
@@ -328,14 +424,17 @@ def main():
     ap.add_argument("--names", action="store_true", help="the leg from names and records in input order")
     ap.add_argument("--barcodes", action="store_true", help="the leg from records in any order: cells from barcodes")
     ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
-    ap.add_argument("--batch-records", type=int, nargs="*", default=[1 << 21, 1 << 23], help="--barcodes-stream: records per pushed batch")
+    ap.add_argument("--barcodes-any-order-stream", action="store_true",
+                    help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
+    ap.add_argument("--batch-records", type=int, nargs="*", default=[1 << 21, 1 << 23], help="the session legs: records per pushed batch")
     ap.add_argument("--styles", nargs="*", default=["uuid", "illumina"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.barcodes_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.barcodes_stream or args.barcodes_any_order_stream else 3
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "cells_barcodes_stream_bench.json" if args.barcodes_stream else
+        args.out = os.path.join(ROOT, "profiles", "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
+                                "cells_barcodes_stream_bench.json" if args.barcodes_stream else
                                 "cells_records_barcodes_bench.json" if args.barcodes else
                                 "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
     T, n = args.txps, args.cells
@@ -399,6 +498,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.barcodes_any_order_stream:
+        barcodes_any_order_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     if args.barcodes_stream:
         barcodes_stream_leg(args, cr, res, save)
         print(json.dumps(res))
