@@ -795,6 +795,89 @@ int oem_em_run_cells_records_barcodes_sparse(
     uint32_t *out_kept /* capacity n_records, or NULL */,
     oem_cells_result **out);
 
+/* Marks the PCR DUPLICATES among the reads of a collated order, on the device.  The reference has no counterpart: its
+ * documentation (docs/index.md:308-312) wants single-cell input "with already (UMI) deduplicated reads", because "a
+ * count will be obtained for each read record", and names UMI counting as future work.  This call lifts that
+ * requirement for input whose UB tags are corrected already; it is the composable step, as oem_collate_names is for
+ * names.  The rule is oarfish_amd/csrc/oem_collate.h ("UMI deduplication"):
+ *   - umis / umi_off: one UMI per INPUT record, as names are passed; a record without a UB tag has the empty string.
+ *     flags: the records' OEM_REC_* words, or NULL (no record is unmapped).
+ *   - order (n_positions), group_off (n_groups + 1; a group is a read) and cell_group_off (n_cells + 1) are a collated
+ *     order as oem_collate_barcodes / oem_collate_names leave it: order[k] is the input index at position k.
+ *   - head(g) = order[group_off[g]] (under OEM_COLLATE_SORT the read's primary); umi(g) is the UMI of record head(g), the
+ *     UMIs of a read's other records are not examined.
+ *   - group g takes part iff it has a record, umi(g) is not empty and record head(g) does not have OEM_REC_UNMAPPED.  A
+ *     group that does not take part is never a duplicate and never shadows another.
+ *   - inside one cell the groups that take part and whose UMIs are byte-identical (same length, same bytes) form a
+ *     class; classes never span cells.  The class's smallest group index is its survivor, every other member a duplicate.
+ *     Under OEM_COLLATE_SORT the survivor is the read whose name sorts first, whatever the input's order; under
+ *     OEM_COLLATE_ADJACENT it is the first read in input order.
+ * out_dup[g] is 0 or 1, out_survivor[g] the survivor's group index for a duplicate and g otherwise, out_cell_dups[c] the
+ * number of duplicates in cell c.  Dropping the duplicate groups' positions from order / group_off / cell_group_off gives
+ * the deduplicated collation; no cell becomes empty through it.
+ *
+ * Limits, on purpose: matching is exact, on corrected UMIs (umi_tools' `unique` method), with no edit-distance
+ * clustering; the key is (cell, UMI), with no gene in it; the survivor is not chosen by read length or by what the
+ * filter keeps.
+ *
+ * OEM_ERR_ARG before any device use: umi_off, group_off, cell_group_off or an output NULL; umis NULL while a UMI has
+ * bytes; order NULL with n_positions > 0; offsets not from 0 or decreasing; group_off not ending at n_positions;
+ * cell_group_off not ending at n_groups; n_records or n_positions > 2^32 - 1; a cell of more than 2^31 - 2 records or
+ * groups.  OEM_ERR_ARG found on the device: an order entry that is not below n_records (naming the first such
+ * position); a UMI that holds a 0 byte (naming the smallest such input index).  Empty UMIs are legal.  The cells are
+ * taken in batches, as oem_collate_names takes them; the UMIs and flags of the whole input are resident during the
+ * call.  Running out of device memory is OEM_ERR_OOM with everything released.  Without a device: OEM_ERR_NO_DEVICE. */
+int oem_dedup_umis(const uint8_t *umis, const uint64_t *umi_off, const uint32_t *flags /* n_records, or NULL */,
+                   uint64_t n_records, const uint32_t *order, uint64_t n_positions,
+                   const uint64_t *group_off, uint64_t n_groups, const uint64_t *cell_group_off, uint32_t n_cells,
+                   int device,
+                   uint8_t *out_dup          /* n_groups */,
+                   uint64_t *out_survivor    /* n_groups */,
+                   uint64_t *out_cell_dups   /* n_cells */);
+
+/* oem_em_run_cells_records_barcodes_sparse with UMI deduplication: cells from raw records in one call.  The arguments
+ * are that call's, with umis / umi_off (one UMI per input record, as oem_dedup_umis takes them) added; the records'
+ * own flags words say which are unmapped.  Per group of cells the duplicates leave the collation on the device, between
+ * the name collation and the record gather: a duplicate's records are never gathered, filtered or counted.
+ *
+ * The result is what the caller gets by joining seven steps: oem_collate_barcodes (order_bc, cell_rec_off); records,
+ * names and secondary put into order_bc order on the host; oem_collate_names with that cell_rec_off (order_names,
+ * group_off, cell_group_off); the composed order, order[k] = order_bc[order_names[k]]; oem_dedup_umis on it with the
+ * caller's umis and the records' flags; the duplicate groups' positions dropped on the host (order', group_off',
+ * cell_group_off', cell_rec_off'); oem_em_run_cells_records_sparse on records[order'] with group_off' and
+ * cell_group_off'.  The seven outputs of the barcodes call describe that DEDUPLICATED collation: *out_n_survivors
+ * positions of out_order are written, out_cell_rec_off counts positions of it, *out_n_groups reads remain.  Exactly
+ * equal to that join: every index array and count, out_kept, every table of oem_cells_result_discard_tables (a
+ * duplicate is in no table), out_cell_dups (capacity n_records; *out_n_cells written: the duplicates dropped from every
+ * cell) and the entries' columns.  Each output but `out` may be NULL.  The entries' values and the infos are equal as
+ * oem_em_run_cells_records_sparse states it: up to floating-point summation order.  With every UMI empty the call
+ * gives oem_em_run_cells_records_barcodes_sparse's result exactly, and no duplicate.
+ *
+ * Resident on the device beyond what the barcodes call holds: the UMI blob and 8 bytes of offsets per record; a group's
+ * UMI collation is released before its records are gathered.  Running out of device memory is OEM_ERR_OOM with
+ * everything released.
+ *
+ * Errors are those of the barcodes call and of oem_dedup_umis.  Before any device use also: umi_off NULL, not from 0 or
+ * decreasing; umis NULL while a UMI has bytes.  Found on the device also: a UMI that holds a 0 byte, OEM_ERR_ARG naming
+ * the smallest such input index.  A mapped record whose ref_id is not below n_txps is found among the survivors only,
+ * and named by its cell and its index in the caller's input order.  Without a device: OEM_ERR_NO_DEVICE.  *out = NULL
+ * on any failure. */
+int oem_em_run_cells_records_umis_sparse(
+    const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+    const oem_aln_record *records, uint64_t n_records,
+    const uint8_t *barcodes, const uint64_t *barcode_off,
+    const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+    const uint8_t *umis, const uint64_t *umi_off,
+    uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT: applied inside each cell, after the barcode collation */,
+    uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+    uint32_t *out_order /* capacity n_records, *out_n_survivors written; or NULL */, uint64_t *out_n_survivors /* or NULL */,
+    uint64_t *out_cell_rec_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_cells /* or NULL */,
+    uint64_t *out_group_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_groups /* or NULL */,
+    uint64_t *out_cell_group_off /* capacity n_records + 1, or NULL */,
+    uint32_t *out_kept /* capacity n_records, or NULL */,
+    uint64_t *out_cell_dups /* capacity n_records, *out_n_cells written; or NULL */,
+    oem_cells_result **out);
+
 /* The bulk parser and oem_store_create_records in one call: parse_alignments (alignment_parser.rs:301-437) from the
  * records and read names as a BAM reader produces them, in input order, to the resident store.  records (n_records),
  * names / name_off and secondary are oem_collate_names' per-record arrays; the rule is oarfish_amd/csrc/oem_collate.h

@@ -28,7 +28,7 @@ LIB_PATH = os.path.join(HERE, "liboarfish_em.so")
 TESTING_LIB_PATH = os.path.join(HERE, "liboarfish_em_testing.so")
 
 # sources of the product library
-SOURCES = ["oem_api.hip", "oem_em_driver.hip", "oem_assignment_text.hip", "oem_lz4.hip", "oem_count_matrix_text.hip", "oem_quant_text.hip", "oem_collate_device.hip", "oem_bootstrap.hip", "oem_cells.hip", "oem_cells_records.hip", "oem_records_names.hip", "oem_cells_stream.hip", "oem_cells_barcodes_stream.hip", "oem_cells_barcodes_sort_stream.hip", "oem_records_stream.hip", "oem_cells_sparse.hip", "oem_timing.hip", "oem_kernels.hip", "oem_tile_kernels.hip", "oem_batch_kernels.hip",
+SOURCES = ["oem_api.hip", "oem_em_driver.hip", "oem_assignment_text.hip", "oem_lz4.hip", "oem_count_matrix_text.hip", "oem_quant_text.hip", "oem_collate_device.hip", "oem_dedup_umis.hip", "oem_bootstrap.hip", "oem_cells.hip", "oem_cells_records.hip", "oem_records_names.hip", "oem_cells_stream.hip", "oem_cells_barcodes_stream.hip", "oem_cells_barcodes_sort_stream.hip", "oem_records_stream.hip", "oem_cells_sparse.hip", "oem_timing.hip", "oem_kernels.hip", "oem_tile_kernels.hip", "oem_batch_kernels.hip",
            "oem_multi_kernels.hip", "oem_layout.cpp", "oem_layout_device.hip", "oem_layout_pack.hip", "oem_layout_dict.hip", "oem_coverage_device.hip", "oem_coverage_cells.hip", "oem_filter_device.hip", "oem_filter_projected_device.hip",
            "oem_builder.cpp", "oem_builder_projected.cpp", "oem_comm.cpp", "oem_p2p.hip", "oem_knobs.cpp"]
 # the testing library swaps these for their -DOEM_TESTING build and adds the hooks
@@ -111,7 +111,8 @@ TESTING_HOOKS = ["oem_debug_layout_hash", "oem_debug_local_comm_create", "oem_te
                  "oem_test_shortest_f64", "oem_debug_collate_last_call", "oem_test_collate_host",
                  "oem_debug_collate_barcodes_last_call", "oem_debug_cells_barcodes_last_call", "oem_test_collate_barcodes_host",
                  "oem_debug_records_stream_finish_csr", "oem_debug_records_stream_last_join",
-                 "oem_debug_records_names_last_call", "oem_test_parse_bulk_host", "oem_debug_barcode_table_last"]
+                 "oem_debug_records_names_last_call", "oem_test_parse_bulk_host", "oem_debug_barcode_table_last",
+                 "oem_test_dedup_umis_host"]
 
 
 def header_symbols() -> list:

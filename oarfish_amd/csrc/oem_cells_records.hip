@@ -40,8 +40,15 @@
 //               collate_resident runs in its device form (no lanes, no validate pass) with positions for record indices
 //   compose     k_order_compose: order[k] = order_bc[r0 + order[k]], the record's index in the caller's input
 //   gather      k_records_gather straight from the whole-input buffer, under either mode (order_bc is no identity)
+//
+// oem_em_run_cells_records_umis_sparse is that call with the UMIs resident too (umis_upload, oem_dedup_umis.hip).  Between a
+// group's collate and its compose run dedup_mark and, where it found duplicates, dedup_compact (oem_collate.h's UMI rule):
+// order, group_off and cell_group_off are replaced by the deduplicated ones, so the duplicates' records are never
+// gathered and the filter sees the survivors only.  A group's place in the call's order is then known only when every
+// group before it is done: its order waits in its slot like kept and group_off.
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -266,6 +273,7 @@ struct ResidentInput {
     const uint32_t *order_bc = nullptr;             // n_records
     const uint64_t *gathered_off = nullptr;         // n_records + 1: the names' offsets in order_bc order
     const uint64_t *cell_name_off = nullptr;        // HOST, n_cells + 1: gathered_off at the cells' first records
+    const UmiInput *umi = nullptr;                  // the UMIs form: the groups are deduplicated behind their name collation
 };
 struct NamesCall {
     CollateInput in;
@@ -278,6 +286,10 @@ struct NamesSlot {
     uint64_t n_groups = 0;
     std::vector<uint64_t> group_off, cell_group_off; // from 0: n_groups + 1 (if asked for), n_cells + 1
     std::vector<uint32_t> kept;                      // n_groups (if asked for)
+    // the UMIs form, whose groups' places in the call's order are known only when the workers have joined
+    uint64_t n_positions = 0;                        // the positions of the group's deduplicated order
+    std::vector<uint32_t> order;                     // n_positions (if asked for)
+    std::vector<uint64_t> cell_pos_off, cell_dups;   // from 0: n_cells + 1; n_cells
 };
 
 // The cells [c0, c1) of the call: collate, gather, filter and run.  rg: the group's place and outputs (records,
@@ -297,6 +309,13 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
     rg.first_record = r0;
     rg.n_cells = n_cells;
     rg.cell_group_off = slot->cell_group_off.data();
+    const bool dedup = nc.dev && nc.dev->umi;
+    uint64_t mp = m;           // the positions of the group's order: fewer than its records once duplicates are dropped
+    std::vector<uint64_t> cpo; // then also the cells' first positions in it, from 0
+    if (dedup) {
+        slot->cell_pos_off.assign((size_t)n_cells + 1, 0);
+        slot->cell_dups.assign(n_cells, 0);
+    }
     if (m == 0) { // cells without records: no groups, and the run of cells without reads
         const uint64_t zero = 0;
         rg.group_off = &zero;
@@ -321,7 +340,23 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
         in.d_n_bytes = nb;
         in.d_secondary = d_gsec.p;
         OEM_TRY(collate_resident(in, c0, c1, 0, 0, 0, info, &cr));
-        hipLaunchKernelGGL(k_order_compose, dim3((uint32_t)((m + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, m, dv.order_bc + r0, cr.order.p);
+        if (dedup) { // the duplicates leave the collation here: their records are never gathered
+            d_gnames.reset();
+            d_gsec.reset();
+            tm.lap("names: collate");
+            UmiMarks mk;
+            OEM_TRY(dedup_mark(*dv.umi, cr.order.p, dv.order_bc + r0, cr.group_off.p, cr.n_groups, cr.cell_group_off.p, n_cells, 0, &mk,
+                               slot->cell_dups.data()));
+            if (mk.n_dups) {
+                cpo.resize((size_t)n_cells + 1);
+                OEM_TRY(dedup_compact(mk, m, n_cells, &cr, &mp, cpo.data()));
+                slot->cell_pos_off = cpo;
+            } else {
+                for (uint32_t c = 0; c <= n_cells; ++c) slot->cell_pos_off[c] = nc.in.cell_rec_off[c0 + c] - r0;
+            }
+            tm.lap("umis: dedup");
+        }
+        hipLaunchKernelGGL(k_order_compose, dim3((uint32_t)((mp + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, mp, dv.order_bc + r0, cr.order.p);
         OEM_HIP(hipGetLastError());
         OEM_HIP(hipStreamSynchronize(nullptr));
     } else {
@@ -331,7 +366,18 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
     const uint64_t ng = cr.n_groups;
     slot->n_groups = ng;
     OEM_HIP(hipMemcpy(slot->cell_group_off.data(), cr.cell_group_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost));
-    if (nc.out_order) OEM_HIP(hipMemcpy(nc.out_order + r0, cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    slot->n_positions = mp;
+    if (nc.out_order && dedup) {
+        slot->order.resize(mp);
+        OEM_HIP(hipMemcpy(slot->order.data(), cr.order.p, sizeof(uint32_t) * mp, hipMemcpyDeviceToHost));
+    } else if (nc.out_order)
+        OEM_HIP(hipMemcpy(nc.out_order + r0, cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    // a record's cell from its position in the group's order: the sort stays inside cells
+    auto cell_at = [&](uint64_t k) -> uint64_t {
+        if (!cpo.empty()) return c0 + (uint64_t)(std::upper_bound(cpo.begin(), cpo.end(), k) - cpo.begin()) - 1;
+        const uint64_t *cro = nc.in.cell_rec_off;
+        return (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, r0 + k) - cro) - 1;
+    };
     if (nc.want_group_off) {
         slot->group_off.resize(ng + 1);
         OEM_HIP(hipMemcpy(slot->group_off.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
@@ -352,8 +398,8 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
         }
         const oem_aln_record *d_recs = d_in.p;
         if (sorting || nc.dev) { // (the adjacent cut's order is the identity; with barcodes it is order_bc's slice)
-            OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
-            const uint64_t n_words = m * kRecordWords;
+            OEM_TRY(dev_alloc(&d_sorted.p, mp, nullptr));
+            const uint64_t n_words = mp * kRecordWords;
             hipLaunchKernelGGL(k_records_gather, dim3((uint32_t)((n_words + kGT - 1) / kGT)), dim3(kGT), 0, nullptr, n_words,
                                (const uint32_t *)cr.order.p, (uint32_t)(nc.dev ? 0 : r0),
                                (const uint64_t *)(nc.dev ? nc.dev->records : d_in.p), (uint64_t *)d_sorted.p);
@@ -370,24 +416,22 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
         if (r.bad_ref_record != kNoRecord) { // a collated index: the caller knows its records by their input index
             uint32_t at = 0;
             OEM_HIP(hipMemcpy(&at, cr.order.p + r.bad_ref_record, sizeof at, hipMemcpyDeviceToHost));
-            const uint64_t *cro = nc.in.cell_rec_off; // (a record's cell from its collated position: the sort stays inside cells)
-            const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, r0 + (uint64_t)r.bad_ref_record) - cro) - 1;
+            const uint64_t c = cell_at((uint64_t)r.bad_ref_record);
             return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)c,
                         (unsigned long long)at, nc.records[at].ref_id);
         }
         host = r.host_rerun;
     }
     if (host) { // the host loop: order and group_off come down, the host gathers the group's records
-        std::vector<uint32_t> order(m);
+        std::vector<uint32_t> order(mp);
         std::vector<uint64_t> goff(ng + 1);
-        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * mp, hipMemcpyDeviceToHost));
         OEM_HIP(hipMemcpy(goff.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
-        std::vector<oem_aln_record> sorted(m);
-        const uint64_t *cro = nc.in.cell_rec_off;
-        for (uint64_t k = 0; k < m; ++k) {
+        std::vector<oem_aln_record> sorted(mp);
+        for (uint64_t k = 0; k < mp; ++k) {
             sorted[k] = nc.records[order[k]];
             if (!(sorted[k].flags & OEM_REC_UNMAPPED) && sorted[k].ref_id >= run.n_txps) {
-                const uint64_t c = (uint64_t)(std::upper_bound(cro + c0, cro + c1 + 1, r0 + k) - cro) - 1;
+                const uint64_t c = cell_at(k);
                 return fail(OEM_ERR_ARG, "%s: cell %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)c,
                             (unsigned long long)order[k], sorted[k].ref_id);
             }
@@ -424,6 +468,37 @@ void names_call_outputs(const std::vector<std::pair<uint32_t, uint32_t>> &groups
     if (out_cell_group_off && groups.empty()) out_cell_group_off[0] = 0;
     if (out_group_off) out_group_off[group_base] = n_records;
     if (out_n_groups) *out_n_groups = group_base;
+}
+
+// The same for the UMIs form, whose groups' first positions are known only now too: a group's order, its cells' first
+// positions and their duplicate counts wait in its slot.
+void umis_call_outputs(const std::vector<std::pair<uint32_t, uint32_t>> &groups, const std::vector<NamesSlot> &slots, uint32_t *out_order,
+                       uint64_t *out_n_survivors, uint64_t *out_cell_rec_off, uint64_t *out_group_off, uint64_t *out_n_groups,
+                       uint64_t *out_cell_group_off, uint32_t *out_kept, uint64_t *out_cell_dups)
+{
+    uint64_t group_base = 0, pos_base = 0;
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const uint32_t c0 = groups[g].first, c1 = groups[g].second;
+        const NamesSlot &sl = slots[g];
+        for (uint32_t c = c0; c <= c1; ++c) {
+            if (out_cell_group_off) out_cell_group_off[c] = group_base + sl.cell_group_off[c - c0];
+            if (out_cell_rec_off) out_cell_rec_off[c] = pos_base + sl.cell_pos_off[c - c0];
+        }
+        if (out_group_off)
+            for (uint64_t k = 0; k < sl.n_groups; ++k) out_group_off[group_base + k] = pos_base + sl.group_off[k];
+        if (out_kept && sl.n_groups) std::memcpy(out_kept + group_base, sl.kept.data(), sizeof(uint32_t) * sl.n_groups);
+        if (out_order && sl.n_positions) std::memcpy(out_order + pos_base, sl.order.data(), sizeof(uint32_t) * sl.n_positions);
+        if (out_cell_dups) std::copy(sl.cell_dups.begin(), sl.cell_dups.end(), out_cell_dups + c0);
+        group_base += sl.n_groups;
+        pos_base += sl.n_positions;
+    }
+    if (groups.empty()) {
+        if (out_cell_group_off) out_cell_group_off[0] = 0;
+        if (out_cell_rec_off) out_cell_rec_off[0] = 0;
+    }
+    if (out_group_off) out_group_off[group_base] = pos_base;
+    if (out_n_groups) *out_n_groups = group_base;
+    if (out_n_survivors) *out_n_survivors = pos_base;
 }
 
 // The cut of the records call (a group's records bound its reads and alignments), and then what the collation adds: a
@@ -711,23 +786,25 @@ extern "C" int oem_em_run_cells_records_names_sparse(const oem_filters *filters,
     OEM_API_END("oem_em_run_cells_records_names_sparse")
 }
 
-extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
-                                                        const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
-                                                        const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off,
-                                                        const uint8_t *secondary, uint32_t mode, uint32_t bin_width, int model,
-                                                        double growth_rate, int device, uint32_t max_iter, double conv_thresh,
-                                                        uint32_t *out_order, uint64_t *out_cell_rec_off, uint64_t *out_n_cells,
-                                                        uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off,
-                                                        uint32_t *out_kept, oem_cells_result **out)
+// The body of oem_em_run_cells_records_barcodes_sparse and, with_umis, of oem_em_run_cells_records_umis_sparse: the same
+// call with the UMIs resident beside the names and every group of cells deduplicated behind its name collation.  UMIs
+// that are all empty take no part anywhere: the call is then the barcodes call, and reports no duplicate.
+static int cells_records_barcodes_call(const char *who, const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                       const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
+                                       const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off,
+                                       const uint8_t *secondary, bool with_umis, const uint8_t *umis, const uint64_t *umi_off, uint32_t mode,
+                                       uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+                                       uint32_t *out_order, uint64_t *out_n_survivors, uint64_t *out_cell_rec_off, uint64_t *out_n_cells,
+                                       uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off, uint32_t *out_kept,
+                                       uint64_t *out_cell_dups, oem_cells_result **out)
 {
-    OEM_API_BEGIN
-    const char *who = "oem_em_run_cells_records_barcodes_sparse";
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
     *out = nullptr;
     if (out_n_groups) *out_n_groups = 0;
     if (out_n_cells) *out_n_cells = 0;
+    if (out_n_survivors) *out_n_survivors = 0;
     // the checks of oem_store_create_records, of oem_collate_barcodes, of oem_collate_names and of the cells calls, before
     // any device use
     OEM_TRY(check_store_from_records(who, filters, txp_len, n_txps, bin_width, model, nullptr));
@@ -736,6 +813,15 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
     const uint64_t n = n_records, one_cell[2] = {0, n};
     OEM_TRY(check_collate_input(who, names, name_off, n, one_cell, 1, mode));
     if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
+    if (with_umis) {
+        if (!umi_off) return fail(OEM_ERR_ARG, "%s: umi_off is NULL", who);
+        if (umi_off[0] != 0) return fail(OEM_ERR_ARG, "%s: umi_off must start at 0", who);
+        for (uint64_t i = 0; i < n; ++i)
+            if (umi_off[i + 1] < umi_off[i])
+                return fail(OEM_ERR_ARG, "%s: umi_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+        if (umi_off[n] && !umis) return fail(OEM_ERR_ARG, "%s: umis is NULL and the UMIs are not all empty", who);
+    }
+    const bool dedup = with_umis && n && umi_off[n] > 0;
     if (model >= 0) OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, 0, 0));
     OEM_TRY(ensure_device(device));
     RecordsFilter rf;
@@ -773,8 +859,8 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
 
     // the whole input, once and in input order; the names are checked behind their chunks
     DevBuf<oem_aln_record> d_records;
-    DevBuf<uint8_t> d_names, d_sec;
-    DevBuf<uint64_t> d_name_off, d_gathered_off, d_cell_name_off;
+    DevBuf<uint8_t> d_names, d_sec, d_umis;
+    DevBuf<uint64_t> d_name_off, d_gathered_off, d_cell_name_off, d_umi_off;
     t0 = clk::now();
     if (n) {
         const uint64_t n_bytes = name_off[n], chunk_bytes = collate_chunk_bytes();
@@ -814,6 +900,7 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
             OEM_HIP(hipMemset(d_sec.p + n, 0, 8));
             OEM_HIP(hipMemcpy(d_sec.p, secondary, n, hipMemcpyHostToDevice));
         }
+        if (dedup) OEM_TRY(umis_upload(who, umis, umi_off, n, &d_umis, &d_umi_off));
         OEM_TRY(upload_records(records, n, d_records.p));
         last[3] = ms_since(t0);
         t0 = clk::now();
@@ -844,6 +931,14 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
     dv.order_bc = bc.order.p;
     dv.gathered_off = d_gathered_off.p;
     dv.cell_name_off = cell_name_off.data();
+    UmiInput um; // the flags are read where they are: word 8 of a record's ten
+    static_assert(offsetof(oem_aln_record, flags) == 32 && sizeof(oem_aln_record) == 40, "the flags word of a resident record");
+    um.who = who;
+    um.d_umis = d_umis.p;
+    um.d_umi_off = d_umi_off.p;
+    um.d_flags = d_records.p ? (const uint32_t *)d_records.p + 8 : nullptr;
+    um.flags_stride = 10;
+    if (dedup) dv.umi = &um;
     NamesCall nc;
     nc.in.who = who;
     nc.in.cell_rec_off = cro.data();
@@ -871,14 +966,55 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
     }));
     last[1] = (double)groups.size();
     last[5] = ms_since(t0);
-    names_call_outputs(groups, slots, cro.data(), n, out_group_off, out_n_groups, out_cell_group_off, out_kept);
+    if (dedup) {
+        umis_call_outputs(groups, slots, out_order, out_n_survivors, out_cell_rec_off, out_group_off, out_n_groups, out_cell_group_off, out_kept,
+                          out_cell_dups);
+    } else {
+        names_call_outputs(groups, slots, cro.data(), n, out_group_off, out_n_groups, out_cell_group_off, out_kept);
+        if (out_cell_rec_off) std::memcpy(out_cell_rec_off, cro.data(), sizeof(uint64_t) * ((size_t)n_cells + 1));
+        if (out_n_survivors) *out_n_survivors = n;
+        if (out_cell_dups) std::fill(out_cell_dups, out_cell_dups + n_cells, 0ull);
+    }
     OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
-    if (out_cell_rec_off) std::memcpy(out_cell_rec_off, cro.data(), sizeof(uint64_t) * ((size_t)n_cells + 1));
     if (out_n_cells) *out_n_cells = n_cells;
     std::memcpy(g_cells_barcodes_last, last, sizeof last);
     *out = r.release();
     return OEM_OK;
+}
+
+extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                                        const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
+                                                        const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off,
+                                                        const uint8_t *secondary, uint32_t mode, uint32_t bin_width, int model,
+                                                        double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+                                                        uint32_t *out_order, uint64_t *out_cell_rec_off, uint64_t *out_n_cells,
+                                                        uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off,
+                                                        uint32_t *out_kept, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    return cells_records_barcodes_call("oem_em_run_cells_records_barcodes_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
+                                       barcode_off, names, name_off, secondary, false, nullptr, nullptr, mode, bin_width, model, growth_rate,
+                                       device, max_iter, conv_thresh, out_order, nullptr, out_cell_rec_off, out_n_cells, out_group_off,
+                                       out_n_groups, out_cell_group_off, out_kept, nullptr, out);
     OEM_API_END("oem_em_run_cells_records_barcodes_sparse")
+}
+
+extern "C" int oem_em_run_cells_records_umis_sparse(const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+                                                    const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
+                                                    const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off,
+                                                    const uint8_t *secondary, const uint8_t *umis, const uint64_t *umi_off, uint32_t mode,
+                                                    uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter,
+                                                    double conv_thresh, uint32_t *out_order, uint64_t *out_n_survivors,
+                                                    uint64_t *out_cell_rec_off, uint64_t *out_n_cells, uint64_t *out_group_off,
+                                                    uint64_t *out_n_groups, uint64_t *out_cell_group_off, uint32_t *out_kept,
+                                                    uint64_t *out_cell_dups, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    return cells_records_barcodes_call("oem_em_run_cells_records_umis_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
+                                       barcode_off, names, name_off, secondary, true, umis, umi_off, mode, bin_width, model, growth_rate, device,
+                                       max_iter, conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off,
+                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, out);
+    OEM_API_END("oem_em_run_cells_records_umis_sparse")
 }
 
 extern "C" int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out)

@@ -212,6 +212,105 @@ inline uint64_t collate_barcodes_host(const uint8_t *barcodes, const uint64_t *b
 
 constexpr uint32_t kRecUnmapped = 1u; // OEM_REC_UNMAPPED
 
+// UMI deduplication (dedup_umis_host below, oem_dedup_umis, oem_em_run_cells_records_umis_sparse).  Nothing of this is in
+// the reference: its documentation (docs/index.md:308-312) wants single-cell input "with already (UMI) deduplicated
+// reads" -- "a count will be obtained for each read record" -- and names UMI counting as future work.  This rule lifts
+// that requirement for input whose UB tags are corrected already.
+// Input: a collated order as the barcode and name rules above leave it -- order (position k holds a caller input index),
+// group_off (n_groups + 1; a group is a read), cell_group_off (n_cells + 1) -- one UMI byte string per INPUT record (a
+// record without a UB tag has the empty string; a UMI holds no 0 byte, which is the caller's to check:
+// dedup_first_bad_umi) and the records' flags.
+//   head(g)   order[group_off[g]], the read's first record in collated order: under kCollateSort its primary.
+//   umi(g)    the UMI of record head(g).  The UMIs of a read's other records are not examined.
+//   takes part   group g takes part iff it has a record, umi(g) is not empty and record head(g) does not have
+//             OEM_REC_UNMAPPED.  A group that does not take part is never a duplicate and never shadows another: an
+//             unmapped read cannot hide a mapped read of the same molecule.
+//   class     inside one cell, the groups that take part and whose UMIs are byte-identical (same length, same bytes:
+//             ACG and ACGT differ).  Classes never span cells.
+//   survivor  of a class: its smallest group index.  Every other member is a duplicate.  Under kCollateSort the groups
+//             of a cell are in name order, so the survivor is the read whose name sorts first and the result does not
+//             depend on the input's order; under kCollateAdjacent it is the first read in input order.
+//   results   dup[g] (0 / 1); survivor[g], the survivor's group index for a duplicate and g itself otherwise;
+//             cell_dups[c], the duplicates of cell c; and the DEDUPLICATED COLLATION order', group_off', cell_group_off',
+//             cell_rec_off': the same arrays with the duplicate groups' positions removed and everything else in place
+//             (dedup_drop_host).  No cell becomes empty through this: every class keeps one member.
+// Limits, on purpose: matching is exact, on corrected UMIs (umi_tools' `unique` method) -- no edit-distance clustering;
+// the key is (cell, UMI), with no gene in it; the survivor is not chosen by read length or by what the filter keeps --
+// deduplication runs before the filter.
+
+// The first input record (kCollateNoRecord: none) whose UMI holds a 0 byte.  Empty UMIs are legal.
+inline uint64_t dedup_first_bad_umi(const uint8_t *umis, const uint64_t *umi_off, uint64_t n_records)
+{
+    for (uint64_t i = 0; i < n_records; ++i) {
+        const uint64_t len = umi_off[i + 1] - umi_off[i];
+        if (len && memchr(umis + umi_off[i], 0, len)) return i;
+    }
+    return kCollateNoRecord;
+}
+
+// The host walk of the UMI rule: the specification.  flags: one word per input record, or NULL (none unmapped).  dup
+// (n_groups), survivor (n_groups), cell_dups (n_cells).  The arguments are checked by the caller.
+inline void dedup_umis_host(const uint8_t *umis, const uint64_t *umi_off, const uint32_t *flags, const uint32_t *order,
+                            const uint64_t *group_off, uint64_t n_groups, const uint64_t *cell_group_off, uint32_t n_cells, uint8_t *dup,
+                            uint64_t *survivor, uint64_t *cell_dups)
+{
+    for (uint64_t g = 0; g < n_groups; ++g) {
+        dup[g] = 0;
+        survivor[g] = g;
+    }
+    auto head = [&](uint64_t g) { return order[group_off[g]]; };
+    auto cmp = [&](uint64_t a, uint64_t b) {
+        const uint32_t i = head(a), j = head(b);
+        return collate_name_cmp(umis + umi_off[i], umi_off[i + 1] - umi_off[i], umis + umi_off[j], umi_off[j + 1] - umi_off[j]);
+    };
+    std::vector<uint64_t> part;
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        cell_dups[c] = 0;
+        part.clear();
+        for (uint64_t g = cell_group_off[c]; g < cell_group_off[c + 1]; ++g) {
+            if (group_off[g + 1] == group_off[g]) continue;
+            const uint32_t i = head(g);
+            if (umi_off[i + 1] > umi_off[i] && !(flags && (flags[i] & kRecUnmapped))) part.push_back(g);
+        }
+        std::sort(part.begin(), part.end(), [&](uint64_t a, uint64_t b) {
+            const int r = cmp(a, b);
+            return r ? r < 0 : a < b;
+        });
+        for (size_t k = 1, first = 0; k < part.size(); ++k) { // a run's first member is its smallest group: the survivor
+            if (cmp(part[first], part[k]) != 0) {
+                first = k;
+                continue;
+            }
+            dup[part[k]] = 1;
+            survivor[part[k]] = part[first];
+            ++cell_dups[c];
+        }
+    }
+}
+
+// The deduplicated collation: the positions of the duplicate groups removed.  out_order (capacity n_positions),
+// out_group_off (capacity n_groups + 1), out_cell_group_off and out_cell_rec_off (n_cells + 1 each).  Returns the number
+// of groups that remain.
+inline uint64_t dedup_drop_host(const uint32_t *order, const uint64_t *group_off, uint64_t n_groups, const uint64_t *cell_group_off,
+                                uint32_t n_cells, const uint8_t *dup, uint32_t *out_order, uint64_t *out_group_off,
+                                uint64_t *out_cell_group_off, uint64_t *out_cell_rec_off)
+{
+    uint64_t at = 0, ng = 0;
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        out_cell_group_off[c] = ng;
+        out_cell_rec_off[c] = at;
+        for (uint64_t g = cell_group_off[c]; g < cell_group_off[c + 1]; ++g) {
+            if (dup[g]) continue;
+            out_group_off[ng++] = at;
+            for (uint64_t p = group_off[g]; p < group_off[g + 1]; ++p) out_order[at++] = order[p];
+        }
+    }
+    out_cell_group_off[n_cells] = ng;
+    out_cell_rec_off[n_cells] = at;
+    out_group_off[ng] = at;
+    return ng;
+}
+
 // What the host walk of the bulk parser finds besides order and group_off.
 struct ParseBulk {
     uint64_t n_unmapped = 0, n_parsed = 0, n_groups = 0, n_checked = 0;

@@ -97,6 +97,35 @@ int upload_records(const oem_aln_record *records, uint64_t m, oem_aln_record *d)
 int order_compose(uint64_t m, const uint32_t *d_outer, uint32_t *d_order);
 int records_gather(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_src, oem_aln_record *d_dst);
 
+// ---- UMI deduplication (oem_dedup_umis.hip; the rule is oem_collate.h's)
+// The whole input's UMIs and flags on the device, in input order.
+struct UmiInput {
+    const char *who = nullptr;           // for the messages of the collation over the UMIs
+    const uint8_t *d_umis = nullptr;     // the blob, 8-byte aligned and padded by 16
+    const uint64_t *d_umi_off = nullptr; // n_records + 1
+    const uint32_t *d_flags = nullptr;   // record i's flags word at d_flags[i * flags_stride], or NULL: none unmapped
+    uint64_t flags_stride = 1;           // (10 with the flags read out of resident 40-byte records)
+};
+// What dedup_mark leaves on the device for a batch of ng groups.
+struct UmiMarks {
+    DevBuf<uint32_t> dup;      // ng: 0 / 1
+    DevBuf<uint64_t> survivor; // ng: survivor_base + the survivor's group
+    DevBuf<uint64_t> keep;     // ng + 1: 1 - dup, then 0
+    DevBuf<uint64_t> gscan;    // ng + 1, only with n_dups > 0: the exclusive scan of keep, the kept groups' new numbers
+    uint64_t n_part = 0, n_classes = 0, n_dups = 0; // (n_classes: only when two groups or more take part)
+};
+// The UMIs (checked: umi_off from 0, non-decreasing) up through the upload lanes, validated behind their chunks: a 0 byte
+// is OEM_ERR_ARG naming the smallest such input index, an empty UMI is legal.
+int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, uint64_t n, DevBuf<uint8_t> *d_umis, DevBuf<uint64_t> *d_umi_off);
+// The duplicates of a batch of nc cells whose collation is on the device: d_order (positions -> input indices, or ->
+// positions of d_order_bc where that is not NULL), d_group_off (ng + 1, from 0), d_cell_group_off (nc + 1, from 0).
+// cell_dups: host, nc.  With out->n_dups == 0 nothing else needs to be done.  Leaves the device idle.
+int dedup_mark(const UmiInput &in, const uint32_t *d_order, const uint32_t *d_order_bc, const uint64_t *d_group_off, uint64_t ng,
+               const uint64_t *d_cell_group_off, uint32_t nc, uint64_t survivor_base, UmiMarks *out, uint64_t *cell_dups);
+// The deduplicated collation in place of cr's arrays (m positions, nc cells; mk.n_dups > 0): *n_positions of order' are
+// filled, cell_pos_off (host, nc + 1) are the cells' first positions in it.
+int dedup_compact(const UmiMarks &mk, uint64_t m, uint32_t nc, CollateResident *cr, uint64_t *n_positions, uint64_t *cell_pos_off);
+
 uint64_t collate_chunk_bytes();   // the upload chunk (testing build: OEM_COLLATE_CHUNK_BYTES)
 uint64_t collate_batch_records(); // records per batch of oem_collate_names (testing build: OEM_COLLATE_BATCH_RECORDS)
 constexpr uint64_t kCollateMaxBatch = (1ull << 31) - 2; // a single cell beyond this is refused (the scans take m + 1 items as an int)

@@ -223,6 +223,30 @@ extern "C" int oem_test_collate_barcodes_host(const uint8_t *barcodes, const uin
     OEM_API_END("oem_test_collate_barcodes_host")
 }
 
+// Test hook: the host walk of oem_collate.h's UMI rule (dedup_umis_host) with oem_dedup_umis' arguments and outputs.  The
+// offsets are taken as checked; an order entry that is not below n_records and a UMI with a 0 byte are OEM_ERR_ARG, worded
+// as the device call words them.
+extern "C" int oem_test_dedup_umis_host(const uint8_t *umis, const uint64_t *umi_off, const uint32_t *flags, uint64_t n_records,
+                                        const uint32_t *order, uint64_t n_positions, const uint64_t *group_off, uint64_t n_groups,
+                                        const uint64_t *cell_group_off, uint32_t n_cells, uint8_t *out_dup, uint64_t *out_survivor,
+                                        uint64_t *out_cell_dups)
+{
+    OEM_API_BEGIN
+    if (!umi_off || !group_off || !cell_group_off || !out_dup || !out_survivor || !out_cell_dups || (n_positions && !order) ||
+        (umi_off[n_records] && !umis))
+        return fail(OEM_ERR_ARG, "oem_test_dedup_umis_host: NULL argument");
+    for (uint64_t k = 0; k < n_positions; ++k)
+        if (order[k] >= n_records)
+            return fail(OEM_ERR_ARG, "oem_test_dedup_umis_host: order[%llu] = %u is not below n_records = %llu", (unsigned long long)k, order[k],
+                        (unsigned long long)n_records);
+    const uint64_t bad = dedup_first_bad_umi(umis, umi_off, n_records);
+    if (bad != kCollateNoRecord)
+        return fail(OEM_ERR_ARG, "oem_test_dedup_umis_host: the UMI of record %llu contains a 0 byte", (unsigned long long)bad);
+    dedup_umis_host(umis, umi_off, flags, order, group_off, n_groups, cell_group_off, n_cells, out_dup, out_survivor, out_cell_dups);
+    return OEM_OK;
+    OEM_API_END("oem_test_dedup_umis_host")
+}
+
 // out[0..7] = this thread's last oem_store_create_records_names: [0] 1 if k_records_gather ran, [1] 1 if the survivors'
 // names were gathered, [2] the groups the collation check looked at, [3] 1 if the host loop took the groups
 namespace oem { void records_names_last_call(double *out8); }

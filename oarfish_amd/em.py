@@ -370,6 +370,68 @@ def collate_barcodes(barcodes, device: int = 0):
     return order[:n], cell_rec_off[:int(n_cells.value) + 1].copy()
 
 
+def dedup_umis(umis, order, group_off, cell_group_off, flags=None, device: int = 0):
+    """The PCR duplicates among the reads of a collated order (``oem_dedup_umis``; the reference wants its single-cell
+    input deduplicated already, docs/index.md:308-312).
+
+    ``umis``: one UMI per INPUT record, whatever ``types.pack_read_names`` accepts; a record without a ``UB`` tag has the
+    empty string, none holds a 0 byte.  ``order`` / ``group_off`` / ``cell_group_off``: a collated order as
+    ``collate_barcodes`` and ``collate_names`` leave it (``order[k]`` is the input index at position ``k``, a group is a
+    read).  ``flags``: the records' flag words (``records["flags"]``), or None when no record is unmapped.
+
+    A read takes part when the UMI of its first record is not empty and that record is mapped; inside a cell the reads
+    that take part and have byte-identical UMIs are one molecule, whose first read survives.  Returns ``(dup, survivor,
+    cell_dups)``: ``dup[g]`` 0 / 1, ``survivor[g]`` the surviving group of a duplicate and ``g`` otherwise, ``cell_dups[c]``
+    the duplicates of cell ``c``.  ``drop_groups`` applies ``dup``.
+    """
+    from .types import pack_read_names
+    n = _n_packed(umis)
+    blob, off = pack_read_names(umis, n)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+    cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
+    if group_off.ndim != 1 or len(group_off) < 1:
+        raise ValueError("group_off needs n_groups + 1 entries")
+    if cell_group_off.ndim != 1 or len(cell_group_off) < 1:
+        raise ValueError("cell_group_off needs n_cells + 1 entries")
+    fl = None
+    if flags is not None:
+        fl = np.ascontiguousarray(flags, dtype=np.uint32)
+        if len(fl) != n:
+            raise ValueError("flags must have one entry per record")
+    n_groups, n_cells = len(group_off) - 1, len(cell_group_off) - 1
+    dup = np.zeros(max(n_groups, 1), dtype=np.uint8)
+    survivor = np.zeros(max(n_groups, 1), dtype=np.uint64)
+    cell_dups = np.zeros(max(n_cells, 1), dtype=np.uint64)
+    if not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)
+    _lib.check(_lib.lib().oem_dedup_umis(
+        blob.ctypes.data, off.ctypes.data, None if fl is None or not n else fl.ctypes.data, n, order.ctypes.data if len(order) else None,
+        len(order), group_off.ctypes.data, n_groups, cell_group_off.ctypes.data, n_cells, device, dup.ctypes.data, survivor.ctypes.data,
+        cell_dups.ctypes.data))
+    return dup[:n_groups], survivor[:n_groups], cell_dups[:n_cells]
+
+
+def drop_groups(order, group_off, cell_group_off, dup):
+    """A collated order without the groups marked in ``dup``: the NumPy compaction behind ``dedup_umis``.  Returns
+    ``(order, group_off, cell_group_off, cell_rec_off)`` of the deduplicated collation -- the marked groups' positions are
+    removed, everything else stays in place."""
+    order = np.asarray(order)
+    group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+    cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
+    keep = np.asarray(dup) == 0
+    if len(keep) != len(group_off) - 1:
+        raise ValueError("dup must have one entry per group")
+    sizes = np.diff(group_off.astype(np.int64))
+    new_group_off = np.zeros(int(keep.sum()) + 1, dtype=np.uint64)
+    np.cumsum(sizes[keep], out=new_group_off[1:])
+    kept_before = np.zeros(len(keep) + 1, dtype=np.uint64)
+    np.cumsum(keep, out=kept_before[1:])
+    new_cell_group_off = kept_before[cell_group_off.astype(np.int64)]
+    return (np.ascontiguousarray(order[np.repeat(keep, sizes)]), new_group_off, new_cell_group_off,
+            new_group_off[new_cell_group_off.astype(np.int64)])
+
+
 def gather_names(names, idx):
     """``names`` (a ``(blob, offsets)`` pair) in the order ``idx``: the NumPy gather of a variable-length blob."""
     blob, off = np.asarray(names[0]), np.ascontiguousarray(names[1], dtype=np.int64)
@@ -381,7 +443,50 @@ def gather_names(names, idx):
     return np.ascontiguousarray(blob[src]), new_off
 
 
-def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes, collate, mode):
+def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, sec, barcodes, umis, collate, mode):
+    """``em_cells_records_sparse(..., barcodes=, names=, umis=)`` behind its packing: the one call
+    (``collate="device"``, oem_em_run_cells_records_umis_sparse), or the seven steps it replaces."""
+    blob, off = names
+    bc_blob, bc_off = barcodes
+    um_blob, um_off = umis
+    n = len(records)
+    if collate == "host":
+        order_bc, cell_rec_off = collate_barcodes((bc_blob, bc_off), device=device)
+        order_names, group_off, cell_group_off = collate_names(gather_names((blob, off), order_bc), cell_rec_off,
+                                                               None if sec is None else sec[order_bc], mode=mode, device=device)
+        order = order_bc[order_names]
+        dup, _, cell_dups = dedup_umis((um_blob, um_off), order, group_off, cell_group_off, flags=records["flags"], device=device)
+        order, group_off, cell_group_off, cell_rec_off = drop_groups(order, group_off, cell_group_off, dup)
+        out = _em_cells_records_plain(F, txp_len, records[order], group_off, cell_group_off, coverage, max_iter, conv_thresh, device)
+        return (*out, order, cell_rec_off, cell_dups)
+    one = np.zeros(1, dtype=np.uint8)
+    blob, bc_blob, um_blob = (b if len(b) else one for b in (blob, bc_blob, um_blob))
+    model, bin_width, growth_rate = _coverage_args(coverage)
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    kept = np.zeros(max(n, 1), dtype=np.uint32)
+    cell_rec_off = np.empty(n + 1, dtype=np.uint64)
+    cell_dups = np.zeros(max(n, 1), dtype=np.uint64)
+    n_groups, n_cells, n_surv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_em_run_cells_records_umis_sparse(
+        C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
+        bc_blob.ctypes.data if n else None, bc_off.ctypes.data, blob.ctypes.data if n else None, off.ctypes.data,
+        None if sec is None or not n else sec.ctypes.data, um_blob.ctypes.data, um_off.ctypes.data, _COLLATE_MODES[mode], bin_width, model,
+        growth_rate, device, max_iter, conv_thresh, order.ctypes.data, C.byref(n_surv), cell_rec_off.ctypes.data, C.byref(n_cells), None,
+        C.byref(n_groups), None, kept.ctypes.data, cell_dups.ctypes.data, C.byref(res)))
+    nc = int(n_cells.value)
+    try:
+        tables = _discard_tables(L, res, nc)
+    except BaseException:
+        L.oem_cells_result_destroy(res)
+        raise
+    return (*_take_cells_result(res, nc, L), kept[:int(n_groups.value)].copy(), tables, order[:int(n_surv.value)].copy(),
+            cell_rec_off[:nc + 1].copy(), cell_dups[:nc].copy())
+
+
+def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes, collate, mode,
+                               umis=None):
     """``em_cells_records_sparse(..., names=, barcodes=)``: the one call (``collate="device"``), or the join it replaces."""
     from .types import pack_read_names
     records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
@@ -397,6 +502,11 @@ def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thr
         sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
         if len(sec) != n:
             raise ValueError("secondary must have one entry per record")
+    if umis is not None:
+        if _n_packed(umis) != n:
+            raise ValueError("umis must have one entry per record")
+        return _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, (blob, off), sec, (bc_blob, bc_off),
+                                      pack_read_names(umis, n), collate, mode)
     if collate == "host":   # the four steps the one call replaces
         order_bc, cell_rec_off = collate_barcodes((bc_blob, bc_off), device=device)
         out = _em_cells_records_names(F, txp_len, records[order_bc], cell_rec_off, coverage, max_iter, conv_thresh, device,
@@ -479,7 +589,7 @@ def _em_cells_records_names(F, txp_len, records, cell_rec_off, coverage, max_ite
 
 def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
                             conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None, collate: str = "host",
-                            mode: str = "sort", barcodes=None):
+                            mode: str = "sort", barcodes=None, umis=None):
     """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
     oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
     model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
@@ -505,14 +615,25 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     records, names and ``secondary``, and the names call: the path the one call replaces.  Both return the seven
     values of the names form -- ``order`` is the composed one, the input index of every collated position -- and
     ``cell_rec_off`` as an eighth.
+
+    ``umis`` (one per record, as ``dedup_umis`` takes them; goes with ``barcodes``): the input is not UMI-deduplicated
+    (the reference wants it to be, docs/index.md:308-312).  Inside every cell the reads whose first records carry the
+    same UMI are one molecule and only the first of them is counted; the records' own ``flags`` say which are unmapped.
+    ``collate="device"`` is one call (oem_em_run_cells_records_umis_sparse): the duplicates leave the collation on the
+    device and their records are never gathered.  ``collate="host"`` is the join it replaces: ``collate_barcodes``, the
+    NumPy gathers, ``collate_names``, the composed order, ``dedup_umis``, ``drop_groups``, the records call.  Both
+    return the eight values of the barcodes form over the DEDUPLICATED collation -- ``order`` holds the surviving
+    positions only -- and ``cell_dups``, the duplicates dropped from every cell, as a ninth.
     """
-    from .builder import check_batch, filters_c
+    from .builder import filters_c
     if collate not in ("host", "device"):
         raise ValueError(f"collate must be 'host' or 'device', not {collate!r}")
     if mode not in _COLLATE_MODES:
         raise ValueError(f"mode must be one of {sorted(_COLLATE_MODES)}, not {mode!r}")
     if names is None and secondary is not None:
         raise ValueError("secondary goes with names")
+    if umis is not None and barcodes is None:
+        raise ValueError("umis goes with barcodes: the molecules of a cell are found where the cells are")
     if barcodes is not None:
         if cell_group_off is not None or group_off is not None:
             raise ValueError("with barcodes the cells are found by the call: group_off and cell_group_off must be None")
@@ -522,7 +643,7 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
     if barcodes is not None:
         return _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes,
-                                          collate, mode)
+                                          collate, mode, umis)
     if names is not None and collate == "device":
         return _em_cells_records_names(F, txp_len, records, cell_group_off, coverage, max_iter, conv_thresh, device, names,
                                        secondary, mode)
@@ -533,6 +654,13 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
         if len(records) != len(order):
             raise ValueError("names must have one entry per record")
         records = records[order]
+    out = _em_cells_records_plain(F, txp_len, records, group_off, cell_group_off, coverage, max_iter, conv_thresh, device)
+    return out if order is None else (*out, order)
+
+
+def _em_cells_records_plain(F, txp_len, records, group_off, cell_group_off, coverage, max_iter, conv_thresh, device):
+    """``em_cells_records_sparse`` on collated records: oem_em_run_cells_records_sparse and its six values."""
+    from .builder import check_batch
     records, group_off = check_batch(records, group_off)
     cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
     if cell_group_off.ndim != 1 or len(cell_group_off) < 1:
@@ -551,8 +679,7 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     except BaseException:
         L.oem_cells_result_destroy(res)
         raise
-    out = (*_take_cells_result(res, n_cells, L), kept, tables)
-    return out if order is None else (*out, order)
+    return (*_take_cells_result(res, n_cells, L), kept, tables)
 
 
 class CellsStream:

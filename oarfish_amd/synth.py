@@ -728,6 +728,113 @@ def interleave_cells(records, names, secondary, cell_rec_off, barcodes, seed: in
             None if secondary is None else np.asarray(secondary)[perm], gather_names((bc_blob, bc_off), cell_of), perm)
 
 
+def add_umi_duplicates(records, names, secondary, barcodes, rate: float, seed: int = BASE_SEED + 29, umi_len: int = 12):
+    """An uncollated single-cell input (``interleave_cells``) given UMIs and PCR duplicates, the input of
+    ``em_cells_records_sparse(..., barcodes=, names=, umis=)``.  ``names`` and ``barcodes`` are ``(blob, offsets)`` pairs,
+    one entry per record; a read is the records of one barcode that share a name.
+
+    Every read gets a UMI of ``umi_len`` nucleotides, the same on all its records, that is unique inside its cell by
+    construction: the read's rank in its cell through an odd multiplier modulo ``4 ** umi_len``, written in base 4.  A
+    fraction ``rate`` of the reads that have no unmapped record is copied 1 to 3 times: identical records and flags, the
+    same barcode and UMI, a fresh name (the read's, ``~`` and the copy's number).  The copied records are inserted at
+    random record positions; the original records keep their relative order.
+
+    Returns ``(records, names, secondary, barcodes, umis, copies)``: the augmented arrays, ``umis`` a ``(blob, offsets)``
+    pair, and ``copies`` a dict from barcode (``bytes``) to the number of copied READS it received -- what deduplication
+    has to drop from that cell.  A pure function of its arguments."""
+    from .em import gather_names
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError("rate must be in [0, 1]")
+    if not 1 <= umi_len <= 31:
+        raise ValueError("umi_len must be in [1, 31]")
+    blob, off = np.asarray(names[0], dtype=np.uint8), np.ascontiguousarray(names[1], dtype=np.int64)
+    bc_blob, bc_off = np.asarray(barcodes[0], dtype=np.uint8), np.ascontiguousarray(barcodes[1], dtype=np.int64)
+    n = len(records)
+    if len(off) != n + 1 or len(bc_off) != n + 1:
+        raise ValueError("names and barcodes must have one entry per record")
+
+    def padded(b, o, lead=0):
+        """The strings as the rows of a zero-padded matrix (none holds a 0 byte), behind `lead` free columns."""
+        lens = np.diff(o)
+        mat = np.zeros((n, lead + int(lens.max(initial=0))), dtype=np.uint8)
+        rows = np.repeat(np.arange(n), lens)
+        mat[rows, lead + np.arange(int(o[-1]) - int(o[0])) - np.repeat(o[:-1] - o[0], lens)] = b[int(o[0]):int(o[-1])]
+        return mat
+
+    def distinct(mat):
+        """(the distinct rows, every row's index among them).  The rows are told apart by a 64-bit hash -- sorting words is
+        far cheaper than sorting rows -- and then compared with their group's first row, so a collision is an error, not
+        a wrong answer.  The distinct rows come in the order of their hashes: fixed by the rows, not by their order."""
+        if not mat.shape[1]:
+            return mat[:min(n, 1)], np.zeros(n, dtype=np.int64)
+        w = -(-mat.shape[1] // 8)
+        words = np.zeros((n, 8 * w), dtype=np.uint8)
+        words[:, :mat.shape[1]] = mat
+        words = words.view(np.uint64)
+        mults = np.random.default_rng(0x5EED).integers(1, 2 ** 63, size=w, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+        h = np.zeros(n, dtype=np.uint64)
+        for k in range(w):
+            h = (h ^ words[:, k]) * mults[k]
+            h ^= h >> np.uint64(29)
+        _, first, inv = np.unique(h, return_index=True, return_inverse=True)
+        inv = inv.reshape(-1).astype(np.int64)
+        if not np.array_equal(words[first[inv]], words):
+            raise RuntimeError("two different strings share a hash: change the hash's seed")
+        return mat[first], inv
+
+    # the cells, then the reads: a read's key is its cell's number (4 bytes, big-endian) and its name
+    cell_rows, cell_of = distinct(padded(bc_blob, bc_off))
+    cell_label = [r.tobytes().rstrip(b"\0") for r in cell_rows]
+    key = padded(blob, off, lead=4)
+    key[:, :4] = cell_of.astype(">u4").view(np.uint8).reshape(n, 4)
+    read_rows, read_of = distinct(key)
+    n_reads = len(read_rows) if n else 0
+    read_cell = (np.ascontiguousarray(read_rows[:, :4]).view(">u4").reshape(-1).astype(np.int64) if n_reads
+                 else np.zeros(0, dtype=np.int64))
+    cell_reads = np.bincount(read_cell, minlength=len(cell_label))
+    first_read = np.zeros(len(cell_label) + 1, dtype=np.int64)
+    np.cumsum(cell_reads, out=first_read[1:])
+    by_cell = np.argsort(read_cell, kind="stable")
+    read_rank = np.empty(n_reads, dtype=np.int64)                              # a read's rank among the reads of its cell
+    read_rank[by_cell] = np.arange(n_reads, dtype=np.int64) - first_read[read_cell[by_cell]]
+    if cell_reads.max(initial=0) > 4 ** umi_len:
+        raise ValueError("umi_len is too short for the largest cell")
+    rng = np.random.default_rng([seed, 0xD0B1])
+    mult, add = 2 * int(rng.integers(0, 4 ** umi_len // 2)) + 1, int(rng.integers(0, 4 ** umi_len))
+    mask = np.uint64(4 ** umi_len - 1)
+    vals = (read_rank.astype(np.uint64) * np.uint64(mult) + np.uint64(add)) & mask     # (wraps mod 2^64: a multiple of 4^umi_len)
+    umi_of_read = _NUC[((vals[:, None] >> (2 * np.arange(umi_len, dtype=np.uint64))[None, :]) & np.uint64(3)).astype(np.int64)]
+
+    unmapped = np.bincount(read_of, weights=(np.asarray(records["flags"]) & 1) != 0, minlength=n_reads) > 0   # OEM_REC_UNMAPPED
+    n_copies = np.where((rng.random(n_reads) < rate) & ~unmapped, rng.integers(1, 4, size=n_reads), 0)
+    per_cell = np.bincount(read_cell, weights=n_copies, minlength=len(cell_label)).astype(np.int64)
+    copies = {cell_label[c]: int(k) for c, k in enumerate(per_cell) if k}
+    # a copied read's records, each as often as its read is copied; the copy's number is its place among those repeats
+    by_read = np.argsort(read_of, kind="stable")
+    reps = n_copies[read_of[by_read]]
+    src = np.repeat(by_read, reps)
+    starts = np.zeros(len(by_read) + 1, dtype=np.int64)
+    np.cumsum(reps, out=starts[1:])
+    copy_no = np.arange(len(src), dtype=np.int64) - np.repeat(starts[:-1], reps) + 1
+    # their names: the read's, "~" and the number
+    cblob, coff = gather_names((blob, off), src)
+    coff = coff.astype(np.int64)
+    new_off = coff + 2 * np.arange(len(src) + 1, dtype=np.int64)
+    new_blob = np.empty(int(new_off[-1]), dtype=np.uint8)
+    new_blob[np.arange(int(coff[-1]), dtype=np.int64) + 2 * np.repeat(np.arange(len(src), dtype=np.int64), np.diff(coff))] = cblob
+    new_blob[new_off[1:] - 2] = ord("~")
+    new_blob[new_off[1:] - 1] = 48 + copy_no
+    where = np.concatenate([np.arange(n, dtype=np.float64), rng.uniform(0.0, float(max(n, 1)), size=len(src))])
+    perm = np.argsort(where, kind="stable")
+    src_all = np.concatenate([np.arange(n, dtype=np.int64), src])[perm]
+    all_names = (np.concatenate([blob[int(off[0]):int(off[-1])], new_blob]), np.concatenate([off - off[0], int(off[-1] - off[0]) + new_off[1:]]))
+    umis = (np.ascontiguousarray(umi_of_read[read_of[src_all]]).reshape(-1),
+            np.arange(len(src_all) + 1, dtype=np.uint64) * np.uint64(umi_len))
+    return (np.ascontiguousarray(records[src_all]), gather_names(all_names, perm),
+            None if secondary is None else np.ascontiguousarray(np.asarray(secondary)[src_all]),
+            gather_names((bc_blob, bc_off), src_all), umis, copies)
+
+
 def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, unmapped_every: int = 0):
     """``shuffle_cell_records``' barcode-collated input cut into batches for a barcoded session
     (``CellsStream(barcodes=True)``), every record with its cell's barcode.  ``barcodes``: one per cell

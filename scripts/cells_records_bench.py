@@ -34,6 +34,17 @@ slice with a 10x barcode per record, alternated in one process, --runs repeats (
 
 With the peak device memory of (a) and (b) and the session's groups_before_finish.
 
+--umis is the leg of UMI deduplication (profiles/cells_records_umis_bench.json): the --barcodes leg's input (the slice
+shuffled, named, with a 10x barcode per record, interleaved uniformly) given UMIs and PCR duplicates by
+synth.add_umi_duplicates(rate=0.1), alternated in one process, --runs repeats (five), best to worst:
+
+  (a) the one call with deduplication (oem_em_run_cells_records_umis_sparse, em_cells_records_sparse(..., umis=));
+  (b) oem_em_run_cells_records_barcodes_sparse on the same augmented records without UMIs: the duplicates are counted;
+  (c) the collate="host" join: collate_barcodes, the NumPy gathers, collate_names, dedup_umis, drop_groups, the records call;
+  (d) (a) with every UMI empty.
+
+With (a) - (b), (a)/(c), (d) - (b) beside (b)'s own spread, and the peak device memory of (a) and (b).
+
 --barcodes-any-order-stream is the leg of the any-order barcoded session
 (profiles/cells_barcodes_any_order_stream_bench.json): the slice with UUID names and a 10x barcode per record, interleaved
 by synth.interleave_cells in both its forms (uniform, blocks), alternated in one process, --runs repeats (five), best to
@@ -247,6 +258,79 @@ def barcodes_leg(args, cr, res, save):
         del rec, names, sec, bc, rec0, names0, sec0
 
 
+def umis_leg(args, cr, res, save):
+    """The --umis leg: the --barcodes leg's input (the slice shuffled, named, barcoded, interleaved uniformly) given UMIs
+    and PCR duplicates by synth.add_umi_duplicates(rate=0.1).  Alternated in one process: (a) the one call with
+    deduplication (oem_em_run_cells_records_umis_sparse); (b) oem_em_run_cells_records_barcodes_sparse on the same
+    augmented records without UMIs -- the path that counts the duplicates as molecules; (c) the collate="host" join --
+    collate_barcodes, the NumPy gathers, collate_names, dedup_umis, drop_groups, the records call; (d) (a) with every UMI
+    empty.  Reported: (a) - (b), the device cost of deduplication (it can be negative: (a) gathers, filters and runs
+    fewer reads); (a) / (c); (d) against (b)'s own spread, what an unused UMI argument costs; the peak device memory of
+    (a) against (b)."""
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    def run(rec, names, sec, bc, umis=None, collate="device"):
+        return oarfish_amd.em_cells_records_sparse(f, tl, rec, None, None, names=names, secondary=sec, barcodes=bc, umis=umis, collate=collate)
+
+    def head(pair, m):
+        return pair[0][:int(pair[1][m])], pair[1][:m + 1]
+
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        rec1, names1, sec1, bc1, _ = synth.interleave_cells(rec0, names0, sec0, cro, synth.make_barcodes(n, "10x"), how="uniform")
+        del rec0, names0, sec0
+        t0 = time.perf_counter()
+        rec, names, sec, bc, umis, copies = synth.add_umi_duplicates(rec1, names1, sec1, bc1, rate=0.1)
+        r = res[style] = dict(records_before=int(len(rec1)), records=int(len(rec)), copied_reads=int(sum(copies.values())),
+                              name_bytes=int(names[0].nbytes), record_bytes=int(rec.nbytes), barcode_bytes=int(bc[0].nbytes),
+                              umi_bytes=int(umis[0].nbytes), add_umi_duplicates_s=round(time.perf_counter() - t0, 2))
+        del rec1, names1, sec1, bc1
+        no_umis = (np.zeros(0, dtype=np.uint8), np.zeros(len(rec) + 1, dtype=np.uint64))
+        m = min(len(rec), int(cro[min(args.warm_cells, n)]))   # warm-up on the first records of the input
+        for u in (head(umis, m), None):
+            run(rec[:m], head(names, m), sec[:m], head(bc, m), u)
+        runs = dict(a=[], b=[], c=[], d=[])
+        for k in range(args.runs):
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_a = clock(lambda: run(rec, names, sec, bc, umis))
+                r["peak_device_bytes_during_the_one_call"] = int(pk.peak)
+            else:
+                dt, got_a = clock(lambda: run(rec, names, sec, bc, umis))
+            runs["a"].append(dt)
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_b = clock(lambda: run(rec, names, sec, bc))
+                r["peak_device_bytes_during_the_barcodes_call"] = int(pk.peak)
+            else:
+                dt, got_b = clock(lambda: run(rec, names, sec, bc))
+            runs["b"].append(dt)
+            dt, got_c = clock(lambda: run(rec, names, sec, bc, umis, collate="host"))
+            runs["c"].append(dt)
+            runs["d"].append(clock(lambda: run(rec, names, sec, bc, no_umis))[0])
+            if k == 0:   # the one call is the join; every copied read is dropped; the barcodes call counts them
+                assert all(np.array_equal(got_a[i], got_c[i]) for i in (0, 1, 4, 6, 7, 8)) and got_a[5] == got_c[5]
+                assert int(got_a[8].sum()) == sum(copies.values()) and len(got_b[4]) == len(got_a[4]) + int(got_a[8].sum())
+                r["n_cells"], r["reads_counted_with_dedup"], r["reads_counted_without"] = int(len(got_a[7]) - 1), int(len(got_a[4])), int(len(got_b[4]))
+            del got_a, got_b, got_c
+            print(f"[bench] {style} run {k}: (a) {runs['a'][-1]:.3f} s, (b) {runs['b'][-1]:.3f} s, (c) {runs['c'][-1]:.3f} s, (d) {runs['d'][-1]:.3f} s",
+                  flush=True)
+            r["one_call_with_umis"], r["barcodes_call_without_umis"] = spread(runs["a"]), spread(runs["b"])
+            r["host_join"], r["one_call_with_empty_umis"] = spread(runs["c"]), spread(runs["d"])
+            r["dedup_device_cost_s_a_minus_b"] = round(min(runs["a"]) - min(runs["b"]), 4)
+            r["one_call_over_host_join"] = round(min(runs["a"]) / min(runs["c"]), 3)
+            r["empty_umis_minus_barcodes_call_s"] = round(min(runs["d"]) - min(runs["b"]), 4)
+            r["barcodes_call_own_spread_s"] = round(max(runs["b"]) - min(runs["b"]), 4)
+            save()
+        del rec, names, sec, bc, umis
+
+
 def barcodes_stream_leg(args, cr, res, save):
     """The --barcodes-stream leg (see the module docstring); fills res[style] for every name style."""
     n = args.cells
@@ -423,6 +507,7 @@ def main():
     ap.add_argument("--models", type=int, nargs="*", default=[-1, 1])
     ap.add_argument("--names", action="store_true", help="the leg from names and records in input order")
     ap.add_argument("--barcodes", action="store_true", help="the leg from records in any order: cells from barcodes")
+    ap.add_argument("--umis", action="store_true", help="the leg of the one call with UMI deduplication against the barcodes call and the host join")
     ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
     ap.add_argument("--barcodes-any-order-stream", action="store_true",
                     help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
@@ -431,10 +516,11 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.barcodes_stream or args.barcodes_any_order_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.umis or args.barcodes_stream or args.barcodes_any_order_stream else 3
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
                                 "cells_barcodes_stream_bench.json" if args.barcodes_stream else
+                                "cells_records_umis_bench.json" if args.umis else
                                 "cells_records_barcodes_bench.json" if args.barcodes else
                                 "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
     T, n = args.txps, args.cells
@@ -504,6 +590,10 @@ def main():
         return
     if args.barcodes_stream:
         barcodes_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
+    if args.umis:
+        umis_leg(args, cr, res, save)
         print(json.dumps(res))
         return
     if args.barcodes:
