@@ -978,6 +978,9 @@ typedef struct {
                                                          the arena while finish lays it out by cell) */
 #define OEM_CELLS_STREAM_INFO_BARCODE_MISSES 8u       /* survivors that missed the first lookup of their batch */
 #define OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS 9u  /* the barcode table's capacity (after finish: the final one) */
+/* a UMI session (oem_cells_stream_set_umis); 0 on every other session */
+#define OEM_CELLS_STREAM_INFO_UMI_DUP_READS 10u       /* reads dropped as duplicates, in groups that have run */
+#define OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS 11u     /* their records */
 
 /* Argument errors (n_txps = 0, opts or out NULL, coverage = 1 without txp_len, with bin_width = 0 or with a model
  * other than 0 / 1, a non-zero reserved word) are reported before any device is touched; without a device the call
@@ -1100,6 +1103,51 @@ int oem_cells_stream_push_barcodes(oem_cells_stream *s, const oem_aln_record *re
  * 2^31 - 2 survivors in the session, refused at the batch that crosses (OEM_ERR_ARG); OEM_ERR_OOM with everything
  * released. */
 int oem_cells_stream_set_barcodes_any_order(oem_cells_stream *s, uint32_t mode /* OEM_COLLATE_SORT, OEM_COLLATE_ADJACENT */);
+/* A UMI SESSION: oem_em_run_cells_records_umis_sparse's deduplication for the two barcoded sessions, so that a reader
+ * of a single-cell BAM need not deduplicate first (the reference wants "already (UMI) deduplicated reads",
+ * docs/index.md:308-312).  oem_cells_stream_set_umis comes after either set_barcodes call and before any push.  On a
+ * session that is not barcoded, after a push, after finish, or a second time: OEM_ERR_STATE.  On a UMI session
+ * oem_cells_stream_push_barcodes returns OEM_ERR_STATE; on every other session oem_cells_stream_push_barcodes_umis does.
+ *
+ * The rule (oarfish_amd/csrc/oem_collate.h, "UMIs in the sessions").  Every batch carries one UMI byte string per
+ * record (umis with n_records + 1 offsets from 0); the empty string means no UB tag.  An unmapped record's UMI is never
+ * examined; a survivor's UMI may be empty and may not hold a 0 byte.  Cells are cut or interned by the form's own rule;
+ * inside a cell, behind the name collation, the reads whose heads carry the same non-empty UMI are one class, its
+ * smallest read survives and the others leave with all their records (oem_dedup_umis' rule).  Classes never span
+ * cells.  With S the survivors' indices, ascending:
+ *   - any-order form: finish gives exactly what oem_em_run_cells_records_umis_sparse gives on records[S], barcodes[S],
+ *     names[S], secondary[S], umis[S], order being S[order of the one call];
+ *   - collated form (a barcode that comes back is a NEW cell, so no one call names it): oem_collate_names on the
+ *     S-arrays with the streamed rule's cell_rec_off, oem_dedup_umis on its output with umis[S], the duplicates'
+ *     positions dropped, oem_em_run_cells_records_sparse on what remains.  Two runs of one barcode that hold the same
+ *     UMI keep both reads.
+ * A session all of whose UMIs are empty gives exactly the result of the same session without UMIs.
+ *
+ * oem_cells_stream_push_barcodes_umis has oem_cells_stream_push_barcodes' preconditions and checks on the calling
+ * thread: umi_off present, from 0 and not decreasing; umis present when its last offset is above 0.  An argument error
+ * rejects that batch only and uses no ticket.  The UMIs are copied into page-locked staging with the rest; no UMI byte
+ * is touched by the host between staging and the result.  A survivor's UMI with a 0 byte is found on the device and is
+ * sticky: OEM_ERR_ARG, "the UMI of record <i> contains a 0 byte" with the batch's "ticket <t>" and the session-global
+ * index; the smallest such index of the batch wins, and on one record the order is barcode, name, UMI.
+ *
+ * A bad ref_id: the sessions differ from the one call and from each other.  The any-order form checks ref_id per batch
+ * on every surviving record, so a bad ref_id in a record that would later turn out to be a duplicate is an error there;
+ * the collated form finds it in the group, among the reads that remain.  The any-order form's bound of 2^31 - 2
+ * survivors counts the duplicates' records too.
+ *
+ * After finish, oem_cells_stream_barcodes_dims / _barcodes_copy describe the DEDUPLICATED collation: n_survivors counts
+ * the positions of out_order and out_cell_rec_off counts positions of it, n_groups counts the reads that remain,
+ * n_unmapped is unchanged; records accepted = n_unmapped + n_survivors + OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS.  A
+ * duplicate is in no discard table.  oem_cells_stream_umis_copy gives the duplicates (reads) dropped from every cell
+ * (n_cells entries); before finish, or on a session without UMIs: OEM_ERR_STATE.  The arena keeps a survivor's UMI and
+ * an 8-byte offset beside its name (OEM_CELLS_STREAM_INFO_ARENA_BYTES counts them). */
+int oem_cells_stream_set_umis(oem_cells_stream *s);
+int oem_cells_stream_push_barcodes_umis(oem_cells_stream *s, const oem_aln_record *records, uint64_t n_records,
+                                        const uint8_t *barcodes, const uint64_t *barcode_off,
+                                        const uint8_t *names, const uint64_t *name_off,
+                                        const uint8_t *secondary /* or NULL */,
+                                        const uint8_t *umis, const uint64_t *umi_off, uint64_t *out_ticket);
+int oem_cells_stream_umis_copy(const oem_cells_stream *s, uint64_t *out_cell_dups /* n_cells */);
 /* After a successful oem_cells_stream_finish of a barcoded session (otherwise OEM_ERR_STATE): the sizes of what
  * oem_cells_stream_barcodes_copy gives (each may be NULL) -- the cells, the survivors, the reads (record groups) of all
  * cells, the bytes of all labels, and the unmapped records that were skipped. */

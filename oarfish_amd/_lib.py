@@ -40,6 +40,8 @@ OEM_CELLS_STREAM_INFO_GROUPS_BATCHED = 6
 OEM_CELLS_STREAM_INFO_ARENA_BYTES = 7
 OEM_CELLS_STREAM_INFO_BARCODE_MISSES = 8
 OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS = 9
+OEM_CELLS_STREAM_INFO_UMI_DUP_READS = 10
+OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS = 11
 OEM_RECORDS_STREAM_INFO_BATCHES = 1
 OEM_RECORDS_STREAM_INFO_GROUPS = 2
 OEM_RECORDS_STREAM_INFO_RECORDS = 3
@@ -84,6 +86,7 @@ ABI_SYMBOLS = [
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_set_barcodes", "oem_cells_stream_push_barcodes", "oem_cells_stream_barcodes_dims",
     "oem_cells_stream_barcodes_copy", "oem_cells_stream_set_barcodes_any_order",
+    "oem_cells_stream_set_umis", "oem_cells_stream_push_barcodes_umis", "oem_cells_stream_umis_copy",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
     "oem_records_stream_destroy", "oem_records_stream_set_names", "oem_records_stream_push_names",
@@ -270,6 +273,9 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_stream_push_barcodes.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.oem_cells_stream_barcodes_dims.argtypes = [vp] + [C.POINTER(u64)] * 5
     L.oem_cells_stream_barcodes_copy.argtypes = [vp] * 8
+    L.oem_cells_stream_set_umis.argtypes = [vp]
+    L.oem_cells_stream_push_barcodes_umis.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.oem_cells_stream_umis_copy.argtypes = [vp, vp]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
     L.oem_cells_stream_push.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]
     L.oem_cells_stream_finish.argtypes = [vp, C.POINTER(vp)]

@@ -81,10 +81,17 @@ int barcodes_stream_create(const BarcodesEnv &env, bool any_order, BarcodesStrea
 // what oem_cells_stream_info reports of an any-order session (0 for a collated one): the arena's peak in bytes, the
 // survivors that missed the first lookup of their batch, the table's capacity
 void barcodes_stream_table_info(BarcodesStream *b, uint64_t *arena_peak, uint64_t *misses, uint64_t *slots);
-// oem_cells_stream_push_barcodes behind its NULL-session check
+// oem_cells_stream_push_barcodes and (with_umis) oem_cells_stream_push_barcodes_umis behind their NULL-session check: the
+// call that does not belong to the session's kind is OEM_ERR_STATE
 int barcodes_stream_push(BarcodesStream *b, const char *who, const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
                          const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary,
-                         uint64_t *out_ticket);
+                         bool with_umis, const uint8_t *umis, const uint64_t *umi_off, uint64_t *out_ticket);
+// oem_cells_stream_set_umis behind its checks of the session: before any push, once (oem_collate.h, "UMIs in the sessions")
+int barcodes_stream_set_umis(BarcodesStream *b, const char *who);
+// the duplicates dropped by the groups that have run: reads, and their records (0 without UMIs)
+void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *dup_records);
+// oem_cells_stream_umis_copy: the duplicates (reads) every cell lost, after finish
+int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_dups);
 bool barcodes_stream_push_in_flight(BarcodesStream *b);
 // finish, before the group workers are stopped: no further push is accepted, the staged batches are parsed, the open
 // cell is closed and what the arena still holds goes to the workers

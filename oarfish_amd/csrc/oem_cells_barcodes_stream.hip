@@ -35,6 +35,17 @@
 // (BarcodeIntern, oem_cells_barcodes_sort_stream.hip) and the arena keeps a cell id per survivor; nothing is handed to the
 // workers before finish, which sorts the survivors by cell id, lays the arena out in that order (finish_any_order) and
 // then makes the last cut of a collated arena whose cells are all closed.
+//
+// A UMI SESSION (oem_cells_stream_set_umis, oem_cells_stream_push_barcodes_umis; oem_collate.h, "UMIs in the sessions") is
+// either form with one UMI per record.  The UMIs take the names' road: staged page-locked with the batch, uploaded, the
+// survivors' gathered into a dense blob and checked for 0 bytes with the empty UMI legal (umis_gather_survivors,
+// oem_dedup_umis.hip), appended to the arena's umis / umi_off, carried by its growth, by the tail's move behind a cut
+// (cubyte beside cbyte) and by finish_any_order's layout by cell.  A group runs dedup_mark behind collate_resident --
+// the arena's blob, its window of umi_off indexed by group-local record -- and dedup_compact where it found duplicates;
+// from there on the group has mp <= m positions, and the order, the gather (under the adjacent cut too: the order is
+// no longer the identity), the filter and the host loop run over the deduplicated collation.  The slot keeps
+// n_positions, the cells' first positions and cell_dups for barcodes_stream_assemble: every later group's place in
+// `order` depends on what the earlier ones lost.  A session without UMIs allocates and launches nothing of this.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -143,15 +154,18 @@ __global__ __launch_bounds__(kBT) void k_order_compose64(uint64_t m, const uint3
 
 // The cells that are not yet run, on the device, in survivor order.  names is 8-byte aligned (an allocation's start) and
 // allocated 16 bytes past cap_bytes; name_off holds n + 1 offsets from 0; sec one byte past cap.
+// A UMI session: umis and umi_off likewise (an empty UMI is legal), 16 bytes past cap_umi_bytes.
 struct Arena {
     DevBuf<oem_aln_record> rec;
-    DevBuf<uint8_t> names, sec;
-    DevBuf<uint64_t> name_off, gidx;
+    DevBuf<uint8_t> names, sec, umis;
+    DevBuf<uint64_t> name_off, gidx, umi_off;
     DevBuf<uint32_t> cell_id; // an any-order session: the survivors' cells
-    uint64_t cap = 0, cap_bytes = 0;
+    uint64_t cap = 0, cap_bytes = 0, cap_umi_bytes = 0;
+    bool with_umis = false;
     uint64_t device_bytes(bool with_ids) const
     {
-        return cap * (sizeof(oem_aln_record) + 2 * sizeof(uint64_t) + 1 + (with_ids ? sizeof(uint32_t) : 0)) + cap_bytes + 32;
+        return cap * (sizeof(oem_aln_record) + 2 * sizeof(uint64_t) + 1 + (with_ids ? sizeof(uint32_t) : 0)) + cap_bytes + 32 +
+               (with_umis ? (cap + 1) * sizeof(uint64_t) + cap_umi_bytes + 16 : 0);
     }
 };
 
@@ -163,7 +177,9 @@ __global__ __launch_bounds__(kBT) void k_sample64(uint64_t n, const uint64_t *__
     if (k < n) dst[k] = src[at[k]];
 }
 
-int arena_make(uint64_t cap, uint64_t cap_bytes, bool with_ids, std::shared_ptr<Arena> *out)
+// umi_bytes: kNoUmis, or the capacity of the UMI blob of a UMI session's arena
+constexpr uint64_t kNoUmis = ~0ull;
+int arena_make(uint64_t cap, uint64_t cap_bytes, bool with_ids, uint64_t umi_bytes, std::shared_ptr<Arena> *out)
 {
     std::shared_ptr<Arena> a(new Arena());
     if (with_ids) OEM_TRY(dev_alloc(&a->cell_id.p, cap, nullptr));
@@ -173,6 +189,14 @@ int arena_make(uint64_t cap, uint64_t cap_bytes, bool with_ids, std::shared_ptr<
     OEM_TRY(dev_alloc(&a->name_off.p, cap + 1, nullptr));
     OEM_TRY(dev_alloc(&a->gidx.p, cap, nullptr));
     OEM_HIP(hipMemset(a->name_off.p, 0, sizeof(uint64_t)));
+    if (umi_bytes != kNoUmis) {
+        OEM_TRY(dev_alloc(&a->umis.p, umi_bytes + 16, nullptr));
+        OEM_TRY(dev_alloc(&a->umi_off.p, cap + 1, nullptr));
+        OEM_HIP(hipMemset(a->umi_off.p, 0, sizeof(uint64_t)));
+        OEM_HIP(hipMemset(a->umis.p, 0, 16));
+        a->with_umis = true;
+        a->cap_umi_bytes = umi_bytes;
+    }
     a->cap = cap;
     a->cap_bytes = cap_bytes;
     *out = std::move(a);
@@ -194,17 +218,20 @@ void host_free(HostMem &h)
 
 inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
-// A staged batch: the records, the two offset tables, the flags, the two blobs.
+// A staged batch: the records, the two offset tables, the flags, the two blobs; in a UMI session the UMIs' offset table
+// and blob behind them.
 struct Batch {
-    uint64_t ticket = 0, n = 0, rec_base = 0, bc_bytes = 0, name_bytes = 0;
-    bool has_sec = false, ready = false;
+    uint64_t ticket = 0, n = 0, rec_base = 0, bc_bytes = 0, name_bytes = 0, umi_bytes = 0;
+    bool has_sec = false, has_umis = false, ready = false;
     HostMem mem;
     size_t at_bc_off() const { return up64(sizeof(oem_aln_record) * n); }
     size_t at_name_off() const { return at_bc_off() + up64(sizeof(uint64_t) * (n + 1)); }
     size_t at_sec() const { return at_name_off() + up64(sizeof(uint64_t) * (n + 1)); }
     size_t at_bc() const { return at_sec() + up64(n); }
     size_t at_names() const { return at_bc() + up64(bc_bytes); }
-    size_t bytes() const { return at_names() + up64(name_bytes); }
+    size_t at_umi_off() const { return at_names() + up64(name_bytes); }
+    size_t at_umis() const { return at_umi_off() + up64(sizeof(uint64_t) * (n + 1)); }
+    size_t bytes() const { return has_umis ? at_umis() + up64(umi_bytes) : at_umi_off(); }
     const char *base() const { return (const char *)mem.p; }
 };
 
@@ -212,8 +239,12 @@ struct Batch {
 struct Slot {
     uint32_t n_cells = 0;
     uint64_t n_records = 0, n_groups = 0;
-    std::vector<uint64_t> order, group_off, cell_group_off; // n_records; n_groups + 1; n_cells + 1
+    std::vector<uint64_t> order, group_off, cell_group_off; // n_positions; n_groups + 1; n_cells + 1
     std::vector<uint32_t> kept;                             // n_groups
+    // n_records positions, or in a UMI session those that remain: then group_off and cell_group_off are the deduplicated
+    // collation's, with the cells' first positions in it and the duplicates (reads) that every cell lost
+    uint64_t n_positions = 0;
+    std::vector<uint64_t> cell_pos_off, cell_dups;          // n_cells + 1; n_cells (a UMI session)
     bool done = false;
 };
 
@@ -249,7 +280,9 @@ struct BarcodesStream {
     // -- the parse worker's state (no lock: one thread; finish reads it after the join) ---------------------------------
     std::shared_ptr<Arena> arena;
     uint64_t arena_n = 0, arena_bytes = 0;     // survivors and name bytes in the arena
+    uint64_t arena_umi_bytes = 0;              // a UMI session: UMI bytes in the arena
     std::vector<uint64_t> cstart, cbyte;       // the arena's cells: first survivor and first name byte; the last one is open
+    std::vector<uint64_t> cubyte;              // a UMI session: the cells' first UMI bytes, beside cbyte
     uint64_t first_cell = 0;                   // the session's number of the arena's first cell
     DevBuf<uint8_t> carry;                     // the open cell's barcode, padded by 16
     uint64_t carry_len = 0;
@@ -261,6 +294,11 @@ struct BarcodesStream {
     // cell id per survivor and nothing is cut before finish
     bool any_order = false;
     BarcodeIntern intern;
+    // a UMI session (oem_cells_stream_set_umis; oem_collate.h, "UMIs in the sessions"): every batch brings a UMI per
+    // record, the arena keeps the survivors', and a group is deduplicated behind its name collation
+    bool with_umis = false;
+    uint64_t dup_reads = 0, dup_records = 0;   // (mu) of the groups that have run
+    std::vector<uint64_t> out_cell_dups;
     uint64_t arena_peak = 0, info_misses = 0, info_slots = 0; // (mu) as of the last batch, for oem_cells_stream_info
 
     // -- what finish leaves ------------------------------------------------------------------------------------------------
@@ -298,9 +336,10 @@ struct BarcodesStream {
         std::lock_guard<std::mutex> lk(mu);
         arena_peak = std::max(arena_peak, held);
     }
-    int arena_reserve(uint64_t need, uint64_t need_bytes);
+    int arena_reserve(uint64_t need, uint64_t need_bytes, uint64_t need_umi_bytes);
     int arena_append(const Batch &b, uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, const uint8_t *d_dnames,
-                     const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id);
+                     const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id,
+                     const uint8_t *d_dumis, const uint64_t *d_dumi_off, uint64_t dumi_bytes);
     int intern_batch(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_order, uint64_t m, const uint8_t *d_dbc,
                      const uint64_t *d_dbc_off, DevBuf<uint32_t> *d_cell_id);
     int finish_any_order(const char *who);
@@ -312,14 +351,16 @@ struct BarcodesStream {
 };
 
 // Room for `need` survivors and `need_bytes` name bytes: the arena as it is, or a larger one with the contents moved over.
-int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes)
+int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes, uint64_t need_umi_bytes)
 {
-    if (arena && need <= arena->cap && need_bytes <= arena->cap_bytes) return OEM_OK;
+    if (arena && need <= arena->cap && need_bytes <= arena->cap_bytes && (!with_umis || need_umi_bytes <= arena->cap_umi_bytes)) return OEM_OK;
     uint64_t cap = arena ? arena->cap : kFirstArenaRecords, cap_bytes = arena ? arena->cap_bytes : kFirstArenaBytes;
+    uint64_t cap_umi = arena ? arena->cap_umi_bytes : kFirstArenaBytes;
     while (cap < need) cap = std::max(cap * 2, need);
     while (cap_bytes < need_bytes) cap_bytes = std::max(cap_bytes * 2, need_bytes);
+    while (cap_umi < need_umi_bytes) cap_umi = std::max(cap_umi * 2, need_umi_bytes);
     std::shared_ptr<Arena> na;
-    OEM_TRY(arena_make(cap, cap_bytes, any_order, &na));
+    OEM_TRY(arena_make(cap, cap_bytes, any_order, with_umis ? cap_umi : kNoUmis, &na));
     note_arena_bytes((arena ? arena->device_bytes(any_order) : 0) + na->device_bytes(any_order)); // (a growing array is held twice)
     if (arena && arena_n && any_order)
         OEM_HIP(hipMemcpy(na->cell_id.p, arena->cell_id.p, sizeof(uint32_t) * arena_n, hipMemcpyDeviceToDevice));
@@ -330,16 +371,23 @@ int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes)
         OEM_HIP(hipMemcpy(na->name_off.p, arena->name_off.p, sizeof(uint64_t) * (arena_n + 1), hipMemcpyDeviceToDevice));
         OEM_HIP(hipMemcpy(na->gidx.p, arena->gidx.p, sizeof(uint64_t) * arena_n, hipMemcpyDeviceToDevice));
     }
+    if (arena && arena_n && with_umis) {
+        if (arena_umi_bytes) OEM_HIP(hipMemcpy(na->umis.p, arena->umis.p, arena_umi_bytes, hipMemcpyDeviceToDevice));
+        OEM_HIP(hipMemset(na->umis.p + arena_umi_bytes, 0, 16));
+        OEM_HIP(hipMemcpy(na->umi_off.p, arena->umi_off.p, sizeof(uint64_t) * (arena_n + 1), hipMemcpyDeviceToDevice));
+    }
     arena = std::move(na);
     return OEM_OK;
 }
 
 // The batch's m survivors into the arena: records, names, flags, session-global indices and (an any-order session)
-// cell ids.  arena_n and arena_bytes are the caller's to advance.
+// cell ids; in a UMI session their UMIs (the dense blob, its m + 1 offsets from 0, its bytes).  arena_n, arena_bytes and
+// arena_umi_bytes are the caller's to advance.
 int BarcodesStream::arena_append(const Batch &b, uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, const uint8_t *d_dnames,
-                                 const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id)
+                                 const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id,
+                                 const uint8_t *d_dumis, const uint64_t *d_dumi_off, uint64_t dumi_bytes)
 {
-    OEM_TRY(arena_reserve(arena_n + m, arena_bytes + dname_bytes));
+    OEM_TRY(arena_reserve(arena_n + m, arena_bytes + dname_bytes, arena_umi_bytes + dumi_bytes));
     Arena &a = *arena;
     OEM_TRY(records_gather(m, d_order, d_in, a.rec.p + arena_n));
     if (dname_bytes) OEM_HIP(hipMemcpyAsync(a.names.p + arena_bytes, d_dnames, dname_bytes, hipMemcpyDeviceToDevice, nullptr));
@@ -350,6 +398,12 @@ int BarcodesStream::arena_append(const Batch &b, uint64_t m, const uint32_t *d_o
     hipLaunchKernelGGL(k_global_index, grid_of(m), dim3(kBT), 0, nullptr, m, d_order, b.rec_base, a.gidx.p + arena_n);
     OEM_HIP(hipGetLastError());
     if (d_cell_id) OEM_HIP(hipMemcpyAsync(a.cell_id.p + arena_n, d_cell_id, sizeof(uint32_t) * m, hipMemcpyDeviceToDevice, nullptr));
+    if (with_umis) {
+        if (dumi_bytes) OEM_HIP(hipMemcpyAsync(a.umis.p + arena_umi_bytes, d_dumis, dumi_bytes, hipMemcpyDeviceToDevice, nullptr));
+        OEM_HIP(hipMemsetAsync(a.umis.p + arena_umi_bytes + dumi_bytes, 0, 16, nullptr));
+        hipLaunchKernelGGL(k_offsets_shift, grid_of(m + 1), dim3(kBT), 0, nullptr, m + 1, d_dumi_off, arena_umi_bytes, a.umi_off.p + arena_n);
+        OEM_HIP(hipGetLastError());
+    }
     OEM_HIP(hipStreamSynchronize(nullptr));
     return OEM_OK;
 }
@@ -392,7 +446,7 @@ int BarcodesStream::finish_any_order(const char *who)
     intern.release();
     const uint64_t nc = bc.n_cells;
     std::shared_ptr<Arena> na;
-    OEM_TRY(arena_make(m, arena_bytes, false, &na));
+    OEM_TRY(arena_make(m, arena_bytes, false, with_umis ? arena_umi_bytes : kNoUmis, &na));
     note_arena_bytes(arena->device_bytes(true) + na->device_bytes(false));
     Arena &a = *arena;
     OEM_HIP(hipMemset(a.names.p + arena_bytes, 0, 16));
@@ -413,6 +467,16 @@ int BarcodesStream::finish_any_order(const char *who)
     cbyte.assign(nc, 0);
     OEM_HIP(hipMemcpy(cstart.data(), bc.cell_rec_off.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
     OEM_HIP(hipMemcpy(cbyte.data(), d_cbyte.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
+    if (with_umis) { // the UMIs as the names: in cell order, and the cells' first UMI bytes
+        OEM_HIP(hipMemset(a.umis.p + arena_umi_bytes, 0, 16));
+        OEM_TRY(gather_name_offsets(bc.order.p, m, a.umi_off.p, na->umi_off.p));
+        OEM_TRY(gather_names(bc.order.p, m, a.umis.p, a.umi_off.p, na->umi_off.p, 0, arena_umi_bytes, na->umis.p, nullptr, nullptr, true));
+        hipLaunchKernelGGL(k_sample64, grid_of(nc), dim3(kBT), 0, nullptr, nc, (const uint64_t *)bc.cell_rec_off.p,
+                           (const uint64_t *)na->umi_off.p, d_cbyte.p);
+        OEM_HIP(hipGetLastError());
+        cubyte.assign(nc, 0);
+        OEM_HIP(hipMemcpy(cubyte.data(), d_cbyte.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
+    }
     first_cell = 0;
     arena = std::move(na);
     (void)who;
@@ -446,6 +510,15 @@ int BarcodesStream::run_batch(const Batch &b)
         OEM_HIP(hipMemcpyAsync(d_sec.p, b.base() + b.at_sec(), n, hipMemcpyHostToDevice, nullptr));
         OEM_HIP(hipMemsetAsync(d_sec.p + n, 0, 8, nullptr));
     }
+    DevBuf<uint8_t> d_umis;
+    DevBuf<uint64_t> d_umi_off;
+    if (with_umis) { // (a batch of a UMI session always has its offsets)
+        OEM_TRY(dev_alloc(&d_umis.p, b.umi_bytes + 16, nullptr));
+        OEM_TRY(dev_alloc(&d_umi_off.p, n + 1, nullptr));
+        OEM_HIP(hipMemcpyAsync(d_umi_off.p, b.base() + b.at_umi_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
+        if (b.umi_bytes) OEM_HIP(hipMemcpyAsync(d_umis.p, b.base() + b.at_umis(), b.umi_bytes, hipMemcpyHostToDevice, nullptr));
+        OEM_HIP(hipMemsetAsync(d_umis.p + b.umi_bytes, 0, 16, nullptr));
+    }
     OEM_HIP(hipStreamSynchronize(nullptr));
 
     // the survivors; their barcodes and names as dense blobs, checked
@@ -462,6 +535,16 @@ int BarcodesStream::run_batch(const Batch &b)
                                  &zero_bc));
     OEM_TRY(parse_survivor_names(d_names.p, b.name_bytes, d_name_off.p, n, d_order.p, m, d_sec.p, &d_dnames, &d_dname_off, &d_dsec,
                                  &dname_bytes, &bad_name, &zero_name));
+    // a UMI session: the survivors' UMIs likewise, an empty one being legal.  On one record the barcode's error comes
+    // first, then the name's, then the UMI's.
+    DevBuf<uint8_t> d_dumis;
+    DevBuf<uint64_t> d_dumi_off;
+    uint64_t dumi_bytes = 0, bad_umi = kNoRecord;
+    if (with_umis) OEM_TRY(umis_gather_survivors(d_umis.p, d_umi_off.p, d_order.p, m, &d_dumis, &d_dumi_off, &dumi_bytes, &bad_umi));
+    if (bad_umi != kNoRecord && bad_umi < bad_bc && bad_umi < bad_name)
+        return fail(OEM_ERR_ARG, "%s: the UMI of record %llu contains a 0 byte", who, (unsigned long long)(b.rec_base + bad_umi));
+    d_umis.reset();
+    d_umi_off.reset();
     if (bad_bc != kNoRecord && bad_bc <= bad_name) {
         if (zero_bc)
             return fail(OEM_ERR_ARG, "%s: the barcode of record %llu contains a 0 byte", who, (unsigned long long)(b.rec_base + bad_bc));
@@ -478,16 +561,18 @@ int BarcodesStream::run_batch(const Batch &b)
         OEM_TRY(intern_batch(b, who, d_in.p, d_order.p, m, d_dbc.p, d_dbc_off.p, &d_cell_id));
         d_dbc.reset();
         d_dbc_off.reset();
-        OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, d_cell_id.p));
+        OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, d_cell_id.p, d_dumis.p, d_dumi_off.p,
+                             dumi_bytes));
         arena_n += m;
         arena_bytes += dname_bytes;
+        arena_umi_bytes += dumi_bytes;
         n_survivors += m;
         return OEM_OK;
     }
 
     // the heads and the batch's cell starts
     DevBuf<uint32_t> d_head, d_start;
-    DevBuf<uint64_t> d_at, d_start_byte;
+    DevBuf<uint64_t> d_at, d_start_byte, d_start_ubyte;
     OEM_TRY(dev_alloc(&d_head.p, m + 1, nullptr));
     OEM_TRY(dev_alloc(&d_at.p, m + 1, nullptr));
     const bool has_carry = !cstart.empty();
@@ -507,6 +592,13 @@ int BarcodesStream::run_batch(const Batch &b)
         OEM_HIP(hipGetLastError());
         OEM_HIP(hipMemcpy(start.data(), d_start.p, sizeof(uint32_t) * nh, hipMemcpyDeviceToHost));
         OEM_HIP(hipMemcpy(start_byte.data(), d_start_byte.p, sizeof(uint64_t) * nh, hipMemcpyDeviceToHost));
+        if (with_umis) { // the same starts over the dense UMIs' offsets: the cells' first UMI bytes
+            OEM_TRY(dev_alloc(&d_start_ubyte.p, nh, nullptr));
+            hipLaunchKernelGGL(k_barcode_starts, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_head.p, (const uint64_t *)d_at.p,
+                               (const uint64_t *)d_dumi_off.p, d_start.p, d_start_ubyte.p);
+            OEM_HIP(hipGetLastError());
+            OEM_HIP(hipStreamSynchronize(nullptr));
+        }
         // the labels of the cells the batch opens: one barcode per cell; the last one is the new carry
         DevBuf<uint64_t> d_lab_off;
         DevBuf<uint8_t> d_lab;
@@ -530,13 +622,18 @@ int BarcodesStream::run_batch(const Batch &b)
     d_dbc.reset();
     d_dbc_off.reset();
 
-    OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, nullptr));
+    OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, nullptr, d_dumis.p, d_dumi_off.p, dumi_bytes));
     for (uint64_t j = 0; j < nh; ++j) {
         cstart.push_back(arena_n + start[j]);
         cbyte.push_back(arena_bytes + start_byte[j]);
     }
+    if (with_umis && nh) { // the cells' first UMI bytes, beside cbyte
+        OEM_HIP(hipMemcpy(start_byte.data(), d_start_ubyte.p, sizeof(uint64_t) * nh, hipMemcpyDeviceToHost));
+        for (uint64_t j = 0; j < nh; ++j) cubyte.push_back(arena_umi_bytes + start_byte[j]);
+    }
     arena_n += m;
     arena_bytes += dname_bytes;
+    arena_umi_bytes += dumi_bytes;
     n_survivors += m;
     return cut_groups(false);
 }
@@ -612,11 +709,21 @@ int BarcodesStream::cut_groups(bool final)
     // what is left moves to the head of a fresh arena; the groups keep the old one
     const uint64_t t = i < n_all ? cstart[i] : arena_n, tb = i < n_all ? cbyte[i] : arena_bytes;
     const uint64_t tail_n = arena_n - t, tail_bytes = arena_bytes - tb;
+    const uint64_t tub = !with_umis ? 0 : i < n_all ? cubyte[i] : arena_umi_bytes, tail_umi_bytes = arena_umi_bytes - tub;
     std::shared_ptr<Arena> old = std::move(arena);
     arena.reset();
     if (!final) {
         const uint64_t cap = std::max(tail_n, std::min(old->cap, 2 * env.group_nnz)) + 4096;
-        OEM_TRY(arena_make(cap, std::max(tail_bytes, std::min<uint64_t>(old->cap_bytes, 64 * cap)) + 4096, false, &arena));
+        OEM_TRY(arena_make(cap, std::max(tail_bytes, std::min<uint64_t>(old->cap_bytes, 64 * cap)) + 4096, false,
+                           with_umis ? std::max(tail_umi_bytes, std::min<uint64_t>(old->cap_umi_bytes, 16 * cap)) + 4096 : kNoUmis, &arena));
+        if (tail_n && with_umis) {
+            if (tail_umi_bytes)
+                OEM_HIP(hipMemcpyAsync(arena->umis.p, old->umis.p + tub, tail_umi_bytes, hipMemcpyDeviceToDevice, nullptr));
+            OEM_HIP(hipMemsetAsync(arena->umis.p + tail_umi_bytes, 0, 16, nullptr));
+            hipLaunchKernelGGL(k_offsets_shift, grid_of(tail_n + 1), dim3(kBT), 0, nullptr, tail_n + 1, (const uint64_t *)(old->umi_off.p + t),
+                               (uint64_t)0 - tub, arena->umi_off.p);
+            OEM_HIP(hipGetLastError());
+        }
         if (tail_n) {
             OEM_HIP(hipMemcpyAsync(arena->rec.p, old->rec.p + t, sizeof(oem_aln_record) * tail_n, hipMemcpyDeviceToDevice, nullptr));
             if (tail_bytes) OEM_HIP(hipMemcpyAsync(arena->names.p, old->names.p + tb, tail_bytes, hipMemcpyDeviceToDevice, nullptr));
@@ -633,8 +740,13 @@ int BarcodesStream::cut_groups(bool final)
     cbyte.erase(cbyte.begin(), cbyte.begin() + i);
     for (uint64_t &v : cstart) v -= t;
     for (uint64_t &v : cbyte) v -= tb;
+    if (with_umis) {
+        cubyte.erase(cubyte.begin(), cubyte.begin() + i);
+        for (uint64_t &v : cubyte) v -= tub;
+    }
     arena_n = tail_n;
     arena_bytes = tail_bytes;
+    arena_umi_bytes = tail_umi_bytes;
     return OEM_OK;
 }
 
@@ -666,21 +778,44 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
     double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     OEM_TRY(collate_resident(in, 0, n_cells, 0, 0, 0, info, &cr));
     tm.lap("barcodes: collate");
+    uint64_t mp = m; // the positions of the group's order: fewer than its records once duplicates are dropped
+    if (a->with_umis) { // the duplicates leave the collation here: their records are never gathered
+        slot->cell_dups.assign(n_cells, 0);
+        slot->cell_pos_off.assign((size_t)n_cells + 1, 0);
+        UmiInput um; // the arena's UMIs; the group's window of their offsets is indexed by group-local record
+        um.who = who;
+        um.d_umis = a->umis.p;
+        um.d_umi_off = a->umi_off.p + r0;
+        UmiMarks mk;
+        OEM_TRY(dedup_mark(um, cr.order.p, nullptr, cr.group_off.p, cr.n_groups, cr.cell_group_off.p, n_cells, 0, &mk, slot->cell_dups.data()));
+        if (mk.n_dups) {
+            OEM_TRY(dedup_compact(mk, m, n_cells, &cr, &mp, slot->cell_pos_off.data()));
+        } else {
+            for (uint32_t c = 0; c <= n_cells; ++c) slot->cell_pos_off[c] = cro[c] - r0;
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            dup_reads += mk.n_dups;
+            dup_records += m - mp;
+        }
+        tm.lap("barcodes: dedup");
+    }
     const uint64_t ng = cr.n_groups;
     slot->n_groups = ng;
+    slot->n_positions = mp;
     slot->cell_group_off.assign((size_t)n_cells + 1, 0);
     slot->group_off.assign(ng + 1, 0);
     slot->kept.assign(ng, 0);
-    slot->order.assign(m, 0);
+    slot->order.assign(mp, 0);
     OEM_HIP(hipMemcpy(slot->cell_group_off.data(), cr.cell_group_off.p, sizeof(uint64_t) * ((size_t)n_cells + 1), hipMemcpyDeviceToHost));
     OEM_HIP(hipMemcpy(slot->group_off.data(), cr.group_off.p, sizeof(uint64_t) * (ng + 1), hipMemcpyDeviceToHost));
     {
         DevBuf<uint64_t> d_order64;
-        OEM_TRY(dev_alloc(&d_order64.p, m, nullptr));
-        hipLaunchKernelGGL(k_order_compose64, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)cr.order.p,
+        OEM_TRY(dev_alloc(&d_order64.p, mp, nullptr));
+        hipLaunchKernelGGL(k_order_compose64, grid_of(mp), dim3(kBT), 0, nullptr, mp, (const uint32_t *)cr.order.p,
                            (const uint64_t *)(a->gidx.p + r0), d_order64.p);
         OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpy(slot->order.data(), d_order64.p, sizeof(uint64_t) * m, hipMemcpyDeviceToHost));
+        OEM_HIP(hipMemcpy(slot->order.data(), d_order64.p, sizeof(uint64_t) * mp, hipMemcpyDeviceToHost));
     }
     RecordsGroup rg;
     rg.n_groups = ng;
@@ -702,9 +837,9 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
     if (!host) {
         DevBuf<oem_aln_record> d_sorted;
         const oem_aln_record *d_recs = a->rec.p + r0;
-        if (env.mode == kCollateSort) { // (the adjacent cut's order is the identity)
-            OEM_TRY(dev_alloc(&d_sorted.p, m, nullptr));
-            OEM_TRY(records_gather(m, cr.order.p, a->rec.p + r0, d_sorted.p));
+        if (env.mode == kCollateSort || mp != m) { // (the adjacent cut's order is the identity until positions are dropped)
+            OEM_TRY(dev_alloc(&d_sorted.p, mp, nullptr));
+            OEM_TRY(records_gather(mp, cr.order.p, a->rec.p + r0, d_sorted.p));
             d_recs = d_sorted.p;
         }
         fc.n_cells = n_cells;
@@ -719,11 +854,11 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
         host = r.host_rerun;
     }
     if (host) { // the host loop: the group's records come down and are gathered here
-        std::vector<uint32_t> order(m);
-        std::vector<oem_aln_record> recs(m), sorted(m);
-        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> order(mp); // (a UMI session: the deduplicated order)
+        std::vector<oem_aln_record> recs(m), sorted(mp);
+        OEM_HIP(hipMemcpy(order.data(), cr.order.p, sizeof(uint32_t) * mp, hipMemcpyDeviceToHost));
         OEM_HIP(hipMemcpy(recs.data(), a->rec.p + r0, sizeof(oem_aln_record) * m, hipMemcpyDeviceToHost));
-        for (uint64_t k = 0; k < m; ++k) {
+        for (uint64_t k = 0; k < mp; ++k) {
             sorted[k] = recs[order[k]];
             if (sorted[k].ref_id >= env.n_txps) return bad_ref(slot->order[k], sorted[k].ref_id);
         }
@@ -792,7 +927,7 @@ void BarcodesStream::work()
 void barcodes_stream_table_info(BarcodesStream *b, uint64_t *arena_peak, uint64_t *misses, uint64_t *slots)
 {
     std::lock_guard<std::mutex> lk(b->mu);
-    *arena_peak = b->any_order ? b->arena_peak : 0;
+    *arena_peak = b->any_order ? b->arena_peak : 0; // (a UMI session: with the arena's UMIs and their offsets)
     *misses = b->any_order ? b->info_misses : 0;
     *slots = b->any_order ? b->info_slots : 0;
 }
@@ -815,11 +950,16 @@ int barcodes_stream_create(const BarcodesEnv &env, bool any_order, BarcodesStrea
 
 int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
                          const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary,
-                         uint64_t *out_ticket)
+                         bool with_umis, const uint8_t *umis, const uint64_t *umi_off, uint64_t *out_ticket)
 {
+    // (set once, before the first push: no lock is needed to read it)
+    if (with_umis != s->with_umis)
+        return fail(OEM_ERR_STATE, with_umis ? "%s: not a UMI session (oem_cells_stream_set_umis)"
+                                             : "%s: a UMI session takes batches through oem_cells_stream_push_barcodes_umis", who);
     // the batch's own checks, on the calling thread, before the session is touched
     const uint64_t n = n_records;
     if (!barcode_off || !name_off) return fail(OEM_ERR_ARG, "%s: barcode_off or name_off is NULL", who);
+    if (with_umis && !umi_off) return fail(OEM_ERR_ARG, "%s: umi_off is NULL", who);
     if (n > kCollateMaxBatch) return fail(OEM_ERR_ARG, "%s: %llu records: at most 2^31 - 2 per batch", who, (unsigned long long)n);
     for (const auto &t : {std::make_pair("barcode", barcode_off), std::make_pair("name", name_off)}) {
         if (t.second[0] != 0) return fail(OEM_ERR_ARG, "%s: %s_off must start at 0", who, t.first);
@@ -830,6 +970,12 @@ int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_recor
     // (a batch of unmapped records only may come without bytes: a blob is needed where its offsets say it has some)
     if (barcode_off[n] && !barcodes) return fail(OEM_ERR_ARG, "%s: barcodes is NULL and barcode_off[n_records] is not 0", who);
     if (name_off[n] && !names) return fail(OEM_ERR_ARG, "%s: names is NULL and name_off[n_records] is not 0", who);
+    if (with_umis) {
+        if (umi_off[0] != 0) return fail(OEM_ERR_ARG, "%s: umi_off must start at 0", who);
+        for (uint64_t i = 0; i < n; ++i)
+            if (umi_off[i + 1] < umi_off[i]) return fail(OEM_ERR_ARG, "%s: umi_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+        if (umi_off[n] && !umis) return fail(OEM_ERR_ARG, "%s: umis is NULL and the UMIs are not all empty", who);
+    }
     if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
 
     Batch *b = nullptr;
@@ -864,6 +1010,8 @@ int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_recor
         nb->bc_bytes = barcode_off[n];
         nb->name_bytes = name_off[n];
         nb->has_sec = secondary != nullptr && n > 0;
+        nb->has_umis = with_umis;
+        nb->umi_bytes = with_umis ? umi_off[n] : 0;
         if (n) { // the smallest idle allocation that holds the batch
             const size_t need = nb->bytes();
             size_t best = s->pool.size();
@@ -904,6 +1052,8 @@ int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_recor
         if (b->has_sec) std::memcpy(mem + b->at_sec(), secondary, n);
         if (b->bc_bytes) std::memcpy(mem + b->at_bc(), barcodes, b->bc_bytes);
         if (b->name_bytes) std::memcpy(mem + b->at_names(), names, b->name_bytes);
+        if (b->has_umis) std::memcpy(mem + b->at_umi_off(), umi_off, sizeof(uint64_t) * (n + 1));
+        if (b->umi_bytes) std::memcpy(mem + b->at_umis(), umis, b->umi_bytes);
     }
     const uint64_t ticket = b->ticket;
     {
@@ -919,6 +1069,32 @@ int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_recor
     s->cv_work.notify_all();
     if (oom) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who);
     if (out_ticket) *out_ticket = ticket;
+    return OEM_OK;
+}
+
+int barcodes_stream_set_umis(BarcodesStream *b, const char *who)
+{
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (b->closed || b->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (b->with_umis) return fail(OEM_ERR_STATE, "%s: the session is a UMI session already", who);
+    if (b->next_ticket || b->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    b->with_umis = true;
+    return OEM_OK;
+}
+
+void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *dup_records)
+{
+    std::lock_guard<std::mutex> lk(b->mu);
+    *dup_reads = b->dup_reads;
+    *dup_records = b->dup_records;
+}
+
+int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_dups)
+{
+    if (!b->with_umis) return fail(OEM_ERR_STATE, "%s: not a UMI session (oem_cells_stream_set_umis)", who);
+    if (!b->assembled) return fail(OEM_ERR_STATE, "%s: after a successful oem_cells_stream_finish", who);
+    if (!out_cell_dups) return fail(OEM_ERR_ARG, "%s: out_cell_dups is NULL", who);
+    if (!b->out_cell_dups.empty()) std::memcpy(out_cell_dups, b->out_cell_dups.data(), sizeof(uint64_t) * b->out_cell_dups.size());
     return OEM_OK;
 }
 
@@ -983,13 +1159,14 @@ int barcodes_stream_assemble(BarcodesStream *b, const char *who)
     for (auto &sl : b->slots) {
         // a cell's records from its groups: the cells' first groups, sampled in the group's own group_off
         for (uint32_t c = 1; c <= sl->n_cells; ++c) {
-            b->out_cell_rec_off.push_back(rec_base + sl->group_off[sl->cell_group_off[c]]);
+            b->out_cell_rec_off.push_back(rec_base + (sl->cell_pos_off.empty() ? sl->group_off[sl->cell_group_off[c]] : sl->cell_pos_off[c]));
             b->out_cell_group_off.push_back(group_base + sl->cell_group_off[c]);
         }
         for (uint64_t g = 0; g < sl->n_groups; ++g) b->out_group_off.push_back(rec_base + sl->group_off[g]);
         b->out_order.insert(b->out_order.end(), sl->order.begin(), sl->order.end());
         b->out_kept.insert(b->out_kept.end(), sl->kept.begin(), sl->kept.end());
-        rec_base += sl->n_records;
+        b->out_cell_dups.insert(b->out_cell_dups.end(), sl->cell_dups.begin(), sl->cell_dups.end());
+        rec_base += sl->n_positions; // (a UMI session: every later group's place depends on what the earlier ones lost)
         group_base += sl->n_groups;
         sl.reset();
     }
@@ -1011,7 +1188,7 @@ int barcodes_stream_dims(const BarcodesStream *b, const char *who, uint64_t *n_c
 {
     if (!b->assembled) return fail(OEM_ERR_STATE, "%s: after a successful oem_cells_stream_finish", who);
     if (n_cells) *n_cells = b->n_cells_opened();
-    if (n_survivors) *n_survivors = b->n_survivors;
+    if (n_survivors) *n_survivors = b->out_order.size(); // (a UMI session: the positions that remain)
     if (n_groups) *n_groups = b->out_kept.size();
     if (barcode_bytes) *barcode_bytes = b->labels.size();
     if (n_unmapped) *n_unmapped = b->n_unmapped;

@@ -720,8 +720,47 @@ extern "C" int oem_cells_stream_push_barcodes(oem_cells_stream *s, const oem_aln
     const char *who = "oem_cells_stream_push_barcodes";
     if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
     if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a barcoded session (oem_cells_stream_set_barcodes)", who);
-    return barcodes_stream_push(s->bc, who, records, n_records, barcodes, barcode_off, names, name_off, secondary, out_ticket);
+    return barcodes_stream_push(s->bc, who, records, n_records, barcodes, barcode_off, names, name_off, secondary, false, nullptr, nullptr,
+                                out_ticket);
     OEM_API_END("oem_cells_stream_push_barcodes")
+}
+
+// A UMI session (oem_collate.h, "UMIs in the sessions"): a barcoded session of either form whose batches bring one UMI
+// per record; its groups are deduplicated behind their name collation (oem_cells_barcodes_stream.hip).
+extern "C" int oem_cells_stream_set_umis(oem_cells_stream *s)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_set_umis";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+        if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a barcoded session (oem_cells_stream_set_barcodes)", who);
+    }
+    return barcodes_stream_set_umis(s->bc, who);
+    OEM_API_END("oem_cells_stream_set_umis")
+}
+
+extern "C" int oem_cells_stream_push_barcodes_umis(oem_cells_stream *s, const oem_aln_record *records, uint64_t n_records,
+                                                   const uint8_t *barcodes, const uint64_t *barcode_off, const uint8_t *names,
+                                                   const uint64_t *name_off, const uint8_t *secondary, const uint8_t *umis,
+                                                   const uint64_t *umi_off, uint64_t *out_ticket)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_push_barcodes_umis";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a barcoded session (oem_cells_stream_set_barcodes)", who);
+    return barcodes_stream_push(s->bc, who, records, n_records, barcodes, barcode_off, names, name_off, secondary, true, umis, umi_off,
+                                out_ticket);
+    OEM_API_END("oem_cells_stream_push_barcodes_umis")
+}
+
+extern "C" int oem_cells_stream_umis_copy(const oem_cells_stream *s, uint64_t *out_cell_dups)
+{
+    const char *who = "oem_cells_stream_umis_copy";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a UMI session (oem_cells_stream_set_umis)", who);
+    return barcodes_stream_umis_copy(s->bc, who, out_cell_dups);
 }
 
 extern "C" int oem_cells_stream_barcodes_dims(const oem_cells_stream *s, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
@@ -803,7 +842,11 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
     uint64_t bc_batches = 0, bc_records = 0, bc_arena = 0, bc_misses = 0, bc_slots = 0;
     if (s->bc) barcodes_stream_counts(s->bc, &bc_batches, &bc_records);
     if (s->bc) barcodes_stream_table_info(s->bc, &bc_arena, &bc_misses, &bc_slots);
+    uint64_t dup_reads = 0, dup_records = 0;
+    if (s->bc) barcodes_stream_umi_info(s->bc, &dup_reads, &dup_records);
     switch (key) {
+    case OEM_CELLS_STREAM_INFO_UMI_DUP_READS: *value = dup_reads; break; // (a UMI session; 0 otherwise)
+    case OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS: *value = dup_records; break;
     case OEM_CELLS_STREAM_INFO_ARENA_BYTES: *value = bc_arena; break; // (an any-order barcoded session; 0 otherwise)
     case OEM_CELLS_STREAM_INFO_BARCODE_MISSES: *value = bc_misses; break;
     case OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS: *value = bc_slots; break;

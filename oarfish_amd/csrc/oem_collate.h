@@ -646,4 +646,36 @@ struct ParseCellsAnyOrderStream {
     }
 };
 
+// UMIs in the sessions (oem_cells_stream_set_umis, oem_cells_stream_push_barcodes_umis; oem_cells_barcodes_stream.hip).  A
+// UMI session is a barcoded session, of either form above, whose batches carry one UMI byte string per record; the empty
+// string means no UB tag.  Cells are cut or interned by the form's own rule, and "UMI deduplication" above is applied
+// to every cell behind its name collation.
+//   skip     an unmapped record takes no part: its UMI bytes are never examined and may hold a 0 byte.
+//   bytes    a surviving record's UMI may be empty; it may not hold a 0 byte.
+//   any-order form   with S the survivors' session-global indices, ascending, finish gives exactly what
+//            oem_em_run_cells_records_umis_sparse gives on records[S], barcodes[S], names[S], secondary[S], umis[S] with
+//            the session's filters, model and mode; `order` is S[order of the one call].
+//   collated form    there is no one call to name, because a barcode that comes back is a NEW cell here.  The contract
+//            is this join on the S-arrays, with cell_rec_off from the streamed cell rule (maximal runs of byte-equal
+//            barcodes): 1. oem_collate_names with that cell_rec_off; 2. oem_dedup_umis on its output with umis[S] and
+//            the flags of records[S]; 3. the duplicates' positions dropped (dedup_drop_host); 4.
+//            oem_em_run_cells_records_sparse on records[S][order'].  Classes never span cells: two runs of one barcode
+//            that hold the same UMI keep both reads.
+//   exact    in both forms every index array and count, kept, the discard tables (a duplicate is in none), cell_dups, the
+//            labels and the columns equal the expected side's; values and infos as a session is held to its one call --
+//            however the input was cut and whichever thread pushed what.  A session all of whose UMIs are empty gives
+//            the result of the same session without UMIs, exactly.
+//   groups   a session deduplicates group by group (a group is a run of whole cells), on group-local record indices and
+//            the group's window of the arena's UMI offsets.  Classes being inside cells, the groups' pieces joined --
+//            every later group's positions and read numbers moved down by what the earlier ones lost -- are the
+//            whole-input walk's, whatever the groups are (tests/native/cells_umis_stream_main.cpp).
+//   counts   the session's cell_rec_off, order and group_off describe the DEDUPLICATED collation: records accepted =
+//            unmapped + positions of order + the duplicates' records.
+//   bad ref_ids   the sessions differ from the one call and from each other.  The any-order form checks ref_id per batch
+//            on every surviving record, as it does without UMIs: a bad ref_id in a record that would later turn out to
+//            be a duplicate is still an error there.  The collated form finds it in the group, among the reads that
+//            remain: a duplicate's records are never gathered, so its ref_ids are never seen.  (The one call checks
+//            among the reads that remain too, but names the cell and the input index instead of a ticket.)  The
+//            any-order form's bound of 2^31 - 2 survivors counts the duplicates' records too.
+
 } // namespace oem

@@ -72,9 +72,10 @@ int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t
 // by gather_name_offsets) and d_out (8-byte aligned, out_bytes + 16 allocated) by gather_names, which takes any window
 // [k0, k1) of the records whose offsets are d_out_off[k0 .. k1] - off_base.  d_sec / d_out_sec: the flags likewise
 // (d_out_sec: m + 1 rounded up to 8, zero behind the m flags), or NULL.  On the null stream, which is left idle.
+// with_empty: some of the names may be empty (a session's UMIs); without it every name holds a byte at least.
 int gather_name_offsets(const uint32_t *d_order, uint64_t m, const uint64_t *d_name_off, uint64_t *d_out_off);
 int gather_names(const uint32_t *d_order, uint64_t m, const uint8_t *d_names, const uint64_t *d_name_off, const uint64_t *d_out_off,
-                 uint64_t off_base, uint64_t out_bytes, uint8_t *d_out, const uint8_t *d_sec, uint8_t *d_out_sec);
+                 uint64_t off_base, uint64_t out_bytes, uint8_t *d_out, const uint8_t *d_sec, uint8_t *d_out_sec, bool with_empty = false);
 // Validates names that are resident (the blob 16-byte padded): the first record with a 0 byte -> d_bad[0], with an empty
 // name -> d_bad[1] (both start as kNoRecord), over the records [r0, r1) and their bytes [b0, b1), on `st`.
 void launch_collate_validate(hipStream_t st, const uint8_t *d_names, uint64_t b0, uint64_t b1, const uint64_t *d_off, uint64_t r0,
@@ -117,6 +118,12 @@ struct UmiMarks {
 // The UMIs (checked: umi_off from 0, non-decreasing) up through the upload lanes, validated behind their chunks: a 0 byte
 // is OEM_ERR_ARG naming the smallest such input index, an empty UMI is legal.
 int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, uint64_t n, DevBuf<uint8_t> *d_umis, DevBuf<uint64_t> *d_umi_off);
+// A session's batch (oem_cells_barcodes_stream.hip), whose UMIs are resident (d_umis padded by 16, n + 1 offsets): the
+// UMIs of the m > 0 survivors d_order[0 .. m) gathered into a dense padded blob with m + 1 offsets from 0, so that a
+// skipped record's bytes are never examined, and validated as umis_upload validates: *bad_record is kNoRecord or the
+// smallest input index of a survivor whose UMI holds a 0 byte; an empty UMI is legal.  parse_survivor_names' sibling.
+int umis_gather_survivors(const uint8_t *d_umis, const uint64_t *d_umi_off, const uint32_t *d_order, uint64_t m, DevBuf<uint8_t> *d_dense,
+                          DevBuf<uint64_t> *d_dense_off, uint64_t *dense_bytes, uint64_t *bad_record);
 // The duplicates of a batch of nc cells whose collation is on the device: d_order (positions -> input indices, or ->
 // positions of d_order_bc where that is not NULL), d_group_off (ng + 1, from 0), d_cell_group_off (nc + 1, from 0).
 // cell_dups: host, nc.  With out->n_dups == 0 nothing else needs to be done.  Leaves the device idle.

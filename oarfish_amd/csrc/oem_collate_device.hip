@@ -363,10 +363,12 @@ __device__ __forceinline__ uint64_t load_bytes(const uint8_t *__restrict__ blob,
 // the bytes [8 j, 8 j + 8) of the concatenation of the names of order[0 .. m), name k at out_off[k] - off_base.  A word
 // may take its bytes from several names (a name can be one byte long); the lane walks them.  The record of the
 // workgroup's first byte is searched once among all m, each lane's own among the few that a workgroup's 2 KiB can hold.
-// Bytes past out_bytes are written as 0.
+// Bytes past out_bytes are written as 0.  with_empty: names may be empty (the UMIs of a session's survivors), so no
+// count of records bounds a lane's search; an empty name is passed by, as it holds no byte.
 __global__ __launch_bounds__(kCT) void k_names_gather(uint64_t n_words, uint64_t out_bytes, uint64_t m, const uint32_t *__restrict__ order,
                                                        const uint8_t *__restrict__ names, const uint64_t *__restrict__ off,
-                                                       const uint64_t *__restrict__ out_off, uint64_t off_base, uint64_t *__restrict__ out)
+                                                       const uint64_t *__restrict__ out_off, uint64_t off_base, uint32_t with_empty,
+                                                       uint64_t *__restrict__ out)
 {
     const uint64_t j = tid64();
     if (j >= n_words) return;
@@ -378,7 +380,7 @@ __global__ __launch_bounds__(kCT) void k_names_gather(uint64_t n_words, uint64_t
             if (out_off[mid] - off_base <= p0) lo = mid;
             else hi = mid - 1;
         }
-        hi = lo + (uint64_t)kCT * 8 < m - 1 ? lo + (uint64_t)kCT * 8 : m - 1; // (names are never empty: a byte each at least)
+        hi = !with_empty && lo + (uint64_t)kCT * 8 < m - 1 ? lo + (uint64_t)kCT * 8 : m - 1; // (names that are never empty: a byte each at least)
     }
     uint64_t p = 8 * j;
     while (lo < hi) {
@@ -723,11 +725,11 @@ int gather_name_offsets(const uint32_t *d_order, uint64_t m, const uint64_t *d_n
 }
 
 int gather_names(const uint32_t *d_order, uint64_t m, const uint8_t *d_names, const uint64_t *d_name_off, const uint64_t *d_out_off,
-                 uint64_t off_base, uint64_t out_bytes, uint8_t *d_out, const uint8_t *d_sec, uint8_t *d_out_sec)
+                 uint64_t off_base, uint64_t out_bytes, uint8_t *d_out, const uint8_t *d_sec, uint8_t *d_out_sec, bool with_empty)
 {
     const uint64_t n_words = (out_bytes + 16) / 8; // the blob and its padding
     hipLaunchKernelGGL(k_names_gather, grid_for(n_words), dim3(kCT), 0, nullptr, n_words, out_bytes, m, d_order, d_names, d_name_off,
-                       d_out_off, off_base, (uint64_t *)d_out);
+                       d_out_off, off_base, with_empty ? 1u : 0u, (uint64_t *)d_out);
     OEM_HIP(hipGetLastError());
     if (d_sec) {
         const uint64_t sec_words = (m + 1 + 7) / 8;

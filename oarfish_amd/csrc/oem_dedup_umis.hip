@@ -220,6 +220,33 @@ int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, u
     return OEM_OK;
 }
 
+int umis_gather_survivors(const uint8_t *d_umis, const uint64_t *d_umi_off, const uint32_t *d_order, uint64_t m, DevBuf<uint8_t> *d_dense,
+                          DevBuf<uint64_t> *d_dense_off, uint64_t *dense_bytes, uint64_t *bad_record)
+{
+    *bad_record = kNoRecord;
+    DevBuf<unsigned long long> d_bad;
+    OEM_TRY(dev_alloc(&d_bad.p, 2, nullptr));
+    const unsigned long long bad0[2] = {kNoRecord, kNoRecord};
+    OEM_HIP(hipMemcpy(d_bad.p, bad0, sizeof bad0, hipMemcpyHostToDevice));
+    OEM_TRY(dev_alloc(&d_dense_off->p, m + 1, nullptr));
+    OEM_TRY(gather_name_offsets(d_order, m, d_umi_off, d_dense_off->p));
+    OEM_HIP(hipMemcpy(dense_bytes, d_dense_off->p + m, sizeof *dense_bytes, hipMemcpyDeviceToHost));
+    OEM_TRY(dev_alloc(&d_dense->p, *dense_bytes + 16, nullptr));
+    OEM_TRY(gather_names(d_order, m, d_umis, d_umi_off, d_dense_off->p, 0, *dense_bytes, d_dense->p, nullptr, nullptr, true));
+    if (!*dense_bytes) return OEM_OK;
+    // (the validate kernel of the names: its empty-name word is not read, an empty UMI being legal)
+    launch_collate_validate(nullptr, d_dense->p, 0, *dense_bytes, d_dense_off->p, 0, m, d_bad.p);
+    OEM_HIP(hipGetLastError());
+    unsigned long long bad[2];
+    OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0] != kNoRecord) {
+        uint32_t record = 0;
+        OEM_HIP(hipMemcpy(&record, d_order + bad[0], sizeof record, hipMemcpyDeviceToHost));
+        *bad_record = record;
+    }
+    return OEM_OK;
+}
+
 int dedup_mark(const UmiInput &in, const uint32_t *d_order, const uint32_t *d_order_bc, const uint64_t *d_group_off, uint64_t ng,
                const uint64_t *d_cell_group_off, uint32_t nc, uint64_t survivor_base, UmiMarks *out, uint64_t *cell_dups)
 {

@@ -712,11 +712,19 @@ class CellsStream:
     device against a table of the labels seen so far; nothing runs before ``finish()``, which gives exactly what
     ``em_cells_records_sparse(..., barcodes=, collate="device")`` gives on the surviving records.  ``info()`` then has
     ``arena_bytes``, ``barcode_misses`` and ``barcode_table_slots`` (0 on every other session).
+
+    ``umis=True`` (with ``barcodes=True``, either form) is a UMI session (``oem_cells_stream_set_umis``): ``push_batch``
+    takes one UMI per record, every group of cells is deduplicated on the device behind its name collation
+    (``dedup_umis``' rule), ``cells()`` describes the deduplicated collation and gains ``cell_dups``, and ``info()`` has
+    ``umi_dup_reads`` and ``umi_dup_records`` (0 on every other session).  The any-order form gives exactly what
+    ``em_cells_records_sparse(..., barcodes=, names=, umis=)`` gives on the surviving records.
     """
 
     def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
                  group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None,
-                 barcodes: bool = False, mode: str = "sort", collated: bool = True):
+                 barcodes: bool = False, mode: str = "sort", collated: bool = True, umis: bool = False):
+        if umis and not barcodes:
+            raise ValueError("umis=True goes with barcodes=True: only a barcoded session takes UMIs")
         if not collated and not barcodes:
             raise ValueError("collated=False goes with barcodes=True: only a barcoded session finds its cells itself")
         if barcodes and filters is None:
@@ -733,6 +741,7 @@ class CellsStream:
         self._cells = None
         self._barcoded = bool(barcodes)
         self._any_order = bool(barcodes) and not collated
+        self._umis = bool(umis)
         self._device = device
         records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
@@ -765,6 +774,8 @@ class CellsStream:
                 if barcodes:
                     set_barcodes = self._L.oem_cells_stream_set_barcodes if collated else self._L.oem_cells_stream_set_barcodes_any_order
                     self._check(set_barcodes(self._h, _COLLATE_MODES[mode]))
+                    if umis:
+                        self._check(self._L.oem_cells_stream_set_umis(self._h))
             except BaseException:
                 self.close()
                 raise
@@ -850,11 +861,14 @@ class CellsStream:
                                                           group_off.ctypes.data, len(group_off) - 1, C.byref(ticket)))
         return int(ticket.value)
 
-    def push_batch(self, records, barcodes, names, secondary=None) -> int:
+    def push_batch(self, records, barcodes, names, secondary=None, umis=None) -> int:
         """One batch of a barcoded session: ``records`` with one barcode and one read name each -- ``(blob, offsets)``
         pairs or sequences of ``bytes``, as ``collate_barcodes`` and ``collate_names`` take them -- and their
         ``secondary`` flags.  The batch may start and end anywhere: inside a cell, inside a read.  Returns the batch's
-        ticket; the session's input is its batches in ticket order.  Thread-safe; releases the GIL."""
+        ticket; the session's input is its batches in ticket order.  Thread-safe; releases the GIL.
+
+        A UMI session takes ``umis`` likewise, one per record (``b""``: no UMI); ``None`` means every UMI of the batch
+        is empty.  Giving ``umis`` to a session without them is a ``ValueError``."""
         from .types import pack_read_names
         if not self._h:
             raise _lib.OemError(_lib.OEM_ERR_STATE, "CellsStream is closed")
@@ -872,6 +886,21 @@ class CellsStream:
             if len(sec) != n:
                 raise ValueError("secondary must have one entry per record")
         ticket = C.c_uint64(0)
+        with_umis = getattr(self, "_umis", False)
+        if umis is not None and not with_umis:
+            raise ValueError("umis go to a UMI session: CellsStream(..., barcodes=True, umis=True)")
+        if with_umis:
+            if umis is None:
+                u_blob, u_off = np.zeros(0, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+            else:
+                if _n_packed(umis) != n:
+                    raise ValueError("umis must have one entry per record")
+                u_blob, u_off = pack_read_names(umis, n)
+            self._check(self._L.oem_cells_stream_push_barcodes_umis(
+                self._h, records.ctypes.data if n else None, n, bc_blob.ctypes.data if len(bc_blob) else None, bc_off.ctypes.data,
+                blob.ctypes.data if len(blob) else None, off.ctypes.data, None if sec is None or not n else sec.ctypes.data,
+                u_blob.ctypes.data if len(u_blob) else None, u_off.ctypes.data, C.byref(ticket)))
+            return int(ticket.value)
         self._check(self._L.oem_cells_stream_push_barcodes(
             self._h, records.ctypes.data if n else None, n, bc_blob.ctypes.data if len(bc_blob) else None, bc_off.ctypes.data,
             blob.ctypes.data if len(blob) else None, off.ctypes.data, None if sec is None or not n else sec.ctypes.data,
@@ -881,7 +910,9 @@ class CellsStream:
     def cells(self) -> dict:
         """After ``finish()`` of a barcoded session: ``barcodes`` (the cells' labels, a list of ``bytes``, in cell order),
         ``cell_rec_off`` (positions among the surviving records), ``order`` (uint64: the index in the pushed stream of the
-        record at every collated position), ``group_off``, ``cell_group_off``, ``kept`` and ``n_unmapped``."""
+        record at every collated position), ``group_off``, ``cell_group_off``, ``kept`` and ``n_unmapped``.  A UMI
+        session: all of them describe the deduplicated collation, and ``cell_dups`` (uint64) are the duplicate reads that
+        every cell lost."""
         if self._cells is None:
             raise _lib.OemError(_lib.OEM_ERR_STATE, "cells(): a finished barcoded session has them")
         return self._cells
@@ -901,8 +932,13 @@ class CellsStream:
             self._h, blob.ctypes.data, bc_off.ctypes.data, cell_rec_off.ctypes.data, order.ctypes.data, group_off.ctypes.data,
             cell_group_off.ctypes.data, kept.ctypes.data))
         raw = blob.tobytes()
-        return dict(barcodes=[raw[int(bc_off[c]):int(bc_off[c + 1])] for c in range(nc)], cell_rec_off=cell_rec_off,
-                    order=order[:m], group_off=group_off, cell_group_off=cell_group_off, kept=kept[:ng], n_unmapped=n_unmapped)
+        out = dict(barcodes=[raw[int(bc_off[c]):int(bc_off[c + 1])] for c in range(nc)], cell_rec_off=cell_rec_off,
+                   order=order[:m], group_off=group_off, cell_group_off=cell_group_off, kept=kept[:ng], n_unmapped=n_unmapped)
+        if self._umis:
+            dups = np.zeros(max(nc, 1), dtype=np.uint64)
+            self._check(self._L.oem_cells_stream_umis_copy(self._h, dups.ctypes.data))
+            out["cell_dups"] = dups[:nc]
+        return out
 
     def finish(self):
         """(indptr, cols, vals, [RunInfo]) of every pushed cell, in ticket order (a barcoded session: of every cell it
@@ -938,7 +974,8 @@ class CellsStream:
                     groups_before_finish=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH,
                     blocked_s=_lib.OEM_CELLS_STREAM_INFO_BLOCKED_US, groups_batched=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BATCHED,
                     arena_bytes=_lib.OEM_CELLS_STREAM_INFO_ARENA_BYTES, barcode_misses=_lib.OEM_CELLS_STREAM_INFO_BARCODE_MISSES,
-                    barcode_table_slots=_lib.OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS)
+                    barcode_table_slots=_lib.OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS,
+                    umi_dup_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_READS, umi_dup_records=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS)
         out = {}
         for name, key in keys.items():
             v = C.c_uint64(0)

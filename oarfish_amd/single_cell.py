@@ -33,6 +33,7 @@ class SingleCellArgs:
     group_cells: int = 0
     max_staged_records: int = 0
     collated: bool = True                  # False: the batches' records come in any order (the any-order barcoded session)
+    umis: bool = False                     # True: the batches carry a UMI per record and every cell is deduplicated
     extra_info: dict = field(default_factory=dict)
 
 
@@ -43,7 +44,11 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
     record positions -- or, with ``args.collated=False``, in any order at all (``synth.cut_interleaved_records``' tuples:
     the any-order barcoded session, whose cells are those of the one barcodes call).  Writes `.count.mtx`, `.features.txt`, `.barcodes.txt` (the session's labels, in cell order) and
     `.meta_info.json` with ``writers.write_single_cell_output_device`` and returns ``(indptr, cols, vals, infos,
-    cells)``: the session's result and its ``cells()``."""
+    cells)``: the session's result and its ``cells()``.
+
+    With ``args.umis`` the batches are 5-tuples ``(records, barcodes, names, secondary, umis)`` (the cutters' tuples under
+    ``umis=``), the session deduplicates every cell on the device, ``cells`` carries ``cell_dups`` and `.meta_info.json`
+    gains ``umi_dedup`` and ``umi_duplicate_reads``."""
     txp_len = np.asarray(txp_lens, dtype=np.uint64)
     coverage = None
     if args.model_coverage is not None:
@@ -51,14 +56,21 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
     with CellsStream(len(txp_len), max_iter=args.max_em_iter, conv_thresh=args.convergence_thresh, coverage=coverage,
                      device=args.device, group_nnz=args.group_nnz, group_cells=args.group_cells,
                      max_staged_nnz=args.max_staged_records, filters=filters, txp_len=txp_len, barcodes=True,
-                     mode=args.mode, collated=args.collated) as cs:
-        for records, barcodes, names, secondary in batches:
-            cs.push_batch(records, barcodes, names, secondary)
+                     mode=args.mode, collated=args.collated, umis=args.umis) as cs:
+        if args.umis:
+            for records, barcodes, names, secondary, umis in batches:
+                cs.push_batch(records, barcodes, names, secondary, umis)
+        else:
+            for records, barcodes, names, secondary in batches:
+                cs.push_batch(records, barcodes, names, secondary)
         indptr, cols, vals, infos = cs.finish()
         cells = cs.cells()
     info = {"output": args.output, "single_cell": True, "em_max_iter": args.max_em_iter,
             "em_convergence_thresh": args.convergence_thresh, "threads": args.threads,
             "filter_options": {"model_coverage": args.model_coverage is not None}}
+    if args.umis:
+        info["umi_dedup"] = True
+        info["umi_duplicate_reads"] = int(cells["cell_dups"].sum())
     info.update(args.extra_info)
     labels = [b.decode("latin-1") for b in cells["barcodes"]]
     writers.write_single_cell_output_device(args.output, info, txps_name, labels, len(labels), indptr, cols, vals,

@@ -835,7 +835,20 @@ def add_umi_duplicates(records, names, secondary, barcodes, rate: float, seed: i
             gather_names((bc_blob, bc_off), src_all), umis, copies)
 
 
-def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, unmapped_every: int = 0):
+def recollate_by_first_barcode(record_barcodes):
+    """The stable permutation that makes an uncollated stream barcode-collated: the records ordered by the first
+    occurrence of their barcode, the records of one barcode keeping their order.  ``record_barcodes`` is a ``(blob,
+    offsets)`` pair with one barcode per record; apply the result with ``records[perm]`` and ``em.gather_names(x, perm)``.
+    It turns ``add_umi_duplicates``' output into input for the collated UMI session.  A pure function of its argument."""
+    blob, off = np.asarray(record_barcodes[0], dtype=np.uint8), np.asarray(record_barcodes[1], dtype=np.int64)
+    raw = blob.tobytes()
+    first = {}
+    rank = np.fromiter((first.setdefault(raw[int(off[i]):int(off[i + 1])], len(first)) for i in range(len(off) - 1)),
+                       dtype=np.int64, count=len(off) - 1)
+    return np.argsort(rank, kind="stable")
+
+
+def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, unmapped_every: int = 0, umis=None):
     """``shuffle_cell_records``' barcode-collated input cut into batches for a barcoded session
     (``CellsStream(barcodes=True)``), every record with its cell's barcode.  ``barcodes``: one per cell
     (``make_barcodes``; a label may recur).  ``unmapped_every=k > 0`` first sprinkles in extra unmapped records, one
@@ -843,7 +856,8 @@ def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, un
     positions of the stream that results (the sprinkled records counted), in any order and with repeats (a repeat gives
     an empty batch); 0 and the stream's length are implied.  A cut may fall inside a cell and inside a read.  Returns a
     list of ``(records, barcodes, names, secondary)``, ``barcodes`` and ``names`` as ``(blob, offsets)`` pairs with the
-    offsets of each batch from 0.  A pure function of its arguments."""
+    offsets of each batch from 0.  With ``umis`` -- a ``(blob, offsets)`` pair, one UMI per record -- the tuples gain
+    the batch's UMIs as a fifth element; a sprinkled record's UMI is empty.  A pure function of its arguments."""
     from .em import gather_names
     records = np.asarray(records)
     blob, off = np.asarray(names[0], dtype=np.uint8), np.asarray(names[1], dtype=np.int64)
@@ -859,15 +873,15 @@ def cut_cell_records(records, names, secondary, cell_rec_off, barcodes, cuts, un
     np.cumsum([len(b) for b in enc], out=cell_off[1:])
     cell_of = np.repeat(np.arange(n_cells), np.diff(cell_rec_off))
     bc_blob, bc_off = gather_names((np.frombuffer(b"".join(enc), dtype=np.uint8), cell_off), cell_of)
-    return _sprinkle_and_cut(records, blob, off, bc_blob, np.asarray(bc_off, dtype=np.int64), secondary, cuts, unmapped_every)
+    return _sprinkle_and_cut(records, blob, off, bc_blob, np.asarray(bc_off, dtype=np.int64), secondary, cuts, unmapped_every, umis)
 
 
-def cut_interleaved_records(records, names, secondary, record_barcodes, cuts, unmapped_every: int = 0):
+def cut_interleaved_records(records, names, secondary, record_barcodes, cuts, unmapped_every: int = 0, umis=None):
     """``interleave_cells``' uncollated input cut into batches for an any-order barcoded session
     (``CellsStream(barcodes=True, collated=False)``), as ``cut_cell_records`` cuts collated input: ``record_barcodes`` is
     the ``(blob, offsets)`` pair with one barcode per record that ``interleave_cells`` returns; ``unmapped_every`` and
-    ``cuts`` mean what they mean there.  Returns a list of ``(records, barcodes, names, secondary)``.  A pure function of
-    its arguments."""
+    ``cuts`` and ``umis`` mean what they mean there.  Returns a list of ``(records, barcodes, names, secondary)``, with
+    ``umis`` of ``(records, barcodes, names, secondary, umis)``.  A pure function of its arguments."""
     records = np.asarray(records)
     blob, off = np.asarray(names[0], dtype=np.uint8), np.asarray(names[1], dtype=np.int64)
     bc_blob, bc_off = np.asarray(record_barcodes[0], dtype=np.uint8), np.asarray(record_barcodes[1], dtype=np.int64)
@@ -877,13 +891,18 @@ def cut_interleaved_records(records, names, secondary, record_barcodes, cuts, un
     secondary = np.zeros(n, dtype=np.uint8) if secondary is None else np.asarray(secondary, dtype=np.uint8)
     if len(secondary) != n:
         raise ValueError("secondary must have one entry per record")
-    return _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unmapped_every)
+    return _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unmapped_every, umis)
 
 
-def _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unmapped_every):
-    """the stream of ``cut_cell_records`` / ``cut_interleaved_records`` from one name and one barcode per record"""
+def _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unmapped_every, umis=None):
+    """the stream of ``cut_cell_records`` / ``cut_interleaved_records`` from one name and one barcode per record (and,
+    with ``umis``, one UMI)"""
     from .builder import REC_UNMAPPED
     n = len(records)
+    if umis is not None:
+        u_blob, u_off = np.asarray(umis[0], dtype=np.uint8), np.asarray(umis[1], dtype=np.int64)
+        if len(u_off) != n + 1:
+            raise ValueError("umis need one entry per record")
     if unmapped_every > 0 and n:   # record i of the input goes to position i + i // k + 1
         pos = np.arange(n) + np.arange(n) // unmapped_every + 1
         total = int(pos[-1]) + 1
@@ -897,6 +916,11 @@ def _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unma
         off, bc_off = np.zeros(total + 1, dtype=np.int64), np.zeros(total + 1, dtype=np.int64)
         np.cumsum(name_len, out=off[1:])
         np.cumsum(bc_len, out=bc_off[1:])
+        if umis is not None:
+            umi_len = np.zeros(total, dtype=np.int64)
+            umi_len[pos] = np.diff(u_off)
+            u_blob, u_off = u_blob[int(u_off[0]):int(u_off[-1])], np.zeros(total + 1, dtype=np.int64)
+            np.cumsum(umi_len, out=u_off[1:])
         records, secondary, n = stream, sec, total
     edges = [0] + sorted(int(c) for c in cuts) + [n]
     if edges[1] < 0 or edges[-2] > n:
@@ -908,6 +932,9 @@ def _sprinkle_and_cut(records, blob, off, bc_blob, bc_off, secondary, cuts, unma
                     (np.ascontiguousarray(bc_blob[int(bo[0]):int(bo[-1])]), np.ascontiguousarray(bo - bo[0], dtype=np.uint64)),
                     (np.ascontiguousarray(blob[int(o[0]):int(o[-1])]), np.ascontiguousarray(o - o[0], dtype=np.uint64)),
                     np.ascontiguousarray(secondary[a:b])))
+        if umis is not None:
+            uo = u_off[a:b + 1]
+            out[-1] += ((np.ascontiguousarray(u_blob[int(uo[0]):int(uo[-1])]), np.ascontiguousarray(uo - uo[0], dtype=np.uint64)),)
     return out
 
 

@@ -55,6 +55,16 @@ worst:
 
 With the peak device memory of both, the arena's peak and its bytes per survivor, finish's share of the session's time and
 the lookups that missed.  No ratio is promised: the baseline is (b) in the same run.
+
+--umis-stream is the leg of the UMI sessions (profiles/cells_umis_stream_bench.json): the --umis leg's input, alternated
+in one process, --runs repeats (five), best to worst, one pushing thread:
+
+  (a) the UMI session (CellsStream(barcodes=True, umis=True)) in both forms at the two --batch-records sizes: the any-order
+      form on the input as it is, the collated form on the input ordered stably by each barcode's first record;
+  (b) the UMIs one call on the concatenation (em_cells_records_sparse(..., barcodes=, names=, umis=));
+  (c) the same sessions without UMIs, which count the duplicates as molecules.
+
+With the peak device memory of each, arena_bytes, the duplicates dropped and (a) - (c).
 """
 import argparse
 import ctypes as C
@@ -497,6 +507,105 @@ def barcodes_any_order_stream_leg(args, cr, res, save):
         del rec, blob, off, sec, bc_blob, bc_off, rec_s, sec_s, names_s, bc_s
 
 
+def umis_stream_leg(args, cr, res, save):
+    """The --umis-stream leg: the --umis leg's input (the slice shuffled, named, barcoded, interleaved uniformly, with
+    synth.add_umi_duplicates(rate=0.1)).  Alternated in one process, from one pushing thread: (a) the UMI session in both
+    forms at every --batch-records -- the any-order form on the input as it is, the collated form on the input ordered
+    stably by each barcode's first occurrence; (b) the UMIs one call on the concatenation; (c) the same sessions without
+    UMIs, which count the duplicates as molecules.  Reported per form: best - worst of each, peak device memory of the
+    first run of each, arena_bytes, the duplicates dropped, and (a) - (c), the cost of the UMIs through the session."""
+    from oarfish_amd.em import gather_names
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        rec1, names1, sec1, bc1, _ = synth.interleave_cells(rec0, names0, sec0, cro, synth.make_barcodes(n, "10x"), how="uniform")
+        del rec0, names0, sec0
+        rec, names, sec, bc, umis, copies = synth.add_umi_duplicates(rec1, names1, sec1, bc1, rate=0.1)
+        del rec1, names1, sec1, bc1
+        m = len(rec)
+        r = res[style] = dict(records=int(m), copied_reads=int(sum(copies.values())), name_bytes=int(names[0].nbytes),
+                              record_bytes=int(rec.nbytes), barcode_bytes=int(bc[0].nbytes), umi_bytes=int(umis[0].nbytes))
+        order_bc, _ = oarfish_amd.collate_barcodes(bc)          # stable, by each barcode's first record: the collated form's input
+        inputs = {"any_order": (rec, names, sec, bc, umis),
+                  "collated": (rec[order_bc], gather_names(names, order_bc), sec[order_bc], gather_names(bc, order_bc),
+                               gather_names(umis, order_bc))}
+        del order_bc
+
+        def session(form, batch, with_umis, upto=m):
+            rc, (nb, no), sc, (bb, bo), (ub, uo) = inputs[form]
+            no, bo, uo = (np.asarray(o, dtype=np.uint64) for o in (no, bo, uo))
+            info = {}
+
+            def go():
+                with oarfish_amd.CellsStream(len(tl), filters=f, txp_len=tl, barcodes=True, collated=form == "collated", umis=with_umis) as cs:
+                    for a in range(0, upto, batch):
+                        b = min(a + batch, upto)
+                        u = dict(umis=(ub[int(uo[a]):int(uo[b])], uo[a:b + 1] - uo[a])) if with_umis else {}
+                        cs.push_batch(rc[a:b], (bb[int(bo[a]):int(bo[b])], bo[a:b + 1] - bo[a]), (nb[int(no[a]):int(no[b])], no[a:b + 1] - no[a]),
+                                      sc[a:b], **u)
+                    out = cs.finish()
+                    cells = cs.cells()
+                    info.update(cs.info(), n_cells=len(cells["barcodes"]), reads=int(len(cells["kept"])))
+                return out
+            dt, out = clock(go)
+            return dt, out, info
+
+        def one_call(upto=m):
+            (nb, no), (bb, bo), (ub, uo) = names, bc, umis
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:upto], None, None, names=(nb[:int(no[upto])], no[:upto + 1]),
+                                                       secondary=sec[:upto], barcodes=(bb[:int(bo[upto])], bo[:upto + 1]),
+                                                       umis=(ub[:int(uo[upto])], uo[:upto + 1]), collate="device")
+
+        warm = min(m, int(cro[min(args.warm_cells, n)]))
+        for form in inputs:
+            for with_umis in (True, False):
+                session(form, args.batch_records[0], with_umis, warm)
+        one_call(warm)
+        points = [(form, batch, w) for form in inputs for batch in args.batch_records for w in (True, False)]
+        runs, runs_b = {p: [] for p in points}, []
+        for k in range(args.runs):
+            for p in points:
+                form, batch, w = p
+                key = f"{form}_{batch}_{'with_umis' if w else 'without_umis'}"
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        dt, got, info = session(*p)
+                    r[key + "_peak_device_bytes"] = int(pk.peak)
+                    r[key + "_info"] = info
+                    if w:   # every copied read is dropped; the record counts add up
+                        assert info["umi_dup_reads"] == sum(copies.values()) and info["n_cells"] == n
+                else:
+                    dt, got, info = session(*p)
+                del got
+                runs[p].append(dt)
+                r[key] = spread(runs[p])
+            if k == 0:
+                with PeakDeviceMemory() as pk:
+                    dt, got_b = clock(one_call)
+                r["one_call_peak_device_bytes"] = int(pk.peak)
+            else:
+                dt, got_b = clock(one_call)
+            del got_b
+            runs_b.append(dt)
+            r["one_call_with_umis"] = spread(runs_b)
+            for form in inputs:
+                for batch in args.batch_records:
+                    a, c = min(runs[(form, batch, True)]), min(runs[(form, batch, False)])
+                    r[f"{form}_{batch}_umis_cost_s_a_minus_c"] = round(a - c, 4)
+                    r[f"{form}_{batch}_over_one_call"] = round(a / min(runs_b), 3)
+            print(f"[bench] {style} run {k}: " + ", ".join(f"{p[0]} {p[1]} {'umis' if p[2] else 'plain'} {runs[p][-1]:.3f} s" for p in points)
+                  + f", one call {runs_b[-1]:.3f} s", flush=True)
+            save()
+        del rec, names, sec, bc, umis, inputs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=625)
@@ -511,14 +620,17 @@ def main():
     ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
     ap.add_argument("--barcodes-any-order-stream", action="store_true",
                     help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
+    ap.add_argument("--umis-stream", action="store_true",
+                    help="the leg of the UMI sessions (both forms) against the UMIs one call and the sessions without UMIs")
     ap.add_argument("--batch-records", type=int, nargs="*", default=[1 << 21, 1 << 23], help="the session legs: records per pushed batch")
     ap.add_argument("--styles", nargs="*", default=["uuid", "illumina"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.umis or args.barcodes_stream or args.barcodes_any_order_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.umis or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream else 3
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
+        args.out = os.path.join(ROOT, "profiles", "cells_umis_stream_bench.json" if args.umis_stream else
+                                "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
                                 "cells_barcodes_stream_bench.json" if args.barcodes_stream else
                                 "cells_records_umis_bench.json" if args.umis else
                                 "cells_records_barcodes_bench.json" if args.barcodes else
@@ -584,6 +696,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.umis_stream:
+        umis_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     if args.barcodes_any_order_stream:
         barcodes_any_order_stream_leg(args, cr, res, save)
         print(json.dumps(res))
