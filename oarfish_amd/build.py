@@ -34,7 +34,7 @@ SOURCES = ["oem_api.hip", "oem_em_driver.hip", "oem_assignment_text.hip", "oem_l
 # the testing library swaps these for their -DOEM_TESTING build and adds the hooks
 TESTING_VARIANTS = ["oem_comm.cpp", "oem_knobs.cpp", "oem_tile_kernels.hip", "oem_batch_kernels.hip"]
 TESTING_ONLY = ["oem_testing.hip"]
-HEADERS = ["oem_internal.h", "oem_stopping_rule.h", "oem_text_format.h", "oem_shortest_f32.h", "oem_shortest_f64.h", "oem_lz4.h", "oem_filter.h", "oem_collate.h", "oem_barcode_table.h", "oem_collate_device.h", "oem_parse_device.h", "oem_filter_projected.h", "oem_exp_f32.h", "oem_filter_device.h", "oem_driver.h", "oem_cells.h", "oem_cells_barcodes_stream.h", "oem_layout.h", "oem_tile_common.h", "oem_lane_runs.h", "oem_coverage_common.h", os.path.join(INCLUDE, "oarfish_em.h")]
+HEADERS = ["oem_internal.h", "oem_stopping_rule.h", "oem_text_format.h", "oem_shortest_f32.h", "oem_shortest_f64.h", "oem_lz4.h", "oem_filter.h", "oem_collate.h", "oem_barcode_table.h", "oem_collate_device.h", "oem_parse_device.h", "oem_stage_queue.h", "oem_filter_projected.h", "oem_exp_f32.h", "oem_filter_device.h", "oem_driver.h", "oem_cells.h", "oem_cells_barcodes_stream.h", "oem_layout.h", "oem_tile_common.h", "oem_lane_runs.h", "oem_coverage_common.h", os.path.join(INCLUDE, "oarfish_em.h")]
 
 FLAGS = [
     "--offload-arch=gfx950",

@@ -40,10 +40,6 @@ inline int bits_of(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 
 enum : int { kStatProbe = 0, kStatWrapped = 1, kStatError = 2, kStatWords = 3 };
 
-struct U32AsU64 {
-    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
-};
-
 // Survivor idx[j] (idx NULL: j) of the batch, j < cnt, against the table: cell_id[k] = its label's id, kBarcodeEmpty on a
 // miss.  miss (or NULL): m + 1 flags for the scan, miss[m] = 0 (cnt == m, idx NULL).  must_hit: a miss is an error (the
 // second pass, after the insert).  bc: the survivors' dense blob, padded by 16, with its offsets from 0.
@@ -248,15 +244,7 @@ int BarcodeIntern::batch(const char *who, const uint8_t *d_bc, const uint64_t *d
                        (const uint32_t *)slot.p, capacity, hash_bits, (const uint8_t *)labels.p, (const uint64_t *)label_off.p, n_labels, 0u,
                        d_cell_id, d_miss.p, stats.p);
     OEM_HIP(hipGetLastError());
-    {
-        hipcub::TransformInputIterator<uint64_t, U32AsU64, const uint32_t *> in(d_miss.p, U32AsU64());
-        size_t tb = 0;
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, d_at.p, (int)(m + 1), nullptr));
-        DevBuf<uint8_t> tmp;
-        OEM_TRY(dev_alloc(&tmp.p, tb, nullptr));
-        OEM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, d_at.p, (int)(m + 1), nullptr));
-        OEM_HIP(hipStreamSynchronize(nullptr));
-    }
+    OEM_TRY(exclusive_scan_u32(d_miss.p, d_at.p, m + 1));
     uint64_t n_miss = 0;
     OEM_HIP(hipMemcpy(&n_miss, d_at.p + m, sizeof n_miss, hipMemcpyDeviceToHost));
     OEM_TRY(check_stats(who));

@@ -40,7 +40,6 @@ struct BarcodesEnv {
     std::function<void(StreamGroupRun)> submit;        // the next group, in cell order, to the group workers
     std::function<void(int, const char *)> set_sticky; // the first error sticks
     std::function<int(std::string *)> sticky;          // OEM_OK, or the session's sticky status and its message
-    std::function<void(uint64_t)> add_blocked_us;
 };
 
 // The any-order session's table of the labels seen so far, on the device (oem_cells_barcodes_sort_stream.hip,
@@ -74,6 +73,8 @@ struct BarcodeIntern {
 void barcode_table_last(uint64_t *out8);
 // *bad = the smallest i = d_order[k], k < m, whose record's ref_id is not below n_txps, or kNoRecord
 int cells_ref_check(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, uint32_t n_txps, uint64_t *bad);
+// d_out[k] = d_in[0] + ... + d_in[k - 1] over n entries, in 64 bits (oem_cells_barcodes_stream.hip); leaves the null stream idle
+int exclusive_scan_u32(const uint32_t *d_in, uint64_t *d_out, uint64_t n);
 
 struct BarcodesStream;
 // any_order: oem_collate.h's "Cells from a stream in any order" instead of "Cells from a barcode-collated stream"
@@ -98,7 +99,8 @@ bool barcodes_stream_push_in_flight(BarcodesStream *b);
 int barcodes_stream_close(BarcodesStream *b, const char *who);
 // finish, after the group workers have joined: the groups' pieces become what oem_cells_stream_barcodes_copy gives
 int barcodes_stream_assemble(BarcodesStream *b, const char *who);
-void barcodes_stream_counts(BarcodesStream *b, uint64_t *n_batches, uint64_t *n_records);
+// batches and records pushed, and the microseconds its pushes have waited for room in the staging budget
+void barcodes_stream_counts(BarcodesStream *b, uint64_t *n_batches, uint64_t *n_records, uint64_t *blocked_us);
 int barcodes_stream_dims(const BarcodesStream *b, const char *who, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
                          uint64_t *barcode_bytes, uint64_t *n_unmapped);
 int barcodes_stream_copy(const BarcodesStream *b, const char *who, uint8_t *out_barcodes, uint64_t *out_barcode_off,

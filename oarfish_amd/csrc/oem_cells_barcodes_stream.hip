@@ -5,9 +5,11 @@
 // cell from batch to batch, and the session's group workers collate, gather, filter and run the closed cells in groups
 // while later batches arrive.  The rule is stated once, in oem_collate.h ("Cells from a barcode-collated stream").
 //
-//   push      checks the batch on the calling thread, waits for room in the staging budget (max_staged_nnz, counted in
-//             records), takes the ticket and copies everything into page-locked staging outside the lock
-//   parse     one worker, batches in ticket order, on the null stream:
+//   push      checks the batch on the calling thread and hands it to the staging queue (oem_stage_queue.h: the wait for
+//             room in the budget -- max_staged_nnz, counted in records --, the ticket, the page-locked staging and the
+//             copy outside the lock).  The session's own: the order of its refusals (the parse worker's error, the owning
+//             session's sticky status, "finished"), ticket_base, and the layout the copy fills (Batch's accessors).
+//   parse     the queue's one worker, batches in ticket order (process), on the null stream:
 //               upload; parse_survivors drops the unmapped records; parse_survivor_names gathers the survivors' names
 //               (with their flags) and barcodes into dense blobs and validates them, so that a skipped record's bytes
 //               are never examined;
@@ -47,7 +49,6 @@
 // n_positions, the cells' first positions and cell_dups for barcodes_stream_assemble: every later group's place in
 // `order` depends on what the earlier ones lost.  A session without UMIs allocates and launches nothing of this.
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -56,7 +57,6 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <hipcub/hipcub.hpp>
@@ -64,6 +64,7 @@
 #include "oem_cells_barcodes_stream.h"
 #include "oem_collate_device.h"
 #include "oem_parse_device.h"
+#include "oem_stage_queue.h"
 
 namespace oem {
 namespace {
@@ -75,10 +76,6 @@ constexpr uint64_t kFirstArenaBytes = 64ull << 10;
 constexpr int kPoolBatches = 8;              // idle staging allocations kept for reuse
 
 inline dim3 grid_of(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kBT - 1) / kBT, 1)); }
-
-struct U32AsU64 {
-    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
-};
 
 // len bytes at a and at b, 8 at a time; both blobs are readable 15 bytes past their last name
 __device__ __forceinline__ bool bytes_equal(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint64_t len)
@@ -203,34 +200,20 @@ int arena_make(uint64_t cap, uint64_t cap_bytes, bool with_ids, uint64_t umi_byt
     return OEM_OK;
 }
 
-// page-locked (or, when that allocation fails, pageable) host memory of one staged batch
-struct HostMem {
-    void *p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-};
-void host_free(HostMem &h)
-{
-    if (h.pinned) (void)hipHostFree(h.p);
-    else free(h.p);
-    h = HostMem();
-}
-
 inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
 
 // A staged batch: the records, the two offset tables, the flags, the two blobs; in a UMI session the UMIs' offset table
 // and blob behind them.
-struct Batch {
-    uint64_t ticket = 0, n = 0, rec_base = 0, bc_bytes = 0, name_bytes = 0, umi_bytes = 0;
-    bool has_sec = false, has_umis = false, ready = false;
-    HostMem mem;
-    size_t at_bc_off() const { return up64(sizeof(oem_aln_record) * n); }
-    size_t at_name_off() const { return at_bc_off() + up64(sizeof(uint64_t) * (n + 1)); }
-    size_t at_sec() const { return at_name_off() + up64(sizeof(uint64_t) * (n + 1)); }
-    size_t at_bc() const { return at_sec() + up64(n); }
+struct Batch : StageBatch {
+    uint64_t bc_bytes = 0, name_bytes = 0, umi_bytes = 0;
+    bool has_sec = false, has_umis = false;
+    size_t at_bc_off() const { return up64(sizeof(oem_aln_record) * n_records); }
+    size_t at_name_off() const { return at_bc_off() + up64(sizeof(uint64_t) * (n_records + 1)); }
+    size_t at_sec() const { return at_name_off() + up64(sizeof(uint64_t) * (n_records + 1)); }
+    size_t at_bc() const { return at_sec() + up64(n_records); }
     size_t at_names() const { return at_bc() + up64(bc_bytes); }
     size_t at_umi_off() const { return at_names() + up64(name_bytes); }
-    size_t at_umis() const { return at_umi_off() + up64(sizeof(uint64_t) * (n + 1)); }
+    size_t at_umis() const { return at_umi_off() + up64(sizeof(uint64_t) * (n_records + 1)); }
     size_t bytes() const { return has_umis ? at_umis() + up64(umi_bytes) : at_umi_off(); }
     const char *base() const { return (const char *)mem.p; }
 };
@@ -248,6 +231,12 @@ struct Slot {
     bool done = false;
 };
 
+struct U32AsU64 {
+    __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
+};
+
+} // namespace
+
 int exclusive_scan_u32(const uint32_t *d_in, uint64_t *d_out, uint64_t n)
 {
     hipcub::TransformInputIterator<uint64_t, U32AsU64, const uint32_t *> in(d_in, U32AsU64());
@@ -260,22 +249,18 @@ int exclusive_scan_u32(const uint32_t *d_in, uint64_t *d_out, uint64_t n)
     return OEM_OK;
 }
 
-} // namespace
-
 struct BarcodesStream {
     BarcodesEnv env;
 
-    std::mutex mu;
-    std::condition_variable cv_work, cv_space, cv_groups;
-    std::deque<std::unique_ptr<Batch>> queue; // ticket order
-    std::vector<HostMem> pool;
+    // The staging queue of the batches (oem_stage_queue.h) with the parse worker.  Its lock is this part's own lock too.
+    StageQueue<Batch> q;
+    std::mutex &mu = q.mu;
+    std::condition_variable cv_groups;        // the group hand-off of cut_groups: not the queue's
     std::vector<uint64_t> ticket_base;        // by ticket: the session-global index of the batch's first record
-    uint64_t next_ticket = 0, total_records = 0, staged_records = 0;
-    int pushes_in_flight = 0, groups_in_flight = 0;
-    bool closed = false, stop = false, cancel = false;
+    int groups_in_flight = 0;
+    bool closed = false, cancel = false;
     int stuck_rc = OEM_OK; // the parse worker's own error (the session's sticky status holds it too)
     std::string stuck_msg;
-    std::thread worker;
 
     // -- the parse worker's state (no lock: one thread; finish reads it after the join) ---------------------------------
     std::shared_ptr<Arena> arena;
@@ -306,11 +291,15 @@ struct BarcodesStream {
     std::vector<uint64_t> out_cell_rec_off, out_order, out_group_off, out_cell_group_off;
     std::vector<uint32_t> out_kept;
 
-    ~BarcodesStream()
+    explicit BarcodesStream(const BarcodesEnv &e)
+        : env(e), q(e.max_staged, kPoolBatches,
+                    [this](size_t bytes, StageMem *m) {
+                        if (stage_host_alloc(env.device, bytes, m)) return true;
+                        set_stuck(OEM_ERR_OOM, "oem_cells_stream_push_barcodes: host allocation of the staging memory failed");
+                        return false;
+                    },
+                    stage_host_free)
     {
-        for (HostMem &h : pool) host_free(h);
-        for (auto &b : queue)
-            if (b->mem.p) host_free(b->mem);
     }
     uint64_t n_cells_opened() const { return label_off.size() - 1; }
     void set_stuck(int rc, const char *msg)
@@ -323,7 +312,7 @@ struct BarcodesStream {
             }
         }
         env.set_sticky(rc, msg);
-        cv_space.notify_all();
+        q.wake_pushers();
     }
     uint64_t ticket_of(uint64_t record)
     {
@@ -347,7 +336,7 @@ struct BarcodesStream {
     int cut_groups(bool final);
     int run_group(const std::shared_ptr<Arena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot, StreamGroupResult *out,
                   bool *batched);
-    void work();
+    void process(Batch &b, bool skip);
 };
 
 // Room for `need` survivors and `need_bytes` name bytes: the arena as it is, or a larger one with the contents moved over.
@@ -486,7 +475,7 @@ int BarcodesStream::finish_any_order(const char *who)
 // One batch on the parse worker: see the head of the file.
 int BarcodesStream::run_batch(const Batch &b)
 {
-    const uint64_t n = b.n;
+    const uint64_t n = b.n_records;
     if (n == 0) return OEM_OK;
     char who[64];
     snprintf(who, sizeof who, "oem_cells_stream: ticket %llu", (unsigned long long)b.ticket);
@@ -879,48 +868,27 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
     return OEM_OK;
 }
 
-void BarcodesStream::work()
+// One batch on the queue's worker (oem_stage_queue.h), in ticket order.  skip: this part is cancelled or the batch was
+// never staged; a stuck session skips too.  The queue takes the staging back and the records out of the budget behind this.
+void BarcodesStream::process(Batch &b, bool skip)
 {
-    const bool dev_ok = hipSetDevice(env.device) == hipSuccess;
-    if (!dev_ok) set_stuck(OEM_ERR_HIP, "oem_cells_stream: the parse worker could not select its device");
-    for (;;) {
-        std::unique_ptr<Batch> b;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv_work.wait(lk, [&] { return (!queue.empty() && queue.front()->ready) || (stop && queue.empty()); });
-            if (queue.empty()) break;
-            b = std::move(queue.front());
-            queue.pop_front();
-        }
-        std::string msg;
-        const bool skip = cancel || env.sticky(&msg) != OEM_OK;
-        int rc = OEM_OK;
-        if (!skip) {
-            try {
-                rc = run_batch(*b);
-            } catch (const std::bad_alloc &) {
-                rc = fail(OEM_ERR_OOM, "oem_cells_stream: host allocation failed in the parse worker");
-            } catch (const std::exception &e) {
-                rc = fail(OEM_ERR_STATE, "oem_cells_stream: %s", e.what());
-            }
-            if (rc != OEM_OK) { // sticky, with everything released
-                msg = last_error_text();
-                arena.reset();
-                carry.reset();
-                intern.release();
-                set_stuck(rc, msg.c_str());
-            }
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            staged_records -= b->n;
-            if (b->mem.p) {
-                if (pool.size() < (size_t)kPoolBatches) pool.push_back(b->mem);
-                else host_free(b->mem);
-                b->mem = HostMem();
-            }
-        }
-        cv_space.notify_all();
+    if (hipSetDevice(env.device) != hipSuccess) set_stuck(OEM_ERR_HIP, "oem_cells_stream: the parse worker could not select its device");
+    std::string msg;
+    if (skip || env.sticky(&msg) != OEM_OK) return;
+    int rc = OEM_OK;
+    try {
+        rc = run_batch(b);
+    } catch (const std::bad_alloc &) {
+        rc = fail(OEM_ERR_OOM, "oem_cells_stream: host allocation failed in the parse worker");
+    } catch (const std::exception &e) {
+        rc = fail(OEM_ERR_STATE, "oem_cells_stream: %s", e.what());
+    }
+    if (rc != OEM_OK) { // sticky, with everything released
+        msg = last_error_text();
+        arena.reset();
+        carry.reset();
+        intern.release();
+        set_stuck(rc, msg.c_str());
     }
 }
 
@@ -934,8 +902,7 @@ void barcodes_stream_table_info(BarcodesStream *b, uint64_t *arena_peak, uint64_
 
 int barcodes_stream_create(const BarcodesEnv &env, bool any_order, BarcodesStream **out)
 {
-    std::unique_ptr<BarcodesStream> b(new BarcodesStream());
-    b->env = env;
+    std::unique_ptr<BarcodesStream> b(new BarcodesStream(env));
     b->any_order = any_order;
     if (any_order) {
         OEM_HIP(hipSetDevice(env.device));
@@ -943,7 +910,7 @@ int barcodes_stream_create(const BarcodesEnv &env, bool any_order, BarcodesStrea
         b->info_slots = b->intern.capacity;
     }
     BarcodesStream *raw = b.get();
-    b->worker = std::thread([raw] { raw->work(); });
+    raw->q.start([raw](Batch &bt, bool skip) { raw->process(bt, skip); });
     *out = b.release();
     return OEM_OK;
 }
@@ -961,115 +928,57 @@ int barcodes_stream_push(BarcodesStream *s, const char *who, const oem_aln_recor
     if (!barcode_off || !name_off) return fail(OEM_ERR_ARG, "%s: barcode_off or name_off is NULL", who);
     if (with_umis && !umi_off) return fail(OEM_ERR_ARG, "%s: umi_off is NULL", who);
     if (n > kCollateMaxBatch) return fail(OEM_ERR_ARG, "%s: %llu records: at most 2^31 - 2 per batch", who, (unsigned long long)n);
-    for (const auto &t : {std::make_pair("barcode", barcode_off), std::make_pair("name", name_off)}) {
-        if (t.second[0] != 0) return fail(OEM_ERR_ARG, "%s: %s_off must start at 0", who, t.first);
-        for (uint64_t i = 0; i < n; ++i)
-            if (t.second[i + 1] < t.second[i])
-                return fail(OEM_ERR_ARG, "%s: %s_off must be non-decreasing (record %llu)", who, t.first, (unsigned long long)i);
-    }
+    OEM_TRY(check_offsets(who, "barcode_off", barcode_off, n, "record"));
+    OEM_TRY(check_offsets(who, "name_off", name_off, n, "record"));
     // (a batch of unmapped records only may come without bytes: a blob is needed where its offsets say it has some)
     if (barcode_off[n] && !barcodes) return fail(OEM_ERR_ARG, "%s: barcodes is NULL and barcode_off[n_records] is not 0", who);
     if (name_off[n] && !names) return fail(OEM_ERR_ARG, "%s: names is NULL and name_off[n_records] is not 0", who);
     if (with_umis) {
-        if (umi_off[0] != 0) return fail(OEM_ERR_ARG, "%s: umi_off must start at 0", who);
-        for (uint64_t i = 0; i < n; ++i)
-            if (umi_off[i + 1] < umi_off[i]) return fail(OEM_ERR_ARG, "%s: umi_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+        OEM_TRY(check_offsets(who, "umi_off", umi_off, n, "record"));
         if (umi_off[n] && !umis) return fail(OEM_ERR_ARG, "%s: umis is NULL and the UMIs are not all empty", who);
     }
     if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
 
-    Batch *b = nullptr;
-    {
-        std::unique_lock<std::mutex> lk(s->mu);
-        ++s->pushes_in_flight;
-        struct InFlight { // (mu is held whenever this scope is left)
-            BarcodesStream *s;
-            ~InFlight() { --s->pushes_in_flight; }
-        } in_flight{s};
-        for (;;) {
+    Batch lay; // the batch's layout: what the initialiser gives the queue's batch and where the copy puts the arrays
+    lay.n_records = n;
+    lay.bc_bytes = barcode_off[n];
+    lay.name_bytes = name_off[n];
+    lay.has_sec = secondary != nullptr && n > 0;
+    lay.has_umis = with_umis;
+    lay.umi_bytes = with_umis ? umi_off[n] : 0;
+    const int rc = s->q.push(
+        n, n ? lay.bytes() : 0,
+        [&](std::unique_lock<std::mutex> &lk) -> int {
             if (s->stuck_rc != OEM_OK) return fail(s->stuck_rc, "%s", s->stuck_msg.c_str()); // (the first error: before all else)
             std::string msg;
             lk.unlock();
-            const int rc = s->env.sticky(&msg); // (a group's error: the session holds it)
+            const int sticky = s->env.sticky(&msg); // (a group's error: the session holds it, under its own lock)
             lk.lock();
-            if (rc != OEM_OK) return fail(rc, "%s", msg.c_str());
-            if (s->closed || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
-            if (s->staged_records == 0 || s->staged_records + n <= s->env.max_staged) break;
-            const auto t0 = std::chrono::steady_clock::now();
-            s->cv_space.wait(lk);
-            const uint64_t us = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-            lk.unlock();
-            s->env.add_blocked_us(us);
-            lk.lock();
-        }
-        std::unique_ptr<Batch> nb(new Batch());
-        s->ticket_base.reserve(s->ticket_base.size() + 1);
-        nb->ticket = s->next_ticket;
-        nb->n = n;
-        nb->rec_base = s->total_records;
-        nb->bc_bytes = barcode_off[n];
-        nb->name_bytes = name_off[n];
-        nb->has_sec = secondary != nullptr && n > 0;
-        nb->has_umis = with_umis;
-        nb->umi_bytes = with_umis ? umi_off[n] : 0;
-        if (n) { // the smallest idle allocation that holds the batch
-            const size_t need = nb->bytes();
-            size_t best = s->pool.size();
-            for (size_t k = 0; k < s->pool.size(); ++k)
-                if (s->pool[k].bytes >= need && (best == s->pool.size() || s->pool[k].bytes < s->pool[best].bytes)) best = k;
-            if (best != s->pool.size()) {
-                nb->mem = s->pool[best];
-                s->pool.erase(s->pool.begin() + best);
-            }
-        }
-        b = nb.get();
-        s->queue.push_back(std::move(nb));
-        s->ticket_base.push_back(s->total_records);
-        ++s->next_ticket;
-        s->total_records += n;
-        s->staged_records += n;
-        ++s->pushes_in_flight; // (the copy below: until the batch is ready)
-    }
-    // outside the lock: the allocation, where the pool had none, and the copies.  The batch stays in the queue until it
-    // is ready (the worker waits for that), so `b` is valid.
-    bool oom = false;
-    if (n && !b->mem.p) {
-        const size_t need = b->bytes(), cap = need + need / 8 + 4096;
-        if (hipSetDevice(s->env.device) == hipSuccess && hipHostMalloc(&b->mem.p, cap, hipHostMallocPortable) == hipSuccess) {
-            b->mem.pinned = true;
-        } else {
-            (void)hipGetLastError();
-            b->mem.p = malloc(cap);
-            oom = !b->mem.p;
-        }
-        b->mem.bytes = cap;
-    }
-    if (n && b->mem.p) {
-        char *mem = (char *)b->mem.p;
-        std::memcpy(mem, records, sizeof(oem_aln_record) * n);
-        std::memcpy(mem + b->at_bc_off(), barcode_off, sizeof(uint64_t) * (n + 1));
-        std::memcpy(mem + b->at_name_off(), name_off, sizeof(uint64_t) * (n + 1));
-        if (b->has_sec) std::memcpy(mem + b->at_sec(), secondary, n);
-        if (b->bc_bytes) std::memcpy(mem + b->at_bc(), barcodes, b->bc_bytes);
-        if (b->name_bytes) std::memcpy(mem + b->at_names(), names, b->name_bytes);
-        if (b->has_umis) std::memcpy(mem + b->at_umi_off(), umi_off, sizeof(uint64_t) * (n + 1));
-        if (b->umi_bytes) std::memcpy(mem + b->at_umis(), umis, b->umi_bytes);
-    }
-    const uint64_t ticket = b->ticket;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (oom) {
-            b->n = 0; // (nothing was staged: the worker passes it by)
-            s->staged_records -= n;
-        }
-        b->ready = true;
-        --s->pushes_in_flight;
-    }
-    if (oom) s->set_stuck(OEM_ERR_OOM, "oem_cells_stream_push_barcodes: host allocation of the staging memory failed");
-    s->cv_work.notify_all();
-    if (oom) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who);
-    if (out_ticket) *out_ticket = ticket;
-    return OEM_OK;
+            if (sticky != OEM_OK) return fail(sticky, "%s", msg.c_str());
+            if (s->closed) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+            return OEM_OK;
+        },
+        [&](Batch &b) {
+            s->ticket_base.push_back(b.rec_base); // (whatever throws, throws here)
+            b.bc_bytes = lay.bc_bytes;
+            b.name_bytes = lay.name_bytes;
+            b.has_sec = lay.has_sec;
+            b.has_umis = lay.has_umis;
+            b.umi_bytes = lay.umi_bytes;
+        },
+        [&](char *mem) {
+            std::memcpy(mem, records, sizeof(oem_aln_record) * n);
+            std::memcpy(mem + lay.at_bc_off(), barcode_off, sizeof(uint64_t) * (n + 1));
+            std::memcpy(mem + lay.at_name_off(), name_off, sizeof(uint64_t) * (n + 1));
+            if (lay.has_sec) std::memcpy(mem + lay.at_sec(), secondary, n);
+            if (lay.bc_bytes) std::memcpy(mem + lay.at_bc(), barcodes, lay.bc_bytes);
+            if (lay.name_bytes) std::memcpy(mem + lay.at_names(), names, lay.name_bytes);
+            if (lay.has_umis) std::memcpy(mem + lay.at_umi_off(), umi_off, sizeof(uint64_t) * (n + 1));
+            if (lay.umi_bytes) std::memcpy(mem + lay.at_umis(), umis, lay.umi_bytes);
+        },
+        out_ticket);
+    if (rc == kStageNoMemory) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who); // (sticky: the queue's alloc)
+    return rc;
 }
 
 int barcodes_stream_set_umis(BarcodesStream *b, const char *who)
@@ -1077,7 +986,7 @@ int barcodes_stream_set_umis(BarcodesStream *b, const char *who)
     std::lock_guard<std::mutex> lk(b->mu);
     if (b->closed || b->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
     if (b->with_umis) return fail(OEM_ERR_STATE, "%s: the session is a UMI session already", who);
-    if (b->next_ticket || b->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    if (b->q.next_ticket || b->q.pushing) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
     b->with_umis = true;
     return OEM_OK;
 }
@@ -1098,22 +1007,15 @@ int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t
     return OEM_OK;
 }
 
-bool barcodes_stream_push_in_flight(BarcodesStream *b)
-{
-    std::lock_guard<std::mutex> lk(b->mu);
-    return b->pushes_in_flight != 0;
-}
+bool barcodes_stream_push_in_flight(BarcodesStream *b) { return b->q.pushes_in_flight() != 0; }
 
 int barcodes_stream_close(BarcodesStream *b, const char *who)
 {
     {
         std::lock_guard<std::mutex> lk(b->mu);
         b->closed = true;
-        b->stop = true;
     }
-    b->cv_work.notify_all();
-    b->cv_space.notify_all();
-    if (b->worker.joinable()) b->worker.join();
+    b->q.close(); // (the parse worker runs what is staged)
     std::string msg;
     const int rc = b->env.sticky(&msg);
     if (rc != OEM_OK) return fail(rc, "%s", msg.c_str());
@@ -1176,11 +1078,12 @@ int barcodes_stream_assemble(BarcodesStream *b, const char *who)
     return OEM_OK;
 }
 
-void barcodes_stream_counts(BarcodesStream *b, uint64_t *n_batches, uint64_t *n_records)
+void barcodes_stream_counts(BarcodesStream *b, uint64_t *n_batches, uint64_t *n_records, uint64_t *blocked_us)
 {
     std::lock_guard<std::mutex> lk(b->mu);
-    *n_batches = b->next_ticket;
-    *n_records = b->total_records;
+    *n_batches = b->q.next_ticket;
+    *n_records = b->q.total_records;
+    *blocked_us = b->q.blocked_us;
 }
 
 int barcodes_stream_dims(const BarcodesStream *b, const char *who, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
@@ -1221,12 +1124,9 @@ void barcodes_stream_cancel(BarcodesStream *b)
         std::lock_guard<std::mutex> lk(b->mu);
         b->cancel = true;
         b->closed = true;
-        b->stop = true;
     }
-    b->cv_work.notify_all();
-    b->cv_space.notify_all();
-    b->cv_groups.notify_all();
-    if (b->worker.joinable()) b->worker.join();
+    b->cv_groups.notify_all(); // (the parse worker may be waiting to hand a group over)
+    b->q.cancel();
 }
 
 void barcodes_stream_destroy(BarcodesStream *b)

@@ -815,10 +815,7 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
     if (n && !records) return fail(OEM_ERR_ARG, "%s: records is NULL", who);
     if (with_umis) {
         if (!umi_off) return fail(OEM_ERR_ARG, "%s: umi_off is NULL", who);
-        if (umi_off[0] != 0) return fail(OEM_ERR_ARG, "%s: umi_off must start at 0", who);
-        for (uint64_t i = 0; i < n; ++i)
-            if (umi_off[i + 1] < umi_off[i])
-                return fail(OEM_ERR_ARG, "%s: umi_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+        OEM_TRY(check_offsets(who, "umi_off", umi_off, n, "record"));
         if (umi_off[n] && !umis) return fail(OEM_ERR_ARG, "%s: umis is NULL and the UMIs are not all empty", who);
     }
     const bool dedup = with_umis && n && umi_off[n] > 0;

@@ -691,10 +691,6 @@ static int set_barcodes(oem_cells_stream *s, const char *who, uint32_t mode, boo
         if (s->sticky_rc != OEM_OK) *msg = s->sticky_msg;
         return s->sticky_rc;
     };
-    env.add_blocked_us = [s](uint64_t us) {
-        std::lock_guard<std::mutex> lk2(s->mu);
-        s->blocked_us += us;
-    };
     return barcodes_stream_create(env, any_order, &s->bc);
 }
 
@@ -839,8 +835,8 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
 {
     if (!s || !value) return fail(OEM_ERR_ARG, "oem_cells_stream_info: NULL argument");
     std::lock_guard<std::mutex> lk(s->mu);
-    uint64_t bc_batches = 0, bc_records = 0, bc_arena = 0, bc_misses = 0, bc_slots = 0;
-    if (s->bc) barcodes_stream_counts(s->bc, &bc_batches, &bc_records);
+    uint64_t bc_batches = 0, bc_records = 0, bc_blocked_us = 0, bc_arena = 0, bc_misses = 0, bc_slots = 0;
+    if (s->bc) barcodes_stream_counts(s->bc, &bc_batches, &bc_records, &bc_blocked_us);
     if (s->bc) barcodes_stream_table_info(s->bc, &bc_arena, &bc_misses, &bc_slots);
     uint64_t dup_reads = 0, dup_records = 0;
     if (s->bc) barcodes_stream_umi_info(s->bc, &dup_reads, &dup_records);
@@ -854,7 +850,7 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
     case OEM_CELLS_STREAM_INFO_ALIGNMENTS: *value = s->bc ? bc_records : s->total_nnz; break;
     case OEM_CELLS_STREAM_INFO_GROUPS: *value = s->groups_started; break;
     case OEM_CELLS_STREAM_INFO_GROUPS_BEFORE_FINISH: *value = s->groups_before_finish; break;
-    case OEM_CELLS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us; break;
+    case OEM_CELLS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us + bc_blocked_us; break; // (a barcoded session: its staging queue's)
     case OEM_CELLS_STREAM_INFO_GROUPS_BATCHED: *value = s->groups_batched; break;
     default: return fail(OEM_ERR_ARG, "oem_cells_stream_info: unknown key %u", key);
     }

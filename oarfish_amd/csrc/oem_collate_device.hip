@@ -828,11 +828,7 @@ int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t
     if (n_records > kCollateMaxBatch)
         return fail(OEM_ERR_ARG, "%s: %llu records: the barcodes are sorted as one batch of at most 2^31 - 2", who, (unsigned long long)n_records);
     if (n_records && !barcodes) return fail(OEM_ERR_ARG, "%s: barcodes is NULL and n_records is not 0", who);
-    if (barcode_off[0] != 0) return fail(OEM_ERR_ARG, "%s: barcode_off must start at 0", who);
-    for (uint64_t i = 0; i < n_records; ++i)
-        if (barcode_off[i + 1] < barcode_off[i])
-            return fail(OEM_ERR_ARG, "%s: barcode_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
-    return OEM_OK;
+    return check_offsets(who, "barcode_off", barcode_off, n_records, "record");
 }
 
 namespace {
@@ -872,12 +868,8 @@ int check_collate_input(const char *who, const uint8_t *names, const uint64_t *n
     if (mode != OEM_COLLATE_SORT && mode != OEM_COLLATE_ADJACENT) return fail(OEM_ERR_ARG, "%s: mode %u is not a mode", who, mode);
     if (n_records > 0xffffffffull) return fail(OEM_ERR_ARG, "%s: %llu records: more than 2^32 - 1", who, (unsigned long long)n_records);
     if (n_records && !names) return fail(OEM_ERR_ARG, "%s: names is NULL and n_records is not 0", who);
-    if (name_off[0] != 0) return fail(OEM_ERR_ARG, "%s: name_off must start at 0", who);
-    for (uint64_t i = 0; i < n_records; ++i)
-        if (name_off[i + 1] < name_off[i]) return fail(OEM_ERR_ARG, "%s: name_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
-    if (cell_rec_off[0] != 0) return fail(OEM_ERR_ARG, "%s: cell_rec_off must start at 0", who);
-    for (uint32_t c = 0; c < n_cells; ++c)
-        if (cell_rec_off[c + 1] < cell_rec_off[c]) return fail(OEM_ERR_ARG, "%s: cell_rec_off must be non-decreasing (cell %u)", who, c);
+    OEM_TRY(check_offsets(who, "name_off", name_off, n_records, "record"));
+    OEM_TRY(check_offsets(who, "cell_rec_off", cell_rec_off, n_cells, "cell"));
     if (cell_rec_off[n_cells] != n_records)
         return fail(OEM_ERR_ARG, "%s: cell_rec_off ends at %llu, not at n_records = %llu", who, (unsigned long long)cell_rec_off[n_cells],
                     (unsigned long long)n_records);

@@ -376,20 +376,14 @@ extern "C" int oem_dedup_umis(const uint8_t *umis, const uint64_t *umi_off, cons
         return fail(OEM_ERR_ARG, "%s: umi_off, group_off, cell_group_off or an output is NULL", who);
     if (n_records > 0xffffffffull) return fail(OEM_ERR_ARG, "%s: %llu records: more than 2^32 - 1", who, (unsigned long long)n_records);
     if (n_positions > 0xffffffffull) return fail(OEM_ERR_ARG, "%s: %llu positions: more than 2^32 - 1", who, (unsigned long long)n_positions);
-    if (umi_off[0] != 0) return fail(OEM_ERR_ARG, "%s: umi_off must start at 0", who);
-    for (uint64_t i = 0; i < n_records; ++i)
-        if (umi_off[i + 1] < umi_off[i]) return fail(OEM_ERR_ARG, "%s: umi_off must be non-decreasing (record %llu)", who, (unsigned long long)i);
+    OEM_TRY(check_offsets(who, "umi_off", umi_off, n_records, "record"));
     if (umi_off[n_records] && !umis) return fail(OEM_ERR_ARG, "%s: umis is NULL and the UMIs are not all empty", who);
     if (n_positions && !order) return fail(OEM_ERR_ARG, "%s: order is NULL and n_positions is not 0", who);
-    if (group_off[0] != 0) return fail(OEM_ERR_ARG, "%s: group_off must start at 0", who);
-    for (uint64_t g = 0; g < n_groups; ++g)
-        if (group_off[g + 1] < group_off[g]) return fail(OEM_ERR_ARG, "%s: group_off must be non-decreasing (group %llu)", who, (unsigned long long)g);
+    OEM_TRY(check_offsets(who, "group_off", group_off, n_groups, "group"));
     if (group_off[n_groups] != n_positions)
         return fail(OEM_ERR_ARG, "%s: group_off ends at %llu, not at n_positions = %llu", who, (unsigned long long)group_off[n_groups],
                     (unsigned long long)n_positions);
-    if (cell_group_off[0] != 0) return fail(OEM_ERR_ARG, "%s: cell_group_off must start at 0", who);
-    for (uint32_t c = 0; c < n_cells; ++c)
-        if (cell_group_off[c + 1] < cell_group_off[c]) return fail(OEM_ERR_ARG, "%s: cell_group_off must be non-decreasing (cell %u)", who, c);
+    OEM_TRY(check_offsets(who, "cell_group_off", cell_group_off, n_cells, "cell"));
     if (cell_group_off[n_cells] != n_groups)
         return fail(OEM_ERR_ARG, "%s: cell_group_off ends at %llu, not at n_groups = %llu", who, (unsigned long long)cell_group_off[n_cells],
                     (unsigned long long)n_groups);

@@ -45,6 +45,18 @@ int fail(int code, const char *fmt, ...);
         if (_rc != OEM_OK) return _rc; \
     } while (0)
 
+// The check of an offsets array the caller hands in: off[0 .. n] starts at 0 and never decreases.  `name` is the array's
+// name and `unit` what it counts, both as the messages say them: "<who>: <name> must start at 0",
+// "<who>: <name> must be non-decreasing (<unit> <index>)".
+template <typename Off, typename N>
+int check_offsets(const char *who, const char *name, const Off *off, N n, const char *unit)
+{
+    if (off[0] != 0) return fail(OEM_ERR_ARG, "%s: %s must start at 0", who, name);
+    for (N i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return fail(OEM_ERR_ARG, "%s: %s must be non-decreasing (%s %llu)", who, name, unit, (unsigned long long)i);
+    return OEM_OK;
+}
+
 // Tuning / test switch (oem_knobs.cpp): the product library always returns `dflt`; only the
 // test-only library built with -DOEM_TESTING reads the environment variable `name`.
 long knob(const char *name, long dflt);

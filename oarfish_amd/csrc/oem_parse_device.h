@@ -1,6 +1,7 @@
 // oem_parse_device.h -- the steps of the bulk parser on the device (oem_records_names.hip) that the one call
 // (oem_store_create_records_names) and the names sessions (oem_records_stream_push_names and _push_sort,
-// oem_records_stream.hip) share.  Everything runs on the null stream and leaves it idle.
+// oem_records_stream.hip) share.  Everything runs on the null stream and leaves it idle.  Also the host memory of the
+// staging queue (oem_stage_queue.h) for the sessions that parse on the device: these and the barcoded cells sessions.
 #pragma once
 
 #include <functional>
@@ -8,8 +9,29 @@
 
 #include "oem_collate_device.h"
 #include "oem_filter_device.h"
+#include "oem_stage_queue.h"
 
 namespace oem {
+
+// A staged batch's host memory: page-locked on `device` so that the worker uploads straight from it, else pageable.
+// False when neither is to be had.
+inline bool stage_host_alloc(int device, size_t bytes, StageMem *m)
+{
+    if (hipSetDevice(device) == hipSuccess && hipHostMalloc(&m->p, bytes, hipHostMallocPortable) == hipSuccess) {
+        m->pinned = true;
+        return true;
+    }
+    (void)hipGetLastError();
+    m->pinned = false;
+    m->p = malloc(bytes);
+    return m->p != nullptr;
+}
+inline void stage_host_free(StageMem &m)
+{
+    if (m.pinned) (void)hipHostFree(m.p);
+    else free(m.p);
+    m = StageMem();
+}
 
 // The survivors of d_in[0 .. n) (the records without OEM_REC_UNMAPPED): *m of them, and order_parse, their input
 // indices in ascending order.  order_parse is left empty when it would be the identity (m == n) unless `always`.

@@ -2,18 +2,19 @@
 // for a caller that never holds all records at once (parse_alignments, alignment_parser.rs:301-437, adds group by
 // group; the raw-read drivers of bulk.rs:364-682 hand chunks from mapper threads to a consumer).
 //
-//   push      checks the batch on the calling thread, waits for room in the staging budget, takes the batch's ticket under
-//             the session lock and copies group offsets and records into a page-locked arena outside it: the staging
-//             copies of several pushing threads run side by side, where the one call has one thread for all of them.
-//             Arenas are reused from batch to batch (page-locking memory costs more than filling it).
-//   worker    one thread takes the batches in ticket order and runs the pass of the one call on each of them
-//             (filter_device with pinned_src: the uploads straight from the arena on two lanes, k_filter_measure behind
+//   push      checks the batch on the calling thread and hands it to the session's staging queue (oem_stage_queue.h: the
+//             wait for room in the budget, the ticket, the reused page-locked arenas, the copies of several pushing
+//             threads side by side, where the one call has one thread for all of them).  What is the session's own: the
+//             order of its refusals (push_status), a batch's fields and its piece's slot (stage_batch), and the layout
+//             the copy fills (Batch's accessors).
+//   worker    the queue's one thread hands the batches over in ticket order (process); the pass of the one call runs on
+//             each of them (filter_device with pinned_src: the uploads straight from the arena on two lanes, k_filter_measure behind
 //             each chunk, the scans, k_filter_emit), with base 0.  What stays is the batch's PIECE: its CSR with u32 row
 //             pointers from 0, its kept counts and its discard counters; coordinates and strand only under a coverage
 //             model.  The batch's device records are freed inside the pass, its arena goes back to the pool.  The
 //             fallbacks are the one call's, per batch: the host loop takes a batch with a score beyond +-2^24, or every
 //             batch when score_prob_denom has no table, and its piece is uploaded.
-//   finish    joins the worker, scans the pieces' sizes into per-piece row, alignment and group bases and launches
+//   finish    closes the queue (the worker runs what is staged and is joined), scans the pieces' sizes into per-piece row, alignment and group bases and launches
 //             k_stream_concat once over all arrays of all pieces: the result is the FilterResult the one call's pass
 //             would have left, and filter_result_to_store makes the store of it.  The pieces are freed after the join.
 //
@@ -36,20 +37,17 @@
 // their 64-bit session-global indices (k_arena_append) -- are appended to an arena that stays on the device and grows
 // geometrically; finish runs the one call's tail (parse_tail, oem_parse_device.h) on the arena as on an uploaded input.
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
-#include <deque>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "oem_filter_device.h"
 #include "oem_parse_device.h"
+#include "oem_stage_queue.h"
 
 namespace oem {
 namespace {
@@ -158,32 +156,15 @@ __global__ __launch_bounds__(kCT) void k_stream_concat(const ConcatJob *__restri
     }
 }
 
-// page-locked (or, when that allocation fails, pageable) host memory of one batch: its group offsets, then its records
-struct Arena {
-    void *p = nullptr;
-    size_t bytes = 0;
-    bool pinned = false;
-};
-void arena_free(Arena &a)
-{
-    if (a.pinned) (void)hipHostFree(a.p);
-    else free(a.p);
-    a = Arena();
-}
-
-struct Batch {
-    uint64_t ticket = 0, n_groups = 0, n_records = 0;
+// A staged batch: in its arena (mem: none for a batch without groups, or without records in a names session) the group
+// offsets, then the records.  rec_base is the session-global input index of its first record.
+struct Batch : StageBatch {
+    uint64_t n_groups = 0;
     // a names session's batch: no groups yet; the arena holds name_off (n_records + 1), the records and the name bytes
     bool named = false;
     bool projected = false; // a projected session's batch: whole groups of oem_proj_record with their read lengths
     bool sorting = false, has_sec = false; // a sorting names session's batch (named too); its n_records flags behind the names
-    uint64_t rec_base = 0, name_bytes = 0; // the session-global input index of its first record; name_off[n_records]
-    Arena mem;          // (none for a batch without groups, or without records in a names session)
-    bool ready = false; // the pushing thread has finished its copy
-    Batch() = default;
-    Batch(const Batch &) = delete;
-    Batch &operator=(const Batch &) = delete;
-    ~Batch() { if (mem.p) arena_free(mem); }
+    uint64_t name_bytes = 0; // name_off[n_records]
     const uint64_t *group_off() const { return (const uint64_t *)mem.p; }
     static size_t records_at(uint64_t n_groups) { return (sizeof(uint64_t) * (n_groups + 1) + 63) & ~(size_t)63; }
     // Where a batch of whole groups keeps its records, by record type: a projected batch has its n_groups read lengths
@@ -390,55 +371,33 @@ struct oem_records_stream {
     std::vector<uint64_t> txp_len;
     std::vector<float> tab; // filter_prob_table of f.score_prob_denom
     bool host_only = false; // ... or there is none: the host loop takes every batch
-    uint64_t max_staged = 0;
 
-    mutable std::mutex mu;
-    std::condition_variable cv_work, cv_space;
-    std::deque<std::unique_ptr<Batch>> queue; // ticket order
-    std::vector<Arena> pool;
+    // The staging queue (oem_stage_queue.h): tickets, budget, arenas and the worker.  Its lock is the session's.
+    StageQueue<Batch> q;
+    std::mutex &mu = q.mu;
     std::vector<std::unique_ptr<Piece>> pieces; // by ticket
-    uint64_t next_ticket = 0, total_groups = 0, total_records = 0, staged_records = 0, total_kept = 0;
-    uint64_t before_finish = 0, blocked_us = 0, host_batches = 0, names_unique = 0;
-    int pushes_in_flight = 0;
-    bool finish_called = false, stop = false, cancel = false;
+    uint64_t total_groups = 0, total_kept = 0;
+    uint64_t before_finish = 0, host_batches = 0, names_unique = 0;
+    bool finish_called = false;
     int sticky_rc = OEM_OK;
     std::string sticky_msg;
-    std::thread worker;
 
-    ~oem_records_stream()
+    explicit oem_records_stream(const oem_records_stream_opts &opts)
+        : o(opts), q(opts.max_staged_records ? opts.max_staged_records : kDefaultMaxStaged, kPoolArenas,
+                     [this](size_t bytes, StageMem *m) {
+                         if (stage_host_alloc(o.device, bytes, m)) return true;
+                         std::lock_guard<std::mutex> lk(mu);
+                         set_sticky(OEM_ERR_OOM, "oem_records_stream_push: host allocation of the staging memory failed");
+                         return false;
+                     },
+                     stage_host_free)
     {
-        for (Arena &a : pool) arena_free(a);
     }
     void set_sticky(int rc, const char *msg) // (mu held)
     {
         if (sticky_rc != OEM_OK) return;
         sticky_rc = rc;
         sticky_msg = msg;
-    }
-    // (mu held) the smallest idle arena that holds `bytes`, or an empty one
-    Arena take_arena(size_t bytes)
-    {
-        size_t best = pool.size();
-        for (size_t k = 0; k < pool.size(); ++k)
-            if (pool[k].bytes >= bytes && (best == pool.size() || pool[k].bytes < pool[best].bytes)) best = k;
-        if (best == pool.size()) return Arena();
-        Arena a = pool[best];
-        pool.erase(pool.begin() + best);
-        return a;
-    }
-    void give_arena(Arena &a) // (mu held)
-    {
-        if (!a.p) return;
-        if (pool.size() >= (size_t)kPoolArenas) { // the smallest one goes
-            size_t least = 0;
-            for (size_t k = 1; k < pool.size(); ++k)
-                if (pool[k].bytes < pool[least].bytes) least = k;
-            if (pool[least].bytes < a.bytes) std::swap(pool[least], a);
-            arena_free(a);
-            return;
-        }
-        pool.push_back(a);
-        a = Arena();
     }
 
     // -- the names session (oem_records_stream_set_names) --------------------------------------------------------------
@@ -487,7 +446,7 @@ struct oem_records_stream {
     int run_check(const char *who);
     int names_close(const char *who);
     int host_piece(const oem_aln_record *records, const uint64_t *group_off, uint64_t n_groups, const char *who, Piece *out);
-    void work();
+    void process(Batch &b, bool skip);
     int join(const char *who, FilterResult *out, uint64_t *n_groups);
     int finish_begin(const char *who, bool names_form);
 };
@@ -882,7 +841,7 @@ int oem_records_stream::names_close(const char *who)
         OEM_HIP(hipMemcpy(d_gb.p, gb, sizeof gb, hipMemcpyHostToDevice));
         std::unique_ptr<Piece> piece(new Piece());
         bool host = false;
-        OEM_TRY(close_groups(who, total_records, 0, nullptr, nullptr, nullptr, 0, d_gb.p, 1, false, d_names.p, d_name_off.p,
+        OEM_TRY(close_groups(who, q.total_records, 0, nullptr, nullptr, nullptr, 0, d_gb.p, 1, false, d_names.p, d_name_off.p,
                              piece.get(), &host));
         total_kept += piece->r.nnz;
         total_groups += piece->n_groups;
@@ -1038,61 +997,50 @@ int oem_records_stream::finish_sort(const char *who, const oem_store_opts *opts,
     return OEM_OK;
 }
 
-void oem_records_stream::work()
+// One batch on the queue's worker (oem_stage_queue.h), in ticket order.  skip: the session is cancelled or the batch was
+// never staged; a stuck session skips too.  The queue takes the arena back and the records out of the budget behind this.
+void oem_records_stream::process(Batch &b, bool skip)
 {
     const bool dev_ok = hipSetDevice(o.device) == hipSuccess;
-    for (;;) {
-        std::unique_ptr<Batch> b;
-        bool skip;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv_work.wait(lk, [&] { return (!queue.empty() && queue.front()->ready) || (stop && queue.empty()); });
-            if (queue.empty()) break;
-            b = std::move(queue.front());
-            queue.pop_front();
-            if (!dev_ok) set_sticky(OEM_ERR_HIP, "oem_records_stream: the device worker could not select its device");
-            skip = cancel || sticky_rc != OEM_OK;
-            if (!skip && !finish_called) ++before_finish;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!dev_ok) set_sticky(OEM_ERR_HIP, "oem_records_stream: the device worker could not select its device");
+        skip = skip || sticky_rc != OEM_OK;
+        if (!skip && !finish_called) ++before_finish;
+    }
+    std::unique_ptr<Piece> piece;
+    bool host = false;
+    int rc = OEM_OK;
+    std::string msg;
+    if (!skip) {
+        try {
+            piece.reset(new Piece());
+            rc = b.sorting     ? run_batch_sort(b)
+                 : b.named     ? run_batch_names(b, piece.get(), &host)
+                 : b.projected ? run_batch<oem_proj_record>(b, piece.get(), &host)
+                               : run_batch<oem_aln_record>(b, piece.get(), &host);
+        } catch (const std::bad_alloc &) {
+            rc = fail(OEM_ERR_OOM, "oem_records_stream: host allocation failed in the device worker");
+        } catch (const std::exception &e) {
+            rc = fail(OEM_ERR_STATE, "oem_records_stream: %s", e.what());
         }
-        std::unique_ptr<Piece> piece;
-        bool host = false;
-        int rc = OEM_OK;
-        std::string msg;
-        if (!skip) {
-            try {
-                piece.reset(new Piece());
-                rc = b->sorting     ? run_batch_sort(*b)
-                     : b->named     ? run_batch_names(*b, piece.get(), &host)
-                     : b->projected ? run_batch<oem_proj_record>(*b, piece.get(), &host)
-                                    : run_batch<oem_aln_record>(*b, piece.get(), &host);
-            } catch (const std::bad_alloc &) {
-                rc = fail(OEM_ERR_OOM, "oem_records_stream: host allocation failed in the device worker");
-            } catch (const std::exception &e) {
-                rc = fail(OEM_ERR_STATE, "oem_records_stream: %s", e.what());
-            }
-            if (rc != OEM_OK) {
-                msg = last_error_text(); // (the message is thread-local)
-                piece.reset();
-                arena.release(); // (a sorting names session is stuck from here on: everything it held goes)
-            }
+        if (rc != OEM_OK) {
+            msg = last_error_text(); // (the message is thread-local)
+            piece.reset();
+            arena.release(); // (a sorting names session is stuck from here on: everything it held goes)
         }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            staged_records -= b->n_records;
-            give_arena(b->mem);
-            arena_peak = arena.peak;
-            if (rc != OEM_OK) {
-                set_sticky(rc, msg.c_str());
-            } else if (!skip) {
-                total_kept += piece->r.nnz;
-                if (b->named) total_groups += piece->n_groups;
-                if (host) ++host_batches;
-                if (total_kept >= (1ull << 32))
-                    set_sticky(OEM_ERR_ARG, "oem_records_stream: 2^32 or more alignments are kept; a resident store needs fewer");
-                pieces[b->ticket] = std::move(piece);
-            }
-        }
-        cv_space.notify_all();
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    arena_peak = arena.peak;
+    if (rc != OEM_OK) {
+        set_sticky(rc, msg.c_str());
+    } else if (!skip) {
+        total_kept += piece->r.nnz;
+        if (b.named) total_groups += piece->n_groups;
+        if (host) ++host_batches;
+        if (total_kept >= (1ull << 32))
+            set_sticky(OEM_ERR_ARG, "oem_records_stream: 2^32 or more alignments are kept; a resident store needs fewer");
+        pieces[b.ticket] = std::move(piece);
     }
 }
 
@@ -1210,12 +1158,10 @@ int oem_records_stream::finish_begin(const char *who, bool names_form)
             return fail(OEM_ERR_STATE, names_form ? "%s: not a names session (oem_records_stream_set_names)"
                                                   : "%s: a names session is finished by oem_records_stream_finish_names", who);
         if (finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished already", who);
-        if (pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a push is in flight", who);
+        if (q.pushing) return fail(OEM_ERR_STATE, "%s: a push is in flight", who);
         finish_called = true;
-        stop = true;
     }
-    cv_work.notify_all();
-    if (worker.joinable()) worker.join();
+    q.close(); // (the worker runs what is staged)
     if (sticky_rc != OEM_OK) return fail(sticky_rc, "%s", sticky_msg.c_str());
     OEM_HIP(hipSetDevice(o.device));
     return OEM_OK;
@@ -1233,14 +1179,12 @@ extern "C" int oem_records_stream_create(const oem_records_stream_opts *opts, co
     for (uint32_t r : opts->reserved)
         if (r) return fail(OEM_ERR_ARG, "%s: a reserved word is not 0", who);
     OEM_TRY(ensure_device(opts->device));
-    std::unique_ptr<oem_records_stream> s(new oem_records_stream());
-    s->o = *opts;
+    std::unique_ptr<oem_records_stream> s(new oem_records_stream(*opts));
     s->f = *filters;
     s->txp_len.assign(txp_len, txp_len + opts->n_txps);
     s->host_only = !filter_prob_table(filters->score_prob_denom, s->tab);
-    s->max_staged = opts->max_staged_records ? opts->max_staged_records : kDefaultMaxStaged;
     oem_records_stream *raw = s.get();
-    raw->worker = std::thread([raw] { raw->work(); });
+    raw->q.start([raw](Batch &b, bool skip) { raw->process(b, skip); });
     *out = s.release();
     return OEM_OK;
     OEM_API_END("oem_records_stream_create")
@@ -1249,89 +1193,47 @@ extern "C" int oem_records_stream_create(const oem_records_stream_opts *opts, co
 namespace oem {
 namespace {
 
-// What the three pushes do once the batch's own checks have passed: wait for room in the staging budget, take the ticket
-// under the session lock, then -- outside it -- find an arena of `bytes` and let fill(arena) copy the caller's arrays.
-// kind: the session the push belongs to (oem_records_stream::kind()).  1: the batch of a names session (n_groups 0,
-// name_bytes = name_off[n_records]); 2: of a projected session; 3: of a sorting names session (as 1, has_sec: with
-// flags); a batch has a payload when `bytes` > 0.
+// What the four pushes do once the batch's own checks have passed: the queue's push (oem_stage_queue.h) with the
+// session's refusals as the status check, the batch's fields and its piece's slot as the initialiser, and fill(arena)
+// to copy the caller's arrays.  kind: the session the push belongs to (oem_records_stream::kind()).  1: the batch of a
+// names session (n_groups 0, name_bytes = name_off[n_records]); 2: of a projected session; 3: of a sorting names session
+// (as 1, has_sec: with flags); a batch has a payload when `bytes` > 0.
 template <typename Fill>
 int stage_batch(oem_records_stream *s, const char *who, int kind, uint64_t n_groups, uint64_t n_records, uint64_t name_bytes, size_t bytes,
                 Fill &&fill, uint64_t *out_ticket, bool has_sec = false)
 {
     const bool named = kind == 1 || kind == 3;
-    Batch *b = nullptr;
-    {
-        std::unique_lock<std::mutex> lk(s->mu);
-        if (s->kind() != kind)
-            return fail(OEM_ERR_STATE,
-                        s->sorting  ? "%s: a sorting names session takes oem_records_stream_push_sort"
-                        : kind == 3 ? "%s: not a sorting names session (oem_records_stream_set_sort)"
-                        : kind == 1 ? "%s: not a names session (oem_records_stream_set_names)"
-                        : kind == 2 ? "%s: not a projected session (oem_records_stream_set_projected)"
-                        : s->named  ? "%s: a names session takes oem_records_stream_push_names"
-                                    : "%s: a projected session takes oem_records_stream_push_projected",
-                        who);
-        ++s->pushes_in_flight;
-        struct InFlight { // (mu is held whenever this scope is left)
-            oem_records_stream *s;
-            ~InFlight() { --s->pushes_in_flight; }
-        } in_flight{s};
-        for (;;) {
+    const int rc = s->q.push(
+        n_records, bytes,
+        [&](std::unique_lock<std::mutex> &) -> int {
+            if (s->kind() != kind)
+                return fail(OEM_ERR_STATE,
+                            s->sorting  ? "%s: a sorting names session takes oem_records_stream_push_sort"
+                            : kind == 3 ? "%s: not a sorting names session (oem_records_stream_set_sort)"
+                            : kind == 1 ? "%s: not a names session (oem_records_stream_set_names)"
+                            : kind == 2 ? "%s: not a projected session (oem_records_stream_set_projected)"
+                            : s->named  ? "%s: a names session takes oem_records_stream_push_names"
+                                        : "%s: a projected session takes oem_records_stream_push_projected",
+                            who);
             if (named && s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str()); // (a names session: before all else)
-            if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+            if (s->finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
             if (s->sticky_rc != OEM_OK) return fail(s->sticky_rc, "%s", s->sticky_msg.c_str());
-            if (s->staged_records == 0 || s->staged_records + n_records <= s->max_staged) break;
-            const auto t0 = std::chrono::steady_clock::now();
-            s->cv_space.wait(lk);
-            s->blocked_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-        }
-        std::unique_ptr<Batch> nb(new Batch());
-        s->pieces.reserve(s->pieces.size() + 2); // (so that taking the ticket below cannot throw half-way; + the carry's piece)
-        nb->ticket = s->next_ticket;
-        nb->n_groups = n_groups;
-        nb->n_records = n_records;
-        nb->named = named;
-        nb->projected = kind == 2;
-        nb->sorting = kind == 3;
-        nb->has_sec = has_sec;
-        nb->rec_base = s->total_records;
-        nb->name_bytes = name_bytes;
-        if (bytes) nb->mem = s->take_arena(bytes);
-        b = nb.get();
-        s->queue.push_back(std::move(nb));
-        s->pieces.emplace_back();
-        ++s->next_ticket;
-        s->total_groups += n_groups;
-        s->total_records += n_records;
-        s->staged_records += n_records;
-        ++s->pushes_in_flight; // (the copy below: until the batch is ready)
-    }
-    // outside the lock: the arena, where the pool had none, and the copies.  The batch stays in the queue until it is
-    // ready (the worker waits for that), so `b` is valid.
-    bool oom = false;
-    if (!b->mem.p && bytes) {
-        const size_t cap = bytes + bytes / 8 + 4096; // (batches of a run are of one size, more or less)
-        if (hipSetDevice(s->o.device) == hipSuccess && hipHostMalloc(&b->mem.p, cap, hipHostMallocPortable) == hipSuccess) {
-            b->mem.pinned = true;
-        } else {
-            (void)hipGetLastError();
-            b->mem.p = malloc(cap);
-            oom = !b->mem.p;
-        }
-        b->mem.bytes = cap;
-    }
-    if (b->mem.p) fill((char *)b->mem.p);
-    const uint64_t ticket = b->ticket;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (oom) s->set_sticky(OEM_ERR_OOM, "oem_records_stream_push: host allocation of the staging memory failed");
-        b->ready = true; // (after a failure the worker drops it: the session is stuck)
-        --s->pushes_in_flight;
-    }
-    s->cv_work.notify_all();
-    if (oom) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who);
-    if (out_ticket) *out_ticket = ticket;
-    return OEM_OK;
+            return OEM_OK;
+        },
+        [&](Batch &b) {
+            s->pieces.reserve(s->pieces.size() + 2); // (whatever throws, throws here: + the carry's piece)
+            s->pieces.emplace_back();
+            b.n_groups = n_groups;
+            b.named = named;
+            b.projected = kind == 2;
+            b.sorting = kind == 3;
+            b.has_sec = has_sec;
+            b.name_bytes = name_bytes;
+            s->total_groups += n_groups;
+        },
+        fill, out_ticket);
+    if (rc == kStageNoMemory) return fail(OEM_ERR_OOM, "%s: host allocation of the staging memory failed", who); // (sticky: the queue's alloc)
+    return rc;
 }
 
 } // namespace
@@ -1367,8 +1269,8 @@ extern "C" int oem_records_stream_set_projected(oem_records_stream *s, const oem
     std::lock_guard<std::mutex> lk(s->mu);
     if (s->projected) return fail(OEM_ERR_STATE, "%s: the session is a projected session already", who);
     if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session", who);
-    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
-    if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    if (s->finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->q.next_ticket || s->q.pushing) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
     s->projected = true;
     s->popts = *popts;
     s->host_only = host_only; // (the worker reads these two with its first batch, which no thread has pushed yet)
@@ -1405,8 +1307,8 @@ extern "C" int oem_records_stream_set_names(oem_records_stream *s, uint64_t sort
     std::lock_guard<std::mutex> lk(s->mu);
     if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session already", who);
     if (s->projected) return fail(OEM_ERR_STATE, "%s: the session is a projected session", who);
-    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
-    if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    if (s->finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->q.next_ticket || s->q.pushing) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
     s->named = true;
     s->sort_check_num = sort_check_num;
     return OEM_OK;
@@ -1444,8 +1346,8 @@ extern "C" int oem_records_stream_set_sort(oem_records_stream *s)
     if (s->sorting) return fail(OEM_ERR_STATE, "%s: the session is a sorting names session already", who);
     if (s->named) return fail(OEM_ERR_STATE, "%s: the session is a names session", who);
     if (s->projected) return fail(OEM_ERR_STATE, "%s: the session is a projected session", who);
-    if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
-    if (s->next_ticket || s->pushes_in_flight) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    if (s->finish_called) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (s->q.next_ticket || s->q.pushing) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
     s->named = true; // (finish_names, names_copy and the sticky rules are the names session's)
     s->sorting = true;
     s->sort_check_num = 0;
@@ -1618,11 +1520,11 @@ extern "C" int oem_records_stream_info(const oem_records_stream *s, uint32_t key
     if (!s || !value) return fail(OEM_ERR_ARG, "oem_records_stream_info: NULL argument");
     std::lock_guard<std::mutex> lk(s->mu);
     switch (key) {
-    case OEM_RECORDS_STREAM_INFO_BATCHES: *value = s->next_ticket; break;
+    case OEM_RECORDS_STREAM_INFO_BATCHES: *value = s->q.next_ticket; break;
     case OEM_RECORDS_STREAM_INFO_GROUPS: *value = s->total_groups; break;
-    case OEM_RECORDS_STREAM_INFO_RECORDS: *value = s->total_records; break;
+    case OEM_RECORDS_STREAM_INFO_RECORDS: *value = s->q.total_records; break;
     case OEM_RECORDS_STREAM_INFO_BATCHES_BEFORE_FINISH: *value = s->before_finish; break;
-    case OEM_RECORDS_STREAM_INFO_BLOCKED_US: *value = s->blocked_us; break;
+    case OEM_RECORDS_STREAM_INFO_BLOCKED_US: *value = s->q.blocked_us; break;
     case OEM_RECORDS_STREAM_INFO_HOST_BATCHES: *value = s->host_batches; break;
     case OEM_RECORDS_STREAM_INFO_ROW_NAME_BYTES: *value = s->out_rows.size(); break;
     case OEM_RECORDS_STREAM_INFO_HOST_FINISHED: *value = s->host_finished; break;
@@ -1637,13 +1539,9 @@ extern "C" void oem_records_stream_destroy(oem_records_stream *s)
     if (!s) return;
     {
         std::lock_guard<std::mutex> lk(s->mu);
-        if (!s->finish_called) s->cancel = true; // staged batches are dropped; the batch on the device runs to its end
         s->finish_called = true;
-        s->stop = true;
     }
-    s->cv_work.notify_all();
-    s->cv_space.notify_all();
-    if (s->worker.joinable()) s->worker.join();
+    s->q.cancel(); // staged batches are dropped; the batch on the device runs to its end
     (void)hipSetDevice(s->o.device); // the pieces and the page-locked arenas are released on their device
     delete s;
 }
