@@ -816,9 +816,9 @@ int oem_em_run_cells_records_barcodes_sparse(
  * number of duplicates in cell c.  Dropping the duplicate groups' positions from order / group_off / cell_group_off gives
  * the deduplicated collation; no cell becomes empty through it.
  *
- * Limits, on purpose: matching is exact, on corrected UMIs (umi_tools' `unique` method), with no edit-distance
- * clustering; the key is (cell, UMI), with no gene in it; the survivor is not chosen by read length or by what the
- * filter keeps.
+ * Limits, on purpose: this call matches exactly, on corrected UMIs (umi_tools' `unique` method), and its key is (cell,
+ * UMI), with no gene in it: oem_dedup_umis_rule below adds the gene and the one-mismatch correction.  In both the
+ * survivor is not chosen by read length or by what the filter keeps.
  *
  * OEM_ERR_ARG before any device use: umi_off, group_off, cell_group_off or an output NULL; umis NULL while a UMI has
  * bytes; order NULL with n_positions > 0; offsets not from 0 or decreasing; group_off not ending at n_positions;
@@ -876,6 +876,67 @@ int oem_em_run_cells_records_umis_sparse(
     uint64_t *out_cell_group_off /* capacity n_records + 1, or NULL */,
     uint32_t *out_kept /* capacity n_records, or NULL */,
     uint64_t *out_cell_dups /* capacity n_records, *out_n_cells written; or NULL */,
+    oem_cells_result **out);
+
+/* A UMI RULE: gene-aware keys and one-mismatch correction for the two calls above.  The reference has no counterpart
+ * (docs/index.md:308-312 wants deduplicated input); the rule is oarfish_amd/csrc/oem_collate.h ("UMI deduplication"),
+ * whose host walk is the specification the device is held to exactly.
+ *   - gene_of: NULL, or one gene id per transcript (n_txps of them).  gene(g) = gene_of[ref_id(head(g))], the gene of the
+ *     read's first record in collated order; 0 for every group when gene_of is NULL.  A segment is the groups of one cell
+ *     that take part and share gene(g); a class is the groups of one SEGMENT with byte-identical UMIs, so the same UMI in
+ *     two genes of one cell is two molecules (Cell Ranger, alevin-fry and UMI-tools key by (cell, gene, UMI)).
+ *   - correct: 0 or 1.  With 1, two classes of one segment whose UMIs have the same length and differ in exactly one
+ *     byte position are neighbours (any bytes; there is no alphabet); a class u takes as its parent the neighbour v with
+ *     n(v) > n(u) that has the most groups, among equals the one whose UMI bytes compare smallest; parents are chosen
+ *     from the original counts, a root is a class without a parent, and a molecule is the groups of all classes with one
+ *     root.  Its smallest group index survives, every other member is a duplicate of it.  A corrected group is one
+ *     whose class has a parent; it may itself be its molecule's survivor.
+ * rule == NULL or {NULL, 0, 0} gives oem_dedup_umis / oem_em_run_cells_records_umis_sparse exactly.
+ * Limits, on purpose: the gene of a read that maps to several genes is its head's; one mismatch only, no indels; the
+ * survivor is not chosen by read length or by what the filter keeps; deduplication still runs before the filter.  The
+ * UMI sessions (oem_cells_stream_set_umis) keep the exact rule. */
+typedef struct {
+    const uint32_t *gene_of; /* n_txps gene ids, or NULL: no gene in the key */
+    uint32_t n_txps;
+    uint32_t correct;        /* 0: exact matching; 1: one-mismatch correction */
+} oem_umi_rule;
+
+/* oem_dedup_umis under a rule.  ref_id (n_records): the records' transcript ids, required iff rule->gene_of is given and
+ * read only at the heads of groups that take part (an unmapped record's ref_id is never looked at).
+ * out_cell_corrected[c] (or NULL) is the number of corrected groups of cell c.  OEM_ERR_ARG before any device use, beyond
+ * oem_dedup_umis': gene_of given and n_txps == 0; gene_of given and ref_id NULL; correct > 1.  Found on the device also:
+ * the head of a group that takes part whose ref_id is not below n_txps, naming the smallest such input index. */
+int oem_dedup_umis_rule(const oem_umi_rule *rule /* or NULL */,
+                        const uint8_t *umis, const uint64_t *umi_off, const uint32_t *flags /* n_records, or NULL */,
+                        const uint32_t *ref_id /* n_records, or NULL */,
+                        uint64_t n_records, const uint32_t *order, uint64_t n_positions,
+                        const uint64_t *group_off, uint64_t n_groups, const uint64_t *cell_group_off, uint32_t n_cells,
+                        int device,
+                        uint8_t *out_dup            /* n_groups */,
+                        uint64_t *out_survivor      /* n_groups */,
+                        uint64_t *out_cell_dups     /* n_cells */,
+                        uint64_t *out_cell_corrected /* n_cells, or NULL */);
+
+/* oem_em_run_cells_records_umis_sparse under a rule: the join of its seven steps with oem_dedup_umis_rule in place of
+ * oem_dedup_umis, the records' own ref_id words being the ref_id; exactly equal to that join as the umis call is to
+ * its own.  rule->gene_of, when given, must have rule->n_txps == n_txps.  out_cell_corrected (capacity n_records,
+ * *out_n_cells written; or NULL): the corrected groups of every cell.  A head of a read that takes part whose ref_id is
+ * not below n_txps is OEM_ERR_ARG found on the device, naming the record by its input index. */
+int oem_em_run_cells_records_umis_rule_sparse(
+    const oem_umi_rule *rule /* or NULL */,
+    const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+    const oem_aln_record *records, uint64_t n_records,
+    const uint8_t *barcodes, const uint64_t *barcode_off,
+    const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+    const uint8_t *umis, const uint64_t *umi_off,
+    uint32_t mode, uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+    uint32_t *out_order /* capacity n_records, *out_n_survivors written; or NULL */, uint64_t *out_n_survivors /* or NULL */,
+    uint64_t *out_cell_rec_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_cells /* or NULL */,
+    uint64_t *out_group_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_groups /* or NULL */,
+    uint64_t *out_cell_group_off /* capacity n_records + 1, or NULL */,
+    uint32_t *out_kept /* capacity n_records, or NULL */,
+    uint64_t *out_cell_dups /* capacity n_records, *out_n_cells written; or NULL */,
+    uint64_t *out_cell_corrected /* capacity n_records, *out_n_cells written; or NULL */,
     oem_cells_result **out);
 
 /* The bulk parser and oem_store_create_records in one call: parse_alignments (alignment_parser.rs:301-437) from the

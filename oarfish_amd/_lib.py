@@ -83,6 +83,7 @@ ABI_SYMBOLS = [
     "oem_em_run_cells_records_sparse", "oem_cells_result_discard_tables", "oem_collate_names",
     "oem_em_run_cells_records_names_sparse", "oem_collate_barcodes", "oem_em_run_cells_records_barcodes_sparse",
     "oem_dedup_umis", "oem_em_run_cells_records_umis_sparse",
+    "oem_dedup_umis_rule", "oem_em_run_cells_records_umis_rule_sparse",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_set_barcodes", "oem_cells_stream_push_barcodes", "oem_cells_stream_barcodes_dims",
     "oem_cells_stream_barcodes_copy", "oem_cells_stream_set_barcodes_any_order",
@@ -264,6 +265,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_em_run_cells_records_umis_sparse.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp, u32, u32, i32, f64, i32,
                                                        u32, f64, vp, C.POINTER(u64), vp, C.POINTER(u64), vp, C.POINTER(u64), vp, vp,
                                                        vp, C.POINTER(vp)]
+    L.oem_dedup_umis_rule.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, i32, vp, vp, vp, vp]
+    L.oem_em_run_cells_records_umis_rule_sparse.argtypes = [vp] + L.oem_em_run_cells_records_umis_sparse.argtypes[:-1] + [vp, C.POINTER(vp)]
     L.oem_store_create_records_names.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, u32, u64, u32, i32, f64, i32, vp, vp, vp, vp, vp,
                                                  vp, vp, vp, C.POINTER(vp)]
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
@@ -353,6 +356,8 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_barcode_table_last.argtypes = [vp]
         L.oem_test_collate_barcodes_host.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
         L.oem_test_dedup_umis_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp]
+        L.oem_test_dedup_umis_rule_host.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp, vp]
+        L.oem_debug_dedup_rule_last_call.argtypes = [vp]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.oem_debug_records_stream_finish_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -112,7 +112,7 @@ TESTING_HOOKS = ["oem_debug_layout_hash", "oem_debug_local_comm_create", "oem_te
                  "oem_debug_collate_barcodes_last_call", "oem_debug_cells_barcodes_last_call", "oem_test_collate_barcodes_host",
                  "oem_debug_records_stream_finish_csr", "oem_debug_records_stream_last_join",
                  "oem_debug_records_names_last_call", "oem_test_parse_bulk_host", "oem_debug_barcode_table_last",
-                 "oem_test_dedup_umis_host"]
+                 "oem_test_dedup_umis_host", "oem_test_dedup_umis_rule_host", "oem_debug_dedup_rule_last_call"]
 
 
 def header_symbols() -> list:

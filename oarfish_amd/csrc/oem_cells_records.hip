@@ -290,6 +290,7 @@ struct NamesSlot {
     uint64_t n_positions = 0;                        // the positions of the group's deduplicated order
     std::vector<uint32_t> order;                     // n_positions (if asked for)
     std::vector<uint64_t> cell_pos_off, cell_dups;   // from 0: n_cells + 1; n_cells
+    std::vector<uint64_t> cell_corrected;            // n_cells (under a UMI rule: the cells' corrected groups)
 };
 
 // The cells [c0, c1) of the call: collate, gather, filter and run.  rg: the group's place and outputs (records,
@@ -315,6 +316,7 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
     if (dedup) {
         slot->cell_pos_off.assign((size_t)n_cells + 1, 0);
         slot->cell_dups.assign(n_cells, 0);
+        slot->cell_corrected.assign(n_cells, 0);
     }
     if (m == 0) { // cells without records: no groups, and the run of cells without reads
         const uint64_t zero = 0;
@@ -346,7 +348,7 @@ int run_names_group(const char *who, const CellsRun &run, const RecordsFilter &r
             tm.lap("names: collate");
             UmiMarks mk;
             OEM_TRY(dedup_mark(*dv.umi, cr.order.p, dv.order_bc + r0, cr.group_off.p, cr.n_groups, cr.cell_group_off.p, n_cells, 0, &mk,
-                               slot->cell_dups.data()));
+                               slot->cell_dups.data(), slot->cell_corrected.data()));
             if (mk.n_dups) {
                 cpo.resize((size_t)n_cells + 1);
                 OEM_TRY(dedup_compact(mk, m, n_cells, &cr, &mp, cpo.data()));
@@ -474,7 +476,7 @@ void names_call_outputs(const std::vector<std::pair<uint32_t, uint32_t>> &groups
 // positions and their duplicate counts wait in its slot.
 void umis_call_outputs(const std::vector<std::pair<uint32_t, uint32_t>> &groups, const std::vector<NamesSlot> &slots, uint32_t *out_order,
                        uint64_t *out_n_survivors, uint64_t *out_cell_rec_off, uint64_t *out_group_off, uint64_t *out_n_groups,
-                       uint64_t *out_cell_group_off, uint32_t *out_kept, uint64_t *out_cell_dups)
+                       uint64_t *out_cell_group_off, uint32_t *out_kept, uint64_t *out_cell_dups, uint64_t *out_cell_corrected)
 {
     uint64_t group_base = 0, pos_base = 0;
     for (size_t g = 0; g < groups.size(); ++g) {
@@ -489,6 +491,7 @@ void umis_call_outputs(const std::vector<std::pair<uint32_t, uint32_t>> &groups,
         if (out_kept && sl.n_groups) std::memcpy(out_kept + group_base, sl.kept.data(), sizeof(uint32_t) * sl.n_groups);
         if (out_order && sl.n_positions) std::memcpy(out_order + pos_base, sl.order.data(), sizeof(uint32_t) * sl.n_positions);
         if (out_cell_dups) std::copy(sl.cell_dups.begin(), sl.cell_dups.end(), out_cell_dups + c0);
+        if (out_cell_corrected) std::copy(sl.cell_corrected.begin(), sl.cell_corrected.end(), out_cell_corrected + c0);
         group_base += sl.n_groups;
         pos_base += sl.n_positions;
     }
@@ -792,11 +795,12 @@ extern "C" int oem_em_run_cells_records_names_sparse(const oem_filters *filters,
 static int cells_records_barcodes_call(const char *who, const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
                                        const oem_aln_record *records, uint64_t n_records, const uint8_t *barcodes,
                                        const uint64_t *barcode_off, const uint8_t *names, const uint64_t *name_off,
-                                       const uint8_t *secondary, bool with_umis, const uint8_t *umis, const uint64_t *umi_off, uint32_t mode,
+                                       const uint8_t *secondary, bool with_umis, const oem_umi_rule *rule, const uint8_t *umis,
+                                       const uint64_t *umi_off, uint32_t mode,
                                        uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
                                        uint32_t *out_order, uint64_t *out_n_survivors, uint64_t *out_cell_rec_off, uint64_t *out_n_cells,
                                        uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off, uint32_t *out_kept,
-                                       uint64_t *out_cell_dups, oem_cells_result **out)
+                                       uint64_t *out_cell_dups, uint64_t *out_cell_corrected, oem_cells_result **out)
 {
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -817,6 +821,13 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
         if (!umi_off) return fail(OEM_ERR_ARG, "%s: umi_off is NULL", who);
         OEM_TRY(check_offsets(who, "umi_off", umi_off, n, "record"));
         if (umi_off[n] && !umis) return fail(OEM_ERR_ARG, "%s: umis is NULL and the UMIs are not all empty", who);
+    }
+    const uint32_t *gene_of = rule ? rule->gene_of : nullptr;
+    if (rule) {
+        if (rule->correct > 1) return fail(OEM_ERR_ARG, "%s: rule->correct = %u is neither 0 nor 1", who, rule->correct);
+        if (gene_of && !rule->n_txps) return fail(OEM_ERR_ARG, "%s: rule->gene_of is given and rule->n_txps is 0", who);
+        if (gene_of && rule->n_txps != n_txps)
+            return fail(OEM_ERR_ARG, "%s: rule->n_txps = %u is not n_txps = %u", who, rule->n_txps, n_txps);
     }
     const bool dedup = with_umis && n && umi_off[n] > 0;
     if (model >= 0) OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, 0, 0));
@@ -935,6 +946,18 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
     um.d_umi_off = d_umi_off.p;
     um.d_flags = d_records.p ? (const uint32_t *)d_records.p + 8 : nullptr;
     um.flags_stride = 10;
+    DevBuf<uint32_t> d_gene_of;
+    if (dedup && gene_of) { // ... and so is the ref_id: word 0
+        static_assert(offsetof(oem_aln_record, ref_id) == 0, "the ref_id word of a resident record");
+        OEM_TRY(dev_alloc(&d_gene_of.p, n_txps, nullptr));
+        OEM_HIP(hipMemcpy(d_gene_of.p, gene_of, sizeof(uint32_t) * n_txps, hipMemcpyHostToDevice));
+        um.d_ref_id = (const uint32_t *)d_records.p;
+        um.ref_id_stride = 10;
+        um.d_gene_of = d_gene_of.p;
+        um.n_txps = n_txps;
+    }
+    um.correct = rule ? rule->correct : 0u;
+    if (rule) dedup_rule_reset_last();
     if (dedup) dv.umi = &um;
     NamesCall nc;
     nc.in.who = who;
@@ -965,12 +988,13 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
     last[5] = ms_since(t0);
     if (dedup) {
         umis_call_outputs(groups, slots, out_order, out_n_survivors, out_cell_rec_off, out_group_off, out_n_groups, out_cell_group_off, out_kept,
-                          out_cell_dups);
+                          out_cell_dups, out_cell_corrected);
     } else {
         names_call_outputs(groups, slots, cro.data(), n, out_group_off, out_n_groups, out_cell_group_off, out_kept);
         if (out_cell_rec_off) std::memcpy(out_cell_rec_off, cro.data(), sizeof(uint64_t) * ((size_t)n_cells + 1));
         if (out_n_survivors) *out_n_survivors = n;
         if (out_cell_dups) std::fill(out_cell_dups, out_cell_dups + n_cells, 0ull);
+        if (out_cell_corrected) std::fill(out_cell_corrected, out_cell_corrected + n_cells, 0ull);
     }
     OEM_TRY(cells_result_from_blocks(who, blocks, r.get()));
     if (out_n_cells) *out_n_cells = n_cells;
@@ -990,9 +1014,9 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
 {
     OEM_API_BEGIN
     return cells_records_barcodes_call("oem_em_run_cells_records_barcodes_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
-                                       barcode_off, names, name_off, secondary, false, nullptr, nullptr, mode, bin_width, model, growth_rate,
+                                       barcode_off, names, name_off, secondary, false, nullptr, nullptr, nullptr, mode, bin_width, model, growth_rate,
                                        device, max_iter, conv_thresh, out_order, nullptr, out_cell_rec_off, out_n_cells, out_group_off,
-                                       out_n_groups, out_cell_group_off, out_kept, nullptr, out);
+                                       out_n_groups, out_cell_group_off, out_kept, nullptr, nullptr, out);
     OEM_API_END("oem_em_run_cells_records_barcodes_sparse")
 }
 
@@ -1008,10 +1032,29 @@ extern "C" int oem_em_run_cells_records_umis_sparse(const oem_filters *filters, 
 {
     OEM_API_BEGIN
     return cells_records_barcodes_call("oem_em_run_cells_records_umis_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
-                                       barcode_off, names, name_off, secondary, true, umis, umi_off, mode, bin_width, model, growth_rate, device,
-                                       max_iter, conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off,
-                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, out);
+                                       barcode_off, names, name_off, secondary, true, nullptr, umis, umi_off, mode, bin_width, model, growth_rate,
+                                       device, max_iter, conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off,
+                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, nullptr, out);
     OEM_API_END("oem_em_run_cells_records_umis_sparse")
+}
+
+extern "C" int oem_em_run_cells_records_umis_rule_sparse(const oem_umi_rule *rule, const oem_filters *filters, const uint64_t *txp_len,
+                                                         uint32_t n_txps, const oem_aln_record *records, uint64_t n_records,
+                                                         const uint8_t *barcodes, const uint64_t *barcode_off, const uint8_t *names,
+                                                         const uint64_t *name_off, const uint8_t *secondary, const uint8_t *umis,
+                                                         const uint64_t *umi_off, uint32_t mode, uint32_t bin_width, int model,
+                                                         double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+                                                         uint32_t *out_order, uint64_t *out_n_survivors, uint64_t *out_cell_rec_off,
+                                                         uint64_t *out_n_cells, uint64_t *out_group_off, uint64_t *out_n_groups,
+                                                         uint64_t *out_cell_group_off, uint32_t *out_kept, uint64_t *out_cell_dups,
+                                                         uint64_t *out_cell_corrected, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    return cells_records_barcodes_call("oem_em_run_cells_records_umis_rule_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
+                                       barcode_off, names, name_off, secondary, true, rule, umis, umi_off, mode, bin_width, model, growth_rate,
+                                       device, max_iter, conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off,
+                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, out_cell_corrected, out);
+    OEM_API_END("oem_em_run_cells_records_umis_rule_sparse")
 }
 
 extern "C" int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out)

@@ -234,9 +234,34 @@ constexpr uint32_t kRecUnmapped = 1u; // OEM_REC_UNMAPPED
 //             cell_dups[c], the duplicates of cell c; and the DEDUPLICATED COLLATION order', group_off', cell_group_off',
 //             cell_rec_off': the same arrays with the duplicate groups' positions removed and everything else in place
 //             (dedup_drop_host).  No cell becomes empty through this: every class keeps one member.
-// Limits, on purpose: matching is exact, on corrected UMIs (umi_tools' `unique` method) -- no edit-distance clustering;
-// the key is (cell, UMI), with no gene in it; the survivor is not chosen by read length or by what the filter keeps --
-// deduplication runs before the filter.
+//
+// The UMI rule (dedup_umis_rule_host below, oem_dedup_umis_rule, oem_em_run_cells_records_umis_rule_sparse) is
+// (gene_of, correct): gene_of is NULL or one uint32 gene id per transcript, correct is 0 or 1.  With gene_of == NULL and
+// correct == 0 everything below reduces to the rule above, result for result.  head, "takes part" and the cell
+// boundaries stay as they are.
+//   gene(g)   gene_of[ref_id(head(g))]: the gene of the read's first record in collated order, under kCollateSort its
+//             primary's.  0 for every group when gene_of is NULL.  Only groups that take part are looked up (their head
+//             is mapped, so it has a ref_id); a ref_id that is not below n_txps is an error naming the smallest such
+//             input index.
+//   segment   the groups of one cell that take part and share gene(g).  A class is now the set of groups of one segment
+//             with byte-identical UMIs; n(u) is the number of groups in class u.
+//   neighbour two classes u != v of one segment are neighbours iff their UMIs have the same length and differ in exactly
+//             one byte position.  Any bytes: there is no alphabet (N, lower case and 0xff are bytes like any other).
+//   parent    (only with correct) parent(u) is chosen among the neighbours v with n(v) > n(u) -- strictly, so there are
+//             no cycles: the one with the greatest n(v), among equals the one whose UMI bytes compare smallest
+//             (collate_name_cmp).  No such neighbour: no parent.  Parents are chosen from the ORIGINAL counts.
+//   root      root(u) follows parent until a class has none; the counts rise strictly along the way.
+//   molecule  the groups of all classes with one root.  Its survivor is its smallest group index, every other member is
+//             a duplicate of it: the convention above, so under kCollateSort the result still does not depend on the
+//             input's order.
+//   corrected a group whose class has a parent; cell_corrected[c] counts them.  A corrected group may itself be its
+//             molecule's survivor.
+//   results   dup, survivor, cell_dups as above, and cell_corrected.  No cell becomes empty; groups that do not take
+//             part are untouched and shadow nothing.
+// Limits, on purpose: the gene of a read that maps to several genes is its head's; one mismatch only, no indels (this is
+// Cell Ranger's rule, not umi_tools' directional network); the survivor is not chosen by read length or by what the
+// filter keeps -- deduplication still runs before the filter.  Without a rule (dedup_umis_host, the sessions) matching
+// is exact, on corrected UMIs (umi_tools' `unique` method), and the key is (cell, UMI), with no gene in it.
 
 // The first input record (kCollateNoRecord: none) whose UMI holds a 0 byte.  Empty UMIs are legal.
 inline uint64_t dedup_first_bad_umi(const uint8_t *umis, const uint64_t *umi_off, uint64_t n_records)
@@ -286,6 +311,94 @@ inline void dedup_umis_host(const uint8_t *umis, const uint64_t *umi_off, const 
             ++cell_dups[c];
         }
     }
+}
+
+// Two UMIs of one length that differ in exactly one byte position.
+OEM_HD inline bool dedup_umis_neighbours(const uint8_t *a, uint64_t la, const uint8_t *b, uint64_t lb)
+{
+    if (la != lb) return false;
+    uint64_t differ = 0;
+    for (uint64_t i = 0; i < la; ++i) differ += a[i] != b[i] ? 1 : 0;
+    return differ == 1;
+}
+
+// The host walk of the UMI rule (gene_of, correct): the specification, all pairs inside a segment.  ref_id: one word per
+// input record, read only with gene_of and only at the heads of groups that take part; cell_corrected (n_cells) may be
+// NULL.  Returns kCollateNoRecord, or the smallest input index of such a head whose ref_id is not below n_txps, and
+// then leaves the outputs alone.  The other arguments are dedup_umis_host's, checked by the caller.
+inline uint64_t dedup_umis_rule_host(const uint8_t *umis, const uint64_t *umi_off, const uint32_t *flags, const uint32_t *ref_id,
+                                     const uint32_t *gene_of, uint32_t n_txps, uint32_t correct, const uint32_t *order,
+                                     const uint64_t *group_off, uint64_t n_groups, const uint64_t *cell_group_off, uint32_t n_cells,
+                                     uint8_t *dup, uint64_t *survivor, uint64_t *cell_dups, uint64_t *cell_corrected)
+{
+    auto head = [&](uint64_t g) { return order[group_off[g]]; };
+    auto takes_part = [&](uint64_t g) {
+        if (group_off[g + 1] == group_off[g]) return false;
+        const uint32_t i = head(g);
+        return umi_off[i + 1] > umi_off[i] && !(flags && (flags[i] & kRecUnmapped));
+    };
+    if (gene_of) {
+        uint64_t bad = kCollateNoRecord;
+        for (uint64_t g = 0; g < n_groups; ++g)
+            if (takes_part(g) && ref_id[head(g)] >= n_txps) bad = std::min<uint64_t>(bad, head(g));
+        if (bad != kCollateNoRecord) return bad;
+    }
+    for (uint64_t g = 0; g < n_groups; ++g) {
+        dup[g] = 0;
+        survivor[g] = g;
+    }
+    auto gene = [&](uint64_t g) { return gene_of ? gene_of[ref_id[head(g)]] : 0u; };
+    auto umi = [&](uint64_t g) { return umis + umi_off[head(g)]; };
+    auto len = [&](uint64_t g) { return umi_off[(uint64_t)head(g) + 1] - umi_off[head(g)]; };
+    auto cmp = [&](uint64_t a, uint64_t b) { return collate_name_cmp(umi(a), len(a), umi(b), len(b)); };
+    std::vector<uint64_t> part, first, parent; // first: where a class starts in part, then part.size()
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        cell_dups[c] = 0;
+        if (cell_corrected) cell_corrected[c] = 0;
+        part.clear();
+        for (uint64_t g = cell_group_off[c]; g < cell_group_off[c + 1]; ++g)
+            if (takes_part(g)) part.push_back(g);
+        std::sort(part.begin(), part.end(), [&](uint64_t a, uint64_t b) {
+            if (gene(a) != gene(b)) return gene(a) < gene(b);
+            const int r = cmp(a, b);
+            return r ? r < 0 : a < b;
+        });
+        first.clear();
+        for (size_t k = 0; k < part.size(); ++k)
+            if (k == 0 || gene(part[k - 1]) != gene(part[k]) || cmp(part[k - 1], part[k]) != 0) first.push_back(k);
+        const size_t n_classes = first.size();
+        first.push_back(part.size());
+        auto rep = [&](size_t u) { return part[first[u]]; }; // a class's smallest group
+        auto count = [&](size_t u) { return first[u + 1] - first[u]; };
+        parent.assign(n_classes, kCollateNoRecord);
+        for (size_t s0 = 0, s1 = 0; correct && s0 < n_classes; s0 = s1) { // a segment: the classes [s0, s1) of one gene
+            for (s1 = s0 + 1; s1 < n_classes && gene(rep(s1)) == gene(rep(s0));) ++s1;
+            for (size_t u = s0; u < s1; ++u)
+                for (size_t v = s0; v < s1; ++v) {
+                    if (v == u || count(v) <= count(u)) continue;
+                    if (!dedup_umis_neighbours(umi(rep(u)), len(rep(u)), umi(rep(v)), len(rep(v)))) continue;
+                    const uint64_t p = parent[u];
+                    if (p == kCollateNoRecord || count(v) > count(p) || (count(v) == count(p) && cmp(rep(v), rep(p)) < 0)) parent[u] = v;
+                }
+        }
+        std::vector<uint64_t> root(n_classes), least(n_classes, kCollateNoRecord); // least: a root's molecule's smallest group
+        for (size_t u = 0; u < n_classes; ++u) {
+            size_t r = u;
+            while (parent[r] != kCollateNoRecord) r = parent[r];
+            root[u] = r;
+            least[r] = std::min(least[r], rep(u));
+        }
+        for (size_t u = 0; u < n_classes; ++u)
+            for (uint64_t k = first[u]; k < first[u + 1]; ++k) {
+                const uint64_t g = part[k];
+                if (parent[u] != kCollateNoRecord && cell_corrected) ++cell_corrected[c];
+                if (g == least[root[u]]) continue;
+                dup[g] = 1;
+                survivor[g] = least[root[u]];
+                ++cell_dups[c];
+            }
+    }
+    return kCollateNoRecord;
 }
 
 // The deduplicated collation: the positions of the duplicate groups removed.  out_order (capacity n_positions),

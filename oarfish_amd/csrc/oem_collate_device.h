@@ -106,6 +106,12 @@ struct UmiInput {
     const uint64_t *d_umi_off = nullptr; // n_records + 1
     const uint32_t *d_flags = nullptr;   // record i's flags word at d_flags[i * flags_stride], or NULL: none unmapped
     uint64_t flags_stride = 1;           // (10 with the flags read out of resident 40-byte records)
+    // The UMI rule (oem_collate.h); with d_gene_of == NULL and correct == 0 dedup_mark launches what it launches without.
+    const uint32_t *d_ref_id = nullptr;  // record i's ref_id at d_ref_id[i * ref_id_stride]: required with d_gene_of
+    uint64_t ref_id_stride = 1;          // (10: word 0 of resident 40-byte records)
+    const uint32_t *d_gene_of = nullptr; // n_txps gene ids, or NULL: no gene in the key
+    uint32_t n_txps = 0;
+    uint32_t correct = 0;                // 1: one-mismatch correction
 };
 // What dedup_mark leaves on the device for a batch of ng groups.
 struct UmiMarks {
@@ -114,6 +120,9 @@ struct UmiMarks {
     DevBuf<uint64_t> keep;     // ng + 1: 1 - dup, then 0
     DevBuf<uint64_t> gscan;    // ng + 1, only with n_dups > 0: the exclusive scan of keep, the kept groups' new numbers
     uint64_t n_part = 0, n_classes = 0, n_dups = 0; // (n_classes: only when two groups or more take part)
+    // under a rule with correct: the classes that have a parent, the rounds of pointer jumping, and the longest walk of
+    // a class over its half-sharing neighbours in the first and in the second (halves swapped) collation
+    uint64_t n_corrected_classes = 0, jump_rounds = 0, walk_max[2] = {0, 0};
 };
 // The UMIs (checked: umi_off from 0, non-decreasing) up through the upload lanes, validated behind their chunks: a 0 byte
 // is OEM_ERR_ARG naming the smallest such input index, an empty UMI is legal.
@@ -126,9 +135,18 @@ int umis_gather_survivors(const uint8_t *d_umis, const uint64_t *d_umi_off, cons
                           DevBuf<uint64_t> *d_dense_off, uint64_t *dense_bytes, uint64_t *bad_record);
 // The duplicates of a batch of nc cells whose collation is on the device: d_order (positions -> input indices, or ->
 // positions of d_order_bc where that is not NULL), d_group_off (ng + 1, from 0), d_cell_group_off (nc + 1, from 0).
-// cell_dups: host, nc.  With out->n_dups == 0 nothing else needs to be done.  Leaves the device idle.
+// cell_dups: host, nc.  With out->n_dups == 0 nothing else needs to be done.  Leaves the device idle.  Under a rule:
+// cell_corrected (host, nc, or NULL) are the cells' corrected groups, and the head of a group that takes part whose
+// ref_id is not below n_txps is OEM_ERR_ARG naming the smallest such input index of the batch.
 int dedup_mark(const UmiInput &in, const uint32_t *d_order, const uint32_t *d_order_bc, const uint64_t *d_group_off, uint64_t ng,
-               const uint64_t *d_cell_group_off, uint32_t nc, uint64_t survivor_base, UmiMarks *out, uint64_t *cell_dups);
+               const uint64_t *d_cell_group_off, uint32_t nc, uint64_t survivor_base, UmiMarks *out, uint64_t *cell_dups,
+               uint64_t *cell_corrected = nullptr);
+// What the corrections since the last reset found, process-wide (the groups of the one call run on worker threads; 8
+// doubles, each the sum or the maximum over the batches that ran dedup_mark with correct): [0] participants,
+// [1] classes, [2] classes with a parent, [3] rounds of pointer jumping (max), [4] / [5] the longest neighbour walk in
+// the first / second collation (max), [6] batches that ran the correction.
+void dedup_rule_last_call(double *out8);
+void dedup_rule_reset_last();
 // The deduplicated collation in place of cr's arrays (m positions, nc cells; mk.n_dups > 0): *n_positions of order' are
 // filled, cell_pos_off (host, nc + 1) are the cells' first positions in it.
 int dedup_compact(const UmiMarks &mk, uint64_t m, uint32_t nc, CollateResident *cr, uint64_t *n_positions, uint64_t *cell_pos_off);

@@ -247,6 +247,49 @@ extern "C" int oem_test_dedup_umis_host(const uint8_t *umis, const uint64_t *umi
     OEM_API_END("oem_test_dedup_umis_host")
 }
 
+// Test hook: the host walk of oem_collate.h's UMI rule (dedup_umis_rule_host) with oem_dedup_umis_rule's arguments and
+// outputs.  Checked and worded as the device call: the rule's own argument errors, an order entry that is not below
+// n_records, a UMI with a 0 byte, the head of a read that takes part whose ref_id is not below n_txps.
+extern "C" int oem_test_dedup_umis_rule_host(const oem_umi_rule *rule, const uint8_t *umis, const uint64_t *umi_off, const uint32_t *flags,
+                                             const uint32_t *ref_id, uint64_t n_records, const uint32_t *order, uint64_t n_positions,
+                                             const uint64_t *group_off, uint64_t n_groups, const uint64_t *cell_group_off, uint32_t n_cells,
+                                             uint8_t *out_dup, uint64_t *out_survivor, uint64_t *out_cell_dups, uint64_t *out_cell_corrected)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_test_dedup_umis_rule_host";
+    if (!umi_off || !group_off || !cell_group_off || !out_dup || !out_survivor || !out_cell_dups || (n_positions && !order) ||
+        (umi_off[n_records] && !umis))
+        return fail(OEM_ERR_ARG, "%s: NULL argument", who);
+    const uint32_t *gene_of = rule ? rule->gene_of : nullptr;
+    if (rule) {
+        if (rule->correct > 1) return fail(OEM_ERR_ARG, "%s: rule->correct = %u is neither 0 nor 1", who, rule->correct);
+        if (gene_of && !rule->n_txps) return fail(OEM_ERR_ARG, "%s: rule->gene_of is given and rule->n_txps is 0", who);
+        if (gene_of && !ref_id) return fail(OEM_ERR_ARG, "%s: rule->gene_of is given and ref_id is NULL", who);
+    }
+    for (uint64_t k = 0; k < n_positions; ++k)
+        if (order[k] >= n_records)
+            return fail(OEM_ERR_ARG, "%s: order[%llu] = %u is not below n_records = %llu", who, (unsigned long long)k, order[k],
+                        (unsigned long long)n_records);
+    uint64_t bad = dedup_first_bad_umi(umis, umi_off, n_records);
+    if (bad != kCollateNoRecord) return fail(OEM_ERR_ARG, "%s: the UMI of record %llu contains a 0 byte", who, (unsigned long long)bad);
+    bad = dedup_umis_rule_host(umis, umi_off, flags, ref_id, gene_of, rule ? rule->n_txps : 0u, rule ? rule->correct : 0u, order, group_off,
+                               n_groups, cell_group_off, n_cells, out_dup, out_survivor, out_cell_dups, out_cell_corrected);
+    if (bad != kCollateNoRecord)
+        return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps = %u (the head of a read that takes part in the UMI rule)", who,
+                    (unsigned long long)bad, ref_id[bad], rule->n_txps);
+    return OEM_OK;
+    OEM_API_END("oem_test_dedup_umis_rule_host")
+}
+
+// out[0..7] = what the corrections of the last oem_dedup_umis_rule / oem_em_run_cells_records_umis_rule_sparse found
+// (oem_collate_device.h, dedup_rule_last_call)
+extern "C" int oem_debug_dedup_rule_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_dedup_rule_last_call: NULL argument");
+    dedup_rule_last_call(out);
+    return OEM_OK;
+}
+
 // out[0..7] = this thread's last oem_store_create_records_names: [0] 1 if k_records_gather ran, [1] 1 if the survivors'
 // names were gathered, [2] the groups the collation check looked at, [3] 1 if the host loop took the groups
 namespace oem { void records_names_last_call(double *out8); }

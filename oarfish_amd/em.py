@@ -412,6 +412,67 @@ def dedup_umis(umis, order, group_off, cell_group_off, flags=None, device: int =
     return dup[:n_groups], survivor[:n_groups], cell_dups[:n_cells]
 
 
+class UmiRuleC(C.Structure):
+    """``oem_umi_rule``."""
+    _fields_ = [("gene_of", C.c_void_p), ("n_txps", C.c_uint32), ("correct", C.c_uint32)]
+
+
+def _umi_rule(gene_of, correct):
+    """(the ``oem_umi_rule`` of a call, the array it points into)."""
+    gene = None if gene_of is None else np.ascontiguousarray(gene_of, dtype=np.uint32)
+    if gene is not None and gene.ndim != 1:
+        raise ValueError("gene_of needs one gene id per transcript")
+    return UmiRuleC(None if gene is None or not len(gene) else gene.ctypes.data, 0 if gene is None else len(gene), int(bool(correct))), gene
+
+
+def dedup_umis_rule(umis, order, group_off, cell_group_off, flags=None, ref_id=None, gene_of=None, correct: bool = False,
+                    device: int = 0):
+    """``dedup_umis`` under a UMI rule (``oem_dedup_umis_rule``): gene-aware keys and one-mismatch correction.
+
+    ``gene_of``: None, or one gene id per transcript; ``ref_id`` (the records' ``records["ref_id"]``) is then required,
+    and the key of a molecule is (cell, gene of the read's first record, UMI): the same UMI in two genes of one cell is
+    two molecules.  ``correct``: a UMI one mismatch away from a more abundant UMI of the same cell and gene is an error of
+    it (Cell Ranger's rule; the most abundant such neighbour, among equals the smallest bytes; chains are followed to
+    their root).  With both at their defaults this is ``dedup_umis``.  Returns ``(dup, survivor, cell_dups,
+    cell_corrected)``: ``cell_corrected[c]`` counts the reads of cell ``c`` whose UMI was corrected.
+    """
+    from .types import pack_read_names
+    n = _n_packed(umis)
+    blob, off = pack_read_names(umis, n)
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    group_off = np.ascontiguousarray(group_off, dtype=np.uint64)
+    cell_group_off = np.ascontiguousarray(cell_group_off, dtype=np.uint64)
+    if group_off.ndim != 1 or len(group_off) < 1:
+        raise ValueError("group_off needs n_groups + 1 entries")
+    if cell_group_off.ndim != 1 or len(cell_group_off) < 1:
+        raise ValueError("cell_group_off needs n_cells + 1 entries")
+    fl = rid = None
+    if flags is not None:
+        fl = np.ascontiguousarray(flags, dtype=np.uint32)
+        if len(fl) != n:
+            raise ValueError("flags must have one entry per record")
+    if ref_id is not None:
+        rid = np.ascontiguousarray(ref_id, dtype=np.uint32)
+        if len(rid) != n:
+            raise ValueError("ref_id must have one entry per record")
+    if gene_of is not None and rid is None:
+        raise ValueError("gene_of needs ref_id: a read's gene is its first record's transcript's")
+    rule, _gene = _umi_rule(gene_of, correct)
+    n_groups, n_cells = len(group_off) - 1, len(cell_group_off) - 1
+    dup = np.zeros(max(n_groups, 1), dtype=np.uint8)
+    survivor = np.zeros(max(n_groups, 1), dtype=np.uint64)
+    cell_dups = np.zeros(max(n_cells, 1), dtype=np.uint64)
+    cell_corrected = np.zeros(max(n_cells, 1), dtype=np.uint64)
+    if not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)
+    _lib.check(_lib.lib().oem_dedup_umis_rule(
+        C.addressof(rule), blob.ctypes.data, off.ctypes.data, None if fl is None or not n else fl.ctypes.data,
+        None if rid is None or not n else rid.ctypes.data, n, order.ctypes.data if len(order) else None, len(order), group_off.ctypes.data,
+        n_groups, cell_group_off.ctypes.data, n_cells, device, dup.ctypes.data, survivor.ctypes.data, cell_dups.ctypes.data,
+        cell_corrected.ctypes.data))
+    return dup[:n_groups], survivor[:n_groups], cell_dups[:n_cells], cell_corrected[:n_cells]
+
+
 def drop_groups(order, group_off, cell_group_off, dup):
     """A collated order without the groups marked in ``dup``: the NumPy compaction behind ``dedup_umis``.  Returns
     ``(order, group_off, cell_group_off, cell_rec_off)`` of the deduplicated collation -- the marked groups' positions are
@@ -443,9 +504,13 @@ def gather_names(names, idx):
     return np.ascontiguousarray(blob[src]), new_off
 
 
-def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, sec, barcodes, umis, collate, mode):
+def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, sec, barcodes, umis, collate, mode,
+                           gene_of=None, umi_correct=False):
     """``em_cells_records_sparse(..., barcodes=, names=, umis=)`` behind its packing: the one call
-    (``collate="device"``, oem_em_run_cells_records_umis_sparse), or the seven steps it replaces."""
+    (``collate="device"``, oem_em_run_cells_records_umis_sparse), or the seven steps it replaces.  With ``gene_of`` or
+    ``umi_correct`` the one call is oem_em_run_cells_records_umis_rule_sparse, the join's fifth step ``dedup_umis_rule``,
+    and ``cell_corrected`` is a tenth value."""
+    with_rule = gene_of is not None or bool(umi_correct)
     blob, off = names
     bc_blob, bc_off = barcodes
     um_blob, um_off = umis
@@ -455,10 +520,16 @@ def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh,
         order_names, group_off, cell_group_off = collate_names(gather_names((blob, off), order_bc), cell_rec_off,
                                                                None if sec is None else sec[order_bc], mode=mode, device=device)
         order = order_bc[order_names]
-        dup, _, cell_dups = dedup_umis((um_blob, um_off), order, group_off, cell_group_off, flags=records["flags"], device=device)
+        cell_corrected = None
+        if with_rule:
+            dup, _, cell_dups, cell_corrected = dedup_umis_rule((um_blob, um_off), order, group_off, cell_group_off, flags=records["flags"],
+                                                                ref_id=records["ref_id"], gene_of=gene_of, correct=umi_correct,
+                                                                device=device)
+        else:
+            dup, _, cell_dups = dedup_umis((um_blob, um_off), order, group_off, cell_group_off, flags=records["flags"], device=device)
         order, group_off, cell_group_off, cell_rec_off = drop_groups(order, group_off, cell_group_off, dup)
         out = _em_cells_records_plain(F, txp_len, records[order], group_off, cell_group_off, coverage, max_iter, conv_thresh, device)
-        return (*out, order, cell_rec_off, cell_dups)
+        return (*out, order, cell_rec_off, cell_dups) + ((cell_corrected,) if with_rule else ())
     one = np.zeros(1, dtype=np.uint8)
     blob, bc_blob, um_blob = (b if len(b) else one for b in (blob, bc_blob, um_blob))
     model, bin_width, growth_rate = _coverage_args(coverage)
@@ -469,12 +540,17 @@ def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh,
     n_groups, n_cells, n_surv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     L = _lib.lib()
     res = C.c_void_p()
-    _lib.check(L.oem_em_run_cells_records_umis_sparse(
-        C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
-        bc_blob.ctypes.data if n else None, bc_off.ctypes.data, blob.ctypes.data if n else None, off.ctypes.data,
-        None if sec is None or not n else sec.ctypes.data, um_blob.ctypes.data, um_off.ctypes.data, _COLLATE_MODES[mode], bin_width, model,
-        growth_rate, device, max_iter, conv_thresh, order.ctypes.data, C.byref(n_surv), cell_rec_off.ctypes.data, C.byref(n_cells), None,
-        C.byref(n_groups), None, kept.ctypes.data, cell_dups.ctypes.data, C.byref(res)))
+    head = (C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
+            bc_blob.ctypes.data if n else None, bc_off.ctypes.data, blob.ctypes.data if n else None, off.ctypes.data,
+            None if sec is None or not n else sec.ctypes.data, um_blob.ctypes.data, um_off.ctypes.data, _COLLATE_MODES[mode], bin_width, model,
+            growth_rate, device, max_iter, conv_thresh, order.ctypes.data, C.byref(n_surv), cell_rec_off.ctypes.data, C.byref(n_cells), None,
+            C.byref(n_groups), None, kept.ctypes.data, cell_dups.ctypes.data)
+    if with_rule:
+        rule, _gene = _umi_rule(gene_of, umi_correct)
+        cell_corrected = np.zeros(max(n, 1), dtype=np.uint64)
+        _lib.check(L.oem_em_run_cells_records_umis_rule_sparse(C.addressof(rule), *head, cell_corrected.ctypes.data, C.byref(res)))
+    else:
+        _lib.check(L.oem_em_run_cells_records_umis_sparse(*head, C.byref(res)))
     nc = int(n_cells.value)
     try:
         tables = _discard_tables(L, res, nc)
@@ -482,11 +558,11 @@ def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh,
         L.oem_cells_result_destroy(res)
         raise
     return (*_take_cells_result(res, nc, L), kept[:int(n_groups.value)].copy(), tables, order[:int(n_surv.value)].copy(),
-            cell_rec_off[:nc + 1].copy(), cell_dups[:nc].copy())
+            cell_rec_off[:nc + 1].copy(), cell_dups[:nc].copy()) + ((cell_corrected[:nc].copy(),) if with_rule else ())
 
 
 def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes, collate, mode,
-                               umis=None):
+                               umis=None, gene_of=None, umi_correct=False):
     """``em_cells_records_sparse(..., names=, barcodes=)``: the one call (``collate="device"``), or the join it replaces."""
     from .types import pack_read_names
     records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
@@ -506,7 +582,7 @@ def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thr
         if _n_packed(umis) != n:
             raise ValueError("umis must have one entry per record")
         return _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, (blob, off), sec, (bc_blob, bc_off),
-                                      pack_read_names(umis, n), collate, mode)
+                                      pack_read_names(umis, n), collate, mode, gene_of, umi_correct)
     if collate == "host":   # the four steps the one call replaces
         order_bc, cell_rec_off = collate_barcodes((bc_blob, bc_off), device=device)
         out = _em_cells_records_names(F, txp_len, records[order_bc], cell_rec_off, coverage, max_iter, conv_thresh, device,
@@ -589,7 +665,7 @@ def _em_cells_records_names(F, txp_len, records, cell_rec_off, coverage, max_ite
 
 def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
                             conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None, collate: str = "host",
-                            mode: str = "sort", barcodes=None, umis=None):
+                            mode: str = "sort", barcodes=None, umis=None, gene_of=None, umi_correct: bool = False):
     """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
     oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
     model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
@@ -624,6 +700,13 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     NumPy gathers, ``collate_names``, the composed order, ``dedup_umis``, ``drop_groups``, the records call.  Both
     return the eight values of the barcodes form over the DEDUPLICATED collation -- ``order`` holds the surviving
     positions only -- and ``cell_dups``, the duplicates dropped from every cell, as a ninth.
+
+    ``gene_of`` (one gene id per transcript) and ``umi_correct`` (both go with ``umis``) are the UMI rule of
+    ``dedup_umis_rule``: molecules keyed by (cell, gene of the read's first record, UMI), and UMIs one mismatch away from
+    a more abundant UMI of the same cell and gene counted as errors of it.  With either, ``collate="device"`` is
+    oem_em_run_cells_records_umis_rule_sparse, ``collate="host"`` the same join with ``dedup_umis_rule``, and
+    ``cell_corrected``, the reads of every cell whose UMI was corrected, is a tenth value.  With both at their defaults
+    nothing changes.
     """
     from .builder import filters_c
     if collate not in ("host", "device"):
@@ -634,6 +717,8 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
         raise ValueError("secondary goes with names")
     if umis is not None and barcodes is None:
         raise ValueError("umis goes with barcodes: the molecules of a cell are found where the cells are")
+    if umis is None and (gene_of is not None or umi_correct):
+        raise ValueError("gene_of and umi_correct go with umis: they are the rule the UMIs are deduplicated by")
     if barcodes is not None:
         if cell_group_off is not None or group_off is not None:
             raise ValueError("with barcodes the cells are found by the call: group_off and cell_group_off must be None")
@@ -643,7 +728,7 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
     if barcodes is not None:
         return _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes,
-                                          collate, mode, umis)
+                                          collate, mode, umis, gene_of, umi_correct)
     if names is not None and collate == "device":
         return _em_cells_records_names(F, txp_len, records, cell_group_off, coverage, max_iter, conv_thresh, device, names,
                                        secondary, mode)

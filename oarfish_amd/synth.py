@@ -728,6 +728,66 @@ def interleave_cells(records, names, secondary, cell_rec_off, barcodes, seed: in
             None if secondary is None else np.asarray(secondary)[perm], gather_names((bc_blob, bc_off), cell_of), perm)
 
 
+def gene_of_txps(n_txps: int, seed: int = BASE_SEED + 31):
+    """A synthetic annotation for the UMI rule: one ``uint32`` gene id per transcript, genes of 1 + Geom(1/4) consecutive
+    transcripts (``_genes``, the gene model of the synthetic stores).  A pure function of its arguments."""
+    return _genes(int(n_txps), np.random.default_rng([seed, 0x6E4E]))[2].astype(np.uint32)
+
+
+def _mix64(x):
+    """splitmix64's finalizer over a ``uint64`` array."""
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _string_hashes(pair, n):
+    """A 64-bit hash of every string of a ``(blob, offsets)`` pair (polynomial in the bytes, then mixed)."""
+    blob, off = np.asarray(pair[0], dtype=np.uint8), np.ascontiguousarray(pair[1], dtype=np.int64)
+    if len(off) != n + 1:
+        raise ValueError("one entry per record is needed")
+    lens = np.diff(off)
+    h = np.zeros(n, dtype=np.uint64)
+    total = int(off[-1] - off[0])
+    if total:
+        pos = np.arange(total, dtype=np.int64) - np.repeat(off[:-1] - off[0], lens)
+        table = np.ones(int(lens.max()) + 1, dtype=np.uint64)
+        np.multiply.accumulate(np.full(len(table) - 1, 0x100000001B3, dtype=np.uint64), out=table[1:])
+        terms = (blob[int(off[0]):int(off[-1])].astype(np.uint64) + np.uint64(1)) * table[pos]
+        full = lens > 0
+        h[full] = np.add.reduceat(terms, (off[:-1] - off[0])[full])
+    return _mix64(h ^ lens.astype(np.uint64))
+
+
+def add_umi_errors(umis, rate: float, seed: int = BASE_SEED + 37, names=None, barcodes=None):
+    """Sequencing errors in the UMIs of an input (``add_umi_duplicates``' ``umis``): in a fraction ``rate`` of the READS one
+    nucleotide of the UMI is substituted by another of ``ACGT``, the same substitution on all records of the read.  A read
+    is the records that share a barcode and a name (``names`` / ``barcodes``: ``(blob, offsets)`` pairs, one entry per
+    record); without them every record is a read of its own.  A PCR copy has its own name, so a copy may carry an error
+    its original does not: what one-mismatch correction (``dedup_umis_rule(correct=True)``) undoes.  Which reads are hit,
+    where and by what depends on the seed, the read's barcode and name and -- without names -- the record's index only,
+    not on the order of the records.  Empty UMIs stay empty.  Returns the new ``(blob, offsets)`` pair."""
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError("rate must be in [0, 1]")
+    blob, off = np.array(umis[0], dtype=np.uint8), np.ascontiguousarray(umis[1], dtype=np.int64)
+    n = len(off) - 1
+    key = np.arange(n, dtype=np.uint64) if names is None else _string_hashes(names, n)
+    if barcodes is not None:
+        key = _mix64(key ^ (_string_hashes(barcodes, n) * np.uint64(0x9E3779B97F4A7C15)))
+    h = _mix64(key ^ _mix64(np.full(n, int(seed) & (2 ** 64 - 1), dtype=np.uint64)))
+    lens = np.diff(off)
+    hit = ((h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53 < rate) & (lens > 0)
+    idx = np.flatnonzero(hit)
+    h2 = _mix64(h[idx] + np.uint64(1))
+    at = off[idx] - off[0] + (h2 % lens[idx].astype(np.uint64)).astype(np.int64)
+    old = blob[at]
+    was = np.argmax(old[:, None] == _NUC[None, :], axis=1)               # (a byte outside ACGT counts as A's place)
+    new = _NUC[(was + 1 + ((h2 >> np.uint64(32)) % np.uint64(3)).astype(np.int64)) % 4]
+    new = np.where(new == old, _NUC[(was + 1) % 4], new)
+    blob[at] = new
+    return blob, np.ascontiguousarray(umis[1], dtype=np.uint64)
+
+
 def add_umi_duplicates(records, names, secondary, barcodes, rate: float, seed: int = BASE_SEED + 29, umi_len: int = 12):
     """An uncollated single-cell input (``interleave_cells``) given UMIs and PCR duplicates, the input of
     ``em_cells_records_sparse(..., barcodes=, names=, umis=)``.  ``names`` and ``barcodes`` are ``(blob, offsets)`` pairs,

@@ -56,6 +56,12 @@ worst:
 With the peak device memory of both, the arena's peak and its bytes per survivor, finish's share of the session's time and
 the lookups that missed.  No ratio is promised: the baseline is (b) in the same run.
 
+--umis-rule is the leg of the UMI rule (profiles/cells_records_umis_rule_bench.json): the --umis leg's input with
+synth.add_umi_errors(rate=0.05) and a synthetic gene_of, alternated in one process:
+  (a) the exact one call; (b) gene keys only; (c) gene keys plus one-mismatch correction; (d) correction without genes.
+Reported: (b) - (a) and (c) - (a), the peak device memory, the duplicates and corrected reads per leg, the longest walks of
+the neighbour search in both collations and the rounds of pointer jumping.
+
 --umis-stream is the leg of the UMI sessions (profiles/cells_umis_stream_bench.json): the --umis leg's input, alternated
 in one process, --runs repeats (five), best to worst, one pushing thread:
 
@@ -341,6 +347,83 @@ def umis_leg(args, cr, res, save):
         del rec, names, sec, bc, umis
 
 
+def umis_rule_leg(args, cr, res, save):
+    """The --umis-rule leg: the --umis leg's input with sequencing errors in the UMIs (synth.add_umi_errors(rate=0.05), per
+    read) and a synthetic annotation (synth.gene_of_txps).  Alternated in one process: (a) the exact one call
+    (oem_em_run_cells_records_umis_sparse); (b) gene keys only; (c) gene keys plus one-mismatch correction; (d) correction
+    without genes, where a segment is a whole cell.  Reported: (b) - (a) and (c) - (a), the peak device memory, the
+    duplicates and the corrected reads per leg, and -- from one more run of (c) and of (d) on the testing library, outside
+    the timings -- the classes, the longest neighbour walk in the first and in the halves-swapped collation and the rounds
+    of pointer jumping."""
+    import ctypes as C
+    from oarfish_amd import _lib
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    def head(pair, m):
+        return pair[0][:int(pair[1][m])], pair[1][:m + 1]
+
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        rec1, names1, sec1, bc1, _ = synth.interleave_cells(rec0, names0, sec0, cro, synth.make_barcodes(n, "10x"), how="uniform")
+        del rec0, names0, sec0
+        rec, names, sec, bc, umis, copies = synth.add_umi_duplicates(rec1, names1, sec1, bc1, rate=0.1)
+        del rec1, names1, sec1, bc1
+        umis = synth.add_umi_errors(umis, 0.05, names=names, barcodes=bc)
+        gene_of = synth.gene_of_txps(len(tl))
+        r = res[style] = dict(records=int(len(rec)), copied_reads=int(sum(copies.values())), umi_bytes=int(umis[0].nbytes),
+                              umi_error_rate=0.05, genes=int(gene_of[-1]) + 1)
+        legs = dict(a=dict(), b=dict(gene_of=gene_of), c=dict(gene_of=gene_of, umi_correct=True), d=dict(umi_correct=True))
+
+        def run(kw, upto=None):
+            if upto is None:
+                return oarfish_amd.em_cells_records_sparse(f, tl, rec, None, None, names=names, secondary=sec, barcodes=bc, umis=umis,
+                                                           collate="device", **kw)
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:upto], None, None, names=head(names, upto), secondary=sec[:upto],
+                                                       barcodes=head(bc, upto), umis=head(umis, upto), collate="device", **kw)
+
+        m = min(len(rec), int(cro[min(args.warm_cells, n)]))   # warm-up on the first records of the input
+        for kw in legs.values():
+            run(kw, m)
+        runs = {k: [] for k in legs}
+        for k in range(args.runs):
+            for leg, kw in legs.items():
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        dt, got = clock(lambda: run(kw))
+                    r[f"peak_device_bytes_{leg}"] = int(pk.peak)
+                    r[f"duplicates_{leg}"] = int(got[8].sum())
+                    r[f"corrected_reads_{leg}"] = int(got[9].sum()) if len(got) > 9 else 0
+                    r[f"reads_counted_{leg}"] = int(len(got[4]))
+                else:
+                    dt, got = clock(lambda: run(kw))
+                runs[leg].append(dt)
+                del got
+            print(f"[bench] {style} run {k}: " + ", ".join(f"({leg}) {runs[leg][-1]:.3f} s" for leg in legs), flush=True)
+            r["exact_one_call"], r["gene_keys"] = spread(runs["a"]), spread(runs["b"])
+            r["gene_keys_and_correction"], r["correction_without_genes"] = spread(runs["c"]), spread(runs["d"])
+            r["gene_keys_cost_s_b_minus_a"] = round(min(runs["b"]) - min(runs["a"]), 4)
+            r["gene_keys_and_correction_cost_s_c_minus_a"] = round(min(runs["c"]) - min(runs["a"]), 4)
+            r["correction_without_genes_cost_s_d_minus_a"] = round(min(runs["d"]) - min(runs["a"]), 4)
+            r["exact_one_call_own_spread_s"] = round(max(runs["a"]) - min(runs["a"]), 4)
+            save()
+        with _lib.testing() as L:   # what the correction met, from the testing library's counters; not timed
+            for leg in ("c", "d"):
+                run(legs[leg])
+                out = (C.c_double * 8)()
+                _lib.check(L.oem_debug_dedup_rule_last_call(out))
+                r[f"correction_{leg}"] = dict(participants=int(out[0]), classes=int(out[1]), classes_with_a_parent=int(out[2]),
+                                              pointer_jumping_rounds_max=int(out[3]), longest_walk_first_collation=int(out[4]),
+                                              longest_walk_swapped_collation=int(out[5]), groups_of_cells=int(out[6]))
+        save()
+        del rec, names, sec, bc, umis
+
+
 def barcodes_stream_leg(args, cr, res, save):
     """The --barcodes-stream leg (see the module docstring); fills res[style] for every name style."""
     n = args.cells
@@ -617,6 +700,8 @@ def main():
     ap.add_argument("--names", action="store_true", help="the leg from names and records in input order")
     ap.add_argument("--barcodes", action="store_true", help="the leg from records in any order: cells from barcodes")
     ap.add_argument("--umis", action="store_true", help="the leg of the one call with UMI deduplication against the barcodes call and the host join")
+    ap.add_argument("--umis-rule", action="store_true",
+                    help="the leg of the UMI rule: the exact one call against gene keys, gene keys plus correction, correction alone")
     ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
     ap.add_argument("--barcodes-any-order-stream", action="store_true",
                     help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
@@ -627,11 +712,12 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.umis or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream else 3
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "cells_umis_stream_bench.json" if args.umis_stream else
                                 "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
                                 "cells_barcodes_stream_bench.json" if args.barcodes_stream else
+                                "cells_records_umis_rule_bench.json" if args.umis_rule else
                                 "cells_records_umis_bench.json" if args.umis else
                                 "cells_records_barcodes_bench.json" if args.barcodes else
                                 "cells_records_names_bench.json" if args.names else "cells_records_bench.json")
@@ -706,6 +792,10 @@ def main():
         return
     if args.barcodes_stream:
         barcodes_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
+    if args.umis_rule:
+        umis_rule_leg(args, cr, res, save)
         print(json.dumps(res))
         return
     if args.umis:
