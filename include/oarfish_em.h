@@ -524,6 +524,26 @@ int oem_count_matrix_text(const uint64_t *cell_off, uint32_t n_cells,
                           const uint8_t *prefix, uint64_t prefix_len,
                           int device, oem_text_result **out);
 
+/* The cells x transcripts matrix collapsed to cells x genes on the device (no counterpart in the reference, which
+ * writes cells x transcripts only).  The input is the CSR that oem_em_run_cells_sparse and the sessions return
+ * (cell_off: n_cells + 1 offsets from 0, never decreasing; col / val: cell_off[n_cells] entries, every col below
+ * n_txps) and gene_of, one gene id below n_genes per transcript; gene_of need not be monotone and ids may be unused.
+ * The rule, which the device is held to exactly:
+ *   - for cell c and gene g the entries of cell c whose gene_of[col] is g are taken in CSR order, each converted to
+ *     f64 and added one after the other starting from 0.0; the sum is rounded once to f32 (nearest-even, denormals
+ *     kept);
+ *   - cell c has an entry for gene g iff it has at least one entry of that gene -- there is no test on the value;
+ *   - a cell's entries come in ascending gene id.
+ * The result is an ordinary oem_cells_result (oem_cells_result_dims / _copy / _destroy): cell_off of n_cells + 1
+ * entries, col the gene ids, val the sums, infos zero-filled; it is what oem_count_matrix_text takes, with n_genes in
+ * the place of n_txps.  oem_cells_result_discard_tables on it returns OEM_ERR_STATE.  No cell may have more than 2^30
+ * entries.  All argument errors are reported before any device use, and *out is NULL after any failure; without a
+ * device the call returns OEM_ERR_NO_DEVICE (there is no host fallback). */
+int oem_cells_gene_counts(const uint64_t *cell_off, uint32_t n_cells,
+                          const uint32_t *col, const float *val,
+                          const uint32_t *gene_of, uint32_t n_txps, uint32_t n_genes,
+                          int device, oem_cells_result **out);
+
 /* The `.quant` file of the bulk path (write_function.rs:104-120): `prefix` followed by one line per transcript,
  *     name '\t' len '\t' count '\n'
  * len in plain decimal, the f64 count as Rust's `{}` prints it: the shortest digits that read back as the same f64,
@@ -894,7 +914,7 @@ int oem_em_run_cells_records_umis_sparse(
  * rule == NULL or {NULL, 0, 0} gives oem_dedup_umis / oem_em_run_cells_records_umis_sparse exactly.
  * Limits, on purpose: the gene of a read that maps to several genes is its head's; one mismatch only, no indels; the
  * survivor is not chosen by read length or by what the filter keeps; deduplication still runs before the filter.  The
- * UMI sessions (oem_cells_stream_set_umis) keep the exact rule. */
+ * UMI sessions take the same rule through oem_cells_stream_set_umi_rule. */
 typedef struct {
     const uint32_t *gene_of; /* n_txps gene ids, or NULL: no gene in the key */
     uint32_t n_txps;
@@ -1042,6 +1062,8 @@ typedef struct {
 /* a UMI session (oem_cells_stream_set_umis); 0 on every other session */
 #define OEM_CELLS_STREAM_INFO_UMI_DUP_READS 10u       /* reads dropped as duplicates, in groups that have run */
 #define OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS 11u     /* their records */
+#define OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS 12u /* reads corrected under a rule with correct (oem_cells_stream_set_umi_rule),
+                                                         in groups that have run */
 
 /* Argument errors (n_txps = 0, opts or out NULL, coverage = 1 without txp_len, with bin_width = 0 or with a model
  * other than 0 / 1, a non-zero reserved word) are reported before any device is touched; without a device the call
@@ -1209,6 +1231,26 @@ int oem_cells_stream_push_barcodes_umis(oem_cells_stream *s, const oem_aln_recor
                                         const uint8_t *secondary /* or NULL */,
                                         const uint8_t *umis, const uint64_t *umi_off, uint64_t *out_ticket);
 int oem_cells_stream_umis_copy(const oem_cells_stream *s, uint64_t *out_cell_dups /* n_cells */);
+/* THE UMI RULE IN A UMI SESSION: oem_cells_stream_set_umi_rule gives a UMI session of either form the oem_umi_rule of
+ * oem_em_run_cells_records_umis_rule_sparse -- gene-aware keys (gene_of, one gene id per transcript) and one-mismatch
+ * correction (correct) -- in every group's deduplication.  It is called after oem_cells_stream_set_umis, before the first
+ * push, and once: anything else is OEM_ERR_STATE.  OEM_ERR_ARG: rule NULL; correct > 1; gene_of given with n_txps == 0
+ * or with an n_txps that is not the session's.  gene_of is copied.  {NULL, 0, 0} is accepted and is the exact rule: the
+ * session then gives what it gives without this call.  The genes come from the records' own ref_id words, at the heads
+ * of the reads that take part.  With S the survivors' indices, ascending:
+ *   - any-order form: finish gives exactly what oem_em_run_cells_records_umis_rule_sparse gives on the S-arrays under
+ *     the same rule (correction reaches every record of a barcode, wherever it was pushed);
+ *   - collated form: the join of oem_cells_stream_set_umis' description with oem_dedup_umis_rule (ref_id = the ref_ids
+ *     of records[S]) in place of oem_dedup_umis.  A barcode that comes back is a new cell: nothing is corrected across
+ *     the two.
+ * A bad ref_id: the any-order form rejects the record's batch as before.  In the collated form the rule may meet a head
+ * of a read that takes part before the filter does; the sticky error is the filter's own,
+ * "ticket <t>: record <i>: ref_id <x> is not below n_txps", with the session-global index.
+ * After a successful finish of a session whose rule has correct, oem_cells_stream_umi_rule_copy gives the reads corrected
+ * in every cell (n_cells entries, in cell order), as out_cell_corrected of the one call; otherwise OEM_ERR_STATE.
+ * OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS is their sum over the groups that have run. */
+int oem_cells_stream_set_umi_rule(oem_cells_stream *s, const oem_umi_rule *rule);
+int oem_cells_stream_umi_rule_copy(const oem_cells_stream *s, uint64_t *out_cell_corrected /* n_cells */);
 /* After a successful oem_cells_stream_finish of a barcoded session (otherwise OEM_ERR_STATE): the sizes of what
  * oem_cells_stream_barcodes_copy gives (each may be NULL) -- the cells, the survivors, the reads (record groups) of all
  * cells, the bytes of all labels, and the unmapped records that were skipped. */

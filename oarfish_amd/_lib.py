@@ -42,6 +42,7 @@ OEM_CELLS_STREAM_INFO_BARCODE_MISSES = 8
 OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS = 9
 OEM_CELLS_STREAM_INFO_UMI_DUP_READS = 10
 OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS = 11
+OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS = 12
 OEM_RECORDS_STREAM_INFO_BATCHES = 1
 OEM_RECORDS_STREAM_INFO_GROUPS = 2
 OEM_RECORDS_STREAM_INFO_RECORDS = 3
@@ -75,7 +76,7 @@ ABI_SYMBOLS = [
     "oem_builder_store_create", "oem_store_create_coverage", "oem_builder_store_create_coverage",
     "oem_m_step", "oem_em_run", "oem_run_history", "oem_aux_counts", "oem_assignment_probs",
     "oem_assignment_text", "oem_text_result_dims", "oem_text_result_copy", "oem_text_result_destroy",
-    "oem_assignment_text_lz4", "oem_text_result_info", "oem_count_matrix_text",
+    "oem_assignment_text_lz4", "oem_text_result_info", "oem_count_matrix_text", "oem_cells_gene_counts",
     "oem_quant_text", "oem_ambig_text",
     "oem_bootstrap_weights", "oem_bootstrap",
     "oem_em_run_cells", "oem_em_run_cells_sparse", "oem_cells_result_dims", "oem_cells_result_copy",
@@ -88,6 +89,7 @@ ABI_SYMBOLS = [
     "oem_cells_stream_set_barcodes", "oem_cells_stream_push_barcodes", "oem_cells_stream_barcodes_dims",
     "oem_cells_stream_barcodes_copy", "oem_cells_stream_set_barcodes_any_order",
     "oem_cells_stream_set_umis", "oem_cells_stream_push_barcodes_umis", "oem_cells_stream_umis_copy",
+    "oem_cells_stream_set_umi_rule", "oem_cells_stream_umi_rule_copy",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
     "oem_records_stream_destroy", "oem_records_stream_set_names", "oem_records_stream_push_names",
@@ -239,6 +241,7 @@ def _load(path: str) -> C.CDLL:
     L.oem_assignment_text_lz4.argtypes = [vp, vp, f64, vp, vp, vp, u64, C.POINTER(vp)]
     L.oem_text_result_info.argtypes = [vp, u32, C.POINTER(u64)]
     L.oem_count_matrix_text.argtypes = [vp, u32, vp, vp, u32, u32, vp, u64, i32, C.POINTER(vp)]
+    L.oem_cells_gene_counts.argtypes = [vp, u32, vp, vp, vp, u32, u32, i32, C.POINTER(vp)]
     L.oem_quant_text.argtypes = [vp, vp, vp, vp, u32, vp, u64, i32, C.POINTER(vp)]
     L.oem_ambig_text.argtypes = [vp, vp, u32, vp, u64, i32, C.POINTER(vp)]
     L.oem_bootstrap_weights.argtypes = [vp, u64, u32, vp]
@@ -279,6 +282,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_stream_set_umis.argtypes = [vp]
     L.oem_cells_stream_push_barcodes_umis.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.oem_cells_stream_umis_copy.argtypes = [vp, vp]
+    L.oem_cells_stream_set_umi_rule.argtypes = [vp, vp]
+    L.oem_cells_stream_umi_rule_copy.argtypes = [vp, vp]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
     L.oem_cells_stream_push.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]
     L.oem_cells_stream_finish.argtypes = [vp, C.POINTER(vp)]
@@ -358,6 +363,8 @@ def testing_lib() -> C.CDLL:
         L.oem_test_dedup_umis_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp]
         L.oem_test_dedup_umis_rule_host.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp, vp]
         L.oem_debug_dedup_rule_last_call.argtypes = [vp]
+        L.oem_test_cells_gene_counts_host.argtypes = [vp, u32, vp, vp, vp, u32, u32, C.POINTER(vp)]
+        L.oem_debug_gene_counts_last_call.argtypes = [vp]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]
         L.oem_debug_cells_records_last_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.oem_debug_records_stream_finish_csr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -150,4 +150,9 @@ struct oem_cells_result {
 namespace oem {
 // The cells' offsets from the groups' blocks, in group (= cell) order; the blocks move into the result.
 int cells_result_from_blocks(const char *who, std::vector<SparseBlock> &blocks, oem_cells_result *r);
+// oem_gene_counts.hip: the argument checks of oem_cells_gene_counts (everything but `out`), before any device use, and
+// its result from the batches' blocks (infos zero-filled, no discard tables).
+int gene_counts_check(const char *who, const uint64_t *cell_off, uint32_t n_cells, const uint32_t *col, const float *val,
+                      const uint32_t *gene_of, uint32_t n_txps, uint32_t n_genes);
+int gene_counts_result(const char *who, uint32_t n_cells, std::vector<SparseBlock> &blocks, oem_cells_result **out);
 } // namespace oem

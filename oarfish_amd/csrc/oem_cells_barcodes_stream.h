@@ -90,7 +90,13 @@ int barcodes_stream_push(BarcodesStream *b, const char *who, const oem_aln_recor
 // oem_cells_stream_set_umis behind its checks of the session: before any push, once (oem_collate.h, "UMIs in the sessions")
 int barcodes_stream_set_umis(BarcodesStream *b, const char *who);
 // the duplicates dropped by the groups that have run: reads, and their records (0 without UMIs)
-void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *dup_records);
+// ... and, under a rule with correct, the reads corrected
+void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *dup_records, uint64_t *corrected_reads);
+// oem_cells_stream_set_umi_rule behind its NULL-session check: after set_umis, before any push, once; gene_of is copied
+// and uploaded to the session's device (oem_collate.h, "The UMI rule")
+int barcodes_stream_set_umi_rule(BarcodesStream *b, const char *who, const oem_umi_rule *rule);
+// oem_cells_stream_umi_rule_copy: the reads corrected in every cell, after finish of a session whose rule has correct
+int barcodes_stream_umi_rule_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_corrected);
 // oem_cells_stream_umis_copy: the duplicates (reads) every cell lost, after finish
 int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_dups);
 bool barcodes_stream_push_in_flight(BarcodesStream *b);

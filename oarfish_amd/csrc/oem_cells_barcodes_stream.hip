@@ -228,6 +228,7 @@ struct Slot {
     // collation's, with the cells' first positions in it and the duplicates (reads) that every cell lost
     uint64_t n_positions = 0;
     std::vector<uint64_t> cell_pos_off, cell_dups;          // n_cells + 1; n_cells (a UMI session)
+    std::vector<uint64_t> cell_corrected;                   // n_cells (a UMI session under a rule with correct)
     bool done = false;
 };
 
@@ -284,6 +285,14 @@ struct BarcodesStream {
     bool with_umis = false;
     uint64_t dup_reads = 0, dup_records = 0;   // (mu) of the groups that have run
     std::vector<uint64_t> out_cell_dups;
+    // the UMI rule (oem_cells_stream_set_umi_rule; oem_collate.h, "The UMI rule"): set once before the first push; the
+    // group workers only read it.  gene_of is the session's copy, d_gene_of its upload to the session's device.
+    bool rule_set = false;
+    std::vector<uint32_t> gene_of;
+    DevBuf<uint32_t> d_gene_of;
+    uint32_t rule_correct = 0;
+    uint64_t corrected_reads = 0;              // (mu) of the groups that have run
+    std::vector<uint64_t> out_cell_corrected;
     uint64_t arena_peak = 0, info_misses = 0, info_slots = 0; // (mu) as of the last batch, for oem_cells_stream_info
 
     // -- what finish leaves ------------------------------------------------------------------------------------------------
@@ -767,6 +776,10 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
     double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     OEM_TRY(collate_resident(in, 0, n_cells, 0, 0, 0, info, &cr));
     tm.lap("barcodes: collate");
+    auto bad_ref = [&](uint64_t record, uint32_t ref_id) { // record: the session-global index
+        return fail(OEM_ERR_ARG, "%s: ticket %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)ticket_of(record),
+                    (unsigned long long)record, ref_id);
+    };
     uint64_t mp = m; // the positions of the group's order: fewer than its records once duplicates are dropped
     if (a->with_umis) { // the duplicates leave the collation here: their records are never gathered
         slot->cell_dups.assign(n_cells, 0);
@@ -775,8 +788,23 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
         um.who = who;
         um.d_umis = a->umis.p;
         um.d_umi_off = a->umi_off.p + r0;
+        if (d_gene_of.p) { // the rule's gene keys: the heads' ref_ids are word 0 of the arena's records
+            um.d_ref_id = reinterpret_cast<const uint32_t *>(a->rec.p + r0);
+            um.ref_id_stride = sizeof(oem_aln_record) / sizeof(uint32_t);
+            um.d_gene_of = d_gene_of.p;
+            um.n_txps = env.n_txps;
+            um.defer_bad_ref = true;
+        }
+        um.correct = rule_correct;
+        if (rule_correct) slot->cell_corrected.assign(n_cells, 0);
         UmiMarks mk;
-        OEM_TRY(dedup_mark(um, cr.order.p, nullptr, cr.group_off.p, cr.n_groups, cr.cell_group_off.p, n_cells, 0, &mk, slot->cell_dups.data()));
+        OEM_TRY(dedup_mark(um, cr.order.p, nullptr, cr.group_off.p, cr.n_groups, cr.cell_group_off.p, n_cells, 0, &mk, slot->cell_dups.data(),
+                           rule_correct ? slot->cell_corrected.data() : nullptr));
+        if (mk.bad_ref_record != kCollateNoRecord) { // a group-local record: the arena knows it by its session index
+            uint64_t record = 0;
+            OEM_HIP(hipMemcpy(&record, a->gidx.p + r0 + mk.bad_ref_record, sizeof record, hipMemcpyDeviceToHost));
+            return bad_ref(record, mk.bad_ref_id);
+        }
         if (mk.n_dups) {
             OEM_TRY(dedup_compact(mk, m, n_cells, &cr, &mp, slot->cell_pos_off.data()));
         } else {
@@ -786,6 +814,7 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
             std::lock_guard<std::mutex> lk(mu);
             dup_reads += mk.n_dups;
             dup_records += m - mp;
+            for (uint64_t v : slot->cell_corrected) corrected_reads += v;
         }
         tm.lap("barcodes: dedup");
     }
@@ -815,10 +844,6 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
     rg.out_tables = out->tables.data();
     rg.blk = &out->blk;
     rg.infos = out->infos.data();
-    auto bad_ref = [&](uint64_t record, uint32_t ref_id) {
-        return fail(OEM_ERR_ARG, "%s: ticket %llu: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)ticket_of(record),
-                    (unsigned long long)record, ref_id);
-    };
 
     FilterResult r;
     FilterCells fc;
@@ -991,11 +1016,50 @@ int barcodes_stream_set_umis(BarcodesStream *b, const char *who)
     return OEM_OK;
 }
 
-void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *dup_records)
+void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *dup_records, uint64_t *corrected_reads)
 {
     std::lock_guard<std::mutex> lk(b->mu);
     *dup_reads = b->dup_reads;
     *dup_records = b->dup_records;
+    *corrected_reads = b->corrected_reads;
+}
+
+int barcodes_stream_set_umi_rule(BarcodesStream *b, const char *who, const oem_umi_rule *rule)
+{
+    if (!rule) return fail(OEM_ERR_ARG, "%s: rule is NULL", who);
+    if (rule->correct > 1) return fail(OEM_ERR_ARG, "%s: rule->correct = %u is neither 0 nor 1", who, rule->correct);
+    if (rule->gene_of && !rule->n_txps) return fail(OEM_ERR_ARG, "%s: rule->gene_of is given and rule->n_txps is 0", who);
+    if (rule->gene_of && rule->n_txps != b->env.n_txps)
+        return fail(OEM_ERR_ARG, "%s: rule->n_txps = %u is not the session's n_txps = %u", who, rule->n_txps, b->env.n_txps);
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (b->closed || b->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (!b->with_umis) return fail(OEM_ERR_STATE, "%s: not a UMI session (oem_cells_stream_set_umis)", who);
+    if (b->rule_set) return fail(OEM_ERR_STATE, "%s: the session has a UMI rule already", who);
+    if (b->q.next_ticket || b->q.pushing) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    if (rule->gene_of) { // the session's copy, and its upload: the group workers only read it
+        std::vector<uint32_t> copy(rule->gene_of, rule->gene_of + rule->n_txps);
+        OEM_HIP(hipSetDevice(b->env.device));
+        OEM_TRY(dev_alloc(&b->d_gene_of.p, copy.size(), nullptr));
+        const hipError_t e = hipMemcpy(b->d_gene_of.p, copy.data(), sizeof(uint32_t) * copy.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            b->d_gene_of.reset();
+            return fail(OEM_ERR_HIP, "%s: the upload of gene_of failed: %s", who, hipGetErrorString(e));
+        }
+        b->gene_of = std::move(copy);
+    }
+    b->rule_correct = rule->correct;
+    b->rule_set = true;
+    return OEM_OK;
+}
+
+int barcodes_stream_umi_rule_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_corrected)
+{
+    if (!b->with_umis || !b->rule_correct) return fail(OEM_ERR_STATE, "%s: not a UMI session under a rule with correct (oem_cells_stream_set_umi_rule)", who);
+    if (!b->assembled) return fail(OEM_ERR_STATE, "%s: after a successful oem_cells_stream_finish", who);
+    if (!out_cell_corrected) return fail(OEM_ERR_ARG, "%s: out_cell_corrected is NULL", who);
+    if (!b->out_cell_corrected.empty())
+        std::memcpy(out_cell_corrected, b->out_cell_corrected.data(), sizeof(uint64_t) * b->out_cell_corrected.size());
+    return OEM_OK;
 }
 
 int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_dups)
@@ -1068,6 +1132,7 @@ int barcodes_stream_assemble(BarcodesStream *b, const char *who)
         b->out_order.insert(b->out_order.end(), sl->order.begin(), sl->order.end());
         b->out_kept.insert(b->out_kept.end(), sl->kept.begin(), sl->kept.end());
         b->out_cell_dups.insert(b->out_cell_dups.end(), sl->cell_dups.begin(), sl->cell_dups.end());
+        b->out_cell_corrected.insert(b->out_cell_corrected.end(), sl->cell_corrected.begin(), sl->cell_corrected.end());
         rec_base += sl->n_positions; // (a UMI session: every later group's place depends on what the earlier ones lost)
         group_base += sl->n_groups;
         sl.reset();

@@ -759,6 +759,30 @@ extern "C" int oem_cells_stream_umis_copy(const oem_cells_stream *s, uint64_t *o
     return barcodes_stream_umis_copy(s->bc, who, out_cell_dups);
 }
 
+// The UMI rule of a UMI session (oem_collate.h, "The UMI rule"): gene-aware keys and one-mismatch correction in every
+// group's dedup_mark, as oem_em_run_cells_records_umis_rule_sparse has them.
+extern "C" int oem_cells_stream_set_umi_rule(oem_cells_stream *s, const oem_umi_rule *rule)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_set_umi_rule";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+        if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a UMI session (oem_cells_stream_set_umis)", who);
+    }
+    return barcodes_stream_set_umi_rule(s->bc, who, rule);
+    OEM_API_END("oem_cells_stream_set_umi_rule")
+}
+
+extern "C" int oem_cells_stream_umi_rule_copy(const oem_cells_stream *s, uint64_t *out_cell_corrected)
+{
+    const char *who = "oem_cells_stream_umi_rule_copy";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a UMI session under a rule with correct (oem_cells_stream_set_umi_rule)", who);
+    return barcodes_stream_umi_rule_copy(s->bc, who, out_cell_corrected);
+}
+
 extern "C" int oem_cells_stream_barcodes_dims(const oem_cells_stream *s, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
                                               uint64_t *barcode_bytes, uint64_t *n_unmapped)
 {
@@ -838,9 +862,10 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
     uint64_t bc_batches = 0, bc_records = 0, bc_blocked_us = 0, bc_arena = 0, bc_misses = 0, bc_slots = 0;
     if (s->bc) barcodes_stream_counts(s->bc, &bc_batches, &bc_records, &bc_blocked_us);
     if (s->bc) barcodes_stream_table_info(s->bc, &bc_arena, &bc_misses, &bc_slots);
-    uint64_t dup_reads = 0, dup_records = 0;
-    if (s->bc) barcodes_stream_umi_info(s->bc, &dup_reads, &dup_records);
+    uint64_t dup_reads = 0, dup_records = 0, corrected_reads = 0;
+    if (s->bc) barcodes_stream_umi_info(s->bc, &dup_reads, &dup_records, &corrected_reads);
     switch (key) {
+    case OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS: *value = corrected_reads; break; // (under a rule with correct; 0 otherwise)
     case OEM_CELLS_STREAM_INFO_UMI_DUP_READS: *value = dup_reads; break; // (a UMI session; 0 otherwise)
     case OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS: *value = dup_records; break;
     case OEM_CELLS_STREAM_INFO_ARENA_BYTES: *value = bc_arena; break; // (an any-order barcoded session; 0 otherwise)

@@ -112,6 +112,9 @@ struct UmiInput {
     const uint32_t *d_gene_of = nullptr; // n_txps gene ids, or NULL: no gene in the key
     uint32_t n_txps = 0;
     uint32_t correct = 0;                // 1: one-mismatch correction
+    // A caller that knows the records' origin (a session's group) words the error of a bad ref_id itself: dedup_mark then
+    // returns OEM_OK with UmiMarks::bad_ref_record set and nothing else filled, as filter_device_resident does.
+    bool defer_bad_ref = false;
 };
 // What dedup_mark leaves on the device for a batch of ng groups.
 struct UmiMarks {
@@ -123,6 +126,10 @@ struct UmiMarks {
     // under a rule with correct: the classes that have a parent, the rounds of pointer jumping, and the longest walk of
     // a class over its half-sharing neighbours in the first and in the second (halves swapped) collation
     uint64_t n_corrected_classes = 0, jump_rounds = 0, walk_max[2] = {0, 0};
+    // with UmiInput::defer_bad_ref: the smallest input index of the batch that heads a group that takes part and whose
+    // ref_id is not below n_txps, and that ref_id (kCollateNoRecord: none)
+    uint64_t bad_ref_record = kCollateNoRecord;
+    uint32_t bad_ref_id = 0;
 };
 // The UMIs (checked: umi_off from 0, non-decreasing) up through the upload lanes, validated behind their chunks: a 0 byte
 // is OEM_ERR_ARG naming the smallest such input index, an empty UMI is legal.

@@ -541,6 +541,7 @@ int dedup_mark(const UmiInput &in, const uint32_t *d_order, const uint32_t *d_or
     if (cell_corrected) std::fill(cell_corrected, cell_corrected + nc, 0ull);
     out->n_part = out->n_classes = out->n_dups = 0;
     out->n_corrected_classes = out->jump_rounds = out->walk_max[0] = out->walk_max[1] = 0;
+    out->bad_ref_record = kCollateNoRecord;
     if (!ng) return OEM_OK;
     const bool genes = in.d_gene_of != nullptr, correct = in.correct != 0;
     const uint32_t gp = genes ? kGenePrefix : 0u;
@@ -572,6 +573,11 @@ int dedup_mark(const UmiInput &in, const uint32_t *d_order, const uint32_t *d_or
         if (bad != kNoRecord) {
             uint32_t t = 0;
             OEM_HIP(hipMemcpy(&t, in.d_ref_id + bad * in.ref_id_stride, sizeof t, hipMemcpyDeviceToHost));
+            if (in.defer_bad_ref) {
+                out->bad_ref_record = bad;
+                out->bad_ref_id = t;
+                return OEM_OK;
+            }
             return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps = %u (the head of a read that takes part in the UMI rule)",
                         in.who, bad, t, in.n_txps);
         }

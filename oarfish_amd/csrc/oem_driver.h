@@ -294,6 +294,10 @@ void text_last_timing(float *ms3);
 void text_lz4_last_timing(float *ms2);
 // oem_count_matrix_text.hip: the same three of this thread's last oem_count_matrix_text under OEM_MTX_TIMING=1
 void mtx_last_timing(float *ms3);
+// oem_gene_counts.hip: this thread's last oem_cells_gene_counts: ms of the uploads with the key kernels behind them and
+// of the read-back by the host clock (both are synchronous), under OEM_GENE_TIMING=1 (test-only library) ms of the sort
+// and of the kernels and the scan behind it from HIP events, then the device bytes it held and its batches
+void gene_counts_last_call(double *out6);
 // oem_quant_text.hip: this thread's last oem_quant_text / oem_ambig_text: its chunks, the workgroup tiles that went
 // through the LDS stage and those written directly, then ms of measure, scan and emit under OEM_QUANT_TIMING=1
 void quant_last_call(double *out6);

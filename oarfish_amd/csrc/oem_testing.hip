@@ -13,6 +13,7 @@
 #include "oem_cells_barcodes_stream.h"
 #include "oem_collate.h"
 #include "oem_collate_device.h"
+#include "oem_gene_counts.h"
 #include "oem_shortest_f64.h"
 
 using namespace oem;
@@ -279,6 +280,30 @@ extern "C" int oem_test_dedup_umis_rule_host(const oem_umi_rule *rule, const uin
                     (unsigned long long)bad, ref_id[bad], rule->n_txps);
     return OEM_OK;
     OEM_API_END("oem_test_dedup_umis_rule_host")
+}
+
+// Test hook: the host walk of oem_gene_counts.h (gene_counts_host) with oem_cells_gene_counts' arguments minus the device,
+// checked and worded as the device call, and its kind of result.
+extern "C" int oem_test_cells_gene_counts_host(const uint64_t *cell_off, uint32_t n_cells, const uint32_t *col, const float *val,
+                                               const uint32_t *gene_of, uint32_t n_txps, uint32_t n_genes, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_test_cells_gene_counts_host";
+    if (out) *out = nullptr;
+    if (!out) return fail(OEM_ERR_ARG, "%s: out is NULL", who);
+    OEM_TRY(gene_counts_check(who, cell_off, n_cells, col, val, gene_of, n_txps, n_genes));
+    std::vector<SparseBlock> blocks(1);
+    gene_counts_host(cell_off, n_cells, col, val, gene_of, &blocks[0].counts, &blocks[0].col, &blocks[0].val);
+    return gene_counts_result(who, n_cells, blocks, out);
+    OEM_API_END("oem_test_cells_gene_counts_host")
+}
+
+// out[0..5] = this thread's last oem_cells_gene_counts (oem_driver.h, gene_counts_last_call)
+extern "C" int oem_debug_gene_counts_last_call(double *out)
+{
+    if (!out) return fail(OEM_ERR_ARG, "oem_debug_gene_counts_last_call: NULL argument");
+    gene_counts_last_call(out);
+    return OEM_OK;
 }
 
 // out[0..7] = what the corrections of the last oem_dedup_umis_rule / oem_em_run_cells_records_umis_rule_sparse found

@@ -211,6 +211,42 @@ def count_matrix_text(indptr, cols, vals, n_txps: int, row_base: int = 0, prefix
     return take_text_result(L, h, offsets)
 
 
+def cells_gene_counts(indptr, cols, vals, gene_of, n_genes: Optional[int] = None, device: int = 0):
+    """The cells x transcripts CSR collapsed to cells x genes on the device (oem_cells_gene_counts; the rule is
+    csrc/oem_gene_counts.h's).  ``indptr, cols, vals`` is the CSR ``em_cells_sparse`` and ``CellsStream.finish`` return,
+    ``gene_of`` one gene id per transcript (``len(gene_of)`` is n_txps), ``n_genes=None`` means ``max(gene_of) + 1``.
+    Per cell and gene the entries are added in CSR order in f64 and rounded once to f32; a gene entry exists wherever
+    the cell has an entry of that gene; a cell's genes ascend.
+
+    Returns ``(indptr_g u64[n_cells + 1], genes u32, vals_g f32)`` -- what ``count_matrix_text`` takes with ``n_genes``
+    columns."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    vals = np.ascontiguousarray(vals, dtype=np.float32)
+    gene_of = np.asarray(gene_of)
+    if gene_of.ndim != 1:
+        raise ValueError("gene_of must be one gene id per transcript")
+    if len(gene_of) and (not np.issubdtype(gene_of.dtype, np.integer) or int(gene_of.min()) < 0 or int(gene_of.max()) > 0xffffffff):
+        raise ValueError("gene_of must hold integers in [0, 2^32)")
+    gene_of = np.ascontiguousarray(gene_of, dtype=np.uint32)
+    if len(indptr) < 1:
+        raise ValueError("indptr needs n_cells + 1 offsets")
+    n_cells = len(indptr) - 1
+    if len(cols) != len(vals) or int(indptr[-1]) != len(cols):
+        raise ValueError("cols and vals must hold indptr[-1] entries each")
+    if n_genes is None:
+        n_genes = int(gene_of.max()) + 1 if len(gene_of) else 0
+    if not 0 <= int(n_genes) <= 0xffffffff:
+        raise ValueError("n_genes must be in [0, 2^32)")
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_cells_gene_counts(indptr.ctypes.data, n_cells, cols.ctypes.data if len(cols) else None,
+                                       vals.ctypes.data if len(vals) else None,
+                                       gene_of.ctypes.data if len(gene_of) else None, len(gene_of), int(n_genes), device,
+                                       C.byref(res)))
+    return _take_cells_result(res, n_cells, L)[:3]
+
+
 _COVERAGE_MODELS = {"logistic": 0, "binomial": 1}
 
 
@@ -803,13 +839,24 @@ class CellsStream:
     (``dedup_umis``' rule), ``cells()`` describes the deduplicated collation and gains ``cell_dups``, and ``info()`` has
     ``umi_dup_reads`` and ``umi_dup_records`` (0 on every other session).  The any-order form gives exactly what
     ``em_cells_records_sparse(..., barcodes=, names=, umis=)`` gives on the surviving records.
+
+    ``gene_of`` (one gene id per transcript) and ``umi_correct`` (both go with ``umis=True``) are the UMI rule of
+    ``dedup_umis_rule`` in every group of the session (``oem_cells_stream_set_umi_rule``): molecules keyed by (cell, gene
+    of the read's first record, UMI), and UMIs one mismatch away from a more abundant one corrected to it.  With
+    ``umi_correct``, ``cells()`` gains ``cell_corrected`` and ``info()["umi_corrected_reads"]`` counts them.  The any-order
+    form gives exactly what ``em_cells_records_sparse(..., umis=, gene_of=, umi_correct=)`` gives on the surviving records.
     """
 
     def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
                  group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None,
-                 barcodes: bool = False, mode: str = "sort", collated: bool = True, umis: bool = False):
+                 barcodes: bool = False, mode: str = "sort", collated: bool = True, umis: bool = False, gene_of=None,
+                 umi_correct: bool = False):
         if umis and not barcodes:
             raise ValueError("umis=True goes with barcodes=True: only a barcoded session takes UMIs")
+        if (gene_of is not None or umi_correct) and not umis:
+            raise ValueError("gene_of and umi_correct go with umis=True: they are the rule the UMIs are deduplicated by")
+        if gene_of is not None and (np.ndim(gene_of) != 1 or len(gene_of) != n_txps):
+            raise ValueError("gene_of must have n_txps entries: one gene id per transcript")
         if not collated and not barcodes:
             raise ValueError("collated=False goes with barcodes=True: only a barcoded session finds its cells itself")
         if barcodes and filters is None:
@@ -827,6 +874,7 @@ class CellsStream:
         self._barcoded = bool(barcodes)
         self._any_order = bool(barcodes) and not collated
         self._umis = bool(umis)
+        self._umi_correct = bool(umi_correct)
         self._device = device
         records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
@@ -861,6 +909,9 @@ class CellsStream:
                     self._check(set_barcodes(self._h, _COLLATE_MODES[mode]))
                     if umis:
                         self._check(self._L.oem_cells_stream_set_umis(self._h))
+                    if gene_of is not None or umi_correct:
+                        rule, _gene = _umi_rule(gene_of, umi_correct)   # (the session copies gene_of)
+                        self._check(self._L.oem_cells_stream_set_umi_rule(self._h, C.addressof(rule)))
             except BaseException:
                 self.close()
                 raise
@@ -997,7 +1048,8 @@ class CellsStream:
         ``cell_rec_off`` (positions among the surviving records), ``order`` (uint64: the index in the pushed stream of the
         record at every collated position), ``group_off``, ``cell_group_off``, ``kept`` and ``n_unmapped``.  A UMI
         session: all of them describe the deduplicated collation, and ``cell_dups`` (uint64) are the duplicate reads that
-        every cell lost."""
+        every cell lost; with ``umi_correct`` also ``cell_corrected`` (uint64), the reads of every cell whose UMI was
+        corrected."""
         if self._cells is None:
             raise _lib.OemError(_lib.OEM_ERR_STATE, "cells(): a finished barcoded session has them")
         return self._cells
@@ -1023,6 +1075,10 @@ class CellsStream:
             dups = np.zeros(max(nc, 1), dtype=np.uint64)
             self._check(self._L.oem_cells_stream_umis_copy(self._h, dups.ctypes.data))
             out["cell_dups"] = dups[:nc]
+        if self._umi_correct:
+            corrected = np.zeros(max(nc, 1), dtype=np.uint64)
+            self._check(self._L.oem_cells_stream_umi_rule_copy(self._h, corrected.ctypes.data))
+            out["cell_corrected"] = corrected[:nc]
         return out
 
     def finish(self):
@@ -1060,7 +1116,8 @@ class CellsStream:
                     blocked_s=_lib.OEM_CELLS_STREAM_INFO_BLOCKED_US, groups_batched=_lib.OEM_CELLS_STREAM_INFO_GROUPS_BATCHED,
                     arena_bytes=_lib.OEM_CELLS_STREAM_INFO_ARENA_BYTES, barcode_misses=_lib.OEM_CELLS_STREAM_INFO_BARCODE_MISSES,
                     barcode_table_slots=_lib.OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS,
-                    umi_dup_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_READS, umi_dup_records=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS)
+                    umi_dup_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_READS, umi_dup_records=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS,
+                    umi_corrected_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS)
         out = {}
         for name, key in keys.items():
             v = C.c_uint64(0)

@@ -34,6 +34,10 @@ class SingleCellArgs:
     max_staged_records: int = 0
     collated: bool = True                  # False: the batches' records come in any order (the any-order barcoded session)
     umis: bool = False                     # True: the batches carry a UMI per record and every cell is deduplicated
+    gene_of: Optional[Sequence[int]] = None     # one gene id per transcript: with umis the molecules' keys, with gene_counts the collapse
+    gene_names: Optional[Sequence[str]] = None  # one name per gene id, for `.gene_features.txt`
+    umi_correct: bool = False              # with umis: UMIs one mismatch from a more abundant one are corrected to it
+    gene_counts: bool = False              # True: `.gene_count.mtx` and `.gene_features.txt` beside `.count.mtx`
     extra_info: dict = field(default_factory=dict)
 
 
@@ -48,15 +52,39 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
 
     With ``args.umis`` the batches are 5-tuples ``(records, barcodes, names, secondary, umis)`` (the cutters' tuples under
     ``umis=``), the session deduplicates every cell on the device, ``cells`` carries ``cell_dups`` and `.meta_info.json`
-    gains ``umi_dedup`` and ``umi_duplicate_reads``."""
+    gains ``umi_dedup`` and ``umi_duplicate_reads``.
+
+    ``args.gene_of`` means one thing end to end.  With ``args.umis`` it goes to the session with ``args.umi_correct`` (the
+    UMI rule of ``CellsStream``): `.meta_info.json` gains ``umi_gene_keys`` and ``umi_correct`` and, with correction,
+    ``umi_corrected_reads``; ``cells`` carries ``cell_corrected``.  With ``args.gene_counts`` the session's matrix is
+    collapsed to cells x genes on the device (``em.cells_gene_counts``) and written as `.gene_count.mtx` with
+    `.gene_features.txt` (``writers.write_single_cell_gene_output_device``); ``args.gene_names`` names the genes,
+    `.meta_info.json` gains ``gene_counts`` and ``n_genes``, and ``cells`` gains ``gene_counts = (indptr_g, genes,
+    vals_g)``."""
     txp_len = np.asarray(txp_lens, dtype=np.uint64)
+    gene_of = None if args.gene_of is None else np.asarray(args.gene_of)
+    if gene_of is not None and (gene_of.ndim != 1 or len(gene_of) != len(txp_len)):
+        raise ValueError("gene_of must hold one gene id per transcript")
+    if args.umi_correct and not args.umis:
+        raise ValueError("umi_correct goes with umis: it is part of the rule the UMIs are deduplicated by")
+    if gene_of is not None and not (args.umis or args.gene_counts):
+        raise ValueError("gene_of goes with umis (the molecules' keys) or gene_counts (the collapse)")
+    if args.gene_counts:
+        if gene_of is None or args.gene_names is None:
+            raise ValueError("gene_counts needs gene_of and gene_names")
+        if not len(gene_of) or int(gene_of.min()) < 0:
+            raise ValueError("gene_of must hold gene ids from 0")
+        n_genes = int(gene_of.max()) + 1
+        if len(args.gene_names) != n_genes:
+            raise ValueError(f"gene_names must name the {n_genes} genes of gene_of, not {len(args.gene_names)}")
+    rule = dict(gene_of=gene_of, umi_correct=args.umi_correct) if args.umis else {}
     coverage = None
     if args.model_coverage is not None:
         coverage = dict(model=args.model_coverage, bin_width=args.bin_width, growth_rate=args.growth_rate, txp_len=txp_len)
     with CellsStream(len(txp_len), max_iter=args.max_em_iter, conv_thresh=args.convergence_thresh, coverage=coverage,
                      device=args.device, group_nnz=args.group_nnz, group_cells=args.group_cells,
                      max_staged_nnz=args.max_staged_records, filters=filters, txp_len=txp_len, barcodes=True,
-                     mode=args.mode, collated=args.collated, umis=args.umis) as cs:
+                     mode=args.mode, collated=args.collated, umis=args.umis, **rule) as cs:
         if args.umis:
             for records, barcodes, names, secondary, umis in batches:
                 cs.push_batch(records, barcodes, names, secondary, umis)
@@ -71,8 +99,21 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
     if args.umis:
         info["umi_dedup"] = True
         info["umi_duplicate_reads"] = int(cells["cell_dups"].sum())
+        if gene_of is not None or args.umi_correct:
+            info["umi_gene_keys"] = gene_of is not None
+            info["umi_correct"] = bool(args.umi_correct)
+        if args.umi_correct:
+            info["umi_corrected_reads"] = int(cells["cell_corrected"].sum())
+    if args.gene_counts:
+        info["gene_counts"] = True
+        info["n_genes"] = n_genes
     info.update(args.extra_info)
     labels = [b.decode("latin-1") for b in cells["barcodes"]]
     writers.write_single_cell_output_device(args.output, info, txps_name, labels, len(labels), indptr, cols, vals,
                                             device=args.device)
+    if args.gene_counts:
+        from .em import cells_gene_counts
+        indptr_g, genes, vals_g = cells_gene_counts(indptr, cols, vals, gene_of, n_genes=n_genes, device=args.device)
+        writers.write_single_cell_gene_output_device(args.output, args.gene_names, len(labels), indptr_g, genes, vals_g, device=args.device)
+        cells["gene_counts"] = (indptr_g, genes, vals_g)
     return indptr, cols, vals, infos, cells

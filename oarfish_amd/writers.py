@@ -348,3 +348,23 @@ def write_single_cell_output_device(output: str, info: dict, feature_names: Sequ
     body = count_matrix_text(indptr, cols, vals, len(feature_names), prefix=prefix, device=device, offsets=False)
     with open(with_additional_extension(output, ".count.mtx"), "wb") as fh:
         fh.write(body.text)
+
+
+def write_single_cell_gene_output_device(output: str, gene_names: Sequence[str], n_cells: int, indptr_g, genes, vals_g,
+                                         device: int = 0) -> None:
+    """The gene-level matrix beside `.count.mtx`, from the CSR ``em.cells_gene_counts`` returns: `.gene_count.mtx`
+    (cells x genes, the text of ``em.count_matrix_text`` with the banner and the dimension line as its prefix: the
+    format of `.count.mtx`, formatted by the same kernel) and `.gene_features.txt`, one gene name per line in gene-id
+    order."""
+    from .em import count_matrix_text
+
+    if len(indptr_g) != int(n_cells) + 1:
+        raise ValueError("indptr_g must hold n_cells + 1 offsets")
+    _make_parent(output)
+    prefix = (_MTX_BANNER + f"{int(n_cells)} {len(gene_names)} {len(vals_g)}\n").encode()
+    body = count_matrix_text(indptr_g, genes, vals_g, len(gene_names), prefix=prefix, device=device, offsets=False)
+    with open(with_additional_extension(output, ".gene_count.mtx"), "wb") as fh:
+        fh.write(body.text)
+    with open(with_additional_extension(output, ".gene_features.txt"), "w") as fh:
+        for n in gene_names:
+            fh.write(f"{n}\n")

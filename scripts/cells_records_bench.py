@@ -71,6 +71,12 @@ in one process, --runs repeats (five), best to worst, one pushing thread:
   (c) the same sessions without UMIs, which count the duplicates as molecules.
 
 With the peak device memory of each, arena_bytes, the duplicates dropped and (a) - (c).
+
+--umis-rule-stream is the leg of the UMI rule in the sessions (profiles/cells_umis_rule_stream_bench.json): the
+--umis-stream leg's input with synth.add_umi_errors(rate=0.05) and a synthetic gene_of, alternated in one process at the
+first --batch-records, one pushing thread: both session forms under (a) the exact rule, (b) gene keys, (c) gene keys plus
+one-mismatch correction, and the rule one call on the concatenation under (c) beside them.  Reported per form: best to
+worst, (b) - (a) and (c) - (a), the duplicates, the corrected reads and the peak device memory.
 """
 import argparse
 import ctypes as C
@@ -689,6 +695,101 @@ def umis_stream_leg(args, cr, res, save):
         del rec, names, sec, bc, umis, inputs
 
 
+def umis_rule_stream_leg(args, cr, res, save):
+    """The --umis-rule-stream leg: the --umis-stream leg's input with sequencing errors in the UMIs
+    (synth.add_umi_errors(rate=0.05)) and a synthetic annotation (synth.gene_of_txps).  Alternated in one process, from one
+    pushing thread, at the first --batch-records: both session forms under (a) the exact rule, (b) gene keys, (c) gene keys
+    plus correction, and the rule one call on the concatenation under (c) beside them.  Reported per form: best - worst of
+    each, (b) - (a) and (c) - (a), the duplicates and the corrected reads, and peak device memory of the first run."""
+    from oarfish_amd.em import gather_names
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+    batch = args.batch_records[0]
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        rec1, names1, sec1, bc1, _ = synth.interleave_cells(rec0, names0, sec0, cro, synth.make_barcodes(n, "10x"), how="uniform")
+        del rec0, names0, sec0
+        rec, names, sec, bc, umis, copies = synth.add_umi_duplicates(rec1, names1, sec1, bc1, rate=0.1)
+        del rec1, names1, sec1, bc1
+        umis = synth.add_umi_errors(umis, 0.05, names=names, barcodes=bc)
+        gene_of = synth.gene_of_txps(len(tl))
+        m = len(rec)
+        r = res[style] = dict(records=int(m), copied_reads=int(sum(copies.values())), umi_bytes=int(umis[0].nbytes), umi_error_rate=0.05,
+                              genes=int(gene_of[-1]) + 1, batch_records=int(batch))
+        order_bc, _ = oarfish_amd.collate_barcodes(bc)
+        inputs = {"any_order": (rec, names, sec, bc, umis),
+                  "collated": (rec[order_bc], gather_names(names, order_bc), sec[order_bc], gather_names(bc, order_bc),
+                               gather_names(umis, order_bc))}
+        del order_bc
+        rules = dict(a=dict(), b=dict(gene_of=gene_of), c=dict(gene_of=gene_of, umi_correct=True))
+
+        def session(form, rule, upto=m):
+            rc, (nb, no), sc, (bb, bo), (ub, uo) = inputs[form]
+            no, bo, uo = (np.asarray(o, dtype=np.uint64) for o in (no, bo, uo))
+            info = {}
+
+            def go():
+                with oarfish_amd.CellsStream(len(tl), filters=f, txp_len=tl, barcodes=True, collated=form == "collated", umis=True,
+                                             **rules[rule]) as cs:
+                    for a in range(0, upto, batch):
+                        b = min(a + batch, upto)
+                        cs.push_batch(rc[a:b], (bb[int(bo[a]):int(bo[b])], bo[a:b + 1] - bo[a]), (nb[int(no[a]):int(no[b])], no[a:b + 1] - no[a]),
+                                      sc[a:b], umis=(ub[int(uo[a]):int(uo[b])], uo[a:b + 1] - uo[a]))
+                    out = cs.finish()
+                    info.update(cs.info(), n_cells=len(cs.cells()["barcodes"]))
+                return out
+            dt, out = clock(go)
+            return dt, out, info
+
+        def one_call(upto=m):
+            (nb, no), (bb, bo), (ub, uo) = names, bc, umis
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:upto], None, None, names=(nb[:int(no[upto])], no[:upto + 1]),
+                                                       secondary=sec[:upto], barcodes=(bb[:int(bo[upto])], bo[:upto + 1]),
+                                                       umis=(ub[:int(uo[upto])], uo[:upto + 1]), collate="device", **rules["c"])
+
+        warm = min(m, int(cro[min(args.warm_cells, n)]))
+        for form in inputs:
+            for rule in rules:
+                session(form, rule, warm)
+        one_call(warm)
+        points = [(form, rule) for form in inputs for rule in rules]
+        runs, runs_one = {p: [] for p in points}, []
+        for k in range(args.runs):
+            for p in points:
+                key = f"{p[0]}_{p[1]}"
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        dt, got, info = session(*p)
+                    r[key + "_peak_device_bytes"] = int(pk.peak)
+                    r[key + "_duplicates"], r[key + "_corrected_reads"] = info["umi_dup_reads"], info["umi_corrected_reads"]
+                else:
+                    dt, got, info = session(*p)
+                del got
+                runs[p].append(dt)
+                r[key] = spread(runs[p])
+            dt, got = clock(one_call)
+            if k == 0:
+                r["one_call_c_duplicates"], r["one_call_c_corrected_reads"] = int(got[8].sum()), int(got[9].sum())
+                assert r["one_call_c_duplicates"] == r["any_order_c_duplicates"] and r["one_call_c_corrected_reads"] == r["any_order_c_corrected_reads"]
+            del got
+            runs_one.append(dt)
+            r["one_call_c"] = spread(runs_one)
+            for form in inputs:
+                r[f"{form}_gene_keys_cost_s_b_minus_a"] = round(min(runs[(form, "b")]) - min(runs[(form, "a")]), 4)
+                r[f"{form}_gene_keys_and_correction_cost_s_c_minus_a"] = round(min(runs[(form, "c")]) - min(runs[(form, "a")]), 4)
+                r[f"{form}_a_own_spread_s"] = round(max(runs[(form, "a")]) - min(runs[(form, "a")]), 4)
+            print(f"[bench] {style} run {k}: " + ", ".join(f"{p[0]} ({p[1]}) {runs[p][-1]:.3f} s" for p in points)
+                  + f", one call (c) {runs_one[-1]:.3f} s", flush=True)
+            save()
+        del rec, names, sec, bc, umis, inputs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=625)
@@ -707,14 +808,17 @@ def main():
                     help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
     ap.add_argument("--umis-stream", action="store_true",
                     help="the leg of the UMI sessions (both forms) against the UMIs one call and the sessions without UMIs")
+    ap.add_argument("--umis-rule-stream", action="store_true",
+                    help="the leg of the UMI rule in the sessions: both forms under the exact rule, gene keys, gene keys plus correction")
     ap.add_argument("--batch-records", type=int, nargs="*", default=[1 << 21, 1 << 23], help="the session legs: records per pushed batch")
     ap.add_argument("--styles", nargs="*", default=["uuid", "illumina"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream or args.umis_rule_stream else 3
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "cells_umis_stream_bench.json" if args.umis_stream else
+        args.out = os.path.join(ROOT, "profiles", "cells_umis_rule_stream_bench.json" if args.umis_rule_stream else
+                                "cells_umis_stream_bench.json" if args.umis_stream else
                                 "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
                                 "cells_barcodes_stream_bench.json" if args.barcodes_stream else
                                 "cells_records_umis_rule_bench.json" if args.umis_rule else
@@ -782,6 +886,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.umis_rule_stream:
+        umis_rule_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     if args.umis_stream:
         umis_stream_leg(args, cr, res, save)
         print(json.dumps(res))
