@@ -8,7 +8,8 @@
 //                  length and then the bytes 8 at a time against that label.  A hit gives cell_id[k]; EMPTY marks a miss.
 //               2. the misses are compacted (scan + scatter), their barcodes gathered dense (gather_names) and collated
 //                  as one cell (collate_barcodes_device: the key rounds of collate_resident, the runs' heads ranked by
-//                  survivor index).  The new labels get the ids n_labels + rank and their bytes go to the label blob.
+//                  survivor index).  The new labels get the ids n_labels + rank and are appended to the label blob (a
+//                  DevBlob, oem_dev_blob.h: the arena's blob, with its growth and its padding).
 //               3. when the load would pass 1/2 a table of at least twice the capacity is built from the label blob;
 //               4. k_barcode_insert, one label per lane, atomicCAS(slot, EMPTY, id) along the probe path (the keys are
 //                  distinct by construction: nothing is compared);
@@ -79,14 +80,6 @@ __global__ __launch_bounds__(kIT) void k_barcode_miss_scatter(uint64_t m, const 
     if (k < m && miss[k]) idx[at[k]] = (uint32_t)k;
 }
 
-// label_off[n_labels + 1 + j] = label_bytes + src_off[j + 1]: the new labels' ends in the label blob
-__global__ __launch_bounds__(kIT) void k_barcode_label_offsets(uint64_t n_new, const uint64_t *__restrict__ src_off, uint64_t label_bytes,
-                                                                uint64_t *__restrict__ dst)
-{
-    const uint64_t j = (uint64_t)blockIdx.x * kIT + threadIdx.x;
-    if (j < n_new) dst[j] = label_bytes + src_off[j + 1];
-}
-
 // Label first + j, j < cnt, into the first free slot of its probe path.  The labels are distinct, so nothing is compared:
 // a lane claims a slot with one compare-and-swap or moves on, and never waits for another lane.
 __global__ __launch_bounds__(kIT) void k_barcode_insert(uint64_t first, uint64_t cnt, uint32_t *__restrict__ slot, uint64_t capacity,
@@ -137,18 +130,6 @@ __global__ __launch_bounds__(kIT) void k_barcode_run_starts(uint64_t n, uint64_t
     if (c < n_cells && (p == 0 || key[p - 1] != c)) cell_rec_off[c] = p;
 }
 
-// *bad = min(*bad, i) over the records i = order[0 .. cnt) whose ref_id (the low half of a record's first word) is not
-// below n_txps
-__global__ __launch_bounds__(kIT) void k_cells_ref_check(uint64_t cnt, const uint32_t *__restrict__ order, const uint64_t *__restrict__ rec_words,
-                                                          uint32_t n_txps, unsigned long long *__restrict__ bad)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * kIT + threadIdx.x;
-    if (k >= cnt) return;
-    const uint32_t i = order[k];
-    if ((uint32_t)rec_words[(uint64_t)i * 5] >= n_txps) atomicMin(bad, (unsigned long long)i);
-}
-static_assert(offsetof(oem_aln_record, ref_id) == 0 && sizeof(oem_aln_record) == 40, "k_cells_ref_check reads ref_id from a record's first word");
-
 std::mutex g_last_mu;
 uint64_t g_table_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -158,19 +139,6 @@ void barcode_table_last(uint64_t *out8)
 {
     std::lock_guard<std::mutex> lk(g_last_mu);
     std::memcpy(out8, g_table_last, sizeof g_table_last);
-}
-
-int cells_ref_check(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, uint32_t n_txps, uint64_t *bad)
-{
-    DevBuf<unsigned long long> d_bad;
-    unsigned long long b = kNoRecord;
-    OEM_TRY(dev_alloc(&d_bad.p, 1, nullptr));
-    OEM_HIP(hipMemcpy(d_bad.p, &b, sizeof b, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_cells_ref_check, grid_of(m), dim3(kIT), 0, nullptr, m, d_order, (const uint64_t *)d_in, n_txps, d_bad.p);
-    OEM_HIP(hipGetLastError());
-    OEM_HIP(hipMemcpy(&b, d_bad.p, sizeof b, hipMemcpyDeviceToHost));
-    *bad = b;
-    return OEM_OK;
 }
 
 int BarcodeIntern::init()
@@ -190,34 +158,9 @@ int BarcodeIntern::init()
 void BarcodeIntern::release()
 {
     slot.reset();
-    labels.reset();
-    label_off.reset();
+    labels.release();
     stats.reset();
-    capacity = n_labels = label_bytes = label_cap = byte_cap = 0;
-}
-
-// room for n_need labels of bytes_need bytes: geometric, the used part copied on the device
-int BarcodeIntern::reserve_labels(uint64_t n_need, uint64_t bytes_need)
-{
-    if (n_need > label_cap || !label_off.p) {
-        const uint64_t nc = std::max<uint64_t>(std::max<uint64_t>(2 * label_cap, n_need), 1024);
-        DevBuf<uint64_t> o2;
-        OEM_TRY(dev_alloc(&o2.p, nc + 1, nullptr));
-        if (label_off.p) OEM_HIP(hipMemcpy(o2.p, label_off.p, sizeof(uint64_t) * (n_labels + 1), hipMemcpyDeviceToDevice));
-        else OEM_HIP(hipMemset(o2.p, 0, sizeof(uint64_t)));
-        std::swap(label_off.p, o2.p);
-        label_cap = nc;
-    }
-    if (bytes_need > byte_cap || !labels.p) {
-        const uint64_t bc = std::max<uint64_t>(std::max<uint64_t>(2 * byte_cap, bytes_need), 4096);
-        DevBuf<uint8_t> l2;
-        OEM_TRY(dev_alloc(&l2.p, bc + 16, nullptr));
-        OEM_HIP(hipMemset(l2.p, 0, bc + 16)); // zero-padded like the arena's names: a label is read 8 bytes at a time
-        if (label_bytes) OEM_HIP(hipMemcpy(l2.p, labels.p, label_bytes, hipMemcpyDeviceToDevice));
-        std::swap(labels.p, l2.p);
-        byte_cap = bc;
-    }
-    return OEM_OK;
+    capacity = 0;
 }
 
 int BarcodeIntern::check_stats(const char *who)
@@ -241,7 +184,7 @@ int BarcodeIntern::batch(const char *who, const uint8_t *d_bc, const uint64_t *d
     OEM_TRY(dev_alloc(&d_miss.p, m + 1, nullptr));
     OEM_TRY(dev_alloc(&d_at.p, m + 1, nullptr));
     hipLaunchKernelGGL(k_barcode_lookup, grid_of(m + 1), dim3(kIT), 0, nullptr, m, (const uint32_t *)nullptr, d_bc, d_bc_off,
-                       (const uint32_t *)slot.p, capacity, hash_bits, (const uint8_t *)labels.p, (const uint64_t *)label_off.p, n_labels, 0u,
+                       (const uint32_t *)slot.p, capacity, hash_bits, (const uint8_t *)labels.bytes.p, (const uint64_t *)labels.off.p, labels.n, 0u,
                        d_cell_id, d_miss.p, stats.p);
     OEM_HIP(hipGetLastError());
     OEM_TRY(exclusive_scan_u32(d_miss.p, d_at.p, m + 1));
@@ -270,15 +213,11 @@ int BarcodeIntern::batch(const char *who, const uint8_t *d_bc, const uint64_t *d
     cells.cell_rec_off.reset();
     if (n_new == 0 || n_new > n_miss) return fail(OEM_ERR_STATE, "%s: %llu misses gave %llu new barcodes", who, (unsigned long long)n_miss, (unsigned long long)n_new);
     OEM_TRY(gather_input_names(d_heads.p, n_new, d_mblob.p, d_moff.p, &d_lab_off, &d_lab, &lab_bytes));
-    OEM_TRY(reserve_labels(n_labels + n_new, label_bytes + lab_bytes));
-    OEM_HIP(hipMemcpyAsync(labels.p + label_bytes, d_lab.p, lab_bytes, hipMemcpyDeviceToDevice, nullptr));
-    hipLaunchKernelGGL(k_barcode_label_offsets, grid_of(n_new), dim3(kIT), 0, nullptr, n_new, (const uint64_t *)d_lab_off.p, label_bytes,
-                       label_off.p + n_labels + 1);
-    OEM_HIP(hipGetLastError());
-    const uint64_t first_new = n_labels;
-    n_labels += n_new;
-    label_bytes += lab_bytes;
+    const uint64_t first_new = labels.n;
+    OEM_TRY(labels.reserve(labels.n + n_new, labels.n_bytes + lab_bytes, 1024, 4096, 0, nullptr));
+    OEM_TRY(labels.append(d_lab.p, d_lab_off.p, n_new, lab_bytes));
     OEM_HIP(hipStreamSynchronize(nullptr));
+    const uint64_t n_labels = labels.n;
 
     // 3. the load stays at or below 1/2: a table of twice the capacity (or more) from the label blob
     uint64_t from = first_new;
@@ -299,11 +238,11 @@ int BarcodeIntern::batch(const char *who, const uint8_t *d_bc, const uint64_t *d
     }
     // 4. the insert
     hipLaunchKernelGGL(k_barcode_insert, grid_of(n_labels - from), dim3(kIT), 0, nullptr, from, n_labels - from, slot.p, capacity, hash_bits,
-                       (const uint8_t *)labels.p, (const uint64_t *)label_off.p, stats.p);
+                       (const uint8_t *)labels.bytes.p, (const uint64_t *)labels.off.p, stats.p);
     OEM_HIP(hipGetLastError());
     // 5. the misses again
     hipLaunchKernelGGL(k_barcode_lookup, grid_of(n_miss + 1), dim3(kIT), 0, nullptr, n_miss, (const uint32_t *)d_idx.p, d_bc, d_bc_off,
-                       (const uint32_t *)slot.p, capacity, hash_bits, (const uint8_t *)labels.p, (const uint64_t *)label_off.p, n_labels, 1u,
+                       (const uint32_t *)slot.p, capacity, hash_bits, (const uint8_t *)labels.bytes.p, (const uint64_t *)labels.off.p, n_labels, 1u,
                        d_cell_id, (uint32_t *)nullptr, stats.p);
     OEM_HIP(hipGetLastError());
     OEM_HIP(hipStreamSynchronize(nullptr));
@@ -318,36 +257,36 @@ int BarcodeIntern::cells(const uint32_t *d_cell_id, uint64_t n, BarcodeCells *ou
     OEM_TRY(dev_alloc(&d_iota.p, n, nullptr));
     OEM_TRY(dev_alloc(&d_key_s.p, n, nullptr));
     OEM_TRY(dev_alloc(&d_order.p, n, nullptr));
-    OEM_TRY(dev_alloc(&d_cro.p, n_labels + 1, nullptr));
+    OEM_TRY(dev_alloc(&d_cro.p, labels.n + 1, nullptr));
     hipLaunchKernelGGL(k_barcode_iota, grid_of(n), dim3(kIT), 0, nullptr, n, d_iota.p);
     OEM_HIP(hipGetLastError());
-    const int bits = std::max(bits_of(n_labels - 1), 1); // a stable sort over only the bits n_cells needs
+    const int bits = std::max(bits_of(labels.n - 1), 1); // a stable sort over only the bits n_cells needs
     size_t tb = 0;
     OEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_cell_id, d_key_s.p, (const uint32_t *)d_iota.p, d_order.p, (int)n, 0, bits, nullptr));
     OEM_TRY(dev_alloc(&tmp.p, tb, nullptr));
     OEM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, d_cell_id, d_key_s.p, (const uint32_t *)d_iota.p, d_order.p, (int)n, 0, bits, nullptr));
-    hipLaunchKernelGGL(k_barcode_run_starts, grid_of(n + 1), dim3(kIT), 0, nullptr, n, n_labels, (const uint32_t *)d_key_s.p, d_cro.p);
+    hipLaunchKernelGGL(k_barcode_run_starts, grid_of(n + 1), dim3(kIT), 0, nullptr, n, labels.n, (const uint32_t *)d_key_s.p, d_cro.p);
     OEM_HIP(hipGetLastError());
     OEM_HIP(hipStreamSynchronize(nullptr));
     std::swap(out->order.p, d_order.p);
     std::swap(out->cell_rec_off.p, d_cro.p);
-    out->n_cells = n_labels;
+    out->n_cells = labels.n;
     return OEM_OK;
 }
 
 int BarcodeIntern::labels_down(std::vector<uint8_t> *out_labels, std::vector<uint64_t> *out_label_off)
 {
-    out_labels->assign(label_bytes, 0);
-    out_label_off->assign(n_labels + 1, 0);
-    if (label_bytes) OEM_HIP(hipMemcpy(out_labels->data(), labels.p, label_bytes, hipMemcpyDeviceToHost));
-    if (n_labels) OEM_HIP(hipMemcpy(out_label_off->data(), label_off.p, sizeof(uint64_t) * (n_labels + 1), hipMemcpyDeviceToHost));
+    out_labels->assign(labels.n_bytes, 0);
+    out_label_off->assign(labels.n + 1, 0);
+    if (labels.n_bytes) OEM_HIP(hipMemcpy(out_labels->data(), labels.bytes.p, labels.n_bytes, hipMemcpyDeviceToHost));
+    if (labels.n) OEM_HIP(hipMemcpy(out_label_off->data(), labels.off.p, sizeof(uint64_t) * (labels.n + 1), hipMemcpyDeviceToHost));
     return OEM_OK;
 }
 
 void BarcodeIntern::publish_last() const
 {
     std::lock_guard<std::mutex> lk(g_last_mu);
-    const uint64_t v[8] = {rebuilds, longest_probe, wrapped ? 1ull : 0ull, max_doublings, capacity, n_labels, misses, 0};
+    const uint64_t v[8] = {rebuilds, longest_probe, wrapped ? 1ull : 0ull, max_doublings, capacity, labels.n, misses, 0};
     std::memcpy(g_table_last, v, sizeof v);
 }
 

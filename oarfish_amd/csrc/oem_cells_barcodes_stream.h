@@ -11,6 +11,7 @@
 #include "oem_cells.h"
 #include "oem_collate.h"
 #include "oem_collate_device.h"
+#include "oem_dev_blob.h"
 #include "oem_filter_device.h"
 
 namespace oem {
@@ -43,14 +44,13 @@ struct BarcodesEnv {
 };
 
 // The any-order session's table of the labels seen so far, on the device (oem_cells_barcodes_sort_stream.hip,
-// oem_barcode_table.h): its slots, the label blob in id order (zero-padded by 16) with its offsets, and what it counts.
+// oem_barcode_table.h): its slots, the labels in id order (a DevBlob, oem_dev_blob.h), and what it counts.
 // Everything runs on the null stream and leaves it idle.
 struct BarcodeIntern {
     DevBuf<uint32_t> slot;
-    DevBuf<uint8_t> labels;
-    DevBuf<uint64_t> label_off;
+    DevBlob labels;
     DevBuf<unsigned long long> stats; // the kernels' words: the longest probe, a probe wrapped, an error
-    uint64_t capacity = 0, n_labels = 0, label_bytes = 0, label_cap = 0, byte_cap = 0;
+    uint64_t capacity = 0;
     uint32_t hash_bits = 64;
     uint64_t misses = 0, rebuilds = 0, max_doublings = 0, longest_probe = 0;
     bool wrapped = false;
@@ -63,16 +63,12 @@ struct BarcodeIntern {
     // finish: order_bc and cell_rec_off of n > 0 survivors from their cell ids, by one stable radix sort
     int cells(const uint32_t *d_cell_id, uint64_t n, BarcodeCells *out);
     int labels_down(std::vector<uint8_t> *out_labels, std::vector<uint64_t> *out_label_off);
-    uint64_t device_bytes() const { return capacity * sizeof(uint32_t) + (label_cap + 1) * sizeof(uint64_t) + byte_cap + 16; }
     void publish_last() const; // what oem_debug_barcode_table_last reports
-    int reserve_labels(uint64_t n_need, uint64_t bytes_need);
     int check_stats(const char *who);
 };
 // the last finished any-order session's table (8 words): [0] rebuilds, [1] the longest probe, [2] a probe wrapped past the
 // table's end, [3] the most doublings one rebuild covered, [4] the final capacity, [5] labels, [6] misses
 void barcode_table_last(uint64_t *out8);
-// *bad = the smallest i = d_order[k], k < m, whose record's ref_id is not below n_txps, or kNoRecord
-int cells_ref_check(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, uint32_t n_txps, uint64_t *bad);
 // d_out[k] = d_in[0] + ... + d_in[k - 1] over n entries, in 64 bits (oem_cells_barcodes_stream.hip); leaves the null stream idle
 int exclusive_scan_u32(const uint32_t *d_in, uint64_t *d_out, uint64_t n);
 

@@ -18,13 +18,14 @@
 //               open cell's barcode, which stays on the device;
 //               a scan of the heads gives the batch's cell starts (k_barcode_starts); the labels of the cells it opens
 //               are gathered (gather_names), one barcode per cell, and come down;
-//               the survivors' records (k_records_gather), names, flags and session-global indices are appended to the
-//               CELL ARENA, the device buffer of the cells that are not yet run; the batch's own buffers are released
+//               the survivors' records, names, flags and session-global indices are appended to the CELL ARENA, the
+//               device buffer of the cells that are not yet run (a SurvivorArena, oem_dev_blob.h: its layout, growth
+//               and padding are stated there, once); the batch's own buffers are released
 //   the cut   once the arena's closed cells reach group_nnz records or group_cells cells (and always within the
 //             driver's own group rule and a collation batch) they go to the session's group workers as groups that
 //             share the arena; what is left -- closed cells short of a group and the open cell -- moves to the head of a
-//             fresh arena with device-to-device copies, so that parsing goes on under the groups' EM.  An arena grows
-//             when a cell outgrows it.
+//             fresh arena with device-to-device copies (take_tail), so that parsing goes on under the groups' EM.  An
+//             arena grows in place when its cells outgrow it: no group holds the arena the parser appends to.
 //   a group   run_names_group's sequence on arena memory instead of caller memory: collate_resident in its device form
 //             over the arena's names and flags, k_order_compose64 (the group's order as session-global indices, kept for
 //             oem_cells_stream_barcodes_copy), records_gather, filter_device_resident, the coverage model if asked,
@@ -41,9 +42,9 @@
 // A UMI SESSION (oem_cells_stream_set_umis, oem_cells_stream_push_barcodes_umis; oem_collate.h, "UMIs in the sessions") is
 // either form with one UMI per record.  The UMIs take the names' road: staged page-locked with the batch, uploaded, the
 // survivors' gathered into a dense blob and checked for 0 bytes with the empty UMI legal (umis_gather_survivors,
-// oem_dedup_umis.hip), appended to the arena's umis / umi_off, carried by its growth, by the tail's move behind a cut
-// (cubyte beside cbyte) and by finish_any_order's layout by cell.  A group runs dedup_mark behind collate_resident --
-// the arena's blob, its window of umi_off indexed by group-local record -- and dedup_compact where it found duplicates;
+// oem_dedup_umis.hip), appended to the arena's second blob (umis), carried by its growth, by the tail's move behind a
+// cut and by finish_any_order's layout by cell.  A group runs dedup_mark behind collate_resident -- the arena's blob,
+// its window of the UMIs' offsets indexed by group-local record -- and dedup_compact where it found duplicates;
 // from there on the group has mp <= m positions, and the order, the gather (under the adjacent cut too: the order is
 // no longer the identity), the filter and the host loop run over the deduplicated collation.  The slot keeps
 // n_positions, the cells' first positions and cell_dups for barcodes_stream_assemble: every later group's place in
@@ -115,30 +116,12 @@ __global__ __launch_bounds__(kBT) void k_barcode_heads(uint64_t m, const uint8_t
     head[k] = h ? 1u : 0u;
 }
 
-// at: the exclusive scan of head.  The j-th head's survivor and its first name byte in the dense names.
+// at: the exclusive scan of head.  The j-th head's survivor.
 __global__ __launch_bounds__(kBT) void k_barcode_starts(uint64_t m, const uint32_t *__restrict__ head, const uint64_t *__restrict__ at,
-                                                         const uint64_t *__restrict__ name_off, uint32_t *__restrict__ start,
-                                                         uint64_t *__restrict__ start_byte)
+                                                         uint32_t *__restrict__ start)
 {
     const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
-    if (k >= m || !head[k]) return;
-    start[at[k]] = (uint32_t)k;
-    start_byte[at[k]] = name_off[k];
-}
-
-// dst[k] = src[k] + add over n entries (add wraps: the tail of an arena moves down by its first byte)
-__global__ __launch_bounds__(kBT) void k_offsets_shift(uint64_t n, const uint64_t *__restrict__ src, uint64_t add, uint64_t *__restrict__ dst)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
-    if (k < n) dst[k] = src[k] + add;
-}
-
-// dst[k] = rec_base + order[k]: the survivors' session-global indices
-__global__ __launch_bounds__(kBT) void k_global_index(uint64_t m, const uint32_t *__restrict__ order, uint64_t rec_base,
-                                                       uint64_t *__restrict__ dst)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
-    if (k < m) dst[k] = rec_base + order[k];
+    if (k < m && head[k]) start[at[k]] = (uint32_t)k;
 }
 
 // out[k] = gidx[order[k]]: a group's collated positions as session-global indices (k_order_compose over 64 bits)
@@ -147,57 +130,6 @@ __global__ __launch_bounds__(kBT) void k_order_compose64(uint64_t m, const uint3
 {
     const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
     if (k < m) out[k] = gidx[order[k]];
-}
-
-// The cells that are not yet run, on the device, in survivor order.  names is 8-byte aligned (an allocation's start) and
-// allocated 16 bytes past cap_bytes; name_off holds n + 1 offsets from 0; sec one byte past cap.
-// A UMI session: umis and umi_off likewise (an empty UMI is legal), 16 bytes past cap_umi_bytes.
-struct Arena {
-    DevBuf<oem_aln_record> rec;
-    DevBuf<uint8_t> names, sec, umis;
-    DevBuf<uint64_t> name_off, gidx, umi_off;
-    DevBuf<uint32_t> cell_id; // an any-order session: the survivors' cells
-    uint64_t cap = 0, cap_bytes = 0, cap_umi_bytes = 0;
-    bool with_umis = false;
-    uint64_t device_bytes(bool with_ids) const
-    {
-        return cap * (sizeof(oem_aln_record) + 2 * sizeof(uint64_t) + 1 + (with_ids ? sizeof(uint32_t) : 0)) + cap_bytes + 32 +
-               (with_umis ? (cap + 1) * sizeof(uint64_t) + cap_umi_bytes + 16 : 0);
-    }
-};
-
-// dst[k] = src[at[k]] over n entries
-__global__ __launch_bounds__(kBT) void k_sample64(uint64_t n, const uint64_t *__restrict__ at, const uint64_t *__restrict__ src,
-                                                   uint64_t *__restrict__ dst)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * kBT + threadIdx.x;
-    if (k < n) dst[k] = src[at[k]];
-}
-
-// umi_bytes: kNoUmis, or the capacity of the UMI blob of a UMI session's arena
-constexpr uint64_t kNoUmis = ~0ull;
-int arena_make(uint64_t cap, uint64_t cap_bytes, bool with_ids, uint64_t umi_bytes, std::shared_ptr<Arena> *out)
-{
-    std::shared_ptr<Arena> a(new Arena());
-    if (with_ids) OEM_TRY(dev_alloc(&a->cell_id.p, cap, nullptr));
-    OEM_TRY(dev_alloc(&a->rec.p, cap, nullptr));
-    OEM_TRY(dev_alloc(&a->names.p, cap_bytes + 16, nullptr));
-    OEM_TRY(dev_alloc(&a->sec.p, cap + 8, nullptr));
-    OEM_TRY(dev_alloc(&a->name_off.p, cap + 1, nullptr));
-    OEM_TRY(dev_alloc(&a->gidx.p, cap, nullptr));
-    OEM_HIP(hipMemset(a->name_off.p, 0, sizeof(uint64_t)));
-    if (umi_bytes != kNoUmis) {
-        OEM_TRY(dev_alloc(&a->umis.p, umi_bytes + 16, nullptr));
-        OEM_TRY(dev_alloc(&a->umi_off.p, cap + 1, nullptr));
-        OEM_HIP(hipMemset(a->umi_off.p, 0, sizeof(uint64_t)));
-        OEM_HIP(hipMemset(a->umis.p, 0, 16));
-        a->with_umis = true;
-        a->cap_umi_bytes = umi_bytes;
-    }
-    a->cap = cap;
-    a->cap_bytes = cap_bytes;
-    *out = std::move(a);
-    return OEM_OK;
 }
 
 inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
@@ -264,11 +196,13 @@ struct BarcodesStream {
     std::string stuck_msg;
 
     // -- the parse worker's state (no lock: one thread; finish reads it after the join) ---------------------------------
-    std::shared_ptr<Arena> arena;
-    uint64_t arena_n = 0, arena_bytes = 0;     // survivors and name bytes in the arena
-    uint64_t arena_umi_bytes = 0;              // a UMI session: UMI bytes in the arena
-    std::vector<uint64_t> cstart, cbyte;       // the arena's cells: first survivor and first name byte; the last one is open
-    std::vector<uint64_t> cubyte;              // a UMI session: the cells' first UMI bytes, beside cbyte
+    // The cells that are not yet run (SurvivorArena, oem_dev_blob.h; with the survivors' cell ids in an any-order
+    // session, their UMIs in a UMI session).  It grows in place under the appends, which is sound because THE PARSE
+    // WORKER NEVER APPENDS TO AN ARENA THAT A GROUP HOLDS: cut_groups moves the arena out of this member before the
+    // first group of a call captures it, so on every return -- the cancelled wait and the errors included -- `arena`
+    // is a fresh one with the tail, or none.  A cancelled part drops arena and cells, and parses no further batch.
+    std::shared_ptr<SurvivorArena> arena;
+    std::vector<uint64_t> cstart;              // the arena's cells: their first survivors; the last one is open
     uint64_t first_cell = 0;                   // the session's number of the arena's first cell
     DevBuf<uint8_t> carry;                     // the open cell's barcode, padded by 16
     uint64_t carry_len = 0;
@@ -334,77 +268,19 @@ struct BarcodesStream {
         std::lock_guard<std::mutex> lk(mu);
         arena_peak = std::max(arena_peak, held);
     }
-    int arena_reserve(uint64_t need, uint64_t need_bytes, uint64_t need_umi_bytes);
-    int arena_append(const Batch &b, uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, const uint8_t *d_dnames,
-                     const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id,
-                     const uint8_t *d_dumis, const uint64_t *d_dumi_off, uint64_t dumi_bytes);
+    std::shared_ptr<SurvivorArena> new_arena(bool with_ids) const // (empty: nothing is allocated yet)
+    {
+        return std::make_shared<SurvivorArena>(kFirstArenaRecords, kFirstArenaBytes, with_ids, with_umis);
+    }
     int intern_batch(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_order, uint64_t m, const uint8_t *d_dbc,
                      const uint64_t *d_dbc_off, DevBuf<uint32_t> *d_cell_id);
     int finish_any_order(const char *who);
     int run_batch(const Batch &b);
     int cut_groups(bool final);
-    int run_group(const std::shared_ptr<Arena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot, StreamGroupResult *out,
+    int run_group(const std::shared_ptr<SurvivorArena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot, StreamGroupResult *out,
                   bool *batched);
     void process(Batch &b, bool skip);
 };
-
-// Room for `need` survivors and `need_bytes` name bytes: the arena as it is, or a larger one with the contents moved over.
-int BarcodesStream::arena_reserve(uint64_t need, uint64_t need_bytes, uint64_t need_umi_bytes)
-{
-    if (arena && need <= arena->cap && need_bytes <= arena->cap_bytes && (!with_umis || need_umi_bytes <= arena->cap_umi_bytes)) return OEM_OK;
-    uint64_t cap = arena ? arena->cap : kFirstArenaRecords, cap_bytes = arena ? arena->cap_bytes : kFirstArenaBytes;
-    uint64_t cap_umi = arena ? arena->cap_umi_bytes : kFirstArenaBytes;
-    while (cap < need) cap = std::max(cap * 2, need);
-    while (cap_bytes < need_bytes) cap_bytes = std::max(cap_bytes * 2, need_bytes);
-    while (cap_umi < need_umi_bytes) cap_umi = std::max(cap_umi * 2, need_umi_bytes);
-    std::shared_ptr<Arena> na;
-    OEM_TRY(arena_make(cap, cap_bytes, any_order, with_umis ? cap_umi : kNoUmis, &na));
-    note_arena_bytes((arena ? arena->device_bytes(any_order) : 0) + na->device_bytes(any_order)); // (a growing array is held twice)
-    if (arena && arena_n && any_order)
-        OEM_HIP(hipMemcpy(na->cell_id.p, arena->cell_id.p, sizeof(uint32_t) * arena_n, hipMemcpyDeviceToDevice));
-    if (arena && arena_n) {
-        OEM_HIP(hipMemcpy(na->rec.p, arena->rec.p, sizeof(oem_aln_record) * arena_n, hipMemcpyDeviceToDevice));
-        OEM_HIP(hipMemcpy(na->names.p, arena->names.p, arena_bytes, hipMemcpyDeviceToDevice));
-        OEM_HIP(hipMemcpy(na->sec.p, arena->sec.p, arena_n, hipMemcpyDeviceToDevice));
-        OEM_HIP(hipMemcpy(na->name_off.p, arena->name_off.p, sizeof(uint64_t) * (arena_n + 1), hipMemcpyDeviceToDevice));
-        OEM_HIP(hipMemcpy(na->gidx.p, arena->gidx.p, sizeof(uint64_t) * arena_n, hipMemcpyDeviceToDevice));
-    }
-    if (arena && arena_n && with_umis) {
-        if (arena_umi_bytes) OEM_HIP(hipMemcpy(na->umis.p, arena->umis.p, arena_umi_bytes, hipMemcpyDeviceToDevice));
-        OEM_HIP(hipMemset(na->umis.p + arena_umi_bytes, 0, 16));
-        OEM_HIP(hipMemcpy(na->umi_off.p, arena->umi_off.p, sizeof(uint64_t) * (arena_n + 1), hipMemcpyDeviceToDevice));
-    }
-    arena = std::move(na);
-    return OEM_OK;
-}
-
-// The batch's m survivors into the arena: records, names, flags, session-global indices and (an any-order session)
-// cell ids; in a UMI session their UMIs (the dense blob, its m + 1 offsets from 0, its bytes).  arena_n, arena_bytes and
-// arena_umi_bytes are the caller's to advance.
-int BarcodesStream::arena_append(const Batch &b, uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, const uint8_t *d_dnames,
-                                 const uint64_t *d_dname_off, uint64_t dname_bytes, const uint8_t *d_dsec, const uint32_t *d_cell_id,
-                                 const uint8_t *d_dumis, const uint64_t *d_dumi_off, uint64_t dumi_bytes)
-{
-    OEM_TRY(arena_reserve(arena_n + m, arena_bytes + dname_bytes, arena_umi_bytes + dumi_bytes));
-    Arena &a = *arena;
-    OEM_TRY(records_gather(m, d_order, d_in, a.rec.p + arena_n));
-    if (dname_bytes) OEM_HIP(hipMemcpyAsync(a.names.p + arena_bytes, d_dnames, dname_bytes, hipMemcpyDeviceToDevice, nullptr));
-    hipLaunchKernelGGL(k_offsets_shift, grid_of(m + 1), dim3(kBT), 0, nullptr, m + 1, d_dname_off, arena_bytes, a.name_off.p + arena_n);
-    OEM_HIP(hipGetLastError());
-    if (d_dsec) OEM_HIP(hipMemcpyAsync(a.sec.p + arena_n, d_dsec, m, hipMemcpyDeviceToDevice, nullptr));
-    else OEM_HIP(hipMemsetAsync(a.sec.p + arena_n, 0, m, nullptr));
-    hipLaunchKernelGGL(k_global_index, grid_of(m), dim3(kBT), 0, nullptr, m, d_order, b.rec_base, a.gidx.p + arena_n);
-    OEM_HIP(hipGetLastError());
-    if (d_cell_id) OEM_HIP(hipMemcpyAsync(a.cell_id.p + arena_n, d_cell_id, sizeof(uint32_t) * m, hipMemcpyDeviceToDevice, nullptr));
-    if (with_umis) {
-        if (dumi_bytes) OEM_HIP(hipMemcpyAsync(a.umis.p + arena_umi_bytes, d_dumis, dumi_bytes, hipMemcpyDeviceToDevice, nullptr));
-        OEM_HIP(hipMemsetAsync(a.umis.p + arena_umi_bytes + dumi_bytes, 0, 16, nullptr));
-        hipLaunchKernelGGL(k_offsets_shift, grid_of(m + 1), dim3(kBT), 0, nullptr, m + 1, d_dumi_off, arena_umi_bytes, a.umi_off.p + arena_n);
-        OEM_HIP(hipGetLastError());
-    }
-    OEM_HIP(hipStreamSynchronize(nullptr));
-    return OEM_OK;
-}
 
 // An any-order session's batch behind its name checks: the ref_ids while the batch still knows its ticket, the bound on
 // the survivors (finish collates them as one batch), then the cells of the m survivors from the table.
@@ -412,12 +288,12 @@ int BarcodesStream::intern_batch(const Batch &b, const char *who, const oem_aln_
                                  const uint8_t *d_dbc, const uint64_t *d_dbc_off, DevBuf<uint32_t> *d_cell_id)
 {
     uint64_t bad = kNoRecord;
-    OEM_TRY(cells_ref_check(m, d_order, d_in, env.n_txps, &bad));
+    OEM_TRY(records_ref_check(m, d_order, d_in, env.n_txps, &bad));
     if (bad != kNoRecord) {
         const oem_aln_record *h = (const oem_aln_record *)b.base();
         return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)(b.rec_base + bad), h[bad].ref_id);
     }
-    if (arena_n + m > kCollateMaxBatch)
+    if ((arena ? arena->n : 0) + m > kCollateMaxBatch)
         return fail(OEM_ERR_ARG, "%s: more than 2^31 - 2 surviving records in the session: its cells are found by one sort at finish", who);
     OEM_TRY(dev_alloc(&d_cell_id->p, m, nullptr));
     OEM_TRY(intern.batch(who, d_dbc, d_dbc_off, m, d_cell_id->p));
@@ -433,7 +309,7 @@ int BarcodesStream::intern_batch(const Batch &b, const char *who, const oem_aln_
 int BarcodesStream::finish_any_order(const char *who)
 {
     intern.publish_last();
-    const uint64_t m = arena_n;
+    const uint64_t m = arena ? arena->n : 0;
     if (m == 0) {
         intern.release();
         return OEM_OK;
@@ -443,38 +319,29 @@ int BarcodesStream::finish_any_order(const char *who)
     OEM_TRY(intern.labels_down(&labels, &label_off));
     intern.release();
     const uint64_t nc = bc.n_cells;
-    std::shared_ptr<Arena> na;
-    OEM_TRY(arena_make(m, arena_bytes, false, with_umis ? arena_umi_bytes : kNoUmis, &na));
-    note_arena_bytes(arena->device_bytes(true) + na->device_bytes(false));
-    Arena &a = *arena;
-    OEM_HIP(hipMemset(a.names.p + arena_bytes, 0, 16));
-    OEM_HIP(hipMemset(a.sec.p + m, 0, 8));
+    const SurvivorArena &a = *arena;
+    std::shared_ptr<SurvivorArena> na = new_arena(false); // at exact size: nothing is appended to it
+    OEM_TRY(na->make(m, a.names.n_bytes, a.umis.n_bytes));
+    note_arena_bytes(a.held() + na->held());
+    // the gathers write whole words, which leaves fewer zeros than the arena's invariant asks: the memsets complete them
+    auto gather_blob = [&](const DevBlob &src, DevBlob &dst, const uint8_t *src_sec, uint8_t *dst_sec, bool with_empty) {
+        OEM_TRY(gather_name_offsets(bc.order.p, m, src.off.p, dst.off.p));
+        OEM_TRY(gather_names(bc.order.p, m, src.bytes.p, src.off.p, dst.off.p, 0, src.n_bytes, dst.bytes.p, src_sec, dst_sec, with_empty));
+        OEM_HIP(hipMemsetAsync(dst.bytes.p + src.n_bytes, 0, kBlobPad, nullptr));
+        dst.n = m;
+        dst.n_bytes = src.n_bytes;
+        return (int)OEM_OK;
+    };
     OEM_TRY(records_gather(m, bc.order.p, a.rec.p, na->rec.p));
-    OEM_TRY(gather_name_offsets(bc.order.p, m, a.name_off.p, na->name_off.p));
-    OEM_TRY(gather_names(bc.order.p, m, a.names.p, a.name_off.p, na->name_off.p, 0, arena_bytes, na->names.p, a.sec.p, na->sec.p));
+    OEM_TRY(gather_blob(a.names, na->names, a.sec.p, na->sec.p, false));
+    if (with_umis) OEM_TRY(gather_blob(a.umis, na->umis, nullptr, nullptr, true)); // in cell order, as the names
+    OEM_HIP(hipMemsetAsync(na->sec.p + m, 0, kFlagPad, nullptr));
     hipLaunchKernelGGL(k_order_compose64, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)bc.order.p, (const uint64_t *)a.gidx.p,
                        na->gidx.p);
     OEM_HIP(hipGetLastError());
-    // the cells: their first survivors and first name bytes
-    DevBuf<uint64_t> d_cbyte;
-    OEM_TRY(dev_alloc(&d_cbyte.p, nc, nullptr));
-    hipLaunchKernelGGL(k_sample64, grid_of(nc), dim3(kBT), 0, nullptr, nc, (const uint64_t *)bc.cell_rec_off.p, (const uint64_t *)na->name_off.p,
-                       d_cbyte.p);
-    OEM_HIP(hipGetLastError());
-    cstart.assign(nc, 0);
-    cbyte.assign(nc, 0);
+    na->n = m;
+    cstart.assign(nc, 0); // the cells: their first survivors
     OEM_HIP(hipMemcpy(cstart.data(), bc.cell_rec_off.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
-    OEM_HIP(hipMemcpy(cbyte.data(), d_cbyte.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
-    if (with_umis) { // the UMIs as the names: in cell order, and the cells' first UMI bytes
-        OEM_HIP(hipMemset(a.umis.p + arena_umi_bytes, 0, 16));
-        OEM_TRY(gather_name_offsets(bc.order.p, m, a.umi_off.p, na->umi_off.p));
-        OEM_TRY(gather_names(bc.order.p, m, a.umis.p, a.umi_off.p, na->umi_off.p, 0, arena_umi_bytes, na->umis.p, nullptr, nullptr, true));
-        hipLaunchKernelGGL(k_sample64, grid_of(nc), dim3(kBT), 0, nullptr, nc, (const uint64_t *)bc.cell_rec_off.p,
-                           (const uint64_t *)na->umi_off.p, d_cbyte.p);
-        OEM_HIP(hipGetLastError());
-        cubyte.assign(nc, 0);
-        OEM_HIP(hipMemcpy(cubyte.data(), d_cbyte.p, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
-    }
     first_cell = 0;
     arena = std::move(na);
     (void)who;
@@ -492,31 +359,16 @@ int BarcodesStream::run_batch(const Batch &b)
     DevBuf<uint8_t> d_bc, d_names, d_sec;
     DevBuf<uint64_t> d_bc_off, d_name_off;
     OEM_TRY(dev_alloc(&d_in.p, n, nullptr));
-    OEM_TRY(dev_alloc(&d_bc.p, b.bc_bytes + 16, nullptr));
-    OEM_TRY(dev_alloc(&d_names.p, b.name_bytes + 16, nullptr));
-    OEM_TRY(dev_alloc(&d_bc_off.p, n + 1, nullptr));
-    OEM_TRY(dev_alloc(&d_name_off.p, n + 1, nullptr));
     OEM_HIP(hipMemcpyAsync(d_in.p, b.base(), sizeof(oem_aln_record) * n, hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemcpyAsync(d_bc_off.p, b.base() + b.at_bc_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemcpyAsync(d_name_off.p, b.base() + b.at_name_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
-    if (b.bc_bytes) OEM_HIP(hipMemcpyAsync(d_bc.p, b.base() + b.at_bc(), b.bc_bytes, hipMemcpyHostToDevice, nullptr));
-    if (b.name_bytes) OEM_HIP(hipMemcpyAsync(d_names.p, b.base() + b.at_names(), b.name_bytes, hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemsetAsync(d_bc.p + b.bc_bytes, 0, 16, nullptr));
-    OEM_HIP(hipMemsetAsync(d_names.p + b.name_bytes, 0, 16, nullptr));
-    if (b.has_sec) {
-        OEM_TRY(dev_alloc(&d_sec.p, n + 8, nullptr));
-        OEM_HIP(hipMemcpyAsync(d_sec.p, b.base() + b.at_sec(), n, hipMemcpyHostToDevice, nullptr));
-        OEM_HIP(hipMemsetAsync(d_sec.p + n, 0, 8, nullptr));
-    }
+    auto up = [&](size_t at_bytes, uint64_t n_bytes, size_t at_off, DevBuf<uint8_t> *d_bytes, DevBuf<uint64_t> *d_off) {
+        return upload_blob_async((const uint8_t *)b.base() + at_bytes, n_bytes, (const uint64_t *)(b.base() + at_off), n, 0, 0, d_bytes, d_off);
+    };
+    OEM_TRY(up(b.at_bc(), b.bc_bytes, b.at_bc_off(), &d_bc, &d_bc_off));
+    OEM_TRY(up(b.at_names(), b.name_bytes, b.at_name_off(), &d_names, &d_name_off));
+    if (b.has_sec) OEM_TRY(upload_flags_async((const uint8_t *)b.base() + b.at_sec(), n, &d_sec));
     DevBuf<uint8_t> d_umis;
     DevBuf<uint64_t> d_umi_off;
-    if (with_umis) { // (a batch of a UMI session always has its offsets)
-        OEM_TRY(dev_alloc(&d_umis.p, b.umi_bytes + 16, nullptr));
-        OEM_TRY(dev_alloc(&d_umi_off.p, n + 1, nullptr));
-        OEM_HIP(hipMemcpyAsync(d_umi_off.p, b.base() + b.at_umi_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
-        if (b.umi_bytes) OEM_HIP(hipMemcpyAsync(d_umis.p, b.base() + b.at_umis(), b.umi_bytes, hipMemcpyHostToDevice, nullptr));
-        OEM_HIP(hipMemsetAsync(d_umis.p + b.umi_bytes, 0, 16, nullptr));
-    }
+    if (with_umis) OEM_TRY(up(b.at_umis(), b.umi_bytes, b.at_umi_off(), &d_umis, &d_umi_off)); // (a UMI session's batch always has its offsets)
     OEM_HIP(hipStreamSynchronize(nullptr));
 
     // the survivors; their barcodes and names as dense blobs, checked
@@ -554,23 +406,26 @@ int BarcodesStream::run_batch(const Batch &b)
     d_names.reset();
     d_name_off.reset();
 
+    // the batch's survivors into the arena, which the first of them makes
+    auto append = [&](const uint32_t *d_cell_id) {
+        if (!arena) arena = new_arena(any_order);
+        OEM_TRY(arena->append(m, d_order.p, d_in.p, n, b.rec_base, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, d_cell_id, d_dumis.p,
+                              d_dumi_off.p, dumi_bytes));
+        note_arena_bytes(arena->peak);
+        n_survivors += m;
+        return (int)OEM_OK;
+    };
     if (any_order) { // the survivors' cells from the table; the arena takes them with their cell ids, and nothing is cut
         DevBuf<uint32_t> d_cell_id;
         OEM_TRY(intern_batch(b, who, d_in.p, d_order.p, m, d_dbc.p, d_dbc_off.p, &d_cell_id));
         d_dbc.reset();
         d_dbc_off.reset();
-        OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, d_cell_id.p, d_dumis.p, d_dumi_off.p,
-                             dumi_bytes));
-        arena_n += m;
-        arena_bytes += dname_bytes;
-        arena_umi_bytes += dumi_bytes;
-        n_survivors += m;
-        return OEM_OK;
+        return append(d_cell_id.p);
     }
 
     // the heads and the batch's cell starts
     DevBuf<uint32_t> d_head, d_start;
-    DevBuf<uint64_t> d_at, d_start_byte, d_start_ubyte;
+    DevBuf<uint64_t> d_at;
     OEM_TRY(dev_alloc(&d_head.p, m + 1, nullptr));
     OEM_TRY(dev_alloc(&d_at.p, m + 1, nullptr));
     const bool has_carry = !cstart.empty();
@@ -581,22 +436,11 @@ int BarcodesStream::run_batch(const Batch &b)
     uint64_t nh = 0;
     OEM_HIP(hipMemcpy(&nh, d_at.p + m, sizeof nh, hipMemcpyDeviceToHost));
     std::vector<uint32_t> start(nh);
-    std::vector<uint64_t> start_byte(nh);
     if (nh) {
         OEM_TRY(dev_alloc(&d_start.p, nh, nullptr));
-        OEM_TRY(dev_alloc(&d_start_byte.p, nh, nullptr));
-        hipLaunchKernelGGL(k_barcode_starts, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_head.p, (const uint64_t *)d_at.p,
-                           (const uint64_t *)d_dname_off.p, d_start.p, d_start_byte.p);
+        hipLaunchKernelGGL(k_barcode_starts, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_head.p, (const uint64_t *)d_at.p, d_start.p);
         OEM_HIP(hipGetLastError());
         OEM_HIP(hipMemcpy(start.data(), d_start.p, sizeof(uint32_t) * nh, hipMemcpyDeviceToHost));
-        OEM_HIP(hipMemcpy(start_byte.data(), d_start_byte.p, sizeof(uint64_t) * nh, hipMemcpyDeviceToHost));
-        if (with_umis) { // the same starts over the dense UMIs' offsets: the cells' first UMI bytes
-            OEM_TRY(dev_alloc(&d_start_ubyte.p, nh, nullptr));
-            hipLaunchKernelGGL(k_barcode_starts, grid_of(m), dim3(kBT), 0, nullptr, m, (const uint32_t *)d_head.p, (const uint64_t *)d_at.p,
-                               (const uint64_t *)d_dumi_off.p, d_start.p, d_start_ubyte.p);
-            OEM_HIP(hipGetLastError());
-            OEM_HIP(hipStreamSynchronize(nullptr));
-        }
         // the labels of the cells the batch opens: one barcode per cell; the last one is the new carry
         DevBuf<uint64_t> d_lab_off;
         DevBuf<uint8_t> d_lab;
@@ -620,19 +464,9 @@ int BarcodesStream::run_batch(const Batch &b)
     d_dbc.reset();
     d_dbc_off.reset();
 
-    OEM_TRY(arena_append(b, m, d_order.p, d_in.p, d_dnames.p, d_dname_off.p, dname_bytes, d_dsec.p, nullptr, d_dumis.p, d_dumi_off.p, dumi_bytes));
-    for (uint64_t j = 0; j < nh; ++j) {
-        cstart.push_back(arena_n + start[j]);
-        cbyte.push_back(arena_bytes + start_byte[j]);
-    }
-    if (with_umis && nh) { // the cells' first UMI bytes, beside cbyte
-        OEM_HIP(hipMemcpy(start_byte.data(), d_start_ubyte.p, sizeof(uint64_t) * nh, hipMemcpyDeviceToHost));
-        for (uint64_t j = 0; j < nh; ++j) cubyte.push_back(arena_umi_bytes + start_byte[j]);
-    }
-    arena_n += m;
-    arena_bytes += dname_bytes;
-    arena_umi_bytes += dumi_bytes;
-    n_survivors += m;
+    const uint64_t n0 = arena ? arena->n : 0;
+    OEM_TRY(append(nullptr));
+    for (uint64_t j = 0; j < nh; ++j) cstart.push_back(n0 + start[j]);
     return cut_groups(false);
 }
 
@@ -640,9 +474,11 @@ int BarcodesStream::run_batch(const Batch &b)
 // to the head of a fresh arena.
 int BarcodesStream::cut_groups(bool final)
 {
+    const uint64_t arena_n = arena ? arena->n : 0;
     const size_t n_all = cstart.size(), n_closed = final ? n_all : (n_all ? n_all - 1 : 0);
     auto cell_end = [&](size_t i) { return i + 1 < n_all ? cstart[i + 1] : arena_n; };
     const uint64_t hard = cells_max_group_nnz(), max_batch = std::min<uint64_t>(collate_batch_records(), kCollateMaxBatch);
+    std::shared_ptr<SurvivorArena> old; // the arena from the first hand-over on: the groups', no longer this part's
     size_t i = 0;
     while (i < n_closed) {
         size_t j = i;
@@ -668,7 +504,11 @@ int BarcodesStream::cut_groups(bool final)
         { // the workers take a few groups at a time: every group holds its arena
             std::unique_lock<std::mutex> lk(mu);
             cv_groups.wait(lk, [&] { return groups_in_flight < kMaxGroupsInFlight || cancel; });
-            if (cancel) return OEM_OK;
+            if (cancel) { // (nothing more is parsed: process)
+                arena.reset();
+                cstart.clear();
+                return OEM_OK;
+            }
             ++groups_in_flight;
         }
         std::vector<uint64_t> cro(j - i + 1);
@@ -694,7 +534,8 @@ int BarcodesStream::cut_groups(bool final)
             }
         };
         std::shared_ptr<InFlight> guard(new InFlight{this});
-        std::shared_ptr<Arena> a = arena;
+        if (!old) old.swap(arena); // (`arena` is none from here on)
+        std::shared_ptr<SurvivorArena> a = old;
         const uint64_t cell0 = first_cell + i;
         run_records += recs;
         env.submit([this, a, cro, cell0, slot, guard](StreamGroupResult *out, bool *batched) {
@@ -705,51 +546,27 @@ int BarcodesStream::cut_groups(bool final)
     }
     if (i == 0) return OEM_OK;
     // what is left moves to the head of a fresh arena; the groups keep the old one
-    const uint64_t t = i < n_all ? cstart[i] : arena_n, tb = i < n_all ? cbyte[i] : arena_bytes;
-    const uint64_t tail_n = arena_n - t, tail_bytes = arena_bytes - tb;
-    const uint64_t tub = !with_umis ? 0 : i < n_all ? cubyte[i] : arena_umi_bytes, tail_umi_bytes = arena_umi_bytes - tub;
-    std::shared_ptr<Arena> old = std::move(arena);
-    arena.reset();
-    if (!final) {
+    const uint64_t t = i < n_all ? cstart[i] : arena_n;
+    if (!final) { // (the tail's first name and UMI bytes are the old arena's offsets at t)
+        uint64_t tb = 0, tub = 0;
+        OEM_HIP(hipMemcpy(&tb, old->names.off.p + t, sizeof tb, hipMemcpyDeviceToHost));
+        if (with_umis) OEM_HIP(hipMemcpy(&tub, old->umis.off.p + t, sizeof tub, hipMemcpyDeviceToHost));
+        const uint64_t tail_n = arena_n - t, tail_bytes = old->names.n_bytes - tb, tail_umi_bytes = old->umis.n_bytes - tub;
         const uint64_t cap = std::max(tail_n, std::min(old->cap, 2 * env.group_nnz)) + 4096;
-        OEM_TRY(arena_make(cap, std::max(tail_bytes, std::min<uint64_t>(old->cap_bytes, 64 * cap)) + 4096, false,
-                           with_umis ? std::max(tail_umi_bytes, std::min<uint64_t>(old->cap_umi_bytes, 16 * cap)) + 4096 : kNoUmis, &arena));
-        if (tail_n && with_umis) {
-            if (tail_umi_bytes)
-                OEM_HIP(hipMemcpyAsync(arena->umis.p, old->umis.p + tub, tail_umi_bytes, hipMemcpyDeviceToDevice, nullptr));
-            OEM_HIP(hipMemsetAsync(arena->umis.p + tail_umi_bytes, 0, 16, nullptr));
-            hipLaunchKernelGGL(k_offsets_shift, grid_of(tail_n + 1), dim3(kBT), 0, nullptr, tail_n + 1, (const uint64_t *)(old->umi_off.p + t),
-                               (uint64_t)0 - tub, arena->umi_off.p);
-            OEM_HIP(hipGetLastError());
-        }
-        if (tail_n) {
-            OEM_HIP(hipMemcpyAsync(arena->rec.p, old->rec.p + t, sizeof(oem_aln_record) * tail_n, hipMemcpyDeviceToDevice, nullptr));
-            if (tail_bytes) OEM_HIP(hipMemcpyAsync(arena->names.p, old->names.p + tb, tail_bytes, hipMemcpyDeviceToDevice, nullptr));
-            OEM_HIP(hipMemcpyAsync(arena->sec.p, old->sec.p + t, tail_n, hipMemcpyDeviceToDevice, nullptr));
-            OEM_HIP(hipMemcpyAsync(arena->gidx.p, old->gidx.p + t, sizeof(uint64_t) * tail_n, hipMemcpyDeviceToDevice, nullptr));
-            hipLaunchKernelGGL(k_offsets_shift, grid_of(tail_n + 1), dim3(kBT), 0, nullptr, tail_n + 1, (const uint64_t *)(old->name_off.p + t),
-                               (uint64_t)0 - tb, arena->name_off.p);
-            OEM_HIP(hipGetLastError());
-            OEM_HIP(hipStreamSynchronize(nullptr));
-        }
+        std::shared_ptr<SurvivorArena> fresh = new_arena(false);
+        OEM_TRY(fresh->make(cap, std::max(tail_bytes, std::min<uint64_t>(old->names.cap_bytes, 64 * cap)) + 4096,
+                            std::max(tail_umi_bytes, std::min<uint64_t>(old->umis.cap_bytes, 16 * cap)) + 4096));
+        OEM_TRY(fresh->take_tail(*old, t, tb, tub));
+        arena = std::move(fresh);
     }
     first_cell += i;
     cstart.erase(cstart.begin(), cstart.begin() + i);
-    cbyte.erase(cbyte.begin(), cbyte.begin() + i);
     for (uint64_t &v : cstart) v -= t;
-    for (uint64_t &v : cbyte) v -= tb;
-    if (with_umis) {
-        cubyte.erase(cubyte.begin(), cubyte.begin() + i);
-        for (uint64_t &v : cubyte) v -= tub;
-    }
-    arena_n = tail_n;
-    arena_bytes = tail_bytes;
-    arena_umi_bytes = tail_umi_bytes;
     return OEM_OK;
 }
 
 // One group on a group worker: the cells at cro[0 .. n_cells] of the arena `a`, the session's cells cell0 ...
-int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot,
+int BarcodesStream::run_group(const std::shared_ptr<SurvivorArena> &a, const std::vector<uint64_t> &cro, uint64_t cell0, Slot *slot,
                               StreamGroupResult *out, bool *batched)
 {
     *batched = false;
@@ -769,8 +586,8 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
     in.cell_rec_off = cro.data();
     in.mode = env.mode;
     in.chunk_bytes = collate_chunk_bytes();
-    in.d_names = a->names.p;
-    in.d_name_off = a->name_off.p + r0;
+    in.d_names = a->names.bytes.p;
+    in.d_name_off = a->names.off.p + r0;
     in.d_secondary = a->sec.p + r0;
     CollateResident cr;
     double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -786,8 +603,8 @@ int BarcodesStream::run_group(const std::shared_ptr<Arena> &a, const std::vector
         slot->cell_pos_off.assign((size_t)n_cells + 1, 0);
         UmiInput um; // the arena's UMIs; the group's window of their offsets is indexed by group-local record
         um.who = who;
-        um.d_umis = a->umis.p;
-        um.d_umi_off = a->umi_off.p + r0;
+        um.d_umis = a->umis.bytes.p;
+        um.d_umi_off = a->umis.off.p + r0;
         if (d_gene_of.p) { // the rule's gene keys: the heads' ref_ids are word 0 of the arena's records
             um.d_ref_id = reinterpret_cast<const uint32_t *>(a->rec.p + r0);
             um.ref_id_stride = sizeof(oem_aln_record) / sizeof(uint32_t);
@@ -899,6 +716,10 @@ void BarcodesStream::process(Batch &b, bool skip)
 {
     if (hipSetDevice(env.device) != hipSuccess) set_stuck(OEM_ERR_HIP, "oem_cells_stream: the parse worker could not select its device");
     std::string msg;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        skip = skip || cancel; // (set before the queue's own flag: cut_groups may have dropped the arena on it already)
+    }
     if (skip || env.sticky(&msg) != OEM_OK) return;
     int rc = OEM_OK;
     try {

@@ -33,6 +33,17 @@ inline void stage_host_free(StageMem &m)
     m = StageMem();
 }
 
+// A staged blob up: d_bytes (n_bytes + 16 + extra_bytes allocated, the 16 bytes behind n_bytes zero) and d_off (n + 1 +
+// extra_off allocated, the n + 1 offsets copied); the flags form: n flags with 8 zero bytes behind them.  The copies
+// are queued on the null stream from memory that stays until the caller has synchronized.
+int upload_blob_async(const uint8_t *h_bytes, uint64_t n_bytes, const uint64_t *h_off, uint64_t n, uint64_t extra_bytes, uint64_t extra_off,
+                      DevBuf<uint8_t> *d_bytes, DevBuf<uint64_t> *d_off);
+int upload_flags_async(const uint8_t *h_sec, uint64_t n, DevBuf<uint8_t> *d_sec);
+
+// *bad = the smallest i = d_order[k], k < m, whose record d_in[i] has a ref_id that is not below n_txps, or kNoRecord: a
+// batch's survivors are checked where the batch still knows its indices
+int records_ref_check(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, uint32_t n_txps, uint64_t *bad);
+
 // The survivors of d_in[0 .. n) (the records without OEM_REC_UNMAPPED): *m of them, and order_parse, their input
 // indices in ascending order.  order_parse is left empty when it would be the identity (m == n) unless `always`.
 int parse_survivors(const oem_aln_record *d_in, uint64_t n, bool always, DevBuf<uint32_t> *d_order_parse, uint64_t *m);

@@ -40,6 +40,7 @@
 #include <cstring>
 #include <vector>
 
+#include "oem_dev_blob.h"
 #include "oem_parse_device.h"
 
 namespace oem {
@@ -116,6 +117,18 @@ __global__ __launch_bounds__(kPT) void k_parse_row_heads(uint64_t n_groups, cons
     if (g < n_groups && n_kept[g]) heads[row_idx[g]] = order[group_off[g]];
 }
 
+// *bad = min(*bad, i) over the records i = order[0 .. cnt) whose ref_id (the low half of a record's first word) is not
+// below n_txps
+__global__ __launch_bounds__(kPT) void k_records_ref_check(uint64_t cnt, const uint32_t *__restrict__ order, const uint64_t *__restrict__ rec_words,
+                                                            uint32_t n_txps, unsigned long long *__restrict__ bad)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * kPT + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t i = order[k];
+    if ((uint32_t)rec_words[(uint64_t)i * 5] >= n_txps) atomicMin(bad, (unsigned long long)i);
+}
+static_assert(offsetof(oem_aln_record, ref_id) == 0 && sizeof(oem_aln_record) == 40, "k_records_ref_check reads ref_id from a record's first word");
+
 template <typename In>
 int exclusive_scan(In in, uint64_t *out, uint64_t n)
 {
@@ -142,6 +155,38 @@ int parse_not_collated(const char *who, uint64_t group, uint64_t record, uint64_
                 "%s: the input is not name-collated: group %llu (first record %llu) has the name of an earlier group (first record %llu); "
                 "OEM_COLLATE_SORT accepts such input",
                 who, (unsigned long long)group, (unsigned long long)record, (unsigned long long)earlier);
+}
+
+int upload_blob_async(const uint8_t *h_bytes, uint64_t n_bytes, const uint64_t *h_off, uint64_t n, uint64_t extra_bytes, uint64_t extra_off,
+                      DevBuf<uint8_t> *d_bytes, DevBuf<uint64_t> *d_off)
+{
+    OEM_TRY(dev_alloc(&d_bytes->p, n_bytes + kBlobPad + extra_bytes, nullptr));
+    OEM_TRY(dev_alloc(&d_off->p, n + 1 + extra_off, nullptr));
+    OEM_HIP(hipMemcpyAsync(d_off->p, h_off, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
+    if (n_bytes) OEM_HIP(hipMemcpyAsync(d_bytes->p, h_bytes, n_bytes, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemsetAsync(d_bytes->p + n_bytes, 0, kBlobPad, nullptr));
+    return OEM_OK;
+}
+
+int upload_flags_async(const uint8_t *h_sec, uint64_t n, DevBuf<uint8_t> *d_sec)
+{
+    OEM_TRY(dev_alloc(&d_sec->p, n + kFlagPad, nullptr)); // (read through aligned 4-byte words: padded)
+    OEM_HIP(hipMemcpyAsync(d_sec->p, h_sec, n, hipMemcpyHostToDevice, nullptr));
+    OEM_HIP(hipMemsetAsync(d_sec->p + n, 0, kFlagPad, nullptr));
+    return OEM_OK;
+}
+
+int records_ref_check(uint64_t m, const uint32_t *d_order, const oem_aln_record *d_in, uint32_t n_txps, uint64_t *bad)
+{
+    DevBuf<unsigned long long> d_bad;
+    unsigned long long b = kNoRecord;
+    OEM_TRY(dev_alloc(&d_bad.p, 1, nullptr));
+    OEM_HIP(hipMemcpy(d_bad.p, &b, sizeof b, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_records_ref_check, grid_for(m), dim3(kPT), 0, nullptr, m, d_order, (const uint64_t *)d_in, n_txps, d_bad.p);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpy(&b, d_bad.p, sizeof b, hipMemcpyDeviceToHost));
+    *bad = b;
+    return OEM_OK;
 }
 
 // The names of the records idx[0 .. k) (input indices) gathered from the resident input into one dense, padded blob on

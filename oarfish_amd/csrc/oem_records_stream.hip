@@ -33,9 +33,9 @@
 //
 // The SORTING NAMES form (oem_records_stream_set_sort; "the sorting names session" in DESIGN.md section 5d) takes records,
 // read names and secondary flags in ANY order.  Nothing can be cut or filtered before the last record is in, so its
-// worker only parses: each batch's survivors -- their records, their dense names with offsets rebased, their flags and
-// their 64-bit session-global indices (k_arena_append) -- are appended to an arena that stays on the device and grows
-// geometrically; finish runs the one call's tail (parse_tail, oem_parse_device.h) on the arena as on an uploaded input.
+// worker only parses: each batch's survivors -- their records, dense names, flags and 64-bit session-global indices --
+// are appended to a SurvivorArena (oem_dev_blob.h), which stays on the device and grows geometrically; finish runs the
+// one call's tail (parse_tail, oem_parse_device.h) on the arena as on an uploaded input.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -45,6 +45,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "oem_dev_blob.h"
 #include "oem_filter_device.h"
 #include "oem_parse_device.h"
 #include "oem_stage_queue.h"
@@ -262,103 +263,7 @@ __global__ __launch_bounds__(kCT) void k_names_row_heads(uint64_t nc, const uint
     if (g < nc && n_kept[g]) out[row_idx[g]] = head[g];
 }
 
-// *bad = min(*bad, i) over the records i = order[0 .. cnt) whose ref_id (the low half of a record's first word) is not
-// below n_txps: the run that goes into the carry is checked where its batch still knows its indices
-__global__ __launch_bounds__(kCT) void k_names_ref_check(uint64_t cnt, const uint32_t *__restrict__ order, const uint64_t *__restrict__ rec_words,
-                                                         uint32_t n_txps, unsigned long long *__restrict__ bad)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * kCT + threadIdx.x;
-    if (k >= cnt) return;
-    const uint32_t i = order[k];
-    if ((uint32_t)rec_words[(uint64_t)i * 5] >= n_txps) atomicMin(bad, (unsigned long long)i);
-}
-
-// ---- the sorting names session: the survivors' arena ----------------------------------------------------------------------
-
-// What a sorting names session keeps on the device until finish: the n survivors of all batches so far in ticket order.
-// recs / idx / sec / off have room for cap survivors (sec 8 bytes and off one entry more), names for byte_cap bytes
-// and 16 more.  off[0] = 0.  rec_held / name_held / peak: the device bytes of the arrays, now and at most (a growing
-// array is held twice while it is copied).
-struct SortArena {
-    DevBuf<oem_aln_record> recs;
-    DevBuf<uint64_t> idx, off;
-    DevBuf<uint8_t> sec, names;
-    uint64_t n = 0, cap = 0, bytes = 0, byte_cap = 0, rec_held = 0, name_held = 0, peak = 0;
-    bool any_sec = false;
-    static uint64_t per_record() { return sizeof(oem_aln_record) + 2 * sizeof(uint64_t) + 1; }
-    void release()
-    {
-        recs.reset();
-        idx.reset();
-        off.reset();
-        sec.reset();
-        names.reset();
-        n = cap = bytes = byte_cap = rec_held = name_held = 0;
-    }
-    // room for n_need survivors and bytes_need name bytes: geometric reallocation, the used part copied on the device
-    int reserve(uint64_t n_need, uint64_t bytes_need)
-    {
-        if (n_need > cap) {
-            const uint64_t nc = std::max<uint64_t>(std::max<uint64_t>(2 * cap, n_need), 1024);
-            const uint64_t grown = nc * per_record() + 16;
-            peak = std::max(peak, rec_held + name_held + grown);
-            DevBuf<oem_aln_record> r2;
-            DevBuf<uint64_t> i2, o2;
-            DevBuf<uint8_t> s2;
-            OEM_TRY(dev_alloc(&r2.p, nc, nullptr));
-            OEM_TRY(dev_alloc(&i2.p, nc, nullptr));
-            OEM_TRY(dev_alloc(&o2.p, nc + 1, nullptr));
-            OEM_TRY(dev_alloc(&s2.p, nc + 8, nullptr));
-            if (n) {
-                OEM_HIP(hipMemcpy(r2.p, recs.p, sizeof(oem_aln_record) * n, hipMemcpyDeviceToDevice));
-                OEM_HIP(hipMemcpy(i2.p, idx.p, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice));
-                OEM_HIP(hipMemcpy(o2.p, off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToDevice));
-                OEM_HIP(hipMemcpy(s2.p, sec.p, n, hipMemcpyDeviceToDevice));
-            } else {
-                OEM_HIP(hipMemset(o2.p, 0, sizeof(uint64_t)));
-            }
-            std::swap(recs.p, r2.p);
-            std::swap(idx.p, i2.p);
-            std::swap(off.p, o2.p);
-            std::swap(sec.p, s2.p);
-            rec_held = grown;
-            cap = nc;
-        }
-        if (bytes_need > byte_cap || !names.p) {
-            const uint64_t bc = std::max<uint64_t>(std::max<uint64_t>(2 * byte_cap, bytes_need), 4096);
-            peak = std::max(peak, rec_held + name_held + bc + 16);
-            DevBuf<uint8_t> n2;
-            OEM_TRY(dev_alloc(&n2.p, bc + 16, nullptr));
-            if (bytes) OEM_HIP(hipMemcpy(n2.p, names.p, bytes, hipMemcpyDeviceToDevice));
-            std::swap(names.p, n2.p);
-            name_held = bc + 16;
-            byte_cap = bc;
-        }
-        return OEM_OK;
-    }
-};
-
-// The per-survivor part of an arena append, one lane per survivor k < m of the batch, which becomes arena record
-// base + k (below cap: checked by the caller, and here):
-//   idx[base + k]     = rec_base + order[k], its session-global input index, 64 bits (order[k] < n_in, the batch's size)
-//   off[base + k + 1] = byte_base + src_off[k + 1]: the batch's dense offsets (from 0) rebased to the arena's blob
-//   sec[base + k]     = src_sec[k] != 0, or 0 for a batch without flags
-// The 40-byte records go through records_gather, the name bytes through k_stream_concat's 16-byte units.
-__global__ __launch_bounds__(kCT) void k_arena_append(uint64_t m, uint64_t n_in, uint64_t base, uint64_t cap, uint64_t rec_base, uint64_t byte_base,
-                                                      const uint32_t *__restrict__ order, const uint64_t *__restrict__ src_off,
-                                                      const uint8_t *__restrict__ src_sec, uint64_t *__restrict__ idx, uint64_t *__restrict__ off,
-                                                      uint8_t *__restrict__ sec)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * kCT + threadIdx.x;
-    if (k >= m || base + k >= cap) return;
-    const uint32_t i = order[k];
-    idx[base + k] = i < n_in ? rec_base + i : kNoRecord;
-    off[base + k + 1] = byte_base + src_off[k + 1];
-    sec[base + k] = src_sec ? (uint8_t)(src_sec[k] != 0) : (uint8_t)0;
-}
-
 inline dim3 names_grid(uint64_t n) { return dim3((unsigned)std::max<uint64_t>((n + kCT - 1) / kCT, 1)); }
-static_assert(offsetof(oem_aln_record, ref_id) == 0, "k_names_ref_check reads ref_id from a record's first word");
 
 } // namespace
 } // namespace oem
@@ -420,7 +325,8 @@ struct oem_records_stream {
 
     // -- the sorting names session (oem_records_stream_set_sort): `named` too ------------------------------------------------
     bool sorting = false;
-    SortArena arena;
+    SurvivorArena arena{1024, 4096, false, false}; // the survivors of all batches so far, in ticket order (the worker's alone)
+    bool any_sec = false;            // a batch has brought flags
     uint64_t arena_peak = 0;         // (mu held) arena.peak as of the last batch
     std::vector<uint64_t> out_order; // what finish leaves for oem_records_stream_order_copy
 
@@ -580,13 +486,8 @@ int oem_records_stream::carry_append(const char *who, uint64_t rec_base, const o
     if (!cnt) return OEM_OK;
     if (carry_n + cnt > 0xffffffffull)
         return fail(OEM_ERR_ARG, "%s: the read that starts at record %llu has more than 2^32 - 1 records", who, (unsigned long long)carry_head);
-    DevBuf<unsigned long long> d_bad;
-    unsigned long long bad = kNoRecord;
-    OEM_TRY(dev_alloc(&d_bad.p, 1, nullptr));
-    OEM_HIP(hipMemcpy(d_bad.p, &bad, sizeof bad, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_names_ref_check, names_grid(cnt), dim3(kCT), 0, nullptr, cnt, d_order, (const uint64_t *)d_in, o.n_txps, d_bad.p);
-    OEM_HIP(hipGetLastError());
-    OEM_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+    uint64_t bad = kNoRecord;
+    OEM_TRY(records_ref_check(cnt, d_order, d_in, o.n_txps, &bad));
     if (bad != kNoRecord) return bad_ref(who, rec_base + bad, h_records[bad].ref_id);
     if (carry_n + cnt > carry_cap) {
         const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * carry_cap, carry_n + cnt), 64);
@@ -751,12 +652,8 @@ int oem_records_stream::run_batch_names(const Batch &b, Piece *out, bool *host)
     DevBuf<uint8_t> d_names;
     DevBuf<uint64_t> d_name_off;
     OEM_TRY(dev_alloc(&d_in.p, n, nullptr));
-    OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16 + L + 16, nullptr));
-    OEM_TRY(dev_alloc(&d_name_off.p, n + 3, nullptr));
     OEM_HIP(hipMemcpyAsync(d_in.p, b.named_records(), sizeof(oem_aln_record) * n, hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemcpyAsync(d_name_off.p, b.name_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
-    if (n_bytes) OEM_HIP(hipMemcpyAsync(d_names.p, b.names(), n_bytes, hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemsetAsync(d_names.p + n_bytes, 0, 16, nullptr));
+    OEM_TRY(upload_blob_async(b.names(), n_bytes, b.name_off(), n, L + 16, 2, &d_names, &d_name_off));
     OEM_HIP(hipMemsetAsync(d_names.p + n_bytes + 16 + L, 0, 16, nullptr));
     if (L) OEM_HIP(hipMemcpyAsync(d_names.p + n_bytes + 16, carry_name.p, L, hipMemcpyDeviceToDevice, nullptr));
     const uint64_t tail[2] = {n_bytes + 16, n_bytes + 16 + L};
@@ -871,17 +768,9 @@ int oem_records_stream::run_batch_sort(const Batch &b)
     DevBuf<uint8_t> d_names, d_sec;
     DevBuf<uint64_t> d_name_off;
     OEM_TRY(dev_alloc(&d_in.p, n, nullptr));
-    OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16, nullptr));
-    OEM_TRY(dev_alloc(&d_name_off.p, n + 1, nullptr));
     OEM_HIP(hipMemcpyAsync(d_in.p, b.named_records(), sizeof(oem_aln_record) * n, hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemcpyAsync(d_name_off.p, b.name_off(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, nullptr));
-    if (n_bytes) OEM_HIP(hipMemcpyAsync(d_names.p, b.names(), n_bytes, hipMemcpyHostToDevice, nullptr));
-    OEM_HIP(hipMemsetAsync(d_names.p + n_bytes, 0, 16, nullptr));
-    if (b.has_sec) { // (read through aligned 4-byte words: padded)
-        OEM_TRY(dev_alloc(&d_sec.p, n + 8, nullptr));
-        OEM_HIP(hipMemcpyAsync(d_sec.p, b.secondary(), n, hipMemcpyHostToDevice, nullptr));
-        OEM_HIP(hipMemsetAsync(d_sec.p + n, 0, 8, nullptr));
-    }
+    OEM_TRY(upload_blob_async(b.names(), n_bytes, b.name_off(), n, 0, 0, &d_names, &d_name_off));
+    if (b.has_sec) OEM_TRY(upload_flags_async(b.secondary(), n, &d_sec));
     OEM_HIP(hipStreamSynchronize(nullptr));
 
     DevBuf<uint32_t> d_order;
@@ -899,33 +788,14 @@ int oem_records_stream::run_batch_sort(const Batch &b)
     OEM_TRY(parse_survivor_names(d_names.p, n_bytes, d_name_off.p, n, dense ? d_order.p : nullptr, m, d_sec.p, &d_dense, &d_dense_off,
                                  &d_dense_sec, &dense_bytes, &bad_record, &zero_byte));
     if (bad_record != kNoRecord) return parse_bad_name(who, zero_byte, b.rec_base + bad_record);
-    {
-        DevBuf<unsigned long long> d_bad;
-        unsigned long long bad = kNoRecord;
-        OEM_TRY(dev_alloc(&d_bad.p, 1, nullptr));
-        OEM_HIP(hipMemcpy(d_bad.p, &bad, sizeof bad, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_names_ref_check, names_grid(m), dim3(kCT), 0, nullptr, m, (const uint32_t *)d_order.p, (const uint64_t *)d_in.p,
-                           o.n_txps, d_bad.p);
-        OEM_HIP(hipGetLastError());
-        OEM_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad != kNoRecord) return bad_ref(who, b.rec_base + bad, b.named_records()[bad].ref_id);
-    }
+    uint64_t bad = kNoRecord;
+    OEM_TRY(records_ref_check(m, d_order.p, d_in.p, o.n_txps, &bad));
+    if (bad != kNoRecord) return bad_ref(who, b.rec_base + bad, b.named_records()[bad].ref_id);
 
-    // the append: records, per-survivor words, name bytes
-    OEM_TRY(arena.reserve(arena.n + m, arena.bytes + dense_bytes));
-    OEM_TRY(records_gather(m, d_order.p, d_in.p, arena.recs.p + arena.n));
     const uint8_t *src_sec = !b.has_sec ? nullptr : dense ? d_dense_sec.p : d_sec.p;
-    hipLaunchKernelGGL(k_arena_append, names_grid(m), dim3(kCT), 0, nullptr, m, n, arena.n, arena.cap, b.rec_base, arena.bytes,
-                       (const uint32_t *)d_order.p, (const uint64_t *)(dense ? d_dense_off.p : d_name_off.p), src_sec, arena.idx.p, arena.off.p,
-                       arena.sec.p);
-    OEM_HIP(hipGetLastError());
-    ConcatPlan plan;
-    plan.add(dense ? d_dense.p : d_names.p, arena.names.p + arena.bytes, dense_bytes, 1, 0);
-    OEM_TRY(plan.run(who, nullptr));
-    OEM_HIP(hipStreamSynchronize(nullptr));
-    arena.n += m;
-    arena.bytes += dense_bytes;
-    arena.any_sec |= b.has_sec;
+    OEM_TRY(arena.append(m, d_order.p, d_in.p, n, b.rec_base, dense ? d_dense.p : d_names.p, dense ? d_dense_off.p : d_name_off.p, dense_bytes,
+                         src_sec, nullptr, nullptr, nullptr, 0));
+    any_sec |= b.has_sec;
     n_parsed += m;
     return OEM_OK;
 }
@@ -946,8 +816,6 @@ int oem_records_stream::finish_sort(const char *who, const oem_store_opts *opts,
         return oem_store_create_records(&f, txp_len.data(), o.n_txps, nullptr, no_groups, 0, o.bin_width, o.model, o.growth_rate, o.device,
                                         opts, nullptr, out_discard, out);
     }
-    OEM_HIP(hipMemset(arena.names.p + arena.bytes, 0, 16));
-    OEM_HIP(hipMemset(arena.sec.p + m, 0, 8));
     double last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     ParseTail t;
     t.who = who;
@@ -963,12 +831,12 @@ int oem_records_stream::finish_sort(const char *who, const oem_store_opts *opts,
     t.device = o.device;
     t.opts = opts;
     t.m = m;
-    t.dense_bytes = arena.bytes;
-    std::swap(t.d_in.p, arena.recs.p);
-    std::swap(t.d_names.p, arena.names.p);
-    std::swap(t.d_name_off.p, arena.off.p);
-    if (arena.any_sec) std::swap(t.d_sec.p, arena.sec.p);
-    t.d_global = arena.idx.p; // (stays the arena's until the tail is over)
+    t.dense_bytes = arena.names.n_bytes;
+    std::swap(t.d_in.p, arena.rec.p); // (the arena's padding is what the tail asks of an uploaded input)
+    std::swap(t.d_names.p, arena.names.bytes.p);
+    std::swap(t.d_name_off.p, arena.names.off.p);
+    if (any_sec) std::swap(t.d_sec.p, arena.sec.p);
+    t.d_global = arena.gidx.p; // (stays the arena's until the tail is over)
     t.want_rows = true;
     t.on_groups = [&](uint64_t ng) {
         out_order.resize(m);
