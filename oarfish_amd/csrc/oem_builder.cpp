@@ -189,8 +189,31 @@ extern "C" int oem_builder_export(const oem_builder *b, uint64_t *row_ptr, uint3
 // ---------------------------------------------------------------------------
 // binomial_probability (binomial_probability.rs:7-168): per-bin Binomial(sum, p_i) pmf at the bin's
 // count after rescaling the counts so that the largest is 709, normalised over the bins.  The f32 /
-// f64 mix of the reference is kept (f32 sums and differences, f64 logs).  ln_gamma: statrs' Lanczos
-// evaluation there, libm's lgamma here (same function, ~1e-15 relative apart).
+// f64 mix of the reference is kept (f32 sums and differences, f64 logs).
+//
+// ln_gamma: statrs::function::gamma::ln_gamma (binomial_probability.rs:4), an 11-term Lanczos sum with g = 10.900511,
+// in its operation order.  libm's lgamma is the same function to an ulp of the result, but ln_gamma(709 n) for a
+// transcript of several hundred bins is 1e7 and its ulp 1e-9 and more of a bin probability.
+static double ln_gamma(double x)
+{
+    static const double kR = 10.900511;
+    static const double kDk[11] = {2.48574089138753565546e-5, 1.05142378581721974210, -3.45687097222016235469,
+                                   4.51227709466894823700, -2.98285225323576655721, 1.05639711577126713077,
+                                   -1.95428773191645869583e-1, 1.70970543404441224307e-2, -5.71926117404305781283e-4,
+                                   4.63399473359905636708e-6, -2.71994908488607703910e-9};
+    static const double kLn2SqrtEOverPi = 0.6207822376352452223455184457816472122518527279025978;
+    static const double kLnPi = 1.1447298858494001741434273513530587116472948129153;
+    static const double kPi = 3.14159265358979323846, kE = 2.71828182845904523536;
+    double s = kDk[0];
+    if (x < 0.5) {
+        for (int i = 1; i < 11; ++i) s += kDk[i] / ((double)i - x);
+        return kLnPi - std::log(std::sin(kPi * x)) - std::log(s) - kLn2SqrtEOverPi -
+               (0.5 - x) * std::log((0.5 - x + kR) / kE);
+    }
+    for (int i = 1; i < 11; ++i) s += kDk[i] / (x + (double)i - 1.0);
+    return std::log(s) + kLn2SqrtEOverPi + (x - 0.5) * std::log((x - 0.5 + kR) / kE);
+}
+
 static int binomial_probability(const std::vector<float> &cnt, const std::vector<float> &len, double distinct_rate,
                                 std::vector<double> &out)
 {
@@ -211,10 +234,10 @@ static int binomial_probability(const std::vector<float> &cnt, const std::vector
         m[i] = cnt[i] == max_val ? (float)kMaxScale : (float)(((double)cnt[i] * kMaxScale) / (double)max_val);
     float sum_vec = 0.0f;
     for (float v : m) sum_vec += v;                                    // :72
-    const double ln1 = std::lgamma((double)sum_vec + 1.0);             // :75
+    const double ln1 = ln_gamma((double)sum_vec + 1.0);             // :75
     double total = 0.0;
     for (size_t i = 0; i < n; ++i) {
-        const double denom = std::lgamma((double)m[i] + 1.0) + std::lgamma((double)(sum_vec - m[i]) + 1.0); // :76-79
+        const double denom = ln_gamma((double)m[i] + 1.0) + ln_gamma((double)(sum_vec - m[i]) + 1.0); // :76-79
         const double num2 = (p[i] > kZero ? std::log(p[i]) : std::log(kZero)) * (double)m[i];              // :82
         const double q = 1.0 - p[i];
         const double num3 = (q > kZero ? std::log(q) : std::log(kZero)) * (double)(sum_vec - m[i]);        // :89

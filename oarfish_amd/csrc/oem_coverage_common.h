@@ -49,6 +49,8 @@ __device__ inline double binomial_bins(const double *tb, uint32_t n, float bwf, 
 {
     // binomial_continuous_prob + binomial_probability (binomial_probability.rs:7-224); tb already holds
     // bins + min_cov.  Two sweeps over the bins recompute the f32 counts rather than store them.
+    // ln_gamma is the device library's lgamma, not the Lanczos sum of statrs that oem_builder.cpp restates: the
+    // device's log is not the host's, so either way the result is an ulp of ln_gamma(709 n) from the reference's.
     const double kZero = 1e-20, kMaxScale = 709.0;
     float count_sum = 0.0f, max_val = 0.0f;
     double distinct_rate = 0.0;

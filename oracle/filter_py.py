@@ -130,6 +130,30 @@ def _f32(x):
     return float(np.float32(x))
 
 
+_GAMMA_R = 10.900511
+_GAMMA_DK = [2.48574089138753565546e-5, 1.05142378581721974210, -3.45687097222016235469, 4.51227709466894823700,
+             -2.98285225323576655721, 1.05639711577126713077, -1.95428773191645869583e-1, 1.70970543404441224307e-2,
+             -5.71926117404305781283e-4, 4.63399473359905636708e-6, -2.71994908488607703910e-9]
+_LN_2_SQRT_E_OVER_PI = 0.6207822376352452223455184457816472122518527279025978
+_LN_PI = 1.1447298858494001741434273513530587116472948129153
+
+
+def ln_gamma(x):
+    """statrs::function::gamma::ln_gamma, the log-gamma binomial_probability.rs:4 imports: an 11-term Lanczos sum
+    (g = 10.900511), with its operation order.  Another log-gamma differs from it by an ulp of the result, which at
+    ln_gamma(709 n) for hundreds of bins is 1e-9 and more of a bin probability."""
+    if x < 0.5:
+        s = _GAMMA_DK[0]
+        for i in range(1, 11):
+            s += _GAMMA_DK[i] / (float(i) - x)
+        return (_LN_PI - math.log(math.sin(math.pi * x)) - math.log(s) - _LN_2_SQRT_E_OVER_PI
+                - (0.5 - x) * math.log((0.5 - x + _GAMMA_R) / math.e))
+    s = _GAMMA_DK[0]
+    for i in range(1, 11):
+        s += _GAMMA_DK[i] / (x + float(i) - 1.0)
+    return math.log(s) + _LN_2_SQRT_E_OVER_PI + (x - 0.5) * math.log((x - 0.5 + _GAMMA_R) / math.e)
+
+
 def binomial_probability(cnt, length, distinct_rate):
     """binomial_probability.rs:7-168 with its f32 / f64 mix (cnt, length: f32 values held as floats)."""
     n = len(cnt)
@@ -146,11 +170,11 @@ def binomial_probability(cnt, length, distinct_rate):
     for v in m:
         sum_vec = np.float32(sum_vec + np.float32(v))                        # :72
     sum_vec = float(sum_vec)
-    ln1 = math.lgamma(sum_vec + 1.0)                                         # :75
+    ln1 = ln_gamma(sum_vec + 1.0)                                         # :75
     res = []
     for pi, mi in zip(p, m):
         rest = _f32(np.float32(sum_vec) - np.float32(mi))                    # (sum_vec - count) in f32
-        denom = math.lgamma(mi + 1.0) + math.lgamma(rest + 1.0)              # :76-79
+        denom = ln_gamma(mi + 1.0) + ln_gamma(rest + 1.0)              # :76-79
         num2 = (math.log(pi) if pi > ZERO else math.log(ZERO)) * mi          # :82
         q = 1.0 - pi
         num3 = (math.log(q) if q > ZERO else math.log(ZERO)) * rest          # :89
@@ -161,7 +185,9 @@ def binomial_probability(cnt, length, distinct_rate):
     return [r / tot for r in res]                                            # :121-137
 
 
-def coverage_probs(st: Store, txp_len, bin_width: int, growth_rate: float, model: str = "logistic"):
+def coverage_bin_probs(st: Store, txp_len, bin_width: int, growth_rate: float, model: str = "logistic"):
+    """The bin probabilities of every transcript (add_interval over the store, then logistic_prob or
+    binomial_continuous_prob): what coverage_probs reads its per-alignment values from."""
     T = len(txp_len)
     bins = [[0.0] * int(math.ceil(float(txp_len[t]) / float(bin_width))) for t in range(T)]
     total_weight = [0.0] * T
@@ -206,6 +232,11 @@ def coverage_probs(st: Store, txp_len, bin_width: int, growth_rate: float, model
             r = 1.0 / (1.0 + math.exp(-growth_rate * diff))
             pr.append(min(max(r, 1e-8), 0.99999))
         prob.append(pr)
+    return prob
+
+
+def coverage_probs(st: Store, txp_len, bin_width: int, growth_rate: float, model: str = "logistic"):
+    prob = coverage_bin_probs(st, txp_len, bin_width, growth_rate, model)
     out = [0.0] * len(st.tid)
     bl = float(bin_width)
     for r in range(len(st.row_ptr) - 1):                         # normalize_read_probs (:5-74)

@@ -1,7 +1,8 @@
 """The store builder: AlignmentFilters::filter + add_filtered_group
 (src/util/oarfish_types.rs:955-1130, :718-738) as oem_builder_* in the C ABI, against a pure-Python
 restatement.  Integer work and f32 probabilities: bit-exact.  Host-only; the last test uploads the
-built store and checks the EM on it."""
+built store and checks the EM on it.
+The coverage model at bin, length and span edges: test_coverage_edges.py (host) and test_coverage_edges_gpu.py."""
 import ctypes as C
 
 import numpy as np
@@ -183,7 +184,7 @@ def test_coverage_model_matches_python_restatement(seed, bin_width, growth):
 def test_binomial_coverage_model_matches_python_restatement(seed, bin_width):
     """The single-cell coverage model (binomial_continuous_prob, binomial_probability.rs:7-224, hook
     single_cell.rs:132-137): same bins and read normalisation, binomial bin probabilities with the
-    reference's f32/f64 mix.  Same operation order, libm lgamma here, CPython's own Lanczos lgamma there (as statrs has its own): 1e-9."""
+    reference's f32/f64 mix.  Same operation order and, on both sides, statrs' Lanczos ln_gamma restated: 1e-9."""
     rng = np.random.default_rng(seed)
     T = 30
     txp_len = rng.integers(400, 4000, size=T)

@@ -1,7 +1,8 @@
 """GPU tests of the per-cell coverage model (oem_coverage_probs_cells_device / cells_coverage_probs): every cell gets
 its own bins, as single_cell.rs:117-137 does -- against the oracle on each cell's own store, against a loop of
 oem_coverage_probs_device over the cells, with the cells cut into many chunks, against the (wrong) whole-store
-binning, end to end into the cells EM, on errors, and at the size of one GPU's slice of BASELINE configs[4]."""
+binning, end to end into the cells EM, on errors, and at the size of one GPU's slice of BASELINE configs[4].
+The per-cell kernels at bin, length and span edges: test_coverage_edges_gpu.py (grid: coverage_edges_common.py)."""
 import os
 
 import numpy as np

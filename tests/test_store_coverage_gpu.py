@@ -2,7 +2,8 @@
 DeviceStore.with_coverage): the store equals oem_coverage_probs_device followed by oem_store_create on that column --
 layout hashes on every layout path and weight coding, the caller-order store, the returned column, the oracle under
 both gates, the steps after the EM, f32 rounding edge cases, the builder variant, errors, the bulk driver and the
-full BASELINE configs[2] size."""
+full BASELINE configs[2] size.
+The whole-store kernels at bin, length and span edges: test_coverage_edges_gpu.py (grid: coverage_edges_common.py)."""
 import ctypes as C
 import json
 import os
