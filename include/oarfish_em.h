@@ -959,6 +959,111 @@ int oem_em_run_cells_records_umis_rule_sparse(
     uint64_t *out_cell_corrected /* capacity n_records, *out_n_cells written; or NULL */,
     oem_cells_result **out);
 
+/* A BARCODE RULE: raw cell barcodes (CR tags) matched against a whitelist, with one-mismatch correction.  The reference
+ * has no counterpart: it wants every record to carry a CORRECTED cell barcode (docs/index.md:308-312), and every other
+ * barcode entry point here compares barcodes as bytes, so that a barcode with one sequencing error would be a cell of its
+ * own.  The rule is oarfish_amd/csrc/oem_barcode_correct.h, whose host walk is the specification the device is held to
+ * exactly.
+ *   - labels / label_off: the whitelist (the chemistry's permit list), n_labels >= 1 distinct labels of 1 .. 64 bytes as
+ *     one blob with n_labels + 1 offsets from 0; a record's id is its label's index.
+ *   - alphabet: NULL for "ACGT", or n_alphabet (1 .. 8) distinct non-zero bytes.
+ *   - exact: a barcode that is byte-identical to label w has id = w and OEM_BARCODE_EXACT.  n(w) is the number of records
+ *     of the call that are exact for w, whatever their flags; a corrected record never adds to it.
+ *   - neighbours of a non-empty barcode b that is not exact: the labels of b's length that differ from b in exactly one
+ *     byte position AND whose byte at that position is in the alphabet.  b's own byte there may be anything (an N is
+ *     handled, two Ns have no neighbour); a label byte outside the alphabet is only ever matched exactly.
+ *   - no neighbour: OEM_BARCODE_NO_NEIGHBOUR.  multi = 0 (STARsolo's 1MM): exactly one neighbour gives
+ *     OEM_BARCODE_CORRECTED to it, more than one OEM_BARCODE_AMBIGUOUS.  multi = 1: one neighbour gives
+ *     OEM_BARCODE_CORRECTED to it whatever its n; of several the one whose n(w) is strictly largest wins, a tie for the
+ *     largest is OEM_BARCODE_AMBIGUOUS.
+ *   - an empty barcode (no tag) is OEM_BARCODE_MISSING: not the error it is for the calls that take corrected barcodes.
+ *   - NO_NEIGHBOUR, AMBIGUOUS and MISSING records are REJECTED: id = OEM_BARCODE_NO_ID, and they belong to no cell.
+ *   - a cell is the accepted records of one label.  Cells are numbered by their first accepted record in input order and
+ *     records keep input order inside a cell: oem_collate_barcodes' numbering, so input that holds only whitelisted
+ *     barcodes gives exactly that call's order / cell_rec_off.  A cell's label is the whitelist's bytes, labels[id of the
+ *     cell's first record], not any record's.
+ * The result never depends on a hash, on probe order or on the arrival order of atomics.  Limits, on purpose: no base
+ * qualities (Cell Ranger's posterior needs them), no indels, no knee; the barcoded sessions do not take the rule yet. */
+typedef struct {
+    const uint8_t *labels; const uint64_t *label_off; uint32_t n_labels;
+    uint32_t multi;            /* 0, 1 */
+    const uint8_t *alphabet;   /* NULL: "ACGT" */
+    uint32_t n_alphabet, reserved;
+} oem_barcode_rule;
+
+#define OEM_BARCODE_EXACT 0
+#define OEM_BARCODE_CORRECTED 1
+#define OEM_BARCODE_NO_NEIGHBOUR 2
+#define OEM_BARCODE_AMBIGUOUS 3
+#define OEM_BARCODE_MISSING 4
+#define OEM_BARCODE_NO_ID 0xffffffffu
+
+/* The composable step, as oem_collate_barcodes is for corrected barcodes: the rule above on the device.  barcodes /
+ * barcode_off: one raw barcode per record, as oem_collate_barcodes takes them, the empty string where the tag is missing.
+ * out_id (n_records) and out_status (n_records): every record's label and OEM_BARCODE_* code.  out_order (capacity
+ * n_records; *out_n_accepted entries are written) and out_cell_rec_off (capacity n_records + 1; *out_n_cells + 1 entries
+ * are written) are the cells of the accepted records, positions counting accepted records only.  out_counts (5): the
+ * records of every status code.  Any output but the two scalars may be NULL.
+ *
+ * OEM_ERR_ARG before any device use: rule, labels or label_off NULL; n_labels == 0; label_off not from 0 or decreasing; an
+ * empty label; a label of more than 64 bytes; multi > 1; an alphabet that is empty, longer than 8 bytes or holds a
+ * repeated or a 0 byte; barcode_off, out_n_cells or out_n_accepted NULL; oem_collate_barcodes' checks and limits on
+ * barcodes, barcode_off and n_records.  OEM_ERR_ARG found on the device, in this order: a label that holds a 0 byte
+ * (naming the smallest such label); two equal labels (naming i < j, the smallest pair with i first, i being the first
+ * label with those bytes); a barcode that holds a 0 byte (naming the smallest such record).  The outputs are then
+ * unspecified.  Resident during the call: the whitelist (its labels and 4 bytes a slot of a table of at least 2
+ * n_labels slots, 4 bytes a label of counts), the barcodes, and 13 bytes a record.  Running out of device memory is
+ * OEM_ERR_OOM with everything released.  Without a device: OEM_ERR_NO_DEVICE. */
+int oem_correct_barcodes(const oem_barcode_rule *rule,
+                         const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records, int device,
+                         uint32_t *out_id            /* n_records, or NULL */,
+                         uint8_t *out_status         /* n_records, or NULL */,
+                         uint32_t *out_order         /* capacity n_records, *out_n_accepted written; or NULL */,
+                         uint64_t *out_cell_rec_off  /* capacity n_records + 1, *out_n_cells + 1 written; or NULL */,
+                         uint64_t *out_n_cells, uint64_t *out_n_accepted,
+                         uint64_t *out_counts        /* 5, indexed by OEM_BARCODE_*; or NULL */);
+
+/* oem_em_run_cells_records_umis_rule_sparse on RAW barcodes: from a sequencer's records to the cells' counts in one
+ * call.  The arguments and outputs are that call's, with the barcode rule in front; umis / umi_off may both be NULL,
+ * meaning no deduplication (umi_rule is then checked and otherwise unused).  Three outputs are added: out_wl_id
+ * (n_records) and out_status (n_records) as oem_correct_barcodes gives them, and out_counts (5).
+ *
+ * The result is what the caller gets by joining five steps: oem_correct_barcodes; the rejected records dropped on the
+ * host from records, names, secondary and umis; the accepted records given their labels' bytes as barcodes;
+ * oem_em_run_cells_records_umis_rule_sparse on that input (with every UMI empty where umis is NULL); its out_order mapped
+ * back to the caller's input indices.  Exactly equal to that join: every index array and count, out_kept, every table of
+ * oem_cells_result_discard_tables, out_cell_dups, out_cell_corrected and the entries' columns; the entries' values and
+ * the infos are equal as that call states it.  out_order holds indices of the CALLER's input; *out_n_survivors, the
+ * capacities and the offsets count accepted records only.  Input that is rejected entirely gives zero cells and an empty
+ * result, not an error.
+ *
+ * A REJECTED RECORD'S NAME, UMI AND ref_id ARE NEVER LOOKED AT: the rejected records go up with the rest and are never
+ * gathered, so an empty name, a 0 byte in a name or UMI, or a ref_id that is not below n_txps is no error on a rejected
+ * record.  On an accepted record they are the errors of the umis call, found on the device and naming the record by its
+ * index in the caller's input.  Errors otherwise: oem_correct_barcodes' on the rule and the barcodes, then that call's.
+ * Resident beyond what that call holds: the whitelist and 5 bytes a record while the cells are found.  *out = NULL on any
+ * failure. */
+int oem_em_run_cells_records_whitelist_sparse(
+    const oem_barcode_rule *rule,
+    const oem_umi_rule *umi_rule /* or NULL */,
+    const oem_filters *filters, const uint64_t *txp_len, uint32_t n_txps,
+    const oem_aln_record *records, uint64_t n_records,
+    const uint8_t *barcodes, const uint64_t *barcode_off,
+    const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary /* or NULL */,
+    const uint8_t *umis /* or NULL */, const uint64_t *umi_off /* or NULL */,
+    uint32_t mode, uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+    uint32_t *out_order /* capacity n_records, *out_n_survivors written; or NULL */, uint64_t *out_n_survivors /* or NULL */,
+    uint64_t *out_cell_rec_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_cells /* or NULL */,
+    uint64_t *out_group_off /* capacity n_records + 1, or NULL */, uint64_t *out_n_groups /* or NULL */,
+    uint64_t *out_cell_group_off /* capacity n_records + 1, or NULL */,
+    uint32_t *out_kept /* capacity n_records, or NULL */,
+    uint64_t *out_cell_dups /* capacity n_records, *out_n_cells written; or NULL */,
+    uint64_t *out_cell_corrected /* capacity n_records, *out_n_cells written; or NULL */,
+    uint32_t *out_wl_id /* n_records, or NULL */,
+    uint8_t *out_status /* n_records, or NULL */,
+    uint64_t *out_counts /* 5, or NULL */,
+    oem_cells_result **out);
+
 /* The bulk parser and oem_store_create_records in one call: parse_alignments (alignment_parser.rs:301-437) from the
  * records and read names as a BAM reader produces them, in input order, to the resident store.  records (n_records),
  * names / name_off and secondary are oem_collate_names' per-record arrays; the rule is oarfish_amd/csrc/oem_collate.h

@@ -59,6 +59,8 @@ OEM_INFO_RUN_HISTORY_STORED = 4
 OEM_TEXT_INFO_CONTENT_BYTES = 1
 OEM_TEXT_INFO_BLOCKS = 2
 OEM_TEXT_INFO_RAW_BLOCKS = 3
+OEM_BARCODE_EXACT, OEM_BARCODE_CORRECTED, OEM_BARCODE_NO_NEIGHBOUR, OEM_BARCODE_AMBIGUOUS, OEM_BARCODE_MISSING = range(5)
+OEM_BARCODE_NO_ID = 0xFFFFFFFF
 OEM_COLLATE_SORT = 0
 OEM_COLLATE_ADJACENT = 1
 
@@ -85,6 +87,7 @@ ABI_SYMBOLS = [
     "oem_em_run_cells_records_names_sparse", "oem_collate_barcodes", "oem_em_run_cells_records_barcodes_sparse",
     "oem_dedup_umis", "oem_em_run_cells_records_umis_sparse",
     "oem_dedup_umis_rule", "oem_em_run_cells_records_umis_rule_sparse",
+    "oem_correct_barcodes", "oem_em_run_cells_records_whitelist_sparse",
     "oem_cells_stream_create", "oem_cells_stream_push", "oem_cells_stream_set_filters", "oem_cells_stream_push_records",
     "oem_cells_stream_set_barcodes", "oem_cells_stream_push_barcodes", "oem_cells_stream_barcodes_dims",
     "oem_cells_stream_barcodes_copy", "oem_cells_stream_set_barcodes_any_order",
@@ -270,6 +273,8 @@ def _load(path: str) -> C.CDLL:
                                                        vp, C.POINTER(vp)]
     L.oem_dedup_umis_rule.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, i32, vp, vp, vp, vp]
     L.oem_em_run_cells_records_umis_rule_sparse.argtypes = [vp] + L.oem_em_run_cells_records_umis_sparse.argtypes[:-1] + [vp, C.POINTER(vp)]
+    L.oem_correct_barcodes.argtypes = [vp, vp, vp, u64, i32, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
+    L.oem_em_run_cells_records_whitelist_sparse.argtypes = [vp] + L.oem_em_run_cells_records_umis_rule_sparse.argtypes[:-1] + [vp, vp, vp, C.POINTER(vp)]
     L.oem_store_create_records_names.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, u32, u64, u32, i32, f64, i32, vp, vp, vp, vp, vp,
                                                  vp, vp, vp, C.POINTER(vp)]
     L.oem_cells_stream_set_filters.argtypes = [vp, vp, vp]
@@ -363,6 +368,7 @@ def testing_lib() -> C.CDLL:
         L.oem_test_dedup_umis_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp]
         L.oem_test_dedup_umis_rule_host.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp, vp]
         L.oem_debug_dedup_rule_last_call.argtypes = [vp]
+        L.oem_test_correct_barcodes_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
         L.oem_test_cells_gene_counts_host.argtypes = [vp, u32, vp, vp, vp, u32, u32, C.POINTER(vp)]
         L.oem_debug_gene_counts_last_call.argtypes = [vp]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]

@@ -141,6 +141,14 @@ void barcode_table_last(uint64_t *out8)
     std::memcpy(out8, g_table_last, sizeof g_table_last);
 }
 
+int barcode_table_insert(uint64_t first, uint64_t cnt, uint32_t *d_slot, uint64_t capacity, uint32_t hash_bits, const uint8_t *d_labels,
+                         const uint64_t *d_label_off, unsigned long long *d_stats)
+{
+    hipLaunchKernelGGL(k_barcode_insert, grid_of(cnt), dim3(kIT), 0, nullptr, first, cnt, d_slot, capacity, hash_bits, d_labels, d_label_off, d_stats);
+    OEM_HIP(hipGetLastError());
+    return OEM_OK;
+}
+
 int BarcodeIntern::init()
 {
     uint64_t cap = 2;
@@ -237,9 +245,7 @@ int BarcodeIntern::batch(const char *who, const uint8_t *d_bc, const uint64_t *d
         max_doublings = std::max(max_doublings, doublings);
     }
     // 4. the insert
-    hipLaunchKernelGGL(k_barcode_insert, grid_of(n_labels - from), dim3(kIT), 0, nullptr, from, n_labels - from, slot.p, capacity, hash_bits,
-                       (const uint8_t *)labels.bytes.p, (const uint64_t *)labels.off.p, stats.p);
-    OEM_HIP(hipGetLastError());
+    OEM_TRY(barcode_table_insert(from, n_labels - from, slot.p, capacity, hash_bits, labels.bytes.p, labels.off.p, stats.p));
     // 5. the misses again
     hipLaunchKernelGGL(k_barcode_lookup, grid_of(n_miss + 1), dim3(kIT), 0, nullptr, n_miss, (const uint32_t *)d_idx.p, d_bc, d_bc_off,
                        (const uint32_t *)slot.p, capacity, hash_bits, (const uint8_t *)labels.bytes.p, (const uint64_t *)labels.off.p, n_labels, 1u,

@@ -69,6 +69,11 @@ struct BarcodeIntern {
 // the last finished any-order session's table (8 words): [0] rebuilds, [1] the longest probe, [2] a probe wrapped past the
 // table's end, [3] the most doublings one rebuild covered, [4] the final capacity, [5] labels, [6] misses
 void barcode_table_last(uint64_t *out8);
+// k_barcode_insert for a table that is built elsewhere (the whitelist of oem_barcode_correct.hip): the labels [first,
+// first + cnt) of a padded label blob, distinct or not, into the first free slots of their probe paths.  d_stats: three
+// words -- the longest probe, a probe wrapped, a probe went round the table.  Queued on the null stream.
+int barcode_table_insert(uint64_t first, uint64_t cnt, uint32_t *d_slot, uint64_t capacity, uint32_t hash_bits, const uint8_t *d_labels,
+                         const uint64_t *d_label_off, unsigned long long *d_stats);
 // d_out[k] = d_in[0] + ... + d_in[k - 1] over n entries, in 64 bits (oem_cells_barcodes_stream.hip); leaves the null stream idle
 int exclusive_scan_u32(const uint32_t *d_in, uint64_t *d_out, uint64_t n);
 

@@ -46,6 +46,12 @@
 // order, group_off and cell_group_off are replaced by the deduplicated ones, so the duplicates' records are never
 // gathered and the filter sees the survivors only.  A group's place in the call's order is then known only when every
 // group before it is done: its order waits in its slot like kept and group_off.
+//
+// oem_em_run_cells_records_whitelist_sparse is that call on RAW barcodes: order_bc and cell_rec_off come from
+// correct_barcodes_resident (oem_barcode_correct.hip) and describe the ACCEPTED records only.  The whole input still goes
+// up once and in input order, but from there on the positions (cro[n_cells], accepted records) and the records (n,
+// resident, indexed by order_bc's entries) are two numbers; a rejected record is never gathered, and because nothing of
+// it may be looked at, names and UMIs are validated over order_bc instead of behind their upload chunks.
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -55,6 +61,7 @@
 #include <new>
 #include <vector>
 
+#include "oem_barcode_correct.h"
 #include "oem_cells.h"
 #include "oem_cells_barcodes_stream.h"
 #include "oem_collate_device.h"
@@ -800,7 +807,8 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
                                        uint32_t bin_width, int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
                                        uint32_t *out_order, uint64_t *out_n_survivors, uint64_t *out_cell_rec_off, uint64_t *out_n_cells,
                                        uint64_t *out_group_off, uint64_t *out_n_groups, uint64_t *out_cell_group_off, uint32_t *out_kept,
-                                       uint64_t *out_cell_dups, uint64_t *out_cell_corrected, oem_cells_result **out)
+                                       uint64_t *out_cell_dups, uint64_t *out_cell_corrected, const oem_barcode_rule *wl_rule,
+                                       uint32_t *out_wl_id, uint8_t *out_status, uint64_t *out_counts, oem_cells_result **out)
 {
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -813,6 +821,7 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
     // any device use
     OEM_TRY(check_store_from_records(who, filters, txp_len, n_txps, bin_width, model, nullptr));
     if (!barcode_off || !name_off) return fail(OEM_ERR_ARG, "%s: barcode_off or name_off is NULL", who);
+    if (wl_rule) OEM_TRY(check_barcode_rule(who, wl_rule));
     OEM_TRY(check_barcode_input(who, barcodes, barcode_off, n_records));
     const uint64_t n = n_records, one_cell[2] = {0, n};
     OEM_TRY(check_collate_input(who, names, name_off, n, one_cell, 1, mode));
@@ -829,7 +838,7 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
         if (gene_of && rule->n_txps != n_txps)
             return fail(OEM_ERR_ARG, "%s: rule->n_txps = %u is not n_txps = %u", who, rule->n_txps, n_txps);
     }
-    const bool dedup = with_umis && n && umi_off[n] > 0;
+    bool dedup = with_umis && n && umi_off[n] > 0;
     if (model >= 0) OEM_TRY(check_cells_coverage_args(who, bin_width, model, n_txps, 0, 0));
     OEM_TRY(ensure_device(device));
     RecordsFilter rf;
@@ -850,14 +859,46 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
     double last[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bc_info[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bc_cells_ms = 0;
     std::memset(g_cells_barcodes_last, 0, sizeof g_cells_barcodes_last);
 
-    // the cells: order_bc and cell_rec_off stay on the device, the offsets come down for the cut
+    // the cells: order_bc and cell_rec_off stay on the device, the offsets come down for the cut.  Under a barcode rule
+    // they are the cells of the ACCEPTED records: from here on the POSITIONS (na = cro[n_cells], what order_bc holds and
+    // every offset counts) and the RECORDS (n, resident in input order and indexed by order_bc's entries) are two numbers.
     BarcodeCells bc;
     std::vector<uint64_t> cro(1, 0), cell_name_off(1, 0);
+    uint64_t na = n;
     auto t0 = clk::now();
-    if (n) {
+    if (n && wl_rule) {
+        CorrectedCells cor;
+        {
+            BarcodeWhitelist wl; // released before the records go up
+            OEM_TRY(whitelist_build(who, wl_rule, &wl));
+            OEM_TRY(correct_barcodes_resident(who, wl, barcodes, barcode_off, n, &cor));
+        }
+        na = cor.n_accepted;
+        std::vector<uint8_t> status;
+        if (out_status || dedup) {
+            status.resize(n);
+            OEM_HIP(hipMemcpy(status.data(), cor.status.p, n, hipMemcpyDeviceToHost));
+        }
+        if (out_wl_id) OEM_HIP(hipMemcpy(out_wl_id, cor.id.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        if (out_status) std::copy(status.begin(), status.end(), out_status);
+        if (out_counts) std::copy(cor.counts, cor.counts + kBarcodeStatuses, out_counts);
+        if (dedup) { // the UMIs of rejected records take no part: accepted UMIs that are all empty deduplicate nothing
+            dedup = false;
+            for (uint64_t i = 0; i < n && !dedup; ++i) dedup = status[i] <= kBarcodeCorrected && umi_off[i + 1] > umi_off[i];
+        }
+        std::swap(bc.order.p, cor.cells.order.p);
+        std::swap(bc.cell_rec_off.p, cor.cells.cell_rec_off.p);
+        bc.n_cells = cor.cells.n_cells;
+        if (na) {
+            cro.resize(bc.n_cells + 1);
+            OEM_HIP(hipMemcpy(cro.data(), bc.cell_rec_off.p, sizeof(uint64_t) * (bc.n_cells + 1), hipMemcpyDeviceToHost));
+        }
+    } else if (n) {
         OEM_TRY(collate_barcodes_resident(who, barcodes, barcode_off, n, timing, bc_info, &bc_cells_ms, &bc));
         cro.resize(bc.n_cells + 1);
         OEM_HIP(hipMemcpy(cro.data(), bc.cell_rec_off.p, sizeof(uint64_t) * (bc.n_cells + 1), hipMemcpyDeviceToHost));
+    } else if (out_counts && wl_rule) {
+        std::fill(out_counts, out_counts + kBarcodeStatuses, 0ull);
     }
     bc_info[2] = bc_cells_ms;
     collate_barcodes_set_last(bc_info);
@@ -870,7 +911,7 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
     DevBuf<uint8_t> d_names, d_sec, d_umis;
     DevBuf<uint64_t> d_name_off, d_gathered_off, d_cell_name_off, d_umi_off;
     t0 = clk::now();
-    if (n) {
+    if (na) {
         const uint64_t n_bytes = name_off[n], chunk_bytes = collate_chunk_bytes();
         DevBuf<unsigned long long> d_bad;
         OEM_TRY(dev_alloc(&d_names.p, n_bytes + 16, nullptr));
@@ -892,6 +933,7 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
         float ms[6] = {0, 0, 0, 0, 0, 0};
         OEM_TRY(filter_upload_measure<uint8_t>(names, d_names.p, byte_cut.data(), byte_cut.size() - 1, 1, timing ? ms : nullptr,
                                                [&](hipStream_t lane, uint64_t g0, uint64_t) {
+                                                   if (wl_rule) return; // a rejected record's name is never looked at
                                                    launch_collate_validate(lane, d_names.p, byte_cut[g0], byte_cut[g0 + 1], d_name_off.p,
                                                                            rec_cut[g0], rec_cut[g0 + 1], d_bad.p);
                                                }));
@@ -899,6 +941,7 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
         last[7] = ms[1];
         unsigned long long bad[2];
         OEM_HIP(hipMemcpy(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
+        if (wl_rule) OEM_TRY(validate_records_of(bc.order.p, na, d_names.p, d_name_off.p, bad));
         if (bad[0] != kNoRecord || bad[1] != kNoRecord) {
             if (bad[1] < bad[0]) return fail(OEM_ERR_ARG, "%s: record %llu has an empty name", who, bad[1]);
             return fail(OEM_ERR_ARG, "%s: the name of record %llu contains a 0 byte", who, bad[0]);
@@ -908,12 +951,17 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
             OEM_HIP(hipMemset(d_sec.p + n, 0, 8));
             OEM_HIP(hipMemcpy(d_sec.p, secondary, n, hipMemcpyHostToDevice));
         }
-        if (dedup) OEM_TRY(umis_upload(who, umis, umi_off, n, &d_umis, &d_umi_off));
+        if (dedup) OEM_TRY(umis_upload(who, umis, umi_off, n, &d_umis, &d_umi_off, wl_rule == nullptr));
+        if (dedup && wl_rule) { // ... nor is its UMI
+            unsigned long long bad_umi[2];
+            OEM_TRY(validate_records_of(bc.order.p, na, d_umis.p, d_umi_off.p, bad_umi));
+            if (bad_umi[0] != kNoRecord) return fail(OEM_ERR_ARG, "%s: the UMI of record %llu contains a 0 byte", who, bad_umi[0]);
+        }
         OEM_TRY(upload_records(records, n, d_records.p));
         last[3] = ms_since(t0);
         t0 = clk::now();
-        OEM_TRY(dev_alloc(&d_gathered_off.p, n + 1, nullptr));
-        OEM_TRY(gather_name_offsets(bc.order.p, n, d_name_off.p, d_gathered_off.p));
+        OEM_TRY(dev_alloc(&d_gathered_off.p, na + 1, nullptr));
+        OEM_TRY(gather_name_offsets(bc.order.p, na, d_name_off.p, d_gathered_off.p));
         OEM_TRY(dev_alloc(&d_cell_name_off.p, (size_t)n_cells + 1, nullptr));
         hipLaunchKernelGGL(k_sample_offsets, dim3((n_cells + 1 + kGT - 1) / kGT), dim3(kGT), 0, nullptr, (uint64_t)n_cells + 1,
                            (const uint64_t *)bc.cell_rec_off.p, (const uint64_t *)d_gathered_off.p, d_cell_name_off.p);
@@ -990,9 +1038,9 @@ static int cells_records_barcodes_call(const char *who, const oem_filters *filte
         umis_call_outputs(groups, slots, out_order, out_n_survivors, out_cell_rec_off, out_group_off, out_n_groups, out_cell_group_off, out_kept,
                           out_cell_dups, out_cell_corrected);
     } else {
-        names_call_outputs(groups, slots, cro.data(), n, out_group_off, out_n_groups, out_cell_group_off, out_kept);
+        names_call_outputs(groups, slots, cro.data(), na, out_group_off, out_n_groups, out_cell_group_off, out_kept);
         if (out_cell_rec_off) std::memcpy(out_cell_rec_off, cro.data(), sizeof(uint64_t) * ((size_t)n_cells + 1));
-        if (out_n_survivors) *out_n_survivors = n;
+        if (out_n_survivors) *out_n_survivors = na;
         if (out_cell_dups) std::fill(out_cell_dups, out_cell_dups + n_cells, 0ull);
         if (out_cell_corrected) std::fill(out_cell_corrected, out_cell_corrected + n_cells, 0ull);
     }
@@ -1016,7 +1064,7 @@ extern "C" int oem_em_run_cells_records_barcodes_sparse(const oem_filters *filte
     return cells_records_barcodes_call("oem_em_run_cells_records_barcodes_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
                                        barcode_off, names, name_off, secondary, false, nullptr, nullptr, nullptr, mode, bin_width, model, growth_rate,
                                        device, max_iter, conv_thresh, out_order, nullptr, out_cell_rec_off, out_n_cells, out_group_off,
-                                       out_n_groups, out_cell_group_off, out_kept, nullptr, nullptr, out);
+                                       out_n_groups, out_cell_group_off, out_kept, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out);
     OEM_API_END("oem_em_run_cells_records_barcodes_sparse")
 }
 
@@ -1034,7 +1082,7 @@ extern "C" int oem_em_run_cells_records_umis_sparse(const oem_filters *filters, 
     return cells_records_barcodes_call("oem_em_run_cells_records_umis_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
                                        barcode_off, names, name_off, secondary, true, nullptr, umis, umi_off, mode, bin_width, model, growth_rate,
                                        device, max_iter, conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off,
-                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, nullptr, out);
+                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, nullptr, nullptr, nullptr, nullptr, nullptr, out);
     OEM_API_END("oem_em_run_cells_records_umis_sparse")
 }
 
@@ -1053,8 +1101,33 @@ extern "C" int oem_em_run_cells_records_umis_rule_sparse(const oem_umi_rule *rul
     return cells_records_barcodes_call("oem_em_run_cells_records_umis_rule_sparse", filters, txp_len, n_txps, records, n_records, barcodes,
                                        barcode_off, names, name_off, secondary, true, rule, umis, umi_off, mode, bin_width, model, growth_rate,
                                        device, max_iter, conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off,
-                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, out_cell_corrected, out);
+                                       out_n_groups, out_cell_group_off, out_kept, out_cell_dups, out_cell_corrected, nullptr, nullptr, nullptr, nullptr, out);
     OEM_API_END("oem_em_run_cells_records_umis_rule_sparse")
+}
+
+extern "C" int oem_em_run_cells_records_whitelist_sparse(const oem_barcode_rule *rule, const oem_umi_rule *umi_rule, const oem_filters *filters,
+                                                         const uint64_t *txp_len, uint32_t n_txps, const oem_aln_record *records,
+                                                         uint64_t n_records, const uint8_t *barcodes, const uint64_t *barcode_off,
+                                                         const uint8_t *names, const uint64_t *name_off, const uint8_t *secondary,
+                                                         const uint8_t *umis, const uint64_t *umi_off, uint32_t mode, uint32_t bin_width,
+                                                         int model, double growth_rate, int device, uint32_t max_iter, double conv_thresh,
+                                                         uint32_t *out_order, uint64_t *out_n_survivors, uint64_t *out_cell_rec_off,
+                                                         uint64_t *out_n_cells, uint64_t *out_group_off, uint64_t *out_n_groups,
+                                                         uint64_t *out_cell_group_off, uint32_t *out_kept, uint64_t *out_cell_dups,
+                                                         uint64_t *out_cell_corrected, uint32_t *out_wl_id, uint8_t *out_status,
+                                                         uint64_t *out_counts, oem_cells_result **out)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_em_run_cells_records_whitelist_sparse";
+    if (out) *out = nullptr;
+    if (!rule) return fail(OEM_ERR_ARG, "%s: the barcode rule is NULL", who);
+    if (umis && !umi_off) return fail(OEM_ERR_ARG, "%s: umis is given and umi_off is NULL", who);
+    return cells_records_barcodes_call(who, filters, txp_len, n_txps, records, n_records, barcodes, barcode_off, names, name_off, secondary,
+                                       umi_off != nullptr, umi_rule, umis, umi_off, mode, bin_width, model, growth_rate, device, max_iter,
+                                       conv_thresh, out_order, out_n_survivors, out_cell_rec_off, out_n_cells, out_group_off, out_n_groups,
+                                       out_cell_group_off, out_kept, out_cell_dups, out_cell_corrected, rule, out_wl_id, out_status, out_counts,
+                                       out);
+    OEM_API_END("oem_em_run_cells_records_whitelist_sparse")
 }
 
 extern "C" int oem_cells_result_discard_tables(const oem_cells_result *r, oem_discard_table *out)

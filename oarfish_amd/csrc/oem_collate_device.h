@@ -66,6 +66,44 @@ int collate_barcodes_device(const char *who, const uint8_t *d_barcodes, const ui
                             BarcodeCells *out, DevBuf<uint32_t> *out_heads);
 // The argument checks of oem_collate_barcodes on the input side, before any device use.
 int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records);
+// The tail of the two calls above, for runs that come from elsewhere (the corrected barcodes, oem_barcode_correct.hip):
+// d_sorted holds n positions' records run by run, input order inside a run; d_run_off (n_runs + 1, from 0) the runs'
+// first positions; every record is below n_input.  The runs are ranked by their first record and laid out in that rank.
+// On the null stream, which is left idle.
+int barcode_cells_from_runs(uint64_t n, uint64_t n_runs, uint64_t n_input, const uint32_t *d_sorted, const uint64_t *d_run_off,
+                            BarcodeCells *out, DevBuf<uint32_t> *out_heads);
+
+// ---- barcode correction against a whitelist (oem_barcode_correct.hip; the rule is oem_barcode_correct.h's)
+// The whitelist of a call on the device: its labels as a padded blob, the table over them, n(w), and the rule's words.
+struct BarcodeWhitelist {
+    DevBuf<uint32_t> slot, count;    // capacity slots; n_labels counts, 0 until a call's exact pass
+    DevBuf<uint8_t> labels;          // padded by 16
+    DevBuf<uint64_t> label_off;      // n_labels + 1
+    DevBuf<unsigned long long> bad;  // the kernels' error words
+    uint64_t capacity = 0, n_labels = 0, len_mask = 0, alphabet = 0; // alphabet: its bytes as one word, byte 0 in the low bits
+    uint32_t n_alphabet = 0, multi = 0, hash_bits = 64;
+};
+// What correct_barcodes_resident leaves on the device: id and status of every record, and the cells of the accepted ones
+// (cells.order: n_accepted input indices; cells.cell_rec_off: n_cells + 1 positions).  With n_accepted == 0 there are no
+// cells and cells' buffers are empty.
+struct CorrectedCells {
+    BarcodeCells cells;
+    DevBuf<uint32_t> id;
+    DevBuf<uint8_t> status;
+    uint64_t n_accepted = 0, n_misses = 0, counts[5] = {0, 0, 0, 0, 0}; // counts: by status (kBarcodeStatuses)
+};
+// oem_correct_barcodes' checks of its rule before any device use
+int check_barcode_rule(const char *who, const oem_barcode_rule *rule);
+// The checked rule's whitelist up and its table built; a label with a 0 byte and two equal labels are OEM_ERR_ARG.
+int whitelist_build(const char *who, const oem_barcode_rule *rule, BarcodeWhitelist *wl);
+// The barcodes of n_records records (checked by check_barcode_input) against the whitelist; a barcode with a 0 byte is
+// OEM_ERR_ARG naming the smallest such record, an empty one is kBarcodeMissing.  One call per BarcodeWhitelist: n(w) is
+// counted into it.  Returns with the device idle and only `out` held.
+int correct_barcodes_resident(const char *who, const BarcodeWhitelist &wl, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n,
+                              CorrectedCells *out);
+// The records d_order[0 .. m) of a resident padded blob with its offsets: bad2[0] = the smallest with a 0 byte, bad2[1] =
+// the smallest without a byte, ~0 where there is none.  The records that are not in d_order are not looked at.
+int validate_records_of(const uint32_t *d_order, uint64_t m, const uint8_t *d_blob, const uint64_t *d_off, unsigned long long *bad2);
 
 // The names of the records order[0 .. m) (indices into the whole input's d_name_off, n + 1 offsets into d_names, which
 // is 8-byte aligned and padded) gathered into one dense blob: d_out_off (m + 1, from 0: the scan of the lengths, filled
@@ -132,8 +170,10 @@ struct UmiMarks {
     uint32_t bad_ref_id = 0;
 };
 // The UMIs (checked: umi_off from 0, non-decreasing) up through the upload lanes, validated behind their chunks: a 0 byte
-// is OEM_ERR_ARG naming the smallest such input index, an empty UMI is legal.
-int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, uint64_t n, DevBuf<uint8_t> *d_umis, DevBuf<uint64_t> *d_umi_off);
+// is OEM_ERR_ARG naming the smallest such input index, an empty UMI is legal.  validate == false: nothing is looked at
+// (the whitelist call, which validates the accepted records only; raw barcodes, which their own kernel checks).
+int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, uint64_t n, DevBuf<uint8_t> *d_umis, DevBuf<uint64_t> *d_umi_off,
+                bool validate = true);
 // A session's batch (oem_cells_barcodes_stream.hip), whose UMIs are resident (d_umis padded by 16, n + 1 offsets): the
 // UMIs of the m > 0 survivors d_order[0 .. m) gathered into a dense padded blob with m + 1 offsets from 0, so that a
 // skipped record's bytes are never examined, and validated as umis_upload validates: *bad_record is kNoRecord or the

@@ -742,6 +742,9 @@ int gather_names(const uint32_t *d_order, uint64_t m, const uint8_t *d_names, co
 
 namespace {
 
+int cells_from_runs(uint64_t n, uint64_t n_runs, uint64_t n_input, const uint32_t *d_sorted, const uint64_t *d_run_off, bool timing,
+                    double *cells_ms, BarcodeCells *out, DevBuf<uint32_t> *out_heads);
+
 // The barcodes as one cell through the key rounds (cc: the host or the device form of the input), then the runs ranked by
 // their first record and laid out in that rank.  out_heads (or NULL): the cells' first records, ascending.
 int barcode_cells_of(CollateInput &cc, uint64_t n, bool timing, double *info, double *cells_ms, BarcodeCells *out,
@@ -756,8 +759,14 @@ int barcode_cells_of(CollateInput &cc, uint64_t n, bool timing, double *info, do
     cc.cut_records = true;
     CollateResident cr; // order: the stable sort by barcode; group_off: where a barcode starts, closed by n
     OEM_TRY(collate_resident(cc, 0, 1, 0, 0, 0, info, &cr));
-    const uint64_t n_runs = cr.n_groups;
+    return cells_from_runs(n, cr.n_groups, n, cr.order.p, cr.group_off.p, timing, cells_ms, out, out_heads);
+}
 
+// The runs of d_sorted (run_off: n_runs + 1 positions from 0, closed by n; the records are below n_input) ranked by their
+// first record and laid out in that rank.
+int cells_from_runs(uint64_t n, uint64_t n_runs, uint64_t n_input, const uint32_t *d_sorted, const uint64_t *d_run_off, bool timing,
+                    double *cells_ms, BarcodeCells *out, DevBuf<uint32_t> *out_heads)
+{
     Scratch sc;
     Event ev[2];
     if (timing)
@@ -773,16 +782,16 @@ int barcode_cells_of(CollateInput &cc, uint64_t n, bool timing, double *info, do
     OEM_TRY(dev_alloc(&d_len.p, n_runs + 1, nullptr));
     OEM_TRY(dev_alloc(&d_cro.p, n_runs + 1, nullptr));
     if (timing) OEM_HIP(hipEventRecord(ev[0].e, nullptr));
-    hipLaunchKernelGGL(k_barcode_heads, grid_for(n_runs), dim3(kCT), 0, nullptr, n_runs, (const uint32_t *)cr.order.p,
-                       (const uint64_t *)cr.group_off.p, d_head.p, d_idx.p);
+    hipLaunchKernelGGL(k_barcode_heads, grid_for(n_runs), dim3(kCT), 0, nullptr, n_runs, d_sorted,
+                       d_run_off, d_head.p, d_idx.p);
     OEM_HIP(hipGetLastError());
-    OEM_TRY(sort_pairs<uint32_t>(sc, d_head.p, d_head_s.p, d_idx.p, d_run_of_rank.p, n_runs, 0, std::max(bits_of(n - 1), 1), nullptr));
+    OEM_TRY(sort_pairs<uint32_t>(sc, d_head.p, d_head_s.p, d_idx.p, d_run_of_rank.p, n_runs, 0, std::max(bits_of(n_input - 1), 1), nullptr));
     hipLaunchKernelGGL(k_barcode_lengths, grid_for(n_runs + 1), dim3(kCT), 0, nullptr, n_runs, (const uint32_t *)d_run_of_rank.p,
-                       (const uint64_t *)cr.group_off.p, d_len.p, d_rank_of_run.p);
+                       d_run_off, d_len.p, d_rank_of_run.p);
     OEM_HIP(hipGetLastError());
     OEM_TRY(scan_u64(sc, false, (const uint64_t *)d_len.p, d_cro.p, n_runs + 1, nullptr));
-    hipLaunchKernelGGL(k_barcode_scatter, grid_for(n), dim3(kCT), 0, nullptr, n, n_runs, (const uint32_t *)cr.order.p,
-                       (const uint64_t *)cr.group_off.p, (const uint32_t *)d_rank_of_run.p, (const uint64_t *)d_cro.p, d_order_bc.p);
+    hipLaunchKernelGGL(k_barcode_scatter, grid_for(n), dim3(kCT), 0, nullptr, n, n_runs, d_sorted,
+                       d_run_off, (const uint32_t *)d_rank_of_run.p, (const uint64_t *)d_cro.p, d_order_bc.p);
     OEM_HIP(hipGetLastError());
     if (timing) OEM_HIP(hipEventRecord(ev[1].e, nullptr));
     OEM_HIP(hipStreamSynchronize(nullptr));
@@ -820,6 +829,13 @@ int collate_barcodes_device(const char *who, const uint8_t *d_barcodes, const ui
     cc.d_n_bytes = n_bytes;
     double info[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ms = 0;
     return barcode_cells_of(cc, n_records, false, info, &ms, out, out_heads);
+}
+
+int barcode_cells_from_runs(uint64_t n, uint64_t n_runs, uint64_t n_input, const uint32_t *d_sorted, const uint64_t *d_run_off,
+                            BarcodeCells *out, DevBuf<uint32_t> *out_heads)
+{
+    double ms = 0;
+    return cells_from_runs(n, n_runs, n_input, d_sorted, d_run_off, false, &ms, out, out_heads);
 }
 
 int check_barcode_input(const char *who, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n_records)

@@ -434,7 +434,8 @@ int exclusive_sum(ScanTmp &t, const uint64_t *in, uint64_t *out, uint64_t n)
 
 } // namespace
 
-int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, uint64_t n, DevBuf<uint8_t> *d_umis, DevBuf<uint64_t> *d_umi_off)
+int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, uint64_t n, DevBuf<uint8_t> *d_umis, DevBuf<uint64_t> *d_umi_off,
+                bool validate)
 {
     const uint64_t n_bytes = umi_off[n], chunk_bytes = collate_chunk_bytes();
     DevBuf<unsigned long long> d_bad;
@@ -457,6 +458,7 @@ int umis_upload(const char *who, const uint8_t *umis, const uint64_t *umi_off, u
     // the validate kernel of the names: its empty-name word (d_bad[1]) is not read here, an empty UMI being legal
     OEM_TRY(filter_upload_measure<uint8_t>(umis, d_umis->p, byte_cut.data(), byte_cut.size() - 1, 1, nullptr,
                                            [&](hipStream_t lane, uint64_t g0, uint64_t) {
+                                               if (!validate) return;
                                                launch_collate_validate(lane, d_umis->p, byte_cut[g0], byte_cut[g0 + 1], d_umi_off->p,
                                                                        rec_cut[g0], rec_cut[g0 + 1], d_bad.p);
                                            }));

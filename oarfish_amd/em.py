@@ -406,6 +406,65 @@ def collate_barcodes(barcodes, device: int = 0):
     return order[:n], cell_rec_off[:int(n_cells.value) + 1].copy()
 
 
+class BarcodeRuleC(C.Structure):
+    """``oem_barcode_rule``."""
+    _fields_ = [("labels", C.c_void_p), ("label_off", C.c_void_p), ("n_labels", C.c_uint32), ("multi", C.c_uint32),
+                ("alphabet", C.c_void_p), ("n_alphabet", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _barcode_rule(whitelist, multi, alphabet):
+    """(the ``oem_barcode_rule`` of a call, the arrays it points into: the whitelist's blob and offsets, the alphabet)."""
+    from .types import pack_read_names
+    w = _n_packed(whitelist)
+    if w < 1:
+        raise ValueError("whitelist needs one label at least")
+    blob, off = pack_read_names(whitelist, w)
+    alpha = None
+    if alphabet is not None:
+        if isinstance(alphabet, str):
+            alphabet = alphabet.encode()
+        alpha = np.frombuffer(bytes(alphabet), dtype=np.uint8).copy()
+        if not 1 <= len(alpha) <= 8:
+            raise ValueError("alphabet needs 1 to 8 bytes")
+    if not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)   # (every label is empty: the call says so)
+    rule = BarcodeRuleC(blob.ctypes.data, off.ctypes.data, w, int(bool(multi)), None if alpha is None else alpha.ctypes.data,
+                        0 if alpha is None else len(alpha), 0)
+    return rule, (blob, off, alpha)
+
+
+def correct_barcodes(barcodes, whitelist, multi: bool = False, alphabet=b"ACGT", device: int = 0):
+    """Raw cell barcodes matched against a whitelist, with one-mismatch correction (``oem_correct_barcodes``; the
+    reference wants every record to carry a corrected barcode, docs/index.md:308-312).
+
+    ``barcodes``: one raw barcode (``CR``) per record, whatever ``types.pack_read_names`` accepts; the empty string where
+    the tag is missing.  ``whitelist``: the chemistry's permit list, distinct labels of 1 to 64 bytes, likewise.  A
+    barcode that is a label is exact; one that differs from labels of its length in exactly one position, the label's byte
+    there being in ``alphabet``, is corrected to that label if it is the only one -- with ``multi`` (STARsolo's
+    ``1MM_multi`` without qualities) also to the one that has strictly the most exact records among several.  Everything
+    else is rejected: no neighbour, ambiguous, missing.
+
+    Returns ``(wl_id, status, order, cell_rec_off, counts)``: every record's label index (``0xffffffff``: rejected) and
+    ``OEM_BARCODE_*`` status, the cells of the accepted records as ``collate_barcodes`` gives them (``order`` holds the
+    accepted records only), and the records of each of the five statuses."""
+    from .types import pack_read_names
+    n = _n_packed(barcodes)
+    blob, off = pack_read_names(barcodes, n)
+    rule, _keep = _barcode_rule(whitelist, multi, alphabet)
+    wl_id = np.empty(max(n, 1), dtype=np.uint32)
+    status = np.empty(max(n, 1), dtype=np.uint8)
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    cell_rec_off = np.empty(n + 1, dtype=np.uint64)
+    counts = np.zeros(5, dtype=np.uint64)
+    n_cells, n_acc = C.c_uint64(0), C.c_uint64(0)
+    if n and not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)   # (every barcode is missing)
+    _lib.check(_lib.lib().oem_correct_barcodes(C.addressof(rule), blob.ctypes.data if n else None, off.ctypes.data, n, device,
+                                               wl_id.ctypes.data, status.ctypes.data, order.ctypes.data, cell_rec_off.ctypes.data,
+                                               C.byref(n_cells), C.byref(n_acc), counts.ctypes.data))
+    return wl_id[:n], status[:n], order[:int(n_acc.value)].copy(), cell_rec_off[:int(n_cells.value) + 1].copy(), counts
+
+
 def dedup_umis(umis, order, group_off, cell_group_off, flags=None, device: int = 0):
     """The PCR duplicates among the reads of a collated order (``oem_dedup_umis``; the reference wants its single-cell
     input deduplicated already, docs/index.md:308-312).
@@ -540,13 +599,65 @@ def gather_names(names, idx):
     return np.ascontiguousarray(blob[src]), new_off
 
 
+def _em_cells_records_whitelist(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, sec, barcodes, umis, collate, mode,
+                                gene_of, umi_correct, whitelist, barcode_multi):
+    """``em_cells_records_sparse(..., barcodes=, names=, whitelist=)`` behind its packing: the one call
+    (``collate="device"``, oem_em_run_cells_records_whitelist_sparse), or the five steps it replaces.  Both return the
+    ten values of the UMI-rule form and ``wl_id``, ``status``, ``counts``."""
+    from .types import pack_read_names
+    n = len(records)
+    if collate == "host":
+        wl_id, status, _, _, counts = correct_barcodes(barcodes, whitelist, multi=barcode_multi, device=device)
+        keep = np.flatnonzero(wl_id != _lib.OEM_BARCODE_NO_ID)
+        labels = pack_read_names(whitelist, _n_packed(whitelist))
+        um = (np.zeros(0, dtype=np.uint8), np.zeros(len(keep) + 1, dtype=np.uint64)) if umis is None else gather_names(umis, keep)
+        out = _em_cells_records_umis(F, txp_len, records[keep], coverage, max_iter, conv_thresh, device, gather_names(names, keep),
+                                     None if sec is None else np.ascontiguousarray(sec[keep]), gather_names(labels, wl_id[keep]), um,
+                                     "device", mode, gene_of, umi_correct, always_rule=True)
+        return (*out[:6], keep.astype(np.uint32)[out[6]], *out[7:], wl_id, status, counts)
+    blob, off = names
+    bc_blob, bc_off = barcodes
+    one = np.zeros(1, dtype=np.uint8)
+    blob, bc_blob = (b if len(b) else one for b in (blob, bc_blob))
+    um_blob, um_off = (None, None) if umis is None else (umis[0] if len(umis[0]) else one, umis[1])
+    rule, _keep = _barcode_rule(whitelist, barcode_multi, None)
+    umi_rule, _gene = _umi_rule(gene_of, umi_correct)
+    model, bin_width, growth_rate = _coverage_args(coverage)
+    order = np.empty(max(n, 1), dtype=np.uint32)
+    kept = np.zeros(max(n, 1), dtype=np.uint32)
+    cell_rec_off = np.empty(n + 1, dtype=np.uint64)
+    cell_dups = np.zeros(max(n, 1), dtype=np.uint64)
+    cell_corrected = np.zeros(max(n, 1), dtype=np.uint64)
+    wl_id = np.empty(max(n, 1), dtype=np.uint32)
+    status = np.empty(max(n, 1), dtype=np.uint8)
+    counts = np.zeros(5, dtype=np.uint64)
+    n_groups, n_cells, n_surv = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    L = _lib.lib()
+    res = C.c_void_p()
+    _lib.check(L.oem_em_run_cells_records_whitelist_sparse(
+        C.addressof(rule), C.addressof(umi_rule), C.addressof(F), txp_len.ctypes.data, len(txp_len), records.ctypes.data if n else None, n,
+        bc_blob.ctypes.data if n else None, bc_off.ctypes.data, blob.ctypes.data if n else None, off.ctypes.data,
+        None if sec is None or not n else sec.ctypes.data, None if um_blob is None else um_blob.ctypes.data,
+        None if um_off is None else um_off.ctypes.data, _COLLATE_MODES[mode], bin_width, model, growth_rate, device, max_iter, conv_thresh,
+        order.ctypes.data, C.byref(n_surv), cell_rec_off.ctypes.data, C.byref(n_cells), None, C.byref(n_groups), None, kept.ctypes.data,
+        cell_dups.ctypes.data, cell_corrected.ctypes.data, wl_id.ctypes.data, status.ctypes.data, counts.ctypes.data, C.byref(res)))
+    nc = int(n_cells.value)
+    try:
+        tables = _discard_tables(L, res, nc)
+    except BaseException:
+        L.oem_cells_result_destroy(res)
+        raise
+    return (*_take_cells_result(res, nc, L), kept[:int(n_groups.value)].copy(), tables, order[:int(n_surv.value)].copy(),
+            cell_rec_off[:nc + 1].copy(), cell_dups[:nc].copy(), cell_corrected[:nc].copy(), wl_id[:n], status[:n], counts)
+
+
 def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, sec, barcodes, umis, collate, mode,
-                           gene_of=None, umi_correct=False):
+                           gene_of=None, umi_correct=False, always_rule=False):
     """``em_cells_records_sparse(..., barcodes=, names=, umis=)`` behind its packing: the one call
     (``collate="device"``, oem_em_run_cells_records_umis_sparse), or the seven steps it replaces.  With ``gene_of`` or
     ``umi_correct`` the one call is oem_em_run_cells_records_umis_rule_sparse, the join's fifth step ``dedup_umis_rule``,
     and ``cell_corrected`` is a tenth value."""
-    with_rule = gene_of is not None or bool(umi_correct)
+    with_rule = gene_of is not None or bool(umi_correct) or always_rule
     blob, off = names
     bc_blob, bc_off = barcodes
     um_blob, um_off = umis
@@ -598,7 +709,7 @@ def _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh,
 
 
 def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes, collate, mode,
-                               umis=None, gene_of=None, umi_correct=False):
+                               umis=None, gene_of=None, umi_correct=False, whitelist=None, barcode_multi=False):
     """``em_cells_records_sparse(..., names=, barcodes=)``: the one call (``collate="device"``), or the join it replaces."""
     from .types import pack_read_names
     records = np.ascontiguousarray(records, dtype=_aln_record_dtype())
@@ -614,9 +725,13 @@ def _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thr
         sec = np.ascontiguousarray(np.asarray(secondary) != 0, dtype=np.uint8)
         if len(sec) != n:
             raise ValueError("secondary must have one entry per record")
+    if umis is not None and _n_packed(umis) != n:
+        raise ValueError("umis must have one entry per record")
+    if whitelist is not None:
+        return _em_cells_records_whitelist(F, txp_len, records, coverage, max_iter, conv_thresh, device, (blob, off), sec, (bc_blob, bc_off),
+                                           None if umis is None else pack_read_names(umis, n), collate, mode, gene_of, umi_correct,
+                                           whitelist, barcode_multi)
     if umis is not None:
-        if _n_packed(umis) != n:
-            raise ValueError("umis must have one entry per record")
         return _em_cells_records_umis(F, txp_len, records, coverage, max_iter, conv_thresh, device, (blob, off), sec, (bc_blob, bc_off),
                                       pack_read_names(umis, n), collate, mode, gene_of, umi_correct)
     if collate == "host":   # the four steps the one call replaces
@@ -701,7 +816,8 @@ def _em_cells_records_names(F, txp_len, records, cell_rec_off, coverage, max_ite
 
 def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off, coverage=None, max_iter: int = 1000,
                             conv_thresh: float = 1e-3, device: int = 0, names=None, secondary=None, collate: str = "host",
-                            mode: str = "sort", barcodes=None, umis=None, gene_of=None, umi_correct: bool = False):
+                            mode: str = "sort", barcodes=None, umis=None, gene_of=None, umi_correct: bool = False, whitelist=None,
+                            barcode_multi: bool = False):
     """A single-cell run from the cells' alignment records on, in one device call (single_cell.rs:104-188,
     oem_em_run_cells_records_sparse): AlignmentFilters::filter into every cell's own store, the per-cell coverage
     model if asked, em::em, the entries ``v > 0`` kept.  The filtered CSR never exists on the host.
@@ -743,6 +859,15 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     oem_em_run_cells_records_umis_rule_sparse, ``collate="host"`` the same join with ``dedup_umis_rule``, and
     ``cell_corrected``, the reads of every cell whose UMI was corrected, is a tenth value.  With both at their defaults
     nothing changes.
+
+    ``whitelist`` (goes with ``barcodes``; ``barcode_multi`` goes with it): the barcodes are RAW (``CR`` tags) and are
+    matched against the whitelist with one-mismatch correction first, as ``correct_barcodes`` does it; the records that
+    are rejected belong to no cell, and their names, UMIs and ``ref_id`` are never looked at.  ``collate="device"`` is one
+    call (oem_em_run_cells_records_whitelist_sparse); ``collate="host"`` the join it replaces: ``correct_barcodes``, the
+    rejected records dropped with NumPy, the labels' bytes as barcodes, the UMI-rule one call, ``order`` mapped back.
+    Both return the ten values of the UMI-rule form (with or without ``umis``; ``order`` holds input indices of accepted
+    records only) and then ``wl_id``, ``status`` and ``counts`` as ``correct_barcodes`` returns them.  ``whitelist=None``
+    changes nothing.
     """
     from .builder import filters_c
     if collate not in ("host", "device"):
@@ -755,6 +880,10 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
         raise ValueError("umis goes with barcodes: the molecules of a cell are found where the cells are")
     if umis is None and (gene_of is not None or umi_correct):
         raise ValueError("gene_of and umi_correct go with umis: they are the rule the UMIs are deduplicated by")
+    if whitelist is not None and barcodes is None:
+        raise ValueError("whitelist goes with barcodes: it is what the raw barcodes are corrected against")
+    if whitelist is None and barcode_multi:
+        raise ValueError("barcode_multi goes with whitelist")
     if barcodes is not None:
         if cell_group_off is not None or group_off is not None:
             raise ValueError("with barcodes the cells are found by the call: group_off and cell_group_off must be None")
@@ -764,7 +893,7 @@ def em_cells_records_sparse(filters, txp_len, records, group_off, cell_group_off
     txp_len = np.ascontiguousarray(txp_len, dtype=np.uint64)
     if barcodes is not None:
         return _em_cells_records_barcodes(F, txp_len, records, coverage, max_iter, conv_thresh, device, names, secondary, barcodes,
-                                          collate, mode, umis, gene_of, umi_correct)
+                                          collate, mode, umis, gene_of, umi_correct, whitelist, barcode_multi)
     if names is not None and collate == "device":
         return _em_cells_records_names(F, txp_len, records, cell_group_off, coverage, max_iter, conv_thresh, device, names,
                                        secondary, mode)

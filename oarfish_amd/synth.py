@@ -788,6 +788,63 @@ def add_umi_errors(umis, rate: float, seed: int = BASE_SEED + 37, names=None, ba
     return blob, np.ascontiguousarray(umis[1], dtype=np.uint64)
 
 
+def make_whitelist(n: int, length: int = 16, seed: int = BASE_SEED + 41):
+    """A barcode whitelist (a chemistry's permit list) for ``correct_barcodes``: ``n`` distinct labels of ``length``
+    nucleotides as a ``(blob, offsets)`` pair.  About an eighth of the labels are made from others by one substitution and
+    as many by two, so the list holds pairs at distance 1 (a raw barcode between them is ambiguous, and an error can turn
+    one label into another) and at distance 2 (one barcode is a neighbour of both).  A pure function of its arguments."""
+    if n < 1 or length < 1 or length > 64 or (length < 32 and n > 4 ** length):
+        raise ValueError("make_whitelist needs 1 <= length <= 64 and room for n distinct labels")
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(0, 4, size=(n, length), dtype=np.uint8)
+    k = n // 8
+    for dist, at in ((1, n - 2 * k), (2, n - k)):
+        if k and length >= dist:
+            rows[at:at + k] = rows[:k]
+            cols = np.argsort(rng.random((k, length)), axis=1)[:, :dist]
+            for d in range(dist):
+                rows[at + np.arange(k), cols[:, d]] = (rows[np.arange(k), cols[:, d]] + rng.integers(1, 4, size=k, dtype=np.uint8)) % 4
+    while True:   # repeated labels are drawn again until none is left
+        if length <= 32:   # two bits a nucleotide: a label is one word
+            codes = (rows.astype(np.uint64) << (np.uint64(2) * np.arange(length, dtype=np.uint64))[None, :]).sum(axis=1, dtype=np.uint64)
+            _, first = np.unique(codes, return_index=True)
+        else:
+            _, first = np.unique(rows, axis=0, return_index=True)
+        again = np.setdiff1d(np.arange(n), first)
+        if not len(again):
+            break
+        rows[again] = rng.integers(0, 4, size=(len(again), length), dtype=np.uint8)
+    rows = rows[rng.permutation(n)]
+    return np.ascontiguousarray(_NUC[rows].reshape(-1)), np.arange(n + 1, dtype=np.uint64) * np.uint64(length)
+
+
+def add_barcode_errors(barcodes, rate: float, n_rate: float = 0.0, seed: int = BASE_SEED + 43, names=None):
+    """Sequencing errors in the cell barcodes of an input, what ``correct_barcodes`` undoes: in a fraction ``rate`` of the
+    READS one nucleotide of the barcode is substituted by another of ``ACGT``, in a further fraction ``n_rate`` one is
+    replaced by ``N``; the same on all records of the read.  A read is the records that share a barcode and a name
+    (``names``: a ``(blob, offsets)`` pair, one entry per record); without names every record is a read of its own.  Which
+    reads are hit, where and by what depends on the seed, the read's barcode and name and -- without names -- the record's
+    index only, not on the order of the records.  Empty barcodes stay empty.  Returns the new ``(blob, offsets)`` pair."""
+    if not (0.0 <= rate <= 1.0 and 0.0 <= n_rate <= 1.0 and rate + n_rate <= 1.0):
+        raise ValueError("rate, n_rate and their sum must be in [0, 1]")
+    blob, off = np.array(barcodes[0], dtype=np.uint8), np.ascontiguousarray(barcodes[1], dtype=np.int64)
+    n = len(off) - 1
+    key = _string_hashes(barcodes, n) * np.uint64(0x9E3779B97F4A7C15)
+    key = _mix64(key ^ (np.arange(n, dtype=np.uint64) if names is None else _string_hashes(names, n)))
+    h = _mix64(key ^ _mix64(np.full(n, int(seed) & (2 ** 64 - 1), dtype=np.uint64)))
+    lens = np.diff(off)
+    u = (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    idx = np.flatnonzero((u < rate + n_rate) & (lens > 0))
+    h2 = _mix64(h[idx] + np.uint64(1))
+    at = off[idx] - off[0] + (h2 % lens[idx].astype(np.uint64)).astype(np.int64)
+    old = blob[at]
+    was = np.argmax(old[:, None] == _NUC[None, :], axis=1)               # (a byte outside ACGT counts as A's place)
+    new = _NUC[(was + 1 + ((h2 >> np.uint64(32)) % np.uint64(3)).astype(np.int64)) % 4]
+    new = np.where(new == old, _NUC[(was + 1) % 4], new)
+    blob[at] = np.where(u[idx] < rate, new, np.uint8(ord("N")))
+    return blob, np.ascontiguousarray(barcodes[1], dtype=np.uint64)
+
+
 def add_umi_duplicates(records, names, secondary, barcodes, rate: float, seed: int = BASE_SEED + 29, umi_len: int = 12):
     """An uncollated single-cell input (``interleave_cells``) given UMIs and PCR duplicates, the input of
     ``em_cells_records_sparse(..., barcodes=, names=, umis=)``.  ``names`` and ``barcodes`` are ``(blob, offsets)`` pairs,

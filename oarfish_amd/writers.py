@@ -303,6 +303,26 @@ def cell_barcodes(barcodes, order, cell_rec_off) -> list:
     return out
 
 
+def cell_labels(whitelist, wl_id, order, cell_rec_off) -> list:
+    """The cells' barcodes in result order under a whitelist, for `.barcodes.txt`: cell c's is the whitelist's label
+    ``wl_id[order[cell_rec_off[c]]]``, never a record's own (raw) bytes.  ``whitelist``: whatever ``types.pack_read_names``
+    accepts; ``wl_id`` / ``order`` / ``cell_rec_off``: what ``em.correct_barcodes`` or ``em_cells_records_sparse(...,
+    whitelist=)`` returned.  Returns a list of ``str`` as ``cell_barcodes`` does."""
+    from .types import pack_read_names
+    w = len(whitelist[1]) - 1 if isinstance(whitelist, tuple) and len(whitelist) == 2 and not isinstance(whitelist[1], (str, bytes)) else len(whitelist)
+    blob, off = pack_read_names(whitelist, w)
+    wl_id, order = np.asarray(wl_id), np.asarray(order)
+    cell_rec_off = np.asarray(cell_rec_off, dtype=np.int64)
+    raw = blob.tobytes()
+    out = []
+    for c in range(len(cell_rec_off) - 1):
+        label = int(wl_id[int(order[cell_rec_off[c]])])
+        if label >= w:
+            raise ValueError(f"cell {c}: its first record has no label")
+        out.append(raw[int(off[label]):int(off[label + 1])].decode("latin-1"))
+    return out
+
+
 def _write_single_cell_side_files(output: str, info: dict, feature_names: Sequence[str],
                                   barcodes: Optional[Sequence[str]]) -> None:
     """What a single-cell run writes besides the matrix: `.meta_info.json`, `.features.txt` and, in row order,

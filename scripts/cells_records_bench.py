@@ -72,6 +72,10 @@ in one process, --runs repeats (five), best to worst, one pushing thread:
 
 With the peak device memory of each, arena_bytes, the duplicates dropped and (a) - (c).
 
+--whitelist is the leg of barcode correction (profiles/cells_records_whitelist_bench.json): the --umis-rule leg's input
+with the cells' barcodes drawn from a 3 M-label whitelist and errors in the barcodes of 5 % of the reads; the whitelist
+one call on the raw barcodes against the UMI-rule one call on the clean ones, alternated in one process.
+
 --umis-rule-stream is the leg of the UMI rule in the sessions (profiles/cells_umis_rule_stream_bench.json): the
 --umis-stream leg's input with synth.add_umi_errors(rate=0.05) and a synthetic gene_of, alternated in one process at the
 first --batch-records, one pushing thread: both session forms under (a) the exact rule, (b) gene keys, (c) gene keys plus
@@ -428,6 +432,75 @@ def umis_rule_leg(args, cr, res, save):
                                               longest_walk_swapped_collation=int(out[5]), groups_of_cells=int(out[6]))
         save()
         del rec, names, sec, bc, umis
+
+
+def whitelist_leg(args, cr, res, save):
+    """The --whitelist leg: the --umis-rule leg's input (UMIs with PCR duplicates and errors, a synthetic annotation) with
+    the cells' barcodes taken from a whitelist of --whitelist-labels labels (synth.make_whitelist) and sequencing errors in
+    the barcodes of 5 % of the reads (synth.add_barcode_errors(rate=0.04, n_rate=0.01), per read).  Alternated in one
+    process: (w) the whitelist one call on the RAW barcodes (oem_em_run_cells_records_whitelist_sparse, multi); (c) the
+    UMI-rule one call on the same records with the CLEAN barcodes, which is what the parent commit offers to a caller whose
+    barcodes were corrected elsewhere.  Both under gene keys plus one-mismatch UMI correction.  Reported: (w) - (c) beside
+    (c)'s own spread, the records of every status, the cells, the peak device memory of both."""
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    def head(pair, m):
+        return pair[0][:int(pair[1][m])], pair[1][:m + 1]
+
+    t0 = time.perf_counter()
+    whitelist = synth.make_whitelist(max(args.whitelist_labels, n))
+    labels = [whitelist[0][16 * c:16 * c + 16].tobytes() for c in range(n)]
+    res["whitelist_labels"], res["make_whitelist_s"] = int(len(whitelist[1]) - 1), round(time.perf_counter() - t0, 2)
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        rec1, names1, sec1, bc1, _ = synth.interleave_cells(rec0, names0, sec0, cro, labels, how="uniform")
+        del rec0, names0, sec0
+        rec, names, sec, bc, umis, copies = synth.add_umi_duplicates(rec1, names1, sec1, bc1, rate=0.1)
+        del rec1, names1, sec1, bc1
+        umis = synth.add_umi_errors(umis, 0.05, names=names, barcodes=bc)
+        raw = synth.add_barcode_errors(bc, 0.04, 0.01, names=names)
+        gene_of = synth.gene_of_txps(len(tl))
+        r = res[style] = dict(records=int(len(rec)), copied_reads=int(sum(copies.values())), barcode_bytes=int(bc[0].nbytes),
+                              barcode_error_rate=0.05, umi_error_rate=0.05, genes=int(gene_of[-1]) + 1)
+        kw = dict(gene_of=gene_of, umi_correct=True, collate="device")
+
+        def run(leg, upto=None):
+            b = raw if leg == "w" else bc
+            wl = dict(whitelist=whitelist, barcode_multi=True) if leg == "w" else {}
+            if upto is None:
+                return oarfish_amd.em_cells_records_sparse(f, tl, rec, None, None, names=names, secondary=sec, barcodes=b, umis=umis, **kw, **wl)
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:upto], None, None, names=head(names, upto), secondary=sec[:upto],
+                                                       barcodes=head(b, upto), umis=head(umis, upto), **kw, **wl)
+
+        m = min(len(rec), int(cro[min(args.warm_cells, n)]))   # warm-up on the first records of the input
+        for leg in ("w", "c"):
+            run(leg, m)
+        runs = dict(w=[], c=[])
+        for k in range(args.runs):
+            for leg in ("w", "c"):
+                if k == 0:
+                    with PeakDeviceMemory() as pk:
+                        dt, got = clock(lambda: run(leg))
+                    r[f"peak_device_bytes_{leg}"] = int(pk.peak)
+                    r[f"cells_{leg}"], r[f"reads_counted_{leg}"] = int(len(got[7]) - 1), int(len(got[4]))
+                    if leg == "w":
+                        r["records_by_status"] = dict(zip(("exact", "corrected", "no_neighbour", "ambiguous", "missing"), (int(x) for x in got[12])))
+                else:
+                    dt, got = clock(lambda: run(leg))
+                runs[leg].append(dt)
+                del got
+            print(f"[bench] {style} run {k}: (w) {runs['w'][-1]:.3f} s, (c) {runs['c'][-1]:.3f} s", flush=True)
+            r["whitelist_one_call_on_raw_barcodes"], r["rule_one_call_on_clean_barcodes"] = spread(runs["w"]), spread(runs["c"])
+            r["whitelist_cost_s_w_minus_c"] = round(min(runs["w"]) - min(runs["c"]), 4)
+            r["clean_call_own_spread_s"] = round(max(runs["c"]) - min(runs["c"]), 4)
+            save()
+        del rec, names, sec, bc, raw, umis
 
 
 def barcodes_stream_leg(args, cr, res, save):
@@ -803,6 +876,9 @@ def main():
     ap.add_argument("--umis", action="store_true", help="the leg of the one call with UMI deduplication against the barcodes call and the host join")
     ap.add_argument("--umis-rule", action="store_true",
                     help="the leg of the UMI rule: the exact one call against gene keys, gene keys plus correction, correction alone")
+    ap.add_argument("--whitelist", action="store_true",
+                    help="the leg of barcode correction: the whitelist one call on raw barcodes against the UMI-rule one call on clean ones")
+    ap.add_argument("--whitelist-labels", type=int, default=3_000_000, help="the --whitelist leg: labels of the whitelist")
     ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
     ap.add_argument("--barcodes-any-order-stream", action="store_true",
                     help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
@@ -815,12 +891,13 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream or args.umis_rule_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.whitelist or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream or args.umis_rule_stream else 3
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "cells_umis_rule_stream_bench.json" if args.umis_rule_stream else
                                 "cells_umis_stream_bench.json" if args.umis_stream else
                                 "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
                                 "cells_barcodes_stream_bench.json" if args.barcodes_stream else
+                                "cells_records_whitelist_bench.json" if args.whitelist else
                                 "cells_records_umis_rule_bench.json" if args.umis_rule else
                                 "cells_records_umis_bench.json" if args.umis else
                                 "cells_records_barcodes_bench.json" if args.barcodes else
@@ -900,6 +977,10 @@ def main():
         return
     if args.barcodes_stream:
         barcodes_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
+    if args.whitelist:
+        whitelist_leg(args, cr, res, save)
         print(json.dumps(res))
         return
     if args.umis_rule:
