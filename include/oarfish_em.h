@@ -983,7 +983,8 @@ int oem_em_run_cells_records_umis_rule_sparse(
  *     barcodes gives exactly that call's order / cell_rec_off.  A cell's label is the whitelist's bytes, labels[id of the
  *     cell's first record], not any record's.
  * The result never depends on a hash, on probe order or on the arrival order of atomics.  Limits, on purpose: no base
- * qualities (Cell Ranger's posterior needs them), no indels, no knee; the barcoded sessions do not take the rule yet. */
+ * qualities (Cell Ranger's posterior needs them), no indels, no knee.  The any-order barcoded session takes the rule
+ * through oem_cells_stream_set_whitelist. */
 typedef struct {
     const uint8_t *labels; const uint64_t *label_off; uint32_t n_labels;
     uint32_t multi;            /* 0, 1 */
@@ -1169,6 +1170,9 @@ typedef struct {
 #define OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS 11u     /* their records */
 #define OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS 12u /* reads corrected under a rule with correct (oem_cells_stream_set_umi_rule),
                                                          in groups that have run */
+/* a whitelist session (oem_cells_stream_set_whitelist); 0 on every other session */
+#define OEM_CELLS_STREAM_INFO_BARCODE_REJECTED 13u    /* mapped records dropped by the barcode rule, in their batch or at finish */
+#define OEM_CELLS_STREAM_INFO_BARCODE_DEFERRED 14u    /* records whose choice between several neighbours waited for finish */
 
 /* Argument errors (n_txps = 0, opts or out NULL, coverage = 1 without txp_len, with bin_width = 0 or with a model
  * other than 0 / 1, a non-zero reserved word) are reported before any device is touched; without a device the call
@@ -1356,6 +1360,45 @@ int oem_cells_stream_umis_copy(const oem_cells_stream *s, uint64_t *out_cell_dup
  * OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS is their sum over the groups that have run. */
 int oem_cells_stream_set_umi_rule(oem_cells_stream *s, const oem_umi_rule *rule);
 int oem_cells_stream_umi_rule_copy(const oem_cells_stream *s, uint64_t *out_cell_corrected /* n_cells */);
+/* THE BARCODE RULE IN THE ANY-ORDER SESSION: oem_cells_stream_set_whitelist gives an any-order barcoded session the
+ * oem_barcode_rule of oem_em_run_cells_records_whitelist_sparse.  The batches' barcodes are then RAW (CR tags): every batch
+ * is matched against the whitelist on the device, and the session's cells are the whitelist's labels.  It is called after
+ * oem_cells_stream_set_barcodes_any_order and before the first push, once, in either order with oem_cells_stream_set_umis
+ * / _set_umi_rule; the rule's arrays are copied.  OEM_ERR_ARG: the rule's own checks, a whitelist of 2^31 labels or more,
+ * and the whitelist errors found on the device (a label with a 0 byte, two equal labels), worded as oem_correct_barcodes
+ * words them.  OEM_ERR_STATE: on a plain or records session, after a push, after finish, a second time -- and on the
+ * COLLATED barcoded session, on purpose: its cells are runs of byte-equal barcodes and a barcode that comes back is a new
+ * cell, so corrected raw barcodes would scatter one label over many cells; use the any-order form.
+ *
+ * The rule in a session.  n(w) grows batch by batch, so a batch decides what does not depend on it and defers the rest:
+ *   - an unmapped record takes no part: its barcode is never examined and it adds nothing to n(w) (oem_correct_barcodes
+ *     and the one call count it: on input that holds unmapped records they differ from the session, which equals them on
+ *     the mapped records' arrays);
+ *   - a mapped record's barcode may be empty (OEM_BARCODE_MISSING); a 0 byte in it is the batch's sticky OEM_ERR_ARG,
+ *     naming ticket and session-global index;
+ *   - exact records get their label and raise n(w); a miss with no neighbour, with one neighbour, or -- multi = 0 -- with
+ *     several is decided in its batch; only multi = 1 with several neighbours is DEFERRED to finish, which decides it with
+ *     the complete counts;
+ *   - a record rejected in its batch is dropped there: its name, UMI and ref_id are NEVER LOOKED AT, as the one call
+ *     promises.  The name and UMI checks and the batch's ref_id check run over the retained records -- the accepted and the
+ *     deferred ones.  THE SESSIONS DIFFER in this: a deferred record is checked in its batch, so an error in it is an
+ *     error of the session even if finish then rejects it; the one call never sees that error;
+ *   - cells are numbered by their first accepted record in session order -- which may be a deferred one: the numbering is
+ *     made at finish, not by first sight -- with session order inside a cell; a cell's label is the whitelist's bytes.
+ * With S the mapped records' indices, ascending, finish gives exactly what oem_em_run_cells_records_whitelist_sparse
+ * gives on records[S], barcodes[S], names[S], secondary[S], umis[S] under the same rules, however the input is cut and
+ * whichever thread pushes what: order is S[order of the one call]; values and infos as a session is held to its one call.
+ * The bound of 2^31 - 2 records counts the retained records.  Batches arrive through oem_cells_stream_push_barcodes /
+ * _push_barcodes_umis, unchanged.  After finish, oem_cells_stream_barcodes_dims / _barcodes_copy describe the ACCEPTED
+ * records: records pushed = n_unmapped + OEM_CELLS_STREAM_INFO_BARCODE_REJECTED + positions of order +
+ * OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS.  oem_cells_stream_whitelist_copy gives, after a successful finish of a whitelist
+ * session (otherwise OEM_ERR_STATE), every cell's label index, the number of its records that were corrected and the
+ * records of each of the five statuses; each output may be NULL.  Resident beyond the any-order session: the whitelist
+ * (as in oem_correct_barcodes) and the deferred records' barcodes with 4 bytes each, counted by
+ * OEM_CELLS_STREAM_INFO_ARENA_BYTES. */
+int oem_cells_stream_set_whitelist(oem_cells_stream *s, const oem_barcode_rule *rule);
+int oem_cells_stream_whitelist_copy(const oem_cells_stream *s, uint32_t *out_cell_wl_id /* n_cells */,
+                                    uint64_t *out_cell_bc_corrected /* n_cells */, uint64_t *out_counts /* 5 */);
 /* After a successful oem_cells_stream_finish of a barcoded session (otherwise OEM_ERR_STATE): the sizes of what
  * oem_cells_stream_barcodes_copy gives (each may be NULL) -- the cells, the survivors, the reads (record groups) of all
  * cells, the bytes of all labels, and the unmapped records that were skipped. */

@@ -43,6 +43,8 @@ OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS = 9
 OEM_CELLS_STREAM_INFO_UMI_DUP_READS = 10
 OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS = 11
 OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS = 12
+OEM_CELLS_STREAM_INFO_BARCODE_REJECTED = 13
+OEM_CELLS_STREAM_INFO_BARCODE_DEFERRED = 14
 OEM_RECORDS_STREAM_INFO_BATCHES = 1
 OEM_RECORDS_STREAM_INFO_GROUPS = 2
 OEM_RECORDS_STREAM_INFO_RECORDS = 3
@@ -93,6 +95,7 @@ ABI_SYMBOLS = [
     "oem_cells_stream_barcodes_copy", "oem_cells_stream_set_barcodes_any_order",
     "oem_cells_stream_set_umis", "oem_cells_stream_push_barcodes_umis", "oem_cells_stream_umis_copy",
     "oem_cells_stream_set_umi_rule", "oem_cells_stream_umi_rule_copy",
+    "oem_cells_stream_set_whitelist", "oem_cells_stream_whitelist_copy",
     "oem_cells_stream_finish", "oem_cells_stream_info", "oem_cells_stream_destroy",
     "oem_records_stream_create", "oem_records_stream_push", "oem_records_stream_finish", "oem_records_stream_info",
     "oem_records_stream_destroy", "oem_records_stream_set_names", "oem_records_stream_push_names",
@@ -289,6 +292,8 @@ def _load(path: str) -> C.CDLL:
     L.oem_cells_stream_umis_copy.argtypes = [vp, vp]
     L.oem_cells_stream_set_umi_rule.argtypes = [vp, vp]
     L.oem_cells_stream_umi_rule_copy.argtypes = [vp, vp]
+    L.oem_cells_stream_set_whitelist.argtypes = [vp, vp]
+    L.oem_cells_stream_whitelist_copy.argtypes = [vp, vp, vp, vp]
     L.oem_cells_stream_create.argtypes = [C.POINTER(CellsStreamOptsC), vp, C.POINTER(vp)]
     L.oem_cells_stream_push.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]
     L.oem_cells_stream_finish.argtypes = [vp, C.POINTER(vp)]
@@ -369,6 +374,7 @@ def testing_lib() -> C.CDLL:
         L.oem_test_dedup_umis_rule_host.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, vp, vp, vp]
         L.oem_debug_dedup_rule_last_call.argtypes = [vp]
         L.oem_test_correct_barcodes_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp]
+        L.oem_test_correct_barcodes_stream_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, vp]
         L.oem_test_cells_gene_counts_host.argtypes = [vp, u32, vp, vp, vp, u32, u32, C.POINTER(vp)]
         L.oem_debug_gene_counts_last_call.argtypes = [vp]
         L.oem_test_shortest_f64.argtypes = [vp, u64, vp, u64, vp]

@@ -113,7 +113,8 @@ TESTING_HOOKS = ["oem_debug_layout_hash", "oem_debug_local_comm_create", "oem_te
                  "oem_debug_records_stream_finish_csr", "oem_debug_records_stream_last_join",
                  "oem_debug_records_names_last_call", "oem_test_parse_bulk_host", "oem_debug_barcode_table_last",
                  "oem_test_dedup_umis_host", "oem_test_dedup_umis_rule_host", "oem_debug_dedup_rule_last_call",
-                 "oem_test_cells_gene_counts_host", "oem_debug_gene_counts_last_call", "oem_test_correct_barcodes_host"]
+                 "oem_test_cells_gene_counts_host", "oem_debug_gene_counts_last_call", "oem_test_correct_barcodes_host",
+                 "oem_test_correct_barcodes_stream_host"]
 
 
 def header_symbols() -> list:

@@ -98,6 +98,15 @@ void barcodes_stream_umi_info(BarcodesStream *b, uint64_t *dup_reads, uint64_t *
 int barcodes_stream_set_umi_rule(BarcodesStream *b, const char *who, const oem_umi_rule *rule);
 // oem_cells_stream_umi_rule_copy: the reads corrected in every cell, after finish of a session whose rule has correct
 int barcodes_stream_umi_rule_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_corrected);
+// oem_cells_stream_set_whitelist behind its NULL-session check: an any-order session, before any push, once; the rule's
+// arrays are copied and its whitelist is built on the session's device (oem_barcode_correct.h, "The rule in a session")
+int barcodes_stream_set_whitelist(BarcodesStream *b, const char *who, const oem_barcode_rule *rule);
+// oem_cells_stream_whitelist_copy: every cell's whitelist id and corrected records, and the five status counts, after
+// finish of a whitelist session; each output or NULL
+int barcodes_stream_whitelist_copy(const BarcodesStream *b, const char *who, uint32_t *out_cell_wl_id, uint64_t *out_cell_bc_corrected,
+                                   uint64_t *out_counts);
+// the mapped records a whitelist session dropped (per batch or at finish) and those that waited for finish
+void barcodes_stream_whitelist_info(BarcodesStream *b, uint64_t *rejected, uint64_t *deferred);
 // oem_cells_stream_umis_copy: the duplicates (reads) every cell lost, after finish
 int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_dups);
 bool barcodes_stream_push_in_flight(BarcodesStream *b);

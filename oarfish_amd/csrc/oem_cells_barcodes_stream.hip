@@ -49,6 +49,15 @@
 // no longer the identity), the filter and the host loop run over the deduplicated collation.  The slot keeps
 // n_positions, the cells' first positions and cell_dups for barcodes_stream_assemble: every later group's place in
 // `order` depends on what the earlier ones lost.  A session without UMIs allocates and launches nothing of this.
+//
+// A WHITELIST SESSION (oem_cells_stream_set_whitelist; oem_barcode_correct.h, "The rule in a session") is the any-order
+// form on RAW barcodes.  Its batches run the barcodes FIRST: the mapped records' barcodes are gathered dense and checked
+// (an empty one is legal), whitelist_batch (oem_barcode_correct.hip) runs the exact pass against the session's resident
+// whitelist and n(w) and the neighbour pass that decides or defers, and the survivor list is compacted to the RETAINED
+// records; names, UMIs, the ref_id check and the arena's append see these only.  The arena's id column holds whitelist
+// ids; a deferred record's barcode and arena position go to the pending list (a DevBlob and positions).  finish decides
+// the pending records with the complete counts (whitelist_finish), numbers the cells from the ids
+// (barcode_cells_from_ids: correct_barcodes_resident's tail) and lays the arena out over the accepted records only.
 #include <algorithm>
 #include <condition_variable>
 #include <cstdio>
@@ -62,6 +71,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "oem_barcode_correct.h"
 #include "oem_cells_barcodes_stream.h"
 #include "oem_collate_device.h"
 #include "oem_parse_device.h"
@@ -228,6 +238,19 @@ struct BarcodesStream {
     uint64_t corrected_reads = 0;              // (mu) of the groups that have run
     std::vector<uint64_t> out_cell_corrected;
     uint64_t arena_peak = 0, info_misses = 0, info_slots = 0; // (mu) as of the last batch, for oem_cells_stream_info
+    // a whitelist session (oem_cells_stream_set_whitelist; oem_barcode_correct.h, "The rule in a session"): the resident
+    // whitelist with the session's n(w), built when the rule is set, and the session's copy of its labels; the pending
+    // list of the deferred records -- their barcodes and arena positions, in arena order --, grown as the arena grows
+    std::unique_ptr<BarcodeWhitelist> wl; // (released at finish and on an error)
+    bool wl_was_set = false;
+    std::vector<uint8_t> wl_labels;
+    std::vector<uint64_t> wl_label_off;
+    DevBlob pending;
+    DevBuf<uint32_t> pending_pos;
+    uint64_t pending_pos_cap = 0;
+    uint64_t wl_counts[kBarcodeStatuses] = {0, 0, 0, 0, 0}, wl_rejected = 0, wl_deferred = 0; // (mu)
+    std::vector<uint32_t> out_cell_wl_id;
+    std::vector<uint64_t> out_cell_bc_corrected;
 
     // -- what finish leaves ------------------------------------------------------------------------------------------------
     bool assembled = false;
@@ -274,6 +297,18 @@ struct BarcodesStream {
     }
     int intern_batch(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_order, uint64_t m, const uint8_t *d_dbc,
                      const uint64_t *d_dbc_off, DevBuf<uint32_t> *d_cell_id);
+    int whitelist_barcodes(const Batch &b, const char *who, const uint8_t *d_bc, const uint64_t *d_bc_off, const uint32_t *d_order, uint64_t m,
+                           WhitelistBatch *wb);
+    int whitelist_retain(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_retained, const WhitelistBatch &wb);
+    int whitelist_cells(const char *who, BarcodeCells *bc, uint64_t *n_accepted);
+    void release_whitelist()
+    {
+        wl.reset();
+        pending.release();
+        pending_pos.reset();
+        pending_pos_cap = 0;
+    }
+    uint64_t pending_held() const { return pending.held() + sizeof(uint32_t) * pending_pos_cap; }
     int finish_any_order(const char *who);
     int run_batch(const Batch &b);
     int cut_groups(bool final);
@@ -303,20 +338,107 @@ int BarcodesStream::intern_batch(const Batch &b, const char *who, const oem_aln_
     return OEM_OK;
 }
 
+// A whitelist session's batch, first step: the m mapped records' barcodes gathered dense -- an unmapped record's are never
+// examined, an empty one is legal, a 0 byte is the batch's error --, then the rule's two passes and the compaction to the
+// retained records (whitelist_batch).
+int BarcodesStream::whitelist_barcodes(const Batch &b, const char *who, const uint8_t *d_bc, const uint64_t *d_bc_off, const uint32_t *d_order,
+                                       uint64_t m, WhitelistBatch *wb)
+{
+    DevBuf<uint8_t> d_dbc;
+    DevBuf<uint64_t> d_dbc_off;
+    uint64_t dbc_bytes = 0, bad = kNoRecord;
+    OEM_TRY(umis_gather_survivors(d_bc, d_bc_off, d_order, m, &d_dbc, &d_dbc_off, &dbc_bytes, &bad));
+    if (bad != kNoRecord)
+        return fail(OEM_ERR_ARG, "%s: the barcode of record %llu contains a 0 byte", who, (unsigned long long)(b.rec_base + bad));
+    OEM_TRY(whitelist_batch(who, *wl, d_dbc.p, d_dbc_off.p, d_order, m, arena ? arena->n : 0, wb));
+    std::lock_guard<std::mutex> lk(mu);
+    for (int k = 0; k < kBarcodeStatuses; ++k) wl_counts[k] += wb->counts[k];
+    wl_rejected += wb->counts[kBarcodeNoNeighbour] + wb->counts[kBarcodeAmbiguous] + wb->counts[kBarcodeMissing];
+    wl_deferred += wb->n_deferred;
+    return OEM_OK;
+}
+
+// ... and behind the name and UMI checks of the retained records: their ref_ids while the batch still knows its ticket,
+// the bound on the retained records, and the deferred ones onto the pending list.
+int BarcodesStream::whitelist_retain(const Batch &b, const char *who, const oem_aln_record *d_in, const uint32_t *d_retained,
+                                     const WhitelistBatch &wb)
+{
+    uint64_t bad = kNoRecord;
+    OEM_TRY(records_ref_check(wb.n_retained, d_retained, d_in, env.n_txps, &bad));
+    if (bad != kNoRecord) {
+        const oem_aln_record *h = (const oem_aln_record *)b.base();
+        return fail(OEM_ERR_ARG, "%s: record %llu: ref_id %u is not below n_txps", who, (unsigned long long)(b.rec_base + bad), h[bad].ref_id);
+    }
+    if ((arena ? arena->n : 0) + wb.n_retained > kCollateMaxBatch)
+        return fail(OEM_ERR_ARG, "%s: more than 2^31 - 2 retained records in the session: its cells are found by one sort at finish", who);
+    if (wb.n_deferred == 0) return OEM_OK;
+    OEM_TRY(pending.reserve(pending.n + wb.n_deferred, pending.n_bytes + wb.deferred_bytes, 1024, 4096, 0, nullptr));
+    if (pending.cap > pending_pos_cap) { // the positions grow with the blob's entries
+        DevBuf<uint32_t> grown;
+        OEM_TRY(dev_alloc(&grown.p, pending.cap, nullptr));
+        if (pending.n) OEM_HIP(hipMemcpy(grown.p, pending_pos.p, sizeof(uint32_t) * pending.n, hipMemcpyDeviceToDevice));
+        std::swap(pending_pos.p, grown.p);
+        pending_pos_cap = pending.cap;
+    }
+    OEM_HIP(hipMemcpy(pending_pos.p + pending.n, wb.deferred_pos.p, sizeof(uint32_t) * wb.n_deferred, hipMemcpyDeviceToDevice));
+    OEM_TRY(pending.append(wb.deferred_bc.p, wb.deferred_off.p, wb.n_deferred, wb.deferred_bytes));
+    OEM_HIP(hipStreamSynchronize(nullptr));
+    return OEM_OK;
+}
+
+// A whitelist session's finish: the pending records decided with the complete counts, the cells from the arena's ids,
+// every cell's whitelist id and corrected records, and the labels -- the whitelist's bytes -- from the session's copy.
+int BarcodesStream::whitelist_cells(const char *who, BarcodeCells *bc, uint64_t *n_accepted)
+{
+    const uint64_t m = arena->n;
+    uint64_t late[kBarcodeStatuses];
+    OEM_TRY(whitelist_finish(who, *wl, pending.bytes.p, pending.off.p, pending_pos.p, pending.n, arena->cell_id.p, m, late));
+    if (late[kBarcodeCorrected] + late[kBarcodeAmbiguous] != pending.n)
+        return fail(OEM_ERR_STATE, "%s: %llu pending records, %llu of them decided", who, (unsigned long long)pending.n,
+                    (unsigned long long)(late[kBarcodeCorrected] + late[kBarcodeAmbiguous]));
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (int k = 0; k < kBarcodeStatuses; ++k) wl_counts[k] += late[k];
+        wl_rejected += late[kBarcodeAmbiguous];
+    }
+    OEM_TRY(barcode_cells_from_ids(who, arena->cell_id.p, ~kBarcodeCorrectedBit, m, wl->n_labels, m - late[kBarcodeAmbiguous], bc, n_accepted));
+    OEM_TRY(whitelist_cell_summary(*bc, arena->cell_id.p, &out_cell_wl_id, &out_cell_bc_corrected));
+    labels.clear();
+    label_off.assign(1, 0);
+    for (const uint32_t w : out_cell_wl_id) {
+        if (w >= wl->n_labels) return fail(OEM_ERR_STATE, "%s: a cell has the whitelist id %u of %llu", who, w, (unsigned long long)wl->n_labels);
+        labels.insert(labels.end(), wl_labels.begin() + wl_label_off[w], wl_labels.begin() + wl_label_off[w + 1]);
+        label_off.push_back(labels.size());
+    }
+    return OEM_OK;
+}
+
 // An any-order session's finish, after the parse worker's end and before the last cut: the survivors sorted by cell id,
 // the arena laid out in that order -- from here on it is a collated session's arena whose cells are all closed -- and
 // the labels down.
 int BarcodesStream::finish_any_order(const char *who)
 {
     intern.publish_last();
-    const uint64_t m = arena ? arena->n : 0;
+    uint64_t m = arena ? arena->n : 0;
     if (m == 0) {
         intern.release();
+        release_whitelist();
         return OEM_OK;
     }
     BarcodeCells bc;
-    OEM_TRY(intern.cells(arena->cell_id.p, m, &bc));
-    OEM_TRY(intern.labels_down(&labels, &label_off));
+    const uint64_t n_arena = m; // a whitelist session: the retained records; m becomes the accepted ones, which are laid out
+    if (wl) {
+        OEM_TRY(whitelist_cells(who, &bc, &m));
+        release_whitelist();
+        n_survivors = m;
+        if (m == 0) { // every retained record was rejected at last: no cells
+            arena.reset();
+            return OEM_OK;
+        }
+    } else {
+        OEM_TRY(intern.cells(arena->cell_id.p, m, &bc));
+        OEM_TRY(intern.labels_down(&labels, &label_off));
+    }
     intern.release();
     const uint64_t nc = bc.n_cells;
     const SurvivorArena &a = *arena;
@@ -326,10 +448,12 @@ int BarcodesStream::finish_any_order(const char *who)
     // the gathers write whole words, which leaves fewer zeros than the arena's invariant asks: the memsets complete them
     auto gather_blob = [&](const DevBlob &src, DevBlob &dst, const uint8_t *src_sec, uint8_t *dst_sec, bool with_empty) {
         OEM_TRY(gather_name_offsets(bc.order.p, m, src.off.p, dst.off.p));
-        OEM_TRY(gather_names(bc.order.p, m, src.bytes.p, src.off.p, dst.off.p, 0, src.n_bytes, dst.bytes.p, src_sec, dst_sec, with_empty));
-        OEM_HIP(hipMemsetAsync(dst.bytes.p + src.n_bytes, 0, kBlobPad, nullptr));
+        uint64_t n_bytes = src.n_bytes; // (of the accepted records only where some were rejected at finish)
+        if (m != n_arena) OEM_HIP(hipMemcpy(&n_bytes, dst.off.p + m, sizeof n_bytes, hipMemcpyDeviceToHost));
+        OEM_TRY(gather_names(bc.order.p, m, src.bytes.p, src.off.p, dst.off.p, 0, n_bytes, dst.bytes.p, src_sec, dst_sec, with_empty));
+        OEM_HIP(hipMemsetAsync(dst.bytes.p + n_bytes, 0, kBlobPad, nullptr));
         dst.n = m;
-        dst.n_bytes = src.n_bytes;
+        dst.n_bytes = n_bytes;
         return (int)OEM_OK;
     };
     OEM_TRY(records_gather(m, bc.order.p, a.rec.p, na->rec.p));
@@ -377,12 +501,21 @@ int BarcodesStream::run_batch(const Batch &b)
     OEM_TRY(parse_survivors(d_in.p, n, true, &d_order, &m));
     n_unmapped += n - m;
     if (m == 0) return OEM_OK;
+    // a whitelist session: the barcodes first; from here on the batch's survivors are its retained records
+    WhitelistBatch wb;
+    if (wl) {
+        OEM_TRY(whitelist_barcodes(b, who, d_bc.p, d_bc_off.p, d_order.p, m, &wb));
+        if (wb.n_retained == 0) return OEM_OK; // (every mapped record was rejected: nothing else of the batch is looked at)
+        std::swap(d_order.p, wb.order.p); // (wb.order: the mapped records from here on; released with wb)
+        m = wb.n_retained;
+    }
     DevBuf<uint8_t> d_dbc, d_dnames, d_dsec, d_none;
     DevBuf<uint64_t> d_dbc_off, d_dname_off;
     uint64_t dbc_bytes = 0, dname_bytes = 0, bad_bc = kNoRecord, bad_name = kNoRecord;
     bool zero_bc = false, zero_name = false;
-    OEM_TRY(parse_survivor_names(d_bc.p, b.bc_bytes, d_bc_off.p, n, d_order.p, m, nullptr, &d_dbc, &d_dbc_off, &d_none, &dbc_bytes, &bad_bc,
-                                 &zero_bc));
+    if (!wl)
+        OEM_TRY(parse_survivor_names(d_bc.p, b.bc_bytes, d_bc_off.p, n, d_order.p, m, nullptr, &d_dbc, &d_dbc_off, &d_none, &dbc_bytes, &bad_bc,
+                                     &zero_bc));
     OEM_TRY(parse_survivor_names(d_names.p, b.name_bytes, d_name_off.p, n, d_order.p, m, d_sec.p, &d_dnames, &d_dname_off, &d_dsec,
                                  &dname_bytes, &bad_name, &zero_name));
     // a UMI session: the survivors' UMIs likewise, an empty one being legal.  On one record the barcode's error comes
@@ -415,6 +548,12 @@ int BarcodesStream::run_batch(const Batch &b)
         n_survivors += m;
         return (int)OEM_OK;
     };
+    if (wl) { // the retained records with their whitelist ids; the deferred ones onto the pending list
+        OEM_TRY(whitelist_retain(b, who, d_in.p, d_order.p, wb));
+        OEM_TRY(append(wb.id.p));
+        note_arena_bytes(arena->peak + pending_held());
+        return OEM_OK;
+    }
     if (any_order) { // the survivors' cells from the table; the arena takes them with their cell ids, and nothing is cut
         DevBuf<uint32_t> d_cell_id;
         OEM_TRY(intern_batch(b, who, d_in.p, d_order.p, m, d_dbc.p, d_dbc_off.p, &d_cell_id));
@@ -734,6 +873,7 @@ void BarcodesStream::process(Batch &b, bool skip)
         arena.reset();
         carry.reset();
         intern.release();
+        release_whitelist();
         set_stuck(rc, msg.c_str());
     }
 }
@@ -883,6 +1023,49 @@ int barcodes_stream_umi_rule_copy(const BarcodesStream *b, const char *who, uint
     return OEM_OK;
 }
 
+int barcodes_stream_set_whitelist(BarcodesStream *b, const char *who, const oem_barcode_rule *rule)
+{
+    OEM_TRY(check_barcode_rule(who, rule));
+    if (rule->n_labels >= kBarcodeCorrectedBit)
+        return fail(OEM_ERR_ARG, "%s: rule->n_labels = %u: a session's whitelist holds at most 2^31 - 1 labels", who, rule->n_labels);
+    std::lock_guard<std::mutex> lk(b->mu);
+    if (b->closed || b->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+    if (!b->any_order)
+        return fail(OEM_ERR_STATE,
+                    "%s: a collated barcoded session takes no whitelist: its cells are runs of equal barcodes, and corrected barcodes "
+                    "would scatter one label over many cells; use the any-order form (oem_cells_stream_set_barcodes_any_order)", who);
+    if (b->wl_was_set) return fail(OEM_ERR_STATE, "%s: the session has a whitelist already", who);
+    if (b->q.next_ticket || b->q.pushing) return fail(OEM_ERR_STATE, "%s: a batch has been pushed already", who);
+    OEM_HIP(hipSetDevice(b->env.device));
+    std::unique_ptr<BarcodeWhitelist> wl(new BarcodeWhitelist());
+    OEM_TRY(whitelist_build(who, rule, wl.get())); // (a label with a 0 byte, two equal labels: found on the device)
+    b->wl_labels.assign(rule->labels, rule->labels + rule->label_off[rule->n_labels]); // the rule's arrays are copied
+    b->wl_label_off.assign(rule->label_off, rule->label_off + rule->n_labels + 1);
+    b->wl = std::move(wl);
+    b->wl_was_set = true;
+    return OEM_OK;
+}
+
+int barcodes_stream_whitelist_copy(const BarcodesStream *b, const char *who, uint32_t *out_cell_wl_id, uint64_t *out_cell_bc_corrected,
+                                   uint64_t *out_counts)
+{
+    if (!b->wl_was_set) return fail(OEM_ERR_STATE, "%s: not a whitelist session (oem_cells_stream_set_whitelist)", who);
+    if (!b->assembled) return fail(OEM_ERR_STATE, "%s: after a successful oem_cells_stream_finish", who);
+    if (out_cell_wl_id && !b->out_cell_wl_id.empty())
+        std::memcpy(out_cell_wl_id, b->out_cell_wl_id.data(), sizeof(uint32_t) * b->out_cell_wl_id.size());
+    if (out_cell_bc_corrected && !b->out_cell_bc_corrected.empty())
+        std::memcpy(out_cell_bc_corrected, b->out_cell_bc_corrected.data(), sizeof(uint64_t) * b->out_cell_bc_corrected.size());
+    if (out_counts) std::copy(b->wl_counts, b->wl_counts + kBarcodeStatuses, out_counts);
+    return OEM_OK;
+}
+
+void barcodes_stream_whitelist_info(BarcodesStream *b, uint64_t *rejected, uint64_t *deferred)
+{
+    std::lock_guard<std::mutex> lk(b->mu);
+    *rejected = b->wl_rejected;
+    *deferred = b->wl_deferred;
+}
+
 int barcodes_stream_umis_copy(const BarcodesStream *b, const char *who, uint64_t *out_cell_dups)
 {
     if (!b->with_umis) return fail(OEM_ERR_STATE, "%s: not a UMI session (oem_cells_stream_set_umis)", who);
@@ -915,6 +1098,7 @@ int barcodes_stream_close(BarcodesStream *b, const char *who)
     b->arena.reset(); // (the groups hold it)
     b->carry.reset();
     b->intern.release();
+    b->release_whitelist();
     if (rc2 != OEM_OK) {
         const std::string m2 = last_error_text();
         b->set_stuck(rc2, m2.c_str());

@@ -783,6 +783,31 @@ extern "C" int oem_cells_stream_umi_rule_copy(const oem_cells_stream *s, uint64_
     return barcodes_stream_umi_rule_copy(s->bc, who, out_cell_corrected);
 }
 
+// The barcode rule of an any-order barcoded session (oem_barcode_correct.h, "The rule in a session"): raw barcodes
+// corrected against a whitelist batch by batch, as oem_em_run_cells_records_whitelist_sparse corrects them in one call.
+extern "C" int oem_cells_stream_set_whitelist(oem_cells_stream *s, const oem_barcode_rule *rule)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_cells_stream_set_whitelist";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->finish_called || s->cancel) return fail(OEM_ERR_STATE, "%s: the session is finished", who);
+        if (!s->bc) return fail(OEM_ERR_STATE, "%s: not an any-order barcoded session (oem_cells_stream_set_barcodes_any_order)", who);
+    }
+    return barcodes_stream_set_whitelist(s->bc, who, rule);
+    OEM_API_END("oem_cells_stream_set_whitelist")
+}
+
+extern "C" int oem_cells_stream_whitelist_copy(const oem_cells_stream *s, uint32_t *out_cell_wl_id, uint64_t *out_cell_bc_corrected,
+                                               uint64_t *out_counts)
+{
+    const char *who = "oem_cells_stream_whitelist_copy";
+    if (!s) return fail(OEM_ERR_ARG, "%s: NULL session", who);
+    if (!s->bc) return fail(OEM_ERR_STATE, "%s: not a whitelist session (oem_cells_stream_set_whitelist)", who);
+    return barcodes_stream_whitelist_copy(s->bc, who, out_cell_wl_id, out_cell_bc_corrected, out_counts);
+}
+
 extern "C" int oem_cells_stream_barcodes_dims(const oem_cells_stream *s, uint64_t *n_cells, uint64_t *n_survivors, uint64_t *n_groups,
                                               uint64_t *barcode_bytes, uint64_t *n_unmapped)
 {
@@ -864,7 +889,11 @@ extern "C" int oem_cells_stream_info(const oem_cells_stream *s, uint32_t key, ui
     if (s->bc) barcodes_stream_table_info(s->bc, &bc_arena, &bc_misses, &bc_slots);
     uint64_t dup_reads = 0, dup_records = 0, corrected_reads = 0;
     if (s->bc) barcodes_stream_umi_info(s->bc, &dup_reads, &dup_records, &corrected_reads);
+    uint64_t bc_rejected = 0, bc_deferred = 0;
+    if (s->bc) barcodes_stream_whitelist_info(s->bc, &bc_rejected, &bc_deferred);
     switch (key) {
+    case OEM_CELLS_STREAM_INFO_BARCODE_REJECTED: *value = bc_rejected; break; // (a whitelist session; 0 otherwise)
+    case OEM_CELLS_STREAM_INFO_BARCODE_DEFERRED: *value = bc_deferred; break;
     case OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS: *value = corrected_reads; break; // (under a rule with correct; 0 otherwise)
     case OEM_CELLS_STREAM_INFO_UMI_DUP_READS: *value = dup_reads; break; // (a UMI session; 0 otherwise)
     case OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS: *value = dup_records; break;

@@ -3,6 +3,8 @@
 // oem_em_run_cells_records_names_sparse (oem_cells_records.hip) gathers and filters the records behind them instead.
 #pragma once
 
+#include <vector>
+
 #include "oem_collate.h"
 #include "oem_driver.h"
 
@@ -101,6 +103,39 @@ int whitelist_build(const char *who, const oem_barcode_rule *rule, BarcodeWhitel
 // counted into it.  Returns with the device idle and only `out` held.
 int correct_barcodes_resident(const char *who, const BarcodeWhitelist &wl, const uint8_t *barcodes, const uint64_t *barcode_off, uint64_t n,
                               CorrectedCells *out);
+// The tail of correct_barcodes_resident, shared with a whitelist session's finish: the cells of the records whose d_id is
+// not kBarcodeNoId -- an accepted flag, a scan, (id & mask, record) compacted, one stable radix sort over the bits
+// n_labels needs, the runs ranked by their first record (barcode_cells_from_runs).  *n_accepted: the records in cells;
+// m_expected: what it must be, or ~0.  Leaves the null stream idle.
+int barcode_cells_from_ids(const char *who, const uint32_t *d_id, uint32_t mask, uint64_t n, uint64_t n_labels, uint64_t m_expected,
+                           BarcodeCells *cells, uint64_t *n_accepted);
+
+// ---- the rule in a session (oem_barcode_correct.h, "The rule in a session"; oem_cells_stream_set_whitelist)
+// What a batch of a whitelist session leaves: its RETAINED records (accepted or deferred) as the batch's survivor list
+// compacted to them with their ids (kBarcodeCorrectedBit on a corrected record, kBarcodeNoId on a deferred one), the
+// deferred records' barcodes as a dense padded blob with their arena positions, both in batch order, and the batch's
+// final statuses by count (a deferred record is in none).
+struct WhitelistBatch {
+    DevBuf<uint32_t> order, id;       // n_retained
+    DevBuf<uint32_t> deferred_pos;    // n_deferred: arena_n + the record's rank among the retained
+    DevBuf<uint8_t> deferred_bc;      // their barcodes ...
+    DevBuf<uint64_t> deferred_off;    // ... n_deferred + 1 offsets from 0
+    uint64_t n_retained = 0, n_deferred = 0, deferred_bytes = 0, counts[5] = {0, 0, 0, 0, 0};
+};
+// One batch: the m mapped records d_order[0 .. m) with their barcodes as a dense blob (checked for 0 bytes, padded by 16,
+// m + 1 offsets from 0; an empty barcode is legal).  k_bc_exact against the session's n(w), which grows; the neighbour
+// pass that decides or defers (k_bc_neighbours_stream); the compaction to the retained records.  arena_n: the arena's
+// records before the batch.  Leaves the null stream idle.
+int whitelist_batch(const char *who, const BarcodeWhitelist &wl, const uint8_t *d_bc, const uint64_t *d_bc_off, const uint32_t *d_order, uint64_t m,
+                    uint64_t arena_n, WhitelistBatch *out);
+// finish: the neighbour pass over the pending list with n(w) complete; the winners' ids go to the arena's id column
+// (arena_n entries) at their positions, counts (5) are the pending records' statuses.
+int whitelist_finish(const char *who, const BarcodeWhitelist &wl, const uint8_t *d_pending, const uint64_t *d_pending_off,
+                     const uint32_t *d_pending_pos, uint64_t n_pending, uint32_t *d_arena_id, uint64_t arena_n, uint64_t *counts);
+// every cell's whitelist id and the number of its records that were corrected, from the arena's id column
+int whitelist_cell_summary(const BarcodeCells &cells, const uint32_t *d_arena_id, std::vector<uint32_t> *cell_label,
+                           std::vector<uint64_t> *cell_corrected);
+
 // The records d_order[0 .. m) of a resident padded blob with its offsets: bad2[0] = the smallest with a 0 byte, bad2[1] =
 // the smallest without a byte, ~0 where there is none.  The records that are not in d_order are not looked at.
 int validate_records_of(const uint32_t *d_order, uint64_t m, const uint8_t *d_blob, const uint64_t *d_off, unsigned long long *bad2);

@@ -317,6 +317,46 @@ extern "C" int oem_test_correct_barcodes_host(const oem_barcode_rule *rule, cons
     OEM_API_END("oem_test_correct_barcodes_host")
 }
 
+// Test hook: the streamed walk of oem_barcode_correct.h (correct_barcodes_stream_host, "The rule in a session"): the input
+// of the hook above cut into n_batches batches at batch_off (n_batches + 1 entries from 0 to the number of records), with
+// a flag per record for the unmapped ones (or NULL).  Checked and worded as the hook above.  out_order is 64 bits wide;
+// out_cell_label / out_cell_corrected have room for rule->n_labels cells; out_info: the records rejected and deferred.
+extern "C" int oem_test_correct_barcodes_stream_host(const oem_barcode_rule *rule, const uint8_t *barcodes, const uint64_t *barcode_off,
+                                                     const uint64_t *batch_off, uint64_t n_batches, const uint8_t *unmapped, uint32_t *out_id,
+                                                     uint8_t *out_status, uint64_t *out_order, uint64_t *out_cell_rec_off,
+                                                     uint32_t *out_cell_label, uint64_t *out_cell_corrected, uint64_t *out_n_cells,
+                                                     uint64_t *out_n_accepted, uint64_t *out_counts, uint64_t *out_info)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_test_correct_barcodes_stream_host";
+    if (!barcode_off || !batch_off || !out_n_cells || !out_n_accepted || !out_info)
+        return fail(OEM_ERR_ARG, "%s: barcode_off, batch_off, out_n_cells, out_n_accepted or out_info is NULL", who);
+    *out_n_cells = 0;
+    *out_n_accepted = 0;
+    OEM_TRY(check_barcode_rule(who, rule));
+    OEM_TRY(check_offsets(who, "batch_off", batch_off, n_batches, "batch"));
+    const uint64_t n_records = batch_off[n_batches];
+    OEM_TRY(check_barcode_input(who, barcodes, barcode_off, n_records));
+    static const uint8_t acgt[4] = {'A', 'C', 'G', 'T'};
+    const uint32_t hash_bits = (uint32_t)std::min<long>(std::max<long>(knob("OEM_BARCODE_HASH_BITS", 64), 0), 64);
+    const uint64_t slots0 = (uint64_t)std::max<long>(knob("OEM_BARCODE_TABLE_SLOTS0", (long)kBarcodeTableSlots0), 2);
+    const BarcodeCorrectHost info = correct_barcodes_stream_host(
+        rule->labels, rule->label_off, rule->n_labels, rule->multi, rule->alphabet ? rule->alphabet : acgt, rule->alphabet ? rule->n_alphabet : 4u,
+        barcodes, barcode_off, batch_off, n_batches, unmapped, out_id, out_status, out_order, out_cell_rec_off, out_cell_label, out_cell_corrected,
+        out_n_cells, out_n_accepted, out_counts, out_info, out_info + 1, hash_bits, slots0);
+    if (info.zero_label != kBarcodeNoIndex)
+        return fail(OEM_ERR_ARG, "%s: label %llu of the whitelist contains a 0 byte", who, (unsigned long long)info.zero_label);
+    if (info.broken) return fail(OEM_ERR_STATE, "%s: the whitelist table is broken", who);
+    if (info.equal_j != kBarcodeNoIndex)
+        return fail(OEM_ERR_ARG, "%s: labels %llu and %llu of the whitelist are equal", who, (unsigned long long)info.equal_i,
+                    (unsigned long long)info.equal_j);
+    if (info.zero_barcode != kBarcodeNoIndex)
+        return fail(OEM_ERR_ARG, "%s: the barcode of record %llu contains a 0 byte", who, (unsigned long long)info.zero_barcode);
+    if (out_cell_rec_off && *out_n_cells == 0) out_cell_rec_off[0] = 0;
+    return OEM_OK;
+    OEM_API_END("oem_test_correct_barcodes_stream_host")
+}
+
 // Test hook: the host walk of oem_gene_counts.h (gene_counts_host) with oem_cells_gene_counts' arguments minus the device,
 // checked and worded as the device call, and its kind of result.
 extern "C" int oem_test_cells_gene_counts_host(const uint64_t *cell_off, uint32_t n_cells, const uint32_t *col, const float *val,

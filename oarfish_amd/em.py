@@ -974,12 +974,30 @@ class CellsStream:
     of the read's first record, UMI), and UMIs one mismatch away from a more abundant one corrected to it.  With
     ``umi_correct``, ``cells()`` gains ``cell_corrected`` and ``info()["umi_corrected_reads"]`` counts them.  The any-order
     form gives exactly what ``em_cells_records_sparse(..., umis=, gene_of=, umi_correct=)`` gives on the surviving records.
+
+    ``whitelist`` (with ``barcodes=True, collated=False``; ``barcode_multi`` and ``barcode_alphabet`` go with it) is the
+    WHITELIST session (``oem_cells_stream_set_whitelist``): the batches' barcodes are RAW (``CR`` tags) and every batch is
+    matched against the whitelist on the device, as ``correct_barcodes`` does it.  A record rejected in its batch is
+    dropped there -- its name, UMI and ``ref_id`` are never looked at --, and under ``barcode_multi`` a barcode between
+    several labels waits for ``finish()``, which decides it with the complete counts.  Unmapped records take no part.
+    ``finish()`` gives exactly what ``em_cells_records_sparse(..., barcodes=, whitelist=)`` gives on the mapped records;
+    ``cells()`` describes the accepted records, its ``barcodes`` are the whitelist's labels, and it gains ``cell_wl_id``,
+    ``cell_bc_corrected`` and ``counts``; ``info()`` has ``barcode_rejected`` and ``barcode_deferred``.  One difference
+    from the one call: a deferred record is checked in its batch, so an error in its name, UMI or ``ref_id`` is the
+    session's even if ``finish()`` then rejects the record.
     """
 
     def __init__(self, n_txps: int, max_iter: int = 1000, conv_thresh: float = 1e-3, coverage=None, device: int = 0,
                  group_nnz: int = 0, group_cells: int = 0, max_staged_nnz: int = 0, filters=None, txp_len=None,
                  barcodes: bool = False, mode: str = "sort", collated: bool = True, umis: bool = False, gene_of=None,
-                 umi_correct: bool = False):
+                 umi_correct: bool = False, whitelist=None, barcode_multi: bool = False, barcode_alphabet=None):
+        if whitelist is not None and not barcodes:
+            raise ValueError("whitelist goes with barcodes=True: it is what a barcoded session's raw barcodes are corrected against")
+        if whitelist is not None and collated:
+            raise ValueError("whitelist goes with collated=False: corrected barcodes would scatter one label over many cells of a "
+                             "collated session")
+        if whitelist is None and (barcode_multi or barcode_alphabet is not None):
+            raise ValueError("barcode_multi goes with whitelist (and so does barcode_alphabet)")
         if umis and not barcodes:
             raise ValueError("umis=True goes with barcodes=True: only a barcoded session takes UMIs")
         if (gene_of is not None or umi_correct) and not umis:
@@ -1004,6 +1022,7 @@ class CellsStream:
         self._any_order = bool(barcodes) and not collated
         self._umis = bool(umis)
         self._umi_correct = bool(umi_correct)
+        self._whitelist = whitelist is not None
         self._device = device
         records_txp_len = txp_len
         o = _lib.CellsStreamOptsC()
@@ -1041,6 +1060,9 @@ class CellsStream:
                     if gene_of is not None or umi_correct:
                         rule, _gene = _umi_rule(gene_of, umi_correct)   # (the session copies gene_of)
                         self._check(self._L.oem_cells_stream_set_umi_rule(self._h, C.addressof(rule)))
+                    if whitelist is not None:
+                        wl_rule, _wl = _barcode_rule(whitelist, barcode_multi, barcode_alphabet)   # (the session copies the arrays)
+                        self._check(self._L.oem_cells_stream_set_whitelist(self._h, C.addressof(wl_rule)))
             except BaseException:
                 self.close()
                 raise
@@ -1178,7 +1200,9 @@ class CellsStream:
         record at every collated position), ``group_off``, ``cell_group_off``, ``kept`` and ``n_unmapped``.  A UMI
         session: all of them describe the deduplicated collation, and ``cell_dups`` (uint64) are the duplicate reads that
         every cell lost; with ``umi_correct`` also ``cell_corrected`` (uint64), the reads of every cell whose UMI was
-        corrected."""
+        corrected.  A whitelist session: they describe the accepted records, ``barcodes`` are the whitelist's labels, and
+        ``cell_wl_id`` (uint32: every cell's label index), ``cell_bc_corrected`` (uint64: the records of every cell whose
+        barcode was corrected) and ``counts`` (uint64, the mapped records of each ``OEM_BARCODE_*`` status) come with them."""
         if self._cells is None:
             raise _lib.OemError(_lib.OEM_ERR_STATE, "cells(): a finished barcoded session has them")
         return self._cells
@@ -1208,6 +1232,12 @@ class CellsStream:
             corrected = np.zeros(max(nc, 1), dtype=np.uint64)
             self._check(self._L.oem_cells_stream_umi_rule_copy(self._h, corrected.ctypes.data))
             out["cell_corrected"] = corrected[:nc]
+        if self._whitelist:
+            wl_id = np.zeros(max(nc, 1), dtype=np.uint32)
+            bc_corrected = np.zeros(max(nc, 1), dtype=np.uint64)
+            counts = np.zeros(5, dtype=np.uint64)
+            self._check(self._L.oem_cells_stream_whitelist_copy(self._h, wl_id.ctypes.data, bc_corrected.ctypes.data, counts.ctypes.data))
+            out["cell_wl_id"], out["cell_bc_corrected"], out["counts"] = wl_id[:nc], bc_corrected[:nc], counts
         return out
 
     def finish(self):
@@ -1246,7 +1276,9 @@ class CellsStream:
                     arena_bytes=_lib.OEM_CELLS_STREAM_INFO_ARENA_BYTES, barcode_misses=_lib.OEM_CELLS_STREAM_INFO_BARCODE_MISSES,
                     barcode_table_slots=_lib.OEM_CELLS_STREAM_INFO_BARCODE_TABLE_SLOTS,
                     umi_dup_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_READS, umi_dup_records=_lib.OEM_CELLS_STREAM_INFO_UMI_DUP_RECORDS,
-                    umi_corrected_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS)
+                    umi_corrected_reads=_lib.OEM_CELLS_STREAM_INFO_UMI_CORRECTED_READS,
+                    barcode_rejected=_lib.OEM_CELLS_STREAM_INFO_BARCODE_REJECTED,
+                    barcode_deferred=_lib.OEM_CELLS_STREAM_INFO_BARCODE_DEFERRED)
         out = {}
         for name, key in keys.items():
             v = C.c_uint64(0)

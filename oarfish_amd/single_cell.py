@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import writers
-from .em import CellsStream
+from .em import CellsStream, _n_packed
 
 
 @dataclass
@@ -38,7 +38,15 @@ class SingleCellArgs:
     gene_names: Optional[Sequence[str]] = None  # one name per gene id, for `.gene_features.txt`
     umi_correct: bool = False              # with umis: UMIs one mismatch from a more abundant one are corrected to it
     gene_counts: bool = False              # True: `.gene_count.mtx` and `.gene_features.txt` beside `.count.mtx`
+    whitelist: Optional[Sequence[bytes]] = None  # the batches' barcodes are raw (CR): corrected against these labels (collated=False)
+    barcode_multi: bool = False            # with whitelist: of several neighbours the one with strictly the most exact records wins
     extra_info: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        if self.whitelist is not None and self.collated:
+            raise ValueError("whitelist requires collated=False: only the any-order barcoded session corrects raw barcodes")
+        if self.whitelist is None and self.barcode_multi:
+            raise ValueError("barcode_multi goes with whitelist")
 
 
 def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], txp_lens: Sequence[int], batches,
@@ -60,7 +68,13 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
     collapsed to cells x genes on the device (``em.cells_gene_counts``) and written as `.gene_count.mtx` with
     `.gene_features.txt` (``writers.write_single_cell_gene_output_device``); ``args.gene_names`` names the genes,
     `.meta_info.json` gains ``gene_counts`` and ``n_genes``, and ``cells`` gains ``gene_counts = (indptr_g, genes,
-    vals_g)``."""
+    vals_g)``.
+
+    With ``args.whitelist`` (and ``args.collated=False``) the batches' barcodes are raw and the session corrects them
+    against the whitelist (``CellsStream(..., whitelist=, barcode_multi=)``): `.barcodes.txt` gets the whitelist's labels,
+    never a record's raw bytes, `.meta_info.json` gains ``barcode_whitelist_labels``, ``barcode_multi`` and the five counts
+    (``barcode_exact``, ``barcode_corrected``, ``barcode_no_neighbour``, ``barcode_ambiguous``, ``barcode_missing``), and
+    ``cells`` carries ``cell_wl_id``, ``cell_bc_corrected`` and ``counts``."""
     txp_len = np.asarray(txp_lens, dtype=np.uint64)
     gene_of = None if args.gene_of is None else np.asarray(args.gene_of)
     if gene_of is not None and (gene_of.ndim != 1 or len(gene_of) != len(txp_len)):
@@ -78,6 +92,8 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
         if len(args.gene_names) != n_genes:
             raise ValueError(f"gene_names must name the {n_genes} genes of gene_of, not {len(args.gene_names)}")
     rule = dict(gene_of=gene_of, umi_correct=args.umi_correct) if args.umis else {}
+    if args.whitelist is not None:
+        rule.update(whitelist=args.whitelist, barcode_multi=args.barcode_multi)
     coverage = None
     if args.model_coverage is not None:
         coverage = dict(model=args.model_coverage, bin_width=args.bin_width, growth_rate=args.growth_rate, txp_len=txp_len)
@@ -104,6 +120,11 @@ def quantify_single_cell_from_record_batches(filters, txps_name: Sequence[str], 
             info["umi_correct"] = bool(args.umi_correct)
         if args.umi_correct:
             info["umi_corrected_reads"] = int(cells["cell_corrected"].sum())
+    if args.whitelist is not None:
+        info["barcode_whitelist_labels"] = _n_packed(args.whitelist)
+        info["barcode_multi"] = bool(args.barcode_multi)
+        for k, word in enumerate(("exact", "corrected", "no_neighbour", "ambiguous", "missing")):
+            info["barcode_" + word] = int(cells["counts"][k])
     if args.gene_counts:
         info["gene_counts"] = True
         info["n_genes"] = n_genes

@@ -76,6 +76,13 @@ With the peak device memory of each, arena_bytes, the duplicates dropped and (a)
 with the cells' barcodes drawn from a 3 M-label whitelist and errors in the barcodes of 5 % of the reads; the whitelist
 one call on the raw barcodes against the UMI-rule one call on the clean ones, alternated in one process.
 
+--whitelist-stream is the leg of barcode correction in the any-order session (profiles/cells_whitelist_stream_bench.json):
+the --whitelist leg's input cut by synth.cut_interleaved_records at the first --batch-records (2 Mi records), three legs
+alternated in one process, five repeats each: (s) the whitelist session on the raw barcodes
+(CellsStream(..., collated=False, whitelist=, barcode_multi=True)); (w) the whitelist one call on the concatenation; (c)
+the any-order UMI-rule session on the clean barcodes.  Reported: (s) - (c), (s) / (w), the records rejected and deferred,
+and the arena's peak.
+
 --umis-rule-stream is the leg of the UMI rule in the sessions (profiles/cells_umis_rule_stream_bench.json): the
 --umis-stream leg's input with synth.add_umi_errors(rate=0.05) and a synthetic gene_of, alternated in one process at the
 first --batch-records, one pushing thread: both session forms under (a) the exact rule, (b) gene keys, (c) gene keys plus
@@ -503,6 +510,112 @@ def whitelist_leg(args, cr, res, save):
         del rec, names, sec, bc, raw, umis
 
 
+def whitelist_stream_leg(args, cr, res, save):
+    """The --whitelist-stream leg: the --whitelist leg's input (raw barcodes against a whitelist of --whitelist-labels labels,
+    UMIs with duplicates and errors, a synthetic annotation) cut by synth.cut_interleaved_records at the first
+    --batch-records.  Alternated in one process, from one pushing thread: (s) the whitelist session on the raw barcodes; (w)
+    the whitelist one call on the concatenation; (c) the any-order UMI-rule session on the clean barcodes, which is what the
+    parent commit offers a streaming caller whose barcodes were corrected elsewhere.  All under gene keys plus one-mismatch
+    UMI correction and barcode_multi.  Reported: best - worst of each, (s) - (c) beside (c)'s own spread, (s) / (w), the
+    records rejected and deferred, the cells, the arena's peak and the peak device memory of the first run."""
+    n = args.cells
+    f, tl = cr.filters, cr.txp_len
+    batch = args.batch_records[0]
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t0, out
+
+    def head(pair, m):
+        return pair[0][:int(pair[1][m])], pair[1][:m + 1]
+
+    whitelist = synth.make_whitelist(max(args.whitelist_labels, n))
+    labels = [whitelist[0][16 * c:16 * c + 16].tobytes() for c in range(n)]
+    res["whitelist_labels"] = int(len(whitelist[1]) - 1)
+    for style in args.styles:
+        rec0, names0, sec0, cro = synth.shuffle_cell_records(cr, style=style, threads=16)
+        rec1, names1, sec1, bc1, _ = synth.interleave_cells(rec0, names0, sec0, cro, labels, how="uniform")
+        del rec0, names0, sec0
+        rec, names, sec, bc, umis, copies = synth.add_umi_duplicates(rec1, names1, sec1, bc1, rate=0.1)
+        del rec1, names1, sec1, bc1
+        umis = synth.add_umi_errors(umis, 0.05, names=names, barcodes=bc)
+        raw = synth.add_barcode_errors(bc, 0.04, 0.01, names=names)
+        gene_of = synth.gene_of_txps(len(tl))
+        m = len(rec)
+        r = res[style] = dict(records=int(m), copied_reads=int(sum(copies.values())), barcode_error_rate=0.05, umi_error_rate=0.05,
+                              genes=int(gene_of[-1]) + 1, batch_records=int(batch))
+        rule = dict(gene_of=gene_of, umi_correct=True)
+
+        def batches(b, upto):
+            return synth.cut_interleaved_records(rec[:upto], head(names, upto), sec[:upto], head(b, upto), list(range(batch, upto, batch)),
+                                                 umis=head(umis, upto))
+
+        def session(leg, upto=m):
+            cut = batches(raw if leg == "s" else bc, upto)   # (views and slices: cut outside the clock)
+            wl = dict(whitelist=whitelist, barcode_multi=True) if leg == "s" else {}
+            info = {}
+
+            def go():
+                with oarfish_amd.CellsStream(len(tl), filters=f, txp_len=tl, barcodes=True, collated=False, umis=True, **rule, **wl) as cs:
+                    for records, barcodes, nm, secondary, um in cut:
+                        cs.push_batch(records, barcodes, nm, secondary, um)
+                    out = cs.finish()
+                    cells = cs.cells()
+                    info.update(cs.info(), n_cells=len(cells["barcodes"]), reads_counted=int(len(cells["kept"])))
+                    if leg == "s":
+                        info["counts"] = [int(x) for x in cells["counts"]]
+                return out
+            dt, out = clock(go)
+            return dt, out, info
+
+        def one_call(upto=m):
+            return oarfish_amd.em_cells_records_sparse(f, tl, rec[:upto], None, None, names=head(names, upto), secondary=sec[:upto],
+                                                       barcodes=head(raw, upto), umis=head(umis, upto), collate="device", whitelist=whitelist,
+                                                       barcode_multi=True, **rule)
+
+        warm = min(m, int(cro[min(args.warm_cells, n)]))
+        session("s", warm)
+        one_call(warm)
+        session("c", warm)
+        runs = dict(s=[], w=[], c=[])
+        for k in range(args.runs):
+            for leg in ("s", "w", "c"):
+                if leg == "w":
+                    if k == 0:
+                        with PeakDeviceMemory() as pk:
+                            dt, got = clock(one_call)
+                        r["peak_device_bytes_w"] = int(pk.peak)
+                        r["cells_w"], r["records_by_status_w"] = int(len(got[7]) - 1), [int(x) for x in got[12]]
+                    else:
+                        dt, got = clock(one_call)
+                    del got
+                else:
+                    if k == 0:
+                        with PeakDeviceMemory() as pk:
+                            dt, got, info = session(leg)
+                        r[f"peak_device_bytes_{leg}"] = int(pk.peak)
+                        r[f"cells_{leg}"], r[f"arena_peak_bytes_{leg}"] = info["n_cells"], info["arena_bytes"]
+                        if leg == "s":
+                            r["records_by_status_s"] = info["counts"]
+                            r["barcode_rejected"], r["barcode_deferred"] = info["barcode_rejected"], info["barcode_deferred"]
+                    else:
+                        dt, got, info = session(leg)
+                    del got
+                runs[leg].append(dt)
+            if k == 0:
+                assert r["records_by_status_s"] == r["records_by_status_w"] and r["cells_s"] == r["cells_w"], "the session is not the one call"
+            print(f"[bench] {style} run {k}: (s) {runs['s'][-1]:.3f} s, (w) {runs['w'][-1]:.3f} s, (c) {runs['c'][-1]:.3f} s", flush=True)
+            r["whitelist_session_on_raw_barcodes"] = spread(runs["s"])
+            r["whitelist_one_call_on_raw_barcodes"] = spread(runs["w"])
+            r["rule_session_on_clean_barcodes"] = spread(runs["c"])
+            r["whitelist_cost_s_s_minus_c"] = round(min(runs["s"]) - min(runs["c"]), 4)
+            r["session_over_one_call_s_over_w"] = round(min(runs["s"]) / min(runs["w"]), 3)
+            r["clean_session_own_spread_s"] = round(max(runs["c"]) - min(runs["c"]), 4)
+            save()
+        del rec, names, sec, bc, raw, umis
+
+
 def barcodes_stream_leg(args, cr, res, save):
     """The --barcodes-stream leg (see the module docstring); fills res[style] for every name style."""
     n = args.cells
@@ -878,7 +991,9 @@ def main():
                     help="the leg of the UMI rule: the exact one call against gene keys, gene keys plus correction, correction alone")
     ap.add_argument("--whitelist", action="store_true",
                     help="the leg of barcode correction: the whitelist one call on raw barcodes against the UMI-rule one call on clean ones")
-    ap.add_argument("--whitelist-labels", type=int, default=3_000_000, help="the --whitelist leg: labels of the whitelist")
+    ap.add_argument("--whitelist-labels", type=int, default=3_000_000, help="the --whitelist legs: labels of the whitelist")
+    ap.add_argument("--whitelist-stream", action="store_true",
+                    help="the leg of barcode correction in the any-order session against the whitelist one call and the session on clean barcodes")
     ap.add_argument("--barcodes-stream", action="store_true", help="the leg of the barcoded session against the one call and push_records(names=)")
     ap.add_argument("--barcodes-any-order-stream", action="store_true",
                     help="the leg of the any-order barcoded session against the one barcodes call on the concatenation")
@@ -891,9 +1006,10 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs is None:
-        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.whitelist or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream or args.umis_rule_stream else 3
+        args.runs = 5 if args.names or args.barcodes or args.umis or args.umis_rule or args.whitelist or args.whitelist_stream or args.barcodes_stream or args.barcodes_any_order_stream or args.umis_stream or args.umis_rule_stream else 3
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "cells_umis_rule_stream_bench.json" if args.umis_rule_stream else
+        args.out = os.path.join(ROOT, "profiles", "cells_whitelist_stream_bench.json" if args.whitelist_stream else
+                                "cells_umis_rule_stream_bench.json" if args.umis_rule_stream else
                                 "cells_umis_stream_bench.json" if args.umis_stream else
                                 "cells_barcodes_any_order_stream_bench.json" if args.barcodes_any_order_stream else
                                 "cells_barcodes_stream_bench.json" if args.barcodes_stream else
@@ -963,6 +1079,10 @@ def main():
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "columns differ"
         return float(np.max(np.abs(got[2] - want[2]) / np.maximum(np.abs(want[2]), 1e-3))) if len(want[2]) else 0.0
 
+    if args.whitelist_stream:
+        whitelist_stream_leg(args, cr, res, save)
+        print(json.dumps(res))
+        return
     if args.umis_rule_stream:
         umis_rule_stream_leg(args, cr, res, save)
         print(json.dumps(res))
