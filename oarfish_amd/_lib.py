@@ -383,6 +383,10 @@ def testing_lib() -> C.CDLL:
         L.oem_debug_records_stream_last_join.argtypes = [vp]
         L.oem_debug_records_names_last_call.argtypes = [vp]
         L.oem_test_parse_bulk_host.argtypes = [vp, u64, vp, vp, vp, u32, u64, vp, vp, vp]
+        L.oem_test_lane_runs.argtypes = [u32, vp, vp, u32, u32, vp, vp, i32]
+        L.oem_test_remote_fold.argtypes = [vp, u32, vp, vp, vp, u32, u32, u32, u32, i32, i32]
+        L.oem_test_remote_fold_b.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, vp, u32, i32]
+        L.oem_test_multi_fold_reldiff.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, i32]
         _testing = L
     return _testing
 

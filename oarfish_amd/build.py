@@ -32,7 +32,7 @@ SOURCES = ["oem_api.hip", "oem_em_driver.hip", "oem_assignment_text.hip", "oem_l
            "oem_multi_kernels.hip", "oem_layout.cpp", "oem_layout_device.hip", "oem_layout_pack.hip", "oem_layout_dict.hip", "oem_coverage_device.hip", "oem_coverage_cells.hip", "oem_filter_device.hip", "oem_filter_projected_device.hip",
            "oem_builder.cpp", "oem_builder_projected.cpp", "oem_comm.cpp", "oem_p2p.hip", "oem_knobs.cpp"]
 # the testing library swaps these for their -DOEM_TESTING build and adds the hooks
-TESTING_VARIANTS = ["oem_comm.cpp", "oem_knobs.cpp", "oem_tile_kernels.hip", "oem_batch_kernels.hip"]
+TESTING_VARIANTS = ["oem_comm.cpp", "oem_knobs.cpp", "oem_tile_kernels.hip", "oem_batch_kernels.hip", "oem_multi_kernels.hip"]
 TESTING_ONLY = ["oem_testing.hip"]
 HEADERS = ["oem_internal.h", "oem_stopping_rule.h", "oem_text_format.h", "oem_shortest_f32.h", "oem_shortest_f64.h", "oem_lz4.h", "oem_filter.h", "oem_collate.h", "oem_gene_counts.h", "oem_barcode_table.h", "oem_barcode_correct.h", "oem_collate_device.h", "oem_parse_device.h", "oem_dev_blob.h", "oem_stage_queue.h", "oem_filter_projected.h", "oem_exp_f32.h", "oem_filter_device.h", "oem_driver.h", "oem_cells.h", "oem_cells_barcodes_stream.h", "oem_layout.h", "oem_tile_common.h", "oem_lane_runs.h", "oem_coverage_common.h", os.path.join(INCLUDE, "oarfish_em.h")]
 
@@ -114,7 +114,8 @@ TESTING_HOOKS = ["oem_debug_layout_hash", "oem_debug_local_comm_create", "oem_te
                  "oem_debug_records_names_last_call", "oem_test_parse_bulk_host", "oem_debug_barcode_table_last",
                  "oem_test_dedup_umis_host", "oem_test_dedup_umis_rule_host", "oem_debug_dedup_rule_last_call",
                  "oem_test_cells_gene_counts_host", "oem_debug_gene_counts_last_call", "oem_test_correct_barcodes_host",
-                 "oem_test_correct_barcodes_stream_host"]
+                 "oem_test_correct_barcodes_stream_host", "oem_test_lane_runs", "oem_test_remote_fold", "oem_test_remote_fold_b",
+                 "oem_test_multi_fold_reldiff"]
 
 
 def header_symbols() -> list:

@@ -1061,4 +1061,17 @@ extern "C" int oem_debug_tile_e_probe_end(unsigned long long *out, uint64_t n_ou
     return OEM_OK;
     OEM_API_END("oem_debug_tile_e_probe_end")
 }
+// One launch of k_remote_fold_b on caller-made arrays (oem_test_remote_fold_b, oem_testing.hip), shaped as launch_batch_pass
+// shapes it.
+int oem::launch_test_remote_fold_b(hipStream_t st, uint32_t n_buckets, const uint32_t *bucket_base, const double *queue,
+                                   const uint16_t *q_dst, const double *theta, double *cnt, const BatchState *state, uint32_t n_groups,
+                                   uint32_t n_txps)
+{
+    constexpr size_t kFoldLds = sizeof(double) * kBucket * kFS;
+    OEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_remote_fold_b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFoldLds));
+    hipLaunchKernelGGL(k_remote_fold_b, dim3(n_buckets * n_groups, kB / kFS), dim3(kFoldThreadsB), kFoldLds, st, bucket_base, queue, q_dst,
+                       theta, cnt, state, n_groups, n_txps);
+    OEM_HIP(hipGetLastError());
+    return OEM_OK;
+}
 #endif

@@ -378,6 +378,19 @@ int launch_batch_reset_slot(oem_store *s, const BatchBuffers &bb, const double *
 int launch_batch_pack_row_w(oem_store *s, const uint32_t *d_row_w, const BatchBuffers &bb, uint32_t slot,
                             uint32_t *d_overflow);
 
+// The three fold kernels on caller-made device arrays, one launch each, for the hooks of oem_testing.hip (the kernels sit
+// in their translation units' anonymous namespaces).  Defined in the -DOEM_TESTING builds only: the product has none of them.
+// k_remote_fold<ntq, threads> (threads: 1024 or 256), problems = NULL, no deferred rule; `state` may be NULL
+int launch_test_remote_fold(hipStream_t st, uint32_t n_buckets, const uint32_t *bucket_base, const double *queue, const uint16_t *q_dst,
+                            double *cnt, const EmState *state, uint32_t n_groups, uint32_t n_txps, bool ntq, uint32_t threads);
+// k_remote_fold_b: queue [entry][kBatch], theta and cnt [T][kBatch], state[kBatch]
+int launch_test_remote_fold_b(hipStream_t st, uint32_t n_buckets, const uint32_t *bucket_base, const double *queue, const uint16_t *q_dst,
+                              const double *theta, double *cnt, const BatchState *state, uint32_t n_groups, uint32_t n_txps);
+// k_multi_fold_reldiff over every bucket (no live list): state[n_txps / T]
+int launch_test_multi_fold_reldiff(hipStream_t st, uint32_t n_buckets, const uint32_t *bucket_base, const double *queue,
+                                   const uint16_t *q_dst, double *theta, double *cnt, double *out, BatchState *state, uint32_t n_txps,
+                                   uint32_t T);
+
 int launch_aux_counts(oem_store *s, uint32_t *d_unique, uint32_t *d_total);
 int launch_assignment_probs(oem_store *s, const double *d_counts, double display_thresh, double *d_out);
 int launch_fill(oem_store *s, double *p, double v, uint64_t n);

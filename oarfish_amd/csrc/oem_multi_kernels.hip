@@ -261,6 +261,20 @@ int launch_multi_fold_reldiff(oem_store *s, double *theta, double *cnt, const Mu
     return OEM_OK;
 }
 
+#ifdef OEM_TESTING
+// One launch of k_multi_fold_reldiff on caller-made arrays (oem_test_multi_fold_reldiff, oem_testing.hip): the fold and the
+// sweep alone, without the state machine's k_multi_decide.
+int launch_test_multi_fold_reldiff(hipStream_t st, uint32_t n_buckets, const uint32_t *bucket_base, const double *queue,
+                                   const uint16_t *q_dst, double *theta, double *cnt, double *out, BatchState *state, uint32_t n_txps,
+                                   uint32_t T)
+{
+    hipLaunchKernelGGL(k_multi_fold_reldiff, dim3(n_buckets), dim3(kFT), 0, st, bucket_base, queue, q_dst, theta, cnt, out, state, n_txps,
+                       T, (const uint32_t *)nullptr);
+    OEM_HIP(hipGetLastError());
+    return OEM_OK;
+}
+#endif
+
 int multi_compact_live(oem_store *s, MultiBuffers &mb)
 {
     const DeviceTiled &t = s->tiled;

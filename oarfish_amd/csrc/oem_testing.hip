@@ -2,8 +2,9 @@
 //
 // Nothing in this file is part of the product (liboarfish_em.so is linked without it) or of the
 // public header.  tests/ and scripts/ use it to look inside a resident store (layout hashes), to
-// hammer the stopping-rule kernel in isolation, and -- together with the OEM_TESTING build of
-// oem_comm.cpp -- to run the row-sharded loop with several shards on one GPU.
+// hammer the stopping-rule kernel in isolation, to run the remote folds on crafted queues, and --
+// together with the OEM_TESTING build of oem_comm.cpp -- to run the row-sharded loop with several
+// shards on one GPU.
 #include <atomic>
 #include <cstring>
 #include <thread>
@@ -606,4 +607,221 @@ extern "C" int oem_test_reldiff_stress(uint32_t n_txps, uint32_t n_launches, uin
     s.stream = nullptr;
     return rc;
     OEM_API_END("oem_test_reldiff_stress")
+}
+
+// ---------------------------------------------------------------------------
+// The remote folds on crafted queues (tests/test_remote_fold_gpu.py).  A fold is a scatter-add: with integer-valued
+// doubles every order of summation gives the same bits, so each of the hooks below can be held to numpy's add.at
+// exactly.  oem_test_lane_runs runs the lane-level helpers of oem_lane_runs.h alone, one wavefront per case; the three
+// others launch one fold kernel once on caller-made arrays (launchers: oem_internal.h) and copy the results back.
+// Every index a kernel would use unchecked is checked here first.
+// ---------------------------------------------------------------------------
+#include "oem_lane_runs.h"
+
+namespace {
+
+// Lanes < n_active of every wavefront call keys_repeat and sum_runs_of_equal_keys, the others stay out under a real
+// branch (a partial exec mask, as in the last trip of a fold's loop); vals / out_vals: [lane][kStride].
+template <int kStride>
+__global__ __launch_bounds__(256) void k_test_lane_runs(const uint32_t *__restrict__ keys, const double *__restrict__ vals, uint32_t n_waves,
+                                                        uint32_t n_active, double *__restrict__ out_vals, uint32_t *__restrict__ out_repeat)
+{
+    const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (wave >= n_waves) return;
+    const size_t i = (size_t)wave * 64 + lane;
+    const uint32_t d = keys[i];
+    double v[kStride];
+#pragma unroll
+    for (int j = 0; j < kStride; ++j) v[j] = vals[i * kStride + j];
+    if (lane < n_active) {
+        const bool rep = keys_repeat<kStride>(d);
+        sum_runs_of_equal_keys<kStride, kStride>(d, v);
+        if (lane == 0) out_repeat[wave] = rep ? 1u : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < kStride; ++j) out_vals[i * kStride + j] = v[j];
+}
+
+// device copies of a hook's arrays: freed when the hook returns, whichever way
+struct TestArrays {
+    std::vector<void *> mem;
+    ~TestArrays() { for (void *p : mem) (void)hipFree(p); }
+    template <typename T>
+    int up(T **d, const T *h, size_t n, hipStream_t st) // (one element at least: an empty queue still has an address)
+    {
+        void *p = nullptr;
+        OEM_HIP(hipMalloc(&p, sizeof(T) * (n ? n : 1)));
+        mem.push_back(p);
+        *d = static_cast<T *>(p);
+        if (n && h) OEM_HIP(hipMemcpyAsync(p, h, sizeof(T) * n, hipMemcpyHostToDevice, st));
+        else OEM_HIP(hipMemsetAsync(p, 0, sizeof(T) * (n ? n : 1), st));
+        return OEM_OK;
+    }
+};
+struct TestStream {
+    hipStream_t st = nullptr;
+    ~TestStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+};
+
+// what every fold reads unchecked: bucket b's range [bucket_base[b], bucket_base[b + 1]) of the queue, destinations inside
+// the LDS window; the buckets cover the transcripts
+int check_fold_queue(const char *who, const uint32_t *bucket_base, uint32_t n_buckets, const uint16_t *q_dst, uint32_t n_txps)
+{
+    if (!bucket_base || !n_txps || n_buckets != (n_txps + kBucket - 1) / kBucket)
+        return fail(OEM_ERR_ARG, "%s: n_buckets = %u does not cover n_txps = %u", who, n_buckets, n_txps);
+    OEM_TRY(check_offsets(who, "bucket_base", bucket_base, n_buckets, "bucket"));
+    if (bucket_base[n_buckets] && !q_dst) return fail(OEM_ERR_ARG, "%s: q_dst is NULL", who);
+    for (uint32_t i = 0; i < bucket_base[n_buckets]; ++i)
+        if (q_dst[i] >= kBucket) return fail(OEM_ERR_ARG, "%s: q_dst[%u] = %u is outside the window", who, i, (unsigned)q_dst[i]);
+    return OEM_OK;
+}
+
+} // namespace
+
+// keys [n_waves][64], vals and out_vals [n_waves][64][stride], out_repeat [n_waves]: the wave's keys_repeat<stride>
+extern "C" int oem_test_lane_runs(uint32_t stride, const uint32_t *keys, const double *vals, uint32_t n_waves, uint32_t n_active,
+                                  double *out_vals, uint32_t *out_repeat, int device)
+{
+    OEM_API_BEGIN
+    if ((stride != 1 && stride != 2) || !keys || !vals || !n_waves || !n_active || n_active > 64 || !out_vals || !out_repeat)
+        return fail(OEM_ERR_ARG, "oem_test_lane_runs: bad argument");
+    OEM_HIP(hipSetDevice(device));
+    TestStream ts;
+    OEM_HIP(hipStreamCreateWithFlags(&ts.st, hipStreamNonBlocking));
+    TestArrays a;
+    const size_t n = (size_t)n_waves * 64;
+    uint32_t *d_keys = nullptr, *d_rep = nullptr;
+    double *d_vals = nullptr, *d_out = nullptr;
+    OEM_TRY(a.up(&d_keys, keys, n, ts.st));
+    OEM_TRY(a.up(&d_vals, vals, n * stride, ts.st));
+    OEM_TRY(a.up(&d_out, (const double *)nullptr, n * stride, ts.st));
+    OEM_TRY(a.up(&d_rep, (const uint32_t *)nullptr, n_waves, ts.st));
+    const uint32_t grid = (n_waves + 3) / 4;
+    if (stride == 1) hipLaunchKernelGGL(k_test_lane_runs<1>, dim3(grid), dim3(256), 0, ts.st, d_keys, d_vals, n_waves, n_active, d_out, d_rep);
+    else hipLaunchKernelGGL(k_test_lane_runs<2>, dim3(grid), dim3(256), 0, ts.st, d_keys, d_vals, n_waves, n_active, d_out, d_rep);
+    OEM_HIP(hipGetLastError());
+    OEM_HIP(hipMemcpyAsync(out_vals, d_out, sizeof(double) * n * stride, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipMemcpyAsync(out_repeat, d_rep, sizeof(uint32_t) * n_waves, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipStreamSynchronize(ts.st));
+    return OEM_OK;
+    OEM_API_END("oem_test_lane_runs")
+}
+
+// One launch of k_remote_fold<ntq, threads> with n_groups workgroups per bucket: cnt (n_txps, in and out) += the queue's
+// entries, entry i of bucket b into cnt[b * kBucket + q_dst[i]].  done: -1 no loop state, else EmState::done of the launch.
+extern "C" int oem_test_remote_fold(const uint32_t *bucket_base, uint32_t n_buckets, const double *queue, const uint16_t *q_dst,
+                                    double *cnt, uint32_t n_txps, uint32_t n_groups, uint32_t ntq, uint32_t threads, int done, int device)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_test_remote_fold";
+    OEM_TRY(check_fold_queue(who, bucket_base, n_buckets, q_dst, n_txps));
+    const uint32_t n = bucket_base[n_buckets];
+    if (!cnt || (n && !queue) || !n_groups || (threads != 1024 && threads != 256) || done < -1 || done > 1)
+        return fail(OEM_ERR_ARG, "%s: bad argument", who);
+    EmState h_state;
+    std::memset(&h_state, 0, sizeof h_state);
+    h_state.done = done > 0 ? 1u : 0u;
+    OEM_HIP(hipSetDevice(device));
+    TestStream ts;
+    OEM_HIP(hipStreamCreateWithFlags(&ts.st, hipStreamNonBlocking));
+    TestArrays a;
+    uint32_t *d_base = nullptr;
+    double *d_queue = nullptr, *d_cnt = nullptr;
+    uint16_t *d_dst = nullptr;
+    EmState *d_state = nullptr;
+    OEM_TRY(a.up(&d_base, bucket_base, (size_t)n_buckets + 1, ts.st));
+    OEM_TRY(a.up(&d_queue, queue, n, ts.st));
+    OEM_TRY(a.up(&d_dst, q_dst, n, ts.st));
+    OEM_TRY(a.up(&d_cnt, (const double *)cnt, n_txps, ts.st));
+    if (done >= 0) OEM_TRY(a.up(&d_state, (const EmState *)&h_state, 1, ts.st));
+    OEM_TRY(launch_test_remote_fold(ts.st, n_buckets, d_base, d_queue, d_dst, d_cnt, d_state, n_groups, n_txps, ntq != 0, threads));
+    OEM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof(double) * n_txps, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipStreamSynchronize(ts.st));
+    return OEM_OK;
+    OEM_API_END("oem_test_remote_fold")
+}
+
+// One launch of k_remote_fold_b: queue [entry][n_slots], theta and cnt (in and out) [n_txps][n_slots], phases [n_slots]
+// (kPhaseRunning 0, kPhaseFinal 1, kPhaseFinished 2).  n_slots must be the library's kBatch.
+extern "C" int oem_test_remote_fold_b(const uint32_t *bucket_base, uint32_t n_buckets, const double *queue, const uint16_t *q_dst,
+                                      const double *theta, double *cnt, uint32_t n_txps, uint32_t n_groups, const uint32_t *phases,
+                                      uint32_t n_slots, int device)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_test_remote_fold_b";
+    if (n_slots != (uint32_t)kBatch) return fail(OEM_ERR_ARG, "%s: n_slots = %u, the library is built for %d", who, n_slots, kBatch);
+    OEM_TRY(check_fold_queue(who, bucket_base, n_buckets, q_dst, n_txps));
+    const uint32_t n = bucket_base[n_buckets];
+    if (!theta || !cnt || !phases || (n && !queue) || !n_groups) return fail(OEM_ERR_ARG, "%s: bad argument", who);
+    BatchState h_state[kBatch];
+    std::memset(h_state, 0, sizeof h_state);
+    for (int b = 0; b < kBatch; ++b) {
+        if (phases[b] > kPhaseFinished) return fail(OEM_ERR_ARG, "%s: phases[%d] = %u", who, b, phases[b]);
+        h_state[b].phase = phases[b];
+    }
+    OEM_HIP(hipSetDevice(device));
+    TestStream ts;
+    OEM_HIP(hipStreamCreateWithFlags(&ts.st, hipStreamNonBlocking));
+    TestArrays a;
+    uint32_t *d_base = nullptr;
+    double *d_queue = nullptr, *d_theta = nullptr, *d_cnt = nullptr;
+    uint16_t *d_dst = nullptr;
+    BatchState *d_state = nullptr;
+    OEM_TRY(a.up(&d_base, bucket_base, (size_t)n_buckets + 1, ts.st));
+    OEM_TRY(a.up(&d_queue, queue, (size_t)n * kBatch, ts.st));
+    OEM_TRY(a.up(&d_dst, q_dst, n, ts.st));
+    OEM_TRY(a.up(&d_theta, theta, (size_t)n_txps * kBatch, ts.st));
+    OEM_TRY(a.up(&d_cnt, (const double *)cnt, (size_t)n_txps * kBatch, ts.st));
+    OEM_TRY(a.up(&d_state, (const BatchState *)h_state, (size_t)kBatch, ts.st));
+    OEM_TRY(launch_test_remote_fold_b(ts.st, n_buckets, d_base, d_queue, d_dst, d_theta, d_cnt, d_state, n_groups, n_txps));
+    OEM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof(double) * n_txps * kBatch, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipStreamSynchronize(ts.st));
+    return OEM_OK;
+    OEM_API_END("oem_test_remote_fold_b")
+}
+
+// One launch of k_multi_fold_reldiff over every bucket: cell p owns transcripts [p T, (p + 1) T) of n_txps = n_cells T;
+// phases [n_cells]; theta, cnt, out (n_txps each) and rel_bits (n_cells: BatchState::rel_bits) go in and come back.
+extern "C" int oem_test_multi_fold_reldiff(const uint32_t *bucket_base, uint32_t n_buckets, const double *queue, const uint16_t *q_dst,
+                                           double *theta, double *cnt, double *out, uint32_t n_txps, uint32_t T, const uint32_t *phases,
+                                           uint64_t *rel_bits, int device)
+{
+    OEM_API_BEGIN
+    const char *who = "oem_test_multi_fold_reldiff";
+    OEM_TRY(check_fold_queue(who, bucket_base, n_buckets, q_dst, n_txps));
+    const uint32_t n = bucket_base[n_buckets];
+    if (!theta || !cnt || !out || !phases || !rel_bits || (n && !queue) || !T || n_txps % T)
+        return fail(OEM_ERR_ARG, "%s: bad argument", who);
+    const uint32_t n_cells = n_txps / T;
+    std::vector<BatchState> h_state(n_cells);
+    std::memset(h_state.data(), 0, sizeof(BatchState) * n_cells);
+    for (uint32_t p = 0; p < n_cells; ++p) {
+        if (phases[p] > kPhaseFinished) return fail(OEM_ERR_ARG, "%s: phases[%u] = %u", who, p, phases[p]);
+        h_state[p].phase = phases[p];
+        h_state[p].rel_bits = rel_bits[p];
+    }
+    OEM_HIP(hipSetDevice(device));
+    TestStream ts;
+    OEM_HIP(hipStreamCreateWithFlags(&ts.st, hipStreamNonBlocking));
+    TestArrays a;
+    uint32_t *d_base = nullptr;
+    double *d_queue = nullptr, *d_theta = nullptr, *d_cnt = nullptr, *d_out = nullptr;
+    uint16_t *d_dst = nullptr;
+    BatchState *d_state = nullptr;
+    OEM_TRY(a.up(&d_base, bucket_base, (size_t)n_buckets + 1, ts.st));
+    OEM_TRY(a.up(&d_queue, queue, n, ts.st));
+    OEM_TRY(a.up(&d_dst, q_dst, n, ts.st));
+    OEM_TRY(a.up(&d_theta, (const double *)theta, n_txps, ts.st));
+    OEM_TRY(a.up(&d_cnt, (const double *)cnt, n_txps, ts.st));
+    OEM_TRY(a.up(&d_out, (const double *)out, n_txps, ts.st));
+    OEM_TRY(a.up(&d_state, (const BatchState *)h_state.data(), n_cells, ts.st));
+    OEM_TRY(launch_test_multi_fold_reldiff(ts.st, n_buckets, d_base, d_queue, d_dst, d_theta, d_cnt, d_out, d_state, n_txps, T));
+    OEM_HIP(hipMemcpyAsync(theta, d_theta, sizeof(double) * n_txps, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof(double) * n_txps, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipMemcpyAsync(out, d_out, sizeof(double) * n_txps, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipMemcpyAsync(h_state.data(), d_state, sizeof(BatchState) * n_cells, hipMemcpyDeviceToHost, ts.st));
+    OEM_HIP(hipStreamSynchronize(ts.st));
+    for (uint32_t p = 0; p < n_cells; ++p) rel_bits[p] = h_state[p].rel_bits;
+    return OEM_OK;
+    OEM_API_END("oem_test_multi_fold_reldiff")
 }

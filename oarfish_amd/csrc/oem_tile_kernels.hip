@@ -822,4 +822,25 @@ extern "C" int oem_debug_overlap_probe(oem_store *s, uint32_t n, double *out_us)
     return rc;
     OEM_API_END("oem_debug_overlap_probe")
 }
+// One launch of k_remote_fold on caller-made arrays (oem_test_remote_fold, oem_testing.hip): every instantiation the
+// launchers and the overlap probe use, plus the 256-thread one with the non-temporal queue.
+int oem::launch_test_remote_fold(hipStream_t st, uint32_t n_buckets, const uint32_t *bucket_base, const double *queue,
+                                 const uint16_t *q_dst, double *cnt, const EmState *state, uint32_t n_groups, uint32_t n_txps, bool ntq,
+                                 uint32_t threads)
+{
+    using namespace oem;
+    const EmParams p0{0, 0, 0, 0.0};
+#define OEM_TEST_FOLD(NTQ, THREADS)                                                                                              \
+    hipLaunchKernelGGL((k_remote_fold<NTQ, THREADS>), dim3(n_buckets * n_groups), dim3(THREADS), 0, st, bucket_base, queue, q_dst, \
+                       cnt, state, n_groups, n_txps, (const BatchState *)nullptr, 0u, (unsigned long long *)nullptr,             \
+                       (EmState *)nullptr, p0, 0u)
+    if (threads == 1024 && !ntq) OEM_TEST_FOLD(false, 1024);
+    else if (threads == 1024) OEM_TEST_FOLD(true, 1024);
+    else if (threads == 256 && !ntq) OEM_TEST_FOLD(false, 256);
+    else if (threads == 256) OEM_TEST_FOLD(true, 256);
+    else return fail(OEM_ERR_ARG, "launch_test_remote_fold: %u threads (1024 or 256)", threads);
+#undef OEM_TEST_FOLD
+    OEM_HIP(hipGetLastError());
+    return OEM_OK;
+}
 #endif
